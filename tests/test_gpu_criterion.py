@@ -300,6 +300,24 @@ def test_ctc_tds_shape_full_size(oracle):
     assert xt.grad.double().sum(-1).abs().max().item() < 1e-5
 
 
+def test_ctc_gradient_repeats_bit_for_bit():
+    """the positions that share a gradient column (the blank at every even one, a label the target repeats) are added in a
+    fixed order: the same inputs give the same gradient bits on every call, so a training run repeats exactly"""
+    from wav2letter_amd import CTCLoss, CriterionScaleMode
+    rng = np.random.default_rng(5)
+    B, T, N, L = 32, 188, 9998, 80
+    x = dev(rng.normal(size=(B, T, N)).astype(np.float32))
+    tgt = dev(make_targets(rng, B, L, N, T, min_len=60, hi=40))    # 40 classes for 60 - 80 labels: every target repeats labels
+    crit = CTCLoss(CriterionScaleMode.TARGET_SZ_SQRT)
+    grads = []
+    for _ in range(3):
+        xt = x.clone().requires_grad_(True)
+        crit(xt, tgt).sum().backward()
+        grads.append(xt.grad)
+    assert torch.isfinite(grads[0]).all()
+    assert all(torch.equal(grads[0], g) for g in grads[1:])
+
+
 def test_error_behaviour_mirrors_flashlight():
     from wav2letter_amd import ASGLoss, CTCLoss
     from wav2letter_amd._lib import W2LInvalidArgument

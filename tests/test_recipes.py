@@ -1,66 +1,68 @@
 """The reference's recipes must load unchanged: every .arch file parses with the reference's
 own grammar/arity rules, every train .cfg parses as a gflags file, and the arch generators
-in wav2letter_amd.recipes reproduce the reference files line for line."""
-import glob
+in wav2letter_amd.recipes reproduce the reference files line for line.  The reference's .arch / .cfg files are stored in
+tests/golden/reference_recipes.json (tests/golden/make_recipe_fixtures.py), keyed by their path under recipes/."""
+import json
 import os
 
 import pytest
 
-REF = "/root/reference/recipes"
-need_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
+_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_recipes.json")
+_RECIPES = json.load(open(_FIXTURE))
+
+
+def _ref(rel):
+    """text of recipes/<rel> in the reference tree"""
+    return _RECIPES["arch" if rel.endswith(".arch") else "cfg"][rel]
 
 
 def _lines(text):
     return [l.strip() for l in text.splitlines() if l.strip() and not l.strip().startswith("#")]
 
 
-@need_ref
 def test_generators_reproduce_reference_arch_files():
     from wav2letter_amd import recipes
-    assert _lines(recipes.tds_ctc_arch()) == _lines(open(f"{REF}/sota/2019/am_arch/am_tds_ctc.arch").read())
-    assert _lines(recipes.conv_glu_librispeech_arch()) == _lines(open(f"{REF}/conv_glu/librispeech/network.arch").read())
-    assert _lines(recipes.conv_glu_wsj_arch()) == _lines(open(f"{REF}/conv_glu/wsj/network.arch").read())
+    assert _lines(recipes.tds_ctc_arch()) == _lines(_ref("sota/2019/am_arch/am_tds_ctc.arch"))
+    assert _lines(recipes.conv_glu_librispeech_arch()) == _lines(_ref("conv_glu/librispeech/network.arch"))
+    assert _lines(recipes.conv_glu_wsj_arch()) == _lines(_ref("conv_glu/wsj/network.arch"))
     assert _lines(recipes.streaming_tds_arch()) == _lines(
-        open(f"{REF}/streaming_convnets/librispeech/am_500ms_future_context.arch").read())
-    assert _lines(recipes.tds_ctc_librivox_arch()) == _lines(open(f"{REF}/sota/2019/am_arch/am_tds_ctc_librivox.arch").read())
-    assert _lines(recipes.transformer_ctc_arch()) == _lines(open(f"{REF}/sota/2019/am_arch/am_transformer_ctc.arch").read())
+        _ref("streaming_convnets/librispeech/am_500ms_future_context.arch"))
+    assert _lines(recipes.tds_ctc_librivox_arch()) == _lines(_ref("sota/2019/am_arch/am_tds_ctc_librivox.arch"))
+    assert _lines(recipes.transformer_ctc_arch()) == _lines(_ref("sota/2019/am_arch/am_transformer_ctc.arch"))
 
 
-@need_ref
 def test_generators_reproduce_reference_train_cfgs():
     """the flags files the `Train` binary is exercised with on the GPU box ARE the reference's (line for line)"""
     from wav2letter_amd import recipes
-    assert _lines(recipes.tds_ctc_train_cfg()) == _lines(open(f"{REF}/sota/2019/librispeech/train_am_tds_ctc.cfg").read())
-    assert _lines(recipes.conv_glu_train_cfg()) == _lines(open(f"{REF}/conv_glu/librispeech/train.cfg").read())
-    assert _lines(recipes.transformer_ctc_train_cfg()) == _lines(open(f"{REF}/sota/2019/librispeech/train_am_transformer_ctc.cfg").read())
+    assert _lines(recipes.tds_ctc_train_cfg()) == _lines(_ref("sota/2019/librispeech/train_am_tds_ctc.cfg"))
+    assert _lines(recipes.conv_glu_train_cfg()) == _lines(_ref("conv_glu/librispeech/train.cfg"))
+    assert _lines(recipes.transformer_ctc_train_cfg()) == _lines(_ref("sota/2019/librispeech/train_am_transformer_ctc.cfg"))
 
 
-@need_ref
 def test_all_reference_arch_files_parse():
     from wav2letter_amd.trainer import arch_check
-    files = sorted(glob.glob(f"{REF}/**/*.arch", recursive=True))
+    files = sorted(_RECIPES["arch"])
     assert len(files) >= 30
     from wav2letter_amd._lib import W2LInvalidArgument
     rejected = []
     for f in files:
         try:
-            n = arch_check(open(f).read(), 80, 9998)
+            n = arch_check(_ref(f), 80, 9998)
         except W2LInvalidArgument as e:
             assert "LN 3" in str(e), (f, e)
-            rejected.append(os.path.relpath(f, REF))
+            rejected.append(f)
             continue
-        assert n == len(_lines(open(f).read())), f
+        assert n == len(_lines(_ref(f))), f
     # the reference's own builder rejects exactly these two pre-migration files (SequentialBuilder.cpp:366-375)
     assert sorted(rejected) == ["self_training/librispeech/am/baseline.arch", "seq2seq_tds/librispeech/network.arch"]
 
 
-@need_ref
 def test_all_reference_train_cfgs_parse():
     from wav2letter_amd.trainer import flags_check
-    files = [f for f in glob.glob(f"{REF}/**/*.cfg", recursive=True)]
+    files = sorted(_RECIPES["cfg"])
     assert len(files) >= 100
     for f in files:
-        assert flags_check(open(f).read()) > 0, f
+        assert flags_check(_ref(f)) > 0, f
 
 
 def test_grammar_errors_match_reference_behaviour():

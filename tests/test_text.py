@@ -91,14 +91,15 @@ def test_asg_prediction_remap_with_replabels_and_surround():
 
 
 def test_generated_recipe_tokens_match_the_prepare_script():
-    """the token file recipes/conv_glu/librispeech/prepare.py writes (when the reference tree is present)"""
+    """the token file recipes/conv_glu/librispeech/prepare.py writes, and a lexicon line in its format, as stored in
+    tests/golden/reference_recipes.json (tests/golden/make_recipe_fixtures.py checks them against the script)"""
+    import json
     import os
-    p = "/root/reference/recipes/conv_glu/librispeech/prepare.py"
-    if not os.path.exists(p):
-        pytest.skip("reference tree not present")
-    src = open(p).read()
-    assert 'fout.write("|\\n")' in src and "fout.write(\"'\\n\")" in src and 'range(ord("a"), ord("z") + 1)' in src
-    assert '"{word}\\t{tokens} |\\n"' in src          # the lexicon line format load_lexicon parses
+    fixture = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_recipes.json")
+    prepare = json.load(open(fixture))["conv_glu_prepare"]
+    assert prepare["tokens"] == LETTERS
+    assert prepare["lexicon_line"] == "hello\th e l l o |\n"
+    assert text.load_lexicon([prepare["lexicon_line"]]) == {"hello": [["h", "e", "l", "l", "o", "|"]]}   # the format load_lexicon parses
 
 
 def test_cpp_header_mirror_compiles_and_agrees(tmp_path):

@@ -27,6 +27,11 @@
 namespace w2l {
 
 constexpr int kRowThreads = 256;
+// ws.link[b][k] (ctc_label_links_k): the next label position with the same label (kLinkNone: none), | kLinkLater when an earlier
+// position holds it too.  The entry points refuse L > kCtcMaxLabels, so a position fits below kLinkNone.
+constexpr int kCtcMaxLabels = 1023;
+constexpr int kLinkNone = 0xFFFF, kLinkLater = 1 << 16;
+static_assert(2 * kCtcMaxLabels + 1 <= 64 * 32 && kCtcMaxLabels < kLinkNone, "label positions: lattice rows and link fields");
 constexpr int kRowMaxPer = 48;  // register-resident row: N <= 256*48 = 12288
 
 struct CtcWs {
@@ -41,6 +46,7 @@ struct CtcWs {
   int* ez;        // [B]
   float* scale;   // [B]
   float* nll;     // [B]  (-log likelihood, unscaled)
+  int* link;      // [B][L] repeated-label links of the targets (ctc_label_links_k, backward only)
   int S;          // row stride of the per-position arrays: 64 * P >= 2 L + 1
   int P;          // lattice positions per lane of the scans
 };
@@ -67,7 +73,8 @@ __host__ __device__ inline CtcWs ctc_ws(void* ws, int B, int T, int N, int L) {
   w.zhat = (double*)p; p += align_up((size_t)B * sizeof(double), 256);
   w.ez = (int*)p; p += align_up((size_t)B * sizeof(int), 256);
   w.scale = (float*)p; p += align_up((size_t)B * sizeof(float), 256);
-  w.nll = (float*)p;
+  w.nll = (float*)p; p += align_up((size_t)B * sizeof(float), 256);
+  w.link = (int*)p;
   return w;
 }
 
@@ -447,6 +454,22 @@ __global__ __launch_bounds__(64) void ctc_scan(int T, int N, int L, int scaleMod
   else ctc_scan_body<P, D, false>(T, N, L, scaleMode, target, targetSize, loss, ws);
 }
 
+// link[b][k] for k < L_b: the next position with the same label (kLinkNone: none), | kLinkLater when an earlier position holds
+// it.  One workgroup per utterance, once per backward call: the O(L^2) comparison is not repeated for every frame.
+__global__ __launch_bounds__(kRowThreads) void ctc_label_links_k(int L, const int* __restrict__ target,
+                                                                 const int* __restrict__ targetSize, int* __restrict__ link) {
+  const int b = blockIdx.x;
+  const int Lb = targetSize[b];
+  const int* y = target + (size_t)b * L;
+  for (int k = threadIdx.x; k < Lb; k += kRowThreads) {
+    const int lab = y[k];
+    int next = kLinkNone, later = 0;
+    for (int j = Lb - 1; j > k; --j) next = y[j] == lab ? j : next;
+    for (int j = 0; j < k; ++j) later |= y[j] == lab;
+    link[(size_t)b * L + k] = next | (later ? kLinkLater : 0);
+  }
+}
+
 // grad row = g * softmax(x); then subtract g * gamma at the frame's labels
 __global__ __launch_bounds__(kRowThreads) void ctc_rows_grad(int T, int N, int L,
                                                              const float* __restrict__ x,
@@ -526,16 +549,58 @@ __global__ __launch_bounds__(kRowThreads) void ctc_rows_grad(int T, int N, int L
   const int* ear = ws.eA + r * ws.S;
   const int* ebr = ws.eB + r * ws.S;
   const double zh = ws.zhat[b];
-  if (zh > 0.0) {   // an infeasible target (Z = 0) has no occupancy: its loss is +inf, its gradient g * softmax
+  if (zh > 0.0) {   // an infeasible target (Z = 0) has no occupancy: its loss is +inf, its gradient g * softmax (zh: row-uniform)
     const int ez = ws.ez[b];
-    for (int si = tid; si < S; si += kRowThreads) {
-      const int lab = (si & 1) ? y[si >> 1] : (N - 1);
+    auto occ = [&](int si) -> float {
       const double av = alr[si], bv = ber[si];
-      if (av > 0.0 && bv > 0.0) {
-        const double pv = pdr[si];
-        const float v = (float)ldexp(av * bv / (pv * zh), ear[si] + ebr[si] - ez);
-        if (v != 0.f) atomicAdd(&out[lab], -g * v);
+      if (!(av > 0.0 && bv > 0.0)) return 0.f;
+      return (float)ldexp(av * bv / (pdr[si] * zh), ear[si] + ebr[si] - ez);
+    };
+    // Several positions share a column (every even one the blank's, a repeated label its own): they are added in a FIXED
+    // order, not by atomics, so that the gradient -- and the training run it drives -- repeats bit for bit.  Blank: per-thread
+    // sums in ascending position, a fixed-shape wave tree, the waves in index order.  Label: the thread of its first
+    // position adds all of its positions in ascending order; the others skip it.
+    // Every position's occupancy is formed in parallel; the label positions' values and their links (ctc_label_links_k, per
+    // utterance) go to LDS, where the thread of a label's first position then walks its chain: O(L) per row.
+    __shared__ float lv[kCtcMaxLabels];
+    __shared__ int ll[kCtcMaxLabels];
+    const int* lnk = ws.link + (size_t)b * L;
+    float blank = 0.f;
+    for (int si = tid; si < S; si += kRowThreads) {
+      const int k = si >> 1;
+      const int lab = (si & 1) ? y[k] : (N - 1);
+      const float v = occ(si);
+      if (lab == N - 1) {
+        if (v != 0.f) blank += -g * v;
+        continue;
       }
+      lv[k] = v;
+      ll[k] = lnk[k];
+    }
+    __syncthreads();
+    for (int k = tid; k < Lb; k += kRowThreads) {
+      int lk = ll[k];
+      const int lab = y[k];
+      if ((lk & kLinkLater) || lab == N - 1) continue;
+      float acc = out[lab];
+      for (int j = k;;) {
+        const float v = lv[j];
+        if (v != 0.f) acc += -g * v;
+        if ((lk & kLinkNone) == kLinkNone) break;
+        j = lk & kLinkNone;
+        lk = ll[j];
+      }
+      out[lab] = acc;
+    }
+    __shared__ float smb[kRowThreads / 64];
+    blank = wave_sum(blank);
+    if ((tid & 63) == 0) smb[tid >> 6] = blank;
+    __syncthreads();
+    if (tid == 0) {
+      float s = smb[0];
+#pragma unroll
+      for (int w = 1; w < kRowThreads / 64; ++w) s += smb[w];
+      out[N - 1] += s;
     }
   }
 }
@@ -620,7 +685,8 @@ W2L_API size_t w2l_ctc_workspace_size(int B, int T, int N, int L) {
   size_t S = 64 * (size_t)ctc_positions_per_lane(L);
   return align_up((size_t)B * T * sizeof(float), 256) +
          3 * align_up((size_t)B * T * S * sizeof(double), 256) + 2 * align_up((size_t)B * T * S * sizeof(int), 256) +
-         align_up((size_t)B * sizeof(double), 256) + align_up((size_t)B * sizeof(int), 256) + 2 * align_up((size_t)B * sizeof(float), 256);
+         align_up((size_t)B * sizeof(double), 256) + align_up((size_t)B * sizeof(int), 256) + 2 * align_up((size_t)B * sizeof(float), 256) +
+         align_up((size_t)B * L * sizeof(int), 256);
 }
 
 W2L_API int w2l_ctc_forward(int B, int T, int N, int L, int scaleMode, const float* input,
@@ -628,7 +694,7 @@ W2L_API int w2l_ctc_forward(int B, int T, int N, int L, int scaleMode, const flo
                             void* workspace, w2l_stream_t stream) {
   if (B <= 0 || T <= 0 || N <= 1 || L <= 0 || !input || !target || !targetSize || !loss || !workspace)
     return W2L_EINVAL;
-  if (2 * L + 1 > 64 * 32) return W2L_EUNSUPPORTED;   // L <= 1023 label positions per utterance (32 per lane)
+  if (L > kCtcMaxLabels) return W2L_EUNSUPPORTED;   // L <= 1023 label positions per utterance (2 L + 1 <= 32 per lane)
   hipStream_t s = (hipStream_t)stream;
   CtcWs ws = ctc_ws(workspace, B, T, N, L);
   const unsigned rows = (unsigned)((size_t)B * T);
@@ -665,9 +731,12 @@ W2L_API int w2l_ctc_backward(int B, int T, int N, int L, const float* input, con
                              void* workspace, w2l_stream_t stream) {
   if (B <= 0 || T <= 0 || N <= 1 || L <= 0 || !input || !target || !targetSize || !grad || !inputGrad || !workspace)
     return W2L_EINVAL;
+  if (L > kCtcMaxLabels) return W2L_EUNSUPPORTED;   // as the forward (and the LDS arrays of ctc_rows_grad)
   hipStream_t s = (hipStream_t)stream;
   CtcWs ws = ctc_ws(workspace, B, T, N, L);
   const unsigned rows = (unsigned)((size_t)B * T);
+  hipLaunchKernelGGL(ctc_label_links_k, dim3((unsigned)B), dim3(kRowThreads), 0, s, L, target, targetSize, ws.link);
+  W2L_LAUNCH_CHECK();
   hipLaunchKernelGGL(ctc_rows_grad, dim3(rows), dim3(kRowThreads), 0, s, T, N, L, input, target, targetSize, grad, inputGrad, ws);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
