@@ -110,38 +110,45 @@ class TDSParams:
         self.g2 = np.float32(1.0 + 0.1 * rng.normal()); self.b2n = np.float32(0.1 * rng.normal())
 
 
-def tds_fwd(x, p, padl, padr, ln_mode="all", streaming=False, eps=1e-5, keep=False, bf16=False):
-    """bf16: the operands of the block's convolution and of its two Linear layers are rounded to bf16 (fl's AMP casts the
-    operands of conv2d and linear: recipes/slimIPL/src/Train.cpp:211, :1681-1760); accumulation, bias, ReLU, LayerNorm, fp32"""
+def tds_fwd(x, p, padl, padr, ln_mode="all", streaming=False, eps=1e-5, keep=False, bf16=False, masks=None):
+    """bf16: the operands of the block's two Linear layers are rounded to bf16, and those of its convolution where the
+    mixed-precision mode has bf16 kernels for it (conv_rounds_to_bf16; fl's AMP casts the operands of conv2d and linear:
+    recipes/slimIPL/src/Train.cpp:211, :1681-1760); accumulation, bias, ReLU, LayerNorm, fp32.
+    masks: the block's three dropout masks (values 0 or 1 / (1 - p)), or None for no dropout --
+    (after conv + ReLU [B][C][H][T], after lin1 + ReLU [B*T][l2], on lin2's output before the residual join [B][C][H][T])"""
     B, Cc, H, T = x.shape
-    a = O.conv_fwd(bf16_round(x), bf16_round(p.wc), p.bc, 1, padl, padr) if bf16 else O.conv_fwd(x, p.wc, p.bc, 1, padl, padr)
-    r = relu(a) + x
+    m1, m2, m3 = masks if masks is not None else (1.0, 1.0, 1.0)
+    rc = bf16 and conv_rounds_to_bf16(Cc, Cc, p.kw, 1, H)
+    a = O.conv_fwd(bf16_round(x), bf16_round(p.wc), p.bc, 1, padl, padr) if rc else O.conv_fwd(x, p.wc, p.bc, 1, padl, padr)
+    r = relu(a) * m1 + x
     y = ln_fwd(r, ln_mode, float(p.g1), float(p.b1n), eps, streaming)
     z = to_frames(y)
     u = lin_fwd(z, p.w1, p.b1, bf16)
-    v = lin_fwd(relu(u), p.w2, p.b2, bf16)
-    s = from_frames(v, B, Cc, H, T) + y
+    v = lin_fwd(relu(u) * m2, p.w2, p.b2, bf16)
+    s = from_frames(v, B, Cc, H, T) * m3 + y
     out = ln_fwd(s, ln_mode, float(p.g2), float(p.b2n), eps, streaming)
     if keep:
-        return out, dict(x=x, a=a, r=r, y=y, z=z, u=u, s=s)
+        return out, dict(x=x, a=a, r=r, y=y, z=z, u=u, s=s, masks=(m1, m2, m3))
     return out
 
 
 def tds_bwd(dout, p, saved, padl, padr, ln_mode="all", eps=1e-5, bf16=False):
-    """returns dx and a dict of parameter grads"""
+    """returns dx and a dict of parameter grads (the dropout masks are those tds_fwd kept)"""
     x, a, r, y, z, u, s = (saved[k] for k in "x a r y z u s".split())
+    m1, m2, m3 = saved.get("masks", (1.0, 1.0, 1.0))
     B, Cc, H, T = x.shape
     g = {}
     ds, g["g2"], g["b2n"] = ln_bwd(s, dout, ln_mode, float(p.g2), eps)
     dy = ds.copy()
-    dv = to_frames(ds)
-    dru, g["w2"], g["b2"] = lin_bwd(relu(u), p.w2, dv, bf16)
-    du = dru * (u > 0)
-    dz, g["w1"], g["b1"] = lin_bwd(z, p.w1, du, bf16)
+    dv = to_frames(ds * m3)
+    dru, g["w2"], g["b2"] = lin_bwd(np.ascontiguousarray(relu(u) * m2, np.float32), p.w2, np.ascontiguousarray(dv, np.float32), bf16)
+    du = dru * (u > 0) * m2
+    dz, g["w1"], g["b1"] = lin_bwd(z, p.w1, np.ascontiguousarray(du, np.float32), bf16)
     dy += from_frames(dz, B, Cc, H, T)
     dr, g["g1"], g["b1n"] = ln_bwd(r, dy, ln_mode, float(p.g1), eps)
-    da = dr * (a > 0)
-    if bf16:   # dx = conv^T(bf(da), bf(w)), dw = bf(x) (*) bf(da), db = sums of bf(da) (summed from the slabs of the filter-gradient kernel)
+    da = np.ascontiguousarray(dr * (a > 0) * m1, np.float32)
+    if bf16 and conv_rounds_to_bf16(Cc, Cc, p.kw, 1, H):
+        # dx = conv^T(bf(da), bf(w)), dw = bf(x) (*) bf(da), db = sums of bf(da) (summed from the slabs of the filter-gradient kernel)
         dxc, g["wc"], dbr = O.conv_bwd(bf16_round(x), bf16_round(p.wc), bf16_round(da), 1, padl, padr)
         g["bc"] = dbr
     else:
@@ -157,8 +164,9 @@ def tds_bwd(dout, p, saved, padl, padr, ln_mode="all", eps=1e-5, bf16=False):
 #   WeightNorm: v (as the wrapped weight), g [nout], (bias)
 class RefNet:
     def __init__(self, arch_text, nfeat, nlabel, bf16=False):
-        """bf16: every fl::Linear (stand-alone `L` lines and the two inside a TDS block) multiplies bf16-rounded operands
-        -- the reference side of the mixed-precision parity tests (BASELINE config 3)"""
+        """bf16: every fl::Linear (stand-alone `L` lines and the two inside a TDS block) multiplies bf16-rounded operands, and
+        every convolution the library has bf16 kernels for (conv_rounds_to_bf16) -- the reference side of the mixed-precision
+        parity tests (BASELINE config 3)"""
         self.bf16 = bf16
         self.lines = []
         for raw in arch_text.splitlines():
@@ -335,7 +343,10 @@ class RefNet:
                 a = O.glu_fwd(a, outer, half, inner).reshape(shp)
             elif t[0] == "TDS":
                 c, kw, h = int(t[1]), int(t[2]), int(t[3])
-                assert (len(t) <= 4 or float(t[4]) == 0.0)
+                # training-mode dropout masks are supplied by the caller: self.tds_masks = [(m1, m2, m3), ...] per block (tds_fwd)
+                masks = getattr(self, "tds_masks", None)
+                mk = masks[sum(1 for r in self.tape if r[0] == "TDS")] if masks else None
+                assert mk is not None or len(t) <= 4 or float(t[4]) == 0.0, "dropout needs the caller's masks"
                 l = c * h
                 l2 = int(t[5]) if len(t) > 5 and int(t[5]) else l
                 p = TDSParams(c, kw, h, l2)
@@ -350,7 +361,7 @@ class RefNet:
                 else:
                     pr, pl = rpad, kw - 1 - rpad
                 mode = "frame" if (len(t) > 7 and int(t[7]) == 0) else "all"
-                out, saved = tds_fwd(a, p, pl, pr, mode, keep=True, bf16=self.bf16)
+                out, saved = tds_fwd(a, p, pl, pr, mode, keep=True, bf16=self.bf16, masks=mk)
                 self.tape.append(("TDS", p, saved, pl, pr, mode, pi))
                 a = out
             elif t[0] == "M":

@@ -1562,3 +1562,185 @@ def test_linseg_phase_has_its_own_momentum():
     want = p0[:n].double() - 0.05 * gs
     assert (tr.params[:n].double() - want).abs().max().item() < 1e-6 * max(1.0, want.abs().max().item())
     assert (tr.mom[:n].double() - gs).abs().max().item() < 1e-6 * max(1.0, gs.abs().max().item())
+
+
+# ---- the mixed-precision TDS block across geometries ------------------------------------------------------------------------
+# One block alone (the `V / TDS / RO / V / V` network of teacher_forced_tds_blocks), random input and output gradient, each case
+# at a geometry meant to reach one branch of TDSLayer's choice between the bf16 operators (host/net.cpp; launch128h's refusal
+# conditions in gemm_bf16g.hpp).  Line: TDS c kw h dropout l2 rPad lnIncludeTime.
+TDS_BF16_CASES = [
+    # config 2's block (sota TDS-CTC), reduced B / T: time-wise LayerNorm, so y1's rows are not the LayerNorm's groups -- no LN
+    # images, y1 joins the weights' w2l_bf16_convert_multi and gets its ones row from ensureOnes; c = 10, kw = 21 at 80 rows:
+    # bf16 convolution kernels
+    pytest.param("TDS 10 21 80 0.0 0 -1 1", 2, 24, id="sota-c2-timewise-ln"),
+    # wide hidden layer with l2 % 32 != 0 (l2 % 4 == 0): lin1's image-writing epilogue at an N that is not a tile multiple
+    # (M = 128 rows: at 32 a single one-sided bf16 rounding of du moves lin1's weight gradient by 2.4e-3 of its largest value)
+    pytest.param("TDS 14 21 80 0.0 1000", 2, 64, id="wide-l2-1000"),
+    # per-frame LayerNorm with 2400-float rows (> 2304): the LayerNorm-images kernels refuse -> plain LayerNorm + conversion;
+    # right padding 1; c = 30 at kw = 11 still has bf16 convolution kernels
+    pytest.param("TDS 30 11 80 0.0 0 1 0", 2, 16, id="frame-ln-row-2400"),
+    # h = 10 (not a multiple of 16): convImgElems == 0, the convolution stays fp32 (the oracle must not round it either)
+    pytest.param("TDS 8 9 10 0.0 0 -1 1", 2, 20, id="conv-fp32-h10"),
+    # c = 40 > 32 at h = 16: convImgElems == 0 as well
+    pytest.param("TDS 40 5 16 0.0 0", 2, 16, id="conv-fp32-c40"),
+    # l = 15 (l % 4 != 0), l2 = 16: lin1 writes u as images only (uOnlyImages); y1's images, the backward-data product of lin1 and
+    # the fp32 du all have rows of 15; h = 3 keeps the convolution fp32
+    pytest.param("TDS 5 3 3 0.0 16", 2, 16, id="l15-l2-16"),
+    # l2 = 30 (l2 % 4 != 0): lin1's image epilogue refuses -> fp32 u + conversion; lin2's backward-data with the fp32 mask
+    pytest.param("TDS 8 9 16 0.0 30", 2, 16, id="l2-30-fp32-u"),
+    # B = 3, T = 37: M = 111 rows, partial GEMM / convolution tiles everywhere
+    pytest.param("TDS 8 9 16 0.0 0", 3, 37, id="ragged-M-111"),
+    # dropout 0.2 in config 2's block: lin1's dropout epilogue into the images; time-wise LayerNorm -> dv's images by
+    # convertDropout (maskInConvert: the bias gradient rides on the weight-gradient product)
+    pytest.param("TDS 10 21 80 0.2 0 -1 1", 2, 24, id="sota-c2-dropout"),
+    # dropout 0.2 in config 3's per-frame block: dropout inside the LayerNorm-images kernels (forward and backward)
+    pytest.param("TDS 15 9 80 0.2 0 1 0", 2, 16, id="c3-frame-dropout"),
+]
+
+
+def _tds_block_run(one, l, B, T, params, feed, dout, mp, step):
+    tr, table = _one_block_trainer(one, l, l, B, T, params)
+    tr.set_mixed_precision(mp)
+    tr.set_step(step)
+    em = tr.forward(torch.tensor(feed).cuda(), train=True).cpu().numpy().copy()
+    tr.backward(torch.tensor(dout).cuda())
+    g = tr.grads.cpu().numpy()
+    grads = [tr.export_from(i, g).copy() for i in range(8)]
+    del tr
+    return em, grads, table
+
+
+@pytest.mark.parametrize("line, B, T", TDS_BF16_CASES)
+def test_tds_block_bf16_geometries_against_bf16_operand_oracle(oracle, line, B, T):
+    """one mixed-precision TDS block, training mode, against refnet.tds_fwd / tds_bwd(bf16=True) with the library's own dropout
+    masks (seed of the step, host/trainer.cpp; streams rngStream, + 1, + 2 of the block's layer, Sequential::finalize): output
+    and EVERY parameter gradient at 2e-3 of the largest magnitude (LayerNorm (gain, bias) pairs 2e-2), as the config 3
+    one-block test.  The bf16 path must have run (the output differs from the fp32 run of the same block), and without dropout
+    the bar must tell the rounded oracle from the unrounded one (error against the first at most half that against the second)"""
+    from oracle import pyoracle
+    t = line.split()
+    c, kw, h = int(t[1]), int(t[2]), int(t[3])
+    pdrop = float(t[4])
+    l = c * h
+    l2 = int(t[5]) if len(t) > 5 and int(t[5]) else l
+    rpad = int(t[6]) if len(t) > 6 else -1
+    mode = "frame" if len(t) > 7 and int(t[7]) == 0 else "all"
+    pl, pr = (pyoracle.same_pad(T, kw, 1),) * 2 if rpad < 0 else (kw - 1 - rpad, rpad)
+    rng = np.random.default_rng(sum(line.encode()) + B * 100 + T)
+    p = refnet.TDSParams(c, kw, h, l2, rng=rng)
+    params = [p.wc, p.bc, np.array([p.g1, p.b1n], np.float32), p.w1, p.b1, p.w2, p.b2, np.array([p.g2, p.b2n], np.float32)]
+    x = rng.normal(size=(B, c, h, T)).astype(np.float32)
+    dout = rng.normal(size=(B, c, h, T)).astype(np.float32)
+    step = 3
+    masks = None
+    if pdrop > 0:
+        seed = (0x9E3779B9 * (step + 1)) & 0xFFFFFFFF    # host/trainer.cpp makeCtx: the step's dropout seed
+        stream = 1 + 4 * 2                                # layer 2 of the Sequential (V, RO, TDS, ...): rngStream
+        n = B * c * h * T
+        draw = lambda k, size: pyoracle.dropout(np.ones(size, np.float32), pdrop, seed, stream + k)
+        masks = (refnet.from_frames(draw(0, n).reshape(B * T, l), B, c, h, T), draw(1, B * T * l2).reshape(B * T, l2),
+                 refnet.from_frames(draw(2, n).reshape(B * T, l), B, c, h, T))
+    want = {}
+    for bf in (True, False):
+        out, saved = refnet.tds_fwd(x, p, pl, pr, mode, keep=True, bf16=bf, masks=masks)
+        dx, g = refnet.tds_bwd(dout, p, saved, pl, pr, mode, bf16=bf)
+        want[bf] = (out, [g["wc"], g["bc"], np.array([g["g1"], g["b1n"]]), g["w1"], g["b1"], g["w2"], g["b2"], np.array([g["g2"], g["b2n"]])])
+    one = "V -1 %d %d 0\nRO 0 2 1 3\n%s\nRO 2 1 0 3\nV %d -1 1 0\nV %d 0 -1 1\n" % (c, h, line, l, l)
+    to_em = lambda a: np.ascontiguousarray(a.transpose(0, 3, 2, 1)).reshape(B, T, l)   # [B][c][h][T] -> [B][T][h * C + c]
+    feed = np.ascontiguousarray(x.transpose(0, 2, 1, 3)).reshape(B, l, T)              # [B][h * C + c][T]
+    em16, g16, table = _tds_block_run(one, l, B, T, params, feed, to_em(dout), True, step)
+    em32, g32, _ = _tds_block_run(one, l, B, T, params, feed, to_em(dout), False, step)
+    err = {bf: [rel(em16, to_em(want[bf][0]))] + [rel(g16[i], want[bf][1][i]) for i in range(8)] for bf in (True, False)}
+    big = [True] + [np.asarray(w).size > 2 for w in want[True][1]]
+    worst = {bf: max(e for e, b in zip(err[bf], big) if b) for bf in (True, False)}
+    d32 = rel(em16, em32)
+    print("\n%s B=%d T=%d: worst error vs bf16-operand oracle %.2e, vs unrounded oracle %.2e; output vs fp32 run %.2e"
+          % (line, B, T, worst[True], worst[False], d32))
+    for i, (e, b) in enumerate(zip(err[True], big)):
+        assert e < (2e-3 if b else 2e-2), (line, "output" if i == 0 else table[i - 1][0], e)
+    assert d32 > 1e-4, d32                           # the bf16 kernels ran
+    assert max(rel(a, b) for a, b in zip(g16, g32)) > 1e-4
+    if pdrop == 0:
+        assert worst[True] <= 0.5 * worst[False], (worst[True], worst[False])
+
+
+# ---- the mixed-precision Transformer block across geometries ----------------------------------------------------------------
+TR_BF16_CASES = [
+    # mlp = 70 (% 4 != 0): lin1's image epilogue refuses -> fp32 u + conversion (TransformerLayer's uOnlyImages false)
+    pytest.param("TR 64 70 4 8", 2, 40, None, id="mlp70"),
+    # mlp = 100 (% 4 == 0, % 32 != 0): the image epilogue at a non-tile-multiple N
+    pytest.param("TR 64 100 4 8", 2, 40, None, id="mlp100"),
+    # csz = 0: no position table
+    pytest.param("TR 64 128 4 0", 2, 40, None, id="csz0"),
+    # head size 32, T <= 192: the fused attention kernels
+    pytest.param("TR 128 256 4 10", 2, 150, None, id="head32-fused-T150"),
+    # head size 32, T > 192: the unfused bf16 attention at a head size that otherwise fuses
+    pytest.param("TR 128 256 4 10", 2, 200, None, id="head32-unfused-T200"),
+    # B = 3 with input sizes: the padded keys are masked (key lengths 48, 40, 29 frames)
+    pytest.param("TR 64 128 4 8", 3, 48, [4800.0, 4000.0, 2900.0], id="padded-B3"),
+]
+
+
+@pytest.mark.parametrize("line, B, T, sizes", TR_BF16_CASES)
+def test_transformer_block_bf16_geometries(oracle, line, B, T, sizes):
+    """one mixed-precision TR block between a View and the output Linear, against the float64 restatement at the bars of
+    test_transformer_block_at_config5_width_bf16 (emissions and loss 1e-2 of the largest magnitude; every parameter gradient
+    cosine > 0.995, relative L2 < 8 %), and against the fp32 step of the same network: emissions and loss within 2e-2 of the
+    largest magnitude, gradients at the same direction-and-size bars (as test_mixed_precision_streaming_tds_step: a gradient's
+    largest element moves by up to ~10 % between the two modes at these sizes)"""
+    from wav2letter_amd.trainer import Trainer
+    C = int(line.split()[1])
+    nfeat, nlabel, L = C, 12, 4
+    arch = "V -1 1 NFEAT 0\nRO 2 0 3 1\n%s 0.0 0.0\nL %d NLABEL\n" % (line, C)
+    rng = np.random.default_rng(B * 1000 + T + C)
+    ref = refnet.RefNet(arch, nfeat, nlabel)
+    params = ref.random_params(rng)
+    x = rng.normal(size=(B, 1, nfeat, T)).astype(np.float32)
+    tgt = rng.integers(0, nlabel - 1, size=(B, L)).astype(np.int32)
+    xd = torch.tensor(x.reshape(B, nfeat, T)).cuda()
+    td = torch.tensor(tgt).cuda()
+    if sizes is not None:
+        ref.input_sizes = np.array(sizes, np.float32)
+        assert rel(ref.forward(x, params), refnet.RefNet(arch, nfeat, nlabel).forward(x, params)) > 1e-2   # the mask matters
+    em_ref = ref.forward(x, params)
+    o = oracle.CTC(em_ref, tgt, scale_mode=4)
+    loss_ref = o.forward()
+    want = ref.backward(o.backward().astype(np.float32), len(params))
+    runs = {}
+    for mp in (False, True):
+        tr = Trainer(arch, nfeat, nlabel, "ctc", 4, 0.0)
+        for i, p in enumerate(params):
+            tr.import_param(i, p)
+        tr.plan(B, T, L)
+        tr.to_device()
+        tr.set_mixed_precision(mp)
+        if sizes is not None:
+            szd = torch.tensor(np.array(sizes, np.float32)).cuda()
+            tr.set_input_sizes(szd)
+        em = tr.forward(xd, train=False).cpu().numpy().copy()
+        loss = tr.forward_backward(xd, td).cpu().numpy().copy()
+        g = tr.grads.cpu().numpy()
+        runs[mp] = (em, loss, [tr.export_from(i, g).copy() for i in range(len(params))], tr.param_table())
+        del tr
+    em, loss, g16, table = runs[True]
+    em32, loss32, g32, _ = runs[False]
+    worst_cos, worst_l2 = 1.0, 0.0
+    print("\n%s B=%d T=%d: emissions vs float64 %.2e, vs fp32 step %.2e" % (line, B, T, rel(em, em_ref), rel(em, em32)))
+    assert rel(em, em_ref) < 1e-2 and rel(loss, loss_ref) < 1e-2, (rel(em, em_ref), rel(loss, loss_ref))
+    assert rel(em, em32) < 2e-2 and rel(loss, loss32) < 2e-2, (rel(em, em32), rel(loss, loss32))
+    assert not np.array_equal(em, em32)           # the bf16 kernels ran
+    bad = []
+    for i, (name, _n, _off) in enumerate(table):
+        if name == "tr.wk.b":   # exactly zero in exact arithmetic
+            continue
+        got = g16[i].astype(np.float64).reshape(-1)
+        w = np.asarray(want[i], np.float64).reshape(-1)
+        cos = float(got @ w / (np.linalg.norm(got) * np.linalg.norm(w) + 1e-300))
+        l2 = float(np.linalg.norm(got - w) / (np.linalg.norm(w) + 1e-300))
+        b = g32[i].astype(np.float64).reshape(-1)
+        cos32 = float(got @ b / (np.linalg.norm(got) * np.linalg.norm(b) + 1e-300))
+        l2_32 = float(np.linalg.norm(got - b) / (np.linalg.norm(b) + 1e-300))
+        worst_cos, worst_l2 = min(worst_cos, cos, cos32), max(worst_l2, l2, l2_32)
+        bad += [(name, cos, l2, cos32, l2_32)] if not (min(cos, cos32) > 0.995 and max(l2, l2_32) < 0.08) else []
+    print("  gradients vs float64 and fp32 step: worst cosine %.5f, relative L2 %.2e" % (worst_cos, worst_l2))
+    assert not bad, bad

@@ -150,15 +150,42 @@ def test_glu_weightnorm_vs_torch(oracle):
     assert np.allclose(w, v * (g / np.linalg.norm(v.astype(np.float64), axis=0)), atol=1e-6)
 
 
+def tds_dropout_masks(oracle, B, Cc, H, T, l2, p, seed, stream):
+    """the TDS block's three dropout masks as the library draws them (net.cpp TDSLayer): the layer's rngStream for the
+    convolution's output, + 1 for lin1's, + 2 for lin2's; each hashed over the flat index of its tensor in the library's
+    frame-major layout [B][T][H][C] ([B*T][l2] for lin1's output) -- returned in the restatement's layouts"""
+    n = B * Cc * H * T
+    m1 = refnet.from_frames(oracle.dropout(np.ones(n, np.float32), p, seed, stream).reshape(B * T, H * Cc), B, Cc, H, T)
+    m2 = oracle.dropout(np.ones(B * T * l2, np.float32), p, seed, stream + 1).reshape(B * T, l2)
+    m3 = refnet.from_frames(oracle.dropout(np.ones(n, np.float32), p, seed, stream + 2).reshape(B * T, H * Cc), B, Cc, H, T)
+    return m1, m2, m3
+
+
 @pytest.mark.parametrize("ln_mode", ["all", "frame"])
 def test_tds_block_backward_vs_torch(oracle, ln_mode):
+    _tds_block_vs_torch(oracle, ln_mode, masked=False)
+
+
+@pytest.mark.parametrize("ln_mode", ["all", "frame"])
+def test_tds_block_backward_vs_torch_masked(oracle, ln_mode):
+    """training-mode dropout (p = 0.3) with the caller's three masks -- after conv + ReLU, after lin1 + ReLU, on lin2's output
+    before the residual join -- in the masks' own streams (rngStream, + 1, + 2) and flat orders"""
+    _tds_block_vs_torch(oracle, ln_mode, masked=True)
+
+
+def _tds_block_vs_torch(oracle, ln_mode, masked):
     rng = np.random.default_rng(4)
     B, Cc, H, T, kw = 2, 3, 4, 9, 5
     p = refnet.TDSParams(Cc, kw, H, l2=20, rng=rng)
     x = rng.normal(size=(B, Cc, H, T)).astype(np.float32)
     dout = rng.normal(size=x.shape).astype(np.float32)
-    out, saved = refnet.tds_fwd(x, p, 2, 2, ln_mode, keep=True)
+    masks = tds_dropout_masks(oracle, B, Cc, H, T, 20, 0.3, 0x9E3779B9, 9) if masked else None
+    if masked:
+        for m in masks:
+            assert 0.15 < (m == 0).mean() < 0.45 and np.allclose(m[m != 0], 1 / 0.7)
+    out, saved = refnet.tds_fwd(x, p, 2, 2, ln_mode, keep=True, masks=masks)
     dx, g = refnet.tds_bwd(dout, p, saved, 2, 2, ln_mode)
+    m1, m2, m3 = (torch.tensor(m, dtype=torch.float64) for m in masks) if masked else (1.0, 1.0, 1.0)
 
     td = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64, requires_grad=True)
     xt, wc, bc, w1, b1, w2, b2 = map(td, (x, p.wc, p.bc, p.w1, p.b1, p.w2, p.b2))
@@ -171,10 +198,10 @@ def test_tds_block_backward_vs_torch(oracle, ln_mode):
         return (v - mu) / torch.sqrt(var + 1e-5) * gam + bet
 
     a = F.conv2d(F.pad(xt, (2, 2)), wc[:, :, None, :], bc)
-    y = ln(torch.relu(a) + xt, g1, b1n)
+    y = ln(torch.relu(a) * m1 + xt, g1, b1n)
     z = y.permute(0, 3, 2, 1).reshape(B * T, H * Cc)
-    v = torch.relu(z @ w1 + b1) @ w2 + b2
-    s = v.reshape(B, T, H, Cc).permute(0, 3, 2, 1) + y
+    v = (torch.relu(z @ w1 + b1) * m2) @ w2 + b2
+    s = v.reshape(B, T, H, Cc).permute(0, 3, 2, 1) * m3 + y
     ot = ln(s, g2, b2n)
     assert np.allclose(out, ot.detach().numpy(), atol=1e-4)
     ot.backward(torch.tensor(dout, dtype=torch.float64))
@@ -488,3 +515,39 @@ def test_oracle_and_library_agree_on_which_convolutions_multiply_in_bf16():
     for cin, cout, kw, stride in ((1, 15, 10, 2), (15, 19, 10, 2), (19, 23, 12, 2), (23, 27, 11, 1), (15, 15, 9, 1), (27, 27, 11, 1),
                                   (1, 10, 21, 2), (10, 14, 21, 2), (14, 18, 21, 2), (18, 18, 21, 1)):
         assert refnet.conv_rounds_to_bf16(cin, cout, kw, stride, 80), (cin, cout, kw, stride)
+
+
+def test_oracle_and_library_agree_on_which_tds_block_convolutions_multiply_in_bf16(oracle):
+    """the TDS block's own convolution (stride 1, cin == cout, SAME or right-padded) is multiplied in bf16 by the library exactly
+    when w2l_tds_conv_bf16_image_elems != 0 (TDSLayer::convImgElems; host logic, no GPU needed) -- refnet.tds_fwd / tds_bwd(bf16)
+    must round its operands by the same rule, and leave them unrounded everywhere else (mel rows h % 16 != 0, c > 32, kernel
+    widths without a bf16 kernel)"""
+    import ctypes as C
+    from wav2letter_amd import _lib
+    L = _lib.lib()
+    n = yes = 0
+    for h in (3, 10, 16, 80):
+        for kw in (3, 5, 9, 11, 15, 21, 33):
+            for c in (1, 5, 8, 10, 14, 15, 16, 19, 23, 24, 27, 30, 32, 33, 40):
+                for padl, padr in ((kw // 2, kw // 2), (kw - 2, 1), (kw - 1, 0)):
+                    d = _lib.ConvDesc(2, 64, h, c, c, kw, 1, padl, padr)
+                    lib_says = h % 16 == 0 and L.w2l_tds_conv_bf16_image_elems(C.byref(d)) != 0
+                    assert lib_says == refnet.conv_rounds_to_bf16(c, c, kw, 1, h), (c, kw, h, padl, padr)
+                    n += 1
+                    yes += lib_says
+    assert yes > 20 and n - yes > 20
+    # the restatement applies it: at a geometry the library keeps in fp32 the bf16 block's convolution sees the exact operands,
+    # at one it multiplies in bf16 the rounded ones
+    rng = np.random.default_rng(8)
+    for c, kw, h, rounds in ((8, 9, 10, False), (40, 5, 16, False), (8, 9, 16, True), (10, 21, 80, True)):
+        assert refnet.conv_rounds_to_bf16(c, c, kw, 1, h) == rounds
+        p = refnet.TDSParams(c, kw, h, rng=rng)
+        x = rng.normal(size=(1, c, h, 6)).astype(np.float32)
+        pad = kw // 2
+        _, saved = refnet.tds_fwd(x, p, pad, pad, keep=True, bf16=True)
+        exact = oracle.conv_fwd(x, p.wc, p.bc, 1, pad, pad)
+        rounded = oracle.conv_fwd(refnet.bf16_round(x), refnet.bf16_round(p.wc), p.bc, 1, pad, pad)
+        assert np.array_equal(saved["a"], rounded if rounds else exact), (c, kw, h)
+        assert not np.array_equal(exact, rounded)
+        dx, g = refnet.tds_bwd(rng.normal(size=x.shape).astype(np.float32), p, saved, pad, pad, bf16=True)
+        assert np.isfinite(dx).all() and g["wc"].shape == p.wc.shape
