@@ -45,6 +45,7 @@
 #include <string>
 #include <type_traits>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #define FL_COMPAT_API __attribute__((visibility("default")))
@@ -530,6 +531,12 @@ class FL_COMPAT_API CTCLoss : public SequenceCriterion {
  private:
   CriterionScaleMode scaleMode_;
 };
+
+// fl_compat extension (the validation loop of the reference's test(), recipes/slimIPL/src/Train.cpp:874-980): loss (B) and
+// Viterbi path (T, B) s32 of a held-out batch in one call, instead of forward() followed by viterbiPath().  CTC reads the
+// emissions once (w2l_ctc_score); ASG runs its loss sequence and the Viterbi pass.  No gradient; the criterion's training
+// workspace is not touched (a workspace of its own), so a forward / backward pair around it is unaffected.
+FL_COMPAT_API std::pair<af::array, af::array> w2lScore(SequenceCriterion& criterion, const Variable& emission, const Variable& target);
 }  // namespace speech
 }  // namespace pkg
 }  // namespace fl

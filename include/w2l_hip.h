@@ -142,6 +142,14 @@ int w2l_ctc_backward(int B, int T, int N, int L, const float* input, const int* 
                      void* workspace, w2l_stream_t stream);
 /* CTCLoss::viterbiPath: per-frame argmax, first max wins */
 int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, w2l_stream_t stream);
+/* Evaluation in one read of the emissions: loss [B] bitwise equal to w2l_ctc_forward's (+inf for an infeasible target) and
+ * path [B][T] bitwise equal to w2l_ctc_viterbi's.  Keeps nothing for a backward pass: the workspace holds the per-frame lse and
+ * label probabilities only (no alpha / beta rows, exponents or label links), so w2l_ctc_backward cannot follow this call.
+ * w2l_ctc_score_workspace_size is host arithmetic and smaller than w2l_ctc_workspace_size for the same shape.
+ * L > 1023: W2L_EUNSUPPORTED, as w2l_ctc_forward. */
+size_t w2l_ctc_score_workspace_size(int B, int T, int N, int L);
+int w2l_ctc_score(int B, int T, int N, int L, int scaleMode, const float* input, const int* target,
+                  const int* targetSize, float* loss, int* path, void* workspace, w2l_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the
@@ -533,6 +541,17 @@ int w2l_trainer_set_optimizer(void* h, int netKind, int critKind);
 int w2l_trainer_set_input_sizes(void* h, const float* inputSizesDev);
 int w2l_trainer_bind_state2(void* h, float* state2);
 int w2l_trainer_viterbi(void* h, const float* emission, int* path, void* stream);
+/* Evaluation of a held-out batch on the planned shape: eval-mode network forward (no dropout), then the criterion's loss and
+ * Viterbi path in one call (CTC: w2l_ctc_score; ASG: its loss sequence and w2l_viterbi_compute).  *lossDev [B] and *pathDev
+ * [B][T'] point into the evaluation buffer (w2l_trainer_bind_eval, else one the trainer owns): valid until the next
+ * w2l_trainer_evaluate of this handle, untouched by training.
+ * Advances no step counter or dropout seed; the activation arena is reused, so it does not survive between a
+ * w2l_trainer_forward(train = 1) and its w2l_trainer_backward.  Replaces: the reference's test() (recipes/slimIPL/src/Train.cpp:874-980). */
+int w2l_trainer_evaluate(void* h, const float* x, const int* target, float** lossDev, int** pathDev, void* stream);
+/* the buffer w2l_trainer_evaluate works in (loss, path, score workspace) for the planned shape, and a caller-owned one to use
+ * instead of the trainer's own (mem = null: back to the trainer's own) */
+size_t w2l_trainer_eval_bytes(void* h);
+int w2l_trainer_bind_eval(void* h, void* mem, size_t bytes);
 int w2l_trainer_set_step(void* h, uint32_t step);
 /* --fl_amp_use_mixed_precision restated for bf16 (BASELINE config 3): the network's fl::Linear GEMMs multiply in bf16
  * with fp32 accumulation (w2l_set_matmul_precision scoped to the network's calls); storage, master weights, convolutions,

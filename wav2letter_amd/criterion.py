@@ -254,6 +254,25 @@ class _CTC(torch.autograd.Function):
         return dx, None, None, None
 
 
+def ctc_score(emission, target, scalemode=CriterionScaleMode.NONE):
+    """CTC evaluation in one read of the emissions (w2l_ctc_score): returns (loss [B] float32, path [B][T] int32), bitwise equal
+    to CTCLoss.forward and CTCLoss.viterbiPath.  No gradient: the loss does not take part in autograd."""
+    _emission_checks(emission, target)
+    _check_dev(emission, target)
+    L = _lib.lib()
+    emission = emission.detach().contiguous()
+    target = target.contiguous()
+    B, T, N = emission.shape
+    Lt = target.shape[1]
+    ts = batch_target_size(target, T, ctc=True)
+    ws = _ws(L.w2l_ctc_score_workspace_size(B, T, N, Lt), emission.device)
+    loss = torch.empty(B, dtype=torch.float32, device=emission.device)
+    path = torch.empty(B, T, dtype=torch.int32, device=emission.device)
+    _lib.check(L.w2l_ctc_score(B, T, N, Lt, int(scalemode), emission.data_ptr(), target.data_ptr(), ts.data_ptr(),
+                               loss.data_ptr(), path.data_ptr(), ws.data_ptr(), _stream()), "ctc_score")
+    return loss, path
+
+
 class SequenceCriterion(torch.nn.Module):
     """fl::pkg::speech::SequenceCriterion: forward({emission,target}) -> {loss[B]},
     viterbiPath(emission) -> [B][T] int32."""
@@ -403,6 +422,10 @@ class CTCLoss(SequenceCriterion):
         _lib.check(_lib.lib().w2l_ctc_viterbi(B, T, N, emission.data_ptr(), path.data_ptr(), _stream()),
                    "ctc_viterbi")
         return path
+
+    def score(self, emission, target):
+        """(loss [B], viterbiPath [B][T]) of a held-out batch in one pass over the emissions (ctc_score)"""
+        return ctc_score(emission, target, self.scalemode)
 
     def prettyString(self):
         return "ConnectionistTemporalClassificationCriterion"

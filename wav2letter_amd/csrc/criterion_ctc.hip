@@ -22,6 +22,9 @@
 //                  <= 2L+1 occupancies gamma[t][s] = exp(alpha+beta-lp-logZ) of
 //                  that frame.
 // Algorithmic HBM bytes: 4BTN (fwd) + 8BTN (bwd) = 12*B*T*N.
+// w2l_ctc_score (evaluation: loss and greedy path, no gradient) reads the emissions once, 4BTN:
+//   ctc_rows_score  the ctc_rows_lse pass (same arithmetic, template flag) that also writes the first-max argmax of the row
+//   ctc_scan_score  the alpha wave alone, grid (B, 1), lattice rows kept in registers: only the loss is written
 #include "common.hpp"
 
 namespace w2l {
@@ -108,6 +111,21 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* sm) {
   return r;
 }
 
+// path[0] = the smallest cand of the workgroup (thread 0 stores)
+__device__ __forceinline__ void block_argmin_store(int cand, int* out) {
+  __shared__ int smi[kRowThreads / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) cand = min(cand, __shfl_xor(cand, off));
+  if ((threadIdx.x & 63) == 0) smi[threadIdx.x >> 6] = cand;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = smi[0];
+#pragma unroll
+    for (int k = 1; k < kRowThreads / 64; ++k) c = min(c, smi[k]);
+    *out = c;
+  }
+}
+
 // Row loader: elements [0,N) of a row that is only 4-byte aligned. Thread tid owns
 // element indices  head: tid (< nh);  body: nh + 4*(tid + 256*k) .. +3;  tail scalars.
 // nh = number of leading scalars so that the body is 16-byte aligned.
@@ -128,12 +146,14 @@ __device__ __forceinline__ RowSplit row_split(const float* row, int N) {
 //   kernel's 68 (profiles/r05_run26_ctc_rows_lse_variants.log: variant 2 = no gather at all).
 // VAR 0: the gather behind the reductions.  Probe library, W2L_CTC_LSE_VAR: 1 = nontemporal row loads (48 us, but ctc_rows_grad
 //   then no longer finds the emissions in the Infinity Cache and takes the 20 us), 2 = no label gather (timing only)
-template <int VAR>
-__global__ __launch_bounds__(kRowThreads) void ctc_rows_lse(int T, int N, int L,
-                                                            const float* __restrict__ x,
-                                                            const int* __restrict__ target,
-                                                            const int* __restrict__ targetSize,
-                                                            CtcWs ws) {
+// kArgmax (ctc_rows_score, w2l_ctc_score): the same pass also writes path[r], the first-max argmax of the row that
+//   ctc_rows_argmax computes, from the register-resident row -- the arithmetic of lse and pd is the forward pass's own.
+template <int VAR, bool kArgmax>
+__device__ __forceinline__ void ctc_rows_lse_body(int T, int N, int L,
+                                                  const float* __restrict__ x,
+                                                  const int* __restrict__ target,
+                                                  const int* __restrict__ targetSize,
+                                                  const CtcWs& ws, int* __restrict__ path) {
   __shared__ float sm[8];
   const size_t r = blockIdx.x;  // row = b*T + t
   const int b = (int)(r / T);
@@ -188,6 +208,23 @@ __global__ __launch_bounds__(kRowThreads) void ctc_rows_lse(int T, int N, int L,
   s = block_reduce_sum(s, sm);
   const float lse = m + __logf(s);
   if (tid == 0) ws.lse[r] = lse;
+  if constexpr (kArgmax) {
+    // smallest index holding the row's max (m: the same fmaxf reduction, NaN ignored; -inf past the row never matches, and an
+    // all -inf row gets ctc_rows_argmax's 0x7fffffff)
+    int cand = 0x7fffffff;
+    if (m > -INFINITY) {
+#pragma unroll
+      for (int k = kRowMaxPer / 4 - 1; k >= 0; --k) {
+        const int i0 = sp.nh + 4 * (tid + kRowThreads * k);
+        if (v[k].w == m) cand = i0 + 3;
+        if (v[k].z == m) cand = i0 + 2;
+        if (v[k].y == m) cand = i0 + 1;
+        if (v[k].x == m) cand = i0;
+      }
+      if (hv == m) cand = tid < sp.nh ? tid : min(cand, sp.nh + 4 * sp.nbody4 + (tid - 64));
+    }
+    block_argmin_store(cand, path + r);
+  }
   if (VAR == 2) return;
   // label log-probs
   double* pd = ws.pd + r * ws.S;
@@ -199,20 +236,38 @@ __global__ __launch_bounds__(kRowThreads) void ctc_rows_lse(int T, int N, int L,
   for (int si = S + tid; si < ws.S; si += kRowThreads) pd[si] = 0.0;   // positions beyond the utterance's lattice: p = 0
 }
 
-// generic-N fallback (N > 256*kRowMaxPer): two passes over the row
-__global__ __launch_bounds__(kRowThreads) void ctc_rows_lse_big(int T, int N, int L,
-                                                                const float* __restrict__ x,
-                                                                const int* __restrict__ target,
-                                                                const int* __restrict__ targetSize,
-                                                                CtcWs ws) {
+template <int VAR>
+__global__ __launch_bounds__(kRowThreads) void ctc_rows_lse(int T, int N, int L,
+                                                            const float* __restrict__ x,
+                                                            const int* __restrict__ target,
+                                                            const int* __restrict__ targetSize,
+                                                            CtcWs ws) {
+  ctc_rows_lse_body<VAR, false>(T, N, L, x, target, targetSize, ws, nullptr);
+}
+
+// generic-N fallback (N > 256*kRowMaxPer): two passes over the row.  kArgmax: the first pass also keeps each thread's
+// first max and its index (ctc_rows_argmax's loop), so the argmax costs no third pass
+template <bool kArgmax>
+__device__ __forceinline__ void ctc_rows_lse_big_body(int T, int N, int L,
+                                                      const float* __restrict__ x,
+                                                      const int* __restrict__ target,
+                                                      const int* __restrict__ targetSize,
+                                                      const CtcWs& ws, int* __restrict__ path) {
   __shared__ float sm[8];
   const size_t r = blockIdx.x;
   const int b = (int)(r / T);
   const float* row = x + r * N;
   const int tid = threadIdx.x;
   float m = -INFINITY;
-  for (int n = tid; n < N; n += kRowThreads) m = fmaxf(m, row[n]);
+  float best = -INFINITY;
+  int arg = 0x7fffffff;
+  for (int n = tid; n < N; n += kRowThreads) {
+    const float v = row[n];
+    m = fmaxf(m, v);
+    if (kArgmax && v > best) { best = v; arg = n; }   // ascending n per thread: first max kept
+  }
   m = block_reduce_max(m, sm);
+  if constexpr (kArgmax) block_argmin_store(best == m ? arg : 0x7fffffff, path + r);
   float s = 0.f;
   for (int n = tid; n < N; n += kRowThreads) s += __expf(row[n] - m);
   s = block_reduce_sum(s, sm);
@@ -227,6 +282,30 @@ __global__ __launch_bounds__(kRowThreads) void ctc_rows_lse_big(int T, int N, in
     pd[si] = exp_wide(row[lab] - lse);
   }
   for (int si = S + tid; si < ws.S; si += kRowThreads) pd[si] = 0.0;   // positions beyond the utterance's lattice: p = 0
+}
+
+__global__ __launch_bounds__(kRowThreads) void ctc_rows_lse_big(int T, int N, int L,
+                                                                const float* __restrict__ x,
+                                                                const int* __restrict__ target,
+                                                                const int* __restrict__ targetSize,
+                                                                CtcWs ws) {
+  ctc_rows_lse_big_body<false>(T, N, L, x, target, targetSize, ws, nullptr);
+}
+
+// w2l_ctc_score's row pass: lse, the label probabilities and the argmax from one read of the row
+__global__ __launch_bounds__(kRowThreads) void ctc_rows_score(int T, int N, int L,
+                                                              const float* __restrict__ x,
+                                                              const int* __restrict__ target,
+                                                              const int* __restrict__ targetSize,
+                                                              CtcWs ws, int* __restrict__ path) {
+  ctc_rows_lse_body<3, true>(T, N, L, x, target, targetSize, ws, path);
+}
+__global__ __launch_bounds__(kRowThreads) void ctc_rows_score_big(int T, int N, int L,
+                                                                  const float* __restrict__ x,
+                                                                  const int* __restrict__ target,
+                                                                  const int* __restrict__ targetSize,
+                                                                  CtcWs ws, int* __restrict__ path) {
+  ctc_rows_lse_big_body<true>(T, N, L, x, target, targetSize, ws, path);
 }
 
 // ---- alpha / beta lattice scans in the SCALED LINEAR domain -----------------------------------------------------------
@@ -253,7 +332,8 @@ constexpr int kCtcNoExp = -(1 << 28);   // exponent of a position that holds no 
 // The direction is a TEMPLATE parameter and the chunk loop has a check-free main part: with `isBeta` a run-time value and
 // `k < T` tested per step and per load, hipcc kept uniform branches and register copies around every step -- ~125 instructions per
 // frame at P = 3 for ~50 of arithmetic (ISA), on a wave that issues one instruction every ~6.5 cycles.
-template <int P, int D, bool isBeta>
+// kScore (w2l_ctc_score): the alpha recursion alone, nothing stored but the loss -- the lattice rows live in registers only.
+template <int P, int D, bool isBeta, bool kScore = false>
 __device__ __forceinline__ void ctc_scan_body(int T, int N, int L, int scaleMode,
                                               const int* __restrict__ target,
                                               const int* __restrict__ targetSize,
@@ -266,8 +346,9 @@ __device__ __forceinline__ void ctc_scan_body(int T, int N, int L, int scaleMode
   const int SW = ws.S;
   const int* y = target + (size_t)b * L;
   const double* pd = ws.pd + (size_t)b * T * SW;
-  double* lat = (isBeta ? ws.beta : ws.alpha) + (size_t)b * T * SW;
-  int* lex = (isBeta ? ws.eB : ws.eA) + (size_t)b * T * SW;
+  static_assert(!(kScore && isBeta), "the score pass has no beta scan");
+  double* lat = kScore ? nullptr : (isBeta ? ws.beta : ws.alpha) + (size_t)b * T * SW;
+  int* lex = kScore ? nullptr : (isBeta ? ws.eB : ws.eA) + (size_t)b * T * SW;
 
   bool skip[P];   // alpha: position s may be entered from s - 2; beta: position s may go to s + 2
 #pragma unroll
@@ -290,8 +371,8 @@ __device__ __forceinline__ void ctc_scan_body(int T, int N, int L, int scaleMode
   const long rstride = isBeta ? -(long)SW : (long)SW;
   const long row0 = (long)(isBeta ? T - 1 : 0) * SW + (long)lane * P;
   const d2_t* pdp = (const d2_t*)(pd + row0);   // p of step k at pdp + k * rstride (in doubles: / 2 vectors)
-  d2_t* latp = (d2_t*)(lat + row0);
-  i2_t* lexp = (i2_t*)(lex + row0);
+  d2_t* latp = kScore ? nullptr : (d2_t*)(lat + row0);
+  i2_t* lexp = kScore ? nullptr : (i2_t*)(lex + row0);
   auto loadp = [&](double (&dst)[P], int k, auto checked) {   // checked: std::true_type = step k may lie beyond the last frame
     constexpr bool CHECK = decltype(checked)::value;
     const double* q1 = (const double*)pdp + (long)k * rstride;
@@ -332,7 +413,7 @@ __device__ __forceinline__ void ctc_scan_body(int T, int N, int L, int scaleMode
       m[p] = __builtin_amdgcn_frexp_mant(h);
       e[p] = h > 0.0 ? __builtin_amdgcn_frexp_exp(h) : kCtcNoExp;
     }
-    storerow(m, e, 0);
+    if constexpr (!kScore) storerow(m, e, 0);
   }
 
   double pc[D][P], pn[D][P];   // p of steps k0 .. k0 + D - 1 (current chunk) and of the next chunk
@@ -399,9 +480,11 @@ __device__ __forceinline__ void ctc_scan_body(int T, int N, int L, int scaleMode
     for (int u = 0; u < D; ++u)
 #pragma unroll
       for (int p = 0; p < P; ++p) asm volatile("" : "+v"(pn[u][p]));   // consumed BEFORE the chunk's stores are issued
+    if constexpr (!kScore) {
 #pragma unroll
-    for (int u = 0; u < D; ++u)
-      if (!CHECK || k0 + u < T) storerow(sm[u], se[u], k0 + u);
+      for (int u = 0; u < D; ++u)
+        if (!CHECK || k0 + u < T) storerow(sm[u], se[u], k0 + u);
+    }
   };
   int k0 = 1;
   for (; k0 + 3 * D <= T; k0 += 2 * D) {   // two chunks per trip, the two p buffers swapping roles: no D P register copies per chunk
@@ -438,6 +521,7 @@ __device__ __forceinline__ void ctc_scan_body(int T, int N, int L, int scaleMode
     double ll = -INFINITY;
     if (zs > 0.0) ll = log(zs) + (double)ez * 0.69314718055994530942;
     loss[b] = (float)(-(double)sc * ll);
+    if constexpr (kScore) return;
     ws.scale[b] = sc;
     ws.nll[b] = (float)(-ll);
     ws.zhat[b] = zs;
@@ -452,6 +536,15 @@ __global__ __launch_bounds__(64) void ctc_scan(int T, int N, int L, int scaleMod
                                                float* __restrict__ loss, CtcWs ws) {
   if (blockIdx.y == 1) ctc_scan_body<P, D, true>(T, N, L, scaleMode, target, targetSize, loss, ws);
   else ctc_scan_body<P, D, false>(T, N, L, scaleMode, target, targetSize, loss, ws);
+}
+
+// w2l_ctc_score: the alpha wave alone, grid (B, 1)
+template <int P, int D>
+__global__ __launch_bounds__(64) void ctc_scan_score(int T, int N, int L, int scaleMode,
+                                                     const int* __restrict__ target,
+                                                     const int* __restrict__ targetSize,
+                                                     float* __restrict__ loss, CtcWs ws) {
+  ctc_scan_body<P, D, false, true>(T, N, L, scaleMode, target, targetSize, loss, ws);
 }
 
 // link[b][k] for k < L_b: the next position with the same label (kLinkNone: none), | kLinkLater when an earlier position holds
@@ -738,6 +831,52 @@ W2L_API int w2l_ctc_backward(int B, int T, int N, int L, const float* input, con
   hipLaunchKernelGGL(ctc_label_links_k, dim3((unsigned)B), dim3(kRowThreads), 0, s, L, target, targetSize, ws.link);
   W2L_LAUNCH_CHECK();
   hipLaunchKernelGGL(ctc_rows_grad, dim3(rows), dim3(kRowThreads), 0, s, T, N, L, input, target, targetSize, grad, inputGrad, ws);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+// The score pass's workspace: lse [B][T] and the label probabilities pd [B][T][S] -- what the row pass hands to the alpha scan.
+// No alpha / beta rows, no exponents, no links: those exist only for the backward pass.
+static CtcWs ctc_score_ws(void* ws, int B, int T, int L) {
+  CtcWs w{};
+  w.P = ctc_positions_per_lane(L);
+  w.S = 64 * w.P;
+  char* p = (char*)ws;
+  w.lse = (float*)p; p += align_up((size_t)B * T * sizeof(float), 256);
+  w.pd = (double*)p;
+  return w;
+}
+
+W2L_API size_t w2l_ctc_score_workspace_size(int B, int T, int N, int L) {
+  if (B <= 0 || T <= 0 || N <= 0 || L < 0) return 0;
+  const size_t S = 64 * (size_t)ctc_positions_per_lane(L);
+  return align_up((size_t)B * T * sizeof(float), 256) + align_up((size_t)B * T * S * sizeof(double), 256);
+}
+
+W2L_API int w2l_ctc_score(int B, int T, int N, int L, int scaleMode, const float* input, const int* target,
+                          const int* targetSize, float* loss, int* path, void* workspace, w2l_stream_t stream) {
+  if (B <= 0 || T <= 0 || N <= 1 || L <= 0 || !input || !target || !targetSize || !loss || !path || !workspace)
+    return W2L_EINVAL;
+  if (L > kCtcMaxLabels) return W2L_EUNSUPPORTED;   // as w2l_ctc_forward
+  hipStream_t s = (hipStream_t)stream;
+  CtcWs ws = ctc_score_ws(workspace, B, T, L);
+  const unsigned rows = (unsigned)((size_t)B * T);
+  if (N <= kRowThreads * kRowMaxPer)
+    hipLaunchKernelGGL(ctc_rows_score, dim3(rows), dim3(kRowThreads), 0, s, T, N, L, input, target, targetSize, ws, path);
+  else
+    hipLaunchKernelGGL(ctc_rows_score_big, dim3(rows), dim3(kRowThreads), 0, s, T, N, L, input, target, targetSize, ws, path);
+  W2L_LAUNCH_CHECK();
+  const dim3 grid((unsigned)B, 1), blk(64);   // the alpha wave of each utterance
+  switch (ws.P) {   // the forward pass's (P, D) pairs
+    case 2: hipLaunchKernelGGL((ctc_scan_score<2, 16>), grid, blk, 0, s, T, N, L, scaleMode, target, targetSize, loss, ws); break;
+    case 3: hipLaunchKernelGGL((ctc_scan_score<3, 10>), grid, blk, 0, s, T, N, L, scaleMode, target, targetSize, loss, ws); break;
+    case 4: hipLaunchKernelGGL((ctc_scan_score<4, 8>), grid, blk, 0, s, T, N, L, scaleMode, target, targetSize, loss, ws); break;
+    case 5: hipLaunchKernelGGL((ctc_scan_score<5, 6>), grid, blk, 0, s, T, N, L, scaleMode, target, targetSize, loss, ws); break;
+    case 6: hipLaunchKernelGGL((ctc_scan_score<6, 5>), grid, blk, 0, s, T, N, L, scaleMode, target, targetSize, loss, ws); break;
+    case 8: hipLaunchKernelGGL((ctc_scan_score<8, 4>), grid, blk, 0, s, T, N, L, scaleMode, target, targetSize, loss, ws); break;
+    case 16: hipLaunchKernelGGL((ctc_scan_score<16, 2>), grid, blk, 0, s, T, N, L, scaleMode, target, targetSize, loss, ws); break;
+    default: hipLaunchKernelGGL((ctc_scan_score<32, 1>), grid, blk, 0, s, T, N, L, scaleMode, target, targetSize, loss, ws); break;
+  }
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }

@@ -38,6 +38,17 @@ class CTCLossImpl : public SequenceCriterion {
   void viterbiPath(Ctx& c, int B, int T, int N, const float* em, int* path, void*, float*) override {
     w2lCheck(w2l_ctc_viterbi(B, T, N, em, path, c.stream), "ctc viterbi");
   }
+  size_t scoreWorkspaceBytes(int B, int T, int N, int L) const override {
+    return up(sizeof(int) * B) + w2l_ctc_score_workspace_size(B, T, N, L);
+  }
+  // one read of the emissions for loss and path (w2l_ctc_score)
+  void score(Ctx& c, int B, int T, int N, int L, const float* em, const int* target, float* loss, int* path, void* ws,
+             float*) override {
+    int* ts = (int*)ws;
+    void* kws = (char*)ws + up(sizeof(int) * B);
+    w2lCheck(w2l_batch_ctc_target_size(B, L, T, target, ts, c.stream), "ctc target size");
+    w2lCheck(w2l_ctc_score(B, T, N, L, mode_, em, target, ts, loss, path, kws, c.stream), "ctc score");
+  }
 
  private:
   int mode_;
@@ -189,11 +200,20 @@ class ASGLossImpl : public SequenceCriterion {
     Ws w = carve(ws, B, T, N, 1);
     w2lCheck(w2l_viterbi_compute(B, T, N, em, trans, path, w.b.fcc, c.stream), "viterbi");
   }
+  // the loss sequence, then the Viterbi path, on the score workspace and a sequence of its own (side stream, events, the
+  // forward-to-backward note of the training sequence stay untouched)
+  void score(Ctx& c, int B, int T, int N, int L, const float* em, const int* target, float* loss, int* path, void* ws,
+             float* trans) override {
+    if (N != N_) throw std::invalid_argument("ASGLoss: N doesn't match with the letter size");
+    const Ws w = carve(ws, B, T, N, L);
+    evalSeq_.forward(c.stream, B, T, N, L, mode_, em, target, trans, loss, w.b);
+    w2lCheck(w2l_viterbi_compute(B, T, N, em, trans, path, w.vit, c.stream), "viterbi");
+  }
 
  private:
   int N_, mode_;
   double transdiag_;
-  AsgSequence seq_;
+  AsgSequence seq_, evalSeq_;
 };
 
 // LinearSegmentationCriterion: ASG on the linearly stretched target (first --linseg updates, Train.cpp:589-617).

@@ -837,7 +837,22 @@ class PlannedNet : public fl::Sequential {
     for (size_t i = 0; i < params_.size(); ++i)
       if (params_[i].array().device<float>() != (float*)paramArena_.get() + net_->params()[i].offset)
         throw std::logic_error("setParams on a planned network must write INTO the parameter (copy), not rebind it");
-    if (B != B_ || T != T_) {
+    // eval mode (the validation sets): a plan of its own -- a second module graph over the same parameter arena, with its own
+    // activation arena -- so that a valid batch's shape never re-plans the training graph, and no forward counter moves: the
+    // dropout seed of the next training forward is the one it would have been without the evaluation
+    const bool useEval = !train_ && !archText_.empty();
+    if (useEval) {
+      if (!evalNet_) {
+        evalNet_ = w2l::buildSequentialFromText(archText_, archNFeat_, archNLabel_);
+        if (!bucketOffsets_.empty()) evalNet_->setGradBuckets(bucketOffsets_, bucketEvents_);
+      }
+      if (B != evalB_ || T != evalT_) {
+        const size_t fl = evalNet_->plan(B, T, nFeat_);
+        if (nLabel_ < 0) nLabel_ = evalNet_->outAct().F;       // (a Sequential of layer objects run in eval mode first)
+        if (fl > evalArenaFloats_) { evalArena_ = devAlloc(fl * sizeof(float)); evalArenaFloats_ = fl; }
+        evalB_ = B; evalT_ = T;
+      }
+    } else if (B != B_ || T != T_) {
       const size_t fl = net_->plan(B, T, nFeat_);
       if (nLabel_ < 0) nLabel_ = net_->outAct().F;           // (... and the last layer the label count)
       arena_ = devAlloc(fl * sizeof(float));
@@ -845,8 +860,10 @@ class PlannedNet : public fl::Sequential {
       B_ = B; T_ = T;
       dEm_ = devAlloc(((size_t)B * net_->outAct().T * nLabel_ + 64) * sizeof(float));
     }
+    w2l::Sequential* net = useEval ? evalNet_.get() : net_.get();
+    std::shared_ptr<void> arena = useEval ? evalArena_ : arena_;
     w2l::Ctx c;
-    c.stream = S(); c.train = train_; c.seed = 0x9E3779B9u * (++step_);
+    c.stream = S(); c.train = train_; c.seed = 0x9E3779B9u * (train_ ? ++step_ : step_ + 1);
     c.params = (float*)paramArena_.get(); c.grads = (float*)gradArena_.get();
     c.bf16 = mixed_;
     if (inputs.size() >= 2 && !inputs[1].isempty()) {  // inputSizes (1, B): padding mask of the Transformer blocks
@@ -858,19 +875,19 @@ class PlannedNet : public fl::Sequential {
       c.inputT = T;
     }
     const int prevMode = mixed_ ? w2l_set_matmul_precision(1) : 0;
-    const float* em = net_->forward(c, (float*)arena_.get(), in.array().device<float>());
+    const float* em = net->forward(c, (float*)arena.get(), in.array().device<float>());
     if (mixed_) w2l_set_matmul_precision(prevMode);
-    const int To = net_->outAct().T;
-    af::array out = af::array::wrap((void*)em, af::dim4(nLabel_, To, B), af::f32, arena_);
+    const int To = net->outAct().T;
+    af::array out = af::array::wrap((void*)em, af::dim4(nLabel_, To, B), af::f32, arena);
     auto self = this;
     auto ctx = c;
     std::vector<Variable> deps(params_.begin(), params_.end());
     deps.push_back(in);
-    return {Variable(out, deps, [self, ctx](std::vector<Variable>& ins, const Variable& gradOut) mutable {
+    return {Variable(out, deps, [self, ctx, net, arena](std::vector<Variable>& ins, const Variable& gradOut) mutable {
       // whole-network backward: overwrites every parameter gradient in the flat gradient arena, then hands each
       // parameter a VIEW of its slice (no per-parameter copies; netoptim steps on the views)
       const int prevMode = self->mixed_ ? w2l_set_matmul_precision(1) : 0;
-      self->net_->backward(ctx, (float*)self->arena_.get(), gradOut.array().device<float>());
+      net->backward(ctx, (float*)arena.get(), gradOut.array().device<float>());
       if (self->mixed_) w2l_set_matmul_precision(prevMode);
       for (size_t i = 0; i + 1 < ins.size(); ++i) {
         const auto& pi = self->net_->params()[i];
@@ -902,7 +919,10 @@ class PlannedNet : public fl::Sequential {
     }
     bucketOffsets_ = offs;
     net_->setGradBuckets(offs, bucketEvents_);
+    if (evalNet_) evalNet_->setGradBuckets(offs, bucketEvents_);
   }
+  std::string archText_;            // what the eval-mode plan is built from (with the sizes the network was built with)
+  int64_t archNFeat_ = 0, archNLabel_ = 0;
 
  private:
   std::shared_ptr<w2l::Sequential> net_;
@@ -911,6 +931,10 @@ class PlannedNet : public fl::Sequential {
   size_t arenaFloats_ = 0;
   int B_ = 0, T_ = 0;
   uint32_t step_ = 0;
+  std::shared_ptr<w2l::Sequential> evalNet_;   // eval mode: same arch and parameter arena, a plan and arena of its own
+  std::shared_ptr<void> evalArena_;
+  size_t evalArenaFloats_ = 0;
+  int evalB_ = 0, evalT_ = 0;
 };
 
 }  // namespace
@@ -959,6 +983,9 @@ std::vector<PlannedNet*>& plannedNets() { static std::vector<PlannedNet*> v; ret
 std::shared_ptr<fl::Sequential> buildSequentialModuleFromText(const std::string& archText, int64_t nFeatures, int64_t nClasses) {
   auto net = std::make_shared<PlannedNet>(w2l::buildSequentialFromText(archText, nFeatures, nClasses), nFeatures, nClasses);
   net->archSha_ = sha256Hex(archText);
+  net->archText_ = archText;
+  net->archNFeat_ = nFeatures;
+  net->archNLabel_ = nClasses;
   plannedNets().push_back(net.get());   // (networks live as long as the trainer process: no removal)
   return net;
 }
@@ -1092,6 +1119,13 @@ struct CritState {
     const size_t need = impl->workspaceBytes(B, T, N, 1) + 256;
     if (need > vwsBytes) { vws = devAlloc(need); vwsBytes = need; }
     return vws.get();
+  }  // w2lScore: a third workspace, so that a score between a forward and its backward leaves `ws` alone
+  std::shared_ptr<void> sws;
+  size_t swsBytes = 0;
+  void* scoreWorkspace(int B, int T, int N, int L) {
+    const size_t need = impl->scoreWorkspaceBytes(B, T, N, L) + 256;
+    if (need > swsBytes) { sws = devAlloc(need); swsBytes = need; }
+    return sws.get();
   }
 };
 
@@ -1204,6 +1238,25 @@ af::array CTCLoss::viterbiPathWithTarget(const af::array&, const af::array&, con
   throw std::logic_error("CTCLoss::viterbiPathWithTarget is not used by the recipes' training loop (forced alignment is an ASG / tools feature)");
 }
 std::string CTCLoss::prettyString() const { return "ConnectionistTemporalClassificationCriterion"; }
+
+std::pair<af::array, af::array> w2lScore(SequenceCriterion& criterion, const Variable& emission, const Variable& target) {
+  int N, T, B, L;
+  checkCritInputs({emission, target}, N, T, B, L);
+  auto st = stateOf(&criterion);
+  if (!st) throw std::invalid_argument("w2lScore: not a criterion of this library (ASGLoss / CTCLoss)");
+  float* trans = nullptr;
+  if (auto* asg = dynamic_cast<ASGLoss*>(&criterion)) {
+    if (N != (int)asg->transitions().dims(0)) throw std::invalid_argument("ASGLoss: N doesn't match with the letter size");
+    trans = asg->transitions().array().device<float>();
+  }
+  w2l::Ctx c;
+  c.stream = S();
+  af::array loss(af::dim4(B), af::f32);
+  af::array path(af::dim4(T, B), af::s32);
+  st->impl->score(c, B, T, N, L, emission.array().device<float>(), target.array().device<int>(), loss.device<float>(),
+                  path.device<int>(), st->scoreWorkspace(B, T, N, L), trans);
+  return {loss, path};
+}
 
 }  // namespace speech
 }  // namespace pkg

@@ -24,7 +24,12 @@
 // ASG), batches of --batchsize in list order, rank r taking its share of every global batch (partitionByRoundRobin); train-TER /
 // train-WER of the log line come from the Viterbi path through tknPrediction2Ltr / tkn2Wrd (Train.cpp:829-872).  Without lists the
 // data is SYNTHETIC: LibriSpeech-shaped padded batches (--w2l_synth_frames frames of --filterbanks features, random targets), which
-// is exactly what bench.py times.  Not here (out of scope): the decoder, cereal checkpoints, validation sets.
+// is exactly what bench.py times.  Not here (out of scope): the decoder (beam search, LM), cereal checkpoints.
+// Validation (test(), Train.cpp:874-980): --valid=[tag:]list,... (relative to --datadir; the tag defaults to the path) and
+// --validbatchsize (-1: --batchsize) -- at every log line each set goes, unshuffled and shared round-robin among the ranks,
+// through the eval-mode network and w2lScore (loss + greedy / Viterbi path in one call); `<tag>-loss | <tag>-TER | <tag>-WER`
+// follow train-WER (MyLogger.cpp:60-70), and NNN_model_<tag>.bin is written when a set's WER beats this run's best.  A
+// synthetic run ignores --valid.
 // Flags of this driver that the reference does not have are prefixed w2l_.
 // Data parallelism is the reference's: --enable_distributed --world_rank --world_size --max_devices_per_node
 // --rndv_filepath (Train.cpp:188-199; RANK / WORLD_SIZE / LOCAL_WORLD_SIZE of a torchrun-style launcher are read when the
@@ -405,45 +410,82 @@ int main(int argc, char** argv) {
       for (std::string one; std::getline(ls, one, ',');) if (!one.empty()) listPaths.push_back(pathJoin(dataDir, one));
     }
     const bool haveLists = !listPaths.empty() && trainLists.find("[DATA_DST]") == std::string::npos && fileExists(listPaths[0]);
-    ListData data;
-    if (haveLists) {
-      for (auto& lp : listPaths) {
+    // list files -> ListData with the train lists' text pipeline (tokens, lexicon, replabel, wordseparator; surround and usewordpiece
+    // are read where the paths are turned into words); `which` names the flag in the error messages
+    // (validation sets: allowEmpty -- every sample on exactly one rank, the tail included)
+    auto loadLists = [&](ListData& d, const std::vector<std::string>& paths, int bsz, const std::string& which, bool allowEmpty) {
+      for (auto& lp : paths) {
         std::ifstream lf(lp);
-        if (!lf) throw std::invalid_argument("cannot read the list file '" + lp + "' (--train / --datadir)");
+        if (!lf) throw std::invalid_argument("cannot read the list file '" + lp + "' (" + which + " / --datadir)");
         std::stringstream buf;
         buf << lf.rdbuf();
         for (auto& smp : fl::pkg::speech::parseList(buf.str())) {
-          data.samples.push_back(smp);
-          auto& pth = data.samples.back().path;   // the recipes' lists hold absolute paths; a relative one is taken from --datadir
+          d.samples.push_back(smp);
+          auto& pth = d.samples.back().path;   // the recipes' lists hold absolute paths; a relative one is taken from --datadir
           if (!pth.empty() && pth[0] != '/' && !fileExists(pth)) pth = pathJoin(dataDir, pth);
         }
       }
-      if (data.samples.empty()) throw std::invalid_argument("the --train lists hold no samples");
-      data.criterion = criterionName;
-      data.replabel = criterionName == "asg" ? (int)flags.geti("replabel", 0) : 0;
-      data.wordsep = flags.get("wordseparator", "|");
-      data.dict = fl::pkg::speech::createTokenDict(fl::lib::text::Dictionary(pathJoin(flags.get("tokensdir", ""), flags.get("tokens", "tokens.txt"))),
-                                                   criterionName, data.replabel);
-      if ((int)data.dict.indexSize() != numClasses) throw std::invalid_argument("token dictionary size != number of classes");
+      if (d.samples.empty()) throw std::invalid_argument("the " + which + " lists hold no samples");
+      d.criterion = criterionName;
+      d.replabel = criterionName == "asg" ? (int)flags.geti("replabel", 0) : 0;
+      d.wordsep = flags.get("wordseparator", "|");
+      d.dict = fl::pkg::speech::createTokenDict(fl::lib::text::Dictionary(pathJoin(flags.get("tokensdir", ""), flags.get("tokens", "tokens.txt"))),
+                                                criterionName, d.replabel);
+      if ((int)d.dict.indexSize() != numClasses) throw std::invalid_argument("token dictionary size != number of classes");
       const std::string lexPath = flags.get("lexicon", "");
-      if (!lexPath.empty() && fileExists(lexPath)) data.lexicon = fl::lib::text::loadWords(lexPath, (int)flags.geti("maxword", -1));
-      data.nFeat = nFeat;
-      data.batch = batch;
-      data.shuffleSeed = seed;
-      data.rate = (int)flags.geti("samplerate", 16000);
-      data.padFrames = (int)flags.geti("w2l_pad_frames", 64);
-      data.nthread = (int)flags.geti("nthread", 6);
+      if (!lexPath.empty() && fileExists(lexPath)) d.lexicon = fl::lib::text::loadWords(lexPath, (int)flags.geti("maxword", -1));
+      d.nFeat = nFeat;
+      d.batch = bsz;
+      d.shuffleSeed = seed;
+      d.rate = (int)flags.geti("samplerate", 16000);
+      d.padFrames = (int)flags.geti("w2l_pad_frames", 64);
+      d.nthread = (int)flags.geti("nthread", 6);
       fl::lib::audio::FeatureParams fp;
-      fp.samplingFreq = data.rate; fp.frameSizeMs = (int)flags.geti("framesizems", 25); fp.frameStrideMs = (int)flags.geti("framestridems", 10);
+      fp.samplingFreq = d.rate; fp.frameSizeMs = (int)flags.geti("framesizems", 25); fp.frameStrideMs = (int)flags.geti("framestridems", 10);
       fp.numFilterbankChans = nFeat; fp.preemCoef = (float)flags.getd("preemcoef", 0.97); fp.melFloor = (float)flags.getd("melfloor", 1.0);
       if (flags.getb("mfcc", false) || flags.getb("pow", false)) throw std::invalid_argument("list data: only --mfsc features are built (--mfcc / --pow are not)");
-      data.mfsc.reset(new fl::lib::audio::Mfsc(fp));
+      d.mfsc.reset(new fl::lib::audio::Mfsc(fp));
       const float unit[2] = {1.f, 0.f};
-      data.unit = af::array(af::dim4(2), unit);
-      for (long i : fl::lib::partitionByRoundRobin((long)data.samples.size(), fl::getWorldRank(), fl::getWorldSize(), batch)) data.mine.push_back(i);
+      d.unit = af::array(af::dim4(2), unit);
+      for (long i : fl::lib::partitionByRoundRobin((long)d.samples.size(), fl::getWorldRank(), fl::getWorldSize(), bsz, allowEmpty))
+        d.mine.push_back(i);
+    };
+    ListData data;
+    if (haveLists) {
+      loadLists(data, listPaths, batch, "--train", false);
       if (data.mine.empty()) throw std::invalid_argument("this rank has no samples (fewer samples than world_size * batchsize)");
       std::cout << "[Data] " << data.samples.size() << " samples in " << listPaths.size() << " list(s), " << data.mine.size() << " on this rank, "
                 << data.batches() << " batches of " << batch << " per epoch; " << nFeat << " MFSC features; " << data.dict.indexSize() << " classes" << std::endl;
+    }
+    // --valid=[tag:]list,... (parseValidSets, Train.cpp:232-233, :362-370): each set is scored in list order (no shuffle), every
+    // rank its round-robin share, the short last batch included; --validbatchsize = -1: --batchsize
+    struct ValidSet {
+      std::string tag;
+      ListData data;
+      double bestWer = std::numeric_limits<double>::infinity();
+      double loss = 0, ter = 0, wer = 0;
+    };
+    std::vector<std::unique_ptr<ValidSet>> validSets;
+    if (!flags.get("valid", "").empty()) {
+      if (!haveLists) {
+        std::cout << "[Valid] --valid is ignored: no --train list files (synthetic data)" << std::endl;
+      } else {
+        const long vb = flags.geti("validbatchsize", -1);
+        const int validBatch = vb == -1 ? batch : (int)vb;
+        if (validBatch <= 0) throw std::invalid_argument("--validbatchsize must be positive (or -1: --batchsize)");
+        std::istringstream vs(flags.get("valid"));
+        for (std::string one; std::getline(vs, one, ',');) {
+          if (one.empty()) continue;
+          auto v = std::make_unique<ValidSet>();
+          const size_t colon = one.find(':');
+          const std::string path = colon == std::string::npos ? one : one.substr(colon + 1);
+          v->tag = colon == std::string::npos ? one : one.substr(0, colon);
+          loadLists(v->data, {pathJoin(dataDir, path)}, validBatch, "--valid", true);
+          std::cout << "[Valid] " << v->tag << ": " << v->data.samples.size() << " samples, " << v->data.mine.size() << " on this rank, "
+                    << v->data.batches() << " batches of " << validBatch << std::endl;
+          validSets.push_back(std::move(v));
+        }
+      }
     }
     std::mt19937_64 rng(2026 + seed + 7919ull * (uint64_t)fl::getWorldRank());   // every rank draws its own shard of the (synthetic) minibatch
     std::normal_distribution<float> gauss(0.f, 1.f);
@@ -498,6 +540,11 @@ int main(int argc, char** argv) {
       const double ter = editLen ? 100.0 * editErr / editLen : 0.0;
       item("train-TER", fmt("%5.2f", ter));
       item("train-WER", fmt("%5.2f", haveLists ? wordMeter.value() : ter));  // synthetic targets: every token is its own word
+      for (auto& v : validSets) {   // MyLogger.cpp:60-70
+        item(v->tag + "-loss", fmt("%10.5f", v->loss));
+        item(v->tag + "-TER", fmt("%5.2f", v->ter));
+        item(v->tag + "-WER", fmt("%5.2f", v->wer));
+      }
       const double framesPerSample = haveLists && nsamples ? (double)framesTotal / nsamples : T;
       item("avg-isz", fmti("%03ld", (long)framesPerSample));
       item("avg-tsz", fmti("%03ld", nsamples ? tszTotal / nsamples : 0));
@@ -564,6 +611,104 @@ int main(int argc, char** argv) {
       }
       if (saug) config["w2l_saug_calls"] = std::to_string(saug->calls());
       Serializer::save(getRunFile("model_last.bin", runIdx, runPath), "0.1", config, network, criterion, netoptim, critoptim);
+    };
+
+    // ---- validation (test(), Train.cpp:874-980): every --valid set through the eval-mode network and w2lScore (one call for the
+    // loss and the Viterbi path; a plan and workspaces of their own, so the training steps around it compute what they would
+    // without it); the sums are all-reduced exactly, so every rank holds the global loss / TER / WER
+    auto runValid = [&]() {
+      if (validSets.empty()) return;
+      network->eval();
+      criterion->eval();
+      const bool wp = flags.getb("usewordpiece", false);
+      const std::string surround = flags.get("surround", "");
+      for (auto& v : validSets) {
+        ListData& d = v->data;
+        double lossSum = 0;
+        long n = 0;
+        fl::EditDistanceMeter letters, words;   // TER over the letters of tknPrediction2Ltr / tknTarget2Ltr, WER over tkn2Wrd (evalOutput)
+        const long nb = d.batches();
+        for (long k = 0; k < nb; ++k) {
+          af::array feats;
+          std::vector<float> sizes;
+          std::vector<int> vt;
+          int vL = 1, vT = 0;
+          const int vB = d.get(k, k + 1 < nb ? k + 1 : 0, feats, vt, vL, sizes, vT);
+          af::array inSizes(af::dim4(1, (af::dim_t)sizes.size()), sizes.data());
+          auto out = network->forward({fl::input(feats), fl::noGrad(inSizes)}).front();
+          fl::Variable tgt(af::array(af::dim4(vL, vB), vt.data()), false);
+          auto sc = w2lScore(*criterion, out, tgt);
+          const int To = (int)out.dims(1);
+          std::vector<float> hl((size_t)vB);
+          std::vector<int> path((size_t)vB * To);
+          sc.first.host(hl.data());
+          sc.second.host(path.data());
+          for (int b = 0; b < vB; ++b) {
+            lossSum += hl[(size_t)b];
+            ++n;
+            std::vector<int> ref;
+            for (int i = 0; i < vL && vt[(size_t)b * vL + i] >= 0; ++i) ref.push_back(vt[(size_t)b * vL + i]);
+            std::vector<int> pv(path.begin() + (size_t)b * To, path.begin() + (size_t)(b + 1) * To);
+            const auto hl = tknPrediction2Ltr(pv, d.dict, criterionName, surround, d.replabel, wp, d.wordsep);
+            const auto rl = tknTarget2Ltr(ref, d.dict, criterionName, surround, d.replabel, wp, d.wordsep);
+            letters.add(hl, rl);
+            words.add(tkn2Wrd(hl, d.wordsep), tkn2Wrd(rl, d.wordsep));
+          }
+        }
+        double sums[6] = {lossSum, (double)n, (double)letters.errors(), (double)letters.length(), (double)words.errors(), (double)words.length()};
+        if (fl::getWorldSize() > 1) {
+          // the collective sums f32: every rank puts its six doubles, each as three floats that add up to it exactly, into a slot of
+          // its own (zeros elsewhere), so the sum hands every rank every rank's numbers unrounded; they are added in double, in
+          // rank order -- the same exact global numbers on every rank
+          const int W = fl::getWorldSize(), R = fl::getWorldRank();
+          std::vector<float> g((size_t)W * 6 * 3, 0.f);
+          for (int i = 0; i < 6; ++i) {
+            float* q = g.data() + ((size_t)R * 6 + i) * 3;
+            const double x = sums[i];
+            q[0] = (float)x;
+            if (std::isfinite(x)) {
+              const double r = x - (double)q[0];
+              q[1] = (float)r;
+              q[2] = (float)(r - (double)q[1]);
+            }
+          }
+          af::array a(af::dim4((af::dim_t)g.size()), g.data());
+          fl::allReduce(a);
+          a.host(g.data());
+          for (int i = 0; i < 6; ++i) {
+            sums[i] = 0;
+            for (int r = 0; r < W; ++r) {
+              const float* q = g.data() + ((size_t)r * 6 + i) * 3;
+              sums[i] += ((double)q[0] + (double)q[1]) + (double)q[2];
+            }
+          }
+        }
+        v->loss = sums[1] > 0 ? sums[0] / sums[1] : 0.0;
+        v->ter = sums[3] > 0 ? 100.0 * sums[2] / sums[3] : 0.0;
+        v->wer = sums[5] > 0 ? 100.0 * sums[4] / sums[5] : 0.0;
+      }
+      network->train();
+      criterion->train();
+    };
+    // NNN_model_<tag>.bin whenever a set's WER is below the best of this run ('/' in the tag -> '#'; Train.cpp:783-800)
+    auto saveBestValid = [&](long epoch, long totalUpdates) {
+      for (auto& v : validSets) {
+        if (!(v->wer < v->bestWer)) continue;
+        v->bestWer = v->wer;
+        if (!haveRunDir || !isMaster) continue;
+        std::string clean = v->tag;
+        std::replace(clean.begin(), clean.end(), '/', '#');
+        std::ostringstream rs;
+        rs << rng << " " << gauss;
+        Serializer::Config config;
+        config["gflags"] = gflagsText;
+        config["epoch"] = std::to_string(epoch);
+        config["nbupdates"] = std::to_string(totalUpdates);
+        config["runIdx"] = std::to_string(runIdx);
+        config["w2l_data_rng.0"] = rs.str();
+        if (saug) config["w2l_saug_calls"] = std::to_string(saug->calls());
+        Serializer::save(getRunFile("model_" + clean + ".bin", runIdx, runPath), "0.1", config, network, criterion, netoptim, critoptim);
+      }
     };
 
     // ---- the hot loop (Train.cpp:1454-1804)
@@ -769,7 +914,10 @@ int main(int argc, char** argv) {
       framesTotal += (long)curB * curT;
       ++nbatches;
 
-      if (isMaster && ((reportiters > 0 && curBatch % reportiters == 0) || curBatch == iters)) logStatus(curEpoch, curBatch, lr, lrcrit);
+      const bool report = (reportiters > 0 && curBatch % reportiters == 0) || curBatch == iters;
+      if (report) runValid();   // on every rank (the sums are all-reduced), before the log line that carries them
+      if (isMaster && report) logStatus(curEpoch, curBatch, lr, lrcrit);
+      if (report) saveBestValid(curEpoch, curBatch);
       if (reportiters > 0 && curBatch % reportiters == 0) {
         // every report starts the next readings afresh (resetTimeStatMeters + the train meters, Train.cpp:1081-1090, :1125-1131,
         // :1844-1847): a report's timers are those of its own window, not of the run so far

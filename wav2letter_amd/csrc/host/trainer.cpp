@@ -47,7 +47,20 @@ struct Trainer {
                                  // in bf16 (fp32 accumulate, fp32 storage, fp32 master weights); convolutions, LayerNorm, the
                                  // criterion and the optimizer stay fp32
   std::vector<hipEvent_t> bucketEvents;  // owned (w2l_trainer_set_grad_buckets)
-  ~Trainer() { for (auto e : bucketEvents) (void)hipEventDestroy(e); }
+  // w2l_trainer_evaluate's loss [B], path [B][T'] and criterion score workspace, apart from every buffer a training step reads
+  // or writes: the caller's (w2l_trainer_bind_eval) or, when none is bound, owned and grown on demand
+  void* evalMem = nullptr;
+  size_t evalBytes = 0;
+  void* evalBound = nullptr;
+  size_t evalBoundBytes = 0;
+  size_t evalNeed() const {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    return up(sizeof(float) * B) + up(sizeof(int) * (size_t)B * Tout) + up(crit->scoreWorkspaceBytes(B, Tout, nLabel, L));
+  }
+  ~Trainer() {
+    for (auto e : bucketEvents) (void)hipEventDestroy(e);
+    if (evalMem) (void)hipFree(evalMem);
+  }
 };
 
 }  // namespace w2l
@@ -277,6 +290,50 @@ W2L_API int w2l_trainer_update(void* h, float lr, float lrcrit, float momentum, 
     stepOne(t->netOptim, 0, t->netFloats, lr, momentum, maxGradNorm, "network optimizer");
     t->step++;
   });
+}
+
+// eval-mode network forward (no dropout) + the criterion's score on the planned shape.  Advances no counter: the dropout seed of
+// the next training step comes from the update count alone (makeCtx), and the criterion scores on a workspace of its own.
+static void evaluateImpl(Trainer* t, const float* x, const int* target, float** lossDev, int** pathDev, void* stream) {
+  if (!x || !target) throw std::invalid_argument("evaluate: null input");
+  Ctx c = makeCtx(t, stream, false);
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  const size_t lossBytes = up(sizeof(float) * t->B), pathBytes = up(sizeof(int) * (size_t)t->B * t->Tout);
+  const size_t need = t->evalNeed();
+  char* mem = (char*)t->evalBound;
+  if (mem && t->evalBoundBytes < need) throw std::invalid_argument("evaluate: the bound buffer is smaller than w2l_trainer_eval_bytes");
+  if (!mem) {
+    if (need > t->evalBytes) {
+      if (t->evalMem) { hipCheck(hipFree(t->evalMem), "evaluate buffers"); t->evalMem = nullptr; t->evalBytes = 0; }
+      hipCheck(hipMalloc(&t->evalMem, need), "evaluate buffers");
+      t->evalBytes = need;
+    }
+    mem = (char*)t->evalMem;
+  }
+  float* loss = (float*)mem;
+  int* path = (int*)(mem + lossBytes);
+  void* ws = mem + lossBytes + pathBytes;
+  const float* em;
+  { MatmulMode mm(t->mixedPrecision); em = t->net->forward(c, t->arena, x); }
+  t->crit->score(c, t->B, t->Tout, t->nLabel, t->L, em, target, loss, path, ws, t->params + t->netFloats);
+  if (lossDev) *lossDev = loss;
+  if (pathDev) *pathDev = path;
+}
+W2L_API int w2l_trainer_evaluate(void* h, const float* x, const int* target, float** lossDev, int** pathDev, void* stream) {
+  TRY(h, evaluateImpl((Trainer*)h, x, target, lossDev, pathDev, stream));
+}
+
+// bytes of the buffer w2l_trainer_evaluate needs on the planned shape; w2l_trainer_bind_eval hands one over (null: the trainer's own)
+W2L_API size_t w2l_trainer_eval_bytes(void* h) {
+  Trainer* t = (Trainer*)h;
+  return (t && t->arenaFloats) ? t->evalNeed() : 0;
+}
+W2L_API int w2l_trainer_bind_eval(void* h, void* mem, size_t bytes) {
+  if (!h || (mem && !bytes)) return W2L_EINVAL;
+  Trainer* t = (Trainer*)h;
+  t->evalBound = mem;
+  t->evalBoundBytes = mem ? bytes : 0;
+  return W2L_OK;
 }
 
 W2L_API int w2l_trainer_viterbi(void* h, const float* emission, int* path, void* stream) {

@@ -185,6 +185,15 @@ class SequenceCriterion {
                         float* critGrads) = 0;
   virtual void viterbiPath(Ctx& c, int B, int T, int N, const float* emission, int* path, void* ws,
                            float* critParams) = 0;
+  // evaluation of a held-out batch: loss [B] (as forward) and path [B][T] (as viterbiPath), no gradient.  ws: a workspace of
+  // scoreWorkspaceBytes of its own -- never the training workspace, so a score between two training steps leaves them alone.
+  // Default: forward followed by viterbiPath on that workspace.
+  virtual size_t scoreWorkspaceBytes(int B, int T, int N, int L) const { return workspaceBytes(B, T, N, L); }
+  virtual void score(Ctx& c, int B, int T, int N, int L, const float* emission, const int* target, float* loss, int* path,
+                     void* ws, float* critParams) {
+    forward(c, B, T, N, L, emission, target, loss, ws, critParams);
+    viterbiPath(c, B, T, N, emission, path, ws, critParams);
+  }
 };
 std::shared_ptr<SequenceCriterion> makeCTCLoss(int scaleMode);
 std::shared_ptr<SequenceCriterion> makeASGLoss(int N, int scaleMode, double transdiag);

@@ -40,6 +40,10 @@ def _lib_tr():
         L.w2l_trainer_backward.argtypes = [vp, vp, vp]
         L.w2l_trainer_update.argtypes = [vp, f, f, f, f, f, i, vp]
         L.w2l_trainer_viterbi.argtypes = [vp, vp, vp, vp]
+        L.w2l_trainer_evaluate.argtypes = [vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
+        L.w2l_trainer_eval_bytes.restype = sz
+        L.w2l_trainer_eval_bytes.argtypes = [vp]
+        L.w2l_trainer_bind_eval.argtypes = [vp, vp, sz]
         L.w2l_trainer_set_step.argtypes = [vp, u32]
         L.w2l_trainer_set_mixed_precision.argtypes = [vp, i]
         L.w2l_trainer_set_optimizer.argtypes = [vp, i, i]
@@ -77,11 +81,52 @@ def flags_check(flags_text):
     return n.value
 
 
+class _EvalPlan:
+    """a second C trainer over the same arch and criterion, planned for one evaluation shape: its own activation arena and
+    evaluation buffer, the training trainer's parameter arena (bound per call).  The training plan is never re-planned."""
+
+    def __init__(self, ctor, B, T, Lt, device):
+        L = _lib_tr()
+        self.L = L
+        arch_text, nfeat, nlabel, criterion, scalemode, transdiag = ctor
+        self.h = L.w2l_trainer_create(arch_text.encode(), nfeat, nlabel, criterion.encode(), int(scalemode), float(transdiag))
+        if not self.h:
+            raise _lib.W2LInvalidArgument(L.w2l_host_last_error().decode())
+        af, cw, to = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+        _check(L.w2l_trainer_plan(self.h, B, T, Lt, C.byref(af), C.byref(cw), C.byref(to)), "evaluate plan")
+        self.Tout = to.value
+        self.arena = torch.empty(af.value, dtype=torch.float32, device=device)
+        self.crit_ws = torch.empty(256, dtype=torch.uint8, device=device)   # (bind needs one; evaluation scores in eval_buf)
+        self.eval_buf = None
+
+    def bind(self, params, grads_full, mom, mixed):
+        _check(self.L.w2l_trainer_bind(self.h, params.data_ptr(), grads_full.data_ptr(), mom.data_ptr() if mom is not None else None,
+                                       self.arena.data_ptr(), self.crit_ws.data_ptr()), "evaluate bind")
+        if self.eval_buf is None:
+            self.eval_buf = torch.empty(max(int(self.L.w2l_trainer_eval_bytes(self.h)), 256), dtype=torch.uint8,
+                                        device=self.arena.device)
+            _check(self.L.w2l_trainer_bind_eval(self.h, self.eval_buf.data_ptr(), self.eval_buf.numel()), "bind_eval")
+        _check(self.L.w2l_trainer_set_mixed_precision(self.h, int(mixed)), "mixed precision")
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.L.w2l_trainer_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
 class Trainer:
+    _EVAL_PLANS = 4   # evaluation shapes kept planned (least recently used dropped)
+
     def __init__(self, arch_text, nfeat, nlabel, criterion="ctc", scalemode=CriterionScaleMode.NONE,
                  transdiag=0.0, device="cuda"):
         L = _lib_tr()
         self.L = L
+        self._ctor = (arch_text, nfeat, nlabel, criterion, scalemode, transdiag)
+        self._eval_plans = {}
+        self._mixed = False
         self.h = L.w2l_trainer_create(arch_text.encode(), nfeat, nlabel, criterion.encode(), int(scalemode),
                                       float(transdiag))
         if not self.h:
@@ -213,6 +258,42 @@ class Trainer:
         _check(self.L.w2l_trainer_update(self.h, lr, lrcrit, momentum, max_grad_norm, tb, int(clamp_crit),
                                          self._stream()), "update")
 
+    def evaluate(self, x, target, input_sizes=None):
+        """Scores a held-out batch: eval-mode forward (no dropout) and the criterion's loss and Viterbi path in one call
+        (w2l_trainer_evaluate; CTC reads the emissions once).  x: [B][NFEAT][T] float32, target: [B][L] int32 (-1 padded), any
+        B / T / L: each shape gets an evaluation plan of its own (a second trainer on the same parameters, a few kept), so the
+        training plan, its arenas and the dropout seed of the next step are left as they were.  input_sizes: optional float32
+        [B], as set_input_sizes.  Returns (loss [B] float32, path [B][T'] int32): views of that plan's evaluation buffer,
+        overwritten by the next evaluate() of the same shape (not by training steps) -- clone them to keep them."""
+        if self.params is None:
+            raise _lib.W2LInvalidArgument("evaluate: no parameters on the device (to_device() first)")
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 3
+                and x.shape[1] == self.nfeat):
+            raise _lib.W2LInvalidArgument(f"evaluate: input must be a contiguous float32 CUDA tensor [B][NFEAT={self.nfeat}][T]")
+        B, T = int(x.shape[0]), int(x.shape[2])
+        if not (torch.is_tensor(target) and target.is_cuda and target.dtype == torch.int32 and target.is_contiguous()
+                and target.dim() == 2 and target.shape[0] == B):
+            raise _lib.W2LInvalidArgument(f"evaluate: target must be a contiguous int32 CUDA tensor [B={B}][L]")
+        key = (B, T, int(target.shape[1]))
+        ev = self._eval_plans.pop(key, None)
+        if ev is None:
+            ev = _EvalPlan(self._ctor, *key, self.device)
+            while len(self._eval_plans) >= self._EVAL_PLANS:
+                self._eval_plans.pop(next(iter(self._eval_plans)))
+        self._eval_plans[key] = ev
+        ev.bind(self.params, self.grads_full, self.mom, self._mixed)
+        if input_sizes is not None and not (torch.is_tensor(input_sizes) and input_sizes.dtype == torch.float32
+                                            and input_sizes.is_cuda and input_sizes.is_contiguous() and input_sizes.numel() == B):
+            raise ValueError("input sizes: contiguous float32 CUDA tensor of B elements")
+        _check(self.L.w2l_trainer_set_input_sizes(ev.h, input_sizes.data_ptr() if input_sizes is not None else None), "set_input_sizes")
+        lp, pp = C.c_void_p(0), C.c_void_p(0)
+        _check(self.L.w2l_trainer_evaluate(ev.h, x.data_ptr(), target.data_ptr(), C.byref(lp), C.byref(pp), self._stream()),
+               "evaluate")
+        base = ev.eval_buf.data_ptr()
+        loss = ev.eval_buf[lp.value - base:lp.value - base + 4 * B].view(torch.float32)
+        path = ev.eval_buf[pp.value - base:pp.value - base + 4 * B * ev.Tout].view(torch.int32).view(B, ev.Tout)
+        return loss, path
+
     def viterbi(self, emission):
         path = torch.empty(self.B, self.Tout, dtype=torch.int32, device=self.device)
         _check(self.L.w2l_trainer_viterbi(self.h, emission.data_ptr(), path.data_ptr(), self._stream()), "viterbi")
@@ -233,6 +314,7 @@ class Trainer:
     def set_mixed_precision(self, on=True):
         """bf16 multiplies (fp32 accumulate / storage / master weights) in the network's fl::Linear GEMMs"""
         _check(self.L.w2l_trainer_set_mixed_precision(self.h, int(bool(on))), "mixed precision")
+        self._mixed = bool(on)
 
     def set_optimizer(self, netoptim="sgd", critoptim="sgd"):
         """--netoptim / --critoptim of the reference Trainer (Train.cpp:577-582): "sgd" (momentum) "adagrad" or "adadelta" (rho 0.9, eps 1e-8:
