@@ -1353,6 +1353,31 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert not any(l.startswith("{") for l in out.stdout.splitlines())
 
 
+def test_bench_plain_run_is_the_headline_only():
+    """`python bench.py` without --full times the headline step and prints its line, and runs none of the legs that take
+    runs of their own (those come with --full)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--batch", "2",
+                          "--frames", "800"], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert (r["metric"], r["unit"], r["higher_is_better"], r["dtype"]) == ("utterances/sec", "utterances/sec", True, "f32")
+    assert (r["steps"], r["warmup"], r["config"]["global_batch"]) == (1, 1, 2)
+    assert r["value"] > 0 and r["ms_per_step"] > 0
+    assert abs(r["value"] - 2 * 1e3 / r["ms_per_step"]) < 1e-2 * r["value"]
+    legs = {"input_pipeline", "train_binary_config2", "asg_loss_ms_per_step", "ctc_loss_ms_per_step", "asg_stress",
+            "conv_glu_asg_step", "streaming_tds_bf16_step", "transformer_ctc_step", "cpu_baseline"}
+    assert not legs & set(r), sorted(legs & set(r))
+    assert "] leg " not in out.stderr
+
+
 def test_mixed_precision_streaming_tds_step(oracle):
     """BASELINE config 3 (streaming_convnets am_500ms_future_context.arch: asymmetric padding, per-frame LayerNorm, TDS
     blocks with 15 / 19 / 23 / 27 channels, 115.1 M parameters), reduced batch / frames, dropout and SpecAugment off:

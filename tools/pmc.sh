@@ -1,8 +1,8 @@
 #!/bin/bash
-# usage: tools/pmc.sh <tag> "<counters>" <python args...>  -> gpurun_out/<tag>_pmc.csv  (counter pass only: no tracing flags)
+# usage: tools/pmc.sh <tag> "<counters>" <python args...>  -> $EVIDENCE_DIR/<tag>_pmc.csv  (counter pass only: no tracing flags; default: evidence/)
 tag=$1; shift; ctr=$1; shift
 export TMPDIR=/tmp
-out=$PWD/gpurun_out
+out=$(realpath -m "${EVIDENCE_DIR:-evidence}")
 root=$PWD
 script=$root/$1; shift
 export PYTHONPATH=$root:$PYTHONPATH
