@@ -1591,8 +1591,8 @@ def test_linseg_phase_has_its_own_momentum():
 
 # ---- the mixed-precision TDS block across geometries ------------------------------------------------------------------------
 # One block alone (the `V / TDS / RO / V / V` network of teacher_forced_tds_blocks), random input and output gradient, each case
-# at a geometry meant to reach one branch of TDSLayer's choice between the bf16 operators (host/net.cpp; launch128h's refusal
-# conditions in gemm_bf16g.hpp).  Line: TDS c kw h dropout l2 rPad lnIncludeTime.
+# at a geometry meant to reach one branch of the choice TDSLayer and its FeedForward pair make between the bf16 operators
+# (host/net.cpp; launch128h's refusal conditions in gemm_bf16g.hpp).  Line: TDS c kw h dropout l2 rPad lnIncludeTime.
 TDS_BF16_CASES = [
     # config 2's block (sota TDS-CTC), reduced B / T: time-wise LayerNorm, so y1's rows are not the LayerNorm's groups -- no LN
     # images, y1 joins the weights' w2l_bf16_convert_multi and gets its ones row from ensureOnes; c = 10, kw = 21 at 80 rows:
@@ -1608,8 +1608,8 @@ TDS_BF16_CASES = [
     pytest.param("TDS 8 9 10 0.0 0 -1 1", 2, 20, id="conv-fp32-h10"),
     # c = 40 > 32 at h = 16: convImgElems == 0 as well
     pytest.param("TDS 40 5 16 0.0 0", 2, 16, id="conv-fp32-c40"),
-    # l = 15 (l % 4 != 0), l2 = 16: lin1 writes u as images only (uOnlyImages); y1's images, the backward-data product of lin1 and
-    # the fp32 du all have rows of 15; h = 3 keeps the convolution fp32
+    # l = 15 (l % 4 != 0), l2 = 16: lin1 writes u as images only (FeedForward::uOnlyImages); y1's images, the backward-data
+    # product of lin1 and the fp32 du all have rows of 15; h = 3 keeps the convolution fp32
     pytest.param("TDS 5 3 3 0.0 16", 2, 16, id="l15-l2-16"),
     # l2 = 30 (l2 % 4 != 0): lin1's image epilogue refuses -> fp32 u + conversion; lin2's backward-data with the fp32 mask
     pytest.param("TDS 8 9 16 0.0 30", 2, 16, id="l2-30-fp32-u"),
@@ -1691,7 +1691,7 @@ def test_tds_block_bf16_geometries_against_bf16_operand_oracle(oracle, line, B, 
 
 # ---- the mixed-precision Transformer block across geometries ----------------------------------------------------------------
 TR_BF16_CASES = [
-    # mlp = 70 (% 4 != 0): lin1's image epilogue refuses -> fp32 u + conversion (TransformerLayer's uOnlyImages false)
+    # mlp = 70 (% 4 != 0): lin1's image epilogue refuses -> fp32 u + conversion (FeedForward::uOnlyImages false)
     pytest.param("TR 64 70 4 8", 2, 40, None, id="mlp70"),
     # mlp = 100 (% 4 == 0, % 32 != 0): the image epilogue at a non-tile-multiple N
     pytest.param("TR 64 100 4 8", 2, 40, None, id="mlp100"),

@@ -372,6 +372,84 @@ struct BfLinear {   // the weight images of one fl::Linear(in, out) and its thre
   }
 };
 
+// The feed-forward pair that fl::TDSBlock and fl::Transformer share, on M frames; x [M][in] is the block's first LayerNorm output:
+//   u  = dropout(relu(x W1 + b1))      lin1 (in -> hidden)
+//   r2 = dropout(u W2 + b2) + x        lin2 (hidden -> in) with the residual join
+// The layer registers the four parameters, converts the weight images bl1.w / bl2.w and owns the images of x and of lin2's output gradient.
+struct FeedForward {
+  const char* who = "";          // error text prefix
+  const P *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;   // the layer's handles
+  bool joinInLin2 = true;        // fp32: the residual join rides in lin2's epilogue (forward() reports it)
+  bool biasWithWeight = false;   // fp32: bias gradients out of w2l_linear_backward_weight_bias, not w2l_colsum (another summation order)
+  int M = 0, in = 0, hidden = 0;
+  size_t uOff = 0, duOff = 0;
+  BfLinear bl1, bl2;             // mixed precision: lin1, lin2
+  BfImage uImg, duImg;           // images of lin2's input and of lin1's output gradient
+  bool uOnlyImages = false;      // mixed precision, this step: u exists only as uImg (set by forward, read by backward)
+  void plan(Planner& pl, const char* who_, int M_, int in_, int hidden_, const P& w1_, const P& b1_, const P& w2_, const P& b2_) {
+    who = who_; M = M_; in = in_; hidden = hidden_; w1 = &w1_; b1 = &b1_; w2 = &w2_; b2 = &b2_;
+    uOff = pl.alloc((size_t)M * hidden); duOff = pl.alloc((size_t)M * hidden);
+    bl1.plan(pl, M, in, hidden); bl2.plan(pl, M, hidden, in);
+    uImg.plan(pl, M, hidden, true); duImg.plan(pl, M, hidden);
+  }
+  std::string tag(const char* what) const { return std::string(who) + " " + what; }
+  void check(int st, const char* what) const { if (st != W2L_OK) w2lCheck(st, tag(what).c_str()); }
+  // lin2's bias gradient comes out of its weight-gradient product (mixed precision)
+  bool lin2BiasRides(Ctx& cx) const { return bl2.biasRides(uImg, w2->g(cx), b2->g(cx)); }
+  // out = r2.  Dropout p with the step's seed, lin1's mask on `stream` and lin2's on stream + 1 (p == 0: no launch reads either).
+  // xImg: the images of x (mixed precision).  false: fp32 without joinInLin2, out = u W2 + b2 -- dropout and join are the caller's
+  bool forward(Ctx& cx, float* ar, const float* x, const BfImage& xImg, float* out, double p, uint32_t stream) {
+    float* u = ar + uOff;
+    if (cx.bf16) {
+      // u is only ever an operand of lin2's products and the mask of lin2's backward-data product: it lives ONLY as its two bf16
+      // images, written by lin1's epilogue (uOnlyImages; where that epilogue cannot run: fp32 u + conversion)
+      uOnlyImages = bl1.forwardImages(cx, ar, xImg, b1->w(cx), uImg, 1, p, cx.seed, stream);
+      if (!uOnlyImages) {
+        bl1.forward(cx, ar, xImg, b1->w(cx), u, 1, p, cx.seed, stream);
+        uImg.convert(cx, ar, u, tag("u images").c_str());
+      }
+      bl2.forwardAdd(cx, ar, uImg, b2->w(cx), x, out, p, cx.seed, stream + 1);
+      return true;
+    }
+    // ReLU, dropout and the join in the GEMM epilogues: the same mask bits as dropout passes over u and over lin2's output
+    if (p > 0) check(w2l_linear_forward_dropout(M, in, hidden, x, w1->w(cx), b1->w(cx), u, 1, p, cx.seed, stream, cx.stream), "lin1+do");
+    else check(w2l_linear_forward(M, in, hidden, x, w1->w(cx), b1->w(cx), u, 1, cx.stream), "lin1");
+    if (joinInLin2) check(w2l_linear_forward_dropout_add(M, hidden, in, u, w2->w(cx), b2->w(cx), x, out, 0, p, cx.seed, stream + 1, cx.stream), "lin2+do+res");
+    else check(w2l_linear_forward(M, hidden, in, u, w2->w(cx), b2->w(cx), out, 0, cx.stream), "lin2");
+    return joinInLin2;
+  }
+  // dw = a^T g of the Linear bl, and db = the column sums of g: out of the same launch (`rides`) or by w2l_colsum behind it
+  void weightGrad(Ctx& cx, float* ar, const BfLinear& bl, const float* a, const BfImage& aImg, const float* g, const BfImage& gImg, const P& w, const P& b,
+                  bool rides) const {
+    if (cx.bf16) bl.backwardWeight(cx, ar, aImg, gImg, w.g(cx), rides);
+    else if (rides) check(w2l_linear_backward_weight_bias(M, bl.in, bl.out, a, g, w.g(cx), b.g(cx), cx.stream), "bwd w + b");
+    else check(w2l_linear_backward_weight(M, bl.in, bl.out, a, g, w.g(cx), cx.stream), "bwd w");
+    if (!rides) check(w2l_colsum(g, b.g(cx), (size_t)M, bl.out, cx.stream), "bwd b");
+  }
+  // dy [M][in]: the gradient of lin2's output, its dropout mask applied (dyImg: its images, mixed precision).  Writes the four parameter
+  // gradients and dx = addend + du W1^T, addend the gradient that the residual join carries.  p: forward's
+  void backward(Ctx& cx, float* ar, const float* x, const BfImage& xImg, const float* dy, const BfImage& dyImg, const float* addend, float* dx, double p) {
+    const bool mixed = cx.bf16;
+    const bool rides2 = mixed ? lin2BiasRides(cx) : biasWithWeight, rides1 = mixed ? bl1.biasRides(xImg, w1->g(cx), b1->g(cx)) : biasWithWeight;
+    const float sc = (float)(1.0 / (1.0 - p));   // of forward's dropout mask
+    float *u = ar + uOff, *du = ar + duOff;
+    weightGrad(cx, ar, bl2, u, uImg, dy, dyImg, *w2, *b2, rides2);
+    // du = (dy W2^T) masked by relu + dropout of u (u holds the dropped value).  With u as images only: the mask from its row image, and
+    // du itself -- only ever an operand of lin1's backward products once its bias gradient rides on one of them -- leaves as images only
+    if (!mixed) {
+      check(w2l_linear_backward_data(M, hidden, in, dy, w2->w(cx), du, 0, u, sc, cx.stream), "lin2 bwd x");
+    } else if (!(uOnlyImages && bl2.backwardDataImages(cx, ar, dyImg, rides1 ? nullptr : du, &duImg, uImg, sc))) {
+      if (uOnlyImages) throw std::runtime_error(tag("u was kept as images only, but the image-writing backward-data product refused"));
+      bl2.backwardData(cx, ar, dyImg, du, u, sc, nullptr, 0);
+      duImg.convert(cx, ar, du, tag("du images").c_str());
+    }
+    weightGrad(cx, ar, bl1, x, xImg, du, duImg, *w1, *b1, rides1);
+    // the residual join rides in the GEMM epilogue as a separate addend (no copy of it into dx)
+    if (mixed) bl1.backwardData(cx, ar, duImg, dx, nullptr, 1.f, addend, 0);
+    else check(w2l_linear_backward_data_add(M, in, hidden, du, w1->w(cx), addend, dx, cx.stream), "lin1 bwd x");
+  }
+};
+
 // LayerNorm of the mixed-precision mode: where the normalised rows are the rows of the next product's operand (`img` non-null,
 // rows of at most 2304 floats) the images come out of the LayerNorm kernel itself (layernorm_images.hip) -- returns true then;
 // otherwise the plain kernels run and the caller converts.
@@ -748,12 +826,11 @@ class TDSLayer : public Layer {
   w2l_conv_desc d{};
   int B = 0, T = 0, M = 0, groups = 0;
   size_t inner = 0, n = 0;
-  size_t aOff, r1Off, y1Off, uOff, vOff, outOff, st1Off, mr1Off, st2Off, mr2Off;   // forward (r2 aliases v)
-  size_t dsOff, duOff, dy1Off, dr1Off, daOff, dxOff;                        // backward
+  size_t aOff, r1Off, y1Off, vOff, outOff, st1Off, mr1Off, st2Off, mr2Off;   // forward (r2 aliases v)
+  size_t dsOff, dy1Off, dr1Off, daOff, dxOff;                               // backward
   const float* xSaved = nullptr;
-  bool uOnlyImages = false;             // mixed precision, this step: u exists only as uImg (set by forward, read by backward)
-  BfLinear bl1, bl2;                    // mixed precision: lin1 (l -> l2), lin2 (l2 -> l)
-  BfImage y1Img, uImg, dvImg, duImg;    // images of the two Linear inputs and of the two output gradients
+  FeedForward ff;                       // lin1 (l -> l2), lin2 (l2 -> l)
+  BfImage y1Img, dvImg;                 // mixed precision: images of lin1's input and of lin2's output gradient
   size_t convImgElems = 0, convImgFOff = 0, convImgBOff = 0;   // bf16 weight images of the convolution (0: fp32 kernels only)
 
   std::string name() const override { return "TDSBlock"; }
@@ -784,13 +861,18 @@ class TDSLayer : public Layer {
     groups = lnTime ? B : B * T;
     inner = n / groups;
     if (inner % 4) throw std::invalid_argument("TDSBlock: LayerNorm size must be a multiple of 4");
-    aOff = pl.alloc(n); r1Off = pl.alloc(n); y1Off = pl.alloc(n); uOff = pl.alloc((size_t)M * l2); vOff = pl.alloc(n); outOff = pl.alloc(n);
+    aOff = pl.alloc(n); r1Off = pl.alloc(n); y1Off = pl.alloc(n); vOff = pl.alloc(n); outOff = pl.alloc(n);
     st1Off = pl.alloc(2 * w2l_layernorm_scratch_doubles(groups, inner)); mr1Off = pl.alloc(2 * (size_t)groups);
     st2Off = pl.alloc(2 * w2l_layernorm_scratch_doubles(groups, inner)); mr2Off = pl.alloc(2 * (size_t)groups);
-    dsOff = pl.alloc(n); duOff = pl.alloc((size_t)M * l2); dy1Off = pl.alloc(n); dr1Off = pl.alloc(n);
-    daOff = pl.alloc(n); dxOff = pl.alloc(n);
-    bl1.plan(pl, M, l, l2); bl2.plan(pl, M, l2, l);
-    y1Img.plan(pl, M, l, true); uImg.plan(pl, M, l2, true); dvImg.plan(pl, M, l); duImg.plan(pl, M, l2);
+    dsOff = pl.alloc(n); dy1Off = pl.alloc(n); dr1Off = pl.alloc(n); daOff = pl.alloc(n); dxOff = pl.alloc(n);
+    // fp32 lin2 with the second dropout and the residual join in its epilogue, then a plain LayerNorm of r2: two tensor passes fewer than
+    // residual_layernorm(v, y1) behind a plain lin2.  Only where the product runs on the LDS-DMA kernels (l2 % 32 == 0: their epilogues fetch
+    // the addend ahead of the LDS turn); the register-staged kernel pays more for the addend than the LayerNorm saves (config 3 in fp32,
+    // l2 = 3600 ... 6480: profiles/r06_run24_c3_lin2_epilogue_ab.log).
+    ff.joinInLin2 = l2 % 32 == 0;
+    ff.biasWithWeight = true;   // the headline's fp32 bias gradients come out of the weight-gradient launch
+    ff.plan(pl, "tds", M, l, l2, w1, b1, w2, b2);
+    y1Img.plan(pl, M, l, true); dvImg.plan(pl, M, l);
     convImgElems = h % 16 == 0 ? w2l_tds_conv_bf16_image_elems(&d) : 0;
     if (convImgElems) { convImgFOff = pl.allocBf16(convImgElems); convImgBOff = pl.allocBf16(convImgElems); }
     return in;
@@ -799,7 +881,7 @@ class TDSLayer : public Layer {
     hipStream_t s = cx.stream;
     const double pd = cx.train ? p : 0.0;
     xSaved = x;
-    float *a = ar + aOff, *r1 = ar + r1Off, *y1 = ar + y1Off, *u = ar + uOff, *v = ar + vOff, *out = ar + outOff;
+    float *a = ar + aOff, *r1 = ar + r1Off, *y1 = ar + y1Off, *v = ar + vOff, *out = ar + outOff;
     if (cx.bf16 && convImgElems) {   // bf16 operands, fp32 accumulation / bias / ReLU (conv_tds_bf16.hip); images once per step
       w2lCheck(w2l_tds_conv_bf16_prepare(&d, wc.w(cx), bfp(ar, convImgFOff), bfp(ar, convImgBOff), s), "tds conv images");
       w2lCheck(w2l_tds_conv_bf16_forward(&d, x, bfp(ar, convImgFOff), bc.w(cx), a, 1, s), "tds conv bf16");
@@ -810,61 +892,27 @@ class TDSLayer : public Layer {
     const bool y1Images = lnForward(cx, ar, groups, inner, a, x, r1, y1, gb1.w(cx), pd, cx.seed, rngStream, (double*)(ar + st1Off), ar + mr1Off,
                                     cx.bf16 ? &y1Img : nullptr, "tds ln1");
     if (cx.bf16) {
-      // the same two products on bf16 images: y1 and u as images (row image for this product, transposed image for the weight
-      // gradient in backward), the weights once per step (both orientations).  y1's images come out of the LayerNorm kernel when
-      // it normalises per frame; otherwise y1 joins the weights' conversion launch (10 us each on their own: launch-bound)
-      if (y1Images) {
-        const w2l_bf16_convert_desc wd[2] = {bl1.w.desc(ar, w1.w(cx)), bl2.w.desc(ar, w2.w(cx))};
-        w2lCheck(w2l_bf16_convert_multi(2, wd, s), "tds weight images");
-      } else {
-        const w2l_bf16_convert_desc wd[3] = {y1Img.desc(ar, y1), bl1.w.desc(ar, w1.w(cx)), bl2.w.desc(ar, w2.w(cx))};
-        w2lCheck(w2l_bf16_convert_multi(3, wd, s), "tds y1 + weight images");
-        y1Img.ensureOnes(cx, ar);
-      }
-      // u = dropout(relu(lin1(y1))) is only ever an operand of lin2's products and the mask of lin2's backward-data product: it lives
-      // ONLY as its two bf16 images, written by lin1's epilogue (uOnlyImages; where that epilogue cannot run: fp32 u + conversion)
-      uOnlyImages = bl1.forwardImages(cx, ar, y1Img, b1.w(cx), uImg, 1, pd, cx.seed, rngStream + 1);
-      if (!uOnlyImages) {
-        bl1.forward(cx, ar, y1Img, b1.w(cx), u, 1, pd, cx.seed, rngStream + 1);
-        uImg.convert(cx, ar, u, "tds u images");
-      }
-      // (as in the fp32 branch below: second dropout + residual join in lin2's epilogue, a plain LayerNorm behind it)
-      bl2.forwardAdd(cx, ar, uImg, b2.w(cx), y1, v, pd, cx.seed, rngStream + 2);
-      w2lCheck(w2l_residual_layernorm_forward(groups, inner, v, nullptr, v, out, gb2.w(cx), 1e-5f, 0.0, 0, 0,
-                                              (double*)(ar + st2Off), ar + mr2Off, s), "tds ln2");
-      y = out;
-      return;
-    } else {
-    // lin1 + ReLU + dropout in one GEMM epilogue (same mask bits as a separate dropout pass over u)
-    if (pd > 0) w2lCheck(w2l_linear_forward_dropout(M, l, l2, y1, w1.w(cx), b1.w(cx), u, 1, pd, cx.seed, rngStream + 1, s), "tds lin1+do");
-    else w2lCheck(w2l_linear_forward(M, l, l2, y1, w1.w(cx), b1.w(cx), u, 1, s), "tds lin1");
-    // lin2 with the second dropout and the residual join in its epilogue: v <- r2 = dropout(lin2(u)) + y1 (the same mask bits as a
-    // dropout pass over v: backward re-derives them from the hash), then a plain LayerNorm of r2 -- two tensor passes fewer than
-    // residual_layernorm(v, y1) behind a plain lin2.  Where the product runs on the LDS-DMA kernels (l2 % 32 == 0: their epilogues
-    // fetch the addend ahead of the LDS turn); the register-staged kernel pays more for the addend than the LayerNorm saves
-    // (config 3 in fp32, l2 = 3600 ... 6480: profiles/r06_run24_c3_lin2_epilogue_ab.log).
-    if (l2 % 32 == 0) {
-    w2lCheck(w2l_linear_forward_dropout_add(M, l2, l, u, w2.w(cx), b2.w(cx), y1, v, 0, pd, cx.seed, rngStream + 2, s), "tds lin2+do+res");
-    w2lCheck(w2l_residual_layernorm_forward(groups, inner, v, nullptr, v, out, gb2.w(cx), 1e-5f, 0.0, 0, 0,
-                                            (double*)(ar + st2Off), ar + mr2Off, s), "tds ln2");
-    y = out;
-    return;
+      // the two products on bf16 images: y1 as images (row image for lin1's product, transposed image for the weight gradient in
+      // backward), the weights once per step (both orientations).  y1's images come out of the LayerNorm kernel when it normalises
+      // per frame; otherwise y1 joins the weights' conversion launch (10 us each on their own: launch-bound)
+      const w2l_bf16_convert_desc wd[3] = {y1Img.desc(ar, y1), ff.bl1.w.desc(ar, w1.w(cx)), ff.bl2.w.desc(ar, w2.w(cx))};
+      w2lCheck(w2l_bf16_convert_multi(y1Images ? 2 : 3, wd + (y1Images ? 1 : 0), s), "tds y1 + weight images");
+      if (!y1Images) y1Img.ensureOnes(cx, ar);
     }
-    w2lCheck(w2l_linear_forward(M, l2, l, u, w2.w(cx), b2.w(cx), v, 0, s), "tds lin2");
-    }
-    // r2 = dropout(v) + y1 (stored over v), out = LN(r2)
-    w2lCheck(w2l_residual_layernorm_forward(groups, inner, v, y1, v, out, gb2.w(cx), 1e-5f, pd, cx.seed, rngStream + 2,
-                                            (double*)(ar + st2Off), ar + mr2Off, s), "tds ln2");
+    // v = r2 = dropout(lin2(u)) + y1 where lin2 joined; else v = lin2(u), and the LayerNorm kernel stores r2 over v.  out = LN(r2)
+    const bool joined = ff.forward(cx, ar, y1, y1Img, v, pd, rngStream + 1);
+    w2lCheck(w2l_residual_layernorm_forward(groups, inner, v, joined ? nullptr : y1, v, out, gb2.w(cx), 1e-5f, joined ? 0.0 : pd,
+                                            joined ? 0 : cx.seed, joined ? 0 : rngStream + 2, (double*)(ar + st2Off), ar + mr2Off, s), "tds ln2");
     y = out;
   }
   void backward(Ctx& cx, float* ar, const float* dy, float*& dx, bool needDx) override {
     hipStream_t s = cx.stream;
     const double pd = cx.train ? p : 0.0;
     const float sc = (float)(1.0 / (1.0 - pd));
-    float *a = ar + aOff, *y1 = ar + y1Off, *u = ar + uOff, *v = ar + vOff;
-    float *ds = ar + dsOff, *du = ar + duOff, *dy1 = ar + dy1Off, *dr1 = ar + dr1Off, *da = ar + daOff;
+    float *a = ar + aOff, *y1 = ar + y1Off, *v = ar + vOff;
+    float *ds = ar + dsOff, *dy1 = ar + dy1Off, *dr1 = ar + dr1Off, *da = ar + daOff;
     // LN2 backward: ds = d r2 ; dv = ds masked by the dropout of v
-    const bool rides2 = cx.bf16 && bl2.biasRides(uImg, w2.g(cx), b2.g(cx));
+    const bool rides2 = cx.bf16 && ff.lin2BiasRides(cx);
     // mixed precision with the bias gradient riding on the weight-gradient product: dv = dropout-masked ds is only ever a GEMM
     // operand -- its images are taken straight from ds with the mask applied on the way, no masked copy; where the LayerNorm
     // normalises per frame they come out of its backward kernel and there is no conversion launch either
@@ -878,33 +926,12 @@ class TDSLayer : public Layer {
       w2lCheck(w2l_dropout_copy(dy1, ds, n, pd, cx.seed, rngStream + 2, s), "tds do2 bwd");
       dv = dy1;
     }
-    if (cx.bf16) {
-      // (dv may live in dy1 -- the masked copy above --, which the last product overwrites: its images are taken first)
-      if (dvImages) {}
-      else if (maskInConvert) dvImg.convertDropout(cx, ar, ds, pd, cx.seed, rngStream + 2, "tds dv images (masked)");
+    if (cx.bf16 && !dvImages) {
+      // (dv may live in dy1 -- the masked copy above --, which the pair's last product overwrites: its images are taken first)
+      if (maskInConvert) dvImg.convertDropout(cx, ar, ds, pd, cx.seed, rngStream + 2, "tds dv images (masked)");
       else dvImg.convert(cx, ar, dv, "tds dv images");
-      bl2.backwardWeight(cx, ar, uImg, dvImg, w2.g(cx), rides2);
-      if (!rides2) w2lCheck(w2l_colsum(dv, b2.g(cx), (size_t)M, l, s), "tds lin2 bwd b");
-      // du = (dv W2^T) masked by u > 0: mask from u's bf16 image, and du itself -- an operand of lin1's two backward products and
-      // nothing else once its bias gradient rides on the weight-gradient product -- leaves only as its images
-      const bool rides1 = bl1.biasRides(y1Img, w1.g(cx), b1.g(cx));
-      if (!(uOnlyImages && bl2.backwardDataImages(cx, ar, dvImg, rides1 ? nullptr : du, &duImg, uImg, sc))) {
-        if (uOnlyImages) throw std::runtime_error("TDSBlock: u was kept as images only, but the image-writing backward-data product refused");
-        bl2.backwardData(cx, ar, dvImg, du, u, sc, nullptr, 0);
-        duImg.convert(cx, ar, du, "tds du images");
-      }
-      bl1.backwardWeight(cx, ar, y1Img, duImg, w1.g(cx), rides1);
-      if (!rides1) w2lCheck(w2l_colsum(du, b1.g(cx), (size_t)M, l2, s), "tds lin1 bwd b");
-      bl1.backwardData(cx, ar, duImg, dy1, nullptr, 1.f, ds, 0);
-    } else {
-    // lin2: dW2 = u^T dv, db2, du = (dv W2^T) masked by relu+dropout of u (u holds the dropped value)
-    w2lCheck(w2l_linear_backward_weight_bias(M, l2, l, u, dv, w2.g(cx), b2.g(cx), s), "tds lin2 bwd w + b");
-    w2lCheck(w2l_linear_backward_data(M, l2, l, dv, w2.w(cx), du, 0, u, sc, s), "tds lin2 bwd x");
-    // lin1: dW1 = y1^T du, db1, dy1 = ds + du W1^T
-    w2lCheck(w2l_linear_backward_weight_bias(M, l, l2, y1, du, w1.g(cx), b1.g(cx), s), "tds lin1 bwd w + b");
-    // dy1 = ds + du W1^T: the residual join rides in the GEMM epilogue as a separate addend (no copy of ds into dy1)
-    w2lCheck(w2l_linear_backward_data_add(M, l, l2, du, w1.w(cx), ds, dy1, s), "tds lin1 bwd x");
     }
+    ff.backward(cx, ar, y1, y1Img, dv, dvImg, ds, dy1, pd);   // lin2 and lin1: the four gradients, dy1 = ds + du W1^T
     // LN1 backward: dr1, and in the same pass da = dr1 masked by the ReLU+dropout pattern of a
     w2lCheck(w2l_layernorm_backward(groups, inner, ar + r1Off, dy1, gb1.w(cx), ar + mr1Off, dr1, gb1.g(cx), a, da, sc,
                                     (double*)(ar + st1Off), s), "tds ln1 bwd");
@@ -972,14 +999,15 @@ class TransformerLayer : public Layer {
   int d = 0;
   P pe, w1, b1, w2, b2, wq, bq, wk, bk, wv, bv, wf, bf, gb1, gb2;
   int B = 0, T = 0, M = 0, W = 0, rlo = 0, ldr = 0, n0 = 0;
-  size_t qOff, kOff, vOff, sOff, pdOff, rOff, ctxOff, oOff, hOff, uOff, m2Off, outOff, st1Off, mr1Off, st2Off, mr2Off;
-  size_t ds2Off, duOff, dhOff, dr1Off, dctxOff, dsOff, dRoff, dqOff, dkOff, dvOff, dxOff, dEpOff, klOff;
+  size_t qOff, kOff, vOff, sOff, pdOff, rOff, ctxOff, oOff, hOff, m2Off, outOff, st1Off, mr1Off, st2Off, mr2Off;
+  size_t ds2Off, dhOff, dr1Off, dctxOff, dsOff, dRoff, dqOff, dkOff, dvOff, dxOff, dEpOff, klOff;
   size_t abwOff = 0, abwBytes = 0;   // workspace of the fused attention backward (0: geometry without a fused kernel)
   const float* xSaved = nullptr;
-  bool dropped = false, fusedFwd = false, uOnlyImages = false;
-  // mixed precision: the six fl::Linear of the block on bf16 images (the attention products stay on the fp32 batched GEMM)
-  BfLinear blq, blk, blv, blf, bl1, bl2;
-  BfImage xImg, ctxImg, hImg, uImg, dqImg, dkImg, dvImg, dr1Img, duImg, ds2Img;
+  bool dropped = false, fusedFwd = false;
+  FeedForward ff;           // the mlp: w1 (C -> mlp), w2 (mlp -> C)
+  // mixed precision: the four projections of the block on bf16 images (the attention products stay on the fp32 batched GEMM)
+  BfLinear blq, blk, blv, blf;
+  BfImage xImg, ctxImg, hImg, dqImg, dkImg, dvImg, dr1Img, ds2Img;
   BfImage outImg;           // images of the block's output, written by its last LayerNorm: the next block's x images (Ctx::imgOf)
   BfImage xSeen;            // the images of x this step's products read: xImg, or the previous block's outImg
 
@@ -1022,11 +1050,11 @@ class TransformerLayer : public Layer {
     } else { rlo = W = ldr = 0; }
     const size_t n = (size_t)M * C, ns = (size_t)B * nH * T * T, nr = (size_t)M * nH * ldr;
     qOff = pl.alloc(n); kOff = pl.alloc(n); vOff = pl.alloc(n); sOff = pl.alloc(ns); pdOff = p > 0 ? pl.alloc(ns) : sOff;
-    rOff = pl.alloc(nr); ctxOff = pl.alloc(n); oOff = pl.alloc(n); hOff = pl.alloc(n); uOff = pl.alloc((size_t)M * mlp);
+    rOff = pl.alloc(nr); ctxOff = pl.alloc(n); oOff = pl.alloc(n); hOff = pl.alloc(n);
     m2Off = pl.alloc(n); outOff = pl.alloc(n);
     st1Off = pl.alloc(2 * w2l_layernorm_scratch_doubles(M, C)); mr1Off = pl.alloc(2 * (size_t)M);
     st2Off = pl.alloc(2 * w2l_layernorm_scratch_doubles(M, C)); mr2Off = pl.alloc(2 * (size_t)M);
-    ds2Off = pl.alloc(n); duOff = pl.alloc((size_t)M * mlp); dhOff = pl.alloc(n); dr1Off = pl.alloc(n); dctxOff = pl.alloc(n);
+    ds2Off = pl.alloc(n); dhOff = pl.alloc(n); dr1Off = pl.alloc(n); dctxOff = pl.alloc(n);
     dsOff = pl.alloc(ns); dRoff = pl.alloc(nr); dqOff = pl.alloc(n); dkOff = pl.alloc(n); dvOff = pl.alloc(n); dxOff = pl.alloc(n);
     dEpOff = pl.alloc((size_t)B * W * d);
     klOff = pl.alloc((size_t)B);
@@ -1035,9 +1063,11 @@ class TransformerLayer : public Layer {
       abwBytes = w2l_attn_fused_backward_workspace(&fd, csz > 0 ? 1 : 0);
       if (abwBytes) abwOff = pl.alloc((abwBytes + 3) / 4);   // (arena slots are 256-byte aligned: 64 floats)
     }
-    blq.plan(pl, M, C, C); blk.plan(pl, M, C, C); blv.plan(pl, M, C, C); blf.plan(pl, M, C, C); bl1.plan(pl, M, C, mlp); bl2.plan(pl, M, mlp, C);
-    xImg.plan(pl, M, C, true); ctxImg.plan(pl, M, C, true); hImg.plan(pl, M, C, true); uImg.plan(pl, M, mlp, true);
-    dqImg.plan(pl, M, C); dkImg.plan(pl, M, C); dvImg.plan(pl, M, C); dr1Img.plan(pl, M, C); duImg.plan(pl, M, mlp); ds2Img.plan(pl, M, C);
+    blq.plan(pl, M, C, C); blk.plan(pl, M, C, C); blv.plan(pl, M, C, C); blf.plan(pl, M, C, C);
+    // fp32: the join always rides in w2's epilogue, the bias gradients are column sums of their own (FeedForward's defaults)
+    ff.plan(pl, "tr", M, C, mlp, w1, b1, w2, b2);
+    xImg.plan(pl, M, C, true); ctxImg.plan(pl, M, C, true); hImg.plan(pl, M, C, true);
+    dqImg.plan(pl, M, C); dkImg.plan(pl, M, C); dvImg.plan(pl, M, C); dr1Img.plan(pl, M, C); ds2Img.plan(pl, M, C);
     outImg.plan(pl, M, C, true);
     return in;
   }
@@ -1066,7 +1096,7 @@ class TransformerLayer : public Layer {
       dropped = (double)(st >> 11) * (1.0 / 9007199254740992.0) < pLayerDrop;
     }
     float *q = ar + qOff, *k = ar + kOff, *v = ar + vOff, *S = ar + sOff, *Pd = ar + pdOff, *R = ar + rOff, *ctx = ar + ctxOff;
-    float *o = ar + oOff, *h = ar + hOff, *u = ar + uOff, *m2 = ar + m2Off, *out = ar + outOff;
+    float *o = ar + oOff, *h = ar + hOff, *m2 = ar + m2Off, *out = ar + outOff;
     float* xm = const_cast<float*>(x);
     if (dropped) {  // f = 0: both sublayers vanish, the two LayerNorms remain
       w2lCheck(w2l_residual_layernorm_forward(M, C, xm, nullptr, xm, h, gb1.w(cx), 1e-5f, 0.0, 0, 0, (double*)(ar + st1Off), ar + mr1Off, s), "tr ln1");
@@ -1085,7 +1115,7 @@ class TransformerLayer : public Layer {
       }
       {   // the six weights of the block in ONE conversion launch (8 us each on their own: launch-bound)
         const w2l_bf16_convert_desc wd[6] = {blq.w.desc(ar, wq.w(cx)), blk.w.desc(ar, wk.w(cx)), blv.w.desc(ar, wv.w(cx)),
-                                             blf.w.desc(ar, wf.w(cx)), bl1.w.desc(ar, w1.w(cx)), bl2.w.desc(ar, w2.w(cx))};
+                                             blf.w.desc(ar, wf.w(cx)), ff.bl1.w.desc(ar, w1.w(cx)), ff.bl2.w.desc(ar, w2.w(cx))};
         w2lCheck(w2l_bf16_convert_multi(6, wd, s), "tr weight images");
       }
       {   // the three projections in ONE grouped launch: 3 x 192 tiles share the grid (one at a time each fills 3/8 of the slots)
@@ -1096,9 +1126,9 @@ class TransformerLayer : public Layer {
         w2lCheck(w2l_gemm_bf16_grouped(3, M, C, C, A3, xSeen.colsP, B3, blq.w.rowsP, C3, C, b3, s), "tr q k v");
       }
     } else {
-    w2lCheck(w2l_linear_forward(M, C, C, x, wq.w(cx), bq.w(cx), q, 0, s), "tr q");
-    w2lCheck(w2l_linear_forward(M, C, C, x, wk.w(cx), bk.w(cx), k, 0, s), "tr k");
-    w2lCheck(w2l_linear_forward(M, C, C, x, wv.w(cx), bv.w(cx), v, 0, s), "tr v");
+      w2lCheck(w2l_linear_forward(M, C, C, x, wq.w(cx), bq.w(cx), q, 0, s), "tr q");
+      w2lCheck(w2l_linear_forward(M, C, C, x, wk.w(cx), bk.w(cx), k, 0, s), "tr k");
+      w2lCheck(w2l_linear_forward(M, C, C, x, wv.w(cx), bv.w(cx), v, 0, s), "tr v");
     }
     const long long TC = (long long)T * C, TT = (long long)T * T;
     const int* keyLen = nullptr;
@@ -1146,20 +1176,8 @@ class TransformerLayer : public Layer {
     }
     // o = r1 = wf(ctx) + x (the residual join in the product's epilogue), h = LN1(r1)
     const bool hImages = lnForward(cx, ar, M, C, o, nullptr, o, h, gb1.w(cx), 0.0, 0, 0, (double*)(ar + st1Off), ar + mr1Off, mixed ? &hImg : nullptr, "tr ln1");
-    if (mixed) {
-      if (!hImages) hImg.convert(cx, ar, h, "tr h images");
-      // u = relu(w1 h) is only ever an operand of w2's products and the mask of w2's backward-data product: bf16 images only
-      uOnlyImages = bl1.forwardImages(cx, ar, hImg, b1.w(cx), uImg, 1, 0.0, 0, 0);
-      if (!uOnlyImages) {
-        bl1.forward(cx, ar, hImg, b1.w(cx), u, 1, 0.0, 0, 0);
-        uImg.convert(cx, ar, u, "tr u images");
-      }
-      bl2.forwardAdd(cx, ar, uImg, b2.w(cx), h, m2, 0.0, 0, 0);
-    } else {
-    w2lCheck(w2l_linear_forward(M, C, mlp, h, w1.w(cx), b1.w(cx), u, 1, s), "tr w1");
-    w2lCheck(w2l_linear_forward_dropout_add(M, mlp, C, u, w2.w(cx), b2.w(cx), h, m2, 0, 0.0, 0, 0, s), "tr w2 + res");
-    }
-    // m2 = r2 = w2(u) + h
+    if (mixed && !hImages) hImg.convert(cx, ar, h, "tr h images");
+    ff.forward(cx, ar, h, hImg, m2, 0.0, 0);   // m2 = r2 = w2(relu(w1 h)) + h (no dropout inside the mlp)
     const bool outImages = lnForward(cx, ar, M, C, m2, nullptr, m2, out, gb2.w(cx), 0.0, 0, 0, (double*)(ar + st2Off), ar + mr2Off,
                                      mixed ? &outImg : nullptr, "tr ln2");
     if (outImages) {   // a following Transformer block of the same width reads them as its x images
@@ -1181,8 +1199,8 @@ class TransformerLayer : public Layer {
     auto bg = cx.bf16 ? w2l_bgemm_bf16 : w2l_bgemm_f32;
     const double pd = cx.train ? p : 0.0;
     float *q = ar + qOff, *k = ar + kOff, *v = ar + vOff, *S = ar + sOff, *Pd = ar + pdOff, *ctx = ar + ctxOff;
-    float *o = ar + oOff, *h = ar + hOff, *u = ar + uOff, *m2 = ar + m2Off;
-    float *ds2 = ar + ds2Off, *du = ar + duOff, *dh = ar + dhOff, *dr1 = ar + dr1Off, *dctx = ar + dctxOff, *dS = ar + dsOff;
+    float *o = ar + oOff, *h = ar + hOff, *m2 = ar + m2Off;
+    float *ds2 = ar + ds2Off, *dh = ar + dhOff, *dr1 = ar + dr1Off, *dctx = ar + dctxOff, *dS = ar + dsOff;
     float *dR = ar + dRoff, *dq = ar + dqOff, *dk = ar + dkOff, *dv = ar + dvOff, *dEp = ar + dEpOff;
     (void)needDx;  // a Transformer block is never the first parameterised layer
     dx = ar + dxOff;
@@ -1210,28 +1228,8 @@ class TransformerLayer : public Layer {
     const bool mixed = cx.bf16;
     const bool ds2Images = lnBackward(cx, ar, M, C, m2, dy, gb2.w(cx), ar + mr2Off, ds2, gb2.g(cx), nullptr, nullptr, 1.f, (double*)(ar + st2Off),
                                       mixed ? &ds2Img : nullptr, 0.0, 0, 0, "tr ln2 bwd");
-    if (mixed) {
-      if (!ds2Images) ds2Img.convert(cx, ar, ds2, "tr ds2 images");
-      const bool rides2 = bl2.biasRides(uImg, w2.g(cx), b2.g(cx));
-      bl2.backwardWeight(cx, ar, uImg, ds2Img, w2.g(cx), rides2);
-      if (!rides2) w2lCheck(w2l_colsum(ds2, b2.g(cx), (size_t)M, C, s), "tr w2 bwd b");
-      const bool rides1 = bl1.biasRides(hImg, w1.g(cx), b1.g(cx));
-      if (!(uOnlyImages && bl2.backwardDataImages(cx, ar, ds2Img, rides1 ? nullptr : du, &duImg, uImg, 1.f))) {
-        if (uOnlyImages) throw std::runtime_error("Transformer: u was kept as images only, but the image-writing backward-data product refused");
-        bl2.backwardData(cx, ar, ds2Img, du, u, 1.f, nullptr, 0);
-        duImg.convert(cx, ar, du, "tr du images");
-      }
-      bl1.backwardWeight(cx, ar, hImg, duImg, w1.g(cx), rides1);
-      if (!rides1) w2lCheck(w2l_colsum(du, b1.g(cx), (size_t)M, mlp, s), "tr w1 bwd b");
-      bl1.backwardData(cx, ar, duImg, dh, nullptr, 1.f, ds2, 0);
-    } else {
-    w2lCheck(w2l_linear_backward_weight(M, mlp, C, u, ds2, w2.g(cx), s), "tr w2 bwd w");
-    w2lCheck(w2l_colsum(ds2, b2.g(cx), (size_t)M, C, s), "tr w2 bwd b");
-    w2lCheck(w2l_linear_backward_data(M, mlp, C, ds2, w2.w(cx), du, 0, u, 1.f, s), "tr w2 bwd x");
-    w2lCheck(w2l_linear_backward_weight(M, C, mlp, h, du, w1.g(cx), s), "tr w1 bwd w");
-    w2lCheck(w2l_colsum(du, b1.g(cx), (size_t)M, mlp, s), "tr w1 bwd b");
-    w2lCheck(w2l_linear_backward_data_add(M, C, mlp, du, w1.w(cx), ds2, dh, s), "tr w1 bwd x");
-    }
+    if (mixed && !ds2Images) ds2Img.convert(cx, ar, ds2, "tr ds2 images");
+    ff.backward(cx, ar, h, hImg, ds2, ds2Img, ds2, dh, 0.0);   // dh = ds2 + du W1^T
     const bool dr1Images = lnBackward(cx, ar, M, C, o, dh, gb1.w(cx), ar + mr1Off, dr1, gb1.g(cx), nullptr, nullptr, 1.f, (double*)(ar + st1Off),
                                       mixed ? &dr1Img : nullptr, 0.0, 0, 0, "tr ln1 bwd");
     if (mixed) {
@@ -1239,9 +1237,9 @@ class TransformerLayer : public Layer {
       // (wf's weight and bias gradients join those of wq / wk / wv in one grouped launch at the end of this function)
       blf.backwardData(cx, ar, dr1Img, dctx, nullptr, 1.f, nullptr, 0);
     } else {
-    w2lCheck(w2l_linear_backward_weight(M, C, C, ctx, dr1, wf.g(cx), s), "tr wf bwd w");
-    w2lCheck(w2l_colsum(dr1, bf.g(cx), (size_t)M, C, s), "tr wf bwd b");
-    w2lCheck(w2l_linear_backward_data(M, C, C, dr1, wf.w(cx), dctx, 0, nullptr, 1.f, s), "tr wf bwd x");
+      w2lCheck(w2l_linear_backward_weight(M, C, C, ctx, dr1, wf.g(cx), s), "tr wf bwd w");
+      w2lCheck(w2l_colsum(dr1, bf.g(cx), (size_t)M, C, s), "tr wf bwd b");
+      w2lCheck(w2l_linear_backward_data(M, C, C, dr1, wf.w(cx), dctx, 0, nullptr, 1.f, s), "tr wf bwd x");
     }
     bool fusedBwd = false;
     if (mixed && fusedFwd && abwBytes) {   // dP, dropout mask, softmax backward, dq (+ position term), dk, dv, table gradient: four launches
