@@ -523,6 +523,10 @@ class FL_COMPAT_API CTCLoss : public SequenceCriterion {
   explicit CTCLoss(CriterionScaleMode scalemode = CriterionScaleMode::NONE);
   std::vector<Variable> forward(const std::vector<Variable>& inputs) override;
   af::array viterbiPath(const af::array& input, const af::array& inputSize = af::array()) override;   // per-frame argmax
+  // forced alignment of the known target (w2l_ctc_align): (T, B) s32, one label per frame, blank = N-1, bit-exact with the fp32
+  // max-plus recursion on the raw emissions (stay beats advance beats skip on ties); a target that does not fit: a column of -1.
+  // inputSizes: empty = all T frames, else (1, B) or (B) s32 EMISSION-frame counts per utterance (frames beyond them hold blank);
+  // targetSizes is ignored (sizes are counted on the device).  Bad target type / batch: std::invalid_argument.
   af::array viterbiPathWithTarget(const af::array& input, const af::array& target, const af::array& inputSizes = af::array(),
                                   const af::array& targetSizes = af::array()) override;
   std::string prettyString() const override;

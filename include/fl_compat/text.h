@@ -1,6 +1,8 @@
 // fl_compat/text.h -- the Trainer's token dictionary, target packing and evaluation remap on the reference's own names
 // (header only, host code, no device dependency).  Python mirror: wav2letter_amd/text.py; tests: tests/test_text.py (Python)
 // and tests/cpp/text_test.cpp (this header, compiled with g++ by the CPU test suite).
+// Forced alignment (a path -> token spans -> word segments -> the Align tool's line): tests/test_ctc_align_host.py and
+// tests/cpp/align_text_test.cpp.
 //
 // In-repo witnesses: class inventory of a run recipes/slimIPL/src/Train.cpp:235-251 (tokens file, `<1>`..`<replabel>`, the CTC
 // blank LAST); evaluation :829-872 (viterbiPath -> tknPrediction2Ltr / tknTarget2Ltr -> tkn2Wrd -> edit distances).  The
@@ -10,11 +12,13 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <fstream>
 #include <sstream>
 #include <stdexcept>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 namespace fl {
@@ -195,6 +199,111 @@ inline std::vector<int> targetIndices(const std::vector<std::string>& words, con
   std::vector<int> idx;
   for (auto& t : wrd2Target(words, lexicon, dict, wordSeparator, 0.f)) idx.push_back(dict.getIndex(t));
   return criterion == kAsgCriterion && replabel > 0 ? packReplabels(idx, dict, replabel) : idx;
+}
+
+// ---- forced alignment: from a path to token spans, word spans and the Align tool's segment lines (Python mirror: text.py) ----
+
+// for each token of targetIndices(words, ...) the index of the transcription word it spells, -1 for word separators and the
+// surround token; a replabel belongs to the word of the token before it; with word pieces every piece (a separator spelled for an
+// out-of-lexicon word included) belongs to the word it was generated for.  Built the way targetIndices builds the target (plus the
+// surround token of the Python front end, empty here by default), so both always have equal length.
+inline std::vector<int> targetWordIndex(const std::vector<std::string>& words, const lib::text::LexiconMap& lexicon,
+                                        const lib::text::Dictionary& dict, const std::string& criterion, int replabel,
+                                        const std::string& wordSeparator, const std::string& surround = "", bool useWordPiece = false,
+                                        bool fallback2LtrWordSepLeft = false, bool fallback2LtrWordSepRight = true,
+                                        bool skipUnk = false) {
+  std::vector<std::string> toks;
+  std::vector<int> widx;
+  for (size_t k = 0; k < words.size(); ++k)
+    for (auto& t : wrd2Target({words[k]}, lexicon, dict, wordSeparator, 0.f, fallback2LtrWordSepLeft, fallback2LtrWordSepRight, skipUnk)) {
+      toks.push_back(t);
+      widx.push_back(useWordPiece || wordSeparator.empty() || t != wordSeparator ? (int)k : -1);
+    }
+  if (!surround.empty()) {
+    toks.insert(toks.begin(), surround); toks.push_back(surround);
+    widx.insert(widx.begin(), -1); widx.push_back(-1);
+  }
+  if (!(criterion == kAsgCriterion && replabel > 0)) return widx;
+  std::vector<int> idx;
+  for (auto& t : toks) idx.push_back(dict.getIndex(t));
+  std::vector<int> isRep(dict.indexSize(), 0);
+  for (int r = 1; r <= replabel; ++r) isRep[(size_t)dict.getIndex(replabelToken(r))] = r;
+  std::vector<int> out;
+  size_t src = 0;   // packReplabels keeps the first token of a run; the replabel <r> stands for the next r
+  for (int t : packReplabels(idx, dict, replabel)) {
+    if (isRep[(size_t)t] && !out.empty()) {
+      out.push_back(out.back());
+      src += (size_t)isRep[(size_t)t];
+    } else {
+      out.push_back(widx[src]);
+      ++src;
+    }
+  }
+  return out;
+}
+
+// a forced-alignment path (one label per frame: CTCLoss::viterbiPathWithTarget with blank = N-1, ASGLoss::viterbiPathWithTarget with
+// blank < 0) -> (first frame, last frame) of each target token; frames holding the blank belong to no token.  std::invalid_argument
+// when the path does not collapse to the target (an infeasible row of -1 included).
+inline std::vector<std::pair<int, int>> alignmentTokenSpans(const std::vector<int>& path, std::vector<int> target, int blank = -1) {
+  target.erase(std::remove_if(target.begin(), target.end(), [](int t) { return t < 0; }), target.end());   // batch padding
+  std::vector<std::pair<int, int>> spans;
+  int prev = -1;   // label of the previous frame, -1 after a blank
+  for (size_t t = 0; t < path.size(); ++t) {
+    const int p = path[t];
+    if (p < 0) throw std::invalid_argument("alignmentTokenSpans: the path holds no alignment (infeasible target)");
+    if (blank >= 0 && p == blank) { prev = -1; continue; }
+    if (p == prev) { spans.back().second = (int)t; continue; }
+    if (spans.size() >= target.size() || target[spans.size()] != p)
+      throw std::invalid_argument("alignmentTokenSpans: the path does not spell the target at frame " + std::to_string(t));
+    spans.emplace_back((int)t, (int)t);
+    prev = p;
+  }
+  if (spans.size() != target.size()) throw std::invalid_argument("alignmentTokenSpans: the path ends before the target does");
+  return spans;
+}
+
+struct WordSegment {
+  double begin, length;   // seconds
+  std::string word;       // "$": silence
+};
+
+// a word runs from the first frame of its first token to the end of the last frame of its last token; every maximal run of frames
+// outside all words is one silence segment `$`.  The list always starts with a `$` segment (length 0 when speech starts in frame 0:
+// the consumers of the file skip entry 0); other zero-length silences are left out.
+inline std::vector<WordSegment> wordSegments(const std::vector<std::pair<int, int>>& tokenSpans, const std::vector<int>& wordIndex,
+                                             const std::vector<std::string>& words, int frames, double secondsPerFrame) {
+  if (tokenSpans.size() != wordIndex.size()) throw std::invalid_argument("wordSegments: token spans and word index differ in length");
+  std::vector<int> first(words.size(), -1), last(words.size(), -1);
+  for (size_t k = 0; k < tokenSpans.size(); ++k) {
+    const int w = wordIndex[k];
+    if (w < 0) continue;
+    if (first[(size_t)w] < 0) first[(size_t)w] = tokenSpans[k].first;
+    last[(size_t)w] = tokenSpans[k].second + 1;
+  }
+  std::vector<WordSegment> segs;
+  int cursor = 0;
+  for (size_t w = 0; w < words.size(); ++w) {
+    if (first[w] < 0) continue;
+    if (first[w] > cursor || segs.empty()) segs.push_back({cursor * secondsPerFrame, (first[w] - cursor) * secondsPerFrame, "$"});
+    segs.push_back({first[w] * secondsPerFrame, (last[w] - first[w]) * secondsPerFrame, words[w]});
+    cursor = last[w];
+  }
+  if (frames > cursor || segs.empty()) segs.push_back({cursor * secondsPerFrame, (frames - cursor) * secondsPerFrame, "$"});
+  return segs;
+}
+
+// one line of the Align tool's output: `<sample id>\t<seg>\n<seg>...` with the two characters backslash-n between segments and a real
+// newline at the end; <seg> = `ID A <begin> <length> <word>`, seconds with 2 decimals.  The literal `ID A` is recalled from upstream's
+// CTM writer and is not pinned by anything in the reference tree; its consumers read fields 3-5 only.
+inline std::string formatAlignmentLine(const std::string& sampleId, const std::vector<WordSegment>& segments) {
+  std::string out = sampleId + "\t";
+  for (size_t k = 0; k < segments.size(); ++k) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "ID A %.2f %.2f ", segments[k].begin, segments[k].length);
+    out += (k ? "\\n" : "") + std::string(buf) + segments[k].word;
+  }
+  return out + "\n";
 }
 
 inline void uniq(std::vector<int>& v) { v.erase(std::unique(v.begin(), v.end()), v.end()); }

@@ -150,6 +150,20 @@ int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, w2l_stre
 size_t w2l_ctc_score_workspace_size(int B, int T, int N, int L);
 int w2l_ctc_score(int B, int T, int N, int L, int scaleMode, const float* input, const int* target,
                   const int* targetSize, float* loss, int* path, void* workspace, w2l_stream_t stream);
+/* Forced alignment: the most probable lattice path of a KNOWN transcript, one label per frame (blank = N-1).
+ *   frames [B]: emission frames that belong to utterance b, 1..T (NULL: T for all); path[b][t] = N-1 for frames[b] <= t < T.
+ *   targetSize as w2l_batch_ctc_target_size(B, L, T, ...) writes it.  A row whose L_b labels with R adjacent equal pairs do not fit
+ *   (L_b + R > frames[b]) gets path -1 everywhere and score -inf; L_b = 0 gives all blank.
+ *   path is BIT-EXACT with the max-plus recursion on the RAW emissions, a'[s] = max(stay, advance, skip) + x[t][ext[s]] with one
+ *   fp32 add, candidates in the order stay, advance, skip, a later one winning only when strictly greater (w2l_fac_viterbi's rule);
+ *   end state 2 L_b, replaced by 2 L_b - 1 only when strictly greater.  (A per-frame constant cannot change the arg-max, so the
+ *   path is also the best one under the log-softmax.)
+ *   score [B] (may be NULL): sum over t < frames[b] of log_softmax(x[t])[path[t]], accumulated in double.  With score == NULL the
+ *   call reads only the L_b + 1 label emissions of every frame.
+ * w2l_ctc_align_workspace_size is host arithmetic.  L > 1023: W2L_EUNSUPPORTED, as w2l_ctc_forward. */
+size_t w2l_ctc_align_workspace_size(int B, int T, int N, int L);
+int w2l_ctc_align(int B, int T, int N, int L, const float* input, const int* target, const int* targetSize,
+                  const int* frames, int* path, float* score, void* workspace, w2l_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the

@@ -273,6 +273,34 @@ def ctc_score(emission, target, scalemode=CriterionScaleMode.NONE):
     return loss, path
 
 
+def ctc_align(emission, target, frames=None, with_score=True):
+    """CTC forced alignment (w2l_ctc_align): the most probable lattice path of the known transcript `target` [B][L] (negative =
+    padding) through `emission` [B][T][N], blank = N-1.  `frames` [B] int32: the emission frames that belong to each utterance,
+    1..T (None: all T); frames beyond them are filled with blank.  Returns (path [B][T] int32, score [B] float32 or None): the
+    path is bit-exact with the fp32 max-plus recursion on the raw emissions (stay beats advance beats skip on ties), the score is
+    its log-probability under the softmax.  A target that does not fit its frames gives a row of -1 and score -inf."""
+    _emission_checks(emission, target)
+    _check_dev(emission, target)
+    L = _lib.lib()
+    emission = emission.detach().contiguous()
+    target = target.contiguous()
+    B, T, N = emission.shape
+    Lt = target.shape[1]
+    if frames is not None:
+        if frames.dtype != torch.int32 or frames.numel() != B:
+            raise _lib.W2LInvalidArgument("ctc_align: frames must be int32 with one entry per utterance")
+        _check_dev(emission, frames)
+        frames = frames.contiguous()
+    ts = batch_target_size(target, T, ctc=True)
+    ws = _ws(L.w2l_ctc_align_workspace_size(B, T, N, Lt), emission.device)
+    path = torch.empty(B, T, dtype=torch.int32, device=emission.device)
+    score = torch.empty(B, dtype=torch.float32, device=emission.device) if with_score else None
+    _lib.check(L.w2l_ctc_align(B, T, N, Lt, emission.data_ptr(), target.data_ptr(), ts.data_ptr(),
+                               frames.data_ptr() if frames is not None else None, path.data_ptr(),
+                               score.data_ptr() if with_score else None, ws.data_ptr(), _stream()), "ctc_align")
+    return path, score
+
+
 class SequenceCriterion(torch.nn.Module):
     """fl::pkg::speech::SequenceCriterion: forward({emission,target}) -> {loss[B]},
     viterbiPath(emission) -> [B][T] int32."""
@@ -422,6 +450,10 @@ class CTCLoss(SequenceCriterion):
         _lib.check(_lib.lib().w2l_ctc_viterbi(B, T, N, emission.data_ptr(), path.data_ptr(), _stream()),
                    "ctc_viterbi")
         return path
+
+    def viterbiPathWithTarget(self, emission, target, frames=None):
+        """forced alignment of `target` to the emissions: [B][T] int32, one label per frame (ctc_align without the score)"""
+        return ctc_align(emission, target, frames, with_score=False)[0]
 
     def score(self, emission, target):
         """(loss [B], viterbiPath [B][T]) of a held-out batch in one pass over the emissions (ctc_score)"""

@@ -22,6 +22,7 @@
 //                  <= 2L+1 occupancies gamma[t][s] = exp(alpha+beta-lp-logZ) of
 //                  that frame.
 // Algorithmic HBM bytes: 4BTN (fwd) + 8BTN (bwd) = 12*B*T*N.
+// w2l_ctc_align (forced alignment: the best lattice path of a known transcript) lives in criterion_ctc_align.hpp, included below.
 // w2l_ctc_score (evaluation: loss and greedy path, no gradient) reads the emissions once, 4BTN:
 //   ctc_rows_score  the ctc_rows_lse pass (same arithmetic, template flag) that also writes the first-max argmax of the row
 //   ctc_scan_score  the alpha wave alone, grid (B, 1), lattice rows kept in registers: only the loss is written
@@ -246,8 +247,8 @@ __global__ __launch_bounds__(kRowThreads) void ctc_rows_lse(int T, int N, int L,
 }
 
 // generic-N fallback (N > 256*kRowMaxPer): two passes over the row.  kArgmax: the first pass also keeps each thread's
-// first max and its index (ctc_rows_argmax's loop), so the argmax costs no third pass
-template <bool kArgmax>
+// first max and its index (ctc_rows_argmax's loop), so the argmax costs no third pass.  kPd = false (w2l_ctc_align): lse alone
+template <bool kArgmax, bool kPd = true>
 __device__ __forceinline__ void ctc_rows_lse_big_body(int T, int N, int L,
                                                       const float* __restrict__ x,
                                                       const int* __restrict__ target,
@@ -273,6 +274,7 @@ __device__ __forceinline__ void ctc_rows_lse_big_body(int T, int N, int L,
   s = block_reduce_sum(s, sm);
   const float lse = m + __logf(s);
   if (tid == 0) ws.lse[r] = lse;
+  if constexpr (!kPd) return;
   const int Lb = targetSize[b];
   const int S = 2 * Lb + 1;
   const int* y = target + (size_t)b * L;
@@ -887,3 +889,5 @@ W2L_API int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, 
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }
+
+#include "criterion_ctc_align.hpp"

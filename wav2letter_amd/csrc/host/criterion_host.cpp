@@ -49,6 +49,17 @@ class CTCLossImpl : public SequenceCriterion {
     w2lCheck(w2l_batch_ctc_target_size(B, L, T, target, ts, c.stream), "ctc target size");
     w2lCheck(w2l_ctc_score(B, T, N, L, mode_, em, target, ts, loss, path, kws, c.stream), "ctc score");
   }
+  size_t alignWorkspaceBytes(int B, int T, int N, int L) const override {
+    return up(sizeof(int) * B) + w2l_ctc_align_workspace_size(B, T, N, L);
+  }
+  // the best lattice path of the known target (w2l_ctc_align without the score: only the label emissions are read)
+  void alignPath(Ctx& c, int B, int T, int N, int L, const float* em, const int* target, const int* frames, int* path, void* ws,
+                 float*) override {
+    int* ts = (int*)ws;
+    void* kws = (char*)ws + up(sizeof(int) * B);
+    w2lCheck(w2l_batch_ctc_target_size(B, L, T, target, ts, c.stream), "ctc target size");
+    w2lCheck(w2l_ctc_align(B, T, N, L, em, target, ts, frames, path, nullptr, kws, c.stream), "ctc align");
+  }
 
  private:
   int mode_;

@@ -1234,8 +1234,24 @@ af::array CTCLoss::viterbiPath(const af::array& input, const af::array&) {
   st->impl->viterbiPath(c, B, T, N, input.device<float>(), path.device<int>(), nullptr, nullptr);
   return path;
 }
-af::array CTCLoss::viterbiPathWithTarget(const af::array&, const af::array&, const af::array&, const af::array&) {
-  throw std::logic_error("CTCLoss::viterbiPathWithTarget is not used by the recipes' training loop (forced alignment is an ASG / tools feature)");
+// forced alignment (w2l_ctc_align): inputSizes empty = all T frames, else (1,B) or (B) s32 EMISSION-frame counts per utterance (the
+// frames beyond them are filled with blank); targetSizes is ignored as in ASGLoss (sizes are counted on the device)
+af::array CTCLoss::viterbiPathWithTarget(const af::array& input, const af::array& target, const af::array& inputSizes, const af::array&) {
+  const int N = (int)input.dims(0), T = (int)input.dims(1), B = (int)input.dims(2), L = (int)target.dims(0);
+  if (target.type() != af::s32 || target.dims(1) != B) throw std::invalid_argument("viterbiPathWithTarget: bad target");
+  const int* frames = nullptr;
+  if (!inputSizes.isempty()) {
+    if (inputSizes.type() != af::s32 || inputSizes.elements() != B) throw std::invalid_argument("viterbiPathWithTarget: bad inputSizes");
+    frames = inputSizes.device<int>();
+  }
+  auto st = stateOf(this);
+  af::array path(af::dim4(T, B), af::s32);
+  auto ws = devAlloc(st->impl->alignWorkspaceBytes(B, T, N, L) + 256);
+  w2l::Ctx c;
+  c.stream = S();
+  st->impl->alignPath(c, B, T, N, L, input.device<float>(), target.device<int>(), frames, path.device<int>(), ws.get(), nullptr);
+  af::sync();  // ws is released at return
+  return path;
 }
 std::string CTCLoss::prettyString() const { return "ConnectionistTemporalClassificationCriterion"; }
 

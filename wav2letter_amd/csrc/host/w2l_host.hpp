@@ -194,6 +194,15 @@ class SequenceCriterion {
     forward(c, B, T, N, L, emission, target, loss, ws, critParams);
     viterbiPath(c, B, T, N, emission, path, ws, critParams);
   }
+  // forced alignment of a KNOWN target: path [B][T], one label per frame.  frames [B] (device int32): the emission frames that
+  // belong to each utterance, 1..T, the rest filled with blank; nullptr = T for all.  ws: alignWorkspaceBytes of its own.  CTC only
+  // (w2l_ctc_align; ASG's forced alignment is ForceAlignmentCriterion's viterbi, called with the transitions: w2l_fac_viterbi).
+  virtual size_t alignWorkspaceBytes(int B, int T, int N, int L) const { (void)B; (void)T; (void)N; (void)L; return 0; }
+  virtual void alignPath(Ctx& c, int B, int T, int N, int L, const float* emission, const int* target, const int* frames, int* path,
+                         void* ws, float* critParams) {
+    (void)c; (void)B; (void)T; (void)N; (void)L; (void)emission; (void)target; (void)frames; (void)path; (void)ws; (void)critParams;
+    throw std::logic_error(prettyString() + ": no forced alignment through this criterion object");
+  }
 };
 std::shared_ptr<SequenceCriterion> makeCTCLoss(int scaleMode);
 std::shared_ptr<SequenceCriterion> makeASGLoss(int N, int scaleMode, double transdiag);

@@ -13,7 +13,7 @@ The functions themselves (fl::lib::text::Dictionary, wrd2Target, packReplabels, 
 tknIdx2Ltr, tkn2Wrd) are un-vendored Flashlight ([UNVENDORED]): restated from their published behaviour, pinned here by
 round trips and by the class counts above (tests/test_text.py).
 """
-from typing import Dict, Iterable, List, Optional, Sequence
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 BLANK = "#"          # fl::pkg::speech::kBlankToken
 UNK = "<unk>"
@@ -173,6 +173,95 @@ def target_indices(words: Sequence[str], lexicon, token_dict: Dictionary, criter
     if criterion == "asg" and replabel > 0:
         idx = pack_replabels(idx, token_dict, replabel)
     return idx
+
+
+def target_word_index(words: Sequence[str], lexicon, token_dict: Dictionary, criterion: str, replabel: int = 0, wordsep: str = "",
+                      surround: str = "", use_wordpiece: bool = False, **kw) -> List[int]:
+    """for each token of target_indices(words, ...) the index of the transcription word it spells, -1 for word separators and the
+    --surround token; a replabel belongs to the word of the token before it; with word pieces every piece (a separator spelled
+    for an out-of-lexicon word included) belongs to the word it was generated for.  Built the way target_indices builds the
+    target, so both always have equal length."""
+    toks: List[str] = []
+    widx: List[int] = []
+    for k, w in enumerate(words):
+        spelled = wrd2target([w], lexicon, token_dict, wordsep, **kw)
+        toks += spelled
+        widx += [k if use_wordpiece or not wordsep or t != wordsep else -1 for t in spelled]
+    if surround:
+        toks = [surround] + toks + [surround]
+        widx = [-1] + widx + [-1]
+    if criterion == "asg" and replabel > 0:
+        idx = [token_dict.get_index(t) for t in toks]
+        packed = pack_replabels(idx, token_dict, replabel)
+        reps = {token_dict.get_index(replabel_token(r)): r for r in range(1, replabel + 1)}
+        out: List[int] = []
+        src = 0                       # pack_replabels keeps the first token of a run; the replabel <r> stands for the next r
+        for t in packed:
+            if t in reps and out:
+                out.append(out[-1])
+                src += reps[t]
+            else:
+                out.append(widx[src])
+                src += 1
+        return out
+    return widx
+
+
+def alignment_token_spans(path: Sequence[int], target: Sequence[int], blank: Optional[int] = None) -> List[Tuple[int, int]]:
+    """a forced-alignment path (one label per frame: w2l_ctc_align with `blank` = N-1, or w2l_fac_viterbi with blank None) ->
+    (first_frame, last_frame) of each target token.  Frames holding the blank belong to no token.  ValueError when the path does
+    not collapse to the target (an infeasible row of -1 included)."""
+    tgt = [int(t) for t in target if int(t) >= 0]
+    spans: List[Tuple[int, int]] = []
+    prev = None                       # label of the previous frame, None after a blank
+    for t, p in enumerate(path):
+        p = int(p)
+        if p < 0:
+            raise ValueError("alignment path holds no alignment (infeasible target)")
+        if blank is not None and p == blank:
+            prev = None
+            continue
+        if p == prev:
+            spans[-1] = (spans[-1][0], t)
+            continue
+        if len(spans) >= len(tgt) or tgt[len(spans)] != p:
+            raise ValueError(f"alignment path does not spell the target at frame {t}")
+        spans.append((t, t))
+        prev = p
+    if len(spans) != len(tgt):
+        raise ValueError("alignment path ends before the target does")
+    return spans
+
+
+def word_segments(token_spans, word_index, words: Sequence[str], frames: int, seconds_per_frame: float):
+    """token spans + the word of each token -> [(begin_s, length_s, word)] over the utterance's `frames` emission frames: a word
+    runs from the first frame of its first token to the end of the last frame of its last token; every maximal run of frames
+    outside all words is one silence segment with the word `$`.  The list always starts with a `$` segment (length 0 when speech
+    starts in frame 0: the consumers of the file skip entry 0); other zero-length silences are left out."""
+    if len(token_spans) != len(word_index):
+        raise ValueError("token spans and word index differ in length")
+    first, last = {}, {}
+    for (a, b), w in zip(token_spans, word_index):
+        if w >= 0:
+            first.setdefault(w, a)
+            last[w] = b + 1
+    segs = []
+    cursor = 0
+    for w in sorted(first):
+        if first[w] > cursor or not segs:
+            segs.append((cursor * seconds_per_frame, (first[w] - cursor) * seconds_per_frame, "$"))
+        segs.append((first[w] * seconds_per_frame, (last[w] - first[w]) * seconds_per_frame, words[w]))
+        cursor = last[w]
+    if frames > cursor or not segs:
+        segs.append((cursor * seconds_per_frame, (frames - cursor) * seconds_per_frame, "$"))
+    return segs
+
+
+def format_alignment_line(sample_id: str, segments) -> str:
+    """one line of the Align tool's output: `<sample id>\t<seg>\\n<seg>...` -- the two characters backslash-n between segments, a
+    real newline at the end; <seg> = `ID A <begin> <length> <word>`, seconds with 2 decimals.  The literal `ID A` is recalled from
+    upstream's CTM writer and is not pinned by anything in the reference tree; its consumers read fields 3-5 only."""
+    return sample_id + "\t" + "\\n".join(f"ID A {b:.2f} {n:.2f} {w}" for b, n, w in segments) + "\n"
 
 
 def pad_targets(rows: Sequence[Sequence[int]], length: Optional[int] = None):
