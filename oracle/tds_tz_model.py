@@ -42,7 +42,7 @@ def cfg(CI, CO, R, NCT, SIG=1, KWM=21, ST=1):
                 GSTEP=GSTEP, NF=NF, PITCH=p, NQF=S + SIG * (R - 1), NQB=ST * (S + R - 1), WPF=wp(SIG, (-CO) % 32), WPB=wp(ST, CO % 32))
 
 
-# the instances conv_tds_rs.hip launches: (CI, CO, stride of the layer / tap step of the phase, backward?)
+# the instances conv_tds_special.hip launches: (CI, CO, stride of the layer / tap step of the phase, backward?)
 CFGS = {(10, 10, 1, False): cfg(10, 10, 3, 1), (14, 14, 1, False): cfg(14, 14, 2, 1), (18, 18, 1, False): cfg(18, 18, 3, 2),
         (10, 10, 1, True): cfg(10, 10, 3, 1), (14, 14, 1, True): cfg(14, 14, 2, 1), (18, 18, 1, True): cfg(18, 18, 3, 2),
         (10, 14, 2, False): cfg(10, 14, 2, 1, SIG=2), (14, 18, 2, False): cfg(14, 18, 3, 2, SIG=2),

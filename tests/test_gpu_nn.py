@@ -535,9 +535,10 @@ def test_conv_backward_data_accumulate_and_add(oracle, B, Cin, Cout, H, T, kw, s
     assert rel(from_fm(add.cpu().numpy()), odx + base) < TOL
 
 
-TDS_RS3_SHAPES = [(10, 48, 2, 80), (18, 12, 2, 80), (10, 50, 2, 80), (18, 15, 3, 80), (10, 1, 1, 80), (18, 2, 2, 80), (10, 129, 3, 80),
-                  (18, 188, 5, 80), (10, 750, 3, 80), (10, 64, 1, 80), (18, 46, 7, 80), (10, 331, 9, 80), (18, 97, 33, 80), (10, 77, 5, 8),
-                  (18, 150, 2, 24), (10, 2100, 2, 16), (14, 24, 2, 80), (14, 77, 2, 80), (14, 375, 3, 80), (14, 1, 1, 80), (14, 33, 5, 16), (14, 200, 9, 8)]
+TDS_CONV_SHAPES = [(10, 48, 2, 80), (18, 12, 2, 80), (10, 50, 2, 80), (18, 15, 3, 80), (10, 1, 1, 80), (18, 2, 2, 80), (10, 129, 3, 80),
+                   (18, 188, 5, 80), (10, 750, 3, 80), (10, 64, 1, 80), (18, 46, 7, 80), (10, 331, 9, 80), (18, 97, 33, 80), (10, 77, 5, 8),
+                   (18, 150, 2, 24), (10, 2100, 2, 16), (14, 24, 2, 80), (14, 77, 2, 80), (14, 375, 3, 80), (14, 1, 1, 80), (14, 33, 5, 16), (14, 200, 9, 8),
+                   (10, 77, 2, 12), (18, 50, 2, 20)]
 
 
 def _tds_conv_ref64(x, w, b, dy, add, kw, padl):
@@ -549,12 +550,13 @@ def _tds_conv_ref64(x, w, b, dy, add, kw, padl):
     return yr.permute(0, 3, 2, 1).detach(), xr.grad.permute(0, 3, 2, 1) + add.double()
 
 
-@pytest.mark.parametrize("Cc,T,B,H", TDS_RS3_SHAPES)
-def test_tds_conv_streamed_wave_specialised_kernel(Cc, T, B, H):
-    """conv_tds_rs3.hpp (the TDS convolution proper, C = 10 / 14 / 18, H % 8 == 0): forward with bias, with and without the fused
-    ReLU, and backward-data with the fused addend, every element against a float64 convolution; segment cuts in the
+@pytest.mark.parametrize("Cc,T,B,H", TDS_CONV_SHAPES)
+def test_tds_conv_proper_every_element(Cc, T, B, H):
+    """the TDS convolution proper (C -> C, C = 10 / 14 / 18, stride 1) on whichever kernel the dispatcher picks -- the block-Toeplitz
+    kernel at H % 16 == 0, the general kernels of conv_tds.hip at H = 8 / 12 / 20 / 24: forward with bias, with and without the
+    fused ReLU, and backward-data with the fused addend, every element against a float64 convolution; segment cuts in the
     middle of utterances, utterances shorter than one tile, one- and two-frame inputs, short kernels, causal padding;
-    run-to-run identical (the overlap-add order is program order)"""
+    run-to-run identical (fixed summation order, no atomics)"""
     import ctypes as C
     from wav2letter_amd import _lib
     L = _lib.lib()
@@ -586,9 +588,10 @@ def test_tds_conv_streamed_wave_specialised_kernel(Cc, T, B, H):
 
 
 @pytest.mark.parametrize("Cc,T,B", [(10, 331, 3), (18, 97, 5), (14, 77, 2)])
-def test_tds_conv_kernel_generations_agree(Cc, T, B, probe):
-    """the previous generations stay selectable in the probe library (W2L_TDS_RS3_OFF: the cooperative role-swapped kernel,
-    W2L_TDS_RS_OFF: conv_tds.hip's 16-wide tiles) and agree with the product kernels"""
+def test_tds_conv_kernel_generations_agree(Cc, T, B):
+    """the specialised kernels of the product library (block-Toeplitz forward / backward-data / filter gradient, the role-swapped
+    filter gradient at C = 18) against the general kernels of conv_tds.hip, selected in the probe library by W2L_TDS_TZ_OFF,
+    W2L_TDS_TZF_OFF and W2L_TDS_RSF_OFF: forward + ReLU, backward-data + addend, filter and bias gradient"""
     import ctypes as C
     import os
     from wav2letter_amd import _lib
@@ -599,20 +602,28 @@ def test_tds_conv_kernel_generations_agree(Cc, T, B, probe):
     x = torch.randn(B, T, H, Cc, generator=g).cuda()
     w = (torch.randn(kw, Cc, Cc, generator=g) / (kw * Cc) ** 0.5).cuda()
     b = torch.randn(Cc, generator=g).cuda()
+    dy = torch.randn(B, T, H, Cc, generator=g).cuda()
+    add = torch.randn(B, T, H, Cc, generator=g).cuda()
 
-    def fwd(Lx):
-        y = torch.empty_like(x)
+    def run(Lx):
+        y, dx, dw, db = torch.empty_like(x), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
         assert Lx.w2l_conv_forward(C.byref(d), x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), 1, s) == 0
+        assert Lx.w2l_conv_backward_data_add(C.byref(d), dy.data_ptr(), w.data_ptr(), add.data_ptr(), dx.data_ptr(), s) == 0
+        assert Lx.w2l_conv_backward_filter(C.byref(d), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), db.data_ptr(), s) == 0
         torch.cuda.synchronize()
-        return y
-    want = fwd(_lib.lib())
-    for sw in ("W2L_TDS_RS3_OFF", "W2L_TDS_RS_OFF"):
-        os.environ[sw] = "1"
+        return y, dx, dw, db
+    want = run(_lib.lib())
+    switches = ("W2L_TDS_TZ_OFF", "W2L_TDS_TZF_OFF", "W2L_TDS_RSF_OFF")
+    with _lib.use_probe() as probe:
+        for sw in switches:
+            os.environ[sw] = "1"
         try:
-            got = fwd(probe)
+            got = run(probe)
         finally:
-            os.environ.pop(sw)
-        assert rel(got, want.cpu().numpy()) < TOL
+            for sw in switches:
+                os.environ.pop(sw)
+    for name, a, r in zip(("forward + ReLU", "backward-data + addend", "filter gradient", "bias gradient"), got, want):
+        assert rel(a, r.cpu().numpy()) < TOL, name
 
 
 @pytest.mark.parametrize("B,Cin,Cout,T,kw,padl,padr", [(2, 40, 100, 60, 13, 0, 0), (2, 321, 706, 64, 19, 0, 0), (2, 40, 400, 90, 13, 170, 170)])

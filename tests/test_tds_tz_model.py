@@ -3,7 +3,7 @@ conv_tds_tzf.hpp + tds_tzf_reduce_k filter gradient) on the CPU: oracle/tds_tz_m
 by lane in float64 (slab addresses, lane-half frame pairing, split tail, B-register order, MFMA ownership, store offsets
 and range checks, the partial-image layout and the fold of D's diagonals into dW) with never-written bytes held as NaN,
 and is held here to a direct convolution.  The HIP kernels themselves are compared with the oracle under -m gpu
-(tests/test_gpu_nn.py::test_tds_conv_streamed_wave_specialised_kernel, test_conv_fwd_bwd, tests/test_gpu_parity_shapes.py)."""
+(tests/test_gpu_nn.py::test_tds_conv_proper_every_element, test_conv_fwd_bwd, tests/test_gpu_parity_shapes.py)."""
 import numpy as np
 import pytest
 

@@ -9,7 +9,8 @@
   model    cycles per MFMA = 64 + 10 * (LDS / MFMA) + 4.5 * ((VALU - MFMA) / MFMA)
            ceiling = 157.3 TF/s * 64 / cycles per MFMA * (algorithmic flops / issued MFMA flops)
            (issued MFMA flops = MFMA instructions * 4096; the role-swapped kernels pad tap groups x channels to the 32 MFMA columns)
-  output   profiles/r04_tds_conv_issue_model.json (read by bench.py: tds_conv.ceiling)
+  output   profiles/r04_tds_conv_issue_model.json (the round-4 model of the role-swapped kernels; bench.py reads its successor
+           profiles/r05_tds_conv_issue_model.json, tools/conv_tz_isa_counts.py)
 
 The model is an UPPER bound on what these instruction streams can reach (it ignores barriers, LDS bank conflicts, the prologue /
 epilogue of a workgroup and the tail of the grid); it does not say that a leaner stream is impossible."""
@@ -40,7 +41,7 @@ for l in lines:
     cyc = 64 + 10 * lds / mfma + 4.5 * valu / mfma
     issued = mfma * 4096 / 1e9
     useful = min(1.0, ALG[C] / issued)
-    key = ("tds_conv_rs3_k" if "rs3_k" in name else "tds_conv_rsf3_k") + f"<C={C}>"
+    key = name.split("::")[1].split("<")[0] + f"<C={C}>"   # the kernel names of the evidence (its forward kernel has since been retired)
     out["kernels"][key] = {"mfma_per_dispatch": mfma, "lds_per_mfma": round(lds / mfma, 3), "valu_per_mfma": round(valu / mfma, 3),
                            "model_cycles_per_mfma": round(cyc, 1), "issued_gflop": round(issued, 2), "algorithmic_gflop": ALG[C],
                            "useful_frac_of_issued": round(useful, 3), "ceiling_TFLOPs": round(PEAK * 64 / cyc * useful, 1),

@@ -1,7 +1,6 @@
 """One shape of one TDS convolution kernel, repeated, for rocprofv3 / counter passes (am_tds_ctc.arch stages: C = 10 / 14 / 18,
-kw = 21, H = 80, B = 32):   python tools/conv_one.py [fwd | fwd3 | filter] [C]
+kw = 21, H = 80, B = 32):   python tools/conv_one.py [fwd | filter] [C]
   fwd     forward through the product library (the round-1 counter passes r17_conv_sq*)
-  fwd3    forward on the third-generation kernel through the probe library (W2L_TDS_RS3=1: the r2h / r2i rs3 passes)
   filter  filter gradient through the product library (the r2i rsf3 passes)"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,7 +9,7 @@ from wav2letter_amd import _lib
 
 kind = sys.argv[1] if len(sys.argv) > 1 else "fwd"
 Cc = int(sys.argv[2]) if len(sys.argv) > 2 else 10
-assert kind in ("fwd", "fwd3", "filter"), kind
+assert kind in ("fwd", "filter"), kind
 T = {10: 750, 14: 375, 18: 188}[Cc]
 B, H, kw = 32, 80, 21
 d = _lib.ConvDesc(B, T, H, Cc, Cc, kw, 1, 10, 10)
@@ -28,10 +27,4 @@ def go(L, reps):
     torch.cuda.synchronize()
 
 
-if kind == "fwd3":
-    os.environ["W2L_TDS_RS3"] = "1"
-    os.environ["W2L_TDS_RS_C14"] = "1"
-    with _lib.use_probe() as P:
-        go(P, 5)
-else:
-    go(_lib.lib(), 8 if kind == "filter" else 5)
+go(_lib.lib(), 8 if kind == "filter" else 5)

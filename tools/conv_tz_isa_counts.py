@@ -1,15 +1,15 @@
 """Static instruction mix of the round loop of the block-Toeplitz TDS convolution kernels, read off the gfx950 ISA hipcc
-emits (conv_tds_rs.hip compiled with -save-temps): MFMA / DS / VMEM / VALU / SALU instructions per round of a wave, and the
+emits (conv_tds_special.hip compiled with -save-temps): MFMA / DS / VMEM / VALU / SALU instructions per round of a wave, and the
 issue-model ceiling of profiles/r02_run15_mfma_issue_microbench.log (a DS instruction beside an MFMA costs the SIMD's matrix
 pipe ~10 cycles, a VALU / VMEM instruction ~4.5) times the algorithmic share of the issued MFMA flops.
-    python tools/conv_tz_isa_counts.py /tmp/conv_tds_rs-hip-amdgcn-amd-amdhsa-gfx950.s > profiles/r05_tds_conv_issue_model.json"""
+    python tools/conv_tz_isa_counts.py /tmp/conv_tds_special-hip-amdgcn-amd-amdhsa-gfx950.s > profiles/r05_tds_conv_issue_model.json"""
 import json
 import re
 import sys
 
 src = open(sys.argv[1]).read()
 out = {"_model": "cycles per MFMA = 64 + 10 DS/MFMA + 4.5 (VALU + VMEM)/MFMA over the round loop of one wave; ceiling = 64 / cycles * useful / issued flops",
-       "_source": "ISA of conv_tds_rs.hip (hipcc -O3 --offload-arch=gfx950), tools/conv_tz_isa_counts.py", "kernels": {}}
+       "_source": "ISA of conv_tds_special.hip (hipcc -O3 --offload-arch=gfx950), tools/conv_tz_isa_counts.py", "kernels": {}}
 useful = {  # algorithmic / issued MFMA flops: taps / S x columns / (32 NCT) x K / K padded
     "tds_conv_tz_k<10,10>": 21 / 23 * 30 / 32 * 230 / 232, "tds_conv_tz_k<14,14>": 21 / 22 * 28 / 32, "tds_conv_tz_k<18,18>": 21 / 23 * 54 / 64 * 414 / 416,
     "tds_conv_tzf_k<10,10>": 210 * 30 / (256 * 32), "tds_conv_tzf_k<14,14>": 294 * 28 / (320 * 32)}

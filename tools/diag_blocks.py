@@ -1,4 +1,4 @@
-"""Localise the gradient error of the role-swapped TDS conv inside a network: reduced archs with k TDS blocks."""
+"""Localise the gradient error of the specialised TDS conv kernels inside a network: reduced archs with k TDS blocks."""
 import os
 import sys
 
@@ -47,6 +47,8 @@ for kw in [dict(c=10, nblocks=2, T=96, l2=2400), dict(c=10, nblocks=1, T=96, sta
            dict(c=10, nblocks=1, T=96, stages=[(10, 5, 2400), (14, 6, 3360), (18, 10, 4320)])]:
     run("product", **kw)
     with _lib.use_probe():
-        os.environ["W2L_TDS_RS_OFF"] = "1"
-        run("probe RS off", **kw)
-        os.environ.pop("W2L_TDS_RS_OFF")
+        general = ("W2L_TDS_TZ_OFF", "W2L_TDS_TZF_OFF", "W2L_TDS_RSF_OFF")
+        os.environ.update({k: "1" for k in general})
+        run("probe, general conv kernels", **kw)
+        for k in general:
+            os.environ.pop(k)

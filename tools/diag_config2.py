@@ -1,5 +1,6 @@
 """Diagnostic for tests/test_gpu_trainer.py::test_tds_ctc_config2_full_network_end_to_end: per-parameter gradient error of
-the product library and of the previous TDS conv kernels (probe library, W2L_TDS_RS_OFF=1), and how many ReLU masks of
+the product library and of the general TDS conv kernels (probe library, W2L_TDS_TZ_OFF=1 W2L_TDS_TZF_OFF=1
+W2L_TDS_RSF_OFF=1), and how many ReLU masks of
 the TDS convolutions differ from the reference's (a pre-activation within rounding of zero flips the mask: relu'(0+-))."""
 import os
 import re
@@ -48,11 +49,11 @@ def run(tag):
     print(f"[{tag}] smallest |conv pre-activation| per TDS block (reference): {['%.1e' % m for m in mins]}")
 
 
-run("product (role-swapped conv)")
+run("product (specialised conv kernels)")
 with _lib.use_probe():
-    run("probe, role-swapped conv")
-    os.environ["W2L_TDS_RS_OFF"] = "1"
-    run("probe, previous conv kernels")
-    os.environ.pop("W2L_TDS_RS_OFF")
-    os.environ["W2L_TDS_RSF_OFF"] = "1"
-    run("probe, role-swapped fwd/bwd-data, previous filter")
+    run("probe, specialised conv kernels")
+    os.environ.update(W2L_TDS_TZ_OFF="1", W2L_TDS_TZF_OFF="1", W2L_TDS_RSF_OFF="1")
+    run("probe, general conv kernels")
+    os.environ.pop("W2L_TDS_TZ_OFF")
+    run("probe, specialised fwd/bwd-data, general filter")
+    os.environ.pop("W2L_TDS_TZF_OFF"); os.environ.pop("W2L_TDS_RSF_OFF")

@@ -1,6 +1,6 @@
 // mfma_rate.hip -- what does v_mfma_f32_32x32x2_f32 sustain on MI355X in the shapes the TDS kernels use?
 // Chains of NK dependent MFMAs (one accumulator), W waves per SIMD, optionally with LDS operations slotted between
-// the MFMAs (the overlap-add / fragment traffic of conv_tds_rs3.hpp), accumulator resets and workgroup barriers.
+// the MFMAs (the overlap-add / fragment traffic of the role-swapped TDS convolution kernels), accumulator resets and workgroup barriers.
 // Reports TFLOP/s, % of the 157.3 TFLOP/s peak, and the shader clock (clock64 / wall_clock64).
 //   hipcc --offload-arch=gfx950 -O3 -o /tmp/mfma_rate tools/micro/mfma_rate.hip && /tmp/mfma_rate
 #include <hip/hip_runtime.h>

@@ -18,6 +18,7 @@
 #include <map>
 #include <mutex>
 
+#include "conv_tds.hpp"   // slab-in-LDS kernels for few-channel convolutions (TDS, C2 sub-sampling)
 #include "gemm.hpp"
 
 namespace w2l {
@@ -347,15 +348,6 @@ static int conv_launch_rowsB(const AOp& a, const float* Bp, int ldb, int N, int 
   if (v == 2) return launch128(a, PlainOp<false, 2>{Bp, ldb, N, K}, o, epi, splitk, s);
   return launch128(a, PlainOp<false, 1>{Bp, ldb, N, K}, o, epi, splitk, s);
 }
-
-// conv_tds.hip: slab-in-LDS kernels for few-channel convolutions (TDS, C2 sub-sampling)
-bool tds_conv_applicable(const w2l_conv_desc* d);
-int tds_conv_forward(const w2l_conv_desc* d, const float* x, const float* w, const float* bias, float* y, int relu,
-                     hipStream_t s);
-int tds_conv_backward_data(const w2l_conv_desc* d, const float* dy, const float* w, float* dx, int accumulate,
-                           const float* add, hipStream_t s);
-int tds_conv_backward_filter(const w2l_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias,
-                             hipStream_t s);
 
 // =====================================================================================================
 // conv_glu path (fl::Conv2D kw x 1 over time with H == 1, stride 1: recipes/conv_glu/*/network.arch).

@@ -26,7 +26,7 @@
 // of this op is C/16 = 62.5 % / 87.5 % / 56 % of the fp32 peak by construction.
 #include <cstdlib>
 
-#include "gemm.hpp"
+#include "conv_tds.hpp"
 
 namespace w2l {
 
@@ -35,22 +35,6 @@ constexpr int kTdsBTF = 16;  // frames per chunk (backward-filter)
 constexpr int kTdsBH = 16;   // mel rows per workgroup = rows of one MFMA tile
 constexpr int kTdsMaxXV = 12;  // float4 slab pieces per thread (register-prefetching kernels)
 constexpr int kTdsMaxTilesPerWave = 6;  // backward-filter: (K+1)/16 row tiles over 4 waves -> K <= 383
-
-struct TdsConvP {
-  const float* x;     // tensor being read as the GEMM A operand [B][Tin][H][Cin]
-  const float* w;     // [kw][CinW][CoutW] weights of the layer (forward orientation)
-  const float* bias;  // [Cout] or null
-  const float* add;   // optional addend with the layout of y (residual / upstream gradient), or null
-  float* y;           // [B][Tout][H][Cout]
-  int B, Tin, Tout, H, Cin, Cout, kw, stride, padl;
-  int K, Kp, FS, NF;
-  int relu, accum, flip;
-  int CinW, CoutW;
-  // phase decomposition of a strided backward-data (tds_conv_backward_data): weight tap of flipped tap j is
-  // tapOff + tapStep*(kw-1-j); output frame u of the launch is frame oOff + oStep*u of a tensor with ToutFull frames
-  int tapOff, tapStep, oOff, oStep, ToutFull;
-  int abl;  // timing-only ablations of the probe tool (W2L_TDS_ABL): 1 = no K loop, 2 = no slab staging, 4 = no output
-};
 
 __device__ __forceinline__ void tds_load_slab(const TdsConvP& p, float* slab, int b, int tIn0, int h0, int nf) {
   const int rowLen = kTdsBH * p.Cin;            // floats per slab frame (without pad)
@@ -815,22 +799,6 @@ __global__ __launch_bounds__(1024) void tds_conv_filter_reduce_k(const float* __
   }
 }
 
-float* sk_scratch(hipStream_t s, size_t bytes);
-// conv_tds_rs.hip: role-swapped 32x32x2 kernel for the TDS convolutions proper (C -> C, stride 1)
-bool tds_tz_try(const float* x, const float* w, const float* bias, const float* add, float* y, int B, int Tin, int Tout, int H,
-                int Cin, int Cout, int kw, int stride, int padl, int relu, int accum, int flip, int tapOff, int tapStep, int oOff,
-                int oStep, int ToutFull, int profKind, hipStream_t s, int* status);
-bool tds_rs_try(const float* x, const float* w, const float* bias, const float* add, float* y, int B, int Tin, int Tout, int H,
-                int C, int kw, int padl, int relu, int accum, int flip, int profKind, hipStream_t s, int* status);
-bool tds_c1_fwd_try(const float* x, const float* w, const float* bias, float* y, int B, int Tin, int Tout, int H, int Cout, int kw, int stride,
-                    int padl, int relu, int profKind, hipStream_t s, int* status);
-bool tds_c1_filter_try(const float* x, const float* dy, float* dw, float* dbias, int B, int Tin, int Tout, int H, int Cout, int kw, int stride,
-                       int padl, hipStream_t s, int* status);
-bool tds_tzf_strided_try(const float* x, const float* dy, float* dw, float* dbias, int B, int Tin, int Tout, int H, int Cin, int Cout, int kw,
-                         int stride, int padl, hipStream_t s, int* status);
-bool tds_rsf_try(const float* x, const float* dy, float* dw, float* dbias, int B, int Tin, int Tout, int H, int C, int kw, int padl,
-                 hipStream_t s, int* status);
-
 static inline int tds_out_len(int T, int kw, int stride, int padl, int padr) {
   int n = T + padl + padr - kw;
   return n < 0 ? 0 : n / stride + 1;
@@ -917,19 +885,8 @@ static bool try_launch_fwd2(const TdsConvP& pIn0, hipStream_t s, int* status, in
 
 static int launch_fwd(const TdsConvP& p, hipStream_t s, int profKind = PROF_TDSCONV) {
   int st2 = W2L_OK;
-  // the one-channel first layer (conv_tds_c1.hpp)
-  if (p.Cin == 1 && !p.flip && !p.add && !p.accum && p.CinW == 1 && p.CoutW == p.Cout && p.tapStep == 1 && p.oStep == 1 &&
-      tds_c1_fwd_try(p.x, p.w, p.bias, p.y, p.B, p.Tin, p.Tout, p.H, p.Cout, p.kw, p.stride, p.padl, p.relu, profKind, s, &st2))
-    return st2;
-  // block-Toeplitz generation (conv_tds_tz.hpp): the TDS convolutions proper and the strided layers between the stages
-  if (p.CinW == (p.flip ? p.Cout : p.Cin) && p.CoutW == (p.flip ? p.Cin : p.Cout) &&
-      tds_tz_try(p.x, p.w, p.bias, p.add, p.y, p.B, p.Tin, p.Tout, p.H, p.Cin, p.Cout, p.kw, p.stride, p.padl, p.relu, p.accum, p.flip,
-                 p.tapOff, p.tapStep, p.oOff, p.oStep, p.ToutFull, profKind, s, &st2))
-    return st2;
-  // the previous generation for the geometries it does not take: role-swapped 32x32x2 kernel (conv_tds_rs.hip)
-  if (p.stride == 1 && p.Cin == p.Cout && p.tapStep == 1 && p.oStep == 1 &&
-      tds_rs_try(p.x, p.w, p.bias, p.add, p.y, p.B, p.Tin, p.Tout, p.H, p.Cin, p.kw, p.padl, p.relu, p.accum, p.flip, profKind, s, &st2))
-    return st2;
+  // the specialised kernels first (conv_tds_special.hip), then the general ones of this file
+  if (tds_c1_fwd_try(p, profKind, s, &st2) || tds_tz_try(p, profKind, s, &st2)) return st2;
   if (try_launch_fwd2(p, s, &st2, profKind)) return st2;
   const size_t shmem = fwd_lds_bytes(p);
   if (shmem > 160 * 1024) return W2L_EUNSUPPORTED;
@@ -984,8 +941,7 @@ int tds_conv_backward_data(const w2l_conv_desc* d, const float* dy, const float*
     p.CinW = d->Cin; p.CoutW = d->Cout;
     p.tapOff = f; p.tapStep = st; p.oOff = c0; p.oStep = st; p.ToutFull = d->T;
     int st2 = W2L_OK;
-    if (tds_tz_try(p.x, p.w, p.bias, p.add, p.y, p.B, p.Tin, p.Tout, p.H, p.Cin, p.Cout, p.kw, p.stride, p.padl, p.relu, p.accum, p.flip,
-                   p.tapOff, p.tapStep, p.oOff, p.oStep, p.ToutFull, PROF_TDS_BWD_DATA, s, &st2)) {
+    if (tds_tz_try(p, PROF_TDS_BWD_DATA, s, &st2)) {
       if (st2 != W2L_OK) return st2;
       launched = true;
       continue;
@@ -1003,20 +959,14 @@ int tds_conv_backward_data(const w2l_conv_desc* d, const float* dy, const float*
 int tds_conv_backward_filter(const w2l_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias,
                              hipStream_t s) {
   const int To = tds_out_len(d->T, d->kw, d->stride, d->padl, d->padr);
-  if (d->stride == 1 && d->Cin == d->Cout) {  // the TDS convolutions proper: role-swapped 32x32x2 kernel (conv_tds_rs.hip)
-    int st2 = W2L_OK;
-    if (tds_rsf_try(x, dy, dw, dbias, d->B, d->T, To, d->H, d->Cin, d->kw, d->padl, s, &st2)) return st2;
-  }
-  if (d->Cin == 1) {  // the one-channel first layer (conv_tds_c1.hpp)
-    int st2 = W2L_OK;
-    if (tds_c1_filter_try(x, dy, dw, dbias, d->B, d->T, To, d->H, d->Cout, d->kw, d->stride, d->padl, s, &st2)) return st2;
-  }
-  {  // the strided layers between the TDS stages: block-Toeplitz filter gradient (conv_tds_tzf.hpp)
-    int st2 = W2L_OK;
-    if (tds_tzf_strided_try(x, dy, dw, dbias, d->B, d->T, To, d->H, d->Cin, d->Cout, d->kw, d->stride, d->padl, s, &st2)) return st2;
-  }
   TdsConvP p = make_p(d->B, d->T, To, d->H, d->Cin, d->Cout, d->kw, d->stride, d->padl, kTdsBTF);
   p.x = x;
+  {  // the specialised kernels first (conv_tds_special.hip), then the general ones of this file
+    int st2 = W2L_OK;
+    if (tds_rsf_try(p, dy, dw, dbias, s, &st2) || tds_c1_filter_try(p, dy, dw, dbias, s, &st2) ||
+        tds_tzf_strided_try(p, dy, dw, dbias, s, &st2))
+      return st2;
+  }
   const int rowTiles = (p.K + 1 + 15) / 16;
   if (rowTiles > 4 * kTdsMaxTilesPerWave) return W2L_EUNSUPPORTED;
   const int NT = d->Cout <= 16 ? 1 : 2;

@@ -1,14 +1,14 @@
-// conv_tds_rsf3.hpp -- the role-swapped TDS filter gradient (see conv_tds_rs.hip: tap = ga*GB + gb, both operands
-// time-shifted, K = time) with the machine shape of conv_tds_rs3.hpp: ONE workgroup per CU, wave roles split.
+// conv_tds_rsf3.hpp -- the role-swapped TDS filter gradient (see conv_tds_special.hip: tap = ga*GB + gb, both operands
+// time-shifted, K = time).  ONE workgroup per CU, wave roles split:
 //   * waves 0..HH-1 CONSUMERS: each owns one mel row of the tile and does nothing but fragment reads (two K steps per
 //     ds_read2_b32, next pair of steps already in registers) and NRT x NCT independent MFMA accumulators that live in
 //     registers over ALL tiles of the workgroup;
 //   * 4 MOVERS: raw buffer loads (frames outside the utterance arrive as zeros: no selects) -> registers -> the two
 //     time-fastest slabs of tile r, the loads of tile r+1 in flight, while the consumers are on tile r-1; the slabs are
 //     double-buffered, one LDS-only barrier per tile.
-// What this buys over tds_conv_rsf_k: there every workgroup staged (global latency exposed), multiplied and staged again,
-// and the 2-3 co-resident workgroups ran in lockstep; here staging costs the SIMD ~70 instructions per tile beside
-// 144-384 MFMAs per consumer wave (measured rule, tools/micro: every non-MFMA instruction a SIMD issues costs the
+// What this buys over a kernel whose workgroups all stage (global latency exposed), multiply and stage again, 2-3 of them
+// co-resident and in lockstep (the cooperative generation before this one): here staging costs the SIMD ~70 instructions
+// per tile beside 144-384 MFMAs per consumer wave (measured rule, tools/micro: every non-MFMA instruction a SIMD issues costs the
 // matrix pipe ~7-10 cycles, nothing overlaps for free -- so count instructions).
 //     C = 10: GA = 3, GB = 7, 8 mel rows, strips of 96 frames: 1 x 3 tiles of 32x32 per wave, two waves per SIMD
 //     C = 18: GA = 7, GB = 3, 4 mel rows, strips of 96 frames: 4 x 2 tiles per wave, one wave per SIMD
@@ -45,6 +45,11 @@ struct Rsf3Cfg {
   static_assert(TS % 4 == 0 && C % 2 == 0 && ROWS % 4 == 0, "strip length / channel count");
   static_assert(LDS <= 160 * 1024, "LDS");
 };
+
+__device__ __forceinline__ void rs3_barrier() {
+  // LDS-only barrier: the slab hand-offs are LDS traffic; global loads (next tile's pieces) stay in flight across it
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
 
 template <int C, int GA, int GB, int HH, int TS>
 __global__ __launch_bounds__((HH + 4) * 64) void tds_conv_rsf3_k(TdsRsf3P p, float* __restrict__ partial) {

@@ -3,7 +3,7 @@
 // recipes/streaming_convnets/inference/inference/module/nn/TDSBlock.cpp:58-70), forward and backward-data:
 // the BLOCK-TOEPLITZ form.
 //
-// What the role-swapped generations (conv_tds_rs.hip, conv_tds_rs3.hpp) pay for: tap GROUPS on the MFMA columns need an
+// What the role-swapped generations (retired; in the history of conv_tds_special.hip) paid for: tap GROUPS on the MFMA columns need an
 // overlap-add of the partial sums through LDS (1.2-1.6 DS and ~0.9 VALU instructions per 64-cycle MFMA), a time-fastest
 // slab that somebody has to transpose into LDS (the mover waves), and a ring / epilogue pipeline around both.  By the
 // issue model of tools/micro/mfma_rate.hip every DS instruction costs ~10 and every VALU ~3-5 cycles of matrix-pipe
