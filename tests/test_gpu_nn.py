@@ -193,7 +193,9 @@ def test_gemm_in_kernel_slab_reduction_is_stable(M, N, K, probe):
                                     (6016, 1440, 4320),    # TDS fc2 (c = 18): 9 x 160 columns
                                     (24000, 800, 2400),    # TDS fc2 (c = 10): 5 x 160 columns, 2 rounds + stream-K tail
                                     (800, 2400, 24000),    # dW: 5 x 160 rows (TALL), very long reduction
-                                    (320, 160, 64)])       # exactly two / one 160-tiles, two K steps
+                                    (320, 160, 64),        # exactly two / one 160-tiles, two K steps
+                                    (131, 160, 64),        # one 160-tile column, a second tile row with three valid rows
+                                    (12000, 1120, 3360)])  # a TDS fc shape (c = 14): 7 x 160 columns
 @pytest.mark.parametrize("akc,bkc", [(True, False), (True, True), (False, False), (False, True)])
 @pytest.mark.parametrize("mode", ["2", "3"])
 def test_gemm_160_wide_tiles(M, N, K, akc, bkc, mode, probe):
@@ -221,37 +223,6 @@ def test_gemm_160_wide_tiles(M, N, K, akc, bkc, mode, probe):
     assert rel(got, want) < TOL
     assert rel(gotr, np.maximum(want, 0)) < TOL
     assert rel(got, old.cpu().numpy()) < 1e-5
-
-
-@pytest.mark.parametrize("M,N,K", [(4, 4, 32), (260, 388, 96), (1028, 2052, 1440), (6016, 1440, 4320), (24000, 800, 2400),
-                                    (131, 160, 64), (12000, 1120, 3360)])
-@pytest.mark.parametrize("bkc", [False, True])
-def test_gemm_160_a_operand_straight_into_registers(M, N, K, bkc, probe):
-    """128x160 tiles with a k-contiguous A: the K loop that loads the wave's own A rows straight into the fragment registers
-    (gemm160_kernel<..., ADIR>, the default) against the all-LDS loop (W2L_GEMM_ADIR=0): same k-slot assignment, same sum
-    order -- bit-identical, incl. clamped edge rows, stream-K ranges and the bias + ReLU epilogue; and the float64 product"""
-    import os
-    from wav2letter_amd import ops
-    g = torch.Generator(device="cpu").manual_seed(7 * M + 5 * N + K)
-    A = torch.randn(M, K, generator=g)
-    Bm = torch.randn(K, N, generator=g) / K ** 0.5
-    bias = torch.randn(N, generator=g)
-    want = (A.double() @ Bm.double() + bias.double()).numpy()
-    Ad = A.cuda()
-    Bd = (Bm.T.contiguous() if bkc else Bm).cuda()
-    os.environ["W2L_GEMM_T160"] = "2"
-    try:
-        os.environ["W2L_GEMM_ADIR"] = "1"
-        got = ops.gemm(Ad, Bd, True, bkc, bias.cuda())
-        gotr = ops.gemm(Ad, Bd, True, bkc, bias.cuda(), relu=True)
-        os.environ["W2L_GEMM_ADIR"] = "0"
-        old = ops.gemm(Ad, Bd, True, bkc, bias.cuda())
-        oldr = ops.gemm(Ad, Bd, True, bkc, bias.cuda(), relu=True)
-    finally:
-        os.environ.pop("W2L_GEMM_T160")
-        os.environ.pop("W2L_GEMM_ADIR", None)
-    assert rel(got, want) < TOL
-    assert torch.equal(got, old) and torch.equal(gotr, oldr)
 
 
 @pytest.mark.parametrize("mode", ["2", "3"])

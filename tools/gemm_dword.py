@@ -1,4 +1,4 @@
-"""do the LDS-DMA kernels work on rows that are only dword aligned (odd leading dimensions)?  W2L_GEMM_UNALIGNED=2"""
+"""do the LDS-DMA kernels work on rows that are only dword aligned (odd leading dimensions)?"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

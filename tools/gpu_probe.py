@@ -46,14 +46,11 @@ def probe_gemm():
         L = _lib.lib()
         s = torch.cuda.current_stream().cuda_stream
         fl = 2.0 * M * N * K
-        for sk in ("1", "0"):
-            os.environ["W2L_GEMM_SK"] = sk
-            tf = timeit(lambda: L.w2l_linear_forward(M, K, N, x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), 1, s))
-            td = timeit(lambda: L.w2l_linear_backward_data(M, K, N, dy.data_ptr(), w.data_ptr(), dx.data_ptr(), 0, None, 1.0, s))
-            tw = timeit(lambda: L.w2l_linear_backward_weight(M, K, N, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), s))
-            print(f"[gemm] {name:7s} M={M} K={K} N={N} sk={sk}: fwd {tf:.3f} ms {fl / tf / 1e9:.1f} TF | "
-                  f"dX {td:.3f} ms {fl / td / 1e9:.1f} TF | dW {tw:.3f} ms {fl / tw / 1e9:.1f} TF", flush=True)
-        os.environ["W2L_GEMM_SK"] = "1"
+        tf = timeit(lambda: L.w2l_linear_forward(M, K, N, x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), 1, s))
+        td = timeit(lambda: L.w2l_linear_backward_data(M, K, N, dy.data_ptr(), w.data_ptr(), dx.data_ptr(), 0, None, 1.0, s))
+        tw = timeit(lambda: L.w2l_linear_backward_weight(M, K, N, x.data_ptr(), dy.data_ptr(), dw.data_ptr(), s))
+        print(f"[gemm] {name:7s} M={M} K={K} N={N}: fwd {tf:.3f} ms {fl / tf / 1e9:.1f} TF | "
+              f"dX {td:.3f} ms {fl / td / 1e9:.1f} TF | dW {tw:.3f} ms {fl / tw / 1e9:.1f} TF", flush=True)
 
 
 def probe_gemm160():
@@ -86,22 +83,6 @@ def probe_gemm160():
                   f"dX {td * 1e3:.0f} us {fl / td / 1e9:.1f} TF | dW {tw * 1e3:.0f} us {fl / tw / 1e9:.1f} TF", flush=True)
     os.environ.pop("W2L_GEMM_T160")
     print(f"[gemm160] sum over shapes (two passes each): 128x128 {tot['0']:.2f} ms, padded-area rule {tot['1']:.2f} ms", flush=True)
-
-
-def probe_gemmfwd():
-    """forward GEMM only (ablation runs: W2L_GEMM_ABL is read once per process)"""
-    L = _lib.lib()
-    s = torch.cuda.current_stream().cuda_stream
-    for name, M, K, N in [("fc1 s1", 24000, 800, 2400), ("fc2 s3", 6016, 4320, 1440), ("4096^3", 4096, 4096, 4096),
-                          ("8192^3", 8192, 8192, 8192)]:
-        x = torch.randn(M, K, device="cuda")
-        w = torch.randn(K, N, device="cuda") / K ** 0.5
-        b = torch.randn(N, device="cuda")
-        y = torch.empty(M, N, device="cuda")
-        fl = 2.0 * M * N * K
-        tf = timeit(lambda: L.w2l_linear_forward(M, K, N, x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), 1, s), n=20, warm=3)
-        print(f"[gemmfwd abl={os.environ.get('W2L_GEMM_ABL', '0')} glds={os.environ.get('W2L_GEMM_GLDS', '1')}] "
-              f"{name:7s} M={M} K={K} N={N}: {tf:.3f} ms {fl / tf / 1e9:.1f} TF", flush=True)
 
 
 def probe_ln():
@@ -270,6 +251,6 @@ if __name__ == "__main__":
     print("device:", torch.cuda.get_device_name(0), flush=True)
     for w in which:
         t0 = time.time()
-        {"gemm": probe_gemm, "gemm160": probe_gemm160, "gemmfwd": probe_gemmfwd, "ln": probe_ln, "conv": probe_conv, "convglu": probe_convglu, "feat": probe_feat, "asg": probe_asg, "fccbig": probe_fccbig, "fccstream": probe_fccstream,
+        {"gemm": probe_gemm, "gemm160": probe_gemm160, "ln": probe_ln, "conv": probe_conv, "convglu": probe_convglu, "feat": probe_feat, "asg": probe_asg, "fccbig": probe_fccbig, "fccstream": probe_fccstream,
          "vitbig": probe_vitbig}[w]()
         print(f"[{w}] done in {time.time() - t0:.1f} s", flush=True)

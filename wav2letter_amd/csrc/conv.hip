@@ -331,22 +331,16 @@ static inline int out_len(int T, int kw, int stride, int padl, int padr) {
   return n < 0 ? 0 : n / stride + 1;
 }
 
-static inline int pick_vec_rows(const float* p, int ld, int extent) {
-  if ((((uintptr_t)p) & 15) == 0 && ld % 4 == 0 && extent % 4 == 0) return 4;
-  if ((((uintptr_t)p) & 7) == 0 && ld % 2 == 0 && extent % 2 == 0) return 2;
-  return 1;
-}
-
 template <class AOp>
 static int conv_launch_rowsB(const AOp& a, const float* Bp, int ldb, int N, int K, const GemmOut& o, int epi,
                              int splitk, hipStream_t s) {
   // B is a plain "k-rows" matrix [K][N]
   if (N <= 16) return launch_skinny<AOp, PlainOp<false, 1>, 16>(a, PlainOp<false, 1>{Bp, ldb, N, K}, o, epi, splitk, s);
   if (N <= 32) return launch_skinny<AOp, PlainOp<false, 1>, 32>(a, PlainOp<false, 1>{Bp, ldb, N, K}, o, epi, splitk, s);
-  int v = pick_vec_rows(Bp, ldb, N);
-  if (v == 4) return launch128(a, PlainOp<false, 4>{Bp, ldb, N, K}, o, epi, splitk, s);
-  if (v == 2) return launch128(a, PlainOp<false, 2>{Bp, ldb, N, K}, o, epi, splitk, s);
-  return launch128(a, PlainOp<false, 1>{Bp, ldb, N, K}, o, epi, splitk, s);
+  int v = pick_vec(Bp, ldb, N);
+  if (v == 4) return launch128(a, PlainOp<false, 4>{Bp, ldb, N, K}, o, epi, s);
+  if (v == 2) return launch128(a, PlainOp<false, 2>{Bp, ldb, N, K}, o, epi, s);
+  return launch128(a, PlainOp<false, 1>{Bp, ldb, N, K}, o, epi, s);
 }
 
 // =====================================================================================================
@@ -640,7 +634,7 @@ W2L_API int w2l_conv_backward_data(const w2l_conv_desc* d, const float* dy, cons
   hipStream_t s = (hipStream_t)stream;
   if (N <= 16) return launch_skinny<ConvAOp, ConvWTOp, 16>(a, b, o, epi, 1, s);
   if (N <= 32) return launch_skinny<ConvAOp, ConvWTOp, 32>(a, b, o, epi, 1, s);
-  return launch128(a, b, o, epi, 1, s);
+  return launch128(a, b, o, epi, s);
 }
 
 // dx = add + backward-data(dy): the residual / upstream gradient joins in the epilogue instead of

@@ -1393,7 +1393,7 @@ int fcc_big_backward(int B, int T, int N, const float* trans, const float* grad,
   hipLaunchKernelGGL(fcc_big_exact_clear, dim3(64, (unsigned)B), dim3(256), 0, s, d, ws);
   W2L_LAUNCH_CHECK();
   // dA_raw[i][j] = sum_{t>=1,b} (g r_t)[b][i] * e_{t-1}[b][j] : both operands "k-rows", reduction over (t,b)
-  st = gemm_f32(ws.rg + (size_t)B * N, N, 0, ws.e, N, 0, transGrad, N, N, N, (T - 1) * B, nullptr, 0, 1, s);
+  st = gemm_f32(ws.rg + (size_t)B * N, N, 0, ws.e, N, 0, GemmOut{transGrad, nullptr, N, N, (T - 1) * B, N, 0}, s);
   if (st) return st;
   hipLaunchKernelGGL(fcc_big_scale_dtrans, dim3(2048), dim3(256), 0, s, N, trans, ws.rm, transGrad, ws.pack, ws.redo + B);
   W2L_LAUNCH_CHECK();

@@ -1,15 +1,20 @@
-// gemm.hpp -- operand loaders and launch interface of the fp32 MFMA GEMM engine.
+// gemm.hpp -- what every user of the fp32 MFMA GEMM engine sees (dispatch order: gemm.hip's header), in this order:
+//   GemmOut, gemm_epi       the output / epilogue descriptor of every GEMM kernel and the derivation of its EPI_* flags
+//   PlainOp                 register-staged operand loader (any alignment; vector width from pick_vec)
+//   prof_begin / prof_end   per-launch event brackets behind w2l_profile_*
+//   SkPlan, make_sk_plan    the stream-K schedule shared by all kernels: whole tiles one per workgroup, the tail's K iterations
+//                           in equal ranges, partial tiles added in range order (no atomics, run-to-run identical)
+//   gemm128_kernel          line 5 of the dispatch: 256 threads = 4 waves (2 x 2), block tile 128 x 128 x 32, each wave 2 x 2 MFMA
+//                           tiles of 32 x 32; operand tiles staged through LDS in K-major form As[k][m], Bs[k][n] (a half-wave's
+//                           fragment read is 32 consecutive dwords), double-buffered with register prefetch of the next K tile
+//   gemm128_fixup           adds the stream-K partial slabs of gemm128_kernel (and of gemm128g_kernel under W2L_GEMM_INFIX=0)
+//   gemm_skinny_kernel      N <= 32 (conv.hip's few-channel convolutions): 256 x 16 / 32 tiles, the only user of split K with
+//                           EPI_ATOMIC (launch_skinny's splitk)
+//   launch128, launch_skinny, gemm_f32, gemm_glds_raw
 #pragma once
 #include <vector>
 
 #include "common.hpp"
-
-#ifndef W2L_MIDSTORE
-#define W2L_MIDSTORE 0
-#endif
-#ifndef W2L_BRANCHFREE
-#define W2L_BRANCHFREE 0
-#endif
 
 namespace w2l {
 
@@ -48,7 +53,6 @@ struct GemmOut {
   uint16_t* imgTrans = nullptr;
   const uint16_t* maskH = nullptr;
   int ldImgRows = 0, ldImgTrans = 0, ldMaskH = 0;
-  int ntStore = 0;   // probe (W2L_GEMM_NTSTORE): the wide epilogues store C nontemporal
 };
 
 inline void gemm_set_row_remap(GemmOut& o, int pin, int pout, int off) {
@@ -143,16 +147,15 @@ struct PlainOp {
       for (int j = 0; j < NP; ++j) {
         const int gi = i0 + rr + RPP * j, gk = k0 + kc;
         const bool ok = gi < extent && gk < K;
-        // branch-free guard: load from a clamped (always valid) address, then select zero
-        const float* src = p + (size_t)((ok || !W2L_BRANCHFREE) ? gi : 0) * ld + ((ok || !W2L_BRANCHFREE) ? gk : 0);
+        const float* src = p + (size_t)gi * ld + gk;
         if (V == 4) {
-          float4 v = (W2L_BRANCHFREE || ok) ? *(const float4*)src : make_float4(0.f, 0.f, 0.f, 0.f);
+          float4 v = ok ? *(const float4*)src : make_float4(0.f, 0.f, 0.f, 0.f);
           r[4 * j] = ok ? v.x : 0.f; r[4 * j + 1] = ok ? v.y : 0.f; r[4 * j + 2] = ok ? v.z : 0.f; r[4 * j + 3] = ok ? v.w : 0.f;
         } else if (V == 2) {
-          float2 v = (W2L_BRANCHFREE || ok) ? *(const float2*)src : make_float2(0.f, 0.f);
+          float2 v = ok ? *(const float2*)src : make_float2(0.f, 0.f);
           r[2 * j] = ok ? v.x : 0.f; r[2 * j + 1] = ok ? v.y : 0.f;
         } else {
-          const float v = (W2L_BRANCHFREE || ok) ? *src : 0.f;
+          const float v = ok ? *src : 0.f;
           r[j] = ok ? v : 0.f;
         }
       }
@@ -166,15 +169,15 @@ struct PlainOp {
       for (int j = 0; j < NP; ++j) {
         const int gi = i0 + ic, gk = k0 + kr + RPP * j;
         const bool ok = gi < extent && gk < K;
-        const float* src = p + (size_t)((ok || !W2L_BRANCHFREE) ? gk : 0) * ld + ((ok || !W2L_BRANCHFREE) ? gi : 0);
+        const float* src = p + (size_t)gk * ld + gi;
         if (V == 4) {
-          float4 v = (W2L_BRANCHFREE || ok) ? *(const float4*)src : make_float4(0.f, 0.f, 0.f, 0.f);
+          float4 v = ok ? *(const float4*)src : make_float4(0.f, 0.f, 0.f, 0.f);
           r[4 * j] = ok ? v.x : 0.f; r[4 * j + 1] = ok ? v.y : 0.f; r[4 * j + 2] = ok ? v.z : 0.f; r[4 * j + 3] = ok ? v.w : 0.f;
         } else if (V == 2) {
-          float2 v = (W2L_BRANCHFREE || ok) ? *(const float2*)src : make_float2(0.f, 0.f);
+          float2 v = ok ? *(const float2*)src : make_float2(0.f, 0.f);
           r[2 * j] = ok ? v.x : 0.f; r[2 * j + 1] = ok ? v.y : 0.f;
         } else {
-          const float v = (W2L_BRANCHFREE || ok) ? *src : 0.f;
+          const float v = ok ? *src : 0.f;
           r[j] = ok ? v : 0.f;
         }
       }
@@ -293,16 +296,12 @@ struct SkPlan {
   float* slabs;  // [skBlocks][2][128*128]
   int grouped;   // tile rasterisation: 0 = M-fastest, 1 = groups of 8 tile-columns, N-fastest inside a group
   unsigned* counters;  // per stream-K tile arrival tickets for the in-kernel slab reduction (null: separate fix-up launch)
-  // aligned K split (gemm160 only; 0 = off): the K axis is cut into `ksplit` chunks of kChunk K tiles, the SAME cut for
-  // every tile, and the units (chunk, tile) are dealt chunk-major: unit u = worker + round * workers.  The 64 workers of
+  // aligned K split (planned by launch128h for the bf16 kernel only; 0 = off): the K axis is cut into `ksplit` chunks of kChunk K
+  // tiles, the SAME cut for every tile, and the units (chunk, tile) are dealt chunk-major: unit u = worker + round * workers.  The 64 workers of
   // an XCD then multiply 64 neighbouring tiles over the same K range at the same time and share their operand panels
   // in that XCD's L2 -- the classic stream-K ranges start at a different k in every tile and share nothing (weight
   // gradients: 10 % L2 hits, profiles/r02_run17_*).  One partial slab per unit (index u), ksplit arrivals per tile.
   int ksplit = 0, kChunk = 0;
-  // probe library only (W2L_GEMM_DBG = device address): per workgroup {start, end (100 MHz ticks), hardware id, XCC id}
-  long long* dbg = nullptr;
-  // wave priority of the two workgroups that share a CU (g_tile_prio, gemm_glds.hpp): 0 = leave it, 1 = alternate per segment
-  int prio = 0;
 };
 constexpr int kSkSlots = 512;           // resident 256-thread workgroups (2 per CU)
 constexpr int kSlabFloats = 128 * 128;
@@ -333,7 +332,7 @@ inline SkPlan make_sk_plan(int M, int N, int K, bool allowSk, int tileM = 128, i
   p.kTiles = (K + 31) / 32;
   const int tiles = p.tilesM * p.tilesN;
   p.dpTiles = tiles; p.skTiles = 0; p.skBlocks = 0; p.slabs = nullptr; p.grouped = 0; p.counters = nullptr;
-  p.ksplit = 0; p.kChunk = 0; p.dbg = nullptr; p.prio = 0;
+  p.ksplit = 0; p.kChunk = 0;
   if (!allowSk || p.kTiles < 8) return p;
   const int rounds = (tiles + slots - 1) / slots;
   const double eff = (double)tiles / ((double)rounds * slots);
@@ -374,7 +373,6 @@ __host__ __device__ inline void sk_tile_ranges(const SkPlan& p, int t, int& sFir
   while (s + 1 < p.skBlocks && sk_begin(p, s + 1) < te) ++s;
   sLast = s;
 }
-bool sk_enabled();                               // W2L_GEMM_SK=0 turns the schedule off (A/B runs)
 
 // ---------------------------------------------------------------- kernels
 template <class AOp, class BOp>
@@ -444,13 +442,6 @@ __device__ __forceinline__ void gemm128_mainloop(const AOp& aop, const BOp& bop,
     float c0, c1, d0, d1;
 #pragma unroll
     for (int kp = 0; kp < BK / 2; kp += 2) {
-      if (W2L_MIDSTORE && kp == BK / 4 && more) {
-        // the next tile's registers go to the other LDS buffer in the MIDDLE of the MFMA phase (their
-        // global loads were issued ~2000 cycles ago), so no separate write phase precedes the barrier
-        aop.store(cur ? As0 : As1, LDA_S, ra, tid);
-        bop.store(cur ? Bs0 : Bs1, LDB_S, rb, tid);
-        __builtin_amdgcn_sched_barrier(0);
-      }
       c0 = ar[(2 * kp + 2) * LDA_S]; c1 = ar[(2 * kp + 2) * LDA_S + 32];
       d0 = br[(2 * kp + 2) * LDB_S]; d1 = br[(2 * kp + 2) * LDB_S + 32];
       __builtin_amdgcn_sched_barrier(0);
@@ -470,7 +461,7 @@ __device__ __forceinline__ void gemm128_mainloop(const AOp& aop, const BOp& bop,
       acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(c1, d1, acc[1][1], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (!W2L_MIDSTORE && more) {
+    if (more) {
       aop.store(cur ? As0 : As1, LDA_S, ra, tid);
       bop.store(cur ? Bs0 : Bs1, LDB_S, rb, tid);
     }
@@ -560,9 +551,8 @@ __global__ __launch_bounds__(256, 2) void gemm128_kernel(AOp aop, BOp bop, GemmO
 
 // one WAVEFRONT per quadrant of a stream-K tile (grid = 4 x skTiles workgroups of 64 threads: four times the
 // waves of the one-workgroup-per-tile version, the kernel is latency-bound on the slab reads): add the
-// partial slabs in range order, then the epilogue
-template <int kUnused>
-__global__ __launch_bounds__(64) void gemm128_fixup(GemmOut out, SkPlan plan) {
+// partial slabs in range order, then the epilogue.  (static: this header is part of several translation units)
+static __global__ __launch_bounds__(64) void gemm128_fixup(GemmOut out, SkPlan plan) {
   const int t = blockIdx.x >> 2;  // index inside the stream-K region
   const int wave = blockIdx.x & 3, lane = threadIdx.x;
   const long long tb = (long long)t * plan.kTiles, te = tb + plan.kTiles;
@@ -705,12 +695,10 @@ __global__ __launch_bounds__(256, 2) void gemm_skinny_kernel(AOp aop, BOp bop, G
 
 // ---------------------------------------------------------------------------
 template <class AOp, class BOp>
-inline int launch128(const AOp& a, const BOp& b, GemmOut o, int epi, int splitk, hipStream_t s) {
+inline int launch128(const AOp& a, const BOp& b, GemmOut o, int epi, hipStream_t s) {
   constexpr int BK = 32;
-  (void)splitk;          // K is split by the stream-K schedule, deterministically
-  epi &= ~EPI_ATOMIC;    // (callers of the old atomic split-K path need no pre-zeroed C any more)
   const size_t shmem = 2 * (size_t)BK * ((128 + AOp::kPad) + (128 + BOp::kPad)) * sizeof(float);
-  SkPlan plan = make_sk_plan(o.M, o.N, o.K, sk_enabled());
+  SkPlan plan = make_sk_plan(o.M, o.N, o.K, true);
   if (plan.skBlocks > 0) {
     plan.slabs = sk_scratch(s, kSkScratchBytes);
     if (!plan.slabs) plan = make_sk_plan(o.M, o.N, o.K, false);
@@ -719,7 +707,7 @@ inline int launch128(const AOp& a, const BOp& b, GemmOut o, int epi, int splitk,
   o.epi = epi;
   prof_begin(s, 2.0 * o.M * (double)o.N * o.K, PROF_GEMM128, o.M, o.N, o.K, 1);
   hipLaunchKernelGGL((gemm128_kernel<AOp, BOp>), grid, block, shmem, s, a, b, o, plan);
-  if (plan.skBlocks > 0) hipLaunchKernelGGL(gemm128_fixup<0>, dim3((unsigned)plan.skTiles * 4), dim3(64), 0, s, o, plan);
+  if (plan.skBlocks > 0) hipLaunchKernelGGL(gemm128_fixup, dim3((unsigned)plan.skTiles * 4), dim3(64), 0, s, o, plan);
   prof_end(s);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
@@ -738,20 +726,26 @@ inline int launch_skinny(const AOp& a, const BOp& b, GemmOut o, int epi, int spl
   return W2L_OK;
 }
 
-// C[M][N] = op(A)[M][K] . op(B)[K][N] (+bias[n]) (relu) ; a_kcontig: A is [M][K] row-major;
-// b_kcontig: B is stored [N][K] row-major.  epi = EPI_* flags; splitk > 1 needs EPI_ATOMIC
-// and a pre-zeroed C.
-struct GemmExtra {  // optional epilogue operands of gemm_f32
-  const float* addend = nullptr;
-  uint32_t dropThr = 0, dropSeed = 0, dropStream = 0;
-  float dropScale = 1.f;
-  float* colsum = nullptr;  // also produce colsum[n] = sum_k B[k][n] (GemmOut::colsum) where the kernel that runs can ...
-  mutable bool colsumDone = false;   // ... and say so: false -> the caller runs its own column-sum launch
-};
+// widest global-load vector (4 / 2 / 1 floats) that the alignment of an operand allows: base pointer, leading dimension and the
+// extent along the contiguous index
+inline int pick_vec(const float* p, int ld, int extent) {
+  if ((((uintptr_t)p) & 15) == 0 && ld % 4 == 0 && extent % 4 == 0) return 4;
+  if ((((uintptr_t)p) & 7) == 0 && ld % 2 == 0 && extent % 2 == 0) return 2;
+  return 1;
+}
+
+// the EPI_* flags of a GemmOut: those the caller set in o.epi (EPI_BIAS, EPI_RELU, EPI_ACCUM into C itself, EPI_ATOMIC) plus the
+// ones that follow from the operands that are set -- the ONE place where they are derived
+inline int gemm_epi(const GemmOut& o) {
+  return o.epi | ((o.mask || o.maskH) ? EPI_MASK : 0) | (o.addend ? EPI_ACCUM : 0) | (o.dropThr ? EPI_DROPOUT : 0);
+}
+
 int colsum(const float* x, float* out, size_t M, int N, hipStream_t s);   // conv.hip: out[n] = sum_m x[m][n]
-int gemm_f32(const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, float* C,
-             int ldc, int M, int N, int K, const float* bias, int epi, int splitk, hipStream_t s,
-             const float* mask = nullptr, float maskScale = 1.f, const GemmExtra* extra = nullptr);
+// C[M][N] = op(A)[M][K] . op(B)[K][N] with the epilogue o describes (gemm_epi); a_kcontig: A is [M][K] row-major; b_kcontig: B
+// is stored [N][K] row-major.  o.colsum: also produce colsum[n] = sum_k B[k][n] where the kernel that runs can; *colsumDone says
+// whether it did (false: the caller runs its own column-sum launch).
+int gemm_f32(const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, GemmOut o, hipStream_t s,
+             bool* colsumDone = nullptr);
 // LDS-DMA kernels on caller-prepared operand views (see gemm.hip); o carries M, N, K, C, ldc, bias and the row remap
 int gemm_glds_raw(const float* A, int lda, bool akc, size_t aBytes, const float* B, int ldb, bool bkc, size_t bBytes,
                   GemmOut o, int epi, hipStream_t s);

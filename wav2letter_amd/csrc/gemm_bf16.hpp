@@ -203,7 +203,7 @@ float* sk_scratch(hipStream_t s, size_t bytes);
 
 template <bool AKC, bool BKC>
 inline int launch128_bf16(const BfOp<AKC>& a, const BfOp<BKC>& b, GemmOut o, int epi, hipStream_t s) {
-  o.epi = epi & ~EPI_ATOMIC;
+  o.epi = epi;
   const int tilesM = (o.M + 127) / 128, tilesN = (o.N + 127) / 128, tiles = tilesM * tilesN;
   const int ktAll = (o.K + 31) / 32;
   int splitK = 1;

@@ -207,23 +207,11 @@ __global__ __launch_bounds__(256, 2) void gemm128h_kernel(GOp aop, GOp bop, Gemm
     if (!doEpi) {
       gemm128_store_partial(plan.slabs + (size_t)seg.slab * kSlabFloats, acc);
       if (plan.counters) {
-        // in-kernel slab reduction: the same release / ticket / acquire hand-over as gemm128g_kernel (see there)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* flag = (int*)(smem + (stage ^ 1) * kGStageFloats);  // the stage the K loop has just released
+        // in-kernel slab reduction (g_slab_handover): the tile's last arriver adds its slabs in range / chunk order
         const int t = seg.tile - plan.dpTiles;
-        if (tid == 0) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          *flag = (int)__hip_atomic_fetch_add(plan.counters + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        const int ticket = *flag;
         int sF = 0, sL = plan.ksplit - 1;   // aligned K split: chunk sr of this tile is slab sr * skTiles + t
         if (!plan.ksplit) sk_tile_ranges(plan, t, sF, sL);
-        if (ticket == sL - sF) {  // uniform: last arriver
-          if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          __syncthreads();
+        if (g_slab_handover(plan.counters + t, (int*)(smem + (stage ^ 1) * kGStageFloats), sL - sF)) {
 #pragma unroll
           for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -395,11 +383,6 @@ __global__ __launch_bounds__(512, 1) void gemm256h_kernel(GOp aop, GOp bop, Gemm
   }
 }
 
-// which tile shape: 1 = 256 x 256 (W2L_GEMM_H256=1 / 0 force it on / off for A/B runs; default by problem size)
-int h256_mode();
-bool sk_forced();
-bool ksplit_enabled();   // W2L_GEMM_KSPLIT=0 (probe build) turns the aligned K split off
-
 // A [M][lda], B [N][ldb] bf16 (lda, ldb in bf16 elements, even, >= Kp), Kp = K rounded up to 64: columns K .. Kp of every
 // row must be ZERO in both operands (convert.hip writes them so).  W2L_EUNSUPPORTED when the schedule cannot run in-kernel.
 // aView / bView (bytes; 0 = a dense image): the address range of an operand whose rows OVERLAP (row stride < Kp: the
@@ -416,7 +399,6 @@ inline int launch128h(const uint16_t* A, int lda, const uint16_t* B, int ldb, Ge
   const unsigned long long ab = ta ? 2ull * (unsigned long long)o.K * lda : aView ? aView : 2ull * ((unsigned long long)(o.M - 1) * lda + Kp);
   const unsigned long long bb = tb ? 2ull * (unsigned long long)o.K * ldb : bView ? bView : 2ull * ((unsigned long long)(o.N - 1) * ldb + Kp);
   if (ab >= 0x7fffffffull || bb >= 0x7fffffffull) return W2L_EUNSUPPORTED;
-  epi &= ~EPI_ATOMIC;
   const double flops = 2.0 * o.M * (double)o.N * o.K;
   o.epi = epi;
   const int wide = (((uintptr_t)o.C) & 15) == 0 && o.ldc % 4 == 0 && (!o.mask || (((uintptr_t)o.mask) & 15) == 0) &&
@@ -441,8 +423,7 @@ inline int launch128h(const uint16_t* A, int lda, const uint16_t* B, int ldb, Ge
   // (up to 512 tiles every workgroup is resident from the start and runs at 0.80 us per K tile, shared CU or not)
   const double t1 = tiles1 <= 512 ? kt * 0.80 + 5.0 : (double)((tiles1 + 255) / 256) * (kt * (kt >= 96 ? 0.54 : 0.45) + 5.0);
   const double t2 = (double)((tiles2 + 255) / 256) * (kt * 2.0 + 8.0);
-  const int mode = h256_mode();
-  const bool big = !ta && !tb && o.M >= 256 && o.N >= 256 && tiles2 < (1 << 30) && (mode == 1 || (mode < 0 && t2 < t1));
+  const bool big = !ta && !tb && o.M >= 256 && o.N >= 256 && tiles2 < (1 << 30) && t2 < t1;
   SkPlan plan;
   if (big) {
     plan = make_sk_plan(o.M, o.N, Kp / 2, false, 256, 256, kH2Slots);
@@ -453,7 +434,7 @@ inline int launch128h(const uint16_t* A, int lda, const uint16_t* B, int ldb, Ge
     // cut for every tile, units (chunk, tile) dealt chunk-major -- the 64 workers of an XCD run neighbouring tiles over the SAME
     // k range and share the panels in its L2; one partial slab per unit, added in chunk order by the tile's last arriver.
     int X = 0;
-    if (sk_enabled() && ksplit_enabled() && kt >= 64 && tiles1 * 2 <= 2 * kSkSlots) {
+    if (kt >= 64 && tiles1 * 2 <= 2 * kSkSlots) {
       double bestT = t1;
       for (int x = 2; x <= 8; ++x) {
         const long long units = tiles1 * x;
@@ -463,7 +444,7 @@ inline int launch128h(const uint16_t* A, int lda, const uint16_t* B, int ldb, Ge
         if (tx < (X ? bestT : 0.8 * t1)) { bestT = tx; X = x; }   // the models are +-15 %: a split must win clearly
       }
     }
-    const bool sk = X == 0 && sk_enabled() && (sk_forced() || (tiles1 <= 128 && kt >= 96));
+    const bool sk = X == 0 && tiles1 <= 128 && kt >= 96;
     plan = make_sk_plan(o.M, o.N, Kp / 2, sk);
     if (X) {
       plan.skTiles = plan.dpTiles; plan.dpTiles = 0;

@@ -18,8 +18,14 @@
 //   * tiles are rasterised in groups of 8 tile-columns, N-fastest inside a group, and the worker id
 //     is XCD-major, so the 64 workgroups of one XCD work on an 8x8 block of tiles that shares
 //     8 + 8 operand panels in that XCD's L2.
-// Requirements (checked by the host; otherwise gemm128_kernel runs): K % 32 == 0, 16-byte aligned
-// operand pointers and leading dimensions, extents % 4 == 0.
+// Shapes (line 4 of the dispatch in gemm.hip's header; launch128g): K % 32 == 0 and either 16-byte aligned operand pointers
+// and leading dimensions with extents % 4 == 0, or dword-aligned operands below 2 GiB; whatever gemm160_kernel does not take.
+// Two instances per operand layout pair:
+//   BUF = true   buffer-addressed LDS-DMA (`buffer_load_dwordx4 ... lds`: 32-bit offsets, bounds-checked): both operands below 2 GiB
+//   BUF = false  64-bit `global_load_lds` addresses: what runs for (strictly aligned) operands of 2 GiB and more
+// Stream-K partial tiles are added inside the launch (g_slab_handover; up to 1024 stream-K tiles), or by gemm128_fixup.
+// Also here, shared with gemm_t160.hpp and gemm_bf16g.hpp: GOp, the swizzled piece addressing, g_segment (the persistent
+// schedule), gemm128g_epilogue_wide and g_slab_handover.
 #pragma once
 #include <cstdlib>
 
@@ -215,7 +221,7 @@ __device__ __forceinline__ void gemm128g_epilogue_wide(const GemmOut& out, int m
         }
         f32x4 w4;
         w4[0] = v[0]; w4[1] = v[1]; w4[2] = v[2]; w4[3] = v[3];
-        if (!IMG || out.C) { if (out.ntStore) __builtin_nontemporal_store(w4, (f32x4*)dst); else *(f32x4*)dst = w4; }
+        if (!IMG || out.C) *(f32x4*)dst = w4;
         if (IMG && out.imgRows) {
           u32x2 h;
           h[0] = g_pack2(v[0], v[1]); h[1] = g_pack2(v[2], v[3]);
@@ -316,45 +322,31 @@ __device__ __forceinline__ GSeg g_pin(GSeg s) {
   return s;
 }
 
-constexpr int kGemmPrioMode = 0;   // the product's value (W2L_GEMM_PRIO overrides it in the probe library)
-__device__ __forceinline__ void g_dbg_record(long long* dbg, long long t0) {
-  unsigned hw, xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  long long* d = dbg + 4 * (size_t)blockIdx.x;
-  d[0] = t0; d[1] = wall_clock64(); d[2] = hw; d[3] = xcc;
-}
-// Fair shares for the two workgroups of a CU.  Left alone, one of the pair runs ~8 % faster than the other for the whole launch (the
-// arbiter's tie-break is not fair), finishes 80 - 140 us early and leaves its partner alone on the CU for 10 - 19 % of the launch
-// (profiles/r06_run35_gemm_workgroup_end_times.log) -- and one workgroup alone does not keep the matrix pipe busy through its
-// barriers and epilogues.  mode 1: the pair swaps priority every segment (who is high first follows the LDS allocation base), so
-// that over two segments both get the same share.  mode 2 (probe): the second workgroup stays low (sensitivity check).
-__device__ __forceinline__ int g_lds_second() {
-  unsigned la;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_LDS_ALLOC)" : "=s"(la));
-  return (la & 0xfffu) != 0;
-}
-__device__ __forceinline__ void g_tile_prio(int mode, int second, int ord) {
-  if (mode == 1) {
-    if ((ord + second) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-  } else if (mode == 2) {
-    if (second) __builtin_amdgcn_s_setprio(0); else __builtin_amdgcn_s_setprio(1);
+// Hand-over of the in-kernel slab reduction (replaces the fix-up launch; cdna_hip_programming.md, in-launch split-K reduction
+// recipe), called by every thread of a workgroup that has just stored a partial slab of stream-K tile `counter`.  Publish: every
+// wave drains its slab stores, one lane releases at agent scope and draws the tile's arrival ticket (handed to the other waves
+// through *flag, an LDS word nobody else uses now: the stage the K loop has just released).  The workgroup that draws ticket
+// `last` (= arrivals - 1: uniform) is the tile's last arriver: it acquires and returns true -- the caller then adds ALL slabs of
+// the tile from memory in range order (its own included: deterministic), runs the ordinary epilogue and re-zeroes the ticket.
+// The order and the scopes below are the protocol: do not reorder.
+__device__ __forceinline__ bool g_slab_handover(unsigned* counter, int* flag, int last) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    *flag = (int)__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-}
-inline int gemm_prio_mode() {
-  static const int v = [] { const char* e = tune_env("W2L_GEMM_PRIO"); return e ? atoi(e) : kGemmPrioMode; }();
-  return v;
-}
-inline long long* gemm_dbg_ptr() {
-  const char* e = tune_env("W2L_GEMM_DBG");
-  return e ? (long long*)strtoull(e, nullptr, 10) : nullptr;
+  __syncthreads();
+  const int ticket = *flag;
+  if (ticket != last) return false;
+  if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  __syncthreads();  // (also: every wave has read the ticket before the stage becomes epilogue scratch)
+  return true;
 }
 
-// ABL: timing-only ablations (results are garbage) selected by W2L_GEMM_ABL for the probe tool:
-//   1 = no LDS-DMA, 2 = no per-K-tile barrier, 4 = no fragment reads in the loop, 8 = no epilogue,
-//   16 = LDS-DMA always re-reads K tile 0 (cache-resident source), 32 = LDS-DMA of the A operand only,
-//   64 = every tile is tile 0 (operands and output stay cache-resident: isolates new-panel memory effects)
-template <bool AKC, bool BKC, int ABL = 0, bool BUF = false>
+// BUF: buffer-addressed LDS-DMA (the default); false: 64-bit global_load_lds addresses, for operands of 2 GiB and more
+template <bool AKC, bool BKC, bool BUF = false>
 __global__ __launch_bounds__(256, 2) void gemm128g_kernel(GOp aop, GOp bop, GemmOut out, SkPlan plan, int workers, int wide) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -368,8 +360,6 @@ __global__ __launch_bounds__(256, 2) void gemm128g_kernel(GOp aop, GOp bop, Gemm
 
   GSeg seg = g_pin(g_segment(plan, w, workers, 0));
   if (!seg.valid) return;
-  const long long dbgT0 = plan.dbg ? wall_clock64() : 0;
-  const int second = plan.prio ? g_lds_second() : 0;
   const float* qa[4];
   const float* qb[4];
   uint32_t va[4], vb[4];
@@ -379,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void gemm128g_kernel(GOp aop, GOp bop, Gemm
     rb = __builtin_amdgcn_make_buffer_rsrc((void*)bop.p, 0, (int)bop.bytes, 0x00020000);
   }
   int bx, by;
-  sk_tile_xy(plan, (ABL & 64) ? 0 : seg.tile, bx, by);
+  sk_tile_xy(plan, seg.tile, bx, by);
   if (BUF) {
     g_init_offs<AKC>(va, aop, bx * 128, wave, lane);
     g_init_offs<BKC>(vb, bop, by * 128, wave, lane);
@@ -391,16 +381,13 @@ __global__ __launch_bounds__(256, 2) void gemm128g_kernel(GOp aop, GOp bop, Gemm
   } else {
     g_init_ptrs<AKC>(qa, aop, bx * 128, wave, lane);
     g_init_ptrs<BKC>(qb, bop, by * 128, wave, lane);
-    if (!(ABL & 1)) {
-      g_issue(qa, aStep * seg.kb, smem, wave);
-      g_issue(qb, bStep * seg.kb, smem + 4096, wave);
-    }
+    g_issue(qa, aStep * seg.kb, smem, wave);
+    g_issue(qb, bStep * seg.kb, smem + 4096, wave);
   }
   int stage = 0;
   __syncthreads();  // (drains the LDS-DMA: vmcnt(0) precedes the barrier)
 
   for (int ord = 0;; ++ord) {
-    if (plan.prio) g_tile_prio(plan.prio, second, ord);
     const GSeg nxt = g_pin(g_segment(plan, w, workers, ord + 1));
     // bias of this lane's four output columns, fetched at the START of the tile (its latency hides under the K loop)
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -424,10 +411,6 @@ __global__ __launch_bounds__(256, 2) void gemm128g_kernel(GOp aop, GOp bop, Gemm
       float fa[2][2][4], fb[2][2][4];
       g_frag<AKC>(fa[0], As, wm, 0, li, lh);
       g_frag<BKC>(fb[0], Bs, wn, 0, li, lh);
-      if (ABL & 4) {
-        g_frag<AKC>(fa[1], As, wm, 1, li, lh);
-        g_frag<BKC>(fb[1], Bs, wn, 1, li, lh);
-      }
       // What goes to the other stage during this iteration: the next K tile, or the first K tile of
       // the next segment, or (very last iteration of this worker) a harmless re-load of this tile.
       // Every wave has passed the barrier that ended the previous iteration, so nobody reads that stage.
@@ -436,7 +419,7 @@ __global__ __launch_bounds__(256, 2) void gemm128g_kernel(GOp aop, GOp bop, Gemm
         offA += aStep; offB += bStep;
       } else if (nxt.valid) {
         int nbx, nby;
-        sk_tile_xy(plan, (ABL & 64) ? 0 : nxt.tile, nbx, nby);
+        sk_tile_xy(plan, nxt.tile, nbx, nby);
         if (BUF) {
           g_init_offs<AKC>(va, aop, nbx * 128, wave, lane);
           g_init_offs<BKC>(vb, bop, nby * 128, wave, lane);
@@ -463,60 +446,37 @@ __global__ __launch_bounds__(256, 2) void gemm128g_kernel(GOp aop, GOp bop, Gemm
           __builtin_amdgcn_sched_barrier(0);
           const int step = 4 * g + q;
           if (q == 0) {
-            if (g < 3 && !(ABL & 4)) {
+            if (g < 3) {
               g_frag<AKC>(fa[cur ^ 1], As, wm, g + 1, li, lh);
               g_frag<BKC>(fb[cur ^ 1], Bs, wn, g + 1, li, lh);
             }
           } else {
             const int piece = step - 1 - g;  // steps 1,2,3,5,6,7,9,10 -> pieces 0..7
             if (BUF) {
-              if (!(ABL & 1)) {
-                if (piece < 4) g_issue1_buf(ra, va[piece], sOffA, An, wave, piece);
-                else if (piece < 8) g_issue1_buf(rb, vb[piece - 4], sOffB, An + 4096, wave, piece - 4);
-              }
-            } else if (!(ABL & 1)) {
-              if (piece < 4) g_issue1(qa[piece], (ABL & 16) ? 0 : offA, An, wave, piece);
-              else if (piece < 8 && !(ABL & 32)) g_issue1(qb[piece - 4], (ABL & 16) ? 0 : offB, An + 4096, wave, piece - 4);
+              if (piece < 4) g_issue1_buf(ra, va[piece], sOffA, An, wave, piece);
+              else if (piece < 8) g_issue1_buf(rb, vb[piece - 4], sOffB, An + 4096, wave, piece - 4);
+            } else {
+              if (piece < 4) g_issue1(qa[piece], offA, An, wave, piece);
+              else if (piece < 8) g_issue1(qb[piece - 4], offB, An + 4096, wave, piece - 4);
             }
           }
           __builtin_amdgcn_sched_barrier(0);
         }
       }
       stage ^= 1;
-      if (!(ABL & 2)) __syncthreads();  // the stage just filled has landed (vmcnt(0)) and is visible to all waves
+      __syncthreads();  // the stage just filled has landed (vmcnt(0)) and is visible to all waves
     }
 
     bool doEpi = seg.slab < 0;  // whole tile: epilogue straight from the accumulators
     int resetTicket = -1;
-    if (ABL & 8) {
-      float t = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) t += acc[0][0][r] + acc[0][1][r] + acc[1][0][r] + acc[1][1][r];
-      if (t == 123.456f) out.C[0] = t;  // keeps every accumulator live
-      doEpi = false;
-    } else if (!doEpi) {
+    if (!doEpi) {
       gemm128_store_partial(plan.slabs + (size_t)seg.slab * kSlabFloats, acc);
       if (plan.counters) {
-        // In-kernel slab reduction (replaces the fix-up launch).  Publish: every wave drains its slab stores, one lane
-        // releases at agent scope and draws the tile's arrival ticket; the workgroup that draws the LAST ticket acquires
-        // and adds ALL slabs of the tile from memory in range order (its own included: deterministic), then runs the
-        // ordinary epilogue below and re-zeroes the ticket (cdna_hip_programming.md, in-launch split-K reduction recipe).
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* flag = (int*)(smem + (stage ^ 1) * kGStageFloats);  // the stage the K loop has just released
+        // in-kernel slab reduction (g_slab_handover): the tile's last arriver adds its slabs in range order
         const int t = seg.tile - plan.dpTiles;
-        if (tid == 0) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          *flag = (int)__hip_atomic_fetch_add(plan.counters + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        const int ticket = *flag;
         int sF, sL;
         sk_tile_ranges(plan, t, sF, sL);
-        if (ticket == sL - sF) {  // uniform: last arriver
-          if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          __syncthreads();  // (also: every wave has read the ticket before the stage becomes epilogue scratch)
+        if (g_slab_handover(plan.counters + t, (int*)(smem + (stage ^ 1) * kGStageFloats), sL - sF)) {
 #pragma unroll
           for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -551,14 +511,12 @@ __global__ __launch_bounds__(256, 2) void gemm128g_kernel(GOp aop, GOp bop, Gemm
     if (wide || plan.counters) __syncthreads();  // the next iteration's LDS-DMA lands in the slices the epilogue / ticket used
 
     seg = nxt;
-    sk_tile_xy(plan, (ABL & 64) ? 0 : seg.tile, bx, by);
+    sk_tile_xy(plan, seg.tile, bx, by);
   }
-  if (plan.dbg && tid == 0) g_dbg_record(plan.dbg, dbgT0);
 }
 
 inline int launch128g(const GOp& a, bool akc, const GOp& b, bool bkc, GemmOut o, int epi, hipStream_t s) {
-  epi &= ~EPI_ATOMIC;
-  SkPlan plan = make_sk_plan(o.M, o.N, o.K, sk_enabled());
+  SkPlan plan = make_sk_plan(o.M, o.N, o.K, true);
   plan.grouped = 1;
   if (plan.skBlocks > 0) {
     plan.slabs = sk_scratch(s, kSkScratchBytes);
@@ -569,57 +527,26 @@ inline int launch128g(const GOp& a, bool akc, const GOp& b, bool bkc, GemmOut o,
   }
   int workers = plan.dpTiles < kSkSlots ? plan.dpTiles : kSkSlots;
   if (workers < plan.skBlocks) workers = plan.skBlocks;
-  plan.dbg = gemm_dbg_ptr();
-  plan.prio = gemm_prio_mode();
-  { static const int nt = [] { const char* e = tune_env("W2L_GEMM_NTSTORE"); return e ? atoi(e) : 0; }(); o.ntStore = nt; }
   const size_t shmem = 2 * (size_t)kGStageFloats * sizeof(float);
   dim3 grid((unsigned)workers), block(256);
   o.epi = epi;
   prof_begin(s, 2.0 * o.M * (double)o.N * o.K, PROF_GEMM128, o.M, o.N, o.K, 2);
-  static const int wideOn = [] { const char* e = tune_env("W2L_GEMM_WIDE"); return e ? atoi(e) : 1; }();
-  const int wide = wideOn && (((uintptr_t)o.C) & 15) == 0 && o.ldc % 4 == 0 &&
-                   (!o.mask || (((uintptr_t)o.mask) & 15) == 0);
-  // buffer-addressed LDS-DMA is the default (+8 % at 4096^3, +5-7 % on the TDS fc shapes over 64-bit global
-  // addresses, MI355X); W2L_GEMM_BUF=0 selects the global_load_lds variant for A/B runs
-  static const int bufOn = [] { const char* e = tune_env("W2L_GEMM_BUF"); return e ? atoi(e) : 1; }();
-#ifdef W2L_PROBE  // timing-only ablations (results are garbage): compiled into the probe library only
-  static const int ablBuf = [] { const char* e = tune_env("W2L_GEMM_ABLBUF"); return e ? atoi(e) : 0; }();
-  static const int abl = [] { const char* e = tune_env("W2L_GEMM_ABL"); return e ? atoi(e) : 0; }();
-  if (abl && akc && !bkc) {
-    switch (abl) {
-      case 1: hipLaunchKernelGGL((gemm128g_kernel<true, false, 1>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 3: hipLaunchKernelGGL((gemm128g_kernel<true, false, 3>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 7: hipLaunchKernelGGL((gemm128g_kernel<true, false, 7>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 15: hipLaunchKernelGGL((gemm128g_kernel<true, false, 15>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 8: hipLaunchKernelGGL((gemm128g_kernel<true, false, 8>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 16: hipLaunchKernelGGL((gemm128g_kernel<true, false, 16>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 32: hipLaunchKernelGGL((gemm128g_kernel<true, false, 32>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 9: hipLaunchKernelGGL((gemm128g_kernel<true, false, 9>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 2: hipLaunchKernelGGL((gemm128g_kernel<true, false, 2>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      default: hipLaunchKernelGGL((gemm128g_kernel<true, false, 4>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-    }
-  } else if (ablBuf && akc && !bkc && a.bytes && b.bytes) {
-    switch (ablBuf) {
-      case 1: hipLaunchKernelGGL((gemm128g_kernel<true, false, 1, true>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 8: hipLaunchKernelGGL((gemm128g_kernel<true, false, 8, true>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 9: hipLaunchKernelGGL((gemm128g_kernel<true, false, 9, true>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 64: hipLaunchKernelGGL((gemm128g_kernel<true, false, 64, true>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      case 72: hipLaunchKernelGGL((gemm128g_kernel<true, false, 72, true>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-      default: hipLaunchKernelGGL((gemm128g_kernel<true, false, 0, true>), grid, block, shmem, s, a, b, o, plan, workers, wide); break;
-    }
-  } else
-#endif
-  if (bufOn && a.bytes && b.bytes) {
-    if (akc && bkc) hipLaunchKernelGGL((gemm128g_kernel<true, true, 0, true>), grid, block, shmem, s, a, b, o, plan, workers, wide);
-    else if (akc) hipLaunchKernelGGL((gemm128g_kernel<true, false, 0, true>), grid, block, shmem, s, a, b, o, plan, workers, wide);
-    else if (bkc) hipLaunchKernelGGL((gemm128g_kernel<false, true, 0, true>), grid, block, shmem, s, a, b, o, plan, workers, wide);
-    else hipLaunchKernelGGL((gemm128g_kernel<false, false, 0, true>), grid, block, shmem, s, a, b, o, plan, workers, wide);
-  } else if (akc && bkc) hipLaunchKernelGGL((gemm128g_kernel<true, true>), grid, block, shmem, s, a, b, o, plan, workers, wide);
-  else if (akc) hipLaunchKernelGGL((gemm128g_kernel<true, false>), grid, block, shmem, s, a, b, o, plan, workers, wide);
-  else if (bkc) hipLaunchKernelGGL((gemm128g_kernel<false, true>), grid, block, shmem, s, a, b, o, plan, workers, wide);
-  else hipLaunchKernelGGL((gemm128g_kernel<false, false>), grid, block, shmem, s, a, b, o, plan, workers, wide);
+  const int wide = (((uintptr_t)o.C) & 15) == 0 && o.ldc % 4 == 0 && (!o.mask || (((uintptr_t)o.mask) & 15) == 0);
+  // buffer-addressed LDS-DMA wherever both operands are below 2 GiB (+8 % at 4096^3, +5-7 % on the TDS fc shapes over 64-bit
+  // global addresses, MI355X); the global_load_lds instances take the (strictly aligned) operands beyond that
+#define W2L_G128_GO(A, B, BUF) hipLaunchKernelGGL((gemm128g_kernel<A, B, BUF>), grid, block, shmem, s, a, b, o, plan, workers, wide)
+  if (a.bytes && b.bytes) {
+    if (akc && bkc) W2L_G128_GO(true, true, true);
+    else if (akc) W2L_G128_GO(true, false, true);
+    else if (bkc) W2L_G128_GO(false, true, true);
+    else W2L_G128_GO(false, false, true);
+  } else if (akc && bkc) W2L_G128_GO(true, true, false);
+  else if (akc) W2L_G128_GO(true, false, false);
+  else if (bkc) W2L_G128_GO(false, true, false);
+  else W2L_G128_GO(false, false, false);
+#undef W2L_G128_GO
   if (plan.skBlocks > 0 && !plan.counters)
-    hipLaunchKernelGGL(gemm128_fixup<0>, dim3((unsigned)plan.skTiles * 4), dim3(64), 0, s, o, plan);
+    hipLaunchKernelGGL(gemm128_fixup, dim3((unsigned)plan.skTiles * 4), dim3(64), 0, s, o, plan);
   prof_end(s);
   W2L_LAUNCH_CHECK();
   return W2L_OK;

@@ -11,8 +11,10 @@
 // 9 LDS-DMA pieces and 24 ds_read_b128 (or up to 96 ds_read_b32 for k-row operands) per wave.  LDS: 36 KiB per
 // stage, two stages, two workgroups per CU (144 of 160 KiB).  The arithmetic intensity per staged byte is 11 %
 // higher than 128x128 (71 vs 64 flop/B).
-// Requirements (host-checked, otherwise gemm128g_kernel runs): as gemm_glds.hpp, plus buffer-addressable
-// operands (< 2 GiB), a 16-byte aligned C with ldc % 4 == 0, and <= 1024 stream-K tiles.
+// Shapes (line 3 of the dispatch in gemm.hip's header; t160_choice + launch160, otherwise gemm128g_kernel runs): as
+// gemm_glds.hpp, plus buffer-addressable operands (< 2 GiB), N % 4 == 0, 16-byte aligned C / mask / addend with ldc % 4 == 0,
+// <= 1024 stream-K tiles, and the tile orientation whose padded area is smallest if that saves >= 2 % against 128 x 128.
+// Instances: AKC x BKC x TALL (8), and CS (k-row operands: the weight gradient that also sums the columns of dy) x TALL (2).
 #pragma once
 #include <type_traits>
 
@@ -139,7 +141,7 @@ __device__ __forceinline__ void t160_epilogue(const GemmOut& out, int m0, int n0
           }
           f32x4 w4;
           w4[0] = v[0]; w4[1] = v[1]; w4[2] = v[2]; w4[3] = v[3];
-          if (out.ntStore) __builtin_nontemporal_store(w4, (f32x4*)dst); else *(f32x4*)dst = w4;
+          *(f32x4*)dst = w4;
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
@@ -155,36 +157,13 @@ __device__ __forceinline__ void t160_epilogue(const GemmOut& out, int m0, int n0
     }
 }
 
-// g_segment with every field pinned to SGPRs.  The schedule arithmetic contains a 64-bit division that the backend
-// runs on the VALU; left alone, the (uniform) K-tile index lived in a VGPR and every LDS-DMA issue of the K loop was
-// wrapped in a readfirstlane "waterfall" loop for its scalar offset (first build of this kernel: 9 loops per K tile).
-__device__ __forceinline__ GSeg t160_segment(const SkPlan& p, int w, int workers, int ord) {
-  GSeg s = g_segment(p, w, workers, ord);
-  s.tile = __builtin_amdgcn_readfirstlane(s.tile);
-  s.kb = __builtin_amdgcn_readfirstlane(s.kb);
-  s.ke = __builtin_amdgcn_readfirstlane(s.ke);
-  s.slab = __builtin_amdgcn_readfirstlane(s.slab);
-  s.valid = __builtin_amdgcn_readfirstlane((int)s.valid) != 0;
-  return s;
-}
-
 // CS (k-row operands only: the weight gradient x^T dy): the tiles of tile row 0 also add up the B fragments they multiply --
 // out.colsum[n] = sum_k B[k][n], the bias gradient (GemmOut::colsum).  WIDE: the four waves hold the same B fragments, wave 0
 // sums them (5 v_add per K step on the 1 / tilesM of the tiles that have bx == 0); TALL: every wave sums its own 32 columns.
 // A lane's sum runs over the k it holds (k = 8g + 4 (lane >> 5) + q) in ascending order, the two lane halves are added at the
 // end of the segment, the segments of a stream-K tile in range order by the tile's last arriver: run-to-run identical.
-//
-// ADIR (WIDE tiles with a k-contiguous A: the forward and backward-data products): in the 128 x 160 layout a wave multiplies only
-// its OWN 32 rows of the A tile, so that operand's trip through LDS is private to the wave -- it is loaded straight into the
-// fragment registers instead (four buffer_load_dwordx4 per K tile and wave: lane (li, lh) takes the 16 bytes at k = 8g + 4 lh of
-// row 32 wave + li, the k-slot assignment of t160_frag), double-buffered in registers one K tile ahead.  The LDS-DMA stream of a K
-// tile shrinks from 9 to 5 pieces per wave, the four ds_read_b128 of the A fragments go away, and the sum order is unchanged
-// (bit-identical results).  MEASURED (profiles/r06_run53_gemm_adir_ab.log): level with the all-LDS loop on every shape of the step
-// (84.52 / 84.55 ms step-weighted, twice) -- the operand stream costs what it costs whichever path its bytes take into the CU
-// (DESIGN section 3.5), so the loop stays off in the product; W2L_GEMM_ADIR=1 (probe library) runs it, and a parity test holds it.
-template <bool AKC, bool BKC, bool TALL, bool CS = false, bool ADIR = false>
+template <bool AKC, bool BKC, bool TALL, bool CS = false>
 __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmOut out, SkPlan plan, int workers) {
-  static_assert(!ADIR || (AKC && !TALL && !CS), "A-direct: k-contiguous A on the 128 x 160 tile");
   constexpr int BM = TALL ? 160 : 128, BN = TALL ? 128 : 160;
   constexpr int MI = TALL ? 5 : 1, NJ = TALL ? 1 : 5;
   constexpr int PA = BM / 32, PB = BN / 32;  // LDS-DMA pieces per wave and K tile
@@ -197,38 +176,20 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
   const uint32_t aStepB = (AKC ? 32u : 32u * (uint32_t)aop.ld) * 4u;  // bytes per K tile
   const uint32_t bStepB = (BKC ? 32u : 32u * (uint32_t)bop.ld) * 4u;
 
-  GSeg seg = t160_segment(plan, w, workers, 0);
+  GSeg seg = g_pin(g_segment(plan, w, workers, 0));
   if (!seg.valid) return;
-  const long long dbgT0 = plan.dbg ? wall_clock64() : 0;
-  const int second = plan.prio ? g_lds_second() : 0;
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)aop.p, 0, (int)aop.bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)bop.p, 0, (int)bop.bytes, 0x00020000);
   uint32_t va[PA], vb[PB];
   int bx, by;
   sk_tile_xy(plan, seg.tile, bx, by);
-  // ADIR: byte offset of this lane's row of the A tile (+ its half's four k); the row is clamped like a piece's
-  auto adir_off = [&](int m0) {
-    int gi = m0 + wm + li;
-    if (gi > aop.extent - 1) gi = aop.extent - 1;
-    return ((uint32_t)gi * (uint32_t)aop.ld + 4u * (uint32_t)lh) * 4u;
-  };
-  uint32_t vaD = 0;
-  u32x4 aCur[4], aNxt[4];
-  if (ADIR) {
-    vaD = adir_off(bx * BM);
 #pragma unroll
-    for (int g = 0; g < 4; ++g) aCur[g] = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)(vaD + 32u * g), (int)(aStepB * seg.kb), 0);
-  } else {
-#pragma unroll
-    for (int j = 0; j < PA; ++j) va[j] = t160_off<AKC, BM>(aop, bx * BM, wave * PA + j, lane);
-  }
+  for (int j = 0; j < PA; ++j) va[j] = t160_off<AKC, BM>(aop, bx * BM, wave * PA + j, lane);
 #pragma unroll
   for (int j = 0; j < PB; ++j) vb[j] = t160_off<BKC, BN>(bop, by * BN, wave * PB + j, lane);
-  if (!ADIR) {
 #pragma unroll
-    for (int j = 0; j < PA; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lptr_t)(smem + (wave * PA + j) * 256), 16, (int)va[j], (int)(aStepB * seg.kb), 0, 0);
-  }
+  for (int j = 0; j < PA; ++j)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lptr_t)(smem + (wave * PA + j) * 256), 16, (int)va[j], (int)(aStepB * seg.kb), 0, 0);
 #pragma unroll
   for (int j = 0; j < PB; ++j)
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lptr_t)(smem + BM * 32 + (wave * PB + j) * 256), 16, (int)vb[j], (int)(bStepB * seg.kb), 0, 0);
@@ -236,8 +197,7 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
   __syncthreads();  // (drains the LDS-DMA: vmcnt(0) precedes the barrier)
 
   for (int ord = 0;; ++ord) {
-    if (plan.prio) g_tile_prio(plan.prio, second, ord);
-    const GSeg nxt = t160_segment(plan, w, workers, ord + 1);
+    const GSeg nxt = g_pin(g_segment(plan, w, workers, ord + 1));
     // bias of this lane's output columns, fetched at the START of the tile (its latency hides under the K loop)
     float bv[NJ][4];
 #pragma unroll
@@ -282,7 +242,7 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
       float* An = smem + (stage ^ 1) * kT160StageFloats;
       float* Bn = An + BM * 32;
       float fa[2][MI][4], fb[2][NJ][4];
-      if (!ADIR) t160_frag<AKC, BM, MI>(fa[0], As, wm, 0, li, lh);
+      t160_frag<AKC, BM, MI>(fa[0], As, wm, 0, li, lh);
       t160_frag<BKC, BN, NJ>(fb[0], Bs, wn, 0, li, lh);
       // What goes to the other stage during this iteration: the next K tile, or the first K tile of the next
       // segment, or (very last iteration of this worker) a harmless re-load of this tile.
@@ -292,11 +252,8 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
       } else if (nxt.valid) {
         int nbx, nby;
         sk_tile_xy(plan, nxt.tile, nbx, nby);
-        if (ADIR) vaD = adir_off(nbx * BM);
-        else {
 #pragma unroll
-          for (int j = 0; j < PA; ++j) va[j] = t160_off<AKC, BM>(aop, nbx * BM, wave * PA + j, lane);
-        }
+        for (int j = 0; j < PA; ++j) va[j] = t160_off<AKC, BM>(aop, nbx * BM, wave * PA + j, lane);
 #pragma unroll
         for (int j = 0; j < PB; ++j) vb[j] = t160_off<BKC, BN>(bop, nby * BN, wave * PB + j, lane);
         soA = aStepB * (uint32_t)nxt.kb; soB = bStepB * (uint32_t)nxt.kb;
@@ -314,7 +271,7 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
           for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
-              acc[i * NJ + j] = __builtin_amdgcn_mfma_f32_32x32x2f32(ADIR ? __uint_as_float(aCur[g][q]) : fa[cur][i][q], fb[cur][j][q], acc[i * NJ + j], 0, 0, 0);
+              acc[i * NJ + j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cur][i][q], fb[cur][j][q], acc[i * NJ + j], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
           if (QS == 4 || QS == q) {
 #pragma unroll
@@ -322,15 +279,14 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
           }
           if (q == 0) {
             if (g < 3) {
-              if (!ADIR) t160_frag<AKC, BM, MI>(fa[cur ^ 1], As, wm, g + 1, li, lh);
+              t160_frag<AKC, BM, MI>(fa[cur ^ 1], As, wm, g + 1, li, lh);
               t160_frag<BKC, BN, NJ>(fb[cur ^ 1], Bs, wn, g + 1, li, lh);
             }
           } else {
             const int piece = 3 * g + q - 1;  // steps 1,2,3,5,6,7,9,10,11 -> pieces 0..8
-            if (piece < PA) {
-              if (ADIR) aNxt[piece] = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)(vaD + 32u * piece), (int)soA, 0);
-              else __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lptr_t)(An + (wave * PA + piece) * 256), 16, (int)va[piece], (int)soA, 0, 0);
-            } else if (piece < PA + PB)
+            if (piece < PA)
+              __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lptr_t)(An + (wave * PA + piece) * 256), 16, (int)va[piece], (int)soA, 0, 0);
+            else if (piece < PA + PB)
               __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lptr_t)(Bn + (wave * PB + piece - PA) * 256), 16, (int)vb[piece - PA], (int)soB, 0, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -338,10 +294,6 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
       }
       stage ^= 1;
       __syncthreads();  // the stage just filled has landed (vmcnt(0)) and is visible to all waves
-      if (ADIR) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) aCur[g] = aNxt[g];
-      }
     }
     };
     if (!csTile) kloop(std::integral_constant<int, -1>{});
@@ -376,23 +328,11 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
     }
     if (!doEpi) {
       t160_store_partial(plan.slabs + (size_t)seg.slab * kT160SlabFloats, acc, wave, lane);
-      // in-kernel slab reduction: see gemm128g_kernel
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      int* flag = (int*)(smem + (stage ^ 1) * kT160StageFloats);  // the stage the K loop has just released
+      // in-kernel slab reduction (g_slab_handover): the tile's last arriver adds its slabs in range order
       const int t = seg.tile - plan.dpTiles;
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        *flag = (int)__hip_atomic_fetch_add(plan.counters + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __syncthreads();
-      const int ticket = *flag;
-      int sF = 0, sL = plan.ksplit - 1;
-      if (!plan.ksplit) sk_tile_ranges(plan, t, sF, sL);
-      if (ticket == sL - sF) {  // uniform: last arriver
-        if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        __syncthreads();  // (also: every wave has read the ticket before the stage becomes epilogue scratch)
+      int sF, sL;
+      sk_tile_ranges(plan, t, sF, sL);
+      if (g_slab_handover(plan.counters + t, (int*)(smem + (stage ^ 1) * kT160StageFloats), sL - sF)) {
 #pragma unroll
         for (int b = 0; b < 5; ++b)
 #pragma unroll
@@ -400,13 +340,8 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
 #pragma unroll
         for (int j = 0; j < NJ; ++j) csum[j] = 0.f;
         for (int sr = sF; sr <= sL; ++sr) {
-          size_t slab;
-          if (plan.ksplit) {
-            slab = (size_t)sr * plan.skTiles + t;   // chunk sr of this tile
-          } else {
-            const int segIdx = t - (int)(sk_begin(plan, sr) / plan.kTiles);  // ranges span <= 2 tiles: 0 or 1
-            slab = (size_t)sr * 2 + segIdx;
-          }
+          const int segIdx = t - (int)(sk_begin(plan, sr) / plan.kTiles);  // ranges span <= 2 tiles: 0 or 1
+          const size_t slab = (size_t)sr * 2 + segIdx;
           const f32x4* s4 = (const f32x4*)(plan.slabs + slab * kT160SlabFloats);
 #pragma unroll
           for (int b = 0; b < 5; ++b)
@@ -442,23 +377,6 @@ __global__ __launch_bounds__(256, 2) void gemm160_kernel(GOp aop, GOp bop, GemmO
     seg = nxt;
     sk_tile_xy(plan, seg.tile, bx, by);
   }
-  if (plan.dbg && tid == 0) g_dbg_record(plan.dbg, dbgT0);
-}
-
-// MEASURED (profiles/r02_run17_gemm_aligned_ksplit_negative.log): correct, the L2 sharing is real, and it does not pay --
-// 120-127 TF/s against 126-132 of the classic ranges on the six weight-gradient shapes (a wash at K = 24000, 6-8 % slower
-// at K = 12000 / 6016): whole rounds of 512 units are 88-93 % full where stream-K balances to the K tile.  Probe library
-// only (W2L_GEMM_KSPLIT=1).
-inline bool t160_ksplit_enabled() {
-  const char* e = tune_env("W2L_GEMM_KSPLIT");
-  return e && atoi(e) != 0;
-}
-
-// A-direct K loop (gemm160_kernel<..., ADIR>) for the 128 x 160 products with a k-contiguous A: W2L_GEMM_ADIR=1 (probe library)
-constexpr int kT160AdirDefault = 0;   // measured level with the all-LDS loop (profiles/r06_run53_gemm_adir_ab.log): kept as a probe variant
-inline bool t160_adir_enabled() {
-  const char* e = tune_env("W2L_GEMM_ADIR");   // read per call (the variant test flips it)
-  return (e ? atoi(e) : kT160AdirDefault) != 0;
 }
 
 // 0 = not eligible / not worth it, 1 = WIDE (128x160), 2 = TALL (160x128): the variant whose padded tile area is
@@ -482,9 +400,8 @@ inline int t160_choice(const GOp& a, const GOp& b, const GemmOut& o) {
 // csDone (may be null): set when o.colsum was produced by the launch (k-row operands on this kernel); otherwise the caller sums
 inline int launch160(const GOp& a, bool akc, const GOp& b, bool bkc, GemmOut o, int epi, int which, hipStream_t s, bool* launched,
                      bool* csDone = nullptr) {
-  epi &= ~EPI_ATOMIC;
   const bool tall = which == 2;
-  SkPlan plan = make_sk_plan(o.M, o.N, o.K, sk_enabled(), tall ? 160 : 128, tall ? 128 : 160);
+  SkPlan plan = make_sk_plan(o.M, o.N, o.K, true, tall ? 160 : 128, tall ? 128 : 160);
   plan.grouped = 1;
   *launched = false;
   if (plan.skBlocks > 0) {
@@ -501,24 +418,6 @@ inline int launch160(const GOp& a, bool akc, const GOp& b, bool bkc, GemmOut o, 
   if (!cs) o.colsum = nullptr;
   int workers = plan.dpTiles < kSkSlots ? plan.dpTiles : kSkSlots;
   if (workers < plan.skBlocks) workers = plan.skBlocks;
-  // aligned K split for a GEMM that is all stream-K (fewer tiles than workgroup slots: the weight gradients): the
-  // smallest number of chunks that fills >= 88 % of whole rounds of 512 units, at most 1024 units (one slab each)
-  if (plan.skBlocks > 0 && plan.dpTiles == 0 && plan.slabs && t160_ksplit_enabled()) {
-    const int tiles = plan.skTiles;
-    for (int X = 2; X <= 8; ++X) {
-      const int units = tiles * X, rounds = (units + kSkSlots - 1) / kSkSlots;
-      const int chunk = (plan.kTiles + X - 1) / X;
-      if (units > 2 * kSkSlots || chunk < 8 || (X - 1) * chunk >= plan.kTiles) continue;
-      if ((double)units / ((double)rounds * kSkSlots) < 0.88) continue;
-      plan.ksplit = X;
-      plan.kChunk = chunk;
-      workers = units < kSkSlots ? units : kSkSlots;
-      break;
-    }
-  }
-  plan.dbg = gemm_dbg_ptr();
-  plan.prio = gemm_prio_mode();
-  { static const int nt = [] { const char* e = tune_env("W2L_GEMM_NTSTORE"); return e ? atoi(e) : 0; }(); o.ntStore = nt; }
   const size_t shmem = 2 * (size_t)kT160StageFloats * sizeof(float);
   dim3 grid((unsigned)workers), block(256);
   o.epi = epi;
@@ -533,8 +432,6 @@ inline int launch160(const GOp& a, bool akc, const GOp& b, bool bkc, GemmOut o, 
     W2L_T160_ATTR(true, true, true); W2L_T160_ATTR(true, false, true); W2L_T160_ATTR(false, true, true); W2L_T160_ATTR(false, false, true);
     (void)hipFuncSetAttribute((const void*)gemm160_kernel<false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
     (void)hipFuncSetAttribute((const void*)gemm160_kernel<false, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    (void)hipFuncSetAttribute((const void*)gemm160_kernel<true, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-    (void)hipFuncSetAttribute((const void*)gemm160_kernel<true, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
 #undef W2L_T160_ATTR
   }
   prof_begin(s, 2.0 * o.M * (double)o.N * o.K, PROF_GEMM128, o.M, o.N, o.K, tall ? 4 : 3);
@@ -543,9 +440,6 @@ inline int launch160(const GOp& a, bool akc, const GOp& b, bool bkc, GemmOut o, 
     if (!tall) hipLaunchKernelGGL((gemm160_kernel<false, false, false, true>), grid, block, shmem, s, a, b, o, plan, workers);
     else hipLaunchKernelGGL((gemm160_kernel<false, false, true, true>), grid, block, shmem, s, a, b, o, plan, workers);
     if (csDone) *csDone = true;
-  } else if (!tall && akc && t160_adir_enabled()) {
-    if (bkc) hipLaunchKernelGGL((gemm160_kernel<true, true, false, false, true>), grid, block, shmem, s, a, b, o, plan, workers);
-    else hipLaunchKernelGGL((gemm160_kernel<true, false, false, false, true>), grid, block, shmem, s, a, b, o, plan, workers);
   } else if (!tall) {
     if (akc && bkc) W2L_T160_GO(true, true, false);
     else if (akc) W2L_T160_GO(true, false, false);
