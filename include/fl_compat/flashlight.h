@@ -529,6 +529,26 @@ class FL_COMPAT_API CTCLoss : public SequenceCriterion {
   // targetSizes is ignored (sizes are counted on the device).  Bad target type / batch: std::invalid_argument.
   af::array viterbiPathWithTarget(const af::array& input, const af::array& target, const af::array& inputSizes = af::array(),
                                   const af::array& targetSizes = af::array()) override;
+  // fl_compat ADDITION to the reference's interface (its lexicon-free decoder is a host class of its own): n-best prefix beam
+  // search over the emissions without lexicon or LM (w2l_ctc_beam_search; the contract is in w2l_hip.h).  inputSizes as in
+  // viterbiPathWithTarget.  The hypotheses are already collapsed label rows: turn them into letters / words with tknLabels2Ltr /
+  // tknLabels2Wrd (fl_compat/text.h), not with tknPrediction2Ltr.  Refused arguments: std::invalid_argument; a beam or token
+  // count beyond the kernel's 64: std::runtime_error.
+  struct BeamSearchOptions {
+    int beamSize = 64;                  // W, 1..64
+    int beamSizeToken = 64;             // K, clipped to N-1, then <= 64
+    float beamThreshold = 1.0f / 0.0f;  // candidates below best - threshold are dropped; +inf: none
+    bool logAdd = false;                // false: max over a prefix's alignments (the 1-best is the greedy transcript); true: their sum
+    int normalize = -1;                 // 1: search on log-softmax rows, 0: on the raw emissions, -1: as logAdd
+    int nbest = 1;                      // M, 1..W
+    int maxLen = 0;                     // Lmax, 0 = T (no hypothesis is longer)
+  };
+  struct BeamSearchResult {
+    af::array labels;    // (Lmax, M, B) s32: the first min(length, Lmax) labels, -1 beyond
+    af::array lengths;   // (M, B) s32: the true label count; -1 for a rank that does not exist
+    af::array scores;    // (M, B) f32; -inf for a rank that does not exist
+  };
+  BeamSearchResult beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& options);
   std::string prettyString() const override;
   CriterionScaleMode scaleMode() const { return scaleMode_; }
 

@@ -356,6 +356,27 @@ inline std::vector<std::string> tknTarget2Ltr(std::vector<int> tokens, const lib
   return tknIdx2Ltr(tokens, dict, useWordPiece, wordSep);
 }
 
+// a DECODED label row (w2l_ctc_beam_search / CTCLoss::beamSearch: already collapsed, no blank, -1 beyond the hypothesis) -> letters.
+// The sibling of tknPrediction2Ltr without its collapse: nothing is dropped but the padding, so the doubled letter of "hello" stays
+// doubled; then the same surround, word-piece and word-separator handling.  (An addition to the reference's helpers, whose decoders
+// return one token per frame.)
+inline std::vector<std::string> tknLabels2Ltr(std::vector<int> labels, const lib::text::Dictionary& dict, const std::string& criterion,
+                                              const std::string& surround, int replabel, bool useWordPiece,
+                                              const std::string& wordSep) {
+  labels.erase(std::remove_if(labels.begin(), labels.end(), [](int t) { return t < 0; }), labels.end());
+  if (labels.empty()) return {};
+  remapLabels(labels, dict, surround, criterion == kAsgCriterion ? replabel : 0);
+  return tknIdx2Ltr(labels, dict, useWordPiece, wordSep);
+}
+
+inline std::vector<std::string> tkn2Wrd(const std::vector<std::string>& letters, const std::string& wordSep);
+// a decoded label row -> words (tknLabels2Ltr, then tkn2Wrd)
+inline std::vector<std::string> tknLabels2Wrd(const std::vector<int>& labels, const lib::text::Dictionary& dict,
+                                              const std::string& criterion, const std::string& surround, int replabel,
+                                              bool useWordPiece, const std::string& wordSep) {
+  return tkn2Wrd(tknLabels2Ltr(labels, dict, criterion, surround, replabel, useWordPiece, wordSep), wordSep);
+}
+
 inline std::vector<std::string> tkn2Wrd(const std::vector<std::string>& letters, const std::string& wordSep) {
   std::vector<std::string> words;
   std::string cur;

@@ -164,6 +164,40 @@ int w2l_ctc_score(int B, int T, int N, int L, int scaleMode, const float* input,
 size_t w2l_ctc_align_workspace_size(int B, int T, int N, int L);
 int w2l_ctc_align(int B, int T, int N, int L, const float* input, const int* target, const int* targetSize,
                   const int* frames, int* path, float* score, void* workspace, w2l_stream_t stream);
+/* CTC prefix beam search without lexicon or LM, n-best output.  Blank is N-1; `frames` as in w2l_ctc_align.
+ * For utterance b, with F = frames[b]:
+ *   Frame scores.  normalize = 0: lp_t[c] = x[t][c] (the raw emission); normalize = 1: lp_t[c] = x[t][c] - lse_t in fp32.
+ *   Frame tokens.  The K non-blank classes with the largest lp_t, ordered by lp descending, then class index ascending.
+ *     K larger than N-1 is clipped to N-1.
+ *   State.  A beam of at most W entries ordered by rank 0, 1, ...  An entry is a label prefix with last label e and two values:
+ *     pb (alignments ending in blank) and pnb (alignments ending in e); tot = pb (+) pnb, where (+) is log(exp a + exp b) when
+ *     logAdd = 1 and max when logAdd = 0.  The beam starts as the empty prefix with pb = 0, pnb = -inf.
+ *   Candidates of frame t.  For the entry of rank r:
+ *     stay(r): pb' = lp[blank] + tot; pnb' = lp[e] + pnb for a non-empty prefix (lp[e] is read from the row even when e is not
+ *       among the frame's tokens), -inf for the empty prefix.
+ *     ext(r, k), k-th frame token c: pb' = -inf, pnb' = lp[c] + (c == e ? pb : tot).
+ *   Merge.  If ext(r, k) spells the prefix of a beam entry j (j's parent is entry r's prefix and j's last label is c), its pnb'
+ *     is (+)-ed into stay(j).pnb' and the extension itself disappears: no two entries ever spell the same prefix.
+ *   Prune.  Candidates whose total is -inf are dropped, then those with total < best - threshold (threshold >= 0; +inf: no
+ *     pruning).  The first W candidates in this order are kept: total descending, then r ascending, then stay before extension,
+ *     then k ascending (a merged candidate carries the key of its stay).  That order defines the ranks of the next beam.
+ *   Output.  After frame F-1 the first M entries in rank order: lengths[b][m] the true label count, labels[b][m] the first
+ *     min(length, Lmax) labels and -1 beyond, scores[b][m] = tot.  Rows beyond the surviving entries: length -1, score -inf,
+ *     labels -1.
+ * With logAdd = 0 every value is one fp32 add of two stored values, or a compare: the result is reproducible bit for bit, ties
+ * included; the one exception is the sign of a zero: a new extension's pnb is stored as recovered from its selection key, which
+ * carries -0 as +0 (the two compare equal, so no decision and no non-zero value depends on it).  With logAdd = 1 the (+) is fp32
+ * (expf / log1pf).
+ * Limits: W in 1..64, K after clipping <= 64 (beyond: W2L_EUNSUPPORTED); 1 <= M <= W, N >= 2, Lmax >= 1, threshold not NaN and
+ * >= 0, non-null pointers other than frames (else W2L_EINVAL).  All argument checks return before anything touches the device.
+ * frames is device memory and therefore NOT checked: a value outside 1..T is clamped into 1..T, as in w2l_ctc_align.
+ * w2l_ctc_beam_workspace_size is host arithmetic (0 for arguments the search refuses). */
+size_t w2l_ctc_beam_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                        int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                        int nbest /*M*/, int maxLen /*Lmax*/,
+                        int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                        void* workspace, w2l_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the

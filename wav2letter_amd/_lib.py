@@ -107,6 +107,8 @@ class _SIGS:
     w2l_ctc_score = (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p])
     w2l_ctc_align_workspace_size = (_sz, [_i, _i, _i, _i])
     w2l_ctc_align = (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p])
+    w2l_ctc_beam_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_ctc_beam_search = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p])
     w2l_gemm_f32 = (_i, [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _p])
     w2l_linear_forward = (_i, [_i, _i, _i, _p, _p, _p, _p, _i, _p])
     w2l_linear_backward_data = (_i, [_i, _i, _i, _p, _p, _p, _i, _p, _f, _p])

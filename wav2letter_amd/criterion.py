@@ -301,6 +301,40 @@ def ctc_align(emission, target, frames=None, with_score=True):
     return path, score
 
 
+def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=None,
+                    nbest=1, max_len=None):
+    """CTC prefix beam search without lexicon or LM (w2l_ctc_beam_search; the contract is in include/w2l_hip.h): `emission`
+    [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64), beam_token = K (clipped to N-1, then <= 64),
+    log_add: sum (True) or max (False) over the alignments of a prefix; normalize: search on log-softmax rows (default: log_add --
+    sums only mean something on log-probabilities; the max search runs on the raw emissions as the reference's decoder does).
+    Returns (labels [B][nbest][max_len] int32, -1 beyond a hypothesis; lengths [B][nbest] int32, the true label counts, -1 for a
+    rank that does not exist; scores [B][nbest] float32, -inf there).  max_len defaults to T (no hypothesis is longer)."""
+    _emission_checks(emission)
+    _check_dev(emission)
+    L = _lib.lib()
+    emission = emission.detach().contiguous()
+    B, T, N = emission.shape
+    if frames is not None:
+        if frames.dtype != torch.int32 or frames.numel() != B:
+            raise _lib.W2LInvalidArgument("ctc_beam_search: frames must be int32 with one entry per utterance")
+        _check_dev(emission, frames)
+        frames = frames.contiguous()
+    if normalize is None:
+        normalize = bool(log_add)
+    max_len = T if max_len is None else int(max_len)
+    nbest = int(nbest)
+    ws = _ws(L.w2l_ctc_beam_workspace_size(B, T, N, int(beam), int(beam_token)), emission.device)
+    shape = (B, max(nbest, 1))
+    labels = torch.empty(*shape, max(max_len, 1), dtype=torch.int32, device=emission.device)
+    lengths = torch.empty(*shape, dtype=torch.int32, device=emission.device)
+    scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
+    _lib.check(L.w2l_ctc_beam_search(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None, int(beam),
+                                     int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
+                                     labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), ws.data_ptr(), _stream()),
+               "ctc_beam_search")
+    return labels, lengths, scores
+
+
 class SequenceCriterion(torch.nn.Module):
     """fl::pkg::speech::SequenceCriterion: forward({emission,target}) -> {loss[B]},
     viterbiPath(emission) -> [B][T] int32."""
@@ -454,6 +488,10 @@ class CTCLoss(SequenceCriterion):
     def viterbiPathWithTarget(self, emission, target, frames=None):
         """forced alignment of `target` to the emissions: [B][T] int32, one label per frame (ctc_align without the score)"""
         return ctc_align(emission, target, frames, with_score=False)[0]
+
+    def beamSearch(self, emission, frames=None, **options):
+        """lexicon-free n-best beam search over the emissions (ctc_beam_search's options): (labels, lengths, scores)"""
+        return ctc_beam_search(emission, frames, **options)
 
     def score(self, emission, target):
         """(loss [B], viterbiPath [B][T]) of a held-out batch in one pass over the emissions (ctc_score)"""

@@ -1,0 +1,405 @@
+// criterion_ctc_beam.hpp -- w2l_ctc_beam_search: LM-free CTC prefix beam search with n-best output (contract: include/w2l_hip.h).
+// Included at the end of criterion_ctc.hip (one translation unit: the row loader, the block reductions and align_frames are that
+// file's and criterion_ctc_align.hpp's).
+//   ctc_beam_rows    one workgroup per emission row (rows at or beyond frames[b] return at once): lse (normalize only), lp[blank]
+//                    and the K best non-blank (class, lp) pairs in the contract's order, written compactly.  The row is read once
+//                    into registers (ctc_rows_lse's loader).  An element's 64-bit key is (lp as an order-preserving integer, ~class),
+//                    so keys are unique and "lp descending, class ascending" is one integer compare.  Selection: the K-th largest of
+//                    the 256 per-thread maxima is a lower bound of the K-th largest key; the elements at or above it (about K of them
+//                    whatever the ties; more only when few threads own all large values) go to LDS and are ranked there.  More than
+//                    kBeamCandCap of them: K rounds of block-wide arg-max extraction instead.  N > 256 * kRowMaxPer: the same
+//                    algorithm re-reading the row from memory.
+//   ctc_beam_scan    one wavefront per utterance, lane r = beam entry of rank r.  Prefixes are nodes of a trie kept as an open-
+//                    addressing hash table (key = parent node, label; node id = slot + 1; root = 0) in the workspace, so one prefix
+//                    has one node whatever its history and the merge test is an integer compare of (parent node, label).  A lane's
+//                    extensions are never materialised: lp_k + tot is non-increasing in k, so a lane's best candidate is the best of
+//                    its stay, its own-label extension (the one that adds pb instead of tot) and the first unconsumed regular
+//                    extension; a selection round is a 64-bit wave max of (total, ~(rank, kind, k)) and an O(1) update of the winner.
+//                    Extensions merged into a beam entry are bits of a per-lane mask.  No waiting between workgroups, no flags.
+//   ctc_beam_finish  one thread per (utterance, output rank): walks the parent chain, writes labels, length, score.
+#pragma once
+
+namespace w2l {
+
+constexpr int kBeamMax = 64;          // W and K: one lane per entry, one mask bit per frame token
+constexpr int kBeamCandCap = 1024;    // LDS candidates of the row pass
+
+struct CtcBeamWs {
+  float* lse;                  // [B][T]  0 when not normalising
+  float* lpb;                  // [B][T]  lp[blank]
+  float* tokLp;                // [B][T][K]
+  int* tokC;                   // [B][T][K]
+  unsigned long long* table;   // [B][cap] trie edges: (parent node << 32) | (label + 1), 0 = free
+  int* finNode;                // [B][64] node of the final entry of rank r
+  float* finTot;               // [B][64]
+  int* finN;                   // [B]
+  int K;
+  unsigned cap;
+};
+
+static size_t ctc_beam_cap(int T, int W) {
+  const size_t need = 2 * (size_t)T * W;   // at most T * W nodes are ever made: load factor <= 1/2
+  size_t c = 64;
+  while (c < need) c <<= 1;
+  return c;
+}
+
+static size_t ctc_beam_layout(CtcBeamWs* w, void* ws, int B, int T, int W, int K) {
+  const size_t rows = (size_t)B * T, cap = ctc_beam_cap(T, W);
+  char* p = (char*)ws;
+  char* const p0 = p;
+  float* lse = (float*)p; p += align_up(rows * sizeof(float), 256);
+  float* lpb = (float*)p; p += align_up(rows * sizeof(float), 256);
+  float* tokLp = (float*)p; p += align_up(rows * K * sizeof(float), 256);
+  int* tokC = (int*)p; p += align_up(rows * K * sizeof(int), 256);
+  unsigned long long* table = (unsigned long long*)p; p += align_up((size_t)B * cap * sizeof(unsigned long long), 256);
+  int* finNode = (int*)p; p += align_up((size_t)B * kBeamMax * sizeof(int), 256);
+  float* finTot = (float*)p; p += align_up((size_t)B * kBeamMax * sizeof(float), 256);
+  int* finN = (int*)p; p += align_up((size_t)B * sizeof(int), 256);
+  if (w) *w = CtcBeamWs{lse, lpb, tokLp, tokC, table, finNode, finTot, finN, K, (unsigned)cap};
+  return (size_t)(p - p0);
+}
+
+// fp32 -> unsigned, order-preserving; -0 and +0 map to one value (they compare equal)
+__device__ __forceinline__ unsigned beam_ord(float f) {
+  const unsigned u = __float_as_uint(f + 0.0f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float beam_unord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off);
+    v = o > v ? o : v;
+  }
+  // every lane holds the maximum: say so to the compiler (scalar compares and branches downstream)
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* sm) {
+  v = wave_max_u64(v);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  unsigned long long r = sm[0];
+#pragma unroll
+  for (int k = 1; k < kRowThreads / 64; ++k) r = sm[k] > r ? sm[k] : r;
+  __syncthreads();
+  return r;
+}
+
+template <bool kBig>
+__global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int normalize,
+                                                             const float* __restrict__ x,
+                                                             const int* __restrict__ frames, CtcBeamWs ws) {
+  typedef unsigned long long u64;
+  __shared__ float sm[8];
+  __shared__ u64 sKey[kRowThreads];
+  __shared__ u64 sCand[kBeamCandCap];
+  __shared__ u64 sRed[kRowThreads / 64];
+  __shared__ u64 sTau;
+  __shared__ unsigned sCnt;
+  const size_t r = blockIdx.x;  // row = b*T + t
+  const int b = (int)(r / T);
+  if ((int)(r - (size_t)b * T) >= align_frames(frames, b, T)) return;
+  const float* row = x + r * N;
+  const int tid = threadIdx.x, K = ws.K, blank = N - 1;
+
+  // the row in registers, every load issued before the first use (ctc_rows_lse_body's loader)
+  constexpr int kPer = kBig ? 1 : kRowMaxPer / 4;
+  float4 v[kPer];
+  float hv = 0.f;
+  int hidx = -1;
+  RowSplit sp{};
+  if constexpr (!kBig) {
+    sp = row_split(row, N);
+    const float4* body = (const float4*)(row + sp.nh);
+    if (sp.nbody4 > 0) {
+      const int lastc = sp.nbody4 - 1;
+#pragma unroll
+      for (int k = 0; k < kPer; ++k) v[k] = body[min(tid + kRowThreads * k, lastc)];
+    }
+    if (tid < sp.nh) hidx = tid;
+    else if (tid >= 64 && tid - 64 < sp.ntail) hidx = sp.nh + 4 * sp.nbody4 + (tid - 64);
+    if (hidx >= 0) hv = row[hidx];
+  }
+  auto each = [&](auto&& f) {   // f(value, class) for every element this thread owns
+    if constexpr (kBig) {
+      for (int n = tid; n < N; n += kRowThreads) f(row[n], n);
+    } else {
+#pragma unroll
+      for (int k = 0; k < kPer; ++k)
+        if (tid + kRowThreads * k < sp.nbody4) {
+          const int i0 = sp.nh + 4 * (tid + kRowThreads * k);
+          f(v[k].x, i0); f(v[k].y, i0 + 1); f(v[k].z, i0 + 2); f(v[k].w, i0 + 3);
+        }
+      if (hidx >= 0) f(hv, hidx);
+    }
+  };
+
+  float lse = 0.f;
+  if (normalize) {
+    float m = -INFINITY;
+    each([&](float a, int) { m = fmaxf(m, a); });
+    m = block_reduce_max(m, sm);
+    float s = 0.f;
+    each([&](float a, int) { s += __expf(a - m); });
+    s = block_reduce_sum(s, sm);
+    lse = m + __logf(s);
+  }
+  auto key = [&](float a, int i) -> u64 {   // larger = earlier in the contract's order; blank is no token
+    return i == blank ? 0ull : ((u64)beam_ord(a - lse) << 32) | (u64)(0xffffffffu - (unsigned)i);
+  };
+
+  u64 tm = 0;
+  each([&](float a, int i) { const u64 k = key(a, i); tm = k > tm ? k : tm; });
+  sKey[tid] = tm;
+  if (tid == 0) {
+    sTau = 1;   // fewer than K threads own a token: every token is a candidate
+    sCnt = 0;
+    ws.lse[r] = lse;
+    ws.lpb[r] = row[blank] - lse;
+  }
+  __syncthreads();
+  int rank = 0;
+  for (int j = 0; j < kRowThreads; ++j) rank += sKey[j] > tm ? 1 : 0;
+  if (tm != 0 && rank == K - 1) sTau = tm;   // keys are unique: one writer
+  __syncthreads();
+  const u64 tau = sTau;
+  each([&](float a, int i) {
+    const u64 k = key(a, i);
+    if (k >= tau) {
+      const unsigned pos = atomicAdd(&sCnt, 1u);
+      if (pos < (unsigned)kBeamCandCap) sCand[pos] = k;
+    }
+  });
+  __syncthreads();
+  const int cnt = (int)sCnt;   // >= K: the K thread maxima at or above tau are among them
+  float* oLp = ws.tokLp + r * K;
+  int* oC = ws.tokC + r * K;
+  if (cnt <= kBeamCandCap) {
+    for (int i = tid; i < cnt; i += kRowThreads) {
+      const u64 ki = sCand[i];
+      int rk = 0;
+      for (int j = 0; j < cnt; ++j) rk += sCand[j] > ki ? 1 : 0;
+      if (rk < K) {
+        oLp[rk] = beam_unord((unsigned)(ki >> 32));
+        oC[rk] = (int)(0xffffffffu - (unsigned)ki);
+      }
+    }
+  } else {   // the large values sit with few threads: K rounds of block-wide extraction
+    u64 last = ~0ull;
+    for (int q = 0; q < K; ++q) {
+      u64 lm = 0;
+      each([&](float a, int i) { const u64 k = key(a, i); lm = (k < last && k > lm) ? k : lm; });
+      const u64 w = block_max_u64(lm, sRed);
+      if (tid == 0) {
+        oLp[q] = beam_unord((unsigned)(w >> 32));
+        oC[q] = (int)(0xffffffffu - (unsigned)w);
+      }
+      last = w;
+    }
+  }
+}
+
+template <bool kLogAdd>
+__device__ __forceinline__ float beam_oplus(float a, float b) {
+  const float m = fmaxf(a, b);
+  if constexpr (!kLogAdd) return m;
+  return m == -INFINITY ? m : m + log1pf(expf(fminf(a, b) - m));
+}
+
+__device__ __forceinline__ unsigned long long beam_key(float total, int r, int ext, int k) {
+  return ((unsigned long long)beam_ord(total) << 32) | (unsigned long long)(0xffffffffu - (unsigned)((r << 7) | (ext << 6) | k));
+}
+
+__device__ __forceinline__ unsigned beam_hash(unsigned long long z) {   // splitmix64's finaliser
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return (unsigned)(z ^ (z >> 31));
+}
+
+template <bool kLogAdd>
+__global__ __launch_bounds__(64) void ctc_beam_scan(int T, int N, int W, float threshold,
+                                                    const float* __restrict__ x,
+                                                    const int* __restrict__ frames, CtcBeamWs ws) {
+  typedef unsigned long long u64;
+  __shared__ u64 sGone[64];   // per beam entry: frame tokens whose extension merged into another entry
+  __shared__ int sTc[64];
+  __shared__ float sTl[64];
+  __shared__ int sNode[64], sPar[64], sE[64];   // the next beam, written by the winners in rank order
+  __shared__ float sPb[64], sPnb[64];
+  const int b = blockIdx.x, lane = threadIdx.x, K = ws.K;
+  const int F = align_frames(frames, b, T);
+  const float* xb = x + (size_t)b * T * N;
+  u64* tab = ws.table + (size_t)b * ws.cap;
+  const unsigned capm = ws.cap - 1;
+  const u64 maskK = K >= 64 ? ~0ull : ((1ull << K) - 1);
+  const size_t row0 = (size_t)b * T;
+
+  // entry of rank `lane`: its node, its parent's node, its last label (-1: the empty prefix), pb, pnb
+  int n = 1;
+  int node = lane == 0 ? 0 : -2, par = -1, e = -1;
+  float pb = lane == 0 ? 0.f : -INFINITY, pnb = -INFINITY;
+
+  int tcN = lane < K ? ws.tokC[row0 * K + lane] : -2;
+  float tlN = lane < K ? ws.tokLp[row0 * K + lane] : -INFINITY;
+  float lpbN = ws.lpb[row0], lseN = ws.lse[row0];
+  for (int t = 0; t < F && n > 0; ++t) {
+    const int tc = tcN;
+    const float tl = tlN, lpb = lpbN, lse = lseN;
+    const float xg = xb[(size_t)t * N + max(e, 0)];   // lp[e] comes from the row whether or not e is a frame token
+    {
+      const size_t rn = row0 + min(t + 1, F - 1);
+      tcN = lane < K ? ws.tokC[rn * K + lane] : -2;
+      tlN = lane < K ? ws.tokLp[rn * K + lane] : -INFINITY;
+      lpbN = ws.lpb[rn];
+      lseN = ws.lse[rn];
+    }
+    sTc[lane] = tc;
+    sTl[lane] = tl;
+    sGone[lane] = 0;
+    const bool active = lane < n;
+    int kj = -1;   // the frame token equal to this entry's last label
+    for (int k = 0; k < K; ++k) kj = __builtin_amdgcn_readlane(tc, k) == e ? k : kj;
+    int pr = -1;   // the rank of this entry's parent prefix, if it is in the beam
+    for (int r = 0; r < n; ++r) pr = __builtin_amdgcn_readlane(node, r) == par ? r : pr;
+
+    const float tot = beam_oplus<kLogAdd>(pb, pnb);
+    const float spb = lpb + tot;
+    float spnb = e >= 0 ? (xg - lse) + pnb : -INFINITY;
+    const int prc = max(pr, 0), kjc = max(kj, 0);
+    const int e_p = __shfl(e, prc);
+    const float pb_p = __shfl(pb, prc), tot_p = __shfl(tot, prc);
+    const float lpk = __shfl(tl, kjc);
+    __syncthreads();
+    if (active && pr >= 0 && kj >= 0) {   // ext(pr, kj) spells this entry: its pnb' joins this stay, the extension disappears
+      atomicOr(&sGone[pr], 1ull << kj);
+      spnb = beam_oplus<kLogAdd>(spnb, lpk + (e == e_p ? pb_p : tot_p));
+    }
+    __syncthreads();
+    const float stot = beam_oplus<kLogAdd>(spb, spnb);
+    u64 avail = active ? (maskK & ~sGone[lane]) : 0ull;   // the regular extensions not yet taken, in k order
+    u64 stayKey = active ? beam_key(stot, lane, 0, 0) : 0ull;
+    u64 specKey = 0ull;   // the extension by the entry's own last label adds pb, not tot: out of the monotone sequence
+    if (kj >= 0 && ((avail >> kj) & 1ull)) {
+      specKey = beam_key(lpk + pb, lane, 1, kj);
+      avail &= ~(1ull << kj);
+    }
+
+    int q = 0;
+    float best = 0.f;
+    while (q < W) {
+      const int kn = avail ? __ffsll((long long)avail) - 1 : -1;
+      const u64 regKey = kn >= 0 ? beam_key(sTl[max(kn, 0)] + tot, lane, 1, kn) : 0ull;
+      u64 lk = stayKey > specKey ? stayKey : specKey;
+      lk = regKey > lk ? regKey : lk;
+      const u64 wk = wave_max_u64(lk);
+      if (wk == 0ull) break;
+      const float wtot = beam_unord((unsigned)(wk >> 32));
+      if (q == 0) best = wtot;
+      if (wtot == -INFINITY || wtot < best - threshold) break;   // candidates come in descending order: the rest fails too
+      const unsigned tie = 0xffffffffu - (unsigned)wk;
+      const int wr = (int)(tie >> 7), wext = (int)((tie >> 6) & 1u), wkk = (int)(tie & 63u);
+      if (lane == wr) {
+        if (!wext) {
+          sNode[q] = node; sPar[q] = par; sE[q] = e; sPb[q] = spb; sPnb[q] = spnb;
+          stayKey = 0ull;
+        } else {
+          sNode[q] = -1; sPar[q] = node; sE[q] = sTc[wkk]; sPb[q] = -INFINITY; sPnb[q] = wtot;
+          if (specKey == wk) specKey = 0ull;
+          else avail &= avail - 1;
+        }
+      }
+      ++q;
+    }
+    __syncthreads();
+    n = __builtin_amdgcn_readfirstlane(q);
+    if (lane < n) {
+      node = sNode[lane]; par = sPar[lane]; e = sE[lane]; pb = sPb[lane]; pnb = sPnb[lane];
+      if (node == -1) {   // a new prefix: find or make its trie node
+        const u64 edge = ((u64)(unsigned)par << 32) | (u64)(unsigned)(e + 1);
+        unsigned h = beam_hash(edge) & capm;
+        for (;;) {
+          const u64 old = atomicCAS(&tab[h], 0ull, edge);
+          if (old == 0ull || old == edge) break;
+          h = (h + 1) & capm;
+        }
+        node = (int)h + 1;
+      }
+    } else {
+      node = -2; par = -1; e = -1; pb = -INFINITY; pnb = -INFINITY;
+    }
+    __syncthreads();
+  }
+  ws.finNode[b * kBeamMax + lane] = lane < n ? node : -1;
+  ws.finTot[b * kBeamMax + lane] = beam_oplus<kLogAdd>(pb, pnb);
+  if (lane == 0) ws.finN[b] = n;
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_finish(int M, int Lmax, CtcBeamWs ws, int* __restrict__ labels,
+                                                      int* __restrict__ lengths, float* __restrict__ scores) {
+  typedef unsigned long long u64;
+  const int b = blockIdx.x, m = threadIdx.x;
+  if (m >= M) return;
+  const u64* tab = ws.table + (size_t)b * ws.cap;
+  int* lab = labels + ((size_t)b * M + m) * Lmax;
+  const bool live = m < ws.finN[b];
+  int len = 0;
+  if (live) {
+    const int node = ws.finNode[b * kBeamMax + m];
+    for (int p = node; p > 0; p = (int)(tab[p - 1] >> 32)) ++len;
+    int i = len - 1;
+    for (int p = node; p > 0; --i) {
+      const u64 edge = tab[p - 1];
+      if (i < Lmax) lab[i] = (int)(unsigned)edge - 1;
+      p = (int)(edge >> 32);
+    }
+  }
+  for (int i = min(len, Lmax); i < Lmax; ++i) lab[i] = -1;
+  lengths[(size_t)b * M + m] = live ? len : -1;
+  scores[(size_t)b * M + m] = live ? ws.finTot[b * kBeamMax + m] : -INFINITY;
+}
+
+static int ctc_beam_clip(int N, int beamToken) { return beamToken < N - 1 ? beamToken : N - 1; }
+
+}  // namespace w2l
+
+W2L_API size_t w2l_ctc_beam_workspace_size(int B, int T, int N, int beam, int beamToken) {
+  if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
+  const int K = w2l::ctc_beam_clip(N, beamToken);
+  if (beam > w2l::kBeamMax || K > w2l::kBeamMax) return 0;
+  return w2l::ctc_beam_layout(nullptr, nullptr, B, T, beam, K);
+}
+
+W2L_API int w2l_ctc_beam_search(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
+                                float* scores, void* workspace, w2l_stream_t stream) {
+  using namespace w2l;
+  if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !workspace) return W2L_EINVAL;
+  if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
+  if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
+  const int K = ctc_beam_clip(N, beamToken);
+  if (beam > kBeamMax || K > kBeamMax) return W2L_EUNSUPPORTED;
+  if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;   // node ids are ints
+  hipStream_t s = (hipStream_t)stream;
+  CtcBeamWs ws{};
+  ctc_beam_layout(&ws, workspace, B, T, beam, K);
+  W2L_HIP_CHECK(hipMemsetAsync(ws.table, 0, (size_t)B * ws.cap * sizeof(unsigned long long), s));
+  const unsigned rows = (unsigned)((size_t)B * T);
+  if (N <= kRowThreads * kRowMaxPer)
+    hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ws);
+  else
+    hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ws);
+  W2L_LAUNCH_CHECK();
+  if (logAdd)
+    hipLaunchKernelGGL(ctc_beam_scan<true>, dim3((unsigned)B), dim3(64), 0, s, T, N, beam, threshold, input, frames, ws);
+  else
+    hipLaunchKernelGGL(ctc_beam_scan<false>, dim3((unsigned)B), dim3(64), 0, s, T, N, beam, threshold, input, frames, ws);
+  W2L_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ctc_beam_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, ws, labels, lengths, scores);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}

@@ -1,0 +1,254 @@
+// decode_main.cpp -- `Decode --am=<NNN_model_*.bin> --test=<list> [--datadir=] [--batchsize=] [--sclite=<dir>] [--beamsize=]
+// [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--k=v ...]`: the
+// reference's Decode tool for its lexicon-free token decoder without LM (`--uselexicon=false --decodertype=tkn`, the configuration
+// of recipes/self_training/librispeech/am/decode_*.cfg) over the fl:: surface.  Output formats: Decode.cpp:683-739, :840-846.
+//
+// Flags come from the checkpoint's `gflags` entry, then from the command line (the last definition wins), as in Align.  The tool
+// builds the network and the CTC criterion, loads both from --am and runs the eval-mode network over the --test list in list order
+// in batches of --batchsize through list_data.hpp; one CTCLoss::beamSearch call per batch (w2l_ctc_beam_search) with the
+// utterances' emission-frame counts, computed as in align_main.cpp: frames_b = clamp(ceil(tb * Tout / Tin), 1, Tout).
+//   --beamsize (2500), --beamsizetoken (250000), --beamthreshold (25), --logadd (false), --nbest (1): the reference's names and
+//   defaults.  The kernel keeps at most 64 beam entries and 64 tokens per frame: larger values are limited to 64 (said on stderr).
+//   --logadd=false (default): a prefix scores the MAX over its alignments, on the raw emissions as in the reference's decoder; the
+//     1-best then equals the greedy transcript (the collapsed per-frame arg-max), the n-best are the next best single alignments.
+//   --logadd=true: the labelling-probability search -- a prefix scores the SUM over its alignments, on log-softmax rows (sums only
+//     mean something on log-probabilities).
+//   --sclite=<dir>: <dir>/<name>.hyp and .ref hold `words (sampleId)\n`, <name> = the list's base name; .log holds what --show
+//     prints and the final line.  --show: the |T|: / |P|: (/ |t|: / |p|: with --showletters) / [sample: ...] block per sample.
+//   --isbeamdump=true (needs --sclite): .hyp holds one line `sampleId | score | amScore | lmScore | wer | words` per hypothesis,
+//     --nbest of them per sample in rank order; lmScore is 0 and amScore equals score (no LM in this build).
+//   The last line gives the total WER / TER (fl::EditDistanceMeter, the --valid evaluation's).
+// Refused, each with a message that names the flag: --lm, --uselexicon=true, --decodertype=wrd, a non-zero --silscore /
+// --wordscore, a --criterion other than ctc.  (--uselexicon and --decodertype default to false / tkn here: the only decoder built.)
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <iomanip>
+#include <iostream>
+#include <limits>
+
+#include "list_data.hpp"
+
+using namespace fl;
+using namespace fl::pkg::speech;
+using namespace w2l::cli;
+
+namespace {
+int usage(const char* exe) {
+  std::cerr << "Usage: \n " << exe
+            << " --am=<model> --test=<list> [--datadir=...] [--batchsize=...] [--sclite=<dir>] [--beamsize=2500] [--beamsizetoken=250000]"
+               " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [flags]\n"
+               " lexicon-free CTC token beam search without LM; beam and tokens per frame are limited to 64.\n"
+               " --logadd=false (default): max over a prefix's alignments on the raw emissions -- the 1-best equals the greedy transcript.\n"
+               " --logadd=true: the labelling-probability search (sum over a prefix's alignments, on log-softmax rows)."
+            << std::endl;
+  return 2;
+}
+
+std::string join(const std::vector<std::string>& v) {
+  std::string out;
+  for (size_t i = 0; i < v.size(); ++i) out += (i ? " " : "") + v[i];
+  return out;
+}
+
+std::string baseName(const std::string& path) {
+  const size_t slash = path.find_last_of('/');
+  std::string name = slash == std::string::npos ? path : path.substr(slash + 1);
+  const size_t dot = name.find_last_of('.');
+  return dot == std::string::npos || dot == 0 ? name : name.substr(0, dot);
+}
+}  // namespace
+
+int main(int argc, char** argv) {
+  if (argc <= 1) return usage(argv[0]);
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]).rfind("--", 0) != 0 || std::string(argv[i]) == "--help") return usage(argv[0]);
+  try {
+    using Serializer = fl::pkg::runtime::Serializer;
+    w2l::Flags cmd;
+    for (int i = 1; i < argc; ++i)
+      for (auto& kv : w2l::parseFlagsText(argv[i]).kv) cmd.kv.push_back(kv);
+    const std::string am = cmd.get("am", "");
+    if (am.empty()) throw std::invalid_argument("--am=<model file> is required");
+    std::string version;
+    Serializer::Config cfg;
+    Serializer::load(am, version, cfg);
+    auto it = cfg.find("gflags");
+    if (it == cfg.end()) throw std::invalid_argument("Invalid config loaded from " + am);
+    w2l::Flags flags = w2l::parseFlagsText(it->second);
+    for (auto& kv : cmd.kv) flags.kv.push_back(kv);
+
+    // ---- what this build does not decode
+    const std::string criterionName = flags.get("criterion", "asg");
+    if (criterionName != "ctc")
+      throw std::invalid_argument("--criterion=" + criterionName + ": Decode searches the CTC lattice only (ASG's best path is Train's Viterbi)");
+    if (!flags.get("lm", "").empty()) throw std::invalid_argument("--lm: no language model in this build (leave it empty)");
+    if (flags.getb("uselexicon", false)) throw std::invalid_argument("--uselexicon=true: no lexicon decoder in this build (use --uselexicon=false)");
+    if (flags.get("decodertype", "tkn") != "tkn")
+      throw std::invalid_argument("--decodertype=" + flags.get("decodertype", "") + ": only the token decoder (--decodertype=tkn) is built");
+    if (flags.getd("silscore", 0.0) != 0.0) throw std::invalid_argument("--silscore: no silence score without a lexicon (leave it 0)");
+    if (flags.getd("wordscore", 0.0) != 0.0) throw std::invalid_argument("--wordscore: no word score without a lexicon (leave it 0)");
+
+    const int batch = (int)flags.geti("batchsize", 1);
+    if (batch <= 0) throw std::invalid_argument("--batchsize must be positive");
+    const bool logAdd = flags.getb("logadd", false), beamDump = flags.getb("isbeamdump", false);
+    const bool show = flags.getb("show", false), showLetters = flags.getb("showletters", false);
+    const std::string sclite = flags.get("sclite", "");
+    if (beamDump && sclite.empty()) throw std::invalid_argument("--isbeamdump needs --sclite=<dir>: nowhere to dump the beam");
+    long beamSize = flags.geti("beamsize", 2500), beamToken = flags.geti("beamsizetoken", 250000), nbest = flags.geti("nbest", 1);
+    const double threshold = flags.getd("beamthreshold", 25.0);
+    if (beamSize <= 0 || beamToken <= 0 || nbest <= 0) throw std::invalid_argument("--beamsize, --beamsizetoken and --nbest must be positive");
+    if (!(threshold >= 0)) throw std::invalid_argument("--beamthreshold must be >= 0");
+
+    const int nFeat = flags.getb("mfcc", false) ? (int)flags.geti("mfcccoeffs", 13) * 3
+                      : flags.getb("pow", false) ? (int)flags.geti("framesizems", 25) * 8 + 1 : (int)flags.geti("filterbanks", 40);
+    const std::string tok = pathJoin(flags.get("tokensdir", ""), flags.get("tokens", "tokens.txt"));
+    int numClasses = countTokens(tok);
+    if (numClasses <= 0) throw std::invalid_argument("cannot read the token dictionary '" + tok + "' (--tokensdir / --tokens)");
+    numClasses += 1;  // blank, appended LAST
+    if (beamSize > 64) { std::cerr << "[Decode] --beamsize=" << beamSize << " limited to 64 (the kernel's beam width)" << std::endl; beamSize = 64; }
+    beamToken = std::min<long>(beamToken, numClasses - 1);
+    if (beamToken > 64) { std::cerr << "[Decode] --beamsizetoken limited to 64 tokens per frame" << std::endl; beamToken = 64; }
+    const int M = beamDump ? (int)std::min(nbest, beamSize) : 1;
+
+    // ---- network and criterion, both from the model file (Train fork's construction)
+    const std::string archPath = pathJoin(flags.get("archdir", ""), flags.get("arch", ""));
+    if (!fileExists(archPath)) throw std::invalid_argument("arch file / plugin '" + archPath + "' not found (--archdir / --arch)");
+    auto scalemode = getCriterionScaleMode(flags.get("onorm", "none"), flags.getb("sqnorm", false));
+    std::shared_ptr<fl::Module> network = fl::pkg::runtime::ModulePlugin(archPath).arch(nFeat, numClasses);
+    if (flags.getb("fl_amp_use_mixed_precision", false)) setMixedPrecision(network, true);
+    auto ctc = std::make_shared<CTCLoss>(scalemode);
+    std::shared_ptr<SequenceCriterion> criterion = ctc;
+    Serializer::Config unused;
+    Serializer::load(am, version, unused, network, criterion);
+    network->eval();
+    criterion->eval();
+    std::cerr << "[Decode] " << criterion->prettyString() << ", " << numClasses << " classes, model " << am << ", beam " << beamSize
+              << ", tokens per frame " << beamToken << ", threshold " << threshold << (logAdd ? ", logadd" : ", max") << std::endl;
+
+    // ---- the list
+    const std::string dataDir = flags.get("datadir", ""), testFlag = flags.get("test", "");
+    std::vector<std::string> listPaths;
+    {
+      std::istringstream ls(testFlag);
+      for (std::string one; std::getline(ls, one, ',');) if (!one.empty()) listPaths.push_back(pathJoin(dataDir, one));
+    }
+    if (listPaths.empty()) throw std::invalid_argument("--test=<list file> is required");
+    ListData d;
+    d.tolerateTextErrors = true;
+    loadListData(d, listPaths, batch, "--test", true, flags, criterionName, nFeat, numClasses, (uint64_t)flags.geti("seed", 0), dataDir);
+    const bool wp = flags.getb("usewordpiece", false);
+    const std::string surround = flags.get("surround", "");
+    const std::string dump = flags.get("w2l_dump_features", "");
+
+    std::ofstream hypFile, refFile, logFile;
+    if (!sclite.empty()) {
+      const std::string stem = pathJoin(sclite, baseName(listPaths.front()));
+      hypFile.open(stem + ".hyp");
+      refFile.open(stem + ".ref");
+      logFile.open(stem + ".log");
+      if (!hypFile || !refFile || !logFile) throw std::runtime_error("cannot open '" + stem + ".hyp / .ref / .log' for writing");
+    }
+
+    fl::EditDistanceMeter sliceWords, sliceLetters;
+    long decoded = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const long nb = d.batches();
+    for (long k = 0; k < nb; ++k) {
+      af::array feats;
+      std::vector<float> sizes;
+      std::vector<int> tgt;
+      int L = 1, Tin = 0;
+      const int B = d.get(k, k + 1 < nb ? k + 1 : 0, feats, tgt, L, sizes, Tin);
+      if (!dump.empty()) {   // [B][NFEAT][T] float32, Train's --w2l_dump_features format
+        std::vector<float> hf((size_t)feats.elements());
+        feats.host(hf.data());
+        std::ofstream df(dump + "." + std::to_string(k + 1), std::ios::binary);
+        const int hd[3] = {B, nFeat, Tin};
+        df.write((const char*)hd, sizeof hd);
+        df.write((const char*)hf.data(), (std::streamsize)(hf.size() * 4));
+      }
+      af::array inSizes(af::dim4(1, (af::dim_t)sizes.size()), sizes.data());
+      auto out = network->forward({fl::input(feats), fl::noGrad(inSizes)}).front();
+      const int N = (int)out.dims(0), Tout = (int)out.dims(1);
+      if (N != numClasses || (int)out.dims(2) != B) throw std::runtime_error("the network's output is not (classes, frames, batch)");
+      std::vector<int> frames((size_t)B);
+      for (int b = 0; b < B; ++b) {
+        const long tb = std::min(d.mfsc->numFrames((long)sizes[(size_t)b]), Tin);
+        frames[(size_t)b] = (int)std::min<long>(std::max<long>((tb * Tout + Tin - 1) / Tin, 1), Tout);
+      }
+      CTCLoss::BeamSearchOptions opt;
+      opt.beamSize = (int)beamSize;
+      opt.beamSizeToken = (int)beamToken;
+      opt.beamThreshold = (float)threshold;
+      opt.logAdd = logAdd;
+      opt.normalize = logAdd ? 1 : 0;   // the reference's decoder consumes the raw emissions; sums need log-probabilities
+      opt.nbest = M;
+      auto res = ctc->beamSearch(out.array(), af::array(af::dim4(1, B), frames.data()), opt);
+      std::vector<int> labels((size_t)B * M * Tout), lengths((size_t)B * M);
+      std::vector<float> scores((size_t)B * M);
+      res.labels.host(labels.data());
+      res.lengths.host(lengths.data());
+      res.scores.host(scores.data());
+
+      for (int b = 0; b < B; ++b) {
+        const auto& smp = d.samples[(size_t)d.mine[(size_t)(k * batch + b)]];
+        std::vector<int> ref;
+        for (int i = 0; i < L && tgt[(size_t)b * L + i] >= 0; ++i) ref.push_back(tgt[(size_t)b * L + i]);
+        const auto letterTarget = tknTarget2Ltr(ref, d.dict, criterionName, surround, d.replabel, wp, d.wordsep);
+        const std::vector<std::string>& wordTarget = smp.transcript;
+        for (int m = 0; m < M; ++m) {
+          int len = lengths[(size_t)b * M + m];
+          if (len < 0 && (beamDump || m > 0)) break;   // fewer surviving hypotheses than asked for
+          if (len < 0) len = 0;   // nothing survived (a row of -inf or NaN emissions): an empty hypothesis, so every sample has its line
+          const int* row = labels.data() + ((size_t)b * M + m) * Tout;
+          const auto letterPrediction = tknLabels2Ltr(std::vector<int>(row, row + len), d.dict, criterionName, surround, d.replabel, wp, d.wordsep);
+          const auto wordPrediction = tkn2Wrd(letterPrediction, d.wordsep);
+          if (beamDump) {
+            fl::EditDistanceMeter one;
+            one.add(wordPrediction, wordTarget);
+            const double score = (double)scores[(size_t)b * M + m];
+            hypFile << smp.id << " | " << std::to_string(score) << " | " << std::to_string(score) << " | " << std::to_string(0.0) << " | "
+                    << std::to_string(one.value()) << " | " << join(wordPrediction) << "\n";
+            continue;
+          }
+          sliceWords.add(wordPrediction, wordTarget);
+          sliceLetters.add(letterPrediction, letterTarget);
+          if (!sclite.empty()) {
+            hypFile << join(wordPrediction) << " (" << smp.id << ")\n";
+            refFile << join(wordTarget) << " (" << smp.id << ")\n";
+          }
+          if (show) {
+            fl::EditDistanceMeter w1, t1;
+            w1.add(wordPrediction, wordTarget);
+            t1.add(letterPrediction, letterTarget);
+            std::stringstream buffer;
+            buffer << "|T|: " << join(wordTarget) << std::endl;
+            buffer << "|P|: " << join(wordPrediction) << std::endl;
+            if (showLetters) {
+              buffer << "|t|: " << join(letterTarget) << std::endl;
+              buffer << "|p|: " << join(letterPrediction) << std::endl;
+            }
+            buffer << "[sample: " << smp.id << ", WER: " << w1.value() << "%, TER: " << t1.value() << "%, slice WER: " << sliceWords.value()
+                   << "%, slice TER: " << sliceLetters.value() << "%, decoded samples (thread 0): " << decoded + 1 << "]" << std::endl;
+            std::cout << buffer.str();
+            if (!sclite.empty()) logFile << buffer.str();
+          }
+        }
+        ++decoded;
+      }
+    }
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    std::stringstream buffer;
+    buffer << "------\n";
+    buffer << "[Decode " << testFlag << " (" << decoded << " samples) in " << seconds << "s (actual decoding time " << std::setprecision(3)
+           << (decoded ? seconds / (double)decoded : 0.0) << "s/sample) -- WER: " << std::setprecision(6) << sliceWords.value() << "%, TER: "
+           << sliceLetters.value() << "%]" << std::endl;
+    std::cout << buffer.str();
+    if (!sclite.empty()) logFile << buffer.str();
+    return decoded > 0 ? 0 : 1;
+  } catch (const std::exception& e) {
+    std::cerr << "Decode: " << e.what() << std::endl;
+    return 1;
+  }
+}

@@ -1253,6 +1253,31 @@ af::array CTCLoss::viterbiPathWithTarget(const af::array& input, const af::array
   af::sync();  // ws is released at return
   return path;
 }
+// n-best prefix beam search (w2l_ctc_beam_search); inputSizes as in viterbiPathWithTarget
+CTCLoss::BeamSearchResult CTCLoss::beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& o) {
+  const int N = (int)input.dims(0), T = (int)input.dims(1), B = (int)input.dims(2);
+  const int* frames = nullptr;
+  if (!inputSizes.isempty()) {
+    if (inputSizes.type() != af::s32 || inputSizes.elements() != B) throw std::invalid_argument("beamSearch: bad inputSizes");
+    frames = inputSizes.device<int>();
+  }
+  const int Lmax = o.maxLen > 0 ? o.maxLen : T;
+  if (input.type() != af::f32 || B <= 0 || T <= 0 || N < 2 || o.nbest < 1 || o.beamSize < 1 || o.beamSizeToken < 1)
+    throw std::invalid_argument("beamSearch: bad input or options");
+  auto st = stateOf(this);
+  BeamSearchResult r;
+  r.labels = af::array(af::dim4(Lmax, o.nbest, B), af::s32);
+  r.lengths = af::array(af::dim4(o.nbest, B), af::s32);
+  r.scores = af::array(af::dim4(o.nbest, B));
+  auto ws = devAlloc(st->impl->beamWorkspaceBytes(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+  w2l::Ctx c;
+  c.stream = S();
+  st->impl->beamSearch(c, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+                       o.normalize < 0 ? o.logAdd : o.normalize != 0, o.nbest, Lmax, r.labels.device<int>(),
+                       r.lengths.device<int>(), r.scores.device<float>(), ws.get());
+  af::sync();  // ws is released at return
+  return r;
+}
 std::string CTCLoss::prettyString() const { return "ConnectionistTemporalClassificationCriterion"; }
 
 std::pair<af::array, af::array> w2lScore(SequenceCriterion& criterion, const Variable& emission, const Variable& target) {

@@ -322,6 +322,24 @@ def tkn_prediction_to_ltr(path: Sequence[int], token_dict: Dictionary, criterion
     return tkn_idx_to_ltr(toks, token_dict, use_wordpiece, wordsep)
 
 
+def tkn_labels_to_ltr(labels: Sequence[int], token_dict: Dictionary, criterion: str, surround: str = "", replabel: int = 0,
+                      use_wordpiece: bool = False, wordsep: str = "") -> List[str]:
+    """a DECODED label row (ctc_beam_search's output: already collapsed, no blank, -1 beyond the hypothesis) -> letters.  The
+    sibling of tkn_prediction_to_ltr without its collapse: nothing is dropped but the padding, so the doubled letter of "hello"
+    stays doubled; then the same surround, word-piece and word-separator handling."""
+    toks = [int(t) for t in labels if int(t) >= 0]
+    if not toks:
+        return []
+    toks = _remap_labels(toks, token_dict, surround, replabel if criterion == "asg" else 0)
+    return tkn_idx_to_ltr(toks, token_dict, use_wordpiece, wordsep)
+
+
+def tkn_labels_to_wrd(labels: Sequence[int], token_dict: Dictionary, criterion: str, surround: str = "", replabel: int = 0,
+                      use_wordpiece: bool = False, wordsep: str = "") -> List[str]:
+    """a decoded label row -> words (tkn_labels_to_ltr, then tkn2wrd)"""
+    return tkn2wrd(tkn_labels_to_ltr(labels, token_dict, criterion, surround, replabel, use_wordpiece, wordsep), wordsep)
+
+
 def tkn_target_to_ltr(target: Sequence[int], token_dict: Dictionary, criterion: str, surround: str = "", replabel: int = 0,
                       use_wordpiece: bool = False, wordsep: str = "") -> List[str]:
     toks = [int(t) for t in target if int(t) >= 0]      # -1 padding of the batch
