@@ -109,12 +109,14 @@ def fac_forward_linear(x, trans, target, S, group=1):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Round 4: models of the arithmetic the shipped N <= 31 kernels run (csrc/criterion_asg_small.hip), op for op where it
-# matters for the numerics: the FCC scan with a LAGGED power-of-two scale (no maximum on the dependency chain), its backward
+# Round 4: models of the arithmetic of the N <= 31 kernels of that round, op for op where it matters for the numerics (the FCC
+# chain is that of csrc/criterion_asg_mitm.hpp today; the one-exponent-per-lane FAC kernel is retired, its model stays as the study): the FCC scan with a LAGGED power-of-two scale (no maximum on the dependency chain), its backward
 # scan in the same scaled domain (beta recursion, no logs), and the FAC scan with fp64 mantissas, one exponent per lane of P
 # adjacent positions, renormalised every R frames with a decaying maximum-scan over the lane exponents.
 def fcc_kernel_model(x, trans, dtype=np.float32, kclamp=64):
-    """x [T][N], trans [N][N].  Returns (loss, u [T][N], q [T][N], ks [T]) as fcc_fwd_dpp computes them:
+    """x [T][N], trans [N][N].  Returns (loss, u [T][N], q [T][N], ks [T]) as the full-length alpha chain of
+       csrc/criterion_asg_mitm.hpp computes them (the kernel runs this chain from frame 0 to its middle frame and the mirrored one
+       from the other end):
          u_0 = 2 ** (z_0 - max z_0),                       z_0 = x_0 log2(e)
          s_t = E u_{t-1},  u_t = s_t * q_t,                 q_t = 2 ** (zz_t - max zz_t) * 2 ** -k_t,  zz_t = x_t log2(e) + rowmax log2(e)
          k_{t+1} = clamp(exponent(sum_j u_{t-1}[j]) - k_t)  (the sum arrives as one more row of the mat-vec: E[31][j] = 1)
@@ -148,7 +150,8 @@ def fcc_kernel_model(x, trans, dtype=np.float32, kclamp=64):
 
 
 def fcc_kernel_model_backward(u, q, trans, dtype=np.float32):
-    """the backward scan of fcc_bwd_dpp on the forward's u, q: b_{T-1} = 1 / sum u_{T-1}; r_t = b_t q_t; b_{t-1} = E^T r_t;
+    """the full-length backward scan on the forward's u, q (the recursion the kernel's beta half and continuations run):
+    b_{T-1} = 1 / sum u_{T-1}; r_t = b_t q_t; b_{t-1} = E^T r_t;
     returns (dx [T][N] = u_t b_t (d loss / d x_t), dA [N][N] = E .* sum_t r_t u_{t-1}^T)"""
     A = np.asarray(trans, np.float64)
     T, N = u.shape
@@ -166,7 +169,9 @@ def fcc_kernel_model_backward(u, q, trans, dtype=np.float32):
 
 
 def fac_kernel_model(x, trans, target, S, P=5, R=4, D=600):
-    """x [T][N], trans [N][N], target[0..S).  Returns (loss, w1 [T][S]) as fac_fwd_lin computes them.
+    """x [T][N], trans [N][N], target[0..S).  Returns (loss, w1 [T][S]) as the one-wave-per-utterance kernel
+       of round 4 computed them (the kernel is retired -- DESIGN.md 3.5 -- and the model stays as the numerics study of
+       ONE EXPONENT PER LANE; what the product runs, one exponent per position, is the group = 1 case of fac_forward_linear).
        h_t[i] = alpha_t[i] * exp(A[y_i][y_i]) (linear, frame-shifted): h_t[i] = c_t[y_i] * (h_{t-1}[i] + kappa[i] h_{t-1}[i-1]),
        c_t[n] = 2 ** (z_t[n] - max_n z_t[n]), z_t[n] = (x_t[n] + A[n][n]) log2(e) -- ONE row of N values per frame, computed with an
        integer / fraction split so that it cannot underflow -- kappa[i] = exp(A[y_i][y_{i-1}] - A[y_{i-1}][y_{i-1}]).
@@ -251,11 +256,11 @@ def fac_kernel_model(x, trans, target, S, P=5, R=4, D=600):
     return (zsum + float(e[last // P])) / L2E + np.log(h[last]) - A[y[last], y[last]], w1
 
 
-FAC_SAFE_BITS = 160.0   # kFacSafeBits of csrc/criterion_fac_lin.hpp
+FAC_SAFE_BITS = 160.0   # the bound the retired one-exponent-per-lane kernel used (the product's, per position: kFacPlinSafeBits = 900)
 
 
 def fac_kernel_gain_bits(x, trans, target, S):
-    """what fac_fwd_lin measures to decide whether its per-lane exponents are exact for an utterance: the largest per-frame
+    """what the modelled kernel measured to decide whether its per-lane exponents are exact for an utterance: the largest per-frame
     spread of the label scores (x_t[n] + A[n][n]) log2 e plus the largest |log2 kappa| of the target; beyond FAC_SAFE_BITS the
     utterance is flagged and the log-domain kernel recomputes it"""
     x = np.asarray(x, np.float64)

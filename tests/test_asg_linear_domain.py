@@ -86,7 +86,8 @@ def test_fcc_kernel_model_lagged_scale(T, N, scale, tscale):
                                              (700, 30, 64, 64, 30.0, 1), (900, 30, 320, 310, 25.0, 5), (301, 30, 300, 298, 22.0, 5), (301, 30, 300, 300, 22.0, 5),
                                              (304, 30, 300, 300, 20.0, 5), (200, 30, 64, 64, 22.0, 1)])
 def test_fac_kernel_model_lane_exponents(T, N, L, S, scale, P):
-    """fp64 mantissas, one exponent per lane of P positions, renormalised every 4 frames through the decaying maximum scan:
+    """(the model of the round-4 one-wave-per-utterance kernel, which is retired: kept as the numerics study behind the design)
+    fp64 mantissas, one exponent per lane of P positions, renormalised every 4 frames through the decaying maximum scan:
     loss 1e-6 relative (the per-frame factors are fp32 exp2 values), stay weights within 1e-5 of the oracle's wherever the
     backward pass can reach"""
     x, A, tgt = _case(T, N, L, S, scale, T + S + 7)

@@ -1,5 +1,5 @@
-"""Round 4: the N <= 31 ASG kernels (csrc/criterion_asg_dpp.hpp: FCC and Viterbi on DPP row rotations in a scaled linear
-domain; csrc/criterion_fac_lin.hpp: FAC with fp64 mantissas and one exponent per lane) and the widened CTC label
+"""Round 4: the N <= 31 ASG kernels (csrc/criterion_asg_mitm.hpp, csrc/criterion_asg_dpp.hpp: FCC and Viterbi on DPP row rotations
+in a scaled linear domain; csrc/criterion_fac_mitm.hpp: FAC with fp64 mantissas and one exponent per position) and the widened CTC label
 probabilities, against the CPU oracle through the C ABI.
 
 Bar (BASELINE.json north_star): Viterbi paths bit-exact; loss / gradients within 1e-4 of the oracle relative to the largest
@@ -95,9 +95,9 @@ def test_fac_lin_positions_per_lane_edges(oracle, L):
                                                (301, 300, 60.0, 0.5), (304, 300, 60.0, 0.5), (1500, 7, 40.0, 3.0), (600, 200, 3.0, 12.0),
                                                (2000, 300, 1.0, 25.0), (600, 200, 3.0, 50.0), (2000, 64, 1.0, 100.0)])
 def test_fac_lin_magnitudes(oracle, T, L, xscale, ascale):
-    """one exponent per lane, renormalised every 4 frames: tight alignments (T ~ L: the lattice front IS the path), emissions
-    whose per-frame spread exceeds what one fp32 (or one shared) scale can hold (scale 22: ~130 bits per frame, inside the
-    range the linear-domain kernel keeps exact); beyond kFacSafeBits (scale 40, 60; transition spreads of tens of nats) the
+    """one exponent per position: tight alignments (T ~ L: the lattice front IS the path), emissions whose per-frame spread
+    exceeds what one fp32 (or one shared) scale can hold (scale 22: ~130 bits per frame, inside the range the linear-domain
+    kernel keeps exact); beyond kFacPlinSafeBits (largest label-score spread plus largest transition ratio, in bits) the
     kernel flags the utterance and the log-domain kernel recomputes it -- the result must be right either way.  Transition
     rows 100+ nats wide (ascale 25 ... 100; round 5): kappa = exp(A[y_i][y_{i-1}] - A[y_{i-1}][y_{i-1}]) leaves the fp32 range --
     taken with __expf it was 0 or inf and the loss of such an utterance -inf / NaN (tools/exp/asg_wide_transitions.py)"""
@@ -168,107 +168,6 @@ def test_ctc_wide_logit_gaps(oracle, B, T, N, L, scale):
     assert np.isfinite(ol).all() and np.isfinite(loss.detach().cpu().numpy()).all()
     assert relerr(loss.detach().cpu().numpy(), ol) < TOL
     assert gradrel(xt.grad.cpu().numpy(), o.backward(w.astype(np.float64))) < TOL
-
-
-def test_asg_generations_agree_and_timing():
-    """the probe library can run the previous kernel generation (W2L_ASG_OLD=1): both agree at the bench shape; prints the
-    four kernel timings side by side (informational)"""
-    import os
-    import subprocess
-    import sys
-    code = r'''
-import os, sys, json, numpy as np, torch
-sys.path.insert(0, os.getcwd())
-from wav2letter_amd import _lib
-_lib.use_probe().__enter__()
-from wav2letter_amd import ASGLoss, CriterionScaleMode
-B, T, N, L = 64, 2000, 30, 300
-g = torch.Generator(device="cpu").manual_seed(4)
-x = torch.randn(B, T, N, generator=g).cuda().requires_grad_(True)
-tgt = torch.full((B, L), -1, dtype=torch.int32)
-for b in range(B):
-    l = int(torch.randint(60, L + 1, (1,), generator=g))
-    y = torch.randint(0, 28, (l,), generator=g, dtype=torch.int32)
-    for i in range(1, l):
-        if y[i] == y[i - 1]:
-            y[i] = (y[i] + 1) % 28
-    tgt[b, :l] = y
-tgt = tgt.cuda()
-crit = ASGLoss(N, CriterionScaleMode.TARGET_SZ_SQRT, 4.0).cuda()
-def timeit(fn, n=10):
-    for _ in range(3): fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-loss = crit(x, tgt); loss.sum().backward()
-out = {"loss": loss.detach().cpu().numpy().tolist(), "dx": x.grad.cpu().numpy().ravel()[::997].tolist(),
-       "dA": crit.transitions.grad.cpu().numpy().ravel().tolist(), "path": crit.viterbiPath(x.detach()).cpu().numpy().ravel()[::13].tolist(),
-       "fwd_ms": timeit(lambda: crit(x, tgt)), "fwd_bwd_ms": timeit(lambda: crit(x, tgt).sum().backward()),
-       "fcc_ms": timeit(lambda: crit.fcc(x, tgt)), "fac_ms": timeit(lambda: crit.fac(x, tgt)), "vit_ms": timeit(lambda: crit.viterbiPath(x.detach()))}
-print("RESULT" + json.dumps(out))
-'''
-    res = {}
-    for name, env in (("new", {}), ("old", {"W2L_ASG_OLD": "1"})):
-        e = dict(os.environ)
-        e.update(env)
-        p = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, timeout=600,
-                           cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-        assert p.returncode == 0, p.stderr[-2000:]
-        import json
-        res[name] = json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT")][0][6:])
-    n, o = res["new"], res["old"]
-    print("ASG generations (ms): " + ", ".join(f"{k} new {n[k]:.3f} old {o[k]:.3f}" for k in ("fwd_ms", "fwd_bwd_ms", "fcc_ms", "fac_ms", "vit_ms")))
-    assert np.abs(np.array(n["loss"]) - np.array(o["loss"])).max() < 1e-4 * np.abs(np.array(o["loss"])).max()
-    assert np.abs(np.array(n["dx"]) - np.array(o["dx"])).max() < 1e-4 * np.abs(np.array(o["dx"])).max()
-    assert np.abs(np.array(n["dA"]) - np.array(o["dA"])).max() < 1e-4 * np.abs(np.array(o["dA"])).max()
-    assert n["path"] == o["path"]
-
-
-_VARIANT_CODE = r'''
-import os, sys, numpy as np, torch
-sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
-from wav2letter_amd import _lib
-_lib.use_probe().__enter__()
-from oracle import pyoracle as O
-from wav2letter_amd import ForceAlignmentCriterion, FullConnectionCriterion
-from test_gpu_criterion import dev, gradrel, make_targets, relerr
-for (B, T, N, L, xs) in [(3, 33, 30, 12, 1.5), (2, 700, 30, 300, 1.0), (2, 301, 29, 300, 6.0), (2, 257, 17, 130, 2.0), (2, 1, 5, 1, 1.0)]:
-    rng = np.random.default_rng(T + L)
-    x = (rng.normal(size=(B, T, N)) * xs).astype(np.float32)
-    A = rng.normal(size=(N, N)).astype(np.float32)
-    tgt = make_targets(rng, B, L, N, T, min_len=max(1, min(L, T) - 3))
-    w = rng.normal(size=B).astype(np.float32)
-    for cls, orc in ((FullConnectionCriterion, None), (ForceAlignmentCriterion, None)):
-        crit = cls(N, 4).cuda(); crit.transitions.data = dev(A)
-        xt = dev(x).requires_grad_(True)
-        loss = crit(xt, dev(tgt)); (loss * dev(w)).sum().backward()
-        o = O.FCC(x, A, O.batch_target_size(tgt, T), 4) if cls is FullConnectionCriterion else O.FAC(x, A, tgt, scale_mode=4)
-        ol = o.forward(); odx, odA = o.backward(w.astype(np.float64))
-        assert relerr(loss.detach().cpu().numpy(), ol) < 1e-4, (cls.__name__, T, L)
-        assert gradrel(xt.grad.cpu().numpy(), odx) < 1e-4, (cls.__name__, T, L)
-        if T > 1: assert gradrel(crit.transitions.grad.cpu().numpy(), odA) < 1e-4, (cls.__name__, T, L)
-print("VARIANT OK")
-'''
-
-
-@pytest.mark.parametrize("env", [{"W2L_FCC_1WAVE": "1"}, {"W2L_FAC_GEN": "wave", "W2L_FAC_BWD": "wave"}, {"W2L_FAC_GEN": "blin", "W2L_FAC_BWD": "blk51"},
-                                 {"W2L_FAC_GEN": "blin2", "W2L_FAC_BWD": "blk42"}, {"W2L_ASG_OLD": "1"}, {"W2L_FCC_DTRANS_OLD": "1"}, {"W2L_FAC_BWD32": "1"}, {"W2L_ASG_NOMITM": "1"}])
-def test_asg_kernel_variants_of_the_probe_library(env):
-    """the kernel generations the product does not run stay selectable in the probe library (A/B work) and stay correct: the
-    one-wave FCC scans, the one-wave FAC scans (with their hand-over to the log-domain kernel), the barrier-per-frame FAC scans (rows by a sixth wave / from the pre-pass; backward 5 x 1 and 4 x 2),
-    the round-3 log-domain kernels, the transition gradient by lane broadcasts instead of the MFMA kernel, the FAC backward scan with 32-frame chunks,
-    the round-4 / round-5 full-length scans (fcc_*_dpp2, fac_*_plin) that the meet-in-the-middle pair replaced in round 6"""
-    import os
-    import subprocess
-    import sys
-    e = dict(os.environ)
-    e.update(env)
-    p = subprocess.run([sys.executable, "-c", _VARIANT_CODE], env=e, capture_output=True, text=True, timeout=900,
-                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    assert p.returncode == 0 and "VARIANT OK" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
 
 
 def _asg_composed(Lb, B, T, N, L, mode, x, tgt, A, w):

@@ -64,7 +64,8 @@ def test_wave_ops_selftest():
     assert (o[320:384] == v[17]).all()
 
 
-@pytest.mark.parametrize("B,T,N", [(3, 1, 2), (2, 2, 5), (3, 9, 30), (2, 50, 33), (2, 17, 64), (4, 301, 30)])
+@pytest.mark.parametrize("B,T,N", [(3, 1, 2), (2, 2, 5), (3, 9, 30), (2, 50, 33), (2, 17, 64), (4, 301, 30),
+                                   (2, 50, 32), (2, 257, 32)])   # N = 32: the only size on fcc_*_small<32> / fcc_*_log<32> / fcc_dtrans_small<32>
 @pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
 def test_fcc_matches_oracle(oracle, B, T, N, mode):
     from wav2letter_amd import FullConnectionCriterion
@@ -88,7 +89,9 @@ def test_fcc_matches_oracle(oracle, B, T, N, mode):
 
 
 @pytest.mark.parametrize("B,T,N,L", [(3, 6, 4, 3), (2, 40, 30, 40), (3, 90, 30, 70), (2, 300, 28, 200),
-                                      (2, 400, 30, 300), (2, 120, 100, 64), (2, 50, 1500, 20)])
+                                      (2, 400, 30, 300), (2, 120, 100, 64), (2, 50, 1500, 20),
+                                      # N = 33: outside the linear-domain path -- fac_fwd_blk / fac_bwd_blk in their 2 x 1, 4 x 1, 8 x 1 and 4 x 2 shapes
+                                      (2, 140, 33, 100), (2, 270, 33, 200), (2, 340, 33, 300)])
 @pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
 def test_fac_matches_oracle(oracle, B, T, N, L, mode):
     from wav2letter_amd import ForceAlignmentCriterion
@@ -154,7 +157,8 @@ def test_asg_full_size_identities():
         assert abs(crit.transitions.grad.double().sum().item() - B * (T - 1)) < 1e-4 * B * (T - 1)
 
 
-@pytest.mark.parametrize("B,T,N", [(3, 1, 2), (2, 7, 5), (5, 60, 30), (2, 33, 64), (3, 700, 30)])
+@pytest.mark.parametrize("B,T,N", [(3, 1, 2), (2, 7, 5), (5, 60, 30), (2, 33, 64), (3, 700, 30),
+                                   (3, 129, 32)])   # N = 32: viterbi_small<32>
 def test_viterbi_bit_exact(oracle, B, T, N):
     from wav2letter_amd import ASGLoss
     rng = np.random.default_rng(T + N)

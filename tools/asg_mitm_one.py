@@ -1,10 +1,10 @@
 """the four ASG criterion calls (FCC / FAC forward / backward) alone at the config-4 criterion shape, timed with events.
-W2L_ASG_NOMITM=1 (probe library): the round-4 / round-5 full-length scans.   usage: asg_mitm_one.py [B T N L]"""
+W2L_MITM_ONLY=0 / 1 (probe library, timing only): one half of every meet-in-the-middle kernel alone.   usage: asg_mitm_one.py [B T N L]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from wav2letter_amd import _lib
-if os.environ.get("W2L_ASG_NOMITM") is not None or os.environ.get("W2L_MITM_ONLY") is not None: _lib.use_probe().__enter__()
+if os.environ.get("W2L_MITM_ONLY") is not None: _lib.use_probe().__enter__()
 B, T, N, Lt = (int(v) for v in sys.argv[1:5]) if len(sys.argv) > 4 else (64, 2000, 30, 300)
 L = _lib.lib(); s = torch.cuda.current_stream().cuda_stream
 g = torch.Generator().manual_seed(1)
@@ -38,4 +38,4 @@ for name, f in calls.items():
     for _ in range(20): f()
     e1.record(); torch.cuda.synchronize()
     out.append("%s %.1f us" % (name, e0.elapsed_time(e1) / 20 * 1e3))
-print("B=%d T=%d N=%d L=%d nomitm=%s only=%s: " % (B, T, N, Lt, os.environ.get("W2L_ASG_NOMITM", "-"), os.environ.get("W2L_MITM_ONLY", "-")) + "  ".join(out), flush=True)
+print("B=%d T=%d N=%d L=%d only=%s: " % (B, T, N, Lt, os.environ.get("W2L_MITM_ONLY", "-")) + "  ".join(out), flush=True)

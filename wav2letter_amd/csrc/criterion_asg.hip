@@ -1,5 +1,5 @@
 // criterion_asg.hip -- FullConnectionCriterion and ForceAlignmentCriterion as ONE translation unit, and the ASG criterion's
-// one-launch forward pass built from both (round 6).
+// one-launch forward pass built from both.
 //
 // fl::pkg::speech::ASGLoss = FullConnectionCriterion - ForceAlignmentCriterion (recipes/slimIPL/src/Train.cpp:408-410, :1675).  The
 // two criteria's forward scans are independent chains of T / 2 dependent frames; side by side on two streams they cost the caller's
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(kFacFinishThreads) void asg_finish_fwd(int T, int N
 }
 
 bool asg_forward_merged_ok(int B, int T, int N, int L) {
-  return fac_asg_fused_ok(B, T, N, L) && asg_dpp_path(N) && asg_mitm_path() && mitm_only() < 0 && 4 * B <= 256;
+  return fac_asg_fused_ok(B, T, N, L) && asg_dpp_path(N) && mitm_only() < 0 && 4 * B <= 256;
 }
 
 // ts [B] (out), loss [B] (out), loss2 [B] (ForceAlignmentCriterion's own loss, kept for diagnostics); the two criteria's workspaces
@@ -66,8 +66,7 @@ int asg_forward_merged(int B, int T, int N, int L, int scaleMode, const float* i
   if (!input || !target || !ts || !trans || !loss || !loss2 || !fccWorkspace || !facWorkspace) return W2L_EINVAL;
   FccWs fw = fcc_ws(fccWorkspace, B, T, N);
   FacWs aw = fac_ws(facWorkspace, B, T, N, L);
-  hipLaunchKernelGGL(fac_rows_k, dim3((unsigned)((T + kFacRowsPerWave * kFacRowsWaves - 1) / (kFacRowsPerWave * kFacRowsWaves)), (unsigned)B), dim3(64 * kFacRowsWaves), 0, s, T, N, input,
-                     trans, aw.crow, aw.zmax, aw.zspr, target, L, ts, aw.tgpart, (unsigned)((size_t)2 * B * N * N));
+  fac_launch_rows(B, T, N, L, input, trans, aw, target, ts, aw.tgpart, (unsigned)((size_t)2 * B * N * N), s);
   W2L_LAUNCH_CHECK();
 #define W2L_ASG_M_GO(NWV) hipLaunchKernelGGL((asg_mitm_fwd<NWV>), dim3(B, 4), dim3(64 * NWV > 128 ? 64 * NWV : 128), mitm_excl(B, (const void*)asg_mitm_fwd<NWV>), s, T, N, L, input, target, (const int*)ts, trans, fw, aw)
   switch ((L + 63) / 64) {

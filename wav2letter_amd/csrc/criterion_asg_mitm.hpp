@@ -1,27 +1,61 @@
-// criterion_asg_mitm.hpp -- FullConnectionCriterion for N <= 31 states, MEET IN THE MIDDLE (round 6); included by criterion_fcc.hip
-// behind criterion_asg_dpp.hpp, whose machinery (scaled linear domain, DPP row-rotation products, the two arrangements of a 32-vector,
-// chain wave + helper wave) it reuses.
+// criterion_asg_mitm.hpp -- FullConnectionCriterion for N <= 31 states (the ASG letter sets: N = 30 for LibriSpeech) in a SCALED
+// LINEAR domain on DPP row-rotation products, scanned from both ends of the utterance to a middle frame (MEET IN THE MIDDLE);
+// included by criterion_fcc.hip behind criterion_asg_dpp.hpp, which has the products and the two arrangements of a 32-vector.
 //
 // Replaces fl::lib::{cpu,cuda}::FullConnectionCriterion<float> (un-vendored; call sites recipes/slimIPL/src/Train.cpp:408-410,
-// :1675; math SURVEY.md App. B.2; CPU restatement oracle/criterion_oracle.c).
+// :1675; math SURVEY.md App. B.2; CPU restatement oracle/criterion_oracle.c; the arithmetic of the alpha chain and of its beta
+// continuation is modelled op for op in oracle/asg_linear_domain.py::fcc_kernel_model*).
 //
-// The scans of criterion_asg_dpp.hpp are T dependent frames per pass: at T = 2000 the forward pass (alpha, 0 -> T-1) took 310 us
-// and the backward pass (beta, T-1 -> 0) 330 us on 64 + 64 waves of an otherwise idle chip.  alpha and beta are independent
-// recursions, so each pass runs BOTH, from the two ends to the middle frame m = (T - 1) / 2, in two workgroups per utterance:
-//   forward  (fcc_mitm_fwd):  block 0: u_t = q_t . (E u_{t-1}),   t = 0 .. m       (alpha: exactly fcc_fwd_dpp2, stopped at m)
+// The domain.  The log-domain recursion carries exp / log / a wave maximum on the chain of every frame.  Here the vector lives in
+// a scaled linear domain with none of them on the chain:
+//   u_t = (E u_{t-1}) * q_t,   E = exp(A - rowmax),   q_t = P_t 2^-k_t,   P_t = 2^(x_t log2 e + rowmax log2 e - max over states)
+// k_t is a power-of-two scale that follows the total mass with a LAG -- k_{t+1} = exponent(sum_j u_{t-1}[j]) - k_t, clamped to
+// +-kFccKClamp -- so it is fixed a frame before it is used: neither a maximum nor a normalisation sits on the chain, and the
+// magnitude of u_t is bounded by the growth of two frames.  The sum arrives for free as row 31 of the product (E[31][j] = 1; that
+// is why N <= 31; lane 63 holds state 31 in both arrangements).  Each frame's growth is at least exp(-spread of a transition row),
+// so rows spread over more than kFccSafeSpread nats could carry the fp32 vector into the denormals: such an utterance is flagged
+// (FccWs::redo) before the first frame and runs on the log-domain pair fcc_fwd_log / fcc_bwd_log instead.
+// The backward recursion is b_{t-1} = E^T (b_t q_t) in the same domain; d loss / d x_t = u_t b_t and the transition gradient is
+// E .* sum_t r_t u_{t-1}^T with r_t = b_t q_t, by the parallel kernel fcc_dtrans_mfma.
+//
+// Two waves per utterance.  A wave that is alone on its SIMD issues one VALU instruction every ~6.5 cycles, dependent or not
+// (tools/micro/clock_probe.hip), so a frame of a one-wave scan costs (instructions it issues) x 6.5 cycles, and only ~25 of a
+// frame's ~67 instructions are the dependency chain.  The utterance therefore gets a SECOND wave on another SIMD of the same CU
+// for everything that is not the chain:
+//   wave 0 (chain):  q = ldexp(P_t, -k_t) ; u = combine(dpp_dot16(u, E)) * q ; scale bookkeeping on the scalar unit ; u, q -> LDS
+//   wave 1 (helper): P_t of the NEXT chunk of kDppChunk frames -> LDS (emission loads, the state maxima, exp2, the fp64 sum of the
+//                    maxima) and the PREVIOUS chunk's u, q from LDS -> workspace
+// with one s_barrier per chunk (double-buffered LDS rings).  The barrier is `s_waitcnt lgkmcnt(0); s_barrier` (W2L_LDS_BARRIER):
+// __syncthreads() would also drain vmcnt(0) -- the helper's prefetch loads and row stores -- once per chunk.  The continuation
+// scans of the backward pass split the same way.
+//
+// Meet in the middle.  A full-length pass is T dependent frames on 2 B waves of an otherwise idle chip.  alpha and beta are
+// independent recursions, so each pass runs BOTH, from the two ends to the middle frame m = fcc_mitm_mid(T), in two workgroups per
+// utterance:
+//   forward  (fcc_mitm_fwd):  block 0: u_t = q_t . (E u_{t-1}),   t = 0 .. m       (alpha)
 //                             block 1: b_{t-1} = E^T (b_t . q'_t), t = T-1 .. m+1   (beta with a scale sequence of its own)
 //                             loss = scale ((S_m + S'_m) ln 2 + log sum_i u_m[i] b_m[i])   (fcc_mitm_finish)
 //   backward (fcc_mitm_bwd):  block 0: b_{t-1} = E^T (b_t . q_t),  t = m .. 1       (beta continued on the ALPHA half's scales)
 //                             block 1: u_t = q'_t . (E u_{t-1}),   t = m+1 .. T-1   (alpha continued on the BETA half's scales)
 // Continuing each recursion on the OTHER half's scale sequence keeps sum_i u_t[i] b_t[i] = G (the middle frame's value) at every
 // frame, so the posterior is u_t b_t / G with no per-frame normaliser, the continuation chains carry no scale bookkeeping at all, and
-//   d loss / d x_t = g u_t b_t / G,   r_t = b_t q_t / G  (the operand of the transition-gradient kernel fcc_dtrans_mfma, unchanged).
-// T / 2 dependent frames per pass instead of T, 2 B workgroups instead of B.  Workspace per frame: ahat[t] = u_t, logs[t] = the scale
-// q the frame's u_t was produced with (q_t for t <= m, q'_t above), r[t] = r_t; r2[t] = b_t q'_t of the forward pass (t > m).
+//   d loss / d x_t = g u_t b_t / G,   r_t = b_t q_t / G  (the operand of the transition-gradient kernel fcc_dtrans_mfma).
+// T / 2 dependent frames per pass, 2 B workgroups.  Workspace per frame: ahat[t] = u_t, logs[t] = the scale q the frame's u_t was
+// produced with (q_t for t <= m, q'_t above), r[t] = r_t; r2[t] = b_t q'_t of the forward pass (t > m).
 #pragma once
 #include "criterion_asg_dpp.hpp"
 
 namespace w2l {
+
+constexpr float kLog2e = 1.44269504088896341f;
+// k_t is clamped to +-kFccKClamp: a sum of 0 or of inf / NaN reads as exponent -127 / +128, and with the clamp the frame's scale
+// q_t = P_t 2^-k_t (P_t in (0, 1]) is a finite fp32 either way
+constexpr int kFccKClamp = 64;
+// the mass of u_t is bounded below by the growth of two frames, each at least exp(-spread of a transition row): rows spread
+// over more than this many nats could carry the fp32 vector into the denormals -> such a call runs on the log-domain kernels
+constexpr float kFccSafeSpread = 30.f;
+
+__device__ __forceinline__ float ldexp_f32(float v, int e) { return __builtin_amdgcn_ldexpf(v, e); }
 
 // the middle frame.  Not the centre: per frame the beta half of the forward pass costs 158 ns against the alpha half's 136 (its
 // emission rows, scale rows and r rows run against the address order) and the continuations 135 / 148 ns
@@ -76,7 +110,7 @@ __device__ __forceinline__ void fcc_mitm_fwd_body(int T, int N, const float* __r
   const float rmlG = actG ? rows.rmG * kLog2e : 0.f, rmlH = actH ? rows.rmH * kLog2e : 0.f;
 
   if (dir == 0) {
-    // ================================================================ alpha: frames 0 .. m (fcc_fwd_dpp2 with the end at m)
+    // ================================================================ alpha: frames 0 .. m
     const int TE = m + 1;
     if (!chain) {
       float* ub = ws.ahat + (size_t)b * T * N;

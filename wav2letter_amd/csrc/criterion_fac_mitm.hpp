@@ -1,26 +1,165 @@
-// criterion_fac_mitm.hpp -- ForceAlignmentCriterion for N <= 32 labels and targets of up to 320 positions, MEET IN THE MIDDLE
-// (round 6); included by criterion_fac.hip behind criterion_fac_lin.hpp, whose pipelined scaled-linear scans (fac_fwd_plin /
-// fac_bwd_plin: one position per thread with its own exponent, the waves of an utterance as a skewed pipeline) it generalises.
+// criterion_fac_mitm.hpp -- ForceAlignmentCriterion for N <= 32 labels and targets of up to 320 positions (the ASG letter recipes:
+// N = 30, L <= 300) in a SCALED LINEAR domain, scanned from both ends of the utterance to a middle frame (MEET IN THE MIDDLE);
+// included by criterion_fac.hip, which keeps the log-domain kernels for every other shape and for the utterances flagged here.
 //
 // Replaces fl::lib::{cpu,cuda}::ForceAlignmentCriterion<float> (un-vendored; call sites recipes/slimIPL/src/Train.cpp:408-410,
-// :1675; math SURVEY.md App. B.1; CPU restatement oracle/criterion_oracle.c).
+// :1675; math SURVEY.md App. B.1; CPU restatement oracle/criterion_oracle.c; the numerics study behind the domain:
+// oracle/asg_linear_domain.py).
 //
-// fac_fwd_plin is T dependent frames (335 us at T = 2000, L = 300), fac_bwd_plin another T (280 us).  The lattice has a forward
-// and a backward recursion that do not depend on each other, so each pass runs both, from the two ends to the middle frame
-// m = (T - 1) / 2, in two workgroups per utterance (fac_mitm_fwd / fac_mitm_bwd, grid (B, 2)):
+// The domain.  The log-domain scan (fac_fwd_blk) pays ~16 dependent fp64 / transcendental operations per position and frame plus
+// one workgroup barrier per frame.  Here the lattice is carried as
+//   h_t[i] = alpha_t[i] exp(A[y_i][y_i])  ->  h_t[i] = c_t[y_i] (h_{t-1}[i] + kappa[i] h_{t-1}[i-1])
+//   c_t[n] = 2^(z_t[n] - max_n z_t[n]),  z_t[n] = (x_t[n] + A[n][n]) log2 e:   ONE row of N values per frame (the 300 positions
+//            share 30 labels), with an integer / fraction split (fp32 exp2 of the fraction, fp64 ldexp of the integer part: no
+//            underflow however far a label lies below the frame's best).  The rows do not depend on the recursion, so a parallel
+//            pre-pass over all (utterance, frame) pairs computes them (fac_rows_k: fp64 [B][T][32], the frame maxima and the
+//            frame spreads [B][T]) and the scans gather c_t[y_i] from there, prefetched a chunk of kPlinChunk frames ahead;
+//   kappa[i] = exp(A[y_i][y_{i-1}] - A[y_{i-1}][y_{i-1}])   (fac_exp_wide: any float difference, as an fp64 value)
+// so a position costs ONE fp64 fma and ONE fp64 multiply per frame.  One position per THREAD, each an fp64 mantissa with ITS OWN
+// integer exponent (FacRec; the `group = 1` case of oracle/asg_linear_domain.py::fac_forward_linear -- the study shows one exponent
+// per frame is not enough): every position keeps the full fp64 range on its own, so there is no renormalisation scan and no
+// pruning on the chain.  What a single frame's update can still do to one position is bounded by the range check (kFacPlinSafeBits).
+// The forward leaves the stay share w1[t][i] = h_{t-1}[i] / (h_{t-1}[i] + kappa[i] h_{t-1}[i-1]) (fp32, [B][T][L]) -- all the
+// backward scan needs.
+//
+// The pipeline.  A wave that is alone on its SIMD issues one VALU instruction every ~6.5 cycles whether or not the instructions
+// depend on each other, and an LDS write -> s_barrier -> LDS read hand-over costs ~65 cycles, ~400 once 5 - 6 waves must meet at it
+// (tools/micro/clock_probe.hip): with one position per thread a frame is ~27 instructions, and a barrier per frame would BE the
+// kernel.  A position needs only its neighbour's value of the PREVIOUS frame: inside a wave that is a DPP lane shift, and between
+// waves it is ONE record per frame per wave boundary.  So the waves of an utterance run as a SKEWED PIPELINE with no workgroup
+// barrier at all: a wave runs a whole chunk of kPlinChunk frames behind its leader; the boundary records go through an LDS ring of
+// kPlinRing frames (four chunks), and the waves synchronise ONCE PER CHUNK through a progress word per wave -- the follower polls
+// until its leader has finished the chunk, and the leader checks that its follower is less than three chunks behind before it
+// overwrites ring slots.  Records first, then the progress word: the LDS executes a wave's operations in order.  Per frame that
+// leaves 3 DPP moves, one broadcast LDS read and one single-lane LDS write.  Every poll is bounded (kPlinSpinMax): a wave that
+// never sees its leader poisons the result (NaN) instead of hanging the GPU.
+//
+// Meet in the middle.  A full-length pass is T dependent frames.  The lattice has a forward and a backward recursion that do not
+// depend on each other, so each pass runs both, from the two ends to the middle frame m = fac_mitm_mid(T), in two workgroups per
+// utterance (fac_mitm_fwd / fac_mitm_bwd, grid (B, 2)):
 //   forward, block 0 (alpha):  h_t[i] = c_t[y_i] (h_{t-1}[i] + kappa_i h_{t-1}[i-1]),  t = 0 .. m;  w1[t][i] = share of the stay term
 //   forward, block 1 (beta):   G_t[i] = c_t[y_i] g_t[i],  g_t[i] = G_{t+1}[i] + kappa_{i+1} G_{t+1}[i+1],  t = T-1 .. m;
 //                              w1[t+1][i] = share of the stay term in g_t[i]   (rows m+1 .. T-1: the share that LEAVES (t, i) upward)
 //   fac_mitm_finish:           Z = sum_i h_m[i] g_m[i]  ->  loss;  gamma_m[i] = h_m[i] g_m[i] / Z;  the range check
-//   backward, block 0 (down):  gamma_{t-1}[i] = gamma_t[i] w1[t][i] + gamma_t[i+1] (1 - w1[t][i+1]),    t = m .. 1   (fac_bwd_plin from m)
+//   backward, block 0 (down):  gamma_{t-1}[i] = gamma_t[i] w1[t][i] + gamma_t[i+1] (1 - w1[t][i+1]),    t = m .. 1
 //   backward, block 1 (up):    gamma_t[i] = gamma_{t-1}[i] w1[t][i] + gamma_{t-1}[i-1] (1 - w1[t][i-1]),  t = m+1 .. T-1
-// Both backward recursions are exp-free fp32 and start from the SAME posterior gamma_m; stay / advance masses are accumulated per
-// position for the transition gradient as before, g gamma_t goes to ws.dal for fac_scatter_k.  T / 2 dependent frames per pass.
-// The h and G recursions are one body (fac_half_fwd<BETA>): mirrored neighbour, mirrored pipeline direction, reversed frame order.
+// Both backward recursions are exp-free fp32 (five operations per position and frame) and start from the SAME posterior gamma_m;
+// stay / advance masses are accumulated per position for the transition gradient, g gamma_t goes to ws.dal for the scatter kernels
+// (criterion_fac.hip).  T / 2 dependent frames per pass.  The h and G recursions are one body (fac_half_fwd<BETA>): mirrored
+// neighbour, mirrored pipeline direction, reversed frame order; likewise the two backward halves (fac_half_bwd<UP>).
+//
+// One idiom recurs in the scans: `asm volatile("" : "+v"(reg))` over a chunk of prefetched registers.  hipcc places
+// `s_waitcnt vmcnt(0)` at the first use of a loaded register, and on gfx9 that counter is shared, in order, by loads AND stores.
+// With a load still pending at the loop head, every frame's first use waits for the NEXT chunk's prefetch -- one memory latency
+// per chunk; with a use behind the chunk's stores, it waits for the stores' round trip too.  So the first chunk is made to land
+// before the loop, and inside the loop the prefetched chunk is consumed after the frames and BEFORE the chunk's stores are issued:
+// the loads have had the whole chunk to land and the stores drain during the next one.
 #pragma once
-#include "criterion_fac_lin.hpp"
+#include "common.hpp"
+#include <type_traits>
 
 namespace w2l {
+
+constexpr int kFacEmptyExp = -(1 << 30);   // exponent of a position without mass (mantissa 0)
+// exp(d) as an fp64 value for any float d: the fraction by the fp32 exp2, the integer part by ldexp; exp(-inf) = 0.  (__expf is 0 /
+// inf beyond -87 / +88 nats: with transition rows that wide -- kappa is exp of a DIFFERENCE of two transitions -- a forced alignment
+// through such a step came out -inf / NaN while the log-domain reference stays finite: tools/exp/asg_wide_transitions.py)
+__device__ __forceinline__ double fac_exp_wide(float d) {
+  if (!(d > -INFINITY)) return d != d ? (double)d : 0.0;   // -inf -> 0 (position 0, positions beyond the target); NaN stays NaN
+  const double z = fmin(fmax((double)d * 1.4426950408889634, -1070.0), 1020.0);
+  const double zi = rint(z);
+  return __builtin_amdgcn_ldexp((double)__builtin_amdgcn_exp2f((float)(z - zi)), (int)zi);
+}
+// one lattice position: h = m 2^e with the mantissa m in [0.5, 1), or m = 0 and e = kFacEmptyExp
+struct FacRec { double m; int e; int pad; };
+
+// ---- label rows: c_t[n] as fp64 [B][T][32], the frame maxima and the frame spreads [B][T] (see the header)
+constexpr int kFacRowsPerWave = 8;
+constexpr int kFacRowsWaves = 4;   // waves per workgroup (16000 one-wave workgroups at B = 64, T = 2000 were launch-rate bound: 20 us)
+// max over the 32 lanes of this lane's half of the wave (every lane gets it): the in-row DPP reduction of wave_max_rows, then the
+// two rows of the half through a 16-lane swap
+__device__ __forceinline__ float half_wave_max(float v) {
+  asm volatile(
+      "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\tv_max_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 0"
+      : "+v"(v));
+  return fmaxf(v, __shfl_xor(v, 16));
+}
+// Two frames per pass: N <= 32 labels fill half a wave, so lanes 0 .. 31 take frame t and lanes 32 .. 63 frame t + 1 -- half the
+// instructions per frame, 512-byte stores (12 us at B = 64, T = 2000).
+__global__ __launch_bounds__(64 * kFacRowsWaves) static void fac_rows_k(int T, int N, const float* __restrict__ x, const float* __restrict__ trans,
+                                                 double* __restrict__ crow, float* __restrict__ zmax, float* __restrict__ zspr = nullptr,
+                                                 const int* __restrict__ tsTarget = nullptr, int tsL = 0, int* __restrict__ tsOut = nullptr,
+                                                 float* __restrict__ zeroBuf = nullptr, unsigned zeroCount = 0) {
+  // (zeroBuf: the transition-gradient partials of the backward pass, cleared here -- backward starts without a fill launch)
+  if (zeroBuf) {
+    const unsigned stride = gridDim.x * gridDim.y * blockDim.x;
+    for (unsigned k = (blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; k < zeroCount; k += stride) zeroBuf[k] = 0.f;
+  }
+  // (tsOut: the ASG criterion's fused sequence -- the utterance's target size, batch_target_size_k's count of the labels in front of
+  //  the first negative one capped at T, by the first wave of the utterance's first block: no launch of its own in front of the scans)
+  if (tsOut && blockIdx.x == 0 && threadIdx.x < 64) {
+    const int* y = tsTarget + (size_t)blockIdx.y * tsL;
+    int first = tsL;
+    for (int i = (int)threadIdx.x; i < tsL; i += 64)
+      if (y[i] < 0) { first = i; break; }
+    for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off));
+    if (threadIdx.x == 0) tsOut[blockIdx.y] = first < T ? first : T;
+  }
+  const int b = blockIdx.y, lane = threadIdx.x & 63, half = lane >> 5, n = lane & 31;
+  const int t0 = (blockIdx.x * kFacRowsWaves + (threadIdx.x >> 6)) * kFacRowsPerWave;
+  const float L2E = 1.44269504088896341f;
+  const bool act = n < N;
+  const float adl = act ? trans[(size_t)n * N + n] * L2E : 0.f;
+  const float* xb = x + (size_t)b * T * N;
+  float xv[kFacRowsPerWave / 2];
+#pragma unroll
+  for (int s = 0; s < kFacRowsPerWave / 2; ++s) xv[s] = (act && t0 + 2 * s + half < T) ? xb[(size_t)(t0 + 2 * s + half) * N + n] : 0.f;
+#pragma unroll
+  for (int s = 0; s < kFacRowsPerWave / 2; ++s) {
+    const int t = t0 + 2 * s + half;
+    const float z = act ? fmaf(xv[s], L2E, adl) : -INFINITY;
+    const float zm = half_wave_max(z);
+    const float zr = fmaxf(z - zm, -4000.f);
+    const float zi = __builtin_rintf(zr);
+    const double c = __builtin_amdgcn_ldexp((double)__builtin_amdgcn_exp2f(zr - zi), (int)zi);
+    float sp = 0.f;
+    if (zspr) sp = half_wave_max(act ? (z == z ? zm - z : INFINITY) : 0.f);   // the frame's spread (bits), for the range check of fac_mitm_finish; a NaN score makes it NaN
+    if (t < T) {
+      crow[((size_t)b * T + t) * 32 + n] = act ? c : 0.0;
+      if (n == 0) {
+        zmax[(size_t)b * T + t] = zm;
+        if (zspr) zspr[(size_t)b * T + t] = zm == zm ? sp : __builtin_nanf("");
+      }
+    }
+  }
+}
+
+// ---- the pipelined waves (see the header)
+constexpr int kPlinChunk = 16;          // frames between two synchronisations of neighbouring waves
+constexpr int kPlinRing = 64;           // ring slots per wave boundary: four chunks
+constexpr int kPlinSpinMax = 1 << 18;   // ~10 ms: a legitimate wait is a few microseconds
+// Range of the linear-domain scans: a position's value is an fp64 mantissa with its own integer exponent, but one frame's update
+// multiplies by kappa (fp64, any |log2| up to ~1020) and by the label weight c_t[y] = 2^(z - max z) (fp64, 0 below 2^-1074) BEFORE it
+// is split again: tot = m + kappa m_left lies in [2^-1 kappa, 2^1021), h = c tot >= 2^-(1 + |log2 kappa| + spread).  While
+// (largest |log2 kappa| of the target) + (largest per-frame spread of the label scores) <= kFacPlinSafeBits nothing leaves the
+// normal range.  Beyond that (transition rows ~100 nats wide: profiles/r05_run31_asg_wide_transitions_after.log had loss -inf
+// against a finite oracle) fac_mitm_finish flags the utterance in ws.redo and the log-domain kernel fac_fwd_blk recomputes it.
+constexpr float kFacPlinSafeBits = 900.f;
+
+__device__ __forceinline__ bool plin_wait_ge(const int* p, int want) {   // poll *p >= want (relaxed LDS loads), bounded
+  int spins = 0, v;
+#pragma clang loop unroll(disable)
+  do {
+    v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (v >= want) return true;
+    __builtin_amdgcn_s_sleep(1);
+  } while (++spins < kPlinSpinMax);
+  return false;
+}
 
 // the middle frame: alpha takes 6 / 11 of the frames -- 168 ns per frame against the beta half's 202 (profiles/r06_run10_*)
 __host__ __device__ inline int fac_mitm_mid(int T) { return (int)(((long long)(T - 1) * 6) / 11); }
@@ -68,7 +207,7 @@ __device__ __forceinline__ void fac_half_fwd(int T, int N, int L, const int* __r
 #pragma unroll
   for (int s = 0; s < kPlinChunk; ++s) cc[s] = cw(s);
 #pragma unroll
-  for (int s = 0; s < kPlinChunk; ++s) asm volatile("" : "+v"(cc[s]));   // landed before the loop (see fac_fwd_plin)
+  for (int s = 0; s < kPlinChunk; ++s) asm volatile("" : "+v"(cc[s]));   // landed before the loop (see the header)
   double m = 0.0;
   int e = kFacEmptyExp;
   bool ok = true;

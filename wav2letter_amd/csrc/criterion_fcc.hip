@@ -6,15 +6,22 @@
 // (ASGLoss), :1675 (forward), :838 (viterbiPath).  Math: SURVEY.md App. B.2/B.3,
 // CPU restatement: oracle/criterion_oracle.c.
 //
-// Small-N path (N <= 64, the ASG letter/phone case, N = 30 for LibriSpeech):
-// ONE WAVEFRONT PER UTTERANCE scans T inside a single launch.
+// Four paths by the number of states:
+//   N <= 31 (the ASG letter sets, N = 30 for LibriSpeech): scaled linear domain on DPP row rotations, scanned from both ends to a
+//            middle frame -- criterion_asg_mitm.hpp; Viterbi on the same rotations -- criterion_asg_dpp.hpp;
+//   N == 32, 33 .. 64: the scaled-exp scans below (fcc_*_small<32>, <64>; viterbi_small);
+//   N > 64:  criterion_fcc_big.hip.
+// Every N <= 64 scan flags the utterances it cannot hold exactly (FccWs::redo), and the log-domain pair fcc_fwd_log / fcc_bwd_log,
+// launched behind it, computes exactly those.
+//
+// The scaled-exp scans: ONE WAVEFRONT PER UTTERANCE scans T inside a single launch.
 //   lane i <-> state i.  exp(A[i][j] - rowmax_i) lives in NP registers per lane.
 //   Step: e_j = exp(ahat_{t-1}[j]) (one v_exp per lane); s_i = sum_j EA[i][j] e_j
 //   with e_j broadcast by v_readlane into an SGPR operand of v_fmac (no LDS, no
 //   barrier); ahat_t[i] = x_t[i] + rowmax_i + log s_i - c_t, c_t = max_i (DPP).
 //   The running offset sum_t c_t is kept in fp64 so the fp32 recursion never
 //   carries O(T) magnitudes (ASG = FCC - FAC cancellation, SURVEY 7 hard part 2b).
-//   Emission rows are read as coalesced [t][0..N) rows, prefetched 8 steps ahead.
+//   Emission rows are read as coalesced [t][0..N) rows, prefetched kChunk steps ahead.
 // Workspace keeps ahat [B][T][N] and log s [B][T][N] (fp32) for backward, which
 // then needs neither the emissions nor any exp-domain re-summation:
 //   w_ij = EA[i][j] e_j / s_i.
@@ -45,7 +52,7 @@ struct FccWs {
   float* bm;     // [B][32] ... : b_m of the beta half, by state
   float* ginv;   // [B]     ... : 1 / sum_i u_m[i] b_m[i]
   int* redo;     // [B]  1 = this utterance is outside what the fp32 scaled-domain scan holds exactly -- N <= 31: transition rows spread
-                 //      over more than kFccSafeSpread nats (fcc_fwd_dpp sets it); 32 <= N <= 64: some state's sum fell under
+                 //      over more than kFccSafeSpread nats (fcc_mitm_fwd sets it); 32 <= N <= 64: some state's sum fell under
                  //      kFccMinSum (fcc_fwd_small sets it) -- and runs on the log-domain pair fcc_fwd_log / fcc_bwd_log instead
 };
 
@@ -71,25 +78,17 @@ __host__ __device__ inline FccWs fcc_ws(void* ws, int B, int T, int N) {
 
 }  // namespace w2l
 
-#include "criterion_asg_dpp.hpp"   // N <= 31: scaled linear domain on DPP row rotations (fcc_fwd_dpp, fcc_bwd_dpp, vit_fwd_dpp, vit_psi_k, vit_walk_k)
-#include "criterion_asg_mitm.hpp"  // N <= 31, the product: the same scans from both ends to the middle frame (fcc_mitm_fwd, fcc_mitm_bwd)
+#include "criterion_asg_dpp.hpp"   // N <= 31: products on DPP row rotations; Viterbi (vit_fwd_dpp, vit_psi_k, vit_walk_k)
+#include "criterion_asg_mitm.hpp"  // N <= 31: scaled linear domain, scans from both ends to the middle frame (fcc_mitm_fwd, fcc_mitm_bwd)
 
 namespace w2l {
 
-// N <= 31 runs the DPP kernels; the probe library can put the previous generation back for A/B work (W2L_ASG_OLD=1)
-inline bool asg_dpp_path(int N) {
-  static const bool old = tune_env("W2L_ASG_OLD") != nullptr;
-  return N <= 31 && !old;
-}
-// ... and, for A/B work, the round-4 full-length scans of criterion_asg_dpp.hpp instead of the meet-in-the-middle pair (W2L_ASG_NOMITM=1)
+// N <= 31 runs the DPP kernels (row 31 of their products carries the total mass)
+inline bool asg_dpp_path(int N) { return N <= 31; }
 // probe, timing only (results are wrong): W2L_MITM_ONLY=0 / 1 launches one half of every meet-in-the-middle kernel alone
 inline int mitm_only() {
   static const int v = [] { const char* e = tune_env("W2L_MITM_ONLY"); return e ? (e[0] == '1' ? 1 : 0) : -1; }();
   return v;
-}
-inline bool asg_mitm_path() {
-  static const bool off = tune_env("W2L_ASG_NOMITM") != nullptr || tune_env("W2L_FCC_1WAVE") != nullptr;
-  return !off;
 }
 
 template <int NP>
@@ -97,10 +96,9 @@ __global__ __launch_bounds__(64) void fcc_fwd_small(int T, int N, int scaleMode,
                                                     const float* __restrict__ x,
                                                     const int* __restrict__ targetSize,
                                                     const float* __restrict__ trans,
-                                                    float* __restrict__ loss, FccWs ws, const int* __restrict__ redo = nullptr) {
+                                                    float* __restrict__ loss, FccWs ws) {
   const int b = blockIdx.x;
   const int lane = threadIdx.x;
-  if (redo && !redo[b]) return;   // launched behind fcc_fwd_dpp: only the utterances it flagged
   const bool act = lane < N;
   const float NEG = -INFINITY;
 
@@ -175,12 +173,12 @@ __global__ __launch_bounds__(64) void fcc_fwd_small(int T, int N, int scaleMode,
   float tot = wave_sum(e);
   float sc = scale_of(scaleMode, T, targetSize[b]);
   // range check: every sum of every state stayed above kFccMinSum (and was a number), else the log-domain kernel behind this one
-  // recomputes the utterance.  (Launched as the fallback of an older generation -- `redo` given -- there is nothing behind it.)
+  // recomputes the utterance
   const bool low = __any(act && !(smin >= kFccMinSum)) != 0;
   if (lane == 0) {
     loss[b] = (float)((double)sc * (C + (double)__logf(tot)));
     ws.scale[b] = sc;
-    if (!redo) ws.redo[b] = low ? 1 : 0;
+    ws.redo[b] = low ? 1 : 0;
   }
 }
 
@@ -276,17 +274,16 @@ __global__ __launch_bounds__(64) void fcc_bwd_small(int T, int N, const float* _
   if (act) dxb[lane] = g * da;
 }
 
-// ---------------------------------------------------------------- the log-domain pair behind the N <= 31 scans (round 5)
-// The utterances the linear-domain scans flag (transition rows more than 30 nats wide) used to re-run on fcc_*_small above,
-// which are scaled-exp recursions too -- exp(A - rowmax) and exp(alpha - c_t) as separate fp32 factors, a floor of 1e-37 under
-// the sums -- and clamp a state that is more than ~87 nats behind: with emissions AND transitions tens of nats wide the posterior
-// moved to another path (loss within 1e-4, gradients off by O(1): profiles/r05_run32_criterion_fuzz.log).  These two evaluate
-// every term as ONE exponential of a sum that is <= 0 by construction, as the reference's recursion does:
+// ---------------------------------------------------------------- the log-domain pair behind every N <= 64 scan
+// For the utterances the scaled scans flag.  A scaled-exp recursion -- exp(A - rowmax) and exp(alpha - c_t) as separate fp32 factors, a
+// floor of 1e-37 under the sums -- clamps a state that is more than ~87 nats behind: with emissions AND transitions tens of nats wide
+// the posterior moves to another path (loss within 1e-4, gradients off by O(1): profiles/r05_run32_criterion_fuzz.log).  These two
+// evaluate every term as ONE exponential of a sum that is <= 0 by construction, as the reference's recursion does:
 //   L_t[i]  = log sum_j exp(ahat_{t-1}[j] + A[i][j])  (max over j first),      alpha_t[i] = x_t[i] + L_t[i],  ahat = alpha - c_t
 //   w_t[i][j] = exp(ahat_{t-1}[j] + A[i][j] - L_t[i]) in (0, 1],   dalpha_{t-1}[j] = sum_i dalpha_t[i] w_t[i][j],
 //   dA[i][j] = sum_t dalpha_t[i] w_t[i][j]   (accumulated by the same loop: no r_t hand-over to the fcc_dtrans kernels).
 // One wave per flagged utterance, lane = state, N <= NP (32 or 64); `ahat` and `logs` (= L_t) keep the workspace meaning of the
-// other kernels.  NP = 64 (round 6): the fallback of the 32-64-label scans fcc_*_small<64>, which flag what they cannot hold.
+// other kernels.  MITM (N <= 31): the grid's "not flagged" branch computes the loss of the two linear-domain halves instead.
 template <int NP, bool MITM = false>
 __device__ __forceinline__ void fcc_fwd_log_body(int T, int N, int scaleMode, const float* __restrict__ x,
                                                  const int* __restrict__ targetSize, const float* __restrict__ trans,
@@ -438,13 +435,11 @@ __global__ __launch_bounds__(64) void fcc_bwd_log(int T, int N, const float* __r
 }
 
 // transition gradient of one (utterance, time chunk): part[i][j] = g * EA[i][j] * sum_{t in chunk} r_t[i] e_{t-1}[j]
-// lane = j; r_t (left in the log-s slots by the scan) is broadcast per i.  No dependence between steps.
-// LIN: the workspace of the DPP scans -- `ahat` holds u_t itself (scaled linear domain), r_t = b_t q_t.
-template <int NP, bool LIN = false>
+// lane = j; r_t (ws.r, left by the backward scan) is broadcast per i; e_{t-1} = exp(ahat_{t-1}).  No dependence between steps.
+template <int NP>
 __global__ __launch_bounds__(64) void fcc_dtrans_small(int T, int N, const float* __restrict__ trans,
                                                        const float* __restrict__ grad, FccWs ws) {
   const int b = blockIdx.x, c = blockIdx.y;
-  const bool lin = LIN;
   const int lane = threadIdx.x;
   const bool act = lane < N;
   if (ws.redo[b]) {   // a flagged utterance ran on fcc_fwd_log / fcc_bwd_log: its whole transition gradient is in chunk 0
@@ -466,7 +461,7 @@ __global__ __launch_bounds__(64) void fcc_dtrans_small(int T, int N, const float
   for (int t = t0; t < t1; ++t) {
     const float r = act ? rb[(size_t)t * N + lane] : 0.f;
     const float ev = act ? ahb[(size_t)(t - 1) * N + lane] : 0.f;
-    const float e = lin ? ev : (act ? __expf(ev) : 0.f);
+    const float e = act ? __expf(ev) : 0.f;
 #pragma unroll
     for (int i = 0; i < NP; ++i) acc[i] = fmaf(readlane(r, i), e, acc[i]);
   }
@@ -487,9 +482,10 @@ __global__ __launch_bounds__(64) void fcc_dtrans_small(int T, int N, const float
   }
 }
 
-// The same partial for the N <= 31 path on the matrix pipe: sum_t r_t[i] e_{t-1}[j] is a [N x frames] . [frames x N] product -- one
+// The same partial for the N <= 31 path (its workspace holds the linear-domain vector itself: e_{t-1} = ahat[t-1] = u_{t-1}, and
+// r_t = b_t q_t / G) on the matrix pipe: sum_t r_t[i] e_{t-1}[j] is a [N x frames] . [frames x N] product -- one
 // v_mfma_f32_32x32x2_f32 per two frames (A: lane (i, k) = r_{t+k}[i], B: lane (k, j) = e_{t+k-1}[j]) instead of 30 broadcasts + 30
-// FMAs per frame: 39 -> ~8 us behind the backward scan at B = 64, T = 2000 (it is on the criterion's critical path).
+// FMAs per frame: ~8 us behind the backward scan at B = 64, T = 2000 (it is on the criterion's critical path).
 __global__ __launch_bounds__(64) void fcc_dtrans_mfma(int T, int N, const float* __restrict__ trans, const float* __restrict__ grad, FccWs ws) {
   typedef float f32x16_t __attribute__((ext_vector_type(16)));
   const int b = blockIdx.x, c = blockIdx.y;
@@ -584,10 +580,6 @@ __global__ void reduce_chunks(int C, size_t n, float* __restrict__ part) {
 }
 
 // ---------------------------------------------------------------- Viterbi
-struct VitWs {
-  unsigned char* psi;  // [B][T][N]
-};
-
 constexpr int kBtChunk = 256;  // backtrace chunk (time steps staged in LDS)
 
 template <int NP>
@@ -735,19 +727,12 @@ W2L_API int w2l_fcc_forward(int B, int T, int N, int scaleMode, const float* inp
   }
   hipStream_t s = (hipStream_t)stream;
   FccWs ws = fcc_ws(workspace, B, T, N);
-  if (asg_dpp_path(N) && asg_mitm_path()) {
-    // product: alpha over frames 0 .. m and beta over T-1 .. m in two workgroups per utterance; the loss from the middle frame
-    // (and the log-domain recursion for the utterances the range check flagged) by the second launch
+  if (asg_dpp_path(N)) {
+    // alpha over frames 0 .. m and beta over T-1 .. m in two workgroups per utterance; the loss from the middle frame (and the
+    // log-domain recursion for the utterances the range check flagged) by the second launch
     hipLaunchKernelGGL(fcc_mitm_fwd, dim3(B, mitm_only() < 0 ? 2 : 1), dim3(128), mitm_excl(B, (const void*)fcc_mitm_fwd), s, T, N, input, trans, ws, mitm_only() < 0 ? 0 : mitm_only());
     W2L_LAUNCH_CHECK();
     hipLaunchKernelGGL((fcc_fwd_log<32, true>), dim3(B), dim3(64), 0, s, T, N, scaleMode, input, targetSize, trans, loss, ws);
-  } else if (asg_dpp_path(N)) {
-    static const bool oneWave = tune_env("W2L_FCC_1WAVE") != nullptr;   // probe: the one-wave scan (A/B)
-    if (oneWave) hipLaunchKernelGGL(fcc_fwd_dpp, dim3(B), dim3(64), 0, s, T, N, scaleMode, input, targetSize, trans, loss, ws);
-    else hipLaunchKernelGGL(fcc_fwd_dpp2, dim3(B), dim3(128), 0, s, T, N, scaleMode, input, targetSize, trans, loss, ws);
-    W2L_LAUNCH_CHECK();
-    // the log-domain kernel for the utterances fcc_fwd_dpp flagged (returns at once for the others)
-    hipLaunchKernelGGL(fcc_fwd_log<32>, dim3(B), dim3(64), 0, s, T, N, scaleMode, input, targetSize, trans, loss, ws);
   } else if (N <= 32) {
     // the scaled-exp scan flags the utterances whose sums left its range (kFccMinSum); the log-domain kernel recomputes those
     hipLaunchKernelGGL(fcc_fwd_small<32>, dim3(B), dim3(64), 0, s, T, N, scaleMode, input, targetSize, trans, loss, ws);
@@ -781,35 +766,26 @@ int w2l::fcc_backward_impl(int B, int T, int N, const float* trans, const float*
   }
   hipStream_t s = (hipStream_t)stream;
   FccWs ws = fcc_ws(workspace, B, T, N);
-  const bool dpp = asg_dpp_path(N);
-  if (dpp && asg_mitm_path()) {
+  // the backward scan, the log-domain kernel for the flagged utterances, the transition-gradient partials per (utterance, time chunk)
+  if (asg_dpp_path(N)) {
     hipLaunchKernelGGL(fcc_mitm_bwd, dim3(B, mitm_only() < 0 ? 2 : 1), dim3(128), mitm_excl(B, (const void*)fcc_mitm_bwd), s, T, N, trans, grad, inputGrad, ws, mitm_only() < 0 ? 0 : mitm_only());
     W2L_LAUNCH_CHECK();
     hipLaunchKernelGGL(fcc_bwd_log<32>, dim3(B), dim3(64), 0, s, T, N, trans, grad, inputGrad, ws);
-  } else if (dpp) {
-    static const bool oneWave = tune_env("W2L_FCC_1WAVE") != nullptr;
-    if (oneWave) hipLaunchKernelGGL(fcc_bwd_dpp, dim3(B), dim3(64), 0, s, T, N, trans, grad, inputGrad, ws);
-    else hipLaunchKernelGGL(fcc_bwd_dpp2, dim3(B), dim3(128), 0, s, T, N, trans, grad, inputGrad, ws);
     W2L_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fcc_bwd_log<32>, dim3(B), dim3(64), 0, s, T, N, trans, grad, inputGrad, ws);
+    hipLaunchKernelGGL(fcc_dtrans_mfma, dim3(B, kDtChunks), dim3(64), 0, s, T, N, trans, grad, ws);
   } else if (N <= 32) {
     hipLaunchKernelGGL(fcc_bwd_small<32>, dim3(B), dim3(64), 0, s, T, N, trans, grad, inputGrad, ws);
     W2L_LAUNCH_CHECK();
     hipLaunchKernelGGL(fcc_bwd_log<32>, dim3(B), dim3(64), 0, s, T, N, trans, grad, inputGrad, ws);
+    W2L_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fcc_dtrans_small<32>, dim3(B, kDtChunks), dim3(64), 0, s, T, N, trans, grad, ws);
   } else {
     hipLaunchKernelGGL(fcc_bwd_small<64>, dim3(B), dim3(64), 0, s, T, N, trans, grad, inputGrad, ws);
     W2L_LAUNCH_CHECK();
     hipLaunchKernelGGL(fcc_bwd_log<64>, dim3(B), dim3(64), 0, s, T, N, trans, grad, inputGrad, ws);
-  }
-  W2L_LAUNCH_CHECK();
-  if (dpp && !tune_env("W2L_FCC_DTRANS_OLD"))
-    hipLaunchKernelGGL(fcc_dtrans_mfma, dim3(B, kDtChunks), dim3(64), 0, s, T, N, trans, grad, ws);
-  else if (dpp)
-    hipLaunchKernelGGL((fcc_dtrans_small<32, true>), dim3(B, kDtChunks), dim3(64), 0, s, T, N, trans, grad, ws);
-  else if (N <= 32)
-    hipLaunchKernelGGL(fcc_dtrans_small<32>, dim3(B, kDtChunks), dim3(64), 0, s, T, N, trans, grad, ws);
-  else
+    W2L_LAUNCH_CHECK();
     hipLaunchKernelGGL(fcc_dtrans_small<64>, dim3(B, kDtChunks), dim3(64), 0, s, T, N, trans, grad, ws);
+  }
   W2L_LAUNCH_CHECK();
   size_t n = (size_t)N * N;
   hipLaunchKernelGGL(reduce_chunks, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, s, kDtChunks, n, ws.tgpart);
