@@ -287,6 +287,10 @@ class FL_COMPAT_API Sequential : public Container {
   std::string prettyString() const override;
   std::shared_ptr<Sequential> planned() const;                // the pipeline behind a Sequential of layer objects (null otherwise)
   void setInputFeatures(int nFeat) { inputFeatures_ = nFeat; } // fl_compat extension: NFEAT of the (T, NFEAT, 1, B) input when the first layer does not say it
+  // fl_compat extension (slimIPL's dynamic dropout, recipes/slimIPL/src/Train.cpp:1465-1469; the recipe's plugin hands the number
+  // to its Transformer layers only, 100h_supervised_slimipl.cpp:41-58): the probabilities the `TR` layers of the planned pipeline
+  // use from the next forward on (w2l_trainer_set_dropout); a negative value restores the arch value; no new plan
+  virtual void setTransformerDropout(double pDropout, double pLayerDrop);
 
  private:
   void materialize();
@@ -426,6 +430,19 @@ class FL_COMPAT_API CoalescingReducer : public Reducer {
   std::vector<Span> spans_;
   size_t lastCollectives_ = 0, lastOverlapped_ = 0;
 };
+
+// ---- fl::ext: fl_compat EXTENSIONS for slimIPL.  The reference has NO such free functions: its Trainer writes the averaged
+// network as one ArrayFire expression per parameter (recipes/slimIPL/src/Train.cpp:1823-1832) and selects the labelled utterances
+// with an indexing expression on the Variable (:1637-1639).
+namespace ext {
+// ema <- decay * ema + (1 - decay) * net, fp32.  Two planned networks of the same arch: ONE w2l_ema_update over the parameter
+// arenas; anything else: one call per parameter.  Whatever the averaged network derives from its parameters (weight-norm
+// products, bf16 weight images) is rebuilt by its next forward.  decay outside [0, 1] / NaN: std::invalid_argument.
+FL_COMPAT_API void emaUpdate(const std::shared_ptr<fl::Module>& ema, const std::shared_ptr<fl::Module>& net, double decay);
+// the (N, T, |rows|) emissions of the listed utterances of an (N, T, B) batch; backward writes their gradients into a zero-filled
+// gradient of the full batch.  All rows in order: the argument itself.
+FL_COMPAT_API Variable selectBatch(const Variable& emission, const std::vector<int>& rows);
+}  // namespace ext
 
 namespace pkg {
 namespace runtime {

@@ -480,6 +480,12 @@ int w2l_pool_time_backward(const float* x, const float* dy, float* dx, int B, in
                            w2l_stream_t stream);
 int w2l_axpy(float* y, const float* x, size_t n, float alpha, w2l_stream_t stream);
 int w2l_fill(float* y, size_t n, float v, w2l_stream_t stream);
+/* ema[i] = (float)decay * ema[i] + (float)(1 - decay) * p[i], fp32, ONE launch over a flat parameter arena: the averaged
+ * "teacher" network of slimIPL (--slimIPL_ema, recipes/slimIPL/src/Train.cpp:1819-1832: one expression per parameter there).
+ * ema and p need float alignment only and may sit differently against a 16-byte boundary.  n == 0: W2L_OK without a
+ * launch.  A null pointer, or a decay that is NaN or outside [0, 1]: W2L_EINVAL before anything touches the device.  No
+ * non-finite guard: the reference moves the average even when the optimizer's update was skipped. */
+int w2l_ema_update(float* ema, const float* p, size_t n, double decay, w2l_stream_t stream);
 int w2l_transpose(const float* in, float* out, int G, int R, int C, w2l_stream_t stream);
 /* MFSC / log-mel front end (fl::lib::audio::Mfsc as configured by LogMelFeature.cpp:78-95, [UNVENDORED]): the linear
  * per-frame part (pre-emphasis, window, DFT) is one w2l_gemm_f32 on overlapping rows of the audio (lda = frame stride);
@@ -605,6 +611,12 @@ int w2l_trainer_set_step(void* h, uint32_t step);
  * with fp32 accumulation (w2l_set_matmul_precision scoped to the network's calls); storage, master weights, convolutions,
  * LayerNorm, the criterion (recipes/joint_training_vox_populi/cpc/Train.cpp:1184) and the optimizer stay fp32 */
 int w2l_trainer_set_mixed_precision(void* h, int on);
+/* slimIPL's dynamic dropout (--slimIPL_dyn_dropout, recipes/slimIPL/src/Train.cpp:1141-1168 with the recipe plugin's
+ * 100h_supervised_slimipl.cpp:41-58): the probabilities the `TR` layers -- and only they -- use from the next forward on.  A
+ * negative value restores that layer's arch value.  No new plan: a trainer with the override set computes, bit for bit, what a
+ * trainer built from the arch text with these numbers in its `TR` lines computes at the same step and seed.  W2L_EINVAL: a
+ * value that is NaN or >= 1. */
+int w2l_trainer_set_dropout(void* h, double pDropout, double pLayerDrop);
 /* gradient norm seen by the last w2l_trainer_update (before the 1/totalBatch scale; taken on every update).  A
  * non-finite norm means the update was SKIPPED on every rank (the norm is taken on the all-reduced gradient):
  * the counterpart of the reference's NaN guards, recipes/slimIPL/src/Train.cpp:1651-1660, :1686-1698. */

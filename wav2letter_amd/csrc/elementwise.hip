@@ -552,6 +552,57 @@ __global__ __launch_bounds__(kEwThreads) void axpy_k(float* __restrict__ y, cons
     y[e] += alpha * x[e];
 }
 
+// ema = d * ema + od * p over a flat parameter arena: the averaged "teacher" network of slimIPL
+// (recipes/slimIPL/src/Train.cpp:1819-1832, one ArrayFire expression per parameter there), one launch here.  The two
+// arenas are only float-aligned and may sit differently against a 16-byte boundary: the vectors are cut on `ema` (a scalar
+// head in front of its first boundary, a scalar tail), its loads and stores are aligned, and `p` is read through a
+// 4-byte-aligned vector type (a dwordx4 load needs dword alignment only).  A trip is kEmaVecs vectors of each array per
+// thread, all loads landed before the first store: stores count in vmcnt on gfx9, so a rolled load / store loop keeps
+// ONE vector per thread in flight.
+typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
+constexpr int kEmaVecs = 4;
+
+__global__ __launch_bounds__(kEwThreads) void ema_k(float* __restrict__ ema, const float* __restrict__ p, size_t n, float d, float od) {
+  size_t head = ((16 - ((uintptr_t)ema & 15)) & 15) >> 2;
+  if (head > n) head = n;
+  const size_t n4 = (n - head) >> 2;
+  float4* __restrict__ e4 = (float4*)(ema + head);
+  const float4u* __restrict__ p4 = (const float4u*)(p + head);
+  constexpr size_t kTrip = (size_t)kEwThreads * kEmaVecs;   // vectors of one block and trip, contiguous
+  for (size_t base = (size_t)blockIdx.x * kTrip; base + kTrip <= n4; base += (size_t)gridDim.x * kTrip) {
+    float4 a[kEmaVecs];
+    float4u b[kEmaVecs];
+#pragma unroll
+    for (int k = 0; k < kEmaVecs; ++k) {
+      a[k] = e4[base + (size_t)k * kEwThreads + threadIdx.x];
+      b[k] = p4[base + (size_t)k * kEwThreads + threadIdx.x];
+    }
+#pragma unroll
+    for (int k = 0; k < kEmaVecs; ++k) {   // landed at one point, before the first store
+      asm volatile("" : "+v"(a[k].x), "+v"(a[k].y), "+v"(a[k].z), "+v"(a[k].w));
+      asm volatile("" : "+v"(b[k].x), "+v"(b[k].y), "+v"(b[k].z), "+v"(b[k].w));
+    }
+#pragma unroll
+    for (int k = 0; k < kEmaVecs; ++k) {
+      a[k].x = d * a[k].x + od * b[k].x; a[k].y = d * a[k].y + od * b[k].y;
+      a[k].z = d * a[k].z + od * b[k].z; a[k].w = d * a[k].w + od * b[k].w;
+      e4[base + (size_t)k * kEwThreads + threadIdx.x] = a[k];
+    }
+  }
+  // the vectors behind the last whole trip (fewer than kTrip), then the scalar head and tail
+  for (size_t i = n4 / kTrip * kTrip + (size_t)blockIdx.x * kEwThreads + threadIdx.x; i < n4; i += (size_t)gridDim.x * kEwThreads) {
+    float4 a = e4[i];
+    const float4u b = p4[i];
+    a.x = d * a.x + od * b.x; a.y = d * a.y + od * b.y; a.z = d * a.z + od * b.z; a.w = d * a.w + od * b.w;
+    e4[i] = a;
+  }
+  if (blockIdx.x == 0) {
+    const size_t tail0 = head + (n4 << 2);
+    if (threadIdx.x < head) ema[threadIdx.x] = d * ema[threadIdx.x] + od * p[threadIdx.x];
+    if (tail0 + threadIdx.x < n) ema[tail0 + threadIdx.x] = d * ema[tail0 + threadIdx.x] + od * p[tail0 + threadIdx.x];
+  }
+}
+
 // ---- batched 2-D transpose: in [G][R][Cc] -> out [G][Cc][R]  (Reorder between the
 // reference's time-fastest input (T,NFEAT,1,B) and the frame-major internal layout)
 __global__ __launch_bounds__(256) void transpose_k(const float* __restrict__ in, float* __restrict__ out, int R, int Cc) {
@@ -1012,6 +1063,15 @@ W2L_API int w2l_axpy(float* y, const float* x, size_t n, float alpha, w2l_stream
   if (!y || !x) return W2L_EINVAL;
   if (!n) return W2L_OK;
   hipLaunchKernelGGL(axpy_k, dim3(ew_grid((n >> 2) + 1)), dim3(kEwThreads), 0, W2L_S, y, x, n, alpha);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+W2L_API int w2l_ema_update(float* ema, const float* p, size_t n, double decay, w2l_stream_t stream) {
+  if (!ema || !p || !(decay >= 0.0 && decay <= 1.0)) return W2L_EINVAL;   // (a NaN decay fails both comparisons)
+  if (!n) return W2L_OK;
+  hipLaunchKernelGGL(ema_k, dim3(ew_grid(((n >> 2) + kEmaVecs) / kEmaVecs)), dim3(kEwThreads), 0, W2L_S, ema, p, n, (float)decay,
+                     (float)(1.0 - decay));
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }

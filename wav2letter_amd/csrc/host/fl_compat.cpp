@@ -897,6 +897,11 @@ class PlannedNet : public fl::Sequential {
     })};
   }
   std::string prettyString() const override { return net_->prettyString(); }
+  // (the eval-mode plan runs without dropout: only the training graph carries the numbers)
+  void setTransformerDropout(double pDropout, double pLayerDrop) override {
+    if (!(pDropout < 1.0) || !(pLayerDrop < 1.0)) throw std::invalid_argument("setTransformerDropout: probabilities must be below 1 (negative: the arch value)");
+    net_->setTransformerDropout(pDropout, pLayerDrop);
+  }
   w2l::Sequential& impl() { return *net_; }
   float* paramPtr() { return (float*)paramArena_.get(); }
   float* gradPtr() { return (float*)gradArena_.get(); }
@@ -1301,6 +1306,61 @@ std::pair<af::array, af::array> w2lScore(SequenceCriterion& criterion, const Var
 
 }  // namespace speech
 }  // namespace pkg
+
+// ------------------------------------------------------------------------------------------------ fl::ext (slimIPL)
+void Sequential::setTransformerDropout(double pDropout, double pLayerDrop) {
+  materialize();
+  if (!planned_) throw std::logic_error("fl_compat: setTransformerDropout needs a planned pipeline (an arch file or layer objects)");
+  planned_->setTransformerDropout(pDropout, pLayerDrop);
+}
+
+namespace ext {
+void emaUpdate(const std::shared_ptr<fl::Module>& ema, const std::shared_ptr<fl::Module>& net, double decay) {
+  if (!ema || !net) throw std::invalid_argument("emaUpdate: null module");
+  if (!(decay >= 0.0 && decay <= 1.0)) throw std::invalid_argument("emaUpdate: decay must lie in [0, 1]");
+  auto* pe = pkg::speech::plannedOf(ema.get());
+  auto* pn = pkg::speech::plannedOf(net.get());
+  if (pe && pn && pe != pn && pe->archSha_ == pn->archSha_ && pe->impl().paramFloats() == pn->impl().paramFloats()) {
+    // same arch: the same arena layout (the 4-float alignment gaps are zero on both sides and stay zero) -- ONE launch
+    w2l::w2lCheck(w2l_ema_update(pe->paramPtr(), pn->paramPtr(), pe->impl().paramFloats(), decay, S()), "emaUpdate");
+    return;
+  }
+  const auto a = ema->params(), b = net->params();
+  if (a.size() != b.size()) throw std::invalid_argument("emaUpdate: the two modules have different parameter lists");
+  for (size_t i = 0; i < a.size(); ++i) {
+    if (a[i].elements() != b[i].elements() || a[i].type() != af::f32 || b[i].type() != af::f32)
+      throw std::invalid_argument("emaUpdate: parameter " + std::to_string(i) + " differs in size or type");
+    w2l::w2lCheck(w2l_ema_update(a[i].array().device<float>(), b[i].array().device<float>(), (size_t)a[i].elements(), decay, S()), "emaUpdate");
+  }
+  // Nothing else to invalidate: a planned pipeline derives the weight-norm products and the bf16 weight images from the
+  // parameter arena inside EVERY forward (they live in the activation arena), so the averaged network's next forward reads
+  // the averaged parameters.
+}
+
+Variable selectBatch(const Variable& emission, const std::vector<int>& rows) {
+  if (emission.type() != af::f32) throw std::invalid_argument("selectBatch: emissions must be f32 (N, T, B)");
+  const af::dim_t N = emission.dims(0), T = emission.dims(1), B = emission.dims(2);
+  if (emission.dims(3) != 1 || rows.empty()) throw std::invalid_argument("selectBatch: (N, T, B) emissions and at least one row");
+  bool identity = (af::dim_t)rows.size() == B;
+  for (size_t k = 0; k < rows.size(); ++k) {
+    if (rows[k] < 0 || rows[k] >= B) throw std::invalid_argument("selectBatch: row " + std::to_string(rows[k]) + " outside the batch of " + std::to_string(B));
+    identity = identity && rows[k] == (int)k;
+  }
+  if (identity) return emission;
+  const size_t per = (size_t)N * T;   // an utterance of the (N, T, B) array is one contiguous run of the [B][T][N] buffer
+  af::array out(af::dim4(N, T, (af::dim_t)rows.size()), af::f32);
+  for (size_t k = 0; k < rows.size(); ++k)
+    w2l::hipCheck(hipMemcpyAsync(out.device<float>() + k * per, emission.array().device<float>() + (size_t)rows[k] * per, per * sizeof(float),
+                                 hipMemcpyDeviceToDevice, S()), "selectBatch");
+  return Variable(out, {emission}, [rows, per, N, T, B](std::vector<Variable>& ins, const Variable& gradOut) {
+    // the listed utterances' gradients into a zero-filled gradient of the full batch (a row listed twice adds up)
+    af::array full = af::constant(0.0, af::dim4(N, T, B), af::f32);
+    for (size_t k = 0; k < rows.size(); ++k)
+      w2l::w2lCheck(w2l_axpy(full.device<float>() + (size_t)rows[k] * per, gradOut.array().device<float>() + k * per, per, 1.f, S()), "selectBatch backward");
+    ins[0].addGrad(Variable(full, false));
+  });
+}
+}  // namespace ext
 }  // namespace fl
 
 // ------------------------------------------------------------------------------------------------ Serializer

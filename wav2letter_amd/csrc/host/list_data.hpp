@@ -58,6 +58,12 @@ struct ListData {
   std::unique_ptr<fl::lib::audio::Mfsc> mfsc;
   af::array unit;                               // LayerNorm (gamma, beta) = (1, 0): the per-utterance normalisation
   long batches() const { return ((long)mine.size() + batch - 1) / batch; }
+  // the samples of batch k, in batch order (slimIPL: the keys of the label cache, the transcript column the labels are scored against)
+  std::vector<const fl::pkg::speech::ListSample*> samplesOf(long k) const {
+    std::vector<const fl::pkg::speech::ListSample*> v;
+    for (long i = k * batch; i < std::min<long>((k + 1) * batch, (long)mine.size()); ++i) v.push_back(&samples[(size_t)mine[(size_t)i]]);
+    return v;
+  }
   // the batch an update trains on: every epoch walks this rank's batches in a fresh order, the SAME order on every rank (the
   // global batch g stays the union of the ranks' batches g), a function of (--seed, epoch) only so that `continue` resumes on the
   // batch the uninterrupted run would have taken (the reference reshuffles per epoch with the epoch as seed:
@@ -124,13 +130,13 @@ struct ListData {
 
   // batch k -> features (T, NFEAT, 1, B) on the device, zero beyond every utterance's own frames; targets [B][L] (-1 padded);
   // sizes [B] in samples.  Returns B (the last batch of an epoch may be short).  The NEXT batch's files are decoded in the
-  // background while the caller trains on this one.
+  // background while the caller trains on this one (kNext < 0: the caller does not know it -- slimIPL's unsupervised batches).
   int get(long k, long kNext, af::array& input, std::vector<int>& tgt, int& L, std::vector<float>& sizes, int& T) {
     std::shared_ptr<HostBatch> hb;
     if (pending.valid() && pendingK == k) hb = pending.get();
     else { if (pending.valid()) pending.get(); hb = decode(k); }
     pendingK = kNext;
-    pending = std::async(std::launch::async, [this]() { return decode(pendingK); });
+    if (kNext >= 0) pending = std::async(std::launch::async, [this]() { return decode(pendingK); });
     if (!hb->error.empty()) throw std::runtime_error(hb->error);
     const int B = (int)hb->audio.size();
     const int S = mfsc->frameStride();

@@ -995,7 +995,8 @@ class PoolTimeLayer : public Layer {
 class TransformerLayer : public Layer {
  public:
   int C = 0, mlp = 0, nH = 0, csz = 0;
-  double p = 0, pLayerDrop = 0;
+  double p = 0, pLayerDrop = 0;          // in use: the arch line's, or slimIPL's dynamic-dropout override
+  double archP = 0, archPLayerDrop = 0;  // the arch line's
   int d = 0;
   P pe, w1, b1, w2, b2, wq, bq, wk, bk, wv, bv, wf, bf, gb1, gb2;
   int B = 0, T = 0, M = 0, W = 0, rlo = 0, ldr = 0, n0 = 0;
@@ -1012,6 +1013,10 @@ class TransformerLayer : public Layer {
   BfImage xSeen;            // the images of x this step's products read: xImg, or the previous block's outImg
 
   std::string name() const override { return "Transformer"; }
+  void setTransformerDropout(double pDropout, double pLayer) override {
+    p = pDropout < 0 ? archP : pDropout;
+    pLayerDrop = pLayer < 0 ? archPLayerDrop : pLayer;
+  }
   void registerParams(std::vector<ParamInfo>& t) override {
     d = C / nH;
     auto lin = [&](const char* nm, int in, int out, double wBound, double bBound, P& w, P& b) {
@@ -1049,7 +1054,8 @@ class TransformerLayer : public Layer {
       ldr = (W + 3) / 4 * 4;
     } else { rlo = W = ldr = 0; }
     const size_t n = (size_t)M * C, ns = (size_t)B * nH * T * T, nr = (size_t)M * nH * ldr;
-    qOff = pl.alloc(n); kOff = pl.alloc(n); vOff = pl.alloc(n); sOff = pl.alloc(ns); pdOff = p > 0 ? pl.alloc(ns) : sOff;
+    qOff = pl.alloc(n); kOff = pl.alloc(n); vOff = pl.alloc(n); sOff = pl.alloc(ns);
+    pdOff = pl.alloc(ns);   // (also with p == 0: setTransformerDropout may raise it without a new plan)
     rOff = pl.alloc(nr); ctxOff = pl.alloc(n); oOff = pl.alloc(n); hOff = pl.alloc(n);
     m2Off = pl.alloc(n); outOff = pl.alloc(n);
     st1Off = pl.alloc(2 * w2l_layernorm_scratch_doubles(M, C)); mr1Off = pl.alloc(2 * (size_t)M);
@@ -1587,6 +1593,7 @@ static std::shared_ptr<Layer> buildOne(const LayerSpec& s, const LayerSpec* wnPa
     auto l = std::make_shared<TransformerLayer>();
     l->C = toI(a[0]); l->mlp = toI(a[1]); l->nH = toI(a[2]); l->csz = toI(a[3]); l->p = toD(a[4]);
     l->pLayerDrop = a.size() >= 6 ? toD(a[5]) : 0.0;
+    l->archP = l->p; l->archPLayerDrop = l->pLayerDrop;
     if ((a.size() >= 7 && toI(a[6]) != 0) || (a.size() >= 8 && toI(a[7]) != 0))
       throw std::invalid_argument("TR: pre-LayerNorm / future-mask variants are outside this build: " + s.line);
     if (l->nH < 1 || l->C % l->nH) throw std::invalid_argument("TR: heads must divide the model size: " + s.line);

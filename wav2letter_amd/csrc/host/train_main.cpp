@@ -30,6 +30,17 @@
 // through the eval-mode network and w2lScore (loss + greedy / Viterbi path in one call); `<tag>-loss | <tag>-TER | <tag>-WER`
 // follow train-WER (MyLogger.cpp:60-70), and NNN_model_<tag>.bin is written when a set's WER beats this run's best.  A
 // synthetic run ignores --valid.
+// slimIPL (the reference file's own purpose; Train.cpp:73-102, :1141-1168, :1214-1333, :1362-1415, :1478-1660, :1786-1841): with
+// --unsup_train=list,... (relative to --unsup_datadir) updates after --slimIPL_start interleave supervised batches with batches of
+// the unlabelled lists, --slimIPL_sup_updates : --slimIPL_unsup_updates, whose transcripts the TEACHER writes -- the network
+// itself or, with --slimIPL_ema, a second network of the same arch that follows it as an exponential moving average after every
+// update (fl::ext::emaUpdate: one launch over the parameter arena; NNN_model_last_ema.bin).  --slimIPL_type = naive (label, then
+// train) | cache (train on the cached labels, relabel after the update) | pre-cache (relabel before it) | fixed-pre-cache (a cache
+// of --slimIPL_fixed_cache_updates batch indices, relabelled with --slimIPL_fixed_cache_update_prob).  The schedule and the caches
+// are fl_compat/ipl.h (NNN_model_last_cache<rank>, NNN_model_last_fixed_cache<rank>, written by every rank); only the samples that
+// have a label enter the criterion (fl::ext::selectBatch), and an update for which ANY rank has none is skipped on all ranks.
+// --slimIPL_dyn_dropout sets the `TR` layers' dropout and layer drop for those updates, --slimIPL_saug a stronger SpecAugment on the
+// supervised batches.  Refused: --slimIPL_use_soft (soft labels), --unsup_train on synthetic data.
 // Flags of this driver that the reference does not have are prefixed w2l_.
 // Data parallelism is the reference's: --enable_distributed --world_rank --world_size --max_devices_per_node
 // --rndv_filepath (Train.cpp:188-199; RANK / WORLD_SIZE / LOCAL_WORLD_SIZE of a torchrun-style launcher are read when the
@@ -55,6 +66,7 @@
 #include "../../../include/fl_compat/flashlight.h"
 #include "../../../include/fl_compat/audio.h"
 #include "../../../include/fl_compat/data.h"
+#include "../../../include/fl_compat/ipl.h"
 #include "../../../include/fl_compat/text.h"
 #include "w2l_host.hpp"
 #include "list_data.hpp"
@@ -164,6 +176,30 @@ int main(int argc, char** argv) {
     const long linseg = flags.geti("linseg", 0);
     const long warmup = flags.geti("warmup", 1);
     const uint64_t seed = (uint64_t)flags.geti("seed", 0);
+    // ---- slimIPL flags (Train.cpp:73-102), refused before anything touches the device
+    const std::string unsupTrain = flags.get("unsup_train", "");
+    if (flags.getb("slimIPL_use_soft", false))
+      throw std::invalid_argument("--slimIPL_use_soft=true is not built (soft labels: the reference's branch prints whole tensors per step)");
+    SlimIPL::Options iplOpt;
+    iplOpt.type = parseIplType(flags.get("slimIPL_type", "naive"));
+    iplOpt.supUpdates = flags.geti("slimIPL_sup_updates", 1);
+    iplOpt.unsupUpdates = flags.geti("slimIPL_unsup_updates", 3);
+    iplOpt.fixedCacheUpdates = flags.geti("slimIPL_fixed_cache_updates", 1000);
+    iplOpt.fixedCacheUpdateProb = flags.getd("slimIPL_fixed_cache_update_prob", 1.0);
+    const long iplStart = flags.geti("slimIPL_start", 0);
+    const double dynDropout = flags.getd("slimIPL_dyn_dropout", -1.0);
+    const bool useEma = flags.getb("slimIPL_ema", false);
+    const double emaDecay = flags.getd("slimIPL_ema_decay", 0.999);
+    if (!(emaDecay >= 0.0 && emaDecay <= 1.0)) throw std::invalid_argument("--slimIPL_ema_decay=" + flags.get("slimIPL_ema_decay") + ": must lie in [0, 1]");
+    if (dynDropout >= 1.0) throw std::invalid_argument("--slimIPL_dyn_dropout must be below 1");
+    const long plPrintEvery = std::max<long>(1, flags.geti("w2l_ipl_print_every", 100));   // "PL for index" lines (Train.cpp:1383: every 100th update)
+    {
+      std::string trainLists0 = flags.get("train", "");
+      const std::string first0 = trainLists0.substr(0, trainLists0.find(','));
+      const bool lists0 = !first0.empty() && trainLists0.find("[DATA_DST]") == std::string::npos && fileExists(pathJoin(flags.get("datadir", ""), first0));
+      if (!unsupTrain.empty() && !lists0)
+        throw std::invalid_argument("--unsup_train needs --train list files: a synthetic run has no audio to label");
+    }
 
     // ---- number of classes: the token dictionary (+ replabels for ASG, + blank for CTC: Train.cpp:230-251)
     int numClasses = (int)flags.geti("w2l_nlabel", 0);
@@ -221,6 +257,15 @@ int main(int argc, char** argv) {
     auto critoptim = initOptimizer(criterion->params(), flags.get("critoptim", "sgd"), lrcrit0, 0.0);
     std::cout << "[Network Optimizer] " << netoptim->prettyString() << std::endl;
     std::cout << "[Criterion Optimizer] " << critoptim->prettyString() << std::endl;
+    // the teacher of slimIPL: the network itself, or with --slimIPL_ema a second network of the same arch (Train.cpp:396-405) --
+    // initialised as a copy once the student's parameters are final (below), saved as NNN_model_last_ema.bin
+    std::shared_ptr<fl::Module> networkEMA = network;
+    if (useEma) {
+      networkEMA = fl::pkg::runtime::ModulePlugin(archPath).arch(nFeat, numClasses);
+      if (flags.getb("fl_amp_use_mixed_precision", false)) setMixedPrecision(networkEMA, true);
+    }
+    // (the file of the averaged network holds the network alone, Train.cpp:776-781: a parameter-free criterion fills the container's slot)
+    std::shared_ptr<fl::Module> emaFileCrit = std::make_shared<CTCLoss>(scalemode);
     if (runStatus == "fork") {            // Train.cpp:452-459: network + criterion, fresh optimizers
       std::string version;
       Serializer::Config unused;
@@ -231,6 +276,10 @@ int main(int argc, char** argv) {
       std::string version;
       Serializer::Config unused;
       Serializer::load(reloadPath, version, unused, network, criterion, netoptim, critoptim);
+      if (useEma) {                       // Train.cpp:469-475
+        Serializer::Config unusedEma;
+        Serializer::load(getRunFile("model_last_ema.bin", runIdx - 1, runPath), version, unusedEma, networkEMA, emaFileCrit);
+      }
       std::cout << "Loaded model for continue training" << std::endl;
     }
 
@@ -248,6 +297,7 @@ int main(int argc, char** argv) {
       std::cout << "[Distributed] world rank " << fl::getWorldRank() << " of " << fl::getWorldSize()
                 << (flags.get("rndv_filepath", "").rfind("shm:", 0) == 0 ? " (host-memory test collective)" : " (RCCL)") << std::endl;
     }
+    if (useEma && runStatus != "continue") fl::ext::emaUpdate(networkEMA, network, 0.0);   // decay 0: a copy of the student
     const bool isMaster = fl::getWorldRank() == 0;
     if (haveRunDir && isMaster) {
       mkdirs(runPath);
@@ -278,6 +328,52 @@ int main(int argc, char** argv) {
       if (data.mine.empty()) throw std::invalid_argument("this rank has no samples (fewer samples than world_size * batchsize)");
       std::cout << "[Data] " << data.samples.size() << " samples in " << listPaths.size() << " list(s), " << data.mine.size() << " on this rank, "
                 << data.batches() << " batches of " << batch << " per epoch; " << nFeat << " MFSC features; " << data.dict.indexSize() << " classes" << std::endl;
+    }
+    // --unsup_train=list,... relative to --unsup_datadir (Train.cpp:326, :341-361): the same pipeline; the transcript column only
+    // serves "PL Quality" (a transcript that cannot be spelled is no error there)
+    ListData unsupData;
+    std::unique_ptr<SlimIPL> ipl;
+    if (!unsupTrain.empty()) {
+      const std::string unsupDir = flags.get("unsup_datadir", "");
+      std::vector<std::string> up;
+      std::istringstream us(unsupTrain);
+      for (std::string one; std::getline(us, one, ',');) if (!one.empty()) up.push_back(pathJoin(unsupDir, one));
+      unsupData.tolerateTextErrors = true;
+      loadListData(unsupData, up, batch, "--unsup_train", false, flags, criterionName, nFeat, numClasses, seed, unsupDir);
+      if (unsupData.mine.empty()) throw std::invalid_argument("this rank has no samples of --unsup_train (fewer samples than world_size * batchsize)");
+      std::cout << "Unsup batches " << unsupData.batches() << std::endl;
+      ipl.reset(new SlimIPL(iplOpt, unsupData.batches(), seed));
+    }
+    std::cout << "Unsup is in use " << (ipl ? 1 : 0) << std::endl;
+    long supDone = startUpdate;   // supervised batches consumed so far = the position in the supervised lists
+    if (ipl && runStatus == "continue") {   // Train.cpp:477-545: every rank's text cache (read-only), this rank's fixed cache
+      if (iplOpt.type != IplType::Naive) {
+        std::cout << "Reading PL cache" << std::endl;
+        for (int r = 0; r < fl::getWorldSize(); ++r) {
+          const std::string name = getRunFile("model_last_cache", runIdx - 1, runPath) + std::to_string(r);
+          const long n = ipl->loadCacheDump(name);
+          if (n < 0) std::cout << "Read cache from " << name << "; Skip, file doesn't exist" << std::endl;
+          else std::cout << "Read cache from " << name << " with number of samples " << n << std::endl;
+        }
+        std::cout << "Reading PL cache is done; total size " << ipl->plCacheDump.size() << std::endl;
+      }
+      if (iplOpt.type == IplType::FixedPreCache) {
+        const std::string name = getRunFile("model_last_fixed_cache", runIdx - 1, runPath) + std::to_string(fl::getWorldRank());
+        if (!ipl->loadFixedCache(name)) std::cout << "Read fixed cache from " << name << "; Skip, file doesn't exist" << std::endl;
+        else std::cout << "Reading PL fixed cache is done; total size " << ipl->fixedCache.size() << std::endl;
+      }
+    }
+    bool iplNeedEpoch = true;   // the next slimIPL step opens a pass over the supervised lists (SlimIPL::startEpoch)
+    {
+      auto st = reloadCfg.find("w2l_ipl_state");
+      auto sd = reloadCfg.find("w2l_ipl_sup_batches");
+      if (ipl && runStatus == "continue" && st != reloadCfg.end() && sd != reloadCfg.end()) {
+        ipl->setState(st->second);   // the schedule goes on where the saved run stopped
+        supDone = std::stol(sd->second);
+        iplNeedEpoch = supDone > 0 && supDone % std::max<long>(1, data.batches()) == 0;
+      } else if (ipl) {
+        ipl->begin();
+      }
     }
     // --valid=[tag:]list,... (parseValidSets, Train.cpp:232-233, :362-370): each set is scored in list order (no shuffle), every
     // rank its round-robin share, the short last batch included; --validbatchsize = -1: --batchsize
@@ -334,6 +430,9 @@ int main(int argc, char** argv) {
     double lossSum = 0;
     long lossN = 0, editErr = 0, editLen = 0, tszTotal = 0, tszMax = 0, nsamples = 0, nbatches = 0;
     fl::EditDistanceMeter wordMeter;   // list data: train-WER over words
+    double lossUnsupSum = 0;           // meters.trainUnsup (MyLogger.cpp:99-106)
+    long lossUnsupN = 0;
+    fl::EditDistanceMeter tknUnsupMeter, wordUnsupMeter;
     long framesTotal = 0;              // list data: padded input frames consumed (avg-isz, hrs)
     runtime.resume();
     network->train();
@@ -380,6 +479,11 @@ int main(int argc, char** argv) {
       char ts[64];
       std::strftime(ts, sizeof ts, "%Y-%m-%d %H:%M:%S", std::localtime(&now));
       item("timestamp", ts);
+      if (ipl) {   // MyLogger.cpp:99-106
+        item("loss Unsup", fmt("%10.5f", lossUnsupN ? lossUnsupSum / lossUnsupN : 0.0));
+        item("train-TER Unsup", fmt("%5.2f", tknUnsupMeter.value()));
+        item("train-WER Unsup", fmt("%5.2f", wordUnsupMeter.value()));
+      }
       std::cout << s.str() << std::endl;
       if (logFile.is_open()) logFile << s.str() << std::endl;
       runtime.resume();
@@ -399,10 +503,26 @@ int main(int argc, char** argv) {
       auto it = reloadCfg.find("w2l_saug_calls");
       if (it != reloadCfg.end()) saug->setCalls((uint32_t)std::stoul(it->second));
     }
+    // --slimIPL_saug (Train.cpp:1052-1076): a stronger augmentation of the SUPERVISED batches -- one frequency mask more, half as
+    // many time masks again; the unsupervised batches keep the one above (saugUnsup)
+    std::shared_ptr<fl::SpecAugment> saugSup = saug;
+    if (saug && flags.getb("slimIPL_saug", false)) {
+      saugSup = std::make_shared<fl::SpecAugment>((int)flags.geti("filterbanks", 40), (int)flags.geti("saug_fmaskf", 27), (int)flags.geti("saug_fmaskn", 2) + 1,
+                                                  (int)flags.geti("saug_tmaskt", 100), (float)flags.getd("saug_tmaskp", 1.0),
+                                                  (int)((double)flags.geti("saug_tmaskn", 2) * 1.5));
+      std::cout << "[SpecAugment of the supervised batches] " << saugSup->prettyString() << std::endl;
+      auto it = reloadCfg.find("w2l_saug_sup_calls");
+      if (runStatus == "continue" && it != reloadCfg.end()) saugSup->setCalls((uint32_t)std::stoul(it->second));
+    }
 
     // ---- checkpoints (saveModels, Train.cpp:718-790): NNN_model_last.bin after every epoch of the run and at its end
     auto saveModels = [&](long epoch, long totalUpdates) {
       if (!haveRunDir) return;
+      if (ipl && iplOpt.type != IplType::Naive) {   // Train.cpp:719-746: by every rank
+        mkdirs(runPath);
+        ipl->saveCache(getRunFile("model_last_cache", runIdx, runPath) + std::to_string(fl::getWorldRank()));
+        ipl->saveFixedCache(getRunFile("model_last_fixed_cache", runIdx, runPath) + std::to_string(fl::getWorldRank()));
+      }
       // every rank's sample-stream position travels in rank 0's file: the others hand theirs over through the run directory
       std::ostringstream rs;
       rs << rng << " " << gauss;
@@ -432,7 +552,13 @@ int main(int argc, char** argv) {
         config["w2l_data_rng." + std::to_string(r)] = b.str();
       }
       if (saug) config["w2l_saug_calls"] = std::to_string(saug->calls());
+      if (saugSup != saug) config["w2l_saug_sup_calls"] = std::to_string(saugSup->calls());
+      if (ipl) {   // the schedule's position (the draws are the same on every rank)
+        config["w2l_ipl_state"] = ipl->state();
+        config["w2l_ipl_sup_batches"] = std::to_string(supDone);
+      }
       Serializer::save(getRunFile("model_last.bin", runIdx, runPath), "0.1", config, network, criterion, netoptim, critoptim);
+      if (useEma) Serializer::save(getRunFile("model_last_ema.bin", runIdx, runPath), "0.1", Serializer::Config(), networkEMA, emaFileCrit, nullptr, nullptr);
     };
 
     // ---- validation (test(), Train.cpp:874-980): every --valid set through the eval-mode network and w2lScore (one call for the
@@ -533,12 +659,57 @@ int main(int argc, char** argv) {
       }
     };
 
+    // ---- labelling with the teacher (predictPLCommon, Train.cpp:1362-1407): teacher and criterion in eval mode, the forward on the
+    // UN-augmented features and on the eval-mode plan of the teacher (a plan and an arena of its own, as runValid's: no training
+    // buffer is touched, no step counter, dropout seed or SpecAugment call counter moves), Viterbi path -> letters -> words, joined
+    // with spaces.  "PL Quality" is the WER of the labels against the list's transcript column, summed over the ranks.
+    auto predictPL = [&](const af::array& feats, const af::array& inSizes, const std::vector<const ListSample*>& smp, long curBatch) {
+      networkEMA->eval();
+      criterion->eval();
+      auto out = networkEMA->forward({fl::input(feats), fl::noGrad(inSizes)}).front();
+      const int To = (int)out.dims(1), pB = (int)out.dims(2);
+      std::vector<int> path((size_t)pB * To);
+      criterion->viterbiPath(out.array(), inSizes).host(path.data());
+      networkEMA->train();
+      criterion->train();
+      const bool print = isMaster && curBatch % plPrintEvery == 0;
+      if (print) {
+        std::cout << "PL for samples ";
+        for (size_t b = 0; b < smp.size(); ++b) std::cout << (b ? "," : "") << smp[b]->id;
+        std::cout << std::endl;
+      }
+      const bool wp = flags.getb("usewordpiece", false);
+      fl::EditDistanceMeter quality;
+      std::vector<std::string> texts;
+      for (int b = 0; b < pB; ++b) {
+        std::vector<int> pv(path.begin() + (size_t)b * To, path.begin() + (size_t)(b + 1) * To);
+        const auto words = tkn2Wrd(tknPrediction2Ltr(pv, unsupData.dict, criterionName, flags.get("surround", ""), unsupData.replabel, wp, unsupData.wordsep),
+                                   unsupData.wordsep);
+        std::string text;
+        for (size_t w = 0; w < words.size(); ++w) text += (w ? " " : "") + words[w];
+        if (print) std::cout << "PL for index " << b << ": " << text << std::endl;
+        quality.add(words, smp[(size_t)b]->transcript);
+        texts.push_back(text);
+      }
+      float q[2] = {(float)quality.errors(), (float)quality.length()};   // (word counts of a batch: exact in f32)
+      if (fl::getWorldSize() > 1) {
+        af::array a(af::dim4(2), q);
+        fl::allReduce(a);
+        a.host(q);
+      }
+      if (isMaster) std::cout << "PL Quality for Batch " << curBatch << " : " << (q[1] > 0 ? 100.0 * (double)q[0] / (double)q[1] : 0.0) << std::endl;
+      return texts;
+    };
+    // --slimIPL_dyn_dropout (Train.cpp:1465-1469): the student's `TR` layers from the first slimIPL update on (the teacher labels
+    // in eval mode anyway)
+    bool dynDropoutSet = false;
+
     // ---- the hot loop (Train.cpp:1454-1804)
     double lr = lr0, lrcrit = lrcrit0;
     for (long curBatch = startUpdate + 1; curBatch <= iters; ++curBatch) {
       // learning rate (Train.cpp:1170-1175, :1334-1348): 0.5^(epoch steps after --lr_decay) * (cosine | gamma^(batch / stepsize)) * warm-up;
       // an epoch of the synthetic run is --w2l_synth_batches_per_epoch updates (default: the whole run is epoch 1)
-      const long curEpoch = 1 + (curBatch - 1) / batchesPerEpoch;
+      const long curEpoch = 1 + supDone / batchesPerEpoch;   // (without slimIPL every update is supervised: supDone == curBatch - 1)
       const long afterDecay = curEpoch - lrDecay;
       const double lrDecayScale = std::pow(0.5, afterDecay < 0 ? 0.0 : (double)(1 + afterDecay / lrDecayStep));
       const double lrScheduleScale = flags.getb("lrcosine", false)
@@ -550,15 +721,47 @@ int main(int argc, char** argv) {
       netoptim->setLr(lr);
       critoptim->setLr(lrcrit);
 
+      // slimIPL (Train.cpp:1214-1333): a supervised or an unsupervised step, and which unsupervised batch
+      bool isSup = true, haveBatch = true;
+      SlimIPL::Unsup us;
+      if (ipl && curBatch > iplStart) {
+        if (!dynDropoutSet && dynDropout >= 0) {
+          auto seq = std::dynamic_pointer_cast<fl::Sequential>(network);
+          if (!seq) throw std::invalid_argument("--slimIPL_dyn_dropout needs a network built from an arch file or layer objects");
+          seq->setTransformerDropout(dynDropout, dynDropout);
+          dynDropoutSet = true;
+        }
+        if (iplNeedEpoch) { ipl->startEpoch(); iplNeedEpoch = false; }
+        isSup = ipl->nextIsSup();
+        if (!isSup) us = ipl->nextUnsup();
+        ipl->advanceOrder();
+        haveBatch = isSup || us.trainBatch >= 0;
+      }
       timer.resume();
       sampletimer.resume();
       int curB = batch, curT = T, curL = Lmax;   // this batch's shape (list data: per batch)
       fl::Variable input;
-      af::array inputSizes;
-      if (haveLists) {
+      af::array inputSizes, cleanFeats;   // cleanFeats: the features before SpecAugment (what the teacher labels)
+      std::vector<const ListSample*> unsupSamples;
+      if (haveLists && !isSup) {
+        if (haveBatch) {
+          std::vector<float> sizes;
+          curB = unsupData.get(us.trainBatch, -1, cleanFeats, ht, curL, sizes, curT);
+          unsupSamples = unsupData.samplesOf(us.trainBatch);
+          input = fl::input(cleanFeats);
+          inputSizes = af::array(af::dim4(1, (af::dim_t)sizes.size()), sizes.data());
+          std::cout << "Unsup batch " << curBatch << " | " << us.position << " | " << curT << " " << nFeat << " 1 " << curB;
+          if (iplOpt.type == IplType::FixedPreCache) std::cout << " update cache " << (us.relabel ? 1 : 0);
+          std::cout << std::endl;
+        } else {
+          curB = 0;
+          std::cout << "Skip usage of unsup batch as fixed cache is not ready " << curBatch << std::endl;
+        }
+      } else if (haveLists) {
         af::array feats;
         std::vector<float> sizes;
-        curB = data.get(data.batchOfUpdate(curBatch), data.batchOfUpdate(curBatch + 1), feats, ht, curL, sizes, curT);
+        curB = data.get(data.batchOfUpdate(supDone + 1), data.batchOfUpdate(supDone + 2), feats, ht, curL, sizes, curT);
+        if (ipl) std::cout << "Sup batch " << curBatch << " | " << supDone % batchesPerEpoch << " | " << curT << " " << nFeat << " 1 " << curB << std::endl;
         for (int b = 0; b < curB; ++b) {
           long len = 0;
           while (len < curL && ht[(size_t)b * curL + len] >= 0) ++len;
@@ -625,112 +828,198 @@ int main(int argc, char** argv) {
       input = fl::input(af::array(af::dim4(T, nFeat, 1, batch), hx.data()));
       inputSizes = af::constant(T, af::dim4(1, batch));
       }
-      if (saug && curBatch >= saugStart) input = saug->forward({input}).front();   // Train.cpp:1453-1461
-      fl::Variable target(af::array(af::dim4(curL, curB), ht.data()), false);
+      if (saug && curBatch >= saugStart && haveBatch) input = (isSup ? saugSup : saug)->forward({input}).front();   // Train.cpp:1453-1461
       af::sync();
       sampletimer.stopAndIncUnit();
 
       // forward
       fwdtimer.resume();
-      auto output = network->forward({input, fl::noGrad(inputSizes)}).front();
-      af::sync();
-      critfwdtimer.resume();
-      auto loss = criterion->forward({output, target}).front();
-      af::sync();
-      fwdtimer.stopAndIncUnit();
-      critfwdtimer.stopAndIncUnit();
-      std::vector<float> hl((size_t)curB);
-      loss.host(hl.data());
-      for (float v : hl) {
-        if (!std::isfinite(v)) {   // LOG(FATAL), Train.cpp:1686-1698
-          std::ostringstream m;
-          m << "Loss has NaN values (update " << curBatch << ", per-utterance losses:";
-          for (float q : hl) m << " " << q;
-          std::vector<float> he((size_t)output.elements());
-          output.array().host(he.data());
-          float mx = 0.f;
-          size_t bad = 0;
-          for (float q : he) { if (std::isfinite(q)) mx = std::max(mx, std::fabs(q)); else ++bad; }
-          m << "; emissions: max |x| " << mx << ", " << bad << " non-finite of " << he.size() << ")";
-          throw std::runtime_error(m.str());
-        }
-        lossSum += v;
-        ++lossN;
-      }
-      if (reportiters > 0 && curBatch % reportiters == 0) {  // token error of the Viterbi path (evalOutput, Train.cpp:1699-1716)
-        std::vector<int> path((size_t)curB * output.dims(1));
-        criterion->viterbiPath(output.array()).host(path.data());
-        const int To = (int)output.dims(1);
-        for (int b = 0; b < curB; ++b) {
-          std::vector<int> hyp, ref;
-          int prev = -1;
-          for (int t = 0; t < To; ++t) {
-            const int y = path[(size_t)b * To + t];
-            if (y != prev && !(criterionName == "ctc" && y == numClasses - 1)) hyp.push_back(y);
-            prev = y;
+      fl::Variable output, critInput, target;
+      if (haveBatch) output = network->forward({input, fl::noGrad(inputSizes)}).front();
+      std::vector<std::string> unsupIds, plToSave;   // pre-cache: labels taken before the update, stored after it (Train.cpp:1786-1788)
+      bool savePl = false;
+      if (isSup) {
+        critInput = output;
+        target = fl::Variable(af::array(af::dim4(curL, curB), ht.data()), false);
+      } else {   // Train.cpp:1478-1649: which samples have a label, and what the teacher labels before the update
+        std::vector<int> rows;
+        std::vector<std::string> texts;
+        for (auto* q : unsupSamples) unsupIds.push_back(q->id);
+        if (iplOpt.type == IplType::Naive) {
+          texts = predictPL(cleanFeats, inputSizes, unsupSamples, curBatch);
+          for (int b = 0; b < curB; ++b) rows.push_back(b);
+        } else {
+          if (haveBatch) {
+            auto l = ipl->labelled(unsupIds);
+            for (auto& id : l.reused) std::cout << "Reuse extra loaded cache for sample " << id << " for batch " << curBatch << std::endl;
+            rows = l.rows;
+            texts = l.texts;
+            if (ipl->labelBeforeUpdate(rows.size())) {
+              plToSave = predictPL(cleanFeats, inputSizes, unsupSamples, curBatch);
+              savePl = true;
+            }
           }
-          for (int i = 0; i < curL && ht[(size_t)b * curL + i] >= 0; ++i) ref.push_back(ht[(size_t)b * curL + i]);
-          editErr += editDistance(hyp, ref);
-          editLen += (long)ref.size();
-          if (haveLists) {   // words: path -> letters (replabels undone, blank dropped) -> split at the word separator (Train.cpp:829-872)
-            std::vector<int> pv(path.begin() + (size_t)b * To, path.begin() + (size_t)(b + 1) * To);
-            const bool wp = flags.getb("usewordpiece", false);
-            auto hw = tkn2Wrd(tknPrediction2Ltr(pv, data.dict, criterionName, flags.get("surround", ""), data.replabel, wp, data.wordsep), data.wordsep);
-            auto rw = tkn2Wrd(tknTarget2Ltr(ref, data.dict, criterionName, flags.get("surround", ""), data.replabel, wp, data.wordsep), data.wordsep);
-            wordMeter.add(hw, rw);
+          if (us.labelNext >= 0) {   // fixed-pre-cache: the next batch of the walk goes into the cache
+            af::array nf;
+            std::vector<float> ns;
+            std::vector<int> nt;
+            int nL = 1, nT = 0;
+            unsupData.get(us.labelNext, -1, nf, nt, nL, ns, nT);
+            const auto smp = unsupData.samplesOf(us.labelNext);
+            std::vector<std::string> ids;
+            for (auto* q : smp) ids.push_back(q->id);
+            ipl->store(ids, predictPL(nf, af::array(af::dim4(1, (af::dim_t)ns.size()), ns.data()), smp, curBatch));
           }
         }
+        if (!rows.empty()) {
+          // text -> target through the transform of the list reader's transcript column (an empty text: an empty target)
+          std::vector<std::vector<int>> tr;
+          curL = 1;
+          for (auto& text : texts) {
+            std::vector<std::string> words;
+            std::istringstream ws(text);
+            for (std::string w; ws >> w;) words.push_back(w);
+            tr.push_back(targetIndices(words, unsupData.lexicon, unsupData.dict, criterionName, unsupData.replabel, unsupData.wordsep));
+            curL = std::max<int>(curL, (int)tr.back().size());
+            tszTotal += (long)tr.back().size();
+            tszMax = std::max<long>(tszMax, (long)tr.back().size());
+          }
+          ht.assign(rows.size() * (size_t)curL, -1);
+          for (size_t r = 0; r < tr.size(); ++r) std::copy(tr[r].begin(), tr[r].end(), ht.begin() + r * (size_t)curL);
+          curB = (int)rows.size();   // totalBatchSize counts the samples that have a label
+          critInput = fl::ext::selectBatch(output, rows);
+          target = fl::Variable(af::array(af::dim4(curL, curB), ht.data()), false);
+        } else {
+          curB = 0;
+          std::cout << "Skip unsupervised part of data as PL are not available yet" << std::endl;
+        }
       }
-
-      // backward
-      bwdtimer.resume();
-      netoptim->zeroGrad();
-      critoptim->zeroGrad();
-      loss.backward();
-      if (reducer) {   // Train.cpp:1721-1735
-        for (auto& p : network->params()) {
-          if (!p.isGradAvailable()) p.addGrad(fl::Variable(af::constant(0.0, p.dims(), p.type()), false));
-          reducer->add(p.grad());
-        }
-        for (auto& p : criterion->params()) {
-          if (!p.isGradAvailable()) p.addGrad(fl::Variable(af::constant(0.0, p.dims(), p.type()), false));
-          reducer->add(p.grad());
-        }
-        reducer->finalize();
+      // Train.cpp:1651-1660: the update happens only if EVERY rank has something to train on
+      bool doUpdate = !critInput.isempty();
+      if (ipl && fl::getWorldSize() > 1) {
+        const float mine = doUpdate ? 1.f : 0.f;
+        af::array du(af::dim4(1), &mine);
+        fl::allReduce(du);
+        doUpdate = du.scalar<float>() >= (float)fl::getWorldSize();
       }
       af::sync();
-      bwdtimer.stopAndIncUnit();
+      if (!doUpdate) {
+        fwdtimer.stop();
+      } else {
+        critfwdtimer.resume();
+        auto loss = criterion->forward({critInput, target}).front();
+        af::sync();
+        fwdtimer.stopAndIncUnit();
+        critfwdtimer.stopAndIncUnit();
+        std::vector<float> hl((size_t)curB);
+        loss.host(hl.data());
+        for (float v : hl) {
+          if (!std::isfinite(v)) {   // LOG(FATAL), Train.cpp:1686-1698
+            std::ostringstream m;
+            m << "Loss has NaN values (update " << curBatch << ", per-utterance losses:";
+            for (float q : hl) m << " " << q;
+            std::vector<float> he((size_t)critInput.elements());
+            critInput.array().host(he.data());
+            float mx = 0.f;
+            size_t bad = 0;
+            for (float q : he) { if (std::isfinite(q)) mx = std::max(mx, std::fabs(q)); else ++bad; }
+            m << "; emissions: max |x| " << mx << ", " << bad << " non-finite of " << he.size() << ")";
+            throw std::runtime_error(m.str());
+          }
+          if (isSup) { lossSum += v; ++lossN; }
+          else { lossUnsupSum += v; ++lossUnsupN; }
+        }
+        if (reportiters > 0 && curBatch % reportiters == 0) {  // token error of the Viterbi path (evalOutput, Train.cpp:1699-1716)
+          std::vector<int> path((size_t)curB * critInput.dims(1));
+          criterion->viterbiPath(critInput.array()).host(path.data());
+          const int To = (int)critInput.dims(1);
+          for (int b = 0; b < curB; ++b) {
+            std::vector<int> hyp, ref;
+            int prev = -1;
+            for (int t = 0; t < To; ++t) {
+              const int y = path[(size_t)b * To + t];
+              if (y != prev && !(criterionName == "ctc" && y == numClasses - 1)) hyp.push_back(y);
+              prev = y;
+            }
+            for (int i = 0; i < curL && ht[(size_t)b * curL + i] >= 0; ++i) ref.push_back(ht[(size_t)b * curL + i]);
+            if (isSup) {
+              editErr += editDistance(hyp, ref);
+              editLen += (long)ref.size();
+            } else {
+              tknUnsupMeter.add(hyp, ref);
+            }
+            if (haveLists) {   // words: path -> letters (replabels undone, blank dropped) -> split at the word separator (Train.cpp:829-872)
+              std::vector<int> pv(path.begin() + (size_t)b * To, path.begin() + (size_t)(b + 1) * To);
+              const bool wp = flags.getb("usewordpiece", false);
+              auto hw = tkn2Wrd(tknPrediction2Ltr(pv, data.dict, criterionName, flags.get("surround", ""), data.replabel, wp, data.wordsep), data.wordsep);
+              auto rw = tkn2Wrd(tknTarget2Ltr(ref, data.dict, criterionName, flags.get("surround", ""), data.replabel, wp, data.wordsep), data.wordsep);
+              (isSup ? wordMeter : wordUnsupMeter).add(hw, rw);
+            }
+          }
+        }
 
-      // optimizer: scale down gradients by batchsize, clamp, update
-      optimtimer.resume();
-      af::array totalBatchSizeArr = af::constant((double)loss.dims(0), af::dim4(1), af::f32);   // Train.cpp:1743-1747
-      if (reducer) fl::allReduce(totalBatchSizeArr);
-      const double totalBatchSize = (double)totalBatchSizeArr.scalar<float>();
-      // (Train.cpp:1748-1760: `p.grad() = p.grad() / totalBatchSize` per parameter -- here in place, the planned network's
-      // gradient arena in one launch)
-      fl::scaleGradients(network->params(), 1.0 / totalBatchSize);
-      fl::scaleGradients(criterion->params(), 1.0 / totalBatchSize);
-      if (maxgradnorm > 0) {
-        auto params = network->params();
-        if (clampCrit) {
-          auto cp = criterion->params();
-          params.insert(params.end(), cp.begin(), cp.end());
+        // backward
+        bwdtimer.resume();
+        netoptim->zeroGrad();
+        critoptim->zeroGrad();
+        loss.backward();
+        if (reducer) {   // Train.cpp:1721-1735
+          for (auto& p : network->params()) {
+            if (!p.isGradAvailable()) p.addGrad(fl::Variable(af::constant(0.0, p.dims(), p.type()), false));
+            reducer->add(p.grad());
+          }
+          for (auto& p : criterion->params()) {
+            if (!p.isGradAvailable()) p.addGrad(fl::Variable(af::constant(0.0, p.dims(), p.type()), false));
+            reducer->add(p.grad());
+          }
+          reducer->finalize();
         }
-        const bool dbg = flags.getb("w2l_debug_gradnorm", false);
-        double gEm = 0, gCrit = 0, gNet = 0;
-        if (dbg) {   // (norms after the division by the batch size; 1e30 never clips)
-          if (output.isGradAvailable()) gEm = fl::clipGradNorm({output}, 1e30);
-          gCrit = fl::clipGradNorm(criterion->params(), 1e30);
-          gNet = fl::clipGradNorm(network->params(), 1e30);
+        af::sync();
+        bwdtimer.stopAndIncUnit();
+
+        // optimizer: scale down gradients by batchsize, clamp, update
+        optimtimer.resume();
+        af::array totalBatchSizeArr = af::constant((double)loss.dims(0), af::dim4(1), af::f32);   // Train.cpp:1743-1747
+        if (reducer) fl::allReduce(totalBatchSizeArr);
+        const double totalBatchSize = (double)totalBatchSizeArr.scalar<float>();
+        // (Train.cpp:1748-1760: `p.grad() = p.grad() / totalBatchSize` per parameter -- here in place, the planned network's
+        // gradient arena in one launch)
+        fl::scaleGradients(network->params(), 1.0 / totalBatchSize);
+        fl::scaleGradients(criterion->params(), 1.0 / totalBatchSize);
+        if (maxgradnorm > 0) {
+          auto params = network->params();
+          if (clampCrit) {
+            auto cp = criterion->params();
+            params.insert(params.end(), cp.begin(), cp.end());
+          }
+          const bool dbg = flags.getb("w2l_debug_gradnorm", false);
+          double gEm = 0, gCrit = 0, gNet = 0;
+          if (dbg) {   // (norms after the division by the batch size; 1e30 never clips)
+            if (critInput.isGradAvailable()) gEm = fl::clipGradNorm({critInput}, 1e30);
+            gCrit = fl::clipGradNorm(criterion->params(), 1e30);
+            gNet = fl::clipGradNorm(network->params(), 1e30);
+          }
+          const double gnorm = fl::clipGradNorm(params, maxgradnorm);
+          if (dbg) std::cout << "[debug] update " << curBatch << " gradient norm " << gnorm << " (network " << gNet << ", criterion " << gCrit
+                             << ", emissions (unscaled) " << gEm << ")" << std::endl;
         }
-        const double gnorm = fl::clipGradNorm(params, maxgradnorm);
-        if (dbg) std::cout << "[debug] update " << curBatch << " gradient norm " << gnorm << " (network " << gNet << ", criterion " << gCrit
-                           << ", emissions (unscaled) " << gEm << ")" << std::endl;
+        critoptim->step();
+        netoptim->step();
+        af::sync();
+        optimtimer.stopAndIncUnit();
       }
-      critoptim->step();
-      netoptim->step();
-      af::sync();
-      optimtimer.stopAndIncUnit();
+      if (savePl) ipl->store(unsupIds, plToSave);
+      if (!doUpdate) std::cout << "Skip update step as unsup data has no label " << curBatch << std::endl;
+      if (useEma) {   // Train.cpp:1823-1832: after EVERY update, skipped or not -- one launch over the parameter arena
+        optimtimer.resume();
+        fl::ext::emaUpdate(networkEMA, network, emaDecay);
+        af::sync();
+        optimtimer.stop();
+      }
+      if (!isSup && haveBatch && ipl->labelAfterUpdate()) ipl->store(unsupIds, predictPL(cleanFeats, inputSizes, unsupSamples, curBatch));   // Train.cpp:1833-1840
+      if (isSup) ++supDone;
+      const bool epochEnd = isSup && supDone % batchesPerEpoch == 0;   // a pass over the supervised lists is complete
+      if (epochEnd) iplNeedEpoch = true;
       timer.stopAndIncUnit();
       nsamples += curB;
       framesTotal += (long)curB * curT;
@@ -747,8 +1036,10 @@ int main(int argc, char** argv) {
         runtime.total = 0;
         lossSum = 0; lossN = 0; editErr = 0; editLen = 0; tszTotal = 0; tszMax = 0; nsamples = 0; nbatches = 0; framesTotal = 0;
         wordMeter = fl::EditDistanceMeter();
+        lossUnsupSum = 0; lossUnsupN = 0;
+        tknUnsupMeter = fl::EditDistanceMeter(); wordUnsupMeter = fl::EditDistanceMeter();
       }
-      if (curBatch % batchesPerEpoch == 0 || curBatch == iters) saveModels(curEpoch, curBatch);
+      if (epochEnd || curBatch == iters) saveModels(curEpoch, curBatch);
     }
     if (auto* cr = dynamic_cast<fl::CoalescingReducer*>(reducer.get()))
       std::cout << "[Distributed] gradient collectives of the last update: " << cr->lastCollectives() << " (" << cr->lastOverlapped()

@@ -433,6 +433,13 @@ W2L_API int w2l_trainer_bind_state2(void* h, float* state2) {
 }
 W2L_API int w2l_trainer_set_mixed_precision(void* h, int on) { ((Trainer*)h)->mixedPrecision = on != 0; return W2L_OK; }
 
+// slimIPL's dynamic dropout: the `TR` layers' probabilities from the next forward on (negative: the arch line's)
+W2L_API int w2l_trainer_set_dropout(void* h, double pDropout, double pLayerDrop) {
+  if (!h || !(pDropout < 1.0) || !(pLayerDrop < 1.0)) return W2L_EINVAL;   // (NaN fails the comparison)
+  ((Trainer*)h)->net->setTransformerDropout(pDropout, pLayerDrop);
+  return W2L_OK;
+}
+
 W2L_API int w2l_trainer_set_step(void* h, uint32_t step) { ((Trainer*)h)->step = step; return W2L_OK; }
 
 // arch / flags parsing without building kernels (recipes must load unchanged)

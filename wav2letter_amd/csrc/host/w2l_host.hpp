@@ -115,6 +115,8 @@ class Layer {
   // true when forward() hands its input through UNCHANGED (same pointer, same values) under this context: only then may
   // a note about the bf16 images of the input (Ctx::imgOf) go on describing the output
   virtual bool passesInputThrough(const Ctx& c) const { (void)c; return false; }
+  // slimIPL's dynamic dropout: only the Transformer block answers (negative: back to the arch line's value)
+  virtual void setTransformerDropout(double pDropout, double pLayerDrop) { (void)pDropout; (void)pLayerDrop; }
   int rngStream = 0;  // distinct dropout stream per layer
 };
 
@@ -126,6 +128,8 @@ class Sequential {
   std::string prettyString() const;
 
   void finalize();  // registers params, assigns offsets and rng streams
+  // the probabilities every `TR` layer uses from the next forward on (negative: the arch line's); no new plan is needed
+  void setTransformerDropout(double pDropout, double pLayerDrop) { for (auto& l : layers_) l->setTransformerDropout(pDropout, pLayerDrop); }
   const std::vector<ParamInfo>& params() const { return params_; }
   size_t paramFloats() const { return paramFloats_; }
 

@@ -195,6 +195,16 @@ def sgd_step_(p, g, v, lr, momentum, grad_scale=1.0, max_grad_norm=0.0):
     check(L.w2l_sgd_step(_p(p), _p(g), _p(v), p.numel(), lr, momentum, grad_scale, max_grad_norm, _p(ss), _s()), "sgd")
 
 
+def ema_update(ema, p, decay):
+    """w2l_ema_update, in place: ema = decay * ema + (1 - decay) * p over two flat float32 CUDA tensors of one size (any float
+    alignment; views into a parameter arena are fine).  slimIPL's averaged teacher network, one launch."""
+    if not (torch.is_tensor(ema) and torch.is_tensor(p) and ema.is_cuda and p.is_cuda and ema.dtype == torch.float32
+            and p.dtype == torch.float32 and ema.is_contiguous() and p.is_contiguous() and ema.numel() == p.numel()):
+        raise _lib.W2LInvalidArgument("ema_update: two contiguous float32 CUDA tensors of the same size")
+    check(_lib.lib().w2l_ema_update(_p(ema), _p(p), ema.numel(), float(decay), _s()), "ema_update")
+    return ema
+
+
 def bf16_convert(x, rows_image=True, transposed_image=False):
     """w2l_bf16_convert: x [rows][cols] fp32 -> (rowMajor [rows][colsP], transposed [cols][rowsP]) bf16 images, zero-padded to
     the next multiple of 64 (None for an image that was not asked for).  The images are torch.bfloat16 tensors."""

@@ -47,6 +47,7 @@ def _lib_tr():
         L.w2l_trainer_set_step.argtypes = [vp, u32]
         L.w2l_trainer_set_mixed_precision.argtypes = [vp, i]
         L.w2l_trainer_set_optimizer.argtypes = [vp, i, i]
+        L.w2l_trainer_set_dropout.argtypes = [vp, d, d]
         L.w2l_trainer_bind_state2.argtypes = [vp, vp]
         L.w2l_trainer_set_input_sizes.argtypes = [vp, vp]
         L.w2l_trainer_set_linseg.argtypes = [vp, u32]
@@ -257,6 +258,11 @@ class Trainer:
         tb = float(total_batch if total_batch is not None else self.B)
         _check(self.L.w2l_trainer_update(self.h, lr, lrcrit, momentum, max_grad_norm, tb, int(clamp_crit),
                                          self._stream()), "update")
+
+    def set_dropout(self, p_dropout, p_layer_drop):
+        """slimIPL's dynamic dropout (w2l_trainer_set_dropout): the probabilities the `TR` layers use from the next forward on;
+        a negative value restores the arch line's.  No new plan."""
+        _check(self.L.w2l_trainer_set_dropout(self.h, float(p_dropout), float(p_layer_drop)), "set_dropout")
 
     def evaluate(self, x, target, input_sizes=None):
         """Scores a held-out batch: eval-mode forward (no dropout) and the criterion's loss and Viterbi path in one call
