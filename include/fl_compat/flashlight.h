@@ -535,6 +535,8 @@ class FL_COMPAT_API ASGLoss : public SequenceCriterion {
   CriterionScaleMode scaleMode_;
 };
 
+class NGramLM;   // fl_compat/lm.h
+
 class FL_COMPAT_API CTCLoss : public SequenceCriterion {
  public:
   explicit CTCLoss(CriterionScaleMode scalemode = CriterionScaleMode::NONE);
@@ -559,11 +561,18 @@ class FL_COMPAT_API CTCLoss : public SequenceCriterion {
     int normalize = -1;                 // 1: search on log-softmax rows, 0: on the raw emissions, -1: as logAdd
     int nbest = 1;                      // M, 1..W
     int maxLen = 0;                     // Lmax, 0 = T (no hypothesis is longer)
+    // the search fused with a token-level n-gram LM (w2l_ctc_beam_search_lm); the defaults mean "no LM", and without lm the
+    // other three must keep them.  lm: a table over the N-1 token classes (fl_compat/lm.h), alive during the call.
+    const NGramLM* lm = nullptr;
+    float lmWeight = 0.f;               // every extension by token c adds lmWeight * log p_LM(c | prefix) + classScore[c]
+    af::array classScore;               // (N-1) f32 on the device, or empty
+    float eosScore = 0.f;               // the end adds lmWeight * log p_LM(EOS | hypothesis) + eosScore; 0 for a model without EOS
   };
   struct BeamSearchResult {
     af::array labels;    // (Lmax, M, B) s32: the first min(length, Lmax) labels, -1 beyond
     af::array lengths;   // (M, B) s32: the true label count; -1 for a rank that does not exist
     af::array scores;    // (M, B) f32; -inf for a rank that does not exist
+    af::array lmScores;  // (M, B) f32 with an LM: the hypotheses' unweighted LM scores (-inf for a rank that does not exist); else empty
   };
   BeamSearchResult beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& options);
   std::string prettyString() const override;

@@ -198,6 +198,70 @@ int w2l_ctc_beam_search(int B, int T, int N, const float* input /*[B][T][N]*/, c
                         int nbest /*M*/, int maxLen /*Lmax*/,
                         int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
                         void* workspace, w2l_stream_t stream);
+/* Back-off n-gram language model over the token dictionary, as a table.  Host only: none of w2l_ngram_lm_* touches the GPU.
+ * Refusals set a message for w2l_host_last_error().
+ *   Words.  0 .. numTokens-1 are the token classes (numTokens = N-1 for a search over N classes), numTokens is BOS, numTokens+1
+ *     is EOS.  <unk> is only a fallback log-probability, unkLogp.  Values are fp32 natural logs.
+ *   States.  State 0 is the empty context; every n-gram of order below the model order is a state with a back-off weight bo[s]
+ *     and a suffix state suf[s], the state of the longest proper suffix of its words that is a state (its context with the first
+ *     word dropped, in a model that lists every suffix).  The start state is the state of (BOS); 0 when the model has no BOS
+ *     unigram or is of order 1.
+ *   Edges.  (state, word) -> (log p, next): one per n-gram, from the state of its context.  next is the n-gram's own state, or,
+ *     for an n-gram of the model order, the state of its longest proper suffix that is a state.
+ *   Score rule, every add one fp32 add in this order:
+ *       q(s, w):  acc = 0
+ *                 loop: if edge (s, w) exists: return (acc + p, next)
+ *                       if s == 0:             return (acc + unkLogp, 0)
+ *                       acc = acc + bo[s];  s = suf[s]
+ *   Blob.  One position-independent block (offsets, no pointers; layout in csrc/ngram_lm.hpp): the same bytes are the table on the
+ *     host and, after one copy, on the device.  Edge lookup is an open-addressing hash at load factor <= 1/2.  The memory holding
+ *     a blob must be 16-byte aligned.
+ * w2l_ngram_lm_build: n-grams per order, concatenated: counts[order]; words: counts[0] 1-grams, then counts[1] 2-grams (2 ints
+ *   each), ...; logp and backoff one value per n-gram in the same sequence (backoff may be NULL: all 0; the top order's are
+ *   ignored).  Two calls: blob = NULL writes the size to *blobBytes; then *blobBytes is the room of blob and becomes the size.
+ *   W2L_EINVAL: an n-gram whose context is not itself an n-gram, a duplicate n-gram, a word id outside 0 .. numTokens+1, a
+ *   non-finite value, too little room.  W2L_EUNSUPPORTED: order above 8.
+ * w2l_ngram_lm_from_arpa: ARPA text -> blob (the same two calls); tokens[i] is the spelling of class i.  log10 values become
+ *   natural logs in double, rounded once to fp32.  <s>, </s> and <unk> are recognised (a token spelled like one of them wins);
+ *   the <unk> unigram sets unkLogp; an n-gram with any other word that is no token is skipped, *skipped (may be NULL) and the
+ *   message count them.  A class without unigram scores as <unk>; without <unk> too the load is refused and the message names the
+ *   first such token.  Refused as well: a \data\ count that disagrees with its section, a file that ends before \end\, a
+ *   KenLM binary (the message asks for the ARPA text), gzip.
+ * w2l_ngram_lm_start / w2l_ngram_lm_score: the start state and q on a host blob (state and word are checked).
+ * w2l_ngram_lm_info: any output may be NULL. */
+int w2l_ngram_lm_build(int order, const size_t* counts, const int* words, const float* logp, const float* backoff,
+                       int numTokens, float unkLogp, void* blob, size_t* blobBytes);
+int w2l_ngram_lm_from_arpa(const char* path, int numTokens, const char* const* tokens, void* blob, size_t* blobBytes,
+                           int* skipped);
+int w2l_ngram_lm_info(const void* blob, int* order, int* numTokens, int* numStates, int* hasBos, int* hasEos);
+int w2l_ngram_lm_start(const void* blob, int* state);
+int w2l_ngram_lm_score(const void* blob, int state, int word, float* logp, int* next);
+/* w2l_ctc_beam_search fused with an n-gram LM (lexicon-free: the LM's words are the token classes).  The contract is
+ * w2l_ctc_beam_search's -- frame tokens by the acoustic lp alone, stay / ext / merge / prune / order / output -- with these changes:
+ *   LM state.  Every entry carries the LM state of its prefix; the empty prefix has the start state.
+ *   Extension.  ext(r, k) with token c:  pnb' = (lp[c] + (c == e ? pb : tot)) + g,  g = (lmWeight * q(s_r, c)) + classScore[c]:
+ *     one fp32 multiply, one fp32 add (skipped when classScore is NULL), then the add to the acoustic sum.  The new entry's state
+ *     is q's next state.
+ *   Merge.  An extension merged into stay(j) contributes this pnb', g included: the entry it joins carries the same LM score, so
+ *     every alignment of a prefix carries the prefix's LM score once.
+ *   Prune and select act on totals that include g; the order is unchanged.
+ *   End.  lmHasEos != 0 (what w2l_ngram_lm_info says of the blob): every surviving entry's score becomes
+ *     tot + ((lmWeight * q(s, EOS)) + eosScore) and the entries are re-ranked by that score descending, then previous rank
+ *     ascending.  lmHasEos == 0: no end term, and eosScore must be 0.
+ *   lmScores[b][m]: the hypothesis's unweighted LM score: q added in label order from the start state in fp32 (0 + q1, + q2, ...),
+ *     then + q(s, EOS) when lmHasEos; -inf for empty rows.
+ * With logAdd = 0 the result is reproducible bit for bit as w2l_ctc_beam_search's is (same exception for the sign of a zero).
+ * Limits and refusals: w2l_ctc_beam_search's, and lm or lmScores NULL, lmWeight or eosScore not finite, eosScore != 0 without
+ * EOS (W2L_EINVAL), all before anything touches the device.  lm (a blob for N-1 tokens) and classScore [N-1] are device memory
+ * and NOT checked: the kernel bounds every probe loop by the table's capacity, every back-off walk by its order and every state
+ * by its state count, so a damaged table gives wrong scores, never a spin. */
+size_t w2l_ctc_beam_lm_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                           int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                           int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                           const float* classScore /*[N-1] or NULL*/, float eosScore,
+                           int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                           float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the

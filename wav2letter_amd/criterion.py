@@ -302,18 +302,32 @@ def ctc_align(emission, target, frames=None, with_score=True):
 
 
 def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=None,
-                    nbest=1, max_len=None):
+                    nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0):
     """CTC prefix beam search without lexicon or LM (w2l_ctc_beam_search; the contract is in include/w2l_hip.h): `emission`
     [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64), beam_token = K (clipped to N-1, then <= 64),
     log_add: sum (True) or max (False) over the alignments of a prefix; normalize: search on log-softmax rows (default: log_add --
     sums only mean something on log-probabilities; the max search runs on the raw emissions as the reference's decoder does).
     Returns (labels [B][nbest][max_len] int32, -1 beyond a hypothesis; lengths [B][nbest] int32, the true label counts, -1 for a
-    rank that does not exist; scores [B][nbest] float32, -inf there).  max_len defaults to T (no hypothesis is longer)."""
+    rank that does not exist; scores [B][nbest] float32, -inf there).  max_len defaults to T (no hypothesis is longer).
+    lm: an lm.NGramLM over the N-1 token classes: the search fused with it (w2l_ctc_beam_search_lm): every extension by token c
+    adds lm_weight * log p_LM(c | prefix) + class_score[c] (class_score: [N-1] float32 on the device, or None), the end adds
+    lm_weight * log p_LM(EOS | hypothesis) + eos_score when the model has EOS.  Returns a fourth tensor then: lm_scores [B][nbest],
+    the hypotheses' unweighted LM scores.  Without lm the other three arguments must keep their defaults."""
     _emission_checks(emission)
+    B, T, N = emission.shape
+    if lm is None:
+        if lm_weight != 0.0 or class_score is not None or eos_score != 0.0:
+            raise _lib.W2LInvalidArgument("ctc_beam_search: lm_weight, class_score and eos_score need lm")
+    else:
+        if lm.num_tokens != N - 1:
+            raise _lib.W2LInvalidArgument(f"ctc_beam_search: the LM has {lm.num_tokens} tokens, the emissions {N - 1}")
+        if not lm.has_eos and eos_score != 0.0:
+            raise _lib.W2LInvalidArgument("ctc_beam_search: eos_score needs a model with EOS")
+        if class_score is not None and (class_score.dtype != torch.float32 or class_score.numel() != N - 1):
+            raise _lib.W2LInvalidArgument("ctc_beam_search: class_score must be float32 with one entry per token class")
     _check_dev(emission)
     L = _lib.lib()
     emission = emission.detach().contiguous()
-    B, T, N = emission.shape
     if frames is not None:
         if frames.dtype != torch.int32 or frames.numel() != B:
             raise _lib.W2LInvalidArgument("ctc_beam_search: frames must be int32 with one entry per utterance")
@@ -323,11 +337,25 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
         normalize = bool(log_add)
     max_len = T if max_len is None else int(max_len)
     nbest = int(nbest)
-    ws = _ws(L.w2l_ctc_beam_workspace_size(B, T, N, int(beam), int(beam_token)), emission.device)
     shape = (B, max(nbest, 1))
     labels = torch.empty(*shape, max(max_len, 1), dtype=torch.int32, device=emission.device)
     lengths = torch.empty(*shape, dtype=torch.int32, device=emission.device)
     scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
+    if lm is not None:
+        if class_score is not None:
+            _check_dev(emission, class_score)
+            class_score = class_score.contiguous()
+        ws = _ws(L.w2l_ctc_beam_lm_workspace_size(B, T, N, int(beam), int(beam_token)), emission.device)
+        lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
+        blob = lm.device_blob(emission.device)
+        _lib.check(L.w2l_ctc_beam_search_lm(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
+                                            int(beam), int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)),
+                                            nbest, max_len, blob.data_ptr(), int(lm.has_eos), float(lm_weight),
+                                            class_score.data_ptr() if class_score is not None else None, float(eos_score),
+                                            labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), lm_scores.data_ptr(),
+                                            ws.data_ptr(), _stream()), "ctc_beam_search")
+        return labels, lengths, scores, lm_scores
+    ws = _ws(L.w2l_ctc_beam_workspace_size(B, T, N, int(beam), int(beam_token)), emission.device)
     _lib.check(L.w2l_ctc_beam_search(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None, int(beam),
                                      int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
                                      labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), ws.data_ptr(), _stream()),
@@ -490,7 +518,8 @@ class CTCLoss(SequenceCriterion):
         return ctc_align(emission, target, frames, with_score=False)[0]
 
     def beamSearch(self, emission, frames=None, **options):
-        """lexicon-free n-best beam search over the emissions (ctc_beam_search's options): (labels, lengths, scores)"""
+        """lexicon-free n-best beam search over the emissions (ctc_beam_search's options, lm= included): (labels, lengths, scores),
+        and lm_scores with an LM"""
         return ctc_beam_search(emission, frames, **options)
 
     def score(self, emission, target):

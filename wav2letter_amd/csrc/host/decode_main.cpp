@@ -1,7 +1,8 @@
 // decode_main.cpp -- `Decode --am=<NNN_model_*.bin> --test=<list> [--datadir=] [--batchsize=] [--sclite=<dir>] [--beamsize=]
 // [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--k=v ...]`: the
-// reference's Decode tool for its lexicon-free token decoder without LM (`--uselexicon=false --decodertype=tkn`, the configuration
-// of recipes/self_training/librispeech/am/decode_*.cfg) over the fl:: surface.  Output formats: Decode.cpp:683-739, :840-846.
+// reference's Decode tool for its lexicon-free token decoder (`--uselexicon=false --decodertype=tkn`), without LM (the configuration
+// of recipes/self_training/librispeech/am/decode_*.cfg) or with a token-level n-gram LM (`--lm=<arpa>`, recipes/lexicon_free and the
+// word-piece runs of sota/2019), over the fl:: surface.  Output formats: Decode.cpp:683-739, :840-846.
 //
 // Flags come from the checkpoint's `gflags` entry, then from the command line (the last definition wins), as in Align.  The tool
 // builds the network and the CTC criterion, loads both from --am and runs the eval-mode network over the --test list in list order
@@ -16,10 +17,16 @@
 //   --sclite=<dir>: <dir>/<name>.hyp and .ref hold `words (sampleId)\n`, <name> = the list's base name; .log holds what --show
 //     prints and the final line.  --show: the |T|: / |P|: (/ |t|: / |p|: with --showletters) / [sample: ...] block per sample.
 //   --isbeamdump=true (needs --sclite): .hyp holds one line `sampleId | score | amScore | lmScore | wer | words` per hypothesis,
-//     --nbest of them per sample in rank order; lmScore is 0 and amScore equals score (no LM in this build).
+//     --nbest of them per sample in rank order; without --lm lmScore is 0 and amScore equals score.
+//   --lm=<arpa> [--lmtype=kenlm] [--lmweight=0] [--eosscore=0] [--wordscore=0]: the search fused with a back-off n-gram LM over the
+//     tokens (w2l_ctc_beam_search_lm).  --lmtype=kenlm (the reference's default) means "n-gram, ARPA text" here: the file is read
+//     by this library, KenLM binaries and gzip are refused; convlm is refused by name.  --wordscore is added to the classes that
+//     begin a word: the pieces that start with the word separator with --usewordpiece=true, else the separator class.  In the
+//     beam dump lmScore is the hypothesis's unweighted LM score and amScore = score - (lmweight * lmScore + its word scores +
+//     eosscore), computed on the host in double.
 //   The last line gives the total WER / TER (fl::EditDistanceMeter, the --valid evaluation's).
-// Refused, each with a message that names the flag: --lm, --uselexicon=true, --decodertype=wrd, a non-zero --silscore /
-// --wordscore, a --criterion other than ctc.  (--uselexicon and --decodertype default to false / tkn here: the only decoder built.)
+// Refused, each with a message that names the flag: an unreadable or malformed --lm, --lmtype other than kenlm, --uselexicon=true,
+// --decodertype=wrd, a non-zero --silscore, a non-zero --wordscore without --lm, a --criterion other than ctc.  (--uselexicon and --decodertype default to false / tkn here: the only decoder built.)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -27,6 +34,7 @@
 #include <iostream>
 #include <limits>
 
+#include "../../../include/fl_compat/lm.h"
 #include "list_data.hpp"
 
 using namespace fl;
@@ -38,7 +46,8 @@ int usage(const char* exe) {
   std::cerr << "Usage: \n " << exe
             << " --am=<model> --test=<list> [--datadir=...] [--batchsize=...] [--sclite=<dir>] [--beamsize=2500] [--beamsizetoken=250000]"
                " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [flags]\n"
-               " lexicon-free CTC token beam search without LM; beam and tokens per frame are limited to 64.\n"
+               " [--lm=<arpa> --lmtype=kenlm --lmweight=0 --eosscore=0 --wordscore=0]\n"
+               " lexicon-free CTC token beam search, optionally with a token-level n-gram LM (ARPA text); beam and tokens per frame are limited to 64.\n"
                " --logadd=false (default): max over a prefix's alignments on the raw emissions -- the 1-best equals the greedy transcript.\n"
                " --logadd=true: the labelling-probability search (sum over a prefix's alignments, on log-softmax rows)."
             << std::endl;
@@ -82,12 +91,20 @@ int main(int argc, char** argv) {
     const std::string criterionName = flags.get("criterion", "asg");
     if (criterionName != "ctc")
       throw std::invalid_argument("--criterion=" + criterionName + ": Decode searches the CTC lattice only (ASG's best path is Train's Viterbi)");
-    if (!flags.get("lm", "").empty()) throw std::invalid_argument("--lm: no language model in this build (leave it empty)");
+    const std::string lmPath = flags.get("lm", "");
+    if (!lmPath.empty()) {
+      const std::string lmType = flags.get("lmtype", "kenlm");
+      if (lmType == "convlm") throw std::invalid_argument("--lmtype=convlm: no ConvLM in this build (an n-gram model as ARPA text: --lmtype=kenlm)");
+      if (lmType != "kenlm") throw std::invalid_argument("--lmtype=" + lmType + ": only kenlm (an n-gram model as ARPA text) is built");
+    }
     if (flags.getb("uselexicon", false)) throw std::invalid_argument("--uselexicon=true: no lexicon decoder in this build (use --uselexicon=false)");
     if (flags.get("decodertype", "tkn") != "tkn")
       throw std::invalid_argument("--decodertype=" + flags.get("decodertype", "") + ": only the token decoder (--decodertype=tkn) is built");
     if (flags.getd("silscore", 0.0) != 0.0) throw std::invalid_argument("--silscore: no silence score without a lexicon (leave it 0)");
-    if (flags.getd("wordscore", 0.0) != 0.0) throw std::invalid_argument("--wordscore: no word score without a lexicon (leave it 0)");
+    const double wordScore = flags.getd("wordscore", 0.0), lmWeight = flags.getd("lmweight", 0.0), eosScore = flags.getd("eosscore", 0.0);
+    if (lmPath.empty() && wordScore != 0.0) throw std::invalid_argument("--wordscore: no word score without --lm (leave it 0)");
+    if (!std::isfinite(wordScore) || !std::isfinite(lmWeight) || !std::isfinite(eosScore))
+      throw std::invalid_argument("--wordscore, --lmweight and --eosscore must be finite");
 
     const int batch = (int)flags.geti("batchsize", 1);
     if (batch <= 0) throw std::invalid_argument("--batchsize must be positive");
@@ -141,6 +158,29 @@ int main(int argc, char** argv) {
     const std::string surround = flags.get("surround", "");
     const std::string dump = flags.get("w2l_dump_features", "");
 
+    // ---- the language model over the token classes, and the word score as class scores
+    std::unique_ptr<NGramLM> lm;
+    std::vector<float> classScore((size_t)numClasses - 1, 0.f);
+    af::array classScoreDev;
+    if (!lmPath.empty()) {
+      std::vector<std::string> tokens;
+      for (int c = 0; c < numClasses - 1; ++c) tokens.push_back(d.dict.getEntry(c));
+      try {
+        lm.reset(new NGramLM(NGramLM::fromArpa(lmPath, tokens)));
+      } catch (const std::exception& e) {
+        throw std::invalid_argument("--lm=" + lmPath + ": " + e.what());
+      }
+      if (!lm->hasEos() && eosScore != 0.0) throw std::invalid_argument("--eosscore: the model of --lm has no </s> (leave it 0)");
+      std::cerr << "[Decode] --lm: order " << lm->order() << ", " << lm->numStates() << " states; " << lm->message() << std::endl;
+      if (wordScore != 0.0) {
+        for (int c = 0; c < numClasses - 1; ++c) {
+          const bool begins = wp ? (!d.wordsep.empty() && tokens[(size_t)c].rfind(d.wordsep, 0) == 0) : tokens[(size_t)c] == d.wordsep;
+          if (begins) classScore[(size_t)c] = (float)wordScore;
+        }
+        classScoreDev = af::array(af::dim4((af::dim_t)classScore.size()), classScore.data());
+      }
+    }
+
     std::ofstream hypFile, refFile, logFile;
     if (!sclite.empty()) {
       const std::string stem = pathJoin(sclite, baseName(listPaths.front()));
@@ -184,12 +224,20 @@ int main(int argc, char** argv) {
       opt.logAdd = logAdd;
       opt.normalize = logAdd ? 1 : 0;   // the reference's decoder consumes the raw emissions; sums need log-probabilities
       opt.nbest = M;
+      if (lm) {
+        opt.lm = lm.get();
+        opt.lmWeight = (float)lmWeight;
+        opt.classScore = classScoreDev;
+        opt.eosScore = (float)eosScore;
+      }
       auto res = ctc->beamSearch(out.array(), af::array(af::dim4(1, B), frames.data()), opt);
       std::vector<int> labels((size_t)B * M * Tout), lengths((size_t)B * M);
       std::vector<float> scores((size_t)B * M);
       res.labels.host(labels.data());
       res.lengths.host(lengths.data());
       res.scores.host(scores.data());
+      std::vector<float> lmScores((size_t)B * M, 0.f);
+      if (lm) res.lmScores.host(lmScores.data());
 
       for (int b = 0; b < B; ++b) {
         const auto& smp = d.samples[(size_t)d.mine[(size_t)(k * batch + b)]];
@@ -208,7 +256,14 @@ int main(int argc, char** argv) {
             fl::EditDistanceMeter one;
             one.add(wordPrediction, wordTarget);
             const double score = (double)scores[(size_t)b * M + m];
-            hypFile << smp.id << " | " << std::to_string(score) << " | " << std::to_string(score) << " | " << std::to_string(0.0) << " | "
+            double amScore = score, lmScore = 0.0;
+            if (lm) {
+              lmScore = (double)lmScores[(size_t)b * M + m];
+              double extra = (double)(float)lmWeight * lmScore + (lm->hasEos() ? (double)(float)eosScore : 0.0);
+              for (int i = 0; i < len; ++i) extra += (double)classScore[(size_t)row[i]];
+              amScore = score - extra;
+            }
+            hypFile << smp.id << " | " << std::to_string(score) << " | " << std::to_string(amScore) << " | " << std::to_string(lmScore) << " | "
                     << std::to_string(one.value()) << " | " << join(wordPrediction) << "\n";
             continue;
           }

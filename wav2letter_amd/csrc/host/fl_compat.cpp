@@ -15,6 +15,7 @@
 #include <unordered_set>
 
 #include "../../../include/fl_compat/flashlight.h"
+#include "../../../include/fl_compat/lm.h"
 #include "w2l_host.hpp"
 
 namespace {
@@ -1274,11 +1275,30 @@ CTCLoss::BeamSearchResult CTCLoss::beamSearch(const af::array& input, const af::
   r.labels = af::array(af::dim4(Lmax, o.nbest, B), af::s32);
   r.lengths = af::array(af::dim4(o.nbest, B), af::s32);
   r.scores = af::array(af::dim4(o.nbest, B));
+  const bool normalize = o.normalize < 0 ? o.logAdd : o.normalize != 0;
+  if (!o.lm) {
+    if (o.lmWeight != 0.f || !o.classScore.isempty() || o.eosScore != 0.f)
+      throw std::invalid_argument("beamSearch: lmWeight, classScore and eosScore need lm");
+  } else {   // the search fused with the n-gram LM (w2l_ctc_beam_search_lm)
+    if (o.lm->numTokens() != N - 1) throw std::invalid_argument("beamSearch: the LM's token count is not the emissions' N - 1");
+    if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != N - 1))
+      throw std::invalid_argument("beamSearch: classScore must be f32 with one entry per token class");
+    r.lmScores = af::array(af::dim4(o.nbest, B));
+    auto wsl = devAlloc(w2l_ctc_beam_lm_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    w2l::w2lCheck(w2l_ctc_beam_search_lm(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+                                         normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
+                                         o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
+                                         r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
+                                         r.lmScores.device<float>(), wsl.get(), S()),
+                  "ctc beam search with LM");
+    af::sync();  // wsl is released at return
+    return r;
+  }
   auto ws = devAlloc(st->impl->beamWorkspaceBytes(B, T, N, o.beamSize, o.beamSizeToken) + 256);
   w2l::Ctx c;
   c.stream = S();
   st->impl->beamSearch(c, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
-                       o.normalize < 0 ? o.logAdd : o.normalize != 0, o.nbest, Lmax, r.labels.device<int>(),
+                       normalize, o.nbest, Lmax, r.labels.device<int>(),
                        r.lengths.device<int>(), r.scores.device<float>(), ws.get());
   af::sync();  // ws is released at return
   return r;

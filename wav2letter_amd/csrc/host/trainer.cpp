@@ -76,6 +76,9 @@ using namespace w2l;
 static thread_local std::string g_err;
 
 W2L_API const char* w2l_host_last_error(void) { return g_err.c_str(); }
+namespace w2l {
+void setHostError(const std::string& m) { g_err = m; }   // for the host entry points of other files (ngram_lm.cpp)
+}
 
 // criterion: "ctc" | "asg" ; archText: contents of an .arch file (NFEAT/NLABEL substituted here)
 W2L_API void* w2l_trainer_create(const char* archText, int nFeat, int nLabel, const char* criterion,
