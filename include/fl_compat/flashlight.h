@@ -536,6 +536,7 @@ class FL_COMPAT_API ASGLoss : public SequenceCriterion {
 };
 
 class NGramLM;   // fl_compat/lm.h
+class Lexicon;   // fl_compat/lexicon.h
 
 class FL_COMPAT_API CTCLoss : public SequenceCriterion {
  public:
@@ -567,12 +568,20 @@ class FL_COMPAT_API CTCLoss : public SequenceCriterion {
     float lmWeight = 0.f;               // every extension by token c adds lmWeight * log p_LM(c | prefix) + classScore[c]
     af::array classScore;               // (N-1) f32 on the device, or empty
     float eosScore = 0.f;               // the end adds lmWeight * log p_LM(EOS | hypothesis) + eosScore; 0 for a model without EOS
+    // the search restricted to the spellings of a lexicon (w2l_ctc_beam_search_lex); lm is required then and is a table over the
+    // lexicon's WORDS (NGramLM::fromArpa(path, lexicon.words())), classScore must be empty.  lexicon: fl_compat/lexicon.h, alive
+    // during the call.  Without lexicon the other two must keep their defaults.
+    const Lexicon* lexicon = nullptr;
+    float wordScore = 0.f;              // every completed word adds lmWeight * log p_LM(word | words before) + wordScore
+    int maxWords = 0;                   // rows of `words`, 0 = Lmax
   };
   struct BeamSearchResult {
     af::array labels;    // (Lmax, M, B) s32: the first min(length, Lmax) labels, -1 beyond
     af::array lengths;   // (M, B) s32: the true label count; -1 for a rank that does not exist
     af::array scores;    // (M, B) f32; -inf for a rank that does not exist
     af::array lmScores;  // (M, B) f32 with an LM: the hypotheses' unweighted LM scores (-inf for a rank that does not exist); else empty
+    af::array words;       // (maxWords, M, B) s32 with a lexicon: the first min(count, maxWords) word ids, -1 beyond; else empty
+    af::array wordCounts;  // (M, B) s32 with a lexicon: the true word count; -1 for a rank that does not exist; else empty
   };
   BeamSearchResult beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& options);
   std::string prettyString() const override;

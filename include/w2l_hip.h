@@ -262,6 +262,69 @@ int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input /*[B][T][N]*/
                            const float* classScore /*[N-1] or NULL*/, float eosScore,
                            int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
                            float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream);
+/* The lexicon as a trie, one table.  Host only: none of w2l_lexicon_* touches the GPU.  Refusals set a message for
+ * w2l_host_last_error().
+ *   Nodes 0 .. numNodes-1, the root is 0, numbered in the order the spelling rows first reach them.  An edge (node, token) -> child
+ *     is found through an open-addressing hash at load factor <= 1/2; every probe loop is bounded by the capacity.  A node stores
+ *     smear (fp32), hasChildren, nw in 0..6 and up to 6 word ids: the first 6 words whose spelling ends at it, in row order.
+ *   Blob.  One position-independent block (offsets, no pointers; layout in csrc/lexicon.hpp): the same bytes are the table on the
+ *     host and, after one copy, on the device.  The memory holding a blob must be 16-byte aligned.
+ * w2l_lexicon_build: numSpellings rows; row i spells word spellWord[i] with the tokens spellTokens[spellOff[i] .. spellOff[i+1]).
+ *   Homophones (several words on one spelling) and several spellings of one word are rows like any other.  Words beyond the 6th of
+ *   a node are dropped and counted in *dropped (may be NULL).  smear[v] is the exact max of wordSmear[w] over the words kept at v or
+ *   below; wordSmear == NULL: all 0, no smearing.  silToken (-1: none) is the token the search lets loop at the root.  The two calls
+ *   of w2l_ngram_lm_build: blob = NULL writes the size to *blobBytes; then *blobBytes is the room of blob and becomes the size.
+ *   W2L_EINVAL: an empty spelling, a token outside 0 .. numTokens-1 (so blank cannot be spelled), a word id outside
+ *   0 .. numWords-1, a duplicate (word, spelling) row, a spelling that begins with silToken, a non-finite smear value, too little
+ *   room.  W2L_EUNSUPPORTED: 2^28 nodes or more.
+ * w2l_lexicon_info (any output may be NULL), w2l_lexicon_child (*child = -1 when the edge is absent) and w2l_lexicon_node
+ *   (words[6], -1 beyond nw; any output may be NULL) walk a host blob; node and token are checked. */
+int w2l_lexicon_build(int numTokens, int numWords, size_t numSpellings, const int* spellWord, const size_t* spellOff,
+                      const int* spellTokens, const float* wordSmear /*[numWords] or NULL*/, int silToken, void* blob,
+                      size_t* blobBytes, size_t* dropped);
+int w2l_lexicon_info(const void* blob, int* numTokens, int* numWords, int* numNodes, int* silToken, int* smeared);
+int w2l_lexicon_child(const void* blob, int node, int token, int* child);
+int w2l_lexicon_node(const void* blob, int node, float* smear, int* nw, int* words /*[6]*/, int* hasChildren);
+/* w2l_ctc_beam_search restricted to the spellings of a lexicon, scored by an n-gram LM over WORDS (lm: a w2l_ngram_lm_* blob whose
+ * "tokens" are the lexicon's numWords words) whose score is smeared down the trie (max smearing).  Like its siblings it is a PREFIX
+ * search with pb / pnb: one hypothesis has one entry.  The contract is w2l_ctc_beam_search's -- frame tokens by the acoustic lp alone,
+ * stay, (+), threshold, W, M, the output rows -- with these changes:
+ *   State.  An entry is a hypothesis: a sequence of extensions.  Besides e, pb, pnb it carries its lexicon node u (the root at the
+ *     start, after a completed word and after silence at the root), its LM state s, its word list and the unweighted LM sum acc;
+ *     all four are functions of the hypothesis.
+ *   Extensions of entry r by frame token k of class c, base = (c == e ? pb : tot):
+ *     sil, slot 0: c == silToken and u is the root: pnb' = lp[c] + base; the new entry is at the root with state s; no word, no LM
+ *       term.
+ *     Otherwise v = child(u, c); without such a child (r, k) has no candidates.  a = (lp[c] + base) + (lmWeight * (smear[v] - su)),
+ *       su = 0 at the root and smear[u] elsewhere: one fp32 subtract, one multiply, one add, in this order.
+ *       in, slot 0: v has children: pnb' = a; the new entry is at v with state s.
+ *       word i, slot 1+i, i < nw(v), w = words(v)[i]: pnb' = a + ((lmWeight * (q(s, w) - smear[v])) + wordScore); the new entry is
+ *         at the root, its state is q's successor, w is appended, acc' = acc + q.
+ *     Every extension has pb' = -inf.  In exact arithmetic the smear terms cancel when a word completes; in fp32 they leave their
+ *     roundings: the contract is the operation sequence above.
+ *   Merge.  A candidate is (+)-ed into stay(j).pnb' and disappears when j's parent hypothesis is entry r's hypothesis and j's last
+ *     extension is the same one: the same token, the same resulting lexicon node and the same word or none.  Two hypotheses that
+ *     spell the same tokens with different words, or with a different word boundary, are different entries.
+ *   Order.  Total descending, r ascending, stay before extension, k ascending, slot ascending.
+ *   End.  Entries whose node is not the root are dropped: only finished words count.  Then w2l_ctc_beam_search_lm's EOS term when
+ *     lmHasEos (EOS is word numWords + 1 of the LM), the re-ranking by score descending, then previous rank ascending.  labels and
+ *     lengths as before, silence tokens included; words[b][m] the first min(count, maxWords) word ids and -1 beyond;
+ *     wordCounts[b][m] the true count, -1 for empty rows; lmScores as in the LM search.  When no entry is at the root, all M rows
+ *     of the utterance are empty.
+ * Not part of the contract: an unknown-word arc, a silence score, log-add smearing.
+ * With logAdd = 0 the result is reproducible bit for bit (same exception for the sign of a zero).
+ * Limits and refusals: w2l_ctc_beam_search_lm's, and lexicon, words or wordCounts NULL, maxWords < 1, wordScore not finite
+ * (W2L_EINVAL), all before anything touches the device.  lexicon and lm are device memory and NOT checked: the kernel bounds every
+ * probe loop by the capacity, every back-off walk by the order and every node and state by its count, so a damaged table gives wrong
+ * scores, never a spin. */
+size_t w2l_ctc_beam_lex_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                            int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                            int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                            const void* lexicon, float wordScore, float eosScore,
+                            int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                            float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/, int* wordCounts /*[B][M]*/,
+                            void* workspace, w2l_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the

@@ -302,7 +302,8 @@ def ctc_align(emission, target, frames=None, with_score=True):
 
 
 def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=None,
-                    nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0):
+                    nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
+                    max_words=None):
     """CTC prefix beam search without lexicon or LM (w2l_ctc_beam_search; the contract is in include/w2l_hip.h): `emission`
     [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64), beam_token = K (clipped to N-1, then <= 64),
     log_add: sum (True) or max (False) over the alignments of a prefix; normalize: search on log-softmax rows (default: log_add --
@@ -312,10 +313,30 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     lm: an lm.NGramLM over the N-1 token classes: the search fused with it (w2l_ctc_beam_search_lm): every extension by token c
     adds lm_weight * log p_LM(c | prefix) + class_score[c] (class_score: [N-1] float32 on the device, or None), the end adds
     lm_weight * log p_LM(EOS | hypothesis) + eos_score when the model has EOS.  Returns a fourth tensor then: lm_scores [B][nbest],
-    the hypotheses' unweighted LM scores.  Without lm the other three arguments must keep their defaults."""
+    the hypotheses' unweighted LM scores.  Without lm the other three arguments must keep their defaults.
+    lexicon: a lexicon.Lexicon over the N-1 token classes: the search restricted to its spellings (w2l_ctc_beam_search_lex).  lm is
+    required then and is an NGramLM over the lexicon's WORDS (NGramLM.from_arpa(path, lexicon.words)); class_score must be None;
+    every completed word adds lm_weight * log p_LM(word | words before) + word_score, smeared down the trie.  Returns
+    (labels, lengths, scores, lm_scores, words [B][nbest][max_words] int32 word ids, -1 beyond; word_counts [B][nbest] int32);
+    max_words defaults to max_len.  A hypothesis that ends inside a word does not count: an utterance may have only empty rows."""
     _emission_checks(emission)
     B, T, N = emission.shape
-    if lm is None:
+    if lexicon is not None:
+        if lm is None:
+            raise _lib.W2LInvalidArgument("ctc_beam_search: lexicon needs lm, a model over the lexicon's words")
+        if class_score is not None:
+            raise _lib.W2LInvalidArgument("ctc_beam_search: class_score must be None with a lexicon (word_score is the per-word term)")
+        if lm.num_tokens != lexicon.num_words:
+            raise _lib.W2LInvalidArgument(f"ctc_beam_search: the LM has {lm.num_tokens} words, the lexicon {lexicon.num_words}")
+        if lexicon.num_tokens != N - 1:
+            raise _lib.W2LInvalidArgument(f"ctc_beam_search: the lexicon has {lexicon.num_tokens} tokens, the emissions {N - 1}")
+        if not lm.has_eos and eos_score != 0.0:
+            raise _lib.W2LInvalidArgument("ctc_beam_search: eos_score needs a model with EOS")
+        if max_words is not None and int(max_words) < 1:
+            raise _lib.W2LInvalidArgument("ctc_beam_search: max_words must be at least 1")
+    elif word_score != 0.0 or max_words is not None:
+        raise _lib.W2LInvalidArgument("ctc_beam_search: word_score and max_words need lexicon")
+    elif lm is None:
         if lm_weight != 0.0 or class_score is not None or eos_score != 0.0:
             raise _lib.W2LInvalidArgument("ctc_beam_search: lm_weight, class_score and eos_score need lm")
     else:
@@ -341,6 +362,20 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     labels = torch.empty(*shape, max(max_len, 1), dtype=torch.int32, device=emission.device)
     lengths = torch.empty(*shape, dtype=torch.int32, device=emission.device)
     scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
+    if lexicon is not None:
+        max_words = max(max_len, 1) if max_words is None else int(max_words)
+        ws = _ws(L.w2l_ctc_beam_lex_workspace_size(B, T, N, int(beam), int(beam_token)), emission.device)
+        lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
+        words = torch.empty(*shape, max_words, dtype=torch.int32, device=emission.device)
+        word_counts = torch.empty(*shape, dtype=torch.int32, device=emission.device)
+        blob, lex_blob = lm.device_blob(emission.device), lexicon.device_blob(emission.device)
+        _lib.check(L.w2l_ctc_beam_search_lex(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
+                                             int(beam), int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)),
+                                             nbest, max_len, blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
+                                             float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),
+                                             scores.data_ptr(), lm_scores.data_ptr(), max_words, words.data_ptr(),
+                                             word_counts.data_ptr(), ws.data_ptr(), _stream()), "ctc_beam_search")
+        return labels, lengths, scores, lm_scores, words, word_counts
     if lm is not None:
         if class_score is not None:
             _check_dev(emission, class_score)
@@ -518,8 +553,8 @@ class CTCLoss(SequenceCriterion):
         return ctc_align(emission, target, frames, with_score=False)[0]
 
     def beamSearch(self, emission, frames=None, **options):
-        """lexicon-free n-best beam search over the emissions (ctc_beam_search's options, lm= included): (labels, lengths, scores),
-        and lm_scores with an LM"""
+        """n-best beam search over the emissions (ctc_beam_search's options, lm= and lexicon= included): (labels, lengths, scores),
+        lm_scores with an LM, and words and word_counts with a lexicon"""
         return ctc_beam_search(emission, frames, **options)
 
     def score(self, emission, target):

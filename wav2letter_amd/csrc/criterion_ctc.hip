@@ -894,3 +894,4 @@ W2L_API int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, 
 #include "criterion_ctc_align.hpp"
 #include "criterion_ctc_beam.hpp"
 #include "criterion_ctc_beam_lm.hpp"
+#include "criterion_ctc_beam_lex.hpp"

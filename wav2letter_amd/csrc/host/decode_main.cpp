@@ -24,9 +24,18 @@
 //     begin a word: the pieces that start with the word separator with --usewordpiece=true, else the separator class.  In the
 //     beam dump lmScore is the hypothesis's unweighted LM score and amScore = score - (lmweight * lmScore + its word scores +
 //     eosscore), computed on the host in double.
+//   --uselexicon=true --decodertype=wrd --lexicon=<file> --lm=<word arpa> [--lmweight=0] [--wordscore=0] [--eosscore=0]
+//     [--smearing=none|max]: the search restricted to the spellings of the lexicon and scored by an n-gram LM over its WORDS
+//     (w2l_ctc_beam_search_lex; the reference recipes' decoder configuration).  The word-separator class is the silence token the
+//     search lets loop between words when the token dictionary has it.  --wordscore is added once per word.  .hyp lines, beam-dump
+//     rows and WER come from the hypotheses' word ids; amScore = score - (lmweight * lmScore + wordscore * words + eosscore).
+//     A sample none of whose hypotheses ends on a word boundary gets an empty hypothesis.
 //   The last line gives the total WER / TER (fl::EditDistanceMeter, the --valid evaluation's).
-// Refused, each with a message that names the flag: an unreadable or malformed --lm, --lmtype other than kenlm, --uselexicon=true,
-// --decodertype=wrd, a non-zero --silscore, a non-zero --wordscore without --lm, a --criterion other than ctc.  (--uselexicon and --decodertype default to false / tkn here: the only decoder built.)
+// Refused, each with a message that names the flag: an unreadable or malformed --lm, --lmtype other than kenlm, --uselexicon=true
+// without --lexicon or --lm, --decodertype=wrd without --uselexicon=true, --decodertype=tkn with it, --smearing=logadd, a finite
+// --unkscore (no unknown-word arc), a lexicon spelling with a token the dictionary lacks (the message names the word), a non-zero
+// --silscore, a non-zero --wordscore without --lm, a --criterion other than ctc.  (--uselexicon and --decodertype default to
+// false / tkn here, so an invocation without them is the lexicon-free search.)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -34,6 +43,7 @@
 #include <iostream>
 #include <limits>
 
+#include "../../../include/fl_compat/lexicon.h"
 #include "../../../include/fl_compat/lm.h"
 #include "list_data.hpp"
 
@@ -47,6 +57,7 @@ int usage(const char* exe) {
             << " --am=<model> --test=<list> [--datadir=...] [--batchsize=...] [--sclite=<dir>] [--beamsize=2500] [--beamsizetoken=250000]"
                " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [flags]\n"
                " [--lm=<arpa> --lmtype=kenlm --lmweight=0 --eosscore=0 --wordscore=0]\n"
+               " [--uselexicon=true --decodertype=wrd --lexicon=<file> --lm=<word arpa> --smearing=none|max]\n"
                " lexicon-free CTC token beam search, optionally with a token-level n-gram LM (ARPA text); beam and tokens per frame are limited to 64.\n"
                " --logadd=false (default): max over a prefix's alignments on the raw emissions -- the 1-best equals the greedy transcript.\n"
                " --logadd=true: the labelling-probability search (sum over a prefix's alignments, on log-softmax rows)."
@@ -97,10 +108,24 @@ int main(int argc, char** argv) {
       if (lmType == "convlm") throw std::invalid_argument("--lmtype=convlm: no ConvLM in this build (an n-gram model as ARPA text: --lmtype=kenlm)");
       if (lmType != "kenlm") throw std::invalid_argument("--lmtype=" + lmType + ": only kenlm (an n-gram model as ARPA text) is built");
     }
-    if (flags.getb("uselexicon", false)) throw std::invalid_argument("--uselexicon=true: no lexicon decoder in this build (use --uselexicon=false)");
-    if (flags.get("decodertype", "tkn") != "tkn")
-      throw std::invalid_argument("--decodertype=" + flags.get("decodertype", "") + ": only the token decoder (--decodertype=tkn) is built");
-    if (flags.getd("silscore", 0.0) != 0.0) throw std::invalid_argument("--silscore: no silence score without a lexicon (leave it 0)");
+    const bool useLexicon = flags.getb("uselexicon", false);
+    const std::string decoderType = flags.get("decodertype", "tkn"), lexiconPath = flags.get("lexicon", "");
+    const std::string smearing = flags.get("smearing", "none");
+    if (decoderType != "tkn" && decoderType != "wrd")
+      throw std::invalid_argument("--decodertype=" + decoderType + ": tkn (lexicon-free) or wrd (with --uselexicon=true)");
+    if (useLexicon) {
+      if (lexiconPath.empty()) throw std::invalid_argument("--uselexicon=true needs --lexicon=<file>");
+      if (lmPath.empty()) throw std::invalid_argument("--uselexicon=true needs --lm=<arpa of a model over the lexicon's words>");
+      if (decoderType != "wrd")
+        throw std::invalid_argument("--decodertype=tkn with --uselexicon=true: no token LM under a lexicon in this build (--decodertype=wrd)");
+      if (smearing == "logadd") throw std::invalid_argument("--smearing=logadd: log-add smearing is not built (none or max)");
+      if (smearing != "none" && smearing != "max") throw std::invalid_argument("--smearing=" + smearing + ": none or max");
+      if (std::isfinite(flags.getd("unkscore", -std::numeric_limits<double>::infinity())))
+        throw std::invalid_argument("--unkscore: no unknown-word arc in this build (leave it -inf)");
+    } else if (decoderType == "wrd") {
+      throw std::invalid_argument("--decodertype=wrd needs --uselexicon=true --lexicon=<file> --lm=<word arpa>");
+    }
+    if (flags.getd("silscore", 0.0) != 0.0) throw std::invalid_argument("--silscore: no silence score in this build (leave it 0)");
     const double wordScore = flags.getd("wordscore", 0.0), lmWeight = flags.getd("lmweight", 0.0), eosScore = flags.getd("eosscore", 0.0);
     if (lmPath.empty() && wordScore != 0.0) throw std::invalid_argument("--wordscore: no word score without --lm (leave it 0)");
     if (!std::isfinite(wordScore) || !std::isfinite(lmWeight) || !std::isfinite(eosScore))
@@ -160,9 +185,29 @@ int main(int argc, char** argv) {
 
     // ---- the language model over the token classes, and the word score as class scores
     std::unique_ptr<NGramLM> lm;
+    std::unique_ptr<Lexicon> lexicon;
     std::vector<float> classScore((size_t)numClasses - 1, 0.f);
     af::array classScoreDev;
-    if (!lmPath.empty()) {
+    if (useLexicon) {   // the lexicon trie, the LM over its words, and the LM's unigram-context scores smeared down the trie
+      std::vector<std::string> tokens;
+      for (int c = 0; c < numClasses - 1; ++c) tokens.push_back(d.dict.getEntry(c));
+      const std::string sil = !d.wordsep.empty() && d.dict.contains(d.wordsep) && d.dict.getIndex(d.wordsep) < numClasses - 1 ? d.wordsep : "";
+      try {
+        lexicon.reset(new Lexicon(Lexicon::fromFile(lexiconPath, tokens, nullptr, sil, "none")));
+      } catch (const std::exception& e) {
+        throw std::invalid_argument("--lexicon=" + lexiconPath + ": " + e.what());
+      }
+      try {
+        lm.reset(new NGramLM(NGramLM::fromArpa(lmPath, lexicon->words())));
+      } catch (const std::exception& e) {
+        throw std::invalid_argument("--lm=" + lmPath + ": " + e.what());
+      }
+      if (smearing == "max") lexicon.reset(new Lexicon(Lexicon::fromFile(lexiconPath, tokens, lm.get(), sil, "max")));
+      if (!lm->hasEos() && eosScore != 0.0) throw std::invalid_argument("--eosscore: the model of --lm has no </s> (leave it 0)");
+      std::cerr << "[Decode] --lexicon: " << lexicon->numWords() << " words, " << lexicon->numNodes() << " nodes, " << lexicon->dropped()
+                << " homophones beyond the sixth dropped, smearing " << smearing << ", silence token " << (sil.empty() ? "none" : sil)
+                << "; --lm over the words: order " << lm->order() << ", " << lm->numStates() << " states; " << lm->message() << std::endl;
+    } else if (!lmPath.empty()) {
       std::vector<std::string> tokens;
       for (int c = 0; c < numClasses - 1; ++c) tokens.push_back(d.dict.getEntry(c));
       try {
@@ -230,6 +275,11 @@ int main(int argc, char** argv) {
         opt.classScore = classScoreDev;
         opt.eosScore = (float)eosScore;
       }
+      if (lexicon) {
+        opt.lexicon = lexicon.get();
+        opt.wordScore = (float)wordScore;
+        opt.maxWords = Tout;
+      }
       auto res = ctc->beamSearch(out.array(), af::array(af::dim4(1, B), frames.data()), opt);
       std::vector<int> labels((size_t)B * M * Tout), lengths((size_t)B * M);
       std::vector<float> scores((size_t)B * M);
@@ -238,6 +288,13 @@ int main(int argc, char** argv) {
       res.scores.host(scores.data());
       std::vector<float> lmScores((size_t)B * M, 0.f);
       if (lm) res.lmScores.host(lmScores.data());
+      std::vector<int> words, wordCounts;
+      if (lexicon) {
+        words.resize((size_t)B * M * Tout);
+        wordCounts.resize((size_t)B * M);
+        res.words.host(words.data());
+        res.wordCounts.host(wordCounts.data());
+      }
 
       for (int b = 0; b < B; ++b) {
         const auto& smp = d.samples[(size_t)d.mine[(size_t)(k * batch + b)]];
@@ -251,7 +308,9 @@ int main(int argc, char** argv) {
           if (len < 0) len = 0;   // nothing survived (a row of -inf or NaN emissions): an empty hypothesis, so every sample has its line
           const int* row = labels.data() + ((size_t)b * M + m) * Tout;
           const auto letterPrediction = tknLabels2Ltr(std::vector<int>(row, row + len), d.dict, criterionName, surround, d.replabel, wp, d.wordsep);
-          const auto wordPrediction = tkn2Wrd(letterPrediction, d.wordsep);
+          const int* wrow = lexicon ? words.data() + ((size_t)b * M + m) * Tout : nullptr;
+          const int nWords = lexicon ? std::max(wordCounts[(size_t)b * M + m], 0) : 0;
+          const auto wordPrediction = lexicon ? lexicon->wordIds2Words(std::vector<int>(wrow, wrow + nWords)) : tkn2Wrd(letterPrediction, d.wordsep);
           if (beamDump) {
             fl::EditDistanceMeter one;
             one.add(wordPrediction, wordTarget);
@@ -261,6 +320,7 @@ int main(int argc, char** argv) {
               lmScore = (double)lmScores[(size_t)b * M + m];
               double extra = (double)(float)lmWeight * lmScore + (lm->hasEos() ? (double)(float)eosScore : 0.0);
               for (int i = 0; i < len; ++i) extra += (double)classScore[(size_t)row[i]];
+              if (lexicon) extra += (double)(float)wordScore * nWords;
               amScore = score - extra;
             }
             hypFile << smp.id << " | " << std::to_string(score) << " | " << std::to_string(amScore) << " | " << std::to_string(lmScore) << " | "

@@ -15,6 +15,7 @@
 #include <unordered_set>
 
 #include "../../../include/fl_compat/flashlight.h"
+#include "../../../include/fl_compat/lexicon.h"
 #include "../../../include/fl_compat/lm.h"
 #include "w2l_host.hpp"
 
@@ -1276,6 +1277,27 @@ CTCLoss::BeamSearchResult CTCLoss::beamSearch(const af::array& input, const af::
   r.lengths = af::array(af::dim4(o.nbest, B), af::s32);
   r.scores = af::array(af::dim4(o.nbest, B));
   const bool normalize = o.normalize < 0 ? o.logAdd : o.normalize != 0;
+  if (o.lexicon) {   // the search restricted to the lexicon's spellings, scored by a LM over words (w2l_ctc_beam_search_lex)
+    if (!o.lm) throw std::invalid_argument("beamSearch: lexicon needs lm, a model over the lexicon's words");
+    if (!o.classScore.isempty()) throw std::invalid_argument("beamSearch: classScore must be empty with a lexicon");
+    if (o.lm->numTokens() != o.lexicon->numWords()) throw std::invalid_argument("beamSearch: the LM's word count is not the lexicon's");
+    if (o.lexicon->numTokens() != N - 1) throw std::invalid_argument("beamSearch: the lexicon's token count is not the emissions' N - 1");
+    if (o.maxWords < 0) throw std::invalid_argument("beamSearch: maxWords must not be negative");
+    const int maxWords = o.maxWords > 0 ? o.maxWords : Lmax;
+    r.lmScores = af::array(af::dim4(o.nbest, B));
+    r.words = af::array(af::dim4(maxWords, o.nbest, B), af::s32);
+    r.wordCounts = af::array(af::dim4(o.nbest, B), af::s32);
+    auto wsx = devAlloc(w2l_ctc_beam_lex_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    w2l::w2lCheck(w2l_ctc_beam_search_lex(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+                                          normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
+                                          o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
+                                          r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
+                                          r.words.device<int>(), r.wordCounts.device<int>(), wsx.get(), S()),
+                  "ctc beam search with lexicon");
+    af::sync();  // wsx is released at return
+    return r;
+  }
+  if (o.wordScore != 0.f || o.maxWords != 0) throw std::invalid_argument("beamSearch: wordScore and maxWords need lexicon");
   if (!o.lm) {
     if (o.lmWeight != 0.f || !o.classScore.isempty() || o.eosScore != 0.f)
       throw std::invalid_argument("beamSearch: lmWeight, classScore and eosScore need lm");

@@ -349,6 +349,17 @@ def tkn_target_to_ltr(target: Sequence[int], token_dict: Dictionary, criterion: 
     return tkn_idx_to_ltr(toks, token_dict, use_wordpiece, wordsep)
 
 
+def word_ids_to_words(ids: Sequence[int], words: Sequence[str]) -> List[str]:
+    """a row of word ids from the lexicon-constrained beam search (lexicon.Lexicon.words is `words`) -> the words; the -1 padding
+    of the row ends it"""
+    out = []
+    for i in ids:
+        if int(i) < 0:
+            break
+        out.append(words[int(i)])
+    return out
+
+
 def tkn2wrd(letters: Sequence[str], wordsep: str) -> List[str]:
     words: List[str] = []
     cur = ""
