@@ -192,7 +192,7 @@ def test_x2_bitwise_against_the_float32_restatement(name):
 # ---- X3: a lexicon of one-token words is w2l_ctc_beam_search_lm ----------------------------------------------------------------
 
 @pytest.mark.parametrize("B,T,N,W,K,thr,log_add", [(2, 24, 9998, 64, 64, INF, False), (3, 30, 30, 8, 5, 6.0, True),
-                                                    (2, 20, 9998, 16, 8, INF, True)])
+                                                    (2, 20, 9998, 16, 8, INF, True), (2, 24, 9998, 64, 64, INF, True)])
 def test_x3_one_token_words_are_the_token_lm_search(B, T, N, W, K, thr, log_add):
     """every token a one-token word whose id is its class, no silence token, wordSmear = NULL, the same LM: the token-LM search with
     classScore filled with wordScore.  The smear terms are lmWeight * 0: scores are equal as values"""

@@ -159,7 +159,7 @@ def _without_eos(tb):
 # ---- L3: lmWeight = 0 is w2l_ctc_beam_search -------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("B,T,N,W,K,thr,log_add", [(2, 24, 9998, 64, 64, INF, False), (3, 30, 30, 8, 5, 6.0, True),
-                                                    (2, 20, 9998, 16, 8, INF, True)])
+                                                    (2, 20, 9998, 16, 8, INF, True), (2, 24, 9998, 64, 64, INF, True)])
 def test_l3_zero_weight_is_the_lm_free_search(B, T, N, W, K, thr, log_add):
     rng = np.random.default_rng(N + T)
     x = rng.normal(0, 2, size=(B, T, N)).astype(F32) if log_add else _ints(rng, B, T, N)

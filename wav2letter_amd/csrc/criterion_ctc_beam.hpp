@@ -17,22 +17,37 @@
 //                    extension; a selection round is a 64-bit wave max of (total, ~(rank, kind, k)) and an O(1) update of the winner.
 //                    Extensions merged into a beam entry are bits of a per-lane mask.  No waiting between workgroups, no flags.
 //   ctc_beam_finish  one thread per (utterance, output rank): walks the parent chain, writes labels, length, score.
+// This file also owns what the three searches share, so that a rule of the contract is written once: the workspace (CtcBeamWs,
+// ctc_beam_layout), the tie key, its decoder and the stops of a selection (beam_key, beam_pick), the prefix table's find-or-make
+// (beam_node); for the workgroup scans of criterion_ctc_beam_lm.hpp and criterion_ctc_beam_lex.hpp beam_load_frame, beam_stay_front,
+// beam_select_round and beam_store_final; for the finishes beam_chain_len, beam_write_labels, beam_eos and beam_rerank; for the
+// entry points ctc_beam_check, ctc_beam_begin and ctc_beam_fused_scan.  The other two files keep what is particular to their search.
+// The LM-free search itself uses neither the LM table (ngram_lm.hpp is here for beam_eos) nor kLmPer (the workgroup scans').
 #pragma once
+#include "ngram_lm.hpp"
 
 namespace w2l {
 
+typedef unsigned long long u64;
+
 constexpr int kBeamMax = 64;          // W and K: one lane per entry, one mask bit per frame token
 constexpr int kBeamCandCap = 1024;    // LDS candidates of the row pass
+constexpr int kLmPer = 4;             // (entry, token) pairs a thread of a workgroup scan owns: threads * kLmPer >= W * K
+
+enum CtcBeamVariant { kBeamPlain = 0, kBeamLm = 1, kBeamLex = 2 };   // each one's workspace is the one before plus its own buffers
 
 struct CtcBeamWs {
   float* lse;                  // [B][T]  0 when not normalising
   float* lpb;                  // [B][T]  lp[blank]
   float* tokLp;                // [B][T][K]
   int* tokC;                   // [B][T][K]
-  unsigned long long* table;   // [B][cap] trie edges: (parent node << 32) | (label + 1), 0 = free
+  u64* table;   // [B][cap] trie edges: (parent node << 32) | (label + 1), 0 = free
   int* finNode;                // [B][64] node of the final entry of rank r
   float* finTot;               // [B][64]
   int* finN;                   // [B]
+  int* finState;               // [B][64] LM state of the final entry of rank r                (null: kBeamPlain)
+  float* finAcc;               // [B][64] sum of q over its labels, in label order             (null: kBeamPlain)
+  int* finU;                   // [B][64] lexicon node of the final entry of rank r            (null: but for kBeamLex)
   int K;
   unsigned cap;
 };
@@ -44,7 +59,7 @@ static size_t ctc_beam_cap(int T, int W) {
   return c;
 }
 
-static size_t ctc_beam_layout(CtcBeamWs* w, void* ws, int B, int T, int W, int K) {
+static size_t ctc_beam_layout(CtcBeamWs* w, void* ws, int B, int T, int W, int K, int variant) {
   const size_t rows = (size_t)B * T, cap = ctc_beam_cap(T, W);
   char* p = (char*)ws;
   char* const p0 = p;
@@ -52,11 +67,15 @@ static size_t ctc_beam_layout(CtcBeamWs* w, void* ws, int B, int T, int W, int K
   float* lpb = (float*)p; p += align_up(rows * sizeof(float), 256);
   float* tokLp = (float*)p; p += align_up(rows * K * sizeof(float), 256);
   int* tokC = (int*)p; p += align_up(rows * K * sizeof(int), 256);
-  unsigned long long* table = (unsigned long long*)p; p += align_up((size_t)B * cap * sizeof(unsigned long long), 256);
+  u64* table = (u64*)p; p += align_up((size_t)B * cap * sizeof(u64), 256);
   int* finNode = (int*)p; p += align_up((size_t)B * kBeamMax * sizeof(int), 256);
   float* finTot = (float*)p; p += align_up((size_t)B * kBeamMax * sizeof(float), 256);
   int* finN = (int*)p; p += align_up((size_t)B * sizeof(int), 256);
-  if (w) *w = CtcBeamWs{lse, lpb, tokLp, tokC, table, finNode, finTot, finN, K, (unsigned)cap};
+  const size_t fin = align_up((size_t)B * kBeamMax * 4, 256);
+  int* finState = nullptr; float* finAcc = nullptr; int* finU = nullptr;
+  if (variant >= kBeamLm) { finState = (int*)p; p += fin; finAcc = (float*)p; p += fin; }
+  if (variant >= kBeamLex) { finU = (int*)p; p += fin; }
+  if (w) *w = CtcBeamWs{lse, lpb, tokLp, tokC, table, finNode, finTot, finN, finState, finAcc, finU, K, (unsigned)cap};
   return (size_t)(p - p0);
 }
 
@@ -67,23 +86,23 @@ __device__ __forceinline__ unsigned beam_ord(float f) {
 }
 __device__ __forceinline__ float beam_unord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+__device__ __forceinline__ u64 wave_max_u64(u64 v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off);
+    const u64 o = __shfl_xor(v, off);
     v = o > v ? o : v;
   }
   // every lane holds the maximum: say so to the compiler (scalar compares and branches downstream)
   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
   const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
+  return ((u64)hi << 32) | lo;
 }
 
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* sm) {
+__device__ __forceinline__ u64 block_max_u64(u64 v, u64* sm) {
   v = wave_max_u64(v);
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
   __syncthreads();
-  unsigned long long r = sm[0];
+  u64 r = sm[0];
 #pragma unroll
   for (int k = 1; k < kRowThreads / 64; ++k) r = sm[k] > r ? sm[k] : r;
   __syncthreads();
@@ -94,7 +113,6 @@ template <bool kBig>
 __global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int normalize,
                                                              const float* __restrict__ x,
                                                              const int* __restrict__ frames, CtcBeamWs ws) {
-  typedef unsigned long long u64;
   __shared__ float sm[8];
   __shared__ u64 sKey[kRowThreads];
   __shared__ u64 sCand[kBeamCandCap];
@@ -211,21 +229,52 @@ __device__ __forceinline__ float beam_oplus(float a, float b) {
   return m == -INFINITY ? m : m + log1pf(expf(fminf(a, b) - m));
 }
 
-__device__ __forceinline__ unsigned long long beam_key(float total, int r, int ext, int k) {
-  return ((unsigned long long)beam_ord(total) << 32) | (unsigned long long)(0xffffffffu - (unsigned)((r << 7) | (ext << 6) | k));
+// The selection key of a candidate, larger = earlier: total descending, rank r ascending, stay before extension, k ascending, slot
+// ascending (the lexicon search's 3 bits; 0 elsewhere, and then the order is total, r, stay first, k: what a word without slot
+// bits would encode).  0 is no candidate.
+__device__ __forceinline__ u64 beam_key(float total, int r, int ext, int k, int slot = 0) {
+  return ((u64)beam_ord(total) << 32) |
+         (u64)(0xffffffffu - (unsigned)((r << 10) | (ext << 9) | (k << 3) | slot));
 }
 
-__device__ __forceinline__ unsigned beam_hash(unsigned long long z) {   // splitmix64's finaliser
+struct BeamWin { u64 key; float tot; int r, ext, k, slot; };   // a round's winner
+
+// The winner of round q from the largest key of the round, or false: no candidate left, -inf, or below the threshold line under
+// the frame's best total (round 0's).  Candidates come in descending order: the rest fails too.  One condition, no early return:
+// the scans' round loops branch once on it; when it is false *w and *best mean nothing (wk = 0 decodes to a NaN total), and every
+// caller ends the frame's rounds.
+__device__ __forceinline__ bool beam_pick(u64 wk, int q, float threshold, float* best, BeamWin* w) {
+  const float wtot = beam_unord((unsigned)(wk >> 32));
+  if (q == 0) *best = wtot;
+  const unsigned tie = 0xffffffffu - (unsigned)wk;
+  w->key = wk; w->tot = wtot;
+  w->r = (int)(tie >> 10); w->ext = (int)((tie >> 9) & 1u); w->k = (int)((tie >> 3) & 63u); w->slot = (int)(tie & 7u);
+  return wk != 0ull && wtot != -INFINITY && !(wtot < *best - threshold);
+}
+
+__device__ __forceinline__ unsigned beam_hash(u64 z) {   // splitmix64's finaliser
   z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
   z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
   return (unsigned)(z ^ (z >> 31));
+}
+
+// Find or make the node of the prefix table for (parent node, label): node id = slot + 1.  At most T * W nodes are ever made and
+// the table has twice as many slots, so a free slot ends the chain long before the bound; a damaged table cannot spin a wavefront.
+__device__ __forceinline__ int beam_node(u64* tab, unsigned capm, int par, int label) {
+  const u64 edge = ((u64)(unsigned)par << 32) | (u64)(unsigned)(label + 1);
+  unsigned h = beam_hash(edge) & capm;
+  for (unsigned probe = 0; probe <= capm; ++probe) {
+    const u64 old = atomicCAS(&tab[h], 0ull, edge);
+    if (old == 0ull || old == edge) break;
+    h = (h + 1) & capm;
+  }
+  return (int)h + 1;
 }
 
 template <bool kLogAdd>
 __global__ __launch_bounds__(64) void ctc_beam_scan(int T, int N, int W, float threshold,
                                                     const float* __restrict__ x,
                                                     const int* __restrict__ frames, CtcBeamWs ws) {
-  typedef unsigned long long u64;
   __shared__ u64 sGone[64];   // per beam entry: frame tokens whose extension merged into another entry
   __shared__ int sTc[64];
   __shared__ float sTl[64];
@@ -296,20 +345,15 @@ __global__ __launch_bounds__(64) void ctc_beam_scan(int T, int N, int W, float t
       const u64 regKey = kn >= 0 ? beam_key(sTl[max(kn, 0)] + tot, lane, 1, kn) : 0ull;
       u64 lk = stayKey > specKey ? stayKey : specKey;
       lk = regKey > lk ? regKey : lk;
-      const u64 wk = wave_max_u64(lk);
-      if (wk == 0ull) break;
-      const float wtot = beam_unord((unsigned)(wk >> 32));
-      if (q == 0) best = wtot;
-      if (wtot == -INFINITY || wtot < best - threshold) break;   // candidates come in descending order: the rest fails too
-      const unsigned tie = 0xffffffffu - (unsigned)wk;
-      const int wr = (int)(tie >> 7), wext = (int)((tie >> 6) & 1u), wkk = (int)(tie & 63u);
-      if (lane == wr) {
-        if (!wext) {
+      BeamWin w;
+      if (!beam_pick(wave_max_u64(lk), q, threshold, &best, &w)) break;
+      if (lane == w.r) {
+        if (!w.ext) {
           sNode[q] = node; sPar[q] = par; sE[q] = e; sPb[q] = spb; sPnb[q] = spnb;
           stayKey = 0ull;
         } else {
-          sNode[q] = -1; sPar[q] = node; sE[q] = sTc[wkk]; sPb[q] = -INFINITY; sPnb[q] = wtot;
-          if (specKey == wk) specKey = 0ull;
+          sNode[q] = -1; sPar[q] = node; sE[q] = sTc[w.k]; sPb[q] = -INFINITY; sPnb[q] = w.tot;
+          if (specKey == w.key) specKey = 0ull;
           else avail &= avail - 1;
         }
       }
@@ -319,16 +363,7 @@ __global__ __launch_bounds__(64) void ctc_beam_scan(int T, int N, int W, float t
     n = __builtin_amdgcn_readfirstlane(q);
     if (lane < n) {
       node = sNode[lane]; par = sPar[lane]; e = sE[lane]; pb = sPb[lane]; pnb = sPnb[lane];
-      if (node == -1) {   // a new prefix: find or make its trie node
-        const u64 edge = ((u64)(unsigned)par << 32) | (u64)(unsigned)(e + 1);
-        unsigned h = beam_hash(edge) & capm;
-        for (;;) {
-          const u64 old = atomicCAS(&tab[h], 0ull, edge);
-          if (old == 0ull || old == edge) break;
-          h = (h + 1) & capm;
-        }
-        node = (int)h + 1;
-      }
+      if (node == -1) node = beam_node(tab, capm, par, e);   // a new prefix
     } else {
       node = -2; par = -1; e = -1; pb = -INFINITY; pnb = -INFINITY;
     }
@@ -339,18 +374,91 @@ __global__ __launch_bounds__(64) void ctc_beam_scan(int T, int N, int W, float t
   if (lane == 0) ws.finN[b] = n;
 }
 
-__global__ __launch_bounds__(64) void ctc_beam_finish(int M, int Lmax, CtcBeamWs ws, int* __restrict__ labels,
-                                                      int* __restrict__ lengths, float* __restrict__ scores) {
-  typedef unsigned long long u64;
-  const int b = blockIdx.x, m = threadIdx.x;
-  if (m >= M) return;
-  const u64* tab = ws.table + (size_t)b * ws.cap;
-  int* lab = labels + ((size_t)b * M + m) * Lmax;
-  const bool live = m < ws.finN[b];
+// ---- the two workgroup scans (ctc_beam_lm_scan, ctc_beam_lex_scan): one workgroup per utterance, the beam double-buffered in LDS
+
+// the frame tokens of `row`, by the first wavefront; the caller's barrier publishes them
+__device__ __forceinline__ void beam_load_frame(const CtcBeamWs& ws, size_t row, int* sTc, float* sTl) {
+  const int tid = threadIdx.x, K = ws.K;
+  if (tid < 64) {
+    sTc[tid] = tid < K ? ws.tokC[row * K + tid] : -2;
+    sTl[tid] = tid < K ? ws.tokLp[row * K + tid] : -INFINITY;
+  }
+}
+
+// The front of stay(j), j = threadIdx.x < n, from the current beam (the arrays of this frame's half): pb' = lp[blank] + tot, pnb' =
+// lp[e] + pnb before any merge, and the extension that spells entry j, if the frame has it: ext(pr, kj) with pr the rank of the
+// parent prefix and kj the frame token equal to the last label e; its total starts from `base`, pb of the parent when the parent
+// ends in e too, else its tot.  The search computes that one total its own way, adds it to spnb and marks the extension gone.
+struct BeamStay { int e, kj, pr; bool merge; float spb, spnb, base; };   // merge: the frame has ext(pr, kj)
+__device__ __forceinline__ BeamStay beam_stay_front(int n, int K, const int* sTc, const int* sNode, const int* sPar, const int* sE,
+                                                    const float* sPb, const float* sPnb, const float* sTot, const float* xrow,
+                                                    float lpb, float lse) {
+  const int j = threadIdx.x;
+  BeamStay s;
+  s.e = sE[j];
+  const int par = sPar[j];
+  s.kj = -1; s.pr = -1;
+  for (int k = 0; k < K; ++k) s.kj = sTc[k] == s.e ? k : s.kj;
+  for (int r = 0; r < n; ++r) s.pr = sNode[r] == par ? r : s.pr;
+  s.spb = lpb + sTot[j];
+  s.spnb = -INFINITY;
+  if (s.e >= 0) s.spnb = (xrow[s.e] - lse) + sPnb[j];   // lp[e] comes from the row whether or not e is a frame token
+  s.merge = s.pr >= 0 && s.kj >= 0;
+  s.base = 0.f;
+  if (s.merge) s.base = s.e == sE[s.pr] ? sPb[s.pr] : sTot[s.pr];
+  return s;
+}
+
+// One selection round: the block-wide 64-bit max of every thread's largest key (wave max, one LDS word per wave, ONE barrier: the
+// words are double-buffered by round parity), then beam_pick.  Every thread gets the same answer.
+template <int kWaves>
+__device__ __forceinline__ bool beam_select_round(u64 local, int q, u64 (*sRed)[kWaves],
+                                                  float threshold, float* best, BeamWin* w) {
+  const int tid = threadIdx.x;
+  const u64 wm = wave_max_u64(local);
+  if ((tid & 63) == 0) sRed[q & 1][tid >> 6] = wm;
+  __syncthreads();
+  u64 wk = sRed[q & 1][0];
+#pragma unroll
+  for (int i = 1; i < kWaves; ++i) wk = sRed[q & 1][i] > wk ? sRed[q & 1][i] : wk;
+  return beam_pick(wk, q, threshold, best, w);
+}
+
+// the final entries of utterance b, from the beam's arrays after the last frame (sU: the lexicon search's, else null)
+__device__ __forceinline__ void beam_store_final(const CtcBeamWs& ws, int b, int n, const int* sNode, const float* sTot,
+                                                 const int* sSt, const float* sAcc, const int* sU) {
+  const int tid = threadIdx.x;
+  if (tid >= 64) return;
+  const bool live = tid < n;
+  ws.finNode[b * kBeamMax + tid] = live ? sNode[tid] : -1;
+  ws.finTot[b * kBeamMax + tid] = live ? sTot[tid] : -INFINITY;
+  ws.finState[b * kBeamMax + tid] = live ? sSt[tid] : 0;
+  ws.finAcc[b * kBeamMax + tid] = live ? sAcc[tid] : -INFINITY;
+  if (sU) ws.finU[b * kBeamMax + tid] = live ? sU[tid] : -1;
+  if (tid == 0) ws.finN[b] = n;
+}
+
+// ---- the finishes
+
+// labels of the prefix that ends at `node`; with nwords, also how many of them carry a slot (the lexicon search's completed words)
+__device__ __forceinline__ int beam_chain_len(const u64* tab, int node, int* nwords = nullptr) {
+  int len = 0, nw = 0;
+  for (int p = node; p > 0;) {
+    const u64 edge = tab[p - 1];
+    ++len;
+    nw += (((unsigned)edge - 1u) & 7u) ? 1 : 0;
+    p = (int)(edge >> 32);
+  }
+  if (nwords) *nwords = nw;
+  return len;
+}
+
+// the labels of a live row (its prefix table's labels are the tokens) or none, padded with -1 to Lmax: the row's length
+__device__ __forceinline__ int beam_write_labels(const u64* tab, bool live, const int* finNode, int Lmax, int* lab) {
   int len = 0;
   if (live) {
-    const int node = ws.finNode[b * kBeamMax + m];
-    for (int p = node; p > 0; p = (int)(tab[p - 1] >> 32)) ++len;
+    const int node = *finNode;
+    len = beam_chain_len(tab, node);
     int i = len - 1;
     for (int p = node; p > 0; --i) {
       const u64 edge = tab[p - 1];
@@ -359,41 +467,110 @@ __global__ __launch_bounds__(64) void ctc_beam_finish(int M, int Lmax, CtcBeamWs
     }
   }
   for (int i = min(len, Lmax); i < Lmax; ++i) lab[i] = -1;
+  return len;
+}
+
+// the end-of-sentence term: score + ((lmWeight * qe) + eosScore), one fp32 operation each, in this order; acc + qe
+__device__ __forceinline__ void beam_eos(const void* __restrict__ lm, int state, int eosWord, float lmWeight, float eosScore,
+                                         float* score, float* acc) {
+  const NgramView lv = ngram_view(lm);
+  int unused;
+  const float qe = ngram_q(lv, state, eosWord, &unused);
+  *score = *score + ((lmWeight * qe) + eosScore);
+  *acc = *acc + qe;
+}
+
+// The output row of lane r = threadIdx.x of a one-wavefront finish: the alive lanes by (score descending, lane ascending), then
+// the others -- the empty rows -- in lane order.  Every lane of the wavefront calls it.
+__device__ __forceinline__ int beam_rerank(float score, bool alive, float* sScore) {
+  const int r = threadIdx.x;
+  const u64 am = __ballot(alive);
+  sScore[r] = score;
+  __syncthreads();
+  if (!alive) return __popcll(am) + __popcll(~am & ((1ull << r) - 1ull));
+  int m = 0;
+  for (u64 rest = am; rest; rest &= rest - 1) {
+    const int o = __ffsll((long long)rest) - 1;
+    m += (sScore[o] > score || (sScore[o] == score && o < r)) ? 1 : 0;
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_finish(int M, int Lmax, CtcBeamWs ws, int* __restrict__ labels,
+                                                      int* __restrict__ lengths, float* __restrict__ scores) {
+  const int b = blockIdx.x, m = threadIdx.x;
+  if (m >= M) return;
+  const u64* tab = ws.table + (size_t)b * ws.cap;
+  int* lab = labels + ((size_t)b * M + m) * Lmax;
+  const bool live = m < ws.finN[b];
+  const int len = beam_write_labels(tab, live, ws.finNode + b * kBeamMax + m, Lmax, lab);
   lengths[(size_t)b * M + m] = live ? len : -1;
   scores[(size_t)b * M + m] = live ? ws.finTot[b * kBeamMax + m] : -INFINITY;
 }
 
 static int ctc_beam_clip(int N, int beamToken) { return beamToken < N - 1 ? beamToken : N - 1; }
 
+static size_t ctc_beam_workspace_size(int B, int T, int N, int beam, int beamToken, int variant) {
+  if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
+  const int K = ctc_beam_clip(N, beamToken);
+  if (beam > kBeamMax || K > kBeamMax) return 0;
+  return ctc_beam_layout(nullptr, nullptr, B, T, beam, K, variant);
+}
+
+// the arguments the three searches share; *K = the clipped beamToken.  Every W2L_EINVAL comes before W2L_EUNSUPPORTED, and a
+// search's own checks (all W2L_EINVAL) run before this one, so the code for a bad argument does not depend on which one is first.
+static int ctc_beam_check(int B, int T, int N, const float* input, int beam, int beamToken, float threshold, int nbest, int maxLen,
+                          const int* labels, const int* lengths, const float* scores, const void* workspace, int* K) {
+  if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !workspace) return W2L_EINVAL;
+  if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
+  if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
+  *K = ctc_beam_clip(N, beamToken);
+  if (beam > kBeamMax || *K > kBeamMax) return W2L_EUNSUPPORTED;
+  if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;   // node ids are ints
+  return W2L_OK;
+}
+
+// the start of a call: the workspace, an empty prefix table, the frame tokens of every row
+static int ctc_beam_begin(CtcBeamWs* ws, int variant, int B, int T, int N, const float* input, const int* frames, int beam, int K,
+                          int normalize, void* workspace, hipStream_t s) {
+  ctc_beam_layout(ws, workspace, B, T, beam, K, variant);
+  W2L_HIP_CHECK(hipMemsetAsync(ws->table, 0, (size_t)B * ws->cap * sizeof(u64), s));
+  const unsigned rows = (unsigned)((size_t)B * T);
+  if (N <= kRowThreads * kRowMaxPer)
+    hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);
+  else
+    hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+// The dispatch of a workgroup scan kernel<logAdd, threads>, one workgroup per utterance: 256 threads while they own every (entry,
+// token) pair, else 1024.  launch(logAdd, threads) gets the two as std::integral_constant types and starts that instantiation.
+template <class Launch>
+static void ctc_beam_fused_scan(int W, int K, int logAdd, Launch&& launch) {
+  const bool wide = W * K > 256 * kLmPer;
+  if (logAdd && wide) launch(std::true_type{}, std::integral_constant<int, 1024>{});
+  else if (logAdd) launch(std::true_type{}, std::integral_constant<int, 256>{});
+  else if (wide) launch(std::false_type{}, std::integral_constant<int, 1024>{});
+  else launch(std::false_type{}, std::integral_constant<int, 256>{});
+}
+
 }  // namespace w2l
 
 W2L_API size_t w2l_ctc_beam_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
-  const int K = w2l::ctc_beam_clip(N, beamToken);
-  if (beam > w2l::kBeamMax || K > w2l::kBeamMax) return 0;
-  return w2l::ctc_beam_layout(nullptr, nullptr, B, T, beam, K);
+  return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamPlain);
 }
 
 W2L_API int w2l_ctc_beam_search(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                 float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
                                 float* scores, void* workspace, w2l_stream_t stream) {
   using namespace w2l;
-  if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !workspace) return W2L_EINVAL;
-  if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
-  if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
-  const int K = ctc_beam_clip(N, beamToken);
-  if (beam > kBeamMax || K > kBeamMax) return W2L_EUNSUPPORTED;
-  if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;   // node ids are ints
+  int K = 0;
+  if (const int rc = ctc_beam_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
   CtcBeamWs ws{};
-  ctc_beam_layout(&ws, workspace, B, T, beam, K);
-  W2L_HIP_CHECK(hipMemsetAsync(ws.table, 0, (size_t)B * ws.cap * sizeof(unsigned long long), s));
-  const unsigned rows = (unsigned)((size_t)B * T);
-  if (N <= kRowThreads * kRowMaxPer)
-    hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ws);
-  else
-    hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ws);
-  W2L_LAUNCH_CHECK();
+  if (const int rc = ctc_beam_begin(&ws, kBeamPlain, B, T, N, input, frames, beam, K, normalize, workspace, s)) return rc;
   if (logAdd)
     hipLaunchKernelGGL(ctc_beam_scan<true>, dim3((unsigned)B), dim3(64), 0, s, T, N, beam, threshold, input, frames, ws);
   else

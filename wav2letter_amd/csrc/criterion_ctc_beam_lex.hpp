@@ -1,8 +1,11 @@
 // criterion_ctc_beam_lex.hpp -- w2l_ctc_beam_search_lex: the CTC prefix beam search restricted to the spellings of a lexicon and
 // scored by a word-level back-off n-gram LM whose score is smeared down the lexicon trie (contract: include/w2l_hip.h; the lexicon
 // table: lexicon.hpp; the LM table and its score rule: ngram_lm.hpp).  Included at the end of criterion_ctc.hip after
-// criterion_ctc_beam_lm.hpp: the row kernel (ctc_beam_rows), the prefix table, (+), the workspace layout and the selection rounds
-// are the LM search's.
+// criterion_ctc_beam_lm.hpp.  criterion_ctc_beam.hpp owns the row kernel (ctc_beam_rows), the workspace, the prefix table, the keys,
+// (+), the entry-point plumbing and the parts of a workgroup scan and of a finish shared with the token-LM search (frame load,
+// front of a stay, selection round, final store; chain length, end-of-sentence term, re-rank).  This file keeps what is particular
+// to the lexicon: the totals of its candidates (beam_lex_a, beam_lex_word), a pair's best-of-seven with its consumed mask
+// (beam_lex_best), the two passes of a frame, and the finish's walk that rebuilds tokens and words from labels and node records.
 //   ctc_beam_lex_scan    one workgroup of 256 or 1024 threads per utterance.  A hypothesis is a node of the prefix table whose edge
 //                        label is (lexicon node reached by the token << 3) | slot -- slot 0: the token moves into the lexicon trie
 //                        (or is the silence loop at the root, lexicon node 0), slot 1 + i: it completes word i of that node -- so
@@ -22,23 +25,6 @@
 
 namespace w2l {
 
-struct CtcBeamLexWs {
-  CtcBeamLmWs l;
-  int* finU;   // [B][64] lexicon node of the final entry of rank r
-};
-
-static size_t ctc_beam_lex_layout(CtcBeamLexWs* w, void* ws, int B, int T, int W, int K) {
-  const size_t base = ctc_beam_lm_layout(w ? &w->l : nullptr, ws, B, T, W, K);   // a multiple of 256
-  if (w) w->finU = (int*)((char*)ws + base);
-  return base + align_up((size_t)B * kBeamMax * 4, 256);
-}
-
-// total descending, r ascending, stay before extension, k ascending, slot ascending
-__device__ __forceinline__ unsigned long long beam_lex_key(float total, int r, int ext, int k, int slot) {
-  return ((unsigned long long)beam_ord(total) << 32) |
-         (unsigned long long)(0xffffffffu - (unsigned)((r << 10) | (ext << 9) | (k << 3) | slot));
-}
-
 // a = (lp[c] + base) + (lmWeight * (smear[v] - su)); a completed word: a + ((lmWeight * (q - smear[v])) + wordScore); one fp32
 // operation each, in this order
 __device__ __forceinline__ float beam_lex_a(float lpc, float base, float lmWeight, float smv, float su) {
@@ -50,14 +36,13 @@ __device__ __forceinline__ float beam_lex_word(float a, float lmWeight, float q,
 
 // the best candidate of a pair that is not in its consumed mask (meta = nw | hasChildren << 3 | consumed << 4): 0 when none is left
 __device__ __forceinline__ void beam_lex_best(const NgramView& lv, const LexView& xv, int v, float a, float smv, unsigned meta, int st,
-                                              float lmWeight, float wordScore, int r, int k, unsigned long long* key, int* nst,
+                                              float lmWeight, float wordScore, int r, int k, u64* key, int* nst,
                                               float* lq) {
-  typedef unsigned long long u64;
   const unsigned done = meta >> 4;
   u64 best = 0ull;
   int bn = 0;
   float bq = 0.f;
-  if (((meta >> 3) & 1u) && !(done & 1u)) best = beam_lex_key(a, r, 1, k, 0);
+  if (((meta >> 3) & 1u) && !(done & 1u)) best = beam_key(a, r, 1, k, 0);
   const int nw = (int)(meta & 7u);
   if (nw > 0 && (done >> 1) != (1u << nw) - 1u) {
     const LexNode& nd = lex_node(xv, v);
@@ -65,7 +50,7 @@ __device__ __forceinline__ void beam_lex_best(const NgramView& lv, const LexView
       if (!((done >> (1 + i)) & 1u)) {
         int ns;
         const float q = ngram_q(lv, st, nd.words[i], &ns);
-        const u64 kk = beam_lex_key(beam_lex_word(a, lmWeight, q, smv, wordScore), r, 1, k, 1 + i);
+        const u64 kk = beam_key(beam_lex_word(a, lmWeight, q, smv, wordScore), r, 1, k, 1 + i);
         if (kk > best) { best = kk; bn = ns; bq = q; }
       }
   }
@@ -74,10 +59,9 @@ __device__ __forceinline__ void beam_lex_best(const NgramView& lv, const LexView
 
 template <bool kLogAdd, int kThreads>
 __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int W, float threshold, const float* __restrict__ x,
-                                                              const int* __restrict__ frames, CtcBeamLexWs wsx,
+                                                              const int* __restrict__ frames, CtcBeamWs ws,
                                                               const void* __restrict__ lex, const void* __restrict__ lm,
                                                               float lmWeight, float wordScore) {
-  typedef unsigned long long u64;
   constexpr int kWaves = kThreads / 64;
   // the beam of this frame and the next one: prefix-table node, parent's node, last token, the label of the last extension, lexicon
   // node, its smear (0 at the root), LM state, pb, pnb, tot, unweighted LM sum
@@ -87,7 +71,6 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
   __shared__ int sTc[64];
   __shared__ float sTl[64];
   __shared__ u64 sRed[2][kWaves];
-  const CtcBeamWs& ws = wsx.l.b;
   const int b = blockIdx.x, tid = threadIdx.x, K = ws.K;
   const int F = align_frames(frames, b, T);
   const float* xb = x + (size_t)b * T * N;
@@ -105,10 +88,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
   }
   for (int t = 0; t < F && n > 0; ++t) {
     const size_t row = row0 + t;
-    if (tid < 64) {
-      sTc[tid] = tid < K ? ws.tokC[row * K + tid] : -2;
-      sTl[tid] = tid < K ? ws.tokLp[row * K + tid] : -INFINITY;
-    }
+    beam_load_frame(ws, row, sTc, sTl);
     for (int i = tid; i < 7 * 64; i += kThreads) (&sGone[0][0])[i] = 0ull;
     const float lpb = ws.lpb[row], lse = ws.lse[row];
     __syncthreads();
@@ -142,33 +122,30 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
     u64 stayKey = 0ull;
     float spb = -INFINITY, spnb = -INFINITY, stot = -INFINITY;
     if (tid < n) {
-      const int e = sE[cur][tid], par = sPar[cur][tid], lab = sLab[cur][tid];
-      int kj = -1, pr = -1;
-      for (int k = 0; k < K; ++k) kj = sTc[k] == e ? k : kj;
-      for (int r = 0; r < n; ++r) pr = sNode[cur][r] == par ? r : pr;
-      spb = lpb + sTot[cur][tid];
-      if (e >= 0) spnb = (xb[(size_t)t * N + e] - lse) + sPnb[cur][tid];   // lp[e] comes from the row whether or not e is a frame token
-      if (pr >= 0 && kj >= 0 && lab >= 0) {
+      const BeamStay s = beam_stay_front(n, K, sTc, sNode[cur], sPar[cur], sE[cur], sPb[cur], sPnb[cur], sTot[cur],
+                                         xb + (size_t)t * N, lpb, lse);
+      const int lab = sLab[cur][tid];
+      spb = s.spb; spnb = s.spnb;
+      if (s.merge && lab >= 0) {
         const int vj = lab >> 3, slot = lab & 7;
-        const float base = e == sE[cur][pr] ? sPb[cur][pr] : sTot[cur][pr];
         float v;
         if (vj == 0) {
-          v = sTl[kj] + base;
+          v = sTl[s.kj] + s.base;
         } else {
           const LexNode& nd = lex_node(xv, vj);
           const float smv = nd.smear;
-          v = beam_lex_a(sTl[kj], base, lmWeight, smv, sSu[cur][pr]);
+          v = beam_lex_a(sTl[s.kj], s.base, lmWeight, smv, sSu[cur][s.pr]);
           if (slot > 0) {
             int unused;
-            const float qm = ngram_q(lv, sSt[cur][pr], nd.words[min(slot - 1, kLexMaxWords - 1)], &unused);
+            const float qm = ngram_q(lv, sSt[cur][s.pr], nd.words[min(slot - 1, kLexMaxWords - 1)], &unused);
             v = beam_lex_word(v, lmWeight, qm, smv, wordScore);
           }
         }
         spnb = beam_oplus<kLogAdd>(spnb, v);
-        atomicOr(&sGone[min(slot, 6)][pr], 1ull << kj);
+        atomicOr(&sGone[min(slot, 6)][s.pr], 1ull << s.kj);
       }
       stot = beam_oplus<kLogAdd>(spb, spnb);
-      stayKey = beam_lex_key(stot, tid, 0, 0, 0);
+      stayKey = beam_key(stot, tid, 0, 0);
     }
     __syncthreads();
     // pass 2: every pair's best candidate among those that did not merge
@@ -194,21 +171,11 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
     int q = 0;
     float best = 0.f;
     while (q < W) {
-      const u64 wm = wave_max_u64(local);
-      if ((tid & 63) == 0) sRed[q & 1][tid >> 6] = wm;
-      __syncthreads();
-      u64 wk = sRed[q & 1][0];
-#pragma unroll
-      for (int w = 1; w < kWaves; ++w) wk = sRed[q & 1][w] > wk ? sRed[q & 1][w] : wk;
-      if (wk == 0ull) break;
-      const float wtot = beam_unord((unsigned)(wk >> 32));
-      if (q == 0) best = wtot;
-      if (wtot == -INFINITY || wtot < best - threshold) break;   // candidates come in descending order: the rest fails too
-      const unsigned tie = 0xffffffffu - (unsigned)wk;
-      const int wr = (int)(tie >> 10), wext = (int)((tie >> 9) & 1u), wkk = (int)((tie >> 3) & 63u), wslot = (int)(tie & 7u);
+      BeamWin w;
+      if (!beam_select_round<kWaves>(local, q, sRed, threshold, &best, &w)) break;
       bool mine = false;
-      if (!wext) {
-        if (tid == wr) {
+      if (!w.ext) {
+        if (tid == w.r) {
           sNode[nxt][q] = sNode[cur][tid]; sPar[nxt][q] = sPar[cur][tid]; sE[nxt][q] = sE[cur][tid]; sLab[nxt][q] = sLab[cur][tid];
           sU[nxt][q] = sU[cur][tid]; sSu[nxt][q] = sSu[cur][tid]; sSt[nxt][q] = sSt[cur][tid]; sAcc[nxt][q] = sAcc[cur][tid];
           sPb[nxt][q] = spb; sPnb[nxt][q] = spnb; sTot[nxt][q] = stot;
@@ -216,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
           mine = true;
         }
       } else {
-        const int idx = wr * K + wkk;
+        const int idx = w.r * K + w.k;
         if (tid == idx % kThreads) {
           const int at = idx / kThreads;
           int v = 0, ns = 0;
@@ -225,14 +192,14 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
 #pragma unroll
           for (int i = 0; i < kLmPer; ++i)
             if (i == at) { v = pv[i]; a = pa[i]; smv = psm[i]; meta = pmeta[i]; ns = nst[i]; q1 = lq[i]; }
-          const bool word = wslot > 0;
-          sNode[nxt][q] = -1; sPar[nxt][q] = sNode[cur][wr]; sE[nxt][q] = sTc[wkk]; sLab[nxt][q] = (v << 3) | wslot;
+          const bool word = w.slot > 0;
+          sNode[nxt][q] = -1; sPar[nxt][q] = sNode[cur][w.r]; sE[nxt][q] = sTc[w.k]; sLab[nxt][q] = (v << 3) | w.slot;
           sU[nxt][q] = word ? 0 : v; sSu[nxt][q] = (word || v == 0) ? 0.f : smv;
-          sSt[nxt][q] = word ? ns : sSt[cur][wr]; sAcc[nxt][q] = word ? sAcc[cur][wr] + q1 : sAcc[cur][wr];
-          sPb[nxt][q] = -INFINITY; sPnb[nxt][q] = wtot; sTot[nxt][q] = wtot;
-          meta |= 1u << (4 + wslot);
+          sSt[nxt][q] = word ? ns : sSt[cur][w.r]; sAcc[nxt][q] = word ? sAcc[cur][w.r] + q1 : sAcc[cur][w.r];
+          sPb[nxt][q] = -INFINITY; sPnb[nxt][q] = w.tot; sTot[nxt][q] = w.tot;
+          meta |= 1u << (4 + w.slot);
           u64 nk;
-          beam_lex_best(lv, xv, v, a, smv, meta, sSt[cur][wr], lmWeight, wordScore, wr, wkk, &nk, &ns, &q1);
+          beam_lex_best(lv, xv, v, a, smv, meta, sSt[cur][w.r], lmWeight, wordScore, w.r, w.k, &nk, &ns, &q1);
 #pragma unroll
           for (int i = 0; i < kLmPer; ++i)
             if (i == at) { pmeta[i] = meta; key[i] = nk; nst[i] = ns; lq[i] = q1; }
@@ -248,78 +215,39 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
     }
     __syncthreads();
     n = q;
-    if (tid < n && sNode[nxt][tid] == -1) {   // a new hypothesis: find or make its node of the prefix table
-      const u64 edge = ((u64)(unsigned)sPar[nxt][tid] << 32) | (u64)(unsigned)(sLab[nxt][tid] + 1);
-      unsigned h = beam_hash(edge) & capm;
-      for (unsigned probe = 0; probe <= capm; ++probe) {   // load factor <= 1/2: a free slot ends the chain long before
-        const u64 old = atomicCAS(&tab[h], 0ull, edge);
-        if (old == 0ull || old == edge) break;
-        h = (h + 1) & capm;
-      }
-      sNode[nxt][tid] = (int)h + 1;
-    }
+    if (tid < n && sNode[nxt][tid] == -1) sNode[nxt][tid] = beam_node(tab, capm, sPar[nxt][tid], sLab[nxt][tid]);   // a new hypothesis
     __syncthreads();
     cur = nxt;
   }
-  if (tid < 64) {
-    const bool live = tid < n;
-    ws.finNode[b * kBeamMax + tid] = live ? sNode[cur][tid] : -1;
-    ws.finTot[b * kBeamMax + tid] = live ? sTot[cur][tid] : -INFINITY;
-    wsx.l.finState[b * kBeamMax + tid] = live ? sSt[cur][tid] : 0;
-    wsx.l.finAcc[b * kBeamMax + tid] = live ? sAcc[cur][tid] : -INFINITY;
-    wsx.finU[b * kBeamMax + tid] = live ? sU[cur][tid] : -1;
-    if (tid == 0) ws.finN[b] = n;
-  }
+  beam_store_final(ws, b, n, sNode[cur], sTot[cur], sSt[cur], sAcc[cur], sU[cur]);
 }
 
-__global__ __launch_bounds__(64) void ctc_beam_lex_finish(int M, int Lmax, int maxWords, CtcBeamLexWs wsx, const void* __restrict__ lex,
+__global__ __launch_bounds__(64) void ctc_beam_lex_finish(int M, int Lmax, int maxWords, CtcBeamWs ws, const void* __restrict__ lex,
                                                           const void* __restrict__ lm, float lmWeight, float eosScore, int useEos,
                                                           int* __restrict__ labels, int* __restrict__ lengths,
                                                           float* __restrict__ scores, float* __restrict__ lmScores,
                                                           int* __restrict__ words, int* __restrict__ wordCounts) {
-  typedef unsigned long long u64;
   __shared__ float sScore[64];
-  __shared__ int sAlive[64];
-  const CtcBeamWs& ws = wsx.l.b;
   const int b = blockIdx.x, r = threadIdx.x;
   const u64* tab = ws.table + (size_t)b * ws.cap;
   const LexView xv = lex_view(lex);
   const int n = ws.finN[b];
-  const bool alive = r < n && wsx.finU[b * kBeamMax + r] == 0;   // only finished words count at the end
+  const bool alive = r < n && ws.finU[b * kBeamMax + r] == 0;   // only finished words count at the end
   float score = -INFINITY, acc = -INFINITY;
   if (alive) {
     score = ws.finTot[b * kBeamMax + r];
-    acc = wsx.l.finAcc[b * kBeamMax + r];
-    if (useEos) {
-      const NgramView lv = ngram_view(lm);
-      int unused;
-      const float qe = ngram_q(lv, wsx.l.finState[b * kBeamMax + r], (int)((const NgramHeader*)lm)->numTokens + 1, &unused);
-      score = score + ((lmWeight * qe) + eosScore);
-      acc = acc + qe;
-    }
+    acc = ws.finAcc[b * kBeamMax + r];
+    if (useEos)
+      beam_eos(lm, ws.finState[b * kBeamMax + r], (int)((const NgramHeader*)lm)->numTokens + 1, lmWeight, eosScore, &score, &acc);
   }
-  sScore[r] = score;
-  sAlive[r] = alive ? 1 : 0;
-  __syncthreads();
-  int na = 0, m = 0, deadBefore = 0;
-  for (int o = 0; o < 64; ++o) {
-    na += sAlive[o];
-    m += (sAlive[o] && (sScore[o] > score || (sScore[o] == score && o < r))) ? 1 : 0;
-    deadBefore += (!sAlive[o] && o < r) ? 1 : 0;
-  }
-  if (!alive) m = na + deadBefore;   // rows na .. M-1 are the empty ones: the other lanes, in lane order
+  const int m = beam_rerank(score, alive, sScore);
   if (m >= M) return;
   int* lab = labels + ((size_t)b * M + m) * Lmax;
   int* wrd = words + ((size_t)b * M + m) * maxWords;
   int len = 0, nwords = 0;
   if (alive) {
     const int node = ws.finNode[b * kBeamMax + r];
-    for (int p = node; p > 0;) {
-      const u64 edge = tab[p - 1];
-      ++len;
-      nwords += (((unsigned)edge - 1u) & 7u) ? 1 : 0;
-      p = (int)(edge >> 32);
-    }
+    len = beam_chain_len(tab, node, &nwords);
     int i = len - 1, j = nwords - 1;
     for (int p = node; p > 0; --i) {
       const u64 edge = tab[p - 1];
@@ -345,10 +273,7 @@ __global__ __launch_bounds__(64) void ctc_beam_lex_finish(int M, int Lmax, int m
 }  // namespace w2l
 
 W2L_API size_t w2l_ctc_beam_lex_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
-  const int K = w2l::ctc_beam_clip(N, beamToken);
-  if (beam > w2l::kBeamMax || K > w2l::kBeamMax) return 0;
-  return w2l::ctc_beam_lex_layout(nullptr, nullptr, B, T, beam, K);
+  return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex);
 }
 
 W2L_API int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
@@ -357,32 +282,19 @@ W2L_API int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input, con
                                     float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
                                     w2l_stream_t stream) {
   using namespace w2l;
-  if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !lmScores || !workspace || !lm) return W2L_EINVAL;
-  if (!lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
-  if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
-  if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
+  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  const int K = ctc_beam_clip(N, beamToken);
-  if (beam > kBeamMax || K > kBeamMax) return W2L_EUNSUPPORTED;
-  if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;   // node ids are ints
+  int K = 0;
+  if (const int rc = ctc_beam_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
-  CtcBeamLexWs ws{};
-  ctc_beam_lex_layout(&ws, workspace, B, T, beam, K);
-  W2L_HIP_CHECK(hipMemsetAsync(ws.l.b.table, 0, (size_t)B * ws.l.b.cap * sizeof(unsigned long long), s));
-  const unsigned rows = (unsigned)((size_t)B * T);
-  if (N <= kRowThreads * kRowMaxPer)
-    hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ws.l.b);
-  else
-    hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ws.l.b);
-  W2L_LAUNCH_CHECK();
-  const bool wide = beam * K > 256 * kLmPer;
-#define W2L_LEX_SCAN(LA, TH)                                                                                                    \
-  hipLaunchKernelGGL((ctc_beam_lex_scan<LA, TH>), dim3((unsigned)B), dim3(TH), 0, s, T, N, beam, threshold, input, frames, ws, lexicon, \
-                     lm, lmWeight, wordScore)
-  if (logAdd) { if (wide) W2L_LEX_SCAN(true, 1024); else W2L_LEX_SCAN(true, 256); }
-  else { if (wide) W2L_LEX_SCAN(false, 1024); else W2L_LEX_SCAN(false, 256); }
-#undef W2L_LEX_SCAN
+  CtcBeamWs ws{};
+  if (const int rc = ctc_beam_begin(&ws, kBeamLex, B, T, N, input, frames, beam, K, normalize, workspace, s)) return rc;
+  ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
+    hipLaunchKernelGGL((ctc_beam_lex_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)B), dim3(decltype(th)::value), 0, s,
+                       T, N, beam, threshold, input, frames, ws, lexicon, lm, lmWeight, wordScore);
+  });
   W2L_LAUNCH_CHECK();
   hipLaunchKernelGGL(ctc_beam_lex_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, maxWords, ws, lexicon, lm, lmWeight,
                      eosScore, lmHasEos ? 1 : 0, labels, lengths, scores, lmScores, words, wordCounts);

@@ -1,6 +1,9 @@
 // criterion_ctc_beam_lm.hpp -- w2l_ctc_beam_search_lm: the CTC prefix beam search fused with a token-level back-off n-gram LM
 // (contract: include/w2l_hip.h; the LM table and its score rule: ngram_lm.hpp).  Included at the end of criterion_ctc.hip after
-// criterion_ctc_beam.hpp, whose row kernel (ctc_beam_rows: frame tokens by the acoustic lp alone), trie, keys and (+) it reuses.
+// criterion_ctc_beam.hpp, whose row kernel (ctc_beam_rows: frame tokens by the acoustic lp alone), workspace, prefix table, keys, (+)
+// and entry-point plumbing it reuses, and which owns the parts of a workgroup scan and of a finish that this search shares with the
+// lexicon search (frame load, front of a stay, selection round, final store; chain walk, end-of-sentence term, re-rank).  This file
+// keeps what is particular to the token LM: the total of an extension (beam_lm_ext) and the bookkeeping of all n * K of them.
 //   ctc_beam_lm_scan    one workgroup of 256 or 1024 threads per utterance.  The LM term depends on (prefix, token), so lp_k + tot
 //                       + g is NOT monotone in k and the LM-free scan's lazy per-lane selection does not hold: every one of the
 //                       n * K extension totals of a frame is made.  Extension (r, k) belongs to thread (r K + k) mod threads, at
@@ -17,27 +20,8 @@
 //                       (score descending, previous rank ascending) as a count over the other lanes, then labels, length, score
 //                       and the unweighted LM score of the rows below M.
 #pragma once
-#include "ngram_lm.hpp"
 
 namespace w2l {
-
-constexpr int kLmPer = 4;   // extensions a thread owns: threads * kLmPer >= W * K
-
-struct CtcBeamLmWs {
-  CtcBeamWs b;
-  int* finState;    // [B][64] LM state of the final entry of rank r
-  float* finAcc;    // [B][64] sum of q over its labels, in label order
-};
-
-static size_t ctc_beam_lm_layout(CtcBeamLmWs* w, void* ws, int B, int T, int W, int K) {
-  const size_t base = ctc_beam_layout(w ? &w->b : nullptr, ws, B, T, W, K);   // a multiple of 256
-  const size_t fin = align_up((size_t)B * kBeamMax * 4, 256);
-  if (w) {
-    w->finState = (int*)((char*)ws + base);
-    w->finAcc = (float*)((char*)ws + base + fin);
-  }
-  return base + 2 * fin;
-}
 
 // pnb' of an extension: (lp[c] + base) + g, g = (lmWeight * q) + classScore[c]; one fp32 operation each, in this order
 __device__ __forceinline__ float beam_lm_ext(float lpc, float base, float lmWeight, float q, const float* __restrict__ classScore, int c) {
@@ -49,9 +33,8 @@ __device__ __forceinline__ float beam_lm_ext(float lpc, float base, float lmWeig
 template <bool kLogAdd, int kThreads>
 __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W, float threshold,
                                                              const float* __restrict__ x, const int* __restrict__ frames,
-                                                             CtcBeamLmWs wsl, const void* __restrict__ lm, float lmWeight,
+                                                             CtcBeamWs ws, const void* __restrict__ lm, float lmWeight,
                                                              const float* __restrict__ classScore) {
-  typedef unsigned long long u64;
   constexpr int kWaves = kThreads / 64;
   __shared__ int sNode[2][64], sPar[2][64], sE[2][64], sSt[2][64];   // the beam of this frame and the next one
   __shared__ float sPb[2][64], sPnb[2][64], sTot[2][64], sAcc[2][64];
@@ -59,7 +42,6 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
   __shared__ int sTc[64];
   __shared__ float sTl[64];
   __shared__ u64 sRed[2][kWaves];
-  const CtcBeamWs& ws = wsl.b;
   const int b = blockIdx.x, tid = threadIdx.x, K = ws.K;
   const int F = align_frames(frames, b, T);
   const float* xb = x + (size_t)b * T * N;
@@ -76,11 +58,8 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
   }
   for (int t = 0; t < F && n > 0; ++t) {
     const size_t row = row0 + t;
-    if (tid < 64) {
-      sTc[tid] = tid < K ? ws.tokC[row * K + tid] : -2;
-      sTl[tid] = tid < K ? ws.tokLp[row * K + tid] : -INFINITY;
-      sGone[tid] = 0;
-    }
+    beam_load_frame(ws, row, sTc, sTl);
+    if (tid < 64) sGone[tid] = 0;
     const float lpb = ws.lpb[row], lse = ws.lse[row];
     __syncthreads();
     const int nxt = cur ^ 1, total = n * K;
@@ -104,18 +83,15 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
     u64 stayKey = 0ull;
     float spb = -INFINITY, spnb = -INFINITY, stot = -INFINITY;
     if (tid < n) {
-      const int e = sE[cur][tid], par = sPar[cur][tid];
-      int kj = -1, pr = -1;
-      for (int k = 0; k < K; ++k) kj = sTc[k] == e ? k : kj;
-      for (int r = 0; r < n; ++r) pr = sNode[cur][r] == par ? r : pr;
-      spb = lpb + sTot[cur][tid];
-      if (e >= 0) spnb = (xb[(size_t)t * N + e] - lse) + sPnb[cur][tid];   // lp[e] comes from the row whether or not e is a frame token
-      if (pr >= 0 && kj >= 0) {
+      const BeamStay s = beam_stay_front(n, K, sTc, sNode[cur], sPar[cur], sE[cur], sPb[cur], sPnb[cur], sTot[cur],
+                                         xb + (size_t)t * N, lpb, lse);
+      spb = s.spb; spnb = s.spnb;
+      if (s.merge) {
         int unused;
-        const float qm = ngram_q(lv, sSt[cur][pr], e, &unused);
-        const float v = beam_lm_ext(sTl[kj], e == sE[cur][pr] ? sPb[cur][pr] : sTot[cur][pr], lmWeight, qm, classScore, e);
+        const float qm = ngram_q(lv, sSt[cur][s.pr], s.e, &unused);
+        const float v = beam_lm_ext(sTl[s.kj], s.base, lmWeight, qm, classScore, s.e);
         spnb = beam_oplus<kLogAdd>(spnb, v);
-        atomicOr(&sGone[pr], 1ull << kj);
+        atomicOr(&sGone[s.pr], 1ull << s.kj);
       }
       stot = beam_oplus<kLogAdd>(spb, spnb);
       stayKey = beam_key(stot, tid, 0, 0);
@@ -135,21 +111,11 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
     int q = 0;
     float best = 0.f;
     while (q < W) {
-      const u64 wm = wave_max_u64(local);
-      if ((tid & 63) == 0) sRed[q & 1][tid >> 6] = wm;
-      __syncthreads();
-      u64 wk = sRed[q & 1][0];
-#pragma unroll
-      for (int w = 1; w < kWaves; ++w) wk = sRed[q & 1][w] > wk ? sRed[q & 1][w] : wk;
-      if (wk == 0ull) break;
-      const float wtot = beam_unord((unsigned)(wk >> 32));
-      if (q == 0) best = wtot;
-      if (wtot == -INFINITY || wtot < best - threshold) break;   // candidates come in descending order: the rest fails too
-      const unsigned tie = 0xffffffffu - (unsigned)wk;
-      const int wr = (int)(tie >> 7), wext = (int)((tie >> 6) & 1u), wkk = (int)(tie & 63u);
+      BeamWin w;
+      if (!beam_select_round<kWaves>(local, q, sRed, threshold, &best, &w)) break;
       bool mine = false;
-      if (!wext) {
-        if (tid == wr) {
+      if (!w.ext) {
+        if (tid == w.r) {
           sNode[nxt][q] = sNode[cur][tid]; sPar[nxt][q] = sPar[cur][tid]; sE[nxt][q] = sE[cur][tid];
           sSt[nxt][q] = sSt[cur][tid]; sAcc[nxt][q] = sAcc[cur][tid];
           sPb[nxt][q] = spb; sPnb[nxt][q] = spnb; sTot[nxt][q] = stot;
@@ -157,15 +123,15 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
           mine = true;
         }
       } else {
-        const int idx = wr * K + wkk;
+        const int idx = w.r * K + w.k;
         if (tid == idx % kThreads) {
           const int slot = idx / kThreads;
 #pragma unroll
           for (int i = 0; i < kLmPer; ++i)
             if (i == slot) {
-              sNode[nxt][q] = -1; sPar[nxt][q] = sNode[cur][wr]; sE[nxt][q] = sTc[wkk];
-              sSt[nxt][q] = nst[i]; sAcc[nxt][q] = sAcc[cur][wr] + lq[i];
-              sPb[nxt][q] = -INFINITY; sPnb[nxt][q] = wtot; sTot[nxt][q] = wtot;
+              sNode[nxt][q] = -1; sPar[nxt][q] = sNode[cur][w.r]; sE[nxt][q] = sTc[w.k];
+              sSt[nxt][q] = nst[i]; sAcc[nxt][q] = sAcc[cur][w.r] + lq[i];
+              sPb[nxt][q] = -INFINITY; sPnb[nxt][q] = w.tot; sTot[nxt][q] = w.tot;
               key[i] = 0ull;
             }
           mine = true;
@@ -180,36 +146,18 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
     }
     __syncthreads();
     n = q;
-    if (tid < n && sNode[nxt][tid] == -1) {   // a new prefix: find or make its trie node
-      const u64 edge = ((u64)(unsigned)sPar[nxt][tid] << 32) | (u64)(unsigned)(sE[nxt][tid] + 1);
-      unsigned h = beam_hash(edge) & capm;
-      for (unsigned probe = 0; probe <= capm; ++probe) {   // load factor <= 1/2: a free slot ends the chain long before
-        const u64 old = atomicCAS(&tab[h], 0ull, edge);
-        if (old == 0ull || old == edge) break;
-        h = (h + 1) & capm;
-      }
-      sNode[nxt][tid] = (int)h + 1;
-    }
+    if (tid < n && sNode[nxt][tid] == -1) sNode[nxt][tid] = beam_node(tab, capm, sPar[nxt][tid], sE[nxt][tid]);   // a new prefix
     __syncthreads();
     cur = nxt;
   }
-  if (tid < 64) {
-    const bool live = tid < n;
-    ws.finNode[b * kBeamMax + tid] = live ? sNode[cur][tid] : -1;
-    ws.finTot[b * kBeamMax + tid] = live ? sTot[cur][tid] : -INFINITY;
-    wsl.finState[b * kBeamMax + tid] = live ? sSt[cur][tid] : 0;
-    wsl.finAcc[b * kBeamMax + tid] = live ? sAcc[cur][tid] : -INFINITY;
-    if (tid == 0) ws.finN[b] = n;
-  }
+  beam_store_final(ws, b, n, sNode[cur], sTot[cur], sSt[cur], sAcc[cur], nullptr);
 }
 
-__global__ __launch_bounds__(64) void ctc_beam_lm_finish(int M, int Lmax, int eosWord, CtcBeamLmWs wsl, const void* __restrict__ lm,
+__global__ __launch_bounds__(64) void ctc_beam_lm_finish(int M, int Lmax, int eosWord, CtcBeamWs ws, const void* __restrict__ lm,
                                                          float lmWeight, float eosScore, int useEos, int* __restrict__ labels,
                                                          int* __restrict__ lengths, float* __restrict__ scores,
                                                          float* __restrict__ lmScores) {
-  typedef unsigned long long u64;
   __shared__ float sScore[64];
-  const CtcBeamWs& ws = wsl.b;
   const int b = blockIdx.x, r = threadIdx.x;
   const u64* tab = ws.table + (size_t)b * ws.cap;
   const int n = ws.finN[b];
@@ -217,36 +165,12 @@ __global__ __launch_bounds__(64) void ctc_beam_lm_finish(int M, int Lmax, int eo
   float score = -INFINITY, acc = -INFINITY;
   if (live) {
     score = ws.finTot[b * kBeamMax + r];
-    acc = wsl.finAcc[b * kBeamMax + r];
-    if (useEos) {
-      const NgramView lv = ngram_view(lm);
-      int unused;
-      const float qe = ngram_q(lv, wsl.finState[b * kBeamMax + r], eosWord, &unused);
-      score = score + ((lmWeight * qe) + eosScore);
-      acc = acc + qe;
-    }
+    acc = ws.finAcc[b * kBeamMax + r];
+    if (useEos) beam_eos(lm, ws.finState[b * kBeamMax + r], eosWord, lmWeight, eosScore, &score, &acc);
   }
-  sScore[r] = score;
-  __syncthreads();
-  int m = r;   // rows n .. M-1 are the empty ones: the ranks of the live entries are a permutation of 0 .. n-1
-  if (live) {
-    m = 0;
-    for (int o = 0; o < n; ++o) m += (sScore[o] > score || (sScore[o] == score && o < r)) ? 1 : 0;
-  }
+  const int m = beam_rerank(score, live, sScore);   // rows n .. M-1 are the empty ones
   if (m >= M) return;
-  int* lab = labels + ((size_t)b * M + m) * Lmax;
-  int len = 0;
-  if (live) {
-    const int node = ws.finNode[b * kBeamMax + r];
-    for (int p = node; p > 0; p = (int)(tab[p - 1] >> 32)) ++len;
-    int i = len - 1;
-    for (int p = node; p > 0; --i) {
-      const u64 edge = tab[p - 1];
-      if (i < Lmax) lab[i] = (int)(unsigned)edge - 1;
-      p = (int)(edge >> 32);
-    }
-  }
-  for (int i = min(len, Lmax); i < Lmax; ++i) lab[i] = -1;
+  const int len = beam_write_labels(tab, live, ws.finNode + b * kBeamMax + r, Lmax, labels + ((size_t)b * M + m) * Lmax);
   lengths[(size_t)b * M + m] = live ? len : -1;
   scores[(size_t)b * M + m] = score;
   lmScores[(size_t)b * M + m] = acc;
@@ -255,10 +179,7 @@ __global__ __launch_bounds__(64) void ctc_beam_lm_finish(int M, int Lmax, int eo
 }  // namespace w2l
 
 W2L_API size_t w2l_ctc_beam_lm_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
-  const int K = w2l::ctc_beam_clip(N, beamToken);
-  if (beam > w2l::kBeamMax || K > w2l::kBeamMax) return 0;
-  return w2l::ctc_beam_lm_layout(nullptr, nullptr, B, T, beam, K);
+  return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm);
 }
 
 W2L_API int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
@@ -266,31 +187,19 @@ W2L_API int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input, cons
                                    float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
                                    float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
   using namespace w2l;
-  if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !lmScores || !workspace || !lm) return W2L_EINVAL;
-  if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
-  if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
+  if (!lmScores || !lm) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  const int K = ctc_beam_clip(N, beamToken);
-  if (beam > kBeamMax || K > kBeamMax) return W2L_EUNSUPPORTED;
-  if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;   // node ids are ints
+  int K = 0;
+  if (const int rc = ctc_beam_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
-  CtcBeamLmWs ws{};
-  ctc_beam_lm_layout(&ws, workspace, B, T, beam, K);
-  W2L_HIP_CHECK(hipMemsetAsync(ws.b.table, 0, (size_t)B * ws.b.cap * sizeof(unsigned long long), s));
-  const unsigned rows = (unsigned)((size_t)B * T);
-  if (N <= kRowThreads * kRowMaxPer)
-    hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ws.b);
-  else
-    hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ws.b);
-  W2L_LAUNCH_CHECK();
-  const bool wide = beam * K > 256 * kLmPer;
-#define W2L_LM_SCAN(LA, TH)                                                                                                   \
-  hipLaunchKernelGGL((ctc_beam_lm_scan<LA, TH>), dim3((unsigned)B), dim3(TH), 0, s, T, N, beam, threshold, input, frames, ws, lm, \
-                     lmWeight, classScore)
-  if (logAdd) { if (wide) W2L_LM_SCAN(true, 1024); else W2L_LM_SCAN(true, 256); }
-  else { if (wide) W2L_LM_SCAN(false, 1024); else W2L_LM_SCAN(false, 256); }
-#undef W2L_LM_SCAN
+  CtcBeamWs ws{};
+  if (const int rc = ctc_beam_begin(&ws, kBeamLm, B, T, N, input, frames, beam, K, normalize, workspace, s)) return rc;
+  ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
+    hipLaunchKernelGGL((ctc_beam_lm_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)B), dim3(decltype(th)::value), 0, s,
+                       T, N, beam, threshold, input, frames, ws, lm, lmWeight, classScore);
+  });
   W2L_LAUNCH_CHECK();
   hipLaunchKernelGGL(ctc_beam_lm_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, N, ws, lm, lmWeight, eosScore,
                      lmHasEos ? 1 : 0, labels, lengths, scores, lmScores);
