@@ -519,6 +519,40 @@ FL_COMPAT_API void setMixedPrecision(const std::shared_ptr<fl::Module>& network,
 FL_COMPAT_API uint32_t networkStep(const std::shared_ptr<fl::Module>& network);
 FL_COMPAT_API void setNetworkStep(const std::shared_ptr<fl::Module>& network, uint32_t step);
 
+class NGramLM;   // fl_compat/lm.h
+class Lexicon;   // fl_compat/lexicon.h
+
+// The options and the result of CTCLoss::beamSearch and ASGLoss::beamSearch (fl_compat ADDITIONS to the reference's interface).
+// "token classes" below are N-1 for CTC (blank = N-1 is none) and all N for ASG.
+struct BeamSearchOptions {
+  int beamSize = 64;                  // W, 1..64
+  int beamSizeToken = 64;             // K, clipped to the token classes (CTC: N-1, ASG: N), then <= 64
+  float beamThreshold = 1.0f / 0.0f;  // candidates below best - threshold are dropped; +inf: none
+  bool logAdd = false;                // false: max over a prefix's alignments (the 1-best is the greedy transcript); true: their sum
+  int normalize = -1;                 // 1: search on log-softmax rows, 0: on the raw emissions, -1: CTC as logAdd, ASG 0
+  int nbest = 1;                      // M, 1..W
+  int maxLen = 0;                     // Lmax, 0 = T (no hypothesis is longer)
+  // the search fused with a token-level n-gram LM (w2l_ctc_beam_search_lm); the defaults mean "no LM", and without lm the
+  // other three must keep them.  lm: a table over the N-1 token classes (fl_compat/lm.h), alive during the call.
+  const NGramLM* lm = nullptr;
+  float lmWeight = 0.f;               // every extension by token c adds lmWeight * log p_LM(c | prefix) + classScore[c]
+  af::array classScore;               // (N-1) f32 on the device, or empty
+  float eosScore = 0.f;               // the end adds lmWeight * log p_LM(EOS | hypothesis) + eosScore; 0 for a model without EOS
+  // the search restricted to the spellings of a lexicon (w2l_ctc_beam_search_lex); lm is required then and is a table over the
+  // lexicon's WORDS (NGramLM::fromArpa(path, lexicon.words())), classScore must be empty.  lexicon: fl_compat/lexicon.h, alive
+  // during the call.  Without lexicon the other two must keep their defaults.
+  const Lexicon* lexicon = nullptr;
+  float wordScore = 0.f;              // every completed word adds lmWeight * log p_LM(word | words before) + wordScore
+  int maxWords = 0;                   // rows of `words`, 0 = Lmax
+};
+struct BeamSearchResult {
+  af::array labels;    // (Lmax, M, B) s32: the first min(length, Lmax) labels, -1 beyond
+  af::array lengths;   // (M, B) s32: the true label count; -1 for a rank that does not exist
+  af::array scores;    // (M, B) f32; -inf for a rank that does not exist
+  af::array lmScores;  // (M, B) f32 with an LM: the hypotheses' unweighted LM scores (-inf for a rank that does not exist); else empty
+  af::array words;       // (maxWords, M, B) s32 with a lexicon: the first min(count, maxWords) word ids, -1 beyond; else empty
+  af::array wordCounts;  // (M, B) s32 with a lexicon: the true word count; -1 for a rank that does not exist; else empty
+};
 class FL_COMPAT_API ASGLoss : public SequenceCriterion {
  public:
   ASGLoss(int N, CriterionScaleMode scalemode = CriterionScaleMode::NONE, double transdiag = 0.0);
@@ -526,6 +560,11 @@ class FL_COMPAT_API ASGLoss : public SequenceCriterion {
   af::array viterbiPath(const af::array& input, const af::array& inputSize = af::array()) override;
   af::array viterbiPathWithTarget(const af::array& input, const af::array& target, const af::array& inputSizes = af::array(),
                                   const af::array& targetSizes = af::array()) override;
+  // fl_compat ADDITION: n-best beam search of the ASG lattice under this criterion's own transitions, param(0)
+  // (w2l_asg_beam_search, w2l_asg_beam_search_lex; the contract is in w2l_hip.h): no blank, all N classes are tokens -- an LM, a
+  // lexicon and classScore are over N classes --, a token never follows itself (replabels spell a repeated letter:
+  // Lexicon::fromFile(..., replabel)).  Options, result, inputSizes and exceptions as CTCLoss::beamSearch; normalize -1 means 0.
+  BeamSearchResult beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& options);
   std::string prettyString() const override;
   Variable transitions() const { return params_[0]; }   // (N, N), [to][from]
   CriterionScaleMode scaleMode() const { return scaleMode_; }
@@ -534,9 +573,6 @@ class FL_COMPAT_API ASGLoss : public SequenceCriterion {
   int N_;
   CriterionScaleMode scaleMode_;
 };
-
-class NGramLM;   // fl_compat/lm.h
-class Lexicon;   // fl_compat/lexicon.h
 
 class FL_COMPAT_API CTCLoss : public SequenceCriterion {
  public:
@@ -554,35 +590,8 @@ class FL_COMPAT_API CTCLoss : public SequenceCriterion {
   // viterbiPathWithTarget.  The hypotheses are already collapsed label rows: turn them into letters / words with tknLabels2Ltr /
   // tknLabels2Wrd (fl_compat/text.h), not with tknPrediction2Ltr.  Refused arguments: std::invalid_argument; a beam or token
   // count beyond the kernel's 64: std::runtime_error.
-  struct BeamSearchOptions {
-    int beamSize = 64;                  // W, 1..64
-    int beamSizeToken = 64;             // K, clipped to N-1, then <= 64
-    float beamThreshold = 1.0f / 0.0f;  // candidates below best - threshold are dropped; +inf: none
-    bool logAdd = false;                // false: max over a prefix's alignments (the 1-best is the greedy transcript); true: their sum
-    int normalize = -1;                 // 1: search on log-softmax rows, 0: on the raw emissions, -1: as logAdd
-    int nbest = 1;                      // M, 1..W
-    int maxLen = 0;                     // Lmax, 0 = T (no hypothesis is longer)
-    // the search fused with a token-level n-gram LM (w2l_ctc_beam_search_lm); the defaults mean "no LM", and without lm the
-    // other three must keep them.  lm: a table over the N-1 token classes (fl_compat/lm.h), alive during the call.
-    const NGramLM* lm = nullptr;
-    float lmWeight = 0.f;               // every extension by token c adds lmWeight * log p_LM(c | prefix) + classScore[c]
-    af::array classScore;               // (N-1) f32 on the device, or empty
-    float eosScore = 0.f;               // the end adds lmWeight * log p_LM(EOS | hypothesis) + eosScore; 0 for a model without EOS
-    // the search restricted to the spellings of a lexicon (w2l_ctc_beam_search_lex); lm is required then and is a table over the
-    // lexicon's WORDS (NGramLM::fromArpa(path, lexicon.words())), classScore must be empty.  lexicon: fl_compat/lexicon.h, alive
-    // during the call.  Without lexicon the other two must keep their defaults.
-    const Lexicon* lexicon = nullptr;
-    float wordScore = 0.f;              // every completed word adds lmWeight * log p_LM(word | words before) + wordScore
-    int maxWords = 0;                   // rows of `words`, 0 = Lmax
-  };
-  struct BeamSearchResult {
-    af::array labels;    // (Lmax, M, B) s32: the first min(length, Lmax) labels, -1 beyond
-    af::array lengths;   // (M, B) s32: the true label count; -1 for a rank that does not exist
-    af::array scores;    // (M, B) f32; -inf for a rank that does not exist
-    af::array lmScores;  // (M, B) f32 with an LM: the hypotheses' unweighted LM scores (-inf for a rank that does not exist); else empty
-    af::array words;       // (maxWords, M, B) s32 with a lexicon: the first min(count, maxWords) word ids, -1 beyond; else empty
-    af::array wordCounts;  // (M, B) s32 with a lexicon: the true word count; -1 for a rank that does not exist; else empty
-  };
+  using BeamSearchOptions = ::fl::pkg::speech::BeamSearchOptions;   // hoisted: ASGLoss::beamSearch takes the same
+  using BeamSearchResult = ::fl::pkg::speech::BeamSearchResult;
   BeamSearchResult beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& options);
   std::string prettyString() const override;
   CriterionScaleMode scaleMode() const { return scaleMode_; }

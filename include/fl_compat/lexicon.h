@@ -18,6 +18,7 @@
 #include "../w2l_hip.h"
 #include "flashlight.h"
 #include "lm.h"
+#include "text.h"
 
 namespace fl {
 namespace pkg {
@@ -66,10 +67,17 @@ class Lexicon {
   // a lexicon file (`word tok tok ...`, every spelling of a word a line) over the token dictionary's entries (without blank).  Rows
   // go word by word in the order the words first appear, a word's spellings in file order.  sil: the spelling of the silence token
   // or empty.  smearing "max": wordSmear[w] = q(start, w) of lm (a LM over words(), or null: no smearing); "none": no smearing.
+  // replabel > 0 (an ASG model's --replabel): every spelling is packed with packReplabels before the trie is built -- `h e l l o`
+  // becomes `h e l <1> o` -- and the tokens `<1>` .. `<replabel>` must be among `tokens`.
   static Lexicon fromFile(const std::string& path, const std::vector<std::string>& tokens, const NGramLM* lm = nullptr,
-                          const std::string& sil = "", const std::string& smearing = "max") {
+                          const std::string& sil = "", const std::string& smearing = "max", int replabel = 0) {
     if (smearing != "max" && smearing != "none")
       throw std::invalid_argument("Lexicon::fromFile: smearing '" + smearing + "' is not built: `max` or `none`");
+    const lib::text::Dictionary dict = replabel > 0 ? lib::text::Dictionary(tokens) : lib::text::Dictionary();
+    for (int r = 1; r <= replabel; ++r)
+      if (!dict.contains(replabelToken(r)))
+        throw std::invalid_argument("Lexicon::fromFile: replabel=" + std::to_string(replabel) + " needs the token `" +
+                                    replabelToken(r) + "` in the token dictionary");
     std::ifstream f(path);
     if (!f) throw std::invalid_argument("Lexicon::fromFile: cannot read " + path);
     std::unordered_map<std::string, int> tokenId, seen;
@@ -89,6 +97,7 @@ class Lexicon {
         sp.push_back(it->second);
       }
       if (sp.empty()) continue;
+      sp = packReplabels(sp, dict, replabel);
       auto at = seen.emplace(word, (int)order.size());
       if (at.second) { order.push_back(word); spellings.emplace_back(); }
       spellings[(size_t)at.first->second].push_back(sp);

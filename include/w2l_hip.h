@@ -325,6 +325,48 @@ int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input /*[B][T][N]*
                             int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
                             float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/, int* wordCounts /*[B][M]*/,
                             void* workspace, w2l_stream_t stream);
+/* Beam search of an ASG model: w2l_asg_beam_search is lexicon-free with an optional token LM (the arguments of
+ * w2l_ctc_beam_search_lm), w2l_asg_beam_search_lex uses a lexicon trie, a word LM and max smearing (the arguments of
+ * w2l_ctc_beam_search_lex); both take trans, the criterion's transition matrix A [N][N], to x from, on the device.  The contract is
+ * the CTC family's -- frame tokens, (+), threshold, W, M, order, tie key, output rows, frames, one prefix or hypothesis one entry --
+ * with these changes:
+ *   Classes.  There is no blank: all N classes are tokens.  K is clipped to N; an LM blob is over N tokens (EOS is word N + 1), a
+ *     lexicon over N tokens; classScore is [N].
+ *   State.  An entry has one value p and its last label e.  The beam starts as the empty prefix with p = 0.
+ *   stay(r): p' = (p + A[e][e]) + lp[e]: two fp32 adds in this order, w2l_viterbi_compute's, so scores compare bit for bit; lp[e] is
+ *     read from the row whether or not e is a frame token.  The empty prefix has no stay (-inf).
+ *   ext(r, k), frame token c:  c == e: no candidates (ASG emits a repeated letter through a replabel).  From the empty prefix
+ *     a = lp[c], no add and no transition.  Otherwise a = (p + A[c][e]) + lp[c].  The siblings' terms are then added to a in their
+ *     order: p' = a + g with a token LM (g as in w2l_ctc_beam_search_lm); in the lexicon search the sil / in / word slots of
+ *     w2l_ctc_beam_search_lex with (lp[c] + base) replaced by a.  The transition term is there from an entry's second label on,
+ *     which under threshold pruning is not "from frame 1 on"; this is the rule that equals Viterbi.
+ *   lm == NULL (w2l_asg_beam_search only): no LM.  No g term is added, lmScores rows are 0 for live rows and -inf for empty ones,
+ *     lmHasEos must be 0 and classScore NULL.
+ *   Lexicon.  The c == e rule holds for all three slots.  So a word whose spelling (as packed with replabels) needs one token
+ *     twice in a row is unreachable, and a word that starts with the token the previous word ended on needs silence between the
+ *     two.  Neither is refused.
+ *   Merge, prune, order, end (root only, EOS term, re-rank) and outputs are the siblings'.
+ * Consequences: with trans = 0 and normalize = 0, labels, lengths and scores equal the CTC sibling's on the same emissions with a
+ * column of -inf appended as blank, bit for bit in both logAdd modes; with logAdd = 0, no LM and a beam that never cuts, the
+ * 1-best is w2l_viterbi_compute's path collapsed over runs and its score, accumulated in the recursion's order.
+ * With logAdd = 0 the result is reproducible bit for bit, ties included (same exception for the sign of a zero).
+ * Limits and refusals: the siblings' (N >= 2 kept for uniformity), and trans NULL (W2L_EINVAL), all before anything touches the
+ * device.  trans, like lm, lexicon and classScore, is device memory and NOT checked. */
+size_t w2l_asg_beam_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                        const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/, float threshold,
+                        int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm /*or NULL*/, int lmHasEos,
+                        float lmWeight, const float* classScore /*[N] or NULL*/, float eosScore,
+                        int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                        float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream);
+size_t w2l_asg_beam_lex_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_lex(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                            const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/, float threshold,
+                            int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos,
+                            float lmWeight, const void* lexicon, float wordScore, float eosScore,
+                            int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                            float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/, int* wordCounts /*[B][M]*/,
+                            void* workspace, w2l_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the

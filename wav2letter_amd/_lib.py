@@ -120,6 +120,11 @@ class _SIGS:
     w2l_lexicon_info = (_i, [_p, _p, _p, _p, _p, _p])
     w2l_lexicon_child = (_i, [_p, _i, _i, _p])
     w2l_lexicon_node = (_i, [_p, _i, _p, _p, _p, _p])
+    w2l_asg_beam_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_asg_beam_search = (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _p, _p, _p, _p, _p, _p])
+    w2l_asg_beam_lex_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_asg_beam_search_lex = (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p, _i,
+                                    _p, _p, _p, _p])
     w2l_ctc_beam_lex_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_ctc_beam_search_lex = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p, _i, _p, _p,
                                     _p, _p])

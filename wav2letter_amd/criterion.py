@@ -398,6 +398,87 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     return labels, lengths, scores
 
 
+def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=False,
+                    nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
+                    max_words=None):
+    """Beam search of an ASG model (w2l_asg_beam_search, w2l_asg_beam_search_lex; the contract is in include/w2l_hip.h):
+    `emission` [B][T][N], every class a token (no blank), `transitions` [N][N] float32 (to x from) on the emissions' device.  The
+    options and the return values are ctc_beam_search's -- (labels, lengths, scores), lm_scores with an LM, words and word_counts
+    with a lexicon -- with beam_token clipped to N, an LM (or lexicon) over N tokens and class_score [N].  normalize defaults to
+    False in both log_add modes: ASG scores are unnormalised by design.  A token never follows itself: a repeated letter is a
+    replabel's (Lexicon.from_file(..., replabel=) packs the spellings)."""
+    _emission_checks(emission)
+    B, T, N = emission.shape
+    if transitions.dtype != torch.float32 or tuple(transitions.shape) != (N, N):
+        raise _lib.W2LInvalidArgument(f"asg_beam_search: transitions must be float32 [{N}][{N}]")
+    if lexicon is not None:
+        if lm is None:
+            raise _lib.W2LInvalidArgument("asg_beam_search: lexicon needs lm, a model over the lexicon's words")
+        if class_score is not None:
+            raise _lib.W2LInvalidArgument("asg_beam_search: class_score must be None with a lexicon (word_score is the per-word term)")
+        if lm.num_tokens != lexicon.num_words:
+            raise _lib.W2LInvalidArgument(f"asg_beam_search: the LM has {lm.num_tokens} words, the lexicon {lexicon.num_words}")
+        if lexicon.num_tokens != N:
+            raise _lib.W2LInvalidArgument(f"asg_beam_search: the lexicon has {lexicon.num_tokens} tokens, the emissions {N}")
+        if max_words is not None and int(max_words) < 1:
+            raise _lib.W2LInvalidArgument("asg_beam_search: max_words must be at least 1")
+    elif word_score != 0.0 or max_words is not None:
+        raise _lib.W2LInvalidArgument("asg_beam_search: word_score and max_words need lexicon")
+    elif lm is None:
+        if lm_weight != 0.0 or class_score is not None or eos_score != 0.0:
+            raise _lib.W2LInvalidArgument("asg_beam_search: lm_weight, class_score and eos_score need lm")
+    else:
+        if lm.num_tokens != N:
+            raise _lib.W2LInvalidArgument(f"asg_beam_search: the LM has {lm.num_tokens} tokens, the emissions {N}")
+        if class_score is not None and (class_score.dtype != torch.float32 or class_score.numel() != N):
+            raise _lib.W2LInvalidArgument("asg_beam_search: class_score must be float32 with one entry per class")
+    if lm is not None and not lm.has_eos and eos_score != 0.0:
+        raise _lib.W2LInvalidArgument("asg_beam_search: eos_score needs a model with EOS")
+    _check_dev(emission, transitions)
+    L = _lib.lib()
+    emission = emission.detach().contiguous()
+    transitions = transitions.detach().contiguous()
+    if frames is not None:
+        if frames.dtype != torch.int32 or frames.numel() != B:
+            raise _lib.W2LInvalidArgument("asg_beam_search: frames must be int32 with one entry per utterance")
+        _check_dev(emission, frames)
+        frames = frames.contiguous()
+    fr = frames.data_ptr() if frames is not None else None
+    max_len = T if max_len is None else int(max_len)
+    nbest = int(nbest)
+    shape = (B, max(nbest, 1))
+    dev = emission.device
+    labels = torch.empty(*shape, max(max_len, 1), dtype=torch.int32, device=dev)
+    lengths = torch.empty(*shape, dtype=torch.int32, device=dev)
+    scores = torch.empty(*shape, dtype=torch.float32, device=dev)
+    lm_scores = torch.empty(*shape, dtype=torch.float32, device=dev)
+    if lexicon is not None:
+        max_words = max(max_len, 1) if max_words is None else int(max_words)
+        ws = _ws(L.w2l_asg_beam_lex_workspace_size(B, T, N, int(beam), int(beam_token)), dev)
+        words = torch.empty(*shape, max_words, dtype=torch.int32, device=dev)
+        word_counts = torch.empty(*shape, dtype=torch.int32, device=dev)
+        blob, lex_blob = lm.device_blob(dev), lexicon.device_blob(dev)
+        _lib.check(L.w2l_asg_beam_search_lex(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
+                                             float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
+                                             blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
+                                             float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),
+                                             scores.data_ptr(), lm_scores.data_ptr(), max_words, words.data_ptr(),
+                                             word_counts.data_ptr(), ws.data_ptr(), _stream()), "asg_beam_search")
+        return labels, lengths, scores, lm_scores, words, word_counts
+    if class_score is not None:
+        _check_dev(emission, class_score)
+        class_score = class_score.contiguous()
+    blob = lm.device_blob(dev) if lm is not None else None
+    ws = _ws(L.w2l_asg_beam_workspace_size(B, T, N, int(beam), int(beam_token)), dev)
+    _lib.check(L.w2l_asg_beam_search(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
+                                     float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
+                                     blob.data_ptr() if blob is not None else None, int(lm.has_eos) if lm is not None else 0,
+                                     float(lm_weight), class_score.data_ptr() if class_score is not None else None,
+                                     float(eos_score), labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(),
+                                     lm_scores.data_ptr(), ws.data_ptr(), _stream()), "asg_beam_search")
+    return (labels, lengths, scores, lm_scores) if lm is not None else (labels, lengths, scores)
+
+
 class SequenceCriterion(torch.nn.Module):
     """fl::pkg::speech::SequenceCriterion: forward({emission,target}) -> {loss[B]},
     viterbiPath(emission) -> [B][T] int32."""
@@ -489,6 +570,10 @@ class ASGLoss(SequenceCriterion):
 
     def viterbiPathWithTarget(self, emission, target):
         return self.fac.viterbiPath(emission, target)
+
+    def beamSearch(self, emission, frames=None, **options):
+        """n-best beam search over the emissions under this criterion's transitions (asg_beam_search's options)"""
+        return asg_beam_search(emission, self.transitions, frames, **options)
 
     def prettyString(self):
         return "AutoSegmentationCriterion"

@@ -23,7 +23,8 @@
 //                  that frame.
 // Algorithmic HBM bytes: 4BTN (fwd) + 8BTN (bwd) = 12*B*T*N.
 // w2l_ctc_align (forced alignment: the best lattice path of a known transcript) lives in criterion_ctc_align.hpp, included below.
-// w2l_ctc_beam_search (lexicon-free n-best prefix beam search) lives in criterion_ctc_beam.hpp, included below.
+// w2l_ctc_beam_search (lexicon-free n-best prefix beam search) lives in criterion_ctc_beam.hpp, included below with its siblings;
+// the beam searches of the ASG lattice (criterion_asg_beam.hpp) come last, on the same helpers and scans.
 // w2l_ctc_score (evaluation: loss and greedy path, no gradient) reads the emissions once, 4BTN:
 //   ctc_rows_score  the ctc_rows_lse pass (same arithmetic, template flag) that also writes the first-max argmax of the row
 //   ctc_scan_score  the alpha wave alone, grid (B, 1), lattice rows kept in registers: only the loss is written
@@ -895,3 +896,4 @@ W2L_API int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, 
 #include "criterion_ctc_beam.hpp"
 #include "criterion_ctc_beam_lm.hpp"
 #include "criterion_ctc_beam_lex.hpp"
+#include "criterion_asg_beam.hpp"

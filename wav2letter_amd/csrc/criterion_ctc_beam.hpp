@@ -22,6 +22,8 @@
 // (beam_node); for the workgroup scans of criterion_ctc_beam_lm.hpp and criterion_ctc_beam_lex.hpp beam_load_frame, beam_stay_front,
 // beam_select_round and beam_store_final; for the finishes beam_chain_len, beam_write_labels, beam_eos and beam_rerank; for the
 // entry points ctc_beam_check, ctc_beam_begin and ctc_beam_fused_scan.  The other two files keep what is particular to their search.
+// What the lattice is -- the acoustic sum of a stay and of an extension -- is a policy of the two workgroup scans: BeamCtc here,
+// BeamAsg in criterion_asg_beam.hpp (no blank, a transition matrix, no token after itself), which also uses ctc_beam_rows<., true>.
 // The LM-free search itself uses neither the LM table (ngram_lm.hpp is here for beam_eos) nor kLmPer (the workgroup scans').
 #pragma once
 #include "ngram_lm.hpp"
@@ -109,7 +111,8 @@ __device__ __forceinline__ u64 block_max_u64(u64 v, u64* sm) {
   return r;
 }
 
-template <bool kBig>
+// kNoBlank (the ASG searches of criterion_asg_beam.hpp): every class is a token, K may reach N, lpb is -inf
+template <bool kBig, bool kNoBlank = false>
 __global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int normalize,
                                                              const float* __restrict__ x,
                                                              const int* __restrict__ frames, CtcBeamWs ws) {
@@ -123,7 +126,7 @@ __global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int n
   const int b = (int)(r / T);
   if ((int)(r - (size_t)b * T) >= align_frames(frames, b, T)) return;
   const float* row = x + r * N;
-  const int tid = threadIdx.x, K = ws.K, blank = N - 1;
+  const int tid = threadIdx.x, K = ws.K, blank = kNoBlank ? -1 : N - 1;
 
   // the row in registers, every load issued before the first use (ctc_rows_lse_body's loader)
   constexpr int kPer = kBig ? 1 : kRowMaxPer / 4;
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int n
     sTau = 1;   // fewer than K threads own a token: every token is a candidate
     sCnt = 0;
     ws.lse[r] = lse;
-    ws.lpb[r] = row[blank] - lse;
+    ws.lpb[r] = kNoBlank ? -INFINITY : row[max(blank, 0)] - lse;
   }
   __syncthreads();
   int rank = 0;
@@ -387,12 +390,32 @@ __device__ __forceinline__ void beam_load_frame(const CtcBeamWs& ws, size_t row,
 
 // The front of stay(j), j = threadIdx.x < n, from the current beam (the arrays of this frame's half): pb' = lp[blank] + tot, pnb' =
 // lp[e] + pnb before any merge, and the extension that spells entry j, if the frame has it: ext(pr, kj) with pr the rank of the
-// parent prefix and kj the frame token equal to the last label e; its total starts from `base`, pb of the parent when the parent
-// ends in e too, else its tot.  The search computes that one total its own way, adds it to spnb and marks the extension gone.
-struct BeamStay { int e, kj, pr; bool merge; float spb, spnb, base; };   // merge: the frame has ext(pr, kj)
-__device__ __forceinline__ BeamStay beam_stay_front(int n, int K, const int* sTc, const int* sNode, const int* sPar, const int* sE,
-                                                    const float* sPb, const float* sPnb, const float* sTot, const float* xrow,
-                                                    float lpb, float lse) {
+// parent prefix and kj the frame token equal to the last label e; its total starts from the acoustic sum `a` (CTC: lp[e] + pb of the
+// parent when the parent ends in e too, else + its tot).  The search adds its own terms to a, adds that to spnb and marks the
+// extension gone.
+// The policy Pol says what the lattice is: BeamCtc below; BeamAsg (criterion_asg_beam.hpp) has no blank and a transition matrix A.
+struct BeamTrans { const float* a; int lds; };   // A [N][N], to x from; lds: stage it in LDS.  BeamCtc: all 0
+struct BeamCtc {
+  static constexpr bool kNoBlank = false;
+  __device__ static __forceinline__ const float* stage(const BeamTrans&, int) { return nullptr; }
+  __device__ static __forceinline__ bool none(int, int) { return false; }   // has (token c, entry ending in e) no candidates?
+  // the acoustic sum of the extension by c of an entry (e, pb, tot)
+  __device__ static __forceinline__ float ext(float lpc, int c, int e, float pb, float tot, const float*, int) {
+    return lpc + (c == e ? pb : tot);
+  }
+  __device__ static __forceinline__ void stay(float lpe, int e, float lpb, float pnb, float tot, const float*, int, float* spb,
+                                              float* spnb) {
+    *spb = lpb + tot;
+    *spnb = e >= 0 ? lpe + pnb : -INFINITY;
+  }
+};
+
+struct BeamStay { int e, kj, pr; bool merge; float spb, spnb, a; };   // merge: the frame has ext(pr, kj); a: its acoustic sum
+template <class Pol = BeamCtc>
+__device__ __forceinline__ BeamStay beam_stay_front(int n, int K, const int* sTc, const float* sTl, const int* sNode,
+                                                    const int* sPar, const int* sE, const float* sPb, const float* sPnb,
+                                                    const float* sTot, const float* xrow, float lpb, float lse,
+                                                    const float* A = nullptr, int N = 0) {
   const int j = threadIdx.x;
   BeamStay s;
   s.e = sE[j];
@@ -400,12 +423,11 @@ __device__ __forceinline__ BeamStay beam_stay_front(int n, int K, const int* sTc
   s.kj = -1; s.pr = -1;
   for (int k = 0; k < K; ++k) s.kj = sTc[k] == s.e ? k : s.kj;
   for (int r = 0; r < n; ++r) s.pr = sNode[r] == par ? r : s.pr;
-  s.spb = lpb + sTot[j];
-  s.spnb = -INFINITY;
-  if (s.e >= 0) s.spnb = (xrow[s.e] - lse) + sPnb[j];   // lp[e] comes from the row whether or not e is a frame token
+  // lp[e] comes from the row whether or not e is a frame token
+  Pol::stay(s.e >= 0 ? xrow[s.e] - lse : 0.f, s.e, lpb, sPnb[j], sTot[j], A, N, &s.spb, &s.spnb);
   s.merge = s.pr >= 0 && s.kj >= 0;
-  s.base = 0.f;
-  if (s.merge) s.base = s.e == sE[s.pr] ? sPb[s.pr] : sTot[s.pr];
+  s.a = 0.f;
+  if (s.merge) s.a = Pol::ext(sTl[s.kj], s.e, sE[s.pr], sPb[s.pr], sTot[s.pr], A, N);
   return s;
 }
 
@@ -508,11 +530,12 @@ __global__ __launch_bounds__(64) void ctc_beam_finish(int M, int Lmax, CtcBeamWs
   scores[(size_t)b * M + m] = live ? ws.finTot[b * kBeamMax + m] : -INFINITY;
 }
 
-static int ctc_beam_clip(int N, int beamToken) { return beamToken < N - 1 ? beamToken : N - 1; }
+// tokens = the classes that are tokens: N - 1 with a blank, N without (noBlank)
+static int ctc_beam_clip(int tokens, int beamToken) { return beamToken < tokens ? beamToken : tokens; }
 
-static size_t ctc_beam_workspace_size(int B, int T, int N, int beam, int beamToken, int variant) {
+static size_t ctc_beam_workspace_size(int B, int T, int N, int beam, int beamToken, int variant, bool noBlank = false) {
   if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
-  const int K = ctc_beam_clip(N, beamToken);
+  const int K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
   if (beam > kBeamMax || K > kBeamMax) return 0;
   return ctc_beam_layout(nullptr, nullptr, B, T, beam, K, variant);
 }
@@ -520,11 +543,12 @@ static size_t ctc_beam_workspace_size(int B, int T, int N, int beam, int beamTok
 // the arguments the three searches share; *K = the clipped beamToken.  Every W2L_EINVAL comes before W2L_EUNSUPPORTED, and a
 // search's own checks (all W2L_EINVAL) run before this one, so the code for a bad argument does not depend on which one is first.
 static int ctc_beam_check(int B, int T, int N, const float* input, int beam, int beamToken, float threshold, int nbest, int maxLen,
-                          const int* labels, const int* lengths, const float* scores, const void* workspace, int* K) {
+                          const int* labels, const int* lengths, const float* scores, const void* workspace, int* K,
+                          bool noBlank = false) {
   if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !workspace) return W2L_EINVAL;
   if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
   if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
-  *K = ctc_beam_clip(N, beamToken);
+  *K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
   if (beam > kBeamMax || *K > kBeamMax) return W2L_EUNSUPPORTED;
   if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;   // node ids are ints
   return W2L_OK;
@@ -532,11 +556,16 @@ static int ctc_beam_check(int B, int T, int N, const float* input, int beam, int
 
 // the start of a call: the workspace, an empty prefix table, the frame tokens of every row
 static int ctc_beam_begin(CtcBeamWs* ws, int variant, int B, int T, int N, const float* input, const int* frames, int beam, int K,
-                          int normalize, void* workspace, hipStream_t s) {
+                          int normalize, void* workspace, hipStream_t s, bool noBlank = false) {
   ctc_beam_layout(ws, workspace, B, T, beam, K, variant);
   W2L_HIP_CHECK(hipMemsetAsync(ws->table, 0, (size_t)B * ws->cap * sizeof(u64), s));
   const unsigned rows = (unsigned)((size_t)B * T);
-  if (N <= kRowThreads * kRowMaxPer)
+  const bool big = N > kRowThreads * kRowMaxPer;
+  if (noBlank && big)
+    hipLaunchKernelGGL((ctc_beam_rows<true, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);
+  else if (noBlank)
+    hipLaunchKernelGGL((ctc_beam_rows<false, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);
+  else if (!big)
     hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);
   else
     hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);

@@ -6,6 +6,7 @@
 // front of a stay, selection round, final store; chain length, end-of-sentence term, re-rank).  This file keeps what is particular
 // to the lexicon: the totals of its candidates (beam_lex_a, beam_lex_word), a pair's best-of-seven with its consumed mask
 // (beam_lex_best), the two passes of a frame, and the finish's walk that rebuilds tokens and words from labels and node records.
+// The lattice is a policy (BeamCtc, the default; BeamAsg of criterion_asg_beam.hpp).
 //   ctc_beam_lex_scan    one workgroup of 256 or 1024 threads per utterance.  A hypothesis is a node of the prefix table whose edge
 //                        label is (lexicon node reached by the token << 3) | slot -- slot 0: the token moves into the lexicon trie
 //                        (or is the silence loop at the root, lexicon node 0), slot 1 + i: it completes word i of that node -- so
@@ -25,10 +26,10 @@
 
 namespace w2l {
 
-// a = (lp[c] + base) + (lmWeight * (smear[v] - su)); a completed word: a + ((lmWeight * (q - smear[v])) + wordScore); one fp32
-// operation each, in this order
-__device__ __forceinline__ float beam_lex_a(float lpc, float base, float lmWeight, float smv, float su) {
-  return (lpc + base) + (lmWeight * (smv - su));
+// a = a0 + (lmWeight * (smear[v] - su)), a0 the policy's acoustic sum (CTC: lp[c] + base); a completed word:
+// a + ((lmWeight * (q - smear[v])) + wordScore); one fp32 operation each, in this order
+__device__ __forceinline__ float beam_lex_a(float a0, float lmWeight, float smv, float su) {
+  return a0 + (lmWeight * (smv - su));
 }
 __device__ __forceinline__ float beam_lex_word(float a, float lmWeight, float q, float smv, float wordScore) {
   return a + ((lmWeight * (q - smv)) + wordScore);
@@ -57,11 +58,11 @@ __device__ __forceinline__ void beam_lex_best(const NgramView& lv, const LexView
   *key = best; *nst = bn; *lq = bq;
 }
 
-template <bool kLogAdd, int kThreads>
+template <bool kLogAdd, int kThreads, class Pol = BeamCtc>
 __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int W, float threshold, const float* __restrict__ x,
                                                               const int* __restrict__ frames, CtcBeamWs ws,
                                                               const void* __restrict__ lex, const void* __restrict__ lm,
-                                                              float lmWeight, float wordScore) {
+                                                              float lmWeight, float wordScore, BeamTrans tr) {
   constexpr int kWaves = kThreads / 64;
   // the beam of this frame and the next one: prefix-table node, parent's node, last token, the label of the last extension, lexicon
   // node, its smear (0 at the root), LM state, pb, pnb, tot, unweighted LM sum
@@ -79,6 +80,7 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
   const size_t row0 = (size_t)b * T;
   const NgramView lv = ngram_view(lm);
   const LexView xv = lex_view(lex);
+  const float* A = Pol::stage(tr, N);
 
   int cur = 0, n = 1;
   if (tid < 64) {
@@ -105,15 +107,16 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
       const int idx = tid + kThreads * i;
       if (idx < total) {
         const int r = idx / K, k = idx - r * K, c = sTc[k], u = sU[cur][r];
-        const float base = c == sE[cur][r] ? sPb[cur][r] : sTot[cur][r];
-        if (c == xv.silToken && u == 0) {
-          pv[i] = 0; pa[i] = sTl[k] + base; pmeta[i] = 8u;
+        const float a0 = Pol::ext(sTl[k], c, sE[cur][r], sPb[cur][r], sTot[cur][r], A, N);
+        if (Pol::none(c, sE[cur][r])) {   // no candidates
+        } else if (c == xv.silToken && u == 0) {
+          pv[i] = 0; pa[i] = a0; pmeta[i] = 8u;
         } else {
           const int v = lex_child(xv, u, c);
           if (v > 0) {
             const LexNode& nd = lex_node(xv, v);
             pv[i] = v; psm[i] = nd.smear; pmeta[i] = (unsigned)lex_nw(nd) | (lex_has_children(nd) ? 8u : 0u);
-            pa[i] = beam_lex_a(sTl[k], base, lmWeight, psm[i], sSu[cur][r]);
+            pa[i] = beam_lex_a(a0, lmWeight, psm[i], sSu[cur][r]);
           }
         }
       }
@@ -122,19 +125,19 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
     u64 stayKey = 0ull;
     float spb = -INFINITY, spnb = -INFINITY, stot = -INFINITY;
     if (tid < n) {
-      const BeamStay s = beam_stay_front(n, K, sTc, sNode[cur], sPar[cur], sE[cur], sPb[cur], sPnb[cur], sTot[cur],
-                                         xb + (size_t)t * N, lpb, lse);
+      const BeamStay s = beam_stay_front<Pol>(n, K, sTc, sTl, sNode[cur], sPar[cur], sE[cur], sPb[cur], sPnb[cur], sTot[cur],
+                                              xb + (size_t)t * N, lpb, lse, A, N);
       const int lab = sLab[cur][tid];
       spb = s.spb; spnb = s.spnb;
       if (s.merge && lab >= 0) {
         const int vj = lab >> 3, slot = lab & 7;
         float v;
         if (vj == 0) {
-          v = sTl[s.kj] + s.base;
+          v = s.a;
         } else {
           const LexNode& nd = lex_node(xv, vj);
           const float smv = nd.smear;
-          v = beam_lex_a(sTl[s.kj], s.base, lmWeight, smv, sSu[cur][s.pr]);
+          v = beam_lex_a(s.a, lmWeight, smv, sSu[cur][s.pr]);
           if (slot > 0) {
             int unused;
             const float qm = ngram_q(lv, sSt[cur][s.pr], nd.words[min(slot - 1, kLexMaxWords - 1)], &unused);
@@ -293,7 +296,7 @@ W2L_API int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input, con
   if (const int rc = ctc_beam_begin(&ws, kBeamLex, B, T, N, input, frames, beam, K, normalize, workspace, s)) return rc;
   ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
     hipLaunchKernelGGL((ctc_beam_lex_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)B), dim3(decltype(th)::value), 0, s,
-                       T, N, beam, threshold, input, frames, ws, lexicon, lm, lmWeight, wordScore);
+                       T, N, beam, threshold, input, frames, ws, lexicon, lm, lmWeight, wordScore, BeamTrans{});
   });
   W2L_LAUNCH_CHECK();
   hipLaunchKernelGGL(ctc_beam_lex_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, maxWords, ws, lexicon, lm, lmWeight,

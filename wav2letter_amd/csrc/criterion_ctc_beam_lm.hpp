@@ -4,6 +4,7 @@
 // and entry-point plumbing it reuses, and which owns the parts of a workgroup scan and of a finish that this search shares with the
 // lexicon search (frame load, front of a stay, selection round, final store; chain walk, end-of-sentence term, re-rank).  This file
 // keeps what is particular to the token LM: the total of an extension (beam_lm_ext) and the bookkeeping of all n * K of them.
+// The lattice is a policy (BeamCtc, the default; BeamAsg of criterion_asg_beam.hpp, which also runs this scan without an LM).
 //   ctc_beam_lm_scan    one workgroup of 256 or 1024 threads per utterance.  The LM term depends on (prefix, token), so lp_k + tot
 //                       + g is NOT monotone in k and the LM-free scan's lazy per-lane selection does not hold: every one of the
 //                       n * K extension totals of a frame is made.  Extension (r, k) belongs to thread (r K + k) mod threads, at
@@ -23,18 +24,20 @@
 
 namespace w2l {
 
-// pnb' of an extension: (lp[c] + base) + g, g = (lmWeight * q) + classScore[c]; one fp32 operation each, in this order
-__device__ __forceinline__ float beam_lm_ext(float lpc, float base, float lmWeight, float q, const float* __restrict__ classScore, int c) {
+// pnb' of an extension: a + g, a the policy's acoustic sum (CTC: lp[c] + base), g = (lmWeight * q) + classScore[c]; one fp32
+// operation each, in this order
+__device__ __forceinline__ float beam_lm_ext(float a, float lmWeight, float q, const float* __restrict__ classScore, int c) {
   float g = lmWeight * q;
   if (classScore) g = g + classScore[c];
-  return (lpc + base) + g;
+  return a + g;
 }
 
-template <bool kLogAdd, int kThreads>
+// Pol::kNoBlank: lm may be null, which means no LM: no g term, q = 0, state 0
+template <bool kLogAdd, int kThreads, class Pol = BeamCtc>
 __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W, float threshold,
                                                              const float* __restrict__ x, const int* __restrict__ frames,
                                                              CtcBeamWs ws, const void* __restrict__ lm, float lmWeight,
-                                                             const float* __restrict__ classScore) {
+                                                             const float* __restrict__ classScore, BeamTrans tr) {
   constexpr int kWaves = kThreads / 64;
   __shared__ int sNode[2][64], sPar[2][64], sE[2][64], sSt[2][64];   // the beam of this frame and the next one
   __shared__ float sPb[2][64], sPnb[2][64], sTot[2][64], sAcc[2][64];
@@ -48,13 +51,15 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
   u64* tab = ws.table + (size_t)b * ws.cap;
   const unsigned capm = ws.cap - 1;
   const size_t row0 = (size_t)b * T;
-  const NgramView lv = ngram_view(lm);
+  const bool useLm = !Pol::kNoBlank || lm != nullptr;
+  const NgramView lv = useLm ? ngram_view(lm) : NgramView{};
+  const float* A = Pol::stage(tr, N);
 
   int cur = 0, n = 1;
   if (tid < 64) {
     sNode[0][tid] = tid == 0 ? 0 : -2; sPar[0][tid] = -1; sE[0][tid] = -1;
     sPb[0][tid] = tid == 0 ? 0.f : -INFINITY; sPnb[0][tid] = -INFINITY; sTot[0][tid] = tid == 0 ? 0.f : -INFINITY;
-    sSt[0][tid] = (int)((const NgramHeader*)lm)->start; sAcc[0][tid] = 0.f;
+    sSt[0][tid] = useLm ? (int)((const NgramHeader*)lm)->start : 0; sAcc[0][tid] = 0.f;
   }
   for (int t = 0; t < F && n > 0; ++t) {
     const size_t row = row0 + t;
@@ -74,22 +79,30 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
       const int idx = tid + kThreads * i;
       if (idx < total) {
         const int r = idx / K, k = idx - r * K, c = sTc[k];
-        lq[i] = ngram_q(lv, sSt[cur][r], c, &nst[i]);
-        const float v = beam_lm_ext(sTl[k], c == sE[cur][r] ? sPb[cur][r] : sTot[cur][r], lmWeight, lq[i], classScore, c);
-        key[i] = beam_key(v, r, 1, k);
+        if (!Pol::none(c, sE[cur][r])) {
+          float v = Pol::ext(sTl[k], c, sE[cur][r], sPb[cur][r], sTot[cur][r], A, N);
+          if (useLm) {
+            lq[i] = ngram_q(lv, sSt[cur][r], c, &nst[i]);
+            v = beam_lm_ext(v, lmWeight, lq[i], classScore, c);
+          }
+          key[i] = beam_key(v, r, 1, k);
+        }
       }
     }
     // stay(tid), with the extension that spells this entry merged in
     u64 stayKey = 0ull;
     float spb = -INFINITY, spnb = -INFINITY, stot = -INFINITY;
     if (tid < n) {
-      const BeamStay s = beam_stay_front(n, K, sTc, sNode[cur], sPar[cur], sE[cur], sPb[cur], sPnb[cur], sTot[cur],
-                                         xb + (size_t)t * N, lpb, lse);
+      const BeamStay s = beam_stay_front<Pol>(n, K, sTc, sTl, sNode[cur], sPar[cur], sE[cur], sPb[cur], sPnb[cur], sTot[cur],
+                                              xb + (size_t)t * N, lpb, lse, A, N);
       spb = s.spb; spnb = s.spnb;
       if (s.merge) {
-        int unused;
-        const float qm = ngram_q(lv, sSt[cur][s.pr], s.e, &unused);
-        const float v = beam_lm_ext(sTl[s.kj], s.base, lmWeight, qm, classScore, s.e);
+        float v = s.a;
+        if (useLm) {
+          int unused;
+          const float qm = ngram_q(lv, sSt[cur][s.pr], s.e, &unused);
+          v = beam_lm_ext(v, lmWeight, qm, classScore, s.e);
+        }
         spnb = beam_oplus<kLogAdd>(spnb, v);
         atomicOr(&sGone[s.pr], 1ull << s.kj);
       }
@@ -198,7 +211,7 @@ W2L_API int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input, cons
   if (const int rc = ctc_beam_begin(&ws, kBeamLm, B, T, N, input, frames, beam, K, normalize, workspace, s)) return rc;
   ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
     hipLaunchKernelGGL((ctc_beam_lm_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)B), dim3(decltype(th)::value), 0, s,
-                       T, N, beam, threshold, input, frames, ws, lm, lmWeight, classScore);
+                       T, N, beam, threshold, input, frames, ws, lm, lmWeight, classScore, BeamTrans{});
   });
   W2L_LAUNCH_CHECK();
   hipLaunchKernelGGL(ctc_beam_lm_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, N, ws, lm, lmWeight, eosScore,

@@ -2,12 +2,19 @@
 // [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--k=v ...]`: the
 // reference's Decode tool for its lexicon-free token decoder (`--uselexicon=false --decodertype=tkn`), without LM (the configuration
 // of recipes/self_training/librispeech/am/decode_*.cfg) or with a token-level n-gram LM (`--lm=<arpa>`, recipes/lexicon_free and the
-// word-piece runs of sota/2019), over the fl:: surface.  Output formats: Decode.cpp:683-739, :840-846.
+// word-piece runs of sota/2019), and for its lexicon decoder with a word LM (recipes/conv_glu/*/decode*.cfg), over the fl::
+// surface, for CTC and for ASG models.  Output formats: Decode.cpp:683-739, :840-846.
 //
 // Flags come from the checkpoint's `gflags` entry, then from the command line (the last definition wins), as in Align.  The tool
-// builds the network and the CTC criterion, loads both from --am and runs the eval-mode network over the --test list in list order
-// in batches of --batchsize through list_data.hpp; one CTCLoss::beamSearch call per batch (w2l_ctc_beam_search) with the
-// utterances' emission-frame counts, computed as in align_main.cpp: frames_b = clamp(ceil(tb * Tout / Tin), 1, Tout).
+// builds the network and the checkpoint's criterion (CTC or ASG), loads both from --am and runs the eval-mode network over the
+// --test list in list order in batches of --batchsize through list_data.hpp; one beamSearch call of the criterion per batch
+// (CTCLoss: w2l_ctc_beam_search*; ASGLoss: w2l_asg_beam_search* under the checkpoint's transitions) with the utterances'
+// emission-frame counts, computed as in align_main.cpp: frames_b = clamp(ceil(tb * Tout / Tin), 1, Tout).
+//   --criterion=asg (from the checkpoint): the classes are the tokens plus --replabel, as Train counts them, and there is no blank;
+//     a token LM is over all of them (the replabels `<1>`.. are words of the ARPA file), the lexicon's spellings are packed with
+//     --replabel (`h e l l o` -> `h e l <1> o`), hypotheses are unpacked by tknLabels2Ltr.  The search runs on the raw emissions in
+//     both --logadd modes: ASG scores are unnormalised by design.  With --logadd=false and without LM or lexicon the 1-best is the
+//     Viterbi transcript of Train.
 //   --beamsize (2500), --beamsizetoken (250000), --beamthreshold (25), --logadd (false), --nbest (1): the reference's names and
 //   defaults.  The kernel keeps at most 64 beam entries and 64 tokens per frame: larger values are limited to 64 (said on stderr).
 //   --logadd=false (default): a prefix scores the MAX over its alignments, on the raw emissions as in the reference's decoder; the
@@ -34,8 +41,9 @@
 // Refused, each with a message that names the flag: an unreadable or malformed --lm, --lmtype other than kenlm, --uselexicon=true
 // without --lexicon or --lm, --decodertype=wrd without --uselexicon=true, --decodertype=tkn with it, --smearing=logadd, a finite
 // --unkscore (no unknown-word arc), a lexicon spelling with a token the dictionary lacks (the message names the word), a non-zero
-// --silscore, a non-zero --wordscore without --lm, a --criterion other than ctc.  (--uselexicon and --decodertype default to
-// false / tkn here, so an invocation without them is the lexicon-free search.)
+// --silscore, a non-zero --wordscore without --lm, a --criterion other than ctc or asg, a --criterion on the command line that is not
+// the checkpoint's (the criterion's parameters come from the checkpoint).  (--uselexicon and --decodertype default to false / tkn
+// here, so an invocation without them is the lexicon-free search.)
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -58,7 +66,7 @@ int usage(const char* exe) {
                " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [flags]\n"
                " [--lm=<arpa> --lmtype=kenlm --lmweight=0 --eosscore=0 --wordscore=0]\n"
                " [--uselexicon=true --decodertype=wrd --lexicon=<file> --lm=<word arpa> --smearing=none|max]\n"
-               " lexicon-free CTC token beam search, optionally with a token-level n-gram LM (ARPA text); beam and tokens per frame are limited to 64.\n"
+               " CTC or ASG (as the checkpoint says) token beam search, optionally with a token-level n-gram LM (ARPA text); beam and tokens per frame are limited to 64.\n"
                " --logadd=false (default): max over a prefix's alignments on the raw emissions -- the 1-best equals the greedy transcript.\n"
                " --logadd=true: the labelling-probability search (sum over a prefix's alignments, on log-softmax rows)."
             << std::endl;
@@ -96,12 +104,16 @@ int main(int argc, char** argv) {
     auto it = cfg.find("gflags");
     if (it == cfg.end()) throw std::invalid_argument("Invalid config loaded from " + am);
     w2l::Flags flags = w2l::parseFlagsText(it->second);
+    const std::string criterionName = flags.get("criterion", "asg");   // the checkpoint's: its parameters are the checkpoint's too
     for (auto& kv : cmd.kv) flags.kv.push_back(kv);
 
     // ---- what this build does not decode
-    const std::string criterionName = flags.get("criterion", "asg");
-    if (criterionName != "ctc")
-      throw std::invalid_argument("--criterion=" + criterionName + ": Decode searches the CTC lattice only (ASG's best path is Train's Viterbi)");
+    if (flags.get("criterion", "asg") != criterionName)
+      throw std::invalid_argument("--criterion=" + flags.get("criterion", "asg") + ": the model was trained with --criterion=" + criterionName +
+                                  ", and Decode searches the lattice of the checkpoint's criterion");
+    if (criterionName != "ctc" && criterionName != "asg")
+      throw std::invalid_argument("--criterion=" + criterionName + ": Decode searches the CTC and the ASG lattice only");
+    const bool asg = criterionName == "asg";
     const std::string lmPath = flags.get("lm", "");
     if (!lmPath.empty()) {
       const std::string lmType = flags.get("lmtype", "kenlm");
@@ -147,9 +159,11 @@ int main(int argc, char** argv) {
     const std::string tok = pathJoin(flags.get("tokensdir", ""), flags.get("tokens", "tokens.txt"));
     int numClasses = countTokens(tok);
     if (numClasses <= 0) throw std::invalid_argument("cannot read the token dictionary '" + tok + "' (--tokensdir / --tokens)");
-    numClasses += 1;  // blank, appended LAST
+    if (asg) numClasses += (int)flags.geti("replabel", 0);   // tokens, then the replabels; no blank (Train's count)
+    else numClasses += 1;                                    // blank, appended LAST
+    const int numTokens = asg ? numClasses : numClasses - 1;   // the classes a hypothesis is made of
     if (beamSize > 64) { std::cerr << "[Decode] --beamsize=" << beamSize << " limited to 64 (the kernel's beam width)" << std::endl; beamSize = 64; }
-    beamToken = std::min<long>(beamToken, numClasses - 1);
+    beamToken = std::min<long>(beamToken, numTokens);
     if (beamToken > 64) { std::cerr << "[Decode] --beamsizetoken limited to 64 tokens per frame" << std::endl; beamToken = 64; }
     const int M = beamDump ? (int)std::min(nbest, beamSize) : 1;
 
@@ -159,8 +173,11 @@ int main(int argc, char** argv) {
     auto scalemode = getCriterionScaleMode(flags.get("onorm", "none"), flags.getb("sqnorm", false));
     std::shared_ptr<fl::Module> network = fl::pkg::runtime::ModulePlugin(archPath).arch(nFeat, numClasses);
     if (flags.getb("fl_amp_use_mixed_precision", false)) setMixedPrecision(network, true);
-    auto ctc = std::make_shared<CTCLoss>(scalemode);
-    std::shared_ptr<SequenceCriterion> criterion = ctc;
+    std::shared_ptr<CTCLoss> ctc;
+    std::shared_ptr<ASGLoss> asgCrit;
+    std::shared_ptr<SequenceCriterion> criterion;
+    if (asg) criterion = asgCrit = std::make_shared<ASGLoss>(numClasses, scalemode, flags.getd("transdiag", 0.0));
+    else criterion = ctc = std::make_shared<CTCLoss>(scalemode);
     Serializer::Config unused;
     Serializer::load(am, version, unused, network, criterion);
     network->eval();
@@ -186,14 +203,14 @@ int main(int argc, char** argv) {
     // ---- the language model over the token classes, and the word score as class scores
     std::unique_ptr<NGramLM> lm;
     std::unique_ptr<Lexicon> lexicon;
-    std::vector<float> classScore((size_t)numClasses - 1, 0.f);
+    std::vector<float> classScore((size_t)numTokens, 0.f);
     af::array classScoreDev;
     if (useLexicon) {   // the lexicon trie, the LM over its words, and the LM's unigram-context scores smeared down the trie
       std::vector<std::string> tokens;
-      for (int c = 0; c < numClasses - 1; ++c) tokens.push_back(d.dict.getEntry(c));
-      const std::string sil = !d.wordsep.empty() && d.dict.contains(d.wordsep) && d.dict.getIndex(d.wordsep) < numClasses - 1 ? d.wordsep : "";
+      for (int c = 0; c < numTokens; ++c) tokens.push_back(d.dict.getEntry(c));
+      const std::string sil = !d.wordsep.empty() && d.dict.contains(d.wordsep) && d.dict.getIndex(d.wordsep) < numTokens ? d.wordsep : "";
       try {
-        lexicon.reset(new Lexicon(Lexicon::fromFile(lexiconPath, tokens, nullptr, sil, "none")));
+        lexicon.reset(new Lexicon(Lexicon::fromFile(lexiconPath, tokens, nullptr, sil, "none", d.replabel)));
       } catch (const std::exception& e) {
         throw std::invalid_argument("--lexicon=" + lexiconPath + ": " + e.what());
       }
@@ -202,14 +219,14 @@ int main(int argc, char** argv) {
       } catch (const std::exception& e) {
         throw std::invalid_argument("--lm=" + lmPath + ": " + e.what());
       }
-      if (smearing == "max") lexicon.reset(new Lexicon(Lexicon::fromFile(lexiconPath, tokens, lm.get(), sil, "max")));
+      if (smearing == "max") lexicon.reset(new Lexicon(Lexicon::fromFile(lexiconPath, tokens, lm.get(), sil, "max", d.replabel)));
       if (!lm->hasEos() && eosScore != 0.0) throw std::invalid_argument("--eosscore: the model of --lm has no </s> (leave it 0)");
       std::cerr << "[Decode] --lexicon: " << lexicon->numWords() << " words, " << lexicon->numNodes() << " nodes, " << lexicon->dropped()
                 << " homophones beyond the sixth dropped, smearing " << smearing << ", silence token " << (sil.empty() ? "none" : sil)
                 << "; --lm over the words: order " << lm->order() << ", " << lm->numStates() << " states; " << lm->message() << std::endl;
     } else if (!lmPath.empty()) {
       std::vector<std::string> tokens;
-      for (int c = 0; c < numClasses - 1; ++c) tokens.push_back(d.dict.getEntry(c));
+      for (int c = 0; c < numTokens; ++c) tokens.push_back(d.dict.getEntry(c));
       try {
         lm.reset(new NGramLM(NGramLM::fromArpa(lmPath, tokens)));
       } catch (const std::exception& e) {
@@ -218,7 +235,7 @@ int main(int argc, char** argv) {
       if (!lm->hasEos() && eosScore != 0.0) throw std::invalid_argument("--eosscore: the model of --lm has no </s> (leave it 0)");
       std::cerr << "[Decode] --lm: order " << lm->order() << ", " << lm->numStates() << " states; " << lm->message() << std::endl;
       if (wordScore != 0.0) {
-        for (int c = 0; c < numClasses - 1; ++c) {
+        for (int c = 0; c < numTokens; ++c) {
           const bool begins = wp ? (!d.wordsep.empty() && tokens[(size_t)c].rfind(d.wordsep, 0) == 0) : tokens[(size_t)c] == d.wordsep;
           if (begins) classScore[(size_t)c] = (float)wordScore;
         }
@@ -262,12 +279,13 @@ int main(int argc, char** argv) {
         const long tb = std::min(d.mfsc->numFrames((long)sizes[(size_t)b]), Tin);
         frames[(size_t)b] = (int)std::min<long>(std::max<long>((tb * Tout + Tin - 1) / Tin, 1), Tout);
       }
-      CTCLoss::BeamSearchOptions opt;
+      BeamSearchOptions opt;
       opt.beamSize = (int)beamSize;
       opt.beamSizeToken = (int)beamToken;
       opt.beamThreshold = (float)threshold;
       opt.logAdd = logAdd;
-      opt.normalize = logAdd ? 1 : 0;   // the reference's decoder consumes the raw emissions; sums need log-probabilities
+      // the reference's decoder consumes the raw emissions; CTC sums need log-probabilities, ASG scores are unnormalised by design
+      opt.normalize = logAdd && !asg ? 1 : 0;
       opt.nbest = M;
       if (lm) {
         opt.lm = lm.get();
@@ -280,7 +298,8 @@ int main(int argc, char** argv) {
         opt.wordScore = (float)wordScore;
         opt.maxWords = Tout;
       }
-      auto res = ctc->beamSearch(out.array(), af::array(af::dim4(1, B), frames.data()), opt);
+      const af::array framesDev(af::dim4(1, B), frames.data());
+      auto res = asg ? asgCrit->beamSearch(out.array(), framesDev, opt) : ctc->beamSearch(out.array(), framesDev, opt);
       std::vector<int> labels((size_t)B * M * Tout), lengths((size_t)B * M);
       std::vector<float> scores((size_t)B * M);
       res.labels.host(labels.data());

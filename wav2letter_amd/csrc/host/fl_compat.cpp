@@ -1260,8 +1260,10 @@ af::array CTCLoss::viterbiPathWithTarget(const af::array& input, const af::array
   af::sync();  // ws is released at return
   return path;
 }
-// n-best prefix beam search (w2l_ctc_beam_search); inputSizes as in viterbiPathWithTarget
-CTCLoss::BeamSearchResult CTCLoss::beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& o) {
+// n-best beam search; inputSizes as in viterbiPathWithTarget.  trans == nullptr: the CTC searches (w2l_ctc_beam_search*), blank =
+// N-1; else the ASG searches (w2l_asg_beam_search*) under that transition matrix, every class a token
+static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, const float* trans, const af::array& input,
+                                      const af::array& inputSizes, const BeamSearchOptions& o) {
   const int N = (int)input.dims(0), T = (int)input.dims(1), B = (int)input.dims(2);
   const int* frames = nullptr;
   if (!inputSizes.isempty()) {
@@ -1271,29 +1273,39 @@ CTCLoss::BeamSearchResult CTCLoss::beamSearch(const af::array& input, const af::
   const int Lmax = o.maxLen > 0 ? o.maxLen : T;
   if (input.type() != af::f32 || B <= 0 || T <= 0 || N < 2 || o.nbest < 1 || o.beamSize < 1 || o.beamSizeToken < 1)
     throw std::invalid_argument("beamSearch: bad input or options");
-  auto st = stateOf(this);
+  const int tokens = trans ? N : N - 1;
   BeamSearchResult r;
   r.labels = af::array(af::dim4(Lmax, o.nbest, B), af::s32);
   r.lengths = af::array(af::dim4(o.nbest, B), af::s32);
   r.scores = af::array(af::dim4(o.nbest, B));
-  const bool normalize = o.normalize < 0 ? o.logAdd : o.normalize != 0;
+  const bool normalize = o.normalize < 0 ? (o.logAdd && !trans) : o.normalize != 0;
   if (o.lexicon) {   // the search restricted to the lexicon's spellings, scored by a LM over words (w2l_ctc_beam_search_lex)
     if (!o.lm) throw std::invalid_argument("beamSearch: lexicon needs lm, a model over the lexicon's words");
     if (!o.classScore.isempty()) throw std::invalid_argument("beamSearch: classScore must be empty with a lexicon");
     if (o.lm->numTokens() != o.lexicon->numWords()) throw std::invalid_argument("beamSearch: the LM's word count is not the lexicon's");
-    if (o.lexicon->numTokens() != N - 1) throw std::invalid_argument("beamSearch: the lexicon's token count is not the emissions' N - 1");
+    if (o.lexicon->numTokens() != tokens)
+      throw std::invalid_argument(trans ? "beamSearch: the lexicon's token count is not the emissions' N"
+                                        : "beamSearch: the lexicon's token count is not the emissions' N - 1");
     if (o.maxWords < 0) throw std::invalid_argument("beamSearch: maxWords must not be negative");
     const int maxWords = o.maxWords > 0 ? o.maxWords : Lmax;
     r.lmScores = af::array(af::dim4(o.nbest, B));
     r.words = af::array(af::dim4(maxWords, o.nbest, B), af::s32);
     r.wordCounts = af::array(af::dim4(o.nbest, B), af::s32);
-    auto wsx = devAlloc(w2l_ctc_beam_lex_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-    w2l::w2lCheck(w2l_ctc_beam_search_lex(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
-                                          normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
-                                          o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
-                                          r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
-                                          r.words.device<int>(), r.wordCounts.device<int>(), wsx.get(), S()),
-                  "ctc beam search with lexicon");
+    auto wsx = devAlloc((trans ? w2l_asg_beam_lex_workspace_size : w2l_ctc_beam_lex_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    if (trans)
+      w2l::w2lCheck(w2l_asg_beam_search_lex(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
+                                            o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
+                                            o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
+                                            r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
+                                            r.words.device<int>(), r.wordCounts.device<int>(), wsx.get(), S()),
+                    "asg beam search with lexicon");
+    else
+      w2l::w2lCheck(w2l_ctc_beam_search_lex(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+                                            normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
+                                            o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
+                                            r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
+                                            r.words.device<int>(), r.wordCounts.device<int>(), wsx.get(), S()),
+                    "ctc beam search with lexicon");
     af::sync();  // wsx is released at return
     return r;
   }
@@ -1301,18 +1313,38 @@ CTCLoss::BeamSearchResult CTCLoss::beamSearch(const af::array& input, const af::
   if (!o.lm) {
     if (o.lmWeight != 0.f || !o.classScore.isempty() || o.eosScore != 0.f)
       throw std::invalid_argument("beamSearch: lmWeight, classScore and eosScore need lm");
+    if (trans) {   // the lexicon-free ASG search is one entry point: a null LM means none
+      af::array lms(af::dim4(o.nbest, B));
+      auto wsa = devAlloc(w2l_asg_beam_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+      w2l::w2lCheck(w2l_asg_beam_search(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
+                                        o.logAdd, normalize, o.nbest, Lmax, nullptr, 0, 0.f, nullptr, 0.f, r.labels.device<int>(),
+                                        r.lengths.device<int>(), r.scores.device<float>(), lms.device<float>(), wsa.get(), S()),
+                    "asg beam search");
+      af::sync();  // wsa is released at return
+      return r;
+    }
   } else {   // the search fused with the n-gram LM (w2l_ctc_beam_search_lm)
-    if (o.lm->numTokens() != N - 1) throw std::invalid_argument("beamSearch: the LM's token count is not the emissions' N - 1");
-    if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != N - 1))
+    if (o.lm->numTokens() != tokens)
+      throw std::invalid_argument(trans ? "beamSearch: the LM's token count is not the emissions' N"
+                                        : "beamSearch: the LM's token count is not the emissions' N - 1");
+    if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != tokens))
       throw std::invalid_argument("beamSearch: classScore must be f32 with one entry per token class");
     r.lmScores = af::array(af::dim4(o.nbest, B));
-    auto wsl = devAlloc(w2l_ctc_beam_lm_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-    w2l::w2lCheck(w2l_ctc_beam_search_lm(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
-                                         normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
-                                         o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
-                                         r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
-                                         r.lmScores.device<float>(), wsl.get(), S()),
-                  "ctc beam search with LM");
+    auto wsl = devAlloc((trans ? w2l_asg_beam_workspace_size : w2l_ctc_beam_lm_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    if (trans)
+      w2l::w2lCheck(w2l_asg_beam_search(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
+                                        o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
+                                        o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
+                                        r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
+                                        r.lmScores.device<float>(), wsl.get(), S()),
+                    "asg beam search with LM");
+    else
+      w2l::w2lCheck(w2l_ctc_beam_search_lm(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+                                           normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
+                                           o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
+                                           r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
+                                           r.lmScores.device<float>(), wsl.get(), S()),
+                    "ctc beam search with LM");
     af::sync();  // wsl is released at return
     return r;
   }
@@ -1324,6 +1356,13 @@ CTCLoss::BeamSearchResult CTCLoss::beamSearch(const af::array& input, const af::
                        r.lengths.device<int>(), r.scores.device<float>(), ws.get());
   af::sync();  // ws is released at return
   return r;
+}
+BeamSearchResult CTCLoss::beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& o) {
+  return beamSearchAny(stateOf(this), nullptr, input, inputSizes, o);
+}
+BeamSearchResult ASGLoss::beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& o) {
+  if ((int)input.dims(0) != N_) throw std::invalid_argument("ASGLoss: N doesn't match with the letter size");
+  return beamSearchAny(stateOf(this), params_[0].array().device<float>(), input, inputSizes, o);
 }
 std::string CTCLoss::prettyString() const { return "ConnectionistTemporalClassificationCriterion"; }
 

@@ -57,14 +57,21 @@ class Lexicon:
         return cls(blob, words, dropped.value)
 
     @classmethod
-    def from_file(cls, path, token_dict, lm=None, sil=None, smearing="max"):
+    def from_file(cls, path, token_dict, lm=None, sil=None, smearing="max", replabel=0):
         """a lexicon file (text.load_lexicon: `word tok tok ...`, every spelling of a word a line) over token_dict (a
         text.Dictionary, or the list of token spellings).  sil: the spelling of the silence token, or None.  smearing "max":
-        wordSmear[w] = lm.score(lm.start, w) (lm: the NGramLM over Lexicon.words); "none": no smearing"""
+        wordSmear[w] = lm.score(lm.start, w) (lm: the NGramLM over Lexicon.words); "none": no smearing.  replabel > 0 (an ASG
+        model's --replabel): every spelling is packed with text.pack_replabels before the trie is built -- `h e l l o` becomes
+        `h e l <1> o` -- and the tokens `<1>` .. `<replabel>` must be in token_dict"""
         if smearing not in ("max", "none"):
             raise _lib.W2LInvalidArgument(f"Lexicon.from_file: smearing {smearing!r} is not built: `max` or `none`")
         if not isinstance(token_dict, text.Dictionary):
             token_dict = text.Dictionary(list(token_dict))
+        replabel = int(replabel)
+        for r in range(1, replabel + 1):
+            if not token_dict.contains(text.replabel_token(r)):
+                raise _lib.W2LInvalidArgument(f"Lexicon.from_file: replabel={replabel} needs the token `{text.replabel_token(r)}` "
+                                              "in the token dictionary")
         lex = text.load_lexicon(str(path))
         words = sorted(lex, key=lambda w: w.encode())
         wid = {w: i for i, w in enumerate(words)}
@@ -75,7 +82,7 @@ class Lexicon:
                     if not token_dict.contains(t):
                         raise _lib.W2LInvalidArgument(f"Lexicon.from_file: the spelling of `{w}` has the token `{t}`, which the token "
                                                       "dictionary lacks")
-                rows.append((wid[w], [token_dict.get_index(t) for t in sp]))
+                rows.append((wid[w], text.pack_replabels([token_dict.get_index(t) for t in sp], token_dict, replabel)))
         smear = None
         if smearing == "max" and lm is not None:
             if lm.num_tokens != len(words):
