@@ -367,6 +367,51 @@ int w2l_asg_beam_search_lex(int B, int T, int N, const float* input /*[B][T][N]*
                             int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
                             float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/, int* wordCounts /*[B][M]*/,
                             void* workspace, w2l_stream_t stream);
+/* The wide twins of the five beam searches above.  Each takes the argument list of its sibling and obeys its sibling's contract
+ * word for word -- frame tokens, stay / ext / merge / prune, the order and its tie key, the sil / in / word slots, the ASG rules,
+ * the end rule and the EOS term, the outputs, the order of the refusals -- with two differences: W may be 1..1024 and M 1..W.  K
+ * after clipping stays <= 64; W > 1024 or K > 64 is W2L_EUNSUPPORTED (and a workspace size of 0), after every W2L_EINVAL, before
+ * anything touches the device.  The kernels are another family (one workgroup per utterance, the candidates of a frame in the
+ * workspace, a parallel selection of the W best keys and a sort of the survivors), but every value is made by the sibling's
+ * operation sequence and the ranks depend on the keys alone: with logAdd = 0 the outputs equal the sibling's bit for bit at every
+ * W both accept, and with logAdd = 1 too (a stay receives at most one merged term, so no sum depends on an order).  The workspace
+ * grows with W * K (* 7 with a lexicon): 8 bytes per possible candidate of a frame and utterance. */
+size_t w2l_ctc_beam_wide_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_wide(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                             int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                             int nbest /*M*/, int maxLen /*Lmax*/,
+                             int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                             void* workspace, w2l_stream_t stream);
+size_t w2l_ctc_beam_lm_wide_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lm_wide(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                                int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                                int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                                const float* classScore /*[N-1] or NULL*/, float eosScore,
+                                int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                                float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream);
+size_t w2l_ctc_beam_lex_wide_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lex_wide(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                                 int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                                 int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                                 const void* lexicon, float wordScore, float eosScore,
+                                 int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                                 float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                                 int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream);
+size_t w2l_asg_beam_wide_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_wide(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                             const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/, float threshold,
+                             int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm /*or NULL*/,
+                             int lmHasEos, float lmWeight, const float* classScore /*[N] or NULL*/, float eosScore,
+                             int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                             float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream);
+size_t w2l_asg_beam_lex_wide_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_lex_wide(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                                 const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/,
+                                 float threshold, int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm,
+                                 int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
+                                 int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                                 float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                                 int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the

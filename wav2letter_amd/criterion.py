@@ -301,11 +301,21 @@ def ctc_align(emission, target, frames=None, with_score=True):
     return path, score
 
 
+def _wide(L, name, wide):
+    """the entry point `name`, or its wide twin: w2l_x_beam_search_y -> w2l_x_beam_search_y_wide, w2l_x_workspace_size ->
+    w2l_x_wide_workspace_size"""
+    if not wide:
+        return getattr(L, name)
+    if name.endswith("_workspace_size"):
+        return getattr(L, name[:-len("_workspace_size")] + "_wide_workspace_size")
+    return getattr(L, name + "_wide")
+
+
 def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=None,
                     nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
-                    max_words=None):
+                    max_words=None, wide=False):
     """CTC prefix beam search without lexicon or LM (w2l_ctc_beam_search; the contract is in include/w2l_hip.h): `emission`
-    [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64), beam_token = K (clipped to N-1, then <= 64),
+    [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64; <= 1024 with wide=True), beam_token = K (clipped to N-1, then <= 64),
     log_add: sum (True) or max (False) over the alignments of a prefix; normalize: search on log-softmax rows (default: log_add --
     sums only mean something on log-probabilities; the max search runs on the raw emissions as the reference's decoder does).
     Returns (labels [B][nbest][max_len] int32, -1 beyond a hypothesis; lengths [B][nbest] int32, the true label counts, -1 for a
@@ -318,7 +328,9 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     required then and is an NGramLM over the lexicon's WORDS (NGramLM.from_arpa(path, lexicon.words)); class_score must be None;
     every completed word adds lm_weight * log p_LM(word | words before) + word_score, smeared down the trie.  Returns
     (labels, lengths, scores, lm_scores, words [B][nbest][max_words] int32 word ids, -1 beyond; word_counts [B][nbest] int32);
-    max_words defaults to max_len.  A hypothesis that ends inside a word does not count: an utterance may have only empty rows."""
+    max_words defaults to max_len.  A hypothesis that ends inside a word does not count: an utterance may have only empty rows.
+    wide: run the wide kernels (the w2l_*_wide entry points): the same contract with beam up to 1024; beam_token stays <= 64.  At
+    beam <= 64 both kernel families return the same bytes."""
     _emission_checks(emission)
     B, T, N = emission.shape
     if lexicon is not None:
@@ -364,12 +376,12 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
     if lexicon is not None:
         max_words = max(max_len, 1) if max_words is None else int(max_words)
-        ws = _ws(L.w2l_ctc_beam_lex_workspace_size(B, T, N, int(beam), int(beam_token)), emission.device)
+        ws = _ws(_wide(L, "w2l_ctc_beam_lex_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), emission.device)
         lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
         words = torch.empty(*shape, max_words, dtype=torch.int32, device=emission.device)
         word_counts = torch.empty(*shape, dtype=torch.int32, device=emission.device)
         blob, lex_blob = lm.device_blob(emission.device), lexicon.device_blob(emission.device)
-        _lib.check(L.w2l_ctc_beam_search_lex(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
+        _lib.check(_wide(L, "w2l_ctc_beam_search_lex", wide)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
                                              int(beam), int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)),
                                              nbest, max_len, blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
                                              float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),
@@ -380,18 +392,18 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
         if class_score is not None:
             _check_dev(emission, class_score)
             class_score = class_score.contiguous()
-        ws = _ws(L.w2l_ctc_beam_lm_workspace_size(B, T, N, int(beam), int(beam_token)), emission.device)
+        ws = _ws(_wide(L, "w2l_ctc_beam_lm_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), emission.device)
         lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
         blob = lm.device_blob(emission.device)
-        _lib.check(L.w2l_ctc_beam_search_lm(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
+        _lib.check(_wide(L, "w2l_ctc_beam_search_lm", wide)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
                                             int(beam), int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)),
                                             nbest, max_len, blob.data_ptr(), int(lm.has_eos), float(lm_weight),
                                             class_score.data_ptr() if class_score is not None else None, float(eos_score),
                                             labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), lm_scores.data_ptr(),
                                             ws.data_ptr(), _stream()), "ctc_beam_search")
         return labels, lengths, scores, lm_scores
-    ws = _ws(L.w2l_ctc_beam_workspace_size(B, T, N, int(beam), int(beam_token)), emission.device)
-    _lib.check(L.w2l_ctc_beam_search(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None, int(beam),
+    ws = _ws(_wide(L, "w2l_ctc_beam_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), emission.device)
+    _lib.check(_wide(L, "w2l_ctc_beam_search", wide)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None, int(beam),
                                      int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
                                      labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), ws.data_ptr(), _stream()),
                "ctc_beam_search")
@@ -400,13 +412,13 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
 
 def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=False,
                     nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
-                    max_words=None):
+                    max_words=None, wide=False):
     """Beam search of an ASG model (w2l_asg_beam_search, w2l_asg_beam_search_lex; the contract is in include/w2l_hip.h):
     `emission` [B][T][N], every class a token (no blank), `transitions` [N][N] float32 (to x from) on the emissions' device.  The
     options and the return values are ctc_beam_search's -- (labels, lengths, scores), lm_scores with an LM, words and word_counts
     with a lexicon -- with beam_token clipped to N, an LM (or lexicon) over N tokens and class_score [N].  normalize defaults to
     False in both log_add modes: ASG scores are unnormalised by design.  A token never follows itself: a repeated letter is a
-    replabel's (Lexicon.from_file(..., replabel=) packs the spellings)."""
+    replabel's (Lexicon.from_file(..., replabel=) packs the spellings).  wide: as in ctc_beam_search."""
     _emission_checks(emission)
     B, T, N = emission.shape
     if transitions.dtype != torch.float32 or tuple(transitions.shape) != (N, N):
@@ -454,11 +466,11 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
     lm_scores = torch.empty(*shape, dtype=torch.float32, device=dev)
     if lexicon is not None:
         max_words = max(max_len, 1) if max_words is None else int(max_words)
-        ws = _ws(L.w2l_asg_beam_lex_workspace_size(B, T, N, int(beam), int(beam_token)), dev)
+        ws = _ws(_wide(L, "w2l_asg_beam_lex_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), dev)
         words = torch.empty(*shape, max_words, dtype=torch.int32, device=dev)
         word_counts = torch.empty(*shape, dtype=torch.int32, device=dev)
         blob, lex_blob = lm.device_blob(dev), lexicon.device_blob(dev)
-        _lib.check(L.w2l_asg_beam_search_lex(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
+        _lib.check(_wide(L, "w2l_asg_beam_search_lex", wide)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
                                              float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
                                              blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
                                              float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),
@@ -469,8 +481,8 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
         _check_dev(emission, class_score)
         class_score = class_score.contiguous()
     blob = lm.device_blob(dev) if lm is not None else None
-    ws = _ws(L.w2l_asg_beam_workspace_size(B, T, N, int(beam), int(beam_token)), dev)
-    _lib.check(L.w2l_asg_beam_search(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
+    ws = _ws(_wide(L, "w2l_asg_beam_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), dev)
+    _lib.check(_wide(L, "w2l_asg_beam_search", wide)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
                                      float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
                                      blob.data_ptr() if blob is not None else None, int(lm.has_eos) if lm is not None else 0,
                                      float(lm_weight), class_score.data_ptr() if class_score is not None else None,

@@ -897,3 +897,4 @@ W2L_API int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, 
 #include "criterion_ctc_beam_lm.hpp"
 #include "criterion_ctc_beam_lex.hpp"
 #include "criterion_asg_beam.hpp"
+#include "criterion_beam_wide.hpp"

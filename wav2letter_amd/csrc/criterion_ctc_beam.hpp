@@ -33,6 +33,7 @@ namespace w2l {
 typedef unsigned long long u64;
 
 constexpr int kBeamMax = 64;          // W and K: one lane per entry, one mask bit per frame token
+constexpr int kBeamWideMax = 1024;    // W of the wide searches (criterion_beam_wide.hpp); their K stays <= kBeamMax
 constexpr int kBeamCandCap = 1024;    // LDS candidates of the row pass
 constexpr int kLmPer = 4;             // (entry, token) pairs a thread of a workgroup scan owns: threads * kLmPer >= W * K
 

@@ -16,7 +16,10 @@
 //     both --logadd modes: ASG scores are unnormalised by design.  With --logadd=false and without LM or lexicon the 1-best is the
 //     Viterbi transcript of Train.
 //   --beamsize (2500), --beamsizetoken (250000), --beamthreshold (25), --logadd (false), --nbest (1): the reference's names and
-//   defaults.  The kernel keeps at most 64 beam entries and 64 tokens per frame: larger values are limited to 64 (said on stderr).
+//   defaults.  A --beamsize given in the flags (the checkpoint's or the command line's) above 64 runs the wide kernels
+//   (BeamSearchOptions::wide), which keep up to 1024 beam entries: larger values are limited to 1024 (said on stderr).  A value up
+//   to 64 runs the narrow kernels; so does an absent --beamsize, whose default is limited to 64 (said on stderr).  Both kernels keep
+//   at most 64 tokens per frame: a larger --beamsizetoken is limited to 64 (said on stderr).
 //   --logadd=false (default): a prefix scores the MAX over its alignments, on the raw emissions as in the reference's decoder; the
 //     1-best then equals the greedy transcript (the collapsed per-frame arg-max), the n-best are the next best single alignments.
 //   --logadd=true: the labelling-probability search -- a prefix scores the SUM over its alignments, on log-softmax rows (sums only
@@ -66,7 +69,7 @@ int usage(const char* exe) {
                " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [flags]\n"
                " [--lm=<arpa> --lmtype=kenlm --lmweight=0 --eosscore=0 --wordscore=0]\n"
                " [--uselexicon=true --decodertype=wrd --lexicon=<file> --lm=<word arpa> --smearing=none|max]\n"
-               " CTC or ASG (as the checkpoint says) token beam search, optionally with a token-level n-gram LM (ARPA text); beam and tokens per frame are limited to 64.\n"
+               " CTC or ASG (as the checkpoint says) token beam search, optionally with a token-level n-gram LM (ARPA text); --beamsize is limited to 1024 when given (above 64: the wide kernels), to 64 when absent; tokens per frame are limited to 64.\n"
                " --logadd=false (default): max over a prefix's alignments on the raw emissions -- the 1-best equals the greedy transcript.\n"
                " --logadd=true: the labelling-probability search (sum over a prefix's alignments, on log-softmax rows)."
             << std::endl;
@@ -162,7 +165,12 @@ int main(int argc, char** argv) {
     if (asg) numClasses += (int)flags.geti("replabel", 0);   // tokens, then the replabels; no blank (Train's count)
     else numClasses += 1;                                    // blank, appended LAST
     const int numTokens = asg ? numClasses : numClasses - 1;   // the classes a hypothesis is made of
-    if (beamSize > 64) { std::cerr << "[Decode] --beamsize=" << beamSize << " limited to 64 (the kernel's beam width)" << std::endl; beamSize = 64; }
+    const long beamLimit = flags.has("beamsize") ? 1024 : 64;   // a beam width that was asked for runs the wide kernels above 64
+    if (beamSize > beamLimit) {
+      std::cerr << "[Decode] --beamsize=" << beamSize << " limited to " << beamLimit << " (the kernel's beam width)" << std::endl;
+      beamSize = beamLimit;
+    }
+    const bool wide = beamSize > 64;
     beamToken = std::min<long>(beamToken, numTokens);
     if (beamToken > 64) { std::cerr << "[Decode] --beamsizetoken limited to 64 tokens per frame" << std::endl; beamToken = 64; }
     const int M = beamDump ? (int)std::min(nbest, beamSize) : 1;
@@ -182,7 +190,7 @@ int main(int argc, char** argv) {
     Serializer::load(am, version, unused, network, criterion);
     network->eval();
     criterion->eval();
-    std::cerr << "[Decode] " << criterion->prettyString() << ", " << numClasses << " classes, model " << am << ", beam " << beamSize
+    std::cerr << "[Decode] " << criterion->prettyString() << ", " << numClasses << " classes, model " << am << ", beam " << beamSize << (wide ? " (wide)" : "")
               << ", tokens per frame " << beamToken << ", threshold " << threshold << (logAdd ? ", logadd" : ", max") << std::endl;
 
     // ---- the list
@@ -281,6 +289,7 @@ int main(int argc, char** argv) {
       }
       BeamSearchOptions opt;
       opt.beamSize = (int)beamSize;
+      opt.wide = wide;
       opt.beamSizeToken = (int)beamToken;
       opt.beamThreshold = (float)threshold;
       opt.logAdd = logAdd;

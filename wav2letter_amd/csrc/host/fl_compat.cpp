@@ -1261,7 +1261,7 @@ af::array CTCLoss::viterbiPathWithTarget(const af::array& input, const af::array
   return path;
 }
 // n-best beam search; inputSizes as in viterbiPathWithTarget.  trans == nullptr: the CTC searches (w2l_ctc_beam_search*), blank =
-// N-1; else the ASG searches (w2l_asg_beam_search*) under that transition matrix, every class a token
+// N-1; else the ASG searches (w2l_asg_beam_search*) under that transition matrix, every class a token; o.wide: their _wide twins
 static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, const float* trans, const af::array& input,
                                       const af::array& inputSizes, const BeamSearchOptions& o) {
   const int N = (int)input.dims(0), T = (int)input.dims(1), B = (int)input.dims(2);
@@ -1291,16 +1291,18 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
     r.lmScores = af::array(af::dim4(o.nbest, B));
     r.words = af::array(af::dim4(maxWords, o.nbest, B), af::s32);
     r.wordCounts = af::array(af::dim4(o.nbest, B), af::s32);
-    auto wsx = devAlloc((trans ? w2l_asg_beam_lex_workspace_size : w2l_ctc_beam_lex_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    auto wsx = devAlloc((trans ? (o.wide ? w2l_asg_beam_lex_wide_workspace_size : w2l_asg_beam_lex_workspace_size)
+                               : (o.wide ? w2l_ctc_beam_lex_wide_workspace_size : w2l_ctc_beam_lex_workspace_size))(
+                            B, T, N, o.beamSize, o.beamSizeToken) + 256);
     if (trans)
-      w2l::w2lCheck(w2l_asg_beam_search_lex(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
+      w2l::w2lCheck((o.wide ? w2l_asg_beam_search_lex_wide : w2l_asg_beam_search_lex)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
                                             o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
                                             o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
                                             r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
                                             r.words.device<int>(), r.wordCounts.device<int>(), wsx.get(), S()),
                     "asg beam search with lexicon");
     else
-      w2l::w2lCheck(w2l_ctc_beam_search_lex(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+      w2l::w2lCheck((o.wide ? w2l_ctc_beam_search_lex_wide : w2l_ctc_beam_search_lex)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
                                             normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
                                             o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
                                             r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
@@ -1315,8 +1317,8 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
       throw std::invalid_argument("beamSearch: lmWeight, classScore and eosScore need lm");
     if (trans) {   // the lexicon-free ASG search is one entry point: a null LM means none
       af::array lms(af::dim4(o.nbest, B));
-      auto wsa = devAlloc(w2l_asg_beam_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-      w2l::w2lCheck(w2l_asg_beam_search(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
+      auto wsa = devAlloc((o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+      w2l::w2lCheck((o.wide ? w2l_asg_beam_search_wide : w2l_asg_beam_search)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
                                         o.logAdd, normalize, o.nbest, Lmax, nullptr, 0, 0.f, nullptr, 0.f, r.labels.device<int>(),
                                         r.lengths.device<int>(), r.scores.device<float>(), lms.device<float>(), wsa.get(), S()),
                     "asg beam search");
@@ -1330,22 +1332,33 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
     if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != tokens))
       throw std::invalid_argument("beamSearch: classScore must be f32 with one entry per token class");
     r.lmScores = af::array(af::dim4(o.nbest, B));
-    auto wsl = devAlloc((trans ? w2l_asg_beam_workspace_size : w2l_ctc_beam_lm_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    auto wsl = devAlloc((trans ? (o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)
+                               : (o.wide ? w2l_ctc_beam_lm_wide_workspace_size : w2l_ctc_beam_lm_workspace_size))(
+                            B, T, N, o.beamSize, o.beamSizeToken) + 256);
     if (trans)
-      w2l::w2lCheck(w2l_asg_beam_search(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
+      w2l::w2lCheck((o.wide ? w2l_asg_beam_search_wide : w2l_asg_beam_search)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
                                         o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
                                         o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
                                         r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
                                         r.lmScores.device<float>(), wsl.get(), S()),
                     "asg beam search with LM");
     else
-      w2l::w2lCheck(w2l_ctc_beam_search_lm(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+      w2l::w2lCheck((o.wide ? w2l_ctc_beam_search_lm_wide : w2l_ctc_beam_search_lm)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
                                            normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
                                            o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
                                            r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
                                            r.lmScores.device<float>(), wsl.get(), S()),
                     "ctc beam search with LM");
     af::sync();  // wsl is released at return
+    return r;
+  }
+  if (o.wide) {   // the LM-free CTC search's wide twin
+    auto wsw = devAlloc(w2l_ctc_beam_wide_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    w2l::w2lCheck(w2l_ctc_beam_search_wide(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+                                           normalize, o.nbest, Lmax, r.labels.device<int>(), r.lengths.device<int>(),
+                                           r.scores.device<float>(), wsw.get(), S()),
+                  "ctc beam search");
+    af::sync();  // wsw is released at return
     return r;
   }
   auto ws = devAlloc(st->impl->beamWorkspaceBytes(B, T, N, o.beamSize, o.beamSizeToken) + 256);
