@@ -514,6 +514,11 @@ FL_COMPAT_API FlatView flatGradients(const std::shared_ptr<fl::Module>& network)
 // images with fp32 accumulation; activations, master weights, LayerNorm, the optimizer and the criterion stay fp32 (no-op for
 // any other module)
 FL_COMPAT_API void setMixedPrecision(const std::shared_ptr<fl::Module>& network, bool on);
+// fl_compat extension (--w2l_amp_convs): the second level of that mode -- the wide time convolutions at H == 1 (the `C` lines of
+// the conv_glu recipes, the Transformer recipes' front end) multiply bf16 images too (w2l_conv_bf16_*).  Acts only while
+// setMixedPrecision is on; the next forward plans again (weight images and image scratch belong to the plan).  No-op for any
+// other module.
+FL_COMPAT_API void setMixedPrecisionConvolutions(const std::shared_ptr<fl::Module>& network, bool on);
 // fl_compat extension: forwards so far of a network built from an arch file = the position of its dropout-seed stream
 // (restored by Serializer::load; `Train fork` starts it from zero)
 FL_COMPAT_API uint32_t networkStep(const std::shared_ptr<fl::Module>& network);

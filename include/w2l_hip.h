@@ -542,6 +542,27 @@ int w2l_tds_conv_bf16_backward_filter(const w2l_conv_desc* d, const float* x, co
 /* the same launch also produces dbias [Cout] = column sums of the bf16-rounded dy (summed from the slabs the kernel stages anyway) */
 int w2l_tds_conv_bf16_backward_filter_bias(const w2l_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias,
                                            w2l_stream_t stream);
+/* The WIDE time convolution at H == 1 in the mixed-precision mode (conv_bf16.hip): the `C cin cout kw s pad` lines of the conv_glu
+ * recipes, the lexicon-free recipe and the Transformer recipes' front end.  Same contract as the TDS family above -- x / dy and w
+ * rounded to bf16 (nearest even), v_mfma_f32_32x32x16_bf16 products, fp32 accumulation / bias / ReLU / addend / results, dbias =
+ * column sums of the ROUNDED dy, run-to-run deterministic -- and the layouts of w2l_conv_*.  Accepted: H == 1, stride 1 or 2,
+ * 32 <= Cin <= 8192 and Cout <= 8192 (any value, multiples of 8 or not), kw <= 64, any padl / padr >= 0, any T with To >= 1, every
+ * operand image below 2 GiB.  Anything else: both size queries return 0 and the calls W2L_EUNSUPPORTED (stay on w2l_conv_*).
+ * Null pointers, misaligned images and bad descriptors: W2L_EINVAL.  All checks precede the first launch; the size queries are
+ * host arithmetic.
+ * w2l_conv_bf16_image_elems: bf16 elements of ONE weight image buffer (two are needed: forward, backward-data).
+ * w2l_conv_bf16_scratch_elems: bf16 elements of the caller-owned scratch the passes write the activation / gradient images to
+ *   (16-byte aligned; nothing in it outlives a call, so one buffer may serve every layer of a network on one stream).
+ * w2l_conv_bf16_prepare: once per step, the two images of the fp32 weight (either pointer may be NULL). */
+size_t w2l_conv_bf16_image_elems(const w2l_conv_desc* d);
+size_t w2l_conv_bf16_scratch_elems(const w2l_conv_desc* d);
+int w2l_conv_bf16_prepare(const w2l_conv_desc* d, const float* w, uint16_t* imgForward, uint16_t* imgBackward, w2l_stream_t stream);
+int w2l_conv_bf16_forward(const w2l_conv_desc* d, const float* x, const uint16_t* imgForward, const float* bias, float* y, int relu,
+                          uint16_t* scratch, w2l_stream_t stream);
+int w2l_conv_bf16_backward_data(const w2l_conv_desc* d, const float* dy, const uint16_t* imgBackward, const float* add, float* dx,
+                                uint16_t* scratch, w2l_stream_t stream);
+int w2l_conv_bf16_backward_filter_bias(const w2l_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias,
+                                       uint16_t* scratch, w2l_stream_t stream);
 
 /* bf16 operand images written by the kernel that PRODUCES a matrix [rows][cols] instead of a w2l_bf16_convert pass over an fp32
  * copy (mixed-precision mode): `rowMajor` [rows][ldRows] and / or `transposed` [cols][ldTrans], the layouts of w2l_bf16_convert;
@@ -825,6 +846,9 @@ int w2l_trainer_set_step(void* h, uint32_t step);
  * with fp32 accumulation (w2l_set_matmul_precision scoped to the network's calls); storage, master weights, convolutions,
  * LayerNorm, the criterion (recipes/joint_training_vox_populi/cpc/Train.cpp:1184) and the optimizer stay fp32 */
 int w2l_trainer_set_mixed_precision(void* h, int on);
+/* second level of that mode: the wide time convolutions (w2l_conv_bf16_*) on bf16 operands too.  Acts only while
+ * w2l_trainer_set_mixed_precision is on.  Call before w2l_trainer_plan: a change after it drops the plan (plan and bind again). */
+int w2l_trainer_set_mixed_precision_convs(void* h, int on);
 /* slimIPL's dynamic dropout (--slimIPL_dyn_dropout, recipes/slimIPL/src/Train.cpp:1141-1168 with the recipe plugin's
  * 100h_supervised_slimipl.cpp:41-58): the probabilities the `TR` layers -- and only they -- use from the next forward on.  A
  * negative value restores that layer's arch value.  No new plan: a trainer with the override set computes, bit for bit, what a

@@ -1,6 +1,7 @@
 """BASELINE config 5 on one GPU: sota/2019 Transformer-CTC (am_transformer_ctc.arch, 322.6 M parameters), batch 16,
 T = 1500 (188 frames after the three max-pools), 9998 word pieces: one full training step (forward, CTC, backward,
-clip + SGD).   python tools/c5_step.py [steps] [f32|bf16] [batch] [drop|nodrop]"""
+clip + SGD).   python tools/c5_step.py [steps] [f32|bf16|bf16+convs] [batch] [drop|nodrop]
+(bf16+convs: the three front-end convolutions on the bf16 wide kernels too, Trainer.set_mixed_precision(True, convs=True))"""
 import json, os, re, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -26,7 +27,7 @@ tr = Trainer(arch, nfeat, nlabel, "ctc", CriterionScaleMode.TARGET_SZ_SQRT, devi
 tr.init_params(seed=1)
 Tout = tr.plan(B, T, Lmax)
 tr.to_device()
-tr.set_mixed_precision(mode == "bf16")
+tr.set_mixed_precision(mode in ("bf16", "bf16+convs"), convs=mode == "bf16+convs")
 tr.set_optimizer(fl["netoptim"], fl["critoptim"])
 it = [0]
 

@@ -218,8 +218,8 @@ namespace w2l {
 bool matmul_bf16_mode() { return g_matmul_bf16.load(std::memory_order_relaxed) != 0; }
 // the bf16-image GEMM for other translation units (conv.hip: overlapping-row operand views)
 int gemm_bf16_images(const uint16_t* A, int lda, unsigned long long aView, const uint16_t* B, int ldb, unsigned long long bView,
-                     const GemmOut& o, int epi, hipStream_t s) {
-  return launch128h(A, lda, B, ldb, o, epi, s, aView, bView);
+                     const GemmOut& o, int epi, hipStream_t s, bool aKMajor, bool bKMajor) {
+  return launch128h(A, lda, B, ldb, o, epi, s, aView, bView, aKMajor, bKMajor);
 }
 }  // namespace w2l
 

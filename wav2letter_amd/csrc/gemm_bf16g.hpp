@@ -390,13 +390,17 @@ __global__ __launch_bounds__(512, 1) void gemm256h_kernel(GOp aop, GOp bop, Gemm
 // ta / tb: the operand is k-MAJOR -- A stored [K][lda] (lda >= M), B stored [K][ldb] (ldb >= N), lda / ldb multiples of 8, base
 // 16-byte aligned; rows k >= K are never read (the buffer ends there: out-of-range loads return 0), so a k-contiguous partner's
 // zero padding is not needed on this side.  128 x 128 kernel only.
+// ta with aView: a k-major A whose rows OVERLAP (lda < M: column i of row k is element i of the run that starts at row k -- the
+// filter gradient of conv_bf16.hip, all taps in one product).  The buffer then ends with the view, not with row K: the rows K ..
+// Kp of the last K tile are read, and must meet zeros of B (a k-major B ends at its row K).
 inline int launch128h(const uint16_t* A, int lda, const uint16_t* B, int ldb, GemmOut o, int epi, hipStream_t s,
                       unsigned long long aView = 0, unsigned long long bView = 0, bool ta = false, bool tb = false) {
   const int Kp = (o.K + 63) / 64 * 64;
   if ((lda & 1) || (ldb & 1) || (!ta && !aView && lda < Kp) || (!tb && !bView && ldb < Kp) || (((uintptr_t)A | (uintptr_t)B) & 3)) return W2L_EINVAL;
-  if ((ta && ((lda & 7) || lda < o.M || (((uintptr_t)A) & 15) || aView)) || (tb && ((ldb & 7) || ldb < o.N || (((uintptr_t)B) & 15) || bView)))
+  if ((ta && ((lda & 7) || (!aView && lda < o.M) || (((uintptr_t)A) & 15) || (aView && !tb))) ||
+      (tb && ((ldb & 7) || ldb < o.N || (((uintptr_t)B) & 15) || bView)))
     return W2L_EINVAL;
-  const unsigned long long ab = ta ? 2ull * (unsigned long long)o.K * lda : aView ? aView : 2ull * ((unsigned long long)(o.M - 1) * lda + Kp);
+  const unsigned long long ab = aView ? aView : ta ? 2ull * (unsigned long long)o.K * lda : 2ull * ((unsigned long long)(o.M - 1) * lda + Kp);
   const unsigned long long bb = tb ? 2ull * (unsigned long long)o.K * ldb : bView ? bView : 2ull * ((unsigned long long)(o.N - 1) * ldb + Kp);
   if (ab >= 0x7fffffffull || bb >= 0x7fffffffull) return W2L_EUNSUPPORTED;
   const double flops = 2.0 * o.M * (double)o.N * o.K;

@@ -51,6 +51,7 @@ int main(int argc, char** argv) {
     if (it == cfg.end()) throw std::invalid_argument("Invalid config loaded from " + am);
     w2l::Flags flags = w2l::parseFlagsText(it->second);
     for (auto& kv : cmd.kv) flags.kv.push_back(kv);
+    w2l::checkFlagDependencies(flags);
 
     const std::string criterionName = flags.get("criterion", "asg");
     const int batch = (int)flags.geti("batchsize", 1);
@@ -69,6 +70,7 @@ int main(int argc, char** argv) {
     auto scalemode = getCriterionScaleMode(flags.get("onorm", "none"), flags.getb("sqnorm", false));
     std::shared_ptr<fl::Module> network = fl::pkg::runtime::ModulePlugin(archPath).arch(nFeat, numClasses);
     if (flags.getb("fl_amp_use_mixed_precision", false)) setMixedPrecision(network, true);
+    if (flags.getb("fl_amp_use_mixed_precision", false) && flags.getb("w2l_amp_convs", false)) setMixedPrecisionConvolutions(network, true);
     std::shared_ptr<SequenceCriterion> criterion;
     if (criterionName == "ctc") criterion = std::make_shared<CTCLoss>(scalemode);
     else if (criterionName == "asg") criterion = std::make_shared<ASGLoss>(numClasses, scalemode, flags.getd("transdiag", 0.0));

@@ -157,6 +157,12 @@ Flags parseFlagsText(const std::string& text) {
 
 Flags parseFlagsFile(const std::string& path) { return parseFlagsText(readFile(path)); }
 
+void checkFlagDependencies(const Flags& flags) {
+  if (flags.getb("w2l_amp_convs", false) && !flags.getb("fl_amp_use_mixed_precision", false))
+    throw std::invalid_argument("--w2l_amp_convs=true needs --fl_amp_use_mixed_precision=true: the bf16 wide convolutions are the second "
+                                "level of the mixed-precision mode");
+}
+
 // getCriterionScaleMode(FLAGS_onorm, FLAGS_sqnorm)  (recipes/slimIPL/src/Train.cpp:389)
 int criterionScaleMode(const std::string& onorm, bool sqnorm) {
   if (onorm == "none" || onorm.empty()) return W2L_SCALE_NONE;

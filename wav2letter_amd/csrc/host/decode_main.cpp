@@ -109,6 +109,7 @@ int main(int argc, char** argv) {
     w2l::Flags flags = w2l::parseFlagsText(it->second);
     const std::string criterionName = flags.get("criterion", "asg");   // the checkpoint's: its parameters are the checkpoint's too
     for (auto& kv : cmd.kv) flags.kv.push_back(kv);
+    w2l::checkFlagDependencies(flags);
 
     // ---- what this build does not decode
     if (flags.get("criterion", "asg") != criterionName)
@@ -181,6 +182,7 @@ int main(int argc, char** argv) {
     auto scalemode = getCriterionScaleMode(flags.get("onorm", "none"), flags.getb("sqnorm", false));
     std::shared_ptr<fl::Module> network = fl::pkg::runtime::ModulePlugin(archPath).arch(nFeat, numClasses);
     if (flags.getb("fl_amp_use_mixed_precision", false)) setMixedPrecision(network, true);
+    if (flags.getb("fl_amp_use_mixed_precision", false) && flags.getb("w2l_amp_convs", false)) setMixedPrecisionConvolutions(network, true);
     std::shared_ptr<CTCLoss> ctc;
     std::shared_ptr<ASGLoss> asgCrit;
     std::shared_ptr<SequenceCriterion> criterion;

@@ -846,6 +846,7 @@ class PlannedNet : public fl::Sequential {
     if (useEval) {
       if (!evalNet_) {
         evalNet_ = w2l::buildSequentialFromText(archText_, archNFeat_, archNLabel_);
+        evalNet_->setMixedPrecisionConvs(net_->mixedPrecisionConvs());
         if (!bucketOffsets_.empty()) evalNet_->setGradBuckets(bucketOffsets_, bucketEvents_);
       }
       if (B != evalB_ || T != evalT_) {
@@ -908,6 +909,13 @@ class PlannedNet : public fl::Sequential {
   float* paramPtr() { return (float*)paramArena_.get(); }
   float* gradPtr() { return (float*)gradArena_.get(); }
   bool mixed_ = false;
+  // the wide convolutions' bf16 images belong to the plan: both graphs plan again at their next forward
+  void setMixedConvs(bool on) {
+    if (net_->mixedPrecisionConvs() == on) return;
+    net_->setMixedPrecisionConvs(on);
+    if (evalNet_) evalNet_->setMixedPrecisionConvs(on);
+    B_ = T_ = evalB_ = evalT_ = -1;
+  }
   std::string archSha_;             // sha-256 of the arch text this network was built from (checkpoint header)
   int nFeat() const { return nFeat_; }
   int nLabel() const { return nLabel_; }
@@ -1093,6 +1101,9 @@ FlatView flatParameters(const std::shared_ptr<fl::Module>& network) {
 }
 void setMixedPrecision(const std::shared_ptr<fl::Module>& network, bool on) {
   if (auto* p = plannedOf(network.get())) p->mixed_ = on;
+}
+void setMixedPrecisionConvolutions(const std::shared_ptr<fl::Module>& network, bool on) {
+  if (auto* p = plannedOf(network.get())) p->setMixedConvs(on);
 }
 uint32_t networkStep(const std::shared_ptr<fl::Module>& network) {
   auto* p = plannedOf(network.get());

@@ -506,6 +506,8 @@ class Conv2DLayer : public Layer {
   const float* xSaved = nullptr;
   // mixed precision: the sub-sampling convolutions of the TDS recipes (<= 32 channels over the mel rows) on the bf16 kernels
   size_t convImgElems = 0, convImgFOff = 0, convImgBOff = 0;
+  // mixed precision, second level (Planner::bf16Convs): the wide time convolutions at H == 1 on the bf16 GEMM engine (conv_bf16.hip)
+  size_t wideImgElems = 0, wideImgFOff = 0, wideImgBOff = 0;
 
   std::string name() const override { return wn.on ? "WeightNorm(Conv2D)" : "Conv2D"; }
   void registerParams(std::vector<ParamInfo>& t) override {
@@ -549,6 +551,11 @@ class Conv2DLayer : public Layer {
     if (kh > 1) { xeOff = pl.alloc(nIn * kh); dxeOff = pl.alloc(nIn * kh); }
     convImgElems = H % 16 == 0 ? w2l_tds_conv_bf16_image_elems(&d) : 0;
     if (convImgElems) { convImgFOff = pl.allocBf16(convImgElems); convImgBOff = pl.allocBf16(convImgElems); }
+    wideImgElems = (pl.bf16Convs && !convImgElems) ? w2l_conv_bf16_image_elems(&d) : 0;
+    if (wideImgElems) {
+      wideImgFOff = pl.allocBf16(wideImgElems); wideImgBOff = pl.allocBf16(wideImgElems);
+      pl.wantConvScratch(w2l_conv_bf16_scratch_elems(&d));
+    }
     if (wn.on) {
       wn.wOff = pl.alloc((size_t)wn.K * wn.N);
       wn.dwOff = pl.alloc((size_t)wn.K * wn.N);
@@ -575,14 +582,25 @@ class Conv2DLayer : public Layer {
       w2lCheck(w2l_tds_conv_bf16_forward(&d, x, bfp(arena, convImgFOff), hasBias ? b.w(c) : nullptr, y, fuseRelu ? 1 : 0, c.stream), "conv fwd bf16");
       return;
     }
+    if (wide(c)) {   // the same contract on the wide kernels: images of the (weight-normalised) fp32 weight once per step
+      w2lCheck(w2l_conv_bf16_prepare(&d, wt, bfp(arena, wideImgFOff), bfp(arena, wideImgBOff), c.stream), "wide conv images");
+      w2lCheck(w2l_conv_bf16_forward(&d, x, bfp(arena, wideImgFOff), hasBias ? b.w(c) : nullptr, y, fuseRelu ? 1 : 0, c.convScratch, c.stream),
+               "wide conv fwd bf16");
+      return;
+    }
     w2lCheck(w2l_conv_forward(&d, x, wt, hasBias ? b.w(c) : nullptr, y, fuseRelu ? 1 : 0, c.stream), "conv fwd");
   }
+  bool wide(const Ctx& c) const { return c.bf16 && wideImgElems && c.convScratch; }
   void backward(Ctx& c, float* arena, const float* dy, float*& dx, bool needDx) override {
     float* dym = const_cast<float*>(dy);
     if (fuseRelu) w2lCheck(w2l_mask_backward(dy, arena + yOff, dym, nOut, 1.f, c.stream), "conv relu bwd");
     float* dwt = wn.on ? arena + wn.dwOff : w.g(c);
     const bool bf = c.bf16 && convImgElems;
-    if (bf) {
+    const bool wd = wide(c);
+    if (wd) {
+      w2lCheck(w2l_conv_bf16_backward_filter_bias(&d, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, c.convScratch, c.stream),
+               "wide conv bwd filter + bias bf16");
+    } else if (bf) {
       w2lCheck(w2l_tds_conv_bf16_backward_filter_bias(&d, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, c.stream), "conv bwd filter + bias bf16");
     } else {
       w2lCheck(w2l_conv_backward_filter(&d, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, c.stream), "conv bwd filter");
@@ -590,7 +608,11 @@ class Conv2DLayer : public Layer {
     const float* wt = wn.on ? arena + wn.wOff : w.w(c);
     if (needDx) {
       dx = arena + dxOff;
-      if (bf && kh > 1) {
+      if (wd) {
+        w2lCheck(w2l_conv_bf16_backward_data(&d, dym, bfp(arena, wideImgBOff), nullptr, kh > 1 ? arena + dxeOff : dx, c.convScratch, c.stream),
+                 "wide conv bwd data bf16");
+        if (kh > 1) w2lCheck(w2l_hexpand_backward(arena + dxeOff, dx, (size_t)d.B * d.T, d.H, cin, kh, padH, c.stream), "conv H fold");
+      } else if (bf && kh > 1) {
         w2lCheck(w2l_tds_conv_bf16_backward_data(&d, dym, bfp(arena, convImgBOff), nullptr, arena + dxeOff, c.stream), "conv bwd data bf16");
         w2lCheck(w2l_hexpand_backward(arena + dxeOff, dx, (size_t)d.B * d.T, d.H, cin, kh, padH, c.stream), "conv H fold");
       } else if (bf) {
@@ -1373,6 +1395,7 @@ void Sequential::finalize() {
 
 size_t Sequential::plan(int B, int T, int nFeat) {
   Planner pl;
+  pl.bf16Convs = bf16Convs_;
   in_ = actInput(B, T, nFeat);
   inOff_ = pl.alloc(in_.numel());
   Act a = in_;
@@ -1399,6 +1422,8 @@ size_t Sequential::plan(int B, int T, int nFeat) {
   ok = ok && rest == std::vector<FKind>{F_TIME, F_BATCH};
   if (!ok) throw std::invalid_argument("network output must be (NLABEL, T, B, 1); got " + out_.str());
   ys_.assign(layers_.size(), nullptr);
+  convScratchElems_ = pl.convScratch();
+  convScratchOff_ = convScratchElems_ ? pl.allocBf16(convScratchElems_) : 0;
   return pl.used();
 }
 
@@ -1408,6 +1433,7 @@ const float* Sequential::forward(Ctx& c, float* arena, const float* xRef) {
   w2lCheck(w2l_transpose(xRef, x, in_.B, in_.F, in_.T, c.stream), "input transpose");
   const float* cur = x;
   c.imgOf = nullptr;
+  c.convScratch = convScratchElems_ ? bfp(arena, convScratchOff_) : nullptr;
   for (size_t i = 0; i < layers_.size(); ++i) {
     float* y = nullptr;
     const float* noteBefore = c.imgOf;
@@ -1426,6 +1452,7 @@ const float* Sequential::forward(Ctx& c, float* arena, const float* xRef) {
 
 void Sequential::backward(Ctx& c, float* arena, const float* dOut) {
   const float* dy = dOut;
+  c.convScratch = convScratchElems_ ? bfp(arena, convScratchOff_) : nullptr;
   // first layer with parameters: nothing before it needs a data gradient
   size_t firstParam = 0;
   for (size_t i = 0; i < layers_.size(); ++i) {

@@ -163,6 +163,7 @@ int main(int argc, char** argv) {
       w2l::Flags one = w2l::parseFlagsText(argv[i]);
       for (auto& kv : one.kv) flags.kv.push_back(kv);
     }
+    w2l::checkFlagDependencies(flags);
     const std::string criterionName = flags.get("criterion", "asg");    // the reference default (FLAGS_criterion)
     const int batch = (int)flags.geti("batchsize", 1);
     const int nFeat = flags.getb("mfcc", false) ? (int)flags.geti("mfcccoeffs", 13) * 3
@@ -233,6 +234,10 @@ int main(int argc, char** argv) {
     if (flags.getb("fl_amp_use_mixed_precision", false)) {
       setMixedPrecision(network, true);   // bf16 multiplies in the fl::Linear GEMMs, fp32 master weights / criterion
       std::cout << "Mixed precision training enabled (bf16 matrix multiplies, fp32 accumulation and storage)" << std::endl;
+      if (flags.getb("w2l_amp_convs", false)) {
+        setMixedPrecisionConvolutions(network, true);   // ... and in the wide time convolutions at H == 1 (conv_glu, Transformer front end)
+        std::cout << "Mixed precision: the wide time convolutions multiply bf16 operands too (--w2l_amp_convs)" << std::endl;
+      }
     }
     std::shared_ptr<SequenceCriterion> criterion;
     if (criterionName == "ctc") criterion = std::make_shared<CTCLoss>(scalemode);
@@ -263,6 +268,7 @@ int main(int argc, char** argv) {
     if (useEma) {
       networkEMA = fl::pkg::runtime::ModulePlugin(archPath).arch(nFeat, numClasses);
       if (flags.getb("fl_amp_use_mixed_precision", false)) setMixedPrecision(networkEMA, true);
+      if (flags.getb("fl_amp_use_mixed_precision", false) && flags.getb("w2l_amp_convs", false)) setMixedPrecisionConvolutions(networkEMA, true);
     }
     // (the file of the averaged network holds the network alone, Train.cpp:776-781: a parameter-free criterion fills the container's slot)
     std::shared_ptr<fl::Module> emaFileCrit = std::make_shared<CTCLoss>(scalemode);

@@ -436,6 +436,21 @@ W2L_API int w2l_trainer_bind_state2(void* h, float* state2) {
 }
 W2L_API int w2l_trainer_set_mixed_precision(void* h, int on) { ((Trainer*)h)->mixedPrecision = on != 0; return W2L_OK; }
 
+// second level of the mixed-precision mode: the wide time convolutions (H == 1, >= 32 channels: the conv_glu recipes, the
+// Transformer front end) on bf16 operands too, wherever w2l_conv_bf16_image_elems has a kernel.  It acts only while
+// w2l_trainer_set_mixed_precision is on.  The plan holds the layers' weight images and the image scratch: call before
+// w2l_trainer_plan -- a change after it drops the plan (plan and bind again, as after w2l_trainer_set_linseg).
+W2L_API int w2l_trainer_set_mixed_precision_convs(void* h, int on) {
+  if (!h) return W2L_EINVAL;
+  Trainer* t = (Trainer*)h;
+  if (t->net->mixedPrecisionConvs() == (on != 0)) return W2L_OK;
+  t->net->setMixedPrecisionConvs(on != 0);
+  t->arenaFloats = 0;
+  t->params = t->grads = t->mom = t->arena = nullptr;
+  t->critWs = nullptr;
+  return W2L_OK;
+}
+
 // slimIPL's dynamic dropout: the `TR` layers' probabilities from the next forward on (negative: the arch line's)
 W2L_API int w2l_trainer_set_dropout(void* h, double pDropout, double pLayerDrop) {
   if (!h || !(pDropout < 1.0) || !(pLayerDrop < 1.0)) return W2L_EINVAL;   // (NaN fails the comparison)
@@ -450,5 +465,5 @@ W2L_API int w2l_arch_check(const char* archText, int nFeat, int nLabel, int* num
   TRY(nullptr, { auto v = parseArch(archText, nFeat, nLabel); if (numLayers) *numLayers = (int)v.size(); });
 }
 W2L_API int w2l_flags_check(const char* flagsText, int* numFlags) {
-  TRY(nullptr, { auto f = parseFlagsText(flagsText); if (numFlags) *numFlags = (int)f.kv.size(); });
+  TRY(nullptr, { auto f = parseFlagsText(flagsText); checkFlagDependencies(f); if (numFlags) *numFlags = (int)f.kv.size(); });
 }

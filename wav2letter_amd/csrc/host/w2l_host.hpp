@@ -91,6 +91,9 @@ struct Ctx {
   const float* imgOf = nullptr;
   size_t imgRowsOff = 0, imgTransOff = 0;
   int imgRows = 0, imgCols = 0;
+  // mixed precision, second level: the image scratch the wide time convolutions share (conv_bf16.hip; Sequential::plan sizes it for
+  // the largest of them, forward / backward point here).  Null: the switch is off.
+  uint16_t* convScratch = nullptr;
 };
 
 class Planner {  // bump allocator over the activation arena (sizes only until bound)
@@ -98,8 +101,14 @@ class Planner {  // bump allocator over the activation arena (sizes only until b
   size_t alloc(size_t floats) { size_t o = used_; used_ += (floats + 63) / 64 * 64; return o; }
   size_t allocBf16(size_t elements) { return alloc((elements + 1) / 2); }   // a bf16 image, addressed in float slots
   size_t used() const { return used_; }
+  // mixed precision, second level (Sequential::setMixedPrecisionConvs): the wide time convolutions plan their bf16 weight images
+  // and ask for ONE scratch between them -- its contents mean nothing between two calls, so the largest request serves all
+  bool bf16Convs = false;
+  void wantConvScratch(size_t bf16Elements) { if (bf16Elements > convScratch_) convScratch_ = bf16Elements; }
+  size_t convScratch() const { return convScratch_; }
  private:
   size_t used_ = 0;
+  size_t convScratch_ = 0;
 };
 
 class Layer {
@@ -130,6 +139,11 @@ class Sequential {
   void finalize();  // registers params, assigns offsets and rng streams
   // the probabilities every `TR` layer uses from the next forward on (negative: the arch line's); no new plan is needed
   void setTransformerDropout(double pDropout, double pLayerDrop) { for (auto& l : layers_) l->setTransformerDropout(pDropout, pLayerDrop); }
+  // mixed precision, second level: the wide time convolutions (H == 1, >= 32 channels) on bf16 operands too, wherever
+  // w2l_conv_bf16_image_elems has a kernel.  Read by plan(): set it BEFORE planning (or plan again); effective only in a pass whose
+  // Ctx::bf16 is set.
+  void setMixedPrecisionConvs(bool on) { bf16Convs_ = on; }
+  bool mixedPrecisionConvs() const { return bf16Convs_; }
   const std::vector<ParamInfo>& params() const { return params_; }
   size_t paramFloats() const { return paramFloats_; }
 
@@ -160,6 +174,8 @@ class Sequential {
   size_t paramFloats_ = 0;
   Act in_, out_;
   size_t inOff_ = 0;
+  bool bf16Convs_ = false;
+  size_t convScratchOff_ = 0, convScratchElems_ = 0;
   std::vector<size_t> dOff_;  // gradient buffer per layer boundary
   std::vector<Act> acts_;
   std::vector<float*> ys_;
@@ -238,6 +254,9 @@ struct Flags {
 Flags parseFlagsText(const std::string& text);
 Flags parseFlagsFile(const std::string& path);
 int criterionScaleMode(const std::string& onorm, bool sqnorm);  // getCriterionScaleMode
+// flags that only mean something beside another one (--w2l_amp_convs without --fl_amp_use_mixed_precision): std::invalid_argument.
+// Host logic: the drivers call it on their final flag set before anything touches the device.
+void checkFlagDependencies(const Flags& flags);
 
 void hipCheck(hipError_t e, const char* what);
 void w2lCheck(int status, const char* what);

@@ -325,3 +325,35 @@ def tds_conv_bf16_backward(x, dy, imgs, d, add=None, with_bias=False):
         return dx, dw, db
     check(_lib.lib().w2l_tds_conv_bf16_backward_filter(C.byref(d), _p(x), _p(dy), _p(dw), _s()), "tds_conv_bf16_backward_filter")
     return dx, dw
+
+
+def conv_bf16(x, w, bias, padl, padr, relu=False, stride=1):
+    """the wide time convolution at H == 1 on bf16-rounded operands (w2l_conv_bf16_*): x [B][T][1][Cin], w [kw][Cin][Cout] ->
+    (y [B][To][1][Cout], (weight images, scratch), descriptor); None when the library has no kernel for the geometry"""
+    import ctypes as C
+    d = conv_desc(x, w, stride, padl, padr)
+    L = _lib.lib()
+    n = L.w2l_conv_bf16_image_elems(C.byref(d))
+    if not n:
+        return None
+    imgs = torch.empty(2, n, dtype=torch.bfloat16, device=x.device)
+    scratch = torch.empty(L.w2l_conv_bf16_scratch_elems(C.byref(d)), dtype=torch.bfloat16, device=x.device)
+    check(L.w2l_conv_bf16_prepare(C.byref(d), _p(w), _p(imgs[0]), _p(imgs[1]), _s()), "conv_bf16_prepare")
+    To = L.w2l_conv_out_len(d.T, d.kw, stride, padl, padr)
+    y = torch.empty(d.B, To, d.H, d.Cout, device=x.device, dtype=torch.float32)
+    check(L.w2l_conv_bf16_forward(C.byref(d), _p(x), _p(imgs[0]), _p(bias), _p(y), int(relu), _p(scratch), _s()), "conv_bf16_forward")
+    return y, (imgs, scratch), d
+
+
+def conv_bf16_backward(x, dy, imgs, d, add=None, with_bias=False):
+    """(dx, dw[, db]) of the same convolution (imgs: the pair conv_bf16 returned): dx = add + conv^T(dy), dw = x (*) dy on the
+    bf16-rounded operands; with_bias: the bias gradient, the column sums of the rounded dy"""
+    import ctypes as C
+    imgs, scratch = imgs
+    L = _lib.lib()
+    dx = torch.empty_like(x)
+    check(L.w2l_conv_bf16_backward_data(C.byref(d), _p(dy), _p(imgs[1]), _p(add), _p(dx), _p(scratch), _s()), "conv_bf16_backward_data")
+    dw = torch.empty(d.kw, d.Cin, d.Cout, dtype=torch.float32, device=x.device)
+    db = torch.empty(d.Cout, dtype=torch.float32, device=x.device) if with_bias else None
+    check(L.w2l_conv_bf16_backward_filter_bias(C.byref(d), _p(x), _p(dy), _p(dw), _p(db), _p(scratch), _s()), "conv_bf16_backward_filter_bias")
+    return (dx, dw, db) if with_bias else (dx, dw)

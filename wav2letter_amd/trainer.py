@@ -46,6 +46,7 @@ def _lib_tr():
         L.w2l_trainer_bind_eval.argtypes = [vp, vp, sz]
         L.w2l_trainer_set_step.argtypes = [vp, u32]
         L.w2l_trainer_set_mixed_precision.argtypes = [vp, i]
+        L.w2l_trainer_set_mixed_precision_convs.argtypes = [vp, i]
         L.w2l_trainer_set_optimizer.argtypes = [vp, i, i]
         L.w2l_trainer_set_dropout.argtypes = [vp, d, d]
         L.w2l_trainer_bind_state2.argtypes = [vp, vp]
@@ -86,13 +87,14 @@ class _EvalPlan:
     """a second C trainer over the same arch and criterion, planned for one evaluation shape: its own activation arena and
     evaluation buffer, the training trainer's parameter arena (bound per call).  The training plan is never re-planned."""
 
-    def __init__(self, ctor, B, T, Lt, device):
+    def __init__(self, ctor, B, T, Lt, device, convs=False):
         L = _lib_tr()
         self.L = L
         arch_text, nfeat, nlabel, criterion, scalemode, transdiag = ctor
         self.h = L.w2l_trainer_create(arch_text.encode(), nfeat, nlabel, criterion.encode(), int(scalemode), float(transdiag))
         if not self.h:
             raise _lib.W2LInvalidArgument(L.w2l_host_last_error().decode())
+        _check(L.w2l_trainer_set_mixed_precision_convs(self.h, int(convs)), "mixed precision convolutions")   # (read by the plan)
         af, cw, to = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
         _check(L.w2l_trainer_plan(self.h, B, T, Lt, C.byref(af), C.byref(cw), C.byref(to)), "evaluate plan")
         self.Tout = to.value
@@ -128,6 +130,7 @@ class Trainer:
         self._ctor = (arch_text, nfeat, nlabel, criterion, scalemode, transdiag)
         self._eval_plans = {}
         self._mixed = False
+        self._mixed_convs = False
         self.h = L.w2l_trainer_create(arch_text.encode(), nfeat, nlabel, criterion.encode(), int(scalemode),
                                       float(transdiag))
         if not self.h:
@@ -283,7 +286,7 @@ class Trainer:
         key = (B, T, int(target.shape[1]))
         ev = self._eval_plans.pop(key, None)
         if ev is None:
-            ev = _EvalPlan(self._ctor, *key, self.device)
+            ev = _EvalPlan(self._ctor, *key, self.device, self._mixed_convs)
             while len(self._eval_plans) >= self._EVAL_PLANS:
                 self._eval_plans.pop(next(iter(self._eval_plans)))
         self._eval_plans[key] = ev
@@ -317,10 +320,19 @@ class Trainer:
         _check(self.L.w2l_trainer_skipped_updates(self.h, C.byref(n), self._stream()), "skipped_updates")
         return n.value
 
-    def set_mixed_precision(self, on=True):
-        """bf16 multiplies (fp32 accumulate / storage / master weights) in the network's fl::Linear GEMMs"""
+    def set_mixed_precision(self, on=True, convs=False):
+        """bf16 multiplies (fp32 accumulate / storage / master weights) in the network's fl::Linear GEMMs, the TDS convolutions and
+        the Transformer block; convs=True: the second level -- the wide time convolutions at H == 1 (conv_glu, the Transformer
+        front end) on bf16 operands too (w2l_conv_bf16_*), effective only while `on`.  Their weight images and image scratch
+        belong to the plan: a change of `convs` plans the current shape again (and drops the evaluation plans)."""
         _check(self.L.w2l_trainer_set_mixed_precision(self.h, int(bool(on))), "mixed precision")
         self._mixed = bool(on)
+        if bool(convs) != self._mixed_convs:
+            _check(self.L.w2l_trainer_set_mixed_precision_convs(self.h, int(bool(convs))), "mixed precision convolutions")
+            self._mixed_convs = bool(convs)
+            self._eval_plans.clear()
+            if self.B:
+                self.plan(self.B, self.T, self.Lt)
 
     def set_optimizer(self, netoptim="sgd", critoptim="sgd"):
         """--netoptim / --critoptim of the reference Trainer (Train.cpp:577-582): "sgd" (momentum) "adagrad" or "adadelta" (rho 0.9, eps 1e-8:
