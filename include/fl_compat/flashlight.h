@@ -494,6 +494,37 @@ FL_COMPAT_API CriterionScaleMode getCriterionScaleMode(const std::string& onorm,
 FL_COMPAT_API std::shared_ptr<fl::Sequential> buildSequentialModule(const std::string& archfile, int64_t nFeatures, int64_t nClasses);
 FL_COMPAT_API std::shared_ptr<fl::Sequential> buildSequentialModuleFromText(const std::string& archText, int64_t nFeatures, int64_t nClasses);
 
+// fl_compat extension: the chunked streaming forward (w2l_stream_*, include/w2l_hip.h) over a network a plugin or an arch file
+// produced.  `slots` concurrent streams, at most `maxChunk` input frames per slot and step; for any utterance and any split of it
+// into chunks the concatenated emissions equal the network's eval-mode forward of that utterance alone (fp32 parity).  The
+// session reads the network's parameter arena at every step and keeps the network alive.  A network with a line that cannot be
+// streamed (TR, M, GLU, LN over time, TDS with lnIncludeTime = 1, SAME padding at a stride above 1) or in mixed-precision mode
+// throws std::invalid_argument naming the line.
+class FL_COMPAT_API StreamingSession {
+ public:
+  StreamingSession(std::shared_ptr<fl::Sequential> network, int slots, int maxChunk);
+  ~StreamingSession();
+  StreamingSession(const StreamingSession&) = delete;
+  StreamingSession& operator=(const StreamingSession&) = delete;
+  int slots() const { return slots_; }
+  int maxChunk() const { return maxChunk_; }
+  int maxOut() const { return maxOut_; }       // emission frames one step can return per slot
+  int numLabels() const { return nLabel_; }
+  // features (maxChunk, NFEAT, 1, slots) f32: the first counts[s] frames of slot s are used.  start[s]: the slot begins a new
+  // utterance; finish[s]: these frames are its last, the network flushes (either vector may be empty = all 0).  Returns the
+  // emissions (NLABEL, maxOut, slots) -- a view of the session's state, valid until the next step -- and fills nOut[s], the new
+  // frames of slot s (host arithmetic: the step enqueues on fl::currentStream() and does not synchronise).
+  af::array step(const af::array& features, const std::vector<int>& counts, const std::vector<int>& start, const std::vector<int>& finish,
+                 std::vector<int>& nOut);
+  void reset(int slot);                        // closes a slot and discards its state
+
+ private:
+  std::shared_ptr<fl::Sequential> net_;
+  std::shared_ptr<void> state_;
+  void* h_ = nullptr;
+  int slots_ = 0, maxChunk_ = 0, maxOut_ = 0, nFeat_ = 0, nLabel_ = 0;
+};
+
 class FL_COMPAT_API SequenceCriterion : public fl::Container {
  public:
   // inputs {emission (N, T, B) f32, target (L, B) s32 (padded with negative values)} -> {loss (B)}

@@ -881,6 +881,57 @@ int w2l_profile_launches(int kind, int maxRows, double* ms, double* work, int* d
 int w2l_arch_check(const char* archText, int nFeat, int nLabel, int* numLayers);
 int w2l_flags_check(const char* flagsText, int* numFlags);
 
+/* ---- chunked streaming forward (csrc/host/stream.cpp, csrc/stream.hip) --------------------------------------------------
+ * A streaming SESSION runs the network of an arch file on audio as it arrives: S slots (concurrent streams), at most maxChunk
+ * input frames per slot and step.  Parameter order and layout are the trainer's, so a checkpoint's arena loads unchanged.
+ * For any utterance and ANY split of it into chunks the concatenated emissions equal w2l_trainer_forward(train = 0) of that
+ * utterance alone (fp32 parity, not bitwise: kernel variants depend on the row count) and the frame count equals its Tout.
+ * Streamable lines: V, RO, SAUG, DO (identity in eval), PD on the time axis, C / C1 / C2 with explicit padding (or SAME at
+ * stride 1), R, LN without the time axis, TDS with lnIncludeTime = 0, L, WN around C / L.  Any other line -- TR, M, GLU, LN over
+ * time, TDS with lnIncludeTime = 1, SAME padding at a stride above 1 -- is refused at creation with W2L_EUNSUPPORTED and a
+ * w2l_host_last_error() that names the line; so is a trainer in mixed-precision mode (fp32 only).
+ * create / create_for_trainer / query / counts / slot_state / reset are host arithmetic and need no device.
+ *   w2l_stream_create(archText, ...)       parameters come from w2l_stream_bind
+ *   w2l_stream_create_for_trainer(h, ...)  arch of the trainer; parameters are the trainer's bound arena at every step unless
+ *                                          w2l_stream_bind gives others.  The trainer must outlive the session.
+ *   w2l_stream_query                       maxOut (emission frames a slot can get from one step) and the state bytes for
+ *                                          (arch, slots, maxChunk) without keeping a session
+ *   w2l_stream_bind                        params: device arena of w2l_stream_param_floats floats (may be NULL over a trainer);
+ *                                          state: device buffer of w2l_stream_state_bytes, 256-byte aligned, the session's
+ *                                          alone (carries, windows, activations); contents need no initialisation
+ *   w2l_stream_step                        x: device [S][nFeat][maxChunk] float32, only the first n[s] columns of slot s are
+ *                                          used; n / start / finish / nOut: HOST int [S] (start, finish may be NULL = all 0).
+ *                                          start[s]: the slot begins a new utterance, its state is discarded; finish[s]: the
+ *                                          frames given are the utterance's last -- the network flushes and the slot closes.
+ *                                          *out: device [S][maxOut][nLabel] inside the state buffer (NULL when no slot had
+ *                                          work), rows [0, nOut[s]) of slot s are that slot's new emission frames; valid until
+ *                                          the next step.  nOut is host arithmetic: the step never synchronises.  Plain launches
+ *                                          on `stream` (use ONE stream per session); the count table of all layers goes to the
+ *                                          device with one async copy from pinned memory.
+ *                                          W2L_EINVAL before anything is enqueued: n[s] outside 0..maxChunk, frames or finish
+ *                                          for a slot that was never started, null pointers.
+ *   w2l_stream_counts                      the bookkeeping of a step alone (advances the host state exactly as a step would)
+ *   w2l_stream_slot_state                  active flag and the carry frame count of each time-extent layer of a slot
+ *   w2l_stream_reset                       closes a slot and discards its state
+ * w2l_stream_window: the hand-over kernel (see csrc/stream.hip): window = carry ++ new ++ zeros, the next carry and a TDS
+ * block's residual frames in one launch; tab: S device entries {carry frames | zero-carry flag << 30, new, nIn, consumed}. */
+int w2l_stream_create(const char* archText, int nFeat, int nLabel, int slots, int maxChunk, void** session);
+int w2l_stream_create_for_trainer(void* trainer, int slots, int maxChunk, void** session);
+void w2l_stream_destroy(void* session);
+int w2l_stream_query(const char* archText, int nFeat, int nLabel, int slots, int maxChunk, int* maxOut, size_t* stateBytes);
+int w2l_stream_max_out(void* session);
+size_t w2l_stream_state_bytes(void* session);
+size_t w2l_stream_param_floats(void* session);
+int w2l_stream_num_time_layers(void* session);
+int w2l_stream_bind(void* session, const float* params, void* state, size_t stateBytes);
+int w2l_stream_counts(void* session, const int* n, const int* start, const int* finish, int* nOut);
+int w2l_stream_slot_state(void* session, int slot, int* active, int* carry, int carryCap);
+int w2l_stream_step(void* session, const float* x, const int* n, const int* start, const int* finish, const float** out, int* nOut,
+                    void* stream);
+int w2l_stream_reset(void* session, int slot);
+int w2l_stream_window(const float* src, int srcRows, const float* carryIn, float* carryOut, int carryCap, float* win, int W,
+                      float* res, int resShift, int To, const int* tab, int S, int F, w2l_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

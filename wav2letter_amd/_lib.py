@@ -24,6 +24,10 @@ class W2LInvalidArgument(W2LError, ValueError):
     """mirrors the std::invalid_argument Flashlight's criteria throw"""
 
 
+class W2LUnsupported(W2LError):
+    """W2L_EUNSUPPORTED: outside what this build implements (a non-streamable arch line, ...)"""
+
+
 def _load(path):
     if not os.path.exists(path):
         raise W2LError(
@@ -219,6 +223,20 @@ class _SIGS:
     w2l_adagrad_step_guarded = (_i, [_p, _p, _p, _sz, _f, _f, _f, _f, _p, _p])
     w2l_adadelta_step_guarded = (_i, [_p, _p, _p, _p, _sz, _f, _f, _f, _f, _f, _p, _p])
     w2l_grad_guard = (_i, [_p, _p, _i, _p])
+    w2l_stream_create = (_i, [C.c_char_p, _i, _i, _i, _i, _p])
+    w2l_stream_create_for_trainer = (_i, [_p, _i, _i, _p])
+    w2l_stream_destroy = (None, [_p])
+    w2l_stream_query = (_i, [C.c_char_p, _i, _i, _i, _i, _p, _p])
+    w2l_stream_max_out = (_i, [_p])
+    w2l_stream_state_bytes = (_sz, [_p])
+    w2l_stream_param_floats = (_sz, [_p])
+    w2l_stream_num_time_layers = (_i, [_p])
+    w2l_stream_bind = (_i, [_p, _p, _p, _sz])
+    w2l_stream_counts = (_i, [_p, _p, _p, _p, _p])
+    w2l_stream_slot_state = (_i, [_p, _i, _p, _p, _i])
+    w2l_stream_step = (_i, [_p, _p, _p, _p, _p, _p, _p, _p])
+    w2l_stream_reset = (_i, [_p, _i])
+    w2l_stream_window = (_i, [_p, _i, _p, _p, _i, _p, _i, _p, _i, _i, _p, _i, _i, _p])
 
 
 class ConvDesc(C.Structure):

@@ -1008,6 +1008,48 @@ std::shared_ptr<fl::Sequential> buildSequentialModule(const std::string& archfil
   return buildSequentialModuleFromText(w2l::readFile(archfile), nFeatures, nClasses);
 }
 
+
+// ---- chunked streaming forward over a planned network (host/stream.cpp)
+StreamingSession::StreamingSession(std::shared_ptr<fl::Sequential> network, int slots, int maxChunk) : net_(std::move(network)), slots_(slots), maxChunk_(maxChunk) {
+  if (!net_) throw std::invalid_argument("StreamingSession: null network");
+  std::shared_ptr<fl::Sequential> planned = net_->planned();
+  PlannedNet* pn = dynamic_cast<PlannedNet*>(planned ? planned.get() : net_.get());
+  if (!pn) throw std::invalid_argument("StreamingSession: the network is not a planned arch pipeline (an arch file or layer objects)");
+  if (pn->mixed_) throw std::invalid_argument("StreamingSession: the network is in mixed-precision mode; the streaming step is fp32 only");
+  nFeat_ = (int)pn->archNFeat_;
+  nLabel_ = pn->archNLabel_ > 0 ? (int)pn->archNLabel_ : pn->impl().outAct().F;
+  const int st = w2l_stream_create(pn->archText_.c_str(), nFeat_, nLabel_, slots, maxChunk, &h_);
+  if (st != W2L_OK) throw std::invalid_argument(std::string("StreamingSession: ") + w2l_host_last_error());
+  maxOut_ = w2l_stream_max_out(h_);
+  const size_t bytes = w2l_stream_state_bytes(h_);
+  state_ = devAlloc(bytes);
+  if (w2l_stream_bind(h_, pn->paramPtr(), state_.get(), bytes) != W2L_OK) {
+    const std::string msg = w2l_host_last_error();
+    w2l_stream_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error("StreamingSession: " + msg);
+  }
+}
+StreamingSession::~StreamingSession() { if (h_) w2l_stream_destroy(h_); }
+af::array StreamingSession::step(const af::array& features, const std::vector<int>& counts, const std::vector<int>& start,
+                                 const std::vector<int>& finish, std::vector<int>& nOut) {
+  if (features.type() != af::f32 || features.dims(0) != maxChunk_ || features.dims(1) * features.dims(2) != nFeat_ || features.dims(3) != slots_)
+    throw std::invalid_argument("StreamingSession::step: features must be f32 (maxChunk, NFEAT, 1, slots)");
+  if ((int)counts.size() != slots_ || (!start.empty() && (int)start.size() != slots_) || (!finish.empty() && (int)finish.size() != slots_))
+    throw std::invalid_argument("StreamingSession::step: one count / flag per slot");
+  nOut.assign(slots_, 0);
+  const float* out = nullptr;
+  const int st = w2l_stream_step(h_, features.device<float>(), counts.data(), start.empty() ? nullptr : start.data(),
+                                 finish.empty() ? nullptr : finish.data(), &out, nOut.data(), S());
+  if (st == W2L_EINVAL) throw std::invalid_argument(std::string("StreamingSession::step: ") + w2l_host_last_error());
+  if (st != W2L_OK) throw std::runtime_error(std::string("StreamingSession::step: ") + w2l_host_last_error());
+  if (!out) return af::array();   // no slot had work
+  return af::array::wrap((void*)out, af::dim4(nLabel_, maxOut_, slots_), af::f32, state_);
+}
+void StreamingSession::reset(int slot) {
+  if (w2l_stream_reset(h_, slot) != W2L_OK) throw std::invalid_argument(std::string("StreamingSession::reset: ") + w2l_host_last_error());
+}
+
 }  // namespace speech
 }  // namespace pkg
 namespace {

@@ -160,6 +160,7 @@ static size_t addParam(std::vector<ParamInfo>& t, ParamInfo pi, P& h) {
 
 class ViewLayer : public Layer {
  public:
+  bool streamGeom(StreamGeom& g, std::string&) const override { g = StreamGeom(); return true; }   // frame-local
   long dims[4];
   std::string name() const override { return "View"; }
   Act plan(const Act& in, Planner&) override { return actView(in, dims); }
@@ -170,6 +171,7 @@ class ViewLayer : public Layer {
 
 class ReorderLayer : public Layer {
  public:
+  bool streamGeom(StreamGeom& g, std::string&) const override { g = StreamGeom(); return true; }   // frame-local
   int perm[4];
   std::string name() const override { return "Reorder"; }
   Act plan(const Act& in, Planner&) override { return actReorder(in, perm); }
@@ -180,6 +182,7 @@ class ReorderLayer : public Layer {
 
 class ReLULayer : public Layer {
  public:
+  bool streamGeom(StreamGeom& g, std::string&) const override { g = StreamGeom(); return true; }   // frame-local
   size_t n = 0;
   float* yPtr = nullptr;
   std::string name() const override { return "ReLU"; }
@@ -197,6 +200,7 @@ class ReLULayer : public Layer {
 
 class DropoutLayer : public Layer {
  public:
+  bool streamGeom(StreamGeom& g, std::string&) const override { g = StreamGeom(); return true; }   // frame-local
   double p = 0;
   size_t n = 0;
   std::string name() const override { return "Dropout"; }
@@ -214,6 +218,7 @@ class DropoutLayer : public Layer {
 
 class SpecAugmentLayer : public Layer {
  public:
+  bool streamGeom(StreamGeom& g, std::string&) const override { g = StreamGeom(); return true; }   // frame-local
   int fMaskF = 0, nFMask = 0, tMaskT = 0, nTMask = 0;
   float tMaskP = 1.f;
   int B = 0, T = 0, F = 0;
@@ -510,6 +515,14 @@ class Conv2DLayer : public Layer {
   size_t wideImgElems = 0, wideImgFOff = 0, wideImgBOff = 0;
 
   std::string name() const override { return wn.on ? "WeightNorm(Conv2D)" : "Conv2D"; }
+  bool streamGeom(StreamGeom& g, std::string& why) const override {
+    if (pad == -1 && stride > 1) { why = "SAME padding with a stride above 1 depends on the utterance length"; return false; }
+    if (stride > kw) { why = "a stride above the kernel width skips frames"; return false; }
+    const int p = pad == -1 ? samePad(4096, kw, 1) : pad;
+    g = StreamGeom();
+    g.timeExtent = true; g.kw = kw; g.stride = stride; g.padL = p + extraPadL; g.padR = p + extraPadR;
+    return true;
+  }
   void registerParams(std::vector<ParamInfo>& t) override {
     ParamInfo pw;
     pw.numel = (size_t)kw * kh * cin * cout;
@@ -540,6 +553,7 @@ class Conv2DLayer : public Layer {
     int pL, pR;
     if (pad == -1) pL = pR = samePad(in.T, kw, stride); else pL = pR = pad;
     pL += extraPadL; pR += extraPadR;
+    if (streamMode_) pL = pR = 0;   // the window carries the padding frames
     d = {in.B, in.T, H, kh * cin, cout, kw, stride, pL, pR};
     int To = w2l_conv_out_len(in.T, kw, stride, pL, pR);
     if (To <= 0) throw std::invalid_argument("Conv2D: input too short: " + in.str());
@@ -632,6 +646,7 @@ class Conv2DLayer : public Layer {
 
 class LinearLayer : public Layer {
  public:
+  bool streamGeom(StreamGeom& g, std::string&) const override { g = StreamGeom(); return true; }   // frame-local
   int in, out;
   bool hasBias = true, fuseRelu = false;
   WNState wn;
@@ -764,6 +779,13 @@ class LinearLayer : public Layer {
 
 class LayerNormLayer : public Layer {
  public:
+  bool streamGeom(StreamGeom& g, std::string& why) const override {
+    std::vector<int> ax = axes;
+    std::sort(ax.begin(), ax.end());
+    if (ax != std::vector<int>{1, 2}) { why = "LayerNorm over the time axis needs the whole utterance"; return false; }
+    g = StreamGeom();
+    return true;
+  }
   std::vector<int> axes;
   P gb;
   int groups = 0;
@@ -856,6 +878,16 @@ class TDSLayer : public Layer {
   size_t convImgElems = 0, convImgFOff = 0, convImgBOff = 0;   // bf16 weight images of the convolution (0: fp32 kernels only)
 
   std::string name() const override { return "TDSBlock"; }
+  bool streamGeom(StreamGeom& g, std::string& why) const override {
+    if (lnTime) { why = "TDS with lnIncludeTime = 1 normalises over the whole utterance"; return false; }
+    if (rPad > kw - 1) { why = "invalid right padding"; return false; }
+    g = StreamGeom();
+    g.timeExtent = true; g.kw = kw; g.stride = 1;
+    g.padR = rPad < 0 ? samePad(4096, kw, 1) : rPad;
+    g.padL = rPad < 0 ? g.padR : kw - 1 - rPad;
+    g.resShift = g.padL;
+    return true;
+  }
   void registerParams(std::vector<ParamInfo>& t) override {
     ParamInfo q;
     q = ParamInfo(); q.name = "tds.conv.w"; q.numel = (size_t)kw * c * c; q.refShape = {kw, 1, c, c}; q.kind = 1;
@@ -877,12 +909,16 @@ class TDSLayer : public Layer {
     int pL, pR;
     if (rPad < 0) { pL = pR = samePad(in.T, kw, 1); }
     else { if (rPad > kw - 1) throw std::invalid_argument("TDSBlock: invalid right padding"); pR = rPad; pL = kw - 1 - rPad; }
+    if (streamMode_) pL = pR = 0;   // a valid convolution over the window; the block runs on its T - kw + 1 output frames
     d = {in.B, in.T, h, c, c, kw, 1, pL, pR};
-    if (w2l_conv_out_len(in.T, kw, 1, pL, pR) != in.T) throw std::invalid_argument("TDSBlock: conv must preserve T (odd kw)");
-    B = in.B; T = in.T; M = B * T; n = in.numel();
+    const int To = w2l_conv_out_len(in.T, kw, 1, pL, pR);
+    if (!streamMode_ && To != in.T) throw std::invalid_argument("TDSBlock: conv must preserve T (odd kw)");
+    if (To <= 0) throw std::invalid_argument("TDSBlock: input too short: " + in.str());
+    B = in.B; T = To; M = B * T; n = (size_t)M * in.F;
     groups = lnTime ? B : B * T;
     inner = n / groups;
-    if (inner % 4) throw std::invalid_argument("TDSBlock: LayerNorm size must be a multiple of 4");
+    // (a streaming session also takes frames of any size -- the reference's golden vectors have 10 floats --: the scalar LayerNorm kernel)
+    if (inner % 4 && !streamMode_) throw std::invalid_argument("TDSBlock: LayerNorm size must be a multiple of 4");
     aOff = pl.alloc(n); r1Off = pl.alloc(n); y1Off = pl.alloc(n); vOff = pl.alloc(n); outOff = pl.alloc(n);
     st1Off = pl.alloc(2 * w2l_layernorm_scratch_doubles(groups, inner)); mr1Off = pl.alloc(2 * (size_t)groups);
     st2Off = pl.alloc(2 * w2l_layernorm_scratch_doubles(groups, inner)); mr2Off = pl.alloc(2 * (size_t)groups);
@@ -897,12 +933,19 @@ class TDSLayer : public Layer {
     y1Img.plan(pl, M, l, true); dvImg.plan(pl, M, l);
     convImgElems = h % 16 == 0 ? w2l_tds_conv_bf16_image_elems(&d) : 0;
     if (convImgElems) { convImgFOff = pl.allocBf16(convImgElems); convImgBOff = pl.allocBf16(convImgElems); }
-    return in;
+    Act o = in;
+    o.T = To;
+    return o;
   }
   void forward(Ctx& cx, float* ar, const float* x, float*& y) override {
     hipStream_t s = cx.stream;
     const double pd = cx.train ? p : 0.0;
     xSaved = x;
+    const float* xr = x;   // the residual operand: the input itself, or in stream mode the window frames under the outputs
+    if (streamMode_) {
+      if (!cx.streamRes) throw std::logic_error("TDSBlock in stream mode without its residual frames");
+      xr = cx.streamRes;
+    }
     float *a = ar + aOff, *r1 = ar + r1Off, *y1 = ar + y1Off, *v = ar + vOff, *out = ar + outOff;
     if (cx.bf16 && convImgElems) {   // bf16 operands, fp32 accumulation / bias / ReLU (conv_tds_bf16.hip); images once per step
       w2lCheck(w2l_tds_conv_bf16_prepare(&d, wc.w(cx), bfp(ar, convImgFOff), bfp(ar, convImgBOff), s), "tds conv images");
@@ -911,7 +954,7 @@ class TDSLayer : public Layer {
       w2lCheck(w2l_conv_forward(&d, x, wc.w(cx), bc.w(cx), a, 1, s), "tds conv");
     }
     // a <- dropout(relu(conv)) in place (kept: its sign pattern is the ReLU+dropout mask); r1 = a + x; y1 = LN(r1)
-    const bool y1Images = lnForward(cx, ar, groups, inner, a, x, r1, y1, gb1.w(cx), pd, cx.seed, rngStream, (double*)(ar + st1Off), ar + mr1Off,
+    const bool y1Images = lnForward(cx, ar, groups, inner, a, xr, r1, y1, gb1.w(cx), pd, cx.seed, rngStream, (double*)(ar + st1Off), ar + mr1Off,
                                     cx.bf16 ? &y1Img : nullptr, "tds ln1");
     if (cx.bf16) {
       // the two products on bf16 images: y1 as images (row image for lin1's product, transposed image for the weight gradient in
@@ -923,7 +966,8 @@ class TDSLayer : public Layer {
     }
     // v = r2 = dropout(lin2(u)) + y1 where lin2 joined; else v = lin2(u), and the LayerNorm kernel stores r2 over v.  out = LN(r2)
     const bool joined = ff.forward(cx, ar, y1, y1Img, v, pd, rngStream + 1);
-    w2lCheck(w2l_residual_layernorm_forward(groups, inner, v, joined ? nullptr : y1, v, out, gb2.w(cx), 1e-5f, joined ? 0.0 : pd,
+    float* r2 = (inner & 3) ? r1 : v;   // the scalar kernel of odd frame sizes (stream mode only) cannot store r over a; r1 is free by now
+    w2lCheck(w2l_residual_layernorm_forward(groups, inner, v, joined ? nullptr : y1, r2, out, gb2.w(cx), 1e-5f, joined ? 0.0 : pd,
                                             joined ? 0 : cx.seed, joined ? 0 : rngStream + 2, (double*)(ar + st2Off), ar + mr2Off, s), "tds ln2");
     y = out;
   }
@@ -1393,6 +1437,25 @@ void Sequential::finalize() {
   for (size_t i = 0; i < layers_.size(); ++i) layerLo_.push_back(firstIdx[i] < params_.size() ? params_[firstIdx[i]].offset : paramFloats_);
 }
 
+void requireEmissionLayout(const Act& out) {
+  // emissions must be (N, T', B, 1) == physical [B][T'][N]
+  // (dimension 0 may be several feature factors -- a View over a convolution layout -- as long as they tile the frame contiguously,
+  // fastest first: the flat feature index is then the logical one)
+  bool ok = out.d[0].size() == out.F;
+  {
+    long run = 1;
+    for (auto& f : out.d[0].f) {
+      ok = ok && f.kind == F_FEAT && f.stride == run;
+      run *= f.size;
+    }
+  }
+  std::vector<FKind> rest;
+  for (int i = 1; i < 4; ++i)
+    for (auto& f : out.d[i].f) rest.push_back(f.kind);
+  ok = ok && rest == std::vector<FKind>{F_TIME, F_BATCH};
+  if (!ok) throw std::invalid_argument("network output must be (NLABEL, T, B, 1); got " + out.str());
+}
+
 size_t Sequential::plan(int B, int T, int nFeat) {
   Planner pl;
   pl.bf16Convs = bf16Convs_;
@@ -1405,22 +1468,7 @@ size_t Sequential::plan(int B, int T, int nFeat) {
     acts_.push_back(a);
   }
   out_ = a;
-  // emissions must be (N, T', B, 1) == physical [B][T'][N]
-  // (dimension 0 may be several feature factors -- a View over a convolution layout -- as long as they tile the frame contiguously,
-  // fastest first: the flat feature index is then the logical one)
-  bool ok = out_.d[0].size() == out_.F;
-  {
-    long run = 1;
-    for (auto& f : out_.d[0].f) {
-      ok = ok && f.kind == F_FEAT && f.stride == run;
-      run *= f.size;
-    }
-  }
-  std::vector<FKind> rest;
-  for (int i = 1; i < 4; ++i)
-    for (auto& f : out_.d[i].f) rest.push_back(f.kind);
-  ok = ok && rest == std::vector<FKind>{F_TIME, F_BATCH};
-  if (!ok) throw std::invalid_argument("network output must be (NLABEL, T, B, 1); got " + out_.str());
+  requireEmissionLayout(out_);
   ys_.assign(layers_.size(), nullptr);
   convScratchElems_ = pl.convScratch();
   convScratchOff_ = convScratchElems_ ? pl.allocBf16(convScratchElems_) : 0;
@@ -1658,7 +1706,7 @@ static std::shared_ptr<Layer> buildOne(const LayerSpec& s, const LayerSpec* wnPa
   return unsupported();
 }
 
-std::shared_ptr<Sequential> buildSequentialFromText(const std::string& text, int64_t nFeat, int64_t nLabel) {
+std::shared_ptr<Sequential> buildSequentialFromText(const std::string& text, int64_t nFeat, int64_t nLabel, bool dryPlan) {
   auto specs = parseArch(text, nFeat, nLabel);
   auto net = std::make_shared<Sequential>();
   int padL = 0, padR = 0;
@@ -1675,6 +1723,7 @@ std::shared_ptr<Sequential> buildSequentialFromText(const std::string& text, int
       continue;
     }
     auto l = buildOne(s, nullptr);
+    l->archLine = s.line;
     if (pendingPad) {
       auto c = std::dynamic_pointer_cast<Conv2DLayer>(l);
       if (!c || c->pad != 0) throw std::invalid_argument("PD must be followed by an unpadded convolution: " + s.line);
@@ -1692,7 +1741,7 @@ std::shared_ptr<Sequential> buildSequentialFromText(const std::string& text, int
   if (pendingPad) throw std::invalid_argument("dangling PD at the end of the architecture");
   net->finalize();
   // dry plan: validates shapes / layouts and fixes the Linear row permutations
-  net->plan(1, 4096, (int)nFeat);
+  if (dryPlan) net->plan(1, 4096, (int)nFeat);
   return net;
 }
 

@@ -23,6 +23,7 @@ struct Trainer {
   std::shared_ptr<SequenceCriterion> crit;
   int nFeat = 0, nLabel = 0;
   std::string critName;
+  std::string archText;   // as given: a streaming session builds a network of its own from it (host/stream.cpp)
   // geometry
   int B = 0, T = 0, L = 0, Tout = 0;
   size_t netFloats = 0, critFloats = 0, arenaFloats = 0, critWsBytes = 0;
@@ -78,6 +79,16 @@ static thread_local std::string g_err;
 W2L_API const char* w2l_host_last_error(void) { return g_err.c_str(); }
 namespace w2l {
 void setHostError(const std::string& m) { g_err = m; }   // for the host entry points of other files (ngram_lm.cpp)
+// what a streaming session over a trainer reads (host/stream.cpp): its arch once, its bound parameters and mode at every step
+void trainerArch(void* h, std::string& archText, int& nFeat, int& nLabel) {
+  Trainer* t = (Trainer*)h;
+  archText = t->archText; nFeat = t->nFeat; nLabel = t->nLabel;
+}
+const float* trainerParams(void* h, bool& mixedPrecision) {
+  Trainer* t = (Trainer*)h;
+  mixedPrecision = t->mixedPrecision;
+  return t->params;
+}
 }
 
 // criterion: "ctc" | "asg" ; archText: contents of an .arch file (NFEAT/NLABEL substituted here)
@@ -86,6 +97,7 @@ W2L_API void* w2l_trainer_create(const char* archText, int nFeat, int nLabel, co
   try {
     auto t = new Trainer();
     t->nFeat = nFeat; t->nLabel = nLabel; t->critName = criterion ? criterion : "ctc"; t->scaleMode = scaleMode;
+    t->archText = archText ? archText : "";
     t->net = buildSequentialFromText(archText, nFeat, nLabel);
     if (t->critName == "ctc") t->crit = makeCTCLoss(scaleMode);
     else if (t->critName == "asg") t->crit = makeASGLoss(nLabel, scaleMode, transdiag);

@@ -94,6 +94,19 @@ struct Ctx {
   // mixed precision, second level: the image scratch the wide time convolutions share (conv_bf16.hip; Sequential::plan sizes it for
   // the largest of them, forward / backward point here).  Null: the switch is off.
   uint16_t* convScratch = nullptr;
+  // streaming step (host/stream.cpp): the residual operand [B][T'][F] of the TDS block about to run -- the frames of its input
+  // window that line up with the convolution's outputs, written by the window kernel (stream.hip).  Read only by a layer in
+  // stream mode.
+  const float* streamRes = nullptr;
+};
+
+// What a layer needs from the chunked streaming forward (host/stream.cpp).  A frame-local layer maps frame t to frame t and
+// keeps no state; a layer with a time extent is a valid convolution (kernel kw, stride) over the frames it has not consumed
+// yet, with padL zero frames ahead of an utterance and padR behind it.
+struct StreamGeom {
+  bool timeExtent = false;
+  int kw = 1, stride = 1, padL = 0, padR = 0;
+  int resShift = -1;   // >= 0 (TDS): output i takes its residual from window frame i + resShift
 };
 
 class Planner {  // bump allocator over the activation arena (sizes only until bound)
@@ -127,6 +140,14 @@ class Layer {
   // slimIPL's dynamic dropout: only the Transformer block answers (negative: back to the arch line's value)
   virtual void setTransformerDropout(double pDropout, double pLayerDrop) { (void)pDropout; (void)pLayerDrop; }
   int rngStream = 0;  // distinct dropout stream per layer
+  // chunked streaming forward: false (and why) when the layer cannot run on audio as it arrives
+  virtual bool streamGeom(StreamGeom& g, std::string& why) const { (void)g; why = "the layer needs the whole utterance"; return false; }
+  // stream mode: plan() takes its input as an assembled window -- no padding of its own, T' = (T - kw) / stride + 1 -- and a TDS
+  // block reads its residual from Ctx::streamRes.  Set before plan(); only ever on a streaming session's own Sequential.
+  void setStreamMode(bool on) { streamMode_ = on; }
+  std::string archLine;   // the arch line that built the layer (a folded PD or R line is not named)
+ protected:
+  bool streamMode_ = false;
 };
 
 class Sequential {
@@ -186,7 +207,10 @@ class Sequential {
 
 // arch file -> Sequential (throws std::invalid_argument like the reference's builder)
 std::shared_ptr<Sequential> buildSequentialModule(const std::string& archfile, int64_t nFeatures, int64_t nClasses);
-std::shared_ptr<Sequential> buildSequentialFromText(const std::string& archText, int64_t nFeatures, int64_t nClasses);
+// dryPlan = false: no whole-utterance plan -- for a caller that plans the layers itself (the streaming session, which validates
+// shapes and fixes the Linear row permutations on its own window plan)
+std::shared_ptr<Sequential> buildSequentialFromText(const std::string& archText, int64_t nFeatures, int64_t nClasses, bool dryPlan = true);
+void requireEmissionLayout(const Act& out);   // (NLABEL, T, B, 1) == physical [B][T][N], or std::invalid_argument
 
 // ----------------------------------------------------------------------------
 // sequence criteria (fl::pkg::speech::SequenceCriterion)
