@@ -590,6 +590,34 @@ struct BeamSearchResult {
   af::array words;       // (maxWords, M, B) s32 with a lexicon: the first min(count, maxWords) word ids, -1 beyond; else empty
   af::array wordCounts;  // (M, B) s32 with a lexicon: the true word count; -1 for a rank that does not exist; else empty
 };
+// fl_compat extension: the CTC beam search of CTCLoss::beamSearch continued chunk by chunk (w2l_beam_session_*; the contract is
+// in w2l_hip.h), beside StreamingSession, whose step() output it takes as it is when maxChunk == session.maxOut().  `slots`
+// utterances in progress, at most maxChunk emission frames per slot and step, at most maxFrames per utterance.  The result after
+// any number of frames is, bit for bit, CTCLoss::beamSearch over those frames alone, with the same options.  options: beamSize,
+// beamSizeToken, beamThreshold, logAdd, normalize (-1: as logAdd), lm, lmWeight, classScore, eosScore, lexicon, wordScore; nbest,
+// maxLen (0 = maxFrames) and maxWords (0 = maxLen) apply to result().  lm, lexicon and classScore must outlive the decoder.
+// options.wide, a beam or token count above 64: std::runtime_error; any other refused argument: std::invalid_argument.
+class FL_COMPAT_API StreamingDecoder {
+ public:
+  StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& options);
+  ~StreamingDecoder();
+  StreamingDecoder(const StreamingDecoder&) = delete;
+  StreamingDecoder& operator=(const StreamingDecoder&) = delete;
+  // emissions (NLABEL, maxChunk, slots) f32: the first counts[s] frames of slot s are its new ones.  start[s]: the slot begins a
+  // new utterance before them (empty = all 0).  Enqueues on fl::currentStream() and does not synchronise.
+  void step(const af::array& emissions, const std::vector<int>& counts, const std::vector<int>& start);
+  // the hypotheses of every slot for the frames fed so far: BeamSearchResult with B = slots; changes nothing
+  BeamSearchResult result();
+  int frames(int slot) const;   // emission frames fed to a slot since its start
+  void reset(int slot);         // closes a slot
+
+ private:
+  BeamSearchOptions o_;
+  std::shared_ptr<void> state_;
+  void* h_ = nullptr;
+  int slots_ = 0, maxChunk_ = 0, maxFrames_ = 0, nLabel_ = 0;
+};
+
 class FL_COMPAT_API ASGLoss : public SequenceCriterion {
  public:
   ASGLoss(int N, CriterionScaleMode scalemode = CriterionScaleMode::NONE, double transdiag = 0.0);

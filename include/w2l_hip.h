@@ -932,6 +932,77 @@ int w2l_stream_reset(void* session, int slot);
 int w2l_stream_window(const float* src, int srcRows, const float* carryIn, float* carryOut, int carryCap, float* win, int W,
                       float* res, int resShift, int To, const int* tab, int S, int F, w2l_stream_t stream);
 
+/* ---- incremental CTC beam search for streaming (csrc/criterion_beam_stream.hpp) -----------------------------------------
+ * A beam SESSION has S slots; a slot holds the search state of one utterance in progress.  A step advances every slot by the
+ * emission frames it received; a result can be asked for at any time.
+ * THE CONTRACT.  Take any slot and any split of its utterance's F emission frames into chunks (chunks of 0 frames count), with
+ * the other slots started, idle or mid-utterance at any other phase.  The result asked for after those F frames is the
+ * whole-utterance search of the same variant at B = 1, T = F, frames = NULL over the concatenated rows (in a buffer that begins
+ * at a 16-byte boundary, as every allocation does: with normalize the whole searches sum a row's exponentials in an order that
+ * follows from the row's address modulo 16 bytes, and the session takes the order of such a buffer), with the same beam,
+ * beamToken, threshold, logAdd, normalize, nbest, maxLen and LM / lexicon arguments: labels, lengths, scores, lmScores, words
+ * and wordCounts are equal BIT FOR BIT, in both logAdd modes (every value is made by the same device code in the same order;
+ * node ids of the prefix table differ, and no output or decision depends on them).  A partial result is the same statement
+ * with F = the frames fed so far, the end rule included: the lexicon search drops unfinished words, the EOS term is added
+ * when lmHasEos.  Asking changes nothing: the same question twice gives the same bytes and later steps behave as if nobody had
+ * asked.  A slot that was started and has had 0 frames returns what the end rule gives on the starting beam -- the empty prefix
+ * (length 0, score 0 plus the EOS term, 0 words) in row 0, empty rows below -- the one value the whole searches cannot state,
+ * since they refuse T = 0.  A slot that was never started, or was reset, returns empty rows (length -1, score -inf, labels -1).
+ * Variants (all on the narrow kernels, beam and beamToken <= 64):
+ *   W2L_BEAM_PLAIN  w2l_ctc_beam_search; lmScores is 0 for live rows, -inf for empty ones (as w2l_asg_beam_search without an LM).
+ *                   lm, lexicon, classScore NULL, every score argument 0.
+ *   W2L_BEAM_LM     w2l_ctc_beam_search_lm (lm, lmHasEos, lmWeight, classScore or NULL, eosScore).
+ *   W2L_BEAM_LEX    w2l_ctc_beam_search_lex (lm, lmHasEos, lmWeight, lexicon, wordScore, eosScore).
+ * lm / lexicon / classScore are device tables that must outlive the session.
+ *   w2l_beam_session_state_bytes  the state buffer's size for a descriptor; 0 for one the session refuses.  Every part is
+ *                                 256-byte aligned: 3 S ints; lse, lpb [S][maxChunk] and tokLp, tokC [S][maxChunk][K] (K =
+ *                                 min(beamToken, N - 1)) for a step's row pass; S prefix tables of cap 8-byte edges (cap = the
+ *                                 power of two >= max(64, 2 maxFrames beam)); S ints; 11 beam arrays [S][64] of 4 bytes.
+ *   w2l_beam_session_bind         state: device buffer, 256-byte aligned, the session's alone; contents need no initialisation.
+ *                                 Binding closes every slot.
+ *   w2l_beam_session_step         emissions: device [S][maxChunk][N], rows [0, h_n[s]) of slot s are its new frames (a session
+ *                                 with maxChunk = w2l_stream_max_out takes *out and nOut of w2l_stream_step as they are);
+ *                                 h_n, h_start: HOST int [S] (h_start may be NULL = all 0).  h_start[s]: the slot begins a new
+ *                                 utterance from the empty prefix before this step's frames.  At most two launches plus the
+ *                                 clears of starting slots' tables, plain launches on `stream` (use ONE stream per session);
+ *                                 the count table goes to the device with one async copy from pinned memory.  Never
+ *                                 synchronises, allocates nothing.
+ *   w2l_beam_session_counts       the bookkeeping of a step alone (host arithmetic, needs no device or bound state)
+ *   w2l_beam_session_result       outputs for all S slots, [S][nbest]... as the whole searches lay out [B][nbest]...; one
+ *                                 launch; reads state only.  words / wordCounts / maxWords: W2L_BEAM_LEX only (else ignored).
+ *   w2l_beam_session_frames       frames fed to a slot since its start
+ *   w2l_beam_session_reset        closes a slot
+ * Refusals, all before anything is enqueued or any count moves (w2l_host_last_error() says which).  W2L_EINVAL: the whole
+ * searches' argument rules; h_n[s] outside 0..maxChunk; frames for a slot that was never started; a step that would take a slot
+ * past maxFrames (the message names the slot and the limit); a step or a result before bind; a state buffer that is too small
+ * or misaligned; nbest outside 1..beam; labels / lengths / scores / lmScores, or the lexicon variant's words / wordCounts,
+ * missing.  W2L_EUNSUPPORTED: beam or beamToken (after clipping to N - 1) above 64, an unknown variant, maxFrames * beam > 2^29.
+ * A state buffer damaged between calls gives wrong hypotheses, never a spin or an access outside the buffer and the tables. */
+typedef enum { W2L_BEAM_PLAIN = 0, W2L_BEAM_LM = 1, W2L_BEAM_LEX = 2 } w2l_beam_variant;
+typedef struct {
+  int slots, maxChunk, maxFrames, N;
+  int beam, beamToken;
+  float threshold;
+  int logAdd, normalize, variant;
+  const void* lm;
+  int lmHasEos;
+  float lmWeight;
+  const float* classScore;
+  float eosScore;
+  const void* lexicon;
+  float wordScore;
+} w2l_beam_session_desc;
+int w2l_beam_session_create(const w2l_beam_session_desc* desc, void** session);
+void w2l_beam_session_destroy(void* session);
+size_t w2l_beam_session_state_bytes(const w2l_beam_session_desc* desc);
+int w2l_beam_session_bind(void* session, void* state, size_t bytes);
+int w2l_beam_session_step(void* session, const float* emissions, const int* h_n, const int* h_start, w2l_stream_t stream);
+int w2l_beam_session_counts(void* session, const int* h_n, const int* h_start);
+int w2l_beam_session_result(void* session, int nbest, int maxLen, int* labels, int* lengths, float* scores, float* lmScores,
+                            int maxWords, int* words, int* wordCounts, w2l_stream_t stream);
+int w2l_beam_session_frames(void* session, int slot, int* h_frames);
+int w2l_beam_session_reset(void* session, int slot);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,106 @@
+"""The incremental CTC beam search (w2l_beam_session_*) against the whole-utterance search of the same variant, in one process,
+timed with hip events after warm-up at the TDS-CTC recipe's emission shape:   python tools/beam_stream_one.py [variant] [reps]
+  N = 9998, T = 188 emission frames per utterance, the max search on the raw emissions, no threshold, nbest = 1
+  variant: lm (default; the 3-gram token LM of tools/ctc_beam_lm_one.py, lmWeight 0.5), lex (the lexicon and word LM of
+  tools/ctc_beam_lex_one.py) or plain
+  S = 1 / 16 / 64 slots, chunks of 1 / 2 / 4 emission frames per step, (W, K) = (64, 64) and (8, 8)
+Per shape one JSON line: the median step latency (a step = every slot advanced by one chunk, timed step by step), microseconds per
+frame summed over the utterance (all steps between two events), beside it the whole-utterance search at B = S, T = 188 -- the
+yardstick -- per frame, their ratio, the constant a step adds ((session - whole) / steps), and what the session replaces: searching
+again from frame 0 after every chunk, the sum of the whole search over the prefixes (timed at 8 prefix lengths, summed by the
+trapezoid rule).  The session's final hypotheses are checked bit for bit against the whole search before anything is timed."""
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np
+import torch
+
+from ctc_beam_lm_one import HOT
+from ctc_beam_lm_one import model as token_model
+from wav2letter_amd import criterion
+from wav2letter_amd.streaming import StreamingDecoder
+
+T, N = 188, 9998
+
+
+def tables(variant):
+    if variant == "plain":
+        return {}
+    if variant == "lm":
+        return dict(lm=token_model(N - 1, np.random.default_rng(3))[0], lm_weight=0.5)
+    from ctc_beam_lex_one import smear_of, spellings, word_model
+    from wav2letter_amd import Lexicon
+    from ctc_beam_lex_one import WORDS
+    rng = np.random.default_rng(3)
+    rows, _ = spellings(N - 1, rng)
+    lm, _ = word_model(WORDS, rng)
+    return dict(lm=lm, lm_weight=0.5, word_score=-0.5, lexicon=Lexicon.from_spellings(rows, N - 1, WORDS, smear_of(lm), None))
+
+
+def events(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / n
+
+
+def bench(S, chunk, W, reps, opts):
+    g = torch.Generator(device="cpu").manual_seed(11)
+    x = torch.randn(S, T, N, generator=g)
+    x[:, :, :HOT] += 2.0
+    x = x.cuda()
+    o = dict(beam=W, beam_token=W, threshold=float("inf"), log_add=False, normalize=False, **opts)
+    dec = StreamingDecoder(S, chunk, T, N, **o)
+    steps = [(x[:, t:t + chunk].contiguous() if t + chunk <= T else
+              torch.cat([x[:, t:], torch.zeros(S, chunk - (T - t), N, device="cuda")], 1), min(chunk, T - t)) for t in range(0, T, chunk)]
+    one = np.ones(S, np.int32)
+
+    def utterance():
+        for i, (em, c) in enumerate(steps):
+            dec.step(em, one * c, one * (i == 0))
+
+    def whole(F=T):
+        return criterion.ctc_beam_search(x[:, :F].contiguous() if F < T else x, nbest=1, max_len=T, **o)
+
+    utterance()
+    got, want = dec.result(nbest=1, max_len=T), whole()
+    torch.cuda.synchronize()
+    assert all((a.cpu().numpy().view(np.int32) == b.cpu().numpy().view(np.int32)).all() for a, b in zip(got, want)), \
+        "the session's hypotheses are not the whole search's"
+    for _ in range(2):
+        utterance()
+    t_utt = min(events(utterance, reps) for _ in range(2))
+    lat = []
+    for _ in range(max(reps // 2, 1)):   # step by step: the latency a caller sees between a chunk's emissions and the beam
+        for i, (em, c) in enumerate(steps):
+            lat.append(events(lambda: dec.step(em, one * c, one * (i == 0)), 1))
+    res = min(events(lambda: dec.result(nbest=1, max_len=T), reps) for _ in range(2))
+    t_whole = min(events(whole, reps) for _ in range(2))
+    marks = sorted({max(1, round(T * k / 8)) for k in range(1, 9)})
+    tp = [min(events(lambda: whole(F), max(reps // 2, 1)) for _ in range(2)) for F in marks]
+    # the sum over the prefixes a chunked caller would search again, by the trapezoid rule over the timed lengths
+    ends = list(range(chunk, T, chunk)) + [T]
+    research = float(np.interp(ends, marks, tp).sum())
+    return {"S": S, "chunk": chunk, "W": W, "K": W, "steps": len(steps), "step_us_median": round(statistics.median(lat), 1),
+            "session_us_per_utterance": round(t_utt, 1), "session_us_per_frame": round(t_utt / T, 2), "result_us": round(res, 1),
+            "whole_us": round(t_whole, 1), "whole_us_per_frame": round(t_whole / T, 2), "ratio": round(t_utt / t_whole, 2),
+            "per_step_constant_us": round((t_utt - t_whole) / len(steps), 1), "research_from_zero_us": round(research, 1),
+            "research_over_session": round(research / t_utt, 1)}
+
+
+if __name__ == "__main__":
+    variant = sys.argv[1] if len(sys.argv) > 1 else "lm"
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 6
+    opts = tables(variant)
+    print(json.dumps({"variant": variant, "T": T, "N": N, "reps": reps}), flush=True)
+    for W in (64, 8):
+        for S in (1, 16, 64):
+            for chunk in (1, 2, 4):
+                print(json.dumps(bench(S, chunk, W, reps, opts)), flush=True)

@@ -237,6 +237,15 @@ class _SIGS:
     w2l_stream_step = (_i, [_p, _p, _p, _p, _p, _p, _p, _p])
     w2l_stream_reset = (_i, [_p, _i])
     w2l_stream_window = (_i, [_p, _i, _p, _p, _i, _p, _i, _p, _i, _i, _p, _i, _i, _p])
+    w2l_beam_session_create = (_i, [_p, _p])
+    w2l_beam_session_destroy = (None, [_p])
+    w2l_beam_session_state_bytes = (_sz, [_p])
+    w2l_beam_session_bind = (_i, [_p, _p, _sz])
+    w2l_beam_session_step = (_i, [_p, _p, _p, _p, _p])
+    w2l_beam_session_counts = (_i, [_p, _p, _p])
+    w2l_beam_session_result = (_i, [_p, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p])
+    w2l_beam_session_frames = (_i, [_p, _i, _p])
+    w2l_beam_session_reset = (_i, [_p, _i])
 
 
 class ConvDesc(C.Structure):
@@ -261,6 +270,13 @@ class Bf16ConvertDesc(C.Structure):  # w2l_bf16_convert_desc
 
 class Bf16ImageSink(C.Structure):  # w2l_bf16_image_sink
     _fields_ = [("rowMajor", C.c_void_p), ("ldRows", C.c_size_t), ("transposed", C.c_void_p), ("ldTrans", C.c_size_t)]
+
+
+class BeamSessionDesc(C.Structure):  # w2l_beam_session_desc
+    _fields_ = ([(n, C.c_int) for n in ("slots", "maxChunk", "maxFrames", "N", "beam", "beamToken")] + [("threshold", C.c_float)] +
+                [(n, C.c_int) for n in ("logAdd", "normalize", "variant")] +
+                [("lm", C.c_void_p), ("lmHasEos", C.c_int), ("lmWeight", C.c_float), ("classScore", C.c_void_p),
+                 ("eosScore", C.c_float), ("lexicon", C.c_void_p), ("wordScore", C.c_float)])
 
 
 class AttnFusedDesc(C.Structure):  # w2l_attn_fused_desc

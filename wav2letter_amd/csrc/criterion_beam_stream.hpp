@@ -1,0 +1,357 @@
+// criterion_beam_stream.hpp -- w2l_beam_session_*: the CTC beam searches made incremental (contract: include/w2l_hip.h).  Included at
+// the end of criterion_ctc.hip after the searches it continues.  A session has S slots; a slot holds the search of one utterance in
+// progress: its beam and its prefix table stay in a caller-supplied state buffer between steps, so a step costs its own frames
+// alone and a result can be asked for after any of them.  What a result is, is stated by the whole searches: the same device
+// helpers in the same order (the scan and finish BODIES of criterion_ctc_beam_lm.hpp / _lex.hpp are the whole searches' own, with
+// kResume set), so hypotheses, scores and ranks are theirs bit for bit whatever the chunking.
+//   step    ctc_beam_rows<., false, true> over [S][maxChunk] rows (rows at or beyond the slot's count return at once; a count of 0
+//           is no rows) into the chunk-sized lse / lpb / tokLp / tokC area, then ONE scan launch, a workgroup per slot:
+//           beam_stream_lm_scan (LM-free: lm == null, and token LM) or beam_stream_lex_scan.  A slot with no frames and no start
+//           exits at once.  Starting slots have their table cleared on the stream first (one memset per run of adjacent slots).
+//   result  beam_stream_finish<lex>: the whole searches' finish bodies over the stored beams; reads state only.
+// The per-slot counts and start flags are host arithmetic; they reach the device with one async copy from pinned memory (a ring
+// of kBeamRing tables, as the streaming forward's count table does).  Nothing here synchronises or allocates after bind.
+// State buffer (every part 256-byte aligned; w2l_beam_session_state_bytes):
+//   cnt[S], base[S], flag[S] int   this call's table: frames of this step, frames before it, start / open flags
+//   lse, lpb  [S][maxChunk] fp32;  tokLp fp32, tokC int [S][maxChunk][K]         the row pass of this step
+//   table     [S][ctc_beam_cap(maxFrames, W)] u64                                 a slot's prefix trie, for its whole utterance
+//   n [S] int;  node, tot, state, acc, u, par, e, lab, pb, pnb, su [S][64]        the beams (11 arrays of 4-byte entries)
+#pragma once
+#include <algorithm>
+#include <string>
+#include <vector>
+
+namespace w2l {
+
+void setHostError(const std::string& m);   // w2l_host_last_error's message (host/trainer.cpp)
+
+constexpr int kBeamRing = 4;   // count tables in flight (pinned): a call reuses one only after the copy out of it has run
+
+struct BeamSessionLayout {
+  int* ctl;   // cnt[S], base[S], flag[S]
+  CtcBeamWs ws;
+  BeamCarry cy;
+};
+
+static size_t beam_session_layout(BeamSessionLayout* L, void* state, int S, int maxChunk, int maxFrames, int W, int K) {
+  const size_t rows = (size_t)S * maxChunk, cap = ctc_beam_cap(maxFrames, W), ent = align_up((size_t)S * kBeamMax * 4, 256);
+  char* p = (char*)state;
+  char* const p0 = p;
+  auto take = [&](size_t bytes) { char* q = p; p += align_up(bytes, 256); return q; };
+  int* ctl = (int*)take((size_t)3 * S * sizeof(int));
+  float* lse = (float*)take(rows * sizeof(float));
+  float* lpb = (float*)take(rows * sizeof(float));
+  float* tokLp = (float*)take(rows * K * sizeof(float));
+  int* tokC = (int*)take(rows * K * sizeof(int));
+  u64* table = (u64*)take((size_t)S * cap * sizeof(u64));
+  int* n = (int*)take((size_t)S * sizeof(int));
+  char* arr[11];
+  for (int i = 0; i < 11; ++i) arr[i] = take(ent);
+  if (L) {
+    L->ctl = ctl;
+    L->ws = CtcBeamWs{lse, lpb, tokLp, tokC, table, (int*)arr[0], (float*)arr[1], n, (int*)arr[2], (float*)arr[3], (int*)arr[4], K,
+                      (unsigned)cap};
+    L->cy = BeamCarry{ctl, ctl + 2 * S, (int*)arr[5], (int*)arr[6], (int*)arr[7], (float*)arr[8], (float*)arr[9], (float*)arr[10]};
+  }
+  return (size_t)(p - p0);
+}
+
+template <bool kLogAdd, int kThreads>
+__global__ __launch_bounds__(kThreads) void beam_stream_lm_scan(int T, int N, int W, float threshold, const float* __restrict__ x,
+                                                                CtcBeamWs ws, const void* __restrict__ lm, float lmWeight,
+                                                                const float* __restrict__ classScore, BeamCarry cy) {
+  beam_lm_scan_body<kLogAdd, kThreads, BeamCtc, true>(T, N, W, threshold, x, nullptr, ws, lm, lmWeight, classScore, BeamTrans{}, cy);
+}
+
+template <bool kLogAdd, int kThreads>
+__global__ __launch_bounds__(kThreads) void beam_stream_lex_scan(int T, int N, int W, float threshold, const float* __restrict__ x,
+                                                                 CtcBeamWs ws, const void* __restrict__ lex,
+                                                                 const void* __restrict__ lm, float lmWeight, float wordScore,
+                                                                 BeamCarry cy) {
+  beam_lex_scan_body<kLogAdd, kThreads, BeamCtc, true>(T, N, W, threshold, x, nullptr, ws, lex, lm, lmWeight, wordScore, BeamTrans{}, cy);
+}
+
+// cy.cnt[slot]: the frames the slot has had (no prefix is longer); cy.flag[slot] bit 1: the slot is open.  A closed or never
+// started slot has no entries: empty rows.
+template <bool kLex>
+__global__ __launch_bounds__(64) void beam_stream_finish(int M, int Lmax, int maxWords, int eosWord, CtcBeamWs ws, BeamCarry cy,
+                                                         const void* __restrict__ lex, const void* __restrict__ lm, float lmWeight,
+                                                         float eosScore, int useEos, int* __restrict__ labels,
+                                                         int* __restrict__ lengths, float* __restrict__ scores,
+                                                         float* __restrict__ lmScores, int* __restrict__ words,
+                                                         int* __restrict__ wordCounts) {
+  const int b = blockIdx.x;
+  const int n = (cy.flag[b] & 2) ? min(max(ws.finN[b], 0), kBeamMax) : 0;
+  BeamWalk g;
+  g.capm = ws.cap - 1;
+  g.steps = max(cy.cnt[b], 0);
+  if constexpr (kLex)
+    beam_lex_finish_body(b, n, g, M, Lmax, maxWords, ws, lex, lm, lmWeight, eosScore, useEos, labels, lengths, scores, lmScores, words,
+                         wordCounts);
+  else
+    beam_lm_finish_body(b, n, g, M, Lmax, eosWord, ws, lm, lmWeight, eosScore, useEos, labels, lengths, scores, lmScores);
+}
+
+struct BeamSession {
+  w2l_beam_session_desc d{};
+  int K = 0;
+  size_t stateBytes = 0, cap = 0;
+  std::vector<int> frames;    // per slot: emission frames fed since its start
+  std::vector<char> active;   // per slot: started and not reset
+  BeamSessionLayout L{};
+  bool bound = false;
+  int* pinned[kBeamRing] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev[kBeamRing] = {nullptr, nullptr, nullptr, nullptr};
+  bool evUsed[kBeamRing] = {false, false, false, false};
+  int ring = 0;
+  ~BeamSession() {
+    for (int r = 0; r < kBeamRing; ++r) {
+      if (ev[r]) (void)hipEventDestroy(ev[r]);
+      if (pinned[r]) (void)hipHostFree(pinned[r]);
+    }
+  }
+};
+
+static int beam_session_fail(int rc, const std::string& m) {
+  setHostError(m);
+  return rc;
+}
+
+// the descriptor against the whole searches' argument rules; *K = the clipped beamToken
+static int beam_session_check(const w2l_beam_session_desc* d, int* K) {
+  if (!d) return beam_session_fail(W2L_EINVAL, "beam session: null descriptor");
+  if (d->slots <= 0 || d->slots > 65535 || d->maxChunk <= 0 || d->maxFrames <= 0 || d->N < 2 || d->beam <= 0 || d->beamToken <= 0 ||
+      !(d->threshold >= 0.f))
+    return beam_session_fail(W2L_EINVAL, "beam session: slots (1..65535), maxChunk, maxFrames, beam, beamToken must be positive, N >= 2, "
+                                         "threshold >= 0");
+  if (d->variant != W2L_BEAM_PLAIN && d->variant != W2L_BEAM_LM && d->variant != W2L_BEAM_LEX)
+    return beam_session_fail(W2L_EUNSUPPORTED, "beam session: unknown variant " + std::to_string(d->variant));
+  if (d->variant == W2L_BEAM_PLAIN) {
+    if (d->lm || d->lexicon || d->classScore || d->lmHasEos || d->lmWeight != 0.f || d->eosScore != 0.f || d->wordScore != 0.f)
+      return beam_session_fail(W2L_EINVAL, "beam session: the LM-free variant takes no LM, lexicon or score arguments");
+  } else {
+    if (!d->lm) return beam_session_fail(W2L_EINVAL, "beam session: this variant needs an LM table");
+    if (!(fabsf(d->lmWeight) < INFINITY) || !(fabsf(d->eosScore) < INFINITY) || (!d->lmHasEos && d->eosScore != 0.f))
+      return beam_session_fail(W2L_EINVAL, "beam session: lmWeight and eosScore must be finite, eosScore 0 without EOS");
+    if (d->variant == W2L_BEAM_LM && (d->lexicon || d->wordScore != 0.f))
+      return beam_session_fail(W2L_EINVAL, "beam session: the token-LM variant takes no lexicon or wordScore");
+    if (d->variant == W2L_BEAM_LEX && (!d->lexicon || d->classScore || !(fabsf(d->wordScore) < INFINITY)))
+      return beam_session_fail(W2L_EINVAL, "beam session: the lexicon variant needs a lexicon table, a finite wordScore, no classScore");
+  }
+  *K = ctc_beam_clip(d->N - 1, d->beamToken);
+  if (d->beam > kBeamMax || *K > kBeamMax)
+    return beam_session_fail(W2L_EUNSUPPORTED, "beam session: beam and beamToken above 64 (the wide searches) are not incremental");
+  if ((size_t)d->maxFrames * d->beam > ((size_t)1 << 29))
+    return beam_session_fail(W2L_EUNSUPPORTED, "beam session: maxFrames * beam above 2^29 (node ids are ints)");
+  return W2L_OK;
+}
+
+// One step's bookkeeping: validates everything first; fills the table (cnt[S], base[S], flag[S]; may be null) and returns the counts
+// after the step in `after` without committing them.
+static int beam_session_advance(const BeamSession& s, const int* n, const int* start, int* table, std::vector<int>& after,
+                                std::vector<char>& activeAfter) {
+  if (!n) return beam_session_fail(W2L_EINVAL, "beam session step: null frame counts");
+  const int S = s.d.slots;
+  for (int i = 0; i < S; ++i) {
+    const bool st = start && start[i];
+    if (n[i] < 0 || n[i] > s.d.maxChunk)
+      return beam_session_fail(W2L_EINVAL, "beam session step: slot " + std::to_string(i) + " was given " + std::to_string(n[i]) +
+                                               " frames, outside 0.." + std::to_string(s.d.maxChunk));
+    if (!st && !s.active[i] && n[i] > 0)
+      return beam_session_fail(W2L_EINVAL, "beam session step: slot " + std::to_string(i) + " is fed before it was started");
+    if ((st ? 0 : s.frames[i]) + n[i] > s.d.maxFrames)
+      return beam_session_fail(W2L_EINVAL, "beam session step: slot " + std::to_string(i) + " would pass maxFrames = " +
+                                               std::to_string(s.d.maxFrames) + " (" + std::to_string(st ? 0 : s.frames[i]) + " fed, " +
+                                               std::to_string(n[i]) + " given)");
+  }
+  after = s.frames;
+  activeAfter = s.active;
+  for (int i = 0; i < S; ++i) {
+    const bool st = start && start[i];
+    if (st) { after[i] = 0; activeAfter[i] = 1; }
+    if (table) { table[i] = n[i]; table[S + i] = after[i]; table[2 * S + i] = st ? 1 : 0; }
+    after[i] += n[i];
+  }
+  return W2L_OK;
+}
+
+// the next pinned table of the ring, free to write
+static int beam_session_table(BeamSession& s, int** table) {
+  const int r = s.ring;
+  if (s.evUsed[r]) W2L_HIP_CHECK(hipEventSynchronize(s.ev[r]));   // the copy of kBeamRing calls ago: long done
+  *table = s.pinned[r];
+  return W2L_OK;
+}
+static int beam_session_send(BeamSession& s, hipStream_t st) {
+  const int r = s.ring;
+  W2L_HIP_CHECK(hipMemcpyAsync(s.L.ctl, s.pinned[r], (size_t)3 * s.d.slots * sizeof(int), hipMemcpyHostToDevice, st));
+  W2L_HIP_CHECK(hipEventRecord(s.ev[r], st));
+  s.evUsed[r] = true;
+  s.ring = (r + 1) % kBeamRing;
+  return W2L_OK;
+}
+
+}  // namespace w2l
+
+W2L_API size_t w2l_beam_session_state_bytes(const w2l_beam_session_desc* desc) {
+  using namespace w2l;
+  int K = 0;
+  if (beam_session_check(desc, &K)) return 0;
+  return beam_session_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K);
+}
+
+W2L_API int w2l_beam_session_create(const w2l_beam_session_desc* desc, void** session) {
+  using namespace w2l;
+  if (!session) return beam_session_fail(W2L_EINVAL, "beam session: null session pointer");
+  *session = nullptr;
+  int K = 0;
+  if (const int rc = beam_session_check(desc, &K)) return rc;
+  BeamSession* s = new BeamSession();
+  s->d = *desc;
+  s->K = K;
+  s->cap = ctc_beam_cap(desc->maxFrames, desc->beam);
+  s->stateBytes = beam_session_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K);
+  s->frames.assign(desc->slots, 0);
+  s->active.assign(desc->slots, 0);
+  *session = s;
+  return W2L_OK;
+}
+
+W2L_API void w2l_beam_session_destroy(void* session) { delete (w2l::BeamSession*)session; }
+
+W2L_API int w2l_beam_session_bind(void* session, void* state, size_t bytes) {
+  using namespace w2l;
+  if (!session) return beam_session_fail(W2L_EINVAL, "beam session bind: null session");
+  BeamSession& s = *(BeamSession*)session;
+  if (!state || ((uintptr_t)state & 255))
+    return beam_session_fail(W2L_EINVAL, "beam session bind: the state buffer must be a 256-byte aligned device pointer");
+  if (bytes < s.stateBytes)
+    return beam_session_fail(W2L_EINVAL, "beam session bind: the state buffer is smaller than w2l_beam_session_state_bytes");
+  const size_t tb = align_up((size_t)3 * s.d.slots * sizeof(int), 256);
+  for (int r = 0; r < kBeamRing; ++r) {
+    if (!s.pinned[r]) W2L_HIP_CHECK(hipHostMalloc((void**)&s.pinned[r], tb, hipHostMallocDefault));
+    if (!s.ev[r]) W2L_HIP_CHECK(hipEventCreateWithFlags(&s.ev[r], hipEventDisableTiming));
+  }
+  beam_session_layout(&s.L, state, s.d.slots, s.d.maxChunk, s.d.maxFrames, s.d.beam, s.K);
+  s.bound = true;
+  // another buffer holds no slot's search
+  std::fill(s.frames.begin(), s.frames.end(), 0);
+  std::fill(s.active.begin(), s.active.end(), 0);
+  return W2L_OK;
+}
+
+W2L_API int w2l_beam_session_counts(void* session, const int* h_n, const int* h_start) {
+  using namespace w2l;
+  if (!session) return beam_session_fail(W2L_EINVAL, "beam session counts: null session");
+  BeamSession& s = *(BeamSession*)session;
+  std::vector<int> fa;
+  std::vector<char> aa;
+  if (const int rc = beam_session_advance(s, h_n, h_start, nullptr, fa, aa)) return rc;
+  s.frames.swap(fa);
+  s.active.swap(aa);
+  return W2L_OK;
+}
+
+W2L_API int w2l_beam_session_step(void* session, const float* emissions, const int* h_n, const int* h_start, w2l_stream_t stream) {
+  using namespace w2l;
+  if (!session) return beam_session_fail(W2L_EINVAL, "beam session step: null session");
+  BeamSession& s = *(BeamSession*)session;
+  if (!s.bound) return beam_session_fail(W2L_EINVAL, "beam session step: no state bound (w2l_beam_session_bind first)");
+  std::vector<int> fa;
+  std::vector<char> aa;
+  if (const int rc = beam_session_advance(s, h_n, h_start, nullptr, fa, aa)) return rc;
+  const int S = s.d.slots, C = s.d.maxChunk, N = s.d.N, W = s.d.beam, K = s.K;
+  bool frames = false, starts = false;
+  for (int i = 0; i < S; ++i) {
+    frames = frames || h_n[i] > 0;
+    starts = starts || (h_start && h_start[i]);
+  }
+  if (frames && !emissions) return beam_session_fail(W2L_EINVAL, "beam session step: null emissions");
+  if (frames || starts) {
+    hipStream_t st = (hipStream_t)stream;
+    int* table = nullptr;
+    if (const int rc = beam_session_table(s, &table)) return rc;
+    (void)beam_session_advance(s, h_n, h_start, table, fa, aa);
+    if (const int rc = beam_session_send(s, st)) return rc;
+    for (int i = 0; i < S;) {   // a starting slot's table is cleared before its frames: one memset per run of adjacent slots
+      if (!(h_start && h_start[i])) { ++i; continue; }
+      int j = i + 1;
+      while (j < S && h_start[j]) ++j;
+      W2L_HIP_CHECK(hipMemsetAsync(s.L.ws.table + (size_t)i * s.cap, 0, (size_t)(j - i) * s.cap * sizeof(u64), st));
+      i = j;
+    }
+    const CtcBeamWs& ws = s.L.ws;
+    if (frames) {
+      const unsigned rows = (unsigned)((size_t)S * C);
+      if (N > kRowThreads * kRowMaxPer)
+        hipLaunchKernelGGL((ctc_beam_rows<true, false, true>), dim3(rows), dim3(kRowThreads), 0, st, C, N, s.d.normalize, emissions,
+                           s.L.cy.cnt, ws);
+      else
+        hipLaunchKernelGGL((ctc_beam_rows<false, false, true>), dim3(rows), dim3(kRowThreads), 0, st, C, N, s.d.normalize, emissions,
+                           s.L.cy.cnt, ws);
+      W2L_LAUNCH_CHECK();
+    }
+    ctc_beam_fused_scan(W, K, s.d.logAdd, [&](auto la, auto th) {
+      if (s.d.variant == W2L_BEAM_LEX)
+        hipLaunchKernelGGL((beam_stream_lex_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)S),
+                           dim3(decltype(th)::value), 0, st, C, N, W, s.d.threshold, emissions, ws, s.d.lexicon, s.d.lm, s.d.lmWeight,
+                           s.d.wordScore, s.L.cy);
+      else
+        hipLaunchKernelGGL((beam_stream_lm_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)S),
+                           dim3(decltype(th)::value), 0, st, C, N, W, s.d.threshold, emissions, ws, s.d.lm, s.d.lmWeight,
+                           s.d.classScore, s.L.cy);
+    });
+    W2L_LAUNCH_CHECK();
+  }
+  s.frames.swap(fa);
+  s.active.swap(aa);
+  return W2L_OK;
+}
+
+W2L_API int w2l_beam_session_result(void* session, int nbest, int maxLen, int* labels, int* lengths, float* scores, float* lmScores,
+                                    int maxWords, int* words, int* wordCounts, w2l_stream_t stream) {
+  using namespace w2l;
+  if (!session) return beam_session_fail(W2L_EINVAL, "beam session result: null session");
+  BeamSession& s = *(BeamSession*)session;
+  if (!s.bound) return beam_session_fail(W2L_EINVAL, "beam session result: no state bound (w2l_beam_session_bind first)");
+  if (nbest < 1 || nbest > s.d.beam || maxLen <= 0)
+    return beam_session_fail(W2L_EINVAL, "beam session result: nbest outside 1..beam or maxLen < 1");
+  if (!labels || !lengths || !scores || !lmScores) return beam_session_fail(W2L_EINVAL, "beam session result: null output");
+  const bool lex = s.d.variant == W2L_BEAM_LEX;
+  if (lex && (!words || !wordCounts || maxWords < 1))
+    return beam_session_fail(W2L_EINVAL, "beam session result: the lexicon variant writes words and wordCounts (maxWords >= 1)");
+  hipStream_t st = (hipStream_t)stream;
+  const int S = s.d.slots;
+  int* table = nullptr;
+  if (const int rc = beam_session_table(s, &table)) return rc;
+  for (int i = 0; i < S; ++i) { table[i] = s.frames[i]; table[S + i] = 0; table[2 * S + i] = s.active[i] ? 2 : 0; }
+  if (const int rc = beam_session_send(s, st)) return rc;
+  const int useEos = s.d.lmHasEos ? 1 : 0;
+  if (lex)
+    hipLaunchKernelGGL(beam_stream_finish<true>, dim3((unsigned)S), dim3(64), 0, st, nbest, maxLen, maxWords, s.d.N, s.L.ws, s.L.cy,
+                       s.d.lexicon, s.d.lm, s.d.lmWeight, s.d.eosScore, useEos, labels, lengths, scores, lmScores, words, wordCounts);
+  else
+    hipLaunchKernelGGL(beam_stream_finish<false>, dim3((unsigned)S), dim3(64), 0, st, nbest, maxLen, 0, s.d.N, s.L.ws, s.L.cy, nullptr,
+                       s.d.lm, s.d.lmWeight, s.d.eosScore, useEos, labels, lengths, scores, lmScores, nullptr, nullptr);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+W2L_API int w2l_beam_session_frames(void* session, int slot, int* h_frames) {
+  using namespace w2l;
+  if (!session || !h_frames) return beam_session_fail(W2L_EINVAL, "beam session frames: null argument");
+  BeamSession& s = *(BeamSession*)session;
+  if (slot < 0 || slot >= s.d.slots) return beam_session_fail(W2L_EINVAL, "beam session frames: no such slot");
+  *h_frames = s.frames[slot];
+  return W2L_OK;
+}
+
+W2L_API int w2l_beam_session_reset(void* session, int slot) {
+  using namespace w2l;
+  if (!session) return beam_session_fail(W2L_EINVAL, "beam session reset: null session");
+  BeamSession& s = *(BeamSession*)session;
+  if (slot < 0 || slot >= s.d.slots) return beam_session_fail(W2L_EINVAL, "beam session reset: no such slot");
+  s.frames[slot] = 0;
+  s.active[slot] = 0;
+  return W2L_OK;
+}

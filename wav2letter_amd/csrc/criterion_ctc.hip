@@ -25,6 +25,7 @@
 // w2l_ctc_align (forced alignment: the best lattice path of a known transcript) lives in criterion_ctc_align.hpp, included below.
 // w2l_ctc_beam_search (lexicon-free n-best prefix beam search) lives in criterion_ctc_beam.hpp, included below with its siblings;
 // the beam searches of the ASG lattice (criterion_asg_beam.hpp) come last, on the same helpers and scans.
+// w2l_beam_session_* (the CTC searches continued chunk by chunk for streaming) lives in criterion_beam_stream.hpp.
 // w2l_ctc_score (evaluation: loss and greedy path, no gradient) reads the emissions once, 4BTN:
 //   ctc_rows_score  the ctc_rows_lse pass (same arithmetic, template flag) that also writes the first-max argmax of the row
 //   ctc_scan_score  the alpha wave alone, grid (B, 1), lattice rows kept in registers: only the loss is written
@@ -133,15 +134,16 @@ __device__ __forceinline__ void block_argmin_store(int cand, int* out) {
 // element indices  head: tid (< nh);  body: nh + 4*(tid + 256*k) .. +3;  tail scalars.
 // nh = number of leading scalars so that the body is 16-byte aligned.
 struct RowSplit { int nh, nbody4, ntail; };
-__device__ __forceinline__ RowSplit row_split(const float* row, int N) {
+// mis: the floats by which the row begins past a 16-byte boundary
+__device__ __forceinline__ RowSplit row_split_at(int mis, int N) {
   RowSplit r;
-  int mis = (int)(((uintptr_t)row >> 2) & 3);
   r.nh = mis ? 4 - mis : 0;
   if (r.nh > N) r.nh = N;
   r.nbody4 = (N - r.nh) >> 2;
   r.ntail = (N - r.nh) & 3;
   return r;
 }
+__device__ __forceinline__ RowSplit row_split(const float* row, int N) { return row_split_at((int)(((uintptr_t)row >> 2) & 3), N); }
 
 // lse[b][t] and the label probabilities pd[b][t][s] = exp(x[ext_s] - lse) in fp64
 // VAR 3 (the product's form when L >= 1): the label gather of the first kRowThreads lattice positions -- target, then x[label] --
@@ -898,3 +900,4 @@ W2L_API int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, 
 #include "criterion_ctc_beam_lex.hpp"
 #include "criterion_asg_beam.hpp"
 #include "criterion_beam_wide.hpp"
+#include "criterion_beam_stream.hpp"

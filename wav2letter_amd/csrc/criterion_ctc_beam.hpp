@@ -21,7 +21,9 @@
 // ctc_beam_layout), the tie key, its decoder and the stops of a selection (beam_key, beam_pick), the prefix table's find-or-make
 // (beam_node); for the workgroup scans of criterion_ctc_beam_lm.hpp and criterion_ctc_beam_lex.hpp beam_load_frame, beam_stay_front,
 // beam_select_round and beam_store_final; for the finishes beam_chain_len, beam_write_labels, beam_eos and beam_rerank; for the
-// entry points ctc_beam_check, ctc_beam_begin and ctc_beam_fused_scan.  The other two files keep what is particular to their search.
+// entry points ctc_beam_check, ctc_beam_begin and ctc_beam_fused_scan; for the beam session of criterion_beam_stream.hpp, which
+// resumes the two workgroup scans from a stored beam, BeamCarry with beam_carry_begin / _load / _store and the bound of a walk up
+// the prefix table (BeamWalk).  The other two files keep what is particular to their search.
 // What the lattice is -- the acoustic sum of a stay and of an extension -- is a policy of the two workgroup scans: BeamCtc here,
 // BeamAsg in criterion_asg_beam.hpp (no blank, a transition matrix, no token after itself), which also uses ctc_beam_rows<., true>.
 // The LM-free search itself uses neither the LM table (ngram_lm.hpp is here for beam_eos) nor kLmPer (the workgroup scans').
@@ -113,7 +115,12 @@ __device__ __forceinline__ u64 block_max_u64(u64 v, u64* sm) {
 }
 
 // kNoBlank (the ASG searches of criterion_asg_beam.hpp): every class is a token, K may reach N, lpb is -inf
-template <bool kBig, bool kNoBlank = false>
+// kCounts (the beam session of criterion_beam_stream.hpp): frames[b] is a count as it stands, and 0 means no rows; frames[B + b]
+// is the utterance's frame index of the slot's first row.  The order in which a row's exponentials are summed follows from where
+// the row begins modulo 16 bytes (row_split), so lse is a function of the row's values AND that phase.  A session's rows lie
+// wherever the chunking put them; they are split as the whole search splits frame t of an utterance that begins at a 16-byte
+// boundary, phase (t N) mod 4, and loaded without an alignment promise: lse has the whole search's bits under any chunking.
+template <bool kBig, bool kNoBlank = false, bool kCounts = false>
 __global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int normalize,
                                                              const float* __restrict__ x,
                                                              const int* __restrict__ frames, CtcBeamWs ws) {
@@ -125,9 +132,11 @@ __global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int n
   __shared__ unsigned sCnt;
   const size_t r = blockIdx.x;  // row = b*T + t
   const int b = (int)(r / T);
-  if ((int)(r - (size_t)b * T) >= align_frames(frames, b, T)) return;
+  if ((int)(r - (size_t)b * T) >= (kCounts ? min(frames[b], T) : align_frames(frames, b, T))) return;
   const float* row = x + r * N;
   const int tid = threadIdx.x, K = ws.K, blank = kNoBlank ? -1 : N - 1;
+  int phase = 0;
+  if constexpr (kCounts) phase = (int)(((size_t)(frames[gridDim.x / T + b] + (int)(r - (size_t)b * T)) * (size_t)N) & 3);
 
   // the row in registers, every load issued before the first use (ctc_rows_lse_body's loader)
   constexpr int kPer = kBig ? 1 : kRowMaxPer / 4;
@@ -136,12 +145,15 @@ __global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int n
   int hidx = -1;
   RowSplit sp{};
   if constexpr (!kBig) {
-    sp = row_split(row, N);
+    sp = kCounts ? row_split_at(phase, N) : row_split(row, N);
     const float4* body = (const float4*)(row + sp.nh);
     if (sp.nbody4 > 0) {
       const int lastc = sp.nbody4 - 1;
 #pragma unroll
-      for (int k = 0; k < kPer; ++k) v[k] = body[min(tid + kRowThreads * k, lastc)];
+      for (int k = 0; k < kPer; ++k) {
+        if constexpr (kCounts) __builtin_memcpy(&v[k], row + sp.nh + 4 * min(tid + kRowThreads * k, lastc), sizeof(float4));
+        else v[k] = body[min(tid + kRowThreads * k, lastc)];
+      }
     }
     if (tid < sp.nh) hidx = tid;
     else if (tid >= 64 && tid - 64 < sp.ntail) hidx = sp.nh + 4 * sp.nbody4 + (tid - 64);
@@ -461,12 +473,74 @@ __device__ __forceinline__ void beam_store_final(const CtcBeamWs& ws, int b, int
   if (tid == 0) ws.finN[b] = n;
 }
 
+// ---- a beam that outlives the launch (the beam session of criterion_beam_stream.hpp; the scan bodies' kResume)
+// The arrays the finishes read anyway -- node, tot, LM state, LM sum, lexicon node, n: the fin* of CtcBeamWs, [slot][64] -- are
+// the stored beam's; BeamCarry adds what only the next frame needs.  pb and pnb are stored apart from tot: the extension by an
+// entry's own last label adds pb alone.  cnt[slot]: the slot's frames of this step; flag[slot] bit 0: it starts from the empty
+// prefix.  (cnt is followed by the slots' frame indices, ctc_beam_rows<., ., true>'s.)
+struct BeamCarry {
+  const int *cnt, *flag;
+  int *par, *e, *lab;      // [S][64]; lab: the lexicon scan's
+  float *pb, *pnb, *su;    // [S][64]; su: the lexicon scan's
+};
+
+// a slot's frames of this step and whether it starts; false: nothing to do
+__device__ __forceinline__ bool beam_carry_begin(const BeamCarry& cy, int b, int T, int* F, bool* fresh) {
+  *F = min(max(cy.cnt[b], 0), T);
+  *fresh = (cy.flag[b] & 1) != 0;
+  return *F > 0 || *fresh;
+}
+
+// The stored beam into the arrays of half 0; returns n.  What indexes memory is held to its range here (n to 64, the last label
+// to the row, node ids to the table); LM states and lexicon nodes are clamped where they are used (ngram_q, lex_child, lex_node).
+// The caller's barrier publishes the arrays.
+__device__ __forceinline__ int beam_carry_load(const BeamCarry& cy, const CtcBeamWs& ws, int b, int N, int* sNode, int* sPar, int* sE,
+                                               float* sPb, float* sPnb, float* sTot, int* sSt, float* sAcc, int* sLab, int* sU,
+                                               float* sSu) {
+  const int tid = threadIdx.x, n = min(max(ws.finN[b], 0), kBeamMax);
+  if (tid < 64) {
+    const int i = b * kBeamMax + tid;
+    const bool live = tid < n;
+    const int node = ws.finNode[i], e = cy.e[i];
+    sNode[tid] = live ? ((unsigned)node <= ws.cap ? node : 0) : -2;
+    sPar[tid] = live ? cy.par[i] : -1;
+    sE[tid] = live && e >= 0 && e < N ? e : -1;
+    sPb[tid] = live ? cy.pb[i] : -INFINITY;
+    sPnb[tid] = live ? cy.pnb[i] : -INFINITY;
+    sTot[tid] = live ? ws.finTot[i] : -INFINITY;
+    sSt[tid] = live ? ws.finState[i] : 0;
+    sAcc[tid] = live ? ws.finAcc[i] : 0.f;
+    if (sLab) {
+      sLab[tid] = live ? cy.lab[i] : -1;
+      sU[tid] = live ? ws.finU[i] : 0;
+      sSu[tid] = live ? cy.su[i] : 0.f;
+    }
+  }
+  return n;
+}
+
+// what beam_store_final does not store (sLab: the lexicon scan's, else null)
+__device__ __forceinline__ void beam_carry_store(const BeamCarry& cy, int b, int n, const int* sPar, const int* sE, const float* sPb,
+                                                 const float* sPnb, const int* sLab, const float* sSu) {
+  const int tid = threadIdx.x;
+  if (tid >= 64 || tid >= n) return;
+  const int i = b * kBeamMax + tid;
+  cy.par[i] = sPar[tid]; cy.e[i] = sE[tid]; cy.pb[i] = sPb[tid]; cy.pnb[i] = sPnb[tid];
+  if (sLab) { cy.lab[i] = sLab[tid]; cy.su[i] = sSu[tid]; }
+}
+
 // ---- the finishes
 
+// What bounds a walk up the prefix table.  A whole search made the table in the same call and trusts it (the default: no bound).  A
+// beam session reads node ids from a state buffer that lives between calls: a walk stays inside the table (capm) and ends after
+// as many labels as the slot has had frames (steps), so a damaged state gives wrong labels, never a spin or a read outside.
+struct BeamWalk { unsigned capm = ~0u; int steps = 0x7fffffff; };
+__device__ __forceinline__ bool beam_walk_ok(const BeamWalk& g, int p) { return p > 0 && (unsigned)(p - 1) <= g.capm; }
+
 // labels of the prefix that ends at `node`; with nwords, also how many of them carry a slot (the lexicon search's completed words)
-__device__ __forceinline__ int beam_chain_len(const u64* tab, int node, int* nwords = nullptr) {
+__device__ __forceinline__ int beam_chain_len(const u64* tab, int node, int* nwords = nullptr, BeamWalk g = BeamWalk{}) {
   int len = 0, nw = 0;
-  for (int p = node; p > 0;) {
+  for (int p = node; len < g.steps && beam_walk_ok(g, p);) {
     const u64 edge = tab[p - 1];
     ++len;
     nw += (((unsigned)edge - 1u) & 7u) ? 1 : 0;
@@ -477,13 +551,14 @@ __device__ __forceinline__ int beam_chain_len(const u64* tab, int node, int* nwo
 }
 
 // the labels of a live row (its prefix table's labels are the tokens) or none, padded with -1 to Lmax: the row's length
-__device__ __forceinline__ int beam_write_labels(const u64* tab, bool live, const int* finNode, int Lmax, int* lab) {
+__device__ __forceinline__ int beam_write_labels(const u64* tab, bool live, const int* finNode, int Lmax, int* lab,
+                                                 BeamWalk g = BeamWalk{}) {
   int len = 0;
   if (live) {
     const int node = *finNode;
-    len = beam_chain_len(tab, node);
+    len = beam_chain_len(tab, node, nullptr, g);
     int i = len - 1;
-    for (int p = node; p > 0; --i) {
+    for (int p = node; i >= 0 && beam_walk_ok(g, p); --i) {
       const u64 edge = tab[p - 1];
       if (i < Lmax) lab[i] = (int)(unsigned)edge - 1;
       p = (int)(edge >> 32);

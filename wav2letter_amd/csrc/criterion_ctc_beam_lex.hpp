@@ -58,11 +58,12 @@ __device__ __forceinline__ void beam_lex_best(const NgramView& lv, const LexView
   *key = best; *nst = bn; *lq = bq;
 }
 
-template <bool kLogAdd, int kThreads, class Pol = BeamCtc>
-__global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int W, float threshold, const float* __restrict__ x,
-                                                              const int* __restrict__ frames, CtcBeamWs ws,
-                                                              const void* __restrict__ lex, const void* __restrict__ lm,
-                                                              float lmWeight, float wordScore, BeamTrans tr) {
+// kResume: utterance b is a slot of a beam session (beam_lm_scan_body, criterion_beam_stream.hpp)
+template <bool kLogAdd, int kThreads, class Pol, bool kResume>
+__device__ __forceinline__ void beam_lex_scan_body(int T, int N, int W, float threshold, const float* __restrict__ x,
+                                                   const int* __restrict__ frames, const CtcBeamWs& ws,
+                                                   const void* __restrict__ lex, const void* __restrict__ lm, float lmWeight,
+                                                   float wordScore, BeamTrans tr, const BeamCarry& cy) {
   constexpr int kWaves = kThreads / 64;
   // the beam of this frame and the next one: prefix-table node, parent's node, last token, the label of the last extension, lexicon
   // node, its smear (0 at the root), LM state, pb, pnb, tot, unweighted LM sum
@@ -73,7 +74,13 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
   __shared__ float sTl[64];
   __shared__ u64 sRed[2][kWaves];
   const int b = blockIdx.x, tid = threadIdx.x, K = ws.K;
-  const int F = align_frames(frames, b, T);
+  int F;
+  bool fresh = true;
+  if constexpr (kResume) {
+    if (!beam_carry_begin(cy, b, T, &F, &fresh)) return;
+  } else {
+    F = align_frames(frames, b, T);
+  }
   const float* xb = x + (size_t)b * T * N;
   u64* tab = ws.table + (size_t)b * ws.cap;
   const unsigned capm = ws.cap - 1;
@@ -83,11 +90,14 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
   const float* A = Pol::stage(tr, N);
 
   int cur = 0, n = 1;
-  if (tid < 64) {
+  if (!fresh) {
+    n = beam_carry_load(cy, ws, b, N, sNode[0], sPar[0], sE[0], sPb[0], sPnb[0], sTot[0], sSt[0], sAcc[0], sLab[0], sU[0], sSu[0]);
+  } else if (tid < 64) {
     sNode[0][tid] = tid == 0 ? 0 : -2; sPar[0][tid] = -1; sE[0][tid] = -1; sLab[0][tid] = -1; sU[0][tid] = 0; sSu[0][tid] = 0.f;
     sPb[0][tid] = tid == 0 ? 0.f : -INFINITY; sPnb[0][tid] = -INFINITY; sTot[0][tid] = tid == 0 ? 0.f : -INFINITY;
     sSt[0][tid] = (int)((const NgramHeader*)lm)->start; sAcc[0][tid] = 0.f;
   }
+  if constexpr (kResume) __syncthreads();   // F may be 0: the store below reads what other threads wrote
   for (int t = 0; t < F && n > 0; ++t) {
     const size_t row = row0 + t;
     beam_load_frame(ws, row, sTc, sTl);
@@ -223,18 +233,28 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int 
     cur = nxt;
   }
   beam_store_final(ws, b, n, sNode[cur], sTot[cur], sSt[cur], sAcc[cur], sU[cur]);
+  if constexpr (kResume) beam_carry_store(cy, b, n, sPar[cur], sE[cur], sPb[cur], sPnb[cur], sLab[cur], sSu[cur]);
 }
 
-__global__ __launch_bounds__(64) void ctc_beam_lex_finish(int M, int Lmax, int maxWords, CtcBeamWs ws, const void* __restrict__ lex,
-                                                          const void* __restrict__ lm, float lmWeight, float eosScore, int useEos,
-                                                          int* __restrict__ labels, int* __restrict__ lengths,
-                                                          float* __restrict__ scores, float* __restrict__ lmScores,
-                                                          int* __restrict__ words, int* __restrict__ wordCounts) {
+template <bool kLogAdd, int kThreads, class Pol = BeamCtc>
+__global__ __launch_bounds__(kThreads) void ctc_beam_lex_scan(int T, int N, int W, float threshold, const float* __restrict__ x,
+                                                              const int* __restrict__ frames, CtcBeamWs ws,
+                                                              const void* __restrict__ lex, const void* __restrict__ lm,
+                                                              float lmWeight, float wordScore, BeamTrans tr) {
+  beam_lex_scan_body<kLogAdd, kThreads, Pol, false>(T, N, W, threshold, x, frames, ws, lex, lm, lmWeight, wordScore, tr, BeamCarry{});
+}
+
+// n: the final entries of utterance b; g: what bounds the walks up the prefix table (BeamWalk{}: nothing does)
+__device__ __forceinline__ void beam_lex_finish_body(int b, int n, BeamWalk g, int M, int Lmax, int maxWords, const CtcBeamWs& ws,
+                                                     const void* __restrict__ lex, const void* __restrict__ lm, float lmWeight,
+                                                     float eosScore, int useEos, int* __restrict__ labels,
+                                                     int* __restrict__ lengths, float* __restrict__ scores,
+                                                     float* __restrict__ lmScores, int* __restrict__ words,
+                                                     int* __restrict__ wordCounts) {
   __shared__ float sScore[64];
-  const int b = blockIdx.x, r = threadIdx.x;
+  const int r = threadIdx.x;
   const u64* tab = ws.table + (size_t)b * ws.cap;
   const LexView xv = lex_view(lex);
-  const int n = ws.finN[b];
   const bool alive = r < n && ws.finU[b * kBeamMax + r] == 0;   // only finished words count at the end
   float score = -INFINITY, acc = -INFINITY;
   if (alive) {
@@ -250,9 +270,9 @@ __global__ __launch_bounds__(64) void ctc_beam_lex_finish(int M, int Lmax, int m
   int len = 0, nwords = 0;
   if (alive) {
     const int node = ws.finNode[b * kBeamMax + r];
-    len = beam_chain_len(tab, node, &nwords);
+    len = beam_chain_len(tab, node, &nwords, g);
     int i = len - 1, j = nwords - 1;
-    for (int p = node; p > 0; --i) {
+    for (int p = node; i >= 0 && beam_walk_ok(g, p); --i) {
       const u64 edge = tab[p - 1];
       const unsigned l = (unsigned)edge - 1u;
       const int v = (int)(l >> 3), slot = (int)(l & 7u);
@@ -271,6 +291,15 @@ __global__ __launch_bounds__(64) void ctc_beam_lex_finish(int M, int Lmax, int m
   wordCounts[(size_t)b * M + m] = alive ? nwords : -1;
   scores[(size_t)b * M + m] = score;
   lmScores[(size_t)b * M + m] = acc;
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_lex_finish(int M, int Lmax, int maxWords, CtcBeamWs ws, const void* __restrict__ lex,
+                                                          const void* __restrict__ lm, float lmWeight, float eosScore, int useEos,
+                                                          int* __restrict__ labels, int* __restrict__ lengths,
+                                                          float* __restrict__ scores, float* __restrict__ lmScores,
+                                                          int* __restrict__ words, int* __restrict__ wordCounts) {
+  beam_lex_finish_body(blockIdx.x, ws.finN[blockIdx.x], BeamWalk{}, M, Lmax, maxWords, ws, lex, lm, lmWeight, eosScore, useEos, labels,
+                       lengths, scores, lmScores, words, wordCounts);
 }
 
 }  // namespace w2l

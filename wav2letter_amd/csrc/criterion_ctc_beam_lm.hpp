@@ -32,12 +32,15 @@ __device__ __forceinline__ float beam_lm_ext(float a, float lmWeight, float q, c
   return a + g;
 }
 
-// Pol::kNoBlank: lm may be null, which means no LM: no g term, q = 0, state 0
-template <bool kLogAdd, int kThreads, class Pol = BeamCtc>
-__global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W, float threshold,
-                                                             const float* __restrict__ x, const int* __restrict__ frames,
-                                                             CtcBeamWs ws, const void* __restrict__ lm, float lmWeight,
-                                                             const float* __restrict__ classScore, BeamTrans tr) {
+// Pol::kNoBlank or kResume: lm may be null, which means no LM: no g term, q = 0, state 0.
+// kResume (criterion_beam_stream.hpp): utterance b is a slot of a beam session: its frame count (0: none) and start flag come from
+// cy.cnt / cy.flag, the beam from the session's state unless the slot starts, and every array of the beam goes back there after
+// the frames.  ctc_beam_lm_scan below is the body with kResume off: the whole search.
+template <bool kLogAdd, int kThreads, class Pol, bool kResume>
+__device__ __forceinline__ void beam_lm_scan_body(int T, int N, int W, float threshold, const float* __restrict__ x,
+                                                  const int* __restrict__ frames, const CtcBeamWs& ws, const void* __restrict__ lm,
+                                                  float lmWeight, const float* __restrict__ classScore, BeamTrans tr,
+                                                  const BeamCarry& cy) {
   constexpr int kWaves = kThreads / 64;
   __shared__ int sNode[2][64], sPar[2][64], sE[2][64], sSt[2][64];   // the beam of this frame and the next one
   __shared__ float sPb[2][64], sPnb[2][64], sTot[2][64], sAcc[2][64];
@@ -46,21 +49,30 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
   __shared__ float sTl[64];
   __shared__ u64 sRed[2][kWaves];
   const int b = blockIdx.x, tid = threadIdx.x, K = ws.K;
-  const int F = align_frames(frames, b, T);
+  int F;
+  bool fresh = true;
+  if constexpr (kResume) {
+    if (!beam_carry_begin(cy, b, T, &F, &fresh)) return;
+  } else {
+    F = align_frames(frames, b, T);
+  }
   const float* xb = x + (size_t)b * T * N;
   u64* tab = ws.table + (size_t)b * ws.cap;
   const unsigned capm = ws.cap - 1;
   const size_t row0 = (size_t)b * T;
-  const bool useLm = !Pol::kNoBlank || lm != nullptr;
+  const bool useLm = !(Pol::kNoBlank || kResume) || lm != nullptr;
   const NgramView lv = useLm ? ngram_view(lm) : NgramView{};
   const float* A = Pol::stage(tr, N);
 
   int cur = 0, n = 1;
-  if (tid < 64) {
+  if (!fresh) {
+    n = beam_carry_load(cy, ws, b, N, sNode[0], sPar[0], sE[0], sPb[0], sPnb[0], sTot[0], sSt[0], sAcc[0], nullptr, nullptr, nullptr);
+  } else if (tid < 64) {
     sNode[0][tid] = tid == 0 ? 0 : -2; sPar[0][tid] = -1; sE[0][tid] = -1;
     sPb[0][tid] = tid == 0 ? 0.f : -INFINITY; sPnb[0][tid] = -INFINITY; sTot[0][tid] = tid == 0 ? 0.f : -INFINITY;
     sSt[0][tid] = useLm ? (int)((const NgramHeader*)lm)->start : 0; sAcc[0][tid] = 0.f;
   }
+  if constexpr (kResume) __syncthreads();   // F may be 0: the store below reads what other threads wrote
   for (int t = 0; t < F && n > 0; ++t) {
     const size_t row = row0 + t;
     beam_load_frame(ws, row, sTc, sTl);
@@ -164,16 +176,25 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W
     cur = nxt;
   }
   beam_store_final(ws, b, n, sNode[cur], sTot[cur], sSt[cur], sAcc[cur], nullptr);
+  if constexpr (kResume) beam_carry_store(cy, b, n, sPar[cur], sE[cur], sPb[cur], sPnb[cur], nullptr, nullptr);
 }
 
-__global__ __launch_bounds__(64) void ctc_beam_lm_finish(int M, int Lmax, int eosWord, CtcBeamWs ws, const void* __restrict__ lm,
-                                                         float lmWeight, float eosScore, int useEos, int* __restrict__ labels,
-                                                         int* __restrict__ lengths, float* __restrict__ scores,
-                                                         float* __restrict__ lmScores) {
+template <bool kLogAdd, int kThreads, class Pol = BeamCtc>
+__global__ __launch_bounds__(kThreads) void ctc_beam_lm_scan(int T, int N, int W, float threshold,
+                                                             const float* __restrict__ x, const int* __restrict__ frames,
+                                                             CtcBeamWs ws, const void* __restrict__ lm, float lmWeight,
+                                                             const float* __restrict__ classScore, BeamTrans tr) {
+  beam_lm_scan_body<kLogAdd, kThreads, Pol, false>(T, N, W, threshold, x, frames, ws, lm, lmWeight, classScore, tr, BeamCarry{});
+}
+
+// n: the final entries of utterance b; g: what bounds the walks up the prefix table (BeamWalk{}: nothing does)
+__device__ __forceinline__ void beam_lm_finish_body(int b, int n, BeamWalk g, int M, int Lmax, int eosWord, const CtcBeamWs& ws,
+                                                    const void* __restrict__ lm, float lmWeight, float eosScore, int useEos,
+                                                    int* __restrict__ labels, int* __restrict__ lengths,
+                                                    float* __restrict__ scores, float* __restrict__ lmScores) {
   __shared__ float sScore[64];
-  const int b = blockIdx.x, r = threadIdx.x;
+  const int r = threadIdx.x;
   const u64* tab = ws.table + (size_t)b * ws.cap;
-  const int n = ws.finN[b];
   const bool live = r < n;
   float score = -INFINITY, acc = -INFINITY;
   if (live) {
@@ -183,10 +204,18 @@ __global__ __launch_bounds__(64) void ctc_beam_lm_finish(int M, int Lmax, int eo
   }
   const int m = beam_rerank(score, live, sScore);   // rows n .. M-1 are the empty ones
   if (m >= M) return;
-  const int len = beam_write_labels(tab, live, ws.finNode + b * kBeamMax + r, Lmax, labels + ((size_t)b * M + m) * Lmax);
+  const int len = beam_write_labels(tab, live, ws.finNode + b * kBeamMax + r, Lmax, labels + ((size_t)b * M + m) * Lmax, g);
   lengths[(size_t)b * M + m] = live ? len : -1;
   scores[(size_t)b * M + m] = score;
   lmScores[(size_t)b * M + m] = acc;
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_lm_finish(int M, int Lmax, int eosWord, CtcBeamWs ws, const void* __restrict__ lm,
+                                                         float lmWeight, float eosScore, int useEos, int* __restrict__ labels,
+                                                         int* __restrict__ lengths, float* __restrict__ scores,
+                                                         float* __restrict__ lmScores) {
+  beam_lm_finish_body(blockIdx.x, ws.finN[blockIdx.x], BeamWalk{}, M, Lmax, eosWord, ws, lm, lmWeight, eosScore, useEos, labels,
+                      lengths, scores, lmScores);
 }
 
 }  // namespace w2l

@@ -1313,6 +1313,84 @@ af::array CTCLoss::viterbiPathWithTarget(const af::array& input, const af::array
   af::sync();  // ws is released at return
   return path;
 }
+// ---- the CTC beam search continued chunk by chunk (csrc/criterion_beam_stream.hpp)
+StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& o)
+    : o_(o), slots_(slots), maxChunk_(maxChunk), maxFrames_(maxFrames), nLabel_(numLabels) {
+  if (o.wide) throw std::runtime_error("StreamingDecoder: the wide searches (beam above 64) are not incremental");
+  if (o.nbest < 1 || o.maxLen < 0 || o.maxWords < 0) throw std::invalid_argument("StreamingDecoder: bad nbest, maxLen or maxWords");
+  w2l_beam_session_desc d{};
+  d.slots = slots; d.maxChunk = maxChunk; d.maxFrames = maxFrames; d.N = numLabels;
+  d.beam = o.beamSize; d.beamToken = o.beamSizeToken; d.threshold = o.beamThreshold;
+  d.logAdd = o.logAdd ? 1 : 0;
+  d.normalize = o.normalize < 0 ? d.logAdd : (o.normalize != 0 ? 1 : 0);
+  d.variant = o.lexicon ? W2L_BEAM_LEX : o.lm ? W2L_BEAM_LM : W2L_BEAM_PLAIN;
+  d.lmWeight = o.lmWeight; d.eosScore = o.eosScore; d.wordScore = o.wordScore;
+  if (o.lexicon) {
+    if (!o.lm) throw std::invalid_argument("StreamingDecoder: lexicon needs lm, a model over the lexicon's words");
+    if (!o.classScore.isempty()) throw std::invalid_argument("StreamingDecoder: classScore must be empty with a lexicon");
+    if (o.lm->numTokens() != o.lexicon->numWords()) throw std::invalid_argument("StreamingDecoder: the LM's word count is not the lexicon's");
+    if (o.lexicon->numTokens() != numLabels - 1) throw std::invalid_argument("StreamingDecoder: the lexicon's token count is not NLABEL - 1");
+    d.lexicon = o.lexicon->deviceBlob();
+  } else if (o.maxWords != 0) {
+    throw std::invalid_argument("StreamingDecoder: maxWords needs lexicon");
+  } else if (o.lm) {
+    if (o.lm->numTokens() != numLabels - 1) throw std::invalid_argument("StreamingDecoder: the LM's token count is not NLABEL - 1");
+    if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != numLabels - 1))
+      throw std::invalid_argument("StreamingDecoder: classScore must be f32 with one entry per token class");
+    if (!o.classScore.isempty()) d.classScore = o_.classScore.device<float>();
+  }
+  if (o.lm) { d.lm = o.lm->deviceBlob(); d.lmHasEos = o.lm->hasEos() ? 1 : 0; }
+  const int st = w2l_beam_session_create(&d, &h_);
+  if (st == W2L_EUNSUPPORTED) throw std::runtime_error(std::string("StreamingDecoder: ") + w2l_host_last_error());
+  if (st != W2L_OK) throw std::invalid_argument(std::string("StreamingDecoder: ") + w2l_host_last_error());
+  const size_t bytes = w2l_beam_session_state_bytes(&d);
+  state_ = devAlloc(bytes);
+  if (w2l_beam_session_bind(h_, state_.get(), bytes) != W2L_OK) {
+    const std::string msg = w2l_host_last_error();
+    w2l_beam_session_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error("StreamingDecoder: " + msg);
+  }
+}
+StreamingDecoder::~StreamingDecoder() { if (h_) w2l_beam_session_destroy(h_); }
+void StreamingDecoder::step(const af::array& emissions, const std::vector<int>& counts, const std::vector<int>& start) {
+  if (emissions.type() != af::f32 || emissions.dims(0) != nLabel_ || emissions.dims(1) != maxChunk_ || emissions.dims(2) != slots_)
+    throw std::invalid_argument("StreamingDecoder::step: emissions must be f32 (NLABEL, maxChunk, slots)");
+  if ((int)counts.size() != slots_ || (!start.empty() && (int)start.size() != slots_))
+    throw std::invalid_argument("StreamingDecoder::step: one count / flag per slot");
+  const int st = w2l_beam_session_step(h_, emissions.device<float>(), counts.data(), start.empty() ? nullptr : start.data(), S());
+  if (st == W2L_EINVAL) throw std::invalid_argument(std::string("StreamingDecoder::step: ") + w2l_host_last_error());
+  w2l::w2lCheck(st, "StreamingDecoder::step");
+}
+BeamSearchResult StreamingDecoder::result() {
+  const int M = o_.nbest, Lmax = o_.maxLen > 0 ? o_.maxLen : maxFrames_, maxWords = o_.maxWords > 0 ? o_.maxWords : Lmax;
+  BeamSearchResult r;
+  r.labels = af::array(af::dim4(Lmax, M, slots_), af::s32);
+  r.lengths = af::array(af::dim4(M, slots_), af::s32);
+  r.scores = af::array(af::dim4(M, slots_));
+  af::array lms(af::dim4(M, slots_));
+  if (o_.lexicon) {
+    r.words = af::array(af::dim4(maxWords, M, slots_), af::s32);
+    r.wordCounts = af::array(af::dim4(M, slots_), af::s32);
+  }
+  const int st = w2l_beam_session_result(h_, M, Lmax, r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
+                                         lms.device<float>(), maxWords, o_.lexicon ? r.words.device<int>() : nullptr,
+                                         o_.lexicon ? r.wordCounts.device<int>() : nullptr, S());
+  if (st == W2L_EINVAL) throw std::invalid_argument(std::string("StreamingDecoder::result: ") + w2l_host_last_error());
+  w2l::w2lCheck(st, "StreamingDecoder::result");
+  if (o_.lm) r.lmScores = lms;
+  else af::sync();   // lms is released at return
+  return r;
+}
+int StreamingDecoder::frames(int slot) const {
+  int f = 0;
+  if (w2l_beam_session_frames(h_, slot, &f) != W2L_OK) throw std::invalid_argument(std::string("StreamingDecoder::frames: ") + w2l_host_last_error());
+  return f;
+}
+void StreamingDecoder::reset(int slot) {
+  if (w2l_beam_session_reset(h_, slot) != W2L_OK) throw std::invalid_argument(std::string("StreamingDecoder::reset: ") + w2l_host_last_error());
+}
+
 // n-best beam search; inputSizes as in viterbiPathWithTarget.  trans == nullptr: the CTC searches (w2l_ctc_beam_search*), blank =
 // N-1; else the ASG searches (w2l_asg_beam_search*) under that transition matrix, every class a token; o.wide: their _wide twins
 static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, const float* trans, const af::array& input,

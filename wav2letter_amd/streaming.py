@@ -4,6 +4,10 @@ A StreamingSession runs a trained network on audio as it arrives: `slots` concur
 frames per slot and step.  For any utterance and any split of it into chunks the concatenated emissions equal
 Trainer.forward(train=False) of that utterance alone (fp32 parity), and the frame count equals its Tout.  Feature extraction
 and normalisation stay with the caller.
+
+A StreamingDecoder (csrc/criterion_beam_stream.hpp) is the CTC beam search continued chunk by chunk over such emissions: it
+takes StreamingSession.step's output directly, and its result after any number of frames is, bit for bit, ctc_beam_search of
+those frames alone.
 """
 import ctypes as C
 
@@ -142,3 +146,165 @@ class StreamingSession:
     def reset(self, slot):
         """closes a slot and discards its state"""
         _check(self.L.w2l_stream_reset(self.h, int(slot)), "stream reset")
+
+
+BEAM_PLAIN, BEAM_LM, BEAM_LEX = 0, 1, 2
+
+
+class StreamingDecoder:
+    """StreamingDecoder(slots, max_chunk, max_frames, nlabel, **options): an incremental criterion.ctc_beam_search (the contract is
+    in include/w2l_hip.h, w2l_beam_session_*).  `slots` utterances in progress, at most max_chunk emission frames per slot and
+    step, at most max_frames per utterance.  options: ctc_beam_search's beam, beam_token, threshold, log_add, normalize, lm,
+    lm_weight, class_score, eos_score, lexicon, word_score; the variant is chosen as ctc_beam_search chooses its entry point (no
+    lm: LM-free; lm: token LM; lm and lexicon: lexicon with a word LM).  wide=True is refused: the wide searches are not
+    incremental.  With max_chunk = StreamingSession.max_out, step() takes StreamingSession.step's (out, n_out) as they are.
+    Creation is host arithmetic; the device state is allocated at the first step."""
+
+    def __init__(self, slots, max_chunk, max_frames, nlabel, beam=64, beam_token=64, threshold=float("inf"), log_add=False,
+                 normalize=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0, wide=False,
+                 device="cuda"):
+        if wide:
+            raise _lib.W2LUnsupported("StreamingDecoder: the wide searches (beam above 64) are not incremental")
+        N = int(nlabel)
+        if lexicon is not None:
+            if lm is None:
+                raise _lib.W2LInvalidArgument("StreamingDecoder: lexicon needs lm, a model over the lexicon's words")
+            if class_score is not None:
+                raise _lib.W2LInvalidArgument("StreamingDecoder: class_score must be None with a lexicon")
+            if lm.num_tokens != lexicon.num_words:
+                raise _lib.W2LInvalidArgument(f"StreamingDecoder: the LM has {lm.num_tokens} words, the lexicon {lexicon.num_words}")
+            if lexicon.num_tokens != N - 1:
+                raise _lib.W2LInvalidArgument(f"StreamingDecoder: the lexicon has {lexicon.num_tokens} tokens, the emissions {N - 1}")
+            variant = BEAM_LEX
+        elif word_score != 0.0:
+            raise _lib.W2LInvalidArgument("StreamingDecoder: word_score needs lexicon")
+        elif lm is None:
+            if lm_weight != 0.0 or class_score is not None or eos_score != 0.0:
+                raise _lib.W2LInvalidArgument("StreamingDecoder: lm_weight, class_score and eos_score need lm")
+            variant = BEAM_PLAIN
+        else:
+            if lm.num_tokens != N - 1:
+                raise _lib.W2LInvalidArgument(f"StreamingDecoder: the LM has {lm.num_tokens} tokens, the emissions {N - 1}")
+            if class_score is not None and not (torch.is_tensor(class_score) and class_score.dtype == torch.float32
+                                                and class_score.numel() == N - 1):
+                raise _lib.W2LInvalidArgument("StreamingDecoder: class_score must be float32 with one entry per token class")
+            variant = BEAM_LM
+        if normalize is None:
+            normalize = bool(log_add)
+        self.L = _lib.lib()
+        self.slots, self.max_chunk, self.max_frames, self.nlabel = int(slots), int(max_chunk), int(max_frames), N
+        self.beam, self.variant, self.device = int(beam), variant, device
+        # the descriptor is checked here, on the host, with placeholders for the device tables (the check looks at presence only);
+        # the session itself is created with the tables at the first step
+        self._lm, self._lexicon, self._class_score = lm, lexicon, class_score
+        self._opts = dict(beam=int(beam), beamToken=int(beam_token), threshold=float(threshold), logAdd=int(bool(log_add)),
+                          normalize=int(bool(normalize)), lmHasEos=int(lm.has_eos) if lm is not None else 0, lmWeight=float(lm_weight),
+                          eosScore=float(eos_score), wordScore=float(word_score))
+        self.h = None
+        self._state = None
+        self._keep = ()
+        self.state_bytes = 0
+        self._create(placeholders=True)
+
+    def _desc(self, lm_ptr, lex_ptr, cs_ptr):
+        return _lib.BeamSessionDesc(slots=self.slots, maxChunk=self.max_chunk, maxFrames=self.max_frames, N=self.nlabel, variant=self.variant,
+                                    lm=lm_ptr, lexicon=lex_ptr, classScore=cs_ptr, **self._opts)
+
+    def _create(self, placeholders):
+        if placeholders:   # host only: any non-null value stands for a table that is given
+            ptrs = (1 if self._lm is not None else None, 1 if self._lexicon is not None else None,
+                    1 if self._class_score is not None else None)
+        else:
+            dev = self.device
+            blob = self._lm.device_blob(dev) if self._lm is not None else None
+            lex = self._lexicon.device_blob(dev) if self._lexicon is not None else None
+            cs = self._class_score.contiguous() if self._class_score is not None else None
+            if cs is not None and not cs.is_cuda:
+                raise _lib.W2LInvalidArgument("StreamingDecoder: class_score must be on the device")
+            self._keep = (blob, lex, cs)
+            ptrs = tuple(t.data_ptr() if t is not None else None for t in self._keep)
+        d = self._desc(*ptrs)
+        h = C.c_void_p(0)
+        _check(self.L.w2l_beam_session_create(C.byref(d), C.byref(h)), "streaming decoder")
+        self.state_bytes = self.L.w2l_beam_session_state_bytes(C.byref(d))
+        if placeholders:
+            self.L.w2l_beam_session_destroy(h)
+        else:
+            self.h = h
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.L.w2l_beam_session_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _bind(self, device):
+        self.device = device
+        self._create(placeholders=False)
+        self._state = torch.empty(max(self.state_bytes, 256), dtype=torch.uint8, device=device)
+        _check(self.L.w2l_beam_session_bind(self.h, self._state.data_ptr(), self._state.numel()), "streaming decoder bind")
+
+    def step(self, emissions, counts, start=None):
+        """emissions: [S][max_chunk][NLABEL] float32 on the device, rows [0, counts[s]) of slot s are its new frames; counts /
+        start: one int per slot on the host.  start[s]: the slot begins a new utterance before these frames.  Does not
+        synchronise."""
+        S = self.slots
+        if not (torch.is_tensor(emissions) and emissions.is_cuda and emissions.dtype == torch.float32 and emissions.is_contiguous()
+                and tuple(emissions.shape) == (S, self.max_chunk, self.nlabel)):
+            raise _lib.W2LInvalidArgument(
+                f"emissions must be a contiguous float32 CUDA tensor [S={S}][max_chunk={self.max_chunk}][NLABEL={self.nlabel}], got "
+                f"{tuple(emissions.shape) if torch.is_tensor(emissions) else type(emissions)}")
+        n, st = _flags(counts, S, "counts"), _flags(start, S, "start")
+        if self._state is None:
+            self._bind(emissions.device)
+        _check(self.L.w2l_beam_session_step(self.h, emissions.data_ptr(), n.ctypes.data, st.ctypes.data,
+                                            torch.cuda.current_stream().cuda_stream), "streaming decoder step")
+
+    def result(self, nbest=1, max_len=None, max_words=None):
+        """the tuple ctc_beam_search returns for this variant, one row block per slot ([S][nbest]...), for the frames fed so far;
+        changes nothing.  max_len defaults to max_frames, max_words to max_len."""
+        if self._state is None:
+            self._bind(self.device)
+        S, nbest = self.slots, int(nbest)
+        max_len = self.max_frames if max_len is None else int(max_len)
+        if max_words is not None and self.variant != BEAM_LEX:
+            raise _lib.W2LInvalidArgument("StreamingDecoder: max_words needs lexicon")
+        max_words = max(max_len, 1) if max_words is None else int(max_words)
+        dev, shape = self._state.device, (S, max(nbest, 1))
+        labels = torch.empty(*shape, max(max_len, 1), dtype=torch.int32, device=dev)
+        lengths = torch.empty(*shape, dtype=torch.int32, device=dev)
+        scores = torch.empty(*shape, dtype=torch.float32, device=dev)
+        lm_scores = torch.empty(*shape, dtype=torch.float32, device=dev)
+        words = word_counts = None
+        if self.variant == BEAM_LEX:
+            words = torch.empty(*shape, max(max_words, 1), dtype=torch.int32, device=dev)
+            word_counts = torch.empty(*shape, dtype=torch.int32, device=dev)
+        _check(self.L.w2l_beam_session_result(self.h, nbest, max_len, labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(),
+                                              lm_scores.data_ptr(), max_words, words.data_ptr() if words is not None else None,
+                                              word_counts.data_ptr() if word_counts is not None else None,
+                                              torch.cuda.current_stream().cuda_stream), "streaming decoder result")
+        if self.variant == BEAM_LEX:
+            return labels, lengths, scores, lm_scores, words, word_counts
+        if self.variant == BEAM_LM:
+            return labels, lengths, scores, lm_scores
+        return labels, lengths, scores
+
+    def frames(self, slot):
+        """emission frames fed to a slot since its start"""
+        if not 0 <= int(slot) < self.slots:
+            raise _lib.W2LInvalidArgument(f"StreamingDecoder: no slot {slot}")
+        if self.h is None:
+            return 0
+        f = C.c_int(0)
+        _check(self.L.w2l_beam_session_frames(self.h, int(slot), C.byref(f)), "streaming decoder frames")
+        return f.value
+
+    def reset(self, slot):
+        """closes a slot"""
+        if not 0 <= int(slot) < self.slots:
+            raise _lib.W2LInvalidArgument(f"StreamingDecoder: no slot {slot}")
+        if self.h is None:
+            return
+        _check(self.L.w2l_beam_session_reset(self.h, int(slot)), "streaming decoder reset")
