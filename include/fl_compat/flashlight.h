@@ -500,9 +500,14 @@ FL_COMPAT_API std::shared_ptr<fl::Sequential> buildSequentialModuleFromText(cons
 // session reads the network's parameter arena at every step and keeps the network alive.  A network with a line that cannot be
 // streamed (TR, M, GLU, LN over time, TDS with lnIncludeTime = 1, SAME padding at a stride above 1) or in mixed-precision mode
 // throws std::invalid_argument naming the line.
+// mixedPrecision = true: a bf16 session (W2L_STREAM_BF16) over a network whose mixed-precision mode is on (setMixedPrecision;
+// std::invalid_argument otherwise, and for the second level, setMixedPrecisionConvolutions): bf16 operands for the fl::Linear
+// products and the TDS convolutions, equal to the network's own mixed-precision eval forward within 2e-3.  Such a session holds a
+// SNAPSHOT of the model -- it copies the parameters and writes the bf16 weight images at its first step -- and shows later changes
+// of the parameters only after refreshWeights(), unlike the fp32 session, which reads the live arena at every step.
 class FL_COMPAT_API StreamingSession {
  public:
-  StreamingSession(std::shared_ptr<fl::Sequential> network, int slots, int maxChunk);
+  StreamingSession(std::shared_ptr<fl::Sequential> network, int slots, int maxChunk, bool mixedPrecision = false);
   ~StreamingSession();
   StreamingSession(const StreamingSession&) = delete;
   StreamingSession& operator=(const StreamingSession&) = delete;
@@ -517,12 +522,15 @@ class FL_COMPAT_API StreamingSession {
   af::array step(const af::array& features, const std::vector<int>& counts, const std::vector<int>& start, const std::vector<int>& finish,
                  std::vector<int>& nOut);
   void reset(int slot);                        // closes a slot and discards its state
+  bool mixedPrecision() const { return mixed_; }
+  void refreshWeights();                       // bf16: the next step takes the parameters again (host only; a no-op for fp32)
 
  private:
   std::shared_ptr<fl::Sequential> net_;
   std::shared_ptr<void> state_;
   void* h_ = nullptr;
   int slots_ = 0, maxChunk_ = 0, maxOut_ = 0, nFeat_ = 0, nLabel_ = 0;
+  bool mixed_ = false;
 };
 
 class FL_COMPAT_API SequenceCriterion : public fl::Container {

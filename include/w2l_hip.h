@@ -583,6 +583,29 @@ typedef struct {
 int w2l_gemm_bf16_images(int M, int N, int K, const uint16_t* A, int lda, const uint16_t* B, int ldb, float* C, int ldc,
                          const float* bias, int relu, const w2l_gemm_epilogue* epilogue, const w2l_bf16_image_sink* images,
                          const uint16_t* maskImage, size_t ldMask, float maskScale, w2l_stream_t stream);
+/* w2l_gemm_bf16_smallm (csrc/gemm_smallm.hip): the same product for FEW rows -- the M = slots x a few frames of a streaming step,
+ * where the block tiles of w2l_gemm_bf16 leave most of the chip idle.  C[M][N] (fp32, ldc >= N) = A[M][K] . B[N][K]^T (+ bias[n])
+ * (ReLU) (+ addend[m][n], the layout of C), bf16 operands, fp32 accumulation.
+ *   A: row-major activation image [M][lda], B: transposed weight image [N][ldb], as w2l_bf16_convert writes them: rows ZERO from
+ *      column K up to K rounded to 64; lda, ldb >= that and multiples of 8; 16-byte aligned bases.
+ *   image: NULL, or a sink whose rowMajor image [M][ldRows >= N] receives what w2l_bf16_convert would make of C, bit for bit (only
+ *      elements of the matrix are written); its `transposed` must be NULL (W2L_EINVAL otherwise).  C may be NULL when the image is given.
+ *   Any N >= 1 and K >= 1; M from 1 to w2l_gemm_bf16_smallm_max_m() (1024).  Above it: W2L_EUNSUPPORTED -- stay on w2l_gemm_bf16.
+ *   workspace: w2l_gemm_bf16_smallm_workspace_bytes(M, N, K) bytes on the device.  The query is host arithmetic and returns 0
+ *      today (one launch, no partial sums: pass NULL, 0); query and arguments stay so that a variant that needs one keeps the ABI.
+ * Every weight byte is read from HBM once per call, in whole 128-byte lines along K.  K is NOT split: an element is one chain of
+ * MFMAs over k = 0, 16, 32, ..., the chain and the epilogue arithmetic of w2l_gemm_bf16 -- wherever that one does not split K
+ * itself (K < 4096) the two results are bit-identical, which is what lets a session equal the trainer's forward: any other
+ * summation order, however accurate, moves bf16 roundings of the activations and the difference grows block by block (DESIGN
+ * 3.14).  Occupancy comes from narrow slabs of weight rows (16; 32 from N = 4096).  The call is deterministic, and row r of the
+ * result is a function of row r of A and of B only: bit-identical whatever M is and whatever the other rows of A hold, NaN included.
+ * Null pointers, non-positive sizes, a leading dimension below K (rounded to 64): W2L_EINVAL.  All checks precede the first
+ * launch.  The probe library returns W2L_EUNSUPPORTED for every call while W2L_SMALLM_OFF is set. */
+int w2l_gemm_bf16_smallm_max_m(void);
+size_t w2l_gemm_bf16_smallm_workspace_bytes(int M, int N, int K);
+int w2l_gemm_bf16_smallm(int M, int N, int K, const uint16_t* A, int lda, const uint16_t* B, int ldb, float* C, int ldc,
+                         const float* bias, int relu, const float* addend, const w2l_bf16_image_sink* image, void* workspace,
+                         size_t workspaceBytes, w2l_stream_t stream);
 /* r = dropout(a) + x ; y = LayerNorm(r) over `groups` contiguous chunks of `inner`
  * elements with scalar affine gammaBeta[2] (fl::LayerNorm axes {0,1,2}: groups = B).
  * a is updated in place to its dropped value; r, meanRstd[2*groups] are kept for
@@ -889,7 +912,8 @@ int w2l_flags_check(const char* flagsText, int* numFlags);
  * Streamable lines: V, RO, SAUG, DO (identity in eval), PD on the time axis, C / C1 / C2 with explicit padding (or SAME at
  * stride 1), R, LN without the time axis, TDS with lnIncludeTime = 0, L, WN around C / L.  Any other line -- TR, M, GLU, LN over
  * time, TDS with lnIncludeTime = 1, SAME padding at a stride above 1 -- is refused at creation with W2L_EUNSUPPORTED and a
- * w2l_host_last_error() that names the line; so is a trainer in mixed-precision mode (fp32 only).
+ * w2l_host_last_error() that names the line; so is a trainer in mixed-precision mode by w2l_stream_create_for_trainer (fp32 only;
+ * the _ex calls below open mixed precision).
  * create / create_for_trainer / query / counts / slot_state / reset are host arithmetic and need no device.
  *   w2l_stream_create(archText, ...)       parameters come from w2l_stream_bind
  *   w2l_stream_create_for_trainer(h, ...)  arch of the trainer; parameters are the trainer's bound arena at every step unless
@@ -931,6 +955,29 @@ int w2l_stream_step(void* session, const float* x, const int* n, const int* star
 int w2l_stream_reset(void* session, int slot);
 int w2l_stream_window(const float* src, int srcRows, const float* carryIn, float* carryOut, int carryCap, float* win, int W,
                       float* res, int resShift, int To, const int* tab, int S, int F, w2l_stream_t stream);
+/* Precision is a property of a session, chosen at creation through the _ex calls.  W2L_STREAM_FP32: exactly the calls above.
+ * W2L_STREAM_BF16: the session computes what the mixed-precision eval forward rounds (w2l_trainer_set_mixed_precision): bf16 operands
+ * for every fl::Linear product and for every convolution that has a bf16 kernel at the window's geometry (w2l_tds_conv_bf16_*);
+ * fp32 accumulation, LayerNorm, residuals, carries, hand-over kernel and count arithmetic; lin1's output of a TDS block only as its
+ * bf16 row image.  Its emissions equal the mixed-precision w2l_trainer_forward(train = 0) within the mixed-precision bar (2e-3 of the
+ * largest magnitude), frame counts exactly -- in fact bit for bit on the recipe's shapes: the products run on w2l_gemm_bf16_smallm
+ * up to 96 rows and on w2l_gemm_bf16 above (where the tile kernel is faster), and the two give the same bits.
+ *   A BF16 SESSION HOLDS A SNAPSHOT OF THE MODEL.  On the first step after w2l_stream_bind, on that step's stream, it copies the
+ *   parameter arena into its own state and writes the bf16 weight images from the copy; no later step reads the caller's
+ *   parameters or converts a weight.  This differs from an FP32 session over a trainer, which reads the trainer's live arena at
+ *   every step: a BF16 session shows further training only after w2l_stream_refresh_weights (pure host: it marks the snapshot
+ *   stale, the next step takes it again; a no-op for FP32 and for an unbound session).  The state is larger by the copy
+ *   (w2l_stream_state_bytes / w2l_stream_query_ex tell).
+ *   Over a trainer, BF16 requires the trainer's mixed-precision mode to be ON (W2L_EINVAL otherwise, at creation and at a step:
+ *   the contract stays "the session equals this trainer's own forward") and its second level (w2l_trainer_set_mixed_precision_convs)
+ *   to be OFF (W2L_EUNSUPPORTED, named in the error text: the wide-convolution scratch is not planned for sessions).  FP32 over a
+ *   mixed-precision trainer stays refused with W2L_EUNSUPPORTED. */
+enum { W2L_STREAM_FP32 = 0, W2L_STREAM_BF16 = 1 };
+int w2l_stream_create_ex(const char* archText, int nFeat, int nLabel, int slots, int maxChunk, int precision, void** session);
+int w2l_stream_create_for_trainer_ex(void* trainer, int slots, int maxChunk, int precision, void** session);
+int w2l_stream_query_ex(const char* archText, int nFeat, int nLabel, int slots, int maxChunk, int precision, int* maxOut,
+                        size_t* stateBytes);
+int w2l_stream_refresh_weights(void* session);
 
 /* ---- incremental CTC beam search for streaming (csrc/criterion_beam_stream.hpp) -----------------------------------------
  * A beam SESSION has S slots; a slot holds the search state of one utterance in progress.  A step advances every slot by the

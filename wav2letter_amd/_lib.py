@@ -157,6 +157,9 @@ class _SIGS:
     w2l_gemm_bf16_images = (_i, [_i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _sz, _f, _p])
     w2l_bf16_convert_dropout = (_i, [_p, _sz, _i, _sz, _p, _sz, _p, _sz, _d, _u32, _u32, _p])
     w2l_gemm_bf16 = (_i, [_i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p])
+    w2l_gemm_bf16_smallm = (_i, [_i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _sz, _p])
+    w2l_gemm_bf16_smallm_max_m = (_i, [])
+    w2l_gemm_bf16_smallm_workspace_bytes = (_sz, [_i, _i, _i])
     w2l_gemm_bf16_ex = (_i, [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _p])
     w2l_gemm_bf16_grouped = (_i, [_i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p])
     w2l_tds_conv_bf16_image_elems = (_sz, [_p])
@@ -236,6 +239,10 @@ class _SIGS:
     w2l_stream_slot_state = (_i, [_p, _i, _p, _p, _i])
     w2l_stream_step = (_i, [_p, _p, _p, _p, _p, _p, _p, _p])
     w2l_stream_reset = (_i, [_p, _i])
+    w2l_stream_create_ex = (_i, [C.c_char_p, _i, _i, _i, _i, _i, _p])
+    w2l_stream_create_for_trainer_ex = (_i, [_p, _i, _i, _i, _p])
+    w2l_stream_query_ex = (_i, [C.c_char_p, _i, _i, _i, _i, _i, _p, _p])
+    w2l_stream_refresh_weights = (_i, [_p])
     w2l_stream_window = (_i, [_p, _i, _p, _p, _i, _p, _i, _p, _i, _i, _p, _i, _i, _p])
     w2l_beam_session_create = (_i, [_p, _p])
     w2l_beam_session_destroy = (None, [_p])

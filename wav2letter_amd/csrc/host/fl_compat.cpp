@@ -1010,15 +1010,21 @@ std::shared_ptr<fl::Sequential> buildSequentialModule(const std::string& archfil
 
 
 // ---- chunked streaming forward over a planned network (host/stream.cpp)
-StreamingSession::StreamingSession(std::shared_ptr<fl::Sequential> network, int slots, int maxChunk) : net_(std::move(network)), slots_(slots), maxChunk_(maxChunk) {
+StreamingSession::StreamingSession(std::shared_ptr<fl::Sequential> network, int slots, int maxChunk, bool mixedPrecision)
+    : net_(std::move(network)), slots_(slots), maxChunk_(maxChunk), mixed_(mixedPrecision) {
   if (!net_) throw std::invalid_argument("StreamingSession: null network");
   std::shared_ptr<fl::Sequential> planned = net_->planned();
   PlannedNet* pn = dynamic_cast<PlannedNet*>(planned ? planned.get() : net_.get());
   if (!pn) throw std::invalid_argument("StreamingSession: the network is not a planned arch pipeline (an arch file or layer objects)");
-  if (pn->mixed_) throw std::invalid_argument("StreamingSession: the network is in mixed-precision mode; the streaming step is fp32 only");
+  if (pn->mixed_ && !mixedPrecision)
+    throw std::invalid_argument("StreamingSession: the network is in mixed-precision mode; the streaming step is fp32 only (pass mixedPrecision = true)");
+  if (mixedPrecision && !pn->mixed_)
+    throw std::invalid_argument("StreamingSession: mixedPrecision needs the network's mixed-precision mode on (setMixedPrecision): the session equals the network's own forward");
+  if (mixedPrecision && pn->impl().mixedPrecisionConvs())
+    throw std::invalid_argument("StreamingSession: the second mixed-precision level (setMixedPrecisionConvolutions) is not planned for sessions");
   nFeat_ = (int)pn->archNFeat_;
   nLabel_ = pn->archNLabel_ > 0 ? (int)pn->archNLabel_ : pn->impl().outAct().F;
-  const int st = w2l_stream_create(pn->archText_.c_str(), nFeat_, nLabel_, slots, maxChunk, &h_);
+  const int st = w2l_stream_create_ex(pn->archText_.c_str(), nFeat_, nLabel_, slots, maxChunk, mixedPrecision ? W2L_STREAM_BF16 : W2L_STREAM_FP32, &h_);
   if (st != W2L_OK) throw std::invalid_argument(std::string("StreamingSession: ") + w2l_host_last_error());
   maxOut_ = w2l_stream_max_out(h_);
   const size_t bytes = w2l_stream_state_bytes(h_);
@@ -1045,6 +1051,9 @@ af::array StreamingSession::step(const af::array& features, const std::vector<in
   if (st != W2L_OK) throw std::runtime_error(std::string("StreamingSession::step: ") + w2l_host_last_error());
   if (!out) return af::array();   // no slot had work
   return af::array::wrap((void*)out, af::dim4(nLabel_, maxOut_, slots_), af::f32, state_);
+}
+void StreamingSession::refreshWeights() {
+  if (w2l_stream_refresh_weights(h_) != W2L_OK) throw std::runtime_error(std::string("StreamingSession::refreshWeights: ") + w2l_host_last_error());
 }
 void StreamingSession::reset(int slot) {
   if (w2l_stream_reset(h_, slot) != W2L_OK) throw std::invalid_argument(std::string("StreamingSession::reset: ") + w2l_host_last_error());

@@ -316,9 +316,27 @@ struct BfLinear {   // the weight images of one fl::Linear(in, out) and its thre
   BfImage w;        // w [in][out]: rows image = B of backward-data, transposed image [out][inP] = B of forward
   void plan(Planner& pl, int M_, int in_, int out_) { M = M_; in = in_; out = out_; w.plan(pl, in, out); }
   void convertWeight(Ctx& c, float* arena, const float* wf) const { w.convert(c, arena, wf, "bf16 weight images"); }
+  // a mixed-precision streaming session (Ctx::smallM): the forward product on the few-rows kernel.  false: M is above kSmallMRows
+  // (or the probe library's switch is set) -- the caller goes on to w2l_gemm_bf16, which gives the same bits.  The kernel accepts
+  // 1024 rows, but every slab's workgroup reads all of them: measured in a session at M = 576 (64 slots) it takes 89 us a product
+  // against 38 for w2l_gemm_bf16 and at M = 144 (16 slots) 45 against 36; at M = 72 it wins, 28 against 35, and at M = 9 by 11.5
+  // against 29 -- so a session hands over above 96 rows
+  static constexpr int kSmallMRows = 96;
+  bool smallM(Ctx& c, float* arena, const BfImage& xImg, const float* bias, const float* add, float* y, int relu, const BfImage* yImg,
+              const char* what) const {
+    if (!c.smallM || M > kSmallMRows) return false;
+    w2l_bf16_image_sink k{};
+    if (yImg) { k = yImg->sink(c, arena); k.transposed = nullptr; k.ldTrans = 0; }   // a session has no backward pass: the row image only
+    const int st = w2l_gemm_bf16_smallm(M, out, in, xImg.r(arena), xImg.colsP, w.t(arena), w.rowsP, y, out, bias, relu, add,
+                                        yImg ? &k : nullptr, nullptr, 0, c.stream);
+    if (st == W2L_EUNSUPPORTED) return false;
+    w2lCheck(st, what);
+    return true;
+  }
   // y [M][out] = x w + b (ReLU) (dropout); xImg: images of x [M][in]
   void forward(Ctx& c, float* arena, const BfImage& xImg, const float* bias, float* y, int relu, double dropP, uint32_t seed,
                uint32_t stream) const {
+    if (dropP <= 0 && smallM(c, arena, xImg, bias, nullptr, y, relu, nullptr, "bf16 linear fwd (few rows)")) return;
     w2l_gemm_epilogue e{};
     e.dropP = dropP; e.dropSeed = seed; e.dropStream = stream;
     w2lCheck(w2l_gemm_bf16(M, out, in, xImg.r(arena), xImg.colsP, w.t(arena), w.rowsP, y, out, bias, relu, dropP > 0 ? &e : nullptr,
@@ -327,6 +345,7 @@ struct BfLinear {   // the weight images of one fl::Linear(in, out) and its thre
   // y [M][out] = dropout(x w + b) + add: the residual join behind the product in its epilogue (w2l_linear_forward_dropout_add)
   void forwardAdd(Ctx& c, float* arena, const BfImage& xImg, const float* bias, const float* add, float* y, double dropP, uint32_t seed,
                   uint32_t stream) const {
+    if (dropP <= 0 && smallM(c, arena, xImg, bias, add, y, 0, nullptr, "bf16 linear fwd + add (few rows)")) return;
     w2l_gemm_epilogue e{};
     e.dropP = dropP; e.dropSeed = seed; e.dropStream = stream; e.addend = add;
     w2lCheck(w2l_gemm_bf16(M, out, in, xImg.r(arena), xImg.colsP, w.t(arena), w.rowsP, y, out, bias, 0, &e, c.stream), "bf16 linear fwd + add");
@@ -336,6 +355,7 @@ struct BfLinear {   // the weight images of one fl::Linear(in, out) and its thre
   // fp32 result + conversion)
   bool forwardImages(Ctx& c, float* arena, const BfImage& xImg, const float* bias, const BfImage& yImg, int relu, double dropP, uint32_t seed,
                      uint32_t stream) const {
+    if (dropP <= 0 && smallM(c, arena, xImg, bias, nullptr, nullptr, relu, &yImg, "bf16 linear fwd -> image (few rows)")) return true;
     w2l_gemm_epilogue e{};
     e.dropP = dropP; e.dropSeed = seed; e.dropStream = stream;
     const w2l_bf16_image_sink k = yImg.sink(c, arena);
@@ -592,7 +612,7 @@ class Conv2DLayer : public Layer {
     xSaved = x;
     const float* wt = weight(c, arena);
     if (c.bf16 && convImgElems) {   // bf16 operands, fp32 accumulation / bias / ReLU (conv_tds_bf16.hip); images once per step
-      w2lCheck(w2l_tds_conv_bf16_prepare(&d, wt, bfp(arena, convImgFOff), bfp(arena, convImgBOff), c.stream), "conv images");
+      if (!c.weightsReady) w2lCheck(w2l_tds_conv_bf16_prepare(&d, wt, bfp(arena, convImgFOff), bfp(arena, convImgBOff), c.stream), "conv images");
       w2lCheck(w2l_tds_conv_bf16_forward(&d, x, bfp(arena, convImgFOff), hasBias ? b.w(c) : nullptr, y, fuseRelu ? 1 : 0, c.stream), "conv fwd bf16");
       return;
     }
@@ -733,7 +753,8 @@ class LinearLayer : public Layer {
     xSaved = x;
     const float* wt = w.table ? w.w(c) : nullptr;
     if (wn.on) {
-      w2lCheck(w2l_weightnorm_forward(wn.v.w(c), wn.g.w(c), arena + wn.wOff, arena + wn.normOff, wn.K, wn.N, c.stream), "wn fwd");
+      if (!(c.bf16 && c.weightsReady))
+        w2lCheck(w2l_weightnorm_forward(wn.v.w(c), wn.g.w(c), arena + wn.wOff, arena + wn.normOff, wn.K, wn.N, c.stream), "wn fwd");
       wt = arena + wn.wOff;
     }
     if (c.bf16) {
@@ -744,7 +765,7 @@ class LinearLayer : public Layer {
       } else {
         xImg.convert(c, arena, x, "linear input images");
       }
-      bl.convertWeight(c, arena, wt);
+      if (!c.weightsReady) bl.convertWeight(c, arena, wt);
       bl.forward(c, arena, xSeen, hasBias ? b.w(c) : nullptr, y, fuseRelu ? 1 : 0, 0.0, 0, 0);
       return;
     }
@@ -948,7 +969,7 @@ class TDSLayer : public Layer {
     }
     float *a = ar + aOff, *r1 = ar + r1Off, *y1 = ar + y1Off, *v = ar + vOff, *out = ar + outOff;
     if (cx.bf16 && convImgElems) {   // bf16 operands, fp32 accumulation / bias / ReLU (conv_tds_bf16.hip); images once per step
-      w2lCheck(w2l_tds_conv_bf16_prepare(&d, wc.w(cx), bfp(ar, convImgFOff), bfp(ar, convImgBOff), s), "tds conv images");
+      if (!cx.weightsReady) w2lCheck(w2l_tds_conv_bf16_prepare(&d, wc.w(cx), bfp(ar, convImgFOff), bfp(ar, convImgBOff), s), "tds conv images");
       w2lCheck(w2l_tds_conv_bf16_forward(&d, x, bfp(ar, convImgFOff), bc.w(cx), a, 1, s), "tds conv bf16");
     } else {
       w2lCheck(w2l_conv_forward(&d, x, wc.w(cx), bc.w(cx), a, 1, s), "tds conv");
@@ -960,8 +981,10 @@ class TDSLayer : public Layer {
       // the two products on bf16 images: y1 as images (row image for lin1's product, transposed image for the weight gradient in
       // backward), the weights once per step (both orientations).  y1's images come out of the LayerNorm kernel when it normalises
       // per frame; otherwise y1 joins the weights' conversion launch (10 us each on their own: launch-bound)
+      // (a streaming session whose weight images stand, Ctx::weightsReady: y1 alone, or nothing)
       const w2l_bf16_convert_desc wd[3] = {y1Img.desc(ar, y1), ff.bl1.w.desc(ar, w1.w(cx)), ff.bl2.w.desc(ar, w2.w(cx))};
-      w2lCheck(w2l_bf16_convert_multi(y1Images ? 2 : 3, wd + (y1Images ? 1 : 0), s), "tds y1 + weight images");
+      const int first = y1Images ? 1 : 0, count = (cx.weightsReady ? 1 : 3) - first;
+      if (count > 0) w2lCheck(w2l_bf16_convert_multi(count, wd + first, s), "tds y1 + weight images");
       if (!y1Images) y1Img.ensureOnes(cx, ar);
     }
     // v = r2 = dropout(lin2(u)) + y1 where lin2 joined; else v = lin2(u), and the LayerNorm kernel stores r2 over v.  out = LN(r2)

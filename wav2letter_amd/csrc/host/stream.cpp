@@ -12,6 +12,13 @@
 // from the counts fed so far (a step never asks the device), sent with one async copy from pinned memory, and applied by one
 // hand-over kernel per time-extent layer (stream.hip).  A TDS block's residual hold-back needs no state of its own: the carry of
 // its convolution (kw - 1 frames) contains every input frame whose output does not exist yet.
+//
+// Precision is a property of the session (w2l_stream_*_ex).  A BF16 session runs the layers' mixed-precision forward (Ctx::bf16) with
+// two differences a session can afford because its model does not change between steps: the bf16 weight images are written once, on
+// the first step after a bind or a refresh, from a copy of the parameter arena that the session keeps in its own state (so nothing
+// a step reads can change under it: the snapshot covers biases and LayerNorm scalars too), and the fl::Linear products run on
+// w2l_gemm_bf16_smallm (Ctx::smallM), whose rows are bitwise independent of each other -- a slot's emissions do not depend on its
+// neighbours -- and which adds in the order of w2l_gemm_bf16: on the recipe's shapes the session equals the trainer's forward bit for bit.  The reference's streaming library serves half-precision weights the same way (fbgemm packs them once).
 #include <algorithm>
 #include <cstring>
 
@@ -21,11 +28,19 @@ namespace w2l {
 void setHostError(const std::string& m);
 void trainerArch(void* h, std::string& archText, int& nFeat, int& nLabel);
 const float* trainerParams(void* h, bool& mixedPrecision);
+bool trainerMixedConvs(void* h);
 
 namespace {
 
 struct Unsupported : std::runtime_error {
   using std::runtime_error::runtime_error;
+};
+
+struct MatmulMode {   // scoped, as the trainer's forward sets it around the network's own calls
+  int prev = 0;
+  bool on;
+  explicit MatmulMode(bool bf16) : on(bf16) { if (on) prev = w2l_set_matmul_precision(1); }
+  ~MatmulMode() { if (on) w2l_set_matmul_precision(prev); }
 };
 
 struct TimeLayer {
@@ -58,6 +73,12 @@ struct Session {
   hipEvent_t ev[kRing] = {nullptr, nullptr, nullptr, nullptr};
   bool evUsed[kRing] = {false, false, false, false};
   int ring = 0, parity = 0;
+  // W2L_STREAM_BF16: the state carries, behind the arena, a copy of the parameters
+  bool bf16 = false;
+  bool weightsStale = true;   // the next step copies the parameters and writes the weight images
+  bool freshState = true;     // the next step zero-fills the arena first: the images' zero padding, whatever the buffer held
+  size_t snapOff = 0;   // bytes into the state
+  float* snapshot() const { return (float*)(state + snapOff); }
   ~Session() {
     for (int r = 0; r < kRing; ++r) {
       if (ev[r]) (void)hipEventDestroy(ev[r]);
@@ -68,7 +89,9 @@ struct Session {
   float* arena() const { return (float*)(state + tabBytes); }
 };
 
-Session* buildSession(const std::string& archText, int nFeat, int nLabel, int slots, int maxChunk) {
+Session* buildSession(const std::string& archText, int nFeat, int nLabel, int slots, int maxChunk, int precision = W2L_STREAM_FP32) {
+  if (precision != W2L_STREAM_FP32 && precision != W2L_STREAM_BF16)
+    throw std::invalid_argument("streaming session: precision must be W2L_STREAM_FP32 or W2L_STREAM_BF16");
   if (slots <= 0 || slots > 65535 || maxChunk <= 0 || nFeat <= 0 || nLabel <= 0)
     throw std::invalid_argument("streaming session: slots (1..65535), max_chunk, NFEAT and NLABEL must be positive");
   std::unique_ptr<Session> s(new Session());
@@ -112,6 +135,11 @@ Session* buildSession(const std::string& archText, int nFeat, int nLabel, int sl
   s->arenaFloats = pl.used();
   s->tabBytes = (s->tl.size() * (size_t)slots * 4 * sizeof(int) + 255) / 256 * 256;
   s->stateBytes = s->tabBytes + s->arenaFloats * sizeof(float);
+  if (precision == W2L_STREAM_BF16) {   // an FP32 session's state is what it always was
+    s->bf16 = true;
+    s->snapOff = (s->stateBytes + 255) / 256 * 256;
+    s->stateBytes = s->snapOff + (s->net->paramFloats() * sizeof(float) + 255) / 256 * 256;
+  }
   s->active.assign(slots, 0);
   s->carry.assign((size_t)slots * s->tl.size(), 0);
   return s.release();
@@ -174,6 +202,8 @@ void bindSession(Session& s, const float* params, void* state, size_t bytes) {
   if (!params && !s.trainer) throw std::invalid_argument("stream bind: null parameters");
   s.params = params;
   s.state = (char*)state;
+  s.weightsStale = true;
+  s.freshState = true;
   const size_t tb = std::max<size_t>(s.tabBytes, 256);
   for (int r = 0; r < kRing; ++r) {
     if (!s.pinned[r]) hipCheck(hipHostMalloc((void**)&s.pinned[r], tb, hipHostMallocDefault), "stream count table (pinned)");
@@ -188,7 +218,10 @@ void stepSession(Session& s, const float* x, const int* n, const int* start, con
   if (s.trainer) {
     bool mixed = false;
     const float* tp = trainerParams(s.trainer, mixed);
-    if (mixed) throw Unsupported("stream step: the trainer is in mixed-precision mode; the streaming step is fp32 only");
+    if (mixed && !s.bf16) throw Unsupported("stream step: the trainer is in mixed-precision mode; this session is fp32 (W2L_STREAM_BF16 at creation)");
+    if (!mixed && s.bf16) throw std::invalid_argument("stream step: a W2L_STREAM_BF16 session needs the trainer's mixed-precision mode on");
+    if (s.bf16 && trainerMixedConvs(s.trainer))
+      throw Unsupported("stream step: the trainer's second mixed-precision level (set_mixed_precision_convs) is not planned for sessions");
     if (!params) params = tp;
     if (!params) throw std::invalid_argument("stream step: the trainer has no parameters bound");
   }
@@ -206,6 +239,16 @@ void stepSession(Session& s, const float* x, const int* n, const int* start, con
     c.stream = stream;
     c.train = false;
     c.params = const_cast<float*>(params);
+    MatmulMode mm(s.bf16);
+    if (s.bf16) {
+      if (s.freshState) hipCheck(hipMemsetAsync(ar, 0, s.arenaFloats * sizeof(float), stream), "stream state");
+      if (s.weightsStale)
+        hipCheck(hipMemcpyAsync(s.snapshot(), params, s.net->paramFloats() * sizeof(float), hipMemcpyDeviceToDevice, stream), "stream parameter snapshot");
+      c.params = s.snapshot();
+      c.bf16 = true;
+      c.smallM = true;
+      c.weightsReady = !s.weightsStale;
+    }
     w2lCheck(w2l_transpose(x, ar + s.inOff, s.S, s.nFeat, s.Cmax, stream), "stream input transpose");
     if (!s.tl.empty()) {
       hipCheck(hipMemcpyAsync(s.devTab(), s.pinned[r], s.tl.size() * (size_t)s.S * 4 * sizeof(int), hipMemcpyHostToDevice, stream),
@@ -233,6 +276,8 @@ void stepSession(Session& s, const float* x, const int* n, const int* start, con
       cur = y;
     }
     s.parity ^= 1;
+    s.weightsStale = false;
+    s.freshState = false;
     if (out) *out = cur;
   }
   s.active.swap(na);
@@ -259,30 +304,63 @@ W2L_API int w2l_stream_create(const char* archText, int nFeat, int nLabel, int s
   });
 }
 
-W2L_API int w2l_stream_create_for_trainer(void* trainer, int slots, int maxChunk, void** session) {
+W2L_API int w2l_stream_create_ex(const char* archText, int nFeat, int nLabel, int slots, int maxChunk, int precision, void** session) {
+  STREAM_TRY({
+    if (!archText || !session) throw std::invalid_argument("stream create: null argument");
+    *session = nullptr;
+    *session = buildSession(archText, nFeat, nLabel, slots, maxChunk, precision);
+  });
+}
+
+W2L_API int w2l_stream_create_for_trainer_ex(void* trainer, int slots, int maxChunk, int precision, void** session) {
   STREAM_TRY({
     if (!trainer || !session) throw std::invalid_argument("stream create: null argument");
     *session = nullptr;
+    if (precision != W2L_STREAM_FP32 && precision != W2L_STREAM_BF16)
+      throw std::invalid_argument("streaming session: precision must be W2L_STREAM_FP32 or W2L_STREAM_BF16");
     bool mixed = false;
     (void)trainerParams(trainer, mixed);
-    if (mixed) throw Unsupported("streaming session: the trainer is in mixed-precision mode; the streaming step is fp32 only");
+    if (precision == W2L_STREAM_FP32) {
+      if (mixed) throw Unsupported("streaming session: the trainer is in mixed-precision mode; the streaming step is fp32 only");
+    } else {
+      if (!mixed) throw std::invalid_argument("streaming session: W2L_STREAM_BF16 needs the trainer's mixed-precision mode on (the session equals the trainer's own forward)");
+      if (trainerMixedConvs(trainer))
+        throw Unsupported("streaming session: the trainer's second mixed-precision level (set_mixed_precision_convs) is not planned for sessions");
+    }
     std::string arch;
     int nFeat = 0, nLabel = 0;
     trainerArch(trainer, arch, nFeat, nLabel);
-    Session* s = buildSession(arch, nFeat, nLabel, slots, maxChunk);
+    Session* s = buildSession(arch, nFeat, nLabel, slots, maxChunk, precision);
     s->trainer = trainer;
     *session = s;
   });
 }
 
+W2L_API int w2l_stream_create_for_trainer(void* trainer, int slots, int maxChunk, void** session) {
+  return w2l_stream_create_for_trainer_ex(trainer, slots, maxChunk, W2L_STREAM_FP32, session);
+}
+
 W2L_API void w2l_stream_destroy(void* session) { delete (Session*)session; }
 
-W2L_API int w2l_stream_query(const char* archText, int nFeat, int nLabel, int slots, int maxChunk, int* maxOut, size_t* stateBytes) {
+W2L_API int w2l_stream_query_ex(const char* archText, int nFeat, int nLabel, int slots, int maxChunk, int precision, int* maxOut,
+                                size_t* stateBytes) {
   STREAM_TRY({
     if (!archText) throw std::invalid_argument("stream query: null arch");
-    std::unique_ptr<Session> s(buildSession(archText, nFeat, nLabel, slots, maxChunk));
+    std::unique_ptr<Session> s(buildSession(archText, nFeat, nLabel, slots, maxChunk, precision));
     if (maxOut) *maxOut = s->maxOut;
     if (stateBytes) *stateBytes = s->stateBytes;
+  });
+}
+
+W2L_API int w2l_stream_query(const char* archText, int nFeat, int nLabel, int slots, int maxChunk, int* maxOut, size_t* stateBytes) {
+  return w2l_stream_query_ex(archText, nFeat, nLabel, slots, maxChunk, W2L_STREAM_FP32, maxOut, stateBytes);
+}
+
+// pure host: the next step of a BF16 session copies the parameters and writes the weight images again
+W2L_API int w2l_stream_refresh_weights(void* session) {
+  STREAM_TRY({
+    if (!session) throw std::invalid_argument("stream refresh weights: null session");
+    ((Session*)session)->weightsStale = true;
   });
 }
 

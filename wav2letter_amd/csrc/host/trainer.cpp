@@ -89,6 +89,7 @@ const float* trainerParams(void* h, bool& mixedPrecision) {
   mixedPrecision = t->mixedPrecision;
   return t->params;
 }
+bool trainerMixedConvs(void* h) { return ((Trainer*)h)->net->mixedPrecisionConvs(); }
 }
 
 // criterion: "ctc" | "asg" ; archText: contents of an .arch file (NFEAT/NLABEL substituted here)

@@ -98,6 +98,11 @@ struct Ctx {
   // window that line up with the convolution's outputs, written by the window kernel (stream.hip).  Read only by a layer in
   // stream mode.
   const float* streamRes = nullptr;
+  // mixed-precision streaming session (host/stream.cpp; only a session sets these): the fl::Linear products go to
+  // w2l_gemm_bf16_smallm while their rows fit its cap, and the bf16 weight images are written only in a pass with
+  // weightsReady == false (the first step after a bind or a refresh) -- every later pass reads them as they are.
+  bool smallM = false;
+  bool weightsReady = false;
 };
 
 // What a layer needs from the chunked streaming forward (host/stream.cpp).  A frame-local layer maps frame t to frame t and

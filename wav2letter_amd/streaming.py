@@ -5,6 +5,12 @@ frames per slot and step.  For any utterance and any split of it into chunks the
 Trainer.forward(train=False) of that utterance alone (fp32 parity), and the frame count equals its Tout.  Feature extraction
 and normalisation stay with the caller.
 
+mixed_precision=True makes it a bf16 session over a mixed-precision trainer (Trainer.set_mixed_precision): bf16 operands for the
+fl::Linear products and the TDS convolutions, everything else fp32, equal to the trainer's own mixed-precision eval forward within
+the mixed-precision bar (2e-3).  Such a session holds a SNAPSHOT of the model: it copies the parameters and writes the bf16 weight
+images at its first step, and shows later changes of the parameters only after refresh_weights() -- unlike an fp32 session over a
+trainer, which reads the trainer's live arena at every step.
+
 A StreamingDecoder (csrc/criterion_beam_stream.hpp) is the CTC beam search continued chunk by chunk over such emissions: it
 takes StreamingSession.step's output directly, and its result after any number of frames is, bit for bit, ctc_beam_search of
 those frames alone.
@@ -28,10 +34,14 @@ def _check(st, what):
     raise _lib.W2LError(msg)
 
 
-def query(arch_text, nfeat, nlabel, slots, max_chunk):
+FP32, BF16 = 0, 1   # W2L_STREAM_FP32 / W2L_STREAM_BF16
+
+
+def query(arch_text, nfeat, nlabel, slots, max_chunk, mixed_precision=False):
     """(max_out, state_bytes) of a session over this arch: host arithmetic, no device"""
     mo, sb = C.c_int(0), C.c_size_t(0)
-    _check(_lib.lib().w2l_stream_query(arch_text.encode(), nfeat, nlabel, slots, max_chunk, C.byref(mo), C.byref(sb)), "stream query")
+    _check(_lib.lib().w2l_stream_query_ex(arch_text.encode(), nfeat, nlabel, slots, max_chunk, BF16 if mixed_precision else FP32,
+                                          C.byref(mo), C.byref(sb)), "stream query")
     return mo.value, sb.value
 
 
@@ -48,22 +58,27 @@ class StreamingSession:
     """StreamingSession(trainer, slots, max_chunk): the trainer's arch, its parameter arena (trainer.params: to_device() first;
     read at every step, so further training shows).  StreamingSession.from_arch(...) takes an arch text and a parameter tensor in
     the trainer's arena layout instead.  Creation is host arithmetic (a non-streamable arch line raises W2LUnsupported naming the
-    line); the device state is allocated at the first step."""
+    line); the device state is allocated at the first step.  mixed_precision=True: a bf16 session (the trainer's mixed-precision
+    mode must be on); it reads the parameters at its first step and again only after refresh_weights()."""
 
-    def __init__(self, trainer, slots, max_chunk, device=None):
+    def __init__(self, trainer, slots, max_chunk, device=None, mixed_precision=False):
         L = _lib.lib()
         h = C.c_void_p(0)
-        _check(L.w2l_stream_create_for_trainer(trainer.h, int(slots), int(max_chunk), C.byref(h)), "streaming session")
+        _check(L.w2l_stream_create_for_trainer_ex(trainer.h, int(slots), int(max_chunk), BF16 if mixed_precision else FP32, C.byref(h)),
+               "streaming session")
         self._init(L, h, trainer.nfeat, trainer.nlabel, slots, max_chunk, device or trainer.device)
+        self.mixed_precision = bool(mixed_precision)
         self._trainer = trainer   # kept alive: the C session reads it
 
     @classmethod
-    def from_arch(cls, arch_text, nfeat, nlabel, params, slots, max_chunk, device="cuda"):
+    def from_arch(cls, arch_text, nfeat, nlabel, params, slots, max_chunk, device="cuda", mixed_precision=False):
         L = _lib.lib()
         h = C.c_void_p(0)
-        _check(L.w2l_stream_create(arch_text.encode(), int(nfeat), int(nlabel), int(slots), int(max_chunk), C.byref(h)), "streaming session")
+        _check(L.w2l_stream_create_ex(arch_text.encode(), int(nfeat), int(nlabel), int(slots), int(max_chunk),
+                                      BF16 if mixed_precision else FP32, C.byref(h)), "streaming session")
         self = cls.__new__(cls)
         self._init(L, h, nfeat, nlabel, slots, max_chunk, device)
+        self.mixed_precision = bool(mixed_precision)
         self._trainer = None
         if params is not None:
             if not (torch.is_tensor(params) and params.dtype == torch.float32 and params.is_contiguous()
@@ -146,6 +161,10 @@ class StreamingSession:
     def reset(self, slot):
         """closes a slot and discards its state"""
         _check(self.L.w2l_stream_reset(self.h, int(slot)), "stream reset")
+
+    def refresh_weights(self):
+        """a bf16 session: the next step copies the parameters and writes the bf16 weight images again (host only; a no-op for fp32)"""
+        _check(self.L.w2l_stream_refresh_weights(self.h), "stream refresh weights")
 
 
 BEAM_PLAIN, BEAM_LM, BEAM_LEX = 0, 1, 2
