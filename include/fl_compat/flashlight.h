@@ -604,7 +604,8 @@ struct BeamSearchResult {
 // any number of frames is, bit for bit, CTCLoss::beamSearch over those frames alone, with the same options.  options: beamSize,
 // beamSizeToken, beamThreshold, logAdd, normalize (-1: as logAdd), lm, lmWeight, classScore, eosScore, lexicon, wordScore; nbest,
 // maxLen (0 = maxFrames) and maxWords (0 = maxLen) apply to result().  lm, lexicon and classScore must outlive the decoder.
-// options.wide, a beam or token count above 64: std::runtime_error; any other refused argument: std::invalid_argument.
+// options.wide, a beam or token count above 64: std::runtime_error (WideStreamingDecoder below takes those); any other refused
+// argument: std::invalid_argument.
 class FL_COMPAT_API StreamingDecoder {
  public:
   StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& options);
@@ -619,11 +620,26 @@ class FL_COMPAT_API StreamingDecoder {
   int frames(int slot) const;   // emission frames fed to a slot since its start
   void reset(int slot);         // closes a slot
 
+ protected:
+  struct WideKernels {};   // WideStreamingDecoder's constructor
+  StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& options, WideKernels);
+
  private:
+  void create(bool wideKernels);
   BeamSearchOptions o_;
   std::shared_ptr<void> state_;
   void* h_ = nullptr;
   int slots_ = 0, maxChunk_ = 0, maxFrames_ = 0, nLabel_ = 0;
+};
+
+// fl_compat extension: StreamingDecoder on the wide kernels (w2l_beam_session_create_wide): the result after any number of frames
+// is, bit for bit, CTCLoss::beamSearch with options.wide = true over those frames alone.  beamSize goes up to 1024, beamSizeToken
+// (after clipping to NLABEL - 1) up to 64; beyond: std::runtime_error.  options.wide is IGNORED: this class is always wide.  The
+// methods are StreamingDecoder's.  A slot's state grows with beamSize * maxFrames: 64 MiB at 1024 and 4096.
+class FL_COMPAT_API WideStreamingDecoder : public StreamingDecoder {
+ public:
+  WideStreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& options)
+      : StreamingDecoder(slots, maxChunk, maxFrames, numLabels, options, WideKernels{}) {}
 };
 
 class FL_COMPAT_API ASGLoss : public SequenceCriterion {

@@ -1050,6 +1050,34 @@ int w2l_beam_session_result(void* session, int nbest, int maxLen, int* labels, i
 int w2l_beam_session_frames(void* session, int slot, int* h_frames);
 int w2l_beam_session_reset(void* session, int slot);
 
+/* ---- the wide beam session: the incremental form of the wide CTC searches (csrc/criterion_beam_stream.hpp) ---------
+ * w2l_beam_session_create_wide makes a session with the protocol above -- bind / step / counts / result / frames / reset / destroy
+ * take either kind of session and dispatch on it -- whose beam goes up to 1024 (beamToken, after clipping to N - 1, up to 64 as in
+ * the wide searches).
+ * THE CONTRACT is the narrow session's with one name changed: for any slot, any split of its F frames into chunks (empty chunks
+ * count) and the other slots at any phase, the result is the whole-utterance search of the same variant ON THE WIDE KERNELS at
+ * B = 1, T = F, frames = NULL over the concatenated rows in a buffer that begins at a 16-byte boundary -- W2L_BEAM_PLAIN:
+ * w2l_ctc_beam_search_wide, W2L_BEAM_LM: w2l_ctc_beam_search_lm_wide, W2L_BEAM_LEX: w2l_ctc_beam_search_lex_wide -- and labels,
+ * lengths, scores, lmScores, words and wordCounts are equal BIT FOR BIT in both logAdd modes, the end rule included.  Partial
+ * results, "asking changes nothing", the empty prefix in row 0 of a started slot without frames, the empty rows of a slot that
+ * was never started or was reset, nbest up to the beam, and W2L_BEAM_PLAIN's lmScores (0 for live rows, -inf for empty ones) read
+ * as above.  At a beam up to 64 a wide and a narrow session return the same bytes.
+ *   w2l_beam_session_wide_state_bytes  the state buffer's size; 0 for a descriptor the wide session refuses.  Every part is
+ *                                 256-byte aligned: 3 S ints; lse, lpb [S][maxChunk] and tokLp, tokC [S][maxChunk][K] (K =
+ *                                 min(beamToken, N - 1)); S prefix tables of cap 8-byte edges (cap = the power of two >=
+ *                                 max(64, 2 maxFrames beam)); S candidate lists of beam K slots + beam 8-byte keys (slots = 7
+ *                                 for W2L_BEAM_LEX, else 1: one frame's scratch, not carried); S ints; 8 beam arrays [S][beam] of
+ *                                 4 bytes, 10 for W2L_BEAM_LEX.  At beam 1024 and maxFrames 4096 a slot's prefix table is 2^23
+ *                                 edges = 64 MiB, its candidate list with a lexicon (K = 64) 3.6 MiB.
+ * A step is the table copy, one clear per run of adjacent starting slots, the row pass and ONE scan launch (a workgroup of 1024
+ * threads per slot; its 64 or 72 KiB of dynamic LDS are asked for at bind); a result is the table copy and one launch.  Never
+ * synchronises, allocates nothing after bind.
+ * Refusals are the narrow session's with two limits changed: W2L_EUNSUPPORTED for beam above 1024, and for beamToken (after
+ * clipping to N - 1) above 64; maxFrames * beam > 2^29 stays W2L_EUNSUPPORTED.  w2l_beam_session_create keeps refusing beam > 64.
+ * A state buffer damaged between calls gives wrong hypotheses, never a spin or an access outside the buffer and the tables. */
+int w2l_beam_session_create_wide(const w2l_beam_session_desc* desc, void** session);
+size_t w2l_beam_session_wide_state_bytes(const w2l_beam_session_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 """The incremental CTC beam search (w2l_beam_session_*) against the whole-utterance search of the same variant, in one process,
-timed with hip events after warm-up at the TDS-CTC recipe's emission shape:   python tools/beam_stream_one.py [variant] [reps]
+timed with hip events after warm-up at the TDS-CTC recipe's emission shape:   python tools/beam_stream_one.py [variant] [reps] [--wide]
   N = 9998, T = 188 emission frames per utterance, the max search on the raw emissions, no threshold, nbest = 1
   variant: lm (default; the 3-gram token LM of tools/ctc_beam_lm_one.py, lmWeight 0.5), lex (the lexicon and word LM of
   tools/ctc_beam_lex_one.py) or plain
@@ -8,7 +8,10 @@ Per shape one JSON line: the median step latency (a step = every slot advanced b
 frame summed over the utterance (all steps between two events), beside it the whole-utterance search at B = S, T = 188 -- the
 yardstick -- per frame, their ratio, the constant a step adds ((session - whole) / steps), and what the session replaces: searching
 again from frame 0 after every chunk, the sum of the whole search over the prefixes (timed at 8 prefix lengths, summed by the
-trapezoid rule).  The session's final hypotheses are checked bit for bit against the whole search before anything is timed."""
+trapezoid rule).  The session's final hypotheses are checked bit for bit against the whole search before anything is timed.
+  --wide: the wide session (w2l_beam_session_create_wide) against the wide whole search (the w2l_*_wide entry points) at B = S in
+  the same run: W = 128, 500 and 1024 with K = 64, S = 1 / 16 / 64, chunks of 1 and 4; then, at W = K = 64 where both families
+  exist, the narrow session and the wide session side by side ("family"), each against its own whole search."""
 import json
 import os
 import statistics
@@ -22,7 +25,7 @@ import torch
 from ctc_beam_lm_one import HOT
 from ctc_beam_lm_one import model as token_model
 from wav2letter_amd import criterion
-from wav2letter_amd.streaming import StreamingDecoder
+from wav2letter_amd.streaming import StreamingDecoder, WideStreamingDecoder
 
 T, N = 188, 9998
 
@@ -51,13 +54,14 @@ def events(fn, n):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
-def bench(S, chunk, W, reps, opts):
+def bench(S, chunk, W, reps, opts, wide=False):
     g = torch.Generator(device="cpu").manual_seed(11)
     x = torch.randn(S, T, N, generator=g)
     x[:, :, :HOT] += 2.0
     x = x.cuda()
-    o = dict(beam=W, beam_token=W, threshold=float("inf"), log_add=False, normalize=False, **opts)
-    dec = StreamingDecoder(S, chunk, T, N, **o)
+    K = min(W, 64)
+    o = dict(beam=W, beam_token=K, threshold=float("inf"), log_add=False, normalize=False, **opts)
+    dec = (WideStreamingDecoder if wide else StreamingDecoder)(S, chunk, T, N, **o)
     steps = [(x[:, t:t + chunk].contiguous() if t + chunk <= T else
               torch.cat([x[:, t:], torch.zeros(S, chunk - (T - t), N, device="cuda")], 1), min(chunk, T - t)) for t in range(0, T, chunk)]
     one = np.ones(S, np.int32)
@@ -67,7 +71,7 @@ def bench(S, chunk, W, reps, opts):
             dec.step(em, one * c, one * (i == 0))
 
     def whole(F=T):
-        return criterion.ctc_beam_search(x[:, :F].contiguous() if F < T else x, nbest=1, max_len=T, **o)
+        return criterion.ctc_beam_search(x[:, :F].contiguous() if F < T else x, nbest=1, max_len=T, wide=wide, **o)
 
     utterance()
     got, want = dec.result(nbest=1, max_len=T), whole()
@@ -88,7 +92,7 @@ def bench(S, chunk, W, reps, opts):
     # the sum over the prefixes a chunked caller would search again, by the trapezoid rule over the timed lengths
     ends = list(range(chunk, T, chunk)) + [T]
     research = float(np.interp(ends, marks, tp).sum())
-    return {"S": S, "chunk": chunk, "W": W, "K": W, "steps": len(steps), "step_us_median": round(statistics.median(lat), 1),
+    return {"family": "wide" if wide else "narrow", "S": S, "chunk": chunk, "W": W, "K": K, "steps": len(steps), "step_us_median": round(statistics.median(lat), 1),
             "session_us_per_utterance": round(t_utt, 1), "session_us_per_frame": round(t_utt / T, 2), "result_us": round(res, 1),
             "whole_us": round(t_whole, 1), "whole_us_per_frame": round(t_whole / T, 2), "ratio": round(t_utt / t_whole, 2),
             "per_step_constant_us": round((t_utt - t_whole) / len(steps), 1), "research_from_zero_us": round(research, 1),
@@ -96,10 +100,22 @@ def bench(S, chunk, W, reps, opts):
 
 
 if __name__ == "__main__":
-    variant = sys.argv[1] if len(sys.argv) > 1 else "lm"
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 6
+    args = [a for a in sys.argv[1:] if a != "--wide"]
+    wide = "--wide" in sys.argv[1:]
+    variant = args[0] if len(args) > 0 else "lm"
+    reps = int(args[1]) if len(args) > 1 else 6
     opts = tables(variant)
-    print(json.dumps({"variant": variant, "T": T, "N": N, "reps": reps}), flush=True)
+    print(json.dumps({"variant": variant, "T": T, "N": N, "reps": reps, "wide": wide}), flush=True)
+    if wide:
+        for W in (128, 500, 1024):
+            for S in (1, 16, 64):
+                for chunk in (1, 4):
+                    print(json.dumps(bench(S, chunk, W, reps, opts, wide=True)), flush=True)
+        for S in (1, 16, 64):
+            for chunk in (1, 4):
+                for fam in (False, True):
+                    print(json.dumps(bench(S, chunk, 64, reps, opts, wide=fam)), flush=True)
+        sys.exit(0)
     for W in (64, 8):
         for S in (1, 16, 64):
             for chunk in (1, 2, 4):

@@ -253,6 +253,8 @@ class _SIGS:
     w2l_beam_session_result = (_i, [_p, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p])
     w2l_beam_session_frames = (_i, [_p, _i, _p])
     w2l_beam_session_reset = (_i, [_p, _i])
+    w2l_beam_session_create_wide = (_i, [_p, _p])
+    w2l_beam_session_wide_state_bytes = (_sz, [_p])
 
 
 class ConvDesc(C.Structure):

@@ -16,9 +16,17 @@
 //   lse, lpb  [S][maxChunk] fp32;  tokLp fp32, tokC int [S][maxChunk][K]         the row pass of this step
 //   table     [S][ctc_beam_cap(maxFrames, W)] u64                                 a slot's prefix trie, for its whole utterance
 //   n [S] int;  node, tot, state, acc, u, par, e, lab, pb, pnb, su [S][64]        the beams (11 arrays of 4-byte entries)
+// THE WIDE SESSION (w2l_beam_session_create_wide; beam up to kBeamWideMax) is the same protocol, bookkeeping and row
+// pass over the wide kernels of criterion_beam_wide.hpp: beam_stream_wide_scan is beam_wide_scan's body with kResume set, one
+// workgroup of 1024 threads per slot, and beam_stream_wide_finish is beam_wide_finish's body under the open flag and a BeamWalk.
+// Its state (w2l_beam_session_wide_state_bytes), every part 256-byte aligned:
+//   cnt, base, flag; lse, lpb, tokLp, tokC; table      as above, the table with cap = ctc_beam_cap(maxFrames, W)
+//   cand      [S][W K slots + W] u64, slots = 7 with a lexicon, else 1            the candidate keys of ONE frame: scratch, not carried
+//   n [S] int;  node, tot, state, acc, par, e, pb, pnb [S][W]; with a lexicon also u, lab [S][W]   the beams (8 or 10 arrays)
 #pragma once
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace w2l {
@@ -54,6 +62,67 @@ static size_t beam_session_layout(BeamSessionLayout* L, void* state, int S, int 
     L->cy = BeamCarry{ctl, ctl + 2 * S, (int*)arr[5], (int*)arr[6], (int*)arr[7], (float*)arr[8], (float*)arr[9], (float*)arr[10]};
   }
   return (size_t)(p - p0);
+}
+
+struct BeamWideSessionLayout {
+  int* ctl;
+  BeamWideWs ww;
+  BeamWideCarry cy;
+};
+
+static size_t beam_session_wide_layout(BeamWideSessionLayout* L, void* state, int S, int maxChunk, int maxFrames, int W, int K,
+                                       bool lex) {
+  const size_t rows = (size_t)S * maxChunk, cap = ctc_beam_cap(maxFrames, W), ent = align_up((size_t)S * W * 4, 256);
+  const size_t candCap = (size_t)W * K * (lex ? 7 : 1) + (size_t)W;
+  char* p = (char*)state;
+  char* const p0 = p;
+  auto take = [&](size_t bytes) { char* q = p; p += align_up(bytes, 256); return q; };
+  int* ctl = (int*)take((size_t)3 * S * sizeof(int));
+  float* lse = (float*)take(rows * sizeof(float));
+  float* lpb = (float*)take(rows * sizeof(float));
+  float* tokLp = (float*)take(rows * K * sizeof(float));
+  int* tokC = (int*)take(rows * K * sizeof(int));
+  u64* table = (u64*)take((size_t)S * cap * sizeof(u64));
+  u64* cand = (u64*)take((size_t)S * candCap * sizeof(u64));
+  int* n = (int*)take((size_t)S * sizeof(int));
+  char* arr[10] = {};
+  for (int i = 0; i < (lex ? 10 : 8); ++i) arr[i] = take(ent);
+  if (L) {
+    L->ctl = ctl;
+    L->ww.c = CtcBeamWs{lse, lpb, tokLp, tokC, table, (int*)arr[0], (float*)arr[1], n, (int*)arr[2], (float*)arr[3], (int*)arr[8], K,
+                        (unsigned)cap};
+    L->ww.cand = cand; L->ww.candCap = candCap; L->ww.W = W;
+    L->cy = BeamWideCarry{ctl, ctl + 2 * S, (int*)arr[4], (int*)arr[5], (int*)arr[9], (float*)arr[6], (float*)arr[7]};
+  }
+  return (size_t)(p - p0);
+}
+
+template <bool kLogAdd, bool kLex>
+__global__ __launch_bounds__(kWideThreads) void beam_stream_wide_scan(int T, int N, int W, float threshold,
+                                                                      const float* __restrict__ x, BeamWideWs ww,
+                                                                      const void* __restrict__ lex, const void* __restrict__ lm,
+                                                                      float lmWeight, const float* __restrict__ classScore,
+                                                                      float wordScore, BeamWideCarry cy) {
+  beam_wide_scan_body<kLogAdd, BeamCtc, kLex, true>(T, N, W, threshold, x, nullptr, ww, lex, lm, lmWeight, classScore, wordScore,
+                                                    BeamTrans{}, cy);
+}
+
+// as beam_stream_finish below: cy.cnt[slot] bounds the walks, cy.flag[slot] bit 1 says the slot is open
+template <bool kLex>
+__global__ __launch_bounds__(kWideThreads) void beam_stream_wide_finish(int M, int Lmax, int maxWords, int eosWord, BeamWideWs ww,
+                                                                        BeamWideCarry cy, const void* __restrict__ lex,
+                                                                        const void* __restrict__ lm, float lmWeight, float eosScore,
+                                                                        int useEos, int* __restrict__ labels,
+                                                                        int* __restrict__ lengths, float* __restrict__ scores,
+                                                                        float* __restrict__ lmScores, int* __restrict__ words,
+                                                                        int* __restrict__ wordCounts) {
+  const int b = blockIdx.x;
+  const int n = (cy.flag[b] & 2) ? min(max(ww.c.finN[b], 0), min(ww.W, kWideThreads)) : 0;
+  BeamWalk g;
+  g.capm = ww.c.cap - 1;
+  g.steps = max(cy.cnt[b], 0);
+  beam_wide_finish_body<kLex>(b, n, g, M, Lmax, maxWords, eosWord, ww, lex, lm, lmWeight, eosScore, useEos, labels, lengths, scores,
+                              lmScores, words, wordCounts);
 }
 
 template <bool kLogAdd, int kThreads>
@@ -99,6 +168,8 @@ struct BeamSession {
   std::vector<int> frames;    // per slot: emission frames fed since its start
   std::vector<char> active;   // per slot: started and not reset
   BeamSessionLayout L{};
+  bool wide = false;          // w2l_beam_session_create_wide: the wide kernels over WL
+  BeamWideSessionLayout WL{};
   bool bound = false;
   int* pinned[kBeamRing] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev[kBeamRing] = {nullptr, nullptr, nullptr, nullptr};
@@ -118,7 +189,7 @@ static int beam_session_fail(int rc, const std::string& m) {
 }
 
 // the descriptor against the whole searches' argument rules; *K = the clipped beamToken
-static int beam_session_check(const w2l_beam_session_desc* d, int* K) {
+static int beam_session_check(const w2l_beam_session_desc* d, int* K, bool wide = false) {
   if (!d) return beam_session_fail(W2L_EINVAL, "beam session: null descriptor");
   if (d->slots <= 0 || d->slots > 65535 || d->maxChunk <= 0 || d->maxFrames <= 0 || d->N < 2 || d->beam <= 0 || d->beamToken <= 0 ||
       !(d->threshold >= 0.f))
@@ -139,8 +210,11 @@ static int beam_session_check(const w2l_beam_session_desc* d, int* K) {
       return beam_session_fail(W2L_EINVAL, "beam session: the lexicon variant needs a lexicon table, a finite wordScore, no classScore");
   }
   *K = ctc_beam_clip(d->N - 1, d->beamToken);
-  if (d->beam > kBeamMax || *K > kBeamMax)
-    return beam_session_fail(W2L_EUNSUPPORTED, "beam session: beam and beamToken above 64 (the wide searches) are not incremental");
+  if (wide && (d->beam > kBeamWideMax || *K > kBeamMax))
+    return beam_session_fail(W2L_EUNSUPPORTED, "wide beam session: beam above 1024 or beamToken (clipped to N - 1) above 64");
+  if (!wide && (d->beam > kBeamMax || *K > kBeamMax))
+    return beam_session_fail(W2L_EUNSUPPORTED, "beam session: beam and beamToken above 64 (the wide searches) are not incremental "
+                                               "here; w2l_beam_session_create_wide takes a beam up to 1024");
   if ((size_t)d->maxFrames * d->beam > ((size_t)1 << 29))
     return beam_session_fail(W2L_EUNSUPPORTED, "beam session: maxFrames * beam above 2^29 (node ids are ints)");
   return W2L_OK;
@@ -175,6 +249,14 @@ static int beam_session_advance(const BeamSession& s, const int* n, const int* s
   return W2L_OK;
 }
 
+// f(std::bool_constant<logAdd>, std::bool_constant<lexicon>) for the session's instantiation of the wide scan
+template <class F>
+static int beam_session_wide_kernel(const BeamSession& s, F&& f) {
+  const bool lex = s.d.variant == W2L_BEAM_LEX;
+  if (lex) return s.d.logAdd ? f(std::true_type{}, std::true_type{}) : f(std::false_type{}, std::true_type{});
+  return s.d.logAdd ? f(std::true_type{}, std::false_type{}) : f(std::false_type{}, std::false_type{});
+}
+
 // the next pinned table of the ring, free to write
 static int beam_session_table(BeamSession& s, int** table) {
   const int r = s.ring;
@@ -184,7 +266,7 @@ static int beam_session_table(BeamSession& s, int** table) {
 }
 static int beam_session_send(BeamSession& s, hipStream_t st) {
   const int r = s.ring;
-  W2L_HIP_CHECK(hipMemcpyAsync(s.L.ctl, s.pinned[r], (size_t)3 * s.d.slots * sizeof(int), hipMemcpyHostToDevice, st));
+  W2L_HIP_CHECK(hipMemcpyAsync(s.wide ? s.WL.ctl : s.L.ctl, s.pinned[r], (size_t)3 * s.d.slots * sizeof(int), hipMemcpyHostToDevice, st));
   W2L_HIP_CHECK(hipEventRecord(s.ev[r], st));
   s.evUsed[r] = true;
   s.ring = (r + 1) % kBeamRing;
@@ -200,21 +282,40 @@ W2L_API size_t w2l_beam_session_state_bytes(const w2l_beam_session_desc* desc) {
   return beam_session_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K);
 }
 
-W2L_API int w2l_beam_session_create(const w2l_beam_session_desc* desc, void** session) {
+W2L_API size_t w2l_beam_session_wide_state_bytes(const w2l_beam_session_desc* desc) {
   using namespace w2l;
+  int K = 0;
+  if (beam_session_check(desc, &K, true)) return 0;
+  return beam_session_wide_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K,
+                                  desc->variant == W2L_BEAM_LEX);
+}
+
+namespace w2l {
+static int beam_session_make(const w2l_beam_session_desc* desc, void** session, bool wide) {
   if (!session) return beam_session_fail(W2L_EINVAL, "beam session: null session pointer");
   *session = nullptr;
   int K = 0;
-  if (const int rc = beam_session_check(desc, &K)) return rc;
+  if (const int rc = beam_session_check(desc, &K, wide)) return rc;
   BeamSession* s = new BeamSession();
   s->d = *desc;
   s->K = K;
+  s->wide = wide;
   s->cap = ctc_beam_cap(desc->maxFrames, desc->beam);
-  s->stateBytes = beam_session_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K);
+  s->stateBytes = wide ? beam_session_wide_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K,
+                                                  desc->variant == W2L_BEAM_LEX)
+                       : beam_session_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K);
   s->frames.assign(desc->slots, 0);
   s->active.assign(desc->slots, 0);
   *session = s;
   return W2L_OK;
+}
+}  // namespace w2l
+
+W2L_API int w2l_beam_session_create(const w2l_beam_session_desc* desc, void** session) {
+  return w2l::beam_session_make(desc, session, false);
+}
+W2L_API int w2l_beam_session_create_wide(const w2l_beam_session_desc* desc, void** session) {
+  return w2l::beam_session_make(desc, session, true);
 }
 
 W2L_API void w2l_beam_session_destroy(void* session) { delete (w2l::BeamSession*)session; }
@@ -226,13 +327,24 @@ W2L_API int w2l_beam_session_bind(void* session, void* state, size_t bytes) {
   if (!state || ((uintptr_t)state & 255))
     return beam_session_fail(W2L_EINVAL, "beam session bind: the state buffer must be a 256-byte aligned device pointer");
   if (bytes < s.stateBytes)
-    return beam_session_fail(W2L_EINVAL, "beam session bind: the state buffer is smaller than w2l_beam_session_state_bytes");
+    return beam_session_fail(W2L_EINVAL, s.wide ? "beam session bind: the state buffer is smaller than w2l_beam_session_wide_state_bytes"
+                                                : "beam session bind: the state buffer is smaller than w2l_beam_session_state_bytes");
   const size_t tb = align_up((size_t)3 * s.d.slots * sizeof(int), 256);
   for (int r = 0; r < kBeamRing; ++r) {
     if (!s.pinned[r]) W2L_HIP_CHECK(hipHostMalloc((void**)&s.pinned[r], tb, hipHostMallocDefault));
     if (!s.ev[r]) W2L_HIP_CHECK(hipEventCreateWithFlags(&s.ev[r], hipEventDisableTiming));
   }
-  beam_session_layout(&s.L, state, s.d.slots, s.d.maxChunk, s.d.maxFrames, s.d.beam, s.K);
+  if (s.wide) {   // the scan's 64 or 72 KiB of dynamic LDS are asked for here, so a step is launches alone
+    const int rc = beam_session_wide_kernel(s, [&](auto la, auto lx) -> int {
+      constexpr bool kLa = decltype(la)::value, kLx = decltype(lx)::value;
+      W2L_HIP_CHECK(hipFuncSetAttribute((const void*)beam_stream_wide_scan<kLa, kLx>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)WideLds<kLx>::bytes));
+      return W2L_OK;
+    });
+    if (rc) return rc;
+  }
+  if (s.wide) beam_session_wide_layout(&s.WL, state, s.d.slots, s.d.maxChunk, s.d.maxFrames, s.d.beam, s.K, s.d.variant == W2L_BEAM_LEX);
+  else beam_session_layout(&s.L, state, s.d.slots, s.d.maxChunk, s.d.maxFrames, s.d.beam, s.K);
   s.bound = true;
   // another buffer holds no slot's search
   std::fill(s.frames.begin(), s.frames.end(), 0);
@@ -277,30 +389,42 @@ W2L_API int w2l_beam_session_step(void* session, const float* emissions, const i
       if (!(h_start && h_start[i])) { ++i; continue; }
       int j = i + 1;
       while (j < S && h_start[j]) ++j;
-      W2L_HIP_CHECK(hipMemsetAsync(s.L.ws.table + (size_t)i * s.cap, 0, (size_t)(j - i) * s.cap * sizeof(u64), st));
+      W2L_HIP_CHECK(hipMemsetAsync((s.wide ? s.WL.ww.c.table : s.L.ws.table) + (size_t)i * s.cap, 0,
+                                   (size_t)(j - i) * s.cap * sizeof(u64), st));
       i = j;
     }
-    const CtcBeamWs& ws = s.L.ws;
+    const CtcBeamWs& ws = s.wide ? s.WL.ww.c : s.L.ws;
+    const int* cnt = s.wide ? s.WL.cy.cnt : s.L.cy.cnt;
     if (frames) {
       const unsigned rows = (unsigned)((size_t)S * C);
       if (N > kRowThreads * kRowMaxPer)
         hipLaunchKernelGGL((ctc_beam_rows<true, false, true>), dim3(rows), dim3(kRowThreads), 0, st, C, N, s.d.normalize, emissions,
-                           s.L.cy.cnt, ws);
+                           cnt, ws);
       else
         hipLaunchKernelGGL((ctc_beam_rows<false, false, true>), dim3(rows), dim3(kRowThreads), 0, st, C, N, s.d.normalize, emissions,
-                           s.L.cy.cnt, ws);
+                           cnt, ws);
       W2L_LAUNCH_CHECK();
     }
-    ctc_beam_fused_scan(W, K, s.d.logAdd, [&](auto la, auto th) {
-      if (s.d.variant == W2L_BEAM_LEX)
-        hipLaunchKernelGGL((beam_stream_lex_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)S),
-                           dim3(decltype(th)::value), 0, st, C, N, W, s.d.threshold, emissions, ws, s.d.lexicon, s.d.lm, s.d.lmWeight,
-                           s.d.wordScore, s.L.cy);
-      else
-        hipLaunchKernelGGL((beam_stream_lm_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)S),
-                           dim3(decltype(th)::value), 0, st, C, N, W, s.d.threshold, emissions, ws, s.d.lm, s.d.lmWeight,
-                           s.d.classScore, s.L.cy);
-    });
+    if (s.wide) {
+      beam_session_wide_kernel(s, [&](auto la, auto lx) -> int {
+        constexpr bool kLa = decltype(la)::value, kLx = decltype(lx)::value;
+        hipLaunchKernelGGL((beam_stream_wide_scan<kLa, kLx>), dim3((unsigned)S), dim3(kWideThreads), WideLds<kLx>::bytes, st, C, N, W,
+                           s.d.threshold, emissions, s.WL.ww, s.d.lexicon, s.d.lm, s.d.lmWeight, s.d.classScore, s.d.wordScore,
+                           s.WL.cy);
+        return W2L_OK;
+      });
+    } else {
+      ctc_beam_fused_scan(W, K, s.d.logAdd, [&](auto la, auto th) {
+        if (s.d.variant == W2L_BEAM_LEX)
+          hipLaunchKernelGGL((beam_stream_lex_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)S),
+                             dim3(decltype(th)::value), 0, st, C, N, W, s.d.threshold, emissions, ws, s.d.lexicon, s.d.lm, s.d.lmWeight,
+                             s.d.wordScore, s.L.cy);
+        else
+          hipLaunchKernelGGL((beam_stream_lm_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)S),
+                             dim3(decltype(th)::value), 0, st, C, N, W, s.d.threshold, emissions, ws, s.d.lm, s.d.lmWeight,
+                             s.d.classScore, s.L.cy);
+      });
+    }
     W2L_LAUNCH_CHECK();
   }
   s.frames.swap(fa);
@@ -327,7 +451,14 @@ W2L_API int w2l_beam_session_result(void* session, int nbest, int maxLen, int* l
   for (int i = 0; i < S; ++i) { table[i] = s.frames[i]; table[S + i] = 0; table[2 * S + i] = s.active[i] ? 2 : 0; }
   if (const int rc = beam_session_send(s, st)) return rc;
   const int useEos = s.d.lmHasEos ? 1 : 0;
-  if (lex)
+  if (s.wide && lex)
+    hipLaunchKernelGGL(beam_stream_wide_finish<true>, dim3((unsigned)S), dim3(kWideThreads), 0, st, nbest, maxLen, maxWords, 0, s.WL.ww,
+                       s.WL.cy, s.d.lexicon, s.d.lm, s.d.lmWeight, s.d.eosScore, useEos, labels, lengths, scores, lmScores, words,
+                       wordCounts);
+  else if (s.wide)
+    hipLaunchKernelGGL(beam_stream_wide_finish<false>, dim3((unsigned)S), dim3(kWideThreads), 0, st, nbest, maxLen, 0, s.d.N, s.WL.ww,
+                       s.WL.cy, nullptr, s.d.lm, s.d.lmWeight, s.d.eosScore, useEos, labels, lengths, scores, lmScores, nullptr, nullptr);
+  else if (lex)
     hipLaunchKernelGGL(beam_stream_finish<true>, dim3((unsigned)S), dim3(64), 0, st, nbest, maxLen, maxWords, s.d.N, s.L.ws, s.L.cy,
                        s.d.lexicon, s.d.lm, s.d.lmWeight, s.d.eosScore, useEos, labels, lengths, scores, lmScores, words, wordCounts);
   else

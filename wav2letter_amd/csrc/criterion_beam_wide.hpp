@@ -28,6 +28,9 @@
 //   beam_wide_finish<lex>  one workgroup of 1024 threads per utterance, thread r = final entry r: the lexicon's root-only rule, the
 //                      end-of-sentence term, the re-ranking by (score descending, previous rank ascending) as a sort of 64-bit keys
 //                      in LDS, then thread m < M writes row m.
+// Both are device BODIES (beam_wide_scan_body with a kResume flag, beam_wide_finish_body with the entry count and the walk bounds
+// as arguments); the kernels above instantiate them for a whole search, criterion_beam_stream.hpp for a slot of a wide beam
+// session, whose beam lives in a state buffer between launches (BeamWideCarry).
 #pragma once
 
 namespace w2l {
@@ -109,12 +112,28 @@ __device__ __forceinline__ int beam_wide_pow2(int m) {
 // the lexicon node an entry stands at, from the label of its last extension: (node << 3) | slot, -1 for the empty prefix
 __device__ __forceinline__ int beam_wide_u(int lab) { return (lab < 0 || (lab & 7)) ? 0 : (lab >> 3); }
 
-template <bool kLogAdd, class Pol, bool kLex>
-__global__ __launch_bounds__(kWideThreads) void beam_wide_scan(int T, int N, int W, float threshold,
-                                                               const float* __restrict__ x, const int* __restrict__ frames,
-                                                               BeamWideWs ww, const void* __restrict__ lex,
-                                                               const void* __restrict__ lm, float lmWeight,
-                                                               const float* __restrict__ classScore, float wordScore, BeamTrans tr) {
+// ---- a wide beam that outlives the launch (the wide beam session of criterion_beam_stream.hpp; the scan body's kResume)
+// As BeamCarry for the narrow scans: the fin* arrays of the workspace ([slot][W]: node, tot, LM state, LM sum, lexicon node, n) are
+// the stored beam's; BeamWideCarry adds what only the next frame needs.  pb and pnb are stored apart from tot: the extension by an
+// entry's own last label adds pb alone.  Rank order is array order.  cnt[slot]: the slot's frames of this step; flag[slot] bit 0: it
+// starts from the empty prefix.  (cnt is followed by the slots' frame indices, ctc_beam_rows<., ., true>'s.)
+struct BeamWideCarry {
+  const int *cnt, *flag;
+  int *par, *e, *lab;   // [S][W]; lab: the lexicon scan's
+  float *pb, *pnb;      // [S][W]
+};
+
+// kResume (criterion_beam_stream.hpp): utterance b is a slot of a wide beam session: its frame count (0: none) and start flag come
+// from cy.cnt / cy.flag -- the same in every thread, read before the first barrier, so the workgroup leaves or stays as one --, the
+// beam from the session's state unless the slot starts, and every field goes back there after the frames.  What indexes memory is
+// held to its range where it is loaded (n to W, node ids to the table, the last token to the row); LM states and lexicon nodes
+// are clamped where they are used (ngram_q, lex_child, lex_node).  beam_wide_scan below is the body with kResume off.
+template <bool kLogAdd, class Pol, bool kLex, bool kResume>
+__device__ __forceinline__ void beam_wide_scan_body(int T, int N, int W, float threshold, const float* __restrict__ x,
+                                                    const int* __restrict__ frames, const BeamWideWs& ww,
+                                                    const void* __restrict__ lex, const void* __restrict__ lm, float lmWeight,
+                                                    const float* __restrict__ classScore, float wordScore, BeamTrans tr,
+                                                    const BeamWideCarry& cy) {
   using L = WideLds<kLex>;
   constexpr int kF = L::kFields, kTh = kWideThreads;
   extern __shared__ float sAsgTrans[];   // BeamAsg::stage's array: the staged matrix comes first
@@ -133,7 +152,15 @@ __global__ __launch_bounds__(kWideThreads) void beam_wide_scan(int T, int N, int
 
   const CtcBeamWs& ws = ww.c;
   const int b = blockIdx.x, tid = threadIdx.x, K = ws.K;
-  const int F = align_frames(frames, b, T);
+  int F;
+  bool fresh = true;
+  if constexpr (kResume) {
+    F = min(max(cy.cnt[b], 0), T);
+    fresh = (cy.flag[b] & 1) != 0;
+    if (F == 0 && !fresh) return;   // the whole workgroup, before any barrier
+  } else {
+    F = align_frames(frames, b, T);
+  }
   const float* xb = x + (size_t)b * T * N;
   u64* tab = ws.table + (size_t)b * ws.cap;
   const unsigned capm = ws.cap - 1;
@@ -152,7 +179,17 @@ __global__ __launch_bounds__(kWideThreads) void beam_wide_scan(int T, int N, int
   auto ff = [&](int h, int f) { return (float*)(sBeam + (h * kF + f) * kTh); };
 
   int cur = 0, n = 1;
-  if (tid == 0) {
+  if (!fresh) {   // kResume alone; thread j loads entry j, the first frame's barrier publishes it
+    n = min(max(ws.finN[b], 0), min(W, kTh));
+    if (tid < n) {
+      const size_t o = (size_t)b * ww.W + tid;
+      const int node = ws.finNode[o], e = cy.e[o];
+      fi(0, 0)[tid] = (unsigned)node <= ws.cap ? node : 0; fi(0, 1)[tid] = cy.par[o]; fi(0, 2)[tid] = e >= 0 && e < N - 1 ? e : -1;
+      fi(0, 3)[tid] = ws.finState[o];
+      ff(0, 4)[tid] = cy.pb[o]; ff(0, 5)[tid] = cy.pnb[o]; ff(0, 6)[tid] = ws.finTot[o]; ff(0, 7)[tid] = ws.finAcc[o];
+      if constexpr (kLex) fi(0, 8)[tid] = cy.lab[o];
+    }
+  } else if (tid == 0) {
     fi(0, 0)[0] = 0; fi(0, 1)[0] = -1; fi(0, 2)[0] = -1; fi(0, 3)[0] = useLm ? (int)((const NgramHeader*)lm)->start : 0;
     ff(0, 4)[0] = 0.f; ff(0, 5)[0] = -INFINITY; ff(0, 6)[0] = 0.f; ff(0, 7)[0] = 0.f;
     if constexpr (kLex) fi(0, 8)[0] = -1;
@@ -385,24 +422,41 @@ __global__ __launch_bounds__(kWideThreads) void beam_wide_scan(int T, int N, int
       if constexpr (kLex) ws.finU[o] = live ? beam_wide_u(fi(cur, 8)[tid]) : -1;
     }
     if (tid == 0) ws.finN[b] = n;
+    if constexpr (kResume) {   // what the fin* arrays do not hold; thread j stores the entry it wrote (or loaded) itself
+      if (live) {
+        const size_t o = (size_t)b * ww.W + tid;
+        cy.par[o] = fi(cur, 1)[tid]; cy.e[o] = fi(cur, 2)[tid]; cy.pb[o] = ff(cur, 4)[tid]; cy.pnb[o] = ff(cur, 5)[tid];
+        if constexpr (kLex) cy.lab[o] = fi(cur, 8)[tid];
+      }
+    }
   }
+}
+
+template <bool kLogAdd, class Pol, bool kLex>
+__global__ __launch_bounds__(kWideThreads) void beam_wide_scan(int T, int N, int W, float threshold,
+                                                               const float* __restrict__ x, const int* __restrict__ frames,
+                                                               BeamWideWs ww, const void* __restrict__ lex,
+                                                               const void* __restrict__ lm, float lmWeight,
+                                                               const float* __restrict__ classScore, float wordScore, BeamTrans tr) {
+  beam_wide_scan_body<kLogAdd, Pol, kLex, false>(T, N, W, threshold, x, frames, ww, lex, lm, lmWeight, classScore, wordScore, tr,
+                                                 BeamWideCarry{});
 }
 
 // eosWord: the LM's index of the end of a sentence (the token searches'; the lexicon search takes it from the LM's header);
 // lmScores null: the LM-free CTC search, which has no such output
+// n: the final entries of utterance b, the same in every thread; g: what bounds the walks up the prefix table (BeamWalk{}: nothing)
 template <bool kLex>
-__global__ __launch_bounds__(kWideThreads) void beam_wide_finish(int M, int Lmax, int maxWords, int eosWord, BeamWideWs ww,
-                                                                 const void* __restrict__ lex, const void* __restrict__ lm,
-                                                                 float lmWeight, float eosScore, int useEos,
-                                                                 int* __restrict__ labels, int* __restrict__ lengths,
-                                                                 float* __restrict__ scores, float* __restrict__ lmScores,
-                                                                 int* __restrict__ words, int* __restrict__ wordCounts) {
+__device__ __forceinline__ void beam_wide_finish_body(int b, int n, BeamWalk g, int M, int Lmax, int maxWords, int eosWord,
+                                                      const BeamWideWs& ww, const void* __restrict__ lex,
+                                                      const void* __restrict__ lm, float lmWeight, float eosScore, int useEos,
+                                                      int* __restrict__ labels, int* __restrict__ lengths,
+                                                      float* __restrict__ scores, float* __restrict__ lmScores,
+                                                      int* __restrict__ words, int* __restrict__ wordCounts) {
   __shared__ u64 sKey[kWideThreads];
   __shared__ float sScore[kWideThreads], sAcc[kWideThreads];
   const CtcBeamWs& ws = ww.c;
-  const int b = blockIdx.x, r = threadIdx.x;
+  const int r = threadIdx.x;
   const u64* tab = ws.table + (size_t)b * ws.cap;
-  const int n = ws.finN[b];
   const size_t o = (size_t)b * ww.W + min(r, ww.W - 1);
   const bool alive = r < n && (!kLex || ws.finU[o] == 0);   // with a lexicon only finished words count at the end
   float score = -INFINITY, acc = -INFINITY;
@@ -426,22 +480,22 @@ __global__ __launch_bounds__(kWideThreads) void beam_wide_finish(int M, int Lmax
   int* lab = labels + row * Lmax;
   int len = 0, nwords = 0;
   if constexpr (!kLex) {
-    len = beam_write_labels(tab, live, ws.finNode + (size_t)b * ww.W + src, Lmax, lab);
+    len = beam_write_labels(tab, live, ws.finNode + (size_t)b * ww.W + src, Lmax, lab, g);
   } else {
     const LexView xv = lex_view(lex);
     int* wrd = words + row * maxWords;
     if (live) {
       const int node = ws.finNode[(size_t)b * ww.W + src];
-      len = beam_chain_len(tab, node, &nwords);
+      len = beam_chain_len(tab, node, &nwords, g);
       int i = len - 1, j = nwords - 1;
-      for (int p = node; p > 0; --i) {
+      for (int p = node; i >= 0 && beam_walk_ok(g, p); --i) {   // len labels: the walk above counted them under the same bound
         const u64 edge = tab[p - 1];
         const unsigned l = (unsigned)edge - 1u;
         const int v = (int)(l >> 3), slot = (int)(l & 7u);
         const LexNode& nd = lex_node(xv, v);
         if (i < Lmax) lab[i] = v == 0 ? xv.silToken : nd.tok;
         if (slot > 0) {
-          if (j < maxWords) wrd[j] = nd.words[min(slot - 1, kLexMaxWords - 1)];
+          if (j >= 0 && j < maxWords) wrd[j] = nd.words[min(slot - 1, kLexMaxWords - 1)];
           --j;
         }
         p = (int)(edge >> 32);
@@ -454,6 +508,17 @@ __global__ __launch_bounds__(kWideThreads) void beam_wide_finish(int M, int Lmax
   lengths[row] = live ? len : -1;
   scores[row] = live ? sScore[src] : -INFINITY;
   if (lmScores) lmScores[row] = live ? sAcc[src] : -INFINITY;
+}
+
+template <bool kLex>
+__global__ __launch_bounds__(kWideThreads) void beam_wide_finish(int M, int Lmax, int maxWords, int eosWord, BeamWideWs ww,
+                                                                 const void* __restrict__ lex, const void* __restrict__ lm,
+                                                                 float lmWeight, float eosScore, int useEos,
+                                                                 int* __restrict__ labels, int* __restrict__ lengths,
+                                                                 float* __restrict__ scores, float* __restrict__ lmScores,
+                                                                 int* __restrict__ words, int* __restrict__ wordCounts) {
+  beam_wide_finish_body<kLex>(blockIdx.x, ww.c.finN[blockIdx.x], BeamWalk{}, M, Lmax, maxWords, eosWord, ww, lex, lm, lmWeight,
+                              eosScore, useEos, labels, lengths, scores, lmScores, words, wordCounts);
 }
 
 static size_t beam_wide_workspace_size(int B, int T, int N, int beam, int beamToken, int variant, bool noBlank) {

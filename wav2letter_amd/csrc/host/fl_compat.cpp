@@ -1325,7 +1325,18 @@ af::array CTCLoss::viterbiPathWithTarget(const af::array& input, const af::array
 // ---- the CTC beam search continued chunk by chunk (csrc/criterion_beam_stream.hpp)
 StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& o)
     : o_(o), slots_(slots), maxChunk_(maxChunk), maxFrames_(maxFrames), nLabel_(numLabels) {
-  if (o.wide) throw std::runtime_error("StreamingDecoder: the wide searches (beam above 64) are not incremental");
+  if (o.wide)
+    throw std::runtime_error("StreamingDecoder runs the narrow searches (beam up to 64); the wide searches are incremental as "
+                             "WideStreamingDecoder");
+  create(false);
+}
+StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& o, WideKernels)
+    : o_(o), slots_(slots), maxChunk_(maxChunk), maxFrames_(maxFrames), nLabel_(numLabels) {
+  create(true);
+}
+void StreamingDecoder::create(bool wideKernels) {
+  const BeamSearchOptions& o = o_;
+  const int slots = slots_, maxChunk = maxChunk_, maxFrames = maxFrames_, numLabels = nLabel_;
   if (o.nbest < 1 || o.maxLen < 0 || o.maxWords < 0) throw std::invalid_argument("StreamingDecoder: bad nbest, maxLen or maxWords");
   w2l_beam_session_desc d{};
   d.slots = slots; d.maxChunk = maxChunk; d.maxFrames = maxFrames; d.N = numLabels;
@@ -1349,10 +1360,10 @@ StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int n
     if (!o.classScore.isempty()) d.classScore = o_.classScore.device<float>();
   }
   if (o.lm) { d.lm = o.lm->deviceBlob(); d.lmHasEos = o.lm->hasEos() ? 1 : 0; }
-  const int st = w2l_beam_session_create(&d, &h_);
+  const int st = wideKernels ? w2l_beam_session_create_wide(&d, &h_) : w2l_beam_session_create(&d, &h_);
   if (st == W2L_EUNSUPPORTED) throw std::runtime_error(std::string("StreamingDecoder: ") + w2l_host_last_error());
   if (st != W2L_OK) throw std::invalid_argument(std::string("StreamingDecoder: ") + w2l_host_last_error());
-  const size_t bytes = w2l_beam_session_state_bytes(&d);
+  const size_t bytes = wideKernels ? w2l_beam_session_wide_state_bytes(&d) : w2l_beam_session_state_bytes(&d);
   state_ = devAlloc(bytes);
   if (w2l_beam_session_bind(h_, state_.get(), bytes) != W2L_OK) {
     const std::string msg = w2l_host_last_error();

@@ -175,15 +175,18 @@ class StreamingDecoder:
     in include/w2l_hip.h, w2l_beam_session_*).  `slots` utterances in progress, at most max_chunk emission frames per slot and
     step, at most max_frames per utterance.  options: ctc_beam_search's beam, beam_token, threshold, log_add, normalize, lm,
     lm_weight, class_score, eos_score, lexicon, word_score; the variant is chosen as ctc_beam_search chooses its entry point (no
-    lm: LM-free; lm: token LM; lm and lexicon: lexicon with a word LM).  wide=True is refused: the wide searches are not
-    incremental.  With max_chunk = StreamingSession.max_out, step() takes StreamingSession.step's (out, n_out) as they are.
+    lm: LM-free; lm: token LM; lm and lexicon: lexicon with a word LM).  beam and beam_token go up to 64; wide=True is refused:
+    WideStreamingDecoder is the incremental form of the wide searches.  With max_chunk = StreamingSession.max_out, step() takes StreamingSession.step's (out, n_out) as they are.
     Creation is host arithmetic; the device state is allocated at the first step."""
+
+    _create_fn, _bytes_fn = "w2l_beam_session_create", "w2l_beam_session_state_bytes"
 
     def __init__(self, slots, max_chunk, max_frames, nlabel, beam=64, beam_token=64, threshold=float("inf"), log_add=False,
                  normalize=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0, wide=False,
                  device="cuda"):
         if wide:
-            raise _lib.W2LUnsupported("StreamingDecoder: the wide searches (beam above 64) are not incremental")
+            raise _lib.W2LUnsupported("StreamingDecoder runs the narrow searches (beam up to 64); the wide searches are incremental "
+                                      "as WideStreamingDecoder")
         N = int(nlabel)
         if lexicon is not None:
             if lm is None:
@@ -244,8 +247,8 @@ class StreamingDecoder:
             ptrs = tuple(t.data_ptr() if t is not None else None for t in self._keep)
         d = self._desc(*ptrs)
         h = C.c_void_p(0)
-        _check(self.L.w2l_beam_session_create(C.byref(d), C.byref(h)), "streaming decoder")
-        self.state_bytes = self.L.w2l_beam_session_state_bytes(C.byref(d))
+        _check(getattr(self.L, self._create_fn)(C.byref(d), C.byref(h)), "streaming decoder")
+        self.state_bytes = getattr(self.L, self._bytes_fn)(C.byref(d))
         if placeholders:
             self.L.w2l_beam_session_destroy(h)
         else:
@@ -327,3 +330,19 @@ class StreamingDecoder:
         if self.h is None:
             return
         _check(self.L.w2l_beam_session_reset(self.h, int(slot)), "streaming decoder reset")
+
+
+class WideStreamingDecoder(StreamingDecoder):
+    """WideStreamingDecoder(slots, max_chunk, max_frames, nlabel, **options): StreamingDecoder on the wide kernels, an incremental
+    criterion.ctc_beam_search(..., wide=True) (the contract is in include/w2l_hip.h, w2l_beam_session_create_wide).  The arguments
+    are StreamingDecoder's without `wide`; beam goes up to 1024, beam_token (after clipping to NLABEL - 1) up to 64.  The methods
+    are StreamingDecoder's.  A slot's state grows with beam * max_frames (16 bytes per prefix-table edge, two edges per entry and
+    frame): 64 MiB at beam 1024 and max_frames 4096."""
+
+    _create_fn, _bytes_fn = "w2l_beam_session_create_wide", "w2l_beam_session_wide_state_bytes"
+
+    def __init__(self, slots, max_chunk, max_frames, nlabel, beam=1024, beam_token=64, threshold=float("inf"), log_add=False,
+                 normalize=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0, device="cuda"):
+        super().__init__(slots, max_chunk, max_frames, nlabel, beam=beam, beam_token=beam_token, threshold=threshold, log_add=log_add,
+                         normalize=normalize, lm=lm, lm_weight=lm_weight, class_score=class_score, eos_score=eos_score, lexicon=lexicon,
+                         word_score=word_score, device=device)
