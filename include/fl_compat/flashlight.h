@@ -619,6 +619,17 @@ class FL_COMPAT_API StreamingDecoder {
   BeamSearchResult result();
   int frames(int slot) const;   // emission frames fed to a slot since its start
   void reset(int slot);         // closes a slot
+  // What can no longer change, handed out, and the prefix tables compacted (w2l_beam_session_commit; the contract is in w2l_hip.h;
+  // the reference's Decoder::prune(lookBack) commits to the best hypothesis instead, which is lossy).  commit[s] != 0: slot s
+  // (empty = every started slot).  labels[s] / words[s]: what THIS call committed for slot s, in order (words with a lexicon);
+  // live[s]: the nodes of its table afterwards (a slot may then take maxFrames - ceil(live / beamSize) further frames before its
+  // next commit).  result() returns the tails behind committed(slot).  Enqueues on fl::currentStream() and WAITS for it.
+  struct Committed { std::vector<std::vector<int>> labels, words; std::vector<int> live; };
+  Committed commit(const std::vector<int>& commit = {});
+  // every label and word slot has committed since its start
+  const std::vector<int>& committedLabels(int slot) const;
+  const std::vector<int>& committedWords(int slot) const;
+  std::pair<std::vector<int>, std::vector<int>> committed(int slot) const { return {committedLabels(slot), committedWords(slot)}; }
 
  protected:
   struct WideKernels {};   // WideStreamingDecoder's constructor
@@ -630,6 +641,9 @@ class FL_COMPAT_API StreamingDecoder {
   std::shared_ptr<void> state_;
   void* h_ = nullptr;
   int slots_ = 0, maxChunk_ = 0, maxFrames_ = 0, nLabel_ = 0;
+  std::shared_ptr<void> scratch_;                       // commit's, allocated at the first commit
+  size_t scratchBytes_ = 0;
+  std::vector<std::vector<int>> doneLabels_, doneWords_;   // per slot, since its start
 };
 
 // fl_compat extension: StreamingDecoder on the wide kernels (w2l_beam_session_create_wide): the result after any number of frames

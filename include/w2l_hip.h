@@ -1078,6 +1078,57 @@ int w2l_beam_session_reset(void* session, int slot);
 int w2l_beam_session_create_wide(const w2l_beam_session_desc* desc, void** session);
 size_t w2l_beam_session_wide_state_bytes(const w2l_beam_session_desc* desc);
 
+/* ---- committing the stable prefix of a beam session and compacting its table (csrc/criterion_beam_commit.hpp) -------
+ * For either kind of session.  Every hypothesis a slot will ever return descends from one of its stored beam entries, so the
+ * labels above the deepest common ancestor C of ALL stored entries (the lexicon variant's entries with an unfinished word, which
+ * a result hides, included) can never change again, whatever audio follows.  w2l_beam_session_commit hands them out -- all labels
+ * above C: C's own label stays back, so that no entry is left at the root with a real last label -- and rebuilds the slot's prefix
+ * table with only the nodes that stored entries still descend from.  The slot's results from then on are TAILS: the labels (and
+ * words) after the committed ones.  If C is the root or a child of the root, or the beam is dead, nothing is committed and the
+ * table is still compacted.
+ * THE CONTRACT.
+ *   Exactness.   Sessions A and B have the same descriptor (but for maxFrames) and are fed the same frames; A never commits
+ *                (and has the maxFrames for that), B commits at any points.  After any number of frames, for every row m of a
+ *                result: B's committed labels since the slot's start followed by B's row m are A's row m; B's lengths and
+ *                wordCounts plus its committed totals are A's; B's committed words followed by its row's words are A's; scores
+ *                and lmScores are equal BIT FOR BIT, in both logAdd modes, all three variants, narrow and wide.  Empty rows stay
+ *                empty rows (length -1: nothing is added to them).
+ *   Stability.   The committed labels are a prefix of every row that A returns at any later time.
+ *   Maximality.  W2L_BEAM_PLAIN and W2L_BEAM_LM: the total committed after a commit is max(0, LCP - 1), LCP the longest common
+ *                prefix of ALL live rows of A's result at nbest = beam at that moment.  W2L_BEAM_LEX: at most that (hidden
+ *                unfinished entries hold the cut back; homophones are different nodes with equal labels).
+ *   Overflow.    A slot whose commit has more than maxLen labels or more than maxWords words is refused with W2L_EINVAL before
+ *                anything of it is changed (the kernel counts first): committed wholly or not at all.  The message names the first
+ *                such slot and what it needs; h_nLabels / h_nWords of a refused slot hold the NEED, h_live its unchanged live
+ *                count, and its totals do not move.  The other flagged slots of the call are committed as usual.
+ *   Budget.      The table after a commit holds `live` nodes.  The slot may then take maxFrames - ceil(live / beam) further frames
+ *                before its next commit (the table then holds at most live + beam * frames <= beam * maxFrames <= cap / 2 nodes);
+ *                a step past that is refused with W2L_EINVAL, naming the slot, and w2l_beam_session_counts follows the same rule.
+ *                A slot that has not committed since its start keeps the maxFrames rule and its message.  Start, reset and bind
+ *                zero the committed totals and the budget.  w2l_beam_session_frames keeps returning the frames since the start.
+ *   w2l_beam_session_commit_bytes  the scratch for ONE slot, every part 256-byte aligned: 4 S ints; a table of cap 8-byte edges;
+ *                                 a label stack [maxFrames][64] ints (wide: [maxFrames][beam]).  At beam 1024 and maxFrames
+ *                                 4096: 64 MiB + 16 MiB.  A caller buffer of its own, so the state sizes do not move.
+ *   w2l_beam_session_commit       h_commit: HOST int [S], non-zero = commit this slot; NULL = every started slot.  A flagged slot
+ *                                 that was never started, or was reset, does nothing and reports 0 / 0 / 0.  labels: device
+ *                                 [S][maxLen], words: device [S][maxWords] (W2L_BEAM_LEX only, else ignored): row s holds what
+ *                                 THIS call committed for slot s, in order, padded with -1 (rows of slots that did nothing are
+ *                                 not written).  h_nLabels, h_nWords (may be NULL), h_live (may be NULL): HOST int [S].  Flagged
+ *                                 slots are processed one after another on `stream` against the one scratch: a clear, one
+ *                                 workgroup that finds the cut, writes the labels and rebuilds the table, one copy pass.  THIS IS
+ *                                 THE ONE SESSION CALL THAT SYNCHRONISES: it waits for `stream` once, at its end, to bring the
+ *                                 counts and live to the host.  A session that never calls it runs exactly the launches it ran
+ *                                 before.
+ *   w2l_beam_session_committed    labels and words (either may be NULL) committed by a slot since its start
+ * Refusals (W2L_EINVAL, before anything is enqueued): a call before bind; scratch missing, misaligned or smaller than
+ * w2l_beam_session_commit_bytes; maxLen < 1; labels missing; words missing or maxWords < 1 for W2L_BEAM_LEX; h_nLabels missing.
+ * A state buffer damaged between calls gives wrong labels, never a spin or an access outside the buffers: every walk up a table
+ * stays inside it and ends after as many labels as the slot has had frames. */
+size_t w2l_beam_session_commit_bytes(void* session);
+int w2l_beam_session_commit(void* session, const int* h_commit, void* scratch, size_t scratchBytes, int maxLen, int* labels,
+                            int maxWords, int* words, int* h_nLabels, int* h_nWords, int* h_live, w2l_stream_t stream);
+int w2l_beam_session_committed(void* session, int slot, int* h_labels, int* h_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,11 +11,18 @@ again from frame 0 after every chunk, the sum of the whole search over the prefi
 trapezoid rule).  The session's final hypotheses are checked bit for bit against the whole search before anything is timed.
   --wide: the wide session (w2l_beam_session_create_wide) against the wide whole search (the w2l_*_wide entry points) at B = S in
   the same run: W = 128, 500 and 1024 with K = 64, S = 1 / 16 / 64, chunks of 1 and 4; then, at W = K = 64 where both families
-  exist, the narrow session and the wide session side by side ("family"), each against its own whole search."""
+  exist, the narrow session and the wide session side by side ("family"), each against its own whole search.
+  --commit-every=K: w2l_beam_session_commit at one-frame steps, W = K = 64 narrow, W = 500 and 1024 wide, S = 1 / 16 /
+  64.  First the exactness contract: a session that commits after every K-th step against one that never does, fed the same frames
+  -- committed ++ tail == the uncommitted rows, scores the same bits, after every commit and at the end.  Then one JSON line per
+  shape: the median one-frame step of the committing session, the median commit (the C call, host clock: it waits for the stream),
+  per slot and as a multiple of the step, the nodes a commit leaves and the labels committed, and the utterance with commits
+  against the utterance without in the same run (host clock, both synchronised at the end)."""
 import json
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -99,7 +106,98 @@ def bench(S, chunk, W, reps, opts, wide=False):
             "research_over_session": round(research / t_utt, 1)}
 
 
+def bench_commit(S, W, every, reps, opts, wide):
+    from wav2letter_amd import _lib
+    L = _lib.lib()
+    g = torch.Generator(device="cpu").manual_seed(11)
+    x = torch.randn(S, T, N, generator=g)
+    x[:, :, :HOT] += 2.0
+    x = x.cuda()
+    K = min(W, 64)
+    o = dict(beam=W, beam_token=K, threshold=float("inf"), log_add=False, normalize=False, **opts)
+    cls = WideStreamingDecoder if wide else StreamingDecoder
+    a, b = cls(S, 1, T, N, **o), cls(S, 1, T, N, **o)
+    steps = [x[:, t:t + 1].contiguous() for t in range(T)]
+    one = np.ones(S, np.int32)
+
+    def rows(dec, full):
+        return [t.cpu().numpy() for t in dec.result(nbest=1, max_len=T, full=full)]
+
+    def check(what):
+        ra, rb = rows(a, False), rows(b, True)
+        assert (rb[0][:, :, :T] == ra[0]).all() and (rb[0][:, :, T:] == -1).all() and (rb[1] == ra[1]).all(), what
+        assert all((p.view(np.int32) == q.view(np.int32)).all() for p, q in zip(ra[2:4], rb[2:4])), what
+
+    # the exactness contract first
+    for i, em in enumerate(steps):
+        a.step(em, one, one * (i == 0))
+        b.step(em, one, one * (i == 0))
+        if i % every == every - 1:
+            b.commit()
+            check(("commit after step", i))
+    check("end")
+    done = [len(b.committed(s)[0]) for s in range(S)]
+
+    # then the clock: the C call, with buffers made once
+    scratch = torch.empty(L.w2l_beam_session_commit_bytes(b.h), dtype=torch.uint8, device="cuda")
+    labels = torch.empty(S, T, dtype=torch.int32, device="cuda")
+    words = torch.empty(S, T, dtype=torch.int32, device="cuda")
+    nl, nw, live = np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(S, np.int32)
+    stream = torch.cuda.current_stream().cuda_stream
+    commits, lives = [], []
+
+    def commit(dec, timed):
+        if timed:
+            torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        st = L.w2l_beam_session_commit(dec.h, None, scratch.data_ptr(), scratch.numel(), T, labels.data_ptr(), T, words.data_ptr(),
+                                       nl.ctypes.data, nw.ctypes.data, live.ctypes.data, stream)
+        assert st == 0, L.w2l_host_last_error().decode()
+        if timed:
+            commits.append((time.perf_counter() - t0) * 1e6)
+            lives.append(float(live.mean()))
+
+    def utterance(dec, k, timed=False):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i, em in enumerate(steps):
+            dec.step(em, one, one * (i == 0))
+            if k and i % k == k - 1:
+                commit(dec, timed)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6
+
+    for k in (0, every):
+        utterance(b, k)
+    t_plain = min(utterance(b, 0) for _ in range(reps))
+    t_commit = min(utterance(b, every) for _ in range(reps))
+    utterance(b, every, timed=True)
+    lat = []
+    for i, em in enumerate(steps):   # one-frame steps of a session that commits, timed one by one
+        lat.append(events(lambda: b.step(em, one, one * (i == 0)), 1))
+        if i % every == every - 1:
+            commit(b, False)
+    step, com = statistics.median(lat), statistics.median(commits)
+    return {"family": "wide" if wide else "narrow", "S": S, "W": W, "K": K, "commit_every": every, "scratch_bytes": scratch.numel(),
+            "step_us_median": round(step, 1), "commit_us_median": round(com, 1), "commit_us_max": round(max(commits), 1),
+            "commit_us_per_slot": round(com / S, 1), "commit_over_step": round(com / step, 2),
+            "live_nodes_mean": round(statistics.mean(lives), 1), "labels_committed_mean": round(statistics.mean(done), 1),
+            "utterance_us": round(t_plain, 1), "utterance_with_commits_us": round(t_commit, 1),
+            "added_percent": round(100 * (t_commit - t_plain) / t_plain, 1)}
+
+
 if __name__ == "__main__":
+    every = [int(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--commit-every=")]
+    if every:
+        args = [a for a in sys.argv[1:] if not a.startswith("--")]
+        variant = args[0] if len(args) > 0 else "lm"
+        reps = int(args[1]) if len(args) > 1 else 3
+        opts = tables(variant)
+        print(json.dumps({"variant": variant, "T": T, "N": N, "reps": reps, "commit_every": every[0]}), flush=True)
+        for W, fam in ((64, False), (500, True), (1024, True)):
+            for S in (1, 16, 64):
+                print(json.dumps(bench_commit(S, W, every[0], reps, opts, fam)), flush=True)
+        sys.exit(0)
     args = [a for a in sys.argv[1:] if a != "--wide"]
     wide = "--wide" in sys.argv[1:]
     variant = args[0] if len(args) > 0 else "lm"

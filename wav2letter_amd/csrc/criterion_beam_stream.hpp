@@ -167,6 +167,11 @@ struct BeamSession {
   size_t stateBytes = 0, cap = 0;
   std::vector<int> frames;    // per slot: emission frames fed since its start
   std::vector<char> active;   // per slot: started and not reset
+  // w2l_beam_session_commit (criterion_beam_commit.hpp); all 0 for a slot that has not committed since its start
+  std::vector<int> doneLabels, doneWords;   // per slot: labels and words committed since its start
+  std::vector<int> live;                    // per slot: nodes of its table after its last commit
+  std::vector<int> credit;                  // per slot: frames the last commit gave back: frames then - ceil(live / beam)
+  int* commitOut = nullptr;                 // pinned [S][4]: a commit's counts
   BeamSessionLayout L{};
   bool wide = false;          // w2l_beam_session_create_wide: the wide kernels over WL
   BeamWideSessionLayout WL{};
@@ -180,6 +185,7 @@ struct BeamSession {
       if (ev[r]) (void)hipEventDestroy(ev[r]);
       if (pinned[r]) (void)hipHostFree(pinned[r]);
     }
+    if (commitOut) (void)hipHostFree(commitOut);
   }
 };
 
@@ -233,7 +239,14 @@ static int beam_session_advance(const BeamSession& s, const int* n, const int* s
                                                " frames, outside 0.." + std::to_string(s.d.maxChunk));
     if (!st && !s.active[i] && n[i] > 0)
       return beam_session_fail(W2L_EINVAL, "beam session step: slot " + std::to_string(i) + " is fed before it was started");
-    if ((st ? 0 : s.frames[i]) + n[i] > s.d.maxFrames)
+    if (!st && (s.credit[i] > 0 || s.live[i] > 0) && s.frames[i] - s.credit[i] + n[i] > s.d.maxFrames)   // a slot that has committed: its budget
+      return beam_session_fail(W2L_EINVAL, "beam session step: slot " + std::to_string(i) + " would pass its budget of maxFrames = " +
+                                               std::to_string(s.d.maxFrames) + " frames (" + std::to_string(s.live[i]) +
+                                               " nodes kept by its last commit count as " +
+                                               std::to_string((s.live[i] + s.d.beam - 1) / s.d.beam) + ", " +
+                                               std::to_string(s.frames[i] - s.credit[i] - (s.live[i] + s.d.beam - 1) / s.d.beam) +
+                                               " fed since, " + std::to_string(n[i]) + " given); commit again or start the slot anew");
+    if ((st ? 0 : s.frames[i] - s.credit[i]) + n[i] > s.d.maxFrames)
       return beam_session_fail(W2L_EINVAL, "beam session step: slot " + std::to_string(i) + " would pass maxFrames = " +
                                                std::to_string(s.d.maxFrames) + " (" + std::to_string(st ? 0 : s.frames[i]) + " fed, " +
                                                std::to_string(n[i]) + " given)");
@@ -258,6 +271,12 @@ static int beam_session_wide_kernel(const BeamSession& s, F&& f) {
 }
 
 // the next pinned table of the ring, free to write
+// after a step's counts are taken over: a slot that started has committed nothing
+static void beam_session_started(BeamSession& s, const int* start) {
+  for (int i = 0; start && i < s.d.slots; ++i)
+    if (start[i]) s.doneLabels[i] = s.doneWords[i] = s.live[i] = s.credit[i] = 0;
+}
+
 static int beam_session_table(BeamSession& s, int** table) {
   const int r = s.ring;
   if (s.evUsed[r]) W2L_HIP_CHECK(hipEventSynchronize(s.ev[r]));   // the copy of kBeamRing calls ago: long done
@@ -306,6 +325,10 @@ static int beam_session_make(const w2l_beam_session_desc* desc, void** session, 
                        : beam_session_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K);
   s->frames.assign(desc->slots, 0);
   s->active.assign(desc->slots, 0);
+  s->doneLabels.assign(desc->slots, 0);
+  s->doneWords.assign(desc->slots, 0);
+  s->live.assign(desc->slots, 0);
+  s->credit.assign(desc->slots, 0);
   *session = s;
   return W2L_OK;
 }
@@ -334,6 +357,7 @@ W2L_API int w2l_beam_session_bind(void* session, void* state, size_t bytes) {
     if (!s.pinned[r]) W2L_HIP_CHECK(hipHostMalloc((void**)&s.pinned[r], tb, hipHostMallocDefault));
     if (!s.ev[r]) W2L_HIP_CHECK(hipEventCreateWithFlags(&s.ev[r], hipEventDisableTiming));
   }
+  if (!s.commitOut) W2L_HIP_CHECK(hipHostMalloc((void**)&s.commitOut, (size_t)4 * s.d.slots * sizeof(int), hipHostMallocDefault));
   if (s.wide) {   // the scan's 64 or 72 KiB of dynamic LDS are asked for here, so a step is launches alone
     const int rc = beam_session_wide_kernel(s, [&](auto la, auto lx) -> int {
       constexpr bool kLa = decltype(la)::value, kLx = decltype(lx)::value;
@@ -349,6 +373,7 @@ W2L_API int w2l_beam_session_bind(void* session, void* state, size_t bytes) {
   // another buffer holds no slot's search
   std::fill(s.frames.begin(), s.frames.end(), 0);
   std::fill(s.active.begin(), s.active.end(), 0);
+  for (std::vector<int>* v : {&s.doneLabels, &s.doneWords, &s.live, &s.credit}) std::fill(v->begin(), v->end(), 0);
   return W2L_OK;
 }
 
@@ -361,6 +386,7 @@ W2L_API int w2l_beam_session_counts(void* session, const int* h_n, const int* h_
   if (const int rc = beam_session_advance(s, h_n, h_start, nullptr, fa, aa)) return rc;
   s.frames.swap(fa);
   s.active.swap(aa);
+  beam_session_started(s, h_start);
   return W2L_OK;
 }
 
@@ -429,6 +455,7 @@ W2L_API int w2l_beam_session_step(void* session, const float* emissions, const i
   }
   s.frames.swap(fa);
   s.active.swap(aa);
+  beam_session_started(s, h_start);
   return W2L_OK;
 }
 
@@ -484,5 +511,6 @@ W2L_API int w2l_beam_session_reset(void* session, int slot) {
   if (slot < 0 || slot >= s.d.slots) return beam_session_fail(W2L_EINVAL, "beam session reset: no such slot");
   s.frames[slot] = 0;
   s.active[slot] = 0;
+  s.doneLabels[slot] = s.doneWords[slot] = s.live[slot] = s.credit[slot] = 0;
   return W2L_OK;
 }

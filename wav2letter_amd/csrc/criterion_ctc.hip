@@ -901,3 +901,4 @@ W2L_API int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, 
 #include "criterion_asg_beam.hpp"
 #include "criterion_beam_wide.hpp"
 #include "criterion_beam_stream.hpp"
+#include "criterion_beam_commit.hpp"

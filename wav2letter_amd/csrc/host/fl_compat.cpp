@@ -1364,6 +1364,8 @@ void StreamingDecoder::create(bool wideKernels) {
   if (st == W2L_EUNSUPPORTED) throw std::runtime_error(std::string("StreamingDecoder: ") + w2l_host_last_error());
   if (st != W2L_OK) throw std::invalid_argument(std::string("StreamingDecoder: ") + w2l_host_last_error());
   const size_t bytes = wideKernels ? w2l_beam_session_wide_state_bytes(&d) : w2l_beam_session_state_bytes(&d);
+  doneLabels_.assign(slots, {});
+  doneWords_.assign(slots, {});
   state_ = devAlloc(bytes);
   if (w2l_beam_session_bind(h_, state_.get(), bytes) != W2L_OK) {
     const std::string msg = w2l_host_last_error();
@@ -1381,6 +1383,45 @@ void StreamingDecoder::step(const af::array& emissions, const std::vector<int>& 
   const int st = w2l_beam_session_step(h_, emissions.device<float>(), counts.data(), start.empty() ? nullptr : start.data(), S());
   if (st == W2L_EINVAL) throw std::invalid_argument(std::string("StreamingDecoder::step: ") + w2l_host_last_error());
   w2l::w2lCheck(st, "StreamingDecoder::step");
+  for (int i = 0; i < (int)start.size(); ++i)
+    if (start[i]) { doneLabels_[i].clear(); doneWords_[i].clear(); }
+}
+StreamingDecoder::Committed StreamingDecoder::commit(const std::vector<int>& flags) {
+  if (!flags.empty() && (int)flags.size() != slots_) throw std::invalid_argument("StreamingDecoder::commit: one flag per slot");
+  if (!scratch_) {
+    scratchBytes_ = w2l_beam_session_commit_bytes(h_);
+    scratch_ = devAlloc(scratchBytes_);
+  }
+  int maxLen = 1;   // no commit is longer than the labels a slot still holds
+  for (int i = 0; i < slots_; ++i) maxLen = std::max(maxLen, frames(i) - (int)doneLabels_[i].size());
+  af::array labels(af::dim4(maxLen, slots_), af::s32), words;
+  if (o_.lexicon) words = af::array(af::dim4(maxLen, slots_), af::s32);
+  std::vector<int> nl(slots_, 0), nw(slots_, 0);
+  Committed c;
+  c.labels.resize(slots_); c.words.resize(slots_); c.live.assign(slots_, 0);
+  const int st = w2l_beam_session_commit(h_, flags.empty() ? nullptr : flags.data(), scratch_.get(), scratchBytes_, maxLen,
+                                         labels.device<int>(), maxLen, o_.lexicon ? words.device<int>() : nullptr, nl.data(), nw.data(),
+                                         c.live.data(), S());
+  if (st == W2L_EINVAL) throw std::invalid_argument(std::string("StreamingDecoder::commit: ") + w2l_host_last_error());
+  w2l::w2lCheck(st, "StreamingDecoder::commit");
+  std::vector<int> hl((size_t)maxLen * slots_), hw;
+  labels.host(hl.data());
+  if (o_.lexicon) { hw.resize((size_t)maxLen * slots_); words.host(hw.data()); }
+  for (int i = 0; i < slots_; ++i) {
+    c.labels[i].assign(hl.begin() + (size_t)i * maxLen, hl.begin() + (size_t)i * maxLen + nl[i]);
+    if (o_.lexicon) c.words[i].assign(hw.begin() + (size_t)i * maxLen, hw.begin() + (size_t)i * maxLen + nw[i]);
+    doneLabels_[i].insert(doneLabels_[i].end(), c.labels[i].begin(), c.labels[i].end());
+    doneWords_[i].insert(doneWords_[i].end(), c.words[i].begin(), c.words[i].end());
+  }
+  return c;
+}
+const std::vector<int>& StreamingDecoder::committedLabels(int slot) const {
+  if (slot < 0 || slot >= slots_) throw std::invalid_argument("StreamingDecoder::committed: no such slot");
+  return doneLabels_[slot];
+}
+const std::vector<int>& StreamingDecoder::committedWords(int slot) const {
+  if (slot < 0 || slot >= slots_) throw std::invalid_argument("StreamingDecoder::committed: no such slot");
+  return doneWords_[slot];
 }
 BeamSearchResult StreamingDecoder::result() {
   const int M = o_.nbest, Lmax = o_.maxLen > 0 ? o_.maxLen : maxFrames_, maxWords = o_.maxWords > 0 ? o_.maxWords : Lmax;
@@ -1409,6 +1450,8 @@ int StreamingDecoder::frames(int slot) const {
 }
 void StreamingDecoder::reset(int slot) {
   if (w2l_beam_session_reset(h_, slot) != W2L_OK) throw std::invalid_argument(std::string("StreamingDecoder::reset: ") + w2l_host_last_error());
+  doneLabels_[slot].clear();
+  doneWords_[slot].clear();
 }
 
 // n-best beam search; inputSizes as in viterbiPathWithTarget.  trans == nullptr: the CTC searches (w2l_ctc_beam_search*), blank =

@@ -226,6 +226,9 @@ class StreamingDecoder:
         self._state = None
         self._keep = ()
         self.state_bytes = 0
+        self._done = None      # per slot: (labels, words) committed since its start; None before the first commit
+        self._scratch = None   # commit's device scratch, allocated at the first commit
+        self.live = None
         self._create(placeholders=True)
 
     def _desc(self, lm_ptr, lex_ptr, cs_ptr):
@@ -283,10 +286,95 @@ class StreamingDecoder:
             self._bind(emissions.device)
         _check(self.L.w2l_beam_session_step(self.h, emissions.data_ptr(), n.ctypes.data, st.ctypes.data,
                                             torch.cuda.current_stream().cuda_stream), "streaming decoder step")
+        for s in np.nonzero(st)[0]:   # a slot that starts has committed nothing
+            self._forget(int(s))
 
-    def result(self, nbest=1, max_len=None, max_words=None):
+    def _forget(self, slot):
+        if self._done is not None:
+            self._done[slot] = (np.zeros(0, np.int32), np.zeros(0, np.int32))
+
+    def committed(self, slot):
+        """(labels, words) a slot has committed since its start, int32 numpy arrays (words is empty without a lexicon)"""
+        if not 0 <= int(slot) < self.slots:
+            raise _lib.W2LInvalidArgument(f"StreamingDecoder: no slot {slot}")
+        if self._done is None:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32)
+        return self._done[int(slot)]
+
+    def commit(self, slots=None):
+        """Commits what can no longer change (w2l_beam_session_commit: the labels above the deepest common ancestor of all beam
+        entries but its own) and compacts the slots' prefix tables, which gives back most of the max_frames budget.  slots: None =
+        every started slot, else an iterable of slot numbers.  Returns a list with one (labels, words) pair of int32 numpy arrays
+        per slot: what THIS call committed (empty for a slot that was not asked or had nothing).  The decoder keeps the total per
+        slot (committed()); result() then returns tails, result(full=True) the whole rows.  Synchronises: the one call that does.
+        self.live[s] is the node count of slot s's table after its last commit."""
+        if self._state is None:
+            self._bind(self.device)
+        S, lex = self.slots, self.variant == BEAM_LEX
+        if self._done is None:
+            self._done = [(np.zeros(0, np.int32), np.zeros(0, np.int32)) for _ in range(S)]
+            self.live = np.zeros(S, np.int32)
+        flags = None
+        if slots is not None:
+            flags = np.zeros(S, np.int32)
+            for s in slots:
+                if not 0 <= int(s) < S:
+                    raise _lib.W2LInvalidArgument(f"StreamingDecoder: no slot {s}")
+                flags[int(s)] = 1
+        if self._scratch is None:
+            nbytes = self.L.w2l_beam_session_commit_bytes(self.h)
+            self._scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self._state.device)
+        # no commit is longer than the labels a slot still holds: its frames less what it has committed
+        max_len = max([1] + [self.frames(s) - len(self._done[s][0]) for s in range(S)])
+        dev = self._state.device
+        labels = torch.empty(S, max_len, dtype=torch.int32, device=dev)
+        words = torch.empty(S, max_len, dtype=torch.int32, device=dev) if lex else None
+        nl, nw, live = np.zeros(S, np.int32), np.zeros(S, np.int32), np.zeros(S, np.int32)
+        _check(self.L.w2l_beam_session_commit(self.h, flags.ctypes.data if flags is not None else None, self._scratch.data_ptr(),
+                                              self._scratch.numel(), max_len, labels.data_ptr(), max_len,
+                                              words.data_ptr() if lex else None, nl.ctypes.data, nw.ctypes.data, live.ctypes.data,
+                                              torch.cuda.current_stream().cuda_stream), "streaming decoder commit")
+        hl = labels.cpu().numpy() if nl.any() else None
+        hw = words.cpu().numpy() if lex and nw.any() else None
+        out = []
+        for s in range(S):
+            a = hl[s, :nl[s]].copy() if nl[s] else np.zeros(0, np.int32)
+            b = hw[s, :nw[s]].copy() if lex and nw[s] else np.zeros(0, np.int32)
+            out.append((a, b))
+            if nl[s] or nw[s]:
+                self._done[s] = (np.concatenate([self._done[s][0], a]), np.concatenate([self._done[s][1], b]))
+        self.live = live
+        return out
+
+    def _full(self, slot_rows, lengths, done, width):
+        """committed ++ tail for every live row of one field ([S][nbest][.]); empty rows (length -1) stay empty"""
+        S, M, L = slot_rows.shape
+        full = torch.full((S, M, width + L), -1, dtype=torch.int32, device=slot_rows.device)
+        total = lengths.clone()
+        for s in range(S):
+            c = len(done[s])
+            live = lengths[s] >= 0
+            full[s, :, c:c + L] = slot_rows[s]
+            if c:
+                full[s, :, :c] = torch.from_numpy(done[s]).to(slot_rows.device)
+                total[s] = torch.where(live, lengths[s] + c, lengths[s])
+            full[s, ~live] = -1
+        return full, total
+
+    def result(self, nbest=1, max_len=None, max_words=None, full=False):
         """the tuple ctc_beam_search returns for this variant, one row block per slot ([S][nbest]...), for the frames fed so far;
-        changes nothing.  max_len defaults to max_frames, max_words to max_len."""
+        changes nothing.  max_len defaults to max_frames, max_words to max_len.  After commit() the rows are the TAILS behind the
+        committed labels (and words); full=True returns the whole rows instead -- committed ++ tail, lengths and word counts with
+        the committed totals added, labels / words as wide as the longest committed part plus max_len / max_words."""
+        if full:
+            r = self.result(nbest, max_len, max_words)
+            if self._done is None or not any(len(d[0]) for d in self._done):
+                return r
+            r = list(r)
+            r[0], r[1] = self._full(r[0], r[1], [d[0] for d in self._done], max(len(d[0]) for d in self._done))
+            if self.variant == BEAM_LEX:
+                r[4], r[5] = self._full(r[4], r[5], [d[1] for d in self._done], max(len(d[1]) for d in self._done))
+            return tuple(r)
         if self._state is None:
             self._bind(self.device)
         S, nbest = self.slots, int(nbest)
@@ -330,6 +418,7 @@ class StreamingDecoder:
         if self.h is None:
             return
         _check(self.L.w2l_beam_session_reset(self.h, int(slot)), "streaming decoder reset")
+        self._forget(int(slot))
 
 
 class WideStreamingDecoder(StreamingDecoder):
