@@ -558,6 +558,11 @@ FL_COMPAT_API void setMixedPrecision(const std::shared_ptr<fl::Module>& network,
 // setMixedPrecision is on; the next forward plans again (weight images and image scratch belong to the plan).  No-op for any
 // other module.
 FL_COMPAT_API void setMixedPrecisionConvolutions(const std::shared_ptr<fl::Module>& network, bool on);
+// fl_compat extension: the weight-gradient stream of a network built from an arch file (on by default).  loss.backward() enqueues
+// the fp32 weight, bias and filter gradients on a side stream the network owns and joins it into the compute stream before it
+// returns; a gradient bucket's event fires once both streams have finished the bucket.  Same results either way
+// (w2l_trainer_set_weight_grad_stream in w2l_hip.h says what stays on one stream).  No-op for any other module.
+FL_COMPAT_API void setWeightGradStream(const std::shared_ptr<fl::Module>& network, bool on);
 // fl_compat extension: forwards so far of a network built from an arch file = the position of its dropout-seed stream
 // (restored by Serializer::load; `Train fork` starts it from zero)
 FL_COMPAT_API uint32_t networkStep(const std::shared_ptr<fl::Module>& network);

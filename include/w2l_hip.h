@@ -872,6 +872,15 @@ int w2l_trainer_set_mixed_precision(void* h, int on);
 /* second level of that mode: the wide time convolutions (w2l_conv_bf16_*) on bf16 operands too.  Acts only while
  * w2l_trainer_set_mixed_precision is on.  Call before w2l_trainer_plan: a change after it drops the plan (plan and bind again). */
 int w2l_trainer_set_mixed_precision_convs(void* h, int on);
+/* Weight-gradient stream (on by default): the fp32 training backward enqueues the products that feed nothing before the optimizer
+ * -- the weight and bias gradients of the TDS blocks' Linears and of plain Linear layers, the filter gradients of the TDS and C2
+ * convolutions -- on a non-blocking side stream the network owns, and makes `stream` wait for it before
+ * w2l_trainer_forward_backward / w2l_trainer_backward return: whatever the caller enqueues on `stream` afterwards sees every
+ * gradient, and a gradient bucket's event (w2l_trainer_set_grad_buckets) fires once both streams have finished the bucket.  Same
+ * kernels, same results, bit for bit.  Stays on `stream` alone: the mixed-precision mode, and any step while
+ * w2l_profile_enable(1) is in force (the per-launch brackets time one kernel at a time).  W2L_EINVAL: null handle.
+ * Host-only, takes effect at the next backward; like every call on one handle, not concurrently with a step of it. */
+int w2l_trainer_set_weight_grad_stream(void* h, int on);
 /* slimIPL's dynamic dropout (--slimIPL_dyn_dropout, recipes/slimIPL/src/Train.cpp:1141-1168 with the recipe plugin's
  * 100h_supervised_slimipl.cpp:41-58): the probabilities the `TR` layers -- and only they -- use from the next forward on.  A
  * negative value restores that layer's arch value.  No new plan: a trainer with the override set computes, bit for bit, what a

@@ -52,6 +52,7 @@ GemmProf& gemm_prof() {
   static GemmProf p;
   return p;
 }
+bool profileEnabled() { return gemm_prof().on; }   // read by host/net.cpp: bracketed launches stay on one stream
 
 // stream-K partial-tile slabs: library-owned, ONE buffer per stream (work on a stream is
 // serialised, so launches on the same stream may share it); allocated on first use.
@@ -107,6 +108,13 @@ unsigned* sk_counters(hipStream_t s) {
     e = (unsigned*)p;
   }
   return e;
+}
+
+// the two first-use allocations of a stream, ahead of the launches that need them (host/net.cpp: when a net takes its
+// weight-gradient stream, for that stream and the caller's -- not in a later, possibly timed, step)
+void warmStreamScratch(hipStream_t s) {
+  (void)sk_scratch(s, kSkScratchBytes);
+  (void)sk_counters(s);
 }
 
 template <class AOp>

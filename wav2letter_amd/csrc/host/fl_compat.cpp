@@ -1156,6 +1156,9 @@ void setMixedPrecision(const std::shared_ptr<fl::Module>& network, bool on) {
 void setMixedPrecisionConvolutions(const std::shared_ptr<fl::Module>& network, bool on) {
   if (auto* p = plannedOf(network.get())) p->setMixedConvs(on);
 }
+void setWeightGradStream(const std::shared_ptr<fl::Module>& network, bool on) {
+  if (auto* p = plannedOf(network.get())) p->impl().setWeightGradStream(on);
+}
 uint32_t networkStep(const std::shared_ptr<fl::Module>& network) {
   auto* p = plannedOf(network.get());
   return p ? p->step() : 0;

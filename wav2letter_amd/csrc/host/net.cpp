@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <mutex>
 #include <sstream>
 
 #include "w2l_host.hpp"
@@ -406,6 +407,7 @@ struct FeedForward {
   const P *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr;   // the layer's handles
   bool joinInLin2 = true;        // fp32: the residual join rides in lin2's epilogue (forward() reports it)
   bool biasWithWeight = false;   // fp32: bias gradients out of w2l_linear_backward_weight_bias, not w2l_colsum (another summation order)
+  bool offChain = false;         // fp32: the weight / bias gradients go to the net's weight-gradient stream (weightGrad; the owner sets it)
   int M = 0, in = 0, hidden = 0;
   size_t uOff = 0, duOff = 0;
   BfLinear bl1, bl2;             // mixed precision: lin1, lin2
@@ -444,12 +446,15 @@ struct FeedForward {
     return joinInLin2;
   }
   // dw = a^T g of the Linear bl, and db = the column sums of g: out of the same launch (`rides`) or by w2l_colsum behind it
+  // fp32 with offChain: on the weight-gradient stream (Ctx::forkWeightGrad) -- a and g are complete on cx.stream by now, and the owner
+  // vouches that neither is written again before the net's backward has joined the streams
   void weightGrad(Ctx& cx, float* ar, const BfLinear& bl, const float* a, const BfImage& aImg, const float* g, const BfImage& gImg, const P& w, const P& b,
                   bool rides) const {
+    hipStream_t s = (offChain && !cx.bf16) ? cx.forkWeightGrad() : cx.stream;
     if (cx.bf16) bl.backwardWeight(cx, ar, aImg, gImg, w.g(cx), rides);
-    else if (rides) check(w2l_linear_backward_weight_bias(M, bl.in, bl.out, a, g, w.g(cx), b.g(cx), cx.stream), "bwd w + b");
-    else check(w2l_linear_backward_weight(M, bl.in, bl.out, a, g, w.g(cx), cx.stream), "bwd w");
-    if (!rides) check(w2l_colsum(g, b.g(cx), (size_t)M, bl.out, cx.stream), "bwd b");
+    else if (rides) check(w2l_linear_backward_weight_bias(M, bl.in, bl.out, a, g, w.g(cx), b.g(cx), s), "bwd w + b");
+    else check(w2l_linear_backward_weight(M, bl.in, bl.out, a, g, w.g(cx), s), "bwd w");
+    if (!rides) check(w2l_colsum(g, b.g(cx), (size_t)M, bl.out, s), "bwd b");
   }
   // dy [M][in]: the gradient of lin2's output, its dropout mask applied (dyImg: its images, mixed precision).  Writes the four parameter
   // gradients and dx = addend + du W1^T, addend the gradient that the residual join carries.  p: forward's
@@ -637,7 +642,9 @@ class Conv2DLayer : public Layer {
     } else if (bf) {
       w2lCheck(w2l_tds_conv_bf16_backward_filter_bias(&d, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, c.stream), "conv bwd filter + bias bf16");
     } else {
-      w2lCheck(w2l_conv_backward_filter(&d, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, c.stream), "conv bwd filter");
+      // off the chain (the weight-normalised filter gradient is not: w2l_weightnorm_backward below reads it): xSaved is the previous
+      // layer's output or this layer's unrolled copy of it, dym is only read from here on
+      w2lCheck(w2l_conv_backward_filter(&d, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, wn.on ? c.stream : c.forkWeightGrad()), "conv bwd filter");
     }
     const float* wt = wn.on ? arena + wn.wOff : w.w(c);
     if (needDx) {
@@ -786,7 +793,9 @@ class LinearLayer : public Layer {
         bl.backwardData(c, arena, dyImg, dx, nullptr, 1.f, nullptr, 0);
       }
     } else {
-    w2lCheck(w2l_linear_backward_weight_bias(M, in, out, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, c.stream), "linear bwd w + b");
+    // off the chain (not under WeightNorm: w2l_weightnorm_backward below reads dwt): xSaved and dym are only read from here on
+    w2lCheck(w2l_linear_backward_weight_bias(M, in, out, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, wn.on ? c.stream : c.forkWeightGrad()),
+             "linear bwd w + b");
     if (needDx) {
       dx = arena + dxOff;
       w2lCheck(w2l_linear_backward_data(M, in, out, dym, wt, dx, 0, nullptr, 1.f, c.stream), "linear bwd x");
@@ -950,6 +959,7 @@ class TDSLayer : public Layer {
     // l2 = 3600 ... 6480: profiles/r06_run24_c3_lin2_epilogue_ab.log).
     ff.joinInLin2 = l2 % 32 == 0;
     ff.biasWithWeight = true;   // the headline's fp32 bias gradients come out of the weight-gradient launch
+    ff.offChain = true;         // u, dv (ds or the masked copy in v), y1 and du are written once per step: see backward
     ff.plan(pl, "tds", M, l, l2, w1, b1, w2, b2);
     y1Img.plan(pl, M, l, true); dvImg.plan(pl, M, l);
     convImgElems = h % 16 == 0 ? w2l_tds_conv_bf16_image_elems(&d) : 0;
@@ -1011,9 +1021,12 @@ class TDSLayer : public Layer {
                                      rngStream + 2, "tds ln2 bwd");
     const float* dv = ds;
     if (pd > 0 && !maskInConvert) {
-      // dy1 buffer doubles as scratch for the masked copy (one out-of-place pass)
-      w2lCheck(w2l_dropout_copy(dy1, ds, n, pd, cx.seed, rngStream + 2, s), "tds do2 bwd");
-      dv = dy1;
+      // one out-of-place pass.  fp32: into v -- lin2's output is dead once LN2 backward has read it (always the v buffer itself, also
+      // where r2 lives in r1, which LN1 backward still needs) --, where dW2 on the weight-gradient stream may read it until the
+      // streams join; dy1, which the pair's last product overwrites, would not do.  Mixed precision: dy1 doubles as the scratch
+      float* masked = cx.bf16 ? dy1 : v;
+      w2lCheck(w2l_dropout_copy(masked, ds, n, pd, cx.seed, rngStream + 2, s), "tds do2 bwd");
+      dv = masked;
     }
     if (cx.bf16 && !dvImages) {
       // (dv may live in dy1 -- the masked copy above --, which the pair's last product overwrites: its images are taken first)
@@ -1032,7 +1045,8 @@ class TDSLayer : public Layer {
       }
       return;
     }
-    w2lCheck(w2l_conv_backward_filter(&d, xSaved, da, wc.g(cx), bc.g(cx), s), "tds conv bwd filter");
+    // off the chain: xSaved is the previous layer's output, da is only read from here on
+    w2lCheck(w2l_conv_backward_filter(&d, xSaved, da, wc.g(cx), bc.g(cx), cx.forkWeightGrad()), "tds conv bwd filter");
     if (needDx) {
       dx = ar + dxOff;
       w2lCheck(w2l_conv_backward_data_add(&d, da, wc.w(cx), dr1, dx, s), "tds conv bwd data");
@@ -1521,9 +1535,86 @@ const float* Sequential::forward(Ctx& c, float* arena, const float* xRef) {
   return cur;
 }
 
+// ---- weight-gradient stream ------------------------------------
+hipStream_t Ctx::forkWeightGrad() {
+  if (!wgStream) return stream;
+  hipCheck(hipEventRecord(wgFork, stream), "weight-gradient fork");
+  hipCheck(hipStreamWaitEvent(wgStream, wgFork, 0), "weight-gradient fork");
+  return wgStream;
+}
+
+// Side streams are handed from net to net, never destroyed: the kernel library keeps its stream-K slabs (64 MiB), tickets and
+// convolution scratch per stream handle for the life of the process, so a fresh stream per net would leave each net's behind.
+// The process holds as many as the most nets that ever trained at once on a device.
+namespace {
+std::mutex g_wgMu;
+std::vector<std::pair<int, hipStream_t>> g_wgFree;   // (device, stream)
+}  // namespace
+
+void Sequential::wgRelease() {
+  if (wgStream_) {
+    std::lock_guard<std::mutex> lk(g_wgMu);
+    g_wgFree.emplace_back(wgDev_, wgStream_);   // whatever it still runs was joined into a stream of the caller's
+  }
+  if (wgFork_) (void)hipEventDestroy(wgFork_);
+  if (wgJoin_) (void)hipEventDestroy(wgJoin_);
+  wgStream_ = nullptr; wgFork_ = wgJoin_ = nullptr; wgDev_ = -1;
+}
+Sequential::~Sequential() { wgRelease(); }
+
+// One training backward with the weight-gradient stream: hands the stream to the layers through the context, and joins it into the
+// caller's stream when backward() ends -- also when it ends by an exception, so that nothing is left in flight unjoined.
+struct Sequential::WgScope {
+  Sequential& n;
+  Ctx& c;
+  bool joined = true;
+  WgScope(Sequential& n_, Ctx& c_) : n(n_), c(c_) {
+    c.wgStream = nullptr; c.wgFork = nullptr;
+    if (!n.wgOn_ || !c.train || c.bf16 || profileEnabled()) return;
+    int dev = 0;
+    hipCheck(hipGetDevice(&dev), "weight-gradient stream");
+    if (n.wgStream_ && dev != n.wgDev_) n.wgRelease();
+    if (!n.wgStream_) {
+      {
+        std::lock_guard<std::mutex> lk(g_wgMu);
+        for (size_t i = 0; i < g_wgFree.size(); ++i)
+          if (g_wgFree[i].first == dev) { n.wgStream_ = g_wgFree[i].second; g_wgFree.erase(g_wgFree.begin() + i); break; }
+      }
+      n.wgDev_ = dev;
+      try {
+        if (!n.wgStream_) hipCheck(hipStreamCreateWithFlags(&n.wgStream_, hipStreamNonBlocking), "weight-gradient stream");
+        hipCheck(hipEventCreateWithFlags(&n.wgFork_, hipEventDisableTiming), "weight-gradient fork event");
+        hipCheck(hipEventCreateWithFlags(&n.wgJoin_, hipEventDisableTiming), "weight-gradient join event");
+      } catch (...) {
+        n.wgRelease();   // all three or none
+        throw;
+      }
+      // both streams' stream-K scratch now, in what is a warm-up step: the side stream's first product would allocate it anyway, the
+      // caller's stream would only meet a weight-gradient product -- and the allocation -- in a step bracketed by w2l_profile_enable
+      warmStreamScratch(n.wgStream_);
+      warmStreamScratch(c.stream);
+    }
+    c.wgStream = n.wgStream_; c.wgFork = n.wgFork_;
+    joined = false;
+  }
+  hipError_t joinNoThrow() {
+    if (joined) return hipSuccess;
+    joined = true;
+    hipError_t e = hipEventRecord(n.wgJoin_, n.wgStream_);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c.stream, n.wgJoin_, 0);
+    c.wgStream = nullptr; c.wgFork = nullptr;
+    return e;
+  }
+  void join() { hipCheck(joinNoThrow(), "weight-gradient join"); }
+  ~WgScope() { (void)joinNoThrow(); }
+  // gradients at and above a bucket's offset are final once BOTH streams have passed this point
+  void recordBucket(hipEvent_t ev) { hipCheck(hipEventRecord(ev, c.forkWeightGrad()), "bucket event"); }
+};
+
 void Sequential::backward(Ctx& c, float* arena, const float* dOut) {
   const float* dy = dOut;
   c.convScratch = convScratchElems_ ? bfp(arena, convScratchOff_) : nullptr;
+  WgScope wg(*this, c);
   // first layer with parameters: nothing before it needs a data gradient
   size_t firstParam = 0;
   for (size_t i = 0; i < layers_.size(); ++i) {
@@ -1535,11 +1626,13 @@ void Sequential::backward(Ctx& c, float* arena, const float* dOut) {
     float* dx = nullptr;
     bool needDx = ii > firstParam;
     layers_[ii]->backward(c, arena, dy, dx, needDx);
-    for (; nb > 0 && bOff_[nb - 1] >= layerLo_[ii]; --nb) hipCheck(hipEventRecord(bEv_[nb - 1], c.stream), "bucket event");
+    for (; nb > 0 && bOff_[nb - 1] >= layerLo_[ii]; --nb) wg.recordBucket(bEv_[nb - 1]);
     if (!needDx) break;
     dy = dx;
   }
-  for (; nb > 0; --nb) hipCheck(hipEventRecord(bEv_[nb - 1], c.stream), "bucket event");
+  for (; nb > 0; --nb) wg.recordBucket(bEv_[nb - 1]);
+  // everything the caller enqueues next -- the gradient scale, clip and optimizer, the next forward -- is ordered behind both streams
+  wg.join();
 }
 
 // ---- parameter init / import / export ----------------------------------------

@@ -449,6 +449,15 @@ W2L_API int w2l_trainer_bind_state2(void* h, float* state2) {
 }
 W2L_API int w2l_trainer_set_mixed_precision(void* h, int on) { ((Trainer*)h)->mixedPrecision = on != 0; return W2L_OK; }
 
+// the fp32 backward's weight, bias and filter gradients on the network's own side stream, joined into the caller's stream before
+// w2l_trainer_forward_backward / w2l_trainer_backward return (Sequential::setWeightGradStream; on by default).  Same results either
+// way; acts from the next backward on.
+W2L_API int w2l_trainer_set_weight_grad_stream(void* h, int on) {
+  if (!h) return W2L_EINVAL;
+  ((Trainer*)h)->net->setWeightGradStream(on != 0);
+  return W2L_OK;
+}
+
 // second level of the mixed-precision mode: the wide time convolutions (H == 1, >= 32 channels: the conv_glu recipes, the
 // Transformer front end) on bf16 operands too, wherever w2l_conv_bf16_image_elems has a kernel.  It acts only while
 // w2l_trainer_set_mixed_precision is on.  The plan holds the layers' weight images and the image scratch: call before

@@ -103,6 +103,14 @@ struct Ctx {
   // weightsReady == false (the first step after a bind or a refresh) -- every later pass reads them as they are.
   bool smallM = false;
   bool weightsReady = false;
+  // weight-gradient stream: set by Sequential::backward for the length of one training backward, null otherwise.
+  // A product that feeds nothing before the optimizer (a weight, bias or filter gradient) is enqueued on the stream this hands
+  // back: the side stream, after it has been made to wait for everything enqueued on `stream` so far -- or `stream` itself when
+  // the overlap is off, so a call site has one code path.  The operands must stay unwritten, and the result unread, until
+  // Sequential::backward has joined the two streams.
+  hipStream_t wgStream = nullptr;
+  hipEvent_t wgFork = nullptr;
+  hipStream_t forkWeightGrad();
 };
 
 // What a layer needs from the chunked streaming forward (host/stream.cpp).  A frame-local layer maps frame t to frame t and
@@ -157,6 +165,10 @@ class Layer {
 
 class Sequential {
  public:
+  Sequential() {}
+  ~Sequential();
+  Sequential(const Sequential&) = delete;
+  Sequential& operator=(const Sequential&) = delete;
   void add(std::shared_ptr<Layer> l) { layers_.push_back(std::move(l)); }
   size_t size() const { return layers_.size(); }
   Layer& at(size_t i) { return *layers_[i]; }
@@ -190,6 +202,16 @@ class Sequential {
   // under the backward pass of the earlier layers.  Empty vectors switch the hooks off.
   void setGradBuckets(std::vector<size_t> offsets, std::vector<hipEvent_t> events) { bOff_ = std::move(offsets); bEv_ = std::move(events); }
 
+  // Weight-gradient stream: the fp32 training backward enqueues the products that feed nothing before the optimizer
+  // -- the weight / bias gradients of the TDS blocks' two Linears and of a plain Linear, the filter gradients of the TDS and C2
+  // convolutions -- on a side stream that the net owns, and joins it into the caller's stream before backward() returns; with gradient
+  // buckets, a bucket's event is recorded once BOTH streams have finished it.  Same kernels, same operands, same results.  The
+  // mixed-precision pass, and any pass while the per-launch event brackets of w2l_profile_enable are on, stays on the caller's stream.
+  // The first backward that uses the side stream allocates the stream-K scratch of BOTH streams (the caller's would otherwise meet
+  // its first weight-gradient product, and the 64 MiB allocation, in a bracketed step): one warm-up step before timing, as before.
+  void setWeightGradStream(bool on) { wgOn_ = on; }
+  bool weightGradStream() const { return wgOn_; }
+
   void initParams(float* hostParams, uint64_t seed) const;            // Flashlight-style init, internal layout
   void importParam(size_t i, const float* ref, float* hostParams) const;  // reference layout -> internal
   void exportParam(size_t i, const float* hostArena, float* ref) const;   // internal -> reference layout
@@ -208,7 +230,16 @@ class Sequential {
   std::vector<size_t> layerLo_;  // per layer: arena offset of its first parameter (paramFloats_ if it has none after it)
   std::vector<size_t> bOff_;
   std::vector<hipEvent_t> bEv_;
+  // weight-gradient stream: taken by the first backward that uses it, handed back to the process's free list with the net
+  struct WgScope;
+  bool wgOn_ = true;
+  int wgDev_ = -1;
+  hipStream_t wgStream_ = nullptr;
+  hipEvent_t wgFork_ = nullptr, wgJoin_ = nullptr;
+  void wgRelease();
 };
+bool profileEnabled();   // gemm.hip: the per-launch event brackets of w2l_profile_enable are on
+void warmStreamScratch(hipStream_t s);   // gemm.hip: allocates the stream's stream-K slabs and tickets now, not at their first use
 
 // arch file -> Sequential (throws std::invalid_argument like the reference's builder)
 std::shared_ptr<Sequential> buildSequentialModule(const std::string& archfile, int64_t nFeatures, int64_t nClasses);

@@ -47,6 +47,7 @@ def _lib_tr():
         L.w2l_trainer_set_step.argtypes = [vp, u32]
         L.w2l_trainer_set_mixed_precision.argtypes = [vp, i]
         L.w2l_trainer_set_mixed_precision_convs.argtypes = [vp, i]
+        L.w2l_trainer_set_weight_grad_stream.argtypes = [vp, i]
         L.w2l_trainer_set_optimizer.argtypes = [vp, i, i]
         L.w2l_trainer_set_dropout.argtypes = [vp, d, d]
         L.w2l_trainer_bind_state2.argtypes = [vp, vp]
@@ -333,6 +334,11 @@ class Trainer:
             self._eval_plans.clear()
             if self.B:
                 self.plan(self.B, self.T, self.Lt)
+
+    def set_weight_grad_stream(self, on=True):
+        """fp32 backward: the weight, bias and filter gradients on the network's own side stream, joined into the step's stream
+        before forward_backward returns (on by default; same results either way, see w2l_trainer_set_weight_grad_stream)"""
+        _check(self.L.w2l_trainer_set_weight_grad_stream(self.h, int(bool(on))), "weight-gradient stream")
 
     def set_optimizer(self, netoptim="sgd", critoptim="sgd"):
         """--netoptim / --critoptim of the reference Trainer (Train.cpp:577-582): "sgd" (momentum) "adagrad" or "adadelta" (rho 0.9, eps 1e-8:
