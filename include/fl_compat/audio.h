@@ -172,6 +172,12 @@ class Mfsc {
   int frameSize() const { return N_; }
   int frameStride() const { return S_; }
   int numFrames(long nSamples) const { return nSamples < N_ ? 0 : (int)(1 + (nSamples - N_) / S_); }
+  // the tables and the geometry behind apply(), as fl::pkg::speech::StreamingFeatures binds them (read only)
+  const FeatureParams& params() const { return p_; }
+  int numBins() const { return nb_; }                      // nfft / 2 + 1
+  int spectrumRows() const { return ld_; }                 // rows of melTable(): numBins() padded to whole K tiles
+  const af::array& spectrumTable() const { return G_; }    // dims (2 numBins, frameSize): memory [frameSize][real | imaginary]
+  const af::array& melTable() const { return H_; }         // dims (numFilterbankChans, spectrumRows)
 
   // audio: device, dims (ns, B) = memory [B][ns] with ns a multiple of the frame stride -> features dims (T, F, 1, B)
   af::array apply(const af::array& audio) const {

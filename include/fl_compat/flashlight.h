@@ -106,6 +106,11 @@ FL_COMPAT_API void sync();          // wait for the stream every fl_compat call 
 }  // namespace af
 
 namespace fl {
+namespace lib {
+namespace audio {
+class Mfsc;   // fl_compat/audio.h
+}
+}
 
 FL_COMPAT_API void* currentStream();                 // hipStream_t the facade enqueues on (default: a private non-blocking stream)
 FL_COMPAT_API void setCurrentStream(void* stream);
@@ -531,6 +536,45 @@ class FL_COMPAT_API StreamingSession {
   void* h_ = nullptr;
   int slots_ = 0, maxChunk_ = 0, maxOut_ = 0, nFeat_ = 0, nLabel_ = 0;
   bool mixed_ = false;
+};
+
+// fl_compat extension: the streaming log-mel front end (w2l_feat_session_*; the contract is in w2l_hip.h), the first module of the
+// chain StreamingFeatures -> StreamingSession -> StreamingDecoder.  Built from an fl::lib::audio::Mfsc (fl_compat/audio.h), whose
+// tables and geometry it binds and which it keeps a copy of; `slots` concurrent streams, at most maxSamples new samples per slot
+// and step.  For any split of an utterance into chunks the concatenated frames are the same bit for bit, and they equal
+// Mfsc::apply of the whole utterance up to summation order.  No normalisation.  A geometry beyond the kernel's bounds
+// (frameSize 512, 257 bins, 128 filters) throws std::runtime_error naming the field; any other refused argument
+// std::invalid_argument.
+class FL_COMPAT_API StreamingFeatures {
+ public:
+  StreamingFeatures(const fl::lib::audio::Mfsc& mfsc, int slots, int maxSamples);
+  ~StreamingFeatures();
+  StreamingFeatures(const StreamingFeatures&) = delete;
+  StreamingFeatures& operator=(const StreamingFeatures&) = delete;
+  int slots() const { return slots_; }
+  int maxSamples() const { return maxSamples_; }
+  int maxOut() const { return maxOut_; }         // frames one step can return per slot: a StreamingSession's maxChunk
+  int numFeatures() const { return nFeat_; }
+  // pcm (maxSamples, slots) f32: the first counts[s] samples of slot s are used.  start[s]: the slot begins a new utterance;
+  // finish[s]: these samples are its last, what does not fill a frame is dropped (either vector may be empty = all 0).  Returns
+  // the features (maxOut, NFEAT, 1, slots) -- a view of the session's state, valid until the next step, which
+  // StreamingSession::step takes as it is -- and fills nOut[s], the new frames of slot s (host arithmetic: the step enqueues on
+  // fl::currentStream() and does not synchronise).  stepInt16: the same over device int16 samples [slots][maxSamples], scaled by
+  // exactly 1 / 32768.
+  af::array step(const af::array& pcm, const std::vector<int>& counts, const std::vector<int>& start, const std::vector<int>& finish,
+                 std::vector<int>& nOut);
+  af::array stepInt16(const int16_t* pcmDevice, const std::vector<int>& counts, const std::vector<int>& start, const std::vector<int>& finish,
+                      std::vector<int>& nOut);
+  void slotState(int slot, bool& active, int& carrySamples) const;
+  void reset(int slot);                          // closes a slot and discards its carry
+
+ private:
+  af::array run(const void* pcm, int pcmType, const std::vector<int>& counts, const std::vector<int>& start, const std::vector<int>& finish,
+                std::vector<int>& nOut);
+  af::array G_, H_;
+  std::shared_ptr<void> state_;
+  void* h_ = nullptr;
+  int slots_ = 0, maxSamples_ = 0, maxOut_ = 0, nFeat_ = 0;
 };
 
 class FL_COMPAT_API SequenceCriterion : public fl::Container {

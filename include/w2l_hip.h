@@ -1138,6 +1138,60 @@ int w2l_beam_session_commit(void* session, const int* h_commit, void* scratch, s
                             int maxWords, int* words, int* h_nLabels, int* h_nWords, int* h_live, w2l_stream_t stream);
 int w2l_beam_session_committed(void* session, int slot, int* h_labels, int* h_words);
 
+/* ---- streaming log-mel front end (csrc/host/feat_stream.cpp, csrc/feat_stream.hip) ----------------------------
+ * A feature session turns audio chunks of `slots` concurrent streams into MFSC frames on the device, one launch per step: the
+ * first module of the reference's streaming pipeline (LogMelFeature: buffer the samples, produce numFrames(buffered) frames,
+ * consume numFrames x stride samples, keep the rest).  For any utterance and any split of it into chunks the concatenated frames
+ * are the same, bit for bit, and equal the whole-utterance Mfsc up to summation order.  No normalisation: as before, that is the
+ * caller's.  The protocol is w2l_stream_*'s:
+ *   w2l_feat_desc                   what Mfsc derives: frameSize N and frameStride St in samples, nbins, ldSpec (rows of H), numFilters
+ *                                   F, usePower, melFloor.  Accepted: 1 <= St <= N <= 512, nbins <= 257, nbins <= ldSpec, F <= 128,
+ *                                   melFloor > 0.  Larger: W2L_EUNSUPPORTED, w2l_host_last_error() names the field; sizes below 1,
+ *                                   St > N, nbins > ldSpec, melFloor <= 0: W2L_EINVAL.
+ *   w2l_feat_session_query          maxOut = (maxSamples - 1) / St + 1 (the frames N - 1 carried and maxSamples new samples can
+ *                                   hold) and the state bytes.  Host arithmetic, like create, counts, slot_state and reset.
+ *   w2l_feat_session_bind           G: device [N][2 nbins] (real | imaginary columns), H: device [ldSpec][F], exactly as Mfsc holds
+ *                                   them (the session's "weights": it keeps the pointers); state: device buffer of
+ *                                   w2l_feat_session_state_bytes, 256-byte aligned, no initialisation needed.  Bind zeroes the
+ *                                   output area (and waits for that).
+ *   w2l_feat_session_step           pcm: device [S][maxSamples], W2L_PCM_F32 float32 or W2L_PCM_S16 int16 (scaled by exactly
+ *                                   1 / 32768), the first n[s] samples of slot s are used, 0 <= n[s] <= maxSamples.  n, start,
+ *                                   finish (either flag array may be NULL) and nOut are HOST int [S].  Per slot: start empties the
+ *                                   carry; have = carry + n; nOut = have < N ? 0 : 1 + (have - N) / St; the slot consumes nOut St
+ *                                   samples and carries the rest (< N); finish drops the rest after the step's frames and closes
+ *                                   the slot, as the whole-utterance Mfsc drops the same tail.  *out: device [S][F][maxOut] inside
+ *                                   the state -- the layout w2l_stream_step takes as x, so a session with maxChunk == maxOut
+ *                                   consumes (*out, nOut) as they are.  Columns at or beyond nOut[s] are not written.  One launch
+ *                                   and one async copy of the count table (pinned ring); never synchronises.
+ *   w2l_feat_session_counts         the bookkeeping of a step alone (advances the host state exactly as a step would)
+ *   w2l_feat_session_slot_state     active flag and carried sample count of a slot
+ *   w2l_feat_session_reset          closes a slot and discards its carry
+ * Refused with W2L_EINVAL before anything is enqueued or any count moves: null pointers, n[s] outside 0..maxSamples, a slot fed
+ * or finished before it was started, a step before bind.
+ * w2l_feat_stream_frames is the kernel behind a step (tab: device int [S][4] = carried samples, new samples, frames, flags with
+ * bit 0 = the current carry buffer and bit 1 = the slot has work; the next carry goes to the other buffer);
+ * w2l_feat_stream_tile_rows the frames one workgroup computes. */
+enum { W2L_PCM_F32 = 0, W2L_PCM_S16 = 1 };
+typedef struct w2l_feat_desc {
+  int frameSize, frameStride, nbins, ldSpec, numFilters, usePower;
+  float melFloor;
+} w2l_feat_desc;
+int w2l_feat_session_query(const w2l_feat_desc* desc, int slots, int maxSamples, int* maxOut, size_t* stateBytes);
+int w2l_feat_session_create(const w2l_feat_desc* desc, int slots, int maxSamples, void** session);
+void w2l_feat_session_destroy(void* session);
+int w2l_feat_session_max_out(void* session);
+size_t w2l_feat_session_state_bytes(void* session);
+int w2l_feat_session_bind(void* session, const float* G, const float* H, void* state, size_t stateBytes);
+int w2l_feat_session_counts(void* session, const int* n, const int* start, const int* finish, int* nOut);
+int w2l_feat_session_step(void* session, const void* pcm, int pcmType, const int* n, const int* start, const int* finish,
+                          const float** out, int* nOut, w2l_stream_t stream);
+int w2l_feat_session_slot_state(void* session, int slot, int* active, int* carrySamples);
+int w2l_feat_session_reset(void* session, int slot);
+int w2l_feat_stream_tile_rows(void);
+int w2l_feat_stream_frames(const w2l_feat_desc* desc, const float* G, const float* H, const void* pcm, int pcmType, int maxSamples,
+                           const int* tab, float* carry0, float* carry1, int carryLd, float* out, int maxOut, int slots,
+                           w2l_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

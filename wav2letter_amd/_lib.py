@@ -258,6 +258,18 @@ class _SIGS:
     w2l_beam_session_commit_bytes = (_sz, [_p])
     w2l_beam_session_commit = (_i, [_p, _p, _p, _sz, _i, _p, _i, _p, _p, _p, _p, _p])
     w2l_beam_session_committed = (_i, [_p, _i, _p, _p])
+    w2l_feat_session_query = (_i, [_p, _i, _i, _p, _p])
+    w2l_feat_session_create = (_i, [_p, _i, _i, _p])
+    w2l_feat_session_destroy = (None, [_p])
+    w2l_feat_session_max_out = (_i, [_p])
+    w2l_feat_session_state_bytes = (_sz, [_p])
+    w2l_feat_session_bind = (_i, [_p, _p, _p, _p, _sz])
+    w2l_feat_session_counts = (_i, [_p, _p, _p, _p, _p])
+    w2l_feat_session_step = (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p])
+    w2l_feat_session_slot_state = (_i, [_p, _i, _p, _p])
+    w2l_feat_session_reset = (_i, [_p, _i])
+    w2l_feat_stream_tile_rows = (_i, [])
+    w2l_feat_stream_frames = (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _i, _p, _i, _i, _p])
 
 
 class ConvDesc(C.Structure):
@@ -289,6 +301,10 @@ class BeamSessionDesc(C.Structure):  # w2l_beam_session_desc
                 [(n, C.c_int) for n in ("logAdd", "normalize", "variant")] +
                 [("lm", C.c_void_p), ("lmHasEos", C.c_int), ("lmWeight", C.c_float), ("classScore", C.c_void_p),
                  ("eosScore", C.c_float), ("lexicon", C.c_void_p), ("wordScore", C.c_float)])
+
+
+class FeatDesc(C.Structure):  # w2l_feat_desc
+    _fields_ = [(n, C.c_int) for n in ("frameSize", "frameStride", "nbins", "ldSpec", "numFilters", "usePower")] + [("melFloor", C.c_float)]
 
 
 class AttnFusedDesc(C.Structure):  # w2l_attn_fused_desc

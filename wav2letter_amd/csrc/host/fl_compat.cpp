@@ -15,6 +15,7 @@
 #include <unordered_set>
 
 #include "../../../include/fl_compat/flashlight.h"
+#include "../../../include/fl_compat/audio.h"
 #include "../../../include/fl_compat/lexicon.h"
 #include "../../../include/fl_compat/lm.h"
 #include "w2l_host.hpp"
@@ -1057,6 +1058,59 @@ void StreamingSession::refreshWeights() {
 }
 void StreamingSession::reset(int slot) {
   if (w2l_stream_reset(h_, slot) != W2L_OK) throw std::invalid_argument(std::string("StreamingSession::reset: ") + w2l_host_last_error());
+}
+
+StreamingFeatures::StreamingFeatures(const fl::lib::audio::Mfsc& mfsc, int slots, int maxSamples)
+    : G_(mfsc.spectrumTable()), H_(mfsc.melTable()), slots_(slots), maxSamples_(maxSamples) {
+  const fl::lib::audio::FeatureParams& p = mfsc.params();
+  w2l_feat_desc d;
+  d.frameSize = mfsc.frameSize(); d.frameStride = mfsc.frameStride(); d.nbins = mfsc.numBins(); d.ldSpec = mfsc.spectrumRows();
+  d.numFilters = p.numFilterbankChans; d.usePower = p.usePower ? 1 : 0; d.melFloor = p.melFloor;
+  nFeat_ = d.numFilters;
+  const int st = w2l_feat_session_create(&d, slots, maxSamples, &h_);
+  if (st == W2L_EINVAL) throw std::invalid_argument(std::string("StreamingFeatures: ") + w2l_host_last_error());
+  if (st != W2L_OK) throw std::runtime_error(std::string("StreamingFeatures: ") + w2l_host_last_error());
+  maxOut_ = w2l_feat_session_max_out(h_);
+  const size_t bytes = w2l_feat_session_state_bytes(h_);
+  state_ = devAlloc(bytes);
+  if (w2l_feat_session_bind(h_, G_.device<float>(), H_.device<float>(), state_.get(), bytes) != W2L_OK) {
+    const std::string msg = w2l_host_last_error();
+    w2l_feat_session_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error("StreamingFeatures: " + msg);
+  }
+}
+StreamingFeatures::~StreamingFeatures() { if (h_) w2l_feat_session_destroy(h_); }
+af::array StreamingFeatures::run(const void* pcm, int pcmType, const std::vector<int>& counts, const std::vector<int>& start,
+                                 const std::vector<int>& finish, std::vector<int>& nOut) {
+  if ((int)counts.size() != slots_ || (!start.empty() && (int)start.size() != slots_) || (!finish.empty() && (int)finish.size() != slots_))
+    throw std::invalid_argument("StreamingFeatures::step: one count / flag per slot");
+  nOut.assign(slots_, 0);
+  const float* out = nullptr;
+  const int st = w2l_feat_session_step(h_, pcm, pcmType, counts.data(), start.empty() ? nullptr : start.data(),
+                                       finish.empty() ? nullptr : finish.data(), &out, nOut.data(), S());
+  if (st == W2L_EINVAL) throw std::invalid_argument(std::string("StreamingFeatures::step: ") + w2l_host_last_error());
+  if (st != W2L_OK) throw std::runtime_error(std::string("StreamingFeatures::step: ") + w2l_host_last_error());
+  return af::array::wrap((void*)out, af::dim4(maxOut_, nFeat_, 1, slots_), af::f32, state_);
+}
+af::array StreamingFeatures::step(const af::array& pcm, const std::vector<int>& counts, const std::vector<int>& start,
+                                  const std::vector<int>& finish, std::vector<int>& nOut) {
+  if (pcm.type() != af::f32 || pcm.dims(0) != maxSamples_ || pcm.dims(1) * pcm.dims(2) * pcm.dims(3) != slots_)
+    throw std::invalid_argument("StreamingFeatures::step: pcm must be f32 (maxSamples, slots)");
+  return run(pcm.device<float>(), W2L_PCM_F32, counts, start, finish, nOut);
+}
+af::array StreamingFeatures::stepInt16(const int16_t* pcmDevice, const std::vector<int>& counts, const std::vector<int>& start,
+                                       const std::vector<int>& finish, std::vector<int>& nOut) {
+  return run(pcmDevice, W2L_PCM_S16, counts, start, finish, nOut);
+}
+void StreamingFeatures::slotState(int slot, bool& active, int& carrySamples) const {
+  int a = 0;
+  if (w2l_feat_session_slot_state(h_, slot, &a, &carrySamples) != W2L_OK)
+    throw std::invalid_argument(std::string("StreamingFeatures::slotState: ") + w2l_host_last_error());
+  active = a != 0;
+}
+void StreamingFeatures::reset(int slot) {
+  if (w2l_feat_session_reset(h_, slot) != W2L_OK) throw std::invalid_argument(std::string("StreamingFeatures::reset: ") + w2l_host_last_error());
 }
 
 }  // namespace speech

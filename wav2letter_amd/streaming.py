@@ -3,7 +3,7 @@
 A StreamingSession runs a trained network on audio as it arrives: `slots` concurrent streams, at most `max_chunk` input
 frames per slot and step.  For any utterance and any split of it into chunks the concatenated emissions equal
 Trainer.forward(train=False) of that utterance alone (fp32 parity), and the frame count equals its Tout.  Feature extraction
-and normalisation stay with the caller.
+normalisation stays with the caller; StreamingFeatures (below) is the feature extraction.
 
 mixed_precision=True makes it a bf16 session over a mixed-precision trainer (Trainer.set_mixed_precision): bf16 operands for the
 fl::Linear products and the TDS convolutions, everything else fp32, equal to the trainer's own mixed-precision eval forward within
@@ -14,6 +14,10 @@ trainer, which reads the trainer's live arena at every step.
 A StreamingDecoder (csrc/criterion_beam_stream.hpp) is the CTC beam search continued chunk by chunk over such emissions: it
 takes StreamingSession.step's output directly, and its result after any number of frames is, bit for bit, ctc_beam_search of
 those frames alone.
+
+StreamingFeatures (csrc/host/feat_stream.cpp, csrc/feat_stream.hip) is the front of that chain: PCM chunks in, features.Mfsc's
+log-mel frames out, one launch per step, the same frames bit for bit however the audio was chunked.  Its step() output is what
+StreamingSession.step takes when max_chunk == StreamingFeatures.max_out.
 """
 import ctypes as C
 
@@ -165,6 +169,95 @@ class StreamingSession:
     def refresh_weights(self):
         """a bf16 session: the next step copies the parameters and writes the bf16 weight images again (host only; a no-op for fp32)"""
         _check(self.L.w2l_stream_refresh_weights(self.h), "stream refresh weights")
+
+
+PCM_F32, PCM_S16 = 0, 1   # W2L_PCM_F32 / W2L_PCM_S16
+
+
+def feat_desc(mfsc):
+    """the w2l_feat_desc of a features.Mfsc"""
+    return _lib.FeatDesc(frameSize=mfsc.N, frameStride=mfsc.S, nbins=mfsc.nb, ldSpec=mfsc.ld, numFilters=mfsc.F,
+                         usePower=int(mfsc.use_power), melFloor=mfsc.floor)
+
+
+class StreamingFeatures:
+    """StreamingFeatures(mfsc, slots, max_samples): features.Mfsc on audio as it arrives (the contract is in include/w2l_hip.h,
+    w2l_feat_session_*).  `slots` concurrent streams, at most max_samples new samples per slot and step; the session uses the
+    Mfsc's own tables (mfsc.G, mfsc.H) and geometry.  A slot buffers what does not fill a frame yet (fewer than mfsc.N samples);
+    finish drops that rest, as Mfsc drops the same tail of a whole utterance.  No normalisation.  Creation is host arithmetic
+    (geometries beyond the kernel's bounds raise W2LUnsupported naming the field); the device state is allocated at the first
+    step."""
+
+    def __init__(self, mfsc, slots, max_samples):
+        self.L = _lib.lib()
+        self.mfsc = mfsc   # kept alive: the session reads its tables
+        self.slots, self.max_samples, self.nfeat = int(slots), int(max_samples), int(mfsc.F)
+        self._desc = feat_desc(mfsc)
+        self.h = C.c_void_p(0)
+        _check(self.L.w2l_feat_session_create(C.byref(self._desc), self.slots, self.max_samples, C.byref(self.h)), "streaming features")
+        self.max_out = self.L.w2l_feat_session_max_out(self.h)
+        self.state_bytes = self.L.w2l_feat_session_state_bytes(self.h)
+        self._state = None
+        self.feats = None   # the view step() returned last
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.L.w2l_feat_session_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def _bind(self):
+        G, H = self.mfsc.G, self.mfsc.H
+        if not (G.is_cuda and H.is_cuda and G.is_contiguous() and H.is_contiguous()):
+            raise _lib.W2LInvalidArgument("streaming features: the Mfsc's tables must be contiguous and on the device")
+        self._state = torch.empty(max(self.state_bytes, 256), dtype=torch.uint8, device=G.device)
+        _check(self.L.w2l_feat_session_bind(self.h, G.data_ptr(), H.data_ptr(), self._state.data_ptr(), self._state.numel()),
+               "streaming features bind")
+
+    def counts(self, counts, start=None, finish=None):
+        """the integer bookkeeping of a step alone (host arithmetic; advances the session's counts as a step would): n_out [S]"""
+        S = self.slots
+        n, st, fi = _flags(counts, S, "counts"), _flags(start, S, "start"), _flags(finish, S, "finish")
+        n_out = np.zeros(S, np.int32)
+        _check(self.L.w2l_feat_session_counts(self.h, n.ctypes.data, st.ctypes.data, fi.ctypes.data, n_out.ctypes.data),
+               "streaming features counts")
+        return n_out
+
+    def slot_state(self, slot):
+        """(active, carried samples) of a slot: host state"""
+        act, carry = C.c_int(0), C.c_int(0)
+        _check(self.L.w2l_feat_session_slot_state(self.h, int(slot), C.byref(act), C.byref(carry)), "streaming features slot state")
+        return bool(act.value), carry.value
+
+    def step(self, pcm, counts, start=None, finish=None):
+        """pcm: [S][max_samples] float32 or int16 (scaled by 1 / 32768) on the device, the first counts[s] samples of slot s are
+        used; counts / start / finish: one int per slot on the host.  Returns (feats, n_out): feats [S][NFEAT][max_out] is a view
+        of the session's state, valid until the next step, whose columns [0, n_out[s]) of slot s are that slot's new frames (the
+        columns beyond keep what they held); n_out is a numpy int32 array computed on the host -- the step does not synchronise."""
+        S = self.slots
+        if not (torch.is_tensor(pcm) and pcm.is_cuda and pcm.dtype in (torch.float32, torch.int16) and pcm.is_contiguous()
+                and tuple(pcm.shape) == (S, self.max_samples)):
+            raise _lib.W2LInvalidArgument(
+                f"pcm must be a contiguous float32 or int16 CUDA tensor [S={S}][max_samples={self.max_samples}], got "
+                f"{(tuple(pcm.shape), pcm.dtype) if torch.is_tensor(pcm) else type(pcm)}")
+        n, st, fi = _flags(counts, S, "counts"), _flags(start, S, "start"), _flags(finish, S, "finish")
+        if self._state is None:
+            self._bind()
+        n_out = np.zeros(S, np.int32)
+        ptr = C.c_void_p(0)
+        _check(self.L.w2l_feat_session_step(self.h, pcm.data_ptr(), PCM_S16 if pcm.dtype == torch.int16 else PCM_F32, n.ctypes.data,
+                                            st.ctypes.data, fi.ctypes.data, C.byref(ptr), n_out.ctypes.data,
+                                            torch.cuda.current_stream().cuda_stream), "streaming features step")
+        off = ptr.value - self._state.data_ptr()
+        numel = S * self.nfeat * self.max_out
+        self.feats = self._state[off:off + 4 * numel].view(torch.float32).view(S, self.nfeat, self.max_out)
+        return self.feats, n_out
+
+    def reset(self, slot):
+        """closes a slot and discards its carry"""
+        _check(self.L.w2l_feat_session_reset(self.h, int(slot)), "streaming features reset")
 
 
 BEAM_PLAIN, BEAM_LM, BEAM_LEX = 0, 1, 2
