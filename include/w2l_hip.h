@@ -728,7 +728,8 @@ int w2l_attn_key_lengths(const float* inputSizes, int B, int Tin, int Tk, int* k
  * size the Tin input frames correspond to and replaces max size as the denominator */
 int w2l_attn_key_lengths_full(const float* inputSizes, const float* fullSize, int B, int Tin, int Tk, int* keyLen,
                               w2l_stream_t stream);
-/* dS (in: dL/dP) -> dL/dS (pre-scale scores) in place; dR (may be NULL) receives the skewed copy, zeros elsewhere */
+/* dS (in: dL/dP) -> dL/dS (pre-scale scores) in place; dR [B*T*H][ldr] (may be NULL) receives the skewed copy, zeros elsewhere:
+ * every column of a row up to ldr is written, so the columns from W to ldr are zero padding that belongs to dR */
 int w2l_attn_softmax_backward(const float* P, float* dS, float* dR, int B, int H, int T, int ldr, int rlo, int W, int n0,
                               float scale, w2l_stream_t stream);
 /* fl::Pool2D(w, 1, stride, 1, 0, 0, MAX) over time on frame-major x[B][T][F] -> y[B][(T-w)/stride+1][F] (arch token `M`,

@@ -134,6 +134,8 @@ __global__ __launch_bounds__(256, 2) void gemm128h_kernel(GOp aop, GOp bop, Gemm
       }
       out.C = grp.c[grpIdx];
       out.bias = grp.bias[grpIdx];
+      // single entries of bias may be null: the dword epilogue (gemm128_epilogue) reads out.bias whenever EPI_BIAS is set
+      out.epi = out.bias ? (out.epi | EPI_BIAS) : (out.epi & ~EPI_BIAS);
     }
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
     if ((out.epi & EPI_BIAS) && out.bias) {
