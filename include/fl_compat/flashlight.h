@@ -577,6 +577,40 @@ class FL_COMPAT_API StreamingFeatures {
   int slots_ = 0, maxSamples_ = 0, maxOut_ = 0, nFeat_ = 0;
 };
 
+// fl_compat extension: LocalNorm, the windowed feature normalisation of the streaming recipe (w2l_local_norm, w2l_norm_session_*;
+// the contract is in w2l_hip.h).  localNormalize: features (T, NFEAT, 1, B) f32 -> the same shape; frame t of utterance b, which
+// has frames[b] frames (an empty vector: T each), is normalised with one mean and deviation over all features of frames
+// max(0, t - left) .. min(frames[b] - 1, t + right); frames at or beyond frames[b] come out zero.  Two launches on
+// fl::currentStream(), one small copy of `frames`; a refused argument throws std::invalid_argument, a window above 65536 frames
+// or NFEAT above 4096 std::runtime_error.
+FL_COMPAT_API af::array localNormalize(const af::array& features, const std::vector<int>& frames, int left, int right);
+
+// StreamingLocalNorm is the reference's streaming::LocalNorm(nFeat, left, 0) between StreamingFeatures and StreamingSession:
+// `slots` concurrent streams, at most maxChunk new frames per slot and step, and for any split of an utterance's frames into
+// chunks the concatenated output is localNormalize(., left, 0) of the whole utterance, bit for bit.  right != 0 throws
+// std::invalid_argument, as the reference's module does.
+class FL_COMPAT_API StreamingLocalNorm {
+ public:
+  StreamingLocalNorm(int nFeat, int slots, int maxChunk, int left, int right = 0);
+  ~StreamingLocalNorm();
+  StreamingLocalNorm(const StreamingLocalNorm&) = delete;
+  StreamingLocalNorm& operator=(const StreamingLocalNorm&) = delete;
+  int slots() const { return slots_; }
+  int maxChunk() const { return maxChunk_; }
+  int numFeatures() const { return nFeat_; }
+  // features (ld, NFEAT, 1, slots) f32, IN PLACE (StreamingFeatures::step's view as it is): the first counts[s] frames of slot s
+  // are normalised, start[s] begins a new utterance (an empty vector = all 0).  One launch on fl::currentStream(), no
+  // synchronisation.
+  void step(af::array& features, const std::vector<int>& counts, const std::vector<int>& start);
+  void slotState(int slot, bool& active, long long& frames) const;
+  void reset(int slot);                          // closes a slot
+
+ private:
+  std::shared_ptr<void> state_;
+  void* h_ = nullptr;
+  int slots_ = 0, maxChunk_ = 0, nFeat_ = 0;
+};
+
 class FL_COMPAT_API SequenceCriterion : public fl::Container {
  public:
   // inputs {emission (N, T, B) f32, target (L, B) s32 (padded with negative values)} -> {loss (B)}

@@ -1193,6 +1193,64 @@ int w2l_feat_stream_frames(const w2l_feat_desc* desc, const float* G, const floa
                            const int* tab, float* carry0, float* carry1, int carryLd, float* out, int maxOut, int slots,
                            w2l_stream_t stream);
 
+/* ---- LocalNorm: windowed feature normalisation, batch and streaming (csrc/local_norm.hip, csrc/host/norm_stream.cpp)
+ * The module between the log-mel features and the network in the reference's streaming pipeline (streaming::LocalNorm(nFeat, left,
+ * right), inference/module/nn/LocalNorm.cpp) and the input transform of its trainer under --localnrmlleftctx / --localnrmlrightctx.
+ * Features are fp32 [B][F][ld] with time fastest: (T, NFEAT, 1, B) column-major, w2l_feat_session_step's [S][NFEAT][maxOut].
+ * THE CONTRACT.  Frame t of an utterance with n frames is normalised over the window lo = max(0, t - left) .. hi = min(n - 1,
+ * t + right), with ONE scalar mean and deviation over all F features of the window's frames:
+ *   1. Frame sums.   s_u = sum_f x[f][u] and q_u = sum_f x[f][u]^2, both in double, f ascending (the square of an fp32 is exact).
+ *   2. Window sums.  S = sum_{u = lo..hi} s_u and Q = sum q_u, in double, u ascending, SUMMED DIRECTLY: differences of running
+ *                    prefix sums are not allowed, their roundings depend on where the utterance began, and a frame's result is a
+ *                    function of its window's frames alone.
+ *   3. Moments.      cnt = (hi - lo + 1) F, mean = S / cnt, var = max(Q / cnt - mean mean, 0), sd = sqrt(var), all in double; if
+ *                    sd <= (double)1e-5f then sd = 1 (the reference's kEpsilon rule, LocalNorm.cpp:18, 93-95).
+ *   4. Output.       m = (float)mean, r = (float)(1.0 / sd), y[f][t] = (x[f][t] - m) * r: one fp32 subtract and one fp32
+ *                    multiply, not contracted into an FMA.
+ * With right = 0 this is the window of the reference's streaming module (left + 1 frames ending at t, LocalNorm.cpp:72-101), the
+ * pinned definition; with right > 0 it is the window of its offline transform as recalled (that code is not in the tree).
+ *   w2l_local_norm_workspace_size   B T (s, q) pairs of doubles: 16 B T bytes (0 for B or T below 1).  Host arithmetic.
+ *   w2l_local_norm                  x: device [B][F][ldx], y: device [B][F][ldy]; frames: device int [B], clamped into 0..T, or
+ *                                   NULL = T for every row.  Columns t >= frames[b] of y are not written.  y == x with ldy == ldx
+ *                                   is allowed (the sums are complete before the first store).  workspace: device, 16-byte
+ *                                   aligned.  Two launches whatever B, no atomics, never synchronises.
+ * Refused before anything touches the device, with a message for w2l_host_last_error(): W2L_EINVAL for B, F, T < 1, left < 0,
+ * right < 0, ldx < T, ldy < T, null pointers, a misaligned workspace and partial overlap of x and y; W2L_EUNSUPPORTED for
+ * left + right + 1 > 65536 or F > 4096.
+ * The session mirrors w2l_feat_session_*: `slots` concurrent streams, each with the (s, q) pairs of its last frames in a ring of
+ * left + maxChunk pairs inside the caller's state buffer.
+ *   w2l_norm_session_query / create right must be 0: W2L_EINVAL otherwise, as the reference's streaming LocalNorm refuses it
+ *                                   (LocalNorm.cpp:33).  nfeat, slots (<= 65535), maxChunk < 1, left < 0: W2L_EINVAL; left + 1 >
+ *                                   65536, nfeat > 4096, maxChunk > 65536: W2L_EUNSUPPORTED.  State bytes = align256(16 slots) +
+ *                                   align256(16 slots (left + maxChunk)).  Host arithmetic, like slot_state and reset.
+ *   w2l_norm_session_bind           state: device buffer of w2l_norm_session_state_bytes, 256-byte aligned, no initialisation
+ *                                   needed.  Allocates the pinned tables; closes every slot.
+ *   w2l_norm_session_step           x: device [S][F][ld], y: device [S][F][ldy]; h_n and h_start (may be NULL) are HOST int [S].
+ *                                   The h_n[s] new frames of every slot (columns 0 .. h_n[s] of its rows) are normalised in ONE
+ *                                   launch after one async copy of the table (pinned ring); h_start[s] != 0 begins a new utterance
+ *                                   with this step's frames.  y == x with ldy == ld is allowed, so a step can run on the feature
+ *                                   session's output before w2l_stream_step reads it.  Columns at or beyond h_n[s] are not
+ *                                   written.  Never synchronises, allocates nothing.  A step without frames enqueues nothing.
+ *   w2l_norm_session_slot_state     active flag and frames since the slot's start
+ *   w2l_norm_session_reset          closes a slot
+ * Refused with W2L_EINVAL before anything is enqueued or any count moves: null pointers, h_n[s] outside 0..maxChunk or above ld or
+ * ldy, frames for a slot that was never started (or was reset), a step before bind, partial overlap of x and y; at bind a state
+ * buffer that is missing, misaligned or smaller than w2l_norm_session_state_bytes.
+ * THE CONTRACT of the session.  For any slot and any split of its frames into chunks (empty chunks count, the other slots at any
+ * phase), the concatenated output equals w2l_local_norm with right = 0 on the whole utterance BIT FOR BIT. */
+size_t w2l_local_norm_workspace_size(int B, int T);
+int w2l_local_norm(int B, int F, int T, size_t ldx, const float* x, const int* frames, int left, int right, size_t ldy, float* y,
+                   void* workspace, w2l_stream_t stream);
+int w2l_norm_session_query(int nfeat, int slots, int maxChunk, int left, int right, size_t* stateBytes);
+int w2l_norm_session_create(int nfeat, int slots, int maxChunk, int left, int right, void** session);
+void w2l_norm_session_destroy(void* session);
+size_t w2l_norm_session_state_bytes(void* session);
+int w2l_norm_session_bind(void* session, void* state, size_t stateBytes);
+int w2l_norm_session_step(void* session, const float* x, size_t ld, const int* h_n, const int* h_start, float* y, size_t ldy,
+                          w2l_stream_t stream);
+int w2l_norm_session_slot_state(void* session, int slot, int* active, long long* frames);
+int w2l_norm_session_reset(void* session, int slot);
+
 #ifdef __cplusplus
 }
 #endif

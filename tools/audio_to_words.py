@@ -3,16 +3,20 @@
 
     python tools/audio_to_words.py [--wav FILE | --seconds 3 --seed 1] [--chunk-ms 160] [--commit-every 4]
                                    [--arch FILE] [--nlabel 29] [--checkpoint FILE] [--tokens FILE] [--beam 16]
+                                   [--local-norm-left N]
 
-    samples -> StreamingFeatures (log-mel, one launch per step) -> StreamingSession (chunked forward) -> StreamingDecoder
-    (incremental CTC beam search), commit() every few steps.
+    samples -> StreamingFeatures (log-mel, one launch per step) [-> StreamingLocalNorm (windowed normalisation, one launch per
+    step, in place)] -> StreamingSession (chunked forward) -> StreamingDecoder (incremental CTC beam search), commit() every few
+    steps.
 
 The audio is a 16-bit mono WAV file, or a seeded synthetic signal (a few drifting tones in noise).  It is cut into chunks of
 --chunk-ms and fed as int16, one chunk per step; every --commit-every steps the decoder commits what can no longer change, and
 the tool prints those labels as they become final, then the tail at the end.  Without --checkpoint the network has its seeded
 initial parameters and the labels are noise: a run of the plumbing.  --arch defaults to the streaming TDS-CTC recipe's;
---tokens names the labels (one per line), else their numbers are printed.  Features are not normalised (a model trained through
-the Python trainer and PrefetchLoader sees them that way)."""
+--tokens names the labels (one per line), else their numbers are printed.  Without --local-norm-left the features are not
+normalised (a model trained through the Python trainer and PrefetchLoader(local_norm=None) sees them that way);
+--local-norm-left=N normalises every frame over itself and the N frames before it, the features a model trained with
+--localnrmlleftctx=N (and no right context) through `Train` or PrefetchLoader(local_norm=(N, 0)) sees."""
 import argparse
 import os
 import sys
@@ -24,7 +28,7 @@ import torch
 
 from wav2letter_amd import checkpoint, recipes
 from wav2letter_amd.features import Mfsc
-from wav2letter_amd.streaming import StreamingDecoder, StreamingFeatures, StreamingSession
+from wav2letter_amd.streaming import StreamingDecoder, StreamingFeatures, StreamingLocalNorm, StreamingSession
 from wav2letter_amd.trainer import Trainer
 
 
@@ -60,6 +64,7 @@ if __name__ == "__main__":
     ap.add_argument("--checkpoint")
     ap.add_argument("--tokens")
     ap.add_argument("--beam", type=int, default=16)
+    ap.add_argument("--local-norm-left", type=int, default=None, help="normalise over this many frames of left context")
     a = ap.parse_args()
 
     x, fs = read_wav(a.wav) if a.wav else (synthetic(a.seconds, a.fs, a.seed), a.fs)
@@ -76,6 +81,7 @@ if __name__ == "__main__":
     fe = Mfsc(num_filters=a.filters, fs=fs, mel_floor=a.mel_floor)
     chunk = max(1, fs * a.chunk_ms // 1000)
     feats = StreamingFeatures(fe, 1, chunk)
+    norm = StreamingLocalNorm(a.filters, 1, feats.max_out, a.local_norm_left) if a.local_norm_left is not None else None
     net = StreamingSession(tr, 1, feats.max_out)
     max_frames = fe.num_frames(len(x)) + 64   # emission frames never outnumber feature frames (plus the flush)
     dec = StreamingDecoder(1, net.max_out, max_frames, a.nlabel, beam=a.beam, beam_token=min(a.beam, a.nlabel - 1))
@@ -88,6 +94,8 @@ if __name__ == "__main__":
         pcm[0, :len(part)] = torch.from_numpy(part).cuda()
         st, fi = [int(i == 0)], [int(i == steps - 1)]
         f, nf = feats.step(pcm, [len(part)], st, fi)
+        if norm is not None:
+            norm.step(f, nf, st)   # in place, on the feature step's view
         out, n_out = net.step(f, nf, st, fi)
         dec.step(out, n_out, st)
         frames += int(nf[0])
@@ -100,5 +108,6 @@ if __name__ == "__main__":
     tail = labels[0, 0, :max(int(lengths[0, 0]), 0)].cpu().numpy()
     print(f"[   tail  ] {show(tail)}")
     done = dec.committed(0)[0]
-    print(f"{len(x)} samples at {fs} Hz in {steps} steps of {a.chunk_ms} ms: {frames} feature frames, {emitted} emission frames, "
+    stages = "features -> local norm (left %d) -> network -> decoder" % a.local_norm_left if norm is not None else "features -> network -> decoder"
+    print(f"{stages}: {len(x)} samples at {fs} Hz in {steps} steps of {a.chunk_ms} ms: {frames} feature frames, {emitted} emission frames, "
           f"{len(done)} labels committed + {len(tail)} in the tail, score {float(scores[0, 0]):.3f}")

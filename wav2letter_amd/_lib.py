@@ -270,6 +270,16 @@ class _SIGS:
     w2l_feat_session_reset = (_i, [_p, _i])
     w2l_feat_stream_tile_rows = (_i, [])
     w2l_feat_stream_frames = (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _i, _p, _i, _i, _p])
+    w2l_local_norm_workspace_size = (_sz, [_i, _i])
+    w2l_local_norm = (_i, [_i, _i, _i, _sz, _p, _p, _i, _i, _sz, _p, _p, _p])
+    w2l_norm_session_query = (_i, [_i, _i, _i, _i, _i, _p])
+    w2l_norm_session_create = (_i, [_i, _i, _i, _i, _i, _p])
+    w2l_norm_session_destroy = (None, [_p])
+    w2l_norm_session_state_bytes = (_sz, [_p])
+    w2l_norm_session_bind = (_i, [_p, _p, _sz])
+    w2l_norm_session_step = (_i, [_p, _p, _sz, _p, _p, _p, _sz, _p])
+    w2l_norm_session_slot_state = (_i, [_p, _i, _p, _p])
+    w2l_norm_session_reset = (_i, [_p, _i])
 
 
 class ConvDesc(C.Structure):

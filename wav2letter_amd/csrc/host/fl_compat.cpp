@@ -1113,6 +1113,57 @@ void StreamingFeatures::reset(int slot) {
   if (w2l_feat_session_reset(h_, slot) != W2L_OK) throw std::invalid_argument(std::string("StreamingFeatures::reset: ") + w2l_host_last_error());
 }
 
+af::array localNormalize(const af::array& features, const std::vector<int>& frames, int left, int right) {
+  if (features.type() != af::f32 || features.elements() < 1)
+    throw std::invalid_argument("localNormalize: features must be a non-empty f32 (T, NFEAT, 1, B) array");
+  const int T = (int)features.dims(0), F = (int)(features.dims(1) * features.dims(2)), B = (int)features.dims(3);
+  if (!frames.empty() && (int)frames.size() != B) throw std::invalid_argument("localNormalize: one frame count per utterance");
+  af::array out = af::constant(0.0, features.dims());
+  af::array fr = frames.empty() ? af::array() : af::array(af::dim4((af::dim_t)B), frames.data());
+  auto ws = devAlloc(w2l_local_norm_workspace_size(B, T) + 256);
+  const int st = w2l_local_norm(B, F, T, (size_t)T, features.device<float>(), frames.empty() ? nullptr : fr.device<int>(), left, right,
+                                (size_t)T, out.device<float>(), ws.get(), S());
+  if (st == W2L_EINVAL) throw std::invalid_argument(std::string("localNormalize: ") + w2l_host_last_error());
+  if (st != W2L_OK) throw std::runtime_error(std::string("localNormalize: ") + w2l_host_last_error());
+  return out;
+}
+
+StreamingLocalNorm::StreamingLocalNorm(int nFeat, int slots, int maxChunk, int left, int right)
+    : slots_(slots), maxChunk_(maxChunk), nFeat_(nFeat) {
+  const int st = w2l_norm_session_create(nFeat, slots, maxChunk, left, right, &h_);
+  if (st == W2L_EINVAL) throw std::invalid_argument(std::string("StreamingLocalNorm: ") + w2l_host_last_error());
+  if (st != W2L_OK) throw std::runtime_error(std::string("StreamingLocalNorm: ") + w2l_host_last_error());
+  const size_t bytes = w2l_norm_session_state_bytes(h_);
+  state_ = devAlloc(bytes);
+  if (w2l_norm_session_bind(h_, state_.get(), bytes) != W2L_OK) {
+    const std::string msg = w2l_host_last_error();
+    w2l_norm_session_destroy(h_);
+    h_ = nullptr;
+    throw std::runtime_error("StreamingLocalNorm: " + msg);
+  }
+}
+StreamingLocalNorm::~StreamingLocalNorm() { if (h_) w2l_norm_session_destroy(h_); }
+void StreamingLocalNorm::step(af::array& features, const std::vector<int>& counts, const std::vector<int>& start) {
+  if (features.type() != af::f32 || features.dims(0) < 1 || features.dims(1) * features.dims(2) != nFeat_ || features.dims(3) != slots_)
+    throw std::invalid_argument("StreamingLocalNorm::step: features must be f32 (ld, NFEAT, 1, slots)");
+  if ((int)counts.size() != slots_ || (!start.empty() && (int)start.size() != slots_))
+    throw std::invalid_argument("StreamingLocalNorm::step: one count / flag per slot");
+  const size_t ld = (size_t)features.dims(0);
+  const int st = w2l_norm_session_step(h_, features.device<float>(), ld, counts.data(), start.empty() ? nullptr : start.data(),
+                                       features.device<float>(), ld, S());
+  if (st == W2L_EINVAL) throw std::invalid_argument(std::string("StreamingLocalNorm::step: ") + w2l_host_last_error());
+  if (st != W2L_OK) throw std::runtime_error(std::string("StreamingLocalNorm::step: ") + w2l_host_last_error());
+}
+void StreamingLocalNorm::slotState(int slot, bool& active, long long& frames) const {
+  int a = 0;
+  if (w2l_norm_session_slot_state(h_, slot, &a, &frames) != W2L_OK)
+    throw std::invalid_argument(std::string("StreamingLocalNorm::slotState: ") + w2l_host_last_error());
+  active = a != 0;
+}
+void StreamingLocalNorm::reset(int slot) {
+  if (w2l_norm_session_reset(h_, slot) != W2L_OK) throw std::invalid_argument(std::string("StreamingLocalNorm::reset: ") + w2l_host_last_error());
+}
+
 }  // namespace speech
 }  // namespace pkg
 namespace {

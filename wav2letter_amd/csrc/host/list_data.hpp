@@ -55,6 +55,7 @@ struct ListData {
   fl::lib::text::LexiconMap lexicon;
   std::string wordsep, criterion;
   int replabel = 0, nFeat = 0, batch = 1, padFrames = 64, rate = 16000;
+  int localLeft = 0, localRight = 0;            // --localnrmlleftctx / --localnrmlrightctx: both 0 = whole-utterance normalisation
   std::unique_ptr<fl::lib::audio::Mfsc> mfsc;
   af::array unit;                               // LayerNorm (gamma, beta) = (1, 0): the per-utterance normalisation
   long batches() const { return ((long)mine.size() + batch - 1) / batch; }
@@ -164,6 +165,24 @@ struct ListData {
     const int Tall = (int)feats.dims(0);
     T = Tb;
     input = af::constant(0.0, af::dim4(T, nFeat, 1, B));
+    if (localLeft > 0 || localRight > 0) {
+      tgt.assign((size_t)B * L, -1);
+      for (int b = 0; b < B; ++b) std::copy(rows[(size_t)b].begin(), rows[(size_t)b].end(), tgt.begin() + (size_t)b * L);
+      // --localnrmlleftctx / --localnrmlrightctx (Train.cpp:311-315): every frame over its window of the utterance's OWN frames, the
+      // whole batch in one w2l_local_norm call on the MFSC output, written into the zeroed batch
+      std::vector<int> fr((size_t)B);
+      for (int b = 0; b < B; ++b) fr[(size_t)b] = std::min(mfsc->numFrames((long)sizes[(size_t)b]), T);
+      af::array frames(af::dim4((af::dim_t)B), fr.data());
+      af::array ws(af::dim4((af::dim_t)(w2l_local_norm_workspace_size(B, T) / 4 + 64)));
+      void* wsp = (void*)(((uintptr_t)ws.device<float>() + 255) & ~(uintptr_t)255);
+      // a context of T - 1 frames already reaches every frame of the batch: the recipes' "whole utterance" values stay inside the
+      // call's window limit
+      w2l::w2lCheck(w2l_local_norm(B, nFeat, T, (size_t)Tall, feats.device<float>(), frames.device<int>(), std::min(localLeft, T - 1),
+                                   std::min(localRight, T - 1), (size_t)T,
+                                   input.device<float>(), wsp, (hipStream_t)fl::currentStream()), "local normalisation of the features");
+      af::sync();   // frames / ws go out of scope
+      return B;
+    }
     // per-utterance normalisation over the utterance's OWN frames (fl::lib::audio normalize(): zero mean, unit variance; applied
     // before padding in the reference): gather [NFEAT][T_b] -> LayerNorm with (1, 0) -> scatter into the zeroed batch
     hipStream_t st = (hipStream_t)fl::currentStream();
@@ -218,6 +237,11 @@ inline void loadListData(ListData& d, const std::vector<std::string>& paths, int
   d.rate = (int)flags.geti("samplerate", 16000);
   d.padFrames = (int)flags.geti("w2l_pad_frames", 64);
   d.nthread = (int)flags.geti("nthread", 6);
+  const long lnLeft = flags.geti("localnrmlleftctx", 0), lnRight = flags.geti("localnrmlrightctx", 0);
+  if (lnLeft < 0) throw std::invalid_argument("--localnrmlleftctx=" + std::to_string(lnLeft) + " is negative");
+  if (lnRight < 0) throw std::invalid_argument("--localnrmlrightctx=" + std::to_string(lnRight) + " is negative");
+  d.localLeft = (int)std::min<long>(lnLeft, 1 << 30);
+  d.localRight = (int)std::min<long>(lnRight, 1 << 30);
   fl::lib::audio::FeatureParams fp;
   fp.samplingFreq = d.rate; fp.frameSizeMs = (int)flags.geti("framesizems", 25); fp.frameStrideMs = (int)flags.geti("framestridems", 10);
   fp.numFilterbankChans = nFeat; fp.preemCoef = (float)flags.getd("preemcoef", 0.97); fp.melFloor = (float)flags.getd("melfloor", 1.0);

@@ -86,3 +86,34 @@ class Mfsc:
         out = torch.empty(B, self.F, T, device=audio.device, dtype=torch.float32)
         check(L.w2l_mfsc_log_transpose(_p(mel), _p(out), B, Tp, T, self.F, self.floor, _s()), "mfsc log")
         return out
+
+
+def local_normalize(x, frames=None, left=0, right=0, out=None):
+    """windowed normalisation of features x [B][F][T] (float32, on the device): frame t of an utterance with n = frames[b] frames
+    (None: T) is normalised with one mean and deviation over all features of frames max(0, t - left) .. min(n - 1, t + right).
+    The contract is in include/w2l_hip.h (w2l_local_norm); with right = 0 it is the reference's streaming LocalNorm, with both
+    contexts at or above T the whole-utterance normalisation.  frames: int32 [B] on the device (or anything torch.as_tensor
+    takes); columns at or beyond frames[b] are not written.  out: a tensor of x's kind, x itself for in place; None allocates
+    zeros.  Two launches, no synchronisation."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise _lib.W2LInvalidArgument("local_normalize: x must be a contiguous float32 [B][F][T] tensor on the device")
+    B, F, T = x.shape
+    if out is None:
+        out = torch.zeros_like(x)
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+            and tuple(out.shape[:2]) == (B, F) and out.dim() == 3 and out.shape[2] >= T):
+        raise _lib.W2LInvalidArgument("local_normalize: out must be a contiguous float32 [B][F][>= T] tensor on the device")
+    if frames is not None:
+        frames = torch.as_tensor(frames, dtype=torch.int32, device=x.device).contiguous()
+        if tuple(frames.shape) != (B,):
+            raise _lib.W2LInvalidArgument(f"local_normalize: frames must hold one count per utterance ({B})")
+    L = _lib.lib()
+    ws = torch.empty(max(L.w2l_local_norm_workspace_size(B, T), 16), dtype=torch.uint8, device=x.device)
+    st = L.w2l_local_norm(B, F, T, T, _p(x), _p(frames) if frames is not None else None, int(left), int(right), out.shape[2], _p(out),
+                          _p(ws), _s())
+    if st != _lib.W2L_OK:
+        msg = "local_normalize: " + L.w2l_host_last_error().decode()
+        if st == _lib.W2L_EINVAL:
+            raise _lib.W2LInvalidArgument(msg)
+        raise (_lib.W2LUnsupported if st == _lib.W2L_EUNSUPPORTED else _lib.W2LError)(msg)
+    return out

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import data as D
+from .features import local_normalize
 
 
 class PrefetchLoader:
@@ -32,9 +33,11 @@ class PrefetchLoader:
     sizes [B] float32 on `device` -- the utterances' sample counts, the batch's `inputSizes` --, the batch's sample indices).
 
     samples: objects with a `.path` (data.Sample) or plain paths; mfsc: features.Mfsc on `device`; `read` decodes one file to
-    (float32 or int16 samples, rate) -- default data.read_audio."""
+    (float32 or int16 samples, rate) -- default data.read_audio.  local_norm: None leaves the features unnormalised;
+    (left, right) normalises every utterance over its OWN frames with features.local_normalize on the side stream (frames at
+    or beyond an utterance's count are zero), the trainer's --localnrmlleftctx / --localnrmlrightctx."""
 
-    def __init__(self, samples, batches, mfsc, device="cuda", workers=4, depth=3, read=None, sample_rate=16000):
+    def __init__(self, samples, batches, mfsc, device="cuda", workers=4, depth=3, read=None, sample_rate=16000, local_norm=None):
         if depth < 2:
             raise ValueError("PrefetchLoader: depth must be >= 2 (one batch in use, one in flight)")
         self.paths = [s.path if hasattr(s, "path") else s for s in samples]
@@ -42,6 +45,11 @@ class PrefetchLoader:
         self.mfsc, self.device = mfsc, torch.device(device)
         self.workers, self.depth, self.rate = int(workers), int(depth), int(sample_rate)
         self.read = read or D.read_audio
+        if local_norm is not None:
+            local_norm = (int(local_norm[0]), int(local_norm[1]))
+            if min(local_norm) < 0:
+                raise ValueError("PrefetchLoader: local_norm = (left, right) must not be negative")
+        self.local_norm = local_norm
         self.stream = torch.cuda.Stream(device=self.device)
         self._q = None
         self._thread = None
@@ -100,6 +108,10 @@ class PrefetchLoader:
                         done[slot] = ev_copy
                         audio = dev.float().mul_(1.0 / 32768.0) if as_i16 else dev
                         feats = self.mfsc(audio)
+                        if self.local_norm is not None:
+                            nfr = np.array([self.mfsc.num_frames(len(a)) for a in audios], np.int32)
+                            feats = local_normalize(feats, torch.from_numpy(nfr).to(self.device, non_blocking=True),
+                                                    self.local_norm[0], self.local_norm[1])
                         sizes = torch.from_numpy(lens).to(self.device, non_blocking=True)
                         ready = torch.cuda.Event()
                         ready.record(self.stream)

@@ -2,8 +2,9 @@
 
 A StreamingSession runs a trained network on audio as it arrives: `slots` concurrent streams, at most `max_chunk` input
 frames per slot and step.  For any utterance and any split of it into chunks the concatenated emissions equal
-Trainer.forward(train=False) of that utterance alone (fp32 parity), and the frame count equals its Tout.  Feature extraction
-normalisation stays with the caller; StreamingFeatures (below) is the feature extraction.
+Trainer.forward(train=False) of that utterance alone (fp32 parity), and the frame count equals its Tout.  StreamingFeatures
+(below) is the feature extraction, StreamingLocalNorm the windowed normalisation between the two (csrc/local_norm.hip,
+csrc/host/norm_stream.cpp): features.local_normalize(left, right = 0) frame by frame, bit for bit under any chunking.
 
 mixed_precision=True makes it a bf16 session over a mixed-precision trainer (Trainer.set_mixed_precision): bf16 operands for the
 fl::Linear products and the TDS convolutions, everything else fp32, equal to the trainer's own mixed-precision eval forward within
@@ -258,6 +259,62 @@ class StreamingFeatures:
     def reset(self, slot):
         """closes a slot and discards its carry"""
         _check(self.L.w2l_feat_session_reset(self.h, int(slot)), "streaming features reset")
+
+
+class StreamingLocalNorm:
+    """StreamingLocalNorm(nfeat, slots, max_chunk, left): features.local_normalize(..., left=left, right=0) on frames as they
+    arrive, the reference's streaming LocalNorm between the features and the network (the contract is in include/w2l_hip.h,
+    w2l_norm_session_*).  `slots` concurrent streams, at most max_chunk new frames per slot and step; however an utterance's frames
+    are split into chunks, the concatenated output is local_normalize of the whole utterance, bit for bit.  Creation is host
+    arithmetic; the device state (16 bytes per slot and frame of left + max_chunk) is allocated at the first step."""
+
+    def __init__(self, nfeat, slots, max_chunk, left, right=0):
+        self.L = _lib.lib()
+        self.nfeat, self.slots, self.max_chunk, self.left = int(nfeat), int(slots), int(max_chunk), int(left)
+        self.h = C.c_void_p(0)
+        _check(self.L.w2l_norm_session_create(self.nfeat, self.slots, self.max_chunk, self.left, int(right), C.byref(self.h)),
+               "streaming local norm")
+        self.state_bytes = self.L.w2l_norm_session_state_bytes(self.h)
+        self._state = None
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.L.w2l_norm_session_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def slot_state(self, slot):
+        """(active, frames since the start) of a slot: host state"""
+        act, frames = C.c_int(0), C.c_longlong(0)
+        _check(self.L.w2l_norm_session_slot_state(self.h, int(slot), C.byref(act), C.byref(frames)), "streaming local norm slot state")
+        return bool(act.value), frames.value
+
+    def step(self, x, counts, start=None, out=None):
+        """x: [S][NFEAT][ld] float32 on the device with a unit time stride and rows of one slot F * ld apart (StreamingFeatures.step's
+        view is one), the first counts[s] columns of slot s are its new frames; counts / start: one int per slot on the host.
+        out=None normalises in place and returns x; otherwise out is a tensor of x's kind (its ld may differ) and is returned.
+        Columns at or beyond counts[s] are not written.  One launch, no synchronisation."""
+        S, F = self.slots, self.nfeat
+        y = x if out is None else out
+        for name, t in (("x", x), ("out", y)):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and tuple(t.shape[:2]) == (S, F)
+                    and t.is_contiguous()):
+                raise _lib.W2LInvalidArgument(
+                    f"{name} must be a contiguous float32 CUDA tensor [S={S}][NFEAT={F}][ld], got "
+                    f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t)}")
+        n, st = _flags(counts, S, "counts"), _flags(start, S, "start")
+        if self._state is None:
+            self._state = torch.empty(max(self.state_bytes, 256), dtype=torch.uint8, device=x.device)
+            _check(self.L.w2l_norm_session_bind(self.h, self._state.data_ptr(), self._state.numel()), "streaming local norm bind")
+        _check(self.L.w2l_norm_session_step(self.h, x.data_ptr(), x.shape[2], n.ctypes.data, st.ctypes.data, y.data_ptr(), y.shape[2],
+                                            torch.cuda.current_stream().cuda_stream), "streaming local norm step")
+        return y
+
+    def reset(self, slot):
+        """closes a slot"""
+        _check(self.L.w2l_norm_session_reset(self.h, int(slot)), "streaming local norm reset")
 
 
 BEAM_PLAIN, BEAM_LM, BEAM_LEX = 0, 1, 2
