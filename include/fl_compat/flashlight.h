@@ -786,6 +786,46 @@ class FL_COMPAT_API CTCLoss : public SequenceCriterion {
   CriterionScaleMode scaleMode_;
 };
 
+// The criterion of the reference's self-supervised trainer (--criterion=cpc; recipes/joint_training_vox_populi/cpc/CPCCriterion.h,
+// CPCCriterion.cpp:38-235) over w2l_cpc_* (the contract is in w2l_hip.h): getMask replaces spans of the encoder output by a learned
+// embedding before the context network sees it; forward scores every masked frame's context against its own encoder output and K
+// negatives, other masked frames of the same utterance.  The fork's step (cpc/Train.cpp:1155-1205) reads
+//     enc = encoder(features);  masked = crit->getMask(enc, maskProb, maskLength);  ctx = context(masked);
+//     loss = crit->forward({enc, ctx}).front();  loss.backward();
+// params() in the reference's order: the mask embedding (nEncoder), uniform in (-1, 1); the encoder projection's weight and bias;
+// the context projection's weight and bias (uniform within 1 / sqrt(fan-in), fl::Linear's rule).  A weight is (in, nMutual) here --
+// the C array [nMutual][in] of the kernels' contract --, the transpose of fl::Linear's (out, in).  nOffset, nUnits, nPieces and
+// nBuffer are stored and unused, exactly as in the reference.  The draws (initial values, masked spans, negatives) come from this
+// project's seeded stream (fl_compat/cpc.h), not from ArrayFire's.  Refused arguments: std::invalid_argument (fewer than 4 masked
+// frames per utterance among them); a shape beyond the kernels: std::runtime_error.
+class FL_COMPAT_API CPCCriterion : public SequenceCriterion {
+ public:
+  CPCCriterion(int nEncoder, int nContext, int nMutual, int nOffset, int nUnits, int nPieces, int nNegative, int nBuffer, float temperature);
+  // input (nEncoder, T, B) f32 -> the same shape with the masked frames replaced; stores the mask, its frames and the negatives
+  // for forward().  The seed of call n is setSeed's value + n.
+  Variable getMask(const Variable& input, float maskProb, int maskLength);
+  // fl_compat extension: frames[b] restricts the spans of utterance b to its first frames[b] frames (empty: all T, padding included,
+  // as the reference), and the seed is the caller's
+  Variable getMask(const Variable& input, double maskProb, int maskLength, const std::vector<int>& frames, uint64_t seed);
+  void setSeed(uint64_t seed) { seed_ = seed; }
+  int numMask() const;                                   // masked frames of the last getMask over the whole batch
+  Variable getMaskEmbedding() const { return params_[0]; }
+  std::vector<int> maskIndex() const;                    // fl_compat extension: [B][M] frames and [B][M][K] negatives of the last getMask
+  std::vector<int> negatives() const;
+  // inputs {enc (nEncoder, T, B) f32: the encoder output BEFORE masking, ctx (nContext, T, B) f32} -> {loss (B)}
+  std::vector<Variable> forward(const std::vector<Variable>& inputs) override;
+  af::array viterbiPath(const af::array& input, const af::array& inputSize = af::array()) override;   // throws std::logic_error
+  af::array viterbiPathWithTarget(const af::array& input, const af::array& target, const af::array& inputSizes = af::array(),
+                                  const af::array& targetSizes = af::array()) override;                // throws std::logic_error
+  std::string prettyString() const override;
+
+ private:
+  int nEncoder_, nContext_, nMutual_, nOffset_, nUnits_, nPieces_, nNegative_, nBuffer_;
+  float temperature_;
+  uint64_t seed_ = 0, calls_ = 0;
+  std::shared_ptr<void> state_;
+};
+
 // fl_compat extension (the validation loop of the reference's test(), recipes/slimIPL/src/Train.cpp:874-980): loss (B) and
 // Viterbi path (T, B) s32 of a held-out batch in one call, instead of forward() followed by viterbiPath().  CTC reads the
 // emissions once (w2l_ctc_score); ASG runs its loss sequence and the Viterbi pass.  No gradient; the criterion's training

@@ -1251,6 +1251,54 @@ int w2l_norm_session_step(void* session, const float* x, size_t ld, const int* h
 int w2l_norm_session_slot_state(void* session, int slot, int* active, long long* frames);
 int w2l_norm_session_reset(void* session, int slot);
 
+/* ---- CPC contrastive criterion (csrc/criterion_cpc.hip)
+ * The criterion of the reference's self-supervised trainer (--criterion=cpc, recipes/joint_training_vox_populi/cpc/CPCCriterion.cpp:
+ * 85-223): a span mask with a learned embedding over the encoder output, two projections into a common space, InfoNCE of every
+ * masked frame against negatives drawn from the other masked frames of its utterance.  Activations are fp32 [B][T][C] (ArrayFire
+ * dims (C, T, B)); the projection weights are [D][C] row-major (weight[d][c], ArrayFire dims (C, D)), the biases [D].
+ * WHICH frames are masked and WHICH negatives are drawn is host logic (include/fl_compat/cpc.h): the device calls take
+ *   mask      [B][T] bytes, nonzero = masked
+ *   maskIndex [B][M] int, the masked frames of every utterance, strictly ascending per row, every value in [0, T)
+ *   neg       [B][M][K] int, for masked position m (an index into the utterance's row of maskIndex) its K negatives, positions of the
+ *             same row.  ANY value in [0, M) is accepted, m itself and repeats included: the window rule belongs to the sampler.
+ * THE CONTRACT.
+ *   Masking   y[b][t][:] = mask[b][t] ? emb[:] : x[b][t][:].  Backward: dx = mask ? 0 : dy; demb[c] = the sum of dy[b][t][c] over the
+ *             masked frames, added in a fixed order (chunks of 64 frames upward, then the chunks upward).
+ *   Loss      with idx = maskIndex[b]:  a = ctx[b][idx] Wc^T + bc and p = enc[b][idx] We^T + be, both [M][D]; every row of a and of p
+ *             is divided by its L2 norm WITHOUT an epsilon, as the reference does: a zero row is outside the contract (it gives
+ *             NaN).  s[m][0] = <p_m, a_m> / tau, s[m][1 + k] = <p_neg[b][m][k], a_m> / tau,
+ *             loss[b] = (1 / M) sum_m (logsumexp_k s[m][k] - s[m][0]).
+ *   Backward  given g [B]: denc [B][T][Ce] and dctx [B][T][Cc] -- every frame is written, the unmasked ones as exactly 0.0f --,
+ *             dWe [D][Ce], dbe [D], dWc [D][Cc], dbc [D].
+ *   Reproducibility  the same inputs give the same bits from run to run: no float atomics; where several anchors share a negative or
+ *             one anchor names a negative twice the terms are added in a fixed order.
+ *   w2l_cpc_workspace_size        bytes for forward and backward of one step; host arithmetic; 0 for a shape the calls refuse
+ *   w2l_cpc_forward               loss: device [B].  The workspace keeps what the backward pass needs.
+ *   w2l_cpc_backward              after w2l_cpc_forward with the same shape, maskIndex, neg, weights and workspace.  It leaves what
+ *                                 the forward pass stored untouched: a second call gives the same bits.
+ *   w2l_cpc_apply_mask            needs no workspace
+ *   w2l_cpc_mask_workspace_size   bytes for w2l_cpc_apply_mask_backward: ceil(B T / 64) C floats; host arithmetic
+ *   w2l_cpc_apply_mask_backward   dx may be dy
+ * All device pointers; the workspaces are the caller's, 16-byte aligned; the calls never synchronise.  The products run on the
+ * library's fp32 GEMM (w2l_gemm_f32, following w2l_set_matmul_precision like every other product).
+ * Refused before anything touches the device, with a message for w2l_host_last_error(): W2L_EINVAL for null pointers, B, T, Ce, Cc,
+ * C or D below 1, M < 1, M > T, K < 1, K > M, tau <= 0 or not finite, a misaligned workspace; W2L_EUNSUPPORTED for M + 2 (K + 1) >
+ * 16000 (the coefficient row of one anchor lives in LDS) and for operands of 2^31 elements or more.  An index outside its range is
+ * outside the contract, but never makes a call read or write outside its operands. */
+size_t w2l_cpc_workspace_size(int B, int T, int Ce, int Cc, int D, int M, int K);
+int w2l_cpc_forward(int B, int T, int Ce, int Cc, int D, int M, int K, float tau, const float* enc /*[B][T][Ce]*/,
+                    const float* ctx /*[B][T][Cc]*/, const int* maskIndex /*[B][M]*/, const int* neg /*[B][M][K]*/,
+                    const float* We /*[D][Ce]*/, const float* be /*[D]*/, const float* Wc /*[D][Cc]*/, const float* bc /*[D]*/,
+                    float* loss /*[B]*/, void* workspace, w2l_stream_t stream);
+int w2l_cpc_backward(int B, int T, int Ce, int Cc, int D, int M, int K, float tau, const int* maskIndex, const int* neg,
+                     const float* We, const float* Wc, const float* g /*[B]*/, float* denc /*[B][T][Ce]*/, float* dctx /*[B][T][Cc]*/,
+                     float* dWe, float* dbe, float* dWc, float* dbc, void* workspace, w2l_stream_t stream);
+int w2l_cpc_apply_mask(int B, int T, int C, const float* x, const unsigned char* mask /*[B][T]*/, const float* emb /*[C]*/, float* y,
+                       w2l_stream_t stream);
+size_t w2l_cpc_mask_workspace_size(int B, int T, int C);
+int w2l_cpc_apply_mask_backward(int B, int T, int C, const float* dy, const unsigned char* mask, float* dx, float* demb /*[C]*/,
+                                void* workspace, w2l_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ torch.distributed (RCCL) only.
 """
 from . import _lib  # noqa: F401
 from . import text  # noqa: F401  (token dictionary, lexicon, targets, TER / WER remap: host logic)
-from .criterion import (ASGLoss, CTCLoss, CriterionScaleMode, ForceAlignmentCriterion,  # noqa: F401
+from . import cpc  # noqa: F401  (which frames the CPC criterion masks, which negatives it draws: host logic)
+from .criterion import (ASGLoss, CPCCriterion, CTCLoss, CriterionScaleMode, ForceAlignmentCriterion,  # noqa: F401
                         FullConnectionCriterion, LinSegCriterion, SequenceCriterion, getCriterionScaleMode, linear_target)
 from .lexicon import Lexicon  # noqa: F401
 from .lm import NGramLM  # noqa: F401

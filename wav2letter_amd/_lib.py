@@ -280,6 +280,12 @@ class _SIGS:
     w2l_norm_session_step = (_i, [_p, _p, _sz, _p, _p, _p, _sz, _p])
     w2l_norm_session_slot_state = (_i, [_p, _i, _p, _p])
     w2l_norm_session_reset = (_i, [_p, _i])
+    w2l_cpc_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i, _i])
+    w2l_cpc_forward = (_i, [_i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p])
+    w2l_cpc_backward = (_i, [_i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p])
+    w2l_cpc_apply_mask = (_i, [_i, _i, _i, _p, _p, _p, _p, _p])
+    w2l_cpc_mask_workspace_size = (_sz, [_i, _i, _i])
+    w2l_cpc_apply_mask_backward = (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p])
 
 
 class ConvDesc(C.Structure):

@@ -6,6 +6,7 @@ shape of SequenceCriterion in recipes/joint_training_vox_populi/cpc/CPCCriterion
 
   ASGLoss(N, scalemode, transdiag).forward(emission, target) -> loss[B]
   CTCLoss(scalemode).forward(emission, target) -> loss[B]
+  CPCCriterion(...).get_mask(enc, mask_prob, mask_length) -> masked enc;  .forward(enc, context) -> loss[B]   (CPCCriterion.cpp:85-223)
   crit.viterbiPath(emission) -> int32 [B][T];  crit.viterbiPathWithTarget(...)
 
 Tensors are torch CUDA(HIP) tensors used only as device buffers: emission is
@@ -660,3 +661,138 @@ class CTCLoss(SequenceCriterion):
 
     def prettyString(self):
         return "ConnectionistTemporalClassificationCriterion"
+
+
+class _CPCMask(torch.autograd.Function):
+    """y = mask ? emb : x over [B][T][C] (w2l_cpc_apply_mask / w2l_cpc_apply_mask_backward); mask: uint8 [B][T] on the device"""
+
+    @staticmethod
+    def forward(ctx, x, emb, mask):
+        L = _lib.lib()
+        x = x.contiguous()
+        emb = emb.contiguous()
+        B, T, C = x.shape
+        y = torch.empty_like(x)
+        _lib.check(L.w2l_cpc_apply_mask(B, T, C, x.data_ptr(), mask.data_ptr(), emb.data_ptr(), y.data_ptr(), _stream()), "cpc_apply_mask")
+        ctx.save_for_backward(mask)
+        ctx.dims = (B, T, C)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        L = _lib.lib()
+        (mask,) = ctx.saved_tensors
+        B, T, C = ctx.dims
+        grad = grad.contiguous().float()
+        dx = torch.empty_like(grad)
+        demb = torch.empty(C, dtype=torch.float32, device=grad.device)
+        ws = _ws(L.w2l_cpc_mask_workspace_size(B, T, C), grad.device)
+        _lib.check(L.w2l_cpc_apply_mask_backward(B, T, C, grad.data_ptr(), mask.data_ptr(), dx.data_ptr(), demb.data_ptr(), ws.data_ptr(),
+                                                 _stream()), "cpc_apply_mask_backward")
+        return dx, demb, None
+
+
+class _CPC(torch.autograd.Function):
+    """the InfoNCE loss of the masked frames (w2l_cpc_forward / w2l_cpc_backward; the contract is in include/w2l_hip.h)"""
+
+    @staticmethod
+    def forward(ctx, enc, context, We, be, Wc, bc, mask_index, neg, tau):
+        L = _lib.lib()
+        enc, context = enc.contiguous(), context.contiguous()
+        We, be, Wc, bc = We.contiguous(), be.contiguous(), Wc.contiguous(), bc.contiguous()
+        B, T, Ce = enc.shape
+        Cc, D = context.shape[2], We.shape[0]
+        M, K = mask_index.shape[1], neg.shape[2]
+        nbytes = L.w2l_cpc_workspace_size(B, T, Ce, Cc, D, M, K)
+        if not nbytes:
+            raise _lib.W2LInvalidArgument(f"w2l_cpc_workspace_size: shape B={B} T={T} Ce={Ce} Cc={Cc} D={D} M={M} K={K} is refused")
+        ws = _ws(nbytes, enc.device)
+        loss = torch.empty(B, dtype=torch.float32, device=enc.device)
+        _lib.check(L.w2l_cpc_forward(B, T, Ce, Cc, D, M, K, float(tau), enc.data_ptr(), context.data_ptr(), mask_index.data_ptr(),
+                                     neg.data_ptr(), We.data_ptr(), be.data_ptr(), Wc.data_ptr(), bc.data_ptr(), loss.data_ptr(),
+                                     ws.data_ptr(), _stream()), "cpc_forward")
+        ctx.save_for_backward(We, Wc, mask_index, neg, ws)
+        ctx.dims = (B, T, Ce, Cc, D, M, K, float(tau))
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad):
+        L = _lib.lib()
+        We, Wc, mask_index, neg, ws = ctx.saved_tensors
+        B, T, Ce, Cc, D, M, K, tau = ctx.dims
+        grad = grad.contiguous().float()
+        dev = grad.device
+        denc = torch.empty(B, T, Ce, dtype=torch.float32, device=dev)
+        dctx = torch.empty(B, T, Cc, dtype=torch.float32, device=dev)
+        dWe, dbe = torch.empty(D, Ce, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
+        dWc, dbc = torch.empty(D, Cc, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
+        _lib.check(L.w2l_cpc_backward(B, T, Ce, Cc, D, M, K, tau, mask_index.data_ptr(), neg.data_ptr(), We.data_ptr(), Wc.data_ptr(),
+                                      grad.data_ptr(), denc.data_ptr(), dctx.data_ptr(), dWe.data_ptr(), dbe.data_ptr(), dWc.data_ptr(),
+                                      dbc.data_ptr(), ws.data_ptr(), _stream()), "cpc_backward")
+        return denc, dctx, dWe, dbe, dWc, dbc, None, None, None
+
+
+class CPCCriterion(SequenceCriterion):
+    """The criterion of the reference's self-supervised trainer (--criterion=cpc, recipes/joint_training_vox_populi/cpc/
+    CPCCriterion.cpp): get_mask replaces spans of the encoder output by a learned embedding before the context network sees it,
+    forward scores every masked frame's context against its own encoder output and K negatives, other masked frames of the same
+    utterance.  Parameters in the reference's order: the mask embedding [nEncoder], uniform in (-1, 1); the encoder projection's
+    weight [nMutual][nEncoder] and bias; the context projection's weight [nMutual][nContext] and bias (fl::Linear's initialisation:
+    uniform within 1 / sqrt(fan-in)).  nOffset, nUnits, nPieces and nBuffer are stored and unused, exactly as in the reference.
+    The draws are this project's seeded stream (wav2letter_amd/cpc.py), not ArrayFire's."""
+
+    def __init__(self, nEncoder, nContext, nMutual, nOffset, nUnits, nPieces, nNegative, nBuffer, temperature):
+        super().__init__()
+        self.nEncoder, self.nContext, self.nMutual = int(nEncoder), int(nContext), int(nMutual)
+        self.nOffset, self.nUnits, self.nPieces, self.nBuffer = nOffset, nUnits, nPieces, nBuffer
+        self.nNegative, self.temperature = int(nNegative), float(temperature)
+        self.mask_embedding = torch.nn.Parameter(torch.empty(self.nEncoder).uniform_(-1.0, 1.0))
+        for name, fan_in in (("encoder", self.nEncoder), ("context", self.nContext)):
+            bound = fan_in ** -0.5
+            setattr(self, name + "_weight", torch.nn.Parameter(torch.empty(self.nMutual, fan_in).uniform_(-bound, bound)))
+            setattr(self, name + "_bias", torch.nn.Parameter(torch.empty(self.nMutual).uniform_(-bound, bound)))
+        self.mask = self.mask_index = self.negatives = None
+        self._draws = 0
+
+    def get_mask(self, x, mask_prob, mask_length, frames=None, seed=None):
+        """x [B][T][nEncoder] with the chosen spans replaced by the mask embedding.  Stores the byte mask [B][T], the masked frames
+        [B][M] and the negatives [B][M][K] for forward().  frames: the valid frames of every utterance (a sequence of B ints), None:
+        all T, padding included, as the reference.  seed: None takes torch's initial seed plus the number of calls so far."""
+        from . import cpc
+        if x.dim() != 3 or x.shape[2] != self.nEncoder or x.dtype != torch.float32:
+            raise _lib.W2LInvalidArgument("CPCCriterion.get_mask: x must be float32 [B][T][nEncoder]")
+        _check_dev(x)
+        B, T, _ = x.shape
+        if seed is None:
+            seed = torch.initial_seed() + self._draws
+        self._draws += 1
+        try:
+            mask, index, neg = cpc.sample(B, T, mask_prob, int(mask_length), self.nNegative,
+                                          None if frames is None else [int(f) for f in frames], seed)
+        except ValueError as e:
+            raise _lib.W2LInvalidArgument(str(e)) from None
+        self.mask = torch.from_numpy(mask).to(x.device)
+        self.mask_index = torch.from_numpy(index).to(x.device)
+        self.negatives = torch.from_numpy(neg).to(x.device)
+        return _CPCMask.apply(x, self.mask_embedding, self.mask)
+
+    def num_mask(self):
+        """masked frames of the last get_mask over the whole batch (the reference's numMask)"""
+        return 0 if self.mask_index is None else int(self.mask_index.numel())
+
+    def forward(self, enc, context):
+        """loss [B]: enc [B][T][nEncoder] is the encoder output BEFORE masking (the targets), context [B][T][nContext] the context
+        network's output on the masked input"""
+        if self.mask_index is None:
+            raise _lib.W2LInvalidArgument("CPCCriterion.forward: call get_mask first")
+        for t, n, what in ((enc, self.nEncoder, "enc"), (context, self.nContext, "context")):
+            if t.dim() != 3 or t.shape[2] != n or t.dtype != torch.float32:
+                raise _lib.W2LInvalidArgument(f"CPCCriterion.forward: {what} must be float32 [B][T][{n}]")
+        _check_dev(enc, context)
+        if enc.shape[:2] != context.shape[:2] or tuple(enc.shape[:2]) != tuple(self.mask.shape):
+            raise _lib.W2LInvalidArgument("CPCCriterion.forward: enc, context and the stored mask must agree in B and T")
+        return _CPC.apply(enc, context, self.encoder_weight, self.encoder_bias, self.context_weight, self.context_bias,
+                          self.mask_index, self.negatives, self.temperature)
+
+    def viterbiPath(self, emission, inputSize=None):
+        raise _lib.W2LError("CPCCriterion has no viterbiPath (the reference exits there)")

@@ -16,6 +16,7 @@
 
 #include "../../../include/fl_compat/flashlight.h"
 #include "../../../include/fl_compat/audio.h"
+#include "../../../include/fl_compat/cpc.h"
 #include "../../../include/fl_compat/lexicon.h"
 #include "../../../include/fl_compat/lm.h"
 #include "w2l_host.hpp"
@@ -1681,6 +1682,125 @@ BeamSearchResult ASGLoss::beamSearch(const af::array& input, const af::array& in
 }
 std::string CTCLoss::prettyString() const { return "ConnectionistTemporalClassificationCriterion"; }
 
+// ---- CPCCriterion over w2l_cpc_* (csrc/criterion_cpc.hip); the sampler is fl_compat/cpc.h
+namespace {
+struct CpcState {
+  CpcSample sample;                       // the last getMask's draws (host)
+  af::array mask, maskIndex, neg;         // their device copies; mask: B T bytes in an s32 array
+  std::shared_ptr<void> ws, maskWs;
+  size_t wsBytes = 0, maskWsBytes = 0;
+  void* grow(std::shared_ptr<void>& p, size_t& have, size_t need) {
+    if (need + 256 > have) { p = devAlloc(need + 256); have = need + 256; }
+    return p.get();
+  }
+};
+CpcState& cpcState(const std::shared_ptr<void>& p) { return *(CpcState*)p.get(); }
+
+af::array cpcUniform(CpcRng& rng, const af::dim4& dims, double bound) {
+  std::vector<float> h((size_t)dims.elements());
+  for (auto& v : h) v = (float)(bound * (2.0 * ((double)(rng.next() >> 11) * (1.0 / 9007199254740992.0)) - 1.0));
+  return af::array(dims, h.data());
+}
+}  // namespace
+
+CPCCriterion::CPCCriterion(int nEncoder, int nContext, int nMutual, int nOffset, int nUnits, int nPieces, int nNegative, int nBuffer,
+                           float temperature)
+    : nEncoder_(nEncoder), nContext_(nContext), nMutual_(nMutual), nOffset_(nOffset), nUnits_(nUnits), nPieces_(nPieces),
+      nNegative_(nNegative), nBuffer_(nBuffer), temperature_(temperature) {
+  if (nEncoder < 1 || nContext < 1 || nMutual < 1 || nNegative < 1) throw std::invalid_argument("CPCCriterion: nEncoder, nContext, nMutual and nNegative must be positive");
+  if (!(temperature > 0.f) || !std::isfinite(temperature)) throw std::invalid_argument("CPCCriterion: the temperature must be positive and finite");
+  state_ = std::make_shared<CpcState>();
+  CpcRng rng;
+  rng.state = 0x4350434372697421ull;   // the initial values are a fixed draw: ArrayFire's stream cannot be reproduced
+  params_.push_back(Variable(cpcUniform(rng, af::dim4(nEncoder), 1.0), true));
+  const int in[2] = {nEncoder, nContext};
+  for (int k = 0; k < 2; ++k) {
+    const double bound = 1.0 / std::sqrt((double)in[k]);
+    params_.push_back(Variable(cpcUniform(rng, af::dim4(in[k], nMutual), bound), true));
+    params_.push_back(Variable(cpcUniform(rng, af::dim4(nMutual), bound), true));
+  }
+}
+
+Variable CPCCriterion::getMask(const Variable& input, float maskProb, int maskLength) {
+  return getMask(input, (double)maskProb, maskLength, {}, seed_ + calls_++);
+}
+
+Variable CPCCriterion::getMask(const Variable& input, double maskProb, int maskLength, const std::vector<int>& frames, uint64_t seed) {
+  if (input.type() != af::f32 || input.dims(0) != nEncoder_ || input.dims(3) != 1 || input.isempty())
+    throw std::invalid_argument("CPCCriterion::getMask: input must be (nEncoder, T, B) f32");
+  const int C = (int)input.dims(0), T = (int)input.dims(1), B = (int)input.dims(2);
+  if (!frames.empty() && (int)frames.size() != B) throw std::invalid_argument("CPCCriterion::getMask: one frame count per utterance");
+  CpcState& st = cpcState(state_);
+  st.sample = cpcSample(B, T, maskProb, maskLength, nNegative_, frames.empty() ? nullptr : frames.data(), seed);
+  std::vector<int> packed(((size_t)B * T + 3) / 4, 0);
+  std::memcpy(packed.data(), st.sample.mask.data(), (size_t)B * T);
+  st.mask = af::array(af::dim4((af::dim_t)packed.size()), packed.data());
+  st.maskIndex = af::array(af::dim4(st.sample.M, B), st.sample.maskIndex.data());
+  st.neg = af::array(af::dim4(st.sample.K, st.sample.M, B), st.sample.neg.data());
+  af::array y(input.dims(), af::f32);
+  w2l::w2lCheck(w2l_cpc_apply_mask(B, T, C, input.array().device<float>(), st.mask.device<unsigned char>(), params_[0].array().device<float>(),
+                                   y.device<float>(), S()), "cpc mask");
+  auto state = state_;
+  af::array mask = st.mask;
+  return Variable(y, {input, params_[0]}, [state, mask, B, T, C](std::vector<Variable>& ins, const Variable& gradOut) {
+    CpcState& s = cpcState(state);
+    af::array dx(af::dim4(C, T, B), af::f32), demb(af::dim4(C), af::f32);
+    void* ws = s.grow(s.maskWs, s.maskWsBytes, w2l_cpc_mask_workspace_size(B, T, C));
+    w2l::w2lCheck(w2l_cpc_apply_mask_backward(B, T, C, gradOut.array().device<float>(), mask.device<unsigned char>(), dx.device<float>(),
+                                              demb.device<float>(), ws, S()), "cpc mask backward");
+    ins[0].addGrad(Variable(dx, false));
+    ins[1].addGrad(Variable(demb, false));
+  });
+}
+
+int CPCCriterion::numMask() const { return (int)cpcState(state_).sample.maskIndex.size(); }
+std::vector<int> CPCCriterion::maskIndex() const { return cpcState(state_).sample.maskIndex; }
+std::vector<int> CPCCriterion::negatives() const { return cpcState(state_).sample.neg; }
+
+std::vector<Variable> CPCCriterion::forward(const std::vector<Variable>& inputs) {
+  if (inputs.size() < 2) throw std::invalid_argument("Invalid inputs size");
+  const Variable& enc = inputs[0];
+  const Variable& ctx = inputs[1];
+  CpcState& st = cpcState(state_);
+  if (st.sample.M < 1) throw std::invalid_argument("CPCCriterion::forward: call getMask first");
+  if (enc.type() != af::f32 || ctx.type() != af::f32 || enc.dims(0) != nEncoder_ || ctx.dims(0) != nContext_)
+    throw std::invalid_argument("CPCCriterion::forward: inputs must be {(nEncoder, T, B), (nContext, T, B)} f32");
+  const int T = (int)enc.dims(1), B = (int)enc.dims(2), Ce = nEncoder_, Cc = nContext_, D = nMutual_, M = st.sample.M, K = st.sample.K;
+  if (ctx.dims(1) != T || ctx.dims(2) != B || st.sample.T != T || st.sample.B != B)
+    throw std::invalid_argument("CPCCriterion::forward: the inputs and the stored mask must agree in T and B");
+  const size_t bytes = w2l_cpc_workspace_size(B, T, Ce, Cc, D, M, K);
+  if (!bytes) throw std::runtime_error("CPCCriterion::forward: shape unsupported by this build");
+  void* ws = st.grow(st.ws, st.wsBytes, bytes);
+  af::array loss(af::dim4(B), af::f32);
+  const float tau = temperature_;
+  af::array maskIndex = st.maskIndex, neg = st.neg;
+  w2l::w2lCheck(w2l_cpc_forward(B, T, Ce, Cc, D, M, K, tau, enc.array().device<float>(), ctx.array().device<float>(), maskIndex.device<int>(),
+                                neg.device<int>(), params_[1].array().device<float>(), params_[2].array().device<float>(),
+                                params_[3].array().device<float>(), params_[4].array().device<float>(), loss.device<float>(), ws, S()),
+                "cpc forward");
+  auto state = state_;
+  return {Variable(loss, {enc, ctx, params_[1], params_[2], params_[3], params_[4]},
+                   [state, maskIndex, neg, B, T, Ce, Cc, D, M, K, tau](std::vector<Variable>& ins, const Variable& gradOut) {
+    CpcState& s = cpcState(state);
+    af::array dEnc(af::dim4(Ce, T, B), af::f32), dCtx(af::dim4(Cc, T, B), af::f32);
+    af::array dWe(af::dim4(Ce, D), af::f32), dbe(af::dim4(D), af::f32), dWc(af::dim4(Cc, D), af::f32), dbc(af::dim4(D), af::f32);
+    w2l::w2lCheck(w2l_cpc_backward(B, T, Ce, Cc, D, M, K, tau, maskIndex.device<int>(), neg.device<int>(), ins[2].array().device<float>(),
+                                   ins[4].array().device<float>(), gradOut.array().device<float>(), dEnc.device<float>(), dCtx.device<float>(),
+                                   dWe.device<float>(), dbe.device<float>(), dWc.device<float>(), dbc.device<float>(), s.ws.get(), S()),
+                  "cpc backward");
+    af::array g[6] = {dEnc, dCtx, dWe, dbe, dWc, dbc};
+    for (int i = 0; i < 6; ++i) ins[(size_t)i].addGrad(Variable(g[i], false));
+  })};
+}
+
+af::array CPCCriterion::viterbiPath(const af::array&, const af::array&) {
+  throw std::logic_error("CPCCriterion has no viterbiPath (the reference exits there)");
+}
+af::array CPCCriterion::viterbiPathWithTarget(const af::array&, const af::array&, const af::array&, const af::array&) {
+  throw std::logic_error("CPCCriterion has no viterbiPathWithTarget");
+}
+std::string CPCCriterion::prettyString() const { return "CPCCriterion"; }
+
 std::pair<af::array, af::array> w2lScore(SequenceCriterion& criterion, const Variable& emission, const Variable& target) {
   int N, T, B, L;
   checkCritInputs({emission, target}, N, T, B, L);
@@ -1906,7 +2026,8 @@ speech::PlannedNet& planned(const std::shared_ptr<fl::Module>& network) {
 std::string critName(const std::shared_ptr<fl::Module>& criterion) {
   if (dynamic_cast<speech::ASGLoss*>(criterion.get())) return "asg";
   if (dynamic_cast<speech::CTCLoss*>(criterion.get())) return "ctc";
-  throw std::invalid_argument("Serializer: unsupported criterion (this build: ASGLoss, CTCLoss)");
+  if (dynamic_cast<speech::CPCCriterion*>(criterion.get())) return "cpc";
+  throw std::invalid_argument("Serializer: unsupported criterion (this build: ASGLoss, CTCLoss, CPCCriterion)");
 }
 size_t critSlot(const std::shared_ptr<fl::Module>& criterion) {   // floats the criterion occupies in the flat arenas (16-byte slots)
   size_t n = 0;
@@ -2022,7 +2143,7 @@ void loadModel(const std::string& path, std::string& version, Serializer::Config
   size_t ni = 0;
   const std::vector<float>* mom = nullptr;
   const std::vector<float>* st2 = nullptr;
-  bool haveCrit = false;
+  size_t ci = 0;   // criterion tensors so far: they are stored in the order of criterion->params()
   for (size_t k = 0; k < ts.arr.size(); ++k) {
     const JVal* kind = ts.arr[k].get("kind");
     const std::string kd = kind ? kind->str : "";
@@ -2032,9 +2153,9 @@ void loadModel(const std::string& path, std::string& version, Serializer::Config
       ++ni;
     } else if (kd == "criterion") {
       auto cp = criterion->params();
-      if (cp.empty() || (size_t)cp[0].elements() != L.arrays[k].size()) throw std::runtime_error("checkpoint: criterion parameters do not match");
-      toDevice(cp[0].array().device<float>(), L.arrays[k].data(), L.arrays[k].size());
-      haveCrit = true;
+      if (ci >= cp.size() || (size_t)cp[ci].elements() != L.arrays[k].size()) throw std::runtime_error("checkpoint: criterion parameters do not match");
+      toDevice(cp[ci].array().device<float>(), L.arrays[k].data(), L.arrays[k].size());
+      ++ci;
     } else if (kd == "momentum") {
       mom = &L.arrays[k];
     } else if (kd == "state2") {
@@ -2042,7 +2163,7 @@ void loadModel(const std::string& path, std::string& version, Serializer::Config
     }
   }
   if (ni != table.size()) throw std::runtime_error("checkpoint: parameter list does not match this network");
-  if (haveCrit != !criterion->params().empty()) throw std::runtime_error("checkpoint: criterion parameters do not match (one side has transitions, the other has none)");
+  if (ci != criterion->params().size()) throw std::runtime_error("checkpoint: criterion parameters do not match (one side has transitions, the other has none)");
   toDevice(net.paramPtr(), host.data(), host.size());
   if (no || co) {
     const JVal* op = L.header.get("optim");
@@ -2072,9 +2193,14 @@ void Serializer::save(const std::string& path, const std::string& version, const
     net.impl().exportParam(i, host.data(), t.data.data());
     tensors.push_back(std::move(t));
   }
+  const bool cpc = critName(criterion) == "cpc";
+  static const char* const kCpcNames[5] = {"criterion.mask_embedding", "criterion.encoder.weight", "criterion.encoder.bias",
+                                           "criterion.context.weight", "criterion.context.bias"};
+  size_t critIndex = 0;
   for (auto& p : criterion->params()) {
     Tensor t;
-    t.name = "criterion.transitions"; t.kind = "criterion";
+    t.name = cpc && critIndex < 5 ? kCpcNames[critIndex] : "criterion.transitions"; t.kind = "criterion";
+    ++critIndex;
     t.shape = {(long)p.dims(0), (long)p.dims(1)};
     t.data = toHost(p.array().device<float>(), (size_t)p.elements());
     tensors.push_back(std::move(t));
