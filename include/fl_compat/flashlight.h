@@ -332,10 +332,13 @@ class FL_COMPAT_API FirstOrderOptimizer {
   void setLr(double lr) { lr_ = lr; }
   virtual void zeroGrad() { for (auto& p : parameters_) p.zeroGrad(); }
   virtual std::string prettyString() const = 0;
-  // fl_compat extension (checkpoints, fl::pkg::runtime::Serializer): "sgd" | "adagrad" | "adadelta", and the per-parameter
-  // state arrays -- slot 0: SGD velocity / Adagrad variance / Adadelta accGrad, slot 1: Adadelta accDelta (empty: stateless)
+  // fl_compat extension (checkpoints, fl::pkg::runtime::Serializer): "sgd" | "adagrad" | "adadelta" | "adam", and the per-parameter
+  // state arrays -- slot 0: SGD velocity / Adagrad variance / Adadelta accGrad / Adam m, slot 1: Adadelta accDelta / Adam v
+  // (empty: stateless); steps(): the updates applied so far where the rule reads them (Adam's bias correction), else 0
   virtual const char* kind() const = 0;
   virtual std::vector<std::vector<af::array>*> state() { return {}; }
+  virtual uint64_t steps() const { return 0; }
+  virtual void setSteps(uint64_t) {}
   const std::vector<Variable>& parameters() const { return parameters_; }
 
  protected:
@@ -396,6 +399,31 @@ class FL_COMPAT_API AdadeltaOptimizer : public FirstOrderOptimizer {
  private:
   double rho_, eps_;
   std::vector<af::array> accGrad_, accDelta_;
+};
+
+// --netoptim=adam (recipes/joint_training_vox_populi/sh_voxpopuli/pretrain.sh; cpc/Train.cpp:569-580 passes --adambeta1 --adambeta2
+// --optimepsilon and, for the network only, --weightdecay).  [UNVENDORED] Flashlight class, restated as w2l_adam_step_guarded states
+// it: t = steps() + 1; clr = lr sqrt(1 - beta2^t) / (1 - beta1^t); p -= weightDecay lr p (decoupled: the moments never see it);
+// m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2; p -= clr m / (sqrt(v) + eps), eps outside the bias correction.
+// The count lives on the host: the caller decides whether to call step() at all.
+class FL_COMPAT_API AdamOptimizer : public FirstOrderOptimizer {
+ public:
+  AdamOptimizer(const std::vector<Variable>& params, double lr, double beta1 = 0.9, double beta2 = 0.999, double eps = 1e-8, double weightDecay = 0);
+  void step() override;
+  std::string prettyString() const override;
+  const char* kind() const override { return "adam"; }
+  std::vector<std::vector<af::array>*> state() override { return {&biasedFirst_, &biasedSecond_}; }
+  uint64_t steps() const override { return count_; }
+  void setSteps(uint64_t n) override { count_ = n; }
+  double beta1() const { return beta1_; }
+  double beta2() const { return beta2_; }
+  double epsilon() const { return eps_; }
+  double weightDecay() const { return wd_; }
+
+ private:
+  double beta1_, beta2_, eps_, wd_;
+  uint64_t count_ = 0;
+  std::vector<af::array> biasedFirst_, biasedSecond_;
 };
 
 // global-norm clipping over the gradients that are available; returns the norm before clipping

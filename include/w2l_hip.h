@@ -791,6 +791,21 @@ int w2l_adagrad_step_guarded(float* p, const float* g, float* var, size_t n, flo
  * accDelta = rho accDelta + (1-rho) delta^2 */
 int w2l_adadelta_step_guarded(float* p, const float* g, float* accGrad, float* accDelta, size_t n, float lr, float rho,
                               float eps, float gradScale, float maxGradNorm, const double* guard, w2l_stream_t stream);
+/* fl::AdamOptimizer::step with decoupled weight decay (--netoptim=adam, recipes/joint_training_vox_populi/cpc/Train.cpp:569-580;
+ * [UNVENDORED] Flashlight class: this comment is the contract).  With t = the number of applied steps including this one:
+ *   clr = lr sqrt(1 - beta2^t) / (1 - beta1^t) (fp64, rounded to fp32 once); p -= (weightDecay lr) p (first, with lr: the moments
+ *   never see the decay); m = beta1 m + (1-beta1) g'; v = beta2 v + (1-beta2) g'^2; p -= clr m / (sqrt(v) + eps), eps OUTSIDE the
+ *   bias correction (torch.optim.Adam divides sqrt(v) by sqrt(1 - beta2^t) first; with eps = 0 the two agree).
+ * g', gradScale, maxGradNorm and guard as w2l_adagrad_step_guarded.  t = `step` (>= 1) when stepCount is NULL; else t =
+ * *stepCount + 1 (device, 8 bytes), read by every thread of the one launch, and a one-thread launch behind it adds 1 to *stepCount
+ * unless guard[0] is non-finite: a skipped update leaves p, m, v AND the bias correction untouched, without a host round trip.
+ * One launch over n floats, 28 bytes moved per parameter; float4 where p, g, m and v share their phase against 16 bytes (a scalar
+ * head up to the first aligned element), element by element where they do not.  W2L_EINVAL, before any launch: a null p, g, m or
+ * v; beta1 or beta2 outside [0, 1) or NaN; eps or weightDecay negative or NaN; step == 0 without a counter.  Zero g, m and v
+ * leave p bit-identical when weightDecay == 0 (0 / (0 + eps): eps == 0 gives NaN there); a zero p stays zero under weight decay. */
+int w2l_adam_step_guarded(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                          float weightDecay, float gradScale, float maxGradNorm, const double* guard, uint64_t step,
+                          uint64_t* stepCount, w2l_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 3. Trainer: arch file -> module graph -> one optimisation step.
@@ -846,9 +861,18 @@ int w2l_trainer_update(void* h, float lr, float lrcrit, float momentum, float ma
 int w2l_trainer_skipped_updates(void* h, uint64_t* count, void* stream);
 /* optimizer of the network / criterion parameters for w2l_trainer_update: 0 = SGD with momentum (default), 1 = Adagrad
  * (eps 1e-8; the momentum arena holds the accumulated squared gradients), 2 = Adadelta (rho 0.9, eps 1e-8; accGrad in the
- * momentum arena, accDelta in a second arena of the same size: w2l_trainer_bind_state2).
+ * momentum arena, accDelta in a second arena of the same size: w2l_trainer_bind_state2), 3 = Adam with decoupled weight decay
+ * (w2l_adam_step_guarded; m in the momentum arena, v in the second arena; hyperparameters: w2l_trainer_set_adam).
  * Train.cpp:577-582 initOptimizer(--netoptim / --critoptim) */
 int w2l_trainer_set_optimizer(void* h, int netKind, int critKind);
+/* Adam's hyperparameters (defaults 0.9, 0.999, 1e-8, 0: --adambeta1 --adambeta2 --optimepsilon --weightdecay of cpc/Train.cpp:569-580).
+ * weightDecay acts on the network's parameters only, as initOptimizer passes it; the criterion's Adam gets 0. */
+int w2l_trainer_set_adam(void* h, float beta1, float beta2, float eps, float weightDecay);
+/* Adam's applied-step counts of the network and the criterion group (what the bias correction reads).  They live on the device,
+ * in a buffer the trainer owns, because w2l_trainer_update decides on the device whether an update is skipped; a skipped update
+ * advances neither.  The --linseg hand-over resets them with the rest of the optimizer state.  For checkpoints; both synchronise. */
+int w2l_trainer_adam_steps(void* h, uint64_t* netSteps, uint64_t* critSteps, void* stream);
+int w2l_trainer_set_adam_steps(void* h, uint64_t netSteps, uint64_t critSteps, void* stream);
 /* input sizes of the NEXT forward calls (device, [B] floats in any unit; NULL = every utterance fills the batch): the
  * Transformer blocks mask the padded keys as the reference's forwardSequentialModuleWithPadMask does.  Call after plan. */
 int w2l_trainer_set_input_sizes(void* h, const float* inputSizesDev);

@@ -225,6 +225,7 @@ class _SIGS:
     w2l_sgd_step_guarded = (_i, [_p, _p, _p, _sz, _f, _f, _f, _f, _p, _p])
     w2l_adagrad_step_guarded = (_i, [_p, _p, _p, _sz, _f, _f, _f, _f, _p, _p])
     w2l_adadelta_step_guarded = (_i, [_p, _p, _p, _p, _sz, _f, _f, _f, _f, _f, _p, _p])
+    w2l_adam_step_guarded = (_i, [_p, _p, _p, _p, _sz, _f, _f, _f, _f, _f, _f, _f, _p, _u64, _p, _p])
     w2l_grad_guard = (_i, [_p, _p, _i, _p])
     w2l_stream_create = (_i, [C.c_char_p, _i, _i, _i, _i, _p])
     w2l_stream_create_for_trainer = (_i, [_p, _i, _i, _p])

@@ -11,12 +11,15 @@ so that a maintainer can convert either way with a few lines of cereal code:
     bytes 8..11   little-endian uint32  n = length of the JSON header
     bytes 12..    JSON header (utf-8): {"nfeat", "nlabel", "criterion", "arch_sha256", "step", "flags": {...},
                    "optim": [netoptim, critoptim],
+                   "adam": {"beta1", "beta2", "eps", "weight_decay", "steps": [network, criterion]}   (only when one of them is "adam"),
                    "tensors": [{"name", "kind": "network"|"criterion"|"momentum"|"state2", "shape": [...], "numel"}]}
     then, 16-byte aligned, every tensor's float32 data in header order (little endian, reference layout).
 
 Network tensors go through `Trainer.export_from / import_param` (internal layout <-> reference layout);
 criterion parameters (ASG transitions `(N, N)`, `[to][from]`) and the optimizer arenas are raw: "momentum" is SGD's velocity,
-Adagrad's squared-gradient sums or Adadelta's accGrad (header "optim" says which), "state2" is Adadelta's accDelta.
+Adagrad's squared-gradient sums, Adadelta's accGrad or Adam's m (header "optim" says which), "state2" is Adadelta's accDelta or
+Adam's v.  Adam's bias correction reads the number of updates it has APPLIED to each group (a skipped update counts for
+neither): header "adam" carries the two counts with the hyperparameters.
 """
 import hashlib
 import json
@@ -57,10 +60,14 @@ def save(path, trainer, arch_text, criterion, step=0, flags=None, momentum=True)
             tensors.append({"name": "netoptim.accDelta(internal arena)", "kind": "state2", "numel": int(trainer.n_floats),
                             "shape": [int(trainer.n_floats)]})
             blobs.append(np.ascontiguousarray(trainer.state2.detach().cpu().numpy(), np.float32))
-    header = json.dumps({"nfeat": trainer.nfeat, "nlabel": trainer.nlabel, "criterion": criterion,
-                         "optim": list(getattr(trainer, "_optim", ("sgd", "sgd"))),
-                         "arch_sha256": hashlib.sha256(arch_text.encode()).hexdigest(), "step": int(step),
-                         "flags": flags or {}, "tensors": tensors}).encode()
+    head = {"nfeat": trainer.nfeat, "nlabel": trainer.nlabel, "criterion": criterion,
+            "optim": list(getattr(trainer, "_optim", ("sgd", "sgd"))),
+            "arch_sha256": hashlib.sha256(arch_text.encode()).hexdigest(), "step": int(step),
+            "flags": flags or {}, "tensors": tensors}
+    if "adam" in head["optim"]:   # (a file of the other optimizers keeps the bytes it always had)
+        b1, b2, eps, wd = trainer._adam
+        head["adam"] = {"beta1": b1, "beta2": b2, "eps": eps, "weight_decay": wd, "steps": list(trainer.adam_steps())}
+    header = json.dumps(head).encode()
     with open(path, "wb") as f:
         f.write(MAGIC)
         f.write(struct.pack("<I", len(header)))
@@ -125,8 +132,14 @@ def load(path, trainer, arch_text=None):
     if mom and optim != tuple(getattr(trainer, "_optim", ("sgd", "sgd"))):
         # the arena's MEANING depends on the optimizer (velocity / squared-gradient sums / accGrad)
         raise ValueError(f"checkpoint holds the state of optimizers {optim}; call trainer.set_optimizer{optim} before load()")
-    if ("adadelta" in optim) != bool(st2) and mom:
-        raise ValueError("Adadelta checkpoint without its accDelta arena")
+    if ("adadelta" in optim or "adam" in optim) != bool(st2) and mom:
+        raise ValueError("Adadelta / Adam checkpoint without its second arena")
+    adam = header.get("adam")
+    if "adam" in optim and mom:
+        if not adam or len(adam.get("steps", ())) != 2:
+            raise ValueError("Adam checkpoint without its step counts")
+        trainer.set_optimizer(*optim, beta1=adam["beta1"], beta2=adam["beta2"], eps=adam["eps"], weight_decay=adam["weight_decay"])
+        trainer.set_adam_steps(*adam["steps"])
     if trainer.params is not None:
         trainer.params.copy_(torch.from_numpy(trainer.host_params))
         if mom:

@@ -814,6 +814,70 @@ __global__ __launch_bounds__(kEwThreads) void adadelta_k(float* __restrict__ p, 
     one(p[e], g[e], accG[e], accD[e]);
 }
 
+// b^t for an integer t by repeated squaring in fp64: at most 2 * 64 products, the same bits in every thread
+__device__ inline double pow_steps(double b, unsigned long long t) {
+  double r = 1.0;
+  for (; t; t >>= 1, b *= b)
+    if (t & 1) r *= b;
+  return r;
+}
+
+// fl::AdamOptimizer::step (--netoptim=adam of recipes/joint_training_vox_populi/sh_voxpopuli/pretrain.sh, cpc/Train.cpp:569-580;
+// un-vendored Flashlight class) with decoupled weight decay.  t = applied steps including this one:
+//   clr = lr sqrt(1 - beta2^t) / (1 - beta1^t)  (fp64, rounded once) ; p -= (wd lr) p  (first, with lr: the moments never see it) ;
+//   m = beta1 m + (1 - beta1) g' ; v = beta2 v + (1 - beta2) g'^2 ; p -= clr m / (sqrt(v) + eps)   (eps OUTSIDE the bias correction)
+// with the gradient scale, global-norm clip and non-finite guard of sgd_k.  t is `step`, or *count + 1 when a device counter is
+// given: adam_tick_k, launched behind this kernel on the same stream, advances it, so every thread of one launch reads one value
+// and a skipped update (non-finite guard) leaves the bias correction where it was.
+// Elements [0, head) and [head + 4 n4, n) go one by one, the n4 float4 from `head` on as vectors: the launcher picks head and
+// n4 so that all four arrays are 16-byte aligned there (n4 = 0 when their phases differ).
+__global__ __launch_bounds__(kEwThreads) void adam_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, size_t n, size_t head, size_t n4, float lr, float beta1,
+                                                    float beta2, float eps, float wd, float gradScale, float maxNorm,
+                                                    const double* __restrict__ sumsq, int guarded, unsigned long long step,
+                                                    const unsigned long long* __restrict__ count) {
+  float coef = gradScale;
+  if (sumsq) {
+    if (!isfinite(sumsq[0])) return;
+    if (guarded && sumsq[1] > 0.0) coef = gradScale = (float)sumsq[1];
+    if (maxNorm > 0.f) {
+      float norm = (float)sqrt(sumsq[0]) * gradScale;
+      float c = maxNorm / (norm + 1e-6f);
+      if (c < 1.f) coef *= c;
+    }
+  }
+  const unsigned long long t = count ? *count + 1ull : step;
+  const float clr = (float)((double)lr * sqrt(1.0 - pow_steps((double)beta2, t)) / (1.0 - pow_steps((double)beta1, t)));
+  const float om1 = 1.f - beta1, om2 = 1.f - beta2, decay = wd * lr;
+  auto one = [&](float& pv, float gv, float& mv, float& vv) {
+    gv *= coef;
+    if (wd != 0.f) pv -= decay * pv;
+    mv = beta1 * mv + om1 * gv;
+    vv = beta2 * vv + om2 * gv * gv;
+    pv -= clr * mv / (sqrtf(vv) + eps);
+  };
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n4; i += stride) {
+    const size_t e = head + 4 * i;
+    float4 pv = *(const float4*)(p + e), gv = *(const float4*)(g + e), mv = *(const float4*)(m + e), vv = *(const float4*)(v + e);
+    one(pv.x, gv.x, mv.x, vv.x); one(pv.y, gv.y, mv.y, vv.y); one(pv.z, gv.z, mv.z, vv.z); one(pv.w, gv.w, mv.w, vv.w);
+    *(float4*)(m + e) = mv;
+    *(float4*)(v + e) = vv;
+    *(float4*)(p + e) = pv;
+  }
+  const size_t tail = head + (n4 << 2);
+  for (size_t i = tid; i < n - (n4 << 2); i += stride) {
+    const size_t e = i < head ? i : tail + (i - head);
+    one(p[e], g[e], m[e], v[e]);
+  }
+}
+
+// one thread, behind adam_k on its stream: the applied-step count of that update, unless the guard skipped it
+__global__ void adam_tick_k(unsigned long long* __restrict__ count, const double* __restrict__ sumsq) {
+  if (sumsq && !isfinite(sumsq[0])) return;
+  *count += 1ull;
+}
+
 // (shared with layernorm_images.hip)
 int ln_param_grad(const double* sums, int groups, float* dGammaBeta, hipStream_t stream) {
   hipLaunchKernelGGL(ln_param_grad_k, dim3(1), dim3(1024), 0, stream, sums, groups, dGammaBeta);
@@ -1164,6 +1228,29 @@ W2L_API int w2l_adadelta_step_guarded(float* p, const float* g, float* accGrad, 
   if (!n) return W2L_OK;
   hipLaunchKernelGGL(adadelta_k, dim3(ew_grid((n >> 2) + 1)), dim3(kEwThreads), 0, W2L_S, p, g, accGrad, accDelta, n, lr, rho, eps,
                      gradScale, maxGradNorm, guard, guard ? 1 : 0);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+W2L_API int w2l_adam_step_guarded(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
+                                  float eps, float weightDecay, float gradScale, float maxGradNorm, const double* guard,
+                                  uint64_t step, uint64_t* stepCount, w2l_stream_t stream) {
+  if (!p || !g || !m || !v || (maxGradNorm > 0.f && !guard)) return W2L_EINVAL;
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) || !(weightDecay >= 0.f)) return W2L_EINVAL;
+  if (!stepCount && step == 0) return W2L_EINVAL;
+  if (!n) return W2L_OK;
+  // float4 only where all four arrays are 16-byte aligned at the same element: a scalar head up to there, none if they never are
+  const uintptr_t phase = (uintptr_t)p & 15;
+  size_t head = 0, n4 = 0;
+  if (((uintptr_t)g & 15) == phase && ((uintptr_t)m & 15) == phase && ((uintptr_t)v & 15) == phase && (phase & 3) == 0) {
+    head = ((16 - phase) & 15) >> 2;
+    if (head > n) head = n;
+    n4 = (n - head) >> 2;
+  }
+  hipLaunchKernelGGL(adam_k, dim3(ew_grid((n >> 2) + 1)), dim3(kEwThreads), 0, W2L_S, p, g, m, v, n, head, n4, lr, beta1, beta2, eps,
+                     weightDecay, gradScale, maxGradNorm, guard, guard ? 1 : 0, (unsigned long long)step,
+                     (const unsigned long long*)stepCount);
+  if (stepCount) hipLaunchKernelGGL(adam_tick_k, dim3(1), dim3(1), 0, W2L_S, (unsigned long long*)stepCount, guard);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }

@@ -397,6 +397,44 @@ std::string AdadeltaOptimizer::prettyString() const {
   return ss.str();
 }
 
+AdamOptimizer::AdamOptimizer(const std::vector<Variable>& params, double lr, double beta1, double beta2, double eps, double weightDecay)
+    : FirstOrderOptimizer(params, lr), beta1_(beta1), beta2_(beta2), eps_(eps), wd_(weightDecay) {
+  if (!(beta1 >= 0 && beta1 < 1) || !(beta2 >= 0 && beta2 < 1) || !(eps >= 0) || !(weightDecay >= 0))
+    throw std::invalid_argument("fl_compat AdamOptimizer: beta1 and beta2 must lie in [0, 1), epsilon and weight decay must not be negative");
+  if (flatParameterArena(parameters_, flatParams_, flatFloats_, flatOffsets_)) {
+    flatStateViews(0, biasedFirst_);
+    flatStateViews(1, biasedSecond_);
+    return;
+  }
+  flatParams_ = nullptr;
+  for (auto& p : parameters_) {
+    biasedFirst_.push_back(af::constant(0.0, p.dims(), af::f32));
+    biasedSecond_.push_back(af::constant(0.0, p.dims(), af::f32));
+  }
+}
+void AdamOptimizer::step() {
+  ++count_;
+  float* gbase = nullptr;
+  if (flatNow(gbase, &biasedFirst_, &biasedSecond_)) {
+    w2l::w2lCheck(w2l_adam_step_guarded(flatParams_, gbase, flatState_[0], flatState_[1], flatFloats_, (float)lr_, (float)beta1_, (float)beta2_,
+                                        (float)eps_, (float)wd_, 1.f, 0.f, nullptr, count_, nullptr, S()), "adam");
+    return;
+  }
+  for (size_t i = 0; i < parameters_.size(); ++i) {
+    auto& p = parameters_[i];
+    if (!p.isGradAvailable()) continue;
+    w2l::w2lCheck(w2l_adam_step_guarded(p.array().device<float>(), p.grad().array().device<float>(), biasedFirst_[i].device<float>(),
+                                        biasedSecond_[i].device<float>(), (size_t)p.elements(), (float)lr_, (float)beta1_, (float)beta2_,
+                                        (float)eps_, (float)wd_, 1.f, 0.f, nullptr, count_, nullptr, S()), "adam");
+  }
+}
+std::string AdamOptimizer::prettyString() const {
+  std::ostringstream ss;
+  ss << "Adam (beta1=" << beta1_ << ") (beta2=" << beta2_ << ") (epsilon=" << eps_ << ")";
+  if (wd_ != 0) ss << " (weight decay=" << wd_ << ")";
+  return ss.str();
+}
+
 double clipGradNorm(const std::vector<Variable>& params, double maxNorm) {
   static std::shared_ptr<void> acc = devAlloc(sizeof(double));
   double* d = (double*)acc.get();
@@ -1884,8 +1922,8 @@ Variable selectBatch(const Variable& emission, const std::vector<int>& rows) {
 // JSON header, then every tensor's float32 data 16-byte aligned in header order.  Network tensors are stored in the
 // REFERENCE's layouts (w2l::Sequential::exportParam / importParam), the ASG transitions (N, N) raw, the optimizer state
 // as flat arenas [network parameters in arena order | criterion parameters] ("momentum": SGD velocity / Adagrad variance /
-// Adadelta accGrad; "state2": Adadelta accDelta) -- the same bytes the Python front-end writes, so either side resumes
-// the other's run.
+// Adadelta accGrad / Adam m; "state2": Adadelta accDelta / Adam v) -- the same bytes the Python front-end writes, so either side
+// resumes the other's run.  Adam's applied-step counts ride in the header ("adam": {..., "steps": [network, criterion]}).
 namespace fl {
 namespace pkg {
 namespace runtime {
@@ -2173,6 +2211,13 @@ void loadModel(const std::string& path, std::string& version, Serializer::Config
     const size_t want = net.impl().paramFloats() + critSlot(criterion);
     if (mom) { if (mom->size() != want) throw std::runtime_error("checkpoint: optimizer arena does not match this trainer"); scatterState(net, no, co, 0, *mom); }
     if (st2) { if (st2->size() != want) throw std::runtime_error("checkpoint: optimizer arena does not match this trainer"); scatterState(net, no, co, 1, *st2); }
+    if (mom && (wantNet == "adam" || wantCrit == "adam")) {   // the bias correction continues where the run stopped
+      const JVal* ad = L.header.get("adam");
+      const JVal* st = ad ? ad->get("steps") : nullptr;
+      if (!st || st->kind != JVal::ARR || st->arr.size() != 2) throw std::runtime_error("checkpoint: Adam state without its step counts");
+      if (no) no->setSteps((uint64_t)st->arr[0].num);
+      if (co) co->setSteps((uint64_t)st->arr[1].num);
+    }
   }
   net.setStep((uint32_t)std::max(0L, num("step")));
 }
@@ -2217,7 +2262,17 @@ void Serializer::save(const std::string& path, const std::string& version, const
   std::ostringstream h;
   h << "{\"nfeat\": " << net.nFeat() << ", \"nlabel\": " << net.nLabel() << ", \"criterion\": " << jstr(critName(criterion))
     << ", \"optim\": [" << jstr(netoptim ? netoptim->kind() : "sgd") << ", " << jstr(critoptim ? critoptim->kind() : "sgd") << "]"
-    << ", \"arch_sha256\": " << jstr(net.archSha_) << ", \"step\": " << net.step() << ", \"flags\": {" << jstr("version") << ": " << jstr(version);
+    << ", \"arch_sha256\": " << jstr(net.archSha_) << ", \"step\": " << net.step();
+  const auto* adamNet = dynamic_cast<const fl::AdamOptimizer*>(netoptim.get());
+  const auto* adamCrit = dynamic_cast<const fl::AdamOptimizer*>(critoptim.get());
+  if (const fl::AdamOptimizer* a = adamNet ? adamNet : adamCrit) {   // (the keys wav2letter_amd/checkpoint.py writes and reads)
+    std::ostringstream hp;
+    hp.precision(17);
+    hp << "{\"beta1\": " << a->beta1() << ", \"beta2\": " << a->beta2() << ", \"eps\": " << a->epsilon() << ", \"weight_decay\": "
+       << (adamNet ? adamNet->weightDecay() : 0.0) << ", \"steps\": [" << (netoptim ? netoptim->steps() : 0) << ", " << (critoptim ? critoptim->steps() : 0) << "]}";
+    h << ", \"adam\": " << hp.str();
+  }
+  h << ", \"flags\": {" << jstr("version") << ": " << jstr(version);
   for (auto& kv : config)
     if (kv.first != "version") h << ", " << jstr(kv.first) << ": " << jstr(kv.second);
   h << "}, \"tensors\": [";

@@ -41,9 +41,21 @@ struct Trainer {
   SequenceCriterion* activeCrit() { return (linseg && step < linsegUpdates) ? linseg.get() : crit.get(); }
   std::string lastError;
   bool guardZeroed = false;
-  int netOptim = 0, critOptim = 0;  // 0 SGD(momentum), 1 Adagrad (variance in the momentum arena), 2 Adadelta (+ state2)
+  int netOptim = 0, critOptim = 0;  // 0 SGD(momentum), 1 Adagrad (variance in the momentum arena), 2 Adadelta (+ state2), 3 Adam (+ state2)
+  float adamBeta1 = 0.9f, adamBeta2 = 0.999f, adamEps = 1e-8f, adamWd = 0.f;   // w2l_trainer_set_adam
+  // Adam's applied-step counts [network, criterion], owned, on the DEVICE: the update is skipped there (grad_guard_k) and a
+  // skipped update must not advance the bias correction.  A buffer of its own (the acc array of w2l_grad_guard keeps its layout).
+  uint64_t* adamSteps = nullptr;
+  uint64_t* adamStepsBuf() {
+    if (!adamSteps) {
+      hipCheck(hipMalloc((void**)&adamSteps, 2 * sizeof(uint64_t)), "Adam step counts");
+      hipCheck(hipMemset(adamSteps, 0, 2 * sizeof(uint64_t)), "Adam step counts");
+      hipCheck(hipStreamSynchronize(nullptr), "Adam step counts");   // once: whatever stream the first update runs on sees the zeros
+    }
+    return adamSteps;
+  }
   const float* inputSizes = nullptr;  // w2l_trainer_set_input_sizes
-  float* state2 = nullptr;          // Adadelta's accDelta, same size and layout as the momentum arena
+  float* state2 = nullptr;          // Adadelta's accDelta / Adam's v, same size and layout as the momentum arena
   bool mixedPrecision = false;   // fl's --fl_amp_use_mixed_precision, restated for bf16: the network's fl::Linear GEMMs multiply
                                  // in bf16 (fp32 accumulate, fp32 storage, fp32 master weights); convolutions, LayerNorm, the
                                  // criterion and the optimizer stay fp32
@@ -61,6 +73,7 @@ struct Trainer {
   ~Trainer() {
     for (auto e : bucketEvents) (void)hipEventDestroy(e);
     if (evalMem) (void)hipFree(evalMem);
+    if (adamSteps) (void)hipFree(adamSteps);
   }
 };
 
@@ -277,28 +290,34 @@ W2L_API int w2l_trainer_update(void* h, float lr, float lrcrit, float momentum, 
     if (!t->guardZeroed) { hipCheck(hipMemsetAsync(t->sumsq, 0, sizeof(double) * 8, s), "memset"); t->guardZeroed = true; }
     // --linseg: the reference trains the warm-up phase with its OWN optimizers (linNetoptim / linCritoptim,
     // Train.cpp:589-617), so the ASG phase proper starts from fresh optimizer state: clear the momentum arena -- SGD
-    // velocity, or the Adagrad / Adadelta gradient statistics it holds -- and Adadelta's second arena at the switch
+    // velocity, or the Adagrad / Adadelta / Adam gradient statistics it holds --, the second arena of Adadelta and Adam, and
+    // Adam's step counts at the switch
     if (t->linseg && t->linsegUpdates && t->step == t->linsegUpdates) {
       const bool stateful = momentum != 0.f || t->netOptim != 0 || t->critOptim != 0;
       if (t->mom && stateful)
         hipCheck(hipMemsetAsync(t->mom, 0, sizeof(float) * (t->netFloats + t->critFloats), s), "linseg optimizer-state reset");
-      if (t->state2 && (t->netOptim == 2 || t->critOptim == 2))
+      if (t->state2 && (t->netOptim >= 2 || t->critOptim >= 2))
         hipCheck(hipMemsetAsync(t->state2, 0, sizeof(float) * (t->netFloats + t->critFloats), s), "linseg optimizer-state reset");
+      if (t->adamSteps) hipCheck(hipMemsetAsync(t->adamSteps, 0, 2 * sizeof(uint64_t), s), "linseg optimizer-state reset");
     }
     // the norm is taken on EVERY update (also with --maxgradnorm=0): it is the non-finite guard of the step
     w2lCheck(w2l_sumsq(t->grads, t->netFloats, t->sumsq, 1, s), "sumsq");
     w2lCheck(w2l_sumsq(t->grads + t->netFloats, t->critFloats, t->sumsq + 1, 1, s), "sumsq");
     w2lCheck(w2l_grad_guard(t->sumsq, totalBatch > 0.f ? nullptr : t->batchSlot, clampCrit, s), "guard");
     const bool needState = t->netOptim != 0 || (t->critOptim != 0 && t->critFloats);
-    const bool needState2 = t->netOptim == 2 || (t->critOptim == 2 && t->critFloats);
+    const bool needState2 = t->netOptim >= 2 || (t->critOptim >= 2 && t->critFloats);
     if (needState && !t->mom) throw std::invalid_argument("Adagrad / Adadelta need the momentum arena bound (it holds the gradient statistics)");
     if (needState2 && !t->state2) throw std::invalid_argument("Adadelta needs w2l_trainer_bind_state2");
+    uint64_t* adamSteps = (t->netOptim == 3 || (t->critOptim == 3 && t->critFloats)) ? t->adamStepsBuf() : nullptr;
     auto stepOne = [&](int kind, size_t off, size_t n, float rate, float mom, float clip, const char* what) {
       float* v = t->mom ? t->mom + off : nullptr;
       if (kind == 1)
         w2lCheck(w2l_adagrad_step_guarded(t->params + off, t->grads + off, v, n, rate, 1e-8f, gs, clip, t->sumsq + 2, s), what);
       else if (kind == 2)
         w2lCheck(w2l_adadelta_step_guarded(t->params + off, t->grads + off, v, t->state2 + off, n, rate, 0.9f, 1e-8f, gs, clip, t->sumsq + 2, s), what);
+      else if (kind == 3)   // (weight decay: the network group only, cpc/Train.cpp:569-580)
+        w2lCheck(w2l_adam_step_guarded(t->params + off, t->grads + off, v, t->state2 + off, n, rate, t->adamBeta1, t->adamBeta2, t->adamEps,
+                                       off ? 0.f : t->adamWd, gs, clip, t->sumsq + 2, 0, adamSteps + (off ? 1 : 0), s), what);
       else
         w2lCheck(w2l_sgd_step_guarded(t->params + off, t->grads + off, mom != 0.f ? v : nullptr, n, rate, mom, gs, clip, t->sumsq + 2, s), what);
     };
@@ -433,9 +452,38 @@ W2L_API int w2l_trainer_skipped_updates(void* h, uint64_t* count, void* stream) 
 }
 
 W2L_API int w2l_trainer_set_optimizer(void* h, int netKind, int critKind) {
-  if (!h || netKind < 0 || netKind > 2 || critKind < 0 || critKind > 2) return W2L_EINVAL;
+  if (!h || netKind < 0 || netKind > 3 || critKind < 0 || critKind > 3) return W2L_EINVAL;
   ((Trainer*)h)->netOptim = netKind; ((Trainer*)h)->critOptim = critKind;
   return W2L_OK;
+}
+W2L_API int w2l_trainer_set_adam(void* h, float beta1, float beta2, float eps, float weightDecay) {
+  if (!h || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) || !(weightDecay >= 0.f)) return W2L_EINVAL;
+  Trainer* t = (Trainer*)h;
+  t->adamBeta1 = beta1; t->adamBeta2 = beta2; t->adamEps = eps; t->adamWd = weightDecay;
+  return W2L_OK;
+}
+W2L_API int w2l_trainer_adam_steps(void* h, uint64_t* netSteps, uint64_t* critSteps, void* stream) {
+  Trainer* t = (Trainer*)h;
+  TRY(h, {
+    if (!t || !netSteps || !critSteps) throw std::invalid_argument("adam_steps: null argument");
+    uint64_t c[2];
+    c[0] = c[1] = 0;
+    if (t->adamSteps) {   // (never allocated: no Adam update has run and none was set)
+      hipCheck(hipMemcpyAsync(c, t->adamSteps, sizeof(c), hipMemcpyDeviceToHost, (hipStream_t)stream), "adam_steps");
+      hipCheck(hipStreamSynchronize((hipStream_t)stream), "adam_steps");
+    }
+    *netSteps = c[0]; *critSteps = c[1];
+  });
+}
+W2L_API int w2l_trainer_set_adam_steps(void* h, uint64_t netSteps, uint64_t critSteps, void* stream) {
+  Trainer* t = (Trainer*)h;
+  TRY(h, {
+    if (!t) throw std::invalid_argument("set_adam_steps: null handle");
+    uint64_t c[2];
+    c[0] = netSteps; c[1] = critSteps;
+    hipCheck(hipMemcpyAsync(t->adamStepsBuf(), c, sizeof(c), hipMemcpyHostToDevice, (hipStream_t)stream), "set_adam_steps");
+    hipCheck(hipStreamSynchronize((hipStream_t)stream), "set_adam_steps");
+  });
 }
 W2L_API int w2l_trainer_set_input_sizes(void* h, const float* inputSizesDev) {
   if (!h) return W2L_EINVAL;

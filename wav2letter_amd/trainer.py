@@ -49,6 +49,9 @@ def _lib_tr():
         L.w2l_trainer_set_mixed_precision_convs.argtypes = [vp, i]
         L.w2l_trainer_set_weight_grad_stream.argtypes = [vp, i]
         L.w2l_trainer_set_optimizer.argtypes = [vp, i, i]
+        L.w2l_trainer_set_adam.argtypes = [vp, f, f, f, f]
+        L.w2l_trainer_adam_steps.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), vp]
+        L.w2l_trainer_set_adam_steps.argtypes = [vp, u64, u64, vp]
         L.w2l_trainer_set_dropout.argtypes = [vp, d, d]
         L.w2l_trainer_bind_state2.argtypes = [vp, vp]
         L.w2l_trainer_set_input_sizes.argtypes = [vp, vp]
@@ -196,12 +199,36 @@ class Trainer:
             self._bind()
 
     def _bind_state2(self):
-        if self.params is not None and "adadelta" in getattr(self, "_optim", ()) and getattr(self, "state2", None) is None:
-            self.state2 = torch.zeros_like(self.params)            # Adadelta's accDelta (accGrad lives in self.mom)
+        optim = getattr(self, "_optim", ())
+        if self.params is not None and ("adadelta" in optim or "adam" in optim) and getattr(self, "state2", None) is None:
+            self.state2 = torch.zeros_like(self.params)            # Adadelta's accDelta / Adam's v (accGrad / m live in self.mom)
             if getattr(self, "_pending_state2", None) is not None:  # checkpoint.load() before to_device()
                 self.state2.copy_(torch.from_numpy(self._pending_state2))
                 self._pending_state2 = None
             _check(self.L.w2l_trainer_bind_state2(self.h, self.state2.data_ptr()), "bind_state2")
+        if self._on_gpu() and getattr(self, "_pending_adam_steps", None) is not None:
+            steps, self._pending_adam_steps = self._pending_adam_steps, None
+            self.set_adam_steps(*steps)
+
+    def _on_gpu(self):
+        return self.params is not None and self.params.is_cuda
+
+    def adam_steps(self):
+        """(network, criterion): the updates Adam has applied to each group -- what its bias correction reads.  The counts live on
+        the device, where an update is skipped; a skipped update advances neither (synchronises)"""
+        if not self._on_gpu():
+            return tuple(getattr(self, "_pending_adam_steps", None) or (0, 0))
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _check(self.L.w2l_trainer_adam_steps(self.h, C.byref(a), C.byref(b), self._stream()), "adam_steps")
+        return a.value, b.value
+
+    def set_adam_steps(self, net_steps, crit_steps):
+        """restore adam_steps() (checkpoints); before to_device() the counts wait for it, as the arenas do (a trainer whose arenas
+        stay on the host -- layout only -- just keeps them)"""
+        if not self._on_gpu():
+            self._pending_adam_steps = (int(net_steps), int(crit_steps))
+            return
+        _check(self.L.w2l_trainer_set_adam_steps(self.h, int(net_steps), int(crit_steps), self._stream()), "set_adam_steps")
 
     def plan(self, B, T, L):
         af, cw, to = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
@@ -340,11 +367,22 @@ class Trainer:
         before forward_backward returns (on by default; same results either way, see w2l_trainer_set_weight_grad_stream)"""
         _check(self.L.w2l_trainer_set_weight_grad_stream(self.h, int(bool(on))), "weight-gradient stream")
 
-    def set_optimizer(self, netoptim="sgd", critoptim="sgd"):
-        """--netoptim / --critoptim of the reference Trainer (Train.cpp:577-582): "sgd" (momentum) "adagrad" or "adadelta" (rho 0.9, eps 1e-8:
-        the recipe of BASELINE config 5).  Adagrad keeps its squared-gradient sums in the momentum arena; Adadelta its accGrad
-        there and accDelta in a second arena (self.state2)"""
-        kinds = {"sgd": 0, "adagrad": 1, "adadelta": 2}
+    def set_optimizer(self, netoptim="sgd", critoptim="sgd", beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
+        """--netoptim / --critoptim of the reference Trainer (Train.cpp:577-582): "sgd" (momentum) "adagrad", "adadelta" (rho 0.9, eps 1e-8:
+        the recipe of BASELINE config 5) or "adam".  Adagrad keeps its squared-gradient sums in the momentum arena; Adadelta its
+        accGrad there and accDelta in a second arena (self.state2); Adam m there and v in self.state2.
+        beta1, beta2, eps, weight_decay: Adam's (--adambeta1 --adambeta2 --optimepsilon --weightdecay, cpc/Train.cpp:569-580); the
+        decay is decoupled and acts on the network's parameters only"""
+        kinds = {"sgd": 0, "adagrad": 1, "adadelta": 2, "adam": 3}
+        if netoptim not in kinds or critoptim not in kinds:
+            raise _lib.W2LInvalidArgument(f"set_optimizer: unknown optimizer in {(netoptim, critoptim)} (this build: {', '.join(kinds)})")
+        adam = (float(beta1), float(beta2), float(eps), float(weight_decay))
+        if "adam" in (netoptim, critoptim):
+            if self.L.w2l_trainer_set_adam(self.h, *adam) != 0:
+                raise _lib.W2LInvalidArgument(f"set_optimizer: Adam needs beta1, beta2 in [0, 1), eps >= 0 and weight_decay >= 0, got {adam}")
+            self._adam = adam
+        elif adam != (0.9, 0.999, 1e-8, 0.0):
+            raise _lib.W2LInvalidArgument("set_optimizer: beta1 / beta2 / eps / weight_decay are Adam's; neither optimizer is \"adam\"")
         _check(self.L.w2l_trainer_set_optimizer(self.h, kinds[netoptim], kinds[critoptim]), "set_optimizer")
         self._optim = (netoptim, critoptim)
         self._bind_state2()
