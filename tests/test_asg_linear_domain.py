@@ -81,6 +81,27 @@ def test_fcc_kernel_model_lagged_scale(T, N, scale, tscale):
     assert np.abs(dA - odA).max() < 1e-4 * np.abs(odA).max()
 
 
+def test_fcc_kernel_model_backward_normaliser_drifts_unless_it_is_refreshed():
+    """quiet emissions under loud transitions, 2000 frames: with ONE normaliser for all frames (chunk = None, the kernel as it was)
+    sum_i u_t b_t walks away from the last frame's value and dx is off by more than the parity bar of 1e-4; taken anew at the first
+    frame of every chunk of 16 (fcc_mitm_bwd's mitm_ginv) dx stays within 1e-5"""
+    from tools.exp import criterion_fuzz as F
+    case = list(F.draw_cases(4, 42, **F.RECIPE))[3]   # the case of the device fuzz that showed it: N = 30, T = 2000, x * 0.1, A * 2, diagonal 4
+    assert (case.N, case.T, case.xs, case.as_, case.diag) == (30, 2000, 0.1, 2.0, 4.0)
+    x, A = case.x[:1], case.A
+    f = O.FCC(x, A, np.array([1], np.int32))
+    f.forward()
+    odx, odA = f.backward()
+    _, u, q, _ = LD.fcc_kernel_model(x[0], A)
+    err = {}
+    for chunk in (None, 16):
+        dx, dA = LD.fcc_kernel_model_backward(u, q, A, chunk=chunk)
+        err[chunk] = (np.abs(dx - odx[0]).max() / np.abs(odx).max(), np.abs(dA - odA).max() / np.abs(odA).max())
+    print(err)
+    assert err[None][0] > 1e-4, err
+    assert err[16][0] < 1e-5 and err[16][1] < 1e-5, err
+
+
 @pytest.mark.parametrize("T,N,L,S,scale,P", [(40, 6, 8, 5, 1.0, 1), (500, 30, 100, 77, 1.0, 2), (2000, 30, 300, 300, 1.0, 5),
                                              (2000, 30, 300, 120, 8.0, 5), (300, 30, 300, 299, 2.0, 5), (64, 30, 40, 1, 1.0, 1),
                                              (700, 30, 64, 64, 30.0, 1), (900, 30, 320, 310, 25.0, 5), (301, 30, 300, 298, 22.0, 5), (301, 30, 300, 300, 22.0, 5),

@@ -40,6 +40,7 @@
 // Continuing each recursion on the OTHER half's scale sequence keeps sum_i u_t[i] b_t[i] = G (the middle frame's value) at every
 // frame, so the posterior is u_t b_t / G with no per-frame normaliser, the continuation chains carry no scale bookkeeping at all, and
 //   d loss / d x_t = g u_t b_t / G,   r_t = b_t q_t / G  (the operand of the transition-gradient kernel fcc_dtrans_mfma).
+// (In fp32 the equality drifts by 1e-7 per frame, so the helper wave takes G from the first frame of each chunk: mitm_ginv.)
 // T / 2 dependent frames per pass, 2 B workgroups.  Workspace per frame: ahat[t] = u_t, logs[t] = the scale q the frame's u_t was
 // produced with (q_t for t <= m, q'_t above), r[t] = r_t; r2[t] = b_t q'_t of the forward pass (t > m).
 #pragma once
@@ -395,6 +396,15 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 }
 
 // ------------------------------------------------------------------------------------------------ backward: the two continuations
+// 1 / G_t, G_t = sum_i u_t[i] b_t[i] summed over the wave (`ub`: the product in the lanes that own a state, 0 elsewhere).  In exact
+// arithmetic G_t is the middle frame's G at every frame; in fp32 the two recursions drift apart by 1e-7 per frame -- the posterior
+// u_t b_t / G was off by 1.1e-4 a thousand frames from the middle (N = 30, T = 2000, quiet emissions, transitions x 2 with diagonal 4;
+// tests/test_gpu_criterion_fuzz.py).  The helper wave measures G_t at the first frame of every chunk: off the chain.
+__device__ __forceinline__ float mitm_ginv(float ub, float ginvMid) {
+  const float Gt = wave_sum(ub);
+  return (Gt > 0.f && Gt < INFINITY) ? 1.f / Gt : ginvMid;
+}
+
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) void fcc_mitm_bwd(int T, int N, const float* __restrict__ trans, const float* __restrict__ grad,
                                                     float* __restrict__ inputGrad, FccWs ws, int dir0 = 0) {
   __shared__ float sQ[2][kDppChunk][64];   // helper -> chain: the frame's scale
@@ -411,7 +421,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
   float* __restrict__ dxb = inputGrad + (size_t)b * T * N;
   float* __restrict__ rb = ws.r + (size_t)b * T * N;
   const float ginv = ws.ginv[b];
-  const float gsc = ws.scale[b] * grad[b] * ginv;
+  const float gsc0 = ws.scale[b] * grad[b];
   if (tid < 32) {
     float rm = NEG;
 #pragma unroll
@@ -445,6 +455,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
       int c = 0;
       float up[kDppChunk], qp[kDppChunk];
       auto emit = [&](int th, int buf) {
+        // G_t of the chunk's first frame (frame th >= 0; s = 0 is held in arrangement G when PAR), each state counted once
+        const float gi = mitm_ginv((PAR ? (g.primG && actG) : (g.primH && actH)) ? up[0] * sB[buf][0][lane] : 0.f, ginv);
+        const float gs = gsc0 * gi;
 #pragma unroll
         for (int s = 0; s < kDppChunk; ++s) {
           const int t = th - s;
@@ -453,8 +466,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
           const int sx = odd ? g.sG : g.sH;
           const float bv = sB[buf][s][lane];
           if (st && t >= 0) {
-            dxb[(size_t)t * N + sx] = g.ok ? gsc * (up[s] * bv) : __builtin_nanf("");
-            if (t >= 1) rb[(size_t)t * N + sx] = ginv * (bv * qp[s]);
+            dxb[(size_t)t * N + sx] = g.ok ? gs * (up[s] * bv) : __builtin_nanf("");
+            if (t >= 1) rb[(size_t)t * N + sx] = gi * (bv * qp[s]);
           }
         }
       };
@@ -537,6 +550,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     for (int s = 0; s < kDppChunk; ++s) sQ[0][s][lane] = qc[s];
     W2L_LDS_BARRIER();
     auto emit = [&](int k0, int buf) {
+      // G_t of the chunk's first frame (k0 < nF; s = 0 is held in arrangement G when PAR): u_t b_t = (E u_{t-1}) (q_t b_t)
+      const float gi = mitm_ginv((PAR ? (g.primG && actG) : (g.primH && actH)) ? sB[buf][0][lane] * rp[0] : 0.f, ginv);
+      const float gs = gsc0 * gi;
 #pragma unroll
       for (int s = 0; s < kDppChunk; ++s) {
         const int t = t1 + k0 + s;
@@ -546,8 +562,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         const float sv = sB[buf][s][lane];
         if (st && k0 + s < nF) {
           uw[(size_t)t * N + sx] = sv * qp[s];                                        // u_t (the chain's own product: same rounding)
-          dxb[(size_t)t * N + sx] = g.ok ? gsc * (sv * rp[s]) : __builtin_nanf("");   // u_t b_t = (E u_{t-1}) (q_t b_t)
-          rb[(size_t)t * N + sx] = ginv * rp[s];
+          dxb[(size_t)t * N + sx] = g.ok ? gs * (sv * rp[s]) : __builtin_nanf("");   // u_t b_t = (E u_{t-1}) (q_t b_t)
+          rb[(size_t)t * N + sx] = gi * rp[s];
         }
       }
     };
