@@ -841,6 +841,13 @@ int w2l_trainer_param_info(void* h, int i, char* name, int nameCap, size_t* nume
 int w2l_trainer_init_params(void* h, float* h_params, uint64_t seed);
 int w2l_trainer_import_param(void* h, int i, const float* h_ref, float* h_params);
 int w2l_trainer_export_param(void* h, int i, const float* h_arena, float* h_ref);
+/* Plans one batch geometry (B utterances of T frames, targets padded to L) and reports what to bind for it.  May be called again
+ * at any time, for any other shape.  A plan KEEPS parameters, gradients and optimizer arenas (and their binding), the step count,
+ * Adam's step counts, the count of skipped updates and the last gradient norm, optimizer kind and hyperparameters, the
+ * mixed-precision switches, dropout overrides, gradient buckets and the linseg countdown.  It DROPS the activation arena and the
+ * criterion workspace (sized for the shape before), the forward pass w2l_trainer_backward would differentiate, and the input
+ * sizes: until the next w2l_trainer_bind every forward / forward_backward / backward / update / evaluate returns W2L_EINVAL
+ * ("trainer not planned / bound"), and sizes are given again with w2l_trainer_set_input_sizes where they are used. */
 int w2l_trainer_plan(void* h, int B, int T, int L, size_t* arenaFloats, size_t* critWsBytes, int* Tout);
 /* params / momentum: w2l_trainer_param_floats floats; grads: w2l_trainer_grad_floats floats (4-float tail) */
 int w2l_trainer_bind(void* h, float* params, float* grads, float* momentum, float* arena, void* critWs);
@@ -858,6 +865,8 @@ int w2l_trainer_backward(void* handle, const float* dEmission, void* stream);
  * clipping -- and counts it (w2l_trainer_skipped_updates). */
 int w2l_trainer_update(void* h, float lr, float lrcrit, float momentum, float maxGradNorm,
                        float totalBatch, int clampCrit, void* stream);
+/* updates skipped so far, over the life of the handle: the count (and the norm w2l_trainer_grad_norm reports) lives in device
+ * memory the trainer owns and survives w2l_trainer_plan / w2l_trainer_bind.  0 before the first update.  Synchronises. */
 int w2l_trainer_skipped_updates(void* h, uint64_t* count, void* stream);
 /* optimizer of the network / criterion parameters for w2l_trainer_update: 0 = SGD with momentum (default), 1 = Adagrad
  * (eps 1e-8; the momentum arena holds the accumulated squared gradients), 2 = Adadelta (rho 0.9, eps 1e-8; accGrad in the
@@ -874,7 +883,8 @@ int w2l_trainer_set_adam(void* h, float beta1, float beta2, float eps, float wei
 int w2l_trainer_adam_steps(void* h, uint64_t* netSteps, uint64_t* critSteps, void* stream);
 int w2l_trainer_set_adam_steps(void* h, uint64_t netSteps, uint64_t critSteps, void* stream);
 /* input sizes of the NEXT forward calls (device, [B] floats in any unit; NULL = every utterance fills the batch): the
- * Transformer blocks mask the padded keys as the reference's forwardSequentialModuleWithPadMask does.  Call after plan. */
+ * Transformer blocks mask the padded keys as the reference's forwardSequentialModuleWithPadMask does.  Call after plan: the
+ * pointer holds B floats of the planned B, so w2l_trainer_plan forgets it (back to NULL) and the caller gives the new batch's. */
 int w2l_trainer_set_input_sizes(void* h, const float* inputSizesDev);
 int w2l_trainer_bind_state2(void* h, float* state2);
 int w2l_trainer_viterbi(void* h, const float* emission, int* path, void* stream);

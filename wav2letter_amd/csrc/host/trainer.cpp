@@ -31,7 +31,18 @@ struct Trainer {
   float *params = nullptr, *grads = nullptr, *mom = nullptr, *arena = nullptr;
   void* critWs = nullptr;
   float *loss = nullptr, *gradLoss = nullptr, *dEm = nullptr;
-  double* sumsq = nullptr;   // acc[8]: see w2l_grad_guard (include/w2l_hip.h)
+  // acc[8] of w2l_grad_guard (include/w2l_hip.h): [2] the last update's squared norm, [4] the count of skipped updates.  Owned, on
+  // the DEVICE, allocated and zeroed once (guardBuf) and kept across w2l_trainer_plan / w2l_trainer_bind: both are facts of the
+  // run, not of a plan.  (The activation arena keeps the 64 floats it used to lend them, unused: arena sizes do not move.)
+  double* sumsq = nullptr;
+  double* guardBuf() {
+    if (!sumsq) {
+      hipCheck(hipMalloc((void**)&sumsq, 8 * sizeof(double)), "guard accumulators");
+      hipCheck(hipMemset(sumsq, 0, 8 * sizeof(double)), "guard accumulators");
+      hipCheck(hipStreamSynchronize(nullptr), "guard accumulators");   // once: whatever stream the first update runs on sees the zeros
+    }
+    return sumsq;
+  }
   float* batchSlot = nullptr;  // grads[paramFloats]: this rank's utterance count, summed by the SAME all-reduce as the gradients
   const float* emission = nullptr;
   uint32_t step = 0;
@@ -40,7 +51,6 @@ struct Trainer {
   int scaleMode = 0;
   SequenceCriterion* activeCrit() { return (linseg && step < linsegUpdates) ? linseg.get() : crit.get(); }
   std::string lastError;
-  bool guardZeroed = false;
   int netOptim = 0, critOptim = 0;  // 0 SGD(momentum), 1 Adagrad (variance in the momentum arena), 2 Adadelta (+ state2), 3 Adam (+ state2)
   float adamBeta1 = 0.9f, adamBeta2 = 0.999f, adamEps = 1e-8f, adamWd = 0.f;   // w2l_trainer_set_adam
   // Adam's applied-step counts [network, criterion], owned, on the DEVICE: the update is skipped there (grad_guard_k) and a
@@ -74,6 +84,7 @@ struct Trainer {
     for (auto e : bucketEvents) (void)hipEventDestroy(e);
     if (evalMem) (void)hipFree(evalMem);
     if (adamSteps) (void)hipFree(adamSteps);
+    if (sumsq) (void)hipFree(sumsq);
   }
 };
 
@@ -163,12 +174,20 @@ W2L_API int w2l_trainer_export_param(void* h, int i, const float* h_arena, float
   TRY(h, { if (i < 0 || i >= (int)t->net->params().size()) throw std::invalid_argument("bad param index"); t->net->exportParam(i, h_arena, h_ref); });
 }
 
-// plan for a batch geometry: B utterances of T frames, targets padded to L.
+// plan for a batch geometry: B utterances of T frames, targets padded to L.  A plan DROPS what belonged to the one before: the
+// arena and criterion-workspace binding (sized for the old shape), the emission pointer of the last forward (Sequential::plan has
+// forgotten that pass) and the input sizes (B of them, of the old B) -- w2l_trainer_bind, and w2l_trainer_set_input_sizes where
+// sizes are used, come again before the next pass.  Everything else stays: parameters, gradients and optimizer arenas, the step
+// count, Adam's counts, the guard's count and last norm, optimizer kind and hyperparameters, the precision switches, dropout
+// overrides, gradient buckets, the linseg countdown.
 W2L_API int w2l_trainer_plan(void* h, int B, int T, int L, size_t* arenaFloats, size_t* critWsBytes,
                              int* Tout) {
   Trainer* t = (Trainer*)h;
   TRY(h, {
     if (B <= 0 || T <= 0 || L <= 0) throw std::invalid_argument("plan: B, T, L must be positive");
+    t->arena = nullptr; t->critWs = nullptr; t->emission = nullptr; t->inputSizes = nullptr;
+    t->dEm = t->loss = t->gradLoss = nullptr;
+    t->arenaFloats = 0;   // (a plan that throws leaves no plan)
     size_t used = t->net->plan(B, T, t->nFeat);
     t->B = B; t->T = T; t->L = L;
     t->Tout = t->net->outAct().T;
@@ -196,9 +215,8 @@ W2L_API int w2l_trainer_bind(void* h, float* params, float* grads, float* moment
   t->dEm = arena + used;
   t->loss = t->dEm + emSlots;
   t->gradLoss = t->loss + bSlots;
-  t->sumsq = (double*)(t->gradLoss + bSlots);  // 64 floats = 32 doubles, 256-byte aligned
-  t->batchSlot = grads + t->netFloats + t->critFloats;
-  t->guardZeroed = false;
+  t->batchSlot = grads + t->netFloats + t->critFloats;   // (the arena's last 64 floats: unused, once the guard accumulators)
+  t->emission = nullptr;   // a pass in another arena is not this binding's to differentiate
   return W2L_OK;
 }
 
@@ -231,6 +249,7 @@ static Ctx makeCtx(Trainer* t, void* stream, bool train) {
 W2L_API int w2l_trainer_forward(void* h, const float* x, int train, const float** emission, void* stream) {
   Trainer* t = (Trainer*)h;
   TRY(h, {
+    requireBound(t);
     if (!x) throw std::invalid_argument("forward: null input");
     Ctx c = makeCtx(t, stream, train != 0);
     { MatmulMode mm(t->mixedPrecision); t->emission = t->net->forward(c, t->arena, x); }
@@ -244,6 +263,7 @@ W2L_API int w2l_trainer_forward_backward(void* h, const float* x, const int* tar
                                          void* stream) {
   Trainer* t = (Trainer*)h;
   TRY(h, {
+    requireBound(t);
     if (!x || !target) throw std::invalid_argument("forward_backward: null input");   // before anything is enqueued with them
     Ctx c = makeCtx(t, stream, true);
     { MatmulMode mm(t->mixedPrecision); t->emission = t->net->forward(c, t->arena, x); }
@@ -287,7 +307,12 @@ W2L_API int w2l_trainer_update(void* h, float lr, float lrcrit, float momentum, 
     hipStream_t s = (hipStream_t)stream;
     // totalBatch > 0: the caller's number; <= 0: the all-reduced utterance count in the gradient arena's tail
     const float gs = totalBatch > 0.f ? 1.f / totalBatch : 0.f;
-    if (!t->guardZeroed) { hipCheck(hipMemsetAsync(t->sumsq, 0, sizeof(double) * 8, s), "memset"); t->guardZeroed = true; }
+    // what the chosen optimizers need bound, before anything is enqueued
+    const bool needState = t->netOptim != 0 || (t->critOptim != 0 && t->critFloats);
+    const bool needState2 = t->netOptim >= 2 || (t->critOptim >= 2 && t->critFloats);
+    if (needState && !t->mom) throw std::invalid_argument("Adagrad / Adadelta need the momentum arena bound (it holds the gradient statistics)");
+    if (needState2 && !t->state2) throw std::invalid_argument("Adadelta needs w2l_trainer_bind_state2");
+    t->guardBuf();
     // --linseg: the reference trains the warm-up phase with its OWN optimizers (linNetoptim / linCritoptim,
     // Train.cpp:589-617), so the ASG phase proper starts from fresh optimizer state: clear the momentum arena -- SGD
     // velocity, or the Adagrad / Adadelta / Adam gradient statistics it holds --, the second arena of Adadelta and Adam, and
@@ -304,10 +329,6 @@ W2L_API int w2l_trainer_update(void* h, float lr, float lrcrit, float momentum, 
     w2lCheck(w2l_sumsq(t->grads, t->netFloats, t->sumsq, 1, s), "sumsq");
     w2lCheck(w2l_sumsq(t->grads + t->netFloats, t->critFloats, t->sumsq + 1, 1, s), "sumsq");
     w2lCheck(w2l_grad_guard(t->sumsq, totalBatch > 0.f ? nullptr : t->batchSlot, clampCrit, s), "guard");
-    const bool needState = t->netOptim != 0 || (t->critOptim != 0 && t->critFloats);
-    const bool needState2 = t->netOptim >= 2 || (t->critOptim >= 2 && t->critFloats);
-    if (needState && !t->mom) throw std::invalid_argument("Adagrad / Adadelta need the momentum arena bound (it holds the gradient statistics)");
-    if (needState2 && !t->state2) throw std::invalid_argument("Adadelta needs w2l_trainer_bind_state2");
     uint64_t* adamSteps = (t->netOptim == 3 || (t->critOptim == 3 && t->critFloats)) ? t->adamStepsBuf() : nullptr;
     auto stepOne = [&](int kind, size_t off, size_t n, float rate, float mom, float clip, const char* what) {
       float* v = t->mom ? t->mom + off : nullptr;
@@ -330,6 +351,7 @@ W2L_API int w2l_trainer_update(void* h, float lr, float lrcrit, float momentum, 
 // eval-mode network forward (no dropout) + the criterion's score on the planned shape.  Advances no counter: the dropout seed of
 // the next training step comes from the update count alone (makeCtx), and the criterion scores on a workspace of its own.
 static void evaluateImpl(Trainer* t, const float* x, const int* target, float** lossDev, int** pathDev, void* stream) {
+  requireBound(t);
   if (!x || !target) throw std::invalid_argument("evaluate: null input");
   Ctx c = makeCtx(t, stream, false);
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -429,10 +451,12 @@ W2L_API int w2l_trainer_set_linseg(void* h, uint32_t updates) {
 W2L_API int w2l_trainer_grad_norm(void* h, double* norm, void* stream) {
   Trainer* t = (Trainer*)h;
   TRY(h, {
-    if (!t->sumsq || !norm) throw std::invalid_argument("trainer not bound");
+    if (!t || !norm) throw std::invalid_argument("grad_norm: null argument");
     double s = 0.0;
-    hipCheck(hipMemcpyAsync(&s, t->sumsq + 2, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "grad norm");
-    hipCheck(hipStreamSynchronize((hipStream_t)stream), "grad norm");
+    if (t->sumsq) {   // (never allocated: no update has run, the norm is 0)
+      hipCheck(hipMemcpyAsync(&s, t->sumsq + 2, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "grad norm");
+      hipCheck(hipStreamSynchronize((hipStream_t)stream), "grad norm");
+    }
     *norm = std::sqrt(s);
   });
 }
@@ -441,9 +465,9 @@ W2L_API int w2l_trainer_grad_norm(void* h, double* norm, void* stream) {
 W2L_API int w2l_trainer_skipped_updates(void* h, uint64_t* count, void* stream) {
   Trainer* t = (Trainer*)h;
   TRY(h, {
-    if (!t->sumsq || !count) throw std::invalid_argument("trainer not bound");
+    if (!t || !count) throw std::invalid_argument("skipped_updates: null argument");
     double s = 0.0;
-    if (t->guardZeroed) {
+    if (t->sumsq) {   // (never allocated: no update has run)
       hipCheck(hipMemcpyAsync(&s, t->sumsq + 4, sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream), "skipped");
       hipCheck(hipStreamSynchronize((hipStream_t)stream), "skipped");
     }

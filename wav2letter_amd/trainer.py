@@ -231,8 +231,12 @@ class Trainer:
         _check(self.L.w2l_trainer_set_adam_steps(self.h, int(net_steps), int(crit_steps), self._stream()), "set_adam_steps")
 
     def plan(self, B, T, L):
+        """plan (or re-plan) the batch geometry: fresh activation arena and criterion workspace, bound at once when the parameters
+        are on the device.  Parameters, optimizer state, counters and switches stay; the input sizes of the shape before are
+        forgotten (w2l_trainer_plan) -- set_input_sizes again for the new batch"""
         af, cw, to = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
         _check(self.L.w2l_trainer_plan(self.h, B, T, L, C.byref(af), C.byref(cw), C.byref(to)), "plan")
+        self._input_sizes = None
         self.B, self.T, self.Lt, self.Tout = B, T, L, to.value
         self.arena = torch.empty(af.value, dtype=torch.float32, device=self.device)
         self.crit_ws = torch.empty(max(cw.value, 256), dtype=torch.uint8, device=self.device)
@@ -360,7 +364,10 @@ class Trainer:
             self._mixed_convs = bool(convs)
             self._eval_plans.clear()
             if self.B:
+                sizes = getattr(self, "_input_sizes", None)   # the same shape again: its sizes still fit
                 self.plan(self.B, self.T, self.Lt)
+                if sizes is not None:
+                    self.set_input_sizes(sizes)
 
     def set_weight_grad_stream(self, on=True):
         """fp32 backward: the weight, bias and filter gradients on the network's own side stream, joined into the step's stream
