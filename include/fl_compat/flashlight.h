@@ -680,7 +680,7 @@ class Lexicon;   // fl_compat/lexicon.h
 // The options and the result of CTCLoss::beamSearch and ASGLoss::beamSearch (fl_compat ADDITIONS to the reference's interface).
 // "token classes" below are N-1 for CTC (blank = N-1 is none) and all N for ASG.
 struct BeamSearchOptions {
-  int beamSize = 64;                  // W, 1..64; 1..1024 with wide
+  int beamSize = 64;                  // W, 1..64; 1..1024 with wide; 1..8192 with xl
   int beamSizeToken = 64;             // K, clipped to the token classes (CTC: N-1, ASG: N), then <= 64
   float beamThreshold = 1.0f / 0.0f;  // candidates below best - threshold are dropped; +inf: none
   bool logAdd = false;                // false: max over a prefix's alignments (the 1-best is the greedy transcript); true: their sum
@@ -700,6 +700,7 @@ struct BeamSearchOptions {
   float wordScore = 0.f;              // every completed word adds lmWeight * log p_LM(word | words before) + wordScore
   int maxWords = 0;                   // rows of `words`, 0 = Lmax
   bool wide = false;                  // every search above on the wide kernels (the w2l_*_wide entry points): the same contract, the same bytes at W <= 64
+  bool xl = false;                    // every search above on the xl kernels (the w2l_*_xl entry points): the same contract, the wide kernels' bytes at W <= 1024; with wide: std::invalid_argument
 };
 struct BeamSearchResult {
   af::array labels;    // (Lmax, M, B) s32: the first min(length, Lmax) labels, -1 beyond
@@ -803,7 +804,7 @@ class FL_COMPAT_API CTCLoss : public SequenceCriterion {
   // search over the emissions without lexicon or LM (w2l_ctc_beam_search; the contract is in w2l_hip.h).  inputSizes as in
   // viterbiPathWithTarget.  The hypotheses are already collapsed label rows: turn them into letters / words with tknLabels2Ltr /
   // tknLabels2Wrd (fl_compat/text.h), not with tknPrediction2Ltr.  Refused arguments: std::invalid_argument; a beam or token
-  // count beyond the kernel's 64 (with options.wide a beam beyond 1024): std::runtime_error.
+  // count beyond the kernel's 64 (with options.wide a beam beyond 1024, with options.xl beyond 8192): std::runtime_error.
   using BeamSearchOptions = ::fl::pkg::speech::BeamSearchOptions;   // hoisted: ASGLoss::beamSearch takes the same
   using BeamSearchResult = ::fl::pkg::speech::BeamSearchResult;
   BeamSearchResult beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& options);

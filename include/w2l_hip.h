@@ -412,6 +412,55 @@ int w2l_asg_beam_search_lex_wide(int B, int T, int N, const float* input /*[B][T
                                  int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
                                  float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
                                  int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream);
+/* The xl twins of the five beam searches: the beam widths the reference's recipes ask for (1500, 2500, 5000, 8000).  Each takes the
+ * argument list of its sibling and obeys its sibling's contract word for word -- frame tokens, stay / ext / merge / prune, the order
+ * and its tie key, the sil / in / word slots, the ASG rules, the end rule and the EOS term, the outputs, the order of the refusals
+ * -- with two differences: W may be 1..8192 and M 1..W.  K after clipping stays <= 64; W > 8192 or K > 64 is W2L_EUNSUPPORTED (and
+ * a workspace size of 0), after every W2L_EINVAL, before anything touches the device; T * W > 2^29 is W2L_EUNSUPPORTED as well
+ * (node ids are ints).  The kernels are a third family (csrc/criterion_beam_xl.hpp, DESIGN 3.24: the wide family's algorithm with
+ * one workgroup per utterance whose threads own entries tid, tid + 1024, ..., the beam, the gone masks and the stays in the
+ * workspace, the node -> rank hash and then the survivors' sort in up to 128 KiB of LDS), but every value is made by the sibling's
+ * operation sequence and the ranks depend on the keys alone: with logAdd = 0 the outputs equal the wide twin's bit for bit at every
+ * W both accept, and with logAdd = 1 they equal them too (a stay receives at most one merged term, so no sum depends on an order).
+ * The workspace is the wide twin's at that W -- 8 bytes per possible candidate of a frame and utterance, W * K (* 7 with a
+ * lexicon) + W of them -- plus 80 (lexicon: 136) bytes per beam entry and utterance; the prefix table is 8 * pow2(2 * T * W) bytes
+ * per utterance, 256 MiB at T = 2000, W = 8192. */
+size_t w2l_ctc_beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_xl(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                           int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                           int nbest /*M*/, int maxLen /*Lmax*/,
+                           int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                           void* workspace, w2l_stream_t stream);
+size_t w2l_ctc_beam_lm_xl_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lm_xl(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                              int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                              int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                              const float* classScore /*[N-1] or NULL*/, float eosScore,
+                              int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                              float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream);
+size_t w2l_ctc_beam_lex_xl_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lex_xl(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                               int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                               int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                               const void* lexicon, float wordScore, float eosScore,
+                               int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                               float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                               int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream);
+size_t w2l_asg_beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_xl(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                           const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/, float threshold,
+                           int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm /*or NULL*/,
+                           int lmHasEos, float lmWeight, const float* classScore /*[N] or NULL*/, float eosScore,
+                           int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                           float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream);
+size_t w2l_asg_beam_lex_xl_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_lex_xl(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                               const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/,
+                               float threshold, int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm,
+                               int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
+                               int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                               float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                               int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the

@@ -113,8 +113,10 @@ class _SIGS:
     w2l_ctc_align = (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p])
     w2l_ctc_beam_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_ctc_beam_wide_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_ctc_beam_xl_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_ctc_beam_search = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p])
     w2l_ctc_beam_search_wide = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p])
+    w2l_ctc_beam_search_xl = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p])
     w2l_ngram_lm_build = (_i, [_i, _p, _p, _p, _p, _i, _f, _p, _p])
     w2l_ngram_lm_from_arpa = (_i, [C.c_char_p, _i, _p, _p, _p, _p])
     w2l_ngram_lm_info = (_i, [_p, _p, _p, _p, _p, _p])
@@ -122,28 +124,38 @@ class _SIGS:
     w2l_ngram_lm_score = (_i, [_p, _i, _i, _p, _p])
     w2l_ctc_beam_lm_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_ctc_beam_lm_wide_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_ctc_beam_lm_xl_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_ctc_beam_search_lm = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _p, _p, _p, _p, _p, _p])
     w2l_ctc_beam_search_lm_wide = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _p, _p, _p, _p, _p, _p])
+    w2l_ctc_beam_search_lm_xl = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _p, _p, _p, _p, _p, _p])
     w2l_lexicon_build = (_i, [_i, _i, _sz, _p, _p, _p, _p, _i, _p, _p, _p])
     w2l_lexicon_info = (_i, [_p, _p, _p, _p, _p, _p])
     w2l_lexicon_child = (_i, [_p, _i, _i, _p])
     w2l_lexicon_node = (_i, [_p, _i, _p, _p, _p, _p])
     w2l_asg_beam_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_asg_beam_wide_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_asg_beam_xl_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_asg_beam_search = (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _p, _p, _p, _p, _p, _p])
     w2l_asg_beam_search_wide = (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _p, _p, _p, _p, _p, _p])
+    w2l_asg_beam_search_xl = (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _p, _p, _p, _p, _p, _p])
     w2l_asg_beam_lex_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_asg_beam_lex_wide_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_asg_beam_lex_xl_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_asg_beam_search_lex = (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p, _i,
                                     _p, _p, _p, _p])
     w2l_asg_beam_search_lex_wide = (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p, _i,
                                          _p, _p, _p, _p])
+    w2l_asg_beam_search_lex_xl = (_i, [_i, _i, _i, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p, _i,
+                                       _p, _p, _p, _p])
     w2l_ctc_beam_lex_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_ctc_beam_lex_wide_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_ctc_beam_lex_xl_workspace_size = (_sz, [_i, _i, _i, _i, _i])
     w2l_ctc_beam_search_lex = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p, _i, _p, _p,
                                     _p, _p])
     w2l_ctc_beam_search_lex_wide = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p, _i, _p, _p,
                                          _p, _p])
+    w2l_ctc_beam_search_lex_xl = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p, _i, _p, _p,
+                                       _p, _p])
     w2l_host_last_error = (C.c_char_p, [])
     w2l_gemm_f32 = (_i, [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _p])
     w2l_linear_forward = (_i, [_i, _i, _i, _p, _p, _p, _p, _i, _p])

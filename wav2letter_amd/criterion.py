@@ -303,20 +303,26 @@ def ctc_align(emission, target, frames=None, with_score=True):
 
 
 def _wide(L, name, wide):
-    """the entry point `name`, or its wide twin: w2l_x_beam_search_y -> w2l_x_beam_search_y_wide, w2l_x_workspace_size ->
-    w2l_x_wide_workspace_size"""
-    if not wide:
+    """the entry point `name`, or its wide or xl twin: w2l_x_beam_search_y -> w2l_x_beam_search_y_wide / _xl, w2l_x_workspace_size
+    -> w2l_x_wide_workspace_size / w2l_x_xl_workspace_size.  wide: False, True or "xl" """
+    if isinstance(wide, str):
+        if wide != "xl":
+            raise _lib.W2LInvalidArgument(f'beam search: wide must be False, True or "xl", not {wide!r}')
+        suffix = "_xl"
+    elif not wide:
         return getattr(L, name)
+    else:
+        suffix = "_wide"
     if name.endswith("_workspace_size"):
-        return getattr(L, name[:-len("_workspace_size")] + "_wide_workspace_size")
-    return getattr(L, name + "_wide")
+        return getattr(L, name[:-len("_workspace_size")] + suffix + "_workspace_size")
+    return getattr(L, name + suffix)
 
 
 def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=None,
                     nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
                     max_words=None, wide=False):
     """CTC prefix beam search without lexicon or LM (w2l_ctc_beam_search; the contract is in include/w2l_hip.h): `emission`
-    [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64; <= 1024 with wide=True), beam_token = K (clipped to N-1, then <= 64),
+    [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64; <= 1024 with wide=True; <= 8192 with wide="xl"), beam_token = K (clipped to N-1, then <= 64),
     log_add: sum (True) or max (False) over the alignments of a prefix; normalize: search on log-softmax rows (default: log_add --
     sums only mean something on log-probabilities; the max search runs on the raw emissions as the reference's decoder does).
     Returns (labels [B][nbest][max_len] int32, -1 beyond a hypothesis; lengths [B][nbest] int32, the true label counts, -1 for a
@@ -331,7 +337,9 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     (labels, lengths, scores, lm_scores, words [B][nbest][max_words] int32 word ids, -1 beyond; word_counts [B][nbest] int32);
     max_words defaults to max_len.  A hypothesis that ends inside a word does not count: an utterance may have only empty rows.
     wide: run the wide kernels (the w2l_*_wide entry points): the same contract with beam up to 1024; beam_token stays <= 64.  At
-    beam <= 64 both kernel families return the same bytes."""
+    beam <= 64 both kernel families return the same bytes.  wide="xl": run the xl kernels (the w2l_*_xl entry points): the same
+    contract with beam up to 8192, the widths the reference's decoding recipes ask for; at beam <= 1024 they return the wide
+    kernels' bytes.  No family is chosen for the caller: wide=True with beam > 1024 is refused as before."""
     _emission_checks(emission)
     B, T, N = emission.shape
     if lexicon is not None:
@@ -585,7 +593,8 @@ class ASGLoss(SequenceCriterion):
         return self.fac.viterbiPath(emission, target)
 
     def beamSearch(self, emission, frames=None, **options):
-        """n-best beam search over the emissions under this criterion's transitions (asg_beam_search's options)"""
+        """n-best beam search over the emissions under this criterion's transitions (asg_beam_search's options; wide=True: beam
+        up to 1024, wide="xl": up to 8192)"""
         return asg_beam_search(emission, self.transitions, frames, **options)
 
     def prettyString(self):
@@ -652,7 +661,7 @@ class CTCLoss(SequenceCriterion):
 
     def beamSearch(self, emission, frames=None, **options):
         """n-best beam search over the emissions (ctc_beam_search's options, lm= and lexicon= included): (labels, lengths, scores),
-        lm_scores with an LM, and words and word_counts with a lexicon"""
+        lm_scores with an LM, and words and word_counts with a lexicon.  wide=True: beam up to 1024, wide="xl": up to 8192"""
         return ctc_beam_search(emission, frames, **options)
 
     def score(self, emission, target):

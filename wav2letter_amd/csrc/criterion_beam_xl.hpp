@@ -1,0 +1,645 @@
+// criterion_beam_xl.hpp -- the five xl beam searches (w2l_*_beam_search*_xl): the contracts of the CTC and ASG beam searches
+// (include/w2l_hip.h) with a beam of up to kBeamXlMax = 8192 entries, the widths the reference's recipes ask for (1500, 2500, 5000,
+// 8000).  Included at the end of criterion_ctc.hip.  The algorithm is criterion_beam_wide.hpp's, frame by frame and operation by
+// operation -- stays with the merged extension, the candidate list of 64-bit keys, the MSB-first radix select, the sorted survivors,
+// the next beam -- on the same device helpers (ctc_beam_rows, beam_node, beam_key, beam_oplus, BeamCtc / BeamAsg, beam_lm_ext,
+// beam_lex_a, beam_lex_word, beam_eos, beam_chain_len, beam_write_labels), so at every W both families take the outputs are the
+// same bits.  What differs is where the state lives and who owns it:
+//   ownership   one workgroup of 1024 threads per utterance; thread tid owns entries tid, tid + 1024, ... of the beam.
+//   the beam    both halves, 8 fields of 4 bytes per entry (9 with a lexicon), [2][kFields][W] words per utterance in the
+//               WORKSPACE, with the gone masks ([slots][W] u64) and pb' / pnb' of the stays ([2][W] float).  At W = 8192 that is
+//               0.6 - 1.1 MiB per utterance: L2-resident.  It is written with plain stores and read with plain loads after a
+//               __syncthreads(), as the wide scan's candidate list is: one workgroup, one CU, one L1.  The gone masks are the
+//               exception: they are set by 64-bit global atomics, which act at L2, so they are read back with device-scope atomic
+//               loads, which go there too.
+//   LDS         the node -> rank hash, 2 * pow2(W) slots of 8 bytes (128 KiB at W = 8192; dynamic LDS, one workgroup per CU).  It
+//               is dead once the stays are done, and the survivors' sort (pow2(m) <= pow2(W) keys: half of it) takes its place,
+//               as the wide scan reuses its sScr.  The frame tokens, the histogram and the counters are 2 KiB more.  The ASG
+//               transition matrix is not staged: it is gathered from global memory (BeamTrans.lds = 0), the whole budget is the
+//               hash's.
+//   atomics     hash CAS, histogram and counters: LDS atomics; gone masks: global 64-bit OR; prefix table: beam_node's global CAS.
+//   sort        bitonic over pow2(m) keys, n2 / 2 compare-exchanges a step, strided over the threads.
+// No waiting between workgroups, no flags, no spin loops; every probe loop is bounded by its table's capacity; every barrier is
+// reached by all 1024 threads, and every loop with a barrier inside runs on counts read from LDS after a barrier, the same in
+// every thread.
+//   beam_xl_finish<lex>  one workgroup per utterance, strided over the final entries and then over the output rows; keys, scores
+//                        and LM sums in dynamic LDS (16 bytes per entry of pow2(W)).
+#pragma once
+
+namespace w2l {
+
+constexpr int kBeamXlMax = 8192;      // W of the xl searches; their K stays <= kBeamMax
+constexpr int kXlThreads = 1024;
+
+struct BeamXlWs {
+  BeamWideWs w;      // the wide family's workspace: rows, table, candidate list, fin* (W entries per utterance)
+  int* beam;         // [B][2][kFields][W]
+  u64* gone;         // [B][slots][W]
+  float* stay;       // [B][2][W]: pb', pnb' of stay(j)
+  int hashN;         // 2 * pow2(W): slots of the LDS hash
+};
+
+__host__ __device__ __forceinline__ int beam_xl_pow2(int m) {
+  int n2 = 2;
+  while (n2 < m) n2 <<= 1;
+  return n2;
+}
+
+static size_t beam_xl_layout(BeamXlWs* x, void* ws, int B, int T, int W, int K, int variant) {
+  const bool lex = variant == kBeamLex;
+  char* p = (char*)ws;
+  char* const p0 = p;
+  p += align_up(beam_wide_layout(x ? &x->w : nullptr, ws, B, T, W, K, variant), 256);
+  int* beam = (int*)p; p += align_up((size_t)B * 2 * (lex ? 9 : 8) * W * 4, 256);
+  u64* gone = (u64*)p; p += align_up((size_t)B * (lex ? 7 : 1) * W * 8, 256);
+  float* stay = (float*)p; p += align_up((size_t)B * 2 * W * 4, 256);
+  if (x) { x->beam = beam; x->gone = gone; x->stay = stay; x->hashN = 2 * beam_xl_pow2(W); }
+  return (size_t)(p - p0);
+}
+
+// the dynamic LDS of beam_xl_scan after the hash (hashN u64), in bytes
+struct XlLds {
+  static constexpr size_t tc = 0;                     // [64] int
+  static constexpr size_t tl = tc + 64 * 4;           // [64] float
+  static constexpr size_t hist = tl + 64 * 4;         // [256] unsigned
+  static constexpr size_t red = hist + 256 * 4;       // [16] u64
+  static constexpr size_t misc = red + 16 * 8;        // [8] unsigned
+  static constexpr size_t bytes = misc + 8 * 4;
+};
+
+// s[0 .. n2) descending, n2 a power of two <= 8192; every thread of the workgroup calls it; ends with a barrier
+__device__ __forceinline__ void beam_xl_sort(u64* s, int n2) {
+  const int half = n2 >> 1;
+  for (int k = 2; k <= n2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int p = threadIdx.x; p < half; p += kXlThreads) {
+        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), o = i | j;
+        const u64 a = s[i], c = s[o];
+        const bool desc = (i & k) == 0;
+        if (desc ? a < c : a > c) { s[i] = c; s[o] = a; }
+      }
+      __syncthreads();
+    }
+}
+
+// a gone mask as the atomics at L2 left it
+__device__ __forceinline__ u64 beam_xl_mask(const u64* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <bool kLogAdd, class Pol, bool kLex>
+__global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, float threshold, const float* __restrict__ x,
+                                                           const int* __restrict__ frames, BeamXlWs xw,
+                                                           const void* __restrict__ lex, const void* __restrict__ lm,
+                                                           float lmWeight, const float* __restrict__ classScore, float wordScore,
+                                                           BeamTrans tr) {
+  constexpr int kF = kLex ? 9 : 8, kSlots = kLex ? 7 : 1, kTh = kXlThreads;
+  extern __shared__ float sAsgTrans[];   // BeamAsg::stage's array; nothing is staged here (tr.lds = 0)
+  const int hashN = xw.hashN;
+  u64* const sHash = (u64*)sAsgTrans;
+  u64* const sSort = sHash;               // the survivors' keys, once the hash is dead
+  char* const base = (char*)(sHash + hashN);
+  int* const sTc = (int*)(base + XlLds::tc);
+  float* const sTl = (float*)(base + XlLds::tl);
+  unsigned* const sHist = (unsigned*)(base + XlLds::hist);
+  u64* const sRed = (u64*)(base + XlLds::red);
+  unsigned* const sMisc = (unsigned*)(base + XlLds::misc);   // 0: candidates, 1: survivors, 2: bin, 3: keys above it, 4: keys in it
+
+  const BeamWideWs& ww = xw.w;
+  const CtcBeamWs& ws = ww.c;
+  const int b = blockIdx.x, tid = threadIdx.x, K = ws.K;
+  const int F = align_frames(frames, b, T);
+  const float* xb = x + (size_t)b * T * N;
+  u64* tab = ws.table + (size_t)b * ws.cap;
+  const unsigned capm = ws.cap - 1;
+  const unsigned hm = (unsigned)hashN - 1u;
+  const size_t row0 = (size_t)b * T;
+  u64* cand = ww.cand + (size_t)b * ww.candCap;
+  const unsigned candCap = (unsigned)ww.candCap;
+  int* const gBeam = xw.beam + (size_t)b * 2 * kF * W;
+  u64* const gGone = xw.gone + (size_t)b * kSlots * W;
+  float* const gSpb = xw.stay + (size_t)b * 2 * W;
+  float* const gSpnb = gSpb + W;
+  const bool useLm = kLex || lm != nullptr;
+  const NgramView lv = useLm ? ngram_view(lm) : NgramView{};
+  LexView xv{};
+  if constexpr (kLex) xv = lex_view(lex);
+  const float* A = Pol::stage(tr, N);
+
+  // field f of half h of the beam: 0 node, 1 parent's node, 2 last token, 3 LM state, 4 pb, 5 pnb, 6 tot, 7 unweighted LM sum,
+  // 8 (lexicon) the label of the last extension
+  auto fi = [&](int h, int f) { return gBeam + ((size_t)h * kF + f) * W; };
+  auto ff = [&](int h, int f) { return (float*)(gBeam + ((size_t)h * kF + f) * W); };
+
+  int cur = 0, n = 1;
+  if (tid == 0) {
+    fi(0, 0)[0] = 0; fi(0, 1)[0] = -1; fi(0, 2)[0] = -1; fi(0, 3)[0] = useLm ? (int)((const NgramHeader*)lm)->start : 0;
+    ff(0, 4)[0] = 0.f; ff(0, 5)[0] = -INFINITY; ff(0, 6)[0] = 0.f; ff(0, 7)[0] = 0.f;
+    if constexpr (kLex) fi(0, 8)[0] = -1;
+  }
+  for (int t = 0; t < F && n > 0; ++t) {
+    const size_t row = row0 + t;
+    const int nxt = cur ^ 1;
+    const int *cNode = fi(cur, 0), *cPar = fi(cur, 1), *cE = fi(cur, 2), *cSt = fi(cur, 3);
+    const float *cPb = ff(cur, 4), *cPnb = ff(cur, 5), *cTot = ff(cur, 6), *cAcc = ff(cur, 7);
+    const int* cLab = kLex ? fi(cur, 8) : nullptr;
+
+    beam_load_frame(ws, row, sTc, sTl);
+    for (int j = tid; j < n; j += kTh)
+      for (int s = 0; s < kSlots; ++s) gGone[(size_t)s * W + j] = 0ull;
+    for (int i = tid; i < hashN; i += kTh) sHash[i] = 0ull;
+    if (tid < 2) sMisc[tid] = 0u;
+    const float lpb = ws.lpb[row], lse = ws.lse[row];
+    __syncthreads();
+    // the rank of every current node
+    for (int j = tid; j < n; j += kTh) {
+      const unsigned nd1 = (unsigned)cNode[j] + 1u;
+      const u64 rec = ((u64)nd1 << 32) | (u64)(unsigned)j;
+      unsigned h = beam_hash(nd1) & hm;
+      for (int probe = 0; probe < hashN; ++probe) {
+        if (atomicCAS(&sHash[h], 0ull, rec) == 0ull) break;
+        h = (h + 1) & hm;
+      }
+    }
+    __syncthreads();
+
+    // every candidate of the frame that is not -inf: its key into the list
+    u64 local = 0ull;
+    auto put = [&](u64 key) {
+      if ((unsigned)(key >> 32) == beam_ord(-INFINITY)) return;
+      const unsigned pos = atomicAdd(&sMisc[0], 1u);
+      if (pos < candCap) cand[pos] = key;
+      local = key > local ? key : local;
+    };
+    // stay(j), with the extension that spells this entry merged in
+    for (int j = tid; j < n; j += kTh) {
+      float spb = -INFINITY, spnb = -INFINITY;
+      const int e = cE[j], par = cPar[j];
+      int kj = -1, pr = -1;
+      for (int k = 0; k < K; ++k) kj = sTc[k] == e ? k : kj;
+      if (par >= 0) {
+        const unsigned pd1 = (unsigned)par + 1u;
+        unsigned h = beam_hash(pd1) & hm;
+        for (int probe = 0; probe < hashN; ++probe) {
+          const u64 rec = sHash[h];
+          if (rec == 0ull) break;
+          if ((unsigned)(rec >> 32) == pd1) { pr = (int)(unsigned)rec; break; }
+          h = (h + 1) & hm;
+        }
+      }
+      Pol::stay(e >= 0 ? xb[(size_t)t * N + e] - lse : 0.f, e, lpb, cPnb[j], cTot[j], A, N, &spb, &spnb);
+      if (pr >= 0 && kj >= 0) {
+        float v = Pol::ext(sTl[kj], e, cE[pr], cPb[pr], cTot[pr], A, N);
+        if constexpr (!kLex) {
+          if (useLm) {
+            int unused;
+            const float qm = ngram_q(lv, cSt[pr], e, &unused);
+            v = beam_lm_ext(v, lmWeight, qm, classScore, e);
+          }
+          spnb = beam_oplus<kLogAdd>(spnb, v);
+          atomicOr(&gGone[pr], 1ull << kj);
+        } else {
+          const int lab = cLab[j];
+          if (lab >= 0) {
+            const int vj = lab >> 3, slot = lab & 7;
+            if (vj != 0) {
+              const LexNode& nd = lex_node(xv, vj);
+              const float smv = nd.smear;
+              const int up = beam_wide_u(cLab[pr]);
+              v = beam_lex_a(v, lmWeight, smv, up == 0 ? 0.f : lex_node(xv, up).smear);
+              if (slot > 0) {
+                int unused;
+                const float qm = ngram_q(lv, cSt[pr], nd.words[min(slot - 1, kLexMaxWords - 1)], &unused);
+                v = beam_lex_word(v, lmWeight, qm, smv, wordScore);
+              }
+            }
+            spnb = beam_oplus<kLogAdd>(spnb, v);
+            atomicOr(&gGone[(size_t)min(slot, 6) * W + pr], 1ull << kj);
+          }
+        }
+      }
+      gSpb[j] = spb; gSpnb[j] = spnb;
+      put(beam_key(beam_oplus<kLogAdd>(spb, spnb), j, 0, 0));
+    }
+    __syncthreads();   // the hash is read, the gone masks are complete
+
+    const int total = n * K;
+    for (int idx = tid; idx < total; idx += kTh) {
+      const int r = idx / K, k = idx - r * K, c = sTc[k], e = cE[r];
+      if (Pol::none(c, e)) continue;
+      const float a0 = Pol::ext(sTl[k], c, e, cPb[r], cTot[r], A, N);
+      if constexpr (!kLex) {
+        if ((beam_xl_mask(&gGone[r]) >> k) & 1ull) continue;
+        float v = a0;
+        if (useLm) {
+          int unused;
+          const float q = ngram_q(lv, cSt[r], c, &unused);
+          v = beam_lm_ext(v, lmWeight, q, classScore, c);
+        }
+        put(beam_key(v, r, 1, k));
+      } else {
+        const int u = beam_wide_u(cLab[r]);
+        if (c == xv.silToken && u == 0) {
+          if (!((beam_xl_mask(&gGone[r]) >> k) & 1ull)) put(beam_key(a0, r, 1, k, 0));
+        } else {
+          const int v = lex_child(xv, u, c);
+          if (v > 0) {
+            const LexNode& nd = lex_node(xv, v);
+            const float smv = nd.smear;
+            const float a = beam_lex_a(a0, lmWeight, smv, u == 0 ? 0.f : lex_node(xv, u).smear);
+            if (lex_has_children(nd) && !((beam_xl_mask(&gGone[r]) >> k) & 1ull)) put(beam_key(a, r, 1, k, 0));
+            const int nw = lex_nw(nd);
+            for (int i = 0; i < nw; ++i)
+              if (!((beam_xl_mask(&gGone[(size_t)(1 + i) * W + r]) >> k) & 1ull)) {
+                int unused;
+                const float q = ngram_q(lv, cSt[r], nd.words[i], &unused);
+                put(beam_key(beam_lex_word(a, lmWeight, q, smv, wordScore), r, 1, k, 1 + i));
+              }
+          }
+        }
+      }
+    }
+    {
+      const u64 wm = wave_max_u64(local);
+      if ((tid & 63) == 0) sRed[tid >> 6] = wm;
+    }
+    __syncthreads();   // the list, its count and the waves' maxima
+    const int cnt = (int)min(sMisc[0], candCap);
+    u64 bestKey = sRed[0];
+#pragma unroll
+    for (int i = 1; i < kTh / 64; ++i) bestKey = sRed[i] > bestKey ? sRed[i] : bestKey;
+    const float best = beam_unord((unsigned)(bestKey >> 32));   // cnt == 0: not used
+
+    // the W-th largest key (1 when there are no more than W): MSB-first radix select
+    u64 tau = 1ull;
+    if (cnt > W) {
+      u64 prefix = 0ull;
+      unsigned want = (unsigned)W;
+      for (int pass = 0; pass < 8; ++pass) {
+        const int shift = 56 - 8 * pass;
+        if (tid < 256) sHist[tid] = 0u;
+        __syncthreads();
+        for (int i = tid; i < cnt; i += kTh) {
+          const u64 key = cand[i];
+          if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&sHist[(unsigned)(key >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid < 256) {
+          unsigned above = 0u;
+          for (int j = tid + 1; j < 256; ++j) above += sHist[j];
+          const unsigned mine = sHist[tid];
+          if (above < want && above + mine >= want) { sMisc[2] = (unsigned)tid; sMisc[3] = above; sMisc[4] = mine; }
+        }
+        __syncthreads();
+        prefix |= (u64)sMisc[2] << shift;
+        want -= sMisc[3];
+        if (want == sMisc[4]) break;   // the bin is taken whole: every key at or above the prefix, and no other
+      }
+      tau = prefix;
+    }
+    // the survivors, then their ranks
+    for (int i = tid; i < cnt; i += kTh) {
+      const u64 key = cand[i];
+      if (key >= tau && !(beam_unord((unsigned)(key >> 32)) < best - threshold)) {
+        const unsigned pos = atomicAdd(&sMisc[1], 1u);
+        if (pos < (unsigned)W) sSort[pos] = key;
+      }
+    }
+    __syncthreads();
+    const int m = (int)min(sMisc[1], (unsigned)W);
+    const int n2 = beam_xl_pow2(m);
+    for (int i = m + tid; i < n2; i += kTh) sSort[i] = 0ull;
+    __syncthreads();
+    beam_xl_sort(sSort, n2);
+
+    // entry q of the next beam
+    for (int q = tid; q < m; q += kTh) {
+      const u64 key = sSort[q];
+      const unsigned tie = 0xffffffffu - (unsigned)key;
+      const int r = min((int)(tie >> 10), W - 1), ext = (int)((tie >> 9) & 1u), k = (int)((tie >> 3) & 63u), slot = (int)(tie & 7u);
+      if (!ext) {
+        const float pb = gSpb[r], pnb = gSpnb[r];
+        fi(nxt, 0)[q] = cNode[r]; fi(nxt, 1)[q] = cPar[r]; fi(nxt, 2)[q] = cE[r]; fi(nxt, 3)[q] = cSt[r];
+        ff(nxt, 4)[q] = pb; ff(nxt, 5)[q] = pnb; ff(nxt, 6)[q] = beam_oplus<kLogAdd>(pb, pnb); ff(nxt, 7)[q] = cAcc[r];
+        if constexpr (kLex) fi(nxt, 8)[q] = cLab[r];
+      } else {
+        const float tot = beam_unord((unsigned)(key >> 32));
+        const int c = sTc[k];
+        int st = cSt[r], label = c;
+        float acc = cAcc[r];
+        if constexpr (!kLex) {
+          st = 0;
+          float q1 = 0.f;
+          if (useLm) q1 = ngram_q(lv, cSt[r], c, &st);
+          acc = acc + q1;
+        } else {
+          const int u = beam_wide_u(cLab[r]);
+          const int v = (c == xv.silToken && u == 0) ? 0 : max(lex_child(xv, u, c), 0);
+          label = (v << 3) | slot;
+          if (slot > 0) {
+            const float q1 = ngram_q(lv, cSt[r], lex_node(xv, v).words[min(slot - 1, kLexMaxWords - 1)], &st);
+            acc = acc + q1;
+          }
+          fi(nxt, 8)[q] = label;
+        }
+        const int par = cNode[r];
+        fi(nxt, 0)[q] = beam_node(tab, capm, par, label);   // a new prefix
+        fi(nxt, 1)[q] = par; fi(nxt, 2)[q] = c; fi(nxt, 3)[q] = st;
+        ff(nxt, 4)[q] = -INFINITY; ff(nxt, 5)[q] = tot; ff(nxt, 6)[q] = tot; ff(nxt, 7)[q] = acc;
+      }
+    }
+    __syncthreads();
+    n = m;
+    cur = nxt;
+  }
+  // the final entries (the barrier above, or none before a first frame that never ran: then thread 0 reads its own entry 0)
+  for (int j = tid; j < W; j += kTh) {
+    const bool live = j < n;
+    const size_t o = (size_t)b * ww.W + j;
+    ws.finNode[o] = live ? fi(cur, 0)[j] : -1;
+    ws.finTot[o] = live ? ff(cur, 6)[j] : -INFINITY;
+    ws.finState[o] = live ? fi(cur, 3)[j] : 0;
+    ws.finAcc[o] = live ? ff(cur, 7)[j] : -INFINITY;
+    if constexpr (kLex) ws.finU[o] = live ? beam_wide_u(fi(cur, 8)[j]) : -1;
+  }
+  if (tid == 0) ws.finN[b] = n;
+}
+
+// beam_wide_finish with thread r owning final entries r, r + 1024, ... and rows m, m + 1024, ...; dynamic LDS: pow2(W) keys, then
+// W scores, W LM sums and the count of the entries that count at the end
+template <bool kLex>
+__global__ __launch_bounds__(kXlThreads) void beam_xl_finish(int M, int Lmax, int maxWords, int eosWord, BeamXlWs xw,
+                                                             const void* __restrict__ lex, const void* __restrict__ lm,
+                                                             float lmWeight, float eosScore, int useEos,
+                                                             int* __restrict__ labels, int* __restrict__ lengths,
+                                                             float* __restrict__ scores, float* __restrict__ lmScores,
+                                                             int* __restrict__ words, int* __restrict__ wordCounts) {
+  extern __shared__ float sAsgTrans[];   // the only LDS of the kernel: the keys come first, 8-byte aligned at offset 0
+  const BeamWideWs& ww = xw.w;
+  const CtcBeamWs& ws = ww.c;
+  const int b = blockIdx.x, tid = threadIdx.x, W = ww.W;
+  const int n = min(max(ws.finN[b], 0), W);
+  const int n2 = beam_xl_pow2(n);
+  u64* const sKey = (u64*)sAsgTrans;
+  float* const sScore = (float*)(sKey + beam_xl_pow2(W));
+  float* const sAcc = sScore + W;
+  unsigned* const sAlive = (unsigned*)(sAcc + W);
+  const u64* tab = ws.table + (size_t)b * ws.cap;
+  const BeamWalk g{};
+  if (tid == 0) *sAlive = 0u;
+  __syncthreads();
+  unsigned mine = 0u;
+  for (int r = tid; r < n2; r += kXlThreads) {
+    const size_t o = (size_t)b * W + min(r, W - 1);
+    const bool alive = r < n && (!kLex || ws.finU[o] == 0);   // with a lexicon only finished words count at the end
+    float score = -INFINITY, acc = -INFINITY;
+    if (alive) {
+      score = ws.finTot[o];
+      acc = ws.finAcc[o];
+      if (useEos) {
+        const int ew = kLex ? (int)((const NgramHeader*)lm)->numTokens + 1 : eosWord;
+        beam_eos(lm, ws.finState[o], ew, lmWeight, eosScore, &score, &acc);
+      }
+      ++mine;
+    }
+    if (r < W) { sScore[r] = score; sAcc[r] = acc; }
+    sKey[r] = alive ? ((u64)beam_ord(score) << 32) | (u64)(0xffffffffu - (unsigned)r) : 0ull;
+  }
+  if (mine) atomicAdd(sAlive, mine);
+  __syncthreads();
+  const int nAlive = (int)*sAlive;
+  beam_xl_sort(sKey, n2);
+  for (int m = tid; m < M; m += kXlThreads) {
+    const bool live = m < nAlive;
+    const int src = live ? min((int)(0xffffffffu - (unsigned)sKey[m]), W - 1) : 0;
+    const size_t row = (size_t)b * M + m;
+    int* lab = labels + row * Lmax;
+    int len = 0, nwords = 0;
+    if constexpr (!kLex) {
+      len = beam_write_labels(tab, live, ws.finNode + (size_t)b * W + src, Lmax, lab, g);
+    } else {
+      const LexView xv = lex_view(lex);
+      int* wrd = words + row * maxWords;
+      if (live) {
+        const int node = ws.finNode[(size_t)b * W + src];
+        len = beam_chain_len(tab, node, &nwords, g);
+        int i = len - 1, j = nwords - 1;
+        for (int p = node; i >= 0 && beam_walk_ok(g, p); --i) {   // len labels: the walk above counted them under the same bound
+          const u64 edge = tab[p - 1];
+          const unsigned l = (unsigned)edge - 1u;
+          const int v = (int)(l >> 3), slot = (int)(l & 7u);
+          const LexNode& nd = lex_node(xv, v);
+          if (i < Lmax) lab[i] = v == 0 ? xv.silToken : nd.tok;
+          if (slot > 0) {
+            if (j >= 0 && j < maxWords) wrd[j] = nd.words[min(slot - 1, kLexMaxWords - 1)];
+            --j;
+          }
+          p = (int)(edge >> 32);
+        }
+      }
+      for (int i = min(len, Lmax); i < Lmax; ++i) lab[i] = -1;
+      for (int j = min(nwords, maxWords); j < maxWords; ++j) wrd[j] = -1;
+      wordCounts[row] = live ? nwords : -1;
+    }
+    lengths[row] = live ? len : -1;
+    scores[row] = live ? sScore[src] : -INFINITY;
+    if (lmScores) lmScores[row] = live ? sAcc[src] : -INFINITY;
+  }
+}
+
+static size_t beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken, int variant, bool noBlank) {
+  if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
+  const int K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
+  if (beam > kBeamXlMax || K > kBeamMax) return 0;
+  return beam_xl_layout(nullptr, nullptr, B, T, beam, K, variant);
+}
+
+// beam_wide_check with the xl limit: every W2L_EINVAL first, then the limits, then T * W (node ids are ints)
+static int beam_xl_check(int B, int T, int N, const float* input, int beam, int beamToken, float threshold, int nbest, int maxLen,
+                         const int* labels, const int* lengths, const float* scores, const void* workspace, int* K, bool noBlank) {
+  if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !workspace) return W2L_EINVAL;
+  if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
+  if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
+  *K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
+  if (beam > kBeamXlMax || *K > kBeamMax) return W2L_EUNSUPPORTED;
+  if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;
+  return W2L_OK;
+}
+
+constexpr size_t kXlScanLdsMax = (size_t)2 * kBeamXlMax * 8 + XlLds::bytes;   // 128 KiB + 2 KiB
+constexpr size_t kXlFinishLdsMax = (size_t)kBeamXlMax * 16 + 8;               // 128 KiB
+
+template <bool kLogAdd, class Pol, bool kLex>
+static int beam_xl_launch(int B, int T, int N, float threshold, const float* input, const int* frames, const BeamXlWs& xw,
+                          const void* lex, const void* lm, float lmWeight, const float* classScore, float wordScore,
+                          const BeamTrans& tr, hipStream_t s) {
+  const size_t shmem = (size_t)xw.hashN * 8 + XlLds::bytes;
+  static bool attr[64] = {};
+  if (first_on_device(attr))
+    W2L_HIP_CHECK(hipFuncSetAttribute((const void*)beam_xl_scan<kLogAdd, Pol, kLex>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)kXlScanLdsMax));
+  hipLaunchKernelGGL((beam_xl_scan<kLogAdd, Pol, kLex>), dim3((unsigned)B), dim3(kXlThreads), shmem, s, T, N, xw.w.W, threshold,
+                     input, frames, xw, lex, lm, lmWeight, classScore, wordScore, tr);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+template <bool kLex>
+static int beam_xl_finish_launch(int B, int M, int Lmax, int maxWords, int eosWord, const BeamXlWs& xw, const void* lex,
+                                 const void* lm, float lmWeight, float eosScore, int useEos, int* labels, int* lengths, float* scores,
+                                 float* lmScores, int* words, int* wordCounts, hipStream_t s) {
+  const size_t shmem = (size_t)beam_xl_pow2(xw.w.W) * 8 + (size_t)xw.w.W * 8 + 8;
+  static bool attr[64] = {};
+  if (first_on_device(attr))
+    W2L_HIP_CHECK(hipFuncSetAttribute((const void*)beam_xl_finish<kLex>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)kXlFinishLdsMax));
+  hipLaunchKernelGGL(beam_xl_finish<kLex>, dim3((unsigned)B), dim3(kXlThreads), shmem, s, M, Lmax, maxWords, eosWord, xw, lex, lm,
+                     lmWeight, eosScore, useEos, labels, lengths, scores, lmScores, words, wordCounts);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+// One xl search after its checks: rows, scan, finish.  trans null: CTC; lex null: the token search
+static int beam_xl_run(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam, int K,
+                       float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
+                       float lmWeight, const float* classScore, const void* lex, float wordScore, float eosScore, int* labels,
+                       int* lengths, float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
+                       hipStream_t s) {
+  const bool asg = trans != nullptr, isLex = lex != nullptr;
+  BeamXlWs xw{};
+  beam_xl_layout(&xw, workspace, B, T, beam, K, isLex ? kBeamLex : kBeamLm);
+  const BeamWideWs& ww = xw.w;
+  W2L_HIP_CHECK(hipMemsetAsync(ww.c.table, 0, (size_t)B * ww.c.cap * sizeof(u64), s));
+  const unsigned rows = (unsigned)((size_t)B * T);
+  const bool big = N > kRowThreads * kRowMaxPer;
+  if (asg && big)
+    hipLaunchKernelGGL((ctc_beam_rows<true, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
+  else if (asg)
+    hipLaunchKernelGGL((ctc_beam_rows<false, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
+  else if (!big)
+    hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
+  else
+    hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
+  W2L_LAUNCH_CHECK();
+
+  const BeamTrans tr{trans, 0};   // gathered from global memory: the LDS is the hash's
+  int rc = W2L_OK;
+#define W2L_XL_SCAN(LA, POL, LEX) \
+  rc = beam_xl_launch<LA, POL, LEX>(B, T, N, threshold, input, frames, xw, lex, lm, lmWeight, classScore, wordScore, tr, s)
+  if (isLex) {
+    if (asg) { if (logAdd) W2L_XL_SCAN(true, BeamAsg, true); else W2L_XL_SCAN(false, BeamAsg, true); }
+    else { if (logAdd) W2L_XL_SCAN(true, BeamCtc, true); else W2L_XL_SCAN(false, BeamCtc, true); }
+  } else {
+    if (asg) { if (logAdd) W2L_XL_SCAN(true, BeamAsg, false); else W2L_XL_SCAN(false, BeamAsg, false); }
+    else { if (logAdd) W2L_XL_SCAN(true, BeamCtc, false); else W2L_XL_SCAN(false, BeamCtc, false); }
+  }
+#undef W2L_XL_SCAN
+  if (rc) return rc;
+  const int useEos = lm && lmHasEos ? 1 : 0;
+  if (isLex)
+    return beam_xl_finish_launch<true>(B, nbest, maxLen, maxWords, 0, xw, lex, lm, lmWeight, eosScore, useEos, labels, lengths,
+                                       scores, lmScores, words, wordCounts, s);
+  return beam_xl_finish_launch<false>(B, nbest, maxLen, 0, asg ? N + 1 : N, xw, nullptr, lm, lmWeight, eosScore, useEos, labels,
+                                      lengths, scores, lmScores, nullptr, nullptr, s);
+}
+
+}  // namespace w2l
+
+W2L_API size_t w2l_ctc_beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
+  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, false);
+}
+W2L_API size_t w2l_ctc_beam_lm_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
+  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, false);
+}
+W2L_API size_t w2l_ctc_beam_lex_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
+  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, false);
+}
+W2L_API size_t w2l_asg_beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
+  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, true);
+}
+W2L_API size_t w2l_asg_beam_lex_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
+  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, true);
+}
+
+W2L_API int w2l_ctc_beam_search_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                   float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
+                                   float* scores, void* workspace, w2l_stream_t stream) {
+  using namespace w2l;
+  int K = 0;
+  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
+                                   false))
+    return rc;
+  return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, nullptr, 0, 0.f, nullptr,
+                     nullptr, 0.f, 0.f, labels, lengths, scores, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream);
+}
+
+W2L_API int w2l_ctc_beam_search_lm_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                      float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                      int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
+                                      int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
+  using namespace w2l;
+  if (!lmScores || !lm) return W2L_EINVAL;
+  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
+  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
+  int K = 0;
+  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
+                                   false))
+    return rc;
+  return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
+                     classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
+                     (hipStream_t)stream);
+}
+
+W2L_API int w2l_ctc_beam_search_lex_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                       float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                       int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
+                                       int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
+                                       int* wordCounts, void* workspace, w2l_stream_t stream) {
+  using namespace w2l;
+  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
+  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
+  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
+  int K = 0;
+  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
+                                   false))
+    return rc;
+  return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
+                     nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
+                     (hipStream_t)stream);
+}
+
+W2L_API int w2l_asg_beam_search_xl(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+                                   int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                   int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
+                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
+  using namespace w2l;
+  if (!lmScores || !trans) return W2L_EINVAL;
+  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
+  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
+  if (!lm && (lmHasEos || classScore)) return W2L_EINVAL;
+  int K = 0;
+  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
+                                   true))
+    return rc;
+  return beam_xl_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
+                     classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
+                     (hipStream_t)stream);
+}
+
+W2L_API int w2l_asg_beam_search_lex_xl(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+                                       int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
+                                       const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
+                                       float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
+                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
+  using namespace w2l;
+  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1 || !trans) return W2L_EINVAL;
+  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
+  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
+  int K = 0;
+  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
+                                   true))
+    return rc;
+  return beam_xl_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
+                     nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
+                     (hipStream_t)stream);
+}

@@ -1,5 +1,5 @@
 // decode_main.cpp -- `Decode --am=<NNN_model_*.bin> --test=<list> [--datadir=] [--batchsize=] [--sclite=<dir>] [--beamsize=]
-// [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--k=v ...]`: the
+// [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--w2l_beam_xl=] [--k=v ...]`: the
 // reference's Decode tool for its lexicon-free token decoder (`--uselexicon=false --decodertype=tkn`), without LM (the configuration
 // of recipes/self_training/librispeech/am/decode_*.cfg) or with a token-level n-gram LM (`--lm=<arpa>`, recipes/lexicon_free and the
 // word-piece runs of sota/2019), and for its lexicon decoder with a word LM (recipes/conv_glu/*/decode*.cfg), over the fl::
@@ -18,8 +18,11 @@
 //   --beamsize (2500), --beamsizetoken (250000), --beamthreshold (25), --logadd (false), --nbest (1): the reference's names and
 //   defaults.  A --beamsize given in the flags (the checkpoint's or the command line's) above 64 runs the wide kernels
 //   (BeamSearchOptions::wide), which keep up to 1024 beam entries: larger values are limited to 1024 (said on stderr).  A value up
-//   to 64 runs the narrow kernels; so does an absent --beamsize, whose default is limited to 64 (said on stderr).  Both kernels keep
+//   to 64 runs the narrow kernels; so does an absent --beamsize, whose default is limited to 64 (said on stderr).  All kernels keep
 //   at most 64 tokens per frame: a larger --beamsizetoken is limited to 64 (said on stderr).
+//   --w2l_beam_xl=true (not the reference's; default false): a --beamsize given in the flags and above 1024 runs the xl kernels
+//   (BeamSearchOptions::xl), which keep up to 8192 beam entries -- the recipes' 1500, 2500, 5000 and 8000 as they are written;
+//   larger values are limited to 8192 (said on stderr).  Values up to 1024 and an absent --beamsize route as without the flag.
 //   --logadd=false (default): a prefix scores the MAX over its alignments, on the raw emissions as in the reference's decoder; the
 //     1-best then equals the greedy transcript (the collapsed per-frame arg-max), the n-best are the next best single alignments.
 //   --logadd=true: the labelling-probability search -- a prefix scores the SUM over its alignments, on log-softmax rows (sums only
@@ -66,10 +69,10 @@ namespace {
 int usage(const char* exe) {
   std::cerr << "Usage: \n " << exe
             << " --am=<model> --test=<list> [--datadir=...] [--batchsize=...] [--sclite=<dir>] [--beamsize=2500] [--beamsizetoken=250000]"
-               " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [flags]\n"
+               " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [--w2l_beam_xl=false] [flags]\n"
                " [--lm=<arpa> --lmtype=kenlm --lmweight=0 --eosscore=0 --wordscore=0]\n"
                " [--uselexicon=true --decodertype=wrd --lexicon=<file> --lm=<word arpa> --smearing=none|max]\n"
-               " CTC or ASG (as the checkpoint says) token beam search, optionally with a token-level n-gram LM (ARPA text); --beamsize is limited to 1024 when given (above 64: the wide kernels), to 64 when absent; tokens per frame are limited to 64.\n"
+               " CTC or ASG (as the checkpoint says) token beam search, optionally with a token-level n-gram LM (ARPA text); --beamsize is limited to 1024 when given (above 64: the wide kernels), to 64 when absent; with --w2l_beam_xl=true a given --beamsize above 1024 runs the xl kernels and is limited to 8192; tokens per frame are limited to 64.\n"
                " --logadd=false (default): max over a prefix's alignments on the raw emissions -- the 1-best equals the greedy transcript.\n"
                " --logadd=true: the labelling-probability search (sum over a prefix's alignments, on log-softmax rows)."
             << std::endl;
@@ -166,12 +169,14 @@ int main(int argc, char** argv) {
     if (asg) numClasses += (int)flags.geti("replabel", 0);   // tokens, then the replabels; no blank (Train's count)
     else numClasses += 1;                                    // blank, appended LAST
     const int numTokens = asg ? numClasses : numClasses - 1;   // the classes a hypothesis is made of
-    const long beamLimit = flags.has("beamsize") ? 1024 : 64;   // a beam width that was asked for runs the wide kernels above 64
+    // a beam width that was asked for runs the wide kernels above 64, and with --w2l_beam_xl=true the xl kernels above 1024
+    const bool xlFlag = flags.getb("w2l_beam_xl", false);
+    const long beamLimit = flags.has("beamsize") ? (xlFlag ? 8192 : 1024) : 64;
     if (beamSize > beamLimit) {
       std::cerr << "[Decode] --beamsize=" << beamSize << " limited to " << beamLimit << " (the kernel's beam width)" << std::endl;
       beamSize = beamLimit;
     }
-    const bool wide = beamSize > 64;
+    const bool xl = beamSize > 1024, wide = beamSize > 64 && !xl;
     beamToken = std::min<long>(beamToken, numTokens);
     if (beamToken > 64) { std::cerr << "[Decode] --beamsizetoken limited to 64 tokens per frame" << std::endl; beamToken = 64; }
     const int M = beamDump ? (int)std::min(nbest, beamSize) : 1;
@@ -192,7 +197,7 @@ int main(int argc, char** argv) {
     Serializer::load(am, version, unused, network, criterion);
     network->eval();
     criterion->eval();
-    std::cerr << "[Decode] " << criterion->prettyString() << ", " << numClasses << " classes, model " << am << ", beam " << beamSize << (wide ? " (wide)" : "")
+    std::cerr << "[Decode] " << criterion->prettyString() << ", " << numClasses << " classes, model " << am << ", beam " << beamSize << (xl ? " (xl)" : wide ? " (wide)" : "")
               << ", tokens per frame " << beamToken << ", threshold " << threshold << (logAdd ? ", logadd" : ", max") << std::endl;
 
     // ---- the list
@@ -292,6 +297,7 @@ int main(int argc, char** argv) {
       BeamSearchOptions opt;
       opt.beamSize = (int)beamSize;
       opt.wide = wide;
+      opt.xl = xl;
       opt.beamSizeToken = (int)beamToken;
       opt.beamThreshold = (float)threshold;
       opt.logAdd = logAdd;

@@ -1475,6 +1475,7 @@ StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int n
   if (o.wide)
     throw std::runtime_error("StreamingDecoder runs the narrow searches (beam up to 64); the wide searches are incremental as "
                              "WideStreamingDecoder");
+  if (o.xl) throw std::runtime_error("StreamingDecoder runs the narrow searches (beam up to 64); the xl searches have no sessions");
   create(false);
 }
 StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& o, WideKernels)
@@ -1602,9 +1603,10 @@ void StreamingDecoder::reset(int slot) {
 }
 
 // n-best beam search; inputSizes as in viterbiPathWithTarget.  trans == nullptr: the CTC searches (w2l_ctc_beam_search*), blank =
-// N-1; else the ASG searches (w2l_asg_beam_search*) under that transition matrix, every class a token; o.wide: their _wide twins
+// N-1; else the ASG searches (w2l_asg_beam_search*) under that transition matrix, every class a token; o.wide: their _wide twins, o.xl: their _xl twins
 static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, const float* trans, const af::array& input,
                                       const af::array& inputSizes, const BeamSearchOptions& o) {
+  if (o.xl && o.wide) throw std::invalid_argument("beamSearch: wide and xl name two kernel families, choose one");
   const int N = (int)input.dims(0), T = (int)input.dims(1), B = (int)input.dims(2);
   const int* frames = nullptr;
   if (!inputSizes.isempty()) {
@@ -1632,18 +1634,18 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
     r.lmScores = af::array(af::dim4(o.nbest, B));
     r.words = af::array(af::dim4(maxWords, o.nbest, B), af::s32);
     r.wordCounts = af::array(af::dim4(o.nbest, B), af::s32);
-    auto wsx = devAlloc((trans ? (o.wide ? w2l_asg_beam_lex_wide_workspace_size : w2l_asg_beam_lex_workspace_size)
-                               : (o.wide ? w2l_ctc_beam_lex_wide_workspace_size : w2l_ctc_beam_lex_workspace_size))(
+    auto wsx = devAlloc((trans ? (o.xl ? w2l_asg_beam_lex_xl_workspace_size : o.wide ? w2l_asg_beam_lex_wide_workspace_size : w2l_asg_beam_lex_workspace_size)
+                               : (o.xl ? w2l_ctc_beam_lex_xl_workspace_size : o.wide ? w2l_ctc_beam_lex_wide_workspace_size : w2l_ctc_beam_lex_workspace_size))(
                             B, T, N, o.beamSize, o.beamSizeToken) + 256);
     if (trans)
-      w2l::w2lCheck((o.wide ? w2l_asg_beam_search_lex_wide : w2l_asg_beam_search_lex)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
+      w2l::w2lCheck((o.xl ? w2l_asg_beam_search_lex_xl : o.wide ? w2l_asg_beam_search_lex_wide : w2l_asg_beam_search_lex)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
                                             o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
                                             o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
                                             r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
                                             r.words.device<int>(), r.wordCounts.device<int>(), wsx.get(), S()),
                     "asg beam search with lexicon");
     else
-      w2l::w2lCheck((o.wide ? w2l_ctc_beam_search_lex_wide : w2l_ctc_beam_search_lex)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+      w2l::w2lCheck((o.xl ? w2l_ctc_beam_search_lex_xl : o.wide ? w2l_ctc_beam_search_lex_wide : w2l_ctc_beam_search_lex)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
                                             normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
                                             o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
                                             r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
@@ -1658,8 +1660,8 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
       throw std::invalid_argument("beamSearch: lmWeight, classScore and eosScore need lm");
     if (trans) {   // the lexicon-free ASG search is one entry point: a null LM means none
       af::array lms(af::dim4(o.nbest, B));
-      auto wsa = devAlloc((o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-      w2l::w2lCheck((o.wide ? w2l_asg_beam_search_wide : w2l_asg_beam_search)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
+      auto wsa = devAlloc((o.xl ? w2l_asg_beam_xl_workspace_size : o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+      w2l::w2lCheck((o.xl ? w2l_asg_beam_search_xl : o.wide ? w2l_asg_beam_search_wide : w2l_asg_beam_search)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
                                         o.logAdd, normalize, o.nbest, Lmax, nullptr, 0, 0.f, nullptr, 0.f, r.labels.device<int>(),
                                         r.lengths.device<int>(), r.scores.device<float>(), lms.device<float>(), wsa.get(), S()),
                     "asg beam search");
@@ -1673,18 +1675,18 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
     if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != tokens))
       throw std::invalid_argument("beamSearch: classScore must be f32 with one entry per token class");
     r.lmScores = af::array(af::dim4(o.nbest, B));
-    auto wsl = devAlloc((trans ? (o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)
-                               : (o.wide ? w2l_ctc_beam_lm_wide_workspace_size : w2l_ctc_beam_lm_workspace_size))(
+    auto wsl = devAlloc((trans ? (o.xl ? w2l_asg_beam_xl_workspace_size : o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)
+                               : (o.xl ? w2l_ctc_beam_lm_xl_workspace_size : o.wide ? w2l_ctc_beam_lm_wide_workspace_size : w2l_ctc_beam_lm_workspace_size))(
                             B, T, N, o.beamSize, o.beamSizeToken) + 256);
     if (trans)
-      w2l::w2lCheck((o.wide ? w2l_asg_beam_search_wide : w2l_asg_beam_search)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
+      w2l::w2lCheck((o.xl ? w2l_asg_beam_search_xl : o.wide ? w2l_asg_beam_search_wide : w2l_asg_beam_search)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
                                         o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
                                         o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
                                         r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
                                         r.lmScores.device<float>(), wsl.get(), S()),
                     "asg beam search with LM");
     else
-      w2l::w2lCheck((o.wide ? w2l_ctc_beam_search_lm_wide : w2l_ctc_beam_search_lm)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+      w2l::w2lCheck((o.xl ? w2l_ctc_beam_search_lm_xl : o.wide ? w2l_ctc_beam_search_lm_wide : w2l_ctc_beam_search_lm)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
                                            normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
                                            o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
                                            r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
@@ -1693,9 +1695,9 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
     af::sync();  // wsl is released at return
     return r;
   }
-  if (o.wide) {   // the LM-free CTC search's wide twin
-    auto wsw = devAlloc(w2l_ctc_beam_wide_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-    w2l::w2lCheck(w2l_ctc_beam_search_wide(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
+  if (o.wide || o.xl) {   // the LM-free CTC search's wide and xl twins
+    auto wsw = devAlloc((o.xl ? w2l_ctc_beam_xl_workspace_size : w2l_ctc_beam_wide_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    w2l::w2lCheck((o.xl ? w2l_ctc_beam_search_xl : w2l_ctc_beam_search_wide)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
                                            normalize, o.nbest, Lmax, r.labels.device<int>(), r.lengths.device<int>(),
                                            r.scores.device<float>(), wsw.get(), S()),
                   "ctc beam search");
