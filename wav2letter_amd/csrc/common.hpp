@@ -118,6 +118,23 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// LayerNorm statistics: a group whose mean is more than 8 of its standard deviations from zero.  Sums of r and r^2 in fp32 partials
+// of four lose 6e-8 (mu^2 + var) / var of var: below 4e-6 up to here, and growing with mu^2 / var beyond -- where the kernels take
+// their sums again about the mean they found (elementwise.hip::residual_ln_small_k).  Negative or zero var (a constant group) counts.
+constexpr double kLnIllCond = 64.0;
+__device__ __forceinline__ bool ln_ill_conditioned(double mu, double var) { return mu * mu > kLnIllCond * var; }
+
+// LayerNorm backward: sum dy * xhat of a group of n, freed of the common shift that xhat = (r - mu) * rstd carries because the
+// saved mu is an fp32 rounding of the mean (s1 = sum dy, s2 = sum dy * xhat, s3 = sum xhat; elementwise.hip::ln_bwd_reduce_k).
+// The shift is at most 3e-8 |mu| rstd: a group whose mean lies within four standard deviations of zero (shift below 1.2e-7) keeps
+// the bits it always had.  (The bound is lower than the forward's: the shift reaches dr multiplied by mean(dy) / spread(dy) and by
+// the group's largest |xhat| -- 100 x 48 for a dy of mean 100 on a group with one outlier, whose mu^2 / var is only 28.)
+constexpr double kLnBwdCond = 16.0;
+__device__ __forceinline__ double ln_bwd_centre(double s1, double s2, double s3, double n, float mu, float rstd) {
+  const double q = (double)mu * (double)rstd;
+  return q * q > kLnBwdCond ? s2 - s1 / n * s3 : s2;
+}
+
 // value of lane-1 (lane 0 receives `fill`)
 __device__ __forceinline__ float lane_shift_up(float v, float fill) {
   float r = __shfl_up(v, 1);

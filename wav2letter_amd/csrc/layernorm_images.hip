@@ -133,10 +133,26 @@ __global__ __launch_bounds__(kLiThreads) void ln_rows_images_k(LiP p) {
           ss += (double)((rv.x * rv.x + rv.y * rv.y) + (rv.z * rv.z + rv.w * rv.w));
         }
       }
+      // the statistic exactly as elementwise.hip::residual_ln_wave_k (see residual_ln_small_k there)
       s = wave_sum_f64(s);
       ss = wave_sum_f64(ss);
-      const double mu = s / (double)inner;
+      double mu = s / (double)inner;
       double var = ss / (double)inner - mu * mu;
+      if (ln_ill_conditioned(mu, var)) {
+        const float K = (float)mu;
+        s = 0; ss = 0;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          if (lane + 64 * j < n4) {
+            const float4 d = make_float4(v[j].x - K, v[j].y - K, v[j].z - K, v[j].w - K);
+            s += (double)((d.x + d.y) + (d.z + d.w));
+            ss += (double)((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w));
+          }
+        }
+        const double m = wave_sum_f64(s) / (double)inner;
+        mu = (double)K + m;
+        var = wave_sum_f64(ss) / (double)inner - m * m;
+      }
       if (var < 0) var = 0;
       const float rstd = (float)(1.0 / sqrt(var + (double)p.eps));
       const float muf = (float)mu;
@@ -173,7 +189,7 @@ __global__ __launch_bounds__(kLiThreads) void ln_rows_images_k(LiP p) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) mvs[j] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
-      double s1 = 0, s2 = 0;
+      double s1 = 0, s2 = 0, s3 = 0;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int i = lane + 64 * j;
@@ -182,10 +198,11 @@ __global__ __launch_bounds__(kLiThreads) void ln_rows_images_k(LiP p) {
         if (i < n4) {
           s1 += (double)((dv[j].x + dv[j].y) + (dv[j].z + dv[j].w));
           s2 += (double)((dv[j].x * xh[j].x + dv[j].y * xh[j].y) + (dv[j].z * xh[j].z + dv[j].w * xh[j].w));
+          s3 += (double)((xh[j].x + xh[j].y) + (xh[j].z + xh[j].w));
         }
       }
       s1 = wave_sum_f64(s1);
-      s2 = wave_sum_f64(s2);
+      s2 = ln_bwd_centre(s1, wave_sum_f64(s2), wave_sum_f64(s3), (double)inner, mu, rstd);   // (as elementwise.hip::ln_bwd_wave_k)
       if (lane == 0) { p.sums[2 * g] = s1; p.sums[2 * g + 1] = s2; }
       const float c1 = (float)(s1 / (double)inner), c2 = (float)(s2 / (double)inner);
       const float gr = p.gammaBeta[0] * rstd;
