@@ -701,6 +701,12 @@ struct BeamSearchOptions {
   int maxWords = 0;                   // rows of `words`, 0 = Lmax
   bool wide = false;                  // every search above on the wide kernels (the w2l_*_wide entry points): the same contract, the same bytes at W <= 64
   bool xl = false;                    // every search above on the xl kernels (the w2l_*_xl entry points): the same contract, the wide kernels' bytes at W <= 1024; with wide: std::invalid_argument
+  // the silence score (the w2l_*_sil entry points; the reference's --silscore): after the frame tokens have been chosen by the
+  // acoustic lp alone, class silToken's frame score is lp + silScore wherever the search reads it.  silToken -1 with a lexicon: the
+  // lexicon's silence token.  silScore != 0 without any silence token: std::invalid_argument.  silScore == 0: the search without it,
+  // the same bytes.  The streaming decoders below have no silence score: a non-zero silScore there is std::invalid_argument.
+  int silToken = -1;
+  float silScore = 0.f;
 };
 struct BeamSearchResult {
   af::array labels;    // (Lmax, M, B) s32: the first min(length, Lmax) labels, -1 beyond

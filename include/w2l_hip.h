@@ -311,7 +311,7 @@ int w2l_lexicon_node(const void* blob, int node, float* smear, int* nw, int* wor
  *     lengths as before, silence tokens included; words[b][m] the first min(count, maxWords) word ids and -1 beyond;
  *     wordCounts[b][m] the true count, -1 for empty rows; lmScores as in the LM search.  When no entry is at the root, all M rows
  *     of the utterance are empty.
- * Not part of the contract: an unknown-word arc, a silence score, log-add smearing.
+ * Not part of the contract: an unknown-word arc, log-add smearing.  (A silence score: the *_sil entry points below.)
  * With logAdd = 0 the result is reproducible bit for bit (same exception for the sign of a zero).
  * Limits and refusals: w2l_ctc_beam_search_lm's, and lexicon, words or wordCounts NULL, maxWords < 1, wordScore not finite
  * (W2L_EINVAL), all before anything touches the device.  lexicon and lm are device memory and NOT checked: the kernel bounds every
@@ -461,6 +461,66 @@ int w2l_asg_beam_search_lex_xl(int B, int T, int N, const float* input /*[B][T][
                                int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
                                float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
                                int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream);
+/* The five beam searches with a SILENCE SCORE (the reference's --silscore, older name --silweight; csrc/criterion_beam_sil.hpp,
+ * DESIGN 3.26).  Each takes `family` first -- 0: the narrow search above, 1: its wide twin, 2: its xl twin --, then its sibling's
+ * argument list, then silToken and silScore.  One rule covers all five searches in all three families:
+ *   With silToken in range and silScore finite, the frame score of class silToken is replaced, AFTER THE FRAME TOKENS HAVE BEEN
+ *   CHOSEN, by lp_t[sil] + silScore: one fp32 add; with normalize = 1 it is (x - lse) + silScore, lse taken from the raw row.
+ *   Every later use of lp_t[sil] reads this value: the stay of an entry whose last label is sil; every extension by sil, in the
+ *   lexicon searches the root's sil slot and any trie edge on that token; the merged term, thresholds, totals, keys.  Frame
+ *   tokens, their order and the tie key's k are still those of the acoustic lp alone: the reference too picks its beamSizeToken
+ *   candidates before it adds silScore.
+ * Everything else of each sibling's contract is unchanged.  This is the project's own operation sequence: the reference adds the
+ * term after the acoustic sum, in double; here it is part of the frame score, in fp32, before any sum.
+ * Consequences.  silScore == 0 or silToken == -1: the sibling's call -- the host routes it there, the same kernels and bytes, no
+ * + 0 is executed.  normalize = 0 and K >= the token count (selection cannot differ): every output equals, bit for bit, the
+ * sibling's on emissions whose sil column had silScore added on the host in fp32, in both logAdd modes; so the ASG max search
+ * without LM is still w2l_viterbi_compute's path and score on those emissions.  The three families agree bit for bit at every W two
+ * of them accept.
+ * The narrow LM-free CTC search with a silence score does not run its sibling's one-wavefront scan, which relies on lp_k + tot
+ * being non-increasing in k; it runs the workgroup token scan without an LM, and its workspace is the LM search's.
+ * In the lexicon searches silToken is an argument like any other: the caller passes the lexicon's; the blob on the device is not
+ * checked against it.
+ * Limits and refusals: the chosen family's, in the sibling's order, and before them, before anything touches the device,
+ * W2L_EINVAL for family outside 0..2, for silScore not finite, and for silToken outside -1 .. N-2 (CTC: blank is no token) or
+ * -1 .. N-1 (ASG).  The *_sil_workspace_size functions are host arithmetic and return 0 for what the call refuses (they do not see
+ * silToken and silScore). */
+size_t w2l_ctc_beam_sil_workspace_size(int family, int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_sil(int family, int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                            int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                            int nbest /*M*/, int maxLen /*Lmax*/,
+                            int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                            void* workspace, w2l_stream_t stream, int silToken, float silScore);
+size_t w2l_ctc_beam_lm_sil_workspace_size(int family, int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lm_sil(int family, int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                               int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                               int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                               const float* classScore /*[N-1] or NULL*/, float eosScore,
+                               int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                               float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
+size_t w2l_ctc_beam_lex_sil_workspace_size(int family, int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lex_sil(int family, int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                                int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                                int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                                const void* lexicon, float wordScore, float eosScore,
+                                int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                                float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                                int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
+size_t w2l_asg_beam_sil_workspace_size(int family, int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_sil(int family, int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                            const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/, float threshold,
+                            int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm /*or NULL*/,
+                            int lmHasEos, float lmWeight, const float* classScore /*[N] or NULL*/, float eosScore,
+                            int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                            float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
+size_t w2l_asg_beam_lex_sil_workspace_size(int family, int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_lex_sil(int family, int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                                const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/,
+                                float threshold, int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm,
+                                int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
+                                int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                                float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                                int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the

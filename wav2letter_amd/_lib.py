@@ -156,6 +156,17 @@ class _SIGS:
                                          _p, _p])
     w2l_ctc_beam_search_lex_xl = (_i, [_i, _i, _i, _p, _p, _i, _i, _f, _i, _i, _i, _i, _p, _i, _f, _p, _f, _f, _p, _p, _p, _p, _i, _p, _p,
                                        _p, _p])
+    # the five searches with a silence score: int family first, the sibling's arguments, then int silToken, float silScore
+    w2l_ctc_beam_sil_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])
+    w2l_ctc_beam_lm_sil_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])
+    w2l_ctc_beam_lex_sil_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])
+    w2l_asg_beam_sil_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])
+    w2l_asg_beam_lex_sil_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])
+    w2l_ctc_beam_search_sil = (_i, [_i] + w2l_ctc_beam_search[1] + [_i, _f])
+    w2l_ctc_beam_search_lm_sil = (_i, [_i] + w2l_ctc_beam_search_lm[1] + [_i, _f])
+    w2l_ctc_beam_search_lex_sil = (_i, [_i] + w2l_ctc_beam_search_lex[1] + [_i, _f])
+    w2l_asg_beam_search_sil = (_i, [_i] + w2l_asg_beam_search[1] + [_i, _f])
+    w2l_asg_beam_search_lex_sil = (_i, [_i] + w2l_asg_beam_search_lex[1] + [_i, _f])
     w2l_host_last_error = (C.c_char_p, [])
     w2l_gemm_f32 = (_i, [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _p])
     w2l_linear_forward = (_i, [_i, _i, _i, _p, _p, _p, _p, _i, _p])

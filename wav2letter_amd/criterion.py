@@ -318,9 +318,37 @@ def _wide(L, name, wide):
     return getattr(L, name + suffix)
 
 
+def _beam_fn(L, name, wide, sil):
+    """_wide(L, name, wide), or with sil = (token, score) the *_sil entry point behind the same call: the family goes in front
+    (0 narrow, 1 wide, 2 xl), the silence token and score behind"""
+    f = _wide(L, name, wide)   # checks `wide`
+    if sil is None:
+        return f
+    family = 2 if wide == "xl" else (1 if wide else 0)
+    if name.endswith("_workspace_size"):
+        g = getattr(L, name[:-len("_workspace_size")] + "_sil_workspace_size")
+        return lambda *a: g(family, *a)
+    g = getattr(L, name + "_sil")
+    return lambda *a: g(family, *a, sil[0], sil[1])
+
+
+def _sil_args(who, sil_token, sil_score, lexicon):
+    """(token, score) for the *_sil entry points, or None: the call without a silence score.  sil_token None: the lexicon's"""
+    sil_score = float(sil_score)
+    if sil_token is None and lexicon is not None and lexicon.sil >= 0:
+        sil_token = lexicon.sil
+    if sil_token is None:
+        if sil_score != 0.0:
+            raise _lib.W2LInvalidArgument(f"{who}: sil_score needs a silence token (sil_token=, or a lexicon that has one)")
+        return None
+    if sil_score == 0.0 and int(sil_token) == -1:
+        return None
+    return int(sil_token), sil_score
+
+
 def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=None,
                     nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
-                    max_words=None, wide=False):
+                    max_words=None, wide=False, sil_token=None, sil_score=0.0):
     """CTC prefix beam search without lexicon or LM (w2l_ctc_beam_search; the contract is in include/w2l_hip.h): `emission`
     [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64; <= 1024 with wide=True; <= 8192 with wide="xl"), beam_token = K (clipped to N-1, then <= 64),
     log_add: sum (True) or max (False) over the alignments of a prefix; normalize: search on log-softmax rows (default: log_add --
@@ -339,9 +367,14 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     wide: run the wide kernels (the w2l_*_wide entry points): the same contract with beam up to 1024; beam_token stays <= 64.  At
     beam <= 64 both kernel families return the same bytes.  wide="xl": run the xl kernels (the w2l_*_xl entry points): the same
     contract with beam up to 8192, the widths the reference's decoding recipes ask for; at beam <= 1024 they return the wide
-    kernels' bytes.  No family is chosen for the caller: wide=True with beam > 1024 is refused as before."""
+    kernels' bytes.  No family is chosen for the caller: wide=True with beam > 1024 is refused as before.
+    sil_token, sil_score: the silence score (the w2l_*_sil entry points; the reference's --silscore): after the frame tokens have
+    been chosen by the acoustic lp alone, class sil_token's frame score is lp + sil_score wherever the search reads it.
+    sil_token=None with a lexicon: the lexicon's silence token.  A non-zero sil_score without any silence token is refused;
+    sil_score = 0 is the search without a silence score, the same bytes."""
     _emission_checks(emission)
     B, T, N = emission.shape
+    sil = _sil_args("ctc_beam_search", sil_token, sil_score, lexicon)
     if lexicon is not None:
         if lm is None:
             raise _lib.W2LInvalidArgument("ctc_beam_search: lexicon needs lm, a model over the lexicon's words")
@@ -385,12 +418,12 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
     if lexicon is not None:
         max_words = max(max_len, 1) if max_words is None else int(max_words)
-        ws = _ws(_wide(L, "w2l_ctc_beam_lex_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), emission.device)
+        ws = _ws(_beam_fn(L, "w2l_ctc_beam_lex_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), emission.device)
         lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
         words = torch.empty(*shape, max_words, dtype=torch.int32, device=emission.device)
         word_counts = torch.empty(*shape, dtype=torch.int32, device=emission.device)
         blob, lex_blob = lm.device_blob(emission.device), lexicon.device_blob(emission.device)
-        _lib.check(_wide(L, "w2l_ctc_beam_search_lex", wide)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
+        _lib.check(_beam_fn(L, "w2l_ctc_beam_search_lex", wide, sil)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
                                              int(beam), int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)),
                                              nbest, max_len, blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
                                              float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),
@@ -401,18 +434,18 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
         if class_score is not None:
             _check_dev(emission, class_score)
             class_score = class_score.contiguous()
-        ws = _ws(_wide(L, "w2l_ctc_beam_lm_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), emission.device)
+        ws = _ws(_beam_fn(L, "w2l_ctc_beam_lm_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), emission.device)
         lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
         blob = lm.device_blob(emission.device)
-        _lib.check(_wide(L, "w2l_ctc_beam_search_lm", wide)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
+        _lib.check(_beam_fn(L, "w2l_ctc_beam_search_lm", wide, sil)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
                                             int(beam), int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)),
                                             nbest, max_len, blob.data_ptr(), int(lm.has_eos), float(lm_weight),
                                             class_score.data_ptr() if class_score is not None else None, float(eos_score),
                                             labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), lm_scores.data_ptr(),
                                             ws.data_ptr(), _stream()), "ctc_beam_search")
         return labels, lengths, scores, lm_scores
-    ws = _ws(_wide(L, "w2l_ctc_beam_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), emission.device)
-    _lib.check(_wide(L, "w2l_ctc_beam_search", wide)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None, int(beam),
+    ws = _ws(_beam_fn(L, "w2l_ctc_beam_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), emission.device)
+    _lib.check(_beam_fn(L, "w2l_ctc_beam_search", wide, sil)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None, int(beam),
                                      int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
                                      labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), ws.data_ptr(), _stream()),
                "ctc_beam_search")
@@ -421,15 +454,16 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
 
 def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=False,
                     nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
-                    max_words=None, wide=False):
+                    max_words=None, wide=False, sil_token=None, sil_score=0.0):
     """Beam search of an ASG model (w2l_asg_beam_search, w2l_asg_beam_search_lex; the contract is in include/w2l_hip.h):
     `emission` [B][T][N], every class a token (no blank), `transitions` [N][N] float32 (to x from) on the emissions' device.  The
     options and the return values are ctc_beam_search's -- (labels, lengths, scores), lm_scores with an LM, words and word_counts
     with a lexicon -- with beam_token clipped to N, an LM (or lexicon) over N tokens and class_score [N].  normalize defaults to
     False in both log_add modes: ASG scores are unnormalised by design.  A token never follows itself: a repeated letter is a
-    replabel's (Lexicon.from_file(..., replabel=) packs the spellings).  wide: as in ctc_beam_search."""
+    replabel's (Lexicon.from_file(..., replabel=) packs the spellings).  wide, sil_token, sil_score: as in ctc_beam_search."""
     _emission_checks(emission)
     B, T, N = emission.shape
+    sil = _sil_args("asg_beam_search", sil_token, sil_score, lexicon)
     if transitions.dtype != torch.float32 or tuple(transitions.shape) != (N, N):
         raise _lib.W2LInvalidArgument(f"asg_beam_search: transitions must be float32 [{N}][{N}]")
     if lexicon is not None:
@@ -475,11 +509,11 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
     lm_scores = torch.empty(*shape, dtype=torch.float32, device=dev)
     if lexicon is not None:
         max_words = max(max_len, 1) if max_words is None else int(max_words)
-        ws = _ws(_wide(L, "w2l_asg_beam_lex_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), dev)
+        ws = _ws(_beam_fn(L, "w2l_asg_beam_lex_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), dev)
         words = torch.empty(*shape, max_words, dtype=torch.int32, device=dev)
         word_counts = torch.empty(*shape, dtype=torch.int32, device=dev)
         blob, lex_blob = lm.device_blob(dev), lexicon.device_blob(dev)
-        _lib.check(_wide(L, "w2l_asg_beam_search_lex", wide)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
+        _lib.check(_beam_fn(L, "w2l_asg_beam_search_lex", wide, sil)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
                                              float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
                                              blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
                                              float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),
@@ -490,8 +524,8 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
         _check_dev(emission, class_score)
         class_score = class_score.contiguous()
     blob = lm.device_blob(dev) if lm is not None else None
-    ws = _ws(_wide(L, "w2l_asg_beam_workspace_size", wide)(B, T, N, int(beam), int(beam_token)), dev)
-    _lib.check(_wide(L, "w2l_asg_beam_search", wide)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
+    ws = _ws(_beam_fn(L, "w2l_asg_beam_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), dev)
+    _lib.check(_beam_fn(L, "w2l_asg_beam_search", wide, sil)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
                                      float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
                                      blob.data_ptr() if blob is not None else None, int(lm.has_eos) if lm is not None else 0,
                                      float(lm_weight), class_score.data_ptr() if class_score is not None else None,

@@ -60,11 +60,12 @@ W2L_API size_t w2l_asg_beam_lex_workspace_size(int B, int T, int N, int beam, in
   return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, true);
 }
 
-W2L_API int w2l_asg_beam_search(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+namespace w2l {
+// w2l_asg_beam_search with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int asg_beam_search_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
                                 int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                 int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !trans) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -75,7 +76,7 @@ W2L_API int w2l_asg_beam_search(int B, int T, int N, const float* input, const i
     return rc;
   hipStream_t s = (hipStream_t)stream;
   CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamLm, B, T, N, input, frames, beam, K, normalize, workspace, s, true)) return rc;
+  if (const int rc = ctc_beam_begin(&ws, kBeamLm, B, T, N, input, frames, beam, K, normalize, workspace, s, true, sil)) return rc;
   size_t lds = 0;
   const BeamTrans tr = asg_beam_trans(trans, N, &lds);
   ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
@@ -88,13 +89,23 @@ W2L_API int w2l_asg_beam_search(int B, int T, int N, const float* input, const i
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }
+}  // namespace w2l
 
-W2L_API int w2l_asg_beam_search_lex(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+W2L_API int w2l_asg_beam_search(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+                                int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
+                                float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
+  return w2l::asg_beam_search_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
+      lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
+}
+
+namespace w2l {
+// w2l_asg_beam_search_lex with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int asg_beam_search_lex_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
                                     int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
                                     const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
                                     float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                    int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                    int* words, int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1 || !trans) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -104,7 +115,7 @@ W2L_API int w2l_asg_beam_search_lex(int B, int T, int N, const float* input, con
     return rc;
   hipStream_t s = (hipStream_t)stream;
   CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamLex, B, T, N, input, frames, beam, K, normalize, workspace, s, true)) return rc;
+  if (const int rc = ctc_beam_begin(&ws, kBeamLex, B, T, N, input, frames, beam, K, normalize, workspace, s, true, sil)) return rc;
   size_t lds = 0;
   const BeamTrans tr = asg_beam_trans(trans, N, &lds);
   ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
@@ -117,4 +128,15 @@ W2L_API int w2l_asg_beam_search_lex(int B, int T, int N, const float* input, con
                      eosScore, lmHasEos ? 1 : 0, labels, lengths, scores, lmScores, words, wordCounts);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
+}
+}  // namespace w2l
+
+W2L_API int w2l_asg_beam_search_lex(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+                                    int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
+                                    const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
+                                    float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
+                                    int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
+  return w2l::asg_beam_search_lex_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
+      lm, lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts,
+      workspace, stream, w2l::BeamSil{});
 }

@@ -236,7 +236,8 @@ __device__ __forceinline__ void beam_wide_scan_body(int T, int N, int W, float t
           h = (h + 1) & (kWideHash - 1);
         }
       }
-      Pol::stay(e >= 0 ? xb[(size_t)t * N + e] - lse : 0.f, e, lpb, cPnb[tid], cTot[tid], A, N, &spb, &spnb);
+      Pol::stay(e >= 0 ? beam_sil_lp(xb[(size_t)t * N + e] - lse, e, ws.sil, ws.silScore) : 0.f, e, lpb, cPnb[tid], cTot[tid], A, N,
+                &spb, &spnb);
       if (pr >= 0 && kj >= 0) {
         float v = Pol::ext(sTl[kj], e, cE[pr], cPb[pr], cTot[pr], A, N);
         if constexpr (!kLex) {
@@ -560,10 +561,11 @@ static int beam_wide_run(int B, int T, int N, const float* input, const int* fra
                          float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
                          float lmWeight, const float* classScore, const void* lex, float wordScore, float eosScore, int* labels,
                          int* lengths, float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                         hipStream_t s) {
+                         hipStream_t s, BeamSil sil) {
   const bool asg = trans != nullptr, isLex = lex != nullptr;
   BeamWideWs ww{};
   beam_wide_layout(&ww, workspace, B, T, beam, K, isLex ? kBeamLex : kBeamLm);
+  ww.c.sil = sil.token; ww.c.silScore = sil.score;
   W2L_HIP_CHECK(hipMemsetAsync(ww.c.table, 0, (size_t)B * ww.c.cap * sizeof(u64), s));
   const unsigned rows = (unsigned)((size_t)B * T);
   const bool big = N > kRowThreads * kRowMaxPer;
@@ -620,23 +622,33 @@ W2L_API size_t w2l_asg_beam_lex_wide_workspace_size(int B, int T, int N, int bea
   return w2l::beam_wide_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, true);
 }
 
-W2L_API int w2l_ctc_beam_search_wide(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+namespace w2l {
+// w2l_ctc_beam_search_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int ctc_beam_search_wide_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                      float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
-                                     float* scores, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                     float* scores, void* workspace, w2l_stream_t stream, BeamSil sil) {
   int K = 0;
   if (const int rc = beam_wide_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
                                      false))
     return rc;
   return beam_wide_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, nullptr, 0, 0.f, nullptr,
-                       nullptr, 0.f, 0.f, labels, lengths, scores, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream);
+                       nullptr, 0.f, 0.f, labels, lengths, scores, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_ctc_beam_search_wide(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                     float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
+                                     float* scores, void* workspace, w2l_stream_t stream) {
+  return w2l::ctc_beam_search_wide_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
+      labels, lengths, scores, workspace, stream, w2l::BeamSil{});
 }
 
-W2L_API int w2l_ctc_beam_search_lm_wide(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+namespace w2l {
+// w2l_ctc_beam_search_lm_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int ctc_beam_search_lm_wide_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                         float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                         int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
-                                        int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                        int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !lm) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -646,15 +658,25 @@ W2L_API int w2l_ctc_beam_search_lm_wide(int B, int T, int N, const float* input,
     return rc;
   return beam_wide_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                        classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                       (hipStream_t)stream);
+                       (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_ctc_beam_search_lm_wide(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                        float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                        int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
+                                        int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
+  return w2l::ctc_beam_search_lm_wide_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
+      lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
 }
 
-W2L_API int w2l_ctc_beam_search_lex_wide(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+namespace w2l {
+// w2l_ctc_beam_search_lex_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int ctc_beam_search_lex_wide_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                          float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                          int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
                                          int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
-                                         int* wordCounts, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                         int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -664,14 +686,26 @@ W2L_API int w2l_ctc_beam_search_lex_wide(int B, int T, int N, const float* input
     return rc;
   return beam_wide_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                        nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                       (hipStream_t)stream);
+                       (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_ctc_beam_search_lex_wide(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                         float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                         int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
+                                         int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
+                                         int* wordCounts, void* workspace, w2l_stream_t stream) {
+  return w2l::ctc_beam_search_lex_wide_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
+      lm, lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts,
+      workspace, stream, w2l::BeamSil{});
 }
 
-W2L_API int w2l_asg_beam_search_wide(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+namespace w2l {
+// w2l_asg_beam_search_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int asg_beam_search_wide_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
                                      int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                      int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                     float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                     float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !trans) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -682,15 +716,25 @@ W2L_API int w2l_asg_beam_search_wide(int B, int T, int N, const float* input, co
     return rc;
   return beam_wide_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                        classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                       (hipStream_t)stream);
+                       (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_asg_beam_search_wide(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+                                     int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                     int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
+                                     float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
+  return w2l::asg_beam_search_wide_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
+      lm, lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
 }
 
-W2L_API int w2l_asg_beam_search_lex_wide(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+namespace w2l {
+// w2l_asg_beam_search_lex_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int asg_beam_search_lex_wide_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
                                          int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
                                          const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
                                          float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                         int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                         int* words, int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1 || !trans) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -700,5 +744,16 @@ W2L_API int w2l_asg_beam_search_lex_wide(int B, int T, int N, const float* input
     return rc;
   return beam_wide_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                        nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                       (hipStream_t)stream);
+                       (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_asg_beam_search_lex_wide(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+                                         int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
+                                         const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
+                                         float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
+                                         int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
+  return w2l::asg_beam_search_lex_wide_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest,
+      maxLen, lm, lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words,
+      wordCounts, workspace, stream, w2l::BeamSil{});
 }

@@ -103,7 +103,8 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
   float* const sTl = (float*)(base + XlLds::tl);
   unsigned* const sHist = (unsigned*)(base + XlLds::hist);
   u64* const sRed = (u64*)(base + XlLds::red);
-  unsigned* const sMisc = (unsigned*)(base + XlLds::misc);   // 0: candidates, 1: survivors, 2: bin, 3: keys above it, 4: keys in it
+  unsigned* const sMisc = (unsigned*)(base + XlLds::misc);   // 0: candidates, 1: survivors, 2: bin, 3: keys above it, 4: keys in it,
+                                                             // 5, 6: the silence class and score (below)
 
   const BeamWideWs& ww = xw.w;
   const CtcBeamWs& ws = ww.c;
@@ -133,6 +134,10 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
 
   int cur = 0, n = 1;
   if (tid == 0) {
+    // The silence class and score wait in LDS for the stays, which read them where they use them.  As two more scalar kernel
+    // arguments alive across the frame loop they cost this kernel, which stands at its scalar-register limit, more spilled scalars
+    // in the loop (3 to 5 % of a CTC search at W = 1024).  The first frame's barrier publishes them.
+    sMisc[5] = (unsigned)ws.sil; sMisc[6] = __float_as_uint(ws.silScore);
     fi(0, 0)[0] = 0; fi(0, 1)[0] = -1; fi(0, 2)[0] = -1; fi(0, 3)[0] = useLm ? (int)((const NgramHeader*)lm)->start : 0;
     ff(0, 4)[0] = 0.f; ff(0, 5)[0] = -INFINITY; ff(0, 6)[0] = 0.f; ff(0, 7)[0] = 0.f;
     if constexpr (kLex) fi(0, 8)[0] = -1;
@@ -187,7 +192,8 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
           h = (h + 1) & hm;
         }
       }
-      Pol::stay(e >= 0 ? xb[(size_t)t * N + e] - lse : 0.f, e, lpb, cPnb[j], cTot[j], A, N, &spb, &spnb);
+      Pol::stay(e >= 0 ? beam_sil_lp(xb[(size_t)t * N + e] - lse, e, (int)sMisc[5], __uint_as_float(sMisc[6])) : 0.f, e, lpb, cPnb[j],
+                cTot[j], A, N, &spb, &spnb);
       if (pr >= 0 && kj >= 0) {
         float v = Pol::ext(sTl[kj], e, cE[pr], cPb[pr], cTot[pr], A, N);
         if constexpr (!kLex) {
@@ -504,10 +510,11 @@ static int beam_xl_run(int B, int T, int N, const float* input, const int* frame
                        float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
                        float lmWeight, const float* classScore, const void* lex, float wordScore, float eosScore, int* labels,
                        int* lengths, float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                       hipStream_t s) {
+                       hipStream_t s, BeamSil sil) {
   const bool asg = trans != nullptr, isLex = lex != nullptr;
   BeamXlWs xw{};
   beam_xl_layout(&xw, workspace, B, T, beam, K, isLex ? kBeamLex : kBeamLm);
+  xw.w.c.sil = sil.token; xw.w.c.silScore = sil.score;
   const BeamWideWs& ww = xw.w;
   W2L_HIP_CHECK(hipMemsetAsync(ww.c.table, 0, (size_t)B * ww.c.cap * sizeof(u64), s));
   const unsigned rows = (unsigned)((size_t)B * T);
@@ -561,23 +568,33 @@ W2L_API size_t w2l_asg_beam_lex_xl_workspace_size(int B, int T, int N, int beam,
   return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, true);
 }
 
-W2L_API int w2l_ctc_beam_search_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+namespace w2l {
+// w2l_ctc_beam_search_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int ctc_beam_search_xl_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                    float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
-                                   float* scores, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                   float* scores, void* workspace, w2l_stream_t stream, BeamSil sil) {
   int K = 0;
   if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
                                    false))
     return rc;
   return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, nullptr, 0, 0.f, nullptr,
-                     nullptr, 0.f, 0.f, labels, lengths, scores, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream);
+                     nullptr, 0.f, 0.f, labels, lengths, scores, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_ctc_beam_search_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                   float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
+                                   float* scores, void* workspace, w2l_stream_t stream) {
+  return w2l::ctc_beam_search_xl_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, labels,
+      lengths, scores, workspace, stream, w2l::BeamSil{});
 }
 
-W2L_API int w2l_ctc_beam_search_lm_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+namespace w2l {
+// w2l_ctc_beam_search_lm_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int ctc_beam_search_lm_xl_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                       float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                       int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
-                                      int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                      int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !lm) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -587,15 +604,25 @@ W2L_API int w2l_ctc_beam_search_lm_xl(int B, int T, int N, const float* input, c
     return rc;
   return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                      classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                     (hipStream_t)stream);
+                     (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_ctc_beam_search_lm_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                      float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                      int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
+                                      int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
+  return w2l::ctc_beam_search_lm_xl_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
+      lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
 }
 
-W2L_API int w2l_ctc_beam_search_lex_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+namespace w2l {
+// w2l_ctc_beam_search_lex_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int ctc_beam_search_lex_xl_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                        float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                        int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
                                        int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
-                                       int* wordCounts, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                       int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -605,14 +632,26 @@ W2L_API int w2l_ctc_beam_search_lex_xl(int B, int T, int N, const float* input, 
     return rc;
   return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                      nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                     (hipStream_t)stream);
+                     (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_ctc_beam_search_lex_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                       float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                       int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
+                                       int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
+                                       int* wordCounts, void* workspace, w2l_stream_t stream) {
+  return w2l::ctc_beam_search_lex_xl_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
+      lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
+      stream, w2l::BeamSil{});
 }
 
-W2L_API int w2l_asg_beam_search_xl(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+namespace w2l {
+// w2l_asg_beam_search_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int asg_beam_search_xl_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
                                    int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                    int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !trans) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -623,15 +662,25 @@ W2L_API int w2l_asg_beam_search_xl(int B, int T, int N, const float* input, cons
     return rc;
   return beam_xl_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                      classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                     (hipStream_t)stream);
+                     (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_asg_beam_search_xl(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+                                   int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
+                                   int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
+                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
+  return w2l::asg_beam_search_xl_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
+      lm, lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
 }
 
-W2L_API int w2l_asg_beam_search_lex_xl(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+namespace w2l {
+// w2l_asg_beam_search_lex_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int asg_beam_search_lex_xl_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
                                        int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
                                        const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
                                        float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1 || !trans) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -641,5 +690,16 @@ W2L_API int w2l_asg_beam_search_lex_xl(int B, int T, int N, const float* input, 
     return rc;
   return beam_xl_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                      nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                     (hipStream_t)stream);
+                     (hipStream_t)stream, sil);
+}
+}  // namespace w2l
+
+W2L_API int w2l_asg_beam_search_lex_xl(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
+                                       int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
+                                       const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
+                                       float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
+                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
+  return w2l::asg_beam_search_lex_xl_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest,
+      maxLen, lm, lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words,
+      wordCounts, workspace, stream, w2l::BeamSil{});
 }

@@ -39,6 +39,8 @@ constexpr int kBeamWideMax = 1024;    // W of the wide searches (criterion_beam_
 constexpr int kBeamCandCap = 1024;    // LDS candidates of the row pass
 constexpr int kLmPer = 4;             // (entry, token) pairs a thread of a workgroup scan owns: threads * kLmPer >= W * K
 
+struct BeamSil { int token = -1; float score = 0.f; };   // a search's silence class and score; the default: none
+
 enum CtcBeamVariant { kBeamPlain = 0, kBeamLm = 1, kBeamLex = 2 };   // each one's workspace is the one before plus its own buffers
 
 struct CtcBeamWs {
@@ -55,7 +57,13 @@ struct CtcBeamWs {
   int* finU;                   // [B][64] lexicon node of the final entry of rank r            (null: but for kBeamLex)
   int K;
   unsigned cap;
+  int sil = -1;                // the silence class (the *_sil entry points of criterion_beam_sil.hpp); -1: none
+  float silScore = 0.f;        // added to lp[sil] after the frame tokens are chosen: beam_sil_lp
 };
+
+// The silence score of the contract: lp[c] of class c as every later use reads it.  One fp32 add, and none when c is not the silence
+// class (sil = -1 matches no class: the searches without a silence score execute no + 0).
+__device__ __forceinline__ float beam_sil_lp(float lp, int c, int sil, float silScore) { return c == sil ? lp + silScore : lp; }
 
 static size_t ctc_beam_cap(int T, int W) {
   const size_t need = 2 * (size_t)T * W;   // at most T * W nodes are ever made: load factor <= 1/2
@@ -218,9 +226,10 @@ __global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int n
       const u64 ki = sCand[i];
       int rk = 0;
       for (int j = 0; j < cnt; ++j) rk += sCand[j] > ki ? 1 : 0;
-      if (rk < K) {
-        oLp[rk] = beam_unord((unsigned)(ki >> 32));
-        oC[rk] = (int)(0xffffffffu - (unsigned)ki);
+      if (rk < K) {   // the list is in acoustic order; the silence score comes after selection and ranking
+        const int c = (int)(0xffffffffu - (unsigned)ki);
+        oLp[rk] = beam_sil_lp(beam_unord((unsigned)(ki >> 32)), c, ws.sil, ws.silScore);
+        oC[rk] = c;
       }
     }
   } else {   // the large values sit with few threads: K rounds of block-wide extraction
@@ -230,8 +239,9 @@ __global__ __launch_bounds__(kRowThreads) void ctc_beam_rows(int T, int N, int n
       each([&](float a, int i) { const u64 k = key(a, i); lm = (k < last && k > lm) ? k : lm; });
       const u64 w = block_max_u64(lm, sRed);
       if (tid == 0) {
-        oLp[q] = beam_unord((unsigned)(w >> 32));
-        oC[q] = (int)(0xffffffffu - (unsigned)w);
+        const int c = (int)(0xffffffffu - (unsigned)w);
+        oLp[q] = beam_sil_lp(beam_unord((unsigned)(w >> 32)), c, ws.sil, ws.silScore);
+        oC[q] = c;
       }
       last = w;
     }
@@ -428,7 +438,7 @@ template <class Pol = BeamCtc>
 __device__ __forceinline__ BeamStay beam_stay_front(int n, int K, const int* sTc, const float* sTl, const int* sNode,
                                                     const int* sPar, const int* sE, const float* sPb, const float* sPnb,
                                                     const float* sTot, const float* xrow, float lpb, float lse,
-                                                    const float* A = nullptr, int N = 0) {
+                                                    const float* A = nullptr, int N = 0, int sil = -1, float silScore = 0.f) {
   const int j = threadIdx.x;
   BeamStay s;
   s.e = sE[j];
@@ -436,8 +446,8 @@ __device__ __forceinline__ BeamStay beam_stay_front(int n, int K, const int* sTc
   s.kj = -1; s.pr = -1;
   for (int k = 0; k < K; ++k) s.kj = sTc[k] == s.e ? k : s.kj;
   for (int r = 0; r < n; ++r) s.pr = sNode[r] == par ? r : s.pr;
-  // lp[e] comes from the row whether or not e is a frame token
-  Pol::stay(s.e >= 0 ? xrow[s.e] - lse : 0.f, s.e, lpb, sPnb[j], sTot[j], A, N, &s.spb, &s.spnb);
+  // lp[e] comes from the row whether or not e is a frame token; with the silence score the extensions' tokLp carries
+  Pol::stay(s.e >= 0 ? beam_sil_lp(xrow[s.e] - lse, s.e, sil, silScore) : 0.f, s.e, lpb, sPnb[j], sTot[j], A, N, &s.spb, &s.spnb);
   s.merge = s.pr >= 0 && s.kj >= 0;
   s.a = 0.f;
   if (s.merge) s.a = Pol::ext(sTl[s.kj], s.e, sE[s.pr], sPb[s.pr], sTot[s.pr], A, N);
@@ -632,8 +642,9 @@ static int ctc_beam_check(int B, int T, int N, const float* input, int beam, int
 
 // the start of a call: the workspace, an empty prefix table, the frame tokens of every row
 static int ctc_beam_begin(CtcBeamWs* ws, int variant, int B, int T, int N, const float* input, const int* frames, int beam, int K,
-                          int normalize, void* workspace, hipStream_t s, bool noBlank = false) {
+                          int normalize, void* workspace, hipStream_t s, bool noBlank = false, BeamSil sil = BeamSil{}) {
   ctc_beam_layout(ws, workspace, B, T, beam, K, variant);
+  ws->sil = sil.token; ws->silScore = sil.score;
   W2L_HIP_CHECK(hipMemsetAsync(ws->table, 0, (size_t)B * ws->cap * sizeof(u64), s));
   const unsigned rows = (unsigned)((size_t)B * T);
   const bool big = N > kRowThreads * kRowMaxPer;

@@ -136,7 +136,7 @@ __device__ __forceinline__ void beam_lex_scan_body(int T, int N, int W, float th
     float spb = -INFINITY, spnb = -INFINITY, stot = -INFINITY;
     if (tid < n) {
       const BeamStay s = beam_stay_front<Pol>(n, K, sTc, sTl, sNode[cur], sPar[cur], sE[cur], sPb[cur], sPnb[cur], sTot[cur],
-                                              xb + (size_t)t * N, lpb, lse, A, N);
+                                              xb + (size_t)t * N, lpb, lse, A, N, ws.sil, ws.silScore);
       const int lab = sLab[cur][tid];
       spb = s.spb; spnb = s.spnb;
       if (s.merge && lab >= 0) {
@@ -308,12 +308,13 @@ W2L_API size_t w2l_ctc_beam_lex_workspace_size(int B, int T, int N, int beam, in
   return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex);
 }
 
-W2L_API int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+namespace w2l {
+// w2l_ctc_beam_search_lex with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int ctc_beam_search_lex_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                     float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
                                     float lmWeight, const void* lexicon, float wordScore, float eosScore, int* labels, int* lengths,
                                     float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                                    w2l_stream_t stream) {
-  using namespace w2l;
+                                    w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -322,7 +323,7 @@ W2L_API int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input, con
     return rc;
   hipStream_t s = (hipStream_t)stream;
   CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamLex, B, T, N, input, frames, beam, K, normalize, workspace, s)) return rc;
+  if (const int rc = ctc_beam_begin(&ws, kBeamLex, B, T, N, input, frames, beam, K, normalize, workspace, s, false, sil)) return rc;
   ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
     hipLaunchKernelGGL((ctc_beam_lex_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)B), dim3(decltype(th)::value), 0, s,
                        T, N, beam, threshold, input, frames, ws, lexicon, lm, lmWeight, wordScore, BeamTrans{});
@@ -332,4 +333,15 @@ W2L_API int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input, con
                      eosScore, lmHasEos ? 1 : 0, labels, lengths, scores, lmScores, words, wordCounts);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
+}
+}  // namespace w2l
+
+W2L_API int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                    float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
+                                    float lmWeight, const void* lexicon, float wordScore, float eosScore, int* labels, int* lengths,
+                                    float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
+                                    w2l_stream_t stream) {
+  return w2l::ctc_beam_search_lex_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
+      lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
+      stream, w2l::BeamSil{});
 }

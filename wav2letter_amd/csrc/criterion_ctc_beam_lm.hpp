@@ -32,7 +32,8 @@ __device__ __forceinline__ float beam_lm_ext(float a, float lmWeight, float q, c
   return a + g;
 }
 
-// Pol::kNoBlank or kResume: lm may be null, which means no LM: no g term, q = 0, state 0.
+// lm may be null, which means no LM: no g term, q = 0, state 0 (the ASG LM-free search, the LM-free session, and the LM-free CTC
+// search with a silence score, whose biased tokLp the lazy scan of criterion_ctc_beam.hpp cannot take).
 // kResume (criterion_beam_stream.hpp): utterance b is a slot of a beam session: its frame count (0: none) and start flag come from
 // cy.cnt / cy.flag, the beam from the session's state unless the slot starts, and every array of the beam goes back there after
 // the frames.  ctc_beam_lm_scan below is the body with kResume off: the whole search.
@@ -60,7 +61,7 @@ __device__ __forceinline__ void beam_lm_scan_body(int T, int N, int W, float thr
   u64* tab = ws.table + (size_t)b * ws.cap;
   const unsigned capm = ws.cap - 1;
   const size_t row0 = (size_t)b * T;
-  const bool useLm = !(Pol::kNoBlank || kResume) || lm != nullptr;
+  const bool useLm = lm != nullptr;
   const NgramView lv = useLm ? ngram_view(lm) : NgramView{};
   const float* A = Pol::stage(tr, N);
 
@@ -106,7 +107,7 @@ __device__ __forceinline__ void beam_lm_scan_body(int T, int N, int W, float thr
     float spb = -INFINITY, spnb = -INFINITY, stot = -INFINITY;
     if (tid < n) {
       const BeamStay s = beam_stay_front<Pol>(n, K, sTc, sTl, sNode[cur], sPar[cur], sE[cur], sPb[cur], sPnb[cur], sTot[cur],
-                                              xb + (size_t)t * N, lpb, lse, A, N);
+                                              xb + (size_t)t * N, lpb, lse, A, N, ws.sil, ws.silScore);
       spb = s.spb; spnb = s.spnb;
       if (s.merge) {
         float v = s.a;
@@ -207,7 +208,7 @@ __device__ __forceinline__ void beam_lm_finish_body(int b, int n, BeamWalk g, in
   const int len = beam_write_labels(tab, live, ws.finNode + b * kBeamMax + r, Lmax, labels + ((size_t)b * M + m) * Lmax, g);
   lengths[(size_t)b * M + m] = live ? len : -1;
   scores[(size_t)b * M + m] = score;
-  lmScores[(size_t)b * M + m] = acc;
+  if (lmScores) lmScores[(size_t)b * M + m] = acc;   // null: the LM-free CTC search, which has no such output
 }
 
 __global__ __launch_bounds__(64) void ctc_beam_lm_finish(int M, int Lmax, int eosWord, CtcBeamWs ws, const void* __restrict__ lm,
@@ -224,11 +225,12 @@ W2L_API size_t w2l_ctc_beam_lm_workspace_size(int B, int T, int N, int beam, int
   return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm);
 }
 
-W2L_API int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+namespace w2l {
+// w2l_ctc_beam_search_lm with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
+static int ctc_beam_search_lm_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                    float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
                                    float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
+                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
   if (!lmScores || !lm) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
@@ -237,7 +239,7 @@ W2L_API int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input, cons
     return rc;
   hipStream_t s = (hipStream_t)stream;
   CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamLm, B, T, N, input, frames, beam, K, normalize, workspace, s)) return rc;
+  if (const int rc = ctc_beam_begin(&ws, kBeamLm, B, T, N, input, frames, beam, K, normalize, workspace, s, false, sil)) return rc;
   ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
     hipLaunchKernelGGL((ctc_beam_lm_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)B), dim3(decltype(th)::value), 0, s,
                        T, N, beam, threshold, input, frames, ws, lm, lmWeight, classScore, BeamTrans{});
@@ -247,4 +249,13 @@ W2L_API int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input, cons
                      lmHasEos ? 1 : 0, labels, lengths, scores, lmScores);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
+}
+}  // namespace w2l
+
+W2L_API int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
+                                   float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
+                                   float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
+                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
+  return w2l::ctc_beam_search_lm_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
+      lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
 }

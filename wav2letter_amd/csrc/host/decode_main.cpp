@@ -1,5 +1,5 @@
 // decode_main.cpp -- `Decode --am=<NNN_model_*.bin> --test=<list> [--datadir=] [--batchsize=] [--sclite=<dir>] [--beamsize=]
-// [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--w2l_beam_xl=] [--k=v ...]`: the
+// [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--w2l_beam_xl=] [--w2l_silscore=] [--silscore=] [--k=v ...]`: the
 // reference's Decode tool for its lexicon-free token decoder (`--uselexicon=false --decodertype=tkn`), without LM (the configuration
 // of recipes/self_training/librispeech/am/decode_*.cfg) or with a token-level n-gram LM (`--lm=<arpa>`, recipes/lexicon_free and the
 // word-piece runs of sota/2019), and for its lexicon decoder with a word LM (recipes/conv_glu/*/decode*.cfg), over the fl::
@@ -23,6 +23,12 @@
 //   --w2l_beam_xl=true (not the reference's; default false): a --beamsize given in the flags and above 1024 runs the xl kernels
 //   (BeamSearchOptions::xl), which keep up to 8192 beam entries -- the recipes' 1500, 2500, 5000 and 8000 as they are written;
 //   larger values are limited to 8192 (said on stderr).  Values up to 1024 and an absent --beamsize route as without the flag.
+//   --w2l_silscore=true (not the reference's; default false): --silscore (older name: --silweight; both given with different
+//   values: refused) takes effect in every search Decode runs (BeamSearchOptions::silToken / silScore, the w2l_*_sil entry points):
+//   the silence token is the class of --wordseparator, and after a frame's tokens have been chosen by the acoustic score alone that
+//   class's frame score is score + silscore wherever the search reads it.  A non-zero score when the separator is no class of its
+//   own (the word-piece recipes) is refused, naming the token.  Without the flag a non-zero --silscore is refused and a non-zero
+//   --silweight stays without effect, which one stderr line says.
 //   --logadd=false (default): a prefix scores the MAX over its alignments, on the raw emissions as in the reference's decoder; the
 //     1-best then equals the greedy transcript (the collapsed per-frame arg-max), the n-best are the next best single alignments.
 //   --logadd=true: the labelling-probability search -- a prefix scores the SUM over its alignments, on log-softmax rows (sums only
@@ -47,7 +53,7 @@
 // Refused, each with a message that names the flag: an unreadable or malformed --lm, --lmtype other than kenlm, --uselexicon=true
 // without --lexicon or --lm, --decodertype=wrd without --uselexicon=true, --decodertype=tkn with it, --smearing=logadd, a finite
 // --unkscore (no unknown-word arc), a lexicon spelling with a token the dictionary lacks (the message names the word), a non-zero
-// --silscore, a non-zero --wordscore without --lm, a --criterion other than ctc or asg, a --criterion on the command line that is not
+// --silscore without --w2l_silscore=true, a non-zero --wordscore without --lm, a --criterion other than ctc or asg, a --criterion on the command line that is not
 // the checkpoint's (the criterion's parameters come from the checkpoint).  (--uselexicon and --decodertype default to false / tkn
 // here, so an invocation without them is the lexicon-free search.)
 #include <chrono>
@@ -69,10 +75,11 @@ namespace {
 int usage(const char* exe) {
   std::cerr << "Usage: \n " << exe
             << " --am=<model> --test=<list> [--datadir=...] [--batchsize=...] [--sclite=<dir>] [--beamsize=2500] [--beamsizetoken=250000]"
-               " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [--w2l_beam_xl=false] [flags]\n"
+               " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [--w2l_beam_xl=false] [--w2l_silscore=false --silscore=0] [flags]\n"
                " [--lm=<arpa> --lmtype=kenlm --lmweight=0 --eosscore=0 --wordscore=0]\n"
                " [--uselexicon=true --decodertype=wrd --lexicon=<file> --lm=<word arpa> --smearing=none|max]\n"
                " CTC or ASG (as the checkpoint says) token beam search, optionally with a token-level n-gram LM (ARPA text); --beamsize is limited to 1024 when given (above 64: the wide kernels), to 64 when absent; with --w2l_beam_xl=true a given --beamsize above 1024 runs the xl kernels and is limited to 8192; tokens per frame are limited to 64.\n"
+               " --w2l_silscore=true: --silscore (older name --silweight) is added to the frame score of the --wordseparator class after the frame's tokens are chosen; without it a non-zero --silscore is refused.\n"
                " --logadd=false (default): max over a prefix's alignments on the raw emissions -- the 1-best equals the greedy transcript.\n"
                " --logadd=true: the labelling-probability search (sum over a prefix's alignments, on log-softmax rows)."
             << std::endl;
@@ -144,7 +151,21 @@ int main(int argc, char** argv) {
     } else if (decoderType == "wrd") {
       throw std::invalid_argument("--decodertype=wrd needs --uselexicon=true --lexicon=<file> --lm=<word arpa>");
     }
-    if (flags.getd("silscore", 0.0) != 0.0) throw std::invalid_argument("--silscore: no silence score in this build (leave it 0)");
+    // the silence score: opt-in (--w2l_silscore=true); --silweight is --silscore's older name
+    const bool silFlag = flags.getb("w2l_silscore", false);
+    double silScore = flags.getd("silscore", 0.0);
+    const double silWeight = flags.getd("silweight", 0.0);
+    if (!silFlag) {
+      if (silScore != 0.0)
+        throw std::invalid_argument("--silscore: no silence score without --w2l_silscore=true (leave it 0, or add --w2l_silscore=true)");
+      if (silWeight != 0.0)
+        std::cerr << "[Decode] --silweight=" << silWeight << " has no effect without --w2l_silscore=true" << std::endl;
+    } else {
+      if (flags.has("silscore") && flags.has("silweight") && silScore != silWeight)
+        throw std::invalid_argument("--silscore and --silweight (its older name) are both given with different values");
+      if (!flags.has("silscore")) silScore = silWeight;
+      if (!std::isfinite(silScore)) throw std::invalid_argument("--silscore must be finite");
+    }
     const double wordScore = flags.getd("wordscore", 0.0), lmWeight = flags.getd("lmweight", 0.0), eosScore = flags.getd("eosscore", 0.0);
     if (lmPath.empty() && wordScore != 0.0) throw std::invalid_argument("--wordscore: no word score without --lm (leave it 0)");
     if (!std::isfinite(wordScore) || !std::isfinite(lmWeight) || !std::isfinite(eosScore))
@@ -214,6 +235,13 @@ int main(int argc, char** argv) {
     const bool wp = flags.getb("usewordpiece", false);
     const std::string surround = flags.get("surround", "");
     const std::string dump = flags.get("w2l_dump_features", "");
+    int silToken = -1;
+    if (silFlag && silScore != 0.0) {
+      if (d.wordsep.empty() || !d.dict.contains(d.wordsep) || d.dict.getIndex(d.wordsep) >= numTokens)
+        throw std::invalid_argument("--silscore: the word separator `" + d.wordsep + "` is no class of its own in the token dictionary, so there is no silence token to score (leave it 0)");
+      silToken = d.dict.getIndex(d.wordsep);
+      std::cerr << "[Decode] --silscore=" << silScore << " on the silence token `" << d.wordsep << "` (class " << silToken << ")" << std::endl;
+    }
 
     // ---- the language model over the token classes, and the word score as class scores
     std::unique_ptr<NGramLM> lm;
@@ -304,6 +332,8 @@ int main(int argc, char** argv) {
       // the reference's decoder consumes the raw emissions; CTC sums need log-probabilities, ASG scores are unnormalised by design
       opt.normalize = logAdd && !asg ? 1 : 0;
       opt.nbest = M;
+      opt.silToken = silToken;
+      opt.silScore = silToken >= 0 ? (float)silScore : 0.f;
       if (lm) {
         opt.lm = lm.get();
         opt.lmWeight = (float)lmWeight;

@@ -1484,6 +1484,7 @@ StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int n
 }
 void StreamingDecoder::create(bool wideKernels) {
   const BeamSearchOptions& o = o_;
+  if (o.silScore != 0.f) throw std::invalid_argument("StreamingDecoder: beam sessions have no silence score (silScore must be 0)");
   const int slots = slots_, maxChunk = maxChunk_, maxFrames = maxFrames_, numLabels = nLabel_;
   if (o.nbest < 1 || o.maxLen < 0 || o.maxWords < 0) throw std::invalid_argument("StreamingDecoder: bad nbest, maxLen or maxWords");
   w2l_beam_session_desc d{};
@@ -1617,6 +1618,11 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
   if (input.type() != af::f32 || B <= 0 || T <= 0 || N < 2 || o.nbest < 1 || o.beamSize < 1 || o.beamSizeToken < 1)
     throw std::invalid_argument("beamSearch: bad input or options");
   const int tokens = trans ? N : N - 1;
+  // the silence score: the *_sil entry points, which take the kernel family as an argument
+  const int family = o.xl ? 2 : o.wide ? 1 : 0;
+  const int silToken = o.silToken >= 0 || !o.lexicon ? o.silToken : o.lexicon->silToken();
+  const bool useSil = o.silScore != 0.f;
+  if (useSil && silToken < 0) throw std::invalid_argument("beamSearch: silScore needs a silence token (silToken, or a lexicon that has one)");
   BeamSearchResult r;
   r.labels = af::array(af::dim4(Lmax, o.nbest, B), af::s32);
   r.lengths = af::array(af::dim4(o.nbest, B), af::s32);
@@ -1634,6 +1640,26 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
     r.lmScores = af::array(af::dim4(o.nbest, B));
     r.words = af::array(af::dim4(maxWords, o.nbest, B), af::s32);
     r.wordCounts = af::array(af::dim4(o.nbest, B), af::s32);
+    if (useSil) {
+      auto wss = devAlloc((trans ? w2l_asg_beam_lex_sil_workspace_size : w2l_ctc_beam_lex_sil_workspace_size)(family, B, T, N, o.beamSize,
+                                                                                                          o.beamSizeToken) + 256);
+      if (trans)
+        w2l::w2lCheck(w2l_asg_beam_search_lex_sil(family, B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
+                                                  o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                                  o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
+                                                  r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
+                                                  r.words.device<int>(), r.wordCounts.device<int>(), wss.get(), S(), silToken, o.silScore),
+                      "asg beam search with lexicon and silence score");
+      else
+        w2l::w2lCheck(w2l_ctc_beam_search_lex_sil(family, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
+                                                  o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                                  o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
+                                                  r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
+                                                  r.words.device<int>(), r.wordCounts.device<int>(), wss.get(), S(), silToken, o.silScore),
+                      "ctc beam search with lexicon and silence score");
+      af::sync();  // wss is released at return
+      return r;
+    }
     auto wsx = devAlloc((trans ? (o.xl ? w2l_asg_beam_lex_xl_workspace_size : o.wide ? w2l_asg_beam_lex_wide_workspace_size : w2l_asg_beam_lex_workspace_size)
                                : (o.xl ? w2l_ctc_beam_lex_xl_workspace_size : o.wide ? w2l_ctc_beam_lex_wide_workspace_size : w2l_ctc_beam_lex_workspace_size))(
                             B, T, N, o.beamSize, o.beamSizeToken) + 256);
@@ -1660,6 +1686,16 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
       throw std::invalid_argument("beamSearch: lmWeight, classScore and eosScore need lm");
     if (trans) {   // the lexicon-free ASG search is one entry point: a null LM means none
       af::array lms(af::dim4(o.nbest, B));
+      if (useSil) {
+        auto wss = devAlloc(w2l_asg_beam_sil_workspace_size(family, B, T, N, o.beamSize, o.beamSizeToken) + 256);
+        w2l::w2lCheck(w2l_asg_beam_search_sil(family, B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
+                                              o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, nullptr, 0, 0.f, nullptr, 0.f,
+                                              r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
+                                              lms.device<float>(), wss.get(), S(), silToken, o.silScore),
+                      "asg beam search with silence score");
+        af::sync();  // wss is released at return
+        return r;
+      }
       auto wsa = devAlloc((o.xl ? w2l_asg_beam_xl_workspace_size : o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
       w2l::w2lCheck((o.xl ? w2l_asg_beam_search_xl : o.wide ? w2l_asg_beam_search_wide : w2l_asg_beam_search)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
                                         o.logAdd, normalize, o.nbest, Lmax, nullptr, 0, 0.f, nullptr, 0.f, r.labels.device<int>(),
@@ -1675,6 +1711,26 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
     if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != tokens))
       throw std::invalid_argument("beamSearch: classScore must be f32 with one entry per token class");
     r.lmScores = af::array(af::dim4(o.nbest, B));
+    if (useSil) {
+      auto wss = devAlloc((trans ? w2l_asg_beam_sil_workspace_size : w2l_ctc_beam_lm_sil_workspace_size)(family, B, T, N, o.beamSize,
+                                                                                                     o.beamSizeToken) + 256);
+      const float* cs = o.classScore.isempty() ? nullptr : o.classScore.device<float>();
+      if (trans)
+        w2l::w2lCheck(w2l_asg_beam_search_sil(family, B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
+                                              o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                              o.lmWeight, cs, o.eosScore, r.labels.device<int>(), r.lengths.device<int>(),
+                                              r.scores.device<float>(), r.lmScores.device<float>(), wss.get(), S(), silToken, o.silScore),
+                      "asg beam search with LM and silence score");
+      else
+        w2l::w2lCheck(w2l_ctc_beam_search_lm_sil(family, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
+                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                                 o.lmWeight, cs, o.eosScore, r.labels.device<int>(), r.lengths.device<int>(),
+                                                 r.scores.device<float>(), r.lmScores.device<float>(), wss.get(), S(), silToken,
+                                                 o.silScore),
+                      "ctc beam search with LM and silence score");
+      af::sync();  // wss is released at return
+      return r;
+    }
     auto wsl = devAlloc((trans ? (o.xl ? w2l_asg_beam_xl_workspace_size : o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)
                                : (o.xl ? w2l_ctc_beam_lm_xl_workspace_size : o.wide ? w2l_ctc_beam_lm_wide_workspace_size : w2l_ctc_beam_lm_workspace_size))(
                             B, T, N, o.beamSize, o.beamSizeToken) + 256);
@@ -1693,6 +1749,15 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
                                            r.lmScores.device<float>(), wsl.get(), S()),
                     "ctc beam search with LM");
     af::sync();  // wsl is released at return
+    return r;
+  }
+  if (useSil) {   // the LM-free CTC search with a silence score
+    auto wss = devAlloc(w2l_ctc_beam_sil_workspace_size(family, B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    w2l::w2lCheck(w2l_ctc_beam_search_sil(family, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold,
+                                          o.logAdd, normalize, o.nbest, Lmax, r.labels.device<int>(), r.lengths.device<int>(),
+                                          r.scores.device<float>(), wss.get(), S(), silToken, o.silScore),
+                  "ctc beam search with silence score");
+    af::sync();  // wss is released at return
     return r;
   }
   if (o.wide || o.xl) {   // the LM-free CTC search's wide and xl twins
