@@ -707,6 +707,10 @@ struct BeamSearchOptions {
   // the same bytes.  The streaming decoders below have no silence score: a non-zero silScore there is std::invalid_argument.
   int silToken = -1;
   float silScore = 0.f;
+  // with lexicon: lm is a model over the lexicon's TOKENS, not its words (the w2l_*_beam_search_lextok entry points; the reference's
+  // --uselexicon=true --decodertype=tkn): every token that moves along a trie edge adds lmWeight * log p_LM(token | tokens before),
+  // a completed word adds wordScore alone.  Without lexicon, or with xl: std::invalid_argument; the streaming decoders refuse it too.
+  bool lmToken = false;
 };
 struct BeamSearchResult {
   af::array labels;    // (Lmax, M, B) s32: the first min(length, Lmax) labels, -1 beyond

@@ -521,6 +521,50 @@ int w2l_asg_beam_search_lex_sil(int family, int B, int T, int N, const float* in
                                 int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
                                 float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
                                 int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
+/* The lexicon searches with a TOKEN-LEVEL LM (the reference's --uselexicon=true --decodertype=tkn; csrc/criterion_beam_lextok.hpp,
+ * DESIGN 3.27): the lexicon constrains the spellings, the LM scores the tokens.  The argument lists are those of
+ * w2l_ctc_beam_search_lex_sil and w2l_asg_beam_search_lex_sil, and the contract is w2l_ctc_beam_search_lex's (ASG:
+ * w2l_asg_beam_search_lex's) with these changes.
+ * `lm` is a w2l_ngram_lm_* blob over the lexicon's numTokens TOKENS, not over its words; EOS is word numTokens + 1.
+ * State: unchanged -- e, pb, pnb, lexicon node u, LM state s, word list, the unweighted LM sum acc.  The trie's smear values are
+ * never read: a smeared and an unsmeared blob give the same bytes.
+ * Extensions of entry r by frame token c, base = (c == e ? pb : tot):
+ *   sil, slot 0     c == silToken (the lexicon's) and u the root: as in the sibling.  pnb' = lp[c] + base, the state stays s, no LM
+ *                   term, acc unchanged.
+ *   otherwise       v = child(u, c); without a child there are no candidates.  a = (lp[c] + base) + (lmWeight * q(s, c)): one fp32
+ *                   multiply, then one add to the acoustic sum.  s' is q's successor, acc' = acc + q.  A trie edge on the silence
+ *                   token inside a spelling is a token like any other and is LM-scored.
+ *   in, slot 0      v has children: pnb' = a; the new entry is at v with state s'.
+ *   word i, 1 + i   pnb' = a + wordScore, one add; the new entry is at the root with state s', w is appended.  Homophones tie and
+ *                   are ordered by slot.
+ * One LM lookup per (entry, token) pair.  ASG: (lp[c] + base) is the policy's a, (tot + A[c][e]) + lp[c], and c == e has no
+ * candidates in any slot.  Merge, prune, order (total, r, stay first, k, slot), end (root only; the EOS term lmWeight * q(s, EOS) +
+ * eosScore from the token LM; re-rank), outputs and lmScores keep the sibling's rules.  The silence score: the rule of the *_sil
+ * entry points above; silScore == 0 or silToken == -1 means none, and no + 0 is executed.
+ * Consequences.  With a lexicon that holds every token as a one-token word, no silence token, wordScore = 0: labels, lengths,
+ * scores and lmScores are w2l_ctc_beam_search_lm's (w2l_asg_beam_search's) with classScore = NULL, bit for bit.  With
+ * lmWeight = 0 and lmHasEos = 0: everything but lmScores is w2l_*_beam_search_lex's on an unsmeared lexicon, bit for bit.
+ * Not part of the contract: an unknown-word arc, log-add smearing, LM orders above the blob format's 8.
+ * family: 0 narrow (W <= 64), 1 wide (W <= 1024); the two agree bit for bit at W <= 64.  family 2 (xl) is W2L_EUNSUPPORTED and its
+ * workspace size is 0.  Refusals, all before anything touches the device: W2L_EINVAL for family outside 0..2, silScore not finite,
+ * silToken out of range (as above); W2L_EUNSUPPORTED for family 2; then the chosen family's lexicon search's, in its order.  The
+ * workspace is the lexicon search's of that family. */
+size_t w2l_ctc_beam_lextok_workspace_size(int family, int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lextok(int family, int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                               int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                               int nbest /*M*/, int maxLen /*Lmax*/, const void* lm /*over tokens*/, int lmHasEos, float lmWeight,
+                               const void* lexicon, float wordScore, float eosScore,
+                               int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                               float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                               int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
+size_t w2l_asg_beam_lextok_workspace_size(int family, int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_lextok(int family, int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                               const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/,
+                               float threshold, int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/,
+                               const void* lm /*over tokens*/, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
+                               float eosScore, int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                               float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                               int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
 
 /* ------------------------------------------------------------------------
  * 2. Network operators (fp32).  Activations are FRAME-MAJOR: a tensor the

@@ -167,6 +167,11 @@ class _SIGS:
     w2l_ctc_beam_search_lex_sil = (_i, [_i] + w2l_ctc_beam_search_lex[1] + [_i, _f])
     w2l_asg_beam_search_sil = (_i, [_i] + w2l_asg_beam_search[1] + [_i, _f])
     w2l_asg_beam_search_lex_sil = (_i, [_i] + w2l_asg_beam_search_lex[1] + [_i, _f])
+    # the lexicon searches with a token LM: the *_lex_sil argument lists
+    w2l_ctc_beam_lextok_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])
+    w2l_asg_beam_lextok_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])
+    w2l_ctc_beam_search_lextok = (_i, [_i] + w2l_ctc_beam_search_lex[1] + [_i, _f])
+    w2l_asg_beam_search_lextok = (_i, [_i] + w2l_asg_beam_search_lex[1] + [_i, _f])
     w2l_host_last_error = (C.c_char_p, [])
     w2l_gemm_f32 = (_i, [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _p])
     w2l_linear_forward = (_i, [_i, _i, _i, _p, _p, _p, _p, _i, _p])

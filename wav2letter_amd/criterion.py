@@ -332,6 +332,21 @@ def _beam_fn(L, name, wide, sil):
     return lambda *a: g(family, *a, sil[0], sil[1])
 
 
+def _lextok_fn(L, name, wide, sil):
+    """the token-LM-under-a-lexicon entry point for `name` (w2l_x_beam_search_lex or w2l_x_beam_lex_workspace_size): the family in
+    front, and behind the search's arguments the silence token and score (-1, 0: none)"""
+    _wide(L, name, wide)   # checks `wide`
+    if wide == "xl":
+        raise _lib.W2LInvalidArgument('beam search: lm_token=True has no xl family (wide must be False or True)')
+    family = 1 if wide else 0
+    if name.endswith("_workspace_size"):
+        g = getattr(L, name.replace("_beam_lex_workspace_size", "_beam_lextok_workspace_size"))
+        return lambda *a: g(family, *a)
+    g = getattr(L, name + "tok")
+    tok, score = sil if sil is not None else (-1, 0.0)
+    return lambda *a: g(family, *a, tok, score)
+
+
 def _sil_args(who, sil_token, sil_score, lexicon):
     """(token, score) for the *_sil entry points, or None: the call without a silence score.  sil_token None: the lexicon's"""
     sil_score = float(sil_score)
@@ -348,7 +363,7 @@ def _sil_args(who, sil_token, sil_score, lexicon):
 
 def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=None,
                     nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
-                    max_words=None, wide=False, sil_token=None, sil_score=0.0):
+                    max_words=None, wide=False, sil_token=None, sil_score=0.0, lm_token=False):
     """CTC prefix beam search without lexicon or LM (w2l_ctc_beam_search; the contract is in include/w2l_hip.h): `emission`
     [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64; <= 1024 with wide=True; <= 8192 with wide="xl"), beam_token = K (clipped to N-1, then <= 64),
     log_add: sum (True) or max (False) over the alignments of a prefix; normalize: search on log-softmax rows (default: log_add --
@@ -371,16 +386,25 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     sil_token, sil_score: the silence score (the w2l_*_sil entry points; the reference's --silscore): after the frame tokens have
     been chosen by the acoustic lp alone, class sil_token's frame score is lp + sil_score wherever the search reads it.
     sil_token=None with a lexicon: the lexicon's silence token.  A non-zero sil_score without any silence token is refused;
-    sil_score = 0 is the search without a silence score, the same bytes."""
+    sil_score = 0 is the search without a silence score, the same bytes.
+    lm_token=True (needs lexicon; w2l_ctc_beam_search_lextok, the reference's --uselexicon=true --decodertype=tkn): lm is an NGramLM
+    over the lexicon's TOKENS, not its words.  Every token that moves along a trie edge adds lm_weight * log p_LM(token | tokens
+    before), a completed word adds word_score alone, the lexicon's smear values are not read.  The return values are the lexicon
+    search's.  wide=True for beams up to 1024; wide="xl" is refused."""
     _emission_checks(emission)
     B, T, N = emission.shape
     sil = _sil_args("ctc_beam_search", sil_token, sil_score, lexicon)
+    if lm_token and lexicon is None:
+        raise ValueError("ctc_beam_search: lm_token=True needs lexicon (without one, lm alone is the token-LM search)")
+    if lm_token and lm is not None and lm.num_tokens != lexicon.num_tokens:
+        raise ValueError(f"ctc_beam_search: lm_token=True: the LM has {lm.num_tokens} tokens, the lexicon {lexicon.num_tokens}")
+    lex_fn = _lextok_fn if lm_token else _beam_fn
     if lexicon is not None:
         if lm is None:
             raise _lib.W2LInvalidArgument("ctc_beam_search: lexicon needs lm, a model over the lexicon's words")
         if class_score is not None:
             raise _lib.W2LInvalidArgument("ctc_beam_search: class_score must be None with a lexicon (word_score is the per-word term)")
-        if lm.num_tokens != lexicon.num_words:
+        if not lm_token and lm.num_tokens != lexicon.num_words:
             raise _lib.W2LInvalidArgument(f"ctc_beam_search: the LM has {lm.num_tokens} words, the lexicon {lexicon.num_words}")
         if lexicon.num_tokens != N - 1:
             raise _lib.W2LInvalidArgument(f"ctc_beam_search: the lexicon has {lexicon.num_tokens} tokens, the emissions {N - 1}")
@@ -418,12 +442,12 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
     if lexicon is not None:
         max_words = max(max_len, 1) if max_words is None else int(max_words)
-        ws = _ws(_beam_fn(L, "w2l_ctc_beam_lex_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), emission.device)
+        ws = _ws(lex_fn(L, "w2l_ctc_beam_lex_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), emission.device)
         lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
         words = torch.empty(*shape, max_words, dtype=torch.int32, device=emission.device)
         word_counts = torch.empty(*shape, dtype=torch.int32, device=emission.device)
         blob, lex_blob = lm.device_blob(emission.device), lexicon.device_blob(emission.device)
-        _lib.check(_beam_fn(L, "w2l_ctc_beam_search_lex", wide, sil)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
+        _lib.check(lex_fn(L, "w2l_ctc_beam_search_lex", wide, sil)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
                                              int(beam), int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)),
                                              nbest, max_len, blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
                                              float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),
@@ -454,16 +478,21 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
 
 def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=False,
                     nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
-                    max_words=None, wide=False, sil_token=None, sil_score=0.0):
+                    max_words=None, wide=False, sil_token=None, sil_score=0.0, lm_token=False):
     """Beam search of an ASG model (w2l_asg_beam_search, w2l_asg_beam_search_lex; the contract is in include/w2l_hip.h):
     `emission` [B][T][N], every class a token (no blank), `transitions` [N][N] float32 (to x from) on the emissions' device.  The
     options and the return values are ctc_beam_search's -- (labels, lengths, scores), lm_scores with an LM, words and word_counts
     with a lexicon -- with beam_token clipped to N, an LM (or lexicon) over N tokens and class_score [N].  normalize defaults to
     False in both log_add modes: ASG scores are unnormalised by design.  A token never follows itself: a repeated letter is a
-    replabel's (Lexicon.from_file(..., replabel=) packs the spellings).  wide, sil_token, sil_score: as in ctc_beam_search."""
+    replabel's (Lexicon.from_file(..., replabel=) packs the spellings).  wide, sil_token, sil_score, lm_token: as in ctc_beam_search."""
     _emission_checks(emission)
     B, T, N = emission.shape
     sil = _sil_args("asg_beam_search", sil_token, sil_score, lexicon)
+    if lm_token and lexicon is None:
+        raise ValueError("asg_beam_search: lm_token=True needs lexicon (without one, lm alone is the token-LM search)")
+    if lm_token and lm is not None and lm.num_tokens != lexicon.num_tokens:
+        raise ValueError(f"asg_beam_search: lm_token=True: the LM has {lm.num_tokens} tokens, the lexicon {lexicon.num_tokens}")
+    lex_fn = _lextok_fn if lm_token else _beam_fn
     if transitions.dtype != torch.float32 or tuple(transitions.shape) != (N, N):
         raise _lib.W2LInvalidArgument(f"asg_beam_search: transitions must be float32 [{N}][{N}]")
     if lexicon is not None:
@@ -471,7 +500,7 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
             raise _lib.W2LInvalidArgument("asg_beam_search: lexicon needs lm, a model over the lexicon's words")
         if class_score is not None:
             raise _lib.W2LInvalidArgument("asg_beam_search: class_score must be None with a lexicon (word_score is the per-word term)")
-        if lm.num_tokens != lexicon.num_words:
+        if not lm_token and lm.num_tokens != lexicon.num_words:
             raise _lib.W2LInvalidArgument(f"asg_beam_search: the LM has {lm.num_tokens} words, the lexicon {lexicon.num_words}")
         if lexicon.num_tokens != N:
             raise _lib.W2LInvalidArgument(f"asg_beam_search: the lexicon has {lexicon.num_tokens} tokens, the emissions {N}")
@@ -509,11 +538,11 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
     lm_scores = torch.empty(*shape, dtype=torch.float32, device=dev)
     if lexicon is not None:
         max_words = max(max_len, 1) if max_words is None else int(max_words)
-        ws = _ws(_beam_fn(L, "w2l_asg_beam_lex_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), dev)
+        ws = _ws(lex_fn(L, "w2l_asg_beam_lex_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), dev)
         words = torch.empty(*shape, max_words, dtype=torch.int32, device=dev)
         word_counts = torch.empty(*shape, dtype=torch.int32, device=dev)
         blob, lex_blob = lm.device_blob(dev), lexicon.device_blob(dev)
-        _lib.check(_beam_fn(L, "w2l_asg_beam_search_lex", wide, sil)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
+        _lib.check(lex_fn(L, "w2l_asg_beam_search_lex", wide, sil)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
                                              float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
                                              blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
                                              float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),

@@ -128,7 +128,9 @@ struct BeamWideCarry {
 // beam from the session's state unless the slot starts, and every field goes back there after the frames.  What indexes memory is
 // held to its range where it is loaded (n to W, node ids to the table, the last token to the row); LM states and lexicon nodes
 // are clamped where they are used (ngram_q, lex_child, lex_node).  beam_wide_scan below is the body with kResume off.
-template <bool kLogAdd, class Pol, bool kLex, bool kResume>
+// kTok (with kLex; criterion_beam_lextok.hpp): `lm` is a token LM under the lexicon: a token that moves along a trie edge adds
+// lmWeight * q(s, c) and advances the LM state, a completed word adds wordScore alone, the smear values are not read.
+template <bool kLogAdd, class Pol, bool kLex, bool kResume, bool kTok = false>
 __device__ __forceinline__ void beam_wide_scan_body(int T, int N, int W, float threshold, const float* __restrict__ x,
                                                     const int* __restrict__ frames, const BeamWideWs& ww,
                                                     const void* __restrict__ lex, const void* __restrict__ lm, float lmWeight,
@@ -252,7 +254,13 @@ __device__ __forceinline__ void beam_wide_scan_body(int T, int N, int W, float t
           const int lab = cLab[tid];
           if (lab >= 0) {
             const int vj = lab >> 3, slot = lab & 7;
-            if (vj != 0) {
+            if constexpr (kTok) {
+              if (vj != 0) {
+                int unused;
+                v = beam_lextok_a(v, lmWeight, ngram_q(lv, cSt[pr], e, &unused));
+                if (slot > 0) v = v + wordScore;
+              }
+            } else if (vj != 0) {
               const LexNode& nd = lex_node(xv, vj);
               const float smv = nd.smear;
               const int up = beam_wide_u(cLab[pr]);
@@ -300,6 +308,17 @@ __device__ __forceinline__ void beam_wide_scan_body(int T, int N, int W, float t
         const int u = beam_wide_u(cLab[r]);
         if (c == xv.silToken && u == 0) {
           if (!((sGone[r] >> k) & 1ull)) put(beam_key(a0, r, 1, k, 0));
+        } else if constexpr (kTok) {   // one LM lookup per pair that has an edge: this scan is bound by its lookups, not their latency
+          const int v = lex_child(xv, u, c);
+          if (v > 0) {
+            const LexNode& nd = lex_node(xv, v);
+            int unused;
+            const float a = beam_lextok_a(a0, lmWeight, ngram_q(lv, cSt[r], c, &unused));
+            if (lex_has_children(nd) && !((sGone[r] >> k) & 1ull)) put(beam_key(a, r, 1, k, 0));
+            const int nw = lex_nw(nd);
+            for (int i = 0; i < nw; ++i)
+              if (!((sGone[(1 + i) * kTh + r] >> k) & 1ull)) put(beam_key(a + wordScore, r, 1, k, 1 + i));
+          }
         } else {
           const int v = lex_child(xv, u, c);
           if (v > 0) {
@@ -395,7 +414,12 @@ __device__ __forceinline__ void beam_wide_scan_body(int T, int N, int W, float t
           const int u = beam_wide_u(cLab[r]);
           const int v = (c == xv.silToken && u == 0) ? 0 : max(lex_child(xv, u, c), 0);
           label = (v << 3) | slot;
-          if (slot > 0) {
+          if constexpr (kTok) {
+            if (v != 0) {
+              const float q = ngram_q(lv, cSt[r], c, &st);
+              acc = acc + q;
+            }
+          } else if (slot > 0) {
             const float q = ngram_q(lv, cSt[r], lex_node(xv, v).words[min(slot - 1, kLexMaxWords - 1)], &st);
             acc = acc + q;
           }
@@ -433,14 +457,14 @@ __device__ __forceinline__ void beam_wide_scan_body(int T, int N, int W, float t
   }
 }
 
-template <bool kLogAdd, class Pol, bool kLex>
+template <bool kLogAdd, class Pol, bool kLex, bool kTok = false>
 __global__ __launch_bounds__(kWideThreads) void beam_wide_scan(int T, int N, int W, float threshold,
                                                                const float* __restrict__ x, const int* __restrict__ frames,
                                                                BeamWideWs ww, const void* __restrict__ lex,
                                                                const void* __restrict__ lm, float lmWeight,
                                                                const float* __restrict__ classScore, float wordScore, BeamTrans tr) {
-  beam_wide_scan_body<kLogAdd, Pol, kLex, false>(T, N, W, threshold, x, frames, ww, lex, lm, lmWeight, classScore, wordScore, tr,
-                                                 BeamWideCarry{});
+  beam_wide_scan_body<kLogAdd, Pol, kLex, false, kTok>(T, N, W, threshold, x, frames, ww, lex, lm, lmWeight, classScore, wordScore,
+                                                       tr, BeamWideCarry{});
 }
 
 // eosWord: the LM's index of the end of a sentence (the token searches'; the lexicon search takes it from the LM's header);
@@ -541,27 +565,28 @@ static int beam_wide_check(int B, int T, int N, const float* input, int beam, in
   return W2L_OK;
 }
 
-template <bool kLogAdd, class Pol, bool kLex>
+template <bool kLogAdd, class Pol, bool kLex, bool kTok = false>
 static int beam_wide_launch(int B, int T, int N, float threshold, const float* input, const int* frames, const BeamWideWs& ww,
                             const void* lex, const void* lm, float lmWeight, const float* classScore, float wordScore,
                             const BeamTrans& tr, size_t transBytes, hipStream_t s) {
   const size_t shmem = align_up(transBytes, 16) + WideLds<kLex>::bytes;
   static bool attr[64] = {};
   if (first_on_device(attr))
-    W2L_HIP_CHECK(hipFuncSetAttribute((const void*)beam_wide_scan<kLogAdd, Pol, kLex>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    W2L_HIP_CHECK(hipFuncSetAttribute((const void*)beam_wide_scan<kLogAdd, Pol, kLex, kTok>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)(align_up(kWideTransLds, 16) + WideLds<kLex>::bytes)));
-  hipLaunchKernelGGL((beam_wide_scan<kLogAdd, Pol, kLex>), dim3((unsigned)B), dim3(kWideThreads), shmem, s, T, N, ww.W, threshold,
+  hipLaunchKernelGGL((beam_wide_scan<kLogAdd, Pol, kLex, kTok>), dim3((unsigned)B), dim3(kWideThreads), shmem, s, T, N, ww.W, threshold,
                      input, frames, ww, lex, lm, lmWeight, classScore, wordScore, tr);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }
 
-// One wide search after its checks: rows, scan, finish.  trans null: CTC; lex null: the token search
+// One wide search after its checks: rows, scan, finish.  trans null: CTC; lex null: the token search; tok (with lex): lm is a
+// token LM under the lexicon (criterion_beam_lextok.hpp)
 static int beam_wide_run(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam, int K,
                          float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
                          float lmWeight, const float* classScore, const void* lex, float wordScore, float eosScore, int* labels,
                          int* lengths, float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                         hipStream_t s, BeamSil sil) {
+                         hipStream_t s, BeamSil sil, bool tok = false) {
   const bool asg = trans != nullptr, isLex = lex != nullptr;
   BeamWideWs ww{};
   beam_wide_layout(&ww, workspace, B, T, beam, K, isLex ? kBeamLex : kBeamLm);
@@ -584,7 +609,13 @@ static int beam_wide_run(int B, int T, int N, const float* input, const int* fra
   int rc = W2L_OK;
 #define W2L_WIDE_SCAN(LA, POL, LEX) \
   rc = beam_wide_launch<LA, POL, LEX>(B, T, N, threshold, input, frames, ww, lex, lm, lmWeight, classScore, wordScore, tr, transBytes, s)
-  if (isLex) {
+#define W2L_WIDE_TOK(LA, POL) \
+  rc = beam_wide_launch<LA, POL, true, true>(B, T, N, threshold, input, frames, ww, lex, lm, lmWeight, nullptr, wordScore, tr, \
+                                             transBytes, s)
+  if (isLex && tok) {
+    if (asg) { if (logAdd) W2L_WIDE_TOK(true, BeamAsg); else W2L_WIDE_TOK(false, BeamAsg); }
+    else { if (logAdd) W2L_WIDE_TOK(true, BeamCtc); else W2L_WIDE_TOK(false, BeamCtc); }
+  } else if (isLex) {
     if (asg) { if (logAdd) W2L_WIDE_SCAN(true, BeamAsg, true); else W2L_WIDE_SCAN(false, BeamAsg, true); }
     else { if (logAdd) W2L_WIDE_SCAN(true, BeamCtc, true); else W2L_WIDE_SCAN(false, BeamCtc, true); }
   } else {
@@ -592,6 +623,7 @@ static int beam_wide_run(int B, int T, int N, const float* input, const int* fra
     else { if (logAdd) W2L_WIDE_SCAN(true, BeamCtc, false); else W2L_WIDE_SCAN(false, BeamCtc, false); }
   }
 #undef W2L_WIDE_SCAN
+#undef W2L_WIDE_TOK
   if (rc) return rc;
   const int useEos = lm && lmHasEos ? 1 : 0;
   if (isLex)

@@ -35,6 +35,10 @@ __device__ __forceinline__ float beam_lex_word(float a, float lmWeight, float q,
   return a + ((lmWeight * (q - smv)) + wordScore);
 }
 
+// a token LM under the lexicon (criterion_beam_lextok.hpp, the wide scan's kTok): a = a0 + (lmWeight * q), q the token's
+// log-probability; a completed word: a + wordScore
+__device__ __forceinline__ float beam_lextok_a(float a0, float lmWeight, float q) { return a0 + (lmWeight * q); }
+
 // the best candidate of a pair that is not in its consumed mask (meta = nw | hasChildren << 3 | consumed << 4): 0 when none is left
 __device__ __forceinline__ void beam_lex_best(const NgramView& lv, const LexView& xv, int v, float a, float smv, unsigned meta, int st,
                                               float lmWeight, float wordScore, int r, int k, u64* key, int* nst,

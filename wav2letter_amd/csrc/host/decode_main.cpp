@@ -1,5 +1,5 @@
 // decode_main.cpp -- `Decode --am=<NNN_model_*.bin> --test=<list> [--datadir=] [--batchsize=] [--sclite=<dir>] [--beamsize=]
-// [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--w2l_beam_xl=] [--w2l_silscore=] [--silscore=] [--k=v ...]`: the
+// [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--w2l_beam_xl=] [--w2l_silscore=] [--silscore=] [--w2l_lex_tkn=] [--k=v ...]`: the
 // reference's Decode tool for its lexicon-free token decoder (`--uselexicon=false --decodertype=tkn`), without LM (the configuration
 // of recipes/self_training/librispeech/am/decode_*.cfg) or with a token-level n-gram LM (`--lm=<arpa>`, recipes/lexicon_free and the
 // word-piece runs of sota/2019), and for its lexicon decoder with a word LM (recipes/conv_glu/*/decode*.cfg), over the fl::
@@ -49,9 +49,15 @@
 //     search lets loop between words when the token dictionary has it.  --wordscore is added once per word.  .hyp lines, beam-dump
 //     rows and WER come from the hypotheses' word ids; amScore = score - (lmweight * lmScore + wordscore * words + eosscore).
 //     A sample none of whose hypotheses ends on a word boundary gets an empty hypothesis.
+//   --w2l_lex_tkn=true (not the reference's; default false) --uselexicon=true --decodertype=tkn --lexicon=<file> --lm=<token arpa>:
+//     the search restricted to the spellings of the lexicon and scored by an n-gram LM over the TOKENS (w2l_ctc_beam_search_lextok,
+//     BeamSearchOptions::lmToken; the reference's lexicon_free recipes).  Every token that moves along a trie edge adds lmweight *
+//     its LM score, a completed word adds --wordscore.  --beamsize up to 1024; --w2l_beam_xl=true with the flag is refused.
+//     --smearing=none|max is accepted and has no effect (said on stderr).  Output rows are the wrd decoder's.  Without the flag
+//     --decodertype=tkn with --uselexicon=true is refused as before.
 //   The last line gives the total WER / TER (fl::EditDistanceMeter, the --valid evaluation's).
 // Refused, each with a message that names the flag: an unreadable or malformed --lm, --lmtype other than kenlm, --uselexicon=true
-// without --lexicon or --lm, --decodertype=wrd without --uselexicon=true, --decodertype=tkn with it, --smearing=logadd, a finite
+// without --lexicon or --lm, --decodertype=wrd without --uselexicon=true, --decodertype=tkn with it unless --w2l_lex_tkn=true, --smearing=logadd, a finite
 // --unkscore (no unknown-word arc), a lexicon spelling with a token the dictionary lacks (the message names the word), a non-zero
 // --silscore without --w2l_silscore=true, a non-zero --wordscore without --lm, a --criterion other than ctc or asg, a --criterion on the command line that is not
 // the checkpoint's (the criterion's parameters come from the checkpoint).  (--uselexicon and --decodertype default to false / tkn
@@ -78,6 +84,7 @@ int usage(const char* exe) {
                " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [--w2l_beam_xl=false] [--w2l_silscore=false --silscore=0] [flags]\n"
                " [--lm=<arpa> --lmtype=kenlm --lmweight=0 --eosscore=0 --wordscore=0]\n"
                " [--uselexicon=true --decodertype=wrd --lexicon=<file> --lm=<word arpa> --smearing=none|max]\n"
+               " [--w2l_lex_tkn=true --uselexicon=true --decodertype=tkn --lexicon=<file> --lm=<token arpa>]\n"
                " CTC or ASG (as the checkpoint says) token beam search, optionally with a token-level n-gram LM (ARPA text); --beamsize is limited to 1024 when given (above 64: the wide kernels), to 64 when absent; with --w2l_beam_xl=true a given --beamsize above 1024 runs the xl kernels and is limited to 8192; tokens per frame are limited to 64.\n"
                " --w2l_silscore=true: --silscore (older name --silweight) is added to the frame score of the --wordseparator class after the frame's tokens are chosen; without it a non-zero --silscore is refused.\n"
                " --logadd=false (default): max over a prefix's alignments on the raw emissions -- the 1-best equals the greedy transcript.\n"
@@ -137,17 +144,24 @@ int main(int argc, char** argv) {
     const bool useLexicon = flags.getb("uselexicon", false);
     const std::string decoderType = flags.get("decodertype", "tkn"), lexiconPath = flags.get("lexicon", "");
     const std::string smearing = flags.get("smearing", "none");
+    // the token LM under a lexicon: opt-in (--w2l_lex_tkn=true), taken by --uselexicon=true --decodertype=tkn
+    const bool lexTkn = flags.getb("w2l_lex_tkn", false);
+    const bool tokenLm = lexTkn && useLexicon && decoderType == "tkn";
+    if (lexTkn && flags.getb("w2l_beam_xl", false))
+      throw std::invalid_argument("--w2l_beam_xl=true with --w2l_lex_tkn=true: the token LM under a lexicon has no xl kernels (beams up to 1024)");
     if (decoderType != "tkn" && decoderType != "wrd")
       throw std::invalid_argument("--decodertype=" + decoderType + ": tkn (lexicon-free) or wrd (with --uselexicon=true)");
     if (useLexicon) {
       if (lexiconPath.empty()) throw std::invalid_argument("--uselexicon=true needs --lexicon=<file>");
       if (lmPath.empty()) throw std::invalid_argument("--uselexicon=true needs --lm=<arpa of a model over the lexicon's words>");
-      if (decoderType != "wrd")
+      if (decoderType != "wrd" && !lexTkn)
         throw std::invalid_argument("--decodertype=tkn with --uselexicon=true: no token LM under a lexicon in this build (--decodertype=wrd)");
       if (smearing == "logadd") throw std::invalid_argument("--smearing=logadd: log-add smearing is not built (none or max)");
       if (smearing != "none" && smearing != "max") throw std::invalid_argument("--smearing=" + smearing + ": none or max");
       if (std::isfinite(flags.getd("unkscore", -std::numeric_limits<double>::infinity())))
         throw std::invalid_argument("--unkscore: no unknown-word arc in this build (leave it -inf)");
+      if (tokenLm && flags.has("smearing"))
+        std::cerr << "[Decode] --smearing=" << smearing << " has no effect with --decodertype=tkn: the token LM scores every token" << std::endl;
     } else if (decoderType == "wrd") {
       throw std::invalid_argument("--decodertype=wrd needs --uselexicon=true --lexicon=<file> --lm=<word arpa>");
     }
@@ -258,15 +272,15 @@ int main(int argc, char** argv) {
         throw std::invalid_argument("--lexicon=" + lexiconPath + ": " + e.what());
       }
       try {
-        lm.reset(new NGramLM(NGramLM::fromArpa(lmPath, lexicon->words())));
+        lm.reset(new NGramLM(NGramLM::fromArpa(lmPath, tokenLm ? tokens : lexicon->words())));
       } catch (const std::exception& e) {
         throw std::invalid_argument("--lm=" + lmPath + ": " + e.what());
       }
-      if (smearing == "max") lexicon.reset(new Lexicon(Lexicon::fromFile(lexiconPath, tokens, lm.get(), sil, "max", d.replabel)));
+      if (smearing == "max" && !tokenLm) lexicon.reset(new Lexicon(Lexicon::fromFile(lexiconPath, tokens, lm.get(), sil, "max", d.replabel)));
       if (!lm->hasEos() && eosScore != 0.0) throw std::invalid_argument("--eosscore: the model of --lm has no </s> (leave it 0)");
       std::cerr << "[Decode] --lexicon: " << lexicon->numWords() << " words, " << lexicon->numNodes() << " nodes, " << lexicon->dropped()
                 << " homophones beyond the sixth dropped, smearing " << smearing << ", silence token " << (sil.empty() ? "none" : sil)
-                << "; --lm over the words: order " << lm->order() << ", " << lm->numStates() << " states; " << lm->message() << std::endl;
+                << "; --lm over the " << (tokenLm ? "tokens" : "words") << ": order " << lm->order() << ", " << lm->numStates() << " states; " << lm->message() << std::endl;
     } else if (!lmPath.empty()) {
       std::vector<std::string> tokens;
       for (int c = 0; c < numTokens; ++c) tokens.push_back(d.dict.getEntry(c));
@@ -344,6 +358,7 @@ int main(int argc, char** argv) {
         opt.lexicon = lexicon.get();
         opt.wordScore = (float)wordScore;
         opt.maxWords = Tout;
+        opt.lmToken = tokenLm;
       }
       const af::array framesDev(af::dim4(1, B), frames.data());
       auto res = asg ? asgCrit->beamSearch(out.array(), framesDev, opt) : ctc->beamSearch(out.array(), framesDev, opt);

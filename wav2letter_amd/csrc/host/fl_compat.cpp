@@ -1485,6 +1485,7 @@ StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int n
 void StreamingDecoder::create(bool wideKernels) {
   const BeamSearchOptions& o = o_;
   if (o.silScore != 0.f) throw std::invalid_argument("StreamingDecoder: beam sessions have no silence score (silScore must be 0)");
+  if (o.lmToken) throw std::invalid_argument("StreamingDecoder: beam sessions have no token LM under a lexicon (lmToken must be false)");
   const int slots = slots_, maxChunk = maxChunk_, maxFrames = maxFrames_, numLabels = nLabel_;
   if (o.nbest < 1 || o.maxLen < 0 || o.maxWords < 0) throw std::invalid_argument("StreamingDecoder: bad nbest, maxLen or maxWords");
   w2l_beam_session_desc d{};
@@ -1618,6 +1619,8 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
   if (input.type() != af::f32 || B <= 0 || T <= 0 || N < 2 || o.nbest < 1 || o.beamSize < 1 || o.beamSizeToken < 1)
     throw std::invalid_argument("beamSearch: bad input or options");
   const int tokens = trans ? N : N - 1;
+  if (o.lmToken && !o.lexicon) throw std::invalid_argument("beamSearch: lmToken needs lexicon (without one, lm alone is the token-LM search)");
+  if (o.lmToken && o.xl) throw std::invalid_argument("beamSearch: lmToken has no xl family (narrow, or wide up to 1024)");
   // the silence score: the *_sil entry points, which take the kernel family as an argument
   const int family = o.xl ? 2 : o.wide ? 1 : 0;
   const int silToken = o.silToken >= 0 || !o.lexicon ? o.silToken : o.lexicon->silToken();
@@ -1631,7 +1634,10 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
   if (o.lexicon) {   // the search restricted to the lexicon's spellings, scored by a LM over words (w2l_ctc_beam_search_lex)
     if (!o.lm) throw std::invalid_argument("beamSearch: lexicon needs lm, a model over the lexicon's words");
     if (!o.classScore.isempty()) throw std::invalid_argument("beamSearch: classScore must be empty with a lexicon");
-    if (o.lm->numTokens() != o.lexicon->numWords()) throw std::invalid_argument("beamSearch: the LM's word count is not the lexicon's");
+    if (o.lmToken && o.lm->numTokens() != o.lexicon->numTokens())
+      throw std::invalid_argument("beamSearch: lmToken: the LM's token count is not the lexicon's");
+    if (!o.lmToken && o.lm->numTokens() != o.lexicon->numWords())
+      throw std::invalid_argument("beamSearch: the LM's word count is not the lexicon's");
     if (o.lexicon->numTokens() != tokens)
       throw std::invalid_argument(trans ? "beamSearch: the lexicon's token count is not the emissions' N"
                                         : "beamSearch: the lexicon's token count is not the emissions' N - 1");
@@ -1640,6 +1646,27 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
     r.lmScores = af::array(af::dim4(o.nbest, B));
     r.words = af::array(af::dim4(maxWords, o.nbest, B), af::s32);
     r.wordCounts = af::array(af::dim4(o.nbest, B), af::s32);
+    if (o.lmToken) {   // the LM scores the tokens, the lexicon constrains them (w2l_*_beam_search_lextok); silScore 0: no score
+      auto wst = devAlloc((trans ? w2l_asg_beam_lextok_workspace_size : w2l_ctc_beam_lextok_workspace_size)(family, B, T, N, o.beamSize,
+                                                                                                        o.beamSizeToken) + 256);
+      const int st = useSil ? silToken : -1;
+      if (trans)
+        w2l::w2lCheck(w2l_asg_beam_search_lextok(family, B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
+                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                                 o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
+                                                 r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
+                                                 r.words.device<int>(), r.wordCounts.device<int>(), wst.get(), S(), st, o.silScore),
+                      "asg beam search with lexicon and token LM");
+      else
+        w2l::w2lCheck(w2l_ctc_beam_search_lextok(family, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
+                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                                 o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
+                                                 r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
+                                                 r.words.device<int>(), r.wordCounts.device<int>(), wst.get(), S(), st, o.silScore),
+                      "ctc beam search with lexicon and token LM");
+      af::sync();  // wst is released at return
+      return r;
+    }
     if (useSil) {
       auto wss = devAlloc((trans ? w2l_asg_beam_lex_sil_workspace_size : w2l_ctc_beam_lex_sil_workspace_size)(family, B, T, N, o.beamSize,
                                                                                                           o.beamSizeToken) + 256);
