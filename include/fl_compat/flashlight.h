@@ -680,8 +680,8 @@ class Lexicon;   // fl_compat/lexicon.h
 // The options and the result of CTCLoss::beamSearch and ASGLoss::beamSearch (fl_compat ADDITIONS to the reference's interface).
 // "token classes" below are N-1 for CTC (blank = N-1 is none) and all N for ASG.
 struct BeamSearchOptions {
-  int beamSize = 64;                  // W, 1..64; 1..1024 with wide; 1..8192 with xl
-  int beamSizeToken = 64;             // K, clipped to the token classes (CTC: N-1, ASG: N), then <= 64
+  int beamSize = 64;                  // W, 1..64; 1..1024 with wide; 1..8192 with xl or manyTokens
+  int beamSizeToken = 64;             // K, clipped to the token classes (CTC: N-1, ASG: N), then <= 64; <= 256 with manyTokens
   float beamThreshold = 1.0f / 0.0f;  // candidates below best - threshold are dropped; +inf: none
   bool logAdd = false;                // false: max over a prefix's alignments (the 1-best is the greedy transcript); true: their sum
   int normalize = -1;                 // 1: search on log-softmax rows, 0: on the raw emissions, -1: CTC as logAdd, ASG 0
@@ -711,6 +711,10 @@ struct BeamSearchOptions {
   // --uselexicon=true --decodertype=tkn): every token that moves along a trie edge adds lmWeight * log p_LM(token | tokens before),
   // a completed word adds wordScore alone.  Without lexicon, or with xl: std::invalid_argument; the streaming decoders refuse it too.
   bool lmToken = false;
+  // every whole-utterance search above on the many-token kernels (the w2l_*_mt entry points): the same contract with W up to 8192 and
+  // K, after clipping, up to 256 -- the --beamsizetoken of the reference's word-piece recipes; the xl kernels' bytes at K <= 64.
+  // With wide, xl or lmToken: std::invalid_argument; the streaming decoders refuse it too.
+  bool manyTokens = false;
 };
 struct BeamSearchResult {
   af::array labels;    // (Lmax, M, B) s32: the first min(length, Lmax) labels, -1 beyond

@@ -521,6 +521,63 @@ int w2l_asg_beam_search_lex_sil(int family, int B, int T, int N, const float* in
                                 int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
                                 float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
                                 int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
+/* The MANY-TOKEN twins of the five beam searches (the reference's --beamsizetoken above 64: 100 in its word-piece recipes, 150;
+ * csrc/criterion_beam_mt.hpp).  Each takes its xl twin's argument list, then silToken and silScore, and obeys the
+ * sibling's contract word for word -- the frame tokens are the K best non-blank classes by lp descending, class ascending; stay /
+ * ext / merge / prune; the order total descending, rank ascending, stay before extension, k ascending, slot ascending; the
+ * threshold line, the lexicon slots, the ASG rules, the end rule and the EOS term; the silence rule of the *_sil entry points
+ * (tokens are chosen by the acoustic lp alone, then lp[sil] + silScore is read wherever the search reads it); the outputs -- with
+ * one difference: W may be 1..8192 as in the xl twins and K AFTER CLIPPING MAY BE 1..256.  silToken = -1 or silScore == 0: no
+ * silence score, and no + 0 is executed.
+ * Consequences.  At K <= 64 every output equals the xl twin's bit for bit (with a silence score: the *_sil entry point's at
+ * family 2), in both logAdd modes; nothing is routed there, the many-token kernels run.
+ * The kernels are the xl family's scan with what a token count above 64 touches changed: 256 LDS slots of frame tokens, gone masks
+ * of ceil(K / 64) 64-bit words per (slot, entry) in the workspace (word k >> 6, bit k & 63), a tie key with 8 bits of k
+ * (r << 12 | ext << 11 | k << 3 | slot: the same lexicographic order, so the same ranks), and a candidate list of W * K (* 7 with
+ * a lexicon) + W keys counted in size_t.  The row pass and the finish are the xl twins'.
+ * Refusals, in the xl twin's order, before anything touches the device: its W2L_EINVALs and those of the *_sil entry points
+ * (silScore not finite; silToken outside -1 .. N-2 for CTC, -1 .. N-1 for ASG); then W2L_EUNSUPPORTED for W > 8192, for K > 256
+ * after clipping, and for T * W > 2^29.  The *_mt_workspace_size functions are host arithmetic and return 0 for what the call
+ * refuses; at K <= 64 the size is the xl twin's, above it the candidate list grows with K and the masks by 8 bytes per (slot,
+ * entry) and further word: 8192 * 256 * 7 + 8192 keys are 112 MiB per utterance.
+ * Only these ten entry points take K above 64.  The narrow, wide and xl searches, the *_sil and *_lextok entry points and the beam
+ * sessions keep K <= 64 and their refusals. */
+size_t w2l_ctc_beam_mt_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_mt(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                           int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                           int nbest /*M*/, int maxLen /*Lmax*/,
+                           int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                           void* workspace, w2l_stream_t stream, int silToken, float silScore);
+size_t w2l_ctc_beam_lm_mt_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lm_mt(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                              int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                              int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                              const float* classScore /*[N-1] or NULL*/, float eosScore,
+                              int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                              float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
+size_t w2l_ctc_beam_lex_mt_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_ctc_beam_search_lex_mt(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                               int beam /*W*/, int beamToken /*K*/, float threshold, int logAdd, int normalize,
+                               int nbest /*M*/, int maxLen /*Lmax*/, const void* lm, int lmHasEos, float lmWeight,
+                               const void* lexicon, float wordScore, float eosScore,
+                               int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                               float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                               int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
+size_t w2l_asg_beam_mt_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_mt(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                           const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/, float threshold,
+                           int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm /*or NULL*/,
+                           int lmHasEos, float lmWeight, const float* classScore /*[N] or NULL*/, float eosScore,
+                           int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                           float* lmScores /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
+size_t w2l_asg_beam_lex_mt_workspace_size(int B, int T, int N, int beam, int beamToken);
+int w2l_asg_beam_search_lex_mt(int B, int T, int N, const float* input /*[B][T][N]*/, const int* frames /*[B] or NULL*/,
+                               const float* trans /*[N][N], to x from, device*/, int beam /*W*/, int beamToken /*K*/,
+                               float threshold, int logAdd, int normalize, int nbest /*M*/, int maxLen /*Lmax*/, const void* lm,
+                               int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
+                               int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
+                               float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
+                               int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
 /* The lexicon searches with a TOKEN-LEVEL LM (the reference's --uselexicon=true --decodertype=tkn; csrc/criterion_beam_lextok.hpp,
  * DESIGN 3.27): the lexicon constrains the spellings, the LM scores the tokens.  The argument lists are those of
  * w2l_ctc_beam_search_lex_sil and w2l_asg_beam_search_lex_sil, and the contract is w2l_ctc_beam_search_lex's (ASG:

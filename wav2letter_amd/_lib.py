@@ -167,6 +167,17 @@ class _SIGS:
     w2l_ctc_beam_search_lex_sil = (_i, [_i] + w2l_ctc_beam_search_lex[1] + [_i, _f])
     w2l_asg_beam_search_sil = (_i, [_i] + w2l_asg_beam_search[1] + [_i, _f])
     w2l_asg_beam_search_lex_sil = (_i, [_i] + w2l_asg_beam_search_lex[1] + [_i, _f])
+    # the five many-token searches (K <= 256): the xl twin's arguments, then int silToken, float silScore
+    w2l_ctc_beam_mt_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_ctc_beam_lm_mt_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_ctc_beam_lex_mt_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_asg_beam_mt_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_asg_beam_lex_mt_workspace_size = (_sz, [_i, _i, _i, _i, _i])
+    w2l_ctc_beam_search_mt = (_i, w2l_ctc_beam_search[1] + [_i, _f])
+    w2l_ctc_beam_search_lm_mt = (_i, w2l_ctc_beam_search_lm[1] + [_i, _f])
+    w2l_ctc_beam_search_lex_mt = (_i, w2l_ctc_beam_search_lex[1] + [_i, _f])
+    w2l_asg_beam_search_mt = (_i, w2l_asg_beam_search[1] + [_i, _f])
+    w2l_asg_beam_search_lex_mt = (_i, w2l_asg_beam_search_lex[1] + [_i, _f])
     # the lexicon searches with a token LM: the *_lex_sil argument lists
     w2l_ctc_beam_lextok_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])
     w2l_asg_beam_lextok_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])

@@ -303,12 +303,13 @@ def ctc_align(emission, target, frames=None, with_score=True):
 
 
 def _wide(L, name, wide):
-    """the entry point `name`, or its wide or xl twin: w2l_x_beam_search_y -> w2l_x_beam_search_y_wide / _xl, w2l_x_workspace_size
-    -> w2l_x_wide_workspace_size / w2l_x_xl_workspace_size.  wide: False, True or "xl" """
+    """the entry point `name`, or its wide, xl or many-token twin: w2l_x_beam_search_y -> w2l_x_beam_search_y_wide / _xl / _mt,
+    w2l_x_workspace_size -> w2l_x_wide_workspace_size / w2l_x_xl_workspace_size / w2l_x_mt_workspace_size.  wide: False, True, "xl"
+    or "mt" (the many-token search's silence arguments are _beam_fn's to add) """
     if isinstance(wide, str):
-        if wide != "xl":
-            raise _lib.W2LInvalidArgument(f'beam search: wide must be False, True or "xl", not {wide!r}')
-        suffix = "_xl"
+        if wide not in ("xl", "mt"):
+            raise _lib.W2LInvalidArgument(f'beam search: wide must be False, True, "xl" or "mt", not {wide!r}')
+        suffix = "_" + wide
     elif not wide:
         return getattr(L, name)
     else:
@@ -318,10 +319,24 @@ def _wide(L, name, wide):
     return getattr(L, name + suffix)
 
 
+def _wide_checks(wide, lm_token):
+    """what `wide` may be, alone and with lm_token, refused before anything else looks at the call"""
+    if isinstance(wide, str) and wide not in ("xl", "mt"):
+        raise _lib.W2LInvalidArgument(f'beam search: wide must be False, True, "xl" or "mt", not {wide!r}')
+    if lm_token and wide == "mt":
+        raise _lib.W2LInvalidArgument('beam search: lm_token=True has no many-token family (wide must be False or True)')
+
+
 def _beam_fn(L, name, wide, sil):
     """_wide(L, name, wide), or with sil = (token, score) the *_sil entry point behind the same call: the family goes in front
-    (0 narrow, 1 wide, 2 xl), the silence token and score behind"""
+    (0 narrow, 1 wide, 2 xl), the silence token and score behind.  wide="mt": the many-token entry point, which takes the token and
+    score itself (-1, 0: none) and no family"""
     f = _wide(L, name, wide)   # checks `wide`
+    if wide == "mt":
+        if name.endswith("_workspace_size"):
+            return f
+        tok, score = sil if sil is not None else (-1, 0.0)
+        return lambda *a: f(*a, tok, score)
     if sil is None:
         return f
     family = 2 if wide == "xl" else (1 if wide else 0)
@@ -336,6 +351,8 @@ def _lextok_fn(L, name, wide, sil):
     """the token-LM-under-a-lexicon entry point for `name` (w2l_x_beam_search_lex or w2l_x_beam_lex_workspace_size): the family in
     front, and behind the search's arguments the silence token and score (-1, 0: none)"""
     _wide(L, name, wide)   # checks `wide`
+    if wide == "mt":
+        raise _lib.W2LInvalidArgument('beam search: lm_token=True has no many-token family (wide must be False or True)')
     if wide == "xl":
         raise _lib.W2LInvalidArgument('beam search: lm_token=True has no xl family (wide must be False or True)')
     family = 1 if wide else 0
@@ -365,7 +382,7 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
                     nbest=1, max_len=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0,
                     max_words=None, wide=False, sil_token=None, sil_score=0.0, lm_token=False):
     """CTC prefix beam search without lexicon or LM (w2l_ctc_beam_search; the contract is in include/w2l_hip.h): `emission`
-    [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64; <= 1024 with wide=True; <= 8192 with wide="xl"), beam_token = K (clipped to N-1, then <= 64),
+    [B][T][N], blank = N-1, `frames` [B] int32 as in ctc_align.  beam = W (<= 64; <= 1024 with wide=True; <= 8192 with wide="xl"), beam_token = K (clipped to N-1, then <= 64; <= 256 with wide="mt"),
     log_add: sum (True) or max (False) over the alignments of a prefix; normalize: search on log-softmax rows (default: log_add --
     sums only mean something on log-probabilities; the max search runs on the raw emissions as the reference's decoder does).
     Returns (labels [B][nbest][max_len] int32, -1 beyond a hypothesis; lengths [B][nbest] int32, the true label counts, -1 for a
@@ -382,7 +399,9 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     wide: run the wide kernels (the w2l_*_wide entry points): the same contract with beam up to 1024; beam_token stays <= 64.  At
     beam <= 64 both kernel families return the same bytes.  wide="xl": run the xl kernels (the w2l_*_xl entry points): the same
     contract with beam up to 8192, the widths the reference's decoding recipes ask for; at beam <= 1024 they return the wide
-    kernels' bytes.  No family is chosen for the caller: wide=True with beam > 1024 is refused as before.
+    kernels' bytes.  No family is chosen for the caller: wide=True with beam > 1024 is refused as before.  wide="mt": run the
+    many-token kernels (the w2l_*_mt entry points): beam up to 8192 as with "xl" and beam_token, after clipping, up to 256 -- the
+    --beamsizetoken of the reference's word-piece recipes (100, 150); at beam_token <= 64 they return the xl kernels' bytes.
     sil_token, sil_score: the silence score (the w2l_*_sil entry points; the reference's --silscore): after the frame tokens have
     been chosen by the acoustic lp alone, class sil_token's frame score is lp + sil_score wherever the search reads it.
     sil_token=None with a lexicon: the lexicon's silence token.  A non-zero sil_score without any silence token is refused;
@@ -390,7 +409,8 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     lm_token=True (needs lexicon; w2l_ctc_beam_search_lextok, the reference's --uselexicon=true --decodertype=tkn): lm is an NGramLM
     over the lexicon's TOKENS, not its words.  Every token that moves along a trie edge adds lm_weight * log p_LM(token | tokens
     before), a completed word adds word_score alone, the lexicon's smear values are not read.  The return values are the lexicon
-    search's.  wide=True for beams up to 1024; wide="xl" is refused."""
+    search's.  wide=True for beams up to 1024; wide="xl" and wide="mt" are refused."""
+    _wide_checks(wide, lm_token)
     _emission_checks(emission)
     B, T, N = emission.shape
     sil = _sil_args("ctc_beam_search", sil_token, sil_score, lexicon)
@@ -485,6 +505,7 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
     with a lexicon -- with beam_token clipped to N, an LM (or lexicon) over N tokens and class_score [N].  normalize defaults to
     False in both log_add modes: ASG scores are unnormalised by design.  A token never follows itself: a repeated letter is a
     replabel's (Lexicon.from_file(..., replabel=) packs the spellings).  wide, sil_token, sil_score, lm_token: as in ctc_beam_search."""
+    _wide_checks(wide, lm_token)
     _emission_checks(emission)
     B, T, N = emission.shape
     sil = _sil_args("asg_beam_search", sil_token, sil_score, lexicon)
@@ -657,7 +678,7 @@ class ASGLoss(SequenceCriterion):
 
     def beamSearch(self, emission, frames=None, **options):
         """n-best beam search over the emissions under this criterion's transitions (asg_beam_search's options; wide=True: beam
-        up to 1024, wide="xl": up to 8192)"""
+        up to 1024, wide="xl": up to 8192, wide="mt": up to 8192 with beam_token up to 256)"""
         return asg_beam_search(emission, self.transitions, frames, **options)
 
     def prettyString(self):
@@ -724,7 +745,8 @@ class CTCLoss(SequenceCriterion):
 
     def beamSearch(self, emission, frames=None, **options):
         """n-best beam search over the emissions (ctc_beam_search's options, lm= and lexicon= included): (labels, lengths, scores),
-        lm_scores with an LM, and words and word_counts with a lexicon.  wide=True: beam up to 1024, wide="xl": up to 8192"""
+        lm_scores with an LM, and words and word_counts with a lexicon.  wide=True: beam up to 1024, wide="xl": up to 8192,
+        wide="mt": up to 8192 with beam_token up to 256"""
         return ctc_beam_search(emission, frames, **options)
 
     def score(self, emission, target):

@@ -22,6 +22,10 @@
 // No waiting between workgroups, no flags, no spin loops; every probe loop is bounded by its table's capacity; every barrier is
 // reached by all 1024 threads, and every loop with a barrier inside runs on counts read from LDS after a barrier, the same in
 // every thread.
+//   kMt                  the many-token searches (w2l_*_beam_search*_mt, criterion_beam_mt.hpp) are this scan with K up
+//                        to kBeamMtMax = 256: 256 LDS slots of frame tokens, gone masks of ceil(K / 64) words per (slot, entry),
+//                        a tie key with 8 bits of k.  Every difference is an `if constexpr (kMt)`; !kMt is the xl scan, whose
+//                        instructions must not change.
 //   beam_xl_finish<lex>  one workgroup per utterance, strided over the final entries and then over the output rows; keys, scores
 //                        and LM sums in dynamic LDS (16 bytes per entry of pow2(W)).
 #pragma once
@@ -29,12 +33,13 @@
 namespace w2l {
 
 constexpr int kBeamXlMax = 8192;      // W of the xl searches; their K stays <= kBeamMax
+constexpr int kBeamMtMax = 256;       // K of the many-token searches (criterion_beam_mt.hpp): this scan with kMt, W as here
 constexpr int kXlThreads = 1024;
 
 struct BeamXlWs {
   BeamWideWs w;      // the wide family's workspace: rows, table, candidate list, fin* (W entries per utterance)
   int* beam;         // [B][2][kFields][W]
-  u64* gone;         // [B][slots][W]
+  u64* gone;         // [B][slots][W]; the many-token scan: [B][slots][W][ceil(K / 64)]
   float* stay;       // [B][2][W]: pb', pnb' of stay(j)
   int hashN;         // 2 * pow2(W): slots of the LDS hash
 };
@@ -45,27 +50,34 @@ __host__ __device__ __forceinline__ int beam_xl_pow2(int m) {
   return n2;
 }
 
-static size_t beam_xl_layout(BeamXlWs* x, void* ws, int B, int T, int W, int K, int variant) {
+// words of a gone mask: one bit per frame token
+__host__ __device__ __forceinline__ int beam_mt_words(int K) { return (K + 63) >> 6; }
+
+static size_t beam_xl_layout(BeamXlWs* x, void* ws, int B, int T, int W, int K, int variant, bool mt = false) {
   const bool lex = variant == kBeamLex;
+  const size_t words = mt ? (size_t)beam_mt_words(K) : 1;
   char* p = (char*)ws;
   char* const p0 = p;
   p += align_up(beam_wide_layout(x ? &x->w : nullptr, ws, B, T, W, K, variant), 256);
   int* beam = (int*)p; p += align_up((size_t)B * 2 * (lex ? 9 : 8) * W * 4, 256);
-  u64* gone = (u64*)p; p += align_up((size_t)B * (lex ? 7 : 1) * W * 8, 256);
+  u64* gone = (u64*)p; p += align_up((size_t)B * (lex ? 7 : 1) * W * words * 8, 256);
   float* stay = (float*)p; p += align_up((size_t)B * 2 * W * 4, 256);
   if (x) { x->beam = beam; x->gone = gone; x->stay = stay; x->hashN = 2 * beam_xl_pow2(W); }
   return (size_t)(p - p0);
 }
 
-// the dynamic LDS of beam_xl_scan after the hash (hashN u64), in bytes
-struct XlLds {
-  static constexpr size_t tc = 0;                     // [64] int
-  static constexpr size_t tl = tc + 64 * 4;           // [64] float
-  static constexpr size_t hist = tl + 64 * 4;         // [256] unsigned
+// the dynamic LDS of beam_xl_scan after the hash (hashN u64), in bytes; kTok: the frame tokens it holds
+template <int kTok>
+struct XlLdsT {
+  static constexpr size_t tc = 0;                     // [kTok] int
+  static constexpr size_t tl = tc + kTok * 4;         // [kTok] float
+  static constexpr size_t hist = tl + kTok * 4;       // [256] unsigned
   static constexpr size_t red = hist + 256 * 4;       // [16] u64
   static constexpr size_t misc = red + 16 * 8;        // [8] unsigned
   static constexpr size_t bytes = misc + 8 * 4;
 };
+using XlLds = XlLdsT<kBeamMax>;
+using MtLds = XlLdsT<kBeamMtMax>;
 
 // s[0 .. n2) descending, n2 a power of two <= 8192; every thread of the workgroup calls it; ends with a barrier
 __device__ __forceinline__ void beam_xl_sort(u64* s, int n2) {
@@ -87,23 +99,48 @@ __device__ __forceinline__ u64 beam_xl_mask(const u64* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool kLogAdd, class Pol, bool kLex>
+// ---- what the many-token scan (kMt: K <= kBeamMtMax, criterion_beam_mt.hpp) does differently; !kMt is the xl scan as it was
+// The selection key with 8 bits of k: total, then ~(r << 12 | ext << 11 | k << 3 | slot), 25 bits for r < 8192: beam_key's order.
+template <bool kMt>
+__device__ __forceinline__ u64 beam_xl_key(float total, int r, int ext, int k, int slot = 0) {
+  if constexpr (!kMt) return beam_key(total, r, ext, k, slot);
+  else return ((u64)beam_ord(total) << 32) | (u64)(0xffffffffu - (unsigned)((r << 12) | (ext << 11) | (k << 3) | slot));
+}
+// the gone-mask word of (slot, entry r) that holds token k's bit, and the bit; mw: words per mask (1 when !kMt)
+template <bool kMt>
+__device__ __forceinline__ u64* beam_xl_gone(u64* gGone, int slot, int W, int r, int k, int mw) {
+  if constexpr (!kMt) return &gGone[(size_t)slot * W + r];
+  else return &gGone[((size_t)slot * W + r) * mw + (k >> 6)];
+}
+template <bool kMt>
+__device__ __forceinline__ u64 beam_xl_bit(int k) { return 1ull << (kMt ? (k & 63) : k); }
+// the frame tokens of `row`: beam_load_frame with kBeamMtMax slots
+__device__ __forceinline__ void beam_mt_load_frame(const CtcBeamWs& ws, size_t row, int* sTc, float* sTl) {
+  const int tid = threadIdx.x, K = ws.K;
+  if (tid < kBeamMtMax) {
+    sTc[tid] = tid < K ? ws.tokC[row * K + tid] : -2;
+    sTl[tid] = tid < K ? ws.tokLp[row * K + tid] : -INFINITY;
+  }
+}
+
+template <bool kLogAdd, class Pol, bool kLex, bool kMt = false>
 __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, float threshold, const float* __restrict__ x,
                                                            const int* __restrict__ frames, BeamXlWs xw,
                                                            const void* __restrict__ lex, const void* __restrict__ lm,
                                                            float lmWeight, const float* __restrict__ classScore, float wordScore,
                                                            BeamTrans tr) {
   constexpr int kF = kLex ? 9 : 8, kSlots = kLex ? 7 : 1, kTh = kXlThreads;
+  using Lds = XlLdsT<kMt ? kBeamMtMax : kBeamMax>;
   extern __shared__ float sAsgTrans[];   // BeamAsg::stage's array; nothing is staged here (tr.lds = 0)
   const int hashN = xw.hashN;
   u64* const sHash = (u64*)sAsgTrans;
   u64* const sSort = sHash;               // the survivors' keys, once the hash is dead
   char* const base = (char*)(sHash + hashN);
-  int* const sTc = (int*)(base + XlLds::tc);
-  float* const sTl = (float*)(base + XlLds::tl);
-  unsigned* const sHist = (unsigned*)(base + XlLds::hist);
-  u64* const sRed = (u64*)(base + XlLds::red);
-  unsigned* const sMisc = (unsigned*)(base + XlLds::misc);   // 0: candidates, 1: survivors, 2: bin, 3: keys above it, 4: keys in it,
+  int* const sTc = (int*)(base + Lds::tc);
+  float* const sTl = (float*)(base + Lds::tl);
+  unsigned* const sHist = (unsigned*)(base + Lds::hist);
+  u64* const sRed = (u64*)(base + Lds::red);
+  unsigned* const sMisc = (unsigned*)(base + Lds::misc);   // 0: candidates, 1: survivors, 2: bin, 3: keys above it, 4: keys in it,
                                                              // 5, 6: the silence class and score (below)
 
   const BeamWideWs& ww = xw.w;
@@ -118,7 +155,8 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
   u64* cand = ww.cand + (size_t)b * ww.candCap;
   const unsigned candCap = (unsigned)ww.candCap;
   int* const gBeam = xw.beam + (size_t)b * 2 * kF * W;
-  u64* const gGone = xw.gone + (size_t)b * kSlots * W;
+  const int mw = kMt ? beam_mt_words(K) : 1;   // words per gone mask
+  u64* const gGone = xw.gone + (size_t)b * kSlots * W * mw;
   float* const gSpb = xw.stay + (size_t)b * 2 * W;
   float* const gSpnb = gSpb + W;
   const bool useLm = kLex || lm != nullptr;
@@ -149,9 +187,15 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
     const float *cPb = ff(cur, 4), *cPnb = ff(cur, 5), *cTot = ff(cur, 6), *cAcc = ff(cur, 7);
     const int* cLab = kLex ? fi(cur, 8) : nullptr;
 
-    beam_load_frame(ws, row, sTc, sTl);
-    for (int j = tid; j < n; j += kTh)
-      for (int s = 0; s < kSlots; ++s) gGone[(size_t)s * W + j] = 0ull;
+    if constexpr (kMt) beam_mt_load_frame(ws, row, sTc, sTl);
+    else beam_load_frame(ws, row, sTc, sTl);
+    if constexpr (kMt) {
+      for (int i = tid; i < n * mw; i += kTh)
+        for (int s = 0; s < kSlots; ++s) gGone[(size_t)s * W * mw + i] = 0ull;
+    } else {
+      for (int j = tid; j < n; j += kTh)
+        for (int s = 0; s < kSlots; ++s) gGone[(size_t)s * W + j] = 0ull;
+    }
     for (int i = tid; i < hashN; i += kTh) sHash[i] = 0ull;
     if (tid < 2) sMisc[tid] = 0u;
     const float lpb = ws.lpb[row], lse = ws.lse[row];
@@ -203,7 +247,7 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
             v = beam_lm_ext(v, lmWeight, qm, classScore, e);
           }
           spnb = beam_oplus<kLogAdd>(spnb, v);
-          atomicOr(&gGone[pr], 1ull << kj);
+          atomicOr(beam_xl_gone<kMt>(gGone, 0, W, pr, kj, mw), beam_xl_bit<kMt>(kj));
         } else {
           const int lab = cLab[j];
           if (lab >= 0) {
@@ -220,46 +264,51 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
               }
             }
             spnb = beam_oplus<kLogAdd>(spnb, v);
-            atomicOr(&gGone[(size_t)min(slot, 6) * W + pr], 1ull << kj);
+            atomicOr(beam_xl_gone<kMt>(gGone, min(slot, 6), W, pr, kj, mw), beam_xl_bit<kMt>(kj));
           }
         }
       }
       gSpb[j] = spb; gSpnb[j] = spnb;
-      put(beam_key(beam_oplus<kLogAdd>(spb, spnb), j, 0, 0));
+      put(beam_xl_key<kMt>(beam_oplus<kLogAdd>(spb, spnb), j, 0, 0));
     }
     __syncthreads();   // the hash is read, the gone masks are complete
 
+    // is the extension of entry r by frame token k gone in `slot`?
+    auto gone = [&](int slot, int r, int k) -> bool {
+      if constexpr (kMt) return (beam_xl_mask(beam_xl_gone<true>(gGone, slot, W, r, k, mw)) >> (k & 63)) & 1ull;
+      else return (beam_xl_mask(&gGone[(size_t)slot * W + r]) >> k) & 1ull;
+    };
     const int total = n * K;
     for (int idx = tid; idx < total; idx += kTh) {
       const int r = idx / K, k = idx - r * K, c = sTc[k], e = cE[r];
       if (Pol::none(c, e)) continue;
       const float a0 = Pol::ext(sTl[k], c, e, cPb[r], cTot[r], A, N);
       if constexpr (!kLex) {
-        if ((beam_xl_mask(&gGone[r]) >> k) & 1ull) continue;
+        if (gone(0, r, k)) continue;
         float v = a0;
         if (useLm) {
           int unused;
           const float q = ngram_q(lv, cSt[r], c, &unused);
           v = beam_lm_ext(v, lmWeight, q, classScore, c);
         }
-        put(beam_key(v, r, 1, k));
+        put(beam_xl_key<kMt>(v, r, 1, k));
       } else {
         const int u = beam_wide_u(cLab[r]);
         if (c == xv.silToken && u == 0) {
-          if (!((beam_xl_mask(&gGone[r]) >> k) & 1ull)) put(beam_key(a0, r, 1, k, 0));
+          if (!gone(0, r, k)) put(beam_xl_key<kMt>(a0, r, 1, k, 0));
         } else {
           const int v = lex_child(xv, u, c);
           if (v > 0) {
             const LexNode& nd = lex_node(xv, v);
             const float smv = nd.smear;
             const float a = beam_lex_a(a0, lmWeight, smv, u == 0 ? 0.f : lex_node(xv, u).smear);
-            if (lex_has_children(nd) && !((beam_xl_mask(&gGone[r]) >> k) & 1ull)) put(beam_key(a, r, 1, k, 0));
+            if (lex_has_children(nd) && !gone(0, r, k)) put(beam_xl_key<kMt>(a, r, 1, k, 0));
             const int nw = lex_nw(nd);
             for (int i = 0; i < nw; ++i)
-              if (!((beam_xl_mask(&gGone[(size_t)(1 + i) * W + r]) >> k) & 1ull)) {
+              if (!gone(1 + i, r, k)) {
                 int unused;
                 const float q = ngram_q(lv, cSt[r], nd.words[i], &unused);
-                put(beam_key(beam_lex_word(a, lmWeight, q, smv, wordScore), r, 1, k, 1 + i));
+                put(beam_xl_key<kMt>(beam_lex_word(a, lmWeight, q, smv, wordScore), r, 1, k, 1 + i));
               }
           }
         }
@@ -322,7 +371,8 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
     for (int q = tid; q < m; q += kTh) {
       const u64 key = sSort[q];
       const unsigned tie = 0xffffffffu - (unsigned)key;
-      const int r = min((int)(tie >> 10), W - 1), ext = (int)((tie >> 9) & 1u), k = (int)((tie >> 3) & 63u), slot = (int)(tie & 7u);
+      const int r = min((int)(tie >> (kMt ? 12 : 10)), W - 1), ext = (int)((tie >> (kMt ? 11 : 9)) & 1u),
+                k = (int)((tie >> 3) & (kMt ? 255u : 63u)), slot = (int)(tie & 7u);
       if (!ext) {
         const float pb = gSpb[r], pnb = gSpnb[r];
         fi(nxt, 0)[q] = cNode[r]; fi(nxt, 1)[q] = cPar[r]; fi(nxt, 2)[q] = cE[r]; fi(nxt, 3)[q] = cSt[r];
@@ -453,38 +503,43 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_finish(int M, int Lmax, in
   }
 }
 
-static size_t beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken, int variant, bool noBlank) {
+// mt: the many-token searches' (K <= kBeamMtMax, the gone masks in words; T * W as the call refuses it)
+static size_t beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken, int variant, bool noBlank, bool mt = false) {
   if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
   const int K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
-  if (beam > kBeamXlMax || K > kBeamMax) return 0;
-  return beam_xl_layout(nullptr, nullptr, B, T, beam, K, variant);
+  if (beam > kBeamXlMax || K > (mt ? kBeamMtMax : kBeamMax)) return 0;
+  if (mt && (size_t)T * beam > ((size_t)1 << 29)) return 0;
+  return beam_xl_layout(nullptr, nullptr, B, T, beam, K, variant, mt);
 }
 
 // beam_wide_check with the xl limit: every W2L_EINVAL first, then the limits, then T * W (node ids are ints)
 static int beam_xl_check(int B, int T, int N, const float* input, int beam, int beamToken, float threshold, int nbest, int maxLen,
-                         const int* labels, const int* lengths, const float* scores, const void* workspace, int* K, bool noBlank) {
+                         const int* labels, const int* lengths, const float* scores, const void* workspace, int* K, bool noBlank,
+                         bool mt = false) {
   if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !workspace) return W2L_EINVAL;
   if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
   if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
   *K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
-  if (beam > kBeamXlMax || *K > kBeamMax) return W2L_EUNSUPPORTED;
+  if (beam > kBeamXlMax || *K > (mt ? kBeamMtMax : kBeamMax)) return W2L_EUNSUPPORTED;
   if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;
   return W2L_OK;
 }
 
 constexpr size_t kXlScanLdsMax = (size_t)2 * kBeamXlMax * 8 + XlLds::bytes;   // 128 KiB + 2 KiB
+constexpr size_t kMtScanLdsMax = (size_t)2 * kBeamXlMax * 8 + MtLds::bytes;   // 128 KiB + 3.2 KiB
 constexpr size_t kXlFinishLdsMax = (size_t)kBeamXlMax * 16 + 8;               // 128 KiB
+static_assert(kMtScanLdsMax <= 160 * 1024, "the many-token scan's hash and frame state must fit the CU's LDS");
 
-template <bool kLogAdd, class Pol, bool kLex>
+template <bool kLogAdd, class Pol, bool kLex, bool kMt = false>
 static int beam_xl_launch(int B, int T, int N, float threshold, const float* input, const int* frames, const BeamXlWs& xw,
                           const void* lex, const void* lm, float lmWeight, const float* classScore, float wordScore,
                           const BeamTrans& tr, hipStream_t s) {
-  const size_t shmem = (size_t)xw.hashN * 8 + XlLds::bytes;
+  const size_t shmem = (size_t)xw.hashN * 8 + (kMt ? MtLds::bytes : XlLds::bytes);
   static bool attr[64] = {};
   if (first_on_device(attr))
-    W2L_HIP_CHECK(hipFuncSetAttribute((const void*)beam_xl_scan<kLogAdd, Pol, kLex>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kXlScanLdsMax));
-  hipLaunchKernelGGL((beam_xl_scan<kLogAdd, Pol, kLex>), dim3((unsigned)B), dim3(kXlThreads), shmem, s, T, N, xw.w.W, threshold,
+    W2L_HIP_CHECK(hipFuncSetAttribute((const void*)beam_xl_scan<kLogAdd, Pol, kLex, kMt>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)(kMt ? kMtScanLdsMax : kXlScanLdsMax)));
+  hipLaunchKernelGGL((beam_xl_scan<kLogAdd, Pol, kLex, kMt>), dim3((unsigned)B), dim3(kXlThreads), shmem, s, T, N, xw.w.W, threshold,
                      input, frames, xw, lex, lm, lmWeight, classScore, wordScore, tr);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
@@ -505,15 +560,15 @@ static int beam_xl_finish_launch(int B, int M, int Lmax, int maxWords, int eosWo
   return W2L_OK;
 }
 
-// One xl search after its checks: rows, scan, finish.  trans null: CTC; lex null: the token search
+// One xl search after its checks: rows, scan, finish.  trans null: CTC; lex null: the token search; mt: the many-token scan
 static int beam_xl_run(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam, int K,
                        float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
                        float lmWeight, const float* classScore, const void* lex, float wordScore, float eosScore, int* labels,
                        int* lengths, float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                       hipStream_t s, BeamSil sil) {
+                       hipStream_t s, BeamSil sil, bool mt = false) {
   const bool asg = trans != nullptr, isLex = lex != nullptr;
   BeamXlWs xw{};
-  beam_xl_layout(&xw, workspace, B, T, beam, K, isLex ? kBeamLex : kBeamLm);
+  beam_xl_layout(&xw, workspace, B, T, beam, K, isLex ? kBeamLex : kBeamLm, mt);
   xw.w.c.sil = sil.token; xw.w.c.silScore = sil.score;
   const BeamWideWs& ww = xw.w;
   W2L_HIP_CHECK(hipMemsetAsync(ww.c.table, 0, (size_t)B * ww.c.cap * sizeof(u64), s));
@@ -531,8 +586,9 @@ static int beam_xl_run(int B, int T, int N, const float* input, const int* frame
 
   const BeamTrans tr{trans, 0};   // gathered from global memory: the LDS is the hash's
   int rc = W2L_OK;
-#define W2L_XL_SCAN(LA, POL, LEX) \
-  rc = beam_xl_launch<LA, POL, LEX>(B, T, N, threshold, input, frames, xw, lex, lm, lmWeight, classScore, wordScore, tr, s)
+#define W2L_XL_SCAN(LA, POL, LEX)                                                                                                  \
+  rc = mt ? beam_xl_launch<LA, POL, LEX, true>(B, T, N, threshold, input, frames, xw, lex, lm, lmWeight, classScore, wordScore, tr, s) \
+          : beam_xl_launch<LA, POL, LEX>(B, T, N, threshold, input, frames, xw, lex, lm, lmWeight, classScore, wordScore, tr, s)
   if (isLex) {
     if (asg) { if (logAdd) W2L_XL_SCAN(true, BeamAsg, true); else W2L_XL_SCAN(false, BeamAsg, true); }
     else { if (logAdd) W2L_XL_SCAN(true, BeamCtc, true); else W2L_XL_SCAN(false, BeamCtc, true); }
@@ -572,13 +628,13 @@ namespace w2l {
 // w2l_ctc_beam_search_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
 static int ctc_beam_search_xl_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                    float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
-                                   float* scores, void* workspace, w2l_stream_t stream, BeamSil sil) {
+                                   float* scores, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
   int K = 0;
   if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   false))
+                                   false, mt))
     return rc;
   return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, nullptr, 0, 0.f, nullptr,
-                     nullptr, 0.f, 0.f, labels, lengths, scores, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream, sil);
+                     nullptr, 0.f, 0.f, labels, lengths, scores, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream, sil, mt);
 }
 }  // namespace w2l
 
@@ -594,17 +650,17 @@ namespace w2l {
 static int ctc_beam_search_lm_xl_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
                                       float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                       int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
-                                      int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
+                                      int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
   if (!lmScores || !lm) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
   int K = 0;
   if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   false))
+                                   false, mt))
     return rc;
   return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                      classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                     (hipStream_t)stream, sil);
+                     (hipStream_t)stream, sil, mt);
 }
 }  // namespace w2l
 
@@ -622,17 +678,17 @@ static int ctc_beam_search_lex_xl_do(int B, int T, int N, const float* input, co
                                        float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                        int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
                                        int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
-                                       int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
+                                       int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
   if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
   int K = 0;
   if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   false))
+                                   false, mt))
     return rc;
   return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                      nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                     (hipStream_t)stream, sil);
+                     (hipStream_t)stream, sil, mt);
 }
 }  // namespace w2l
 
@@ -651,18 +707,18 @@ namespace w2l {
 static int asg_beam_search_xl_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
                                    int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
                                    int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
+                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
   if (!lmScores || !trans) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
   if (!lm && (lmHasEos || classScore)) return W2L_EINVAL;
   int K = 0;
   if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   true))
+                                   true, mt))
     return rc;
   return beam_xl_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                      classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                     (hipStream_t)stream, sil);
+                     (hipStream_t)stream, sil, mt);
 }
 }  // namespace w2l
 
@@ -680,17 +736,17 @@ static int asg_beam_search_lex_xl_do(int B, int T, int N, const float* input, co
                                        int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
                                        const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
                                        float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
+                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
   if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1 || !trans) return W2L_EINVAL;
   if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
   if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
   int K = 0;
   if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   true))
+                                   true, mt))
     return rc;
   return beam_xl_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
                      nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                     (hipStream_t)stream, sil);
+                     (hipStream_t)stream, sil, mt);
 }
 }  // namespace w2l
 

@@ -1,5 +1,5 @@
 // decode_main.cpp -- `Decode --am=<NNN_model_*.bin> --test=<list> [--datadir=] [--batchsize=] [--sclite=<dir>] [--beamsize=]
-// [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--w2l_beam_xl=] [--w2l_silscore=] [--silscore=] [--w2l_lex_tkn=] [--k=v ...]`: the
+// [--beamsizetoken=] [--beamthreshold=] [--logadd=] [--isbeamdump=] [--nbest=] [--show=] [--showletters=] [--w2l_beam_xl=] [--w2l_beam_tokens=] [--w2l_silscore=] [--silscore=] [--w2l_lex_tkn=] [--k=v ...]`: the
 // reference's Decode tool for its lexicon-free token decoder (`--uselexicon=false --decodertype=tkn`), without LM (the configuration
 // of recipes/self_training/librispeech/am/decode_*.cfg) or with a token-level n-gram LM (`--lm=<arpa>`, recipes/lexicon_free and the
 // word-piece runs of sota/2019), and for its lexicon decoder with a word LM (recipes/conv_glu/*/decode*.cfg), over the fl::
@@ -23,6 +23,11 @@
 //   --w2l_beam_xl=true (not the reference's; default false): a --beamsize given in the flags and above 1024 runs the xl kernels
 //   (BeamSearchOptions::xl), which keep up to 8192 beam entries -- the recipes' 1500, 2500, 5000 and 8000 as they are written;
 //   larger values are limited to 8192 (said on stderr).  Values up to 1024 and an absent --beamsize route as without the flag.
+//   --w2l_beam_tokens=true (not the reference's; default false): a --beamsizetoken given in the flags and, after clipping to the
+//   token count, above 64 runs the many-token kernels (BeamSearchOptions::manyTokens, the w2l_*_mt entry points) at that value --
+//   the word-piece recipes' 100 and 150 as they are written -- for any given --beamsize up to 8192; larger values are limited to
+//   256 tokens and 8192 entries, each said on stderr (an absent --beamsize is limited to 64 as ever).  With a token count at or
+//   under 64 after clipping, or an absent --beamsizetoken, routing is as without the flag.  --w2l_lex_tkn=true with it is refused.
 //   --w2l_silscore=true (not the reference's; default false): --silscore (older name: --silweight; both given with different
 //   values: refused) takes effect in every search Decode runs (BeamSearchOptions::silToken / silScore, the w2l_*_sil entry points):
 //   the silence token is the class of --wordseparator, and after a frame's tokens have been chosen by the acoustic score alone that
@@ -81,11 +86,11 @@ namespace {
 int usage(const char* exe) {
   std::cerr << "Usage: \n " << exe
             << " --am=<model> --test=<list> [--datadir=...] [--batchsize=...] [--sclite=<dir>] [--beamsize=2500] [--beamsizetoken=250000]"
-               " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [--w2l_beam_xl=false] [--w2l_silscore=false --silscore=0] [flags]\n"
+               " [--beamthreshold=25] [--logadd=false] [--isbeamdump=false] [--nbest=1] [--show=false] [--showletters=false] [--w2l_beam_xl=false] [--w2l_beam_tokens=false] [--w2l_silscore=false --silscore=0] [flags]\n"
                " [--lm=<arpa> --lmtype=kenlm --lmweight=0 --eosscore=0 --wordscore=0]\n"
                " [--uselexicon=true --decodertype=wrd --lexicon=<file> --lm=<word arpa> --smearing=none|max]\n"
                " [--w2l_lex_tkn=true --uselexicon=true --decodertype=tkn --lexicon=<file> --lm=<token arpa>]\n"
-               " CTC or ASG (as the checkpoint says) token beam search, optionally with a token-level n-gram LM (ARPA text); --beamsize is limited to 1024 when given (above 64: the wide kernels), to 64 when absent; with --w2l_beam_xl=true a given --beamsize above 1024 runs the xl kernels and is limited to 8192; tokens per frame are limited to 64.\n"
+               " CTC or ASG (as the checkpoint says) token beam search, optionally with a token-level n-gram LM (ARPA text); --beamsize is limited to 1024 when given (above 64: the wide kernels), to 64 when absent; with --w2l_beam_xl=true a given --beamsize above 1024 runs the xl kernels and is limited to 8192; tokens per frame are limited to 64, or with --w2l_beam_tokens=true a given --beamsizetoken above 64 runs the many-token kernels (any given --beamsize up to 8192) and is limited to 256.\n"
                " --w2l_silscore=true: --silscore (older name --silweight) is added to the frame score of the --wordseparator class after the frame's tokens are chosen; without it a non-zero --silscore is refused.\n"
                " --logadd=false (default): max over a prefix's alignments on the raw emissions -- the 1-best equals the greedy transcript.\n"
                " --logadd=true: the labelling-probability search (sum over a prefix's alignments, on log-softmax rows)."
@@ -149,6 +154,8 @@ int main(int argc, char** argv) {
     const bool tokenLm = lexTkn && useLexicon && decoderType == "tkn";
     if (lexTkn && flags.getb("w2l_beam_xl", false))
       throw std::invalid_argument("--w2l_beam_xl=true with --w2l_lex_tkn=true: the token LM under a lexicon has no xl kernels (beams up to 1024)");
+    if (lexTkn && flags.getb("w2l_beam_tokens", false))
+      throw std::invalid_argument("--w2l_beam_tokens=true with --w2l_lex_tkn=true: the token LM under a lexicon has no many-token kernels (64 tokens per frame)");
     if (decoderType != "tkn" && decoderType != "wrd")
       throw std::invalid_argument("--decodertype=" + decoderType + ": tkn (lexicon-free) or wrd (with --uselexicon=true)");
     if (useLexicon) {
@@ -205,15 +212,19 @@ int main(int argc, char** argv) {
     else numClasses += 1;                                    // blank, appended LAST
     const int numTokens = asg ? numClasses : numClasses - 1;   // the classes a hypothesis is made of
     // a beam width that was asked for runs the wide kernels above 64, and with --w2l_beam_xl=true the xl kernels above 1024
+    // and with --w2l_beam_tokens=true a token count that was asked for and is above 64 after clipping runs the many-token kernels
     const bool xlFlag = flags.getb("w2l_beam_xl", false);
-    const long beamLimit = flags.has("beamsize") ? (xlFlag ? 8192 : 1024) : 64;
+    beamToken = std::min<long>(beamToken, numTokens);
+    const bool manyTokens = flags.getb("w2l_beam_tokens", false) && flags.has("beamsizetoken") && beamToken > 64;
+    const long beamLimit = flags.has("beamsize") ? (xlFlag || manyTokens ? 8192 : 1024) : 64;
     if (beamSize > beamLimit) {
       std::cerr << "[Decode] --beamsize=" << beamSize << " limited to " << beamLimit << " (the kernel's beam width)" << std::endl;
       beamSize = beamLimit;
     }
-    const bool xl = beamSize > 1024, wide = beamSize > 64 && !xl;
-    beamToken = std::min<long>(beamToken, numTokens);
-    if (beamToken > 64) { std::cerr << "[Decode] --beamsizetoken limited to 64 tokens per frame" << std::endl; beamToken = 64; }
+    const bool xl = !manyTokens && beamSize > 1024, wide = !manyTokens && beamSize > 64 && !xl;
+    if (manyTokens) {
+      if (beamToken > 256) { std::cerr << "[Decode] --beamsizetoken limited to 256 tokens per frame" << std::endl; beamToken = 256; }
+    } else if (beamToken > 64) { std::cerr << "[Decode] --beamsizetoken limited to 64 tokens per frame" << std::endl; beamToken = 64; }
     const int M = beamDump ? (int)std::min(nbest, beamSize) : 1;
 
     // ---- network and criterion, both from the model file (Train fork's construction)
@@ -232,7 +243,7 @@ int main(int argc, char** argv) {
     Serializer::load(am, version, unused, network, criterion);
     network->eval();
     criterion->eval();
-    std::cerr << "[Decode] " << criterion->prettyString() << ", " << numClasses << " classes, model " << am << ", beam " << beamSize << (xl ? " (xl)" : wide ? " (wide)" : "")
+    std::cerr << "[Decode] " << criterion->prettyString() << ", " << numClasses << " classes, model " << am << ", beam " << beamSize << (manyTokens ? " (many-token)" : xl ? " (xl)" : wide ? " (wide)" : "")
               << ", tokens per frame " << beamToken << ", threshold " << threshold << (logAdd ? ", logadd" : ", max") << std::endl;
 
     // ---- the list
@@ -340,6 +351,7 @@ int main(int argc, char** argv) {
       opt.beamSize = (int)beamSize;
       opt.wide = wide;
       opt.xl = xl;
+      opt.manyTokens = manyTokens;
       opt.beamSizeToken = (int)beamToken;
       opt.beamThreshold = (float)threshold;
       opt.logAdd = logAdd;

@@ -1486,6 +1486,7 @@ void StreamingDecoder::create(bool wideKernels) {
   const BeamSearchOptions& o = o_;
   if (o.silScore != 0.f) throw std::invalid_argument("StreamingDecoder: beam sessions have no silence score (silScore must be 0)");
   if (o.lmToken) throw std::invalid_argument("StreamingDecoder: beam sessions have no token LM under a lexicon (lmToken must be false)");
+  if (o.manyTokens) throw std::invalid_argument("StreamingDecoder: beam sessions keep at most 64 tokens per frame (manyTokens must be false)");
   const int slots = slots_, maxChunk = maxChunk_, maxFrames = maxFrames_, numLabels = nLabel_;
   if (o.nbest < 1 || o.maxLen < 0 || o.maxWords < 0) throw std::invalid_argument("StreamingDecoder: bad nbest, maxLen or maxWords");
   w2l_beam_session_desc d{};
@@ -1605,10 +1606,14 @@ void StreamingDecoder::reset(int slot) {
 }
 
 // n-best beam search; inputSizes as in viterbiPathWithTarget.  trans == nullptr: the CTC searches (w2l_ctc_beam_search*), blank =
-// N-1; else the ASG searches (w2l_asg_beam_search*) under that transition matrix, every class a token; o.wide: their _wide twins, o.xl: their _xl twins
+// N-1; else the ASG searches (w2l_asg_beam_search*) under that transition matrix, every class a token; o.wide: their _wide twins, o.xl: their _xl twins,
+// o.manyTokens: their _mt twins
 static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, const float* trans, const af::array& input,
                                       const af::array& inputSizes, const BeamSearchOptions& o) {
   if (o.xl && o.wide) throw std::invalid_argument("beamSearch: wide and xl name two kernel families, choose one");
+  if (o.manyTokens && (o.wide || o.xl))
+    throw std::invalid_argument("beamSearch: manyTokens is a kernel family of its own (beam up to 8192), not with wide or xl");
+  if (o.manyTokens && o.lmToken) throw std::invalid_argument("beamSearch: lmToken has no many-token family (narrow, or wide up to 1024)");
   const int N = (int)input.dims(0), T = (int)input.dims(1), B = (int)input.dims(2);
   const int* frames = nullptr;
   if (!inputSizes.isempty()) {
@@ -1626,6 +1631,7 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
   const int silToken = o.silToken >= 0 || !o.lexicon ? o.silToken : o.lexicon->silToken();
   const bool useSil = o.silScore != 0.f;
   if (useSil && silToken < 0) throw std::invalid_argument("beamSearch: silScore needs a silence token (silToken, or a lexicon that has one)");
+  const int mtSil = useSil ? silToken : -1;   // the *_mt entry points take the silence token and score themselves; -1: none
   BeamSearchResult r;
   r.labels = af::array(af::dim4(Lmax, o.nbest, B), af::s32);
   r.lengths = af::array(af::dim4(o.nbest, B), af::s32);
@@ -1665,6 +1671,26 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
                                                  r.words.device<int>(), r.wordCounts.device<int>(), wst.get(), S(), st, o.silScore),
                       "ctc beam search with lexicon and token LM");
       af::sync();  // wst is released at return
+      return r;
+    }
+    if (o.manyTokens) {
+      auto wsm = devAlloc((trans ? w2l_asg_beam_lex_mt_workspace_size : w2l_ctc_beam_lex_mt_workspace_size)(B, T, N, o.beamSize,
+                                                                                                        o.beamSizeToken) + 256);
+      if (trans)
+        w2l::w2lCheck(w2l_asg_beam_search_lex_mt(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
+                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                                 o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
+                                                 r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
+                                                 r.words.device<int>(), r.wordCounts.device<int>(), wsm.get(), S(), mtSil, o.silScore),
+                      "asg many-token beam search with lexicon");
+      else
+        w2l::w2lCheck(w2l_ctc_beam_search_lex_mt(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
+                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                                 o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
+                                                 r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
+                                                 r.words.device<int>(), r.wordCounts.device<int>(), wsm.get(), S(), mtSil, o.silScore),
+                      "ctc many-token beam search with lexicon");
+      af::sync();  // wsm is released at return
       return r;
     }
     if (useSil) {
@@ -1713,6 +1739,16 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
       throw std::invalid_argument("beamSearch: lmWeight, classScore and eosScore need lm");
     if (trans) {   // the lexicon-free ASG search is one entry point: a null LM means none
       af::array lms(af::dim4(o.nbest, B));
+      if (o.manyTokens) {
+        auto wsm = devAlloc(w2l_asg_beam_mt_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+        w2l::w2lCheck(w2l_asg_beam_search_mt(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
+                                             o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, nullptr, 0, 0.f, nullptr, 0.f,
+                                             r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
+                                             lms.device<float>(), wsm.get(), S(), mtSil, o.silScore),
+                      "asg many-token beam search");
+        af::sync();  // wsm is released at return
+        return r;
+      }
       if (useSil) {
         auto wss = devAlloc(w2l_asg_beam_sil_workspace_size(family, B, T, N, o.beamSize, o.beamSizeToken) + 256);
         w2l::w2lCheck(w2l_asg_beam_search_sil(family, B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
@@ -1738,6 +1774,25 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
     if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != tokens))
       throw std::invalid_argument("beamSearch: classScore must be f32 with one entry per token class");
     r.lmScores = af::array(af::dim4(o.nbest, B));
+    if (o.manyTokens) {
+      auto wsm = devAlloc((trans ? w2l_asg_beam_mt_workspace_size : w2l_ctc_beam_lm_mt_workspace_size)(B, T, N, o.beamSize,
+                                                                                                   o.beamSizeToken) + 256);
+      const float* cs = o.classScore.isempty() ? nullptr : o.classScore.device<float>();
+      if (trans)
+        w2l::w2lCheck(w2l_asg_beam_search_mt(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
+                                             o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                             o.lmWeight, cs, o.eosScore, r.labels.device<int>(), r.lengths.device<int>(),
+                                             r.scores.device<float>(), r.lmScores.device<float>(), wsm.get(), S(), mtSil, o.silScore),
+                      "asg many-token beam search with LM");
+      else
+        w2l::w2lCheck(w2l_ctc_beam_search_lm_mt(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
+                                                o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
+                                                o.lmWeight, cs, o.eosScore, r.labels.device<int>(), r.lengths.device<int>(),
+                                                r.scores.device<float>(), r.lmScores.device<float>(), wsm.get(), S(), mtSil, o.silScore),
+                      "ctc many-token beam search with LM");
+      af::sync();  // wsm is released at return
+      return r;
+    }
     if (useSil) {
       auto wss = devAlloc((trans ? w2l_asg_beam_sil_workspace_size : w2l_ctc_beam_lm_sil_workspace_size)(family, B, T, N, o.beamSize,
                                                                                                      o.beamSizeToken) + 256);
@@ -1776,6 +1831,15 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
                                            r.lmScores.device<float>(), wsl.get(), S()),
                     "ctc beam search with LM");
     af::sync();  // wsl is released at return
+    return r;
+  }
+  if (o.manyTokens) {   // the LM-free CTC search's many-token twin
+    auto wsm = devAlloc(w2l_ctc_beam_mt_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
+    w2l::w2lCheck(w2l_ctc_beam_search_mt(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold,
+                                         o.logAdd, normalize, o.nbest, Lmax, r.labels.device<int>(), r.lengths.device<int>(),
+                                         r.scores.device<float>(), wsm.get(), S(), mtSil, o.silScore),
+                  "ctc many-token beam search");
+    af::sync();  // wsm is released at return
     return r;
   }
   if (useSil) {   // the LM-free CTC search with a silence score
