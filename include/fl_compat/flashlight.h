@@ -304,6 +304,79 @@ class FL_COMPAT_API Sequential : public Container {
   int inputFeatures_ = 0;
 };
 
+// fl::Residual as the arch grammar builds it (cpc/SequentialBuilder.cpp:525-599; the class itself is un-vendored): layers in
+// order, shortcuts between them, a scale where a shortcut lands.  Like every layer object it IS its arch lines -- here several:
+//   RES <layers> <shortcuts> 1 / the layers' lines / SKIP <from> <to> [scale]   or   SKIPL <from> <to> <n> [scale] + n projection lines
+// -- and runs as part of the fl::Sequential it is added to.  Layer indices count from 1; `from` = 0 is the block's input and
+// `to` = layers + 1 its output.  What the pipeline builds is y = scale * (f(x) + p(x)), one shortcut from the input to the output
+// (DESIGN 3.29): any other from / to, a second shortcut or a block without one is refused with std::invalid_argument when the
+// Sequential plans (params() / forward()), as for an arch file, and so is an output of f that differs from the shortcut's in
+// shape or layout.  add() takes layer objects only (no nested fl::Residual); a projection is one layer object or an
+// fl::Sequential of them.
+class Residual : public ArchLayer {
+ public:
+  Residual() : ArchLayer("") { compose(); }
+  void add(std::shared_ptr<Module> m) {
+    auto* l = dynamic_cast<ArchLayer*>(m.get());
+    if (!l || dynamic_cast<Residual*>(l)) throw std::invalid_argument("fl_compat: fl::Residual::add takes layer objects (and no nested fl::Residual)");
+    layers_.push_back(l->archLine());
+    kept_.push_back(std::move(m));
+    compose();
+  }
+  template <class T, class = typename std::enable_if<std::is_base_of<Module, T>::value>::type>
+  void add(const T& layer) { add(std::static_pointer_cast<Module>(std::make_shared<T>(layer))); }
+  void addShortcut(int fromLayer, int toLayer) { shortcuts_.push_back({fromLayer, toLayer, false, 0.f, {}}); compose(); }
+  void addShortcut(int fromLayer, int toLayer, std::shared_ptr<Module> projection) {
+    Shortcut s{fromLayer, toLayer, false, 0.f, {}};
+    s.linear = true;
+    if (auto* l = dynamic_cast<ArchLayer*>(projection.get())) {
+      if (dynamic_cast<Residual*>(l)) throw std::invalid_argument("fl_compat: the projection of an fl::Residual shortcut cannot be an fl::Residual");
+      s.projection.push_back(l->archLine());
+    } else if (auto* c = dynamic_cast<Container*>(projection.get())) {
+      for (auto& m : c->modules()) {
+        auto* l2 = dynamic_cast<ArchLayer*>(m.get());
+        if (!l2 || dynamic_cast<Residual*>(l2)) throw std::invalid_argument("fl_compat: the projection of an fl::Residual shortcut is made of layer objects");
+        s.projection.push_back(l2->archLine());
+      }
+    } else {
+      throw std::invalid_argument("fl_compat: the projection of an fl::Residual shortcut is a layer object or an fl::Sequential of them");
+    }
+    kept_.push_back(std::move(projection));
+    shortcuts_.push_back(std::move(s));
+    compose();
+  }
+  template <class T, class = typename std::enable_if<std::is_base_of<Module, T>::value>::type>
+  void addShortcut(int fromLayer, int toLayer, const T& projection) { addShortcut(fromLayer, toLayer, std::static_pointer_cast<Module>(std::make_shared<T>(projection))); }
+  // the sum that enters layer `beforeLayer` (layers + 1: the block's output) is multiplied by `scale`: the arch grammar writes it
+  // on the shortcut line that lands there
+  void addScale(int beforeLayer, float scale) {
+    for (auto& s : shortcuts_)
+      if (s.to == beforeLayer && !s.scaled) { s.scaled = true; s.scale = scale; compose(); return; }
+    throw std::invalid_argument("fl_compat: fl::Residual::addScale(" + std::to_string(beforeLayer) + ", ...) needs a shortcut that lands there: add the shortcut first");
+  }
+  std::string prettyString() const override {
+    std::string s = "Residual [";
+    for (char ch : line_) { if (ch == '\n') s += " | "; else s += ch; }
+    return s + "]";
+  }
+
+ private:
+  struct Shortcut { int from, to; bool scaled; float scale; std::vector<std::string> projection; bool linear = false; };
+  void compose() {
+    line_ = "RES " + std::to_string(layers_.size()) + " " + std::to_string(shortcuts_.size()) + " 1";
+    for (auto& l : layers_) line_ += "\n" + l;
+    for (auto& s : shortcuts_) {
+      std::string k = s.linear ? join("SKIPL", {(double)s.from, (double)s.to, (double)s.projection.size()}) : join("SKIP", {(double)s.from, (double)s.to});
+      if (s.scaled) k += join("", {(double)s.scale});
+      line_ += "\n" + k;
+      for (auto& p : s.projection) line_ += "\n" + p;
+    }
+  }
+  std::vector<std::string> layers_;
+  std::vector<Shortcut> shortcuts_;
+  std::vector<std::shared_ptr<Module>> kept_;
+};
+
 // fl::SpecAugment as the Trainer instantiates it from --saug_start_update (recipes/slimIPL/src/Train.cpp:1026-1048, applied
 // at :1453-1461): frequency / time masking with zeros on the features (T, NFEAT, 1, B); identity in eval mode.  Same kernel as
 // the SAUG arch token (w2l_specaugment_inplace; one mask set per batch).  Time warping (tWarpW) is not applied by the

@@ -948,6 +948,16 @@ int w2l_pool_time_forward(const float* x, float* y, int B, int T, int F, int w, 
 int w2l_pool_time_backward(const float* x, const float* dy, float* dx, int B, int T, int F, int w, int stride,
                            w2l_stream_t stream);
 int w2l_axpy(float* y, const float* x, size_t n, float alpha, w2l_stream_t stream);
+/* The join of a residual block (arch tokens RES / SKIP / SKIPL; [UNVENDORED] fl::Residual: this comment is the contract).
+ * forward: y[i] = scale * (a[i] + b[i]) -- one fp32 add, then one fp32 multiply, no FMA --, then with relu != 0 the positive part
+ * (-0 and NaN become +0).  backward: g[i] = scale * dy[i], and with relu != 0 g[i] = 0 where y[i] <= 0 (y: forward's result; it is
+ * read only with relu).  The gradient is the same for both operands: the shortcut's share is added with w2l_axpy(dx, g, n, 1).
+ * One launch over n floats, two reads and one write each; float4 where the three pointers share their phase against 16 bytes (a
+ * scalar head up to the first aligned element, a scalar tail), element by element where they do not.  y may be exactly a or
+ * exactly b, g may be exactly dy; any other overlap is the caller's error.  W2L_EINVAL, before any launch: a non-finite scale; a
+ * null pointer with n > 0.  n == 0 launches nothing. */
+int w2l_residual_join_forward(float* y, const float* a, const float* b, size_t n, float scale, int relu, w2l_stream_t stream);
+int w2l_residual_join_backward(float* g, const float* dy, const float* y, size_t n, float scale, int relu, w2l_stream_t stream);
 int w2l_fill(float* y, size_t n, float v, w2l_stream_t stream);
 /* ema[i] = (float)decay * ema[i] + (float)(1 - decay) * p[i], fp32, ONE launch over a flat parameter arena: the averaged
  * "teacher" network of slimIPL (--slimIPL_ema, recipes/slimIPL/src/Train.cpp:1819-1832: one expression per parameter there).
@@ -1126,6 +1136,13 @@ int w2l_trainer_set_mixed_precision_convs(void* h, int on);
  * w2l_profile_enable(1) is in force (the per-launch brackets time one kernel at a time).  W2L_EINVAL: null handle.
  * Host-only, takes effect at the next backward; like every call on one handle, not concurrently with a step of it. */
 int w2l_trainer_set_weight_grad_stream(void* h, int on);
+/* The gradient of the network's INPUT, which training has no use for: off by default, and then no layer in front of the first one
+ * with parameters computes a data gradient.  On: every backward from the next one on runs them all and leaves the input's gradient
+ * in the activation arena, frame-major [B][T][NFEAT] (the input itself arrives time-fastest, [B][NFEAT][T]);
+ * w2l_trainer_input_gradient hands out the device pointer, valid until the next pass or plan (null before the first such
+ * backward).  Parameter gradients are the same bits either way.  W2L_EINVAL: null handle / null result.  Host-only. */
+int w2l_trainer_set_input_gradient(void* h, int on);
+int w2l_trainer_input_gradient(void* h, const float** dInput);
 /* slimIPL's dynamic dropout (--slimIPL_dyn_dropout, recipes/slimIPL/src/Train.cpp:1141-1168 with the recipe plugin's
  * 100h_supervised_slimipl.cpp:41-58): the probabilities the `TR` layers -- and only they -- use from the next forward on.  A
  * negative value restores that layer's arch value.  No new plan: a trainer with the override set computes, bit for bit, what a

@@ -250,6 +250,8 @@ class _SIGS:
     w2l_pool_time_forward = (_i, [_p, _p, _i, _i, _i, _i, _i, _p])
     w2l_pool_time_backward = (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p])
     w2l_axpy = (_i, [_p, _p, _sz, _f, _p])
+    w2l_residual_join_forward = (_i, [_p, _p, _p, _sz, _f, _i, _p])
+    w2l_residual_join_backward = (_i, [_p, _p, _p, _sz, _f, _i, _p])
     w2l_transpose = (_i, [_p, _p, _i, _i, _i, _p])
     w2l_glu_forward = (_i, [_p, _p, _sz, _i, _p])
     w2l_glu_backward = (_i, [_p, _p, _p, _sz, _i, _p])

@@ -8,6 +8,8 @@
 // :358-377, :423-428, :388-394, :467-473, :106-119); TDS data flow:
 // recipes/streaming_convnets/inference/inference/module/nn/TDSBlock.cpp:58-70.
 // All kernels are float4-vectorised grid-stride loops (coalesced 16 B/lane).
+#include <cmath>
+
 #include "common.hpp"
 #include "gemm.hpp"  // sk_scratch: the shared per-stream scratch (sumsq partials)
 
@@ -678,6 +680,61 @@ __global__ __launch_bounds__(kEwThreads) void axpy_k(float* __restrict__ y, cons
   }
   for (size_t e = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x)
     y[e] += alpha * x[e];
+}
+
+// The join of a residual block (arch tokens RES / SKIP / SKIPL, host/net.cpp ResidualLayer): y = scale * (a + b), then max(., 0)
+// with `relu`.  One fp32 add, then one fp32 multiply (the file is built with -ffp-contract=off, and a sum times a constant has no
+// FMA form anyway).  Two reads and one write per element, no LDS, no atomics.  Elements [0, head) and [head + 4 n4, n) go one by
+// one, the n4 float4 from `head` on as vectors (adam_k's split: the launcher picks head and n4 so that all three arrays are
+// 16-byte aligned there, n4 = 0 when their phases differ).  y may be a or b exactly: every element is read before it is written,
+// by the thread that writes it -- so no __restrict__ here.
+__global__ __launch_bounds__(kEwThreads) void residual_join_fwd_k(float* y, const float* a, const float* b, size_t n, size_t head, size_t n4,
+                                                                 float scale, int relu) {
+  auto one = [&](float av, float bv) {
+    float s = av + bv;
+    s = scale * s;
+    return relu ? (s > 0.f ? s : 0.f) : s;   // -0 becomes +0, as backward's y <= 0 reads it
+  };
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n4; i += stride) {
+    const size_t e = head + 4 * i;
+    const float4 av = *(const float4*)(a + e), bv = *(const float4*)(b + e);
+    float4 r;
+    r.x = one(av.x, bv.x); r.y = one(av.y, bv.y); r.z = one(av.z, bv.z); r.w = one(av.w, bv.w);
+    *(float4*)(y + e) = r;
+  }
+  const size_t tail = head + (n4 << 2);
+  for (size_t i = tid; i < n - (n4 << 2); i += stride) {
+    const size_t e = i < head ? i : tail + (i - head);
+    y[e] = one(a[e], b[e]);
+  }
+}
+
+// g = scale * dy, 0 where the joined output y <= 0 with `relu` (y is not read without it).  g may be dy exactly.
+__global__ __launch_bounds__(kEwThreads) void residual_join_bwd_k(float* g, const float* dy, const float* y, size_t n, size_t head, size_t n4,
+                                                                 float scale, int relu) {
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n4; i += stride) {
+    const size_t e = head + 4 * i;
+    const float4 d = *(const float4*)(dy + e);
+    float4 r;
+    r.x = scale * d.x; r.y = scale * d.y; r.z = scale * d.z; r.w = scale * d.w;
+    if (relu) {
+      const float4 yv = *(const float4*)(y + e);
+      if (yv.x <= 0.f) r.x = 0.f;
+      if (yv.y <= 0.f) r.y = 0.f;
+      if (yv.z <= 0.f) r.z = 0.f;
+      if (yv.w <= 0.f) r.w = 0.f;
+    }
+    *(float4*)(g + e) = r;
+  }
+  const size_t tail = head + (n4 << 2);
+  for (size_t i = tid; i < n - (n4 << 2); i += stride) {
+    const size_t e = i < head ? i : tail + (i - head);
+    float r = scale * dy[e];
+    if (relu && y[e] <= 0.f) r = 0.f;
+    g[e] = r;
+  }
 }
 
 // ema = d * ema + od * p over a flat parameter arena: the averaged "teacher" network of slimIPL
@@ -1380,6 +1437,39 @@ W2L_API int w2l_adam_step_guarded(float* p, const float* g, float* m, float* v, 
                      weightDecay, gradScale, maxGradNorm, guard, guard ? 1 : 0, (unsigned long long)step,
                      (const unsigned long long*)stepCount);
   if (stepCount) hipLaunchKernelGGL(adam_tick_k, dim3(1), dim3(1), 0, W2L_S, (unsigned long long*)stepCount, guard);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+// float4 only where all three arrays are 16-byte aligned at the same element (w2l_adam_step_guarded's rule)
+static inline void join_split(const void* p0, const void* p1, const void* p2, size_t n, size_t& head, size_t& n4) {
+  const uintptr_t phase = (uintptr_t)p0 & 15;
+  head = 0; n4 = 0;
+  if (((uintptr_t)p1 & 15) == phase && ((uintptr_t)p2 & 15) == phase && (phase & 3) == 0) {
+    head = ((16 - phase) & 15) >> 2;
+    if (head > n) head = n;
+    n4 = (n - head) >> 2;
+  }
+}
+
+W2L_API int w2l_residual_join_forward(float* y, const float* a, const float* b, size_t n, float scale, int relu, w2l_stream_t stream) {
+  if (!std::isfinite(scale)) return W2L_EINVAL;
+  if (!n) return W2L_OK;
+  if (!y || !a || !b) return W2L_EINVAL;
+  size_t head, n4;
+  join_split(y, a, b, n, head, n4);
+  hipLaunchKernelGGL(residual_join_fwd_k, dim3(ew_grid((n >> 2) + 1)), dim3(kEwThreads), 0, W2L_S, y, a, b, n, head, n4, scale, relu ? 1 : 0);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+W2L_API int w2l_residual_join_backward(float* g, const float* dy, const float* y, size_t n, float scale, int relu, w2l_stream_t stream) {
+  if (!std::isfinite(scale)) return W2L_EINVAL;
+  if (!n) return W2L_OK;
+  if (!g || !dy || !y) return W2L_EINVAL;   // y is read only with relu
+  size_t head, n4;
+  join_split(g, dy, relu ? (const void*)y : (const void*)g, n, head, n4);
+  hipLaunchKernelGGL(residual_join_bwd_k, dim3(ew_grid((n >> 2) + 1)), dim3(kEwThreads), 0, W2L_S, g, dy, y, n, head, n4, scale, relu ? 1 : 0);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }

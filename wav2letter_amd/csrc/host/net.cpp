@@ -1442,6 +1442,169 @@ class TransformerLayer : public Layer {
   }
 };
 
+// fl::Residual as the arch grammar builds it (tokens RES / SKIP / SKIPL, SequentialBuilder.cpp:525-599; the class itself is
+// un-vendored).  Every shortcut in the reference's arch files goes from the block's input to its output, and that is the one
+// form built here:
+//   y = scale * (f(x) + p(x))      f: the block's layers in order; p: the identity (SKIP) or the projection layers (SKIPL)
+// followed by a ReLU when an `R` line directly behind the block was folded into the join (w2l_residual_join_forward / _backward).
+// The block owns its layers; they plan on the net's planner, run under Sequential::forward's protocol and keep their own
+// backward passes, weight-gradient stream included.
+enum Touch { kKeeps, kPasses, kWrites };
+// what a layer's forward does to its input buffer / its backward to its output-gradient buffer: leaves it alone and writes a
+// buffer of its own, hands the pointer on untouched, or rewrites it in place
+static Touch touchesInput(Layer& l) {
+  if (dynamic_cast<ViewLayer*>(&l) || dynamic_cast<ReorderLayer*>(&l)) return kPasses;
+  if (dynamic_cast<ReLULayer*>(&l) || dynamic_cast<DropoutLayer*>(&l) || dynamic_cast<SpecAugmentLayer*>(&l)) return kWrites;
+  return kKeeps;
+}
+static Touch touchesGradient(Layer& l) {
+  if (dynamic_cast<ViewLayer*>(&l) || dynamic_cast<ReorderLayer*>(&l) || dynamic_cast<SpecAugmentLayer*>(&l)) return kPasses;
+  if (dynamic_cast<ReLULayer*>(&l) || dynamic_cast<DropoutLayer*>(&l)) return kWrites;
+  if (auto* c = dynamic_cast<Conv2DLayer*>(&l)) return c->fuseRelu ? kWrites : kKeeps;
+  if (auto* li = dynamic_cast<LinearLayer*>(&l)) return li->fuseRelu ? kWrites : kKeeps;
+  return kKeeps;
+}
+static bool sameAct(const Act& a, const Act& b) {
+  if (a.B != b.B || a.T != b.T || a.F != b.F) return false;
+  for (int i = 0; i < 4; ++i) {
+    // (size-1 factors carry no layout)
+    std::vector<Factor> fa, fb;
+    for (auto& f : a.d[i].f) if (f.size != 1) fa.push_back(f);
+    for (auto& f : b.d[i].f) if (f.size != 1) fb.push_back(f);
+    if (fa.size() != fb.size()) return false;
+    for (size_t k = 0; k < fa.size(); ++k)
+      if (fa[k].size != fb[k].size || fa[k].stride != fb[k].stride || fa[k].kind != fb[k].kind) return false;
+  }
+  return true;
+}
+
+class ResidualLayer : public Layer {
+ public:
+  std::vector<std::shared_ptr<Layer>> f, proj;   // the block's layers; the projection of a SKIPL shortcut (empty: SKIP, the identity)
+  size_t projAt = 0;          // the projection registers its parameters in front of f[projAt]: the place of the SKIPL line
+  float scale = 1.f;
+  bool relu = false;          // an `R` line right behind the block, folded into the join
+  std::string skipLine;
+  size_t nIn = 0, nOut = 0;
+  size_t yOff = 0, gOff = 0, gsOff = 0, xsOff = 0;
+  bool copyX = false, splitG = false;
+
+  std::string name() const override { return "Residual"; }
+  int claimRngStreams(int first) override {
+    rngStream = first;
+    int s = first;
+    for (auto& l : f) s += l->claimRngStreams(s);
+    for (auto& l : proj) s += l->claimRngStreams(s);
+    return std::max(s - first, 4);
+  }
+  void registerParams(std::vector<ParamInfo>& t) override {
+    for (size_t i = 0; i <= f.size(); ++i) {
+      if (i == projAt) for (auto& l : proj) l->registerParams(t);
+      if (i < f.size()) f[i]->registerParams(t);
+    }
+  }
+  void setTransformerDropout(double pDropout, double pLayerDrop) override {
+    for (auto& l : f) l->setTransformerDropout(pDropout, pLayerDrop);
+    for (auto& l : proj) l->setTransformerDropout(pDropout, pLayerDrop);
+  }
+  void setStreamMode(bool on) override {
+    Layer::setStreamMode(on);
+    for (auto& l : f) l->setStreamMode(on);
+    for (auto& l : proj) l->setStreamMode(on);
+  }
+  // does the chain rewrite the buffer it is handed (its input in forward, its output gradient in backward) before a layer that
+  // writes a buffer of its own takes over?  owns: such a layer exists at all
+  static bool chainWrites(const std::vector<std::shared_ptr<Layer>>& ls, bool backward, bool& owns) {
+    owns = false;
+    for (size_t k = 0; k < ls.size(); ++k) {
+      Layer& l = *ls[backward ? ls.size() - 1 - k : k];
+      const Touch t = backward ? touchesGradient(l) : touchesInput(l);
+      if (t == kWrites) { owns = true; return true; }   // (in place: the buffer it hands on is the one it was given)
+      if (t == kKeeps) { owns = true; return false; }
+    }
+    return false;
+  }
+  Act plan(const Act& in, Planner& pl) override {
+    Act a = in, s = in;
+    for (auto& l : f) a = l->plan(a, pl);
+    for (auto& l : proj) s = l->plan(s, pl);
+    if (!sameAct(a, s))
+      throw std::invalid_argument("RES: the block's output " + a.str() + " and its shortcut " + s.str() + " differ in shape or layout: '" +
+                                  skipLine + "' of '" + archLine + "'");
+    nIn = in.numel(); nOut = a.numel();
+    yOff = pl.alloc(nOut);
+    gOff = pl.alloc(nOut);
+    // The shortcut reads the block's input after f has run, and f's layers keep pointers into it for their backward passes: a path
+    // whose first layers rewrite their input in place (R, DO, SAUG) must not share the buffer with the other one -- the shortcut
+    // then works on a copy.  Likewise in backward: g is the output gradient of BOTH paths, and a path whose last layers rewrite it
+    // in place (R, DO, a folded R) gets a second copy of it, gs.  So does an f without a layer that writes a data gradient of its
+    // own, whose "dx" would be g itself -- the sum below never goes into g.  The ResNet recipes need neither.
+    bool fOwns, pOwns, fOwnsB, pOwnsB;
+    const bool fw = chainWrites(f, false, fOwns), pw = chainWrites(proj, false, pOwns);
+    const bool fwB = chainWrites(f, true, fOwnsB), pwB = chainWrites(proj, true, pOwnsB);
+    copyX = fw || pw;
+    splitG = fwB || pwB || !fOwnsB;
+    xsOff = copyX ? pl.alloc(nIn) : 0;
+    gsOff = splitG ? pl.alloc(nOut) : 0;
+    return a;
+  }
+  // Sequential::forward's protocol over a chain: the note about bf16 images of the activation handed on (Ctx::imgOf)
+  static const float* runChain(std::vector<std::shared_ptr<Layer>>& ls, Ctx& c, float* arena, const float* cur) {
+    for (auto& l : ls) {
+      float* y = nullptr;
+      const float* noteBefore = c.imgOf;
+      l->forward(c, arena, cur, y);
+      if (c.imgOf == noteBefore && !l->passesInputThrough(c)) c.imgOf = nullptr;
+      if (c.imgOf != y) c.imgOf = nullptr;
+      cur = y;
+    }
+    return cur;
+  }
+  void forward(Ctx& c, float* arena, const float* x, float*& y) override {
+    const Ctx entry = c;   // the note about x as the block met it: the projection starts from it too
+    const float* xs = x;
+    if (copyX) {
+      hipCheck(hipMemcpyAsync(arena + xsOff, x, nIn * sizeof(float), hipMemcpyDeviceToDevice, c.stream), "residual input copy");
+      xs = arena + xsOff;
+    }
+    const float* fx = runChain(f, c, arena, x);
+    if (xs == x) { c.imgOf = entry.imgOf; c.imgRowsOff = entry.imgRowsOff; c.imgTransOff = entry.imgTransOff; c.imgRows = entry.imgRows; c.imgCols = entry.imgCols; }
+    else c.imgOf = nullptr;
+    const float* px = runChain(proj, c, arena, xs);
+    y = arena + yOff;
+    w2lCheck(w2l_residual_join_forward(y, fx, px, nOut, scale, relu ? 1 : 0, c.stream), "residual join");
+    c.imgOf = nullptr;   // nobody has written images of y
+  }
+  static float* backChain(std::vector<std::shared_ptr<Layer>>& ls, Ctx& c, float* arena, float* dy, bool needFirstDx) {
+    float* cur = dy;
+    for (size_t ii = ls.size(); ii-- > 0;) {
+      float* dx = nullptr;
+      const bool need = ii > 0 || needFirstDx;
+      ls[ii]->backward(c, arena, cur, dx, need);
+      if (!need) return nullptr;
+      cur = dx;
+    }
+    return cur;
+  }
+  void backward(Ctx& c, float* arena, const float* dy, float*& dx, bool needDx) override {
+    // g into a buffer of the block's own: it is the dy operand of the last layers' filter / weight gradients, which run on the
+    // weight-gradient stream until Sequential::backward joins it -- nothing below writes g
+    float *g = arena + gOff, *gs = g;
+    const float* yv = arena + yOff;
+    w2lCheck(w2l_residual_join_backward(g, dy, yv, nOut, scale, relu ? 1 : 0, c.stream), "residual join bwd");
+    if (splitG) {
+      gs = arena + gsOff;
+      w2lCheck(w2l_residual_join_backward(gs, dy, yv, nOut, scale, relu ? 1 : 0, c.stream), "residual join bwd (shortcut)");
+    }
+    float* dxF = backChain(f, c, arena, g, needDx);
+    float* dxP = backChain(proj, c, arena, gs, needDx);
+    if (!needDx) return;
+    // the shortcut's share goes into f's data gradient
+    w2lCheck(w2l_axpy(dxF, dxP, nIn, 1.0f, c.stream), "residual shortcut gradient");
+    dx = dxF;
+  }
+};
+
 }  // namespace
 
 // ============================================================================ Sequential
@@ -1459,8 +1622,7 @@ void Sequential::finalize() {
   int stream = 1;
   std::vector<size_t> firstIdx;
   for (auto& l : layers_) {
-    l->rngStream = stream;
-    stream += 4;
+    stream += l->claimRngStreams(stream);
     firstIdx.push_back(params_.size());
     l->registerParams(params_);
   }
@@ -1507,6 +1669,7 @@ size_t Sequential::plan(int B, int T, int nFeat) {
   out_ = a;
   requireEmissionLayout(out_);
   ys_.assign(layers_.size(), nullptr);
+  inputGrad_ = nullptr;
   convScratchElems_ = pl.convScratch();
   convScratchOff_ = convScratchElems_ ? pl.allocBf16(convScratchElems_) : 0;
   return pl.used();
@@ -1624,12 +1787,13 @@ void Sequential::backward(Ctx& c, float* arena, const float* dOut) {
   size_t nb = bOff_.size();  // buckets [nb, ...) already signalled
   for (size_t ii = layers_.size(); ii-- > 0;) {
     float* dx = nullptr;
-    bool needDx = ii > firstParam;
+    bool needDx = ii > firstParam || wantInputGrad_;
     layers_[ii]->backward(c, arena, dy, dx, needDx);
     for (; nb > 0 && bOff_[nb - 1] >= layerLo_[ii]; --nb) wg.recordBucket(bEv_[nb - 1]);
     if (!needDx) break;
     dy = dx;
   }
+  inputGrad_ = wantInputGrad_ ? dy : nullptr;
   for (; nb > 0; --nb) wg.recordBucket(bEv_[nb - 1]);
   // everything the caller enqueues next -- the gradient scale, clip and optimizer, the next forward -- is ordered behind both streams
   wg.join();
@@ -1822,22 +1986,36 @@ static std::shared_ptr<Layer> buildOne(const LayerSpec& s, const LayerSpec* wnPa
   return unsupported();
 }
 
-std::shared_ptr<Sequential> buildSequentialFromText(const std::string& text, int64_t nFeat, int64_t nLabel, bool dryPlan) {
-  auto specs = parseArch(text, nFeat, nLabel);
-  auto net = std::make_shared<Sequential>();
+static size_t buildResidual(const std::vector<LayerSpec>& specs, size_t at, std::vector<std::shared_ptr<Layer>>& out);
+
+// arch lines -> layers.  A PD line folds into the convolution behind it; an R line folds into the Conv2D / Linear / residual
+// block in front of it.  srcOf (optional): per layer, the index of the line that built it.  inBlock: the lines of a RES block
+// (or of a projection), where `where` names the block for the error texts.
+static void buildLayers(const std::vector<LayerSpec>& specs, bool inBlock, const std::string& where, std::vector<std::shared_ptr<Layer>>& out,
+                        std::vector<size_t>* srcOf = nullptr) {
   int padL = 0, padR = 0;
   bool pendingPad = false;
   std::shared_ptr<Layer> last;
-  for (auto& s : specs) {
+  for (size_t i = 0; i < specs.size(); ++i) {
+    const LayerSpec& s = specs[i];
     if (s.tok == "PD") {
       // only zero padding of the time axis (dim 0), folded into the next convolution
       if (toD(s.args[0]) != 0.0) throw std::invalid_argument("PD: only zero padding is supported: " + s.line);
-      for (size_t i = 3; i < s.args.size(); ++i)
-        if (toI(s.args[i]) != 0) throw std::invalid_argument("PD: only the time axis can be padded: " + s.line);
+      for (size_t k = 3; k < s.args.size(); ++k)
+        if (toI(s.args[k]) != 0) throw std::invalid_argument("PD: only the time axis can be padded: " + s.line);
       padL = toI(s.args[1]); padR = toI(s.args[2]);
       pendingPad = true;
       continue;
     }
+    if (s.tok == "RES") {
+      if (inBlock) throw std::invalid_argument("RES: a residual block inside a residual block is not built: '" + s.line + "' in " + where);
+      if (pendingPad) throw std::invalid_argument("PD must be followed by an unpadded convolution: " + s.line);
+      i += buildResidual(specs, i, out);
+      last = out.back();
+      continue;
+    }
+    if ((s.tok == "SKIP" || s.tok == "SKIPL") && !inBlock)
+      throw std::invalid_argument("'" + s.line + "' (line " + std::to_string(s.lineNo) + ") stands outside the lines a RES block announces");
     auto l = buildOne(s, nullptr);
     l->archLine = s.line;
     if (pendingPad) {
@@ -1846,15 +2024,94 @@ std::shared_ptr<Sequential> buildSequentialFromText(const std::string& text, int
       c->extraPadL = padL; c->extraPadR = padR;
       pendingPad = false;
     }
-    // peephole: Conv/Linear + ReLU -> fused epilogue
+    // peephole: Conv/Linear + ReLU -> fused epilogue; residual block + ReLU -> the ReLU of its join
     if (s.tok == "R" && last) {
       if (auto c = std::dynamic_pointer_cast<Conv2DLayer>(last)) { if (!c->fuseRelu) { c->fuseRelu = true; continue; } }
       if (auto li = std::dynamic_pointer_cast<LinearLayer>(last)) { if (!li->fuseRelu) { li->fuseRelu = true; continue; } }
+      if (auto r = std::dynamic_pointer_cast<ResidualLayer>(last)) { if (!r->relu) { r->relu = true; continue; } }
     }
-    net->add(l);
+    out.push_back(l);
+    if (srcOf) srcOf->push_back(i);
     last = l;
   }
-  if (pendingPad) throw std::invalid_argument("dangling PD at the end of the architecture");
+  if (pendingPad) throw std::invalid_argument(inBlock ? "dangling PD at the end of " + where : std::string("dangling PD at the end of the architecture"));
+}
+
+// `RES numLayers numSkips [numBlocks]` at specs[at] (SequentialBuilder.cpp:525-599): the next numLayers + numSkips ARCH LINES are the
+// block's, plus the projection lines a `SKIPL from to nProj [scale]` announces; PD and R lines count as lines and fold afterwards.
+// numBlocks > 1 builds the same lines again, each block with parameters of its own.  Appends the block(s) to `out`; returns the
+// number of lines behind the RES line that belong to it (the reference's numLinesParsed).
+static size_t buildResidual(const std::vector<LayerSpec>& specs, size_t at, std::vector<std::shared_ptr<Layer>>& out) {
+  const LayerSpec& r = specs[at];
+  const std::string where = "'" + r.line + "' (line " + std::to_string(r.lineNo) + ")";
+  const int numLayers = toI(r.args[0]), numSkips = toI(r.args[1]);
+  const int numBlocks = r.args.size() == 3 ? toI(r.args[2]) : 1;   // (as the reference: a fifth field switches the count off)
+  if (numBlocks <= 0) throw std::invalid_argument("Invalid number of residual blocks: " + std::to_string(numBlocks) + " in " + where);
+  if (numLayers < 0 || numSkips < 0) throw std::invalid_argument("Failed parsing - " + r.line);
+  std::vector<LayerSpec> fLines, pLines;
+  const LayerSpec* skip = nullptr;
+  size_t skipAt = 0, numProj = 0;
+  int shortcuts = 0;
+  for (int k = 1; k <= numLayers + numSkips; ++k) {
+    const size_t idx = at + (size_t)k + numProj;
+    if (idx >= specs.size()) throw std::invalid_argument("Failed parsing Residual block: the file ends inside " + where);
+    const LayerSpec& s = specs[idx];
+    if (s.tok == "RES") throw std::invalid_argument("RES: a residual block inside a residual block is not built: '" + s.line + "' in " + where);
+    if (s.tok == "SKIP" || s.tok == "SKIPL") {
+      if (++shortcuts > 1)
+        throw std::invalid_argument("RES: more than one shortcut in a block is not built: '" + s.line + "' in " + where);
+      skip = &s; skipAt = fLines.size();
+      if (s.tok == "SKIPL") {
+        const int nProj = toI(s.args[2]);
+        if (nProj < 0) throw std::invalid_argument("Failed parsing - " + s.line);
+        for (int j = 1; j <= nProj; ++j) {
+          if (idx + (size_t)j >= specs.size()) throw std::invalid_argument("Failed parsing Residual block: the file ends inside the projection of " + where);
+          const LayerSpec& pj = specs[idx + (size_t)j];
+          if (pj.tok == "SKIP" || pj.tok == "SKIPL")
+            throw std::invalid_argument("RES: a shortcut line among the projection layers: '" + pj.line + "' in " + where);
+          pLines.push_back(pj);
+        }
+        numProj += (size_t)nProj;
+      }
+    } else {
+      fLines.push_back(s);
+    }
+  }
+  if (!skip) throw std::invalid_argument("RES: a block without a shortcut is not built: " + where);
+  if (shortcuts != numSkips)
+    throw std::invalid_argument("RES: " + where + " announces " + std::to_string(numSkips) + " shortcut lines, its lines hold " + std::to_string(shortcuts));
+  const int from = toI(skip->args[0]), to = toI(skip->args[1]);
+  const bool linear = skip->tok == "SKIPL";
+  if (from != 0)
+    throw std::invalid_argument("RES: only a shortcut from the block's input (from = 0) is built: '" + skip->line + "' in " + where);
+  if (to != numLayers + 1)
+    throw std::invalid_argument("RES: only a shortcut to the block's output (to = numLayers + 1 = " + std::to_string(numLayers + 1) +
+                                ") is built: '" + skip->line + "' in " + where);
+  const size_t scaleArg = linear ? 3 : 2;
+  const float scale = skip->args.size() > scaleArg ? std::stof(skip->args[scaleArg]) : 1.f;
+  if (!std::isfinite(scale)) throw std::invalid_argument("RES: the scale must be finite: '" + skip->line + "' in " + where);
+  for (int n = 0; n < numBlocks; ++n) {
+    auto blk = std::make_shared<ResidualLayer>();
+    blk->archLine = r.line;
+    blk->skipLine = skip->line;
+    blk->scale = scale;
+    std::vector<size_t> srcOf;
+    buildLayers(fLines, true, where, blk->f, &srcOf);
+    buildLayers(pLines, true, "the projection of " + where, blk->proj);
+    blk->projAt = blk->f.size();
+    for (size_t i = 0; i < srcOf.size(); ++i)
+      if (srcOf[i] >= skipAt) { blk->projAt = i; break; }
+    out.push_back(blk);
+  }
+  return (size_t)(numLayers + numSkips) + numProj;
+}
+
+std::shared_ptr<Sequential> buildSequentialFromText(const std::string& text, int64_t nFeat, int64_t nLabel, bool dryPlan) {
+  auto specs = parseArch(text, nFeat, nLabel);
+  auto net = std::make_shared<Sequential>();
+  std::vector<std::shared_ptr<Layer>> layers;
+  buildLayers(specs, false, "", layers);
+  for (auto& l : layers) net->add(l);
   net->finalize();
   // dry plan: validates shapes / layouts and fixes the Linear row permutations
   if (dryPlan) net->plan(1, 4096, (int)nFeat);

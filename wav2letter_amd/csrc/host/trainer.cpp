@@ -530,6 +530,20 @@ W2L_API int w2l_trainer_set_weight_grad_stream(void* h, int on) {
   return W2L_OK;
 }
 
+// the data gradient of the network's input, which a training step has no use for: off by default.  On: every backward from the
+// next one on leaves it in the activation arena, frame-major [B][T][NFEAT] (the input arrives time-fastest, [B][NFEAT][T]);
+// w2l_trainer_input_gradient hands out where (null before the first such backward).  The parameter gradients are the same either way.
+W2L_API int w2l_trainer_set_input_gradient(void* h, int on) {
+  if (!h) return W2L_EINVAL;
+  ((Trainer*)h)->net->setInputGradient(on != 0);
+  return W2L_OK;
+}
+W2L_API int w2l_trainer_input_gradient(void* h, const float** dInput) {
+  if (!h || !dInput) return W2L_EINVAL;
+  *dInput = ((Trainer*)h)->net->inputGradient();
+  return W2L_OK;
+}
+
 // second level of the mixed-precision mode: the wide time convolutions (H == 1, >= 32 channels: the conv_glu recipes, the
 // Transformer front end) on bf16 operands too, wherever w2l_conv_bf16_image_elems has a kernel.  It acts only while
 // w2l_trainer_set_mixed_precision is on.  The plan holds the layers' weight images and the image scratch: call before

@@ -153,11 +153,14 @@ class Layer {
   // slimIPL's dynamic dropout: only the Transformer block answers (negative: back to the arch line's value)
   virtual void setTransformerDropout(double pDropout, double pLayerDrop) { (void)pDropout; (void)pLayerDrop; }
   int rngStream = 0;  // distinct dropout stream per layer
+  // Sequential::finalize hands out the dropout streams: takes `first` and says how many it used (a layer has four to itself; a
+  // residual block passes them on to the layers it owns)
+  virtual int claimRngStreams(int first) { rngStream = first; return 4; }
   // chunked streaming forward: false (and why) when the layer cannot run on audio as it arrives
   virtual bool streamGeom(StreamGeom& g, std::string& why) const { (void)g; why = "the layer needs the whole utterance"; return false; }
   // stream mode: plan() takes its input as an assembled window -- no padding of its own, T' = (T - kw) / stride + 1 -- and a TDS
   // block reads its residual from Ctx::streamRes.  Set before plan(); only ever on a streaming session's own Sequential.
-  void setStreamMode(bool on) { streamMode_ = on; }
+  virtual void setStreamMode(bool on) { streamMode_ = on; }   // (virtual: a residual block forwards it to its layers)
   std::string archLine;   // the arch line that built the layer (a folded PD or R line is not named)
  protected:
   bool streamMode_ = false;
@@ -212,6 +215,11 @@ class Sequential {
   void setWeightGradStream(bool on) { wgOn_ = on; }
   bool weightGradStream() const { return wgOn_; }
 
+  // Off (default): nothing in front of the first layer with parameters gets a data gradient.  On: backward runs every layer's data
+  // gradient and inputGradient() is the gradient of the network's input, frame-major [B][T][nFeat] in the arena, until the next pass
+  void setInputGradient(bool on) { wantInputGrad_ = on; inputGrad_ = nullptr; }
+  const float* inputGradient() const { return inputGrad_; }
+
   void initParams(float* hostParams, uint64_t seed) const;            // Flashlight-style init, internal layout
   void importParam(size_t i, const float* ref, float* hostParams) const;  // reference layout -> internal
   void exportParam(size_t i, const float* hostArena, float* ref) const;   // internal -> reference layout
@@ -223,6 +231,8 @@ class Sequential {
   Act in_, out_;
   size_t inOff_ = 0;
   bool bf16Convs_ = false;
+  bool wantInputGrad_ = false;
+  const float* inputGrad_ = nullptr;
   size_t convScratchOff_ = 0, convScratchElems_ = 0;
   std::vector<size_t> dOff_;  // gradient buffer per layer boundary
   std::vector<Act> acts_;

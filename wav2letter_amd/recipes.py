@@ -8,6 +8,7 @@ recipes load unchanged:
   recipes/conv_glu/librispeech/network.arch, conv_glu/wsj/network.arch   (configs 4, 1)
   recipes/streaming_convnets/librispeech/am_500ms_future_context.arch    (config 3)
   recipes/sota/2019/am_arch/am_transformer_ctc.arch                      (config 5)
+  recipes/sota/2019/am_arch/am_resnet_ctc.arch, am_resnet_ctc_librivox.arch  (residual blocks: RES / SKIP)
 """
 
 
@@ -45,6 +46,62 @@ def transformer_ctc_arch():
         lines += [f"WN 3 C {cin} {cout} 3 1 -1", "GLU 2", "DO 0.2", "M 1 1 2 1"]
     lines += ["RO 2 0 3 1"] + ["TR 1024 4096 4 460 0.2 0.2"] * 24 + ["DO 0.2", "L 1024 NLABEL"]
     return "\n".join(lines) + "\n"
+
+
+def _resnet_ctc_lines(note, stages, tail):
+    """the sota/2019 ResNet-CTC topology: a strided front convolution, then per stage residual blocks of three k = 3 convolutions
+    (`RES 9 1 1` ... `SKIP 0 10 0.70711`, each followed by R / DO / LN), an optional widening convolution and an optional max-pool"""
+    def post(p):
+        return ["R", f"DO {p}", "LN 0 1 2"]
+    front = stages[0][2]
+    lines = ["SAUG 80 27 2 100 1.0 2", "V -1 1 NFEAT 0", "C NFEAT 1024 3 2 -1 1"] + post(front)
+    for c, blocks, p, widen, pool in stages:
+        for _ in range(blocks):
+            lines += [note, "RES 9 1 1"]
+            lines += ([f"C {c} {c} 3 1 -1 1"] + post(p)) * 2 + [f"C {c} {c} 3 1 -1 1", "SKIP 0 10 0.70711"] + post(p)
+        if widen:
+            lines += [f"C {c} {widen} 3 1 -1 1"] + post(p)
+        if pool:
+            lines += ["M 2 1 2 1"]
+    return "\n".join(lines + tail) + "\n"
+
+
+def resnet_ctc_arch():
+    """sota/2019 ResNet-CTC (am_resnet_ctc.arch): 12 residual blocks of three k = 3 convolutions over 1024 / 2048 / 2304 channels,
+    three max-pools, 306.3 M params"""
+    stages = [(1024, 3, "0.15", 0, True), (1024, 4, "0.15", 0, True), (1024, 1, "0.15", 2048, False), (2048, 2, "0.20", 2304, True),
+              (2304, 2, "0.25", 0, False)]
+    tail = ["C 2304 2304 3 1 -1 1", "R", "LN 0 1 2", "DO 0.25", "C 2304 NLABEL 1 1 -1 1", "RO 2 0 3 1"]
+    return _resnet_ctc_lines("# block1 kernel 5", stages, tail)
+
+
+def resnet_ctc_librivox_arch():
+    """sota/2019 ResNet-CTC for the LibriVox-scale model (am_resnet_ctc_librivox.arch): the same 12 blocks over 1024 / 2048 / 4096
+    channels and a 512-wide bottleneck in front of the output, 542.3 M params"""
+    stages = [(1024, 3, "0.05", 0, True), (1024, 4, "0.05", 0, True), (1024, 1, "0.05", 2048, False), (2048, 2, "0.10", 4096, True),
+              (4096, 2, "0.15", 0, False)]
+    tail = ["C 4096 4096 3 1 -1 1", "R", "DO 0.15", "LN 0 1 2", "C 4096 512 1 1 -1 1", "R", "DO 0.15", "LN 0 1 2", "C 512 NLABEL 1 1 -1 1",
+            "RO 2 0 3 1"]
+    return _resnet_ctc_lines("# block1 kernel 3", stages, tail)
+
+
+# recipes/sota/2019/librispeech/train_am_resnet_ctc.cfg:11-31
+RESNET_CTC_FLAGS = dict(criterion="ctc", lr=0.4, momentum=0.6, maxgradnorm=1.0, onorm="target", sqnorm=True, filterbanks=80, batchsize=4)
+
+
+def resnet_ctc_train_cfg():
+    """recipes/sota/2019/librispeech/train_am_resnet_ctc.cfg, regenerated (checked line for line against tests/golden/reference_recipes.json)"""
+    fl = [("runname", "am_resnet_ctc_librispeech"), ("rundir", "[...]"), ("archdir", "[...]"), ("arch", "am_arch/am_resnet_ctc.arch"),
+          ("tokensdir", "[MODEL_DST]/am"), ("tokens", "librispeech-train-all-unigram-10000.tokens"),
+          ("lexicon", "[MODEL_DST]/am/librispeech-train+dev-unigram-10000-nbest10.lexicon"),
+          ("train", "[DATA_DST]/lists/train-clean-100.lst,[DATA_DST]/lists/train-clean-360.lst,[DATA_DST]/lists/train-other-500.lst"),
+          ("valid", "dev-clean:[DATA_DST]/lists/dev-clean.lst,dev-other:[DATA_DST]/lists/dev-other.lst"),
+          ("criterion", "ctc"), ("mfsc", None), ("labelsmooth", "0.05"), ("wordseparator", "_"), ("usewordpiece", "true"),
+          ("sampletarget", "0.01"), ("lr", "0.4"), ("linseg", "0"), ("momentum", "0.6"), ("maxgradnorm", "1"), ("onorm", "target"),
+          ("sqnorm", None), ("nthread", "4"), ("batchsize", "4"), ("filterbanks", "80"), ("lrcosine", None), ("mintsz", "2"),
+          ("minisz", "200"), ("reportiters", "2000"), ("enable_distributed", None), ("lr_decay", "10000")]
+    return ("# Replace `[...]`, `[MODEL_DST]`, `[DATA_DST]`, with appropriate paths\n" +
+            "".join(f"--{k}\n" if v is None else f"--{k}={v}\n" for k, v in fl))
 
 
 # recipes/sota/2019/librispeech/train_am_transformer_ctc.cfg:11-41

@@ -48,6 +48,8 @@ def _lib_tr():
         L.w2l_trainer_set_mixed_precision.argtypes = [vp, i]
         L.w2l_trainer_set_mixed_precision_convs.argtypes = [vp, i]
         L.w2l_trainer_set_weight_grad_stream.argtypes = [vp, i]
+        L.w2l_trainer_set_input_gradient.argtypes = [vp, i]
+        L.w2l_trainer_input_gradient.argtypes = [vp, C.POINTER(vp)]
         L.w2l_trainer_set_optimizer.argtypes = [vp, i, i]
         L.w2l_trainer_set_adam.argtypes = [vp, f, f, f, f]
         L.w2l_trainer_adam_steps.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), vp]
@@ -373,6 +375,20 @@ class Trainer:
         """fp32 backward: the weight, bias and filter gradients on the network's own side stream, joined into the step's stream
         before forward_backward returns (on by default; same results either way, see w2l_trainer_set_weight_grad_stream)"""
         _check(self.L.w2l_trainer_set_weight_grad_stream(self.h, int(bool(on))), "weight-gradient stream")
+
+    def set_input_gradient(self, on=True):
+        """also compute the gradient of the network's input in every backward from the next one on (off by default: training has
+        no use for it); input_gradient() reads it"""
+        _check(self.L.w2l_trainer_set_input_gradient(self.h, int(bool(on))), "input gradient")
+
+    def input_gradient(self):
+        """the input's gradient of the last backward, a view [B][T][NFEAT] of the arena (frame-major; the input is [B][NFEAT][T])"""
+        ptr = C.c_void_p(0)
+        _check(self.L.w2l_trainer_input_gradient(self.h, C.byref(ptr)), "input gradient")
+        if not ptr.value:
+            raise _lib.W2LInvalidArgument("input_gradient: set_input_gradient() and a backward pass first")
+        off = (ptr.value - self.arena.data_ptr()) // 4
+        return self.arena[off:off + self.B * self.T * self.nfeat].view(self.B, self.T, self.nfeat)
 
     def set_optimizer(self, netoptim="sgd", critoptim="sgd", beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
         """--netoptim / --critoptim of the reference Trainer (Train.cpp:577-582): "sgd" (momentum) "adagrad", "adadelta" (rho 0.9, eps 1e-8:
