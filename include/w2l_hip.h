@@ -461,7 +461,7 @@ int w2l_asg_beam_search_lex_xl(int B, int T, int N, const float* input /*[B][T][
                                int* labels /*[B][M][Lmax]*/, int* lengths /*[B][M]*/, float* scores /*[B][M]*/,
                                float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
                                int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream);
-/* The five beam searches with a SILENCE SCORE (the reference's --silscore, older name --silweight; csrc/criterion_beam_sil.hpp,
+/* The five beam searches with a SILENCE SCORE (the reference's --silscore, older name --silweight; csrc/criterion_beam_entry.hpp,
  * DESIGN 3.26).  Each takes `family` first -- 0: the narrow search above, 1: its wide twin, 2: its xl twin --, then its sibling's
  * argument list, then silToken and silScore.  One rule covers all five searches in all three families:
  *   With silToken in range and silScore finite, the frame score of class silToken is replaced, AFTER THE FRAME TOKENS HAVE BEEN
@@ -522,7 +522,7 @@ int w2l_asg_beam_search_lex_sil(int family, int B, int T, int N, const float* in
                                 float* lmScores /*[B][M]*/, int maxWords, int* words /*[B][M][maxWords]*/,
                                 int* wordCounts /*[B][M]*/, void* workspace, w2l_stream_t stream, int silToken, float silScore);
 /* The MANY-TOKEN twins of the five beam searches (the reference's --beamsizetoken above 64: 100 in its word-piece recipes, 150;
- * csrc/criterion_beam_mt.hpp).  Each takes its xl twin's argument list, then silToken and silScore, and obeys the
+ * csrc/criterion_beam_xl.hpp).  Each takes its xl twin's argument list, then silToken and silScore, and obeys the
  * sibling's contract word for word -- the frame tokens are the K best non-blank classes by lp descending, class ascending; stay /
  * ext / merge / prune; the order total descending, rank ascending, stay before extension, k ascending, slot ascending; the
  * threshold line, the lexicon slots, the ASG rules, the end rule and the EOS term; the silence rule of the *_sil entry points
@@ -1249,6 +1249,49 @@ int w2l_stream_create_for_trainer_ex(void* trainer, int slots, int maxChunk, int
 int w2l_stream_query_ex(const char* archText, int nFeat, int nLabel, int slots, int maxChunk, int precision, int* maxOut,
                         size_t* stateBytes);
 int w2l_stream_refresh_weights(void* session);
+
+/* ---- one descriptor call for every whole-utterance beam search (csrc/criterion_beam_entry.hpp) ---------------------------
+ * THE CONTRACT is by reference to the named entry points above and to nothing else: w2l_beam_search is the call that
+ * (trans ? asg : ctc, kind, family) names, with that call's refusals in that call's order and that call's bytes in labels,
+ * lengths, scores, lmScores, words and wordCounts; w2l_beam_search_workspace_size is that call's size function.
+ *   family NARROW, WIDE, XL   the *_sil entry point with that family; without a score (silToken == -1 or silScore == 0) that
+ *                             is the plain sibling.  family MT: the *_mt entry point.
+ *   kind PLAIN   w2l_ctc_beam_search*, or w2l_asg_beam_search* with lm == NULL.   LM: w2l_ctc_beam_search_lm*, w2l_asg_beam_search*.
+ *        LEX     w2l_*_beam_search_lex*.   LEXTOK: w2l_*_beam_search_lextok; with family XL or MT W2L_EUNSUPPORTED after every
+ *                W2L_EINVAL, as family 2 is there, and a workspace size of 0.
+ * Checked first, W2L_EINVAL: desc == NULL or family or kind out of range (a size of 0); a field the chosen search does not take
+ * that is not NULL / 0, the rule of W2L_BEAM_PLAIN below -- PLAIN: lm, lmHasEos, lmWeight, classScore, eosScore (CTC: lmScores
+ * too); PLAIN and LM: lexicon, wordScore, maxWords, words, wordCounts; LEX and LEXTOK: classScore.  trans == NULL: CTC. */
+typedef enum { W2L_BEAM_NARROW = 0, W2L_BEAM_WIDE = 1, W2L_BEAM_XL = 2, W2L_BEAM_MT = 3 } w2l_beam_family;
+typedef enum { W2L_SEARCH_PLAIN = 0, W2L_SEARCH_LM = 1, W2L_SEARCH_LEX = 2, W2L_SEARCH_LEXTOK = 3 } w2l_beam_search_kind;
+typedef struct {
+  int family, kind;
+  int B, T, N;
+  const float* input;
+  const int* frames;
+  const float* trans;
+  int beam, beamToken;
+  float threshold;
+  int logAdd, normalize, nbest, maxLen;
+  const void* lm;
+  int lmHasEos;
+  float lmWeight;
+  const float* classScore;
+  float eosScore;
+  const void* lexicon;
+  float wordScore;
+  int* labels;
+  int* lengths;
+  float* scores;
+  float* lmScores;
+  int maxWords;
+  int* words;
+  int* wordCounts;
+  int silToken;
+  float silScore;
+} w2l_beam_search_desc;
+size_t w2l_beam_search_workspace_size(const w2l_beam_search_desc* desc);
+int w2l_beam_search(const w2l_beam_search_desc* desc, void* workspace, w2l_stream_t stream);
 
 /* ---- incremental CTC beam search for streaming (csrc/criterion_beam_stream.hpp) -----------------------------------------
  * A beam SESSION has S slots; a slot holds the search state of one utterance in progress.  A step advances every slot by the

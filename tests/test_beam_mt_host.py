@@ -132,30 +132,31 @@ def test_mt_twin_sizes_its_workspace_and_refuses_in_order(name):
 
 
 def test_python_front_end_routes_mt():
-    """criterion._wide and _beam_fn: "mt" names the many-token twin, which takes the silence pair itself and no family; an
-    unknown string is refused with the accepted values named; lm_token=True has no many-token family"""
+    """criterion._beam_family: "mt" names the many-token family, whose descriptor call is the many-token twin (its size, the silence
+    pair in the descriptor); an unknown string is refused with the accepted values named; lm_token=True has no many-token family"""
     L = _L()
     from wav2letter_amd import criterion
     lib = L.lib()
-    for base in ("w2l_ctc_beam_search", "w2l_ctc_beam_search_lm", "w2l_ctc_beam_search_lex", "w2l_asg_beam_search",
-                 "w2l_asg_beam_search_lex"):
-        assert criterion._wide(lib, base, "mt") is getattr(lib, base + "_mt")
-        assert criterion._wide(lib, base, "xl") is getattr(lib, base + "_xl")
-    for stem in ("w2l_ctc_beam", "w2l_ctc_beam_lm", "w2l_ctc_beam_lex", "w2l_asg_beam", "w2l_asg_beam_lex"):
-        assert criterion._wide(lib, stem + "_workspace_size", "mt") is getattr(lib, stem + "_mt_workspace_size")
-        assert criterion._beam_fn(lib, stem + "_workspace_size", "mt", (3, 0.5)) is getattr(lib, stem + "_mt_workspace_size")
+    assert criterion._beam_family("mt") == L.BEAM_MT == 3 and criterion._beam_family("xl") == L.BEAM_XL == 2
+    for kind, stem in ((L.SEARCH_PLAIN, "w2l_ctc_beam"), (L.SEARCH_LM, "w2l_ctc_beam_lm"), (L.SEARCH_LEX, "w2l_ctc_beam_lex")):
+        d = L.BeamSearchDesc(family=criterion._beam_family("mt"), kind=kind, B=2, T=10, N=400, beam=300, beamToken=200, silToken=3,
+                             silScore=0.5)
+        assert lib.w2l_beam_search_workspace_size(C.byref(d)) == getattr(lib, stem + "_mt_workspace_size")(2, 10, 400, 300, 200) > 0
     with pytest.raises(L.W2LInvalidArgument) as e:
-        criterion._wide(lib, "w2l_ctc_beam_search", "many")
+        criterion._beam_family("many")
     assert all(v in str(e.value) for v in ("True", '"xl"', '"mt"'))
     with pytest.raises(L.W2LInvalidArgument):
-        criterion._lextok_fn(lib, "w2l_ctc_beam_search_lex", "mt", None)
-    # the silence pair goes behind the xl twin's list: null pointers are refused by the library, not by ctypes' argument count
+        criterion._beam_family("mt", lm_token=True)
+    # the silence pair rides in the descriptor: null pointers are refused by the library, then the limits, the silence token first
     buf = np.zeros(64, np.uint8).ctypes.data
-    f = criterion._beam_fn(lib, "w2l_ctc_beam_search", "mt", None)
-    assert f(2, 10, 400, None, None, 8, 257, INF, 0, 0, 2, 10, buf, buf, buf, buf, None) == L.W2L_EINVAL
-    assert f(2, 10, 400, buf, None, 8, 257, INF, 0, 0, 2, 10, buf, buf, buf, buf, None) == L.W2L_EUNSUPPORTED
-    g = criterion._beam_fn(lib, "w2l_ctc_beam_search", "mt", (399, 0.5))                     # the blank is no silence token
-    assert g(2, 10, 400, buf, None, 8, 8, INF, 0, 0, 2, 10, buf, buf, buf, buf, None) == L.W2L_EINVAL
+
+    def call(x, K, sil=-1, sil_score=0.0):
+        d = L.BeamSearchDesc(family=L.BEAM_MT, kind=L.SEARCH_PLAIN, B=2, T=10, N=400, input=x, beam=8, beamToken=K, threshold=INF,
+                             nbest=2, maxLen=10, labels=buf, lengths=buf, scores=buf, silToken=sil, silScore=sil_score)
+        return lib.w2l_beam_search(C.byref(d), buf, None)
+    assert call(None, 257) == L.W2L_EINVAL
+    assert call(buf, 257) == L.W2L_EUNSUPPORTED
+    assert call(buf, 8, 399, 0.5) == L.W2L_EINVAL                                            # the blank is no silence token
 
 
 def test_python_argument_checks_with_mt():

@@ -3,6 +3,7 @@ bad arguments in their siblings' order -- every W2L_EINVAL before W2L_EUNSUPPORT
 entry points still refuse W = 1025; the Python front end knows wide="xl" and nothing else but False / True; and the fl:: options
 carry `xl` (false by default, refused together with `wide`), checked by a compiled C++ program.  The oracle of
 tests/test_gpu_beam_xl.py is the set of numpy restatements tests/test_beam_wide_host.py holds against an enumeration."""
+import ctypes as C
 import os
 import subprocess
 
@@ -106,20 +107,26 @@ def test_xl_twin_exists_sizes_its_workspace_and_refuses_in_order(name):
 
 
 def test_python_front_end_routes_wide_xl():
-    """criterion._wide: False the sibling, True the wide twin, "xl" the xl twin, any other string refused"""
+    """criterion._beam_family: False the narrow family, True the wide one, "xl" the xl one, any other string refused; the
+    descriptor call with that family is the named twin: its size, and its refusal of a beam above the family's limit"""
     L = _L()
     from wav2letter_amd import criterion
     lib = L.lib()
-    for base in ("w2l_ctc_beam_search", "w2l_ctc_beam_search_lm", "w2l_ctc_beam_search_lex", "w2l_asg_beam_search",
-                 "w2l_asg_beam_search_lex"):
-        assert criterion._wide(lib, base, False) is getattr(lib, base)
-        assert criterion._wide(lib, base, True) is getattr(lib, base + "_wide")
-        assert criterion._wide(lib, base, "xl") is getattr(lib, base + "_xl")
-    for stem in ("w2l_ctc_beam", "w2l_ctc_beam_lm", "w2l_ctc_beam_lex", "w2l_asg_beam", "w2l_asg_beam_lex"):
-        assert criterion._wide(lib, stem + "_workspace_size", "xl") is getattr(lib, stem + "_xl_workspace_size")
-        assert criterion._wide(lib, stem + "_workspace_size", True) is getattr(lib, stem + "_wide_workspace_size")
+    assert [criterion._beam_family(w) for w in (False, True, "xl")] == [L.BEAM_NARROW, L.BEAM_WIDE, L.BEAM_XL] == [0, 1, 2]
     with pytest.raises(L.W2LInvalidArgument):
-        criterion._wide(lib, "w2l_ctc_beam_search", "xxl")
+        criterion._beam_family("xxl")
+    buf = np.zeros(64, np.uint8).ctypes.data
+    for wide, suffix, limit in ((False, "", 64), (True, "_wide", 1024), ("xl", "_xl", 8192)):
+        for kind, stem in ((L.SEARCH_LM, "w2l_ctc_beam_lm"), (L.SEARCH_LEX, "w2l_ctc_beam_lex")):
+            d = L.BeamSearchDesc(family=criterion._beam_family(wide), kind=kind, B=2, T=10, N=30, beam=limit, beamToken=8, silToken=-1)
+            assert lib.w2l_beam_search_workspace_size(C.byref(d)) == getattr(lib, stem + suffix + "_workspace_size")(2, 10, 30, limit, 8) > 0
+            d.beam = limit + 1
+            assert lib.w2l_beam_search_workspace_size(C.byref(d)) == 0
+        d = L.BeamSearchDesc(family=criterion._beam_family(wide), kind=L.SEARCH_PLAIN, B=2, T=10, N=30, input=buf, beam=limit + 1,
+                             beamToken=8, threshold=INF, nbest=2, maxLen=10, labels=buf, lengths=buf, scores=buf, silToken=-1)
+        assert lib.w2l_beam_search(C.byref(d), buf, None) == L.W2L_EUNSUPPORTED
+        d.input = None
+        assert lib.w2l_beam_search(C.byref(d), buf, None) == L.W2L_EINVAL
 
 
 def test_cpp_options_carry_xl(tmp_path):

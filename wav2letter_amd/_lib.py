@@ -183,6 +183,9 @@ class _SIGS:
     w2l_asg_beam_lextok_workspace_size = (_sz, [_i, _i, _i, _i, _i, _i])
     w2l_ctc_beam_search_lextok = (_i, [_i] + w2l_ctc_beam_search_lex[1] + [_i, _f])
     w2l_asg_beam_search_lextok = (_i, [_i] + w2l_asg_beam_search_lex[1] + [_i, _f])
+    # every search above through one descriptor (BeamSearchDesc): desc; desc, workspace, stream
+    w2l_beam_search_workspace_size = (_sz, [_p])
+    w2l_beam_search = (_i, [_p, _p, _p])
     w2l_host_last_error = (C.c_char_p, [])
     w2l_gemm_f32 = (_i, [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _p])
     w2l_linear_forward = (_i, [_i, _i, _i, _p, _p, _p, _p, _i, _p])
@@ -359,6 +362,20 @@ class BeamSessionDesc(C.Structure):  # w2l_beam_session_desc
                 [(n, C.c_int) for n in ("logAdd", "normalize", "variant")] +
                 [("lm", C.c_void_p), ("lmHasEos", C.c_int), ("lmWeight", C.c_float), ("classScore", C.c_void_p),
                  ("eosScore", C.c_float), ("lexicon", C.c_void_p), ("wordScore", C.c_float)])
+
+
+class BeamSearchDesc(C.Structure):  # w2l_beam_search_desc; family: w2l_beam_family, kind: w2l_beam_search_kind
+    _fields_ = ([(n, C.c_int) for n in ("family", "kind", "B", "T", "N")] + [(n, C.c_void_p) for n in ("input", "frames", "trans")] +
+                [("beam", C.c_int), ("beamToken", C.c_int), ("threshold", C.c_float)] +
+                [(n, C.c_int) for n in ("logAdd", "normalize", "nbest", "maxLen")] +
+                [("lm", C.c_void_p), ("lmHasEos", C.c_int), ("lmWeight", C.c_float), ("classScore", C.c_void_p),
+                 ("eosScore", C.c_float), ("lexicon", C.c_void_p), ("wordScore", C.c_float)] +
+                [(n, C.c_void_p) for n in ("labels", "lengths", "scores", "lmScores")] +
+                [("maxWords", C.c_int), ("words", C.c_void_p), ("wordCounts", C.c_void_p), ("silToken", C.c_int), ("silScore", C.c_float)])
+
+
+BEAM_NARROW, BEAM_WIDE, BEAM_XL, BEAM_MT = range(4)                  # w2l_beam_family
+SEARCH_PLAIN, SEARCH_LM, SEARCH_LEX, SEARCH_LEXTOK = range(4)        # w2l_beam_search_kind
 
 
 class FeatDesc(C.Structure):  # w2l_feat_desc

@@ -13,6 +13,7 @@ Tensors are torch CUDA(HIP) tensors used only as device buffers: emission is
 [B][T][N] float32 contiguous (== ArrayFire dims (N,T,B)), target [B][L] int32
 padded with -1.  Every op runs in libw2l_hip.so; there is no PyTorch fallback.
 """
+import ctypes
 import enum
 
 import torch
@@ -302,23 +303,6 @@ def ctc_align(emission, target, frames=None, with_score=True):
     return path, score
 
 
-def _wide(L, name, wide):
-    """the entry point `name`, or its wide, xl or many-token twin: w2l_x_beam_search_y -> w2l_x_beam_search_y_wide / _xl / _mt,
-    w2l_x_workspace_size -> w2l_x_wide_workspace_size / w2l_x_xl_workspace_size / w2l_x_mt_workspace_size.  wide: False, True, "xl"
-    or "mt" (the many-token search's silence arguments are _beam_fn's to add) """
-    if isinstance(wide, str):
-        if wide not in ("xl", "mt"):
-            raise _lib.W2LInvalidArgument(f'beam search: wide must be False, True, "xl" or "mt", not {wide!r}')
-        suffix = "_" + wide
-    elif not wide:
-        return getattr(L, name)
-    else:
-        suffix = "_wide"
-    if name.endswith("_workspace_size"):
-        return getattr(L, name[:-len("_workspace_size")] + suffix + "_workspace_size")
-    return getattr(L, name + suffix)
-
-
 def _wide_checks(wide, lm_token):
     """what `wide` may be, alone and with lm_token, refused before anything else looks at the call"""
     if isinstance(wide, str) and wide not in ("xl", "mt"):
@@ -327,41 +311,23 @@ def _wide_checks(wide, lm_token):
         raise _lib.W2LInvalidArgument('beam search: lm_token=True has no many-token family (wide must be False or True)')
 
 
-def _beam_fn(L, name, wide, sil):
-    """_wide(L, name, wide), or with sil = (token, score) the *_sil entry point behind the same call: the family goes in front
-    (0 narrow, 1 wide, 2 xl), the silence token and score behind.  wide="mt": the many-token entry point, which takes the token and
-    score itself (-1, 0: none) and no family"""
-    f = _wide(L, name, wide)   # checks `wide`
-    if wide == "mt":
-        if name.endswith("_workspace_size"):
-            return f
-        tok, score = sil if sil is not None else (-1, 0.0)
-        return lambda *a: f(*a, tok, score)
-    if sil is None:
-        return f
-    family = 2 if wide == "xl" else (1 if wide else 0)
-    if name.endswith("_workspace_size"):
-        g = getattr(L, name[:-len("_workspace_size")] + "_sil_workspace_size")
-        return lambda *a: g(family, *a)
-    g = getattr(L, name + "_sil")
-    return lambda *a: g(family, *a, sil[0], sil[1])
-
-
-def _lextok_fn(L, name, wide, sil):
-    """the token-LM-under-a-lexicon entry point for `name` (w2l_x_beam_search_lex or w2l_x_beam_lex_workspace_size): the family in
-    front, and behind the search's arguments the silence token and score (-1, 0: none)"""
-    _wide(L, name, wide)   # checks `wide`
-    if wide == "mt":
-        raise _lib.W2LInvalidArgument('beam search: lm_token=True has no many-token family (wide must be False or True)')
-    if wide == "xl":
+def _beam_family(wide, lm_token=False):
+    """the w2l_beam_family `wide` names: False narrow, True wide, "xl", "mt"; lm_token=True has the first two only"""
+    _wide_checks(wide, lm_token)
+    if lm_token and wide == "xl":
         raise _lib.W2LInvalidArgument('beam search: lm_token=True has no xl family (wide must be False or True)')
-    family = 1 if wide else 0
-    if name.endswith("_workspace_size"):
-        g = getattr(L, name.replace("_beam_lex_workspace_size", "_beam_lextok_workspace_size"))
-        return lambda *a: g(family, *a)
-    g = getattr(L, name + "tok")
+    if isinstance(wide, str):
+        return _lib.BEAM_XL if wide == "xl" else _lib.BEAM_MT
+    return _lib.BEAM_WIDE if wide else _lib.BEAM_NARROW
+
+
+def _beam_search(who, wide, lm_token, kind, sil, device, **fields):
+    """one w2l_beam_search call on a workspace of its size: `fields` are w2l_beam_search_desc's, sil = (token, score) or None"""
+    L = _lib.lib()
     tok, score = sil if sil is not None else (-1, 0.0)
-    return lambda *a: g(family, *a, tok, score)
+    d = _lib.BeamSearchDesc(family=_beam_family(wide, lm_token), kind=kind, silToken=tok, silScore=score, **fields)
+    ws = _ws(L.w2l_beam_search_workspace_size(ctypes.byref(d)), device)
+    _lib.check(L.w2l_beam_search(ctypes.byref(d), ws.data_ptr(), _stream()), who)
 
 
 def _sil_args(who, sil_token, sil_score, lexicon):
@@ -418,7 +384,6 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
         raise ValueError("ctc_beam_search: lm_token=True needs lexicon (without one, lm alone is the token-LM search)")
     if lm_token and lm is not None and lm.num_tokens != lexicon.num_tokens:
         raise ValueError(f"ctc_beam_search: lm_token=True: the LM has {lm.num_tokens} tokens, the lexicon {lexicon.num_tokens}")
-    lex_fn = _lextok_fn if lm_token else _beam_fn
     if lexicon is not None:
         if lm is None:
             raise _lib.W2LInvalidArgument("ctc_beam_search: lexicon needs lm, a model over the lexicon's words")
@@ -445,7 +410,7 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
         if class_score is not None and (class_score.dtype != torch.float32 or class_score.numel() != N - 1):
             raise _lib.W2LInvalidArgument("ctc_beam_search: class_score must be float32 with one entry per token class")
     _check_dev(emission)
-    L = _lib.lib()
+    _lib.lib()
     emission = emission.detach().contiguous()
     if frames is not None:
         if frames.dtype != torch.int32 or frames.numel() != B:
@@ -460,40 +425,31 @@ def ctc_beam_search(emission, frames=None, beam=64, beam_token=64, threshold=flo
     labels = torch.empty(*shape, max(max_len, 1), dtype=torch.int32, device=emission.device)
     lengths = torch.empty(*shape, dtype=torch.int32, device=emission.device)
     scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
+    common = dict(B=B, T=T, N=N, input=emission.data_ptr(), frames=frames.data_ptr() if frames is not None else None, beam=int(beam),
+                  beamToken=int(beam_token), threshold=float(threshold), logAdd=int(bool(log_add)), normalize=int(bool(normalize)),
+                  nbest=nbest, maxLen=max_len, labels=labels.data_ptr(), lengths=lengths.data_ptr(), scores=scores.data_ptr())
+    if lm is None:
+        _beam_search("ctc_beam_search", wide, lm_token, _lib.SEARCH_PLAIN, sil, emission.device, **common)
+        return labels, lengths, scores
+    lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
+    blob = lm.device_blob(emission.device)
+    common.update(lm=blob.data_ptr(), lmHasEos=int(lm.has_eos), lmWeight=float(lm_weight), eosScore=float(eos_score),
+                  lmScores=lm_scores.data_ptr())
     if lexicon is not None:
         max_words = max(max_len, 1) if max_words is None else int(max_words)
-        ws = _ws(lex_fn(L, "w2l_ctc_beam_lex_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), emission.device)
-        lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
         words = torch.empty(*shape, max_words, dtype=torch.int32, device=emission.device)
         word_counts = torch.empty(*shape, dtype=torch.int32, device=emission.device)
-        blob, lex_blob = lm.device_blob(emission.device), lexicon.device_blob(emission.device)
-        _lib.check(lex_fn(L, "w2l_ctc_beam_search_lex", wide, sil)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
-                                             int(beam), int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)),
-                                             nbest, max_len, blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
-                                             float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),
-                                             scores.data_ptr(), lm_scores.data_ptr(), max_words, words.data_ptr(),
-                                             word_counts.data_ptr(), ws.data_ptr(), _stream()), "ctc_beam_search")
+        lex_blob = lexicon.device_blob(emission.device)
+        _beam_search("ctc_beam_search", wide, lm_token, _lib.SEARCH_LEXTOK if lm_token else _lib.SEARCH_LEX, sil, emission.device,
+                     lexicon=lex_blob.data_ptr(), wordScore=float(word_score), maxWords=max_words, words=words.data_ptr(),
+                     wordCounts=word_counts.data_ptr(), **common)
         return labels, lengths, scores, lm_scores, words, word_counts
-    if lm is not None:
-        if class_score is not None:
-            _check_dev(emission, class_score)
-            class_score = class_score.contiguous()
-        ws = _ws(_beam_fn(L, "w2l_ctc_beam_lm_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), emission.device)
-        lm_scores = torch.empty(*shape, dtype=torch.float32, device=emission.device)
-        blob = lm.device_blob(emission.device)
-        _lib.check(_beam_fn(L, "w2l_ctc_beam_search_lm", wide, sil)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None,
-                                            int(beam), int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)),
-                                            nbest, max_len, blob.data_ptr(), int(lm.has_eos), float(lm_weight),
-                                            class_score.data_ptr() if class_score is not None else None, float(eos_score),
-                                            labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), lm_scores.data_ptr(),
-                                            ws.data_ptr(), _stream()), "ctc_beam_search")
-        return labels, lengths, scores, lm_scores
-    ws = _ws(_beam_fn(L, "w2l_ctc_beam_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), emission.device)
-    _lib.check(_beam_fn(L, "w2l_ctc_beam_search", wide, sil)(B, T, N, emission.data_ptr(), frames.data_ptr() if frames is not None else None, int(beam),
-                                     int(beam_token), float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
-                                     labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), ws.data_ptr(), _stream()),
-               "ctc_beam_search")
-    return labels, lengths, scores
+    if class_score is not None:
+        _check_dev(emission, class_score)
+        class_score = class_score.contiguous()
+    _beam_search("ctc_beam_search", wide, lm_token, _lib.SEARCH_LM, sil, emission.device,
+                 classScore=class_score.data_ptr() if class_score is not None else None, **common)
+    return labels, lengths, scores, lm_scores
 
 
 def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, threshold=float("inf"), log_add=False, normalize=False,
@@ -513,7 +469,6 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
         raise ValueError("asg_beam_search: lm_token=True needs lexicon (without one, lm alone is the token-LM search)")
     if lm_token and lm is not None and lm.num_tokens != lexicon.num_tokens:
         raise ValueError(f"asg_beam_search: lm_token=True: the LM has {lm.num_tokens} tokens, the lexicon {lexicon.num_tokens}")
-    lex_fn = _lextok_fn if lm_token else _beam_fn
     if transitions.dtype != torch.float32 or tuple(transitions.shape) != (N, N):
         raise _lib.W2LInvalidArgument(f"asg_beam_search: transitions must be float32 [{N}][{N}]")
     if lexicon is not None:
@@ -540,7 +495,7 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
     if lm is not None and not lm.has_eos and eos_score != 0.0:
         raise _lib.W2LInvalidArgument("asg_beam_search: eos_score needs a model with EOS")
     _check_dev(emission, transitions)
-    L = _lib.lib()
+    _lib.lib()
     emission = emission.detach().contiguous()
     transitions = transitions.detach().contiguous()
     if frames is not None:
@@ -557,30 +512,27 @@ def asg_beam_search(emission, transitions, frames=None, beam=64, beam_token=64, 
     lengths = torch.empty(*shape, dtype=torch.int32, device=dev)
     scores = torch.empty(*shape, dtype=torch.float32, device=dev)
     lm_scores = torch.empty(*shape, dtype=torch.float32, device=dev)
+    common = dict(B=B, T=T, N=N, input=emission.data_ptr(), frames=fr, trans=transitions.data_ptr(), beam=int(beam),
+                  beamToken=int(beam_token), threshold=float(threshold), logAdd=int(bool(log_add)), normalize=int(bool(normalize)),
+                  nbest=nbest, maxLen=max_len, labels=labels.data_ptr(), lengths=lengths.data_ptr(), scores=scores.data_ptr(),
+                  lmScores=lm_scores.data_ptr(), lmWeight=float(lm_weight), eosScore=float(eos_score))
+    if lm is not None:
+        blob = lm.device_blob(dev)
+        common.update(lm=blob.data_ptr(), lmHasEos=int(lm.has_eos))
     if lexicon is not None:
         max_words = max(max_len, 1) if max_words is None else int(max_words)
-        ws = _ws(lex_fn(L, "w2l_asg_beam_lex_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), dev)
         words = torch.empty(*shape, max_words, dtype=torch.int32, device=dev)
         word_counts = torch.empty(*shape, dtype=torch.int32, device=dev)
-        blob, lex_blob = lm.device_blob(dev), lexicon.device_blob(dev)
-        _lib.check(lex_fn(L, "w2l_asg_beam_search_lex", wide, sil)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
-                                             float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
-                                             blob.data_ptr(), int(lm.has_eos), float(lm_weight), lex_blob.data_ptr(),
-                                             float(word_score), float(eos_score), labels.data_ptr(), lengths.data_ptr(),
-                                             scores.data_ptr(), lm_scores.data_ptr(), max_words, words.data_ptr(),
-                                             word_counts.data_ptr(), ws.data_ptr(), _stream()), "asg_beam_search")
+        lex_blob = lexicon.device_blob(dev)
+        _beam_search("asg_beam_search", wide, lm_token, _lib.SEARCH_LEXTOK if lm_token else _lib.SEARCH_LEX, sil, dev,
+                     lexicon=lex_blob.data_ptr(), wordScore=float(word_score), maxWords=max_words, words=words.data_ptr(),
+                     wordCounts=word_counts.data_ptr(), **common)
         return labels, lengths, scores, lm_scores, words, word_counts
     if class_score is not None:
         _check_dev(emission, class_score)
         class_score = class_score.contiguous()
-    blob = lm.device_blob(dev) if lm is not None else None
-    ws = _ws(_beam_fn(L, "w2l_asg_beam_workspace_size", wide, sil)(B, T, N, int(beam), int(beam_token)), dev)
-    _lib.check(_beam_fn(L, "w2l_asg_beam_search", wide, sil)(B, T, N, emission.data_ptr(), fr, transitions.data_ptr(), int(beam), int(beam_token),
-                                     float(threshold), int(bool(log_add)), int(bool(normalize)), nbest, max_len,
-                                     blob.data_ptr() if blob is not None else None, int(lm.has_eos) if lm is not None else 0,
-                                     float(lm_weight), class_score.data_ptr() if class_score is not None else None,
-                                     float(eos_score), labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(),
-                                     lm_scores.data_ptr(), ws.data_ptr(), _stream()), "asg_beam_search")
+    _beam_search("asg_beam_search", wide, lm_token, _lib.SEARCH_LM if lm is not None else _lib.SEARCH_PLAIN, sil, dev,
+                 classScore=class_score.data_ptr() if class_score is not None else None, **common)
     return (labels, lengths, scores, lm_scores) if lm is not None else (labels, lengths, scores)
 
 

@@ -50,93 +50,13 @@ static BeamTrans asg_beam_trans(const float* trans, int N, size_t* ldsBytes) {
   return BeamTrans{trans, lds ? 1 : 0};
 }
 
+// The dispatch of a scan over its (logAdd, lattice policy, lexicon) template parameters: launch(logAdd, policy, lex) gets the two
+// flags as std::integral_constant types and a BeamCtc or BeamAsg value, and returns the status of the launch it starts.
+template <class Launch>
+static int beam_scan_dispatch(int logAdd, bool asg, bool lex, Launch&& launch) {
+  auto pol = [&](auto la, auto lx) { return asg ? launch(la, BeamAsg{}, lx) : launch(la, BeamCtc{}, lx); };
+  auto la = [&](auto lx) { return logAdd ? pol(std::true_type{}, lx) : pol(std::false_type{}, lx); };
+  return lex ? la(std::true_type{}) : la(std::false_type{});
+}
+
 }  // namespace w2l
-
-W2L_API size_t w2l_asg_beam_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, true);
-}
-
-W2L_API size_t w2l_asg_beam_lex_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, true);
-}
-
-namespace w2l {
-// w2l_asg_beam_search with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int asg_beam_search_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
-  if (!lmScores || !trans) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  if (!lm && (lmHasEos || classScore)) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = ctc_beam_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                    true))
-    return rc;
-  hipStream_t s = (hipStream_t)stream;
-  CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamLm, B, T, N, input, frames, beam, K, normalize, workspace, s, true, sil)) return rc;
-  size_t lds = 0;
-  const BeamTrans tr = asg_beam_trans(trans, N, &lds);
-  ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
-    hipLaunchKernelGGL((ctc_beam_lm_scan<decltype(la)::value, decltype(th)::value, BeamAsg>), dim3((unsigned)B),
-                       dim3(decltype(th)::value), lds, s, T, N, beam, threshold, input, frames, ws, lm, lmWeight, classScore, tr);
-  });
-  W2L_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_beam_lm_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, N + 1, ws, lm, lmWeight, eosScore,
-                     lmHasEos ? 1 : 0, labels, lengths, scores, lmScores);
-  W2L_LAUNCH_CHECK();
-  return W2L_OK;
-}
-}  // namespace w2l
-
-W2L_API int w2l_asg_beam_search(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  return w2l::asg_beam_search_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
-      lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
-}
-
-namespace w2l {
-// w2l_asg_beam_search_lex with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int asg_beam_search_lex_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                    int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
-                                    const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
-                                    float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                    int* words, int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
-  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1 || !trans) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = ctc_beam_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                    true))
-    return rc;
-  hipStream_t s = (hipStream_t)stream;
-  CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamLex, B, T, N, input, frames, beam, K, normalize, workspace, s, true, sil)) return rc;
-  size_t lds = 0;
-  const BeamTrans tr = asg_beam_trans(trans, N, &lds);
-  ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
-    hipLaunchKernelGGL((ctc_beam_lex_scan<decltype(la)::value, decltype(th)::value, BeamAsg>), dim3((unsigned)B),
-                       dim3(decltype(th)::value), lds, s, T, N, beam, threshold, input, frames, ws, lexicon, lm, lmWeight, wordScore,
-                       tr);
-  });
-  W2L_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_beam_lex_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, maxWords, ws, lexicon, lm, lmWeight,
-                     eosScore, lmHasEos ? 1 : 0, labels, lengths, scores, lmScores, words, wordCounts);
-  W2L_LAUNCH_CHECK();
-  return W2L_OK;
-}
-}  // namespace w2l
-
-W2L_API int w2l_asg_beam_search_lex(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                    int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
-                                    const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
-                                    float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                    int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
-  return w2l::asg_beam_search_lex_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
-      lm, lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts,
-      workspace, stream, w2l::BeamSil{});
-}

@@ -1,6 +1,7 @@
 // criterion_beam_lextok.hpp -- w2l_ctc_beam_search_lextok and w2l_asg_beam_search_lextok: the beam searches restricted to the
 // spellings of a lexicon and scored by a TOKEN-level back-off n-gram LM (contract: include/w2l_hip.h; the reference's
-// --uselexicon=true --decodertype=tkn).  Included at the end of criterion_ctc.hip after criterion_beam_sil.hpp.  The lexicon search
+// --uselexicon=true --decodertype=tkn).  Included at the end of criterion_ctc.hip after criterion_beam_xl.hpp; the
+// host side (checks, launches, entry points) is criterion_beam_entry.hpp's beam_narrow_run and criterion_beam_wide.hpp's beam_wide_run.  The lexicon search
 // (criterion_ctc_beam_lex.hpp) owns the state -- prefix-table labels (lexicon node << 3) | slot, the sil / in / word slots, the
 // root-only end -- and its finishes serve as they are: they rebuild tokens and words from labels and node records, and their
 // end-of-sentence term reads word numTokens + 1 of whatever blob it is given.  What changes is where the LM enters: every token
@@ -199,98 +200,4 @@ __global__ __launch_bounds__(kThreads) void beam_lextok_scan(int T, int N, int W
   beam_store_final(ws, b, n, sNode[cur], sTot[cur], sSt[cur], sAcc[cur], sU[cur]);
 }
 
-// the silence arguments' refusals, the lexicon searches' in their order, then the family's limits: every W2L_EINVAL comes before
-// W2L_EUNSUPPORTED, which is also what the xl family gets; *K = the clipped beamToken
-static int beam_lextok_check(int family, int B, int T, int N, const float* input, const float* trans, bool asg, int beam, int beamToken,
-                             float threshold, int nbest, int maxLen, const void* lm, int lmHasEos, float lmWeight, const void* lexicon,
-                             float wordScore, float eosScore, const int* labels, const int* lengths, const float* scores,
-                             const float* lmScores, int maxWords, const int* words, const int* wordCounts, const void* workspace,
-                             int* K, int silToken, float silScore) {
-  if (const int rc = beam_sil_check(family, asg ? N : N - 1, silToken, silScore)) return rc;
-  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1 || (asg && !trans)) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  if (family == 0)
-    return ctc_beam_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, K, asg);
-  const int rc = beam_wide_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, K, asg);
-  return rc == W2L_EINVAL ? rc : family == 2 ? W2L_EUNSUPPORTED : rc;
-}
-
-// one search after its checks.  trans null: CTC
-static int beam_lextok_run(int family, int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                           int K, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
-                           float lmWeight, const void* lexicon, float wordScore, float eosScore, int* labels, int* lengths,
-                           float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                           hipStream_t s, BeamSil sil) {
-  if (family == 1)
-    return beam_wide_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
-                         nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts,
-                         workspace, s, sil, true);
-  const bool asg = trans != nullptr;
-  CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamLex, B, T, N, input, frames, beam, K, normalize, workspace, s, asg, sil)) return rc;
-  size_t lds = 0;
-  const BeamTrans tr = asg ? asg_beam_trans(trans, N, &lds) : BeamTrans{};
-  ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
-    if (asg)
-      hipLaunchKernelGGL((beam_lextok_scan<decltype(la)::value, decltype(th)::value, BeamAsg>), dim3((unsigned)B),
-                         dim3(decltype(th)::value), lds, s, T, N, beam, threshold, input, frames, ws, lexicon, lm, lmWeight, wordScore,
-                         tr);
-    else
-      hipLaunchKernelGGL((beam_lextok_scan<decltype(la)::value, decltype(th)::value, BeamCtc>), dim3((unsigned)B),
-                         dim3(decltype(th)::value), 0, s, T, N, beam, threshold, input, frames, ws, lexicon, lm, lmWeight, wordScore,
-                         tr);
-  });
-  W2L_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_beam_lex_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, maxWords, ws, lexicon, lm, lmWeight,
-                     eosScore, lmHasEos ? 1 : 0, labels, lengths, scores, lmScores, words, wordCounts);
-  W2L_LAUNCH_CHECK();
-  return W2L_OK;
-}
-
 }  // namespace w2l
-
-W2L_API size_t w2l_ctc_beam_lextok_workspace_size(int family, int B, int T, int N, int beam, int beamToken) {
-  if (family != 0 && family != 1) return 0;
-  return w2l::beam_sil_workspace_size(family, B, T, N, beam, beamToken, w2l::kBeamLex, false);
-}
-W2L_API size_t w2l_asg_beam_lextok_workspace_size(int family, int B, int T, int N, int beam, int beamToken) {
-  if (family != 0 && family != 1) return 0;
-  return w2l::beam_sil_workspace_size(family, B, T, N, beam, beamToken, w2l::kBeamLex, true);
-}
-
-W2L_API int w2l_ctc_beam_search_lextok(int family, int B, int T, int N, const float* input, const int* frames, int beam,
-                                       int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
-                                       const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
-                                       float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream, int silToken,
-                                       float silScore) {
-  using namespace w2l;
-  int K = 0;
-  if (const int rc = beam_lextok_check(family, B, T, N, input, nullptr, false, beam, beamToken, threshold, nbest, maxLen, lm, lmHasEos,
-                                       lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words,
-                                       wordCounts, workspace, &K, silToken, silScore))
-    return rc;
-  const BeamSil sil = beam_sil_none(silToken, silScore) ? BeamSil{} : BeamSil{silToken, silScore};
-  return beam_lextok_run(family, B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos,
-                         lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts,
-                         workspace, (hipStream_t)stream, sil);
-}
-
-W2L_API int w2l_asg_beam_search_lextok(int family, int B, int T, int N, const float* input, const int* frames, const float* trans,
-                                       int beam, int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
-                                       const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
-                                       float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream, int silToken,
-                                       float silScore) {
-  using namespace w2l;
-  int K = 0;
-  if (const int rc = beam_lextok_check(family, B, T, N, input, trans, true, beam, beamToken, threshold, nbest, maxLen, lm, lmHasEos,
-                                       lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words,
-                                       wordCounts, workspace, &K, silToken, silScore))
-    return rc;
-  const BeamSil sil = beam_sil_none(silToken, silScore) ? BeamSil{} : BeamSil{silToken, silScore};
-  return beam_lextok_run(family, B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos,
-                         lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts,
-                         workspace, (hipStream_t)stream, sil);
-}

@@ -546,25 +546,6 @@ __global__ __launch_bounds__(kWideThreads) void beam_wide_finish(int M, int Lmax
                               eosScore, useEos, labels, lengths, scores, lmScores, words, wordCounts);
 }
 
-static size_t beam_wide_workspace_size(int B, int T, int N, int beam, int beamToken, int variant, bool noBlank) {
-  if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
-  const int K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
-  if (beam > kBeamWideMax || K > kBeamMax) return 0;
-  return beam_wide_layout(nullptr, nullptr, B, T, beam, K, variant);
-}
-
-// ctc_beam_check with the wide limit
-static int beam_wide_check(int B, int T, int N, const float* input, int beam, int beamToken, float threshold, int nbest, int maxLen,
-                           const int* labels, const int* lengths, const float* scores, const void* workspace, int* K, bool noBlank) {
-  if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !workspace) return W2L_EINVAL;
-  if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
-  if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
-  *K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
-  if (beam > kBeamWideMax || *K > kBeamMax) return W2L_EUNSUPPORTED;
-  if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;   // node ids are ints
-  return W2L_OK;
-}
-
 template <bool kLogAdd, class Pol, bool kLex, bool kTok = false>
 static int beam_wide_launch(int B, int T, int N, float threshold, const float* input, const int* frames, const BeamWideWs& ww,
                             const void* lex, const void* lm, float lmWeight, const float* classScore, float wordScore,
@@ -580,212 +561,38 @@ static int beam_wide_launch(int B, int T, int N, float threshold, const float* i
   return W2L_OK;
 }
 
-// One wide search after its checks: rows, scan, finish.  trans null: CTC; lex null: the token search; tok (with lex): lm is a
-// token LM under the lexicon (criterion_beam_lextok.hpp)
-static int beam_wide_run(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam, int K,
-                         float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
-                         float lmWeight, const float* classScore, const void* lex, float wordScore, float eosScore, int* labels,
-                         int* lengths, float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                         hipStream_t s, BeamSil sil, bool tok = false) {
-  const bool asg = trans != nullptr, isLex = lex != nullptr;
+// One wide search after its checks: rows, scan, finish.  K: the clipped beamToken.  kSearchLextok: lm is a token LM under the
+// lexicon (criterion_beam_lextok.hpp)
+static int beam_wide_run(const BeamReq& q, int K) {
+  const bool tok = q.kind == kSearchLextok;
+  const int N = q.N;
   BeamWideWs ww{};
-  beam_wide_layout(&ww, workspace, B, T, beam, K, isLex ? kBeamLex : kBeamLm);
-  ww.c.sil = sil.token; ww.c.silScore = sil.score;
-  W2L_HIP_CHECK(hipMemsetAsync(ww.c.table, 0, (size_t)B * ww.c.cap * sizeof(u64), s));
-  const unsigned rows = (unsigned)((size_t)B * T);
-  const bool big = N > kRowThreads * kRowMaxPer;
-  if (asg && big)
-    hipLaunchKernelGGL((ctc_beam_rows<true, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
-  else if (asg)
-    hipLaunchKernelGGL((ctc_beam_rows<false, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
-  else if (!big)
-    hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
-  else
-    hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
-  W2L_LAUNCH_CHECK();
+  beam_wide_layout(&ww, q.workspace, q.B, q.T, q.beam, K, q.lex() ? kBeamLex : kBeamLm);
+  if (const int rc = beam_rows_launch(q, &ww.c)) return rc;
 
-  const size_t transBytes = asg && (size_t)N * N * sizeof(float) <= kWideTransLds ? (size_t)N * N * sizeof(float) : 0;
-  const BeamTrans tr{trans, transBytes ? 1 : 0};
-  int rc = W2L_OK;
-#define W2L_WIDE_SCAN(LA, POL, LEX) \
-  rc = beam_wide_launch<LA, POL, LEX>(B, T, N, threshold, input, frames, ww, lex, lm, lmWeight, classScore, wordScore, tr, transBytes, s)
-#define W2L_WIDE_TOK(LA, POL) \
-  rc = beam_wide_launch<LA, POL, true, true>(B, T, N, threshold, input, frames, ww, lex, lm, lmWeight, nullptr, wordScore, tr, \
-                                             transBytes, s)
-  if (isLex && tok) {
-    if (asg) { if (logAdd) W2L_WIDE_TOK(true, BeamAsg); else W2L_WIDE_TOK(false, BeamAsg); }
-    else { if (logAdd) W2L_WIDE_TOK(true, BeamCtc); else W2L_WIDE_TOK(false, BeamCtc); }
-  } else if (isLex) {
-    if (asg) { if (logAdd) W2L_WIDE_SCAN(true, BeamAsg, true); else W2L_WIDE_SCAN(false, BeamAsg, true); }
-    else { if (logAdd) W2L_WIDE_SCAN(true, BeamCtc, true); else W2L_WIDE_SCAN(false, BeamCtc, true); }
-  } else {
-    if (asg) { if (logAdd) W2L_WIDE_SCAN(true, BeamAsg, false); else W2L_WIDE_SCAN(false, BeamAsg, false); }
-    else { if (logAdd) W2L_WIDE_SCAN(true, BeamCtc, false); else W2L_WIDE_SCAN(false, BeamCtc, false); }
-  }
-#undef W2L_WIDE_SCAN
-#undef W2L_WIDE_TOK
+  const size_t transBytes = q.asg && (size_t)N * N * sizeof(float) <= kWideTransLds ? (size_t)N * N * sizeof(float) : 0;
+  const BeamTrans tr{q.trans, transBytes ? 1 : 0};
+  const int rc = beam_scan_dispatch(q.logAdd, q.asg, q.lex(), [&](auto la, auto pol, auto lx) {
+    constexpr bool kLa = decltype(la)::value, kLex = decltype(lx)::value;
+    using Pol = decltype(pol);
+    if constexpr (kLex)
+      if (tok)
+        return beam_wide_launch<kLa, Pol, true, true>(q.B, q.T, N, q.threshold, q.input, q.frames, ww, q.lexicon, q.lm, q.lmWeight,
+                                                      nullptr, q.wordScore, tr, transBytes, q.stream);
+    return beam_wide_launch<kLa, Pol, kLex>(q.B, q.T, N, q.threshold, q.input, q.frames, ww, q.lexicon, q.lm, q.lmWeight, q.classScore,
+                                            q.wordScore, tr, transBytes, q.stream);
+  });
   if (rc) return rc;
-  const int useEos = lm && lmHasEos ? 1 : 0;
-  if (isLex)
-    hipLaunchKernelGGL(beam_wide_finish<true>, dim3((unsigned)B), dim3(kWideThreads), 0, s, nbest, maxLen, maxWords, 0, ww, lex, lm,
-                       lmWeight, eosScore, useEos, labels, lengths, scores, lmScores, words, wordCounts);
+  const int useEos = q.lm && q.lmHasEos ? 1 : 0;
+  const dim3 grid((unsigned)q.B), threads(kWideThreads);
+  if (q.lex())
+    hipLaunchKernelGGL(beam_wide_finish<true>, grid, threads, 0, q.stream, q.nbest, q.maxLen, q.maxWords, 0, ww, q.lexicon, q.lm,
+                       q.lmWeight, q.eosScore, useEos, q.labels, q.lengths, q.scores, q.lmScores, q.words, q.wordCounts);
   else
-    hipLaunchKernelGGL(beam_wide_finish<false>, dim3((unsigned)B), dim3(kWideThreads), 0, s, nbest, maxLen, 0, asg ? N + 1 : N, ww,
-                       nullptr, lm, lmWeight, eosScore, useEos, labels, lengths, scores, lmScores, nullptr, nullptr);
+    hipLaunchKernelGGL(beam_wide_finish<false>, grid, threads, 0, q.stream, q.nbest, q.maxLen, 0, q.asg ? N + 1 : N, ww, nullptr, q.lm,
+                       q.lmWeight, q.eosScore, useEos, q.labels, q.lengths, q.scores, q.lmScores, nullptr, nullptr);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }
 
 }  // namespace w2l
-
-W2L_API size_t w2l_ctc_beam_wide_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_wide_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, false);
-}
-W2L_API size_t w2l_ctc_beam_lm_wide_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_wide_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, false);
-}
-W2L_API size_t w2l_ctc_beam_lex_wide_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_wide_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, false);
-}
-W2L_API size_t w2l_asg_beam_wide_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_wide_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, true);
-}
-W2L_API size_t w2l_asg_beam_lex_wide_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_wide_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, true);
-}
-
-namespace w2l {
-// w2l_ctc_beam_search_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int ctc_beam_search_wide_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                     float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
-                                     float* scores, void* workspace, w2l_stream_t stream, BeamSil sil) {
-  int K = 0;
-  if (const int rc = beam_wide_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                     false))
-    return rc;
-  return beam_wide_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, nullptr, 0, 0.f, nullptr,
-                       nullptr, 0.f, 0.f, labels, lengths, scores, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream, sil);
-}
-}  // namespace w2l
-
-W2L_API int w2l_ctc_beam_search_wide(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                     float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
-                                     float* scores, void* workspace, w2l_stream_t stream) {
-  return w2l::ctc_beam_search_wide_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
-      labels, lengths, scores, workspace, stream, w2l::BeamSil{});
-}
-
-namespace w2l {
-// w2l_ctc_beam_search_lm_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int ctc_beam_search_lm_wide_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                        float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                        int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
-                                        int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
-  if (!lmScores || !lm) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = beam_wide_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                     false))
-    return rc;
-  return beam_wide_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
-                       classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                       (hipStream_t)stream, sil);
-}
-}  // namespace w2l
-
-W2L_API int w2l_ctc_beam_search_lm_wide(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                        float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                        int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
-                                        int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  return w2l::ctc_beam_search_lm_wide_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
-      lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
-}
-
-namespace w2l {
-// w2l_ctc_beam_search_lex_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int ctc_beam_search_lex_wide_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                         float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                         int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
-                                         int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
-                                         int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
-  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = beam_wide_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                     false))
-    return rc;
-  return beam_wide_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
-                       nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                       (hipStream_t)stream, sil);
-}
-}  // namespace w2l
-
-W2L_API int w2l_ctc_beam_search_lex_wide(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                         float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                         int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
-                                         int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
-                                         int* wordCounts, void* workspace, w2l_stream_t stream) {
-  return w2l::ctc_beam_search_lex_wide_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
-      lm, lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts,
-      workspace, stream, w2l::BeamSil{});
-}
-
-namespace w2l {
-// w2l_asg_beam_search_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int asg_beam_search_wide_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                     int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                     int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                     float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
-  if (!lmScores || !trans) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  if (!lm && (lmHasEos || classScore)) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = beam_wide_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                     true))
-    return rc;
-  return beam_wide_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
-                       classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                       (hipStream_t)stream, sil);
-}
-}  // namespace w2l
-
-W2L_API int w2l_asg_beam_search_wide(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                     int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                     int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                     float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  return w2l::asg_beam_search_wide_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
-      lm, lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
-}
-
-namespace w2l {
-// w2l_asg_beam_search_lex_wide with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int asg_beam_search_lex_wide_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                         int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
-                                         const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
-                                         float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                         int* words, int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil) {
-  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1 || !trans) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = beam_wide_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                     true))
-    return rc;
-  return beam_wide_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
-                       nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                       (hipStream_t)stream, sil);
-}
-}  // namespace w2l
-
-W2L_API int w2l_asg_beam_search_lex_wide(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                         int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
-                                         const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
-                                         float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                         int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
-  return w2l::asg_beam_search_lex_wide_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest,
-      maxLen, lm, lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words,
-      wordCounts, workspace, stream, w2l::BeamSil{});
-}

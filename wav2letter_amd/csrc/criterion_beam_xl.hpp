@@ -22,7 +22,7 @@
 // No waiting between workgroups, no flags, no spin loops; every probe loop is bounded by its table's capacity; every barrier is
 // reached by all 1024 threads, and every loop with a barrier inside runs on counts read from LDS after a barrier, the same in
 // every thread.
-//   kMt                  the many-token searches (w2l_*_beam_search*_mt, criterion_beam_mt.hpp) are this scan with K up
+//   kMt                  the many-token searches (w2l_*_beam_search*_mt) are this scan with K up
 //                        to kBeamMtMax = 256: 256 LDS slots of frame tokens, gone masks of ceil(K / 64) words per (slot, entry),
 //                        a tie key with 8 bits of k.  Every difference is an `if constexpr (kMt)`; !kMt is the xl scan, whose
 //                        instructions must not change.
@@ -33,7 +33,7 @@
 namespace w2l {
 
 constexpr int kBeamXlMax = 8192;      // W of the xl searches; their K stays <= kBeamMax
-constexpr int kBeamMtMax = 256;       // K of the many-token searches (criterion_beam_mt.hpp): this scan with kMt, W as here
+constexpr int kBeamMtMax = 256;       // K of the many-token searches (beam_xl_run with mt): this scan with kMt, W as here
 constexpr int kXlThreads = 1024;
 
 struct BeamXlWs {
@@ -99,7 +99,7 @@ __device__ __forceinline__ u64 beam_xl_mask(const u64* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// ---- what the many-token scan (kMt: K <= kBeamMtMax, criterion_beam_mt.hpp) does differently; !kMt is the xl scan as it was
+// ---- what the many-token scan (kMt: K <= kBeamMtMax) does differently; !kMt is the xl scan as it was
 // The selection key with 8 bits of k: total, then ~(r << 12 | ext << 11 | k << 3 | slot), 25 bits for r < 8192: beam_key's order.
 template <bool kMt>
 __device__ __forceinline__ u64 beam_xl_key(float total, int r, int ext, int k, int slot = 0) {
@@ -503,28 +503,6 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_finish(int M, int Lmax, in
   }
 }
 
-// mt: the many-token searches' (K <= kBeamMtMax, the gone masks in words; T * W as the call refuses it)
-static size_t beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken, int variant, bool noBlank, bool mt = false) {
-  if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
-  const int K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
-  if (beam > kBeamXlMax || K > (mt ? kBeamMtMax : kBeamMax)) return 0;
-  if (mt && (size_t)T * beam > ((size_t)1 << 29)) return 0;
-  return beam_xl_layout(nullptr, nullptr, B, T, beam, K, variant, mt);
-}
-
-// beam_wide_check with the xl limit: every W2L_EINVAL first, then the limits, then T * W (node ids are ints)
-static int beam_xl_check(int B, int T, int N, const float* input, int beam, int beamToken, float threshold, int nbest, int maxLen,
-                         const int* labels, const int* lengths, const float* scores, const void* workspace, int* K, bool noBlank,
-                         bool mt = false) {
-  if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !workspace) return W2L_EINVAL;
-  if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
-  if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
-  *K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
-  if (beam > kBeamXlMax || *K > (mt ? kBeamMtMax : kBeamMax)) return W2L_EUNSUPPORTED;
-  if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;
-  return W2L_OK;
-}
-
 constexpr size_t kXlScanLdsMax = (size_t)2 * kBeamXlMax * 8 + XlLds::bytes;   // 128 KiB + 2 KiB
 constexpr size_t kMtScanLdsMax = (size_t)2 * kBeamXlMax * 8 + MtLds::bytes;   // 128 KiB + 3.2 KiB
 constexpr size_t kXlFinishLdsMax = (size_t)kBeamXlMax * 16 + 8;               // 128 KiB
@@ -560,202 +538,29 @@ static int beam_xl_finish_launch(int B, int M, int Lmax, int maxWords, int eosWo
   return W2L_OK;
 }
 
-// One xl search after its checks: rows, scan, finish.  trans null: CTC; lex null: the token search; mt: the many-token scan
-static int beam_xl_run(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam, int K,
-                       float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
-                       float lmWeight, const float* classScore, const void* lex, float wordScore, float eosScore, int* labels,
-                       int* lengths, float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                       hipStream_t s, BeamSil sil, bool mt = false) {
-  const bool asg = trans != nullptr, isLex = lex != nullptr;
+// One xl search after its checks: rows, scan, finish.  K: the clipped beamToken; mt: the many-token scan
+static int beam_xl_run(const BeamReq& q, int K, bool mt) {
   BeamXlWs xw{};
-  beam_xl_layout(&xw, workspace, B, T, beam, K, isLex ? kBeamLex : kBeamLm, mt);
-  xw.w.c.sil = sil.token; xw.w.c.silScore = sil.score;
-  const BeamWideWs& ww = xw.w;
-  W2L_HIP_CHECK(hipMemsetAsync(ww.c.table, 0, (size_t)B * ww.c.cap * sizeof(u64), s));
-  const unsigned rows = (unsigned)((size_t)B * T);
-  const bool big = N > kRowThreads * kRowMaxPer;
-  if (asg && big)
-    hipLaunchKernelGGL((ctc_beam_rows<true, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
-  else if (asg)
-    hipLaunchKernelGGL((ctc_beam_rows<false, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
-  else if (!big)
-    hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
-  else
-    hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, ww.c);
-  W2L_LAUNCH_CHECK();
+  beam_xl_layout(&xw, q.workspace, q.B, q.T, q.beam, K, q.lex() ? kBeamLex : kBeamLm, mt);
+  if (const int rc = beam_rows_launch(q, &xw.w.c)) return rc;
 
-  const BeamTrans tr{trans, 0};   // gathered from global memory: the LDS is the hash's
-  int rc = W2L_OK;
-#define W2L_XL_SCAN(LA, POL, LEX)                                                                                                  \
-  rc = mt ? beam_xl_launch<LA, POL, LEX, true>(B, T, N, threshold, input, frames, xw, lex, lm, lmWeight, classScore, wordScore, tr, s) \
-          : beam_xl_launch<LA, POL, LEX>(B, T, N, threshold, input, frames, xw, lex, lm, lmWeight, classScore, wordScore, tr, s)
-  if (isLex) {
-    if (asg) { if (logAdd) W2L_XL_SCAN(true, BeamAsg, true); else W2L_XL_SCAN(false, BeamAsg, true); }
-    else { if (logAdd) W2L_XL_SCAN(true, BeamCtc, true); else W2L_XL_SCAN(false, BeamCtc, true); }
-  } else {
-    if (asg) { if (logAdd) W2L_XL_SCAN(true, BeamAsg, false); else W2L_XL_SCAN(false, BeamAsg, false); }
-    else { if (logAdd) W2L_XL_SCAN(true, BeamCtc, false); else W2L_XL_SCAN(false, BeamCtc, false); }
-  }
-#undef W2L_XL_SCAN
+  const BeamTrans tr{q.trans, 0};   // gathered from global memory: the LDS is the hash's
+  const int rc = beam_scan_dispatch(q.logAdd, q.asg, q.lex(), [&](auto la, auto pol, auto lx) {
+    constexpr bool kLa = decltype(la)::value, kLex = decltype(lx)::value;
+    using Pol = decltype(pol);
+    if (mt)
+      return beam_xl_launch<kLa, Pol, kLex, true>(q.B, q.T, q.N, q.threshold, q.input, q.frames, xw, q.lexicon, q.lm, q.lmWeight,
+                                                  q.classScore, q.wordScore, tr, q.stream);
+    return beam_xl_launch<kLa, Pol, kLex>(q.B, q.T, q.N, q.threshold, q.input, q.frames, xw, q.lexicon, q.lm, q.lmWeight, q.classScore,
+                                          q.wordScore, tr, q.stream);
+  });
   if (rc) return rc;
-  const int useEos = lm && lmHasEos ? 1 : 0;
-  if (isLex)
-    return beam_xl_finish_launch<true>(B, nbest, maxLen, maxWords, 0, xw, lex, lm, lmWeight, eosScore, useEos, labels, lengths,
-                                       scores, lmScores, words, wordCounts, s);
-  return beam_xl_finish_launch<false>(B, nbest, maxLen, 0, asg ? N + 1 : N, xw, nullptr, lm, lmWeight, eosScore, useEos, labels,
-                                      lengths, scores, lmScores, nullptr, nullptr, s);
+  const int useEos = q.lm && q.lmHasEos ? 1 : 0;
+  if (q.lex())
+    return beam_xl_finish_launch<true>(q.B, q.nbest, q.maxLen, q.maxWords, 0, xw, q.lexicon, q.lm, q.lmWeight, q.eosScore, useEos,
+                                       q.labels, q.lengths, q.scores, q.lmScores, q.words, q.wordCounts, q.stream);
+  return beam_xl_finish_launch<false>(q.B, q.nbest, q.maxLen, 0, q.asg ? q.N + 1 : q.N, xw, nullptr, q.lm, q.lmWeight, q.eosScore,
+                                      useEos, q.labels, q.lengths, q.scores, q.lmScores, nullptr, nullptr, q.stream);
 }
 
 }  // namespace w2l
-
-W2L_API size_t w2l_ctc_beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, false);
-}
-W2L_API size_t w2l_ctc_beam_lm_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, false);
-}
-W2L_API size_t w2l_ctc_beam_lex_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, false);
-}
-W2L_API size_t w2l_asg_beam_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm, true);
-}
-W2L_API size_t w2l_asg_beam_lex_xl_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::beam_xl_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex, true);
-}
-
-namespace w2l {
-// w2l_ctc_beam_search_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int ctc_beam_search_xl_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                   float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
-                                   float* scores, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
-  int K = 0;
-  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   false, mt))
-    return rc;
-  return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, nullptr, 0, 0.f, nullptr,
-                     nullptr, 0.f, 0.f, labels, lengths, scores, nullptr, 0, nullptr, nullptr, workspace, (hipStream_t)stream, sil, mt);
-}
-}  // namespace w2l
-
-W2L_API int w2l_ctc_beam_search_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                   float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
-                                   float* scores, void* workspace, w2l_stream_t stream) {
-  return w2l::ctc_beam_search_xl_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, labels,
-      lengths, scores, workspace, stream, w2l::BeamSil{});
-}
-
-namespace w2l {
-// w2l_ctc_beam_search_lm_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int ctc_beam_search_lm_xl_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                      float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                      int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
-                                      int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
-  if (!lmScores || !lm) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   false, mt))
-    return rc;
-  return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
-                     classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                     (hipStream_t)stream, sil, mt);
-}
-}  // namespace w2l
-
-W2L_API int w2l_ctc_beam_search_lm_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                      float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                      int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels,
-                                      int* lengths, float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  return w2l::ctc_beam_search_lm_xl_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
-      lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
-}
-
-namespace w2l {
-// w2l_ctc_beam_search_lex_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int ctc_beam_search_lex_xl_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                       float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                       int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
-                                       int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
-                                       int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
-  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   false, mt))
-    return rc;
-  return beam_xl_run(B, T, N, input, frames, nullptr, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
-                     nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                     (hipStream_t)stream, sil, mt);
-}
-}  // namespace w2l
-
-W2L_API int w2l_ctc_beam_search_lex_xl(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                       float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                       int lmHasEos, float lmWeight, const void* lexicon, float wordScore, float eosScore,
-                                       int* labels, int* lengths, float* scores, float* lmScores, int maxWords, int* words,
-                                       int* wordCounts, void* workspace, w2l_stream_t stream) {
-  return w2l::ctc_beam_search_lex_xl_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
-      lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-      stream, w2l::BeamSil{});
-}
-
-namespace w2l {
-// w2l_asg_beam_search_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int asg_beam_search_xl_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                   int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                   int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
-  if (!lmScores || !trans) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  if (!lm && (lmHasEos || classScore)) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   true, mt))
-    return rc;
-  return beam_xl_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
-                     classScore, nullptr, 0.f, eosScore, labels, lengths, scores, lmScores, 0, nullptr, nullptr, workspace,
-                     (hipStream_t)stream, sil, mt);
-}
-}  // namespace w2l
-
-W2L_API int w2l_asg_beam_search_xl(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                   int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm,
-                                   int lmHasEos, float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  return w2l::asg_beam_search_xl_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen,
-      lm, lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
-}
-
-namespace w2l {
-// w2l_asg_beam_search_lex_xl with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int asg_beam_search_lex_xl_do(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                       int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
-                                       const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
-                                       float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream, BeamSil sil, bool mt = false) {
-  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1 || !trans) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = beam_xl_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K,
-                                   true, mt))
-    return rc;
-  return beam_xl_run(B, T, N, input, frames, trans, beam, K, threshold, logAdd, normalize, nbest, maxLen, lm, lmHasEos, lmWeight,
-                     nullptr, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-                     (hipStream_t)stream, sil, mt);
-}
-}  // namespace w2l
-
-W2L_API int w2l_asg_beam_search_lex_xl(int B, int T, int N, const float* input, const int* frames, const float* trans, int beam,
-                                       int beamToken, float threshold, int logAdd, int normalize, int nbest, int maxLen,
-                                       const void* lm, int lmHasEos, float lmWeight, const void* lexicon, float wordScore,
-                                       float eosScore, int* labels, int* lengths, float* scores, float* lmScores, int maxWords,
-                                       int* words, int* wordCounts, void* workspace, w2l_stream_t stream) {
-  return w2l::asg_beam_search_lex_xl_do(B, T, N, input, frames, trans, beam, beamToken, threshold, logAdd, normalize, nbest,
-      maxLen, lm, lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words,
-      wordCounts, workspace, stream, w2l::BeamSil{});
-}

@@ -904,6 +904,5 @@ W2L_API int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, 
 #include "criterion_beam_stream.hpp"
 #include "criterion_beam_commit.hpp"
 #include "criterion_beam_xl.hpp"
-#include "criterion_beam_sil.hpp"
-#include "criterion_beam_mt.hpp"
 #include "criterion_beam_lextok.hpp"
+#include "criterion_beam_entry.hpp"

@@ -21,7 +21,8 @@
 // ctc_beam_layout), the tie key, its decoder and the stops of a selection (beam_key, beam_pick), the prefix table's find-or-make
 // (beam_node); for the workgroup scans of criterion_ctc_beam_lm.hpp and criterion_ctc_beam_lex.hpp beam_load_frame, beam_stay_front,
 // beam_select_round and beam_store_final; for the finishes beam_chain_len, beam_write_labels, beam_eos and beam_rerank; for the
-// entry points ctc_beam_check, ctc_beam_begin and ctc_beam_fused_scan; for the beam session of criterion_beam_stream.hpp, which
+// host side (criterion_beam_entry.hpp and the wide and xl runs) BeamReq with beam_sil_check, beam_req_check, beam_common_check and
+// beam_rows_launch, and ctc_beam_fused_scan; for the beam session of criterion_beam_stream.hpp, which
 // resumes the two workgroup scans from a stored beam, BeamCarry with beam_carry_begin / _load / _store and the bound of a walk up
 // the prefix table (BeamWalk).  The other two files keep what is particular to their search.
 // What the lattice is -- the acoustic sum of a stay and of an extension -- is a policy of the two workgroup scans: BeamCtc here,
@@ -57,7 +58,7 @@ struct CtcBeamWs {
   int* finU;                   // [B][64] lexicon node of the final entry of rank r            (null: but for kBeamLex)
   int K;
   unsigned cap;
-  int sil = -1;                // the silence class (the *_sil entry points of criterion_beam_sil.hpp); -1: none
+  int sil = -1;                // the silence class (BeamReq::sil, the *_sil entry points'); -1: none
   float silScore = 0.f;        // added to lp[sil] after the frame tokens are chosen: beam_sil_lp
 };
 
@@ -619,43 +620,93 @@ __global__ __launch_bounds__(64) void ctc_beam_finish(int M, int Lmax, CtcBeamWs
 // tokens = the classes that are tokens: N - 1 with a blank, N without (noBlank)
 static int ctc_beam_clip(int tokens, int beamToken) { return beamToken < tokens ? beamToken : tokens; }
 
-static size_t ctc_beam_workspace_size(int B, int T, int N, int beam, int beamToken, int variant, bool noBlank = false) {
-  if (B <= 0 || T <= 0 || N < 2 || beam <= 0 || beamToken <= 0) return 0;
-  const int K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
-  if (beam > kBeamMax || K > kBeamMax) return 0;
-  return ctc_beam_layout(nullptr, nullptr, B, T, beam, K, variant);
-}
+// ---- the host side of a whole search: one request, its checks, the row pass.  The route from a request to a kernel family, the
+// narrow family's run and every entry point are criterion_beam_entry.hpp's; the wide and xl runs are their headers'.
 
-// the arguments the three searches share; *K = the clipped beamToken.  Every W2L_EINVAL comes before W2L_EUNSUPPORTED, and a
-// search's own checks (all W2L_EINVAL) run before this one, so the code for a bad argument does not depend on which one is first.
-static int ctc_beam_check(int B, int T, int N, const float* input, int beam, int beamToken, float threshold, int nbest, int maxLen,
-                          const int* labels, const int* lengths, const float* scores, const void* workspace, int* K,
-                          bool noBlank = false) {
-  if (B <= 0 || T <= 0 || N < 2 || !input || !labels || !lengths || !scores || !workspace) return W2L_EINVAL;
-  if (beam <= 0 || beamToken <= 0 || nbest <= 0 || nbest > beam || maxLen <= 0) return W2L_EINVAL;
-  if (!(threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
-  *K = ctc_beam_clip(noBlank ? N : N - 1, beamToken);
-  if (beam > kBeamMax || *K > kBeamMax) return W2L_EUNSUPPORTED;
-  if ((size_t)T * beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;   // node ids are ints
+enum BeamKind { kSearchPlain = 0, kSearchLm = 1, kSearchLex = 2, kSearchLextok = 3 };   // w2l_beam_search_kind's values
+enum BeamFamily { kFamNarrow = 0, kFamWide = 1, kFamXl = 2, kFamMt = 3 };               // w2l_beam_family's values
+
+// Everything a search call carries; never crosses into device code.  asg: every class a token and `trans` required (an entry
+// point's name says so, not the pointer).  kind: the ASG token search is kSearchLm with or without an LM; kSearchPlain is CTC's.
+struct BeamReq {
+  int kind = kSearchPlain;
+  bool asg = false;
+  int B = 0, T = 0, N = 0;
+  const float* input = nullptr;
+  const int* frames = nullptr;
+  const float* trans = nullptr;
+  int beam = 0, beamToken = 0;
+  float threshold = 0.f;
+  int logAdd = 0, normalize = 0, nbest = 0, maxLen = 0;
+  const void* lm = nullptr;
+  int lmHasEos = 0;
+  float lmWeight = 0.f;
+  const float* classScore = nullptr;
+  const void* lexicon = nullptr;
+  float wordScore = 0.f;
+  float eosScore = 0.f;
+  int* labels = nullptr;
+  int* lengths = nullptr;
+  float* scores = nullptr;
+  float* lmScores = nullptr;
+  int maxWords = 0;
+  int* words = nullptr;
+  int* wordCounts = nullptr;
+  void* workspace = nullptr;
+  hipStream_t stream = nullptr;
+  BeamSil sil;
+
+  int tokens() const { return asg ? N : N - 1; }   // the classes that are tokens
+  bool lex() const { return kind >= kSearchLex; }
+};
+
+static bool beam_finite(float v) { return fabsf(v) < INFINITY; }
+
+// what the silence arguments add to a search's refusals
+static int beam_sil_check(const BeamReq& q) {
+  if (!beam_finite(q.sil.score) || q.sil.token < -1 || q.sil.token >= q.tokens()) return W2L_EINVAL;
   return W2L_OK;
 }
 
-// the start of a call: the workspace, an empty prefix table, the frame tokens of every row
-static int ctc_beam_begin(CtcBeamWs* ws, int variant, int B, int T, int N, const float* input, const int* frames, int beam, int K,
-                          int normalize, void* workspace, hipStream_t s, bool noBlank = false, BeamSil sil = BeamSil{}) {
-  ctc_beam_layout(ws, workspace, B, T, beam, K, variant);
-  ws->sil = sil.token; ws->silScore = sil.score;
-  W2L_HIP_CHECK(hipMemsetAsync(ws->table, 0, (size_t)B * ws->cap * sizeof(u64), s));
-  const unsigned rows = (unsigned)((size_t)B * T);
-  const bool big = N > kRowThreads * kRowMaxPer;
-  if (noBlank && big)
-    hipLaunchKernelGGL((ctc_beam_rows<true, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);
-  else if (noBlank)
-    hipLaunchKernelGGL((ctc_beam_rows<false, true>), dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);
-  else if (!big)
-    hipLaunchKernelGGL(ctc_beam_rows<false>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);
-  else
-    hipLaunchKernelGGL(ctc_beam_rows<true>, dim3(rows), dim3(kRowThreads), 0, s, T, N, normalize, input, frames, *ws);
+// no silence score: the search runs with BeamSil{}, whose token matches no class -- the sibling's kernels and bytes, no + 0
+static bool beam_sil_none(const BeamSil& sil) { return sil.token < 0 || sil.score == 0.f; }
+
+// a search's own refusals, all W2L_EINVAL; the plain CTC search has none
+static int beam_req_check(const BeamReq& q) {
+  if (q.asg && !q.trans) return W2L_EINVAL;
+  if (q.kind == kSearchPlain) return W2L_OK;
+  if (!q.lmScores || (!q.lm && !(q.asg && q.kind == kSearchLm))) return W2L_EINVAL;
+  if (q.lex() && (!q.lexicon || !q.words || !q.wordCounts || q.maxWords < 1)) return W2L_EINVAL;
+  if (!beam_finite(q.lmWeight) || !beam_finite(q.eosScore) || (q.lex() && !beam_finite(q.wordScore))) return W2L_EINVAL;
+  if (!q.lmHasEos && q.eosScore != 0.f) return W2L_EINVAL;
+  if (!q.lm && (q.lmHasEos || q.classScore)) return W2L_EINVAL;   // the ASG token search without an LM
+  return W2L_OK;
+}
+
+// The arguments every search shares, against a family's limits; *K = the clipped beamToken.  Every W2L_EINVAL comes before
+// W2L_EUNSUPPORTED, and the silence arguments' and the search's own checks (all W2L_EINVAL) run before this one, so the code for a
+// bad argument does not depend on which one is first.
+static int beam_common_check(const BeamReq& q, int maxBeam, int maxTokens, int* K) {
+  if (q.B <= 0 || q.T <= 0 || q.N < 2 || !q.input || !q.labels || !q.lengths || !q.scores || !q.workspace) return W2L_EINVAL;
+  if (q.beam <= 0 || q.beamToken <= 0 || q.nbest <= 0 || q.nbest > q.beam || q.maxLen <= 0) return W2L_EINVAL;
+  if (!(q.threshold >= 0.f)) return W2L_EINVAL;   // NaN or negative
+  *K = ctc_beam_clip(q.tokens(), q.beamToken);
+  if (q.beam > maxBeam || *K > maxTokens) return W2L_EUNSUPPORTED;
+  if ((size_t)q.T * q.beam > ((size_t)1 << 29)) return W2L_EUNSUPPORTED;   // node ids are ints
+  return W2L_OK;
+}
+
+// the start of a run after the workspace is laid out: the silence score, an empty prefix table, the frame tokens of every row
+static int beam_rows_launch(const BeamReq& q, CtcBeamWs* ws) {
+  ws->sil = q.sil.token; ws->silScore = q.sil.score;
+  W2L_HIP_CHECK(hipMemsetAsync(ws->table, 0, (size_t)q.B * ws->cap * sizeof(u64), q.stream));
+  const dim3 rows((unsigned)((size_t)q.B * q.T)), threads(kRowThreads);
+  const bool big = q.N > kRowThreads * kRowMaxPer;
+  auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, rows, threads, 0, q.stream, q.T, q.N, q.normalize, q.input, q.frames, *ws); };
+  if (q.asg && big) launch(ctc_beam_rows<true, true>);
+  else if (q.asg) launch(ctc_beam_rows<false, true>);
+  else if (!big) launch(ctc_beam_rows<false>);
+  else launch(ctc_beam_rows<true>);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }
@@ -672,27 +723,3 @@ static void ctc_beam_fused_scan(int W, int K, int logAdd, Launch&& launch) {
 }
 
 }  // namespace w2l
-
-W2L_API size_t w2l_ctc_beam_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamPlain);
-}
-
-W2L_API int w2l_ctc_beam_search(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                float threshold, int logAdd, int normalize, int nbest, int maxLen, int* labels, int* lengths,
-                                float* scores, void* workspace, w2l_stream_t stream) {
-  using namespace w2l;
-  int K = 0;
-  if (const int rc = ctc_beam_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K))
-    return rc;
-  hipStream_t s = (hipStream_t)stream;
-  CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamPlain, B, T, N, input, frames, beam, K, normalize, workspace, s)) return rc;
-  if (logAdd)
-    hipLaunchKernelGGL(ctc_beam_scan<true>, dim3((unsigned)B), dim3(64), 0, s, T, N, beam, threshold, input, frames, ws);
-  else
-    hipLaunchKernelGGL(ctc_beam_scan<false>, dim3((unsigned)B), dim3(64), 0, s, T, N, beam, threshold, input, frames, ws);
-  W2L_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_beam_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, ws, labels, lengths, scores);
-  W2L_LAUNCH_CHECK();
-  return W2L_OK;
-}

@@ -307,45 +307,3 @@ __global__ __launch_bounds__(64) void ctc_beam_lex_finish(int M, int Lmax, int m
 }
 
 }  // namespace w2l
-
-W2L_API size_t w2l_ctc_beam_lex_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLex);
-}
-
-namespace w2l {
-// w2l_ctc_beam_search_lex with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int ctc_beam_search_lex_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                    float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
-                                    float lmWeight, const void* lexicon, float wordScore, float eosScore, int* labels, int* lengths,
-                                    float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                                    w2l_stream_t stream, BeamSil sil) {
-  if (!lmScores || !lm || !lexicon || !words || !wordCounts || maxWords < 1) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY) || !(fabsf(wordScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = ctc_beam_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K))
-    return rc;
-  hipStream_t s = (hipStream_t)stream;
-  CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamLex, B, T, N, input, frames, beam, K, normalize, workspace, s, false, sil)) return rc;
-  ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
-    hipLaunchKernelGGL((ctc_beam_lex_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)B), dim3(decltype(th)::value), 0, s,
-                       T, N, beam, threshold, input, frames, ws, lexicon, lm, lmWeight, wordScore, BeamTrans{});
-  });
-  W2L_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_beam_lex_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, maxWords, ws, lexicon, lm, lmWeight,
-                     eosScore, lmHasEos ? 1 : 0, labels, lengths, scores, lmScores, words, wordCounts);
-  W2L_LAUNCH_CHECK();
-  return W2L_OK;
-}
-}  // namespace w2l
-
-W2L_API int w2l_ctc_beam_search_lex(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                    float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
-                                    float lmWeight, const void* lexicon, float wordScore, float eosScore, int* labels, int* lengths,
-                                    float* scores, float* lmScores, int maxWords, int* words, int* wordCounts, void* workspace,
-                                    w2l_stream_t stream) {
-  return w2l::ctc_beam_search_lex_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
-      lmHasEos, lmWeight, lexicon, wordScore, eosScore, labels, lengths, scores, lmScores, maxWords, words, wordCounts, workspace,
-      stream, w2l::BeamSil{});
-}

@@ -220,42 +220,3 @@ __global__ __launch_bounds__(64) void ctc_beam_lm_finish(int M, int Lmax, int eo
 }
 
 }  // namespace w2l
-
-W2L_API size_t w2l_ctc_beam_lm_workspace_size(int B, int T, int N, int beam, int beamToken) {
-  return w2l::ctc_beam_workspace_size(B, T, N, beam, beamToken, w2l::kBeamLm);
-}
-
-namespace w2l {
-// w2l_ctc_beam_search_lm with a silence class and score (BeamSil{}: none, the entry point below; else criterion_beam_sil.hpp)
-static int ctc_beam_search_lm_do(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                   float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
-                                   float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream, BeamSil sil) {
-  if (!lmScores || !lm) return W2L_EINVAL;
-  if (!(fabsf(lmWeight) < INFINITY) || !(fabsf(eosScore) < INFINITY)) return W2L_EINVAL;
-  if (!lmHasEos && eosScore != 0.f) return W2L_EINVAL;
-  int K = 0;
-  if (const int rc = ctc_beam_check(B, T, N, input, beam, beamToken, threshold, nbest, maxLen, labels, lengths, scores, workspace, &K))
-    return rc;
-  hipStream_t s = (hipStream_t)stream;
-  CtcBeamWs ws{};
-  if (const int rc = ctc_beam_begin(&ws, kBeamLm, B, T, N, input, frames, beam, K, normalize, workspace, s, false, sil)) return rc;
-  ctc_beam_fused_scan(beam, K, logAdd, [&](auto la, auto th) {
-    hipLaunchKernelGGL((ctc_beam_lm_scan<decltype(la)::value, decltype(th)::value>), dim3((unsigned)B), dim3(decltype(th)::value), 0, s,
-                       T, N, beam, threshold, input, frames, ws, lm, lmWeight, classScore, BeamTrans{});
-  });
-  W2L_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_beam_lm_finish, dim3((unsigned)B), dim3(64), 0, s, nbest, maxLen, N, ws, lm, lmWeight, eosScore,
-                     lmHasEos ? 1 : 0, labels, lengths, scores, lmScores);
-  W2L_LAUNCH_CHECK();
-  return W2L_OK;
-}
-}  // namespace w2l
-
-W2L_API int w2l_ctc_beam_search_lm(int B, int T, int N, const float* input, const int* frames, int beam, int beamToken,
-                                   float threshold, int logAdd, int normalize, int nbest, int maxLen, const void* lm, int lmHasEos,
-                                   float lmWeight, const float* classScore, float eosScore, int* labels, int* lengths,
-                                   float* scores, float* lmScores, void* workspace, w2l_stream_t stream) {
-  return w2l::ctc_beam_search_lm_do(B, T, N, input, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, lm,
-      lmHasEos, lmWeight, classScore, eosScore, labels, lengths, scores, lmScores, workspace, stream, w2l::BeamSil{});
-}

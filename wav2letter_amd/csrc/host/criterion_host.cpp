@@ -60,14 +60,6 @@ class CTCLossImpl : public SequenceCriterion {
     w2lCheck(w2l_batch_ctc_target_size(B, L, T, target, ts, c.stream), "ctc target size");
     w2lCheck(w2l_ctc_align(B, T, N, L, em, target, ts, frames, path, nullptr, kws, c.stream), "ctc align");
   }
-  size_t beamWorkspaceBytes(int B, int T, int N, int beam, int beamToken) const override {
-    return w2l_ctc_beam_workspace_size(B, T, N, beam, beamToken);
-  }
-  void beamSearch(Ctx& c, int B, int T, int N, const float* em, const int* frames, int beam, int beamToken, float threshold,
-                  bool logAdd, bool normalize, int nbest, int maxLen, int* labels, int* lengths, float* scores, void* ws) override {
-    w2lCheck(w2l_ctc_beam_search(B, T, N, em, frames, beam, beamToken, threshold, logAdd, normalize, nbest, maxLen, labels, lengths,
-                                 scores, ws, c.stream), "ctc beam search");
-  }
 
  private:
   int mode_;

@@ -1608,8 +1608,8 @@ void StreamingDecoder::reset(int slot) {
 // n-best beam search; inputSizes as in viterbiPathWithTarget.  trans == nullptr: the CTC searches (w2l_ctc_beam_search*), blank =
 // N-1; else the ASG searches (w2l_asg_beam_search*) under that transition matrix, every class a token; o.wide: their _wide twins, o.xl: their _xl twins,
 // o.manyTokens: their _mt twins
-static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, const float* trans, const af::array& input,
-                                      const af::array& inputSizes, const BeamSearchOptions& o) {
+static BeamSearchResult beamSearchAny(const float* trans, const af::array& input, const af::array& inputSizes,
+                                      const BeamSearchOptions& o) {
   if (o.xl && o.wide) throw std::invalid_argument("beamSearch: wide and xl name two kernel families, choose one");
   if (o.manyTokens && (o.wide || o.xl))
     throw std::invalid_argument("beamSearch: manyTokens is a kernel family of its own (beam up to 8192), not with wide or xl");
@@ -1626,18 +1626,25 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
   const int tokens = trans ? N : N - 1;
   if (o.lmToken && !o.lexicon) throw std::invalid_argument("beamSearch: lmToken needs lexicon (without one, lm alone is the token-LM search)");
   if (o.lmToken && o.xl) throw std::invalid_argument("beamSearch: lmToken has no xl family (narrow, or wide up to 1024)");
-  // the silence score: the *_sil entry points, which take the kernel family as an argument
-  const int family = o.xl ? 2 : o.wide ? 1 : 0;
+  // the kernel family and the silence score: one descriptor call (w2l_beam_search) names the entry point
   const int silToken = o.silToken >= 0 || !o.lexicon ? o.silToken : o.lexicon->silToken();
   const bool useSil = o.silScore != 0.f;
   if (useSil && silToken < 0) throw std::invalid_argument("beamSearch: silScore needs a silence token (silToken, or a lexicon that has one)");
-  const int mtSil = useSil ? silToken : -1;   // the *_mt entry points take the silence token and score themselves; -1: none
   BeamSearchResult r;
   r.labels = af::array(af::dim4(Lmax, o.nbest, B), af::s32);
   r.lengths = af::array(af::dim4(o.nbest, B), af::s32);
   r.scores = af::array(af::dim4(o.nbest, B));
-  const bool normalize = o.normalize < 0 ? (o.logAdd && !trans) : o.normalize != 0;
-  if (o.lexicon) {   // the search restricted to the lexicon's spellings, scored by a LM over words (w2l_ctc_beam_search_lex)
+  w2l_beam_search_desc d{};
+  d.family = o.manyTokens ? W2L_BEAM_MT : o.xl ? W2L_BEAM_XL : o.wide ? W2L_BEAM_WIDE : W2L_BEAM_NARROW;
+  d.B = B; d.T = T; d.N = N;
+  d.input = input.device<float>(); d.frames = frames; d.trans = trans;
+  d.beam = o.beamSize; d.beamToken = o.beamSizeToken; d.threshold = o.beamThreshold;
+  d.logAdd = o.logAdd; d.normalize = o.normalize < 0 ? (o.logAdd && !trans) : o.normalize != 0;
+  d.nbest = o.nbest; d.maxLen = Lmax;
+  d.silToken = useSil ? silToken : -1; d.silScore = o.silScore;   // silScore 0: no score, whatever the token
+  af::array lms;   // the ASG search without an LM writes LM sums nobody asked for
+  const char* with = "";
+  if (o.lexicon) {   // the search restricted to the lexicon's spellings, scored by a LM over words, or with lmToken over tokens
     if (!o.lm) throw std::invalid_argument("beamSearch: lexicon needs lm, a model over the lexicon's words");
     if (!o.classScore.isempty()) throw std::invalid_argument("beamSearch: classScore must be empty with a lexicon");
     if (o.lmToken && o.lm->numTokens() != o.lexicon->numTokens())
@@ -1648,233 +1655,52 @@ static BeamSearchResult beamSearchAny(const std::shared_ptr<CritState>& st, cons
       throw std::invalid_argument(trans ? "beamSearch: the lexicon's token count is not the emissions' N"
                                         : "beamSearch: the lexicon's token count is not the emissions' N - 1");
     if (o.maxWords < 0) throw std::invalid_argument("beamSearch: maxWords must not be negative");
-    const int maxWords = o.maxWords > 0 ? o.maxWords : Lmax;
-    r.lmScores = af::array(af::dim4(o.nbest, B));
-    r.words = af::array(af::dim4(maxWords, o.nbest, B), af::s32);
+    d.kind = o.lmToken ? W2L_SEARCH_LEXTOK : W2L_SEARCH_LEX;
+    d.maxWords = o.maxWords > 0 ? o.maxWords : Lmax;
+    r.words = af::array(af::dim4(d.maxWords, o.nbest, B), af::s32);
     r.wordCounts = af::array(af::dim4(o.nbest, B), af::s32);
-    if (o.lmToken) {   // the LM scores the tokens, the lexicon constrains them (w2l_*_beam_search_lextok); silScore 0: no score
-      auto wst = devAlloc((trans ? w2l_asg_beam_lextok_workspace_size : w2l_ctc_beam_lextok_workspace_size)(family, B, T, N, o.beamSize,
-                                                                                                        o.beamSizeToken) + 256);
-      const int st = useSil ? silToken : -1;
-      if (trans)
-        w2l::w2lCheck(w2l_asg_beam_search_lextok(family, B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
-                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                                 o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
-                                                 r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
-                                                 r.words.device<int>(), r.wordCounts.device<int>(), wst.get(), S(), st, o.silScore),
-                      "asg beam search with lexicon and token LM");
-      else
-        w2l::w2lCheck(w2l_ctc_beam_search_lextok(family, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
-                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                                 o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
-                                                 r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
-                                                 r.words.device<int>(), r.wordCounts.device<int>(), wst.get(), S(), st, o.silScore),
-                      "ctc beam search with lexicon and token LM");
-      af::sync();  // wst is released at return
-      return r;
+    d.lexicon = o.lexicon->deviceBlob(); d.wordScore = o.wordScore;
+    d.words = r.words.device<int>(); d.wordCounts = r.wordCounts.device<int>();
+    with = o.lmToken ? "lexicon and token LM" : "lexicon";
+  } else {
+    if (o.wordScore != 0.f || o.maxWords != 0) throw std::invalid_argument("beamSearch: wordScore and maxWords need lexicon");
+    if (!o.lm) {
+      if (o.lmWeight != 0.f || !o.classScore.isempty() || o.eosScore != 0.f)
+        throw std::invalid_argument("beamSearch: lmWeight, classScore and eosScore need lm");
+      d.kind = W2L_SEARCH_PLAIN;
+      if (trans) lms = af::array(af::dim4(o.nbest, B));
+    } else {   // the search fused with the n-gram LM over the tokens
+      if (o.lm->numTokens() != tokens)
+        throw std::invalid_argument(trans ? "beamSearch: the LM's token count is not the emissions' N"
+                                          : "beamSearch: the LM's token count is not the emissions' N - 1");
+      if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != tokens))
+        throw std::invalid_argument("beamSearch: classScore must be f32 with one entry per token class");
+      d.kind = W2L_SEARCH_LM;
+      d.classScore = o.classScore.isempty() ? nullptr : o.classScore.device<float>();
+      with = "LM";
     }
-    if (o.manyTokens) {
-      auto wsm = devAlloc((trans ? w2l_asg_beam_lex_mt_workspace_size : w2l_ctc_beam_lex_mt_workspace_size)(B, T, N, o.beamSize,
-                                                                                                        o.beamSizeToken) + 256);
-      if (trans)
-        w2l::w2lCheck(w2l_asg_beam_search_lex_mt(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
-                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                                 o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
-                                                 r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
-                                                 r.words.device<int>(), r.wordCounts.device<int>(), wsm.get(), S(), mtSil, o.silScore),
-                      "asg many-token beam search with lexicon");
-      else
-        w2l::w2lCheck(w2l_ctc_beam_search_lex_mt(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
-                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                                 o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
-                                                 r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
-                                                 r.words.device<int>(), r.wordCounts.device<int>(), wsm.get(), S(), mtSil, o.silScore),
-                      "ctc many-token beam search with lexicon");
-      af::sync();  // wsm is released at return
-      return r;
-    }
-    if (useSil) {
-      auto wss = devAlloc((trans ? w2l_asg_beam_lex_sil_workspace_size : w2l_ctc_beam_lex_sil_workspace_size)(family, B, T, N, o.beamSize,
-                                                                                                          o.beamSizeToken) + 256);
-      if (trans)
-        w2l::w2lCheck(w2l_asg_beam_search_lex_sil(family, B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
-                                                  o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                                  o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
-                                                  r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
-                                                  r.words.device<int>(), r.wordCounts.device<int>(), wss.get(), S(), silToken, o.silScore),
-                      "asg beam search with lexicon and silence score");
-      else
-        w2l::w2lCheck(w2l_ctc_beam_search_lex_sil(family, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
-                                                  o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                                  o.lmWeight, o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
-                                                  r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
-                                                  r.words.device<int>(), r.wordCounts.device<int>(), wss.get(), S(), silToken, o.silScore),
-                      "ctc beam search with lexicon and silence score");
-      af::sync();  // wss is released at return
-      return r;
-    }
-    auto wsx = devAlloc((trans ? (o.xl ? w2l_asg_beam_lex_xl_workspace_size : o.wide ? w2l_asg_beam_lex_wide_workspace_size : w2l_asg_beam_lex_workspace_size)
-                               : (o.xl ? w2l_ctc_beam_lex_xl_workspace_size : o.wide ? w2l_ctc_beam_lex_wide_workspace_size : w2l_ctc_beam_lex_workspace_size))(
-                            B, T, N, o.beamSize, o.beamSizeToken) + 256);
-    if (trans)
-      w2l::w2lCheck((o.xl ? w2l_asg_beam_search_lex_xl : o.wide ? w2l_asg_beam_search_lex_wide : w2l_asg_beam_search_lex)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
-                                            o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
-                                            o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
-                                            r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
-                                            r.words.device<int>(), r.wordCounts.device<int>(), wsx.get(), S()),
-                    "asg beam search with lexicon");
-    else
-      w2l::w2lCheck((o.xl ? w2l_ctc_beam_search_lex_xl : o.wide ? w2l_ctc_beam_search_lex_wide : w2l_ctc_beam_search_lex)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
-                                            normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
-                                            o.lexicon->deviceBlob(), o.wordScore, o.eosScore, r.labels.device<int>(),
-                                            r.lengths.device<int>(), r.scores.device<float>(), r.lmScores.device<float>(), maxWords,
-                                            r.words.device<int>(), r.wordCounts.device<int>(), wsx.get(), S()),
-                    "ctc beam search with lexicon");
-    af::sync();  // wsx is released at return
-    return r;
   }
-  if (o.wordScore != 0.f || o.maxWords != 0) throw std::invalid_argument("beamSearch: wordScore and maxWords need lexicon");
-  if (!o.lm) {
-    if (o.lmWeight != 0.f || !o.classScore.isempty() || o.eosScore != 0.f)
-      throw std::invalid_argument("beamSearch: lmWeight, classScore and eosScore need lm");
-    if (trans) {   // the lexicon-free ASG search is one entry point: a null LM means none
-      af::array lms(af::dim4(o.nbest, B));
-      if (o.manyTokens) {
-        auto wsm = devAlloc(w2l_asg_beam_mt_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-        w2l::w2lCheck(w2l_asg_beam_search_mt(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
-                                             o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, nullptr, 0, 0.f, nullptr, 0.f,
-                                             r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
-                                             lms.device<float>(), wsm.get(), S(), mtSil, o.silScore),
-                      "asg many-token beam search");
-        af::sync();  // wsm is released at return
-        return r;
-      }
-      if (useSil) {
-        auto wss = devAlloc(w2l_asg_beam_sil_workspace_size(family, B, T, N, o.beamSize, o.beamSizeToken) + 256);
-        w2l::w2lCheck(w2l_asg_beam_search_sil(family, B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
-                                              o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, nullptr, 0, 0.f, nullptr, 0.f,
-                                              r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
-                                              lms.device<float>(), wss.get(), S(), silToken, o.silScore),
-                      "asg beam search with silence score");
-        af::sync();  // wss is released at return
-        return r;
-      }
-      auto wsa = devAlloc((o.xl ? w2l_asg_beam_xl_workspace_size : o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-      w2l::w2lCheck((o.xl ? w2l_asg_beam_search_xl : o.wide ? w2l_asg_beam_search_wide : w2l_asg_beam_search)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
-                                        o.logAdd, normalize, o.nbest, Lmax, nullptr, 0, 0.f, nullptr, 0.f, r.labels.device<int>(),
-                                        r.lengths.device<int>(), r.scores.device<float>(), lms.device<float>(), wsa.get(), S()),
-                    "asg beam search");
-      af::sync();  // wsa is released at return
-      return r;
-    }
-  } else {   // the search fused with the n-gram LM (w2l_ctc_beam_search_lm)
-    if (o.lm->numTokens() != tokens)
-      throw std::invalid_argument(trans ? "beamSearch: the LM's token count is not the emissions' N"
-                                        : "beamSearch: the LM's token count is not the emissions' N - 1");
-    if (!o.classScore.isempty() && (o.classScore.type() != af::f32 || o.classScore.elements() != tokens))
-      throw std::invalid_argument("beamSearch: classScore must be f32 with one entry per token class");
+  if (o.lm) {
     r.lmScores = af::array(af::dim4(o.nbest, B));
-    if (o.manyTokens) {
-      auto wsm = devAlloc((trans ? w2l_asg_beam_mt_workspace_size : w2l_ctc_beam_lm_mt_workspace_size)(B, T, N, o.beamSize,
-                                                                                                   o.beamSizeToken) + 256);
-      const float* cs = o.classScore.isempty() ? nullptr : o.classScore.device<float>();
-      if (trans)
-        w2l::w2lCheck(w2l_asg_beam_search_mt(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
-                                             o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                             o.lmWeight, cs, o.eosScore, r.labels.device<int>(), r.lengths.device<int>(),
-                                             r.scores.device<float>(), r.lmScores.device<float>(), wsm.get(), S(), mtSil, o.silScore),
-                      "asg many-token beam search with LM");
-      else
-        w2l::w2lCheck(w2l_ctc_beam_search_lm_mt(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
-                                                o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                                o.lmWeight, cs, o.eosScore, r.labels.device<int>(), r.lengths.device<int>(),
-                                                r.scores.device<float>(), r.lmScores.device<float>(), wsm.get(), S(), mtSil, o.silScore),
-                      "ctc many-token beam search with LM");
-      af::sync();  // wsm is released at return
-      return r;
-    }
-    if (useSil) {
-      auto wss = devAlloc((trans ? w2l_asg_beam_sil_workspace_size : w2l_ctc_beam_lm_sil_workspace_size)(family, B, T, N, o.beamSize,
-                                                                                                     o.beamSizeToken) + 256);
-      const float* cs = o.classScore.isempty() ? nullptr : o.classScore.device<float>();
-      if (trans)
-        w2l::w2lCheck(w2l_asg_beam_search_sil(family, B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken,
-                                              o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                              o.lmWeight, cs, o.eosScore, r.labels.device<int>(), r.lengths.device<int>(),
-                                              r.scores.device<float>(), r.lmScores.device<float>(), wss.get(), S(), silToken, o.silScore),
-                      "asg beam search with LM and silence score");
-      else
-        w2l::w2lCheck(w2l_ctc_beam_search_lm_sil(family, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken,
-                                                 o.beamThreshold, o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(),
-                                                 o.lmWeight, cs, o.eosScore, r.labels.device<int>(), r.lengths.device<int>(),
-                                                 r.scores.device<float>(), r.lmScores.device<float>(), wss.get(), S(), silToken,
-                                                 o.silScore),
-                      "ctc beam search with LM and silence score");
-      af::sync();  // wss is released at return
-      return r;
-    }
-    auto wsl = devAlloc((trans ? (o.xl ? w2l_asg_beam_xl_workspace_size : o.wide ? w2l_asg_beam_wide_workspace_size : w2l_asg_beam_workspace_size)
-                               : (o.xl ? w2l_ctc_beam_lm_xl_workspace_size : o.wide ? w2l_ctc_beam_lm_wide_workspace_size : w2l_ctc_beam_lm_workspace_size))(
-                            B, T, N, o.beamSize, o.beamSizeToken) + 256);
-    if (trans)
-      w2l::w2lCheck((o.xl ? w2l_asg_beam_search_xl : o.wide ? w2l_asg_beam_search_wide : w2l_asg_beam_search)(B, T, N, input.device<float>(), frames, trans, o.beamSize, o.beamSizeToken, o.beamThreshold,
-                                        o.logAdd, normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
-                                        o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
-                                        r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
-                                        r.lmScores.device<float>(), wsl.get(), S()),
-                    "asg beam search with LM");
-    else
-      w2l::w2lCheck((o.xl ? w2l_ctc_beam_search_lm_xl : o.wide ? w2l_ctc_beam_search_lm_wide : w2l_ctc_beam_search_lm)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
-                                           normalize, o.nbest, Lmax, o.lm->deviceBlob(), o.lm->hasEos(), o.lmWeight,
-                                           o.classScore.isempty() ? nullptr : o.classScore.device<float>(), o.eosScore,
-                                           r.labels.device<int>(), r.lengths.device<int>(), r.scores.device<float>(),
-                                           r.lmScores.device<float>(), wsl.get(), S()),
-                    "ctc beam search with LM");
-    af::sync();  // wsl is released at return
-    return r;
+    d.lm = o.lm->deviceBlob(); d.lmHasEos = o.lm->hasEos(); d.lmWeight = o.lmWeight; d.eosScore = o.eosScore;
   }
-  if (o.manyTokens) {   // the LM-free CTC search's many-token twin
-    auto wsm = devAlloc(w2l_ctc_beam_mt_workspace_size(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-    w2l::w2lCheck(w2l_ctc_beam_search_mt(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold,
-                                         o.logAdd, normalize, o.nbest, Lmax, r.labels.device<int>(), r.lengths.device<int>(),
-                                         r.scores.device<float>(), wsm.get(), S(), mtSil, o.silScore),
-                  "ctc many-token beam search");
-    af::sync();  // wsm is released at return
-    return r;
-  }
-  if (useSil) {   // the LM-free CTC search with a silence score
-    auto wss = devAlloc(w2l_ctc_beam_sil_workspace_size(family, B, T, N, o.beamSize, o.beamSizeToken) + 256);
-    w2l::w2lCheck(w2l_ctc_beam_search_sil(family, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold,
-                                          o.logAdd, normalize, o.nbest, Lmax, r.labels.device<int>(), r.lengths.device<int>(),
-                                          r.scores.device<float>(), wss.get(), S(), silToken, o.silScore),
-                  "ctc beam search with silence score");
-    af::sync();  // wss is released at return
-    return r;
-  }
-  if (o.wide || o.xl) {   // the LM-free CTC search's wide and xl twins
-    auto wsw = devAlloc((o.xl ? w2l_ctc_beam_xl_workspace_size : w2l_ctc_beam_wide_workspace_size)(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-    w2l::w2lCheck((o.xl ? w2l_ctc_beam_search_xl : w2l_ctc_beam_search_wide)(B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
-                                           normalize, o.nbest, Lmax, r.labels.device<int>(), r.lengths.device<int>(),
-                                           r.scores.device<float>(), wsw.get(), S()),
-                  "ctc beam search");
-    af::sync();  // wsw is released at return
-    return r;
-  }
-  auto ws = devAlloc(st->impl->beamWorkspaceBytes(B, T, N, o.beamSize, o.beamSizeToken) + 256);
-  w2l::Ctx c;
-  c.stream = S();
-  st->impl->beamSearch(c, B, T, N, input.device<float>(), frames, o.beamSize, o.beamSizeToken, o.beamThreshold, o.logAdd,
-                       normalize, o.nbest, Lmax, r.labels.device<int>(),
-                       r.lengths.device<int>(), r.scores.device<float>(), ws.get());
-  af::sync();  // ws is released at return
+  d.labels = r.labels.device<int>(); d.lengths = r.lengths.device<int>(); d.scores = r.scores.device<float>();
+  d.lmScores = o.lm ? r.lmScores.device<float>() : trans ? lms.device<float>() : nullptr;
+  // what the call is named in an exception: "<ctc|asg> [many-token ]beam search[ with <LM | lexicon ...>][ and | with silence score]"
+  std::string what = std::string(trans ? "asg" : "ctc") + (o.manyTokens ? " many-token" : "") + " beam search";
+  if (*with) what += std::string(" with ") + with;
+  if (useSil && !o.manyTokens && !o.lmToken) what += *with ? " and silence score" : " with silence score";
+  auto ws = devAlloc(w2l_beam_search_workspace_size(&d) + 256);
+  w2l::w2lCheck(w2l_beam_search(&d, ws.get(), S()), what.c_str());
+  af::sync();  // ws (and lms) are released at return
   return r;
 }
 BeamSearchResult CTCLoss::beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& o) {
-  return beamSearchAny(stateOf(this), nullptr, input, inputSizes, o);
+  return beamSearchAny(nullptr, input, inputSizes, o);
 }
 BeamSearchResult ASGLoss::beamSearch(const af::array& input, const af::array& inputSizes, const BeamSearchOptions& o) {
   if ((int)input.dims(0) != N_) throw std::invalid_argument("ASGLoss: N doesn't match with the letter size");
-  return beamSearchAny(stateOf(this), params_[0].array().device<float>(), input, inputSizes, o);
+  return beamSearchAny(params_[0].array().device<float>(), input, inputSizes, o);
 }
 std::string CTCLoss::prettyString() const { return "ConnectionistTemporalClassificationCriterion"; }
 

@@ -293,19 +293,6 @@ class SequenceCriterion {
     (void)c; (void)B; (void)T; (void)N; (void)L; (void)emission; (void)target; (void)frames; (void)path; (void)ws; (void)critParams;
     throw std::logic_error(prettyString() + ": no forced alignment through this criterion object");
   }
-  // lexicon-free n-best beam search over the emissions (w2l_ctc_beam_search's arguments and outputs; ws: beamWorkspaceBytes of its
-  // own).  CTC only (ASG's best path is viterbiPath).
-  virtual size_t beamWorkspaceBytes(int B, int T, int N, int beam, int beamToken) const {
-    (void)B; (void)T; (void)N; (void)beam; (void)beamToken;
-    return 0;
-  }
-  virtual void beamSearch(Ctx& c, int B, int T, int N, const float* emission, const int* frames, int beam, int beamToken,
-                          float threshold, bool logAdd, bool normalize, int nbest, int maxLen, int* labels, int* lengths,
-                          float* scores, void* ws) {
-    (void)c; (void)B; (void)T; (void)N; (void)emission; (void)frames; (void)beam; (void)beamToken; (void)threshold; (void)logAdd;
-    (void)normalize; (void)nbest; (void)maxLen; (void)labels; (void)lengths; (void)scores; (void)ws;
-    throw std::logic_error(prettyString() + ": no beam search through this criterion object");
-  }
 };
 std::shared_ptr<SequenceCriterion> makeCTCLoss(int scaleMode);
 std::shared_ptr<SequenceCriterion> makeASGLoss(int N, int scaleMode, double transdiag);
