@@ -777,7 +777,8 @@ struct BeamSearchOptions {
   // the silence score (the w2l_*_sil entry points; the reference's --silscore): after the frame tokens have been chosen by the
   // acoustic lp alone, class silToken's frame score is lp + silScore wherever the search reads it.  silToken -1 with a lexicon: the
   // lexicon's silence token.  silScore != 0 without any silence token: std::invalid_argument.  silScore == 0: the search without it,
-  // the same bytes.  The streaming decoders below have no silence score: a non-zero silScore there is std::invalid_argument.
+  // the same bytes.  Of the streaming decoders below ManyTokenStreamingDecoder takes the pair; StreamingDecoder and
+  // WideStreamingDecoder have no silence score: a non-zero silScore there is std::invalid_argument.
   int silToken = -1;
   float silScore = 0.f;
   // with lexicon: lm is a model over the lexicon's TOKENS, not its words (the w2l_*_beam_search_lextok entry points; the reference's
@@ -786,7 +787,8 @@ struct BeamSearchOptions {
   bool lmToken = false;
   // every whole-utterance search above on the many-token kernels (the w2l_*_mt entry points): the same contract with W up to 8192 and
   // K, after clipping, up to 256 -- the --beamsizetoken of the reference's word-piece recipes; the xl kernels' bytes at K <= 64.
-  // With wide, xl or lmToken: std::invalid_argument; the streaming decoders refuse it too.
+  // With wide, xl or lmToken: std::invalid_argument.  StreamingDecoder and WideStreamingDecoder refuse it; the incremental form of
+  // these searches is ManyTokenStreamingDecoder.
   bool manyTokens = false;
 };
 struct BeamSearchResult {
@@ -833,9 +835,11 @@ class FL_COMPAT_API StreamingDecoder {
  protected:
   struct WideKernels {};   // WideStreamingDecoder's constructor
   StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& options, WideKernels);
+  struct ManyTokenKernels {};   // ManyTokenStreamingDecoder's constructor
+  StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& options, ManyTokenKernels);
 
  private:
-  void create(bool wideKernels);
+  void create(bool wideKernels, bool manyTokenKernels = false);
   BeamSearchOptions o_;
   std::shared_ptr<void> state_;
   void* h_ = nullptr;
@@ -853,6 +857,18 @@ class FL_COMPAT_API WideStreamingDecoder : public StreamingDecoder {
  public:
   WideStreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& options)
       : StreamingDecoder(slots, maxChunk, maxFrames, numLabels, options, WideKernels{}) {}
+};
+
+// fl_compat extension: StreamingDecoder on the many-token kernels (w2l_beam_session_create_mt): the result after any number of
+// frames is, bit for bit, CTCLoss::beamSearch with options.manyTokens = true over those frames alone, options.silToken / silScore
+// included (silToken -1 with a lexicon: the lexicon's silence token).  beamSize goes up to 8192, beamSizeToken (after clipping to
+// NLABEL - 1) up to 256 -- the streaming recipes' 500 / 100; beyond: std::runtime_error.  options.manyTokens is IGNORED: this class
+// is always many-token.  options.lmToken, wide or xl: std::invalid_argument.  The methods are StreamingDecoder's; commit() needs
+// beamSize <= 1024 (beyond: std::runtime_error, nothing changed).
+class FL_COMPAT_API ManyTokenStreamingDecoder : public StreamingDecoder {
+ public:
+  ManyTokenStreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& options)
+      : StreamingDecoder(slots, maxChunk, maxFrames, numLabels, options, ManyTokenKernels{}) {}
 };
 
 class FL_COMPAT_API ASGLoss : public SequenceCriterion {

@@ -1392,6 +1392,49 @@ int w2l_beam_session_reset(void* session, int slot);
 int w2l_beam_session_create_wide(const w2l_beam_session_desc* desc, void** session);
 size_t w2l_beam_session_wide_state_bytes(const w2l_beam_session_desc* desc);
 
+/* ---- the many-token beam session: the incremental form of the many-token CTC searches (csrc/criterion_beam_stream.hpp,
+ * csrc/criterion_beam_xl.hpp) ----------------------------------------------------------------------------------------
+ * w2l_beam_session_create_mt makes a session with the protocol above -- bind / step / counts / result / frames / reset / destroy /
+ * commit_bytes / commit / committed take any kind of session and dispatch on it -- whose beam goes up to 8192 and whose beamToken
+ * (after clipping to N - 1) up to 256, with the silence score of the many-token searches: the streaming recipes' 500 / 100.  The
+ * descriptor keeps its layout; silToken / silScore are arguments.
+ * THE CONTRACT is the wide session's with one name changed: for any slot, any split of its F frames into chunks (empty chunks
+ * count) and the other slots at any phase, the result is the whole-utterance search of the same variant ON THE MANY-TOKEN ENTRY
+ * POINTS at B = 1, T = F, frames = NULL over the concatenated rows in a buffer that begins at a 16-byte boundary, called with the
+ * same silToken / silScore -- W2L_BEAM_PLAIN: w2l_ctc_beam_search_mt, W2L_BEAM_LM: w2l_ctc_beam_search_lm_mt, W2L_BEAM_LEX:
+ * w2l_ctc_beam_search_lex_mt -- and labels, lengths, scores, lmScores, words and wordCounts are equal BIT FOR BIT in both logAdd
+ * modes, the end rule and the EOS term included.  Partial results, "asking changes nothing", the empty prefix in row 0 of a started
+ * slot without frames, the empty rows of a slot that was never started or was reset, nbest up to the beam, and W2L_BEAM_PLAIN's
+ * lmScores (0 for live rows, -inf for empty ones) read as above.  Two consequences of the many-token searches' own contract: at
+ * beamToken (clipped) <= 64 and beam <= 1024 with no silence score, a many-token session and a wide session return the same
+ * bytes; and silToken = -1 or silScore == 0 executes no + 0 (the session then runs with a silence class that matches no token).
+ *   w2l_beam_session_mt_state_bytes  the state buffer's size; 0 for a descriptor the many-token session refuses (it does not
+ *                                 depend on the silence pair).  Every part is 256-byte aligned: 3 S control ints; the chunk's row
+ *                                 pass, lse, lpb [S][maxChunk] and tokLp, tokC [S][maxChunk][K] (K = min(beamToken, N - 1), up to
+ *                                 256); S prefix tables of cap 8-byte edges (cap = the power of two >= max(64, 2 maxFrames beam));
+ *                                 S candidate lists of beam K slots + beam 8-byte keys (slots = 7 for W2L_BEAM_LEX, else 1); S
+ *                                 gone-mask areas of slots beam ceil(K / 64) 8-byte words; S stay areas of 2 beam floats (these
+ *                                 three are one frame's scratch, not carried); S pairs of ints (the current half of the slot's
+ *                                 beam, its entry count); the beam halves [S][2][kF][beam] of 4 bytes, kF = 9 for W2L_BEAM_LEX,
+ *                                 else 8; and the arrays the result reads: [S][beam] node, total, [S] count, [S][beam] LM state, LM
+ *                                 sum, and for W2L_BEAM_LEX lexicon node.  At beam 500, K = 100, maxFrames 1024 with a lexicon a
+ *                                 slot is 8 MiB of table, 2.7 MiB of candidate list and 55 KiB of masks.
+ * A step is the table copy, one clear per run of adjacent starting slots, the row pass and ONE scan launch (a workgroup of 1024
+ * threads per slot; its dynamic LDS, 16 bytes per entry of the beam rounded up to a power of two plus 3.2 KiB, up to 131 KiB, and
+ * the result's, up to 128 KiB, are asked for at bind); a result is the table copy and one launch.  Never synchronises, allocates
+ * nothing after bind.
+ * Refusals are the wide session's, in its order, before anything is enqueued or any count moves, with W2L_EINVAL first of all for
+ * a silScore that is not finite or a silToken outside -1 .. N - 2 (the many-token searches' rule), and W2L_EUNSUPPORTED for beam
+ * above 8192, for beamToken (after clipping to N - 1) above 256, and for maxFrames * beam > 2^29.  w2l_beam_session_create and
+ * w2l_beam_session_create_wide keep their own limits and messages.
+ * COMMIT: w2l_beam_session_commit works on a many-token session with beam <= 1024 under the contract below (exactness,
+ * stability, maximality, overflow, budget), stated against a many-token session that never commits.  Above 1024 it is refused
+ * with W2L_EUNSUPPORTED before anything is enqueued (the walk is an entry per thread; the message names the limit), and
+ * w2l_beam_session_commit_bytes returns 0.
+ * A state buffer damaged between calls gives wrong hypotheses, never a spin or an access outside the buffer and the tables. */
+int w2l_beam_session_create_mt(const w2l_beam_session_desc* desc, int silToken, float silScore, void** session);
+size_t w2l_beam_session_mt_state_bytes(const w2l_beam_session_desc* desc);
+
 /* ---- committing the stable prefix of a beam session and compacting its table (csrc/criterion_beam_commit.hpp) -------
  * For either kind of session.  Every hypothesis a slot will ever return descends from one of its stored beam entries, so the
  * labels above the deepest common ancestor C of ALL stored entries (the lexicon variant's entries with an unfinished word, which

@@ -3,7 +3,7 @@
 
     python tools/audio_to_words.py [--wav FILE | --seconds 3 --seed 1] [--chunk-ms 160] [--commit-every 4]
                                    [--arch FILE] [--nlabel 29] [--checkpoint FILE] [--tokens FILE] [--beam 16]
-                                   [--local-norm-left N]
+                                   [--local-norm-left N] [--beam-token K] [--sil-token C] [--sil-score X]
 
     samples -> StreamingFeatures (log-mel, one launch per step) [-> StreamingLocalNorm (windowed normalisation, one launch per
     step, in place)] -> StreamingSession (chunked forward) -> StreamingDecoder (incremental CTC beam search), commit() every few
@@ -16,7 +16,12 @@ initial parameters and the labels are noise: a run of the plumbing.  --arch defa
 --tokens names the labels (one per line), else their numbers are printed.  Without --local-norm-left the features are not
 normalised (a model trained through the Python trainer and PrefetchLoader(local_norm=None) sees them that way);
 --local-norm-left=N normalises every frame over itself and the N frames before it, the features a model trained with
---localnrmlleftctx=N (and no right context) through `Train` or PrefetchLoader(local_norm=(N, 0)) sees."""
+--localnrmlleftctx=N (and no right context) through `Train` or PrefetchLoader(local_norm=(N, 0)) sees.
+--beam-token (default: the beam, at most the token classes), --sil-token and --sil-score are the decoder's --beamsizetoken and
+--silscore.  With none of the three and --beam up to 64 the decoder is StreamingDecoder, as before; a beam up to 1024 with at most
+64 tokens is WideStreamingDecoder; more than 64 tokens per frame, a beam above 1024 or a silence score pick
+ManyTokenStreamingDecoder (the streaming recipe's 500 / 100 is --beam=500 --beam-token=100), which commits at a beam up to 1024:
+above that the tool prints the whole hypothesis at the end."""
 import argparse
 import os
 import sys
@@ -28,7 +33,8 @@ import torch
 
 from wav2letter_amd import checkpoint, recipes
 from wav2letter_amd.features import Mfsc
-from wav2letter_amd.streaming import StreamingDecoder, StreamingFeatures, StreamingLocalNorm, StreamingSession
+from wav2letter_amd.streaming import (ManyTokenStreamingDecoder, StreamingDecoder, StreamingFeatures, StreamingLocalNorm, StreamingSession,
+                                     WideStreamingDecoder)
 from wav2letter_amd.trainer import Trainer
 
 
@@ -65,6 +71,9 @@ if __name__ == "__main__":
     ap.add_argument("--tokens")
     ap.add_argument("--beam", type=int, default=16)
     ap.add_argument("--local-norm-left", type=int, default=None, help="normalise over this many frames of left context")
+    ap.add_argument("--beam-token", type=int, default=None, help="tokens kept per frame (default: the beam)")
+    ap.add_argument("--sil-token", type=int, default=None, help="the silence class of --sil-score")
+    ap.add_argument("--sil-score", type=float, default=0.0, help="added to the silence class's frame score")
     a = ap.parse_args()
 
     x, fs = read_wav(a.wav) if a.wav else (synthetic(a.seconds, a.fs, a.seed), a.fs)
@@ -84,7 +93,15 @@ if __name__ == "__main__":
     norm = StreamingLocalNorm(a.filters, 1, feats.max_out, a.local_norm_left) if a.local_norm_left is not None else None
     net = StreamingSession(tr, 1, feats.max_out)
     max_frames = fe.num_frames(len(x)) + 64   # emission frames never outnumber feature frames (plus the flush)
-    dec = StreamingDecoder(1, net.max_out, max_frames, a.nlabel, beam=a.beam, beam_token=min(a.beam, a.nlabel - 1))
+    tokens = min(a.beam if a.beam_token is None else a.beam_token, a.nlabel - 1)
+    if tokens > 64 or a.beam > 1024 or a.sil_score != 0.0:
+        dec = ManyTokenStreamingDecoder(1, net.max_out, max_frames, a.nlabel, beam=a.beam, beam_token=tokens, sil_token=a.sil_token,
+                                        sil_score=a.sil_score)
+    elif a.beam > 64:
+        dec = WideStreamingDecoder(1, net.max_out, max_frames, a.nlabel, beam=a.beam, beam_token=tokens)
+    else:
+        dec = StreamingDecoder(1, net.max_out, max_frames, a.nlabel, beam=a.beam, beam_token=tokens)
+    commits = a.beam <= 1024 or not isinstance(dec, ManyTokenStreamingDecoder)
 
     pcm = torch.zeros(1, chunk, dtype=torch.int16, device="cuda")
     steps = max(1, -(-len(x) // chunk))
@@ -100,7 +117,7 @@ if __name__ == "__main__":
         dec.step(out, n_out, st)
         frames += int(nf[0])
         emitted += int(n_out[0])
-        if (i + 1) % a.commit_every == 0 or i == steps - 1:
+        if commits and ((i + 1) % a.commit_every == 0 or i == steps - 1):
             labels, _ = dec.commit()[0]
             if len(labels):
                 print(f"[{(i + 1) * chunk / fs:7.2f} s] {show(labels)}", flush=True)

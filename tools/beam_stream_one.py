@@ -17,7 +17,12 @@ trapezoid rule).  The session's final hypotheses are checked bit for bit against
   -- committed ++ tail == the uncommitted rows, scores the same bits, after every commit and at the end.  Then one JSON line per
   shape: the median one-frame step of the committing session, the median commit (the C call, host clock: it waits for the stream),
   per slot and as a multiple of the step, the nodes a commit leaves and the labels committed, and the utterance with commits
-  against the utterance without in the same run (host clock, both synchronised at the end)."""
+  against the utterance without in the same run (host clock, both synchronised at the end).
+  --mt: the many-token session (w2l_beam_session_create_mt) against the many-token whole search (the w2l_*_mt entry
+  points) at B = S in the same run: (W, K) = (500, 100) -- the streaming recipes' pair --, (500, 64) and (2500, 100), S = 1 / 16 /
+  64, chunks of 1 and 4; then, at W = 500, K = 64 where both families exist, the wide session and the many-token session side by
+  side ("family"), each against its own whole search, nothing routed.  With --commit-every=K: the commit leg at W = 500, K = 100 on
+  the many-token session alone."""
 import json
 import os
 import statistics
@@ -32,7 +37,7 @@ import torch
 from ctc_beam_lm_one import HOT
 from ctc_beam_lm_one import model as token_model
 from wav2letter_amd import criterion
-from wav2letter_amd.streaming import StreamingDecoder, WideStreamingDecoder
+from wav2letter_amd.streaming import ManyTokenStreamingDecoder, StreamingDecoder, WideStreamingDecoder
 
 T, N = 188, 9998
 
@@ -61,14 +66,22 @@ def events(fn, n):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
-def bench(S, chunk, W, reps, opts, wide=False):
+def family(wide, mt):
+    """(name, session class, ctc_beam_search's wide=) of a kernel family"""
+    if mt:
+        return "mt", ManyTokenStreamingDecoder, "mt"
+    return ("wide", WideStreamingDecoder, True) if wide else ("narrow", StreamingDecoder, False)
+
+
+def bench(S, chunk, W, reps, opts, wide=False, K=None, mt=False):
     g = torch.Generator(device="cpu").manual_seed(11)
     x = torch.randn(S, T, N, generator=g)
     x[:, :, :HOT] += 2.0
     x = x.cuda()
-    K = min(W, 64)
+    K = K or min(W, 64)
+    fam, cls, whole_family = family(wide, mt)
     o = dict(beam=W, beam_token=K, threshold=float("inf"), log_add=False, normalize=False, **opts)
-    dec = (WideStreamingDecoder if wide else StreamingDecoder)(S, chunk, T, N, **o)
+    dec = cls(S, chunk, T, N, **o)
     steps = [(x[:, t:t + chunk].contiguous() if t + chunk <= T else
               torch.cat([x[:, t:], torch.zeros(S, chunk - (T - t), N, device="cuda")], 1), min(chunk, T - t)) for t in range(0, T, chunk)]
     one = np.ones(S, np.int32)
@@ -78,7 +91,7 @@ def bench(S, chunk, W, reps, opts, wide=False):
             dec.step(em, one * c, one * (i == 0))
 
     def whole(F=T):
-        return criterion.ctc_beam_search(x[:, :F].contiguous() if F < T else x, nbest=1, max_len=T, wide=wide, **o)
+        return criterion.ctc_beam_search(x[:, :F].contiguous() if F < T else x, nbest=1, max_len=T, wide=whole_family, **o)
 
     utterance()
     got, want = dec.result(nbest=1, max_len=T), whole()
@@ -99,23 +112,23 @@ def bench(S, chunk, W, reps, opts, wide=False):
     # the sum over the prefixes a chunked caller would search again, by the trapezoid rule over the timed lengths
     ends = list(range(chunk, T, chunk)) + [T]
     research = float(np.interp(ends, marks, tp).sum())
-    return {"family": "wide" if wide else "narrow", "S": S, "chunk": chunk, "W": W, "K": K, "steps": len(steps), "step_us_median": round(statistics.median(lat), 1),
+    return {"family": fam, "S": S, "chunk": chunk, "W": W, "K": K, "steps": len(steps), "step_us_median": round(statistics.median(lat), 1),
             "session_us_per_utterance": round(t_utt, 1), "session_us_per_frame": round(t_utt / T, 2), "result_us": round(res, 1),
             "whole_us": round(t_whole, 1), "whole_us_per_frame": round(t_whole / T, 2), "ratio": round(t_utt / t_whole, 2),
             "per_step_constant_us": round((t_utt - t_whole) / len(steps), 1), "research_from_zero_us": round(research, 1),
             "research_over_session": round(research / t_utt, 1)}
 
 
-def bench_commit(S, W, every, reps, opts, wide):
+def bench_commit(S, W, every, reps, opts, wide, K=None, mt=False):
     from wav2letter_amd import _lib
     L = _lib.lib()
     g = torch.Generator(device="cpu").manual_seed(11)
     x = torch.randn(S, T, N, generator=g)
     x[:, :, :HOT] += 2.0
     x = x.cuda()
-    K = min(W, 64)
+    K = K or min(W, 64)
+    fam, cls, _ = family(wide, mt)
     o = dict(beam=W, beam_token=K, threshold=float("inf"), log_add=False, normalize=False, **opts)
-    cls = WideStreamingDecoder if wide else StreamingDecoder
     a, b = cls(S, 1, T, N, **o), cls(S, 1, T, N, **o)
     steps = [x[:, t:t + 1].contiguous() for t in range(T)]
     one = np.ones(S, np.int32)
@@ -178,7 +191,7 @@ def bench_commit(S, W, every, reps, opts, wide):
         if i % every == every - 1:
             commit(b, False)
     step, com = statistics.median(lat), statistics.median(commits)
-    return {"family": "wide" if wide else "narrow", "S": S, "W": W, "K": K, "commit_every": every, "scratch_bytes": scratch.numel(),
+    return {"family": fam, "S": S, "W": W, "K": K, "commit_every": every, "scratch_bytes": scratch.numel(),
             "step_us_median": round(step, 1), "commit_us_median": round(com, 1), "commit_us_max": round(max(commits), 1),
             "commit_us_per_slot": round(com / S, 1), "commit_over_step": round(com / step, 2),
             "live_nodes_mean": round(statistics.mean(lives), 1), "labels_committed_mean": round(statistics.mean(done), 1),
@@ -188,6 +201,25 @@ def bench_commit(S, W, every, reps, opts, wide):
 
 if __name__ == "__main__":
     every = [int(a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--commit-every=")]
+    mt = "--mt" in sys.argv[1:]
+    if mt:
+        args = [a for a in sys.argv[1:] if not a.startswith("--")]
+        variant = args[0] if len(args) > 0 else "lm"
+        reps = int(args[1]) if len(args) > 1 else 3
+        opts = tables(variant)
+        print(json.dumps({"variant": variant, "T": T, "N": N, "reps": reps, "mt": True, "commit_every": every[0] if every else None}), flush=True)
+        if every:
+            for S in (1, 16, 64):
+                print(json.dumps(bench_commit(S, 500, every[0], reps, opts, False, K=100, mt=True)), flush=True)
+            sys.exit(0)
+        for W, K in ((500, 100), (500, 64), (2500, 100)):
+            for S in (1, 16, 64):
+                for chunk in (1, 4):
+                    print(json.dumps(bench(S, chunk, W, reps, opts, K=K, mt=True)), flush=True)
+        for S in (1, 16, 64):
+            for chunk in (1, 4):
+                print(json.dumps(bench(S, chunk, 500, reps, opts, wide=True)), flush=True)   # the mt lines at (500, 64) are above
+        sys.exit(0)
     if every:
         args = [a for a in sys.argv[1:] if not a.startswith("--")]
         variant = args[0] if len(args) > 0 else "lm"

@@ -300,6 +300,8 @@ class _SIGS:
     w2l_beam_session_reset = (_i, [_p, _i])
     w2l_beam_session_create_wide = (_i, [_p, _p])
     w2l_beam_session_wide_state_bytes = (_sz, [_p])
+    w2l_beam_session_create_mt = (_i, [_p, _i, _f, _p])
+    w2l_beam_session_mt_state_bytes = (_sz, [_p])
     w2l_beam_session_commit_bytes = (_sz, [_p])
     w2l_beam_session_commit = (_i, [_p, _p, _p, _sz, _i, _p, _i, _p, _p, _p, _p, _p])
     w2l_beam_session_committed = (_i, [_p, _i, _p, _p])

@@ -1,6 +1,6 @@
 // criterion_beam_commit.hpp -- w2l_beam_session_commit: the stable prefix of a beam session's slot handed out, its prefix table
 // rebuilt with the nodes that live entries still descend from (contract: include/w2l_hip.h).  Included after
-// criterion_beam_stream.hpp, whose sessions (narrow and wide) it works on.
+// criterion_beam_stream.hpp, whose sessions (narrow, wide, and many-token up to a beam of 1024) it works on.
 // A slot's stored beam is n entries, each at a node of the slot's prefix table.  The deepest node C that is an ancestor-or-self of
 // every entry's node spells what no later frame can change: every hypothesis the search will ever return descends from an entry of
 // today.  The new root is C's PARENT: C's own label stays in the table, so no live entry sits at node 0 with a real last label, a
@@ -9,7 +9,7 @@
 // Per flagged slot, in stream order, against ONE slot's worth of scratch:
 //   clear   the scratch table (a memset)
 //   walk    beam_commit_walk, ONE workgroup, thread j = entry j (256 threads for a narrow session: 64 entries, and the label padding
-//           strides; 1024 for a wide one: an entry per thread, as its scan and finish): depths, the cut (the entries level their
+//           strides; 1024 for a wide or many-token one: an entry per thread): depths, the cut (the entries level their
 //           nodes to the smallest depth, then step up together until all stand on one node), the committed labels and words in
 //           root-to-cut order, or the refusal when they do not fit (nothing of the slot changed); then every entry re-inserts its
 //           chain below the new root top-down into the scratch table with beam_node (find-or-make: entries that share an ancestor
@@ -32,7 +32,7 @@ struct BeamCommit {
   int* node;         // the slot's stored node and parent ids, nmax of each
   int* par;
   const int* finN;   // the slot's entry count
-  int nmax;          // 64, or the wide session's beam
+  int nmax;          // 64, or the wide or many-token session's beam
   int* stack;        // scratch [D][nmax]
   int D;
   int steps;         // no chain has more labels
@@ -47,9 +47,27 @@ __device__ __forceinline__ int beam_commit_up(const u64* tab, const BeamWalk& g,
   return beam_walk_ok(g, p) ? (int)(tab[p - 1] >> 32) : 0;
 }
 
-template <int kThreads>
-__global__ __launch_bounds__(kThreads) void beam_commit_walk(BeamCommit a) {
+// The many-token session's one more kernel argument (beam <= 1024: an entry per thread).  a.node / a.par are those of half 0 of the
+// slot's beam; the current half is curn[0] on the device (a dead beam stops flipping: the frame count does not tell); a half is
+// halfWords ints; finNode, which the session's finish reads, follows the half's node ids.
+struct BeamCommitMt {
+  const int* curn;
+  int halfWords;
+  int* finNode;
+};
+template <class C>
+__device__ __forceinline__ const C& beam_commit_mt(const C& c) { return c; }
+
+// Mt: nothing (the narrow and wide sessions, whose kernels are what they were before there was an Mt) or a BeamCommitMt
+template <int kThreads, class... Mt>
+__global__ __launch_bounds__(kThreads) void beam_commit_walk(BeamCommit a, Mt... mt) {
   __shared__ int sMin, sRef, sDiff, sStop, sWords;
+  if constexpr (sizeof...(Mt) > 0) {
+    const BeamCommitMt& m = beam_commit_mt(mt...);
+    const size_t off = (size_t)(m.curn[0] & 1) * m.halfWords;
+    a.node += off;
+    a.par += off;
+  }
   const int tid = threadIdx.x;
   const int n = min(max(*a.finN, 0), min(a.nmax, kThreads));
   BeamWalk g;
@@ -146,6 +164,7 @@ __global__ __launch_bounds__(kThreads) void beam_commit_walk(BeamCommit a) {
     }
     a.node[tid] = np;
     a.par[tid] = npar;
+    if constexpr (sizeof...(Mt) > 0) beam_commit_mt(mt...).finNode[tid] = np;
   }
 }
 
@@ -174,7 +193,7 @@ struct BeamCommitLayout {
 };
 
 static size_t beam_commit_layout(BeamCommitLayout* L, void* scratch, const BeamSession& s) {
-  const size_t nmax = s.wide ? (size_t)s.d.beam : (size_t)kBeamMax;
+  const size_t nmax = s.wide || s.mt ? (size_t)s.d.beam : (size_t)kBeamMax;
   char* p = (char*)scratch;
   char* const p0 = p;
   auto take = [&](size_t bytes) { char* q = p; p += align_up(bytes, 256); return q; };
@@ -190,7 +209,9 @@ static size_t beam_commit_layout(BeamCommitLayout* L, void* scratch, const BeamS
 W2L_API size_t w2l_beam_session_commit_bytes(void* session) {
   using namespace w2l;
   if (!session) return 0;
-  return beam_commit_layout(nullptr, nullptr, *(BeamSession*)session);
+  const BeamSession& s = *(BeamSession*)session;
+  if (s.mt && s.d.beam > kBeamWideMax) return 0;   // the walk is an entry per thread
+  return beam_commit_layout(nullptr, nullptr, s);
 }
 
 W2L_API int w2l_beam_session_commit(void* session, const int* h_commit, void* scratch, size_t scratchBytes, int maxLen, int* labels,
@@ -198,6 +219,9 @@ W2L_API int w2l_beam_session_commit(void* session, const int* h_commit, void* sc
   using namespace w2l;
   if (!session) return beam_session_fail(W2L_EINVAL, "beam session commit: null session");
   BeamSession& s = *(BeamSession*)session;
+  if (s.mt && s.d.beam > kBeamWideMax)
+    return beam_session_fail(W2L_EUNSUPPORTED, "beam session commit: a many-token session commits at a beam up to 1024 (the walk is an "
+                                               "entry per thread), this one has " + std::to_string(s.d.beam));
   const size_t need = beam_commit_layout(nullptr, nullptr, s);
   if (!scratch || ((uintptr_t)scratch & 255))
     return beam_session_fail(W2L_EINVAL, "beam session commit: the scratch buffer must be a 256-byte aligned device pointer");
@@ -211,12 +235,13 @@ W2L_API int w2l_beam_session_commit(void* session, const int* h_commit, void* sc
     return beam_session_fail(W2L_EINVAL, "beam session commit: the lexicon variant writes words (maxWords >= 1)");
   if (!h_nLabels) return beam_session_fail(W2L_EINVAL, "beam session commit: null h_nLabels");
   if (!s.bound) return beam_session_fail(W2L_EINVAL, "beam session commit: no state bound (w2l_beam_session_bind first)");
-  const int S = s.d.slots, nmax = s.wide ? s.d.beam : kBeamMax;
+  const int S = s.d.slots, nmax = s.wide || s.mt ? s.d.beam : kBeamMax;
   hipStream_t st = (hipStream_t)stream;
   BeamCommitLayout L;
   beam_commit_layout(&L, scratch, s);
-  const CtcBeamWs& ws = s.wide ? s.WL.ww.c : s.L.ws;
-  int* const par = s.wide ? s.WL.cy.par : s.L.cy.par;
+  const CtcBeamWs& ws = beam_session_ws(s);
+  int* const par = s.wide ? s.WL.cy.par : s.L.cy.par;   // not the many-token session's: its ids are in the halves of its beam
+  const int half = (lex ? 9 : 8) * nmax;                 // the many-token session: the ints of a half
   std::vector<char> run(S, 0);
   bool any = false;
   for (int i = 0; i < S; ++i) {
@@ -238,7 +263,12 @@ W2L_API int w2l_beam_session_commit(void* session, const int* h_commit, void* sc
       a.maxLen = maxLen; a.maxWords = lex ? maxWords : 0;
       a.labels = labels + (size_t)i * maxLen; a.words = lex ? words + (size_t)i * maxWords : nullptr;
       a.out = L.out + 4 * i;
-      if (s.wide) hipLaunchKernelGGL(beam_commit_walk<kWideThreads>, dim3(1), dim3(kWideThreads), 0, st, a);
+      if (s.mt) {
+        a.node = s.ML.xw.beam + (size_t)i * 2 * half;
+        a.par = a.node + nmax;
+        hipLaunchKernelGGL((beam_commit_walk<kWideThreads, BeamCommitMt>), dim3(1), dim3(kWideThreads), 0, st, a,
+                           BeamCommitMt{s.ML.cy.curn + 2 * i, half, ws.finNode + (size_t)i * nmax});
+      } else if (s.wide) hipLaunchKernelGGL(beam_commit_walk<kWideThreads>, dim3(1), dim3(kWideThreads), 0, st, a);
       else hipLaunchKernelGGL(beam_commit_walk<256>, dim3(1), dim3(256), 0, st, a);
       W2L_LAUNCH_CHECK();
       hipLaunchKernelGGL(beam_commit_copy, dim3(blocks), dim3(256), 0, st, a.tab, a.ntab, a.cap, a.out);

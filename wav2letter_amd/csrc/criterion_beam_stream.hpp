@@ -97,6 +97,61 @@ static size_t beam_session_wide_layout(BeamWideSessionLayout* L, void* state, in
   return (size_t)(p - p0);
 }
 
+// THE MANY-TOKEN SESSION (w2l_beam_session_create_mt; beam up to kBeamXlMax, beamToken up to kBeamMtMax, a silence score; DESIGN
+// 3.30): the same protocol, bookkeeping and row pass over the kernels of criterion_beam_xl.hpp.  The xl scan keeps both halves of
+// its beam in memory, so the stored beam is the halves themselves, with (cur, n) beside them.  State, every part 256-byte aligned:
+//   cnt, base, flag; lse, lpb, tokLp, tokC; table; cand   as the wide session's
+//   gone      [S][slots][W][ceil(K / 64)] u64;  stay [S][2][W] fp32                one frame's scratch, not carried
+//   curn      [S][2] int: the current half and its entry count
+//   beam      [S][2][kF][W] 4-byte words, kF = 9 with a lexicon, else 8
+//   finNode, finTot [S][W]; finN [S]; finState, finAcc [S][W]; with a lexicon finU [S][W]   what the finish reads
+struct BeamMtSessionLayout {
+  int* ctl;
+  BeamXlWs xw;
+  BeamXlCarry cy;
+};
+
+static size_t beam_session_mt_layout(BeamMtSessionLayout* L, void* state, int S, int maxChunk, int maxFrames, int W, int K, bool lex,
+                                     BeamSil sil) {
+  const size_t rows = (size_t)S * maxChunk, cap = ctc_beam_cap(maxFrames, W), ent = align_up((size_t)S * W * 4, 256);
+  const size_t slots = lex ? 7 : 1, candCap = (size_t)W * K * slots + (size_t)W;
+  char* p = (char*)state;
+  char* const p0 = p;
+  auto take = [&](size_t bytes) { char* q = p; p += align_up(bytes, 256); return q; };
+  int* ctl = (int*)take((size_t)3 * S * sizeof(int));
+  float* lse = (float*)take(rows * sizeof(float));
+  float* lpb = (float*)take(rows * sizeof(float));
+  float* tokLp = (float*)take(rows * K * sizeof(float));
+  int* tokC = (int*)take(rows * K * sizeof(int));
+  u64* table = (u64*)take((size_t)S * cap * sizeof(u64));
+  u64* cand = (u64*)take((size_t)S * candCap * sizeof(u64));
+  u64* gone = (u64*)take((size_t)S * slots * W * beam_mt_words(K) * sizeof(u64));
+  float* stay = (float*)take((size_t)S * 2 * W * sizeof(float));
+  int* curn = (int*)take((size_t)S * 2 * sizeof(int));
+  int* beam = (int*)take((size_t)S * 2 * (lex ? 9 : 8) * W * 4);
+  int* finNode = (int*)take(ent);
+  float* finTot = (float*)take(ent);
+  int* finN = (int*)take((size_t)S * sizeof(int));
+  int* finState = (int*)take(ent);
+  float* finAcc = (float*)take(ent);
+  int* finU = lex ? (int*)take(ent) : nullptr;
+  if (L) {
+    L->ctl = ctl;
+    L->xw.w.c = CtcBeamWs{lse, lpb, tokLp, tokC, table, finNode, finTot, finN, finState, finAcc, finU, K, (unsigned)cap, sil.token,
+                          sil.score};
+    L->xw.w.cand = cand; L->xw.w.candCap = candCap; L->xw.w.W = W;
+    L->xw.beam = beam; L->xw.gone = gone; L->xw.stay = stay; L->xw.hashN = 2 * beam_xl_pow2(W);
+    L->cy = BeamXlCarry{ctl, ctl + 2 * S, curn};
+  }
+  return (size_t)(p - p0);
+}
+
+// the session's kernels: the xl scan with kMt and kResume, the xl finish with kOpen, a BeamXlCarry behind their arguments
+template <bool kLogAdd, bool kLex>
+constexpr auto beam_stream_mt_scan = beam_xl_scan<kLogAdd, BeamCtc, kLex, true, true, BeamXlCarry>;
+template <bool kLex>
+constexpr auto beam_stream_mt_finish = beam_xl_finish<kLex, true, BeamXlCarry>;
+
 template <bool kLogAdd, bool kLex>
 __global__ __launch_bounds__(kWideThreads) void beam_stream_wide_scan(int T, int N, int W, float threshold,
                                                                       const float* __restrict__ x, BeamWideWs ww,
@@ -175,6 +230,9 @@ struct BeamSession {
   BeamSessionLayout L{};
   bool wide = false;          // w2l_beam_session_create_wide: the wide kernels over WL
   BeamWideSessionLayout WL{};
+  bool mt = false;            // w2l_beam_session_create_mt: the many-token kernels over ML
+  BeamMtSessionLayout ML{};
+  BeamSil sil;                // the many-token session's; BeamSil{} when there is no silence score
   bool bound = false;
   int* pinned[kBeamRing] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev[kBeamRing] = {nullptr, nullptr, nullptr, nullptr};
@@ -194,8 +252,15 @@ static int beam_session_fail(int rc, const std::string& m) {
   return rc;
 }
 
+enum BeamSessionKind { kSessNarrow = 0, kSessWide = 1, kSessMt = 2 };
+
+// the state a session's row pass writes and its finish reads, and its control ints
+static const CtcBeamWs& beam_session_ws(const BeamSession& s) { return s.mt ? s.ML.xw.w.c : s.wide ? s.WL.ww.c : s.L.ws; }
+static int* beam_session_ctl(const BeamSession& s) { return s.mt ? s.ML.ctl : s.wide ? s.WL.ctl : s.L.ctl; }
+
 // the descriptor against the whole searches' argument rules; *K = the clipped beamToken
-static int beam_session_check(const w2l_beam_session_desc* d, int* K, bool wide = false) {
+static int beam_session_check(const w2l_beam_session_desc* d, int* K, int kind = kSessNarrow) {
+  const bool wide = kind == kSessWide;
   if (!d) return beam_session_fail(W2L_EINVAL, "beam session: null descriptor");
   if (d->slots <= 0 || d->slots > 65535 || d->maxChunk <= 0 || d->maxFrames <= 0 || d->N < 2 || d->beam <= 0 || d->beamToken <= 0 ||
       !(d->threshold >= 0.f))
@@ -216,9 +281,11 @@ static int beam_session_check(const w2l_beam_session_desc* d, int* K, bool wide 
       return beam_session_fail(W2L_EINVAL, "beam session: the lexicon variant needs a lexicon table, a finite wordScore, no classScore");
   }
   *K = ctc_beam_clip(d->N - 1, d->beamToken);
+  if (kind == kSessMt && (d->beam > kBeamXlMax || *K > kBeamMtMax))
+    return beam_session_fail(W2L_EUNSUPPORTED, "many-token beam session: beam above 8192 or beamToken (clipped to N - 1) above 256");
   if (wide && (d->beam > kBeamWideMax || *K > kBeamMax))
     return beam_session_fail(W2L_EUNSUPPORTED, "wide beam session: beam above 1024 or beamToken (clipped to N - 1) above 64");
-  if (!wide && (d->beam > kBeamMax || *K > kBeamMax))
+  if (kind == kSessNarrow && (d->beam > kBeamMax || *K > kBeamMax))
     return beam_session_fail(W2L_EUNSUPPORTED, "beam session: beam and beamToken above 64 (the wide searches) are not incremental "
                                                "here; w2l_beam_session_create_wide takes a beam up to 1024");
   if ((size_t)d->maxFrames * d->beam > ((size_t)1 << 29))
@@ -262,7 +329,7 @@ static int beam_session_advance(const BeamSession& s, const int* n, const int* s
   return W2L_OK;
 }
 
-// f(std::bool_constant<logAdd>, std::bool_constant<lexicon>) for the session's instantiation of the wide scan
+// f(std::bool_constant<logAdd>, std::bool_constant<lexicon>) for the session's instantiation of the wide or many-token scan
 template <class F>
 static int beam_session_wide_kernel(const BeamSession& s, F&& f) {
   const bool lex = s.d.variant == W2L_BEAM_LEX;
@@ -285,7 +352,7 @@ static int beam_session_table(BeamSession& s, int** table) {
 }
 static int beam_session_send(BeamSession& s, hipStream_t st) {
   const int r = s.ring;
-  W2L_HIP_CHECK(hipMemcpyAsync(s.wide ? s.WL.ctl : s.L.ctl, s.pinned[r], (size_t)3 * s.d.slots * sizeof(int), hipMemcpyHostToDevice, st));
+  W2L_HIP_CHECK(hipMemcpyAsync(beam_session_ctl(s), s.pinned[r], (size_t)3 * s.d.slots * sizeof(int), hipMemcpyHostToDevice, st));
   W2L_HIP_CHECK(hipEventRecord(s.ev[r], st));
   s.evUsed[r] = true;
   s.ring = (r + 1) % kBeamRing;
@@ -304,25 +371,39 @@ W2L_API size_t w2l_beam_session_state_bytes(const w2l_beam_session_desc* desc) {
 W2L_API size_t w2l_beam_session_wide_state_bytes(const w2l_beam_session_desc* desc) {
   using namespace w2l;
   int K = 0;
-  if (beam_session_check(desc, &K, true)) return 0;
+  if (beam_session_check(desc, &K, kSessWide)) return 0;
   return beam_session_wide_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K,
                                   desc->variant == W2L_BEAM_LEX);
 }
 
+W2L_API size_t w2l_beam_session_mt_state_bytes(const w2l_beam_session_desc* desc) {
+  using namespace w2l;
+  int K = 0;
+  if (beam_session_check(desc, &K, kSessMt)) return 0;
+  return beam_session_mt_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K,
+                                desc->variant == W2L_BEAM_LEX, BeamSil{});
+}
+
 namespace w2l {
-static int beam_session_make(const w2l_beam_session_desc* desc, void** session, bool wide) {
+static int beam_session_make(const w2l_beam_session_desc* desc, void** session, int kind, BeamSil sil = BeamSil{}) {
   if (!session) return beam_session_fail(W2L_EINVAL, "beam session: null session pointer");
   *session = nullptr;
+  if (kind == kSessMt && desc && (!beam_finite(sil.score) || sil.token < -1 || sil.token >= desc->N - 1))
+    return beam_session_fail(W2L_EINVAL, "many-token beam session: silScore must be finite, silToken -1 (none) or a token class "
+                                         "(0 .. N - 2)");
   int K = 0;
-  if (const int rc = beam_session_check(desc, &K, wide)) return rc;
+  if (const int rc = beam_session_check(desc, &K, kind)) return rc;
+  const bool wide = kind == kSessWide, mt = kind == kSessMt, lex = desc->variant == W2L_BEAM_LEX;
   BeamSession* s = new BeamSession();
   s->d = *desc;
   s->K = K;
   s->wide = wide;
+  s->mt = mt;
+  s->sil = beam_sil_none(sil) ? BeamSil{} : sil;   // no silence score: a token that matches no class, no + 0
   s->cap = ctc_beam_cap(desc->maxFrames, desc->beam);
-  s->stateBytes = wide ? beam_session_wide_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K,
-                                                  desc->variant == W2L_BEAM_LEX)
-                       : beam_session_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K);
+  s->stateBytes = mt ? beam_session_mt_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K, lex, s->sil)
+                  : wide ? beam_session_wide_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K, lex)
+                         : beam_session_layout(nullptr, nullptr, desc->slots, desc->maxChunk, desc->maxFrames, desc->beam, K);
   s->frames.assign(desc->slots, 0);
   s->active.assign(desc->slots, 0);
   s->doneLabels.assign(desc->slots, 0);
@@ -335,10 +416,13 @@ static int beam_session_make(const w2l_beam_session_desc* desc, void** session, 
 }  // namespace w2l
 
 W2L_API int w2l_beam_session_create(const w2l_beam_session_desc* desc, void** session) {
-  return w2l::beam_session_make(desc, session, false);
+  return w2l::beam_session_make(desc, session, w2l::kSessNarrow);
 }
 W2L_API int w2l_beam_session_create_wide(const w2l_beam_session_desc* desc, void** session) {
-  return w2l::beam_session_make(desc, session, true);
+  return w2l::beam_session_make(desc, session, w2l::kSessWide);
+}
+W2L_API int w2l_beam_session_create_mt(const w2l_beam_session_desc* desc, int silToken, float silScore, void** session) {
+  return w2l::beam_session_make(desc, session, w2l::kSessMt, w2l::BeamSil{silToken, silScore});
 }
 
 W2L_API void w2l_beam_session_destroy(void* session) { delete (w2l::BeamSession*)session; }
@@ -350,8 +434,9 @@ W2L_API int w2l_beam_session_bind(void* session, void* state, size_t bytes) {
   if (!state || ((uintptr_t)state & 255))
     return beam_session_fail(W2L_EINVAL, "beam session bind: the state buffer must be a 256-byte aligned device pointer");
   if (bytes < s.stateBytes)
-    return beam_session_fail(W2L_EINVAL, s.wide ? "beam session bind: the state buffer is smaller than w2l_beam_session_wide_state_bytes"
-                                                : "beam session bind: the state buffer is smaller than w2l_beam_session_state_bytes");
+    return beam_session_fail(W2L_EINVAL, s.mt     ? "beam session bind: the state buffer is smaller than w2l_beam_session_mt_state_bytes"
+                                         : s.wide ? "beam session bind: the state buffer is smaller than w2l_beam_session_wide_state_bytes"
+                                                  : "beam session bind: the state buffer is smaller than w2l_beam_session_state_bytes");
   const size_t tb = align_up((size_t)3 * s.d.slots * sizeof(int), 256);
   for (int r = 0; r < kBeamRing; ++r) {
     if (!s.pinned[r]) W2L_HIP_CHECK(hipHostMalloc((void**)&s.pinned[r], tb, hipHostMallocDefault));
@@ -367,7 +452,18 @@ W2L_API int w2l_beam_session_bind(void* session, void* state, size_t bytes) {
     });
     if (rc) return rc;
   }
-  if (s.wide) beam_session_wide_layout(&s.WL, state, s.d.slots, s.d.maxChunk, s.d.maxFrames, s.d.beam, s.K, s.d.variant == W2L_BEAM_LEX);
+  if (s.mt) {   // the scan's hash and the finish's keys (up to 131 and 128 KiB of dynamic LDS) are asked for here too
+    const int rc = beam_session_wide_kernel(s, [&](auto la, auto lx) -> int {
+      constexpr bool kLa = decltype(la)::value, kLx = decltype(lx)::value;
+      W2L_HIP_CHECK(hipFuncSetAttribute((const void*)beam_stream_mt_scan<kLa, kLx>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)kMtScanLdsMax));
+      W2L_HIP_CHECK(hipFuncSetAttribute((const void*)beam_stream_mt_finish<kLx>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)kXlFinishLdsMax));
+      return W2L_OK;
+    });
+    if (rc) return rc;
+    beam_session_mt_layout(&s.ML, state, s.d.slots, s.d.maxChunk, s.d.maxFrames, s.d.beam, s.K, s.d.variant == W2L_BEAM_LEX, s.sil);
+  } else if (s.wide) beam_session_wide_layout(&s.WL, state, s.d.slots, s.d.maxChunk, s.d.maxFrames, s.d.beam, s.K, s.d.variant == W2L_BEAM_LEX);
   else beam_session_layout(&s.L, state, s.d.slots, s.d.maxChunk, s.d.maxFrames, s.d.beam, s.K);
   s.bound = true;
   // another buffer holds no slot's search
@@ -415,12 +511,12 @@ W2L_API int w2l_beam_session_step(void* session, const float* emissions, const i
       if (!(h_start && h_start[i])) { ++i; continue; }
       int j = i + 1;
       while (j < S && h_start[j]) ++j;
-      W2L_HIP_CHECK(hipMemsetAsync((s.wide ? s.WL.ww.c.table : s.L.ws.table) + (size_t)i * s.cap, 0,
+      W2L_HIP_CHECK(hipMemsetAsync(beam_session_ws(s).table + (size_t)i * s.cap, 0,
                                    (size_t)(j - i) * s.cap * sizeof(u64), st));
       i = j;
     }
-    const CtcBeamWs& ws = s.wide ? s.WL.ww.c : s.L.ws;
-    const int* cnt = s.wide ? s.WL.cy.cnt : s.L.cy.cnt;
+    const CtcBeamWs& ws = beam_session_ws(s);
+    const int* cnt = beam_session_ctl(s);
     if (frames) {
       const unsigned rows = (unsigned)((size_t)S * C);
       if (N > kRowThreads * kRowMaxPer)
@@ -431,7 +527,15 @@ W2L_API int w2l_beam_session_step(void* session, const float* emissions, const i
                            cnt, ws);
       W2L_LAUNCH_CHECK();
     }
-    if (s.wide) {
+    if (s.mt) {
+      beam_session_wide_kernel(s, [&](auto la, auto lx) -> int {
+        constexpr bool kLa = decltype(la)::value, kLx = decltype(lx)::value;
+        hipLaunchKernelGGL((beam_stream_mt_scan<kLa, kLx>), dim3((unsigned)S), dim3(kXlThreads),
+                           (size_t)s.ML.xw.hashN * 8 + MtLds::bytes, st, C, N, W, s.d.threshold, emissions, (const int*)nullptr, s.ML.xw, s.d.lexicon, s.d.lm,
+                           s.d.lmWeight, s.d.classScore, s.d.wordScore, BeamTrans{nullptr, 0}, s.ML.cy);
+        return W2L_OK;
+      });
+    } else if (s.wide) {
       beam_session_wide_kernel(s, [&](auto la, auto lx) -> int {
         constexpr bool kLa = decltype(la)::value, kLx = decltype(lx)::value;
         hipLaunchKernelGGL((beam_stream_wide_scan<kLa, kLx>), dim3((unsigned)S), dim3(kWideThreads), WideLds<kLx>::bytes, st, C, N, W,
@@ -478,7 +582,16 @@ W2L_API int w2l_beam_session_result(void* session, int nbest, int maxLen, int* l
   for (int i = 0; i < S; ++i) { table[i] = s.frames[i]; table[S + i] = 0; table[2 * S + i] = s.active[i] ? 2 : 0; }
   if (const int rc = beam_session_send(s, st)) return rc;
   const int useEos = s.d.lmHasEos ? 1 : 0;
-  if (s.wide && lex)
+  const size_t mtLds = (size_t)beam_xl_pow2(s.d.beam) * 8 + (size_t)s.d.beam * 8 + 8;   // beam_xl_finish's keys, scores, LM sums
+  if (s.mt && lex)
+    hipLaunchKernelGGL(beam_stream_mt_finish<true>, dim3((unsigned)S), dim3(kXlThreads), mtLds, st, nbest, maxLen, maxWords, 0, s.ML.xw,
+                       s.d.lexicon, s.d.lm, s.d.lmWeight, s.d.eosScore, useEos, labels, lengths, scores, lmScores, words, wordCounts,
+                       s.ML.cy);
+  else if (s.mt)
+    hipLaunchKernelGGL(beam_stream_mt_finish<false>, dim3((unsigned)S), dim3(kXlThreads), mtLds, st, nbest, maxLen, 0, s.d.N, s.ML.xw,
+                       (const void*)nullptr, s.d.lm, s.d.lmWeight, s.d.eosScore, useEos, labels, lengths, scores, lmScores,
+                       (int*)nullptr, (int*)nullptr, s.ML.cy);
+  else if (s.wide && lex)
     hipLaunchKernelGGL(beam_stream_wide_finish<true>, dim3((unsigned)S), dim3(kWideThreads), 0, st, nbest, maxLen, maxWords, 0, s.WL.ww,
                        s.WL.cy, s.d.lexicon, s.d.lm, s.d.lmWeight, s.d.eosScore, useEos, labels, lengths, scores, lmScores, words,
                        wordCounts);

@@ -26,6 +26,9 @@
 //                        to kBeamMtMax = 256: 256 LDS slots of frame tokens, gone masks of ceil(K / 64) words per (slot, entry),
 //                        a tie key with 8 bits of k.  Every difference is an `if constexpr (kMt)`; !kMt is the xl scan, whose
 //                        instructions must not change.
+//   kResume, kOpen       the many-token beam session (criterion_beam_stream.hpp) is this scan with kMt and kResume and
+//                        this finish with kOpen, a BeamXlCarry behind their arguments (a parameter pack, empty for a whole search:
+//                        the whole searches' kernels keep their argument lists and their instructions).
 //   beam_xl_finish<lex>  one workgroup per utterance, strided over the final entries and then over the output rows; keys, scores
 //                        and LM sums in dynamic LDS (16 bytes per entry of pow2(W)).
 #pragma once
@@ -123,12 +126,31 @@ __device__ __forceinline__ void beam_mt_load_frame(const CtcBeamWs& ws, size_t r
   }
 }
 
-template <bool kLogAdd, class Pol, bool kLex, bool kMt = false>
+// ---- an xl beam that outlives the launch (the many-token beam session of criterion_beam_stream.hpp; kResume below)
+// Both halves of the beam already live in memory, so a slot's stored beam IS its halves: what a resume adds is which half is
+// current and how many entries it has.  cnt[slot]: the slot's frames of this step; flag[slot] bit 0: it starts from the empty
+// prefix, bit 1 (the finish): it is open; curn[slot]: (cur, n).  (cnt is followed by the slots' frame indices,
+// ctc_beam_rows<., ., true>'s.)
+struct BeamXlCarry {
+  const int *cnt, *flag;
+  int* curn;   // [S][2]
+};
+template <class C>
+__device__ __forceinline__ const C& beam_xl_carry(const C& c) { return c; }
+
+// kResume, with one more kernel argument, a BeamXlCarry (the pack Cy; a whole search has none, and its kernel is what it was before
+// there was a kResume, instruction for instruction): utterance b is a slot of a many-token beam session: its frame count (0: none)
+// and start flag come from cy.cnt / cy.flag -- the same in every thread, read before the first barrier, so the workgroup leaves or
+// stays as one --, cur and n from cy.curn unless the slot starts, and both go back there after the frames: they wait in memory, not
+// in scalars of their own across the frame loop.  What indexes memory is held to its range before the first frame (n
+// to W, node ids to the table, the last token to the row: thread j mends the entries it owns in place, the first frame's barrier
+// publishes them); LM states and lexicon nodes are clamped where they are used (ngram_q, lex_child, lex_node).
+template <bool kLogAdd, class Pol, bool kLex, bool kMt = false, bool kResume = false, class... Cy>
 __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, float threshold, const float* __restrict__ x,
                                                            const int* __restrict__ frames, BeamXlWs xw,
                                                            const void* __restrict__ lex, const void* __restrict__ lm,
                                                            float lmWeight, const float* __restrict__ classScore, float wordScore,
-                                                           BeamTrans tr) {
+                                                           BeamTrans tr, Cy... cy) {
   constexpr int kF = kLex ? 9 : 8, kSlots = kLex ? 7 : 1, kTh = kXlThreads;
   using Lds = XlLdsT<kMt ? kBeamMtMax : kBeamMax>;
   extern __shared__ float sAsgTrans[];   // BeamAsg::stage's array; nothing is staged here (tr.lds = 0)
@@ -146,7 +168,17 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
   const BeamWideWs& ww = xw.w;
   const CtcBeamWs& ws = ww.c;
   const int b = blockIdx.x, tid = threadIdx.x, K = ws.K;
-  const int F = align_frames(frames, b, T);
+  int F0;
+  bool fresh = true;
+  if constexpr (kResume) {
+    const BeamXlCarry& c = beam_xl_carry(cy...);
+    F0 = min(max(c.cnt[b], 0), T);
+    fresh = (c.flag[b] & 1) != 0;
+    if (F0 == 0 && !fresh) return;   // the whole workgroup, before any barrier
+  } else {
+    F0 = align_frames(frames, b, T);
+  }
+  const int F = F0;
   const float* xb = x + (size_t)b * T * N;
   u64* tab = ws.table + (size_t)b * ws.cap;
   const unsigned capm = ws.cap - 1;
@@ -171,14 +203,28 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
   auto ff = [&](int h, int f) { return (float*)(gBeam + ((size_t)h * kF + f) * W); };
 
   int cur = 0, n = 1;
+  if constexpr (kResume) {
+    if (!fresh) {
+      const BeamXlCarry& c = beam_xl_carry(cy...);
+      cur = c.curn[2 * b] & 1;
+      n = min(max(c.curn[2 * b + 1], 0), W);
+      for (int j = tid; j < n; j += kTh) {
+        const int node = fi(cur, 0)[j], e = fi(cur, 2)[j];
+        if ((unsigned)node > ws.cap) fi(cur, 0)[j] = 0;
+        if (e < -1 || e >= N - 1) fi(cur, 2)[j] = -1;
+      }
+    }
+  }
   if (tid == 0) {
     // The silence class and score wait in LDS for the stays, which read them where they use them.  As two more scalar kernel
     // arguments alive across the frame loop they cost this kernel, which stands at its scalar-register limit, more spilled scalars
     // in the loop (3 to 5 % of a CTC search at W = 1024).  The first frame's barrier publishes them.
     sMisc[5] = (unsigned)ws.sil; sMisc[6] = __float_as_uint(ws.silScore);
-    fi(0, 0)[0] = 0; fi(0, 1)[0] = -1; fi(0, 2)[0] = -1; fi(0, 3)[0] = useLm ? (int)((const NgramHeader*)lm)->start : 0;
-    ff(0, 4)[0] = 0.f; ff(0, 5)[0] = -INFINITY; ff(0, 6)[0] = 0.f; ff(0, 7)[0] = 0.f;
-    if constexpr (kLex) fi(0, 8)[0] = -1;
+    if (!kResume || fresh) {
+      fi(0, 0)[0] = 0; fi(0, 1)[0] = -1; fi(0, 2)[0] = -1; fi(0, 3)[0] = useLm ? (int)((const NgramHeader*)lm)->start : 0;
+      ff(0, 4)[0] = 0.f; ff(0, 5)[0] = -INFINITY; ff(0, 6)[0] = 0.f; ff(0, 7)[0] = 0.f;
+      if constexpr (kLex) fi(0, 8)[0] = -1;
+    }
   }
   for (int t = 0; t < F && n > 0; ++t) {
     const size_t row = row0 + t;
@@ -419,29 +465,47 @@ __global__ __launch_bounds__(kXlThreads) void beam_xl_scan(int T, int N, int W, 
     if constexpr (kLex) ws.finU[o] = live ? beam_wide_u(fi(cur, 8)[j]) : -1;
   }
   if (tid == 0) ws.finN[b] = n;
+  if constexpr (kResume) {
+    if (tid == 0) {
+      const BeamXlCarry& c = beam_xl_carry(cy...);
+      c.curn[2 * b] = cur; c.curn[2 * b + 1] = n;
+    }
+  }
 }
 
 // beam_wide_finish with thread r owning final entries r, r + 1024, ... and rows m, m + 1024, ...; dynamic LDS: pow2(W) keys, then
 // W scores, W LM sums and the count of the entries that count at the end
-template <bool kLex>
+// kOpen, with one more kernel argument, a BeamXlCarry (the many-token beam session's result): cy.flag[slot] bit 1 says the slot is
+// open -- a closed or never started slot has no entries: empty rows --, cy.cnt[slot] is the frames it has had (no prefix is longer)
+// and bounds the walks up the table with the table's size.  A whole search's kernel is what it was before there was a kOpen.
+template <bool kLex, bool kOpen = false, class... Cy>
 __global__ __launch_bounds__(kXlThreads) void beam_xl_finish(int M, int Lmax, int maxWords, int eosWord, BeamXlWs xw,
                                                              const void* __restrict__ lex, const void* __restrict__ lm,
                                                              float lmWeight, float eosScore, int useEos,
                                                              int* __restrict__ labels, int* __restrict__ lengths,
                                                              float* __restrict__ scores, float* __restrict__ lmScores,
-                                                             int* __restrict__ words, int* __restrict__ wordCounts) {
+                                                             int* __restrict__ words, int* __restrict__ wordCounts, Cy... cy) {
   extern __shared__ float sAsgTrans[];   // the only LDS of the kernel: the keys come first, 8-byte aligned at offset 0
   const BeamWideWs& ww = xw.w;
   const CtcBeamWs& ws = ww.c;
   const int b = blockIdx.x, tid = threadIdx.x, W = ww.W;
-  const int n = min(max(ws.finN[b], 0), W);
+  int n0 = min(max(ws.finN[b], 0), W);
+  if constexpr (kOpen) {
+    if (!(beam_xl_carry(cy...).flag[b] & 2)) n0 = 0;
+  }
+  const int n = n0;
   const int n2 = beam_xl_pow2(n);
   u64* const sKey = (u64*)sAsgTrans;
   float* const sScore = (float*)(sKey + beam_xl_pow2(W));
   float* const sAcc = sScore + W;
   unsigned* const sAlive = (unsigned*)(sAcc + W);
   const u64* tab = ws.table + (size_t)b * ws.cap;
-  const BeamWalk g{};
+  BeamWalk g0{};
+  if constexpr (kOpen) {
+    g0.capm = ws.cap - 1;
+    g0.steps = max(beam_xl_carry(cy...).cnt[b], 0);
+  }
+  const BeamWalk g = g0;
   if (tid == 0) *sAlive = 0u;
   __syncthreads();
   unsigned mine = 0u;

@@ -26,7 +26,8 @@
 // w2l_ctc_beam_search (lexicon-free n-best prefix beam search) lives in criterion_ctc_beam.hpp, included below with its siblings;
 // the beam searches of the ASG lattice (criterion_asg_beam.hpp) come last, on the same helpers and scans.
 // w2l_beam_session_* (the CTC searches continued chunk by chunk for streaming) lives in criterion_beam_stream.hpp.
-// w2l_*_beam_search*_xl (the five searches with a beam of up to 8192 entries) lives in criterion_beam_xl.hpp, included last.
+// w2l_*_beam_search*_xl (the five searches with a beam of up to 8192 entries) lives in criterion_beam_xl.hpp, included before the
+// sessions, whose many-token kind runs its kernels.
 // w2l_ctc_score (evaluation: loss and greedy path, no gradient) reads the emissions once, 4BTN:
 //   ctc_rows_score  the ctc_rows_lse pass (same arithmetic, template flag) that also writes the first-max argmax of the row
 //   ctc_scan_score  the alpha wave alone, grid (B, 1), lattice rows kept in registers: only the loss is written
@@ -901,8 +902,8 @@ W2L_API int w2l_ctc_viterbi(int B, int T, int N, const float* input, int* path, 
 #include "criterion_ctc_beam_lex.hpp"
 #include "criterion_asg_beam.hpp"
 #include "criterion_beam_wide.hpp"
+#include "criterion_beam_xl.hpp"
 #include "criterion_beam_stream.hpp"
 #include "criterion_beam_commit.hpp"
-#include "criterion_beam_xl.hpp"
 #include "criterion_beam_lextok.hpp"
 #include "criterion_beam_entry.hpp"

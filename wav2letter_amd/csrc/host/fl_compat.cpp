@@ -1482,11 +1482,24 @@ StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int n
     : o_(o), slots_(slots), maxChunk_(maxChunk), maxFrames_(maxFrames), nLabel_(numLabels) {
   create(true);
 }
-void StreamingDecoder::create(bool wideKernels) {
+StreamingDecoder::StreamingDecoder(int slots, int maxChunk, int maxFrames, int numLabels, const BeamSearchOptions& o, ManyTokenKernels)
+    : o_(o), slots_(slots), maxChunk_(maxChunk), maxFrames_(maxFrames), nLabel_(numLabels) {
+  if (o.wide || o.xl)
+    throw std::invalid_argument("ManyTokenStreamingDecoder: the many-token kernels are a family of their own (beam up to 8192), not "
+                                "with wide or xl");
+  create(false, true);
+}
+void StreamingDecoder::create(bool wideKernels, bool manyTokenKernels) {
   const BeamSearchOptions& o = o_;
-  if (o.silScore != 0.f) throw std::invalid_argument("StreamingDecoder: beam sessions have no silence score (silScore must be 0)");
+  if (!manyTokenKernels && o.silScore != 0.f)
+    throw std::invalid_argument("StreamingDecoder: beam sessions have no silence score (silScore must be 0)");
   if (o.lmToken) throw std::invalid_argument("StreamingDecoder: beam sessions have no token LM under a lexicon (lmToken must be false)");
-  if (o.manyTokens) throw std::invalid_argument("StreamingDecoder: beam sessions keep at most 64 tokens per frame (manyTokens must be false)");
+  if (!manyTokenKernels && o.manyTokens)
+    throw std::invalid_argument("StreamingDecoder: beam sessions keep at most 64 tokens per frame (manyTokens must be false)");
+  // the silence pair as CTCLoss::beamSearch reads it: the lexicon's silence token stands in for -1; a score of 0 is no score
+  const int silToken = o.silToken >= 0 || !o.lexicon ? o.silToken : o.lexicon->silToken();
+  if (manyTokenKernels && o.silScore != 0.f && silToken < 0)
+    throw std::invalid_argument("ManyTokenStreamingDecoder: silScore needs a silence token (silToken, or a lexicon that has one)");
   const int slots = slots_, maxChunk = maxChunk_, maxFrames = maxFrames_, numLabels = nLabel_;
   if (o.nbest < 1 || o.maxLen < 0 || o.maxWords < 0) throw std::invalid_argument("StreamingDecoder: bad nbest, maxLen or maxWords");
   w2l_beam_session_desc d{};
@@ -1511,10 +1524,14 @@ void StreamingDecoder::create(bool wideKernels) {
     if (!o.classScore.isempty()) d.classScore = o_.classScore.device<float>();
   }
   if (o.lm) { d.lm = o.lm->deviceBlob(); d.lmHasEos = o.lm->hasEos() ? 1 : 0; }
-  const int st = wideKernels ? w2l_beam_session_create_wide(&d, &h_) : w2l_beam_session_create(&d, &h_);
+  const int st = manyTokenKernels ? w2l_beam_session_create_mt(&d, o.silScore != 0.f ? silToken : -1, o.silScore, &h_)
+                 : wideKernels    ? w2l_beam_session_create_wide(&d, &h_)
+                                  : w2l_beam_session_create(&d, &h_);
   if (st == W2L_EUNSUPPORTED) throw std::runtime_error(std::string("StreamingDecoder: ") + w2l_host_last_error());
   if (st != W2L_OK) throw std::invalid_argument(std::string("StreamingDecoder: ") + w2l_host_last_error());
-  const size_t bytes = wideKernels ? w2l_beam_session_wide_state_bytes(&d) : w2l_beam_session_state_bytes(&d);
+  const size_t bytes = manyTokenKernels ? w2l_beam_session_mt_state_bytes(&d)
+                       : wideKernels    ? w2l_beam_session_wide_state_bytes(&d)
+                                        : w2l_beam_session_state_bytes(&d);
   doneLabels_.assign(slots, {});
   doneWords_.assign(slots, {});
   state_ = devAlloc(bytes);
@@ -1541,7 +1558,7 @@ StreamingDecoder::Committed StreamingDecoder::commit(const std::vector<int>& fla
   if (!flags.empty() && (int)flags.size() != slots_) throw std::invalid_argument("StreamingDecoder::commit: one flag per slot");
   if (!scratch_) {
     scratchBytes_ = w2l_beam_session_commit_bytes(h_);
-    scratch_ = devAlloc(scratchBytes_);
+    scratch_ = devAlloc(std::max<size_t>(scratchBytes_, 256));   // 0: a session that cannot commit, refused below
   }
   int maxLen = 1;   // no commit is longer than the labels a slot still holds
   for (int i = 0; i < slots_; ++i) maxLen = std::max(maxLen, frames(i) - (int)doneLabels_[i].size());

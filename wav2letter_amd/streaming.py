@@ -400,12 +400,15 @@ class StreamingDecoder:
             ptrs = tuple(t.data_ptr() if t is not None else None for t in self._keep)
         d = self._desc(*ptrs)
         h = C.c_void_p(0)
-        _check(getattr(self.L, self._create_fn)(C.byref(d), C.byref(h)), "streaming decoder")
+        _check(self._make(d, h), "streaming decoder")
         self.state_bytes = getattr(self.L, self._bytes_fn)(C.byref(d))
         if placeholders:
             self.L.w2l_beam_session_destroy(h)
         else:
             self.h = h
+
+    def _make(self, d, h):
+        return getattr(self.L, self._create_fn)(C.byref(d), C.byref(h))
 
     def __del__(self):
         try:
@@ -417,7 +420,8 @@ class StreamingDecoder:
 
     def _bind(self, device):
         self.device = device
-        self._create(placeholders=False)
+        if self.h is None:
+            self._create(placeholders=False)
         self._state = torch.empty(max(self.state_bytes, 256), dtype=torch.uint8, device=device)
         _check(self.L.w2l_beam_session_bind(self.h, self._state.data_ptr(), self._state.numel()), "streaming decoder bind")
 
@@ -437,6 +441,17 @@ class StreamingDecoder:
         _check(self.L.w2l_beam_session_step(self.h, emissions.data_ptr(), n.ctypes.data, st.ctypes.data,
                                             torch.cuda.current_stream().cuda_stream), "streaming decoder step")
         for s in np.nonzero(st)[0]:   # a slot that starts has committed nothing
+            self._forget(int(s))
+
+    def counts(self, counts, start=None):
+        """the bookkeeping of a step alone (w2l_beam_session_counts): counts / start are checked as step() checks them and the
+        slots' frame counts move as a step would move them; host arithmetic, nothing is enqueued (with an LM or a lexicon the
+        session is made here, with its device tables).  For a caller that keeps the counts of frames fed elsewhere in step."""
+        n, st = _flags(counts, self.slots, "counts"), _flags(start, self.slots, "start")
+        if self.h is None:
+            self._create(placeholders=False)
+        _check(self.L.w2l_beam_session_counts(self.h, n.ctypes.data, st.ctypes.data), "streaming decoder counts")
+        for s in np.nonzero(st)[0]:
             self._forget(int(s))
 
     def _forget(self, slot):
@@ -585,3 +600,27 @@ class WideStreamingDecoder(StreamingDecoder):
         super().__init__(slots, max_chunk, max_frames, nlabel, beam=beam, beam_token=beam_token, threshold=threshold, log_add=log_add,
                          normalize=normalize, lm=lm, lm_weight=lm_weight, class_score=class_score, eos_score=eos_score, lexicon=lexicon,
                          word_score=word_score, device=device)
+
+
+class ManyTokenStreamingDecoder(StreamingDecoder):
+    """ManyTokenStreamingDecoder(slots, max_chunk, max_frames, nlabel, **options): StreamingDecoder on the many-token kernels, an
+    incremental criterion.ctc_beam_search(..., wide="mt") (the contract is in include/w2l_hip.h, w2l_beam_session_create_mt).  The
+    arguments are StreamingDecoder's without `wide`, plus the silence score of ctc_beam_search: sil_token (None with a lexicon: the
+    lexicon's silence token) and sil_score (0: the search without it, the same bytes; non-zero without any silence token is
+    refused).  beam goes up to 8192, beam_token (after clipping to NLABEL - 1) up to 256: the streaming recipes' 500 / 100.  The
+    methods are StreamingDecoder's; commit() needs beam <= 1024 (beyond, W2LUnsupported and nothing changed)."""
+
+    _create_fn, _bytes_fn = "w2l_beam_session_create_mt", "w2l_beam_session_mt_state_bytes"
+
+    def __init__(self, slots, max_chunk, max_frames, nlabel, beam=500, beam_token=100, threshold=float("inf"), log_add=False,
+                 normalize=None, lm=None, lm_weight=0.0, class_score=None, eos_score=0.0, lexicon=None, word_score=0.0, sil_token=None,
+                 sil_score=0.0, device="cuda"):
+        from .criterion import _sil_args
+        sil = _sil_args("ManyTokenStreamingDecoder", sil_token, sil_score, lexicon)
+        self.sil_token, self.sil_score = sil if sil is not None else (-1, 0.0)
+        super().__init__(slots, max_chunk, max_frames, nlabel, beam=beam, beam_token=beam_token, threshold=threshold, log_add=log_add,
+                         normalize=normalize, lm=lm, lm_weight=lm_weight, class_score=class_score, eos_score=eos_score, lexicon=lexicon,
+                         word_score=word_score, device=device)
+
+    def _make(self, d, h):
+        return self.L.w2l_beam_session_create_mt(C.byref(d), int(self.sil_token), float(self.sil_score), C.byref(h))
