@@ -27,7 +27,7 @@
  * parameters / gradients in flat arenas: w2l_host.hpp); fl::Sequential::modules() lists its lines for prettyString
  * and parameter bookkeeping, the forward / backward run as a whole.  A plugin module (createModule) composes such
  * pipelines -- from arch text, or (round 5) from LAYER OBJECTS the way the reference's plugins are written:
- * fl::View / Reorder / Dropout / ReLU / GatedLinearUnit / LayerNorm / Linear / Conv2D / Pool2D / Transformer / TDSBlock /
+ * fl::View / Reorder / Dropout / ReLU / Swish / GatedLinearUnit / LayerNorm / Linear / Conv2D / Pool2D / Transformer / TDSBlock /
  * WeightNorm, constructed with the reference's arguments and add()ed to an fl::Sequential, are their lines of the arch
  * grammar, and the Sequential plans one pipeline out of them on first use (tests/cpp/plugin_layers.cpp).  What is NOT
  * provided is per-layer execution (`modules()[i]->forward(x)`, a custom forward() that interleaves af:: arithmetic, as
@@ -243,11 +243,19 @@ class Linear : public ArchLayer {
 class Conv2D : public ArchLayer {
  public:
   Conv2D(int nIn, int nOut, int wx, int wy, int sx = 1, int sy = 1, int px = 0, int py = 0, int dx = 1, int dy = 1, bool bias = true, int groups = 1)
-      : ArchLayer(dx == 1 && dy == 1 ? join("C2", {(double)nIn, (double)nOut, (double)wx, (double)wy, (double)sx, (double)sy, (double)px, (double)py})
-                                     : join("C2", {(double)nIn, (double)nOut, (double)wx, (double)wy, (double)sx, (double)sy, (double)px, (double)py, (double)dx, (double)dy})) {
-    if (!bias || groups != 1) throw std::invalid_argument("fl_compat: fl::Conv2D without bias / with groups is not in the arch grammar");
+      : ArchLayer(groups != 1 ? join("C", {(double)nIn, (double)nOut, (double)wx, (double)sx, (double)px, (double)dx, 1.0, (double)groups})
+                  : dx == 1 && dy == 1 ? join("C2", {(double)nIn, (double)nOut, (double)wx, (double)wy, (double)sx, (double)sy, (double)px, (double)py})
+                                       : join("C2", {(double)nIn, (double)nOut, (double)wx, (double)wy, (double)sx, (double)sy, (double)px, (double)py, (double)dx, (double)dy})) {
+    if (!bias) throw std::invalid_argument("fl_compat: fl::Conv2D without bias is not in the arch grammar");
+    // groups: the ninth field of a `C` line, which has no second axis -- a depthwise convolution over time (groups == nIn == nOut)
+    if (groups != 1 && !(groups == nIn && groups == nOut))
+      throw std::invalid_argument("fl_compat: fl::Conv2D with groups = " + std::to_string(groups) + ": besides 1, only depthwise (groups == nIn == nOut) is built");
+    if (groups != 1 && !(wy == 1 && sy == 1 && (py == 0 || py == -1) && dy == 1))
+      throw std::invalid_argument("fl_compat: a depthwise fl::Conv2D runs over time only (wy == 1, sy == 1, py 0 or -1, dy == 1)");
   }
 };
+// fl::Swish(beta): x * sigmoid(beta * x)
+class Swish : public ArchLayer { public: explicit Swish(double beta = 1.0) : ArchLayer(beta == 1.0 ? std::string("SH") : join("SH", {beta})) {} };
 enum class PoolingMode { MAX = 0 };
 class Pool2D : public ArchLayer {
  public:

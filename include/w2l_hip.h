@@ -733,6 +733,22 @@ int w2l_conv_backward_data_add(const w2l_conv_desc* d, const float* dy, const fl
                                const float* add, float* dx, w2l_stream_t stream);
 int w2l_conv_backward_filter(const w2l_conv_desc* d, const float* x, const float* dy, float* dw,
                              float* dbias, w2l_stream_t stream);
+/* Depthwise convolutions over time (fl::Conv2D with groups == nIn == nOut; arch line `C c c kw 1 pad 1 bias c`): one input channel
+ * per group, so w is [kw][C] (= [kw][Cin / groups][Cout]), bias [C]; x [B][T][H][C], y / dy [B][To][H][C] as w2l_conv_*, fp32
+ * throughout (conv_depthwise.hip).  Accepted: Cin == Cout, stride == 1, kw <= 64, any padl / padr >= 0 and H; anything else of a
+ * valid descriptor is W2L_EUNSUPPORTED (a descriptor that is no convolution at all -- a size below 1, To < 1 -- W2L_EINVAL).
+ * forward: y[b][t][h][c] = bias[c] + sum_k w[k][c] x[b][t - padl + k][h][c], taps outside 0 .. T-1 contributing nothing; every
+ *   output is one chain of fp32 fused multiply-adds over k ascending that starts at the bias (0 without one), so a frame's bits
+ *   depend on its own window alone, not on how the launch was cut into tiles.
+ * backward_data: dx[b][t][h][c] = sum_k w[k][c] dy[b][t + padl - k][h][c] (the same chain over the reversed filter).  dx must not be dy.
+ * backward_filter: dw[k][c] = sum_{b,t,h} dy[b][t][h][c] x[b][t - padl + k][h][c] and, unless dbias is NULL, dbias[c] = sum dy.
+ *   No atomics: segment partials go to `workspace` (w2l_conv_depthwise_workspace_floats(d) floats, 0 for a refused descriptor;
+ *   contents mean nothing between calls) and a second launch adds them in index order -- two runs give the same bits. */
+int w2l_conv_depthwise_forward(const w2l_conv_desc* d, const float* x, const float* w, const float* bias, float* y, w2l_stream_t stream);
+int w2l_conv_depthwise_backward_data(const w2l_conv_desc* d, const float* dy, const float* w, float* dx, w2l_stream_t stream);
+size_t w2l_conv_depthwise_workspace_floats(const w2l_conv_desc* d);
+int w2l_conv_depthwise_backward_filter(const w2l_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias, float* workspace,
+                                       w2l_stream_t stream);
 /* The kw x 1 convolutions over the mel rows of the TDS recipes in the mixed-precision mode (bf16 operand storage, see
  * w2l_gemm_bf16) -- fl::TDSBlock's time convolution (C -> C channels, stride 1) and the sub-sampling `C2 cin cout kw 1 s 1`
  * lines between the blocks (cin != cout <= 32 channels, stride 1 or 2, any padding): x / dy and the weights rounded to bf16,
@@ -958,6 +974,13 @@ int w2l_axpy(float* y, const float* x, size_t n, float alpha, w2l_stream_t strea
  * null pointer with n > 0.  n == 0 launches nothing. */
 int w2l_residual_join_forward(float* y, const float* a, const float* b, size_t n, float scale, int relu, w2l_stream_t stream);
 int w2l_residual_join_backward(float* g, const float* dy, const float* y, size_t n, float scale, int relu, w2l_stream_t stream);
+/* fl::Swish (arch token SH [beta]).  forward: y[i] = x[i] s, s = 1 / (1 + exp(-beta x[i])).  backward: dx[i] = dy[i] (s + beta x[i] s (1 - s)).
+ * exp is expf (not the hardware approximation): 1e-4 of the largest magnitude holds at |beta x| around 20; beta x below -88 gives s = 0.
+ * One launch over n floats; float4 where the pointers share their phase against 16 bytes (scalar head and tail), element by element
+ * where they do not.  dx may be exactly dy (and y exactly x); any other overlap is the caller's error.  W2L_EINVAL, before any
+ * launch: a non-finite beta; a null pointer with n > 0.  n == 0 launches nothing. */
+int w2l_swish_forward(const float* x, float* y, size_t n, float beta, w2l_stream_t stream);
+int w2l_swish_backward(const float* x, const float* dy, float* dx, size_t n, float beta, w2l_stream_t stream);
 int w2l_fill(float* y, size_t n, float v, w2l_stream_t stream);
 /* ema[i] = (float)decay * ema[i] + (float)(1 - decay) * p[i], fp32, ONE launch over a flat parameter arena: the averaged
  * "teacher" network of slimIPL (--slimIPL_ema, recipes/slimIPL/src/Train.cpp:1819-1832: one expression per parameter there).

@@ -226,6 +226,12 @@ class _SIGS:
     w2l_conv_backward_data = (_i, [_p, _p, _p, _p, _i, _p])
     w2l_conv_backward_data_add = (_i, [_p, _p, _p, _p, _p, _p])
     w2l_conv_backward_filter = (_i, [_p, _p, _p, _p, _p, _p])
+    w2l_conv_depthwise_forward = (_i, [_p, _p, _p, _p, _p, _p])
+    w2l_conv_depthwise_backward_data = (_i, [_p, _p, _p, _p, _p])
+    w2l_conv_depthwise_workspace_floats = (_sz, [_p])
+    w2l_conv_depthwise_backward_filter = (_i, [_p, _p, _p, _p, _p, _p, _p])
+    w2l_swish_forward = (_i, [_p, _p, _sz, _f, _p])
+    w2l_swish_backward = (_i, [_p, _p, _p, _sz, _f, _p])
     w2l_layernorm_scratch_doubles = (_sz, [_i, _sz])
     w2l_residual_layernorm_forward_images = (_i, [_i, _sz, _p, _p, _p, _p, _p, _f, _d, _u32, _u32, _p, _p, _p])
     w2l_layernorm_backward_images = (_i, [_i, _sz, _p, _p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _d, _u32, _u32, _p])

@@ -1473,3 +1473,76 @@ W2L_API int w2l_residual_join_backward(float* g, const float* dy, const float* y
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }
+
+// fl::Swish (arch token SH [beta], cpc/SequentialBuilder.cpp:483-489; host/net.cpp SwishLayer): y = x s, s = sigmoid(beta x), and
+// dx = dy (s + beta x s (1 - s)).  expf, not __expf: the sigmoid's tail at |beta x| around 20 is what the 1e-4 bar sees.  exp(-beta x)
+// overflows to +inf for beta x < -88 and s becomes 0 there, as it should.  Elements [0, head) and [head + 4 n4, n) go one by one,
+// the n4 float4 from `head` on as vectors (join_split: all arrays 16-byte aligned there, n4 = 0 when their phases differ).  dx may
+// be dy exactly: every element is read before it is written, by the thread that writes it -- so no __restrict__ here.
+// (No packed fp32 arithmetic in these two kernels, whichever way the file is built.)
+#define W2L_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+namespace w2l {
+
+__device__ __forceinline__ W2L_NO_PK_F32 float swish_sigmoid(float z) { return 1.f / (1.f + expf(-z)); }
+
+__global__ __launch_bounds__(kEwThreads) W2L_NO_PK_F32 void swish_fwd_k(const float* x, float* y, size_t n, size_t head, size_t n4, float beta) {
+  auto one = [&](float v) W2L_NO_PK_F32 { return v * swish_sigmoid(beta * v); };
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n4; i += stride) {
+    const size_t e = head + 4 * i;
+    const float4 v = *(const float4*)(x + e);
+    float4 r;
+    r.x = one(v.x); r.y = one(v.y); r.z = one(v.z); r.w = one(v.w);
+    *(float4*)(y + e) = r;
+  }
+  const size_t tail = head + (n4 << 2);
+  for (size_t i = tid; i < n - (n4 << 2); i += stride) {
+    const size_t e = i < head ? i : tail + (i - head);
+    y[e] = one(x[e]);
+  }
+}
+
+__global__ __launch_bounds__(kEwThreads) W2L_NO_PK_F32 void swish_bwd_k(const float* x, const float* dy, float* dx, size_t n, size_t head, size_t n4,
+                                                                       float beta) {
+  auto one = [&](float v, float g) W2L_NO_PK_F32 {
+    const float s = swish_sigmoid(beta * v);
+    return g * (s + beta * v * s * (1.f - s));
+  };
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = tid; i < n4; i += stride) {
+    const size_t e = head + 4 * i;
+    const float4 v = *(const float4*)(x + e), g = *(const float4*)(dy + e);
+    float4 r;
+    r.x = one(v.x, g.x); r.y = one(v.y, g.y); r.z = one(v.z, g.z); r.w = one(v.w, g.w);
+    *(float4*)(dx + e) = r;
+  }
+  const size_t tail = head + (n4 << 2);
+  for (size_t i = tid; i < n - (n4 << 2); i += stride) {
+    const size_t e = i < head ? i : tail + (i - head);
+    dx[e] = one(x[e], dy[e]);
+  }
+}
+
+}  // namespace w2l
+
+W2L_API int w2l_swish_forward(const float* x, float* y, size_t n, float beta, w2l_stream_t stream) {
+  if (!std::isfinite(beta)) return W2L_EINVAL;
+  if (!n) return W2L_OK;
+  if (!x || !y) return W2L_EINVAL;
+  size_t head, n4;
+  join_split(y, x, x, n, head, n4);
+  hipLaunchKernelGGL(swish_fwd_k, dim3(ew_grid((n >> 2) + 1)), dim3(kEwThreads), 0, W2L_S, x, y, n, head, n4, beta);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}
+
+W2L_API int w2l_swish_backward(const float* x, const float* dy, float* dx, size_t n, float beta, w2l_stream_t stream) {
+  if (!std::isfinite(beta)) return W2L_EINVAL;
+  if (!n) return W2L_OK;
+  if (!x || !dy || !dx) return W2L_EINVAL;
+  size_t head, n4;
+  join_split(dx, dy, x, n, head, n4);
+  hipLaunchKernelGGL(swish_bwd_k, dim3(ew_grid((n >> 2) + 1)), dim3(kEwThreads), 0, W2L_S, x, dy, dx, n, head, n4, beta);
+  W2L_LAUNCH_CHECK();
+  return W2L_OK;
+}

@@ -199,6 +199,32 @@ class ReLULayer : public Layer {
   }
 };
 
+// fl::Swish(beta) (arch token `SH [beta]`): y = x sigmoid(beta x), on any layout.  Keeps its input for backward and writes buffers
+// of its own in both directions.
+class SwishLayer : public Layer {
+ public:
+  bool streamGeom(StreamGeom& g, std::string&) const override { g = StreamGeom(); return true; }   // frame-local
+  float beta = 1.f;
+  size_t n = 0, yOff = 0, dxOff = 0;
+  const float* xSaved = nullptr;
+  std::string name() const override { return "Swish"; }
+  Act plan(const Act& in, Planner& pl) override {
+    n = in.numel();
+    yOff = pl.alloc(n);
+    dxOff = pl.alloc(n);
+    return in;
+  }
+  void forward(Ctx& c, float* arena, const float* x, float*& y) override {
+    y = arena + yOff;
+    xSaved = x;
+    w2lCheck(w2l_swish_forward(x, y, n, beta, c.stream), "swish fwd");
+  }
+  void backward(Ctx& c, float* arena, const float* dy, float*& dx, bool) override {
+    dx = arena + dxOff;
+    w2lCheck(w2l_swish_backward(xSaved, dy, dx, n, beta, c.stream), "swish bwd");
+  }
+};
+
 class DropoutLayer : public Layer {
  public:
   bool streamGeom(StreamGeom& g, std::string&) const override { g = StreamGeom(); return true; }   // frame-local
@@ -525,6 +551,11 @@ class Conv2DLayer : public Layer {
  public:
   int cin, cout, kw, stride, pad;  // pad -1 = SAME
   int kh = 1, padH = 0;            // kh > 1: the mel axis is unrolled into kh*cin channels (w2l_hexpand_*), SAME padding on it
+  // groups == cin == cout (the only value besides 1 that is built): a depthwise convolution, one [kw] filter per channel, on the
+  // w2l_conv_depthwise_* kernels at every mixed-precision level (nothing in it is a matrix product).  No folded ReLU.
+  int groups = 1;
+  size_t dwWsOff = 0;              // depthwise: the filter gradient's segment partials
+  bool depthwise() const { return groups != 1; }
   size_t xeOff = 0, dxeOff = 0, nIn = 0;
   bool hasBias = true, fuseRelu = false;
   int extraPadL = 0, extraPadR = 0;  // from a preceding "PD" (time axis)
@@ -541,6 +572,7 @@ class Conv2DLayer : public Layer {
 
   std::string name() const override { return wn.on ? "WeightNorm(Conv2D)" : "Conv2D"; }
   bool streamGeom(StreamGeom& g, std::string& why) const override {
+    if (depthwise()) { why = "depthwise convolutions (groups != 1) are not built for streaming sessions"; return false; }
     if (pad == -1 && stride > 1) { why = "SAME padding with a stride above 1 depends on the utterance length"; return false; }
     if (stride > kw) { why = "a stride above the kernel width skips frames"; return false; }
     const int p = pad == -1 ? samePad(4096, kw, 1) : pad;
@@ -550,17 +582,18 @@ class Conv2DLayer : public Layer {
   }
   void registerParams(std::vector<ParamInfo>& t) override {
     ParamInfo pw;
-    pw.numel = (size_t)kw * kh * cin * cout;
-    pw.refShape = {kw, kh, cin, cout};
-    pw.kind = 1; pw.kw = kw; pw.kh = kh; pw.cin = cin; pw.cout = cout;
-    pw.initBound = std::sqrt(1.0 / ((double)cin * kw * kh));
+    const int cinG = cin / groups;   // input channels of one group: the reference's weight is (kw, kh, cin / groups, cout)
+    pw.numel = (size_t)kw * kh * cinG * cout;
+    pw.refShape = {kw, kh, cinG, cout};
+    pw.kind = 1; pw.kw = kw; pw.kh = kh; pw.cin = cinG; pw.cout = cout;
+    pw.initBound = std::sqrt(1.0 / ((double)cinG * kw * kh));
     if (wn.on) {
       pw.name = "wn.v";
       addParam(t, pw, wn.v);
       ParamInfo pg;
       pg.name = "wn.g"; pg.numel = cout; pg.refShape = {1, 1, 1, cout}; pg.kind = 4;  // init = ||v||
       addParam(t, pg, wn.g);
-      wn.K = kw * kh * cin; wn.N = cout;
+      wn.K = kw * kh * cinG; wn.N = cout;
     } else {
       pw.name = "conv.w";
       addParam(t, pw, w);
@@ -568,7 +601,7 @@ class Conv2DLayer : public Layer {
     if (hasBias) {
       ParamInfo pb;
       pb.name = "conv.b"; pb.numel = cout; pb.refShape = {1, 1, cout, 1};
-      pb.initBound = std::sqrt(1.0 / ((double)cin * kw * kh));
+      pb.initBound = std::sqrt(1.0 / ((double)cinG * kw * kh));
       addParam(t, pb, b);
     }
   }
@@ -588,9 +621,16 @@ class Conv2DLayer : public Layer {
     dxOff = pl.alloc(in.numel());
     nIn = in.numel();
     if (kh > 1) { xeOff = pl.alloc(nIn * kh); dxeOff = pl.alloc(nIn * kh); }
-    convImgElems = H % 16 == 0 ? w2l_tds_conv_bf16_image_elems(&d) : 0;
+    if (depthwise()) {
+      const size_t ws = w2l_conv_depthwise_workspace_floats(&d);
+      if (!ws)
+        throw std::invalid_argument(kw > 64 ? "Conv2D: the depthwise kernels take kernel widths up to 64: " + archLine
+                                            : "Conv2D: the depthwise kernels do not take this geometry (" + in.str() + "): " + archLine);
+      dwWsOff = pl.alloc(ws);
+    }
+    convImgElems = (H % 16 == 0 && !depthwise()) ? w2l_tds_conv_bf16_image_elems(&d) : 0;
     if (convImgElems) { convImgFOff = pl.allocBf16(convImgElems); convImgBOff = pl.allocBf16(convImgElems); }
-    wideImgElems = (pl.bf16Convs && !convImgElems) ? w2l_conv_bf16_image_elems(&d) : 0;
+    wideImgElems = (pl.bf16Convs && !convImgElems && !depthwise()) ? w2l_conv_bf16_image_elems(&d) : 0;
     if (wideImgElems) {
       wideImgFOff = pl.allocBf16(wideImgElems); wideImgBOff = pl.allocBf16(wideImgElems);
       pl.wantConvScratch(w2l_conv_bf16_scratch_elems(&d));
@@ -616,6 +656,10 @@ class Conv2DLayer : public Layer {
     }
     xSaved = x;
     const float* wt = weight(c, arena);
+    if (depthwise()) {
+      w2lCheck(w2l_conv_depthwise_forward(&d, x, wt, hasBias ? b.w(c) : nullptr, y, c.stream), "depthwise conv fwd");
+      return;
+    }
     if (c.bf16 && convImgElems) {   // bf16 operands, fp32 accumulation / bias / ReLU (conv_tds_bf16.hip); images once per step
       if (!c.weightsReady) w2lCheck(w2l_tds_conv_bf16_prepare(&d, wt, bfp(arena, convImgFOff), bfp(arena, convImgBOff), c.stream), "conv images");
       w2lCheck(w2l_tds_conv_bf16_forward(&d, x, bfp(arena, convImgFOff), hasBias ? b.w(c) : nullptr, y, fuseRelu ? 1 : 0, c.stream), "conv fwd bf16");
@@ -636,7 +680,10 @@ class Conv2DLayer : public Layer {
     float* dwt = wn.on ? arena + wn.dwOff : w.g(c);
     const bool bf = c.bf16 && convImgElems;
     const bool wd = wide(c);
-    if (wd) {
+    if (depthwise()) {
+      // on the caller's stream: the partials are this layer's own arena slot, read by the second launch of the same call
+      w2lCheck(w2l_conv_depthwise_backward_filter(&d, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, arena + dwWsOff, c.stream), "depthwise conv bwd filter");
+    } else if (wd) {
       w2lCheck(w2l_conv_bf16_backward_filter_bias(&d, xSaved, dym, dwt, hasBias ? b.g(c) : nullptr, c.convScratch, c.stream),
                "wide conv bwd filter + bias bf16");
     } else if (bf) {
@@ -649,7 +696,9 @@ class Conv2DLayer : public Layer {
     const float* wt = wn.on ? arena + wn.wOff : w.w(c);
     if (needDx) {
       dx = arena + dxOff;
-      if (wd) {
+      if (depthwise()) {
+        w2lCheck(w2l_conv_depthwise_backward_data(&d, dym, wt, dx, c.stream), "depthwise conv bwd data");
+      } else if (wd) {
         w2lCheck(w2l_conv_bf16_backward_data(&d, dym, bfp(arena, wideImgBOff), nullptr, kh > 1 ? arena + dxeOff : dx, c.convScratch, c.stream),
                  "wide conv bwd data bf16");
         if (kh > 1) w2lCheck(w2l_hexpand_backward(arena + dxeOff, dx, (size_t)d.B * d.T, d.H, cin, kh, padH, c.stream), "conv H fold");
@@ -1895,7 +1944,9 @@ static std::shared_ptr<Layer> buildOne(const LayerSpec& s, const LayerSpec* wnPa
     l->pad = a.size() >= 5 ? toI(a[4]) : 0;
     if (a.size() >= 6 && toI(a[5]) != 1) throw std::invalid_argument("dilation != 1 not supported: " + s.line);
     l->hasBias = a.size() >= 7 ? toI(a[6]) != 0 : true;
-    if (a.size() >= 8 && toI(a[7]) != 1) throw std::invalid_argument("groups != 1 not supported: " + s.line);
+    l->groups = a.size() >= 8 ? toI(a[7]) : 1;
+    if (l->groups != 1 && !(l->groups == l->cin && l->groups == l->cout && l->stride == 1))
+      throw std::invalid_argument("groups = " + std::to_string(l->groups) + ": besides 1, only a depthwise convolution is built (groups == cin == cout, stride 1): " + s.line);
     return l;
   }
   if (s.tok == "C2") {
@@ -1960,6 +2011,12 @@ static std::shared_ptr<Layer> buildOne(const LayerSpec& s, const LayerSpec* wnPa
     return l;
   }
   if (s.tok == "R") return std::make_shared<ReLULayer>();
+  if (s.tok == "SH") {
+    auto l = std::make_shared<SwishLayer>();
+    l->beta = a.empty() ? 1.f : std::stof(a[0]);
+    if (!std::isfinite(l->beta)) throw std::invalid_argument("SH: beta must be finite: " + s.line);
+    return l;
+  }
   if (s.tok == "DO") { auto l = std::make_shared<DropoutLayer>(); l->p = toD(a[0]); return l; }
   if (s.tok == "GLU") { auto l = std::make_shared<GLULayer>(); l->dim = toI(a[0]); return l; }
   if (s.tok == "SAUG") {
@@ -2026,7 +2083,7 @@ static void buildLayers(const std::vector<LayerSpec>& specs, bool inBlock, const
     }
     // peephole: Conv/Linear + ReLU -> fused epilogue; residual block + ReLU -> the ReLU of its join
     if (s.tok == "R" && last) {
-      if (auto c = std::dynamic_pointer_cast<Conv2DLayer>(last)) { if (!c->fuseRelu) { c->fuseRelu = true; continue; } }
+      if (auto c = std::dynamic_pointer_cast<Conv2DLayer>(last)) { if (!c->fuseRelu && !c->depthwise()) { c->fuseRelu = true; continue; } }
       if (auto li = std::dynamic_pointer_cast<LinearLayer>(last)) { if (!li->fuseRelu) { li->fuseRelu = true; continue; } }
       if (auto r = std::dynamic_pointer_cast<ResidualLayer>(last)) { if (!r->relu) { r->relu = true; continue; } }
     }

@@ -101,6 +101,49 @@ def conv_backward(x, w, dy, stride=1, padl=0, padr=0, need_dx=True):
     return dx, dw, db
 
 
+def conv_depthwise_desc(x, w, stride=1, padl=0, padr=0):
+    B, T, H, Cin = x.shape
+    kw, Cout = w.shape
+    return ConvDesc(B, T, H, Cin, Cout, kw, stride, padl, padr)
+
+
+def conv_depthwise_forward(x, w, bias=None, stride=1, padl=0, padr=0):
+    """depthwise (groups == C) convolution over time: x [B][T][H][C], w [kw][C], bias [C] -> y [B][To][H][C]"""
+    d = conv_depthwise_desc(x, w, stride, padl, padr)
+    To = max(_lib.lib().w2l_conv_out_len(d.T, d.kw, stride, padl, padr), 0)
+    y = torch.empty(d.B, To, d.H, d.Cout, device=x.device, dtype=torch.float32)
+    check(_lib.lib().w2l_conv_depthwise_forward(C.byref(d), _p(x), _p(w), _p(bias), _p(y), _s()), "conv_depthwise_forward")
+    return y
+
+
+def conv_depthwise_backward(x, w, dy, stride=1, padl=0, padr=0, need_dx=True, need_dbias=True):
+    """-> (dx or None, dw [kw][C], dbias [C] or None); the filter gradient is run-to-run deterministic (no atomics)"""
+    d = conv_depthwise_desc(x, w, stride, padl, padr)
+    L = _lib.lib()
+    dx = torch.empty_like(x) if need_dx else None
+    dw = torch.empty_like(w)
+    db = torch.empty(d.Cout, device=x.device, dtype=torch.float32) if need_dbias else None
+    ws = torch.empty(max(L.w2l_conv_depthwise_workspace_floats(C.byref(d)), 1), device=x.device, dtype=torch.float32)
+    if need_dx:
+        check(L.w2l_conv_depthwise_backward_data(C.byref(d), _p(dy), _p(w), _p(dx), _s()), "conv_depthwise_bwd_data")
+    check(L.w2l_conv_depthwise_backward_filter(C.byref(d), _p(x), _p(dy), _p(dw), _p(db), _p(ws), _s()), "conv_depthwise_bwd_filter")
+    return dx, dw, db
+
+
+def swish_forward(x, beta=1.0):
+    """fl::Swish: y = x * sigmoid(beta * x)"""
+    y = torch.empty_like(x)
+    check(_lib.lib().w2l_swish_forward(_p(x), _p(y), x.numel(), beta, _s()), "swish_forward")
+    return y
+
+
+def swish_backward(x, dy, beta=1.0, out=None):
+    """dx = dy * (s + beta x s (1 - s)), s = sigmoid(beta x); out may be dy itself"""
+    dx = torch.empty_like(dy) if out is None else out
+    check(_lib.lib().w2l_swish_backward(_p(x), _p(dy), _p(dx), x.numel(), beta, _s()), "swish_backward")
+    return dx
+
+
 def _ln_scratch(groups, inner):
     return int(_lib.lib().w2l_layernorm_scratch_doubles(groups, inner))
 

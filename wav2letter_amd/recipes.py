@@ -194,6 +194,15 @@ def conv_glu_small_arch(widths=(16, 24), kws=(5, 4), pad0=4, drop=0.0):
     return "\n".join(lines) + "\n"
 
 
+def conformer_conv_module_arch(C, kw, p):
+    """the convolution module of a Conformer block on a (T, 1, C, B) activation, as ten arch lines: a residual block around
+    LayerNorm, a pointwise convolution to 2C with GLU, a depthwise convolution of width kw with SAME padding (groups = C),
+    LayerNorm, Swish, a pointwise convolution and dropout p.  (`RES 8 1 1`: the grammar wants the block count written out.)"""
+    lines = ["RES 8 1 1", "LN 1 2", f"C {C} {2 * C} 1 1 0", "GLU 2", f"C {C} {C} {kw} 1 -1 1 1 {C}", "LN 1 2", "SH", f"C {C} {C} 1 1 0",
+             f"DO {p}", "SKIP 0 9"]
+    return "\n".join(lines) + "\n"
+
+
 # train.cfg essentials of the two headline recipes (flags the hot path consumes)
 TDS_CTC_FLAGS = dict(criterion="ctc", lr=0.3, momentum=0.5, maxgradnorm=1.0, onorm="target", sqnorm=True,
                      filterbanks=80, batchsize=4)       # recipes/sota/2019/librispeech/train_am_tds_ctc.cfg:11-30
