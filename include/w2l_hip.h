@@ -908,7 +908,9 @@ int w2l_attn_softmax_forward(float* S, const float* R, const int* keyLen, int B,
  * count as 0); keyLen as in w2l_attn_softmax_forward.  Writes P [B][H][T][T] (the backward pass reads it), Pd (same shape, only when
  * dropP > 0: the same keep pattern as w2l_dropout_copy over P) and ctx [B][T][ldc].  Operands are rounded to bf16 where
  * w2l_bgemm_bf16 rounds them; the result equals the unfused sequence to fp32 summation order.
- * W2L_EUNSUPPORTED when the geometry has no fused kernel (d in {32, 256}, T <= 192, 16-byte aligned rows): run the unfused one.
+ * W2L_EUNSUPPORTED when the geometry has no fused kernel: run the unfused one.  Fused: d in {32, 192, 256}, T <= 512, 16-byte aligned
+ * rows -- T <= 192 with every key of an (utterance, head) resident in LDS (attention_fused.hip), 192 < T <= 512 with the keys
+ * streamed through LDS in chunks and two passes over them (attention_fused_long.hip); same results, same contract.
  * Replaces: TransformerCPC.cpp:117-151 (selfAttention) for the forward pass. */
 typedef struct {
   int B, H, T, d;
@@ -930,7 +932,8 @@ int w2l_attn_fused_forward(const w2l_attn_fused_desc* d, const float* q, const f
  * when posTable is NULL).  Operands are rounded to bf16 where the unfused w2l_bgemm_bf16 sequence rounds them (dctx, v, Pd, dS, k,
  * q, posTable); the result equals that sequence to fp32 summation order.  workspace: w2l_attn_fused_backward_workspace(d,
  * posTable != NULL) bytes, 256-byte aligned; it holds the bf16 images dS^T / Pd^T [B H][32 NT][32 NT] (row = key, column = query,
- * NT = ceil(T / 32) rounded up to 2, 4 or 6) first, which tests read.  The key-padding mask needs no argument: P is zero there.
+ * NT = ceil(T / 32) rounded up to 2, 4 or 6 for T <= 192 and to the next even number, 8 .. 16, for 192 < T <= 512: 32 NT = 64 ceil(T / 64))
+ * first, which tests read.  The key-padding mask needs no argument: P is zero there.
  * W2L_EUNSUPPORTED (workspace size 0) for a geometry without a fused kernel: the same set as the forward call.
  * Replaces: the gradient of TransformerCPC.cpp:117-151 (selfAttention). */
 /* The same two calls writing the bf16 images the NEXT product reads (w2l_bf16_image_sink) instead of, or beside, the fp32 result

@@ -46,13 +46,14 @@ def unfused():
     L.w2l_bgemm_bf16(C.byref(g), dR.data_ptr(), q.data_ptr(), dEp.data_ptr(), s)
     L.w2l_fill(dE.data_ptr(), dE.numel(), 0.0, s)
     L.w2l_colsum(dEp.data_ptr(), dE[rlo:].data_ptr(), B, W * d, s)
-def timeit(f, n=50):
-    for _ in range(3): f()
+def timeit(f, n=200):
+    for _ in range(5): f()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(n): f()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n * 1e3
-print("attention backward B=%d H=%d T=%d d=%d csz=%d p=%.1f bpw=%s: fused %.1f us, unfused sequence %.1f us" % (
-    B, H, T, d, csz, p, os.environ.get("W2L_AB_BPW", "-"), timeit(fused), timeit(unfused)))
+rounds = [(timeit(fused), timeit(unfused)) for _ in range(3)]   # alternating windows of 200 calls
+print("attention backward B=%d H=%d T=%d d=%d csz=%d p=%.1f bpw=%s: fused %s us, unfused sequence %s us" % (
+    B, H, T, d, csz, p, os.environ.get("W2L_AB_BPW", "-"), " / ".join("%.1f" % a for a, _ in rounds), " / ".join("%.1f" % b for _, b in rounds)))

@@ -23,7 +23,7 @@
 //
 // Operands are rounded to bf16 (nearest even) exactly where the unfused bf16 path rounds them (q, k, E, P, v), accumulation,
 // scores and softmax are fp32: the two paths agree to fp32 summation order.
-#include "common.hpp"
+#include "attention_fused.hpp"
 
 namespace w2l {
 
@@ -32,19 +32,6 @@ typedef __bf16 af_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float af_f32x2 __attribute__((ext_vector_type(2)));
 typedef float af_f32x4 __attribute__((ext_vector_type(4)));
 typedef float af_f32x16 __attribute__((ext_vector_type(16)));
-
-struct AfP {
-  const float *q, *k, *v;   // [B][T][ld], head h at columns h d .. (h + 1) d
-  const float* E;           // position table rows [2 csz - 1][d] (internal layout), or null
-  const int* keyLen;
-  float *P, *Pd, *ctx;      // P, Pd [B][H][T][T]; ctx [B][T][ldc] (may be null when its images are asked for)
-  w2l_bf16_image_sink ctxI; // bf16 images of ctx written in place of a conversion pass (null pointers: none)
-  int B, H, T, ld, ldc;
-  int W, n0, rlo;           // table rows rlo .. rlo + W are the ones an utterance of T frames reaches
-  float scale;
-  uint32_t thr, seed, stream;
-  float keepScale;
-};
 
 __device__ __forceinline__ uint32_t af_pack2(float a, float b) {
   const af_f32x2 v = {a, b};
@@ -358,8 +345,10 @@ W2L_API int w2l_attn_fused_forward_images(const w2l_attn_fused_desc* d, const fl
   hipStream_t s = (hipStream_t)stream;
 #define W2L_AF(NTv, Dv) if (nt <= NTv && d->d == Dv) return af_launch<NTv, Dv>(p, s);
   W2L_AF(2, 32) W2L_AF(4, 32) W2L_AF(6, 32)
+  W2L_AF(2, 192) W2L_AF(4, 192) W2L_AF(6, 192)
   W2L_AF(2, 256) W2L_AF(4, 256) W2L_AF(6, 256)
 #undef W2L_AF
+  if (attn_long_supported(d->T, d->d)) return attn_long_forward(p, d->d, s);   // 192 < T <= 512: keys streamed through LDS
   return W2L_EUNSUPPORTED;
 }
 

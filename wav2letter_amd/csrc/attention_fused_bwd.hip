@@ -27,7 +27,7 @@
 //
 // Operands are rounded to bf16 (nearest even) exactly where the unfused bf16 path rounds them (dctx, v, Pd, dS, k, q, E);
 // accumulation and the softmax backward are fp32: the two paths agree to fp32 summation order.
-#include "common.hpp"
+#include "attention_fused.hpp"
 
 namespace w2l {
 
@@ -36,25 +36,6 @@ typedef __bf16 ab_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float ab_f32x2 __attribute__((ext_vector_type(2)));
 typedef float ab_f32x4 __attribute__((ext_vector_type(4)));
 typedef float ab_f32x16 __attribute__((ext_vector_type(16)));
-
-struct AbP {
-  const float *q, *k, *v;   // [B][T][ld], head h at columns h d .. (h + 1) d
-  const float* E;           // position table rows [2 csz - 1][d] (internal layout), or null
-  const float* P;           // [B][H][T][T] of the forward pass
-  const float* dctx;        // [B][T][ldc]
-  float *dq, *dk, *dv;      // [B][T][ld] (each may be null when its images are asked for)
-  w2l_bf16_image_sink dqI, dkI, dvI;   // bf16 images of dq / dk / dv written in place of a conversion pass (null pointers: none)
-  float* dE;                // [2 n0 + 1][d] or null
-  uint16_t *dSt, *Pdt;      // bf16 [B H][TP][TP]: row = key, column = query
-  uint16_t* dRt;            // bf16 [B H][GW][TP]: row = window row (global numbering), column = query
-  uint16_t* Et;             // bf16 [d][GW]
-  float* dEp;               // [B H][GW][d]
-  int B, H, T, ld, ldc;
-  int W, n0, rlo;
-  float scale;
-  uint32_t thr, seed, stream;
-  float keepScale;
-};
 
 __device__ __forceinline__ uint32_t ab_pack2(float a, float b) {
   const ab_f32x2 v = {a, b};
@@ -537,7 +518,7 @@ using namespace w2l;
 static bool ab_supported(const w2l_attn_fused_desc* d, int& nt) {
   if (!d || d->B <= 0 || d->H <= 0 || d->T <= 0 || d->d <= 0 || d->B > 65535 || d->H > 65535) return false;
   nt = (d->T + 31) / 32;
-  return (d->d == 32 || d->d == 256) && nt <= 6;
+  return ((d->d == 32 || d->d == 192 || d->d == 256) && nt <= 6) || attn_long_supported(d->T, d->d);
 }
 
 W2L_API size_t w2l_attn_fused_backward_workspace(const w2l_attn_fused_desc* d, int withPosTable) {
@@ -547,9 +528,10 @@ W2L_API size_t w2l_attn_fused_backward_workspace(const w2l_attn_fused_desc* d, i
   const bool t = withPosTable != 0;
 #define W2L_AB(NTv, Dv) if (nt <= NTv && d->d == Dv) return AbGeom<NTv, Dv>::total(BH, t);
   W2L_AB(2, 32) W2L_AB(4, 32) W2L_AB(6, 32)
+  W2L_AB(2, 192) W2L_AB(4, 192) W2L_AB(6, 192)
   W2L_AB(2, 256) W2L_AB(4, 256) W2L_AB(6, 256)
 #undef W2L_AB
-  return 0;
+  return attn_long_backward_workspace(d->B, d->H, d->T, d->d, t);
 }
 
 // returns W2L_EUNSUPPORTED for a geometry without a fused kernel (the caller runs the unfused sequence then)
@@ -587,8 +569,10 @@ W2L_API int w2l_attn_fused_backward_images(const w2l_attn_fused_desc* d, const f
   hipStream_t s = (hipStream_t)stream;
 #define W2L_AB(NTv, Dv) if (nt <= NTv && d->d == Dv) return ab_launch<NTv, Dv>(p, workspace, workspaceBytes, s);
   W2L_AB(2, 32) W2L_AB(4, 32) W2L_AB(6, 32)
+  W2L_AB(2, 192) W2L_AB(4, 192) W2L_AB(6, 192)
   W2L_AB(2, 256) W2L_AB(4, 256) W2L_AB(6, 256)
 #undef W2L_AB
+  if (attn_long_supported(d->T, d->d)) return attn_long_backward(p, d->d, workspace, workspaceBytes, s);
   return W2L_EUNSUPPORTED;
 }
 

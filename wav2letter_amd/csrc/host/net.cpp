@@ -1229,6 +1229,11 @@ class TransformerLayer : public Layer {
     outImg.plan(pl, M, C, true);
     return in;
   }
+  // Where the fused FORWARD launch is the faster route: T <= 192 at head width 32 / 256.  The forward kernels for 192 < T <= 512 and
+  // for head width 192 measured slower than the unfused sequence (profiles/attn_long_one.log: 1.1 x at d = 192, T = 188; 1.3 - 2.4 x
+  // past 192 frames) and are served by the C ABI only.  The fused BACKWARD is 1.5 - 2.4 x faster in every measured cell and needs only
+  // P and the dropout seed, which the unfused forward leaves in the same buffers: there it follows the unfused forward.
+  static bool fusedForwardPays(int T, int d) { return T <= 192 && (d == 32 || d == 256); }
   w2l_attn_fused_desc fusedDesc(double pd, uint32_t seed) const {
     w2l_attn_fused_desc fd{};
     fd.B = B; fd.H = nH; fd.T = T; fd.d = d; fd.ld = C; fd.ldc = C; fd.W = W; fd.n0 = n0; fd.rlo = rlo;
@@ -1297,7 +1302,7 @@ class TransformerLayer : public Layer {
     }
     const float scale = (float)(1.0 / std::sqrt((double)d));
     bool fused = false;
-    if (mixed) {   // scores, position term, softmax, dropout and P V in one launch where the geometry has a fused kernel
+    if (mixed && fusedForwardPays(T, d)) {   // scores, position term, softmax, dropout and P V in one launch where the geometry has a fused kernel
       // (ctx is only ever the operand of the wf products in this mode: the kernel writes its bf16 images, no fp32 copy)
       const w2l_attn_fused_desc fd = fusedDesc(pd, cx.seed);
       const w2l_bf16_image_sink ctxSink = ctxImg.sink(cx, ar);
@@ -1400,7 +1405,7 @@ class TransformerLayer : public Layer {
       w2lCheck(w2l_linear_backward_data(M, C, C, dr1, wf.w(cx), dctx, 0, nullptr, 1.f, s), "tr wf bwd x");
     }
     bool fusedBwd = false;
-    if (mixed && fusedFwd && abwBytes) {   // dP, dropout mask, softmax backward, dq (+ position term), dk, dv, table gradient: four launches
+    if (mixed && (fusedFwd || !fusedForwardPays(T, d)) && abwBytes) {   // dP, dropout mask, softmax backward, dq (+ position term), dk, dv, table gradient: four launches
       // dq / dk / dv are only ever GEMM operands once their bias gradients ride on the weight-gradient products: bf16 images from the
       // kernels, no fp32 copies, no conversion launch
       const w2l_attn_fused_desc fd = fusedDesc(pd, cx.seed);
