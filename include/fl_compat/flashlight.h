@@ -256,6 +256,16 @@ class Conv2D : public ArchLayer {
 };
 // fl::Swish(beta): x * sigmoid(beta * x)
 class Swish : public ArchLayer { public: explicit Swish(double beta = 1.0) : ArchLayer(beta == 1.0 ? std::string("SH") : join("SH", {beta})) {} };
+// fl::RNN(inputSize, hiddenSize, numLayers, mode, bidirectional, dropout): the RNN / GRU / LSTM arch lines.  RnnMode::TANH
+// has no arch token of the reference's; its line is `RNN i h n b p TANH`.  Input (inputSize, B, T, 1), output (hiddenSize * dirs, B, T, 1).
+enum class RnnMode { RELU = 0, TANH = 1, LSTM = 2, GRU = 3 };
+class RNN : public ArchLayer {
+ public:
+  RNN(int inputSize, int hiddenSize, int numLayers, RnnMode mode, bool bidirectional = false, float dropout = 0.f)
+      : ArchLayer(join(mode == RnnMode::LSTM ? "LSTM" : mode == RnnMode::GRU ? "GRU" : "RNN",
+                       {(double)inputSize, (double)hiddenSize, (double)numLayers, bidirectional ? 1.0 : 0.0, (double)dropout}) +
+                  (mode == RnnMode::TANH ? " TANH" : "")) {}
+};
 enum class PoolingMode { MAX = 0 };
 class Pool2D : public ArchLayer {
  public:

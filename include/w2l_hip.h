@@ -749,6 +749,40 @@ int w2l_conv_depthwise_backward_data(const w2l_conv_desc* d, const float* dy, co
 size_t w2l_conv_depthwise_workspace_floats(const w2l_conv_desc* d);
 int w2l_conv_depthwise_backward_filter(const w2l_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias, float* workspace,
                                        w2l_stream_t stream);
+/* fl::RNN (arch tokens RNN / GRU / LSTM; rnn.hip): `layers` stacked recurrent layers, `dirs` = 1 or 2 directions,
+ * cuDNN's equations (= torch.nn.RNN / GRU / LSTM), gates stacked in the order given, initial h and c zero, every one of the T frames
+ * scanned (no lengths), the reverse direction starting at frame T - 1:
+ *   W2L_RNN_RELU / _TANH  h' = act(W_ih x + b_ih + W_hh h + b_hh)
+ *   W2L_RNN_LSTM          i, f, g, o;  c' = f c + i g,  h' = o tanh(c')
+ *   W2L_RNN_GRU           r, z, n;     n = tanh(W_in x + b_in + r (W_hn h + b_hn)),  h' = (1 - z) n + z h
+ * x [B][T][ldx] (I columns used), y / dy [B][T][ldy] (direction d at columns d H .. d H + H - 1), dx [B][T][ldx]; fp32.  Layer
+ * l > 0 reads the H dirs columns of layer l - 1, in training (train != 0) after dropout(dropP): the mask of
+ * w2l_dropout_copy(p, seed ^ (0x9E3779B9 * l), rngStream) over the dense [B T][H dirs] activation, applied again in the backward.
+ * params / dparams: w2l_rnn_param_count floats -- layer by layer, forward direction then reverse, each W_ih [G H][I_l], W_hh [G H][H],
+ * b_ih [G H], b_hh [G H] (G = 1, 4, 3).  backward overwrites ALL of dparams and, unless dx is NULL, the I columns of dx.
+ * workspace: w2l_rnn_workspace_size(d) bytes (it depends on d->train; 0 for a refused descriptor).  Its contents mean nothing before
+ * forward; backward takes the SAME descriptor (train != 0), x, params, y and the workspace as the forward call left it.
+ * The recurrence is one launch per time step and layer (both directions in it); every sum has one order, so two calls give the same
+ * bits, and -- in the recurrence -- a batch row's bits do not depend on B.
+ * W2L_EINVAL: a null pointer (but dx), a mode outside 0..3, a size below 1, dirs outside 1..2, ldx < I, ldy < H dirs, dropP outside
+ * [0, 1), a workspace below the size asked for, backward with train == 0.  W2L_EUNSUPPORTED: I or H above 4096, B above 1024, layers
+ * above 8, T above 65536, or B T max(4 H, ldx, ldy) >= 2^31 - 1.  All checks precede the first launch. */
+typedef enum { W2L_RNN_RELU = 0, W2L_RNN_TANH = 1, W2L_RNN_LSTM = 2, W2L_RNN_GRU = 3 } w2l_rnn_mode;
+typedef struct {
+  int mode;           /* w2l_rnn_mode */
+  int I, H, layers, dirs;
+  int B, T;
+  int ldx, ldy;       /* floats between two frames of x / dx and of y / dy */
+  int train;          /* 0: inference (no dropout, nothing kept); else what backward needs is kept in the workspace */
+  double dropP;
+  uint32_t seed, rngStream;
+} w2l_rnn_desc;
+size_t w2l_rnn_param_count(const w2l_rnn_desc* d);
+size_t w2l_rnn_workspace_size(const w2l_rnn_desc* d);
+int w2l_rnn_forward(const w2l_rnn_desc* d, const float* x, const float* params, float* y, void* workspace, size_t workspaceBytes,
+                    w2l_stream_t stream);
+int w2l_rnn_backward(const w2l_rnn_desc* d, const float* x, const float* params, const float* y, const float* dy, float* dx,
+                     float* dparams, void* workspace, size_t workspaceBytes, w2l_stream_t stream);
 /* The kw x 1 convolutions over the mel rows of the TDS recipes in the mixed-precision mode (bf16 operand storage, see
  * w2l_gemm_bf16) -- fl::TDSBlock's time convolution (C -> C channels, stride 1) and the sub-sampling `C2 cin cout kw 1 s 1`
  * lines between the blocks (cin != cout <= 32 channels, stride 1 or 2, any padding): x / dy and the weights rounded to bf16,

@@ -230,6 +230,10 @@ class _SIGS:
     w2l_conv_depthwise_backward_data = (_i, [_p, _p, _p, _p, _p])
     w2l_conv_depthwise_workspace_floats = (_sz, [_p])
     w2l_conv_depthwise_backward_filter = (_i, [_p, _p, _p, _p, _p, _p, _p])
+    w2l_rnn_param_count = (_sz, [_p])
+    w2l_rnn_workspace_size = (_sz, [_p])
+    w2l_rnn_forward = (_i, [_p, _p, _p, _p, _p, _sz, _p])
+    w2l_rnn_backward = (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
     w2l_swish_forward = (_i, [_p, _p, _sz, _f, _p])
     w2l_swish_backward = (_i, [_p, _p, _p, _sz, _f, _p])
     w2l_layernorm_scratch_doubles = (_sz, [_i, _sz])
@@ -343,6 +347,11 @@ class _SIGS:
 
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "T", "H", "Cin", "Cout", "kw", "stride", "padl", "padr")]
+
+
+class RnnDesc(C.Structure):  # w2l_rnn_desc; mode: 0 ReLU, 1 tanh, 2 LSTM, 3 GRU
+    _fields_ = ([(n, C.c_int) for n in ("mode", "I", "H", "layers", "dirs", "B", "T", "ldx", "ldy", "train")] +
+                [("dropP", C.c_double), ("seed", C.c_uint32), ("rngStream", C.c_uint32)])
 
 
 class GemmEpilogue(C.Structure):  # w2l_gemm_epilogue

@@ -1503,6 +1503,54 @@ class TransformerLayer : public Layer {
 // followed by a ReLU when an `R` line directly behind the block was folded into the join (w2l_residual_join_forward / _backward).
 // The block owns its layers; they plan on the net's planner, run under Sequential::forward's protocol and keep their own
 // backward passes, weight-gradient stream included.
+// fl::RNN (arch tokens RNN / GRU / LSTM) on w2l_rnn_forward / _backward: fp32 at every mixed-precision level.  Takes
+// Flashlight's (I, B, T, 1): dim 0 the whole contiguous frame, dim 1 the batch, dim 2 time -- the physical [B][T][I] as it is.
+// Keeps its input, writes buffers of its own; one flat parameter.
+class RecurrentLayer : public Layer {
+ public:
+  w2l_rnn_desc d{};
+  P w;
+  size_t yOff = 0, dxOff = 0, wsOff = 0, wsBytes = 0;
+  const float* xSaved = nullptr;
+  std::string name() const override {
+    return d.mode == W2L_RNN_LSTM ? "LSTM" : d.mode == W2L_RNN_GRU ? "GRU" : d.mode == W2L_RNN_TANH ? "RNN(tanh)" : "RNN";
+  }
+  void registerParams(std::vector<ParamInfo>& t) override {
+    ParamInfo p;
+    p.name = "rnn.params";
+    p.numel = w2l_rnn_param_count(&d);
+    p.refShape = {(int)p.numel};
+    p.initBound = std::sqrt(1.0 / (double)d.H);   // uniform +-1/sqrt(H), every matrix and bias (recalled from upstream: DESIGN 3.32)
+    addParam(t, p, w);
+  }
+  Act plan(const Act& a, Planner& pl) override {
+    const bool frame = a.d[0].f.size() == 1 && a.d[0].f[0].kind == F_FEAT && a.d[0].f[0].stride == 1 && a.d[0].f[0].size == d.I && a.F == d.I;
+    if (!frame || !isKind(a.d[1], F_BATCH) || !isKind(a.d[2], F_TIME) || a.d[3].size() != 1)
+      throw std::invalid_argument(name() + ": input must be (" + std::to_string(d.I) + ", B, T, 1) with the " + std::to_string(d.I) +
+                                  " features one contiguous frame (e.g. RO 1 3 0 2 from the input layout), got " + a.str() + ": " + archLine);
+    d.B = a.B; d.T = a.T; d.ldx = d.I; d.ldy = d.H * d.dirs; d.train = 1;
+    wsBytes = w2l_rnn_workspace_size(&d);
+    if (!wsBytes) throw std::invalid_argument(name() + ": outside the scan's caps (I, H <= 4096, B <= 1024, layers <= 8) at " + a.str() + ": " + archLine);
+    yOff = pl.alloc(a.numel() / d.I * d.ldy);
+    dxOff = pl.alloc(a.numel());
+    wsOff = pl.alloc(wsBytes / sizeof(float));
+    Act o = a;
+    o.F = d.ldy;
+    o.d[0].f = {{d.ldy, 1, F_FEAT}};
+    return o;
+  }
+  void forward(Ctx& c, float* arena, const float* x, float*& y) override {
+    y = arena + yOff;
+    xSaved = x;
+    d.train = c.train ? 1 : 0; d.seed = c.seed; d.rngStream = (uint32_t)rngStream;
+    w2lCheck(w2l_rnn_forward(&d, x, w.w(c), y, arena + wsOff, wsBytes, c.stream), "rnn fwd");
+  }
+  void backward(Ctx& c, float* arena, const float* dy, float*& dx, bool needDx) override {
+    if (needDx) dx = arena + dxOff;
+    w2lCheck(w2l_rnn_backward(&d, xSaved, w.w(c), arena + yOff, dy, needDx ? dx : nullptr, w.g(c), arena + wsOff, wsBytes, c.stream), "rnn bwd");
+  }
+};
+
 enum Touch { kKeeps, kPasses, kWrites };
 // what a layer's forward does to its input buffer / its backward to its output-gradient buffer: leaves it alone and writes a
 // buffer of its own, hands the pointer on untouched, or rewrites it in place
@@ -2013,6 +2061,26 @@ static std::shared_ptr<Layer> buildOne(const LayerSpec& s, const LayerSpec* wnPa
   if (s.tok == "LN") {
     auto l = std::make_shared<LayerNormLayer>();
     for (auto& x : a) l->axes.push_back(toI(x));
+    return l;
+  }
+  if (s.tok == "RNN" || s.tok == "GRU" || s.tok == "LSTM") {
+    // <inputSize> <hiddenSize> [numLayers = 1] [bidirectional = 0] [dropout = 0], as the reference's rnnLayer lambda reads them
+    // (cpc/SequentialBuilder.cpp:493-501).  A seventh field TANH on an RNN line is fl::RNN(.., RnnMode::TANH)'s own spelling.
+    auto l = std::make_shared<RecurrentLayer>();
+    auto& d = l->d;
+    try {
+      size_t used = 0;
+      auto num = [&](size_t i, int def) { if (a.size() <= i) return def; int v = std::stoi(a[i], &used); if (used != a[i].size()) throw std::invalid_argument(""); return v; };
+      d.I = num(0, 0); d.H = num(1, 0); d.layers = num(2, 1); d.dirs = num(3, 0) > 0 ? 2 : 1;
+      d.dropP = a.size() > 4 ? std::stod(a[4], &used) : 0.0;
+      if (a.size() > 4 && used != a[4].size()) throw std::invalid_argument("");
+    } catch (const std::exception&) {
+      throw std::invalid_argument("Failed parsing - " + s.line);
+    }
+    const bool tanhMode = s.tok == "RNN" && a.size() == 6 && a[5] == "TANH";
+    if (d.I < 1 || d.H < 1 || d.layers < 1 || !(d.dropP >= 0.0 && d.dropP < 1.0) || a.size() > (tanhMode ? 6u : 5u))
+      throw std::invalid_argument("Failed parsing - " + s.line);
+    d.mode = s.tok == "LSTM" ? W2L_RNN_LSTM : s.tok == "GRU" ? W2L_RNN_GRU : tanhMode ? W2L_RNN_TANH : W2L_RNN_RELU;
     return l;
   }
   if (s.tok == "R") return std::make_shared<ReLULayer>();

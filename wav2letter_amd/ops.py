@@ -7,7 +7,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, check
+from ._lib import ConvDesc, RnnDesc, check
 
 
 def _s():
@@ -142,6 +142,61 @@ def swish_backward(x, dy, beta=1.0, out=None):
     dx = torch.empty_like(dy) if out is None else out
     check(_lib.lib().w2l_swish_backward(_p(x), _p(dy), _p(dx), x.numel(), beta, _s()), "swish_backward")
     return dx
+
+
+RNN_MODES = {"relu": 0, "tanh": 1, "lstm": 2, "gru": 3}
+
+
+def rnn_desc(x, mode, H, layers=1, bidirectional=False, dropout=0.0, train=False, seed=0, rng_stream=0):
+    """x [B][T][I] (dense); mode: a key of RNN_MODES or its number"""
+    B, T, I = x.shape
+    dirs = 2 if bidirectional else 1
+    return RnnDesc(RNN_MODES.get(mode, mode), I, H, layers, dirs, B, T, I, H * dirs, int(train), dropout, seed, rng_stream)
+
+
+def rnn_param_count(mode, I, H, layers=1, bidirectional=False):
+    d = RnnDesc(RNN_MODES.get(mode, mode), I, H, layers, 2 if bidirectional else 1, 1, 1, I, H * (2 if bidirectional else 1), 0, 0.0, 0, 0)
+    return int(_lib.lib().w2l_rnn_param_count(C.byref(d)))
+
+
+def rnn_forward(d, x, params):
+    """fl::RNN forward (w2l_rnn_forward) -> (y [B][T][H dirs], workspace); the workspace is what rnn_backward needs when d.train"""
+    L = _lib.lib()
+    nbytes = L.w2l_rnn_workspace_size(C.byref(d))
+    ws = torch.empty(max(nbytes // 4, 1), device=x.device, dtype=torch.float32)
+    y = torch.empty(d.B, d.T, d.ldy, device=x.device, dtype=torch.float32)
+    check(L.w2l_rnn_forward(C.byref(d), _p(x), _p(params), _p(y), _p(ws), nbytes, _s()), "rnn_forward")
+    return y, ws
+
+
+def rnn_backward(d, x, params, y, dy, ws, need_dx=True):
+    """-> (dx or None, dparams), from the descriptor, operands and workspace of a training rnn_forward"""
+    dx = torch.empty_like(x) if need_dx else None
+    dparams = torch.empty_like(params)
+    check(_lib.lib().w2l_rnn_backward(C.byref(d), _p(x), _p(params), _p(y), _p(dy), _p(dx), _p(dparams), _p(ws), ws.numel() * 4, _s()), "rnn_backward")
+    return dx, dparams
+
+
+class _Rnn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, params, d):
+        x, params = x.contiguous(), params.contiguous()
+        y, ws = rnn_forward(d, x, params)
+        ctx.d, ctx.ws = d, ws
+        ctx.save_for_backward(x, params, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, params, y = ctx.saved_tensors
+        dx, dparams = rnn_backward(ctx.d, x, params, y, dy.contiguous(), ctx.ws, ctx.needs_input_grad[0])
+        return dx, dparams, None
+
+
+def rnn(x, params, mode, H, layers=1, bidirectional=False, dropout=0.0, train=True, seed=0, rng_stream=0):
+    """fl::RNN as a differentiable torch op over the C ABI: x [B][T][I], params flat (rnn_param_count floats, the order of
+    include/w2l_hip.h) -> y [B][T][H dirs].  train=False: no dropout and no backward."""
+    return _Rnn.apply(x, params, rnn_desc(x, mode, H, layers, bidirectional, dropout, train, seed, rng_stream))
 
 
 def _ln_scratch(groups, inner):

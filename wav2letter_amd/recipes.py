@@ -203,6 +203,13 @@ def conformer_conv_module_arch(C, kw, p):
     return "\n".join(lines) + "\n"
 
 
+def blstm_ctc_arch(nfeat, hidden, layers, nclass, dropout):
+    """a bidirectional LSTM acoustic model for CTC on the (T, nfeat, 1, B) input: reorder into Flashlight's recurrent layout
+    (nfeat, B, T, 1), `layers` stacked BLSTM layers of `hidden` units, reorder to (2 hidden, T, B, 1), a Linear onto the classes"""
+    lines = ["RO 1 3 0 2", f"LSTM {nfeat} {hidden} {layers} 1 {dropout}", "RO 0 2 1 3", f"L {2 * hidden} {nclass}"]
+    return "\n".join(lines) + "\n"
+
+
 # train.cfg essentials of the two headline recipes (flags the hot path consumes)
 TDS_CTC_FLAGS = dict(criterion="ctc", lr=0.3, momentum=0.5, maxgradnorm=1.0, onorm="target", sqnorm=True,
                      filterbanks=80, batchsize=4)       # recipes/sota/2019/librispeech/train_am_tds_ctc.cfg:11-30
