@@ -750,6 +750,14 @@ FL_COMPAT_API FlatView flatGradients(const std::shared_ptr<fl::Module>& network)
 // images with fp32 accumulation; activations, master weights, LayerNorm, the optimizer and the criterion stay fp32 (no-op for
 // any other module)
 FL_COMPAT_API void setMixedPrecision(const std::shared_ptr<fl::Module>& network, bool on);
+// fl_compat extension (--w2l_split_gemm): split precision -- every fl::Linear product of a network built from an arch file
+// (forward, data and weight gradients, reduction length >= 32) multiplies its fp32 operands as two bf16 values each, three bf16
+// MFMA products per fp32 product, fp32 accumulation (w2l_gemm_f32_split in w2l_hip.h: within (2^-16 + K 2^-23) |A||B| of the exact
+// product).  Activations, master weights, the convolutions, the attention core, the recurrent layers, LayerNorm, the optimizer and
+// the criterion stay fp32; the weight-gradient stream stays on; nothing is planned again; checkpoints do not record it.  The two
+// modes exclude each other: std::invalid_argument while setMixedPrecision is on, and from setMixedPrecision(network, true) while
+// this is on.  No-op for any other module.
+FL_COMPAT_API void setSplitPrecision(const std::shared_ptr<fl::Module>& network, bool on);
 // fl_compat extension (--w2l_amp_convs): the second level of that mode -- the wide time convolutions at H == 1 (the `C` lines of
 // the conv_glu recipes, the Transformer recipes' front end) multiply bf16 images too (w2l_conv_bf16_*).  Acts only while
 // setMixedPrecision is on; the next forward plans again (weight images and image scratch belong to the plan).  No-op for any

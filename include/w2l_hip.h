@@ -715,6 +715,23 @@ int w2l_gemm_bf16_ex(int M, int N, int K, const uint16_t* A, int lda, int aKMajo
                      int ldc, const float* bias, int relu, const w2l_gemm_epilogue* e, w2l_stream_t stream);
 int w2l_gemm_bf16_grouped(int groups, int M, int N, int K, const uint16_t* const* A, int lda, const uint16_t* const* B, int ldb,
                           float* const* C, int ldc, const float* const* bias, w2l_stream_t stream);
+/* Split-bf16 products ("3xBF16", "fast fp32"; gemm_split.hpp): fp32 operands, results and accumulation, every operand
+ * element split in registers into hi = rne_bf16(x) and lo = rne_bf16(x - hi) on the way into LDS, and a . b multiplied as
+ * a_lo b_hi + a_hi b_lo + a_hi b_hi (that order, one fp32 accumulator) on v_mfma_f32_32x32x16_bf16.  Every element of C is within
+ * (2^-16 + K 2^-23) (|A| |B|)[m][n] of the exact product; the same bits every run.  Finite operands below 2^127 in magnitude:
+ * anything else gives a non-finite result.
+ * w2l_gemm_f32_split: w2l_gemm_f32's operand description (a_kcontig: A is [M][K] row-major, else [K][M]; b_kcontig: B is [N][K]
+ *   row-major, else [K][N]; any alignment, any leading dimension) with w2l_gemm_bf16's epilogue (may be NULL).  ALWAYS this kernel,
+ *   whatever the two process-wide switches say.  W2L_EINVAL: null operand or non-positive size; W2L_EUNSUPPORTED: K < 32.
+ * w2l_set_matmul_split(1): every w2l_linear_* product and w2l_gemm_f32 with K >= 32 of this process takes that kernel from now on
+ *   (the bias gradient of w2l_linear_backward_weight_bias then comes from w2l_colsum), except two classes that measured faster on the
+ *   fp32 kernels and stay there: weight-gradient products with K >= 16384, and data-gradient products (both operands k-contiguous) whose rows are not 16-byte aligned float4 rows, with K >= 256; returns
+ *   the previous value.
+ *   w2l_set_matmul_precision(1) takes precedence while both are on.  The time convolutions, the attention core, the recurrent scan
+ *   and the criteria stay on their fp32 kernels. */
+int w2l_gemm_f32_split(int M, int N, int K, const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, float* C,
+                       int ldc, const float* bias, int relu, const w2l_gemm_epilogue* epilogue, w2l_stream_t stream);
+int w2l_set_matmul_split(int on);
 int w2l_colsum(const float* x, float* out, size_t M, int N, w2l_stream_t stream); /* bias grads */
 
 /* fl::Conv2D kw x 1 over time (arch tokens C / C2 / TDS). x [B][T][H][Cin],
@@ -1187,6 +1204,13 @@ int w2l_trainer_set_mixed_precision(void* h, int on);
 /* second level of that mode: the wide time convolutions (w2l_conv_bf16_*) on bf16 operands too.  Acts only while
  * w2l_trainer_set_mixed_precision is on.  Call before w2l_trainer_plan: a change after it drops the plan (plan and bind again). */
 int w2l_trainer_set_mixed_precision_convs(void* h, int on);
+/* Split precision: the network's fl::Linear products (forward, data and weight gradients, K >= 32) on the split-bf16 kernel
+ * (w2l_set_matmul_split scoped to the network's passes; the weight-gradient stream stays on and its products take the same route).
+ * Storage, master weights, the time convolutions, the attention core, the recurrent layers, LayerNorm, the criterion and the
+ * optimizer stay fp32.  No new plan: the mode holds no images and no workspace, and a later w2l_trainer_plan keeps it.  A property
+ * of the run: checkpoints do not record it.  W2L_EINVAL: null handle, or on = 1 while w2l_trainer_set_mixed_precision is on --
+ * and w2l_trainer_set_mixed_precision(1) answers W2L_EINVAL while this is on: the two modes exclude each other. */
+int w2l_trainer_set_split_precision(void* h, int on);
 /* Weight-gradient stream (on by default): the fp32 training backward enqueues the products that feed nothing before the optimizer
  * -- the weight and bias gradients of the TDS blocks' Linears and of plain Linear layers, the filter gradients of the TDS and C2
  * convolutions -- on a non-blocking side stream the network owns, and makes `stream` wait for it before

@@ -194,6 +194,8 @@ class _SIGS:
     w2l_linear_backward_weight_bias = (_i, [_i, _i, _i, _p, _p, _p, _p, _p])
     w2l_colsum = (_i, [_p, _p, _sz, _i, _p])
     w2l_set_matmul_precision = (_i, [_i])
+    w2l_set_matmul_split = (_i, [_i])
+    w2l_gemm_f32_split = (_i, [_i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _p])
     w2l_bf16_convert = (_i, [_p, _sz, _i, _sz, _p, _sz, _p, _sz, _p])
     w2l_bf16_convert_multi = (_i, [_i, _p, _p])
     w2l_gemm_bf16_images = (_i, [_i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _sz, _f, _p])

@@ -16,6 +16,9 @@
 // Dispatch.  gemm_f32 (every w2l_linear_* product, w2l_gemm_f32, the dA product of criterion_fcc_big.hip) sends a product
 // C[M][N] = op(A) op(B) to the first line whose conditions hold -- this comment is the one place where the order is written down:
 //   1. launch128_bf16   gemm_bf16.hpp     w2l_set_matmul_precision(1) is in force and K >= 32: fp32 operands in memory, bf16 multiply
+//   1s. gemm_split     gemm_split.hpp    w2l_set_matmul_split(1) is in force (and line 1 is not) and K >= 32: fp32 operands in memory, each
+//                                         split into two bf16 values in registers, three bf16 products per fp32 product -- except
+//                                         k-row x k-row products with K >= 16384 and k-contiguous x k-contiguous products with rows that are not float4-able and K >= 256, which go on below
 //   2. (ragged K)                         K % 32 != 0, K >= 256, no bias / epilogue, operands LDS-DMA eligible (dX of the final
 //                                         layer, K = 9998): the whole K tiles go through lines 3 - 4, the K % 32 tail through
 //                                         line 5, accumulated into C
@@ -134,6 +137,8 @@ static int dispatch_b(const AOp& a, const float* B, int ldb, int b_kcontig, cons
 // ---- mixed precision (BASELINE config 3): w2l_set_matmul_precision(1) routes the fl::Linear GEMMs through the
 // bf16-multiply / fp32-accumulate kernel of gemm_bf16.hpp; operands and results stay fp32 in memory
 static std::atomic<int> g_matmul_bf16{0};
+// ---- split precision: w2l_set_matmul_split(1) routes the same products through the split-bf16 kernel of gemm_split.hpp
+static std::atomic<int> g_matmul_split{0};
 
 static int gemm_bf16(const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, const GemmOut& o, int epi,
                      hipStream_t s) {
@@ -157,6 +162,14 @@ int gemm_f32(const float* A, int lda, int a_kcontig, const float* B, int ldb, in
   float* const colsumOut = o.colsum;   // only the 160-wide LDS-DMA kernel produces it (below)
   o.colsum = nullptr;
   if (g_matmul_bf16.load(std::memory_order_relaxed) && K >= 32) return gemm_bf16(A, lda, a_kcontig, B, ldb, b_kcontig, o, epi, s);
+  // split mode: two classes stay on the fp32 kernels below, which measured faster there (fp32 is the more accurate product; DESIGN
+  // 3.33, profiles/gemm_split_one.log): k-row x k-row products with K >= 16384 (dW at M = 24000: 0.775 ms fp32, 0.912 ms split) and
+  // k-contiguous x k-contiguous products whose rows are not float4-able, which the split kernel loads element by element, with K >= 256 (dX of the final layer,
+  // K = ld = 9998: 1.488 ms fp32, 1.644 ms split; the K - K % 32 part that line 2 hands back here has the same leading dimension)
+  const bool splitScalar = a_kcontig && b_kcontig && (pick_vec(A, lda, K) != 4 || pick_vec(B, ldb, K) != 4);
+  const bool splitKeepsFp32 = (!a_kcontig && !b_kcontig && K >= 16384) || (splitScalar && K >= 256);
+  if (g_matmul_split.load(std::memory_order_relaxed) && K >= 32 && !splitKeepsFp32)
+    return gemm_split(A, lda, a_kcontig, B, ldb, b_kcontig, o, epi, s);
   // address range of each operand in bytes (the buffer-addressed instances need 32-bit offsets)
   const unsigned long long ab = 4ull * (a_kcontig ? (unsigned long long)(M - 1) * lda + K : (unsigned long long)(K - 1) * lda + M);
   const unsigned long long bb = 4ull * (b_kcontig ? (unsigned long long)(N - 1) * ldb + K : (unsigned long long)(K - 1) * ldb + N);
@@ -221,6 +234,9 @@ using namespace w2l;
 // 0 = fp32 MFMA (default), 1 = bf16 multiply / fp32 accumulate for every w2l_linear_* / w2l_gemm_f32 call of this
 // process from now on; returns the previous mode.  (fl's --fl_amp_use_mixed_precision, restated for bf16.)
 W2L_API int w2l_set_matmul_precision(int mode) { return g_matmul_bf16.exchange(mode ? 1 : 0); }
+
+// 1 = the split-bf16 kernel for the same calls (K >= 32) from now on; returns the previous value.  Mode 1 above takes precedence.
+W2L_API int w2l_set_matmul_split(int on) { return g_matmul_split.exchange(on ? 1 : 0); }
 
 namespace w2l {
 bool matmul_bf16_mode() { return g_matmul_bf16.load(std::memory_order_relaxed) != 0; }
@@ -370,6 +386,15 @@ W2L_API int w2l_gemm_bf16_ex(int M, int N, int K, const uint16_t* A, int lda, in
   GemmOut o{C, bias, M, N, K, ldc, (bias ? EPI_BIAS : 0) | (relu ? EPI_RELU : 0)};
   set_epilogue(o, e, true);
   return launch128h(A, lda, B, ldb, o, gemm_epi(o), (hipStream_t)stream, 0, 0, aKMajor != 0, bKMajor != 0);
+}
+
+// the split-bf16 product on fp32 operands of any layout, directly (whatever the process-wide switches say)
+W2L_API int w2l_gemm_f32_split(int M, int N, int K, const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, float* C,
+                               int ldc, const float* bias, int relu, const w2l_gemm_epilogue* e, w2l_stream_t stream) {
+  if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C) return W2L_EINVAL;
+  GemmOut o{C, bias, M, N, K, ldc, (bias ? EPI_BIAS : 0) | (relu ? EPI_RELU : 0)};
+  set_epilogue(o, e, true);
+  return gemm_split(A, lda, a_kcontig, B, ldb, b_kcontig, o, gemm_epi(o), (hipStream_t)stream);
 }
 
 // `groups` (1 .. 4) products of ONE shape in one launch: C_g = A_g . B_g^T (+ bias_g); A, B, C, bias: host arrays of device pointers

@@ -747,6 +747,8 @@ int colsum(const float* x, float* out, size_t M, int N, hipStream_t s);   // con
 int gemm_f32(const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, GemmOut o, hipStream_t s,
              bool* colsumDone = nullptr);
 // LDS-DMA kernels on caller-prepared operand views (see gemm.hip); o carries M, N, K, C, ldc, bias and the row remap
+// the split-bf16 product (gemm_split.hip): fp32 operands of any layout and alignment, K >= 32 (else W2L_EUNSUPPORTED); epi = gemm_epi(o)
+int gemm_split(const float* A, int lda, int a_kcontig, const float* B, int ldb, int b_kcontig, const GemmOut& o, int epi, hipStream_t s);
 int gemm_glds_raw(const float* A, int lda, bool akc, size_t aBytes, const float* B, int ldb, bool bkc, size_t bBytes,
                   GemmOut o, int epi, hipStream_t s);
 

@@ -71,6 +71,7 @@ int main(int argc, char** argv) {
     std::shared_ptr<fl::Module> network = fl::pkg::runtime::ModulePlugin(archPath).arch(nFeat, numClasses);
     if (flags.getb("fl_amp_use_mixed_precision", false)) setMixedPrecision(network, true);
     if (flags.getb("fl_amp_use_mixed_precision", false) && flags.getb("w2l_amp_convs", false)) setMixedPrecisionConvolutions(network, true);
+    if (flags.getb("w2l_split_gemm", false)) setSplitPrecision(network, true);
     std::shared_ptr<SequenceCriterion> criterion;
     if (criterionName == "ctc") criterion = std::make_shared<CTCLoss>(scalemode);
     else if (criterionName == "asg") criterion = std::make_shared<ASGLoss>(numClasses, scalemode, flags.getd("transdiag", 0.0));

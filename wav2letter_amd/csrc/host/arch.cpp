@@ -161,6 +161,9 @@ void checkFlagDependencies(const Flags& flags) {
   if (flags.getb("w2l_amp_convs", false) && !flags.getb("fl_amp_use_mixed_precision", false))
     throw std::invalid_argument("--w2l_amp_convs=true needs --fl_amp_use_mixed_precision=true: the bf16 wide convolutions are the second "
                                 "level of the mixed-precision mode");
+  if (flags.getb("w2l_split_gemm", false) && flags.getb("fl_amp_use_mixed_precision", false))
+    throw std::invalid_argument("--w2l_split_gemm=true and --fl_amp_use_mixed_precision=true exclude each other: the split-bf16 products "
+                                "keep fp32 operands, the mixed-precision mode rounds them to bf16 -- choose one");
 }
 
 // getCriterionScaleMode(FLAGS_onorm, FLAGS_sqnorm)  (recipes/slimIPL/src/Train.cpp:389)

@@ -234,6 +234,7 @@ int main(int argc, char** argv) {
     std::shared_ptr<fl::Module> network = fl::pkg::runtime::ModulePlugin(archPath).arch(nFeat, numClasses);
     if (flags.getb("fl_amp_use_mixed_precision", false)) setMixedPrecision(network, true);
     if (flags.getb("fl_amp_use_mixed_precision", false) && flags.getb("w2l_amp_convs", false)) setMixedPrecisionConvolutions(network, true);
+    if (flags.getb("w2l_split_gemm", false)) setSplitPrecision(network, true);
     std::shared_ptr<CTCLoss> ctc;
     std::shared_ptr<ASGLoss> asgCrit;
     std::shared_ptr<SequenceCriterion> criterion;

@@ -887,6 +887,7 @@ class PlannedNet : public fl::Sequential {
       if (!evalNet_) {
         evalNet_ = w2l::buildSequentialFromText(archText_, archNFeat_, archNLabel_);
         evalNet_->setMixedPrecisionConvs(net_->mixedPrecisionConvs());
+        evalNet_->setSplitPrecision(net_->splitPrecision());
         if (!bucketOffsets_.empty()) evalNet_->setGradBuckets(bucketOffsets_, bucketEvents_);
       }
       if (B != evalB_ || T != evalT_) {
@@ -949,6 +950,16 @@ class PlannedNet : public fl::Sequential {
   float* paramPtr() { return (float*)paramArena_.get(); }
   float* gradPtr() { return (float*)gradArena_.get(); }
   bool mixed_ = false;
+  // the two precision modes exclude each other: the second one to be switched on is refused
+  void setMixed(bool on) {
+    if (on && net_->splitPrecision()) throw std::invalid_argument("setMixedPrecision: the network is in split-precision mode (setSplitPrecision(network, false) first)");
+    mixed_ = on;
+  }
+  void setSplit(bool on) {
+    if (on && mixed_) throw std::invalid_argument("setSplitPrecision: the network is in mixed-precision mode (setMixedPrecision(network, false) first)");
+    net_->setSplitPrecision(on);
+    if (evalNet_) evalNet_->setSplitPrecision(on);
+  }
   // the wide convolutions' bf16 images belong to the plan: both graphs plan again at their next forward
   void setMixedConvs(bool on) {
     if (net_->mixedPrecisionConvs() == on) return;
@@ -1295,7 +1306,10 @@ FlatView flatParameters(const std::shared_ptr<fl::Module>& network) {
   return p ? FlatView{p->paramPtr(), p->impl().paramFloats()} : FlatView{nullptr, 0};
 }
 void setMixedPrecision(const std::shared_ptr<fl::Module>& network, bool on) {
-  if (auto* p = plannedOf(network.get())) p->mixed_ = on;
+  if (auto* p = plannedOf(network.get())) p->setMixed(on);
+}
+void setSplitPrecision(const std::shared_ptr<fl::Module>& network, bool on) {
+  if (auto* p = plannedOf(network.get())) p->setSplit(on);
 }
 void setMixedPrecisionConvolutions(const std::shared_ptr<fl::Module>& network, bool on) {
   if (auto* p = plannedOf(network.get())) p->setMixedConvs(on);

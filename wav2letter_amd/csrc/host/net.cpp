@@ -1777,7 +1777,17 @@ size_t Sequential::plan(int B, int T, int nFeat) {
   return pl.used();
 }
 
+namespace {
+struct SplitMode {   // scoped w2l_set_matmul_split: covers one pass of the network, also when it ends by an exception
+  int prev = 0;
+  bool on;
+  explicit SplitMode(bool on_) : on(on_) { if (on) prev = w2l_set_matmul_split(1); }
+  ~SplitMode() { if (on) w2l_set_matmul_split(prev); }
+};
+}  // namespace
+
 const float* Sequential::forward(Ctx& c, float* arena, const float* xRef) {
+  SplitMode sm(split_);
   // reference input (T, NFEAT, 1, B) is time-fastest [B][NFEAT][T]; internal layout is frame-major
   float* x = arena + inOff_;
   w2lCheck(w2l_transpose(xRef, x, in_.B, in_.F, in_.T, c.stream), "input transpose");
@@ -1879,6 +1889,7 @@ struct Sequential::WgScope {
 void Sequential::backward(Ctx& c, float* arena, const float* dOut) {
   const float* dy = dOut;
   c.convScratch = convScratchElems_ ? bfp(arena, convScratchOff_) : nullptr;
+  SplitMode sm(split_);   // (in force on this thread for the products of both streams)
   WgScope wg(*this, c);
   // first layer with parameters: nothing before it needs a data gradient
   size_t firstParam = 0;

@@ -239,6 +239,10 @@ int main(int argc, char** argv) {
         std::cout << "Mixed precision: the wide time convolutions multiply bf16 operands too (--w2l_amp_convs)" << std::endl;
       }
     }
+    if (flags.getb("w2l_split_gemm", false)) {
+      setSplitPrecision(network, true);   // fp32 operands as hi + lo bf16, three bf16 products per fp32 product in the fl::Linear GEMMs
+      std::cout << "Split-precision matrix multiplies enabled (--w2l_split_gemm: 3 x bf16 per fp32 product, fp32 accumulation and storage)" << std::endl;
+    }
     std::shared_ptr<SequenceCriterion> criterion;
     if (criterionName == "ctc") criterion = std::make_shared<CTCLoss>(scalemode);
     else if (criterionName == "asg") criterion = std::make_shared<ASGLoss>(numClasses, scalemode, flags.getd("transdiag", 0.0));
@@ -273,6 +277,7 @@ int main(int argc, char** argv) {
       networkEMA = fl::pkg::runtime::ModulePlugin(archPath).arch(nFeat, numClasses);
       if (flags.getb("fl_amp_use_mixed_precision", false)) setMixedPrecision(networkEMA, true);
       if (flags.getb("fl_amp_use_mixed_precision", false) && flags.getb("w2l_amp_convs", false)) setMixedPrecisionConvolutions(networkEMA, true);
+      if (flags.getb("w2l_split_gemm", false)) setSplitPrecision(networkEMA, true);
     }
     // (the file of the averaged network holds the network alone, Train.cpp:776-781: a parameter-free criterion fills the container's slot)
     std::shared_ptr<fl::Module> emaFileCrit = std::make_shared<CTCLoss>(scalemode);

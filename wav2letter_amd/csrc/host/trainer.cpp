@@ -519,7 +519,25 @@ W2L_API int w2l_trainer_bind_state2(void* h, float* state2) {
   ((Trainer*)h)->state2 = state2;
   return W2L_OK;
 }
-W2L_API int w2l_trainer_set_mixed_precision(void* h, int on) { ((Trainer*)h)->mixedPrecision = on != 0; return W2L_OK; }
+// the two precision modes exclude each other: the second one to be switched on is refused
+static int modeConflict(Trainer* t, const char* what) {
+  t->lastError = g_err = std::string(what) + ": mixed precision and split precision exclude each other (switch the other one off first)";
+  return W2L_EINVAL;
+}
+W2L_API int w2l_trainer_set_mixed_precision(void* h, int on) {
+  Trainer* t = (Trainer*)h;
+  if (on && t->net->splitPrecision()) return modeConflict(t, "set_mixed_precision");
+  t->mixedPrecision = on != 0;
+  return W2L_OK;
+}
+// the network's fl::Linear products on the split-bf16 kernel (Sequential::setSplitPrecision): no images, no workspace, no new plan
+W2L_API int w2l_trainer_set_split_precision(void* h, int on) {
+  if (!h) return W2L_EINVAL;
+  Trainer* t = (Trainer*)h;
+  if (on && t->mixedPrecision) return modeConflict(t, "set_split_precision");
+  t->net->setSplitPrecision(on != 0);
+  return W2L_OK;
+}
 
 // the fp32 backward's weight, bias and filter gradients on the network's own side stream, joined into the caller's stream before
 // w2l_trainer_forward_backward / w2l_trainer_backward return (Sequential::setWeightGradStream; on by default).  Same results either

@@ -185,6 +185,12 @@ class Sequential {
   // Ctx::bf16 is set.
   void setMixedPrecisionConvs(bool on) { bf16Convs_ = on; }
   bool mixedPrecisionConvs() const { return bf16Convs_; }
+  // split precision: forward() and backward() run with w2l_set_matmul_split(1) in force, so every fl::Linear product
+  // of the pass (K >= 32) -- the weight-gradient stream's included: the same thread enqueues them inside backward() -- takes the
+  // split-bf16 kernel; everything else stays fp32.  No plan is involved.  Not together with a pass whose Ctx::bf16 is set: the
+  // owners of the two switches (the trainer, the fl:: network) refuse the pair.
+  void setSplitPrecision(bool on) { split_ = on; }
+  bool splitPrecision() const { return split_; }
   const std::vector<ParamInfo>& params() const { return params_; }
   size_t paramFloats() const { return paramFloats_; }
 
@@ -231,6 +237,7 @@ class Sequential {
   Act in_, out_;
   size_t inOff_ = 0;
   bool bf16Convs_ = false;
+  bool split_ = false;
   bool wantInputGrad_ = false;
   const float* inputGrad_ = nullptr;
   size_t convScratchOff_ = 0, convScratchElems_ = 0;
@@ -311,7 +318,8 @@ struct Flags {
 Flags parseFlagsText(const std::string& text);
 Flags parseFlagsFile(const std::string& path);
 int criterionScaleMode(const std::string& onorm, bool sqnorm);  // getCriterionScaleMode
-// flags that only mean something beside another one (--w2l_amp_convs without --fl_amp_use_mixed_precision): std::invalid_argument.
+// flags that only mean something beside another one (--w2l_amp_convs without --fl_amp_use_mixed_precision), or that exclude each
+// other (--w2l_split_gemm with --fl_amp_use_mixed_precision): std::invalid_argument.
 // Host logic: the drivers call it on their final flag set before anything touches the device.
 void checkFlagDependencies(const Flags& flags);
 

@@ -346,6 +346,33 @@ def gemm_bf16(A, B, K, bias=None, relu=False, mask=None, mask_scale=1.0, addend=
     return c
 
 
+def gemm_split(A, B, a_kcontig=True, b_kcontig=False, bias=None, relu=False, mask=None, mask_scale=1.0, addend=None, out=None,
+               accumulate=False, drop_p=0.0, drop_seed=0, drop_stream=0):
+    """w2l_gemm_f32_split: C[M][N] fp32 = op(A) op(B) on the split-bf16 kernel (fp32 operands split into hi + lo bf16 in registers,
+    three bf16 MFMA products per fp32 product, fp32 accumulation) whatever the process-wide switches say.  A is [M][K]
+    (a_kcontig) or [K][M]; B is [N][K] (b_kcontig) or [K][N]; 2-d float32 CUDA tensors or views with unit inner stride.
+    K >= 32.  The epilogue operands are w2l_gemm_bf16's."""
+    import ctypes as C
+    for t in (A, B):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1):
+            raise _lib.W2LInvalidArgument("gemm_split: 2-d float32 CUDA operands with unit inner stride")
+    (M, K) = A.shape if a_kcontig else (A.shape[1], A.shape[0])
+    (N, Kb) = B.shape if b_kcontig else (B.shape[1], B.shape[0])
+    if K != Kb:
+        raise _lib.W2LInvalidArgument(f"gemm_split: reduction lengths differ ({K} and {Kb})")
+    c = out if out is not None else torch.empty(M, N, dtype=torch.float32, device=A.device)
+    e = _lib.GemmEpilogue()
+    e.mask = _p(mask) if mask is not None else None
+    e.maskScale = mask_scale
+    e.addend = _p(addend) if addend is not None else None
+    e.accumulate = int(accumulate)
+    e.dropP = drop_p
+    e.dropSeed, e.dropStream = drop_seed, drop_stream
+    _lib.check(_lib.lib().w2l_gemm_f32_split(M, N, K, _p(A), A.stride(0), int(a_kcontig), _p(B), B.stride(0), int(b_kcontig), _p(c),
+                                             c.stride(0), _p(bias) if bias is not None else None, int(relu), C.byref(e), _s()), "gemm_split")
+    return c
+
+
 def gemm_bf16_images(A, B, K, bias=None, relu=False, keep_f32=False, rows_image=True, transposed_image=True, mask_image=None,
                      mask_scale=1.0, addend=None, drop_p=0.0, drop_seed=0, drop_stream=0):
     """w2l_gemm_bf16_images: the product's result as bf16 images (zero-padded to multiples of 64 here, the caller's job in the ABI)

@@ -47,6 +47,7 @@ def _lib_tr():
         L.w2l_trainer_set_step.argtypes = [vp, u32]
         L.w2l_trainer_set_mixed_precision.argtypes = [vp, i]
         L.w2l_trainer_set_mixed_precision_convs.argtypes = [vp, i]
+        L.w2l_trainer_set_split_precision.argtypes = [vp, i]
         L.w2l_trainer_set_weight_grad_stream.argtypes = [vp, i]
         L.w2l_trainer_set_input_gradient.argtypes = [vp, i]
         L.w2l_trainer_input_gradient.argtypes = [vp, C.POINTER(vp)]
@@ -108,14 +109,16 @@ class _EvalPlan:
         self.crit_ws = torch.empty(256, dtype=torch.uint8, device=device)   # (bind needs one; evaluation scores in eval_buf)
         self.eval_buf = None
 
-    def bind(self, params, grads_full, mom, mixed):
+    def bind(self, params, grads_full, mom, mixed, split=False):
         _check(self.L.w2l_trainer_bind(self.h, params.data_ptr(), grads_full.data_ptr(), mom.data_ptr() if mom is not None else None,
                                        self.arena.data_ptr(), self.crit_ws.data_ptr()), "evaluate bind")
         if self.eval_buf is None:
             self.eval_buf = torch.empty(max(int(self.L.w2l_trainer_eval_bytes(self.h)), 256), dtype=torch.uint8,
                                         device=self.arena.device)
             _check(self.L.w2l_trainer_bind_eval(self.h, self.eval_buf.data_ptr(), self.eval_buf.numel()), "bind_eval")
+        _check(self.L.w2l_trainer_set_split_precision(self.h, 0), "split precision")   # (the two exclude each other: off first)
         _check(self.L.w2l_trainer_set_mixed_precision(self.h, int(mixed)), "mixed precision")
+        _check(self.L.w2l_trainer_set_split_precision(self.h, int(split)), "split precision")
 
     def __del__(self):
         try:
@@ -137,6 +140,7 @@ class Trainer:
         self._eval_plans = {}
         self._mixed = False
         self._mixed_convs = False
+        self._split = False
         self.h = L.w2l_trainer_create(arch_text.encode(), nfeat, nlabel, criterion.encode(), int(scalemode),
                                       float(transdiag))
         if not self.h:
@@ -324,7 +328,7 @@ class Trainer:
             while len(self._eval_plans) >= self._EVAL_PLANS:
                 self._eval_plans.pop(next(iter(self._eval_plans)))
         self._eval_plans[key] = ev
-        ev.bind(self.params, self.grads_full, self.mom, self._mixed)
+        ev.bind(self.params, self.grads_full, self.mom, self._mixed, self._split)
         if input_sizes is not None and not (torch.is_tensor(input_sizes) and input_sizes.dtype == torch.float32
                                             and input_sizes.is_cuda and input_sizes.is_contiguous() and input_sizes.numel() == B):
             raise ValueError("input sizes: contiguous float32 CUDA tensor of B elements")
@@ -370,6 +374,14 @@ class Trainer:
                 self.plan(self.B, self.T, self.Lt)
                 if sizes is not None:
                     self.set_input_sizes(sizes)
+
+    def set_split_precision(self, on=True):
+        """the network's fl::Linear products (forward, data and weight gradients) on the split-bf16 kernel: fp32 operands split into
+        two bf16 values in registers, three bf16 MFMA products per fp32 product, fp32 accumulation (ops.gemm_split).  Everything
+        else stays fp32; no new plan, a later plan() keeps the mode, checkpoints do not record it.  ValueError together with
+        set_mixed_precision(True), whichever comes second."""
+        _check(self.L.w2l_trainer_set_split_precision(self.h, int(bool(on))), "split precision")
+        self._split = bool(on)
 
     def set_weight_grad_stream(self, on=True):
         """fp32 backward: the weight, bias and filter gradients on the network's own side stream, joined into the step's stream
