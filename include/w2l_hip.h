@@ -800,6 +800,56 @@ int w2l_rnn_forward(const w2l_rnn_desc* d, const float* x, const float* params, 
                     w2l_stream_t stream);
 int w2l_rnn_backward(const w2l_rnn_desc* d, const float* x, const float* params, const float* y, const float* dy, float* dx,
                      float* dparams, void* workspace, size_t workspaceBytes, w2l_stream_t stream);
+/* The kernels of the teacher-forced seq2seq criterion (criterion_s2s.hip, DESIGN 3.34 is the contract; the criterion itself is
+ * composed in wav2letter_amd/seq2seq.py from these, w2l_rnn_* in GRU mode and w2l_linear_*).  fp32, row-major.  Lengths, targets and
+ * tokens are HOST arrays of int32: every call checks them before its first launch and copies them into its workspace.  Every sum has
+ * one order: two calls give the same bits, and what an utterance receives does not depend on B.
+ *
+ * Encoder-decoder attention, one head: for b < B, u < U, t < T
+ *   score[b][u][t] = h[b][u] . k[b][t] / sqrt(H) + w[b][u][t],   -inf for t >= keyLen[b]
+ *   w = -(t - c)^2 / (2 windowStd^2), c = u keyLen[b] / tgtLen[b], when windowStd > 0 and u < tgtLen[b]; else 0 (never materialised)
+ *   alpha = softmax over t (exactly 0 for t >= keyLen[b]),   out[b][u] = sum_t alpha[b][u][t] v[b][t]  (+ h[b][u] when addQuery)
+ * h, out, dout, dh [B][U][H] dense and 16-byte aligned; alpha, dalpha [B][U][T] dense; k, v, dk, dv [B][T][ldenc] with H columns used
+ * (so both halves of a [B][T][2 H] encoder output are read and written in place).  backward: dout (and dalpha unless NULL) to dh, dk,
+ * dv; all T rows of dk / dv are written; dk == dv receives dk + dv (keys == values).  workspace: w2l_s2s_attn_workspace_size(d, 0)
+ * bytes for forward, (d, 1) for backward; contents mean nothing between calls.
+ * W2L_EINVAL: null pointers (but dalpha), sizes below 1, ldenc < H, a keyLen outside 1..T, a tgtLen outside 1..U, a small workspace.
+ * W2L_EUNSUPPORTED: H not a multiple of 32 or above 1024, T above 1024, U above 512, B above 1024. */
+typedef struct {
+  int B, U, T, H;
+  int ldenc;          /* floats between two frames of k, v, dk, dv */
+  float windowStd;    /* <= 0: no window */
+  int addQuery;       /* out = h + context; backward then adds dout to dh */
+} w2l_s2s_attn_desc;
+size_t w2l_s2s_attn_workspace_size(const w2l_s2s_attn_desc* d, int backward);
+int w2l_s2s_attn_forward(const w2l_s2s_attn_desc* d, const float* h, const float* k, const float* v, const int* keyLen, const int* tgtLen,
+                         float* out, float* alpha, void* workspace, size_t workspaceBytes, w2l_stream_t stream);
+int w2l_s2s_attn_backward(const w2l_s2s_attn_desc* d, const float* h, const float* k, const float* v, const int* keyLen, const int* tgtLen,
+                          const float* alpha, const float* dout, const float* dalpha, float* dh, float* dk, float* dv, void* workspace,
+                          size_t workspaceBytes, w2l_stream_t stream);
+/* Label-smoothed cross entropy over z [M][N] (dense): target[m] in 0..N-1, or -1 for a row that counts nothing; rowUtt[m] in 0..B-1,
+ * non-decreasing (NULL: M / B rows per utterance, M % B == 0).  With lp = log_softmax(z[m]):
+ *   loss[b] = sum over the valid rows of b, in row order, of (1 - eps) (-lp[target[m]]) - (eps / N) sum_c lp[c]
+ * forward writes lse [M] (of every row) and loss [B]; one pass over each row.  backward writes
+ *   dz[m][c] = g[rowUtt[m]] (exp(z[m][c] - lse[m]) - (1 - eps) [c == target[m]] - eps / N),  +0.0f in the rows with target -1;
+ * dz may be z.  workspace: w2l_s2s_xent_workspace_size(M, B) bytes.
+ * W2L_EINVAL: null pointers (but rowUtt), sizes below 1, eps outside [0, 1), a target outside -1..N-1, a rowUtt out of range or
+ * descending, a small workspace.  W2L_EUNSUPPORTED: N above 65536, M above 524288, B above 1024. */
+size_t w2l_s2s_xent_workspace_size(int M, int B);
+int w2l_s2s_xent_forward(int M, int N, int B, const float* z, const int* target, const int* rowUtt, float eps, float* lse, float* loss,
+                         void* workspace, size_t workspaceBytes, w2l_stream_t stream);
+int w2l_s2s_xent_backward(int M, int N, int B, const float* z, const float* lse, const int* target, const int* rowUtt, float eps,
+                          const float* g, float* dz, void* workspace, size_t workspaceBytes, w2l_stream_t stream);
+/* Token embedding: x[m] = E[tokens[m]] (E [N][H]), or the start embedding `start` [H] where tokens[m] == -1; x, dx [M][H] dense.
+ * backward: dE[c] = the sum of dx[m] over the positions m that hold c, in ascending m (0 for a token nobody holds; all N rows are
+ * written) and dstart likewise for the positions that hold -1.  workspace: w2l_embedding_workspace_size(M, N) bytes.
+ * W2L_EINVAL: null pointers, sizes below 1, a token outside -1..N-1, a small workspace.  W2L_EUNSUPPORTED: N above 65536, M above
+ * 524288, H above 4096. */
+size_t w2l_embedding_workspace_size(int M, int N);
+int w2l_embedding_forward(int M, int N, int H, const int* tokens, const float* E, const float* start, float* x, void* workspace,
+                          size_t workspaceBytes, w2l_stream_t stream);
+int w2l_embedding_backward(int M, int N, int H, const int* tokens, const float* dx, float* dE, float* dstart, void* workspace,
+                           size_t workspaceBytes, w2l_stream_t stream);
 /* The kw x 1 convolutions over the mel rows of the TDS recipes in the mixed-precision mode (bf16 operand storage, see
  * w2l_gemm_bf16) -- fl::TDSBlock's time convolution (C -> C channels, stride 1) and the sub-sampling `C2 cin cout kw 1 s 1`
  * lines between the blocks (cin != cout <= 32 channels, stride 1 or 2, any padding): x / dy and the weights rounded to bf16,

@@ -9,5 +9,6 @@ from . import text  # noqa: F401  (token dictionary, lexicon, targets, TER / WER
 from . import cpc  # noqa: F401  (which frames the CPC criterion masks, which negatives it draws: host logic)
 from .criterion import (ASGLoss, CPCCriterion, CTCLoss, CriterionScaleMode, ForceAlignmentCriterion,  # noqa: F401
                         FullConnectionCriterion, LinSegCriterion, SequenceCriterion, getCriterionScaleMode, linear_target)
+from .seq2seq import Seq2SeqCriterion  # noqa: F401
 from .lexicon import Lexicon  # noqa: F401
 from .lm import NGramLM  # noqa: F401

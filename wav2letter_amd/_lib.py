@@ -236,6 +236,15 @@ class _SIGS:
     w2l_rnn_workspace_size = (_sz, [_p])
     w2l_rnn_forward = (_i, [_p, _p, _p, _p, _p, _sz, _p])
     w2l_rnn_backward = (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
+    w2l_s2s_attn_workspace_size = (_sz, [_p, _i])
+    w2l_s2s_attn_forward = (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
+    w2l_s2s_attn_backward = (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p])
+    w2l_s2s_xent_workspace_size = (_sz, [_i, _i])
+    w2l_s2s_xent_forward = (_i, [_i, _i, _i, _p, _p, _p, _f, _p, _p, _p, _sz, _p])
+    w2l_s2s_xent_backward = (_i, [_i, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p, _sz, _p])
+    w2l_embedding_workspace_size = (_sz, [_i, _i])
+    w2l_embedding_forward = (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _sz, _p])
+    w2l_embedding_backward = (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _sz, _p])
     w2l_swish_forward = (_i, [_p, _p, _sz, _f, _p])
     w2l_swish_backward = (_i, [_p, _p, _p, _sz, _f, _p])
     w2l_layernorm_scratch_doubles = (_sz, [_i, _sz])
@@ -354,6 +363,10 @@ class ConvDesc(C.Structure):
 class RnnDesc(C.Structure):  # w2l_rnn_desc; mode: 0 ReLU, 1 tanh, 2 LSTM, 3 GRU
     _fields_ = ([(n, C.c_int) for n in ("mode", "I", "H", "layers", "dirs", "B", "T", "ldx", "ldy", "train")] +
                 [("dropP", C.c_double), ("seed", C.c_uint32), ("rngStream", C.c_uint32)])
+
+
+class S2sAttnDesc(C.Structure):  # w2l_s2s_attn_desc
+    _fields_ = [(n, C.c_int) for n in ("B", "U", "T", "H", "ldenc")] + [("windowStd", C.c_float), ("addQuery", C.c_int)]
 
 
 class GemmEpilogue(C.Structure):  # w2l_gemm_epilogue

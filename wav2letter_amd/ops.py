@@ -4,10 +4,11 @@ section 2).  Used by tests and by the Python side of bench.py; the C++ host
 activations: [B][T][H][C]."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, RnnDesc, check
+from ._lib import ConvDesc, RnnDesc, S2sAttnDesc, check
 
 
 def _s():
@@ -197,6 +198,157 @@ def rnn(x, params, mode, H, layers=1, bidirectional=False, dropout=0.0, train=Tr
     """fl::RNN as a differentiable torch op over the C ABI: x [B][T][I], params flat (rnn_param_count floats, the order of
     include/w2l_hip.h) -> y [B][T][H dirs].  train=False: no dropout and no backward."""
     return _Rnn.apply(x, params, rnn_desc(x, mode, H, layers, bidirectional, dropout, train, seed, rng_stream))
+
+
+def _host_i32(a):
+    """lengths, targets and tokens of the seq2seq kernels are HOST int32 arrays (the C ABI checks them before its first launch)"""
+    return np.ascontiguousarray((a.detach().cpu() if torch.is_tensor(a) else a), dtype=np.int32)
+
+
+def _ws(nbytes, device):
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+class _S2sAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, enc, key_len, tgt_len, keyvalue, window_std, add_query):
+        if h.dim() != 3 or enc.dim() != 3 or h.dtype != torch.float32 or enc.dtype != torch.float32 or enc.shape[0] != h.shape[0]:
+            raise _lib.W2LInvalidArgument("s2s_attention: h [B][U][H] and enc [B][T][C] float32")
+        h, enc = h.contiguous(), enc.contiguous()
+        (B, U, H), (_, T, Cc) = h.shape, enc.shape
+        if Cc != (2 * H if keyvalue else H):
+            raise _lib.W2LInvalidArgument(f"s2s_attention: enc must have {'2 H' if keyvalue else 'H'} = {2 * H if keyvalue else H} columns, got {Cc}")
+        kl, tl = _host_i32(key_len), _host_i32(tgt_len)
+        if kl.shape != (B,) or tl.shape != (B,):
+            raise _lib.W2LInvalidArgument("s2s_attention: key_len and tgt_len must hold B lengths")
+        d = S2sAttnDesc(B, U, T, H, Cc, float(window_std or 0.0), int(bool(add_query)))
+        L = _lib.lib()
+        out, alpha = torch.empty_like(h), torch.empty(B, U, T, device=h.device, dtype=torch.float32)
+        nbytes = L.w2l_s2s_attn_workspace_size(C.byref(d), 0)
+        ws = _ws(nbytes, h.device)
+        k = enc.data_ptr()
+        check(L.w2l_s2s_attn_forward(C.byref(d), _p(h), k, k + 4 * H * int(keyvalue), kl.ctypes.data, tl.ctypes.data, _p(out), _p(alpha),
+                                     _p(ws), nbytes, _s()), "s2s_attn_forward")
+        ctx.d, ctx.kl, ctx.tl, ctx.keyvalue = d, kl, tl, keyvalue
+        ctx.save_for_backward(h, enc, alpha)
+        ctx.set_materialize_grads(False)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx, dout, dalpha):
+        h, enc, alpha = ctx.saved_tensors
+        d, L = ctx.d, _lib.lib()
+        dout = torch.zeros_like(h) if dout is None else dout.contiguous()
+        dalpha = None if dalpha is None else dalpha.contiguous()
+        dh, denc = torch.empty_like(h), torch.empty_like(enc)
+        nbytes = L.w2l_s2s_attn_workspace_size(C.byref(d), 1)
+        ws = _ws(nbytes, h.device)
+        k, dk = enc.data_ptr(), denc.data_ptr()
+        off = 4 * d.H * int(ctx.keyvalue)
+        check(L.w2l_s2s_attn_backward(C.byref(d), _p(h), k, k + off, ctx.kl.ctypes.data, ctx.tl.ctypes.data, _p(alpha), _p(dout), _p(dalpha),
+                                      _p(dh), dk, dk + off, _p(ws), nbytes, _s()), "s2s_attn_backward")
+        return dh, denc, None, None, None, None, None
+
+
+def s2s_attention(h, enc, key_len, tgt_len, keyvalue=False, window_std=None, add_query=False):
+    """encoder-decoder attention of the seq2seq criterion (w2l_s2s_attn_*): h [B][U][H] against enc [B][T][C] -- keys
+    the columns 0..H-1 and values H..2H-1 when keyvalue (C = 2 H), else keys = values = enc (C = H) -- with key_len [B] valid keys,
+    the soft window of width window_std around u key_len / tgt_len (None: no window) -> (context [B][U][H], + h when add_query;
+    alpha [B][U][T]).  Differentiable in h and enc, through both results."""
+    return _S2sAttention.apply(h, enc, key_len, tgt_len, bool(keyvalue), window_std, add_query)
+
+
+def s2s_xent_forward(z, target, eps, row_utt=None, B=None):
+    """w2l_s2s_xent_forward: z [M][N], target [M] host (-1: the row counts nothing) -> (loss [B], lse [M])"""
+    M, N = z.shape
+    B = int(B if B is not None else max(row_utt) + 1)
+    L = _lib.lib()
+    lse, loss = torch.empty(M, device=z.device, dtype=torch.float32), torch.empty(B, device=z.device, dtype=torch.float32)
+    nbytes = L.w2l_s2s_xent_workspace_size(M, B)
+    ws = _ws(nbytes, z.device)
+    check(L.w2l_s2s_xent_forward(M, N, B, _p(z), target.ctypes.data, None if row_utt is None else row_utt.ctypes.data, eps, _p(lse), _p(loss),
+                                 _p(ws), nbytes, _s()), "s2s_xent_forward")
+    return loss, lse
+
+
+def s2s_xent_backward(z, lse, target, eps, g, row_utt=None, out=None):
+    """w2l_s2s_xent_backward -> dz [M][N]; out may be z itself"""
+    M, N = z.shape
+    B = g.numel()
+    L = _lib.lib()
+    dz = torch.empty_like(z) if out is None else out
+    nbytes = L.w2l_s2s_xent_workspace_size(M, B)
+    ws = _ws(nbytes, z.device)
+    check(L.w2l_s2s_xent_backward(M, N, B, _p(z), _p(lse), target.ctypes.data, None if row_utt is None else row_utt.ctypes.data, eps, _p(g),
+                                  _p(dz), _p(ws), nbytes, _s()), "s2s_xent_backward")
+    return dz
+
+
+class _S2sXent(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, target, eps, row_utt, B):
+        z = z.contiguous()
+        loss, lse = s2s_xent_forward(z, target, eps, row_utt, B)
+        ctx.target, ctx.eps, ctx.row_utt = target, eps, row_utt
+        ctx.save_for_backward(z, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        z, lse = ctx.saved_tensors
+        return s2s_xent_backward(z, lse, ctx.target, ctx.eps, g.contiguous(), ctx.row_utt), None, None, None, None
+
+
+def s2s_cross_entropy(z, target, eps=0.0, row_utt=None, B=None):
+    """label-smoothed cross entropy summed per utterance (w2l_s2s_xent_*): z [M][N] float32, target [M] integers with
+    -1 for a row that counts nothing, row_utt [M] the utterance of every row, non-decreasing (None: M / B rows each) -> loss [B]"""
+    if z.dim() != 2 or z.dtype != torch.float32:
+        raise _lib.W2LInvalidArgument("s2s_cross_entropy: z must be float32 [M][N]")
+    target = _host_i32(target).reshape(-1)
+    row_utt = None if row_utt is None else _host_i32(row_utt).reshape(-1)
+    if target.shape[0] != z.shape[0] or (row_utt is not None and row_utt.shape != target.shape) or (row_utt is None and B is None):
+        raise _lib.W2LInvalidArgument("s2s_cross_entropy: one target (and one row_utt, or B) per row of z")
+    return _S2sXent.apply(z, target, float(eps), row_utt, B)
+
+
+def embedding_forward(tokens, E, start):
+    M, (N, H), L = tokens.shape[0], E.shape, _lib.lib()
+    x = torch.empty(M, H, device=E.device, dtype=torch.float32)
+    nbytes = L.w2l_embedding_workspace_size(M, N)
+    ws = _ws(nbytes, E.device)
+    check(L.w2l_embedding_forward(M, N, H, tokens.ctypes.data, _p(E), _p(start), _p(x), _p(ws), nbytes, _s()), "embedding_forward")
+    return x
+
+
+def embedding_backward(tokens, dx, N):
+    """-> (dE [N][H], dstart [H]): position order inside every row, rows nobody holds are zero; no atomics"""
+    (M, H), L = dx.shape, _lib.lib()
+    dE, ds = torch.empty(N, H, device=dx.device, dtype=torch.float32), torch.empty(H, device=dx.device, dtype=torch.float32)
+    nbytes = L.w2l_embedding_workspace_size(M, N)
+    ws = _ws(nbytes, dx.device)
+    check(L.w2l_embedding_backward(M, N, H, tokens.ctypes.data, _p(dx), _p(dE), _p(ds), _p(ws), nbytes, _s()), "embedding_backward")
+    return dE, ds
+
+
+class _Embedding(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, E, start, tokens):
+        ctx.tokens, ctx.N = tokens, E.shape[0]
+        return embedding_forward(tokens, E.contiguous(), start.contiguous())
+
+    @staticmethod
+    def backward(ctx, dx):
+        dE, ds = embedding_backward(ctx.tokens, dx.contiguous(), ctx.N)
+        return dE, ds, None
+
+
+def embedding(tokens, E, start):
+    """token embedding (w2l_embedding_*): tokens, any shape of integers on the host, -1 = the start embedding ->
+    x [*tokens.shape][H] = E[token] or start.  Differentiable in E [N][H] and start [H]."""
+    if E.dim() != 2 or start.dim() != 1 or start.shape[0] != E.shape[1] or E.dtype != torch.float32 or start.dtype != torch.float32:
+        raise _lib.W2LInvalidArgument("embedding: E [N][H] and start [H] float32")
+    tokens = _host_i32(tokens)
+    return _Embedding.apply(E, start, tokens.reshape(-1)).view(*tokens.shape, E.shape[1])
 
 
 def _ln_scratch(groups, inner):
