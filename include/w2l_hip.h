@@ -850,6 +850,42 @@ int w2l_embedding_forward(int M, int N, int H, const int* tokens, const float* E
                           size_t workspaceBytes, w2l_stream_t stream);
 int w2l_embedding_backward(int M, int N, int H, const int* tokens, const float* dx, float* dE, float* dstart, void* workspace,
                            size_t workspaceBytes, w2l_stream_t stream);
+/* Decoding a seq2seq model (criterion_s2s_decode.hip, DESIGN 3.35 is the contract): a token beam search over the step-by-step decoder
+ * of the model of DESIGN 3.34 -- embedding E [N][H], start embedding [H], the GRU's flat parameter (w2l_rnn_*, one layer, I = H), the
+ * output Linear W [H][N] and bias [N]; keys and values k, v [B][T][ldenc] with H columns used, keyLen [B] a HOST array (both
+ * calls have copied their host arrays when they return: the caller may free or change them at once).  fp32, no window.  Rows are r = b beam + j.  One step is five launches in stream order (cell, attention, vocabulary, merge, prune); no grid
+ * barrier, no atomics; two calls give the same bits and an utterance's result does not depend on B.
+ * w2l_s2s_decode: beam 1 is greedy decoding.  Results, all DEVICE arrays: tokens [B][nbest][maxLen] (eos included when reached,
+ *   then -1), lengths [B][nbest], scores [B][nbest]; a hypothesis that does not exist has length 0, score -inf and tokens -1.
+ * w2l_s2s_decode_step: the cell, attention, vocabulary and merge kernels for given rows.  parent [B beam] and token [B beam] are HOST
+ *   arrays: parent[r] < 0 is a dead row (nothing of it is written), else the slot 0..beam-1 of utterance b whose row of hPrev
+ *   [B beam][H] is the previous state; token[r] == -1 is the start embedding with a zero state (hPrev is not read).  Writes h, o
+ *   [B beam][H], peak [B beam] (the first argmax of the attention), lse [B beam] (of z = (o W + bias) / temperature) and the
+ *   min(beamToken, N) largest z of every row, descending, lower token first among equals: candVal, candTok [B beam][beamToken].
+ * W2L_EINVAL: null pointers, sizes below 1, ldenc < H, eos outside 0..N-1, nbest outside 1..beam, temperature not above 0, a negative
+ *   or NaN threshold, a keyLen outside 1..T, a parent >= beam, a token outside -1..N-1, unaligned E / start / rnn / hPrev, a small
+ *   workspace.  W2L_EUNSUPPORTED: lmWeight != 0 (LM fusion is not built), beam above 128, beamToken above 64, maxLen above 512, H not a
+ *   multiple of 32 or above 1024, T above 1024, B above 1024, N above 65536. */
+typedef struct {
+  int B, T, H, N;
+  int ldenc;                /* floats between two frames of k, v */
+  int eos;
+  int beam, beamToken;      /* hypotheses kept per utterance; tokens every hypothesis proposes */
+  int maxLen, nbest;
+  float threshold;          /* candidates further than this below the step's best are dropped; INFINITY: none */
+  float eosScore;           /* added to a candidate that ends in eos */
+  float temperature;
+  int attentionThreshold;   /* a hypothesis whose attention peak moved further than this from its parent's proposes nothing; < 0: off */
+  float lmWeight;           /* must be 0 */
+} w2l_s2s_decode_desc;
+size_t w2l_s2s_decode_workspace_size(const w2l_s2s_decode_desc* d);
+int w2l_s2s_decode(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W, const float* bias,
+                   const float* k, const float* v, const int* keyLen, int* tokens, int* lengths, float* scores, void* workspace,
+                   size_t workspaceBytes, w2l_stream_t stream);
+int w2l_s2s_decode_step(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W,
+                        const float* bias, const float* k, const float* v, const int* keyLen, const int* parent, const int* token,
+                        const float* hPrev, float* h, float* o, int* peak, float* lse, float* candVal, int* candTok, void* workspace,
+                        size_t workspaceBytes, w2l_stream_t stream);
 /* The kw x 1 convolutions over the mel rows of the TDS recipes in the mixed-precision mode (bf16 operand storage, see
  * w2l_gemm_bf16) -- fl::TDSBlock's time convolution (C -> C channels, stride 1) and the sub-sampling `C2 cin cout kw 1 s 1`
  * lines between the blocks (cin != cout <= 32 channels, stride 1 or 2, any padding): x / dy and the weights rounded to bf16,

@@ -245,6 +245,9 @@ class _SIGS:
     w2l_embedding_workspace_size = (_sz, [_i, _i])
     w2l_embedding_forward = (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _sz, _p])
     w2l_embedding_backward = (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _sz, _p])
+    w2l_s2s_decode_workspace_size = (_sz, [_p])
+    w2l_s2s_decode = (_i, [_p] * 13 + [_sz, _p])
+    w2l_s2s_decode_step = (_i, [_p] * 19 + [_sz, _p])
     w2l_swish_forward = (_i, [_p, _p, _sz, _f, _p])
     w2l_swish_backward = (_i, [_p, _p, _p, _sz, _f, _p])
     w2l_layernorm_scratch_doubles = (_sz, [_i, _sz])
@@ -367,6 +370,11 @@ class RnnDesc(C.Structure):  # w2l_rnn_desc; mode: 0 ReLU, 1 tanh, 2 LSTM, 3 GRU
 
 class S2sAttnDesc(C.Structure):  # w2l_s2s_attn_desc
     _fields_ = [(n, C.c_int) for n in ("B", "U", "T", "H", "ldenc")] + [("windowStd", C.c_float), ("addQuery", C.c_int)]
+
+
+class S2sDecodeDesc(C.Structure):  # w2l_s2s_decode_desc
+    _fields_ = ([(n, C.c_int) for n in ("B", "T", "H", "N", "ldenc", "eos", "beam", "beamToken", "maxLen", "nbest")] +
+                [(n, C.c_float) for n in ("threshold", "eosScore", "temperature")] + [("attentionThreshold", C.c_int), ("lmWeight", C.c_float)])
 
 
 class GemmEpilogue(C.Structure):  # w2l_gemm_epilogue

@@ -351,6 +351,71 @@ def embedding(tokens, E, start):
     return _Embedding.apply(E, start, tokens.reshape(-1)).view(*tokens.shape, E.shape[1])
 
 
+def _s2s_decode_operands(who, params, enc, key_len, keyvalue, beam, beam_token, max_len, nbest, eos, threshold, eos_score, attention_threshold,
+                         temperature):
+    """the checks that need no device, the descriptor and the operand pointers of the two decode calls"""
+    E, start, rnn_p, W, bias = (t.contiguous() for t in params)
+    if enc.dim() != 3 or E.dim() != 2 or any(t.dtype != torch.float32 for t in (enc, E, start, rnn_p, W, bias)):
+        raise _lib.W2LInvalidArgument(f"{who}: enc [B][T][C], the embedding [N][H] and the other parameters must be float32")
+    enc = enc.contiguous()
+    (B, T, Cc), (N, H) = enc.shape, E.shape
+    if Cc != (2 * H if keyvalue else H):
+        raise _lib.W2LInvalidArgument(f"{who}: enc must have {'2 H' if keyvalue else 'H'} = {2 * H if keyvalue else H} columns, got {Cc}")
+    if start.shape != (H,) or rnn_p.shape != (3 * H * (2 * H + 2),) or W.shape != (H, N) or bias.shape != (N,):
+        raise _lib.W2LInvalidArgument(f"{who}: parameters must be E [N][H], start [H], the GRU's 3 H (2 H + 2) floats, W [H][N], bias [N]")
+    kl = np.full(B, T, np.int32) if key_len is None else _host_i32(key_len)
+    if kl.shape != (B,):
+        raise _lib.W2LInvalidArgument(f"{who}: key_len must hold B lengths")
+    d = _lib.S2sDecodeDesc(B, T, H, N, Cc, int(eos), int(beam), int(beam_token), int(max_len), int(nbest),
+                           float("inf") if threshold is None else float(threshold), float(eos_score), float(temperature),
+                           -1 if attention_threshold is None else int(attention_threshold), 0.0)
+    k = enc.data_ptr()
+    return d, kl, (E, start, rnn_p, W, bias, enc), [_p(E), _p(start), _p(rnn_p), _p(W), _p(bias), k, k + 4 * H * int(keyvalue), kl.ctypes.data]
+
+
+def s2s_decode(params, enc, key_len=None, keyvalue=False, *, eos, beam=1, beam_token=None, threshold=None, eos_score=0.0,
+               attention_threshold=None, temperature=1.0, max_len=120, nbest=1):
+    """token beam search over the step-by-step decoder of a seq2seq model (w2l_s2s_decode).  params: the embedding
+    [N][H], the start embedding [H], the GRU's flat parameter, the output weight [H][N] and bias [N]; enc [B][T][C] as
+    ops.s2s_attention, key_len [B] on the host (None: T).  beam_token None: min(N, 64).  threshold None: no beam threshold;
+    attention_threshold None: off.  -> (tokens [B][nbest][max_len] int32, -1 behind the end; lengths [B][nbest]; scores
+    [B][nbest]) on the device; a hypothesis that does not exist has length 0 and score -inf.  beam 1 is greedy decoding."""
+    beam_token = min(params[0].shape[0], 64) if beam_token is None else beam_token
+    d, kl, keep, ptrs = _s2s_decode_operands("s2s_decode", params, enc, key_len, keyvalue, beam, beam_token, max_len, nbest, eos, threshold,
+                                             eos_score, attention_threshold, temperature)
+    L, dev = _lib.lib(), enc.device
+    nbytes = L.w2l_s2s_decode_workspace_size(C.byref(d))
+    ws = _ws(nbytes, dev)
+    tokens = torch.empty(d.B, max(d.nbest, 1), max(d.maxLen, 1), device=dev, dtype=torch.int32)
+    lengths = torch.empty(d.B, max(d.nbest, 1), device=dev, dtype=torch.int32)
+    scores = torch.empty(d.B, max(d.nbest, 1), device=dev, dtype=torch.float32)
+    check(L.w2l_s2s_decode(C.byref(d), *ptrs, _p(tokens), _p(lengths), _p(scores), _p(ws), nbytes, _s()), "s2s_decode")
+    return tokens, lengths, scores
+
+
+def s2s_decode_step(params, enc, parent, token, h_prev, key_len=None, keyvalue=False, *, beam, beam_token, temperature=1.0):
+    """one decoder step for B x beam given rows (w2l_s2s_decode_step): parent, token [B][beam] on the host -- parent < 0
+    is a dead row, of which nothing is written; else the slot of the same utterance whose row of h_prev [B][beam][H] is the previous
+    state; token -1 is the start embedding with a zero state -> h, o [B][beam][H], peak [B][beam] (the first argmax of the
+    attention), lse [B][beam] of z = (o W + bias) / temperature, and the min(beam_token, N) largest z of every row with their tokens,
+    descending: cand_val, cand_tok [B][beam][beam_token]"""
+    d, kl, keep, ptrs = _s2s_decode_operands("s2s_decode_step", params, enc, key_len, keyvalue, beam, beam_token, 1, 1, 0, None, 0.0, None,
+                                             temperature)
+    parent, token = _host_i32(parent), _host_i32(token)
+    h_prev = None if h_prev is None else h_prev.contiguous()
+    if parent.shape != (d.B, beam) or token.shape != parent.shape or (h_prev is not None and (h_prev.shape != (d.B, beam, d.H) or h_prev.dtype != torch.float32)):
+        raise _lib.W2LInvalidArgument("s2s_decode_step: parent and token [B][beam] integers, h_prev [B][beam][H] float32")
+    L, dev = _lib.lib(), enc.device
+    nbytes = L.w2l_s2s_decode_workspace_size(C.byref(d))
+    ws = _ws(nbytes, dev)
+    f = lambda *s: torch.zeros(d.B, beam, *s, device=dev, dtype=torch.float32)
+    i = lambda *s: torch.zeros(d.B, beam, *s, device=dev, dtype=torch.int32)
+    h, o, peak, lse, cv, ct = f(d.H), f(d.H), i(), f(), f(beam_token), i(beam_token)
+    check(L.w2l_s2s_decode_step(C.byref(d), *ptrs, parent.ctypes.data, token.ctypes.data, _p(h_prev), _p(h), _p(o), _p(peak), _p(lse), _p(cv), _p(ct),
+                                _p(ws), nbytes, _s()), "s2s_decode_step")
+    return h, o, peak, lse, cv, ct
+
+
 def _ln_scratch(groups, inner):
     return int(_lib.lib().w2l_layernorm_scratch_doubles(groups, inner))
 

@@ -46,7 +46,7 @@ class Seq2SeqCriterion(SequenceCriterion):
     enc) and 2 hiddenDim for "keyvalue" (keys, then values).  Parameters in the reference's order: the embedding [nClass][hiddenDim],
     the GRU (one flat parameter, include/w2l_hip.h), the output Linear [hiddenDim][nClass] and its bias, the start embedding
     [hiddenDim].  Not built, and refused by name: input feeding, model / gumbel sampling, more than one attention round or RNN layer,
-    the other attention and window kinds.  The step-by-step decoder and beam search are not part of this class."""
+    the other attention and window kinds.  beamSearch and viterbiPath decode the trained model."""
 
     def __init__(self, nClass, hiddenDim, eos, attention="content", window=None, trainWithWindow=False, pctTeacherForcing=100,
                  labelSmooth=0.0, inputFeeding=False, samplingStrategy="rand", nAttnRound=1, nRnnLayer=1):
@@ -121,6 +121,43 @@ class Seq2SeqCriterion(SequenceCriterion):
         z = _Linear.apply(o.view(B * U, H), self.linear_weight, self.linear_bias)
         loss = ops.s2s_cross_entropy(z, np.where(valid, y, -1).reshape(-1), self.labelSmooth if self.training else 0.0, B=B)
         return loss, alpha
+
+    def _key_len(self, enc, inputSizes):
+        B, T, _ = enc.shape
+        if inputSizes is None:
+            return np.full(B, T, np.int32)
+        sz = np.asarray(inputSizes.detach().cpu() if torch.is_tensor(inputSizes) else inputSizes, dtype=np.float64).reshape(-1)
+        if sz.shape != (B,) or not (sz > 0).all():
+            raise _lib.W2LInvalidArgument("Seq2SeqCriterion: inputSizes must hold B positive sizes")
+        return np.ceil(sz / sz.max() * T).astype(np.int32).clip(1, T)
+
+    @torch.no_grad()
+    def beamSearch(self, enc, inputSizes=None, beam=1, beam_token=None, threshold=None, eos_score=0.0, attention_threshold=None,
+                   temperature=1.0, max_len=120, nbest=1, **refused):
+        """token beam search over the step-by-step decoder (ops.s2s_decode; the reference's LexiconFreeSeq2SeqDecoder with a zero LM,
+        DESIGN.md 3.35) -> (tokens [B][nbest][max_len], -1 behind the end and eos included when reached; lengths [B][nbest]; scores
+        [B][nbest]).  beam_token None: min(nClass, 64); threshold None: no beam threshold; attention_threshold None: off.  The
+        decoder applies NO window: the recipe's softPretrain window is a pre-training device, and its centre u keyLen / tgtLen has no
+        meaning without a target.  Refused by name: LM fusion, hard and soft selection."""
+        refuse = _lib.W2LInvalidArgument
+        names = {"lm_weight": "LM fusion (lm_weight) is not built", "lmweight": "LM fusion (lmweight) is not built",
+                 "hardselection": "hardselection is not built", "softselection": "softselection is not built",
+                 "hard_selection": "hardselection is not built", "soft_selection": "softselection is not built"}
+        for k, v in refused.items():
+            if k not in names:
+                raise TypeError(f"Seq2SeqCriterion.beamSearch: unknown option '{k}'")
+            if k in ("lm_weight", "lmweight") and not v:
+                continue
+            raise refuse(f"Seq2SeqCriterion.beamSearch: {names[k]}")
+        _check_dev(enc)
+        params = [p.detach() for p in (self.embedding, self.start, self.rnn, self.linear_weight, self.linear_bias)]
+        return ops.s2s_decode(params, enc, self._key_len(enc, inputSizes), self.attention == "keyvalue", eos=self.eos, beam=beam,
+                              beam_token=beam_token, threshold=threshold, eos_score=eos_score, attention_threshold=attention_threshold,
+                              temperature=temperature, max_len=max_len, nbest=nbest)
+
+    def viterbiPath(self, enc, inputSizes=None, max_len=120):
+        """greedy step-by-step decoding, the beam-1 case of beamSearch -> tokens [B][max_len] int32, -1 behind the end"""
+        return self.beamSearch(enc, inputSizes, beam=1, beam_token=1, max_len=max_len)[0][:, 0]
 
     def prettyString(self):
         return f"Seq2SeqCriterion(nClass={self.nClass}, hiddenDim={self.hiddenDim}, attention={self.attention})"
