@@ -864,7 +864,7 @@ int w2l_embedding_backward(int M, int N, int H, const int* tokens, const float* 
  *   min(beamToken, N) largest z of every row, descending, lower token first among equals: candVal, candTok [B beam][beamToken].
  * W2L_EINVAL: null pointers, sizes below 1, ldenc < H, eos outside 0..N-1, nbest outside 1..beam, temperature not above 0, a negative
  *   or NaN threshold, a keyLen outside 1..T, a parent >= beam, a token outside -1..N-1, unaligned E / start / rnn / hPrev, a small
- *   workspace.  W2L_EUNSUPPORTED: lmWeight != 0 (LM fusion is not built), beam above 128, beamToken above 64, maxLen above 512, H not a
+ *   workspace.  W2L_EUNSUPPORTED: lmWeight != 0 (LM fusion is w2l_s2s_decode_lm's), beam above 128, beamToken above 64, maxLen above 512, H not a
  *   multiple of 32 or above 1024, T above 1024, B above 1024, N above 65536. */
 typedef struct {
   int B, T, H, N;
@@ -876,7 +876,7 @@ typedef struct {
   float eosScore;           /* added to a candidate that ends in eos */
   float temperature;
   int attentionThreshold;   /* a hypothesis whose attention peak moved further than this from its parent's proposes nothing; < 0: off */
-  float lmWeight;           /* must be 0 */
+  float lmWeight;           /* must be 0 in w2l_s2s_decode and w2l_s2s_decode_step; w2l_s2s_decode_lm honours it */
 } w2l_s2s_decode_desc;
 size_t w2l_s2s_decode_workspace_size(const w2l_s2s_decode_desc* d);
 int w2l_s2s_decode(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W, const float* bias,
@@ -886,6 +886,25 @@ int w2l_s2s_decode_step(const w2l_s2s_decode_desc* d, const float* E, const floa
                         const float* bias, const float* k, const float* v, const int* keyLen, const int* parent, const int* token,
                         const float* hPrev, float* h, float* o, int* peak, float* lse, float* candVal, int* candTok, void* workspace,
                         size_t workspaceBytes, w2l_stream_t stream);
+/* w2l_s2s_decode fused with an n-gram LM over the token classes (DESIGN 3.36 is the contract; the reference's
+ * LexiconFreeSeq2SeqDecoder with a non-zero LM weight).  lm: a w2l_ngram_lm_* blob built for numTokens = N (word c is class c), DEVICE
+ * memory, not checked: every loop over it is bounded by ngram_q.  The contract is w2l_s2s_decode's with these changes:
+ *   LM state.  Every hypothesis carries an LM state; the root has the blob's start state.  The eos class is never looked up as a word.
+ *   Candidates.  A hypothesis proposes its min(beamToken, N) best tokens by the acoustic lp alone.  For n != eos the candidate's score is
+ *     (score_p + lp[n]) + lmWeight * q(state_p, n): one fp32 multiply, then one fp32 add behind the acoustic add; the child's state is
+ *     q's next state.  For n == eos it is ((score_p + lp[eos]) + eosScore) + lmWeight * q(state_p, EOS) when lmHasEos != 0 (what
+ *     w2l_ngram_lm_info says of the blob), and has no LM term otherwise.  lmWeight == 0 gives w2l_s2s_decode's bits.
+ *   Threshold, order, pool, end rule and attention threshold act on these scores.  Nothing is merged: two hypotheses never share a
+ *     token history.
+ *   lmScores [B][nbest]: the unweighted q terms of a hypothesis added in token order in fp32 (0 + q1 + q2 ..., the EOS term last); -inf
+ *     for a hypothesis that does not exist.
+ * The step stays five launches (the merge also looks the row's tokens up, a lane each; the prune carries state and LM score); no
+ * atomics; two calls give the same bits.  Refusals: w2l_s2s_decode's (its limits included) except lmWeight != 0, and W2L_EINVAL for
+ * lm or lmScores NULL, lmWeight or eosScore not finite, lmHasEos outside 0 / 1; all before the first launch. */
+size_t w2l_s2s_decode_lm_workspace_size(const w2l_s2s_decode_desc* d);
+int w2l_s2s_decode_lm(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W,
+                      const float* bias, const float* k, const float* v, const int* keyLen, int* tokens, int* lengths, float* scores,
+                      float* lmScores, void* workspace, size_t workspaceBytes, w2l_stream_t stream, const void* lm, int lmHasEos);
 /* The kw x 1 convolutions over the mel rows of the TDS recipes in the mixed-precision mode (bf16 operand storage, see
  * w2l_gemm_bf16) -- fl::TDSBlock's time convolution (C -> C channels, stride 1) and the sub-sampling `C2 cin cout kw 1 s 1`
  * lines between the blocks (cin != cout <= 32 channels, stride 1 or 2, any padding): x / dy and the weights rounded to bf16,

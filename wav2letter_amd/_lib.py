@@ -248,6 +248,8 @@ class _SIGS:
     w2l_s2s_decode_workspace_size = (_sz, [_p])
     w2l_s2s_decode = (_i, [_p] * 13 + [_sz, _p])
     w2l_s2s_decode_step = (_i, [_p] * 19 + [_sz, _p])
+    w2l_s2s_decode_lm_workspace_size = (_sz, [_p])
+    w2l_s2s_decode_lm = (_i, [_p] * 14 + [_sz, _p, _p, _i])
     w2l_swish_forward = (_i, [_p, _p, _sz, _f, _p])
     w2l_swish_backward = (_i, [_p, _p, _p, _sz, _f, _p])
     w2l_layernorm_scratch_doubles = (_sz, [_i, _sz])

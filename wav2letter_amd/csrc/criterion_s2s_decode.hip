@@ -25,10 +25,19 @@
 // A tile whose rows are all dead returns at once.  A row's bits depend on its own operands only: every sum has one order and no tile
 // mixes rows, so two calls agree bit for bit and an utterance decodes the same alone or in a batch.  The host launches steps back to
 // back and reads one count of unfinished utterances every 8 steps.  A last launch ranks the results and walks the back-pointers.
+//
+// LM fusion: merge, prune and the last launch have a second instantiation, kLm.  Every row carries the
+// n-gram state of its hypothesis and its running unweighted LM score.  The merge wave, once its row's tokens are popped, has lane k look
+// up q(state, token k) -- R waves of min(beamToken, N) hash walks each, spread over the chip -- and writes (q, next state) beside the
+// candidate; the prune packs the candidate's place in its row into the sort value, adds lmWeight q after the acoustic adds, and writes
+// the child's state and LM score into the next level and, for finished hypotheses, into the pool.  The LM-free kernels are the
+// kLm = false instantiations with an empty argument pack: their arguments and their instructions do not change.
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <vector>
 
+#include "ngram_lm.hpp"
 #include "s2s_attn.hpp"
 
 namespace w2l {
@@ -64,6 +73,24 @@ struct DecPrune {
   int B, beam, bt, ldc, eos, u, attThr, n2max;
   float threshold, eosScore;
 };
+
+// what the kLm instantiations take beside DecStep / DecPrune: the blob (device memory, read through ngram_view / ngram_q only), the two
+// levels' LM columns, a step's (q, next state) per candidate, the pool's LM scores
+struct DecLmTable { int* state; float* lmScore; };
+struct DecLm {
+  const void* blob;
+  DecLmTable cur, nxt;
+  float *candLm, *poolLm;
+  int* candNext;
+  float weight;
+  int hasEos, eos, eosWord;
+};
+struct DecLmOut { const float *poolLm, *lm0, *lm1; float* lmScores; };
+// merge, prune and the last launch are templates <kLm, Lm...>: the LM-free instantiation has an empty pack, so its arguments and its
+// instructions are what they were; the kLm one takes one more argument (DecLm, or DecLmOut in the last launch)
+struct DecNoLm {};
+__device__ __forceinline__ DecNoLm dec_lm_arg() { return DecNoLm{}; }
+template <class T> __device__ __forceinline__ T dec_lm_arg(const T& x) { return x; }
 
 __device__ __forceinline__ float dec_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ int wave_min_int(int v) {
@@ -278,7 +305,9 @@ __global__ __launch_bounds__(kDecThreads) void s2s_dec_vocab_k(DecStep a) {
 }
 
 // ---- 3b. a row's slabs into its lse and its best tokens ------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void s2s_dec_merge_k(DecStep a) {
+template <bool kLm, class... Lm>
+__global__ __launch_bounds__(64) void s2s_dec_merge_k(DecStep a, Lm... lmArg) {
+  [[maybe_unused]] const auto lm = dec_lm_arg(lmArg...);
   __shared__ float sv[kDecMergeLds];
   const int r = blockIdx.x, lane = threadIdx.x, nSlab = a.nSlab, kk = a.kk, n = nSlab * kk;
   if (a.src[r] < 0) return;
@@ -309,6 +338,7 @@ __global__ __launch_bounds__(64) void s2s_dec_merge_k(DecStep a) {
   }
   float* cv = a.candVal + (size_t)r * a.ldc;
   int* ct = a.candTok + (size_t)r * a.ldc;
+  [[maybe_unused]] int myTok = -1;   // kLm: lane i keeps the i-th token
   for (int i = 0; i < a.bt; ++i) {
     float best = -INFINITY;
     int bq = 0;
@@ -331,6 +361,11 @@ __global__ __launch_bounds__(64) void s2s_dec_merge_k(DecStep a) {
       const int low = wave_min_int(tok);
       who = __ballot(tied && tok == low);
     }
+    if constexpr (kLm) {
+      const int win = __ffsll((long long)who) - 1;
+      const int t = __shfl(lane == win ? gt[head + p] : -1, win);
+      if (lane == i) myTok = t;
+    }
     if (lane == __ffsll((long long)who) - 1) {
       cv[i] = top;
       ct[i] = gt[head + p];
@@ -341,10 +376,25 @@ __global__ __launch_bounds__(64) void s2s_dec_merge_k(DecStep a) {
     }
   }
   for (int i = a.bt + lane; i < a.ldc; i += 64) { cv[i] = -INFINITY; ct[i] = -1; }
+  if constexpr (kLm) {   // lane k scores the k-th token in the row's LM state; eos is the LM's EOS word, or nothing in a model without one
+    const NgramView v = ngram_view(lm.blob);
+    if (lane < a.bt) {
+      const bool isEos = myTok == lm.eos;
+      float q = 0.f;
+      int next = 0;
+      if (myTok >= 0 && (!isEos || lm.hasEos)) q = ngram_q(v, lm.cur.state[r], isEos ? lm.eosWord : myTok, &next);
+      lm.candLm[(size_t)r * a.ldc + lane] = q;
+      lm.candNext[(size_t)r * a.ldc + lane] = next;
+    }
+  }
 }
 
 // ---- 4. the next beam level of an utterance ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kDecThreads) void s2s_dec_prune_k(DecPrune a) {
+// kLm: the sort value is (parent slot << 22) | (token << 6) | the candidate's place in its row -- the same order, since a row holds a
+// token once -- and pLm [kDecPool] stands behind flag
+template <bool kLm, class... Lm>
+__global__ __launch_bounds__(kDecThreads) void s2s_dec_prune_k(DecPrune a, Lm... lmArg) {
+  [[maybe_unused]] const auto lm = dec_lm_arg(lmArg...);
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* key = lds;
   int* val = reinterpret_cast<int*>(lds + a.n2max);
@@ -352,6 +402,7 @@ __global__ __launch_bounds__(kDecThreads) void s2s_dec_prune_k(DecPrune a) {
   int* pVal = reinterpret_cast<int*>(pKey + kDecPool);
   int* pRef = pVal + kDecPool;
   int* flag = pRef + kDecPool;   // [kDecMaxBeam]
+  [[maybe_unused]] float* pLm = reinterpret_cast<float*>(flag + kDecMaxBeam);
   const int b = blockIdx.x, tid = threadIdx.x, beam = a.beam, base = b * beam;
   if (a.done[b]) return;
   const int n = a.cur.nSlots[b], nLive = a.cur.nLive[b], nEos = n - nLive;
@@ -364,11 +415,14 @@ __global__ __launch_bounds__(kDecThreads) void s2s_dec_prune_k(DecPrune a) {
       if (tid < pc) { s = a.poolScore[(size_t)b * cap + tid]; ref = a.poolRef[(size_t)b * cap + tid]; }
       else if (tid < all) { const int j = nLive + tid - pc; s = a.cur.score[base + j]; ref = (a.u << 8) | j; }
       pKey[tid] = s; pRef[tid] = ref; pVal[tid] = tid < all ? tid : INT_MAX;
+      if constexpr (kLm) pLm[tid] = tid < pc ? lm.poolLm[(size_t)b * cap + tid] : tid < all ? lm.cur.lmScore[base + nLive + tid - pc] : 0.f;
     }
     __syncthreads();
     if (all >= beam) dec_sort(pKey, pVal, kDecPool);   // the best `beam`; among equals the earlier entry
     const int keep = min(all, beam);
     if (tid < keep) { a.poolScore[(size_t)b * cap + tid] = pKey[tid]; a.poolRef[(size_t)b * cap + tid] = pRef[min(pVal[tid], kDecPool - 1)]; }
+    if constexpr (kLm)
+      if (tid < keep) lm.poolLm[(size_t)b * cap + tid] = pLm[min(pVal[tid], kDecPool - 1)];
     if (tid == 0) a.poolCount[b] = keep;
   }
   if (nLive == 0) {   // nobody proposes: this utterance's search is over; its last levels stay as they are
@@ -389,6 +443,10 @@ __global__ __launch_bounds__(kDecThreads) void s2s_dec_prune_k(DecPrune a) {
         s = a.cur.score[r] + (a.candVal[(size_t)r * a.ldc + c] - a.lse[r]);
         if (tok == a.eos) s += a.eosScore;
         v = (j << 16) | tok;
+        if constexpr (kLm) {
+          if (tok != a.eos || lm.hasEos) s = s + lm.weight * lm.candLm[(size_t)r * a.ldc + c];
+          v = (j << 22) | (tok << 6) | c;
+        }
       }
     }
     key[i] = s; val[i] = v;
@@ -396,7 +454,7 @@ __global__ __launch_bounds__(kDecThreads) void s2s_dec_prune_k(DecPrune a) {
   dec_sort(key, val, n2);
   const float best = key[0];
   const bool keep = tid < min(beam, n2) && key[tid] > -INFINITY && key[tid] >= best - a.threshold;
-  const int tok = keep ? (val[tid] & 0xffff) : 0, par = keep ? (val[tid] >> 16) : 0;
+  const int tok = keep ? (kLm ? (val[tid] >> 6) & 0xffff : val[tid] & 0xffff) : 0, par = keep ? (val[tid] >> (kLm ? 22 : 16)) : 0;
   const bool ends = keep && tok == a.eos;
   if (tid < kDecMaxBeam) flag[tid] = keep ? (ends ? 2 : 1) : 0;
   __syncthreads();
@@ -416,6 +474,11 @@ __global__ __launch_bounds__(kDecThreads) void s2s_dec_prune_k(DecPrune a) {
     a.nxt.peakPrev[base + slot] = a.peak[base + par];
     a.trPar[tr] = par;
     a.trTok[tr] = tok;
+    if constexpr (kLm) {   // the child's LM state and its unweighted LM score, one fp32 add per token (q is 0 where no term was added)
+      const size_t at = (size_t)(base + par) * a.ldc + (val[tid] & 63);
+      lm.nxt.state[base + slot] = lm.candNext[at];
+      lm.nxt.lmScore[base + slot] = lm.cur.lmScore[base + par] + lm.candLm[at];
+    }
   }
   for (int j = nNew + tid; j < beam; j += kDecThreads) a.nxt.src[base + j] = -1;
   if (tid == 0) {
@@ -438,6 +501,14 @@ __global__ void s2s_dec_init_k(DecTable t0, DecTable t1, int* poolCount, int* do
   }
 }
 
+// level 0 of the LM columns: the root holds the blob's start state and an LM score of 0
+__global__ void s2s_dec_lm_init_k(const void* blob, DecLmTable t0, int beam, int B) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  t0.state[b * beam] = (int)((const NgramHeader*)blob)->start;
+  t0.lmScore[b * beam] = 0.f;
+}
+
 __global__ __launch_bounds__(kDecThreads) void s2s_dec_count_k(const int* done, int* liveUtts, int B) {
   int c = 0;
   for (int b = threadIdx.x; b < B; b += kDecThreads) c += done[b] == 0;
@@ -446,21 +517,28 @@ __global__ __launch_bounds__(kDecThreads) void s2s_dec_count_k(const int* done, 
 }
 
 // ---- 5. the results: the best nbest of the pool (or of the last level that holds anything), their tokens by the back-pointers ----
+template <bool kLm, class... Lm>
 __global__ __launch_bounds__(kDecThreads) void s2s_dec_trace_k(DecTable t0, DecTable t1, const float* poolScore, const int* poolRef, const int* poolCount,
                                                                const int* lastLevel, const int* trPar, const int* trTok, int* tokens, int* lengths,
-                                                               float* scores, int B, int beam, int maxLen, int nbest) {
+                                                               float* scores, int B, int beam, int maxLen, int nbest, Lm... lmArg) {
+  [[maybe_unused]] const auto lo = dec_lm_arg(lmArg...);
   __shared__ float sc[kDecPool];
   __shared__ int ref[kDecPool];
   const int b = blockIdx.x, tid = threadIdx.x, pc = poolCount[b];
   int cnt;
+  [[maybe_unused]] float lmv = 0.f;   // kLm: the unweighted LM score of this thread's hypothesis
   if (pc > 0) {
     cnt = min(pc, kDecPool);
     if (tid < cnt) { sc[tid] = poolScore[(size_t)b * 2 * beam + tid]; ref[tid] = poolRef[(size_t)b * 2 * beam + tid]; }
+    if constexpr (kLm)
+      if (tid < cnt) lmv = lo.poolLm[(size_t)b * 2 * beam + tid];
   } else {
     const int L = lastLevel[b];
     const DecTable& t = (L & 1) ? t1 : t0;
     cnt = min(t.nSlots[b], beam);
     if (tid < cnt) { sc[tid] = t.score[b * beam + tid]; ref[tid] = (L << 8) | tid; }
+    if constexpr (kLm)
+      if (tid < cnt) lmv = ((L & 1) ? lo.lm1 : lo.lm0)[b * beam + tid];
   }
   __syncthreads();
   if (tid < cnt) {
@@ -471,6 +549,7 @@ __global__ __launch_bounds__(kDecThreads) void s2s_dec_trace_k(DecTable t0, DecT
       const int L = ref[tid] >> 8;
       int j = ref[tid] & 255;
       scores[out] = sc[tid];
+      if constexpr (kLm) lo.lmScores[out] = lmv;
       lengths[out] = L;
       int* row = tokens + out * maxLen;
       for (int l = L; l >= 1; --l) {
@@ -484,17 +563,20 @@ __global__ __launch_bounds__(kDecThreads) void s2s_dec_trace_k(DecTable t0, DecT
   if (tid >= cnt && tid < nbest) {   // fewer hypotheses than asked for
     const size_t out = (size_t)b * nbest + tid;
     scores[out] = -INFINITY;
+    if constexpr (kLm) lo.lmScores[out] = -INFINITY;
     lengths[out] = 0;
     for (int l = 0; l < maxLen; ++l) tokens[out * maxLen + l] = -1;
   }
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
-static int dec_check(const w2l_s2s_decode_desc* d) {
+// lm: the check of w2l_s2s_decode_lm, which honours lmWeight and wants it and eosScore finite
+static int dec_check(const w2l_s2s_decode_desc* d, bool lm = false) {
   if (!d || d->B < 1 || d->T < 1 || d->H < 1 || d->N < 2 || d->ldenc < d->H || d->eos < 0 || d->eos >= d->N || d->beam < 1 || d->beamToken < 1 ||
       d->maxLen < 1 || d->nbest < 1 || d->nbest > d->beam || !(d->temperature > 0.f) || !(d->threshold >= 0.f) || !(d->eosScore == d->eosScore))
     return W2L_EINVAL;
-  if (d->lmWeight != 0.f) return W2L_EUNSUPPORTED;   // LM fusion is not built
+  if (lm && (!std::isfinite(d->lmWeight) || !std::isfinite(d->eosScore))) return W2L_EINVAL;
+  if (!lm && d->lmWeight != 0.f) return W2L_EUNSUPPORTED;   // LM fusion is w2l_s2s_decode_lm's
   if (d->beam > kDecMaxBeam || d->beamToken > kDecMaxBt || d->maxLen > kDecMaxLen || d->H % 32 || d->H > kS2sMaxH || d->T > kS2sMaxT ||
       d->B > kS2sMaxB || d->N > kDecMaxN)
     return W2L_EUNSUPPORTED;
@@ -503,10 +585,10 @@ static int dec_check(const w2l_s2s_decode_desc* d) {
 
 struct DecWs {
   size_t keyLen, tab[2][6], hbuf[2], o, peak, partMS, partVal, partTok, lse, candVal, candTok, poolScore, poolRef, poolCount, done, lastLevel,
-      liveUtts, trPar, trTok, total;
+      liveUtts, trPar, trTok, lmState[2], lmScore[2], candLm, candNext, poolLm, total;
   int R, nSlab, kk, bt, n2max;
 };
-static DecWs dec_ws(const w2l_s2s_decode_desc& d) {
+static DecWs dec_ws(const w2l_s2s_decode_desc& d, bool lm = false) {
   DecWs w{};
   w.R = d.B * d.beam;
   w.nSlab = (d.N + kDecSlab - 1) / kDecSlab;
@@ -527,6 +609,10 @@ static DecWs dec_ws(const w2l_s2s_decode_desc& d) {
   w.lse = take(R); w.candVal = take(R * d.beamToken); w.candTok = take(R * d.beamToken);
   w.poolScore = take(2 * R); w.poolRef = take(2 * R); w.poolCount = take(B); w.done = take(B); w.lastLevel = take(B); w.liveUtts = take(1);
   w.trPar = take((size_t)d.maxLen * R); w.trTok = take((size_t)d.maxLen * R);
+  if (lm) {   // behind everything else: the LM-free layout is a prefix of this one
+    for (int s = 0; s < 2; ++s) { w.lmState[s] = take(R); w.lmScore[s] = take(R); }
+    w.candLm = take(R * d.beamToken); w.candNext = take(R * d.beamToken); w.poolLm = take(2 * R);
+  }
   w.total = at;
   return w;
 }
@@ -551,8 +637,8 @@ static DecStep dec_step_args(const w2l_s2s_decode_desc& d, const DecWs& w, char*
   return a;
 }
 
-// the cell, attention, vocabulary and merge launches of one step
-static int dec_launch_step(const DecStep& a, hipStream_t s) {
+// the cell, attention, vocabulary and merge launches of one step; lm: the merge that also scores its tokens
+static int dec_launch_step(const DecStep& a, hipStream_t s, const DecLm* lm = nullptr) {
   static bool seen[64] = {};
   if (first_on_device(seen))
     W2L_HIP_CHECK(hipFuncSetAttribute((const void*)s2s_dec_attn_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds_bytes(kS2sMaxT)));
@@ -563,17 +649,18 @@ static int dec_launch_step(const DecStep& a, hipStream_t s) {
   W2L_LAUNCH_CHECK();
   s2s_dec_vocab_k<<<dim3(a.nSlab, tiles), kDecThreads, 0, s>>>(a);
   W2L_LAUNCH_CHECK();
-  s2s_dec_merge_k<<<a.R, 64, 0, s>>>(a);
+  if (lm) s2s_dec_merge_k<true><<<a.R, 64, 0, s>>>(a, *lm);
+  else s2s_dec_merge_k<false><<<a.R, 64, 0, s>>>(a);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
 }
 
 static int dec_common_check(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W, const float* bias,
-                            const float* k, const float* v, const int* keyLen, void* workspace, size_t workspaceBytes) {
-  const int st = dec_check(d);
+                            const float* k, const float* v, const int* keyLen, void* workspace, size_t workspaceBytes, bool lm = false) {
+  const int st = dec_check(d, lm);
   if (st != W2L_OK) return st;
   if (!E || !start || !rnn || !W || !bias || !k || !v || !keyLen || !workspace || !s2s_aligned(E, start, rnn, workspace) ||
-      workspaceBytes < dec_ws(*d).total)
+      workspaceBytes < dec_ws(*d, lm).total)
     return W2L_EINVAL;
   for (int b = 0; b < d->B; ++b)
     if (keyLen[b] < 1 || keyLen[b] > d->T) return W2L_EINVAL;
@@ -614,21 +701,24 @@ W2L_API int w2l_s2s_decode_step(const w2l_s2s_decode_desc* d, const float* E, co
   return dec_launch_step(a, s);
 }
 
-W2L_API int w2l_s2s_decode(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W, const float* bias,
-                           const float* k, const float* v, const int* keyLen, int* tokens, int* lengths, float* scores, void* workspace,
-                           size_t workspaceBytes, w2l_stream_t stream) {
-  DEC_OK(dec_common_check(d, E, start, rnn, W, bias, k, v, keyLen, workspace, workspaceBytes));
-  if (!tokens || !lengths || !scores) return W2L_EINVAL;
-  const DecWs w = dec_ws(*d);
-  hipStream_t s = (hipStream_t)stream;
+// the whole search; lm: the blob and lmScores of w2l_s2s_decode_lm, whose merge, prune and last launch are the kLm instantiations
+struct DecLmCall { const void* blob; int hasEos; float* lmScores; };
+
+static int dec_search(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W, const float* bias,
+                      const float* k, const float* v, const int* keyLen, int* tokens, int* lengths, float* scores, void* workspace, hipStream_t s,
+                      const DecLmCall* lm) {
+  const DecWs w = dec_ws(*d, lm != nullptr);
   char* ws = (char*)workspace;
   const DecTable tab[2] = {dec_table(ws, w, 0), dec_table(ws, w, 1)};
   float* hbuf[2] = {(float*)(ws + w.hbuf[0]), (float*)(ws + w.hbuf[1])};
-  const size_t pruneLds = (2 * (size_t)w.n2max + 3 * kDecPool + kDecMaxBeam) * sizeof(float);
+  const size_t pruneLds = (2 * (size_t)w.n2max + (lm ? 4 : 3) * kDecPool + kDecMaxBeam) * sizeof(float);
   static bool seen[64] = {};
-  if (first_on_device(seen))
-    W2L_HIP_CHECK(hipFuncSetAttribute((const void*)s2s_dec_prune_k, hipFuncAttributeMaxDynamicSharedMemorySize,
+  if (first_on_device(seen)) {
+    W2L_HIP_CHECK(hipFuncSetAttribute((const void*)s2s_dec_prune_k<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)((2 * 8192 + 3 * kDecPool + kDecMaxBeam) * sizeof(float))));
+    W2L_HIP_CHECK(hipFuncSetAttribute((const void*)s2s_dec_prune_k<true, DecLm>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)((2 * 8192 + 4 * kDecPool + kDecMaxBeam) * sizeof(float))));
+  }
   W2L_HIP_CHECK(hipMemcpyAsync(ws + w.keyLen, keyLen, (size_t)d->B * sizeof(int), hipMemcpyHostToDevice, s));
   W2L_HIP_CHECK(hipStreamSynchronize(s));   // before any launch: keyLen is the caller's again, as after the step entry
   DecStep a = dec_step_args(*d, w, ws, E, start, rnn, W, bias, k, v);
@@ -640,15 +730,28 @@ W2L_API int w2l_s2s_decode(const w2l_s2s_decode_desc* d, const float* E, const f
   p.done = (int*)(ws + w.done); p.lastLevel = (int*)(ws + w.lastLevel); p.trPar = (int*)(ws + w.trPar); p.trTok = (int*)(ws + w.trTok);
   p.B = d->B; p.beam = d->beam; p.bt = w.bt; p.ldc = d->beamToken; p.eos = d->eos; p.attThr = d->attentionThreshold; p.n2max = w.n2max;
   p.threshold = d->threshold; p.eosScore = d->eosScore;
+  DecLm m{};
+  DecLmTable ltab[2] = {};
+  if (lm) {
+    for (int i = 0; i < 2; ++i) ltab[i] = DecLmTable{(int*)(ws + w.lmState[i]), (float*)(ws + w.lmScore[i])};
+    m.blob = lm->blob; m.candLm = (float*)(ws + w.candLm); m.candNext = (int*)(ws + w.candNext); m.poolLm = (float*)(ws + w.poolLm);
+    m.weight = d->lmWeight; m.hasEos = lm->hasEos; m.eos = d->eos; m.eosWord = d->N + 1;   // the words of a blob for N tokens: N is BOS, N + 1 EOS
+  }
   int* liveUtts = (int*)(ws + w.liveUtts);
   s2s_dec_init_k<<<(w.R + 255) / 256, 256, 0, s>>>(tab[0], tab[1], p.poolCount, p.done, p.lastLevel, d->beam, w.R);
   W2L_LAUNCH_CHECK();
+  if (lm) {
+    s2s_dec_lm_init_k<<<(d->B + 255) / 256, 256, 0, s>>>(m.blob, ltab[0], d->beam, d->B);
+    W2L_LAUNCH_CHECK();
+  }
   for (int u = 0; u < d->maxLen; ++u) {
     const int cur = u & 1;
     a.src = tab[cur].src; a.token = tab[cur].token; a.hPrev = hbuf[cur ^ 1]; a.h = hbuf[cur];
-    DEC_OK(dec_launch_step(a, s));
+    m.cur = ltab[cur]; m.nxt = ltab[cur ^ 1];
+    DEC_OK(dec_launch_step(a, s, lm ? &m : nullptr));
     p.cur = tab[cur]; p.nxt = tab[cur ^ 1]; p.u = u;
-    s2s_dec_prune_k<<<d->B, kDecThreads, pruneLds, s>>>(p);
+    if (lm) s2s_dec_prune_k<true><<<d->B, kDecThreads, pruneLds, s>>>(p, m);
+    else s2s_dec_prune_k<false><<<d->B, kDecThreads, pruneLds, s>>>(p);
     W2L_LAUNCH_CHECK();
     if ((u & 7) == 7 && u + 1 < d->maxLen) {   // is anybody still searching?  one blocking 4-byte copy every 8 steps
       int live = 1;
@@ -659,8 +762,35 @@ W2L_API int w2l_s2s_decode(const w2l_s2s_decode_desc* d, const float* E, const f
       if (!live) break;
     }
   }
-  s2s_dec_trace_k<<<d->B, kDecThreads, 0, s>>>(tab[0], tab[1], p.poolScore, p.poolRef, p.poolCount, p.lastLevel, p.trPar, p.trTok, tokens, lengths,
-                                              scores, d->B, d->beam, d->maxLen, d->nbest);
+  if (lm)
+    s2s_dec_trace_k<true><<<d->B, kDecThreads, 0, s>>>(tab[0], tab[1], p.poolScore, p.poolRef, p.poolCount, p.lastLevel, p.trPar, p.trTok, tokens,
+                                                   lengths, scores, d->B, d->beam, d->maxLen, d->nbest,
+                                                   DecLmOut{m.poolLm, ltab[0].lmScore, ltab[1].lmScore, lm->lmScores});
+  else
+    s2s_dec_trace_k<false><<<d->B, kDecThreads, 0, s>>>(tab[0], tab[1], p.poolScore, p.poolRef, p.poolCount, p.lastLevel, p.trPar, p.trTok, tokens, lengths,
+                                                scores, d->B, d->beam, d->maxLen, d->nbest);
   W2L_LAUNCH_CHECK();
   return W2L_OK;
+}
+
+W2L_API int w2l_s2s_decode(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W, const float* bias,
+                           const float* k, const float* v, const int* keyLen, int* tokens, int* lengths, float* scores, void* workspace,
+                           size_t workspaceBytes, w2l_stream_t stream) {
+  DEC_OK(dec_common_check(d, E, start, rnn, W, bias, k, v, keyLen, workspace, workspaceBytes));
+  if (!tokens || !lengths || !scores) return W2L_EINVAL;
+  return dec_search(d, E, start, rnn, W, bias, k, v, keyLen, tokens, lengths, scores, workspace, (hipStream_t)stream, nullptr);
+}
+
+W2L_API size_t w2l_s2s_decode_lm_workspace_size(const w2l_s2s_decode_desc* d) {
+  if (dec_check(d, true) != W2L_OK) return 0;
+  return dec_ws(*d, true).total;
+}
+
+W2L_API int w2l_s2s_decode_lm(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W, const float* bias,
+                              const float* k, const float* v, const int* keyLen, int* tokens, int* lengths, float* scores, float* lmScores,
+                              void* workspace, size_t workspaceBytes, w2l_stream_t stream, const void* lm, int lmHasEos) {
+  DEC_OK(dec_common_check(d, E, start, rnn, W, bias, k, v, keyLen, workspace, workspaceBytes, true));
+  if (!tokens || !lengths || !scores || !lmScores || !lm || (lmHasEos != 0 && lmHasEos != 1)) return W2L_EINVAL;
+  const DecLmCall call{lm, lmHasEos, lmScores};
+  return dec_search(d, E, start, rnn, W, bias, k, v, keyLen, tokens, lengths, scores, workspace, (hipStream_t)stream, &call);
 }

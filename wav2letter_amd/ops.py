@@ -352,7 +352,7 @@ def embedding(tokens, E, start):
 
 
 def _s2s_decode_operands(who, params, enc, key_len, keyvalue, beam, beam_token, max_len, nbest, eos, threshold, eos_score, attention_threshold,
-                         temperature):
+                         temperature, lm_weight=0.0):
     """the checks that need no device, the descriptor and the operand pointers of the two decode calls"""
     E, start, rnn_p, W, bias = (t.contiguous() for t in params)
     if enc.dim() != 3 or E.dim() != 2 or any(t.dtype != torch.float32 for t in (enc, E, start, rnn_p, W, bias)):
@@ -368,27 +368,39 @@ def _s2s_decode_operands(who, params, enc, key_len, keyvalue, beam, beam_token, 
         raise _lib.W2LInvalidArgument(f"{who}: key_len must hold B lengths")
     d = _lib.S2sDecodeDesc(B, T, H, N, Cc, int(eos), int(beam), int(beam_token), int(max_len), int(nbest),
                            float("inf") if threshold is None else float(threshold), float(eos_score), float(temperature),
-                           -1 if attention_threshold is None else int(attention_threshold), 0.0)
+                           -1 if attention_threshold is None else int(attention_threshold), float(lm_weight))
     k = enc.data_ptr()
     return d, kl, (E, start, rnn_p, W, bias, enc), [_p(E), _p(start), _p(rnn_p), _p(W), _p(bias), k, k + 4 * H * int(keyvalue), kl.ctypes.data]
 
 
 def s2s_decode(params, enc, key_len=None, keyvalue=False, *, eos, beam=1, beam_token=None, threshold=None, eos_score=0.0,
-               attention_threshold=None, temperature=1.0, max_len=120, nbest=1):
+               attention_threshold=None, temperature=1.0, max_len=120, nbest=1, lm=None, lm_weight=0.0):
     """token beam search over the step-by-step decoder of a seq2seq model (w2l_s2s_decode).  params: the embedding
     [N][H], the start embedding [H], the GRU's flat parameter, the output weight [H][N] and bias [N]; enc [B][T][C] as
     ops.s2s_attention, key_len [B] on the host (None: T).  beam_token None: min(N, 64).  threshold None: no beam threshold;
     attention_threshold None: off.  -> (tokens [B][nbest][max_len] int32, -1 behind the end; lengths [B][nbest]; scores
-    [B][nbest]) on the device; a hypothesis that does not exist has length 0 and score -inf.  beam 1 is greedy decoding."""
-    beam_token = min(params[0].shape[0], 64) if beam_token is None else beam_token
+    [B][nbest]) on the device; a hypothesis that does not exist has length 0 and score -inf.  beam 1 is greedy decoding.
+    lm: an NGramLM over the N classes, fused into the search with lm_weight (w2l_s2s_decode_lm); a fourth result is then
+    lm_scores [B][nbest], the hypotheses' unweighted LM scores."""
+    N = params[0].shape[0]
+    beam_token = min(N, 64) if beam_token is None else beam_token
+    if lm is None and lm_weight:
+        raise _lib.W2LInvalidArgument("s2s_decode: LM fusion (lm_weight) needs lm=")
+    if lm is not None and lm.num_tokens != N:
+        raise _lib.W2LInvalidArgument(f"s2s_decode: the LM has {lm.num_tokens} tokens, the model {N} classes")
     d, kl, keep, ptrs = _s2s_decode_operands("s2s_decode", params, enc, key_len, keyvalue, beam, beam_token, max_len, nbest, eos, threshold,
-                                             eos_score, attention_threshold, temperature)
+                                             eos_score, attention_threshold, temperature, lm_weight)
     L, dev = _lib.lib(), enc.device
-    nbytes = L.w2l_s2s_decode_workspace_size(C.byref(d))
+    nbytes = (L.w2l_s2s_decode_workspace_size if lm is None else L.w2l_s2s_decode_lm_workspace_size)(C.byref(d))
     ws = _ws(nbytes, dev)
     tokens = torch.empty(d.B, max(d.nbest, 1), max(d.maxLen, 1), device=dev, dtype=torch.int32)
     lengths = torch.empty(d.B, max(d.nbest, 1), device=dev, dtype=torch.int32)
     scores = torch.empty(d.B, max(d.nbest, 1), device=dev, dtype=torch.float32)
+    if lm is not None:
+        lm_scores, blob = torch.empty_like(scores), lm.device_blob(dev)
+        check(L.w2l_s2s_decode_lm(C.byref(d), *ptrs, _p(tokens), _p(lengths), _p(scores), _p(lm_scores), _p(ws), nbytes, _s(), _p(blob),
+                                  int(lm.has_eos)), "s2s_decode")
+        return tokens, lengths, scores, lm_scores
     check(L.w2l_s2s_decode(C.byref(d), *ptrs, _p(tokens), _p(lengths), _p(scores), _p(ws), nbytes, _s()), "s2s_decode")
     return tokens, lengths, scores
 

@@ -133,27 +133,32 @@ class Seq2SeqCriterion(SequenceCriterion):
 
     @torch.no_grad()
     def beamSearch(self, enc, inputSizes=None, beam=1, beam_token=None, threshold=None, eos_score=0.0, attention_threshold=None,
-                   temperature=1.0, max_len=120, nbest=1, **refused):
-        """token beam search over the step-by-step decoder (ops.s2s_decode; the reference's LexiconFreeSeq2SeqDecoder with a zero LM,
-        DESIGN.md 3.35) -> (tokens [B][nbest][max_len], -1 behind the end and eos included when reached; lengths [B][nbest]; scores
-        [B][nbest]).  beam_token None: min(nClass, 64); threshold None: no beam threshold; attention_threshold None: off.  The
+                   temperature=1.0, max_len=120, nbest=1, lm=None, **refused):
+        """token beam search over the step-by-step decoder (ops.s2s_decode; the reference's LexiconFreeSeq2SeqDecoder)
+        -> (tokens [B][nbest][max_len], -1 behind the end and eos included when reached; lengths [B][nbest]; scores [B][nbest]).
+        lm=<NGramLM over the nClass classes>, lm_weight= (or lmweight=): the n-gram LM fused into the search; a
+        fourth value is then the hypotheses' unweighted LM scores [B][nbest].
+        beam_token None: min(nClass, 64); threshold None: no beam threshold; attention_threshold None: off.  The
         decoder applies NO window: the recipe's softPretrain window is a pre-training device, and its centre u keyLen / tgtLen has no
-        meaning without a target.  Refused by name: LM fusion, hard and soft selection."""
+        meaning without a target.  Refused by name: LM fusion without lm=, hard and soft selection."""
         refuse = _lib.W2LInvalidArgument
-        names = {"lm_weight": "LM fusion (lm_weight) is not built", "lmweight": "LM fusion (lmweight) is not built",
+        names = {"lm_weight": "LM fusion (lm_weight) needs lm=", "lmweight": "LM fusion (lmweight) needs lm=",
                  "hardselection": "hardselection is not built", "softselection": "softselection is not built",
                  "hard_selection": "hardselection is not built", "soft_selection": "softselection is not built"}
         for k, v in refused.items():
             if k not in names:
                 raise TypeError(f"Seq2SeqCriterion.beamSearch: unknown option '{k}'")
-            if k in ("lm_weight", "lmweight") and not v:
+            if k in ("lm_weight", "lmweight") and (lm is not None or not v):
                 continue
             raise refuse(f"Seq2SeqCriterion.beamSearch: {names[k]}")
+        if lm is not None and lm.num_tokens != self.nClass:
+            raise refuse(f"Seq2SeqCriterion.beamSearch: the LM has {lm.num_tokens} tokens, nClass is {self.nClass}")
+        lm_weight = float(refused.get("lm_weight", refused.get("lmweight", 0.0)))
         _check_dev(enc)
         params = [p.detach() for p in (self.embedding, self.start, self.rnn, self.linear_weight, self.linear_bias)]
         return ops.s2s_decode(params, enc, self._key_len(enc, inputSizes), self.attention == "keyvalue", eos=self.eos, beam=beam,
                               beam_token=beam_token, threshold=threshold, eos_score=eos_score, attention_threshold=attention_threshold,
-                              temperature=temperature, max_len=max_len, nbest=nbest)
+                              temperature=temperature, max_len=max_len, nbest=nbest, lm=lm, lm_weight=lm_weight)
 
     def viterbiPath(self, enc, inputSizes=None, max_len=120):
         """greedy step-by-step decoding, the beam-1 case of beamSearch -> tokens [B][max_len] int32, -1 behind the end"""
