@@ -905,6 +905,37 @@ size_t w2l_s2s_decode_lm_workspace_size(const w2l_s2s_decode_desc* d);
 int w2l_s2s_decode_lm(const w2l_s2s_decode_desc* d, const float* E, const float* start, const float* rnn, const float* W,
                       const float* bias, const float* k, const float* v, const int* keyLen, int* tokens, int* lengths, float* scores,
                       float* lmScores, void* workspace, size_t workspaceBytes, w2l_stream_t stream, const void* lm, int lmHasEos);
+/* Fused causal multi-head self-attention with a relative-position term, fp32 (attention_causal.hip, DESIGN 3.37 is the contract): the
+ * self-attention of the Transformer decoder criterion (wav2letter_amd/transformer_criterion.py).  For b < B, head h < Hd, i, j < U, with
+ * head h in columns h d .. (h + 1) d of rows of stride ld (q, k, v may be the thirds of one interleaved [B][U][3 Hd d] buffer):
+ *   s[i][j] = scale (q_i . k_j + q_i . E[j - i + n0])   for j <= i;  -inf for j > i
+ *   P = softmax_j s,  Pd = dropout(P),  ctx_i = sum_j Pd[i][j] v_j
+ * E: the [2 n0 + 1][d] position table shared by all heads (dense), or NULL; rows outside the table count as 0.  len: a HOST int32 [B],
+ * values 1..U, checked and copied before the first launch.  Rows i >= len[b] write ctx and lse exactly +0.0f, and give and receive no
+ * gradient (dq, dk, dv rows >= len[b] are +0.0f); nothing is read of the rows >= len[b] of q, k, v and dctx, which may hold anything.
+ * The rows below len[b] must be finite: a masked probability is a 0 that still multiplies v_j in the tile's product.  Dropout: the mask of w2l_dropout_copy over a dense [B][Hd][U][U] array with the same
+ * (dropP, dropSeed, dropStream); P is never written to memory.  forward writes ctx [B][U][ldc] (head h in columns h d ..) and lse
+ * [B][Hd][U].  backward takes the operands, forward's lse and dctx [B][U][ldc]; it recomputes the score tiles and writes dq,
+ * dk, dv (stride ld, all U rows) and, when E is given, the whole of dE [2 n0 + 1][d] (0 in the rows no pair reaches).  No atomics, one
+ * order for every sum: two calls give the same bits, and what an utterance receives does not depend on B.
+ * workspace: w2l_attn_causal_workspace_size(d, 0) bytes for forward, (d, 1) for backward; contents mean nothing between calls.
+ * W2L_EINVAL: null pointers (but E, and dE when E is NULL), sizes below 1, n0 < 0, ld or ldc below Hd d, dropP outside [0, 1), a NaN
+ * scale, a len outside 1..U, a small workspace.  W2L_EUNSUPPORTED: d not a multiple of 32 or above 256, Hd d above 1024, U above 512, B
+ * above 1024, ld or ldc not a multiple of 4, a pointer that is not 16-byte aligned.  All checks precede the first launch. */
+typedef struct {
+  int B, Hd, U, d;
+  int ld, ldc;        /* floats between two rows of q, k, v, dq, dk, dv; of ctx, dctx */
+  int n0;             /* E has 2 n0 + 1 rows; row n0 is distance 0 */
+  float scale;
+  double dropP;
+  uint32_t dropSeed, dropStream;
+} w2l_attn_causal_desc;
+size_t w2l_attn_causal_workspace_size(const w2l_attn_causal_desc* d, int backward);
+int w2l_attn_causal_forward(const w2l_attn_causal_desc* d, const float* q, const float* k, const float* v, const float* E, const int* len,
+                            float* ctx, float* lse, void* workspace, size_t workspaceBytes, w2l_stream_t stream);
+int w2l_attn_causal_backward(const w2l_attn_causal_desc* d, const float* q, const float* k, const float* v, const float* E, const int* len,
+                             const float* lse, const float* dctx, float* dq, float* dk, float* dv, float* dE,
+                             void* workspace, size_t workspaceBytes, w2l_stream_t stream);
 /* The kw x 1 convolutions over the mel rows of the TDS recipes in the mixed-precision mode (bf16 operand storage, see
  * w2l_gemm_bf16) -- fl::TDSBlock's time convolution (C -> C channels, stride 1) and the sub-sampling `C2 cin cout kw 1 s 1`
  * lines between the blocks (cin != cout <= 32 channels, stride 1 or 2, any padding): x / dy and the weights rounded to bf16,

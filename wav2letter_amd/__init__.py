@@ -10,5 +10,6 @@ from . import cpc  # noqa: F401  (which frames the CPC criterion masks, which ne
 from .criterion import (ASGLoss, CPCCriterion, CTCLoss, CriterionScaleMode, ForceAlignmentCriterion,  # noqa: F401
                         FullConnectionCriterion, LinSegCriterion, SequenceCriterion, getCriterionScaleMode, linear_target)
 from .seq2seq import Seq2SeqCriterion  # noqa: F401
+from .transformer_criterion import TransformerCriterion  # noqa: F401
 from .lexicon import Lexicon  # noqa: F401
 from .lm import NGramLM  # noqa: F401

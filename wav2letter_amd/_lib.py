@@ -250,6 +250,9 @@ class _SIGS:
     w2l_s2s_decode_step = (_i, [_p] * 19 + [_sz, _p])
     w2l_s2s_decode_lm_workspace_size = (_sz, [_p])
     w2l_s2s_decode_lm = (_i, [_p] * 14 + [_sz, _p, _p, _i])
+    w2l_attn_causal_workspace_size = (_sz, [_p, _i])
+    w2l_attn_causal_forward = (_i, [_p] * 9 + [_sz, _p])
+    w2l_attn_causal_backward = (_i, [_p] * 13 + [_sz, _p])
     w2l_swish_forward = (_i, [_p, _p, _sz, _f, _p])
     w2l_swish_backward = (_i, [_p, _p, _p, _sz, _f, _p])
     w2l_layernorm_scratch_doubles = (_sz, [_i, _sz])
@@ -372,6 +375,11 @@ class RnnDesc(C.Structure):  # w2l_rnn_desc; mode: 0 ReLU, 1 tanh, 2 LSTM, 3 GRU
 
 class S2sAttnDesc(C.Structure):  # w2l_s2s_attn_desc
     _fields_ = [(n, C.c_int) for n in ("B", "U", "T", "H", "ldenc")] + [("windowStd", C.c_float), ("addQuery", C.c_int)]
+
+
+class AttnCausalDesc(C.Structure):  # w2l_attn_causal_desc
+    _fields_ = ([(n, C.c_int) for n in ("B", "Hd", "U", "d", "ld", "ldc", "n0")] +
+                [("scale", C.c_float), ("dropP", C.c_double), ("dropSeed", C.c_uint32), ("dropStream", C.c_uint32)])
 
 
 class S2sDecodeDesc(C.Structure):  # w2l_s2s_decode_desc

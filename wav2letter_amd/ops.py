@@ -351,6 +351,64 @@ def embedding(tokens, E, start):
     return _Embedding.apply(E, start, tokens.reshape(-1)).view(*tokens.shape, E.shape[1])
 
 
+class _AttnCausal(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, E, length, n_heads, n0, scale, p, seed, stream_id):
+        if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape or any(t.dtype != torch.float32 for t in (q, k, v)):
+            raise _lib.W2LInvalidArgument("attn_causal: q, k, v must be float32 [B][U][C]")
+        B, U, Cc = q.shape
+        if n_heads < 1 or Cc % n_heads:
+            raise _lib.W2LInvalidArgument(f"attn_causal: C = {Cc} is no multiple of n_heads = {n_heads}")
+        row = lambda t: t.stride(2) == 1 and t.stride(0) == U * t.stride(1) and t.stride(1) % 4 == 0 and t.data_ptr() % 16 == 0
+        if not (row(q) and row(k) and row(v) and q.stride(1) == k.stride(1) == v.stride(1)):   # else: thirds of one buffer, read in place
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        if E is not None:
+            E = E.contiguous()
+            if E.dtype != torch.float32 or E.shape != (2 * n0 + 1, Cc // n_heads):
+                raise _lib.W2LInvalidArgument(f"attn_causal: E must be float32 [2 n0 + 1 = {2 * n0 + 1}][d = {Cc // n_heads}]")
+        ln = _host_i32(length)
+        if ln.shape != (B,):
+            raise _lib.W2LInvalidArgument("attn_causal: len must hold B lengths")
+        d = _lib.AttnCausalDesc(B, n_heads, U, Cc // n_heads, q.stride(1), Cc, int(n0), float(scale), float(p), int(seed), int(stream_id))
+        L = _lib.lib()
+        out = torch.empty(B, U, Cc, device=q.device, dtype=torch.float32)
+        lse = torch.empty(B, n_heads, U, device=q.device, dtype=torch.float32)
+        nbytes = L.w2l_attn_causal_workspace_size(C.byref(d), 0)
+        ws = _ws(nbytes, q.device)
+        check(L.w2l_attn_causal_forward(C.byref(d), _p(q), _p(k), _p(v), _p(E), ln.ctypes.data, _p(out), _p(lse), _p(ws), nbytes, _s()),
+              "attn_causal_forward")
+        ctx.d, ctx.ln, ctx.has_E = d, ln, E is not None
+        ctx.save_for_backward(q, k, v, E, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, E, lse = ctx.saved_tensors
+        d, L = ctx.d, _lib.lib()
+        B, U, Cc = dout.shape
+        dout = dout.contiguous()
+        # the gradients have the operands' row stride: thirds of one [B][U][3 C] buffer for an interleaved q | k | v, else three arrays
+        if d.ld == 3 * Cc:
+            g = torch.empty(B, U, 3 * Cc, device=dout.device, dtype=torch.float32)
+            dq, dk, dv = g[..., :Cc], g[..., Cc:2 * Cc], g[..., 2 * Cc:]
+        else:
+            dq, dk, dv = (torch.empty(B, U, d.ld, device=dout.device, dtype=torch.float32)[..., :Cc] for _ in range(3))
+        dE = torch.empty_like(E) if ctx.has_E else None
+        nbytes = L.w2l_attn_causal_workspace_size(C.byref(d), 1)
+        ws = _ws(nbytes, dout.device)
+        check(L.w2l_attn_causal_backward(C.byref(d), _p(q), _p(k), _p(v), _p(E), ctx.ln.ctypes.data, _p(lse), _p(dout),
+                                         _p(dq), _p(dk), _p(dv), _p(dE), _p(ws), nbytes, _s()), "attn_causal_backward")
+        return dq, dk, dv, dE, None, None, None, None, None, None, None
+
+
+def attn_causal(q, k, v, E, len, n_heads, n0, scale, p=0.0, seed=0, stream_id=0):
+    """fused causal multi-head self-attention with a relative-position term (w2l_attn_causal_*): q, k, v [B][U][C] -- the
+    thirds of one [B][U][3 C] buffer are read in place --, head h in columns h d .., E [2 n0 + 1][d] or None, len [B] on the host ->
+    ctx [B][U][C] = dropout(softmax_j<=i(scale (q_i . k_j + q_i . E[j - i + n0]))) v, exactly 0 in the rows i >= len[b].  The dropout
+    mask is ops.dropout_copy's over a dense [B][n_heads][U][U] array with the same (p, seed, stream_id).  Differentiable in q, k, v, E."""
+    return _AttnCausal.apply(q, k, v, E, len, int(n_heads), int(n0), float(scale), float(p), int(seed), int(stream_id))
+
+
 def _s2s_decode_operands(who, params, enc, key_len, keyvalue, beam, beam_token, max_len, nbest, eos, threshold, eos_score, attention_threshold,
                          temperature, lm_weight=0.0):
     """the checks that need no device, the descriptor and the operand pointers of the two decode calls"""
